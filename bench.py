@@ -8,7 +8,11 @@ configs[2], the largest single-GPU configuration: 8 IFs x 32 MHz, 2-bit dual-pol
 full-Stokes IQUV on one GPU (per IF the digifil flags `-c -b8 -d4 -F1024:2048`,
 process_vdif.py:157-171), all IFs into ONE row buffer through frbch_scan_device.  With N GPUs every
 rank owns its own 8 IFs (the path shards by IF, base2fil.sh:60-66: no collective on the data path)
--> weak scaling.  The other BASELINE configurations ride in the same line under "configs".
+-> weak scaling.  With --full the other BASELINE configurations ride in the same line under "configs".
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps, writes the last step's outputs
+if --dump-outputs DIR is given, and prints the line; everything that takes runs of its own (the live PMC passes behind
+roofline.traffic, the steady state, host_inclusive, configs, cpu_baseline) runs only with --full and is null otherwise.
 
 Prints ONE JSON line on rank 0 (contract in the task statement), including
   "roofline":       the SURVEY 8(d) figure.  `achieved` / `frac` = WHOLE PATH: value x the 8(d) budget bytes per sample
@@ -170,6 +174,11 @@ def build_parser():
     ap.add_argument("--freq-res", type=int, default=None)
     ap.add_argument("--maxb", type=int, default=0, help="filterbank blocks per kernel launch (0 = library default)")
     ap.add_argument("--overlap", type=int, default=0, help="frbch_config.overlap: front-lane CUs | batches << 16 (0 = automatic, 1 = no overlap)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: live PMC traffic passes, steady state, host-inclusive legs, the "
+                         "other BASELINE configurations, CPU baseline (each can still be dropped with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed to DIR/<name>.npy (float32 / float64, 64 MB at most)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-host", action="store_true", help="skip the host-inclusive (frbch_run_file / frbch_run_scan) leg")
@@ -458,6 +467,43 @@ class Workload:
                 f"frames and rows resident in HBM")
 
 
+DUMP_BYTES = 64 * 10 ** 6   # all files of --dump-outputs together (64 MB)
+DUMP_SEED = 0xF4B0        # which rows the sample holds: fixed, so that two builds are compared row for row
+
+
+def dump_outputs(wl, out_dir, rank=0, world=1):
+    """What the last timed step handed its caller (frbch_scan_device: the row buffer, the rows written, every IF's rescale
+    state), as .npy files in DIR (with N ranks each writes its own, suffix _rank<r>, 64 MB / N at most):
+      rows_written      the call's return value (float64, one element)
+      row_sample        a fixed seeded sample of the rows [row][product][IF-major channel], the 8-bit codes as float32
+      row_sample_index  the row numbers of that sample (float64, ascending)
+      column_sum        every column of the row buffer summed over ALL rows (exact integers, float64)
+      rescale_offset, rescale_scale   frbch_get_rescale of every IF, splice order (float32 [IF][nif][nchan])"""
+    import numpy as np
+    torch = wl.torch
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    rows, pitch = wl.rows, wl.row_pitch
+    torch.cuda.synchronize()
+    buf = wl.out[: rows * pitch].view(rows, pitch)
+    col = torch.zeros(pitch, dtype=torch.int64, device=buf.device)
+    for r0 in range(0, rows, 8192):
+        col += buf[r0:r0 + 8192].to(torch.int32).sum(0)
+    resc = [c.get_rescale() for c in wl.chans]
+    arrays = {"rows_written": np.array([rows], dtype=np.float64),
+              "column_sum": col.double().cpu().numpy(),
+              "rescale_offset": np.stack([o for o, _ in resc]).astype(np.float32),
+              "rescale_scale": np.stack([s for _, s in resc]).astype(np.float32)}
+    room = DUMP_BYTES // world - 4096 - sum(a.nbytes for a in arrays.values())     # (4 KB: the .npy headers)
+    nsample = int(min(rows, max(1, room // (4 * pitch + 8))))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, nsample, replace=False))
+    arrays["row_sample_index"] = idx.astype(np.float64)
+    arrays["row_sample"] = buf[torch.from_numpy(idx).to(buf.device)].float().cpu().numpy()
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BYTES // world
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+
+
 def budget_share_bytes_per_sample(name, spec):
     """a kernel's share of the SURVEY 8(d) budget, bytes per dual-pol sample: the compulsory input and the spill write belong to
     K1, the spill read and the output codes to K2 (the coherent path spills twice: K2c reads and writes, K3 reads, K4 emits);
@@ -696,7 +742,10 @@ def host_inclusive(args, torch, dist, wl, rank, world):
 
 
 def main():
-    args = build_parser().parse_args()
+    ap = build_parser()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     argv = sys.argv[1:]
     world_env = os.environ.get("WORLD_SIZE")
     if args.gpus > 1 and world_env is None:
@@ -707,6 +756,8 @@ def main():
     if args.backend is None:
         args.backend = "gloo" if args.share_gpu else "nccl"
     spec = workload_spec(args)
+    if not args.full:     # a plain run: only what the headline figure needs
+        args.no_cpu = args.no_host = args.no_traffic = args.no_configs = args.no_steady = True
 
     # live PMC passes first: the children must start before this process initialises the GPU
     live_traffic = None
@@ -744,7 +795,9 @@ def main():
     if args.pmc_child:
         wl.close()
         return
-    steady = wl.steady_state(args.steps) if not args.no_steady else 0.0
+    if args.dump_outputs:      # before anything else reuses the row buffer
+        dump_outputs(wl, args.dump_outputs, rank, world)
+    steady = wl.steady_state(args.steps) if not args.no_steady else None
     samples_per_step, nblocks, nif = wl.samples_per_step, wl.nblocks, spec["nif"]
     workload_text = wl.describe(world)
     host = None
@@ -824,7 +877,7 @@ def main():
                 "kernel_budget_bytes_per_launch": share * samples_timed / max(1, rec["launches"]),
                 "kernel_model_frac": round(model / HBM_PEAK_GBS, 5),     # the engine's own byte model of that kernel (float rows of a buffered interval included)
                 "kernel_traffic_per_launch": (live_traffic or {}).get(name),
-                "steady_state_frac": round(steady * 1e6 * bps / 1e9 / HBM_PEAK_GBS, 5),
+                "steady_state_frac": round(steady * 1e6 * bps / 1e9 / HBM_PEAK_GBS, 5) if steady is not None else None,
                 "valu_frac": (valu or {}).get("frac"),
                 "dominance_rule": "largest summed launch time (HIP events on the launch streams), no exclusions",
                 "concurrency": concurrency_note(timing, args.steps, dt),
@@ -843,7 +896,7 @@ def main():
             "config": {"workload": workload_text, "baseline_config": args.workload,
                        "samples_per_step_per_gpu": samples_per_step, "blocks_per_step_per_if": nblocks, "ifs_per_gpu": nif,
                        "realtime_x": round(value / world / (2 * spec["bw"] * nif), 2),
-                       "steady_state_msamples_per_gpu": round(steady, 1),
+                       "steady_state_msamples_per_gpu": round(steady, 1) if steady is not None else None,
                        "per_rank_seconds": per_rank},
             "roofline": roof,
             "host_inclusive": host,

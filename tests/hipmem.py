@@ -16,6 +16,17 @@ def hip():
     return _hip
 
 
+def gpu_visible() -> bool:
+    """torch.cuda.is_available(), asked in a child process.  torch brings its own HIP runtime; initialised in the test
+    process before the product library's (the system one, loaded first), it leaves the library seeing no device."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.is_available())"], capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stderr
+    return r.stdout.split()[-1] == "True"
+
+
 class DeviceBuffer:
     def __init__(self, nbytes: int):
         self.ptr = C.c_void_p()

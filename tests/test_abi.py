@@ -47,8 +47,8 @@ def test_shim_exists_and_rejects_bad_args():
 
 
 def test_no_cpu_fallback():
-    import torch
-    if torch.cuda.is_available():
+    from tests.hipmem import gpu_visible
+    if gpu_visible():
         pytest.skip("GPU present")
     with pytest.raises(ch.RunError) as ei:
         ch.Channeliser(ch.new_config())

@@ -179,8 +179,8 @@ def test_bench_launcher_starts_ranks_without_touching_the_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "1", "--warmup", "0",
                         "--no-cpu", "--no-host", "--seconds", "0.2"], env=env, capture_output=True, text=True, timeout=600)
-    import torch
-    if torch.cuda.is_available():
+    from tests.hipmem import gpu_visible
+    if gpu_visible():
         line = json.loads(r.stdout.strip().splitlines()[-1])
         assert r.returncode == 0 and line["n_gpus"] == 2 and len(line["config"]["per_rank_seconds"]) == 2
     else:
@@ -295,3 +295,51 @@ def test_bench_roofline_follows_survey_8d():
     assert bench.kernels_overlap(timing, 1, 0.030) and not bench.kernels_overlap(timing, 1, 0.0385)
     total, missing = bench.step_traffic({"frbch_k1_wave<3,8,1>": 5.4e9, "frbch_k0_stage": 0.6e9}, timing, 1)
     assert abs(total - 8 * 6.0e9) < 1 and missing == ["frbch_k2_wave<3,4,4,2>"]
+
+
+def test_bench_options_and_output_dump(tmp_path, monkeypatch):
+    """bench.py: the extras are off unless --full; --dump-outputs writes the last step's row buffer as float .npy files within
+    the size cap -- a fixed row sample, exact column sums over every row, the rows written and the rescale state -- and the
+    same files on every call"""
+    import sys
+    import types
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    try:
+        import bench
+    finally:
+        sys.path.remove(root)
+    args = bench.build_parser().parse_args(["--steps", "3"])
+    assert not args.full and args.dump_outputs is None and args.steps == 3
+    assert bench.build_parser().parse_args(["--full", "--dump-outputs", "d"]).full
+
+    class Chan:
+        def __init__(self, i):
+            self.i = i
+
+        def get_rescale(self):
+            return np.full((4, 64), self.i, np.float32), np.full((4, 64), 2.0 * self.i, np.float32)
+
+    rows, pitch = 20000, 512
+    gen = torch.Generator().manual_seed(7)
+    wl = types.SimpleNamespace(torch=torch, rows=rows, row_pitch=pitch, chans=[Chan(i) for i in range(2)],
+                               out=torch.randint(0, 256, (rows * pitch,), dtype=torch.uint8, generator=gen))
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8 << 20)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    dirs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    for d in dirs:
+        bench.dump_outputs(wl, d)
+    names = sorted(os.listdir(dirs[0]))
+    assert names == ["column_sum.npy", "rescale_offset.npy", "rescale_scale.npy", "row_sample.npy", "row_sample_index.npy",
+                     "rows_written.npy"]
+    assert sum(os.path.getsize(os.path.join(dirs[0], n)) for n in names) <= 8 << 20
+    got = {n[:-4]: np.load(os.path.join(dirs[0], n)) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    buf = wl.out.view(rows, pitch)
+    idx = got["row_sample_index"].astype(np.int64)
+    assert 0 < idx.size < rows and np.all(np.diff(idx) > 0)
+    assert np.array_equal(got["row_sample"], buf[torch.from_numpy(idx)].numpy().astype(np.float32))
+    assert np.array_equal(got["column_sum"], buf.to(torch.int64).sum(0).numpy().astype(np.float64))
+    assert got["rows_written"].tolist() == [rows] and got["rescale_scale"].shape == (2, 4, 64)
+    assert all(np.array_equal(got[n[:-4]], np.load(os.path.join(dirs[1], n))) for n in names)

@@ -4,7 +4,7 @@
 tag=$1; wl=$2; vals=$3; shift 3
 mkdir -p gpurun_out/$tag
 for v in $vals; do
-  timeout -k 10 240 python3 bench.py --workload $wl --no-cpu --no-host --no-traffic --no-configs --steps 8 --warmup 3 --overlap $v "$@" \
+  timeout -k 10 240 python3 bench.py --full --workload $wl --no-cpu --no-host --no-traffic --no-configs --steps 8 --warmup 3 --overlap $v "$@" \
     > gpurun_out/$tag/${wl}_$v.json 2> gpurun_out/$tag/${wl}_$v.err || { echo "$wl overlap=$v FAILED"; tail -3 gpurun_out/$tag/${wl}_$v.err; continue; }
   python3 - "$wl" "$v" gpurun_out/$tag/${wl}_$v.json <<'PY'
 import json, sys

@@ -1,11 +1,11 @@
 #!/bin/bash
-# Round artifacts (run on the GPU box): the default bench line (with its own live PMC traffic passes, the host-inclusive legs and
+# Round artifacts (run on an MI355X): the full bench line (--full: its own live PMC traffic passes, the host-inclusive legs and
 # the other configurations), rocprofv3 kernel stats of the same workload, per-kernel HBM traffic from separate PMC passes.
 tag=${1:-r04_final}
-cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
+export TMPDIR=/tmp && cd "$(dirname "$0")/.."
 out=gpurun_out/$tag
 mkdir -p $out
-timeout -k 10 700 python3 bench.py > $out/bench.json 2> $out/bench.err
+timeout -k 10 700 python3 bench.py --full > $out/bench.json 2> $out/bench.err
 echo "bench done rc=$?"
 plain="--no-cpu --no-host --no-traffic --no-configs --no-steady"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py $plain > $out/trace_bench.json 2> $out/trace.err
