@@ -9,7 +9,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# FRBCH_LIB: another build of the same library for this process (the profiling build `make exp`); default: the product
+# FRBCH_LIB: another build of the same library for this process (an A/B run against another commit, tools/ab.sh); default: the product
 LIB_PATH = os.environ.get("FRBCH_LIB") or os.path.join(_HERE, "csrc", "libfrbch.so")
 
 ABI_VERSION = 5

@@ -29,11 +29,7 @@ void mark_user_stream(frbch_handle* h, dev_stream_t s) {
 }  // namespace frbchi
 using namespace frbchi;
 
-#ifdef FRBCH_EXPERIMENTS
-extern "C" const char* frbch_version(void) { return "frbch abi 5 backend " FRBCH_BACKEND_NAME " +experiments"; }
-#else
 extern "C" const char* frbch_version(void) { return "frbch abi 5 backend " FRBCH_BACKEND_NAME; }
-#endif
 
 extern "C" int frbch_open(const frbch_config* cfg, frbch_handle** out) {
   if (!cfg || !out) return FRBCH_E_ARG;
@@ -47,12 +43,12 @@ extern "C" int frbch_open(const frbch_config* cfg, frbch_handle** out) {
   if (ndev <= 0) return fail(h, FRBCH_E_DEVICE, "no GPU visible to HIP (there is no CPU fallback)");
   if (cfg->device >= ndev) return fail(h, FRBCH_E_DEVICE, "device ordinal out of range");
   if (cfg->flags & ~kAcceptedFlags)
-    return fail(h, FRBCH_E_ARG, "unknown bit in cfg.flags (kernel variants kept for A/B runs and timing-only ablations exist only in FRBCH_EXPERIMENTS builds)");
+    return fail(h, FRBCH_E_ARG, "unknown bit in cfg.flags (include/frbch.h lists the four switches)");
   if ((cfg->flags & kFlagBuffered) && (cfg->flags & kFlagTwoPass)) return fail(h, FRBCH_E_ARG, "cfg.flags asks for the buffered AND the two-pass rescale");
-  if (!kExperiments) {   // overlap: automatic (0), off (1), or the plain-stream mode 3 with a CU count; no CU-masked lanes, no forced batching
+  {   // overlap: automatic (0), off (1), or mode 3 (the digitiser beside the next K1 on plain streams) with a CU count
     const uint32_t mode = (cfg->overlap >> 24) & 0xFFu, batches = (cfg->overlap >> 16) & 0xFFu;
     if ((mode != 0 && mode != 3) || batches)
-      return fail(h, FRBCH_E_ARG, "cfg.overlap: CU-masked lane modes and forced batching exist only in FRBCH_EXPERIMENTS builds");
+      return fail(h, FRBCH_E_ARG, "cfg.overlap: only mode 3 (or 0) and no batch count are accepted (include/frbch.h)");
   }
   h->device = cfg->device;
   DeviceGuard dg(h->device);
@@ -77,8 +73,8 @@ extern "C" int frbch_open(const frbch_config* cfg, frbch_handle** out) {
   {
     char nm[64];
     if (pl.fast_k1_log2m && pl.fast_k1_wave) {
-      const int nw = pl.fast_k1_kind == 1 ? 4 : (pl.fast_k1_kind == 3 ? 16 : 8), wps = pl.fast_k1_kind == 5 ? 4 : (pl.fast_k1_kind >= 2 ? 2 : 1);   // kind 4: <4,8,2>, kind 5: <5,8,4>
-      snprintf(nm, sizeof nm, "frbch_k1_wave<%d,%d,%d>", pl.fast_k1_log2m, nw, wps);
+      const int wps = pl.fast_k1_log2m == 5 ? 4 : (pl.fast_k1_log2m == 4 ? 2 : 1);   // <5,8,4>, <4,8,2>, else <M,8,1>
+      snprintf(nm, sizeof nm, "frbch_k1_wave<%d,8,%d>", pl.fast_k1_log2m, wps);
       h->kname[KID_K1] = nm;
     } else if (pl.fast_k1_log2m) {
       snprintf(nm, sizeof nm, "frbch_k1_fast<%d>", pl.fast_k1_log2m);
@@ -88,7 +84,7 @@ extern "C" int frbch_open(const frbch_config* cfg, frbch_handle** out) {
       snprintf(nm, sizeof nm, "frbch_kc_fast<%d>", pl.fast_k2_log2m);
       h->kname[KID_KC] = nm;
       if (pl.fast_k2_wave) {
-        const bool two = (pl.fast_k2_log2m == 4) || (pl.fast_k2_log2m == 3 && !(h->cfg.flags & 32u) && pl.fast_k2_nw != 8);
+        const bool two = (pl.fast_k2_log2m == 4) || (pl.fast_k2_log2m == 3 && pl.fast_k2_nw != 8);
         const int nw = two ? (pl.fast_k2_nw == 2 ? 4 : 8) : pl.fast_k2_nw;
         const int pm = h->cfg.pol_mode == 2 ? 2 : (h->cfg.pol_mode >= 4 ? 4 : 0);
         if (pl.fast_k2_log2m == 5) snprintf(nm, sizeof nm, "frbch_k2_wave<5,8,%d,4>", pm);
@@ -131,7 +127,7 @@ extern "C" int frbch_open(const frbch_config* cfg, frbch_handle** out) {
     if ((rc = build_chirp(h, pl.coh_fast_r ? (1 << pl.coh_fast_r) : 0))) return rc;
     h->kname[KID_K2] = pl.coh_fast_c ? "frbch_k2c_fast" : "frbch_k2c_chirp";
     if (pl.ncol % 64 == 0 && pl.rows_per_block % 2 == 0 && pl.c % 4 == 0 && !(h->cfg.flags & 2u)) h->kname[KID_K4] = "frbch_k4_fast";
-    if (pl.coh_fast_r) h->kname[KID_K3] = (pl.coh_fast_r == 4 && pl.coh_nt == 512 && !(h->cfg.flags & 8u)) ? "frbch_k3_wave<4>" : "frbch_k3_fast";
+    if (pl.coh_fast_r) h->kname[KID_K3] = (pl.coh_fast_r == 4 && pl.coh_nt == 512) ? "frbch_k3_wave<4>" : "frbch_k3_fast";
   }
   if (pl.dls_lg_ns) {
     const std::vector<float> tab = dls_table(1u << pl.dls_lg_ns, h->cfg.dls_cutoff_sigma, h->cfg.dls_threshold);
@@ -158,7 +154,6 @@ extern "C" void frbch_close(frbch_handle* h) {
   if (h->stream) (void)dev_sync(h->stream);
   drain_events(h);
   dev_free(h->tw_r); dev_free(h->tw_c2); dev_free(h->tw_nhi); dev_free(h->tw_nlo);
-  dev_free(h->ftw1_h); dev_free(h->ftw2_h);
   dev_free(h->ftw1_r); dev_free(h->ftw2_r); dev_free(h->ftw1_c); dev_free(h->ftw2_c); dev_free(h->td1); dev_free(h->td2);
   dev_free(h->spill); dev_free(h->s_dc); dev_free(h->p0);
   dev_free(h->spill2); dev_free(h->chirp); dev_free(h->ptmp); dev_free(h->scr2);
@@ -170,7 +165,7 @@ extern "C" void frbch_close(frbch_handle* h) {
   if (h->user_ev_made) dev_event_destroy(h->user_ev);
   if (h->quant_ev_made) dev_event_destroy(h->quant_ev);
   if (h->reset_ev_made) dev_event_destroy(h->reset_ev);
-  if (h->region_ev_made) for (auto& e : h->region_ev) dev_event_destroy(e);
+  if (h->spill_ev_made) dev_event_destroy(h->spill_ev);
   for (auto& e : h->evpool) dev_event_destroy(e);
   delete h;
 }
@@ -323,12 +318,12 @@ extern "C" int frbch_scan_device(frbch_handle* const* ifs, uint32_t nif, const v
     if (!stream && h != h0) CHECK_DEV(h0, dev_sync(h->stream), "sync");   // (earlier work of this IF on its own stream)
     join_reset(h, s);
   }
-  // one chain over all IFs: the front stages of IF i + 1 overlap the back stages (and the flush) of IF i
-  Lanes* ln = overlap_usable(h0) ? get_lanes(h0->device, overlap_front_cus(h0), overlap_mode(h0) == 3) : nullptr;
+  // one chain over all IFs: the digitiser of a completed interval of IF i may run beside the K1 of IF i + 1
+  Lanes* ln = overlap_usable(h0) ? get_lanes(h0->device, overlap_front_cus(h0)) : nullptr;
   uint64_t stages = 0;
-  for (uint32_t i = 0; i < nif; ++i) stages += feed_stage_count(ifs[i], nblocks, ln != nullptr && overlap_mode(h0) == 1);
+  for (uint32_t i = 0; i < nif; ++i) stages += feed_stage_count(ifs[i], nblocks);
   Chain ch;
-  chain_begin(&ch, h0, s, ln, (uint32_t)stages, pl.nif < 4, overlap_mode(h0));
+  chain_begin(&ch, h0, s, ln, (uint32_t)stages);
   const size_t seg = pl.row_bytes / pl.nif;                     // bytes of one product line of one IF
   const uint64_t bits = pl.row_bytes * 8 / pl.ncol;
   uint64_t rows_min = UINT64_MAX;
@@ -342,10 +337,8 @@ extern "C" int frbch_scan_device(frbch_handle* const* ifs, uint32_t nif, const v
     if (nblocks) rc = engine_feed(h, (const uint8_t*)d_frames[i], frame_bytes, header_bytes, payload_byte_offset, nblocks, dst, cap, &r1, s,
                                   nullptr, 0, nullptr, &ch);
     if (!rc && flush) {
-      const dev_stream_t sb = (ch.ln && ch.backs) ? ch.s_back : s;
       const uint64_t used = r1 * out_row_span(h);
-      rc = engine_flush(h, dst + used, cap - (size_t)used, &r2, sb, &ch);
-      if (!rc && r2) chain_back_touch(&ch);
+      rc = engine_flush(h, dst + used, cap - (size_t)used, &r2, s, &ch);
     }
     h->out_pitch = 0;
     if (rc && h != h0) fail(h0, rc, std::string("IF ") + std::to_string(i) + ": " + h->err);
@@ -385,7 +378,7 @@ extern "C" int frbch_power_device(frbch_handle* h, const void* d_frames, size_t 
     p.header_bytes = header_bytes;
     p.payload_bytes = frame_bytes - header_bytes;
     p.payload_off = payload_byte_offset + b0 * pl.block_stride_bytes;
-    int rc = launch_front(h, p, nb, s, s);
+    int rc = launch_front(h, p, nb, s);
     if (rc) return rc;
     p.out_mode = FRBCH_OUT_FLOAT_POWER;
     p.power_out = d_power;

@@ -376,23 +376,8 @@ bool vdif_file_contiguous(int fd, const frbch_config& cfg) {
   return i1 - i0 == nfile - 1;
 }
 
-#ifdef FRBCH_EXPERIMENTS
-struct PhaseClock {   // FRBCH_TIMING=1: wall-clock phases of a whole-file call on stderr
-  bool on = getenv("FRBCH_TIMING") != nullptr;
-  double t0 = now();
-  static double now() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
-  void mark(const char* what) { if (on) { const double t = now(); fprintf(stderr, "[frbch timing] %-28s %8.2f ms\n", what, (t - t0) * 1e3); t0 = t; } }
-};
-#define PHASE_MARK(pc, what) (pc).mark(what)
-#else
-struct PhaseClock {};
-#define PHASE_MARK(pc, what) ((void)0)
-#endif
-
 int run_pipelined(frbch_handle* const* hs, uint32_t nif, const int* in_fds, int out_fd, uint8_t* d_rows, size_t row_pitch) {
   frbch_handle* h0 = hs[0];
-  PhaseClock pc;
-  (void)pc;
   const bool scan = d_rows != nullptr;
   struct Batch { uint64_t nb, f0, nfr, pay_off; };
   std::vector<std::vector<Batch>> batches(nif);
@@ -430,7 +415,6 @@ int run_pipelined(frbch_handle* const* hs, uint32_t nif, const int* in_fds, int 
   const Plan& pl0 = h0->pl;
   int rc = FRBCH_OK;
 
-  PHASE_MARK(pc, "stream_begin (allocations)");
   // Pinned rings (kept in the first handle: pinning costs ~0.5 ms per MB).  Page-cache / tmpfs reads run at ~3 GB/s per
   // thread, far below the PCIe link, and scale with threads: each input slot has its own reader thread (pread).
   // Writes into ONE file do not scale (the kernel serialises them per inode; positional writes from four threads and
@@ -497,7 +481,6 @@ int run_pipelined(frbch_handle* const* hs, uint32_t nif, const int* in_fds, int 
       pre_done.store(1, std::memory_order_release);    // (without a mapping the writers take turns: one sequential stream of write() calls)
     });
 
-  PHASE_MARK(pc, "pinned rings");
   // every batch's frames travel in pieces of whole frames that fit a pinned buffer; batch rounds go IF by IF
   struct Piece { uint32_t ifx; size_t batch; uint64_t f0, nfr; size_t dst_off; bool ends_batch, ends_round; };
   std::vector<Piece> pieces;
@@ -732,7 +715,6 @@ int run_pipelined(frbch_handle* const* hs, uint32_t nif, const int* in_fds, int 
     }
     if (!rc && scan && pc.ends_round) rc = drain_scan(false);
   }
-  PHASE_MARK(pc, "input + transform");
   for (uint32_t i = 0; i < nif && !rc; ++i) {
     frbch_handle* h = hs[i];
     uint64_t rows = 0;
@@ -742,7 +724,6 @@ int run_pipelined(frbch_handle* const* hs, uint32_t nif, const int* in_fds, int 
     if (!rc && rows) rc = scan ? queue_rows(h, rows) : emit_bytes(h->d_out, (size_t)(rows * h->pl.row_bytes), h->stream);
   }
   if (!rc && scan) rc = drain_scan(true);
-  PHASE_MARK(pc, "flush + output");
   {   // stop the threads: readers may be waiting for a slot, writers for data
     { std::lock_guard<std::mutex> lk(qin.m); qin.stop = true; qin.cv.notify_all(); }
     for (auto& t : readers) t.join();
@@ -767,7 +748,6 @@ int run_pipelined(frbch_handle* const* hs, uint32_t nif, const int* in_fds, int 
   }
   if (out_expect && out_off != out_expect && ftruncate(out_fd, (off_t)out_off) != 0 && !rc)
     rc = fail(h0, FRBCH_E_IO, std::string("ftruncate: ") + strerror(errno));
-  PHASE_MARK(pc, "writers drained");
   release();
   return rc;
 }

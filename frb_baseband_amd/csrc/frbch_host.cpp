@@ -202,50 +202,30 @@ std::string make_plan(const frbch_config& cfg, Plan* pl, size_t lds_limit, int i
     default: pl->digi_mean = 0.0f; pl->digi_scale = 1.0f; pl->digi_max = 0.0f; break;
   }
 
-  // fast path (kernels_fast.inc): lengths 512..4096 = 256*M, 16 points per (virtual) thread.
-  // wave-private variant for M <= 8 (flags & 8 selects the barrier variant instead).
+  // fast path (kernels_fast.inc): lengths 512..8192 = 256*M, 16 points per (virtual) thread; the wave-private K1
   pl->fast_k1_log2m = pl->fast_k2_log2m = 0;
   pl->fast_k1_wave = pl->fast_k2_wave = 0;
   pl->fast_k2_m1 = 0;
   pl->k2_two_stage = 0;
   pl->k2_stage1_tscr = 0;
   pl->spill_tile_major = 0;
-  pl->fast_k2_nt = (cfg.flags & 4u) ? 1024 : 512;
+  pl->fast_k2_nt = 512;
   pl->k1_fast_lds = pl->k2_fast_lds = 0;
-  const bool want_wave = !(cfg.flags & 8u);
   if (!(cfg.flags & 1u) && r >= 512 && r <= 8192 && in_bits == 2 && !pl->coherent) {   // the fast gather is written for 2-bit input
     const int m = (int)r / 256;
-    const bool wave = want_wave;               // (every M <= 32 has a wave-private K1; flags & 8 asks for the barrier kernels)
     const int tps = 16 * m;
-    const int gfast = wave ? (m == 32 ? 2 : (m == 16 ? 4 : 8 * (tps < 64 ? 64 / tps : 1))) : 64 / m;
+    // branches per workgroup: R = 8192 2 (8 waves, four per sequence, two virtual threads per lane), R = 4096 4 (8 waves, two
+    // per sequence), else 8 (one wave per sequence; x 64/TPS sequences per wave)
+    const int gfast = m == 32 ? 2 : (m == 16 ? 4 : 8 * (tps < 64 ? 64 / tps : 1));
     const size_t seq = (size_t)r + r / 8 + 8;
-    // M = 8 experiments (flags & 64): two half-size workgroups per CU (4 branches each) filling interleaved
-    // halves of the 8-branch layout rows, with 2 waves (or, flags & 128, 1 wave) per sequence
-    int kind = 0, kg = gfast;
-    if (wave && m == 8 && (cfg.flags & 64u)) {   // experiments only: the single 8-branch workgroup measured fastest
-      kind = (cfg.flags & 128u) ? 1 : 2;
-      kg = 4;
-    } else if (wave && m == 8 && (cfg.flags & 128u)) {
-      kind = 3;                                   // 16 waves, two per sequence, 8 branches
-    } else if (wave && m == 16) {
-      kind = 4;                                   // R = 4096: 8 waves, two per sequence, 4 branches
-    } else if (wave && m == 32) {
-      kind = 5;                                   // R = 8192: 8 waves, four per sequence (two virtual threads per lane), 2 branches
-    }
-    const size_t lds = (size_t)kg * seq * 8 + (size_t)r * (kg / 2) + 128 + (wave ? (size_t)kg * 132 : 0) +   // + unpack LUT + coarse delay factors + arrival counters
-                       ((m >= 16 && !wave) || m == 32 ? (size_t)m * 128 : 0);                               // + the radix-M pass's twiddles (barrier kernels, M >= 16; every kernel at M = 32)
+    const size_t lds = (size_t)gfast * seq * 8 + (size_t)r * (gfast / 2) + 128 + (size_t)gfast * 132 +   // + unpack LUT + coarse delay factors + arrival counters
+                       (m == 32 ? (size_t)m * 128 : 0);                                                   // + the radix-32 pass's twiddles
     const size_t generic_lds = (size_t)gfast * seq1;   // fallback for unaligned calls keeps the layout
-#ifdef FRBCH_EXPERIMENTS
-    static const int gl_env = getenv("FRBCH_GL") ? atoi(getenv("FRBCH_GL")) : 0;   // layout group = workgroup group
-#else
-    const int gl_env = 0;
-#endif
     if (gfast <= pl->c2 && lds <= lds_limit && generic_lds <= lds_limit) {
       pl->fast_k1_log2m = ilog2(m);
-      pl->fast_k1_wave = wave ? 1 : 0;
-      pl->fast_k1_kind = kind;
-      pl->fast_k1_g = kg;
-      pl->g = (gl_env && gl_env == kg) ? kg : gfast;
+      pl->fast_k1_wave = 1;
+      pl->fast_k1_g = gfast;
+      pl->g = gfast;
       pl->k1_lds = (size_t)pl->g * seq1;
       pl->k1_fast_lds = lds;
     }
@@ -257,11 +237,11 @@ std::string make_plan(const frbch_config& cfg, Plan* pl, size_t lds_limit, int i
     // stays on the barrier kernels
     // tscrunch > 2: two stages -- the same kernel with two time samples per row into a scratch buffer, then frbch_k2_scrunch
     // (K2 1.98 + 0.2 ms instead of the barrier kernel walking its sub-tiles, 3.85 ms at -t 8)
-    const bool wave32 = m == 32 && pl->nif == 1 && pl->fast_k1_log2m == 5 && pl->g == 2 && !(cfg.flags & (1u << 21)) &&
+    const bool wave32 = m == 32 && pl->nif == 1 && pl->fast_k1_log2m == 5 && pl->g == 2 &&
                         (pl->tscr <= 2 || (pl->tscr % 2 == 0 && pl->tscr <= (int)r));
-    pl->k2_two_stage = (wave32 && want_wave && !(cfg.flags & 4u) && pl->tscr > 2) ? pl->tscr / 2 : 0;
+    pl->k2_two_stage = (wave32 && pl->tscr > 2) ? pl->tscr / 2 : 0;
     pl->k2_stage1_tscr = 2;
-    const bool wave = want_wave && (m <= 16 || wave32) && !(cfg.flags & 4u);
+    const bool wave = m <= 16 || wave32;
     const int tps = 16 * m;
     const int spw = tps < 64 ? 64 / tps : 1;
     // the same beyond the largest tile of the other wave K2s (8 sequences x spw; 4 at 2C = 4096): -t 16 at 1024 channels
@@ -273,14 +253,13 @@ std::string make_plan(const frbch_config& cfg, Plan* pl, size_t lds_limit, int i
         pl->k2_stage1_tscr = tmax;
       }
     }
-    // wave variant: 2 waves per workgroup (more, smaller workgroups resident per CU) when tscrunch
-    // allows it and flags & 16 does not ask for 4
+    // wave variant: 2 waves per workgroup (more, smaller workgroups resident per CU) when tscrunch allows it
     // sequences (time samples) per workgroup = nw*spw: the smallest of 2, 4, 8 (x spw) that holds one
     // tscrunch group; small workgroups keep more of them resident per CU
     int nw = 4;
     if (wave && m == 16)
       nw = 4;                                     // 2C = 4096: 4 time samples per workgroup (128-B gather runs), two waves each
-    else if (wave && !(cfg.flags & 16u) && pl->tscr <= 2 * spw && ((2 * spw * pl->g) % 2 == 0) &&
+    else if (wave && pl->tscr <= 2 * spw && ((2 * spw * pl->g) % 2 == 0) &&
         (size_t)2 * spw * pl->ncol * 4 <= (size_t)2 * spw * ((size_t)pl->c2 + pl->c2 / 8 + 8) * 8)
       nw = 2;
     else if (wave && pl->tscr > 4 * spw)
@@ -288,7 +267,7 @@ std::string make_plan(const frbch_config& cfg, Plan* pl, size_t lds_limit, int i
     pl->fast_k2_nw = nw;
     // 2C = 8192: one workgroup = 2 time samples (147 KB of LDS, one workgroup per CU), or -- no tscrunch -- ONE time
     // sample with 512 threads (74 KB: two workgroups per CU, one gathers while the other transforms)
-    if (m == 32) pl->fast_k2_nt = (pl->tscr == 1 && !(cfg.flags & 4u)) ? 512 : 1024;
+    if (m == 32) pl->fast_k2_nt = pl->tscr == 1 ? 512 : 1024;
     const int tt = wave ? (m == 32 ? 2 : nw * spw) : pl->fast_k2_nt / tps;
     // 2C = 8192: a workgroup may walk tscrunch/tt tiles and add them up in registers
     const bool walk = m == 32 && !wave && pl->nif == 1 && pl->tscr > tt && pl->tscr % tt == 0 && pl->tscr <= (int)r;
@@ -322,37 +301,28 @@ std::string make_plan(const frbch_config& cfg, Plan* pl, size_t lds_limit, int i
     if (pl->tscr <= 64 / nh && ((int)r * nh) % 256 == 0) pl->fast_k2_lane = nh;
   }
 
-  // R = 2048, flag bit 24: the split K1 (bin-parity halves, 16 independent waves per CU) instead of the paired-branch wave
-  // K1 whenever frbch_k0_stage has corner-turned the batch (measured slower: 1.76 vs 1.54 ms)
-  pl->fast_k1_split = 0;
-  pl->k1_split_lds = (size_t)2 * 8 * (1024 + 128 + 2) * 8 + 2048 * 4 + (16 + 8 * 16 + 32) * 8;
-  if (pl->fast_k1_wave && pl->fast_k1_log2m == 3 && pl->fast_k1_kind == 0 && pl->fast_k1_g == 8 && pl->g == 8 &&
-      (cfg.flags & (1u << 24)) && pl->k1_split_lds <= lds_limit)
-    pl->fast_k1_split = 1;
-
   // tile-major spill: the paired-branch wave K1 (R = 2048, 8 branches per workgroup) in front of a wave K2 whose
   // workgroup takes two time samples (measured: K2 1.34 -> 1.29 ms, its gather alone 1.06 -> 0.95 ms; K1 unchanged)
   pl->spill_tile_major = 0;
-  if (pl->fast_k1_wave && pl->fast_k1_log2m == 3 && pl->fast_k1_kind == 0 && pl->fast_k1_g == 8 && pl->g == 8 &&
-      pl->fast_k2_wave && !pl->coherent && !(cfg.flags & (1u << 21))) {   // flag bit 21: keep the slab layout (A/B tests)
+  if (pl->fast_k1_wave && pl->fast_k1_log2m == 3 && pl->fast_k1_g == 8 && pl->g == 8 && pl->fast_k2_wave && !pl->coherent) {
     const int m2 = pl->c2 / 256, tps2 = 16 * m2, spw2 = tps2 < 64 ? 64 / tps2 : 1;
-    const bool two = (m2 == 16) || (m2 == 8 && !(cfg.flags & 32u) && pl->fast_k2_nw != 8);   // two waves per sequence
+    const bool two = (m2 == 16) || (m2 == 8 && pl->fast_k2_nw != 8);   // two waves per sequence
     const int tt2 = two ? (pl->fast_k2_nw == 2 ? 2 : 4) : pl->fast_k2_nw * spw2;
     if (tt2 == 2) pl->spill_tile_major = 2;
   }
   // 2C = 2048 behind that K1: the wave-private K2 (one wave per time sample, four per workgroup, two workgroups per CU; tscrunch up
-  // to its four-sample tile).  flag bit 26 keeps frbch_k2_wave (kernel-family cross-checks)
+  // to its four-sample tile)
   pl->fast_k2_priv = 0;
   pl->k2_priv_lds = (size_t)4 * (2048 + 256) * 8 + 1024 * 8;      // = 81,920: exactly half of the CU's 160 KiB
-  if (pl->fast_k1_wave && pl->fast_k1_log2m == 3 && pl->fast_k1_kind == 0 && pl->fast_k1_g == 8 && pl->g == 8 && !pl->fast_k1_split &&
-      pl->fast_k2_wave && pl->fast_k2_log2m == 3 && pl->c2 == 2048 && !pl->coherent && !(cfg.flags & ((1u << 21) | (1u << 26))) &&
+  if (pl->fast_k1_wave && pl->fast_k1_log2m == 3 && pl->fast_k1_g == 8 && pl->g == 8 &&
+      pl->fast_k2_wave && pl->fast_k2_log2m == 3 && pl->c2 == 2048 && !pl->coherent &&
       pl->k2_priv_lds <= lds_limit && pl->tscr <= 4 && !pl->k2_two_stage) {
     pl->fast_k2_priv = 1;
     pl->spill_tile_major = 2;      // (what the paired-branch K1 writes for it, whatever tile the two-wave K2 would have taken)
   }
   // chunks of eight time samples between the M = 32 barrier kernels (2 branches per K1 workgroup: the slab layout
   // leaves K2 one 32-byte piece per 128-KB slab)
-  if (pl->fast_k1_log2m == 5 && pl->fast_k2_log2m == 5 && !pl->coherent && !(cfg.flags & (1u << 21)))
+  if (pl->fast_k1_log2m == 5 && pl->fast_k2_log2m == 5 && !pl->coherent)
     pl->spill_tile_major = 8;   // (the wave K2 at 2C = 8192 reads this layout only: its plan condition above repeats these terms)
 
   // coherent pipeline on the register-pass kernels (barrier variants): K1 forward-only + K3 need R = 256*M, K2c needs
@@ -361,7 +331,7 @@ std::string make_plan(const frbch_config& cfg, Plan* pl, size_t lds_limit, int i
   pl->k2c_fast_lds = pl->k3_fast_lds = 0;
   // R = 4096 (M = 16, config 5): 512-thread K3 workgroups (one channel and its mirror), two per CU: one gathers while
   // the other transforms (K3 2.55 -> 2.20 ms)
-  pl->coh_nt = (pl->coherent && r == 4096 && !(cfg.flags & 4u)) ? 512 : 1024;
+  pl->coh_nt = (pl->coherent && r == 4096) ? 512 : 1024;
   if (pl->coherent && !(cfg.flags & 1u) && r >= 512 && r <= 8192 && in_bits == 2 && pl->c >= 4) {
     const int m = (int)r / 256;
     const int gfast = 64 / m;
@@ -375,7 +345,6 @@ std::string make_plan(const frbch_config& cfg, Plan* pl, size_t lds_limit, int i
       pl->coh_fast_r = ilog2(m);
       pl->fast_k1_log2m = ilog2(m);
       pl->fast_k1_wave = 0;
-      pl->fast_k1_kind = 0;
       pl->fast_k1_g = gfast;
       pl->g = gfast;
       pl->k1_lds = (size_t)gfast * seq1;
@@ -383,9 +352,8 @@ std::string make_plan(const frbch_config& cfg, Plan* pl, size_t lds_limit, int i
       pl->k3_fast_lds = lds3;
       // R = 4096 (config 5): the wave K1 (8 waves, two per branch, 4 branches = the same layout group) in its forward-only form
       const size_t ldsw = (size_t)gfast * seq * 8 + (size_t)r * (gfast / 2) + 128 + (size_t)gfast * 132;
-      if (m == 16 && want_wave && ldsw <= lds_limit) {
+      if (m == 16 && ldsw <= lds_limit) {
         pl->fast_k1_wave = 1;
-        pl->fast_k1_kind = 4;
         pl->k1_fast_lds = ldsw;
       }
     }
@@ -424,14 +392,9 @@ std::string make_plan(const frbch_config& cfg, Plan* pl, size_t lds_limit, int i
   pl->maxb = maxb;
   // Spill slabs of one block are R*g*8 B = a power of two apart: the 2C/g pieces K2 gathers for one tile would
   // all sit on one HBM channel.  A pad per slab spreads them.
-#ifdef FRBCH_EXPERIMENTS
-  static const int pad_env = getenv("FRBCH_SPILL_PAD") ? atoi(getenv("FRBCH_SPILL_PAD")) : -1;   // in cf
-#else
-  const int pad_env = -1;
-#endif
   // measured (K2, cfg 2): pad 0 -> 1.55 ms, 16 -> 1.38, 48..8208 -> 1.29-1.33; 272 cf = 2 KB + 128 B
   const int pad = (uint64_t)pl->r * pl->g >= 2048 ? 272 : 16;
-  pl->gs = (uint64_t)pl->r * pl->g + (uint64_t)(pad_env >= 0 ? pad_env : pad);
+  pl->gs = (uint64_t)pl->r * pl->g + (uint64_t)pad;
   return "";
 }
 

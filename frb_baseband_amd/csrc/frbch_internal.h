@@ -65,7 +65,6 @@ struct frbch_handle {
   // constant tables
   cf *tw_r = nullptr, *tw_c2 = nullptr, *tw_nhi = nullptr, *tw_nlo = nullptr;
   cf *ftw1_r = nullptr, *ftw2_r = nullptr, *ftw1_c = nullptr, *ftw2_c = nullptr, *td1 = nullptr, *td2 = nullptr;
-  cf *ftw1_h = nullptr, *ftw2_h = nullptr;
   // per-launch work buffers
   cf *spill = nullptr, *s_dc = nullptr, *p0 = nullptr;
   // coherent dedispersion (-F C:D): second spill, kernel table, channel-major power
@@ -133,25 +132,22 @@ struct frbch_handle {
 
   // rows for a wider row buffer: values between consecutive (row, product) lines of code_out (0 = nchan: packed rows)
   uint64_t out_pitch = 0;
-  // two-lane pipeline: spill regions in flight, ordering events
-  uint8_t* stg_cur = nullptr;      // staged payload of the launch in progress (stg + region offset)
-  int lane_cus = 0;                // compute units of the stream the next K1 goes to (0 = all of them)
+  // the digitiser beside the next K1 of a scan: CU counts, ordering events
+  int lane_cus = 0;                // compute units the next K1 may count on (0 = all of them)
   int lane_ncu = 0;                // compute units of the device (frbch_open)
-  bool quant_lds_allowed = false;  // the digitiser's LDS reservation (overlap mode 3) was enabled on this handle's device
-  dev_event_t region_ev[8];        // recorded behind the last back stage that read spill region r
-  bool region_busy[8] = {false, false, false, false, false, false, false, false};
-  bool region_ev_made = false;
+  bool quant_lds_allowed = false;  // the digitiser's LDS reservation was enabled on this handle's device
+  dev_event_t spill_ev{};          // recorded (on a scan's chain) behind the last back stage that read the spill
+  bool spill_ev_made = false, spill_busy = false;
   std::vector<dev_event_t> evpool; // ordering events, used round-robin
   size_t evnext = 0;
-  uint32_t next_region = 0;        // spill region of the next batch
   uint32_t diag = 0;               // frbch_info::diag
   uint8_t* scan_rows = nullptr;    // frbch_run_scan (first handle of the scan): the row buffer of all its IFs, kept between calls
   size_t scan_rows_bytes = 0;
   dev_event_t reset_ev{};          // behind the identity rescale a reset queued on the handle's stream
   bool reset_ev_made = false, reset_pending = false;
-  dev_event_t quant_ev{};          // behind a digitiser that ran on the back lane (mode 2)
+  dev_event_t quant_ev{};          // behind a digitiser that ran on a scan's second stream
   bool quant_ev_made = false, quant_busy = false;
-  int quant_lane_cus = 0;          // CUs of the lane the digitiser was sent to
+  int quant_lane_cus = 0;          // CUs the digitiser on the second stream holds (negative: by its LDS reservation)
 
   // profiling
   bool profiling = false;
@@ -184,23 +180,15 @@ struct DeviceGuard {
   DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 
-// cfg.flags of a product build (include/frbch.h): four kernel-selection switches, every one produces the same (correct) output
-// and has parity cases.  Everything else -- rejected kernel variants, layouts and lane modes kept for A/B runs, the timing-only
-// ablations of bits 8..19 -- exists only in libraries built with -DFRBCH_EXPERIMENTS; bit 22 (whole-file paths without their
-// reader / writer threads) also in the test-only emulator build.
+// cfg.flags (include/frbch.h): four kernel-selection switches, every one produces the same (correct) output and has parity
+// cases; bit 22 (whole-file paths without their reader / writer threads) in the test-only emulator build as well
 constexpr uint32_t kFlagGenericK1 = 1u, kFlagGenericK2 = 2u, kFlagSeparateStats = 1u << 20;
 constexpr uint32_t kFlagBuffered = 1u << 27, kFlagTwoPass = 1u << 28;   // form of a first `-c` rescale interval: neither = automatic
 constexpr uint32_t kProductFlags = kFlagGenericK1 | kFlagGenericK2 | kFlagSeparateStats | kFlagBuffered | kFlagTwoPass;
-constexpr uint32_t kFlagNoPipeline = 1u << 22, kFlagNoK0 = 1u << 23, kFlagGenericQuant = 1u << 25;
-[[maybe_unused]] constexpr uint32_t kExperimentFlags = 4u | 8u | 16u | 32u | 64u | 128u | (1u << 21) | (1u << 22) | (1u << 23) | (1u << 24) | (1u << 25) | (1u << 26);
-#ifdef FRBCH_EXPERIMENTS
-constexpr bool kExperiments = true;
-constexpr uint32_t kAcceptedFlags = kProductFlags | kExperimentFlags | 0x000FFF00u;
-#elif defined(FRBCH_TEST_HOOKS)
-constexpr bool kExperiments = false;
+constexpr uint32_t kFlagNoPipeline = 1u << 22;
+#ifdef FRBCH_TEST_HOOKS
 constexpr uint32_t kAcceptedFlags = kProductFlags | kFlagNoPipeline;
 #else
-constexpr bool kExperiments = false;
 constexpr uint32_t kAcceptedFlags = kProductFlags;
 #endif
 
@@ -243,35 +231,27 @@ inline void drain_events(frbch_handle* h) {
 }
 
 // =============================================================================================
-// Two lanes.  The front half of a batch (K0, K1, Kc) is bound by the instruction chain of its
-// waves and leaves HBM more than half idle; the back half (K2, statistics, digitiser) is bound by HBM and leaves the
-// vector units idle.  They run on two streams whose CU masks split the chip, so that the front of batch b + 1 overlaps the
-// back of batch b.  Mask bit i is CU i / 8 of XCD i % 8 (the driver deals the bits round-robin over the XCDs): a lane of
-// the first 8 k bits owns k CUs of every XCD, and the workgroup -> XCD round-robin the kernels' tile orders rely on holds
-// inside a lane as on the whole chip.  Placement affects speed only: every dependency is a stream-ordered event.
+// The digitiser beside the next K1.  In a scan, the digitiser of a completed rescale interval of IF i
+// (HBM-bound, most CUs idle) runs on a second plain stream while the K1 of IF i + 1 (bound by its waves) goes to the caller's
+// stream: the digitiser holds ncu - ncu_f CUs by an LDS reservation, K1 sizes its grid for the ncu_f CUs left to it.
+// Placement affects speed only: every dependency is a stream-ordered event.
 // =============================================================================================
 struct Lanes {
-  dev_stream_t f = 0, b = 0, b2 = 0;   // front lane; back lane; a second stream on the back lane's CUs (K0 beside K2)
-  int ncu = 0, ncu_f = 0;
+  dev_stream_t b = 0;     // the digitiser's stream
+  int ncu = 0, ncu_f = 0; // compute units of the device; those left to the K1 beside the digitiser
   bool ok = false;
 };
 
-// The stages of one API call (or of one scan call, across its IFs) in the order they are queued.
+// The stages of one scan call, across its IFs, in the order they are queued; every stage but such a digitiser goes to `user`.
 struct Chain {
   Lanes* ln = nullptr;            // null: every stage on `user`, as queued
   dev_stream_t user = 0;
   frbch_handle* owner = nullptr;  // whose event pool is used
-  uint32_t stages_total = 0;      // (front, back) pairs the chain will run; the last back stage runs on the whole chip
-  uint32_t fronts = 0, backs = 0;
-  bool k0_back = false;           // K0 beside the back lane's kernels instead of in front of K1 on the front lane
-  int mode = 1;                   // 1: K2 / statistics / digitiser on the back lane, K0 / K1 / Kc on the front lane
-                                  // 2: only the digitiser of a completed interval on the (small) back lane, beside the NEXT
-                                  //    front stage on the front lane; K2 keeps the whole chip
-  dev_event_t ev_entry{}, ev_front{}, ev_back{}, ev_q{};
-  dev_stream_t s_front = 0, s_back = 0;   // streams of the last front / back stage queued
-  bool f_rooted = false, b_rooted = false, b2_rooted = false;
-  bool q_pending = false, have_q = false; // mode 2: a digitiser runs on the back lane (the next front stage goes beside it)
-  bool front_beside_q = false;            // mode 3: the front stage being queued shares the chip with a digitiser
+  uint32_t stages_total = 0;      // front stages (batches) the chain will run
+  uint32_t fronts = 0;
+  dev_event_t ev_entry{}, ev_q{};
+  bool b_rooted = false;
+  bool q_pending = false, have_q = false; // a digitiser runs on the second stream (the next front stage goes beside it)
 };
 
 // ---- frbch_launch.cpp -----------------------------------------------------------------------------------------------------------
@@ -280,7 +260,7 @@ KParams base_params(const frbch_handle* h);
 int allow_generic_lds(frbch_handle* h);                      // LDS sizes of the generic kernels for the handle's plan
 int setup_fast(frbch_handle* h);                             // tables and LDS sizes of the register-pass kernels
 int build_chirp(frbch_handle* h, int order_m);
-int launch_front(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s, dev_stream_t sk);   // K0, K1, Kc
+int launch_front(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s);   // K0, K1, Kc
 int launch_dls_count(frbch_handle* h, KParams& p, uint64_t nsamples, dev_stream_t s);            // dynamic level setting: the windows' low-state counts
 int launch_back(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s);                     // K2 (or K2c, K3, K4)
 int launch_unpack_tap(frbch_handle* h, KParams& p, uint64_t nsamples, int decoder, dev_stream_t s);
@@ -288,20 +268,18 @@ int fused_chunks_of(const frbch_handle* h);                  // rows of partial 
 int ensure_partial(frbch_handle* h);
 int ensure_powbuf(frbch_handle* h);
 int run_stats(frbch_handle* h, uint64_t rows, dev_stream_t s);
-bool quant_fast_geometry(const frbch_handle* h, int ncu, int wgs_per_cu, uint64_t rp_force, uint64_t* wgs_out, uint64_t* nthr_out, uint64_t* rp_out);
+bool quant_fast_geometry(const frbch_handle* h, int ncu, uint64_t* wgs_out, uint64_t* nthr_out, uint64_t* rp_out);
 int run_quantise(frbch_handle* h, uint64_t rows, uint8_t* dst, dev_stream_t s, int ncu = 0);
 uint64_t out_row_span(const frbch_handle* h);
 uint64_t out_extent(const frbch_handle* h, uint64_t rows);
 // ---- frbch_stream.cpp -----------------------------------------------------------------------------------------------------------
-Lanes* get_lanes(int device, int ncu_front, bool plain = false);
+Lanes* get_lanes(int device, int ncu_front);
 dev_event_t pool_event(frbch_handle* h);
-void chain_begin(Chain* c, frbch_handle* owner, dev_stream_t user, Lanes* ln, uint32_t stages_total, bool k0_back, int mode);
+void chain_begin(Chain* c, frbch_handle* owner, dev_stream_t user, Lanes* ln, uint32_t stages_total);
 void chain_end(Chain* c);
-void chain_back_touch(Chain* c);
 int overlap_front_cus(const frbch_handle* h);
-int overlap_mode(const frbch_handle* h);
 bool overlap_usable(const frbch_handle* h);
-uint64_t feed_stage_count(const frbch_handle* h, uint64_t nblocks, bool overlap);
+uint64_t feed_stage_count(const frbch_handle* h, uint64_t nblocks);
 int engine_feed(frbch_handle* h, const uint8_t* d_frames, uint32_t frame_bytes, uint32_t header_bytes,
                 uint64_t payload_off, uint64_t nblocks, uint8_t* d_out, size_t cap, uint64_t* rows_written,
                 dev_stream_t s, const uint8_t* h_bad = nullptr, uint64_t nfr_bad = 0, const uint32_t* d_fbad = nullptr,

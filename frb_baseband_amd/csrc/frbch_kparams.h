@@ -49,8 +49,6 @@ struct KParams {
   // fast-path tables (kernels_fast.inc): L = 256*M, TPS = 16*M
   const cf* ftw1_r;         // [16][R/16]   exp(-2 pi i p ka / R)
   const cf* ftw2_r;         // [M][16]      exp(-2 pi i c kb / (R/16))
-  const cf* ftw1_h;         // same two tables for length R/2 (frbch_k1_split: half transforms)
-  const cf* ftw2_h;
   const cf* ftw1_c;         // same for the across-branch length 2C
   const cf* ftw2_c;
   const cf* td1;            // [2C][16]     exp(-2 pi i n1 kc / (16*2C))      (delay, coarse part)
@@ -70,7 +68,6 @@ struct KParams {
   int coherent;             // 1 = that pipeline
   int nfilt_pos;            // channel samples discarded at the start of every block (overlap-save)
   int keep;                 // channel samples kept per block, a multiple of tscr
-  int stag;                 // K1 wave kernels: priority schedule of the two halves of a workgroup (bit mask, see the kernel)
   uint64_t hop;             // real samples between block starts: N, or 2C*keep with overlap-save
   cf* spill2;               // [nblk][2C/4][R][4]  chirped spectrum P'[k'][pos]: groups of 4 channels side by side, so that a
                             // K2c tile (few positions x all channels) writes 32-byte x tile-width runs; pos = position of
@@ -83,7 +80,6 @@ struct KParams {
   double* stat_partial;     // fast K2, float power: [workgroup row][ncol][2] running (sum, sum of squares); null = off
   uint64_t stat_limit;      // ... of the rows below this absolute row of power_out (the end of the rescale interval)
   uint32_t nblk;            // blocks in this launch (persistent kernels loop over them)
-  uint32_t dbg;             // timing-only ablations (cfg.flags >> 8); results are wrong when set
   const uint8_t* stg;        // wave K1: the launch's payload re-ordered by frbch_k0_stage, [blk][branch group][row][RB bytes]: the
                              // rows of one workgroup and block are contiguous (null = gather from the frames)
   uint8_t* stg_out;          // frbch_k0_stage: where it writes that buffer
@@ -91,7 +87,6 @@ struct KParams {
                              // with two time samples per workgroup: a K2 tile is one contiguous run).  8 = chunks of eight time samples
                              // [blk][t/8][n1/G][t%8][n1%G] (frbch_k1_fast<5> -> frbch_k2_fast<5>: whole cache lines on both sides).
                              // Set per launch by the engine (the K1 that runs decides)
-  unsigned long long* stamps; // diagnostic builds of the wave K1: s_memtime stamps [workgroup][wave][16] of one block; null = off
   const uint32_t* fbad;       // generic K1 only: bitmap over the frames of `frames` (bit f = frame f is flagged invalid or is a
                               // filler for a missing frame): its samples enter the filterbank as 0.  null = every frame is good
   uint64_t fbad_frame0;       // index, inside the bitmap, of the frame `frames` points at

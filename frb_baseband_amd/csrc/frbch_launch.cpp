@@ -49,8 +49,6 @@ KParams base_params(const frbch_handle* h) {
   p.tw_nlo = h->tw_nlo;
   p.ftw1_r = h->ftw1_r;
   p.ftw2_r = h->ftw2_r;
-  p.ftw1_h = h->ftw1_h;
-  p.ftw2_h = h->ftw2_h;
   p.ftw1_c = h->ftw1_c;
   p.ftw2_c = h->ftw2_c;
   p.td1 = h->td1;
@@ -67,11 +65,6 @@ KParams base_params(const frbch_handle* h) {
   p.digi_scale = pl.digi_scale;
   p.digi_max = pl.digi_max;
   p.out_pitch = h->out_pitch ? h->out_pitch : (uint64_t)pl.c;
-#ifdef FRBCH_EXPERIMENTS
-  p.dbg = (h->cfg.flags >> 8) & 0xFFFu;   // bits 8..19: timing-only ablations (wrong output)
-#else
-  p.dbg = 0;
-#endif
   p.coherent = pl.coherent;
   p.nfilt_pos = pl.nfilt_pos;
   p.keep = pl.keep;
@@ -91,12 +84,6 @@ template <int LOG2M>
 void launch_k1_wave_t(const Plan& pl, KParams& p, uint32_t nb, dev_stream_t s, int ncu) {
   // persistent over blocks: the resident workgroups each keep their branch group and loop over the batch
   p.nblk = nb;
-#ifdef FRBCH_EXPERIMENTS
-  static const int stag_env = getenv("FRBCH_K1_STAG") ? atoi(getenv("FRBCH_K1_STAG")) : 3;   // priority schedule (3: the halves swap priority behind the forward passes; measured 1.96 -> 1.94 ms)
-  p.stag = stag_env;
-#else
-  p.stag = 3;
-#endif
   const int kg = pl.fast_k1_g;            // branches per workgroup (<= pl.g, the layout group)
   {
     static const int ks[6] = {1, 2, 3, 4, 8, 12};
@@ -108,35 +95,14 @@ void launch_k1_wave_t(const Plan& pl, KParams& p, uint32_t nb, dev_stream_t s, i
     }
   }
   const uint32_t ngrp = (uint32_t)(pl.c2 / kg);
-#ifdef FRBCH_EXPERIMENTS
-  static const char* stamp_path = getenv("FRBCH_STAMPS");   // diagnostic: phase stamps of one block, dumped after every launch
-#else
-  const char* const stamp_path = nullptr;
-#endif
-  static unsigned long long* stamp_buf = nullptr;
-  const size_t stamp_n = (size_t)ngrp * 16 * 16;
-  if (stamp_path) {
-    if (!stamp_buf) (void)hipMalloc((void**)&stamp_buf, (size_t)4096 * 16 * 16 * 8);
-    (void)hipMemsetAsync(stamp_buf, 0, stamp_n * 8, s);
-    p.stamps = stamp_buf;
-  }
-#ifdef FRBCH_EXPERIMENTS
-  static const uint32_t cap_env = getenv("FRBCH_K1_MAXWG") ? (uint32_t)atoi(getenv("FRBCH_K1_MAXWG")) : 0u;
-#else
-  const uint32_t cap_env = 0u;
-#endif
-  const uint32_t resident = cap_env ? cap_env : (uint32_t)(ncu > 0 ? ncu : 256) * (uint32_t)std::max<size_t>(1, (160 * 1024) / pl.k1_fast_lds);
+  const uint32_t resident = (uint32_t)(ncu > 0 ? ncu : 256) * (uint32_t)std::max<size_t>(1, (160 * 1024) / pl.k1_fast_lds);
   uint32_t ny = std::max<uint32_t>(1, std::min<uint32_t>(nb, resident / std::max<uint32_t>(1, ngrp)));
   if (ngrp > resident && ngrp % resident != 0) {
-    // more branch groups than resident workgroups and not a whole number of rounds (a CU-masked lane, e.g. 256 groups on
-    // 160 CUs): split the blocks over ny workgroups per group so that ngrp * ny fills whole rounds
+    // more branch groups than resident workgroups and not a whole number of rounds (K1 beside the digitiser, e.g. 256 groups
+    // on 176 CUs): split the blocks over ny workgroups per group so that ngrp * ny fills whole rounds
     uint32_t g = ngrp, r = resident;
     while (r) { const uint32_t t = g % r; g = r; r = t; }
-    uint32_t want = resident / g;
-#ifdef FRBCH_EXPERIMENTS
-    static const int ny_env = getenv("FRBCH_K1_NY") ? atoi(getenv("FRBCH_K1_NY")) : 0;
-    if (ny_env > 0) want = (uint32_t)ny_env;
-#endif
+    const uint32_t want = resident / g;
     if (want <= nb) ny = want;
   }
   const size_t lds_msk = pl.k1_fast_lds + (size_t)(LOG2M >= 5 ? pl.r / 8 : pl.r);   // + one flag per n2 row (frames flagged invalid / fillers: MSK): a byte, at R = 8192 a bit
@@ -156,36 +122,24 @@ void launch_k1_wave_t(const Plan& pl, KParams& p, uint32_t nb, dev_stream_t s, i
     } else
     FRBCH_K1W(4, 8, 2, 512);
   } else {
-#ifdef FRBCH_EXPERIMENTS   // K1 shapes with more, smaller waves (flags 64 / 128): all measured slower than eight wave-private waves
-    if (LOG2M == 3 && pl.fast_k1_kind == 1) FRBCH_K1W(3, 4, 1, 256);
-    else if (LOG2M == 3 && pl.fast_k1_kind == 2) FRBCH_K1W(3, 8, 2, 512);
-    else if (LOG2M == 3 && pl.fast_k1_kind == 3) FRBCH_K1W(3, 16, 2, 1024);
-    else
-#endif
     FRBCH_K1W(LOG2M, 8, 1, 512);
   }
 #undef FRBCH_K1W
-  if (stamp_path && nb > 8 * ny) {
-    std::vector<unsigned long long> hst(stamp_n);
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpy(hst.data(), stamp_buf, stamp_n * 8, hipMemcpyDeviceToHost);
-    if (FILE* f = fopen(stamp_path, "wb")) { fwrite(hst.data(), 8, stamp_n, f); fclose(f); }
-  }
 }
 constexpr uint32_t kFusedStatWgs = 2048;   // persistent K2 workgroups (= rows of partial sums per thread row) while statistics are fused
 // threads per workgroup of the wave-private K2 variant launch_k2_wave_t selects
-int k2_wave_nt(const Plan& pl, uint32_t h_flags) {
+int k2_wave_nt(const Plan& pl) {
   if (pl.fast_k2_log2m == 5) return 512;
   if (pl.fast_k2_log2m == 4) return pl.fast_k2_nw == 2 ? 256 : 512;
   if (pl.fast_k2_nw == 8) return 512;
-  if (pl.fast_k2_log2m == 3 && !(h_flags & 32u)) return pl.fast_k2_nw == 2 ? 256 : 512;
+  if (pl.fast_k2_log2m == 3) return pl.fast_k2_nw == 2 ? 256 : 512;
   return pl.fast_k2_nw == 2 ? 128 : 256;
 }
 // rows of partial sums the fused statistics use; 0 = this configuration cannot fuse (one column group per thread needed)
 // the wave K3 (coherent filterbank, R = 4096) sums the statistics of its channel: one row of partial sums per persistent workgroup
 constexpr uint32_t kK3WaveWgs = 2048;
-bool k3_wave_planned(const Plan& pl, uint32_t h_flags) {
-  return pl.coherent && pl.coh_fast_r == 4 && pl.coh_nt == 512 && !(h_flags & 8u);
+bool k3_wave_planned(const Plan& pl) {
+  return pl.coherent && pl.coh_fast_r == 4 && pl.coh_nt == 512;
 }
 // frbch_k2_priv: one row of partial sums per (workgroup, row phase); `grid` = its workgroups (one per CU)
 int priv_stat_chunks(const Plan& pl, int grid) { return grid * (pl.ncol / 4 >= 256 ? 1 : (int)(256 / (pl.ncol / 4))); }
@@ -209,12 +163,12 @@ int fused_stat_chunks(const Plan& pl, uint32_t h_flags, int pol_mode, int priv_g
 }
 int wave_stat_chunks(const Plan& pl, uint32_t h_flags, int pol_mode) {
   if (pol_mode == 3 || pl.k2_two_stage) return 0;   // (two-stage tscrunch: K2 does not see the output rows)
-  if (k3_wave_planned(pl, h_flags)) return (h_flags & (1u << 20)) ? 0 : (int)kK3WaveWgs;   // (PP+QQ)^2: its square overflows the fp32 partial sums (~1e24 squared)
+  if (k3_wave_planned(pl)) return (h_flags & (1u << 20)) ? 0 : (int)kK3WaveWgs;   // (PP+QQ)^2: its square overflows the fp32 partial sums (~1e24 squared)
   if (!(pl.fast_k2_log2m || pl.fast_k2_m1) || !pl.fast_k2_wave || pl.coherent || (h_flags & (1u << 20))) return 0;
-  const int nt = k2_wave_nt(pl, h_flags), cg = (int)(pl.ncol / 4);
+  const int nt = k2_wave_nt(pl), cg = (int)(pl.ncol / 4);
   if (cg > nt)   // a thread owns cg/nt column groups, one row of sums per workgroup (the MSTAT instantiations: 2C = 2048, two waves per sequence)
     return (cg % nt == 0 && cg / nt <= 4)
-               ? (pl.fast_k2_log2m == 5 ? 256 : ((pl.fast_k2_log2m == 3 && !(h_flags & 32u) && pl.fast_k2_nw != 8) ? (int)kFusedStatWgs : 0))   // 2C = 8192: resident workgroups only
+               ? (pl.fast_k2_log2m == 5 ? 256 : ((pl.fast_k2_log2m == 3 && pl.fast_k2_nw != 8) ? (int)kFusedStatWgs : 0))   // 2C = 8192: resident workgroups only
                : 0;
   if (nt % cg != 0) return 0;
   return (int)kFusedStatWgs * (nt / cg);
@@ -226,12 +180,7 @@ void launch_k2_wave_t(const Plan& pl, KParams& p, uint32_t nb, dev_stream_t s, u
   // persistent: one wave of workgroups loops over the (tiles per block) x nb tiles of the launch
   p.nblk = nb;
   if (!wave_stat_chunks(pl, h_flags, p.pol_mode)) p.stat_partial = nullptr;
-#ifdef FRBCH_EXPERIMENTS
-  static const uint32_t npers_env = getenv("FRBCH_K2_NPERS") ? (uint32_t)atoi(getenv("FRBCH_K2_NPERS")) : 0u;
-#else
-  const uint32_t npers_env = 0u;
-#endif
-  const uint32_t npers = p.stat_partial ? kFusedStatWgs : (npers_env ? npers_env : 8192u);   // measured: 768 (= resident) 1.59 ms, 2048 1.56, 8192 1.49 (shorter tail)
+  const uint32_t npers = p.stat_partial ? kFusedStatWgs : 8192u;   // measured: 768 (= resident) 1.59 ms, 2048 1.56, 8192 1.49 (shorter tail)
   auto pers = [&](uint32_t tiles_per_block) { return dim3(std::min<uint64_t>((uint64_t)tiles_per_block * nb, npers)); };
   const dim3 grid2 = pers(pl.r / (2 * spw)), grid4 = pers(pl.r / (4 * spw)), grid8 = pers(pl.r / (8 * spw));
   const int pm = p.pol_mode == 2 ? 2 : (p.pol_mode >= 4 ? 4 : 0);
@@ -262,7 +211,7 @@ void launch_k2_wave_t(const Plan& pl, KParams& p, uint32_t nb, dev_stream_t s, u
     if (pm == 2) FRBCH_K2W(8, 2, grid8); else if (pm == 4) FRBCH_K2W(8, 4, grid8); else FRBCH_K2W(8, 0, grid8);
   } else
   // M = 8: two waves per sequence (16 points per lane), 2 or 4 sequences per workgroup -> 16 waves per CU
-  if (LOG2M == 3 && !(h_flags & 32u)) {
+  if constexpr (LOG2M == 3) {
     if (pl.fast_k2_nw == 2) {
       if (pm == 2) hipLaunchKernelGGL((fast::frbch_k2_wave<3, 4, 2, 2>), grid2, dim3(256), pl.k2_fast_lds, s, p);
       else if (pm == 4 && (p.stat_partial || p.out_mode != FRBCH_OUT_FLOAT_POWER)) hipLaunchKernelGGL((fast::frbch_k2_wave<3, 4, 4, 2, true>), grid2, dim3(256), pl.k2_fast_lds, s, p);
@@ -274,7 +223,7 @@ void launch_k2_wave_t(const Plan& pl, KParams& p, uint32_t nb, dev_stream_t s, u
       else if (pm == 4) hipLaunchKernelGGL((fast::frbch_k2_wave<3, 8, 4, 2>), grid4, dim3(512), pl.k2_fast_lds, s, p);
       else hipLaunchKernelGGL((fast::frbch_k2_wave<3, 8, 0, 2>), grid4, dim3(512), pl.k2_fast_lds, s, p);
     }
-  } else if constexpr (LOG2M != 3 || kExperiments) {   // (2C = 2048 with one wave per sequence and 2 / 4 waves: flag 32, experiments builds only)
+  } else {
   if (pl.fast_k2_nw == 2) {
     if (pm == 2) FRBCH_K2W(2, 2, grid2); else if (pm == 4) FRBCH_K2W(2, 4, grid2); else FRBCH_K2W(2, 0, grid2);
   } else {
@@ -290,16 +239,6 @@ void set_fastdiv(KParams& p) {
   while ((1ull << l) < d) ++l;
   p.div_magic = (uint32_t)((((1ull << l) - d) << 32) / d + 1);
   p.div_shift = l ? l - 1 : 0;
-}
-template <int LOG2M>
-void launch_k2_fast_t(const Plan& pl, KParams& p, uint32_t nb, dev_stream_t s) {
-  const int tps = 16 << LOG2M;
-  // time samples per workgroup: its TT-sample tile, or (M = 32 only) tscrunch/TT tiles in a row
-  const int tile_t = std::max(pl.fast_k2_nt / tps, pl.tscr);
-  if (pl.fast_k2_nt == 1024)
-    hipLaunchKernelGGL((fast::frbch_k2_fast<LOG2M, 1024>), dim3(pl.r / tile_t, nb), dim3(1024), pl.k2_fast_lds, s, p);
-  else
-    hipLaunchKernelGGL((fast::frbch_k2_fast<LOG2M, 512>), dim3(pl.r / tile_t, nb), dim3(512), pl.k2_fast_lds, s, p);
 }
 template <int LOG2M>
 void launch_kc_fast_t(const Plan& pl, KParams& p, uint32_t nb, dev_stream_t s) {
@@ -327,8 +266,7 @@ bool launch_kc_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
 void launch_k0_stage(frbch_handle* h, const KParams& p, uint32_t nb, dev_stream_t s) {
   const Plan& pl = h->pl;
   h->stg_ready = false;
-  const bool no_k0 = (h->cfg.flags & kFlagNoK0) != 0;   // gather straight from the frames
-  if (!h->stg || no_k0 || !pl.fast_k1_log2m || pl.c % 256 != 0 || pl.r % 64 != 0) return;
+  if (!h->stg || !pl.fast_k1_log2m || pl.c % 256 != 0 || pl.r % 64 != 0) return;
   if (pl.coherent && !h->coh_order_m) return;              // the generic K1 is in use
   const uint32_t rb = (uint32_t)(pl.fast_k1_wave ? pl.fast_k1_g : pl.g) / 2;
   if (rb < 1 || p.payload_off % rb || p.payload_bytes % rb || p.header_bytes % rb || p.frame_bytes % rb || ((uintptr_t)p.frames % 16) ||
@@ -341,7 +279,7 @@ void launch_k0_stage(frbch_handle* h, const KParams& p, uint32_t nb, dev_stream_
   q.frames = p.frames + fr0 * p.frame_bytes;
   q.rel0 = (uint32_t)rel0;
   set_fastdiv(q);
-  q.stg_out = h->stg_cur ? h->stg_cur : h->stg;
+  q.stg_out = h->stg;
   ProfScope ps(h, s, KID_K0, (double)nb * (double)pl.block_payload_bytes * (1.0 + (double)p.frame_bytes / p.payload_bytes));
   const dim3 grid((pl.r / 64) * (pl.c / 256), nb);
   const bool wide = !(rel0 % 16 || p.payload_bytes % 16 || p.header_bytes % 16 || p.frame_bytes % 16);
@@ -374,26 +312,14 @@ bool launch_k1_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
     q.frames = p.frames + fr0 * p.frame_bytes;
     q.rel0 = (uint32_t)rel0;
     set_fastdiv(q);
-    if (h->stg_ready) q.stg = h->stg_cur ? h->stg_cur : h->stg;   // launch_k0_stage has corner-turned this batch
+    if (h->stg_ready) q.stg = h->stg;   // launch_k0_stage has corner-turned this batch
     h->stg_ready = false;
     if (p.fbad) {   // flagged frames: the staged wave K1 masks them (a flag per row beside the stage: a byte, at R = 8192 a bit)
-      if (!q.stg || pl.fast_k1_kind == 1 || pl.fast_k1_kind == 2 || pl.fast_k1_kind == 3 || pl.fast_k1_split ||
-          pl.k1_fast_lds + (size_t)(pl.fast_k1_log2m >= 5 ? pl.r / 8 : pl.r) > h->lds_limit)
+      if (!q.stg || pl.k1_fast_lds + (size_t)(pl.fast_k1_log2m >= 5 ? pl.r / 8 : pl.r) > h->lds_limit)
         return false;
       q.fbad_frame0 = p.fbad_frame0 + fr0;
     }
     q.tile_major = p.tile_major = pl.spill_tile_major;   // 2 (R = 2048, paired branches) or 8 (R = 8192) or 0 (K2 of this batch reads what this launch writes)
-#ifdef FRBCH_EXPERIMENTS
-    if (pl.fast_k1_split && q.stg) {    // persistent over blocks, one 16-wave workgroup per CU
-      q.nblk = nb;
-      const uint32_t ngrp = (uint32_t)(pl.c2 / 8);
-      const uint32_t ny = std::max<uint32_t>(1, std::min<uint32_t>(nb, 256u / std::max<uint32_t>(1, ngrp)));
-      hipLaunchKernelGGL(fast::frbch_k1_split, dim3(ngrp, ny), dim3(1024), pl.k1_split_lds, s, q);
-      h->kname[KID_K1] = "frbch_k1_split";
-      return true;
-    }
-    if (pl.fast_k1_split) h->kname[KID_K1] = "frbch_k1_wave<3,8,1>";
-#endif
     switch (pl.fast_k1_log2m) {
       case 1: launch_k1_wave_t<1>(pl, q, nb, s, h->lane_cus); break;
       case 2: launch_k1_wave_t<2>(pl, q, nb, s, h->lane_cus); break;
@@ -406,7 +332,7 @@ bool launch_k1_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
   }
   p.tile_major = pl.spill_tile_major == 8 ? 8 : 0;   // (K2 of this batch reads what this launch writes)
   KParams q = p;
-  if (h->stg_ready) q.stg = h->stg_cur ? h->stg_cur : h->stg;   // launch_k0_stage has corner-turned this batch
+  if (h->stg_ready) q.stg = h->stg;   // launch_k0_stage has corner-turned this batch
   h->stg_ready = false;
   {   // launch-relative 32-bit addressing where the batch fits (else the kernel divides in 64 bits)
     const uint64_t fr0 = p.payload_off / p.payload_bytes;
@@ -511,19 +437,9 @@ bool launch_k2_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
     hipLaunchKernelGGL(fast::frbch_k2_scrunch, dim3((unsigned)std::min<uint64_t>((groups + 255) / 256, 8192)), dim3(256), 0, s, p);
     return true;
   }
-  switch (pl.fast_k2_log2m) {
-#ifdef FRBCH_EXPERIMENTS   // the barrier K2 below 2C = 8192: flags 4 / 8 only
-    case 1: launch_k2_fast_t<1>(pl, p, nb, s); break;
-    case 2: launch_k2_fast_t<2>(pl, p, nb, s); break;
-    case 3: launch_k2_fast_t<3>(pl, p, nb, s); break;
-    case 4: launch_k2_fast_t<4>(pl, p, nb, s); break;
-#endif
-    case 5:
-      if (pl.fast_k2_nt == 512) hipLaunchKernelGGL((fast::frbch_k2_fast<5, 512>), dim3(pl.r, nb), dim3(512), pl.k2_fast_lds, s, p);   // one time sample per workgroup (tscrunch 1)
-      else hipLaunchKernelGGL((fast::frbch_k2_fast<5, 1024>), dim3(pl.r / std::max(2, pl.tscr), nb), dim3(1024), pl.k2_fast_lds, s, p);
-      break;
-    default: return false;
-  }
+  if (pl.fast_k2_log2m != 5) return false;   // (the barrier K2: 2C = 8192 only)
+  if (pl.fast_k2_nt == 512) hipLaunchKernelGGL((fast::frbch_k2_fast<5, 512>), dim3(pl.r, nb), dim3(512), pl.k2_fast_lds, s, p);   // one time sample per workgroup (tscrunch 1)
+  else hipLaunchKernelGGL((fast::frbch_k2_fast<5, 1024>), dim3(pl.r / std::max(2, pl.tscr), nb), dim3(1024), pl.k2_fast_lds, s, p);
   return true;
 }
 bool launch_k2c_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
@@ -552,26 +468,17 @@ bool launch_k3_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
   if (!pl.coh_fast_r || !h->coh_order_m) return false;
   const int np = pl.coh_nt / (16 << pl.coh_fast_r) / 2;
   const dim3 grid(pl.c / np, nb);
-  if (pl.coh_nt == 512) {
+  if (pl.coh_nt == 512) {   // R = 4096: the wave form, persistent over the (block, channel) tiles, next tile prefetched piecewise
     if (pl.coh_fast_r != 4) return false;
-    if (!(h->cfg.flags & 8u)) {   // wave form: persistent over the (block, channel) tiles, next tile prefetched piecewise
-      p.nblk = nb;
-      const uint64_t ntiles = (uint64_t)nb * pl.c;
-      hipLaunchKernelGGL((fast::frbch_k3_wave<4>), dim3((unsigned)std::min<uint64_t>(ntiles, kK3WaveWgs)), dim3(256), pl.k3_fast_lds, s, p);
-      return true;
-    }
-#ifdef FRBCH_EXPERIMENTS
-    hipLaunchKernelGGL((fast::frbch_k3_fast<4, 512>), grid, dim3(512), pl.k3_fast_lds, s, p);
+    p.nblk = nb;
+    const uint64_t ntiles = (uint64_t)nb * pl.c;
+    hipLaunchKernelGGL((fast::frbch_k3_wave<4>), dim3((unsigned)std::min<uint64_t>(ntiles, kK3WaveWgs)), dim3(256), pl.k3_fast_lds, s, p);
     return true;
-#else
-    return false;
-#endif
   }
   switch (pl.coh_fast_r) {
     case 1: hipLaunchKernelGGL((fast::frbch_k3_fast<1, 1024>), grid, dim3(1024), pl.k3_fast_lds, s, p); break;
     case 2: hipLaunchKernelGGL((fast::frbch_k3_fast<2, 1024>), grid, dim3(1024), pl.k3_fast_lds, s, p); break;
     case 3: hipLaunchKernelGGL((fast::frbch_k3_fast<3, 1024>), grid, dim3(1024), pl.k3_fast_lds, s, p); break;
-    case 4: hipLaunchKernelGGL((fast::frbch_k3_fast<4, 1024>), grid, dim3(1024), pl.k3_fast_lds, s, p); break;
     case 5: hipLaunchKernelGGL((fast::frbch_k3_fast<5, 1024>), grid, dim3(1024), pl.k3_fast_lds, s, p); break;
     default: return false;
   }
@@ -627,14 +534,6 @@ int setup_fast(frbch_handle* h) {
       }
     }
     if ((rc = upload_cf(h, &h->td1, d1)) || (rc = upload_cf(h, &h->td2, d2))) return rc;
-#ifdef FRBCH_EXPERIMENTS
-    if (pl.fast_k1_split) {
-      std::vector<float> h1, h2;
-      fft_tables(pl.r / 2, &h1, &h2);
-      if ((rc = upload_cf(h, &h->ftw1_h, h1)) || (rc = upload_cf(h, &h->ftw2_h, h2))) return rc;
-      if ((rc = allow_lds(h, fast::frbch_k1_split, pl.k1_split_lds))) return rc;
-    }
-#endif
     if (!h->stg)
       CHECK_DEV(h, dev_malloc((void**)&h->stg, (size_t)pl.maxb * pl.block_payload_bytes), "hipMalloc(staged payload)");
 #define FRBCH_AL(L, NWV, WPSV) do { if (!rc) rc = allow_lds(h, fast::frbch_k1_wave<L, NWV, WPSV, false>, pl.k1_fast_lds); \
@@ -652,11 +551,7 @@ int setup_fast(frbch_handle* h) {
         if (!rc && pl.k1_fast_lds + (size_t)pl.r <= h->lds_limit) rc = allow_lds(h, fast::frbch_k1_wave<4, 8, 2, true, true, true>, pl.k1_fast_lds + (size_t)pl.r);
         break;
       case 5: FRBCH_AL(5, 8, 4); break;
-#ifdef FRBCH_EXPERIMENTS
-      default: FRBCH_AL(3, 8, 1); FRBCH_AL(3, 4, 1); FRBCH_AL(3, 8, 2); FRBCH_AL(3, 16, 2); break;
-#else
       default: FRBCH_AL(3, 8, 1); break;
-#endif
     }
 #undef FRBCH_AL
     else switch (pl.fast_k1_log2m) {
@@ -685,14 +580,7 @@ int setup_fast(frbch_handle* h) {
       case 1: rc = allow_lds(h, fast::frbch_k3_fast<1, 1024>, pl.k3_fast_lds); break;
       case 2: rc = allow_lds(h, fast::frbch_k3_fast<2, 1024>, pl.k3_fast_lds); break;
       case 3: rc = allow_lds(h, fast::frbch_k3_fast<3, 1024>, pl.k3_fast_lds); break;
-      case 4:
-#ifdef FRBCH_EXPERIMENTS
-        rc = pl.coh_nt == 512 ? allow_lds(h, fast::frbch_k3_fast<4, 512>, pl.k3_fast_lds) : allow_lds(h, fast::frbch_k3_fast<4, 1024>, pl.k3_fast_lds);
-#else
-        rc = pl.coh_nt == 512 ? FRBCH_OK : allow_lds(h, fast::frbch_k3_fast<4, 1024>, pl.k3_fast_lds);
-#endif
-        if (!rc && pl.coh_nt == 512) rc = allow_lds(h, fast::frbch_k3_wave<4>, pl.k3_fast_lds);
-        break;
+      case 4: rc = allow_lds(h, fast::frbch_k3_wave<4>, pl.k3_fast_lds); break;   // (R = 4096: coh_nt = 512, the wave K3)
       default: rc = allow_lds(h, fast::frbch_k3_fast<5, 1024>, pl.k3_fast_lds); break;
     }
     if (rc) return rc;
@@ -750,8 +638,7 @@ int setup_fast(frbch_handle* h) {
       if (pl.fast_k2_log2m == 1) { FRBCH_ALLOW_L(1); }
       else if (pl.fast_k2_log2m == 2) { FRBCH_ALLOW_L(2); }
       else {
-        if constexpr (kExperiments) { FRBCH_ALLOW_L(3); }
-        else { FRBCH_ALLOW(3, 8, 0); FRBCH_ALLOW(3, 8, 2); FRBCH_ALLOW(3, 8, 4); }
+        FRBCH_ALLOW(3, 8, 0); FRBCH_ALLOW(3, 8, 2); FRBCH_ALLOW(3, 8, 4);
         if (!rc) rc = allow_lds(h, fast::frbch_k2_wave<3, 4, 0, 2>, pl.k2_fast_lds);
         if (!rc) rc = allow_lds(h, fast::frbch_k2_wave<3, 4, 2, 2>, pl.k2_fast_lds);
         if (!rc) rc = allow_lds(h, fast::frbch_k2_wave<3, 4, 4, 2>, pl.k2_fast_lds);
@@ -764,17 +651,8 @@ int setup_fast(frbch_handle* h) {
 #undef FRBCH_ALLOW_L
 #undef FRBCH_ALLOW
     }
-    else switch (pl.fast_k2_log2m) {
-#ifdef FRBCH_EXPERIMENTS
-      case 1: rc = big ? allow_lds(h, fast::frbch_k2_fast<1, 1024>, pl.k2_fast_lds) : allow_lds(h, fast::frbch_k2_fast<1, 512>, pl.k2_fast_lds); break;
-      case 2: rc = big ? allow_lds(h, fast::frbch_k2_fast<2, 1024>, pl.k2_fast_lds) : allow_lds(h, fast::frbch_k2_fast<2, 512>, pl.k2_fast_lds); break;
-      case 3: rc = big ? allow_lds(h, fast::frbch_k2_fast<3, 1024>, pl.k2_fast_lds) : allow_lds(h, fast::frbch_k2_fast<3, 512>, pl.k2_fast_lds); break;
-      case 4: rc = big ? allow_lds(h, fast::frbch_k2_fast<4, 1024>, pl.k2_fast_lds) : allow_lds(h, fast::frbch_k2_fast<4, 512>, pl.k2_fast_lds); break;
-#else
-      case 1: case 2: case 3: case 4: rc = fail(h, FRBCH_E_ARG, "the barrier K2 below 8192 branches exists only in experiments builds"); break;
-#endif
-      default: rc = big ? allow_lds(h, fast::frbch_k2_fast<5, 1024>, pl.k2_fast_lds) : allow_lds(h, fast::frbch_k2_fast<5, 512>, pl.k2_fast_lds); break;
-    }
+    else   // the barrier K2: 2C = 8192 only
+      rc = big ? allow_lds(h, fast::frbch_k2_fast<5, 1024>, pl.k2_fast_lds) : allow_lds(h, fast::frbch_k2_fast<5, 512>, pl.k2_fast_lds);
     if (rc) return rc;
   }
   return FRBCH_OK;
@@ -809,8 +687,6 @@ int build_chirp(frbch_handle* h, int order_m) {
   return FRBCH_OK;
 }
 
-dev_event_t pool_event(frbch_handle* h);
-// K0 + K1 + Kc over nb blocks: frames -> spill, P0.  K0 may run on another stream (`sk`, the back lane's CUs): K1 waits for it.
 // dynamic level setting: the low-state counts of the windows covering the launch's first `nsamples` samples (a multiple of the window)
 int launch_dls_count(frbch_handle* h, KParams& p, uint64_t nsamples, dev_stream_t s) {
   const Plan& pl = h->pl;
@@ -833,7 +709,8 @@ int launch_dls_count(frbch_handle* h, KParams& p, uint64_t nsamples, dev_stream_
   return FRBCH_OK;
 }
 
-int launch_front(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s, dev_stream_t sk) {
+// K0 + K1 + Kc over nb blocks: frames -> spill, P0
+int launch_front(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
   const Plan& pl = h->pl;
   p.tile_major = 0;   // set by the K1 that writes that layout
   if (pl.dls_lg_ns) {
@@ -844,14 +721,7 @@ int launch_front(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s, dev_s
     // blocks that touch invalid / filler frames: the staged wave K1 reads their samples as 0 through a flag per row (MSK);
     // where it cannot run (R = 8192, unaligned input, the barrier K1) the generic K1 tests the bitmap per sample
     const bool masked = p.fbad != nullptr;
-    if (!masked || pl.fast_k1_wave) {
-      launch_k0_stage(h, p, nb, sk);
-      if (sk != s && h->stg_ready) {
-        const dev_event_t e = pool_event(h);
-        dev_event_record(e, sk);
-        (void)dev_stream_wait(s, e);
-      }
-    }
+    if (!masked || pl.fast_k1_wave) launch_k0_stage(h, p, nb, s);
     const double bytes = (double)nb * ((double)pl.block_payload_bytes * p.frame_bytes / p.payload_bytes +
                                        (double)pl.n * 8.0 + (double)pl.c2 * 8.0);
     ProfScope ps(h, s, KID_K1, bytes);
@@ -893,7 +763,7 @@ int launch_back(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
   const double out_b = p.out_mode == FRBCH_OUT_FLOAT_POWER ? (double)pl.ncol * 4.0 : (double)pl.row_bytes;
   const double bytes = (double)nb * ((double)pl.n * 8.0 + (double)pl.rows_per_block * out_b);
 #ifndef FRBCH_NO_FAST
-  const bool k3_sums = k3_wave_planned(pl, h->cfg.flags) && h->coh_order_m != 0;   // (the generic K3 of a fallen-back launch does not sum)
+  const bool k3_sums = k3_wave_planned(pl) && h->coh_order_m != 0;   // (the generic K3 of a fallen-back launch does not sum)
 #else
   const bool k3_sums = false;
 #endif
@@ -1016,16 +886,15 @@ int run_stats(frbch_handle* h, uint64_t rows, dev_stream_t s) {
 
 // Geometry of the lean 8-bit digitiser (frbch_quantise_fast) on `ncu` CUs (0 = the whole chip; negative: |ncu| CUs held by one
 // 512-thread workgroup each, see run_quantise): workgroups, threads per workgroup and row phases; false = the generic kernel runs
-bool quant_fast_geometry(const frbch_handle* h, int ncu, int wgs_per_cu, uint64_t rp_force, uint64_t* wgs_out, uint64_t* nthr_out, uint64_t* rp_out) {
+bool quant_fast_geometry(const frbch_handle* h, int ncu, uint64_t* wgs_out, uint64_t* nthr_out, uint64_t* rp_out) {
   const Plan& pl = h->pl;
-  if ((h->cfg.flags & kFlagGenericQuant) || h->cfg.nbit_out != 8 || pl.digi_max != 255.0f) return false;
+  if (h->cfg.nbit_out != 8 || pl.digi_max != 255.0f) return false;
   const uint64_t cg = pl.ncol / 4;
   const bool pow2 = (pl.ncol & (pl.ncol - 1)) == 0 && (pl.c & (pl.c - 1)) == 0;
   if (!pow2 || pl.c < 4 || cg < 8) return false;   // (narrow rows, 32 .. 128 columns: a wave covers several rows -- one contiguous run all the same)
   const bool excl = ncu < 0;
   const uint64_t nthr = excl ? 512 : 256;
-  uint64_t rp = excl ? (uint64_t)(-ncu) * nthr / cg : (uint64_t)(ncu > 0 ? ncu : 256) * (uint64_t)(wgs_per_cu > 0 ? wgs_per_cu : 3) * 256 / cg;
-  if (rp_force) rp = rp_force;
+  const uint64_t rp = excl ? (uint64_t)(-ncu) * nthr / cg : (uint64_t)(ncu > 0 ? ncu : 256) * 3 * 256 / cg;
   const uint64_t wgs = rp * cg / nthr;
   const uint64_t pitch = h->out_pitch ? h->out_pitch : (uint64_t)pl.c;
   if (!wgs || wgs * nthr != rp * cg || pitch % 4 || rp * (uint64_t)pl.nif * pitch >= (1ull << 31) || rp * pl.ncol * 4 >= (1ull << 31)) return false;
@@ -1057,12 +926,7 @@ int run_quantise(frbch_handle* h, uint64_t rows, uint8_t* dst, dev_stream_t s, i
   // stream reads fastest with 8 waves per CU, tools/micro/stream_cus; this kernel carries ~60 VALU instructions per group --
   // index arithmetic, rescale, four digitiser chains -- and needs the waves: 1 / 2 / 4 / 8 / 32 workgroups per CU measured
   // 2.8 / 1.76 / 1.41 / 1.59 / 1.28 ms per 6.4 GB, profiles/r03_overlap_sweep_quantise_lane.txt)
-#ifdef FRBCH_EXPERIMENTS
-  static const int wgs_env = getenv("FRBCH_QUANT_WGS") ? atoi(getenv("FRBCH_QUANT_WGS")) : 0;
-#else
-  const int wgs_env = 0;
-#endif
-  const uint64_t gx = std::min<uint64_t>((total + 256 * 4 - 1) / (256 * 4), (uint64_t)(ncu != 0 ? std::abs(ncu) : 256) * (uint64_t)(wgs_env > 0 ? wgs_env : 32));
+  const uint64_t gx = std::min<uint64_t>((total + 256 * 4 - 1) / (256 * 4), (uint64_t)(ncu != 0 ? std::abs(ncu) : 256) * 32);
   qp.grid_x = (uint32_t)std::max<uint64_t>(1, gx);
   qp.log2_c = 0;
   while ((1 << qp.log2_c) < pl.c) ++qp.log2_c;
@@ -1081,13 +945,8 @@ int run_quantise(frbch_handle* h, uint64_t rows, uint8_t* dst, dev_stream_t s, i
     // beside it -- the digitiser holds |ncu| CUs to itself on a plain stream while the next IF's K1 runs on the others.  (16 loads
     // in flight per thread or 1024 threads per workgroup: the same time; the two kernels together move 5.2 TB/s.)
     const bool excl = ncu < 0;
-#ifdef FRBCH_EXPERIMENTS
-    static const int rp_env = getenv("FRBCH_QUANT_RP") ? atoi(getenv("FRBCH_QUANT_RP")) : 0;
-#else
-    const int rp_env = 0;
-#endif
     uint64_t wgs = 0, nthr = 0, rp = 0;
-    if (quant_fast_geometry(h, ncu, wgs_env, excl ? 0 : (uint64_t)rp_env, &wgs, &nthr, &rp)) {
+    if (quant_fast_geometry(h, ncu, &wgs, &nthr, &rp)) {
       qp.grid_x = (uint32_t)wgs;
       qp.rphases = (uint32_t)rp;
       h->kname[KID_QUANT] = "frbch_quantise_fast<8>";

@@ -19,12 +19,13 @@ int finalize_interval(frbch_handle* h, uint64_t stat_rows, uint8_t* d_out, size_
   }
   int rc = run_stats(h, stat_rows, s0);
   if (rc) return rc;
-  // the back lane when the digitiser can run beside the next K1 (on CUs it holds by an LDS reservation: only the lean kernel does that)
+  // the scan's second stream when the digitiser can run beside the next K1 (on CUs it holds by an LDS reservation: only the lean
+  // kernel does that)
   dev_stream_t s = s0;
   {
     const int lane = chain_quant_lane_cus(ch);
     uint64_t a_ = 0, b_ = 0, c_ = 0;
-    if (lane > 0 || (lane < 0 && quant_fast_geometry(h, lane, 0, 0, &a_, &b_, &c_))) s = chain_quant_stream(ch, s0, &h->quant_lane_cus);
+    if (lane && quant_fast_geometry(h, lane, &a_, &b_, &c_)) s = chain_quant_stream(ch, s0, &h->quant_lane_cus);
   }
   h->have_scale = true;
   if (h->cfg.rescale_constant) h->scale_frozen = true;
@@ -113,63 +114,27 @@ int deferred_materialise(frbch_handle* h, dev_stream_t s) {
 }
 
 std::mutex g_lanes_mutex;
-std::vector<std::pair<std::pair<int, int>, Lanes*>> g_lanes;   // (device, front CUs) -> lanes; live until the process ends
+std::vector<std::pair<std::pair<int, int>, Lanes*>> g_lanes;   // (device, CUs left to K1) -> lanes; live until the process ends
 
-Lanes* get_lanes(int device, int ncu_front, bool plain) {
+Lanes* get_lanes(int device, int ncu_front) {
   std::lock_guard<std::mutex> lk(g_lanes_mutex);
-  const int key = plain ? -ncu_front : ncu_front;
   for (auto& e : g_lanes)
-    if (e.first.first == device && e.first.second == key) return e.second->ok ? e.second : nullptr;
+    if (e.first.first == device && e.first.second == ncu_front) return e.second->ok ? e.second : nullptr;
   Lanes* ln = new Lanes();
-  g_lanes.push_back({{device, key}, ln});
+  g_lanes.push_back({{device, ncu_front}, ln});
   ln->ncu = dev_cu_count(device);
-  // (a failed creation leaves the entry with ok = false: the streams made so far are destroyed, later calls get nullptr)
-  auto three_plain = [&]() {
-    if (dev_stream_create(&ln->f) == 0 && dev_stream_create(&ln->b) == 0 && dev_stream_create(&ln->b2) == 0) return true;
-    if (ln->f) dev_stream_destroy(ln->f);
-    if (ln->b) dev_stream_destroy(ln->b);
-    if (ln->b2) dev_stream_destroy(ln->b2);
-    ln->f = ln->b = ln->b2 = 0;
-    (void)dev_last_error_string();
-    return false;
-  };
-  if (plain && ln->ncu > 0) {
-    // mode 3: plain streams (no CU masks: a masked queue costs every launch of the process 50 - 100 us while it is active,
-    // profiles/NOTES.md); the digitiser claims its CUs by its LDS reservation, ncu_f is what is left for the K1 beside it
-    if (ncu_front < 8 || ncu_front > ln->ncu - 8) return nullptr;
-    if (!three_plain()) return nullptr;
-    ln->ncu_f = ncu_front;
-    ln->ok = true;
-    return ln;
-  }
-  if (ncu_front >= ln->ncu && ln->ncu > 0) {
-    // no partition: plain streams.  Kernels of the two lanes share every CU as far as its registers, LDS and wave slots go
-    // (the digitiser's 4-wave workgroups fit beside the wave K1's eight 216-register waves: one per CU)
-    if (!three_plain()) return nullptr;
-    ln->ncu_f = ln->ncu;
-    ln->ok = true;
-    return ln;
-  }
-#ifndef FRBCH_EXPERIMENTS
-  return nullptr;   // CU-masked lanes (overlap modes 1 and 2) were measured slower: experiments builds only
-#else
-  if (ln->ncu < 32 || ln->ncu % 8 || ncu_front < 8 || ncu_front > ln->ncu - 8 || ncu_front % 8) return nullptr;
-  const uint32_t words = (uint32_t)((ln->ncu + 31) / 32);
-  std::vector<uint32_t> mf(words, 0u), mb(words, 0u);
-  for (int i = 0; i < ln->ncu; ++i) (i < ncu_front ? mf : mb)[(size_t)i >> 5] |= 1u << (i & 31);
-  if (dev_stream_create_masked(&ln->f, mf.data(), words) != 0 || dev_stream_create_masked(&ln->b, mb.data(), words) != 0 ||
-      dev_stream_create_masked(&ln->b2, mb.data(), words) != 0) {
-    if (ln->f) dev_stream_destroy(ln->f);
-    if (ln->b) dev_stream_destroy(ln->b);
-    if (ln->b2) dev_stream_destroy(ln->b2);
-    ln->f = ln->b = ln->b2 = 0;
+  // a plain stream (no CU mask: a masked queue costs every launch of the process 50 - 100 us while it is active,
+  // profiles/NOTES.md); the digitiser claims its CUs by its LDS reservation, ncu_f is what is left for the K1 beside it.
+  // (a failed creation leaves the entry with ok = false: later calls get nullptr)
+  if (ln->ncu <= 0 || ncu_front < 8 || ncu_front > ln->ncu - 8) return nullptr;
+  if (dev_stream_create(&ln->b) != 0) {
+    ln->b = 0;
     (void)dev_last_error_string();
     return nullptr;
   }
   ln->ncu_f = ncu_front;
   ln->ok = true;
   return ln;
-#endif
 }
 
 dev_event_t pool_event(frbch_handle* h) {
@@ -183,93 +148,32 @@ dev_event_t pool_event(frbch_handle* h) {
 }
 
 
-void chain_begin(Chain* c, frbch_handle* owner, dev_stream_t user, Lanes* ln, uint32_t stages_total, bool k0_back, int mode) {
+void chain_begin(Chain* c, frbch_handle* owner, dev_stream_t user, Lanes* ln, uint32_t stages_total) {
   *c = Chain();
   c->owner = owner;
   c->user = user;
   c->ln = stages_total >= 2 ? ln : nullptr;
   c->stages_total = stages_total;
-  c->mode = mode;
-  c->k0_back = k0_back && mode == 1;
   if (c->ln) {
     c->ev_entry = pool_event(owner);
     dev_event_record(c->ev_entry, user);
   }
 }
-// stream of the next front stage: the first one has the chip to itself (nothing to overlap with yet)
-dev_stream_t chain_front_stream(Chain* c) {
-  if (!c->ln || c->fronts == 0) return c->user;
-  if (c->mode == 3) {   // the caller's stream throughout; only the K1 grid changes while a digitiser holds part of the chip
-    c->front_beside_q = c->q_pending;
-    c->q_pending = false;
-    return c->user;
-  }
-  if (c->mode == 2) {
-    if (!c->q_pending) return c->user;
-    c->q_pending = false;
-    if (!c->f_rooted) {
-      (void)dev_stream_wait(c->ln->f, c->ev_entry);
-      c->f_rooted = true;
-    }
-    if (c->backs) (void)dev_stream_wait(c->ln->f, c->ev_back);   // the K2 before it had the whole chip
-    return c->ln->f;
-  }
-  if (!c->f_rooted) {
-    (void)dev_stream_wait(c->ln->f, c->ev_entry);
-    if (c->s_front == c->user && c->fronts) (void)dev_stream_wait(c->ln->f, c->ev_front);   // behind the whole-chip first front
-    c->f_rooted = true;
-  }
-  return c->ln->f;
-}
-dev_stream_t chain_k0_stream(Chain* c, dev_stream_t front) {
-  if (!c->ln || !c->k0_back || front == c->user) return front;
-  if (!c->b2_rooted) {
-    (void)dev_stream_wait(c->ln->b2, c->ev_entry);
-    c->b2_rooted = true;
-  }
-  return c->ln->b2;
-}
-void chain_front_done(Chain* c, dev_stream_t sf) {
-  c->s_front = sf;
+// a front stage is queued on the caller's stream: the CUs left to its K1 when it shares the chip with the digitiser the back
+// stage before it sent to the second stream, else 0 (all of them)
+int chain_front(Chain* c) {
+  const bool beside = c->ln && c->q_pending;
+  c->q_pending = false;
   c->fronts++;
-  if (c->ln) {
-    c->ev_front = pool_event(c->owner);
-    dev_event_record(c->ev_front, sf);
-  }
+  return beside ? c->ln->ncu_f : 0;
 }
-// stream of the next back stage (ordered behind its front stage and the previous back stage)
-dev_stream_t chain_back_stream(Chain* c) {
-  if (!c->ln) return c->user;
-  if (c->mode >= 2) {
-    if (c->s_front != c->user) (void)dev_stream_wait(c->user, c->ev_front);
-    return c->user;
-  }
-  const bool last = c->backs + 1 >= c->stages_total;
-  const dev_stream_t sb = last ? c->user : c->ln->b;
-  if (sb == c->ln->b && !c->b_rooted) {
-    (void)dev_stream_wait(sb, c->ev_entry);
-    c->b_rooted = true;
-  }
-  if (c->s_front != sb) (void)dev_stream_wait(sb, c->ev_front);
-  if (c->backs && c->s_back != sb) (void)dev_stream_wait(sb, c->ev_back);
-  return sb;
+// CUs the digitiser of a completed interval would hold on the second stream, negative: held by its LDS reservation (see
+// run_quantise); 0 = no second stream, or no front stage left to run beside it
+int chain_quant_lane_cus(const Chain* c) {
+  if (!c || !c->ln || c->fronts >= c->stages_total) return 0;
+  return -(c->ln->ncu - c->ln->ncu_f);
 }
-void chain_back_done(Chain* c, dev_stream_t sb) {
-  c->s_back = sb;
-  c->backs++;
-  if (c->ln) {
-    c->ev_back = pool_event(c->owner);
-    dev_event_record(c->ev_back, sb);
-  }
-}
-// everything the chain queued is ordered in front of what follows on the caller's stream
-// mode 2: the stream the digitiser of a completed interval goes to -- the back lane while another front stage is still to
-// come (it runs beside that stage's K1), else the stream `s` of the statistics in front of it
-int chain_quant_lane_cus(const Chain* c) {   // CUs the digitiser would get on the back lane (negative: held by its LDS reservation); 0 = no lane
-  if (!c || !c->ln || c->mode < 2 || c->fronts >= c->stages_total) return 0;
-  const int n = c->ln->ncu_f >= c->ln->ncu ? c->ln->ncu : c->ln->ncu - c->ln->ncu_f;
-  return c->mode == 3 ? -n : n;
-}
+// the second stream for that digitiser, ordered behind the statistics in front of it on `s`
 dev_stream_t chain_quant_stream(Chain* c, dev_stream_t s, int* ncu) {
   if (!chain_quant_lane_cus(c)) return s;
   const dev_stream_t sq = c->ln->b;
@@ -284,68 +188,37 @@ dev_stream_t chain_quant_stream(Chain* c, dev_stream_t s, int* ncu) {
   return sq;
 }
 void chain_quant_done(Chain* c, dev_stream_t sq) {
-  if (!c || !c->ln || c->mode < 2 || sq != c->ln->b) return;
+  if (!c || !c->ln || sq != c->ln->b) return;
   c->ev_q = pool_event(c->owner);
   dev_event_record(c->ev_q, sq);
   c->q_pending = true;
   c->have_q = true;
 }
+// everything the chain queued is ordered in front of what follows on the caller's stream
 void chain_end(Chain* c) {
-  if (!c->ln) return;
-  if (c->have_q) (void)dev_stream_wait(c->user, c->ev_q);
-  if (c->fronts && c->s_front != c->user) (void)dev_stream_wait(c->user, c->ev_front);
-  if (c->backs && c->s_back != c->user) (void)dev_stream_wait(c->user, c->ev_back);
-  // (every K0 on the second back-lane stream was waited for by its K1, whose back stage is ordered above)
-}
-// more work was queued on the stream of the last back stage (the digitiser of a flushed interval): later stages and the
-// end of the chain are ordered behind it
-void chain_back_touch(Chain* c) {
-  if (!c->ln || !c->backs) return;
-  c->ev_back = pool_event(c->owner);
-  dev_event_record(c->ev_back, c->s_back);
+  if (c->ln && c->have_q) (void)dev_stream_wait(c->user, c->ev_q);
 }
 
-// front CUs / batches per call requested through frbch_config::overlap (0 = automatic)
+// front CUs requested through frbch_config::overlap (0 = automatic)
 int overlap_front_cus(const frbch_handle* h) {
   const uint32_t v = h->cfg.overlap & 0xFFFFu;
-#ifdef FRBCH_EXPERIMENTS
-  static const int env = getenv("FRBCH_FRONT_CUS") ? atoi(getenv("FRBCH_FRONT_CUS")) : -1;
-  if (env >= 0) return env;
-#endif
   if (v == 1) return 0;                       // overlap off
   if (v) return (int)(v / 8 * 8);
-  // automatic.  K1 against K2 (mode 1): never -- both scale with their share of the CUs (K2 on 96 CUs takes 2.4x its
-  // whole-chip time), splitting the chip between them only adds launches (profiles/r03_overlap_sweep_*.txt).
-  // The digitiser of a completed interval beside the next IF's K1 (mode 3, a scan): yes when it is a stream of four products
+  // automatic.  K1 beside K2: never -- both scale with their share of the CUs (K2 on 96 CUs takes 2.4x its whole-chip time),
+  // splitting the chip between them only adds launches (profiles/r03_overlap_sweep_*.txt).
+  // The digitiser of a completed interval beside the next IF's K1 (a scan): yes when it is a stream of four products
   // -- 6.4 GB per IF, HBM-bound on the whole chip with most CUs idle, while K1 is bound by its waves and leaves HBM half idle.
   // 80 of 256 CUs for the digitiser make both take ~2.3 ms (1.55 + 1.14 one after the other): 39.5 -> 36.4 ms per 8-IF step of
   // config 3, the two together moving 5.2 TB/s.  One product (1.6 GB): what it hides is what K1 loses on fewer CUs: off.
   const Plan& pl = h->pl;
-  if (pl.nif == 4 && h->cfg.nbit_out == 8 && pl.fast_k1_log2m == 3 && pl.fast_k1_wave && !pl.fast_k1_split && h->lane_ncu >= 64)
+  if (pl.nif == 4 && h->cfg.nbit_out == 8 && pl.fast_k1_log2m == 3 && pl.fast_k1_wave && h->lane_ncu >= 64)
     return h->lane_ncu * 11 / 16 / 8 * 8;
   return 0;
-}
-int overlap_mode(const frbch_handle* h) {
-  const uint32_t m = (h->cfg.overlap >> 24) & 3u;
-#ifdef FRBCH_EXPERIMENTS
-  static const int env = getenv("FRBCH_OVERLAP_MODE") ? atoi(getenv("FRBCH_OVERLAP_MODE")) : 0;
-  if (env > 0) return env;
-#endif
-  return m ? (int)m : 3;
 }
 bool overlap_usable(const frbch_handle* h) {
   const Plan& pl = h->pl;
   return !pl.coherent && pl.fast_k1_log2m && pl.fast_k1_wave && (pl.fast_k2_log2m || pl.fast_k2_m1) && pl.fast_k2_wave &&
          overlap_front_cus(h) >= 8;
-}
-uint32_t overlap_batches(const frbch_handle* h, uint64_t nblocks) {
-  uint32_t v = (h->cfg.overlap >> 16) & 0xFFu;
-#ifdef FRBCH_EXPERIMENTS
-  static const int env = getenv("FRBCH_PIPE_BATCHES") ? atoi(getenv("FRBCH_PIPE_BATCHES")) : 0;
-  if (env > 0) v = (uint32_t)env;
-#endif
-  if (!v) v = (uint32_t)std::min<uint64_t>(4, nblocks / 24);    // batches of at least 24 blocks (ramp-up and tail of the persistent kernels)
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(v, nblocks));
 }
 
 // Transform `nblocks` blocks starting `payload_off` bytes into the payload stream of d_frames.
@@ -384,62 +257,41 @@ int engine_feed(frbch_handle* h, const uint8_t* d_frames, uint32_t frame_bytes, 
   return FRBCH_OK;
 }
 
-// batches a run of `nblocks` blocks is cut into: equal sizes (no short tail launch), at most maxb blocks each, and -- when
-// the stages overlap -- at most half the spill (two regions in flight) and at least `want` batches
-static void plan_batches(const Plan& pl, uint64_t nblocks, bool overlap, uint32_t want, uint64_t* nbatch, uint64_t* per) {
-  const uint64_t cap = overlap ? std::max<uint64_t>(1, pl.maxb / 2) : pl.maxb;
+// batches a run of `nblocks` blocks is cut into: equal sizes (no short tail launch), at most maxb blocks each
+static void plan_batches(const Plan& pl, uint64_t nblocks, uint64_t* nbatch, uint64_t* per) {
+  const uint64_t cap = pl.maxb;
   uint64_t nb = (nblocks + cap - 1) / cap;
-  if (overlap) nb = std::max<uint64_t>(nb, want);
   nb = std::max<uint64_t>(1, std::min<uint64_t>(nb, nblocks));
   *nbatch = nb;
   *per = nblocks ? (nblocks + nb - 1) / nb : 0;
   if (*per) *nbatch = (nblocks + *per - 1) / *per;
 }
-uint64_t feed_stage_count(const frbch_handle* h, uint64_t nblocks, bool overlap) {
+uint64_t feed_stage_count(const frbch_handle* h, uint64_t nblocks) {
   uint64_t nbatch = 0, per = 0;
-  plan_batches(h->pl, nblocks, overlap, overlap ? overlap_batches(h, nblocks) : 1, &nbatch, &per);
+  plan_batches(h->pl, nblocks, &nbatch, &per);
   return nblocks ? nbatch : 0;
 }
 
-// one run of blocks; *rows_written is the running row count of the call (rows land behind those already written)
+// one run of blocks; *rows_written is the running row count of the call (rows land behind those already written).  Every stage
+// goes to `s`; on a scan's chain the digitiser of a completed interval may go to the chain's second stream beside the next K1.
 int engine_feed_run(frbch_handle* h, const uint8_t* d_frames, uint32_t frame_bytes, uint32_t header_bytes,
                     uint64_t payload_off, uint64_t nblocks, uint8_t* d_out, size_t cap, uint64_t* rows_written,
-                    dev_stream_t s, const uint32_t* d_fbad, Chain* outer) {
+                    dev_stream_t s, const uint32_t* d_fbad, Chain* chain) {
   const Plan& pl = h->pl;
   if (!nblocks) return FRBCH_OK;
-  // own chain unless the caller brought one; blocks that touch flagged frames run in queue order on the caller's stream
-  Chain own;
-  Chain* ch = outer;
-  const bool may_overlap = !d_fbad && overlap_usable(h);
-  Lanes* ln = nullptr;
-  if (!ch && may_overlap) ln = get_lanes(h->device, overlap_front_cus(h), overlap_mode(h) == 3);
-  if (!ch && overlap_mode(h) != 1) ln = nullptr;     // (mode 2 only overlaps across the IFs of a scan: the caller's chain)
-  const bool overlap = ch ? (ch->ln != nullptr && ch->mode == 1) : (ln != nullptr);   // batches cut for two regions in flight
   uint64_t nbatch = 0, per = 0;
-  plan_batches(pl, nblocks, overlap, overlap ? overlap_batches(h, nblocks) : 1, &nbatch, &per);
-  if (!ch) {
-    chain_begin(&own, h, s, nbatch >= 2 ? ln : nullptr, (uint32_t)nbatch, pl.nif < 4, 1);
-    ch = &own;
+  plan_batches(pl, nblocks, &nbatch, &per);
+  if (!h->spill_ev_made) {
+    (void)dev_event_create_sync(&h->spill_ev);
+    h->spill_ev_made = true;
   }
-  const uint32_t nreg = (uint32_t)std::min<uint64_t>(8, std::max<uint64_t>(1, pl.maxb / per));
-  if (!h->region_ev_made) {
-    for (auto& e : h->region_ev) (void)dev_event_create_sync(&e);
-    h->region_ev_made = true;
-  }
-  const uint64_t spill_blk = (uint64_t)(pl.c2 / pl.g) * pl.gs;      // cf per block of the spill
   int rc = FRBCH_OK;
   // a batch deferred by the two-pass rescale whose interval goes on: its float rows are written NOW, before the front stage of
   // the next batch overwrites the spill they come from
-  if (h->deferred.active && !fused_ok(h)) rc = deferred_materialise(h, ch->user);
+  if (h->deferred.active && !fused_ok(h)) rc = deferred_materialise(h, s);
   for (uint64_t b0 = 0; b0 < nblocks && !rc; b0 += per) {
     const uint32_t nb = (uint32_t)std::min<uint64_t>(per, nblocks - b0);
-    const uint32_t reg = (ch->ln && ch->mode == 1) ? (h->next_region++ % nreg) : 0;
-    const uint64_t rb0 = (uint64_t)reg * per;                        // first block of the region inside the work buffers
     KParams p = base_params(h);
-    p.spill += rb0 * spill_blk;
-    p.s_dc += rb0 * pl.c2;
-    p.p0 += rb0 * pl.c2;
-    h->stg_cur = h->stg ? h->stg + rb0 * pl.block_payload_bytes : nullptr;
     p.fbad = d_fbad;
     p.fbad_frame0 = 0;
     p.frames = d_frames;
@@ -448,21 +300,16 @@ int engine_feed_run(frbch_handle* h, const uint8_t* d_frames, uint32_t frame_byt
     p.payload_bytes = frame_bytes - header_bytes;
     p.payload_off = payload_off + b0 * pl.block_stride_bytes;
     // ---- front: K0, K1, Kc --------------------------------------------------------------------------------------
-    const dev_stream_t sf = chain_front_stream(ch);
-    const bool region_wait = h->region_busy[reg] && (ch->ln || outer);   // the back stage that read this region last must be through
-    if (region_wait) (void)dev_stream_wait(sf, h->region_ev[reg]);
-    h->region_busy[reg] = false;
-    const dev_stream_t sk = chain_k0_stream(ch, sf);
-    if (sk != sf && region_wait) (void)dev_stream_wait(sk, h->region_ev[reg]);
-    h->lane_cus = (ch->ln && (sf == ch->ln->f || (ch->mode == 3 && ch->front_beside_q))) ? ch->ln->ncu_f : 0;
-    rc = launch_front(h, p, nb, sf, sk);
+    // on a scan's chain the back stage that read the spill last (maybe on the stream of an earlier call) must be through
+    if (h->spill_busy && chain) (void)dev_stream_wait(s, h->spill_ev);
+    h->spill_busy = false;
+    h->lane_cus = chain ? chain_front(chain) : 0;
+    rc = launch_front(h, p, nb, s);
     h->lane_cus = 0;
     if (rc) break;
-    chain_front_done(ch, sf);
     // ---- back: K2 (+ statistics and digitiser of a completed interval) ------------------------------------------
-    const dev_stream_t sb = chain_back_stream(ch);
-    if (h->quant_busy) {   // a digitiser of this handle on the back lane still reads the power buffer
-      (void)dev_stream_wait(sb, h->quant_ev);
+    if (h->quant_busy) {   // a digitiser of this handle on the scan's second stream still reads the power buffer
+      (void)dev_stream_wait(s, h->quant_ev);
       h->quant_busy = false;
     }
     const uint64_t rows = (uint64_t)nb * pl.rows_per_block;
@@ -471,7 +318,7 @@ int engine_feed_run(frbch_handle* h, const uint8_t* d_frames, uint32_t frame_byt
       p.out_mode = FRBCH_OUT_CODES;
       p.code_out = d_out;
       p.row0 = *rows_written;
-      rc = launch_back(h, p, nb, sb);
+      rc = launch_back(h, p, nb, s);
       if (rc) break;
       *rows_written += rows;
       h->rows_out += rows;
@@ -480,12 +327,12 @@ int engine_feed_run(frbch_handle* h, const uint8_t* d_frames, uint32_t frame_byt
       // ---- two-pass rescale: statistics-only pass now, the digitising pass once the interval is complete ----------------------
       rc = ensure_partial(h);
       if (rc) break;
-      if (dev_memset(h->partial, 0, (size_t)h->fused_chunks * pl.ncol * 2 * sizeof(double), sb) != 0) { rc = fail(h, FRBCH_E_DEVICE, "clear partial sums"); break; }
+      if (dev_memset(h->partial, 0, (size_t)h->fused_chunks * pl.ncol * 2 * sizeof(double), s) != 0) { rc = fail(h, FRBCH_E_DEVICE, "clear partial sums"); break; }
       p.out_mode = FRBCH_OUT_STATS;
       p.row0 = 0;
       p.stat_partial = h->partial;
       p.stat_limit = pl.interval_rows;
-      rc = launch_back(h, p, nb, sb);
+      rc = launch_back(h, p, nb, s);
       if (rc) break;
       h->fused_rows = std::min<uint64_t>(rows, pl.interval_rows);
       h->fused_valid = true;
@@ -494,13 +341,13 @@ int engine_feed_run(frbch_handle* h, const uint8_t* d_frames, uint32_t frame_byt
       h->deferred.nb = nb;
       h->deferred.rows = rows;
       if (rows >= pl.interval_rows) {   // the interval ends inside this batch: offset / scale now, then every row of the batch
-        rc = run_stats(h, pl.interval_rows, sb);
+        rc = run_stats(h, pl.interval_rows, s);
         if (rc) break;
         h->have_scale = true;
         h->scale_frozen = true;        // (-c: twopass_usable)
         h->fused_rows = 0;
         h->fused_valid = false;
-        rc = deferred_emit(h, d_out, cap, rows_written, sb);
+        rc = deferred_emit(h, d_out, cap, rows_written, s);
         if (rc) break;
       }
     } else {
@@ -511,7 +358,7 @@ int engine_feed_run(frbch_handle* h, const uint8_t* d_frames, uint32_t frame_byt
       p.power_out = h->powbuf;
       p.row0 = h->pow_rows;
       if (h->pow_rows == 0 && h->fused_chunks) {   // an interval starts here: K2 can sum it while writing it
-        if (dev_memset(h->partial, 0, (size_t)h->fused_chunks * pl.ncol * 2 * sizeof(double), sb) != 0) { rc = fail(h, FRBCH_E_DEVICE, "clear partial sums"); break; }
+        if (dev_memset(h->partial, 0, (size_t)h->fused_chunks * pl.ncol * 2 * sizeof(double), s) != 0) { rc = fail(h, FRBCH_E_DEVICE, "clear partial sums"); break; }
         h->fused_rows = 0;
         h->fused_valid = true;
       }
@@ -519,7 +366,7 @@ int engine_feed_run(frbch_handle* h, const uint8_t* d_frames, uint32_t frame_byt
         p.stat_partial = h->partial;
         p.stat_limit = pl.interval_rows;
       }
-      rc = launch_back(h, p, nb, sb);
+      rc = launch_back(h, p, nb, s);
       if (rc) break;
       if (h->fused_valid) {
         if (p.stat_partial) {
@@ -530,18 +377,15 @@ int engine_feed_run(frbch_handle* h, const uint8_t* d_frames, uint32_t frame_byt
         }
       }
       h->pow_rows += rows;
-      while (!rc && !fused_ok(h) && h->pow_rows >= pl.interval_rows) rc = finalize_interval(h, pl.interval_rows, d_out, cap, rows_written, sb, ch);
+      while (!rc && !fused_ok(h) && h->pow_rows >= pl.interval_rows) rc = finalize_interval(h, pl.interval_rows, d_out, cap, rows_written, s, chain);
       if (rc) break;
     }
-    chain_back_done(ch, sb);
-    if (ch->ln || outer) {
-      dev_event_record(h->region_ev[reg], sb);
-      h->region_busy[reg] = true;
+    if (chain) {
+      dev_event_record(h->spill_ev, s);
+      h->spill_busy = true;
     }
     h->blocks_done += nb;
   }
-  h->stg_cur = nullptr;
-  if (ch == &own) chain_end(&own);
   return rc;
 }
 

@@ -20,16 +20,6 @@ namespace fast {
 
 #define FI __device__ __forceinline__
 
-// Timing-only ablations (results are WRONG when set), the K1 priority-schedule knob and the phase stamps exist only in
-// builds with -DFRBCH_EXPERIMENTS (profiling notes in DESIGN.md); the product build compiles them out.
-#ifdef FRBCH_EXPERIMENTS
-#define FRBCH_DBG(p, m) ((p).dbg & (m))
-#define FRBCH_STAG(p) ((p).stag)
-#else
-#define FRBCH_DBG(p, m) 0u
-#define FRBCH_STAG(p) 3   // the halves of a K1 workgroup swap priority behind the forward passes (measured best)
-#endif
-
 constexpr float kC1 = 0.92387953251128674f;  // cos(pi/8)
 constexpr float kS1 = 0.38268343236508977f;  // sin(pi/8)
 constexpr float kC2 = 0.70710678118654752f;  // cos(pi/4)
@@ -543,10 +533,8 @@ __global__ void __launch_bounds__(1024) frbch_k1_fast(KParams p) {
     if (tid < M * 16) tl[tid] = p.ftw2_r[tid];
     tw2 = tl;     // (visible after the first barrier inside fwd_passes)
   }
-  if (!FRBCH_DBG(p, 1u)) {   // (timing-only ablation 1: no transforms)
-    if constexpr (PRE_TW) fwd_passes_t<LOG2M>(v, s, q, Tw1Reg{t1r}, tw2);
-    else fwd_passes<LOG2M>(v, s, q, p.ftw1_r, tw2);
-  }
+  if constexpr (PRE_TW) fwd_passes_t<LOG2M>(v, s, q, Tw1Reg{t1r}, tw2);
+  else fwd_passes<LOG2M>(v, s, q, p.ftw1_r, tw2);
 
   // ---- side product S[n1] = A[0]; fractional delay A[k] *= exp(-2 pi i n1 k / N) ----------------
   if (q == 0) p.s_dc[(uint64_t)blk * p.c2 + n1] = v[0];
@@ -558,9 +546,8 @@ __global__ void __launch_bounds__(1024) frbch_k1_fast(KParams p) {
   }
   // coherent (-F C:D): the dedispersion kernel depends on (channel, fine bin), so the inverse transform waits for K3;
   // the delayed spectrum is spilled as it lies: register kc of thread q = position kc*TPS + q (bin ka + 16 kb + 16M kc)
-  if (!p.coherent && !FRBCH_DBG(p, 1u)) bwd_passes<LOG2M>(v, s, q, p.ftw1_r, tw2);
+  if (!p.coherent) bwd_passes<LOG2M>(v, s, q, p.ftw1_r, tw2);
   __syncthreads();  // every thread holds its outputs; LDS may be re-used
-  if (FRBCH_DBG(p, 2u) && v[3].x != 123.456f) return;   // timing-only ablation 2: no transpose, no stores
 
   // ---- transpose through LDS into [t][gi] rows (slot swizzled), then one contiguous burst -------
   {
@@ -656,8 +643,6 @@ __global__ void __launch_bounds__(NT, (LOG2M >= 5 && NT == 512) ? 2 : 1) frbch_k
           ? reinterpret_cast<const cf2*>(p.spill + (uint64_t)blk * ngrp * p.gs +
                                          ((((uint64_t)(t0 >> 3) * ngrp + grp) << 3) + (uint64_t)(t0 & 7)) * G1)
           : reinterpret_cast<const cf2*>(p.spill + ((uint64_t)blk * ngrp + grp) * p.gs + (uint64_t)t0 * G1);
-      if (FRBCH_DBG(p, 16u)) buf[i] = cf2{cf{(float)id, 1.f}, cf{2.f, (float)i}};   // timing-only ablation: no gather
-      else
       buf[i] = src[rem];   // (plain: the 16..128-byte pieces of neighbouring tiles share cache lines -- non-temporal loads were measured 20 % slower)
     }
 #pragma unroll
@@ -681,7 +666,6 @@ __global__ void __launch_bounds__(NT, (LOG2M >= 5 && NT == 512) ? 2 : 1) frbch_k
     tl[tid] = p.ftw2_c[tid];
     tw2 = tl;
   }
-  if (!FRBCH_DBG(p, 64u))   // (timing-only ablation 64: no transform)
   fwd_passes<LOG2M>(v, s, q, p.ftw1_c, tw2);
 
   // ---- mirror exchange: bins k' = 2C-1-k (k' >= C) live in registers kc >= 8 of thread TPS-1-q --
@@ -778,7 +762,6 @@ __global__ void __launch_bounds__(NT, (LOG2M >= 5 && NT == 512) ? 2 : 1) frbch_k
   __syncthreads();
 
   // ---- A8 tscrunch + (float power | A9 rescale + A10 digitise), 4 channels per thread-task -------
-  if (FRBCH_DBG(p, 32u) && pw[tid0] != 123.456f) return;   // timing-only ablation: no output sweep
   {
     const int tid = tid0;
     const int Te = T > TT ? TT : T;             // rows of the tile that add up to one output row
@@ -1195,18 +1178,6 @@ __global__ void __launch_bounds__(256) frbch_k0_stage(KParams p) {
   }
 }
 
-// diagnostic phase stamps (experiment builds, FRBCH_STAMPS=<file>): one s_memtime per phase boundary of one block, per wave
-#ifdef FRBCH_EXPERIMENTS
-#define K1_STAMP(i)                                                                                         \
-  if (p.stamps != nullptr) {                                                                                \
-    __builtin_amdgcn_sched_barrier(0);                                                                      \
-    if (blk == (int)blockIdx.y + 8 * (int)gridDim.y && lane == 0)                                           \
-      p.stamps[((size_t)blockIdx.x * NW + wave) * 16 + (i)] = __builtin_amdgcn_s_memtime();                 \
-    __builtin_amdgcn_sched_barrier(0);                                                                      \
-  }
-#else
-#define K1_STAMP(i)
-#endif
 // NW waves per workgroup, WPS waves per sequence: G = (NW/WPS)*SPW branches per workgroup.  The
 // spill layout group is GL = p.g >= G branches; a workgroup fills its G*8-byte share of every row.
 // STG: the input comes corner-turned from frbch_k0_stage (compile-time: a run-time choice between the two fetches
@@ -1218,7 +1189,7 @@ __global__ void __launch_bounds__(256) frbch_k0_stage(KParams p) {
 // into the stage looks its frame up in the bitmap and leaves a flag per row beside the stage; the unpack reads samples of flagged
 // rows as 0 (the level table's mean), as the generic K1 does per sample.  Round 3 sent such blocks to the generic radix-2 K1.
 template <int LOG2M, int NW, int WPS, bool STG = false, bool COH = false, bool MSK = false>
-__global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((NW >= 16 || (WPS > 1 && LOG2M == 3)) ? 4 : 2))) frbch_k1_wave(KParams p) {
+__global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : 2)) frbch_k1_wave(KParams p) {
   static_assert(!MSK || STG, "the frame mask rides on the staged input");
   using GE = GeoW<LOG2M, WPS>;
   constexpr int M = GE::M, R = GE::L, TPS = GE::TPS, LPS = GE::LPS, VT = GE::VT, SPW = GE::SPW;
@@ -1255,11 +1226,11 @@ __global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((NW >= 16 || (WPS 
   // per-branch fractional-delay factors: constant over the blocks of this launch
   // the 16 coarse delay factors of every branch go to the LDS once: the loop body must not issue vector-memory
   // loads (they would queue behind the stores of the previous block)
-  if (tid < G * 16) sigl[tid] = p.td1[(size_t)((FRBCH_DBG(p, 8u)) ? 0 : grp * G + (tid >> 4)) * 16 + (tid & 15)];
+  if (tid < G * 16) sigl[tid] = p.td1[(size_t)(grp * G + (tid >> 4)) * 16 + (tid & 15)];
   if (WPS > 1 && tid < G) paircnt[tid] = 0u;
   PairSync psync{paircnt + seq, 0u, (uint32_t)WPS, lane == 0};
   // (R = 8192, four waves per sequence: the hardware barrier of the eight waves beats the polled counters, K1 1.94 -> 1.84 ms)
-  PairSync* const psp = (WPS > 1 && LOG2M < 5 && !(FRBCH_DBG(p, 256u))) ? &psync : nullptr;   // dbg 256: workgroup barriers between the passes
+  PairSync* const psp = (WPS > 1 && LOG2M < 5) ? &psync : nullptr;
   const cf* sig = sigl + seq * 16;
 
   // A3: frame arithmetic (multiply-shift division) + header strip; RB bytes per n2 row.
@@ -1293,7 +1264,7 @@ __global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((NW >= 16 || (WPS 
 #pragma unroll
     for (int i = 0; i < NROW; ++i) {
       const int row = tid + NT * i;
-      const uint32_t x = (FRBCH_DBG(p, 4u)) ? (uint32_t)(row * RB) : x0 + (uint32_t)p.c * (uint32_t)row;
+      const uint32_t x = x0 + (uint32_t)p.c * (uint32_t)row;
       const uint32_t fr = fastdiv(x, p.div_magic, p.div_shift);
       const uint32_t off = x - fr * p.payload_bytes;
       nxt[i] = *reinterpret_cast<const piece_t*>(p.frames + (size_t)fr * p.frame_bytes + p.header_bytes + off);
@@ -1325,18 +1296,15 @@ __global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((NW >= 16 || (WPS 
   constexpr bool PAIRED = !COH && (LOG2M == 3) && (WPS == 1) && (G == 8) && (TPS * G == NW * 128);
   constexpr bool AHEAD2 = STG && PAIRED;
 
-  const bool dbg_notw = FRBCH_DBG(p, 1u);
-  const int qtw = dbg_notw ? -ql : 0;   // ablation: every lane reads table column 0 (no real traffic)
-  const cf* tw1 = p.ftw1_r + qtw;
-  const cf* tw2 = p.ftw2_r - (dbg_notw ? (ql & 15) : 0);
-  const int imgflip = (FRBCH_DBG(p, 2048u)) ? (G / 2) : 0;   // experiment: swap the LDS images of the two halves of the workgroup
-  cf* s = lds + (seq ^ imgflip) * SEQ;
+  const cf* tw1 = p.ftw1_r;
+  const cf* tw2 = p.ftw2_r;
+  cf* s = lds + seq * SEQ;
   RegTw<LOG2M, VT> rtw;
   rtw.load(tw1, tw2, ql, LPS, TPS);
   if constexpr (LOG2M >= 5) {   // the radix-32 twiddles behind the arrival counters (visible after the barrier in front of the loop)
     cf* tl = reinterpret_cast<cf*>(paircnt + ((G + 1) & ~1));
     for (int i = tid; i < M * 16; i += NT) tl[i] = p.ftw2_r[i];
-    rtw.tl = tl + (ql & 15) - (dbg_notw ? (ql & 15) : 0);
+    rtw.tl = tl + (ql & 15);
   }
   // The fine part of the fractional delay, exp(-2 pi i n1 k0 / N) for bin k = k0 + 16M kc with k0 = ka + 16 kb, is
   // A^ka B^kb (A = exp(-2 pi i n1 / N), B = A^16): a factor per OUTPUT INDEX of the first and of the middle forward pass,
@@ -1376,7 +1344,7 @@ __global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((NW >= 16 || (WPS 
   {
     constexpr int PPW0 = PAIRED ? 128 / G : 64 / G, NSW0 = TPS / (NW * PPW0);
     const int pp0 = (wave * NSW0) * PPW0 + lane / (PAIRED ? G / 2 : G);
-    const cf* twp = tw1 - qtw + (dbg_notw ? 0 : pp0);
+    const cf* twp = tw1 + pp0;
 #pragma unroll
     for (int j = 1; j < 4; ++j) {
       tlo0[j] = twp[j * TPS];
@@ -1389,20 +1357,6 @@ __global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((NW >= 16 || (WPS 
   __syncthreads();   // stage holds the rows of the first block
 
   for (int blk = blockIdx.y; blk < nblk; blk += gridDim.y) {
-    if constexpr (WPS > 1 && LOG2M == 3) {
-      // 128-VGPR variants (16 waves per CU): the loop-invariant twiddle bases are laundered every trip so that no
-      // product derived from them is hoisted out of the loop (that is what spilled under the cap)
-#pragma unroll
-      for (int vt = 0; vt < VT; ++vt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          asm volatile("" : "+v"(rtw.lo[vt][j].x), "+v"(rtw.lo[vt][j].y), "+v"(rtw.hi[vt][j].x), "+v"(rtw.hi[vt][j].y),
-                            "+v"(rtw.b2[vt][j].x), "+v"(rtw.b2[vt][j].y));
-        }
-#pragma unroll
-      for (int j = 1; j < 4; ++j)
-        asm volatile("" : "+v"(tlo0[j].x), "+v"(tlo0[j].y), "+v"(thi0[j].x), "+v"(thi0[j].y));
-    }
     const bool more = blk + (int)gridDim.y < nblk;
     // Placement of the vector-memory instructions of a trip (phase stamps, tools_stamps.py): the CU needs ~11000
     // cycles into the next trip to drain the 128 KB of row stores, its vector-memory queue is in order, and a load
@@ -1417,8 +1371,7 @@ __global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((NW >= 16 || (WPS 
     // the workgroup (waves NW/2..) loses every phase (phase stamps: it reaches the first barrier ~3000 cycles after
     // the first half, which waits).  The halves take turns at priority 1, so that both arrive together.
     const bool young = wave >= NW / 2;
-    if (FRBCH_STAG(p) & 1) { if (young) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
-    K1_STAMP(0)
+    if (young) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
 
     // ---- A4: 2-bit unpack (16-entry LUT: nibble -> both polarisations) --------------------------
     cf v[VT][16];
@@ -1439,7 +1392,6 @@ __global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((NW >= 16 || (WPS 
         }
       }
     }
-    K1_STAMP(1)
     if constexpr (LOG2M >= 5) {
       fwd_passes_w<LOG2M, WPS, VT, true, PairSync>(v, s, ql, tw1, tw2, &rtw, psp);
     } else {
@@ -1453,8 +1405,7 @@ __global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((NW >= 16 || (WPS 
         }
       fwd_passes_w<LOG2M, WPS, VT, true, PairSync>(v, s, ql, tw1, tw2, &rtf, psp);
     }
-    K1_STAMP(2)
-    if (FRBCH_STAG(p) & 2) { if (young) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(1); }
+    if (young) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(1);
     const cf sdc = v[0][0];
     if constexpr (LOG2M >= 5) {                    // whole fine factor here (nothing folded into the forward twiddles)
 #pragma unroll
@@ -1466,7 +1417,6 @@ __global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((NW >= 16 || (WPS 
 #pragma unroll
       for (int vt = 0; vt < VT; ++vt) v[vt][kc] = (LOG2M >= 5) ? mul(mul(v[vt][kc], sg), rho[vt]) : mul(v[vt][kc], sg);
     }
-    K1_STAMP(3)
     if constexpr (COH) {
       if (more) fetch(blk + gridDim.y);
       if constexpr (WPS > 1) { if (psp) (*psp)(); else __syncthreads(); }   // the partner wave has read its rows of the image
@@ -1480,9 +1430,7 @@ __global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((NW >= 16 || (WPS 
       auto mid = [&]() { if constexpr (!AHEAD2) { if (more) fetch(blk + gridDim.y); } };
       bwd_passes_w<LOG2M, WPS, VT, false, true, decltype(mid), PairSync>(v, s, ql, tw1, tw2, &rtw, mid, psp);
     }
-    K1_STAMP(4)
     __syncthreads();  // all sequences of the workgroup are in the LDS, one pass short of natural order
-    K1_STAMP(5)
     // every wave is past the unpack: refill the stage with the next block's rows now, i.e. BEFORE this
     // block's stores are queued (vmcnt retires in order: a later wait for these loads would drain the stores)
     if (more) refill();
@@ -1499,10 +1447,9 @@ __global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((NW >= 16 || (WPS 
       const int pp = wave * PPW + pl;
       const int GL = p.g;
       const int lgrp = (grp * G) / GL, sub = (grp * G) % GL;
-      cf* dst = p.spill + ((uint64_t)((FRBCH_DBG(p, 512u)) ? 0 : blk) * (uint64_t)(p.c2 / GL) + lgrp) * p.gs + sub;   // wave-uniform
-      const cf* sa = lds + ((2 * g2) ^ imgflip) * SEQ + pidx(pp);
+      cf* dst = p.spill + ((uint64_t)blk * (uint64_t)(p.c2 / GL) + lgrp) * p.gs + sub;   // wave-uniform
+      const cf* sa = lds + (2 * g2) * SEQ + pidx(pp);
       const cf* sb = sa + SEQ;
-      K1_STAMP(6)
       cf ua[16], ub[16];
 #pragma unroll
       for (int ka = 0; ka < 16; ++ka) {
@@ -1517,7 +1464,7 @@ __global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((NW >= 16 || (WPS 
       }
       Dft<16, +1>::run(ua);
       Dft<16, +1>::run(ub);
-      if (!(FRBCH_DBG(p, 2u)) || ua[0].x == 123.456f) {
+      {
         // 16-byte stores: the 64 lanes of one instruction cover 16 rows x 64 bytes = 1 KB contiguous; half as many
         // entries in the CU's vector-memory queue as with one branch per lane
         if (p.tile_major == 2) {   // spill [blk][t/2][group][t%2][GL]: the K2 tile of two time samples is one contiguous run
@@ -1533,8 +1480,6 @@ __global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((NW >= 16 || (WPS 
         for (int a = 0; a < 16; ++a) store_spill(reinterpret_cast<cf2*>(dst + (size_t)a * (size_t)(TPS * GL) + loff), ua[a], ub[a]);
         }
       }
-      K1_STAMP(7)
-      K1_STAMP(8)
     } else {
       constexpr int PPW = 64 / G;                       // time indices per wave and sweep
       constexpr int NSW = TPS / (NW * PPW);             // sweeps per wave
@@ -1542,7 +1487,7 @@ __global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((NW >= 16 || (WPS 
       const int gi = lane & (G - 1), pl = lane / G;
       const int GL = p.g;
       const int lgrp = (grp * G) / GL, sub = (grp * G) % GL;
-      cf* dst = p.spill + ((uint64_t)((FRBCH_DBG(p, 512u)) ? 0 : blk) * (uint64_t)(p.c2 / GL) + lgrp) * p.gs + sub;   // wave-uniform
+      cf* dst = p.spill + ((uint64_t)blk * (uint64_t)(p.c2 / GL) + lgrp) * p.gs + sub;   // wave-uniform
       const cf* sg_ = lds + gi * SEQ;
       // vmcnt retires loads and stores in issue order: a wait for a load issued after a store would also
       // wait for that store to complete.  So the twiddles of the NEXT sweep are fetched and drained before
@@ -1556,12 +1501,8 @@ __global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((NW >= 16 || (WPS 
         tlo[j] = tlo0[j];
         thi[j] = thi0[j];
       }
-      K1_STAMP(6)
-      if (FRBCH_STAG(p) & 4) { if (young) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
-      if (FRBCH_STAG(p) & 16) __builtin_amdgcn_s_setprio(0);
 #pragma unroll 1
       for (int sw = 0; sw < NSW; ++sw) {
-        if ((FRBCH_STAG(p) & 8) && sw == NSW / 2) { if (young) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(1); }
         const int pp = (wave * NSW + sw) * PPW + pl;
         cf u[16];
 #pragma unroll
@@ -1581,7 +1522,7 @@ __global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((NW >= 16 || (WPS 
             thi[j] = mul(thi[j], p.rot6[2 + j]);
           }
         }
-        if (!(FRBCH_DBG(p, 2u)) || u[0].x == 123.456f) {
+        {
           // 8-byte stores, 512 contiguous bytes per instruction.  Pairing lanes (v_permlane32_swap) into 16-byte
           // stores was measured slower (2.26 vs 2.05 ms): the limit is bytes per clock on the CU's write path
           // (~16 B/clk, the same with a cache-resident target), not the number of store instructions.
@@ -1599,270 +1540,20 @@ __global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((NW >= 16 || (WPS 
           for (int a = 0; a < 16; ++a) store_spill(dst + (size_t)a * (size_t)(TPS * GL) + loff, u[a]);
           }
         }
-        K1_STAMP(7 + (sw & 1))
       }
     }
     // (behind the row stores: in front of the sweep loop the compiler drains vmcnt, and a store waited for there costs
     // its round trip to the L2 in every block)
     if (ql == 0) p.s_dc[(uint64_t)blk * p.c2 + n1] = sdc;
-    K1_STAMP(9)
     __syncthreads();  // the LDS images are consumed: the next block may overwrite them
-    K1_STAMP(10)
   }
 }
-
-#ifdef FRBCH_EXPERIMENTS   // measured 14 % slower than frbch_k1_wave<3,8,1> (profiles/NOTES.md): kept for the record, not in the product library
-// =================================================================================================
-// K1 "split" (R = 2048, staged input): the same transform as frbch_k1_wave<3,8,1>, arranged for SIXTEEN independent waves
-// per CU (four per SIMD, 128 VGPRs) instead of eight.  One wave is bound by its own issue interval (one VALU
-// instruction per ~4.5 cycles whatever its SIMD neighbour does, DESIGN.md section 8) and two waves per SIMD leave half
-// the VALU slots and most LDS latencies uncovered; more waves per sequence needed barriers between the passes.  Here a
-// branch is split by BIN PARITY (decimation in frequency, one level): with a[n], n < R, H = R/2,
-//     A[2m]   = FFT_H( a[n] + a[n+H] )[m]                  (wave "even")
-//     A[2m+1] = FFT_H( (a[n] - a[n+H]) W_R^n )[m]          (wave "odd")
-// the delay factor is diagonal in the bins, and  w[t] = E[t] + W_R^-t O[t],  w[t+H] = E[t] - W_R^-t O[t]  with E, O the
-// backward half transforms: the two waves of a branch share NOTHING until the last pass, which reads all images behind
-// the workgroup barrier anyway.  Each wave runs wave-private 1024-point transforms (radix 16 x 4 x 16, 16 points per
-// lane, 9-KB image): 16 images = 148 KB.  Costs: both waves unpack both halves of the rows, ~15 % more VALU work in
-// total (W_32 rotations, the final radix-2 across lane pairs).
-// Last pass: lane = (branch gi, parity, time index pp): 16 points of E (or O W_R^-t) at t = a*64 + pp; the partner
-// parity sits 8 lanes away in the same DPP row; lane (gi, 0, pp) stores w[a*64+pp], lane (gi, 1, pp) w[H + a*64+pp]:
-// a store instruction covers 2 x 2 tile-major lines of 128 bytes.  Images are SEQ = 1154 cf apart, parity-major:
-// 16 bytes askew per image in the 256-byte bank row, so the 32 lanes of a ds_read_b64 group (8 branches x 2 parities x
-// 2 time indices) hit 32 distinct 8-byte slots.
-// =================================================================================================
-namespace split {
-constexpr int R = 2048, H = 1024, TPS = 64, G = 8, NT = 1024, RB = 4;
-constexpr int SEQ = H + H / 8 + 2;       // cf per image
-constexpr int KS = TPS + TPS / 8;        // cf between the rows ka of an image (as in the wave passes)
-constexpr size_t lds_bytes() { return (size_t)2 * G * SEQ * sizeof(cf) + (size_t)R * RB + (16 + G * 16 + 32) * sizeof(cf); }
-}  // namespace split
-
-// twiddle of row ka from the per-lane bases: plain W^(j x) in lo, and W^(4 i x) E, W^(j x) E, E in hip / lop / ex with E the
-// extra per-lane factor (1 in the even half, W_R^x in the odd one)
-FI cf split_tw(int ka, const cf (&lo)[4], const cf (&lop)[4], const cf (&hip)[4], cf ex) {
-  const int i = ka >> 2, j = ka & 3;
-  if (i == 0) return j == 0 ? ex : lop[j];
-  if (j == 0) return hip[i];
-  return mul(hip[i], lo[j]);
-}
-
-__global__ void __launch_bounds__(1024, 1) frbch_k1_split(KParams p) {
-  using namespace split;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  cf* lds = reinterpret_cast<cf*>(smem);
-  unsigned char* stage = smem + (size_t)2 * G * SEQ * sizeof(cf);
-  cf* lut16 = reinterpret_cast<cf*>(stage + (size_t)R * RB);
-  cf* sigl = lut16 + 16;                 // [G][16] coarse delay factors of this workgroup's branches
-  cf* rtab = sigl + G * 16;              // [2][16] W_32^(-a) for the odd half, 1 for the even one
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int gi = wave >> 1, par = wave & 1;
-  const int q = lane;
-  const int ngrp_ = gridDim.x;           // XCD-aware group mapping as in frbch_k1_wave
-  const int grp = (ngrp_ % 8 == 0) ? (int)(blockIdx.x % 8) * (ngrp_ / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
-  const int n1 = grp * G + gi;
-  const int nblk = (int)p.nblk;
-
-  fill_lut16(lut16, p, tid);
-  if (tid < G * 16) sigl[tid] = p.td1[(size_t)(grp * G + (tid >> 4)) * 16 + (tid & 15)];
-  if (tid < 32) {                        // exp(+2 pi i a / 32) = conj of table entry exp(-2 pi i (8a) 8 / 2048)
-    const cf w = p.ftw1_r[8 * (R / 16) + 8 * (tid & 15)];
-    rtab[tid] = (tid >> 4) ? cf{w.x, -w.y} : cf{1.f, 0.f};
-  }
-
-  // ---- loop-invariant per-lane factors of the wave-private passes (thread q of this wave's half transform) -----
-  cf lo[4], lop[4], hip[4], b2a, b2b, ex;
-  {
-    ex = par ? p.ftw1_r[(R / 16) + q] : cf{1.f, 0.f};               // W_R^q
-#pragma unroll
-    for (int j = 1; j < 4; ++j) {
-      lo[j] = p.ftw1_h[j * TPS + q];
-      lop[j] = mul(lo[j], ex);
-      hip[j] = mul(p.ftw1_h[4 * j * TPS + q], ex);
-    }
-    lo[0] = lop[0] = hip[0] = cf{1.f, 0.f};
-    b2a = p.ftw2_h[1 * 16 + (q & 15)];
-    b2b = p.ftw2_h[2 * 16 + (q & 15)];
-  }
-  const cf rho = p.td2[(uint64_t)n1 * (R / 16) + (2 * ((q >> 2) + 16 * (q & 3)) + par)];
-  const cf* sig = sigl + gi * 16;
-  cf* s = lds + (par * G + gi) * SEQ;
-
-  // ---- ... and of the last pass: lane = (branch fgi, parity fpar, time index pp) ------------------------------------
-  const int fgi = lane & 7, fpar = (lane >> 3) & 1;
-  const int pp = wave * 4 + ((lane >> 5) << 1) + ((lane >> 4) & 1);
-  cf flo[4], flop[4], fhip[4], fex;
-  {
-    fex = fpar ? p.ftw1_r[(R / 16) + pp] : cf{1.f, 0.f};            // W_R^pp
-#pragma unroll
-    for (int j = 1; j < 4; ++j) {
-      flo[j] = p.ftw1_h[j * TPS + pp];
-      flop[j] = mul(flo[j], fex);
-      fhip[j] = mul(p.ftw1_h[4 * j * TPS + pp], fex);
-    }
-    flo[0] = flop[0] = fhip[0] = cf{1.f, 0.f};
-  }
-  const float fsgn = fpar ? -1.0f : 1.0f;
-  const cf* simg = lds + (fpar * G + fgi) * SEQ + pidx(pp);
-  const cf* rt = rtab + fpar * 16;
-
-  // staged input (frbch_k0_stage): the R*RB = 8192 bytes of this workgroup and block are contiguous, in stage order
-  uint2 nxtc = make_uint2(0u, 0u);
-  auto fetch = [&](int blk) {
-    nxtc = *reinterpret_cast<const uint2*>(p.stg + ((size_t)blk * gridDim.x + grp) * (size_t)(R * RB) + (size_t)tid * 8);
-  };
-  auto refill = [&]() { *reinterpret_cast<uint2*>(stage + (size_t)tid * 8) = nxtc; };
-  fetch(blockIdx.y);
-  refill();
-  if ((int)blockIdx.y + (int)gridDim.y < nblk) fetch(blockIdx.y + gridDim.y);   // the second block's rows wait in registers
-  __syncthreads();
-
-  const int GL = p.g;
-  const uint32_t ng = (uint32_t)(p.c2 / GL);
-  const int lgrp = (grp * G) / GL, sub = (grp * G) % GL;
-
-  for (int blk = blockIdx.y; blk < nblk; blk += gridDim.y) {
-    // the loop-invariant bases are laundered every trip so that no product derived from them is hoisted out of the loop
-    // (that is what spills under the 128-VGPR cap)
-#pragma unroll
-    for (int j = 1; j < 4; ++j) {
-      asm volatile("" : "+v"(lo[j].x), "+v"(lo[j].y), "+v"(lop[j].x), "+v"(lop[j].y), "+v"(hip[j].x), "+v"(hip[j].y));
-      asm volatile("" : "+v"(flo[j].x), "+v"(flo[j].y), "+v"(flop[j].x), "+v"(flop[j].y), "+v"(fhip[j].x), "+v"(fhip[j].y));
-    }
-    asm volatile("" : "+v"(b2a.x), "+v"(b2a.y), "+v"(b2b.x), "+v"(b2b.y));
-    const bool more = blk + (int)gridDim.y < nblk;
-
-    // ---- A4: 2-bit unpack of both halves of the rows, first radix-2 level across them ------------------------------
-    cf v[16];
-    {
-      const uint32_t sh = (uint32_t)(gi & 1) << 2;
-      const unsigned char* st = stage + (gi >> 1);
-      const float sg = par ? -1.0f : 1.0f;
-#pragma unroll
-      for (int a = 0; a < 16; ++a) {
-        const uint32_t b0 = FRBCH_DBG(p, 4u) ? (uint32_t)(a + q) : st[(a * TPS + q) * RB];
-        const uint32_t b1 = FRBCH_DBG(p, 4u) ? (uint32_t)(a * 3 + q) : st[(a * TPS + q + H) * RB];
-        const cf x0 = FRBCH_DBG(p, 4u) ? cf{(float)b0, 1.f} : lut16[(b0 >> sh) & 15u], x1 = FRBCH_DBG(p, 4u) ? cf{(float)b1, 2.f} : lut16[(b1 >> sh) & 15u];
-        v[a] = cf{fmaf(x1.x, sg, x0.x), fmaf(x1.y, sg, x0.y)};
-      }
-      if (par) Rot32Loop<-1, 1>::run(v);          // x W_32^a  (the factor W_R^q rides on the pass twiddles)
-    }
-    // ---- forward half transform, wave-private: radix 16 | 4 | 16 --------------------------------------------------
-    Dft<16, -1>::run(v);
-    if (par) v[0] = mul(v[0], ex);
-#pragma unroll
-    for (int ka = 1; ka < 16; ++ka) v[ka] = mul(v[ka], split_tw(ka, lo, lop, hip, ex));
-#pragma unroll
-    for (int ka = 0; ka < 16; ++ka) s[pidx(q) + ka * KS] = v[ka];
-    if (!FRBCH_DBG(p, 2u)) {
-      const int c = q & 15, r = q >> 4;
-      const cf tw3 = mul(b2a, b2b);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int ka = r + 4 * i;
-        cf u[4];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) u[b] = s[ka * KS + b * 18 + c];
-        Dft<4, -1>::run(u);
-        u[1] = mul(u[1], b2a);
-        u[2] = mul(u[2], b2b);
-        u[3] = mul(u[3], tw3);
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) s[ka * KS + kb * 18 + c] = u[kb];
-      }
-    }
-    {
-      const cf2* src = reinterpret_cast<const cf2*>(s + q * 18);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const cf2 t = src[i];
-        v[2 * i] = t.a;
-        v[2 * i + 1] = t.b;
-      }
-    }
-    Dft<16, -1>::run(v);
-    // register kc of thread q holds half-transform bin m = (q >> 2) + 16 (q & 3) + 64 kc, i.e. bin k = 2m + par
-    const cf sdc = v[0];
-#pragma unroll
-    for (int kc = 0; kc < 16; ++kc) v[kc] = mul(mul(v[kc], sig[kc]), rho);
-    // ---- backward half transform, one pass short ---------------------------------------------------------------------
-    Dft<16, +1>::run(v);
-    {
-      cf2* dst = reinterpret_cast<cf2*>(s + q * 18);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) dst[i] = cf2{v[2 * i], v[2 * i + 1]};
-    }
-    if (!FRBCH_DBG(p, 2u)) {
-      const int c = q & 15, r = q >> 4;
-      const cf tw3 = mul(b2a, b2b);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int ka = r + 4 * i;
-        cf u[4];
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) u[kb] = s[ka * KS + kb * 18 + c];
-        u[1] = mulc(u[1], b2a);
-        u[2] = mulc(u[2], b2b);
-        u[3] = mulc(u[3], tw3);
-        Dft<4, +1>::run(u);
-#pragma unroll
-        for (int b = 0; b < 4; ++b) s[ka * KS + b * 18 + c] = u[b];
-      }
-    }
-    __syncthreads();   // all 16 images are in the LDS, one pass short of natural order; every wave is past its unpack
-    if (more) refill();
-    if (blk + 2 * (int)gridDim.y < nblk) fetch(blk + 2 * gridDim.y);
-
-    // ---- last pass: 16 points of E (even lanes) or O W_R^-t (odd lanes), radix 2 across the lane pair, row stores ---
-    {
-      cf u[16];
-#pragma unroll
-      for (int ka = 0; ka < 16; ++ka) u[ka] = simg[ka * KS];
-      if (!FRBCH_DBG(p, 8u)) {
-#pragma unroll
-      for (int ka = 0; ka < 16; ++ka) u[ka] = mulc(u[ka], split_tw(ka, flo, flop, fhip, fex));
-      Dft<16, +1>::run(u);
-#pragma unroll
-      for (int a = 1; a < 16; ++a) u[a] = mul(u[a], rt[a]);
-      }
-      // partner parity: 8 lanes away inside the 16-lane DPP row (row_ror:8).  even lane: E + O', odd lane: E - O'
-#pragma unroll
-      for (int a = 0; a < 16; ++a) {
-        const float px = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, u[a].x), 0x128, 0xF, 0xF, false));
-        const float py = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, u[a].y), 0x128, 0xF, 0xF, false));
-        u[a] = cf{fmaf(u[a].x, fsgn, px), fmaf(u[a].y, fsgn, py)};
-      }
-      if (FRBCH_DBG(p, 1u) && u[0].x != 123.456f) {
-      } else if (p.tile_major == 2) {   // spill [blk][t/2][group][t%2][GL]
-        cf* dstT = p.spill + (uint64_t)blk * (uint64_t)ng * p.gs + (uint64_t)lgrp * (uint64_t)(2 * GL) + sub;
-        const uint32_t loffT = (uint32_t)(fpar * (H / 2) + (pp >> 1)) * (ng * 2u * (uint32_t)GL) + (uint32_t)((pp & 1) * GL + fgi);
-        const size_t strideT = (size_t)(TPS / 2) * (size_t)ng * (size_t)(2 * GL);
-#pragma unroll
-        for (int a = 0; a < 16; ++a) store_spill(dstT + (size_t)a * strideT + loffT, u[a]);
-      } else {                   // slab layout [blk][group][t][GL]
-        cf* dst = p.spill + ((uint64_t)blk * (uint64_t)ng + lgrp) * p.gs + sub;
-        const uint32_t loff = (uint32_t)((fpar * H + pp) * GL + fgi);
-#pragma unroll
-        for (int a = 0; a < 16; ++a) store_spill(dst + (size_t)a * (size_t)(TPS * GL) + loff, u[a]);
-      }
-    }
-    if (par == 0 && q == 0) p.s_dc[(uint64_t)blk * p.c2 + n1] = sdc;
-    __syncthreads();   // the images are consumed: the next block may overwrite them
-  }
-}
-
-#endif   // FRBCH_EXPERIMENTS (frbch_k1_split)
 
 // PM: 2 = Stokes I (-d1), 4 = coherency products (-d4), 0 = the single-product modes decided at run time
 // MSTAT: four products with the rescale statistics summed in the kernel (a thread owns several column groups: 32 more
 // registers, one wave less per SIMD; used only while a rescale interval is being measured)
-#ifndef K2_MSTAT_OCC3
-#define K2_MSTAT_OCC3 0   // A/B knob: three waves per SIMD for the four-product statistics instantiation too (168 registers, 14 spilled)
-#endif
 template <int LOG2M, int NW, int PM, int WPS = 1, bool MSTAT = false>
-__global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((WPS > 1 && LOG2M < 4 && (!MSTAT || K2_MSTAT_OCC3)) ? 3 : 2))) frbch_k2_wave(KParams p) {
+__global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((WPS > 1 && LOG2M < 4 && !MSTAT) ? 3 : 2))) frbch_k2_wave(KParams p) {
   using GE = GeoW<LOG2M, WPS>;
   constexpr int M = GE::M, C2 = GE::L, C = C2 / 2, TPS = GE::TPS, SEQ = GE::SEQ, LPS = GE::LPS, VT = GE::VT, SPW = GE::SPW;
   constexpr int NT = 64 * NW;
@@ -1921,18 +1612,13 @@ __global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((WPS > 1 && LOG2M 
                                                    : ((uint64_t)t_ << lg_g)));
   };
   auto fetch_part = [&](const char* base, int i0, int i1) {   // pieces [i0, i1) of the tile at `base`
-    if (FRBCH_DBG(p, 16u)) {   // timing-only ablation: no global traffic
 #pragma unroll
-      for (int i = 0; i < NLD; ++i) if (i >= i0 && i < i1) buf[i] = cf2{cf{1.f, 2.f}, cf{3.f, 4.f}};
-    } else {
-#pragma unroll
-      for (int i = 0; i < NLD; ++i) {   // streamed once: non-temporal (not at 2C = 8192: neighbouring tiles share the lines)
-        if (i < i0 || i >= i1) continue;
-        nf4 t4;
-        if constexpr (LOG2M >= 5) t4 = *reinterpret_cast<const nf4*>(base + (uint64_t)i * step + voff);
-        else t4 = __builtin_nontemporal_load(reinterpret_cast<const nf4*>(base + (uint64_t)i * step + voff));
-        buf[i] = cf2{cf{t4.x, t4.y}, cf{t4.z, t4.w}};
-      }
+    for (int i = 0; i < NLD; ++i) {   // streamed once: non-temporal (not at 2C = 8192: neighbouring tiles share the lines)
+      if (i < i0 || i >= i1) continue;
+      nf4 t4;
+      if constexpr (LOG2M >= 5) t4 = *reinterpret_cast<const nf4*>(base + (uint64_t)i * step + voff);
+      else t4 = __builtin_nontemporal_load(reinterpret_cast<const nf4*>(base + (uint64_t)i * step + voff));
+      buf[i] = cf2{cf{t4.x, t4.y}, cf{t4.z, t4.w}};
     }
   };
   auto fetch = [&](uint32_t tl) { fetch_part(fetch_base(tl), 0, NLD); };
@@ -2026,7 +1712,7 @@ __global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((WPS > 1 && LOG2M 
   auto pf_hook = [&](int n) { fetch_part(pf_base, 2 * n, 2 * n + 2); };   // hooks 0..6 inside the passes, 7 behind them
 
   float* pw = reinterpret_cast<float*>(lds);
-  if (!(FRBCH_DBG(p, 64u))) {   // (timing-only ablation 64: memory traffic without the transform)
+  {
   cf* s = lds + seq * SEQ;
   cf v[VT][16];
   if constexpr (LOG2M >= 5) {
@@ -2184,7 +1870,6 @@ __global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((WPS > 1 && LOG2M 
       }
       const uint64_t o = (row_base + rr) * (uint64_t)NCOL + col0;
       const uint64_t oc = FRBCH_CODE_INDEX(p.out_pitch, row_base + rr, NIF, prod, cout0);
-      if ((FRBCH_DBG(p, 32u)) && sv[0] != 123.456f) return;
       if constexpr (ROT % 4 == 0) {
         if (om != FRBCH_OUT_FLOAT_POWER && nbit == 8) {
           // 8-bit codes: rescale in the order the row lies in the LDS (= the order of offset / scale: input channels); a flipped
@@ -2240,7 +1925,7 @@ __global__ void __launch_bounds__(64 * NW, (LOG2M >= 5 ? 1 : ((WPS > 1 && LOG2M 
     // the tile's height): the tile's groups of a thread in three sweeps -- every LDS read requested first, then the arithmetic, then
     // the stores.  (The general form below waits for each read where it is issued and walks a chain of mode branches per group: a
     // quarter of this kernel's time with four products.)  Sums run over the time samples in ascending order, as there.
-    const bool sweeps = ROT % 4 == 0 && (lg_t == 0 || (1 << lg_t) == TT) && !(FRBCH_DBG(p, 32u)) &&
+    const bool sweeps = ROT % 4 == 0 && (lg_t == 0 || (1 << lg_t) == TT) &&
                         (om == FRBCH_OUT_FLOAT_POWER || nbit == 8);
     const int nr = lg_t == 0 ? TT : 1;            // output rows of the tile on that path
     if constexpr (MULTI_COLS) {
@@ -2656,13 +2341,10 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 2 : 1) frbch_k3_fast(KParams p
   cf v[16];
 #pragma unroll
   for (int kc = 0; kc < 16; ++kc) v[kc] = base[S2_INDEX(row, kc * TPS + q, R)];   // (plain loads: four channels share every 32 bytes)
-  // requested with the gather instead of where they are used (behind the passes: a whole L2 round trip exposed per tile):
-  // the DC correction of the mirror row, and -- 512-thread workgroups, where the registers allow it -- the last pass's twiddles
+  // requested with the gather instead of where it is used (behind the passes: a whole L2 round trip exposed per tile):
+  // the DC correction of the mirror row
   cf dp = cf{0.f, 0.f};
   if (!(seq & 1)) dp = sub(base[S2_INDEX((m + 1) & (C2 - 1), 0, R)], base[S2_INDEX(m, 0, R)]);
-  constexpr bool PRE_TW = NT == 512;
-  cf t1r[16];
-  if constexpr (PRE_TW) load_tw1<LOG2M>(t1r, p.ftw1_r, q);
   cf* s = lds + seq * SEQ;
   const cf* tw2 = p.ftw2_r;
   if constexpr (LOG2M >= 4) {   // radix-M twiddles from the LDS, behind the images (see frbch_k1_fast)
@@ -2670,8 +2352,7 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 2 : 1) frbch_k3_fast(KParams p
     if (tid < GE::M * 16) tl[tid] = p.ftw2_r[tid];
     tw2 = tl;
   }
-  if constexpr (PRE_TW) bwd_passes_t<LOG2M>(v, s, q, Tw1Reg{t1r}, tw2);
-  else bwd_passes<LOG2M>(v, s, q, p.ftw1_r, tw2);      // v[a] = x[a*TPS + q], natural time order
+  bwd_passes<LOG2M>(v, s, q, p.ftw1_r, tw2);      // v[a] = x[a*TPS + q], natural time order
   __syncthreads();
   // the mirror sequence parks its series in its own image; its partner separates the polarisations
   if (seq & 1) {

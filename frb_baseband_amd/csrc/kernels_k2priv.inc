@@ -37,19 +37,9 @@
 namespace fast {
 
 enum { K2P_CODES = 0, K2P_POWER = 1, K2P_STATS = 2 };
-// tunables (A/B builds: make EXTRA_HIPFLAGS=-D...; the defaults are the measured best, profiles/NOTES.md round 4)
-#ifndef K2P_FLUSH_MASK
-#define K2P_FLUSH_MASK 7u      // rescale sums leave the fp32 registers every 8 trips (32 rows)
-#endif
-#ifndef K2P_QREADS
-#define K2P_QREADS 8           // 16-byte LDS reads of the emit in flight per thread
-#endif
-#ifndef K2P_PRIO
-#define K2P_PRIO 1             // wave priority during the transform and the detection (0 = leave it alone)
-#endif
-#ifndef K2P_STAGGER
-#define K2P_STAGGER 1          // the second half of the grid starts ~half a trip late
-#endif
+// tunables (the measured best, profiles/NOTES.md round 4)
+constexpr uint32_t kK2PFlushMask = 7u;   // rescale sums leave the fp32 registers every 8 trips (32 rows)
+constexpr int kK2PQReads = 8;            // 16-byte LDS reads of the emit in flight per thread
 #ifndef FI
 #define FI __device__ __forceinline__
 #endif
@@ -88,7 +78,7 @@ __global__ void __launch_bounds__(256, 2) frbch_k2_priv(KParams p) {
 
   // The second half of the grid lands in the CUs' second workgroup slots: started ~half a trip late, so that the two workgroups
   // of a CU do not wait for their tiles (and then compute) at the same time.  (Placement affects speed only.)
-  if (K2P_STAGGER && gridDim.x > 1 && blockIdx.x >= (gridDim.x + 1) / 2) __builtin_amdgcn_s_sleep(127);
+  if (gridDim.x > 1 && blockIdx.x >= (gridDim.x + 1) / 2) __builtin_amdgcn_s_sleep(127);
 
   RegTw<LOG2M, VT> rtw;
   rtw.load(p.ftw1_c, p.ftw2_c, ql, LPS, TPS);
@@ -191,8 +181,8 @@ __global__ void __launch_bounds__(256, 2) frbch_k2_priv(KParams p) {
     // ---- FFT_2C across the branches, wave-private (three register passes, two exchanges through the wave's own image) ----
     // the transform and the detection at raised priority: the partner workgroup of the CU is in its emit or waits for its tile, and
     // the wave that computes should win the issue arbitration (digitising pass 1.27 -> 1.25 ms; the statistics pass does not react)
-    if (K2P_PRIO) __builtin_amdgcn_s_setprio(K2P_PRIO);
-    if (!(FRBCH_DBG(p, 1u))) fwd_passes_w<LOG2M, 1, VT, true>(v, s, ql, p.ftw1_c, p.ftw2_c, &rtw);   // (dbg: timing-only ablations, experiments builds)
+    __builtin_amdgcn_s_setprio(1);
+    fwd_passes_w<LOG2M, 1, VT, true>(v, s, ql, p.ftw1_c, p.ftw2_c, &rtw);
 
     // ---- DC repair + mirror exchange inside the wave: D[k] = conj(W[2C-1-k] + dP[2C-1-k]) ---------------------------------
     // The NEXT tile is requested register by register, each load right behind the last use of its register (unconditional: a load
@@ -201,7 +191,6 @@ __global__ void __launch_bounds__(256, 2) frbch_k2_priv(KParams p) {
     // that issues its 32 loads in one go sits in the issue stage until the CU's memory pipe has taken them all; spread like this the
     // first ones are also a detection earlier on their way.  (round 4: K2 passes 1.45 / 1.50 -> 1.33 / 1.39 ms with the halves, ...)
     const cf* const nbase = tile_base(it + 1 < count ? tile + 1 : tile);
-    const bool do_loads = !(FRBCH_DBG(p, 8u));
 #pragma unroll
     for (int vt = 0; vt < VT; ++vt) {
       const int q = ql + LPS * vt;
@@ -212,12 +201,10 @@ __global__ void __launch_bounds__(256, 2) frbch_k2_priv(KParams p) {
         const cf a = add(v[vt][8 + 2 * i], dpl[pw_swz(k0 + TPS * (2 * i), ROT)]);
         const cf b = add(v[vt][9 + 2 * i], dpl[pw_swz(k0 + TPS * (2 * i + 1), ROT)]);
         dst[i] = cf2{a, b};
-        if (do_loads) {
-          __builtin_amdgcn_sched_barrier(0);
-          load_reg(nbase, vt, 8 + 2 * i);
-          load_reg(nbase, vt, 9 + 2 * i);
-          __builtin_amdgcn_sched_barrier(0);
-        }
+        __builtin_amdgcn_sched_barrier(0);
+        load_reg(nbase, vt, 8 + 2 * i);
+        load_reg(nbase, vt, 9 + 2 * i);
+        __builtin_amdgcn_sched_barrier(0);
       }
     }
     cf wm[VT][8];
@@ -233,7 +220,7 @@ __global__ void __launch_bounds__(256, 2) frbch_k2_priv(KParams p) {
       }
     }
     // ---- A7: detection; the wave's power row goes over its own image (in-order LDS: the reads above are through) ----------
-    if (!(FRBCH_DBG(p, 2u)) || v[0][0].x == 123.456f) {
+    {
       float* row = reinterpret_cast<float*>(s);
       const int pm = p.pol_mode;
 #pragma unroll
@@ -275,25 +262,19 @@ __global__ void __launch_bounds__(256, 2) frbch_k2_priv(KParams p) {
             const float i1 = pp + qq;
             row[ks] = pm == 0 ? pp : (pm == 1 ? qq : i1 * i1);
           }
-          if (do_loads) {   // register (vt, kc) has had its last use
-            __builtin_amdgcn_sched_barrier(0);
-            load_reg(nbase, vt, kc);
-            __builtin_amdgcn_sched_barrier(0);
-          }
+          // register (vt, kc) has had its last use
+          __builtin_amdgcn_sched_barrier(0);
+          load_reg(nbase, vt, kc);
+          __builtin_amdgcn_sched_barrier(0);
         }
       }
-    } else if (do_loads) {
-#pragma unroll
-      for (int vt = 0; vt < VT; ++vt)
-#pragma unroll
-        for (int kc = 0; kc < 8; ++kc) load_reg(nbase, vt, kc);
     }
-    if (K2P_PRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     __syncthreads();   // every wave's power row is complete (the next tile is on its way: in front of this trip's row stores in
                        // the in-order vector-memory queue)
 
     // ---- A8 + (A9 + A10 | float rows | rescale sums): workgroup-wide, a thread owns fixed column groups --------------------
-    if (!(FRBCH_DBG(p, 4u))) {
+    {
       const int T = 1 << lg_t;
       const int rows_out = TT >> lg_t;
       const uint64_t row_base = p.row0 + (uint64_t)blk * (uint64_t)(R >> lg_t) + (uint64_t)(t0 >> lg_t);
@@ -344,7 +325,7 @@ __global__ void __launch_bounds__(256, 2) frbch_k2_priv(KParams p) {
         // requested, would be waited for here): no tscrunch, 8-bit codes or float rows / sums; four rows at a time -- every LDS
         // read of the quartet requested first, then the arithmetic and the stores
         constexpr int NR = TT / RS;              // rows of this thread
-        constexpr int QR = (NR * CGT > K2P_QREADS) ? (K2P_QREADS / CGT > 0 ? K2P_QREADS / CGT : 1) : NR;   // at most eight 16-byte reads in flight per thread
+        constexpr int QR = (NR * CGT > kK2PQReads) ? (kK2PQReads / CGT > 0 ? kK2PQReads / CGT : 1) : NR;   // at most eight 16-byte reads in flight per thread
 #pragma unroll
         for (int j0 = 0; j0 < NR; j0 += QR) {
           float4 acc[QR][CGT];
@@ -373,7 +354,7 @@ __global__ void __launch_bounds__(256, 2) frbch_k2_priv(KParams p) {
     }
     __syncthreads();   // the power rows are consumed: the next trip's first pass may overwrite the images
     if constexpr (MODE != K2P_CODES) {
-      if (stat_on && ((it & K2P_FLUSH_MASK) == K2P_FLUSH_MASK || it + 1 == count)) flush_sums();   // at most 8 trips = 32 rows in fp32
+      if (stat_on && ((it & kK2PFlushMask) == kK2PFlushMask || it + 1 == count)) flush_sums();   // at most 8 trips = 32 rows in fp32
     }
   }
 

@@ -67,9 +67,7 @@ typedef struct frbch_config {
                                 * automatic, 1<<27 buffered -- float rows written, then digitised --, 1<<28 two-pass -- K2 runs twice
                                 * over the resident spill, no float rows; automatic = two-pass for four products at 1024 channels,
                                 * DESIGN.md section 5b; both at once is an error).
-                                * Any other bit makes frbch_open fail with FRBCH_E_ARG: rejected kernel variants, layouts and lane
-                                * modes kept for A/B runs and the timing-only ablations (which produce WRONG output) exist only in
-                                * libraries built with -DFRBCH_EXPERIMENTS (make EXPERIMENTS=1), never in the product build. */
+                                * Any other bit makes frbch_open fail with FRBCH_E_ARG. */
   char telescope[64];          /* .hdr TELESCOPE  (process_vdif.py:123)                       */
   char source[64];             /* .hdr SOURCE     (:124)                                      */
   char ra[32];                 /* .hdr RA         (:125)                                      */
@@ -81,8 +79,8 @@ typedef struct frbch_config {
                                 * the next IF of a scan, on plain streams, holding its CUs by an LDS reservation (DESIGN.md section
                                 * 4b; automatic: four products at 8 bits, 11/16 of the CUs for K1; else off).  1 = off: every kernel
                                 * on the whole chip, one after the other.  (3 << 24) | n = that mode with n CUs (a multiple of 8)
-                                * left to K1.  Every setting produces the same output.  CU-masked lane modes (1 << 24, 2 << 24) and
-                                * forced batching (bits 16..23) were measured slower and exist only in FRBCH_EXPERIMENTS builds. */
+                                * left to K1.  Every setting produces the same output.  Any other mode in bits 24..31 and any
+                                * non-zero bits 16..23 make frbch_open fail with FRBCH_E_ARG. */
   float levels[4];             /* 2-bit level table, state 0..3 -> voltage (process_vdif.py:157 passes the bare `-2`: DSPSR's
                                 * static table); all four 0 = the default -3.3359, -1, +1, +3.3359.  A run-time table in
                                 * every kernel, so another level scheme is a data change.                                  */

@@ -45,7 +45,7 @@ def test_hdr_values_that_do_not_fit_are_argument_errors(tmp_path, hip_lib):
 
 
 def test_unknown_flag_bits_are_rejected(emu_lib):
-    # ablations (8..19), rejected kernel variants / layouts / lane modes kept for A/B runs (4 .. 128, 21, 23 .. 26): experiments builds only
+    # the former timing-only ablations (8..19) and rejected kernel variants / layouts / lane modes (4 .. 128, 21, 23 .. 26)
     for bad in (1 << 8, 1 << 12, 1 << 19, 4, 8, 16, 32, 64, 128, 1 << 21, 1 << 23, 1 << 24, 1 << 25, 1 << 26, 1 << 31):
         with pytest.raises(ch.InputError, match="unknown bit"):
             ch.Channeliser(ch.new_config(emu_lib, flags=bad), emu_lib)

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Host-inclusive scan path in context (run on the GPU box): frbch_run_scan of N IFs (VDIF files on tmpfs) into /dev/null, a
-drained FIFO and a tmpfs file, with the phase clock of the profiling build (FRBCH_LIB=.../libfrbch_exp.so FRBCH_TIMING=1),
-next to the PCIe ceilings of the box measured with pinned buffers (torch)."""
+drained FIFO and a tmpfs file, next to the PCIe ceilings of the box measured with pinned buffers (torch)."""
 import os, sys, threading, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
