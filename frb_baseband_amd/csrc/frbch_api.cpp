@@ -60,75 +60,15 @@ extern "C" int frbch_open(const frbch_config* cfg, frbch_handle** out) {
   if (!why.empty()) return fail(h, FRBCH_E_ARG, why);
   const Plan& pl = h->pl;
   CHECK_DEV(h, dev_stream_create(&h->stream), "hipStreamCreate");
-  { const int rc0 = allow_generic_lds(h); if (rc0) return rc0; }
-
   int rc;
   if ((rc = upload_table(h, &h->tw_r, pl.r, std::max(1, pl.r / 2), 1))) return rc;
   if ((rc = upload_table(h, &h->tw_c2, pl.c2, pl.c, 1))) return rc;
   const uint64_t nlo = 1ull << pl.log2_nlo, nhi = pl.n >> pl.log2_nlo;
   if ((rc = upload_table(h, &h->tw_nlo, pl.n, nlo, 1))) return rc;
   if ((rc = upload_table(h, &h->tw_nhi, pl.n, std::max<uint64_t>(1, nhi), nlo))) return rc;
-  h->priv_grid = pl.fast_k2_priv ? 2 * std::max(1, h->lane_ncu) : 0;   // two 80-KiB workgroups per CU
-  if ((rc = setup_fast(h))) return rc;
-  {
-    char nm[64];
-    if (pl.fast_k1_log2m && pl.fast_k1_wave) {
-      const int wps = pl.fast_k1_log2m == 5 ? 4 : (pl.fast_k1_log2m == 4 ? 2 : 1);   // <5,8,4>, <4,8,2>, else <M,8,1>
-      snprintf(nm, sizeof nm, "frbch_k1_wave<%d,8,%d>", pl.fast_k1_log2m, wps);
-      h->kname[KID_K1] = nm;
-    } else if (pl.fast_k1_log2m) {
-      snprintf(nm, sizeof nm, "frbch_k1_fast<%d>", pl.fast_k1_log2m);
-      h->kname[KID_K1] = nm;
-    }
-    if (pl.fast_k2_log2m) {
-      snprintf(nm, sizeof nm, "frbch_kc_fast<%d>", pl.fast_k2_log2m);
-      h->kname[KID_KC] = nm;
-      if (pl.fast_k2_wave) {
-        const bool two = (pl.fast_k2_log2m == 4) || (pl.fast_k2_log2m == 3 && pl.fast_k2_nw != 8);
-        const int nw = two ? (pl.fast_k2_nw == 2 ? 4 : 8) : pl.fast_k2_nw;
-        const int pm = h->cfg.pol_mode == 2 ? 2 : (h->cfg.pol_mode >= 4 ? 4 : 0);
-        if (pl.fast_k2_log2m == 5) snprintf(nm, sizeof nm, "frbch_k2_wave<5,8,%d,4>", pm);
-        else snprintf(nm, sizeof nm, "frbch_k2_wave<%d,%d,%d,%d>", pl.fast_k2_log2m, nw, pm, two ? 2 : 1);
-      } else {
-        snprintf(nm, sizeof nm, "frbch_k2_fast<%d,%d>", pl.fast_k2_log2m, pl.fast_k2_nt);
-      }
-      h->kname[KID_K2] = nm;
-    } else if (pl.fast_k2_m1) {
-      snprintf(nm, sizeof nm, "frbch_k2_wave<0,%d,%d,1>", pl.fast_k2_nw, h->cfg.pol_mode == 2 ? 2 : (h->cfg.pol_mode >= 4 ? 4 : 0));
-      h->kname[KID_K2] = nm;
-    }
-#ifndef FRBCH_NO_FAST
-    if (pl.fast_k2_priv) {   // (KID_K2 keeps frbch_k2_wave's name: float rows of four products and fallen-back launches run it)
-      const int pmn = h->cfg.pol_mode == 2 ? 2 : (h->cfg.pol_mode >= 4 ? h->cfg.pol_mode : 0);
-      snprintf(nm, sizeof nm, "frbch_k2_priv<%d>", pmn);
-      h->kname[KID_K2P] = nm;
-      snprintf(nm, sizeof nm, "frbch_k2_priv<%d,stats>", pmn);
-      h->kname[KID_K2S] = nm;
-    }
-    if (pl.fast_k2_lane) {
-      snprintf(nm, sizeof nm, "frbch_k2_lane<%d,%d>", pl.fast_k2_lane, h->cfg.pol_mode == 2 ? 2 : (h->cfg.pol_mode >= 4 ? 4 : 0));
-      h->kname[KID_K2] = nm;
-      if (pl.fast_k2_lane == 1) h->kname[KID_KC] = "frbch_kc_lane";
-    }
-#endif
-  }
-
-  CHECK_DEV(h, dev_malloc((void**)&h->spill, (size_t)pl.maxb * (pl.c2 / pl.g) * pl.gs * sizeof(cf)), "hipMalloc(spill)");
-#ifndef FRBCH_NO_FAST
-  if (pl.k2_two_stage)
-    CHECK_DEV(h, dev_malloc((void**)&h->scr2, (size_t)pl.maxb * (pl.r / pl.k2_stage1_tscr) * pl.ncol * sizeof(float)), "hipMalloc(tscrunch scratch)");
-#endif
+  if ((rc = apply_plan(h))) return rc;
   CHECK_DEV(h, dev_malloc((void**)&h->s_dc, (size_t)pl.maxb * pl.c2 * sizeof(cf)), "hipMalloc(s_dc)");
   CHECK_DEV(h, dev_malloc((void**)&h->p0, (size_t)pl.maxb * pl.c2 * sizeof(cf)), "hipMalloc(p0)");
-  if (pl.coherent) {
-    CHECK_DEV(h, dev_malloc((void**)&h->spill2, (size_t)pl.maxb * pl.n * sizeof(cf)), "hipMalloc(spill2)");
-    CHECK_DEV(h, dev_malloc((void**)&h->chirp, (size_t)pl.n * sizeof(cf)), "hipMalloc(chirp)");
-    CHECK_DEV(h, dev_malloc((void**)&h->ptmp, (size_t)pl.maxb * pl.rows_per_block * pl.ncol * sizeof(float)), "hipMalloc(ptmp)");
-    if ((rc = build_chirp(h, pl.coh_fast_r ? (1 << pl.coh_fast_r) : 0))) return rc;
-    h->kname[KID_K2] = pl.coh_fast_c ? "frbch_k2c_fast" : "frbch_k2c_chirp";
-    if (pl.ncol % 64 == 0 && pl.rows_per_block % 2 == 0 && pl.c % 4 == 0 && !(h->cfg.flags & 2u)) h->kname[KID_K4] = "frbch_k4_fast";
-    if (pl.coh_fast_r) h->kname[KID_K3] = (pl.coh_fast_r == 4 && pl.coh_nt == 512) ? "frbch_k3_wave<4>" : "frbch_k3_fast";
-  }
   if (pl.dls_lg_ns) {
     const std::vector<float> tab = dls_table(1u << pl.dls_lg_ns, h->cfg.dls_cutoff_sigma, h->cfg.dls_threshold);
     CHECK_DEV(h, dev_malloc((void**)&h->dls_tab, tab.size() * sizeof(float)), "hipMalloc(level table)");

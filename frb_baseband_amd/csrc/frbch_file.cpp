@@ -19,11 +19,7 @@ int stream_begin(frbch_handle* h, const uint8_t* first_frame) {
     if (h->cfg.input_bits) return fail(h, FRBCH_E_FORMAT, "VDIF bits/sample differs from cfg.input_bits");
     const std::string why2 = make_plan(h->cfg, &h->pl, h->lds_limit, (int)v.bits_per_sample);   // same sizes, other gather
     if (!why2.empty()) return fail(h, FRBCH_E_ARG, why2);
-    { const int rc0 = allow_generic_lds(h); if (rc0) return rc0; }
-    h->kname[KID_K1].clear();
-    dev_free(h->spill);   // the group size (hence the padded slab count) may have changed
-    h->spill = nullptr;
-    CHECK_DEV(h, dev_malloc((void**)&h->spill, (size_t)h->pl.maxb * (h->pl.c2 / h->pl.g) * h->pl.gs * sizeof(cf)), "hipMalloc(spill)");
+    { const int rc0 = apply_plan(h); if (rc0) return rc0; }   // (the kernels, their names, the group size of the spill: all may have changed)
   }
   const Plan& pl = h->pl;
   const uint64_t spb = 4 / (uint64_t)pl.in_bits;                       // dual-pol samples per payload byte

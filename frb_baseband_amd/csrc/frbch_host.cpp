@@ -304,7 +304,7 @@ std::string make_plan(const frbch_config& cfg, Plan* pl, size_t lds_limit, int i
   // tile-major spill: the paired-branch wave K1 (R = 2048, 8 branches per workgroup) in front of a wave K2 whose
   // workgroup takes two time samples (measured: K2 1.34 -> 1.29 ms, its gather alone 1.06 -> 0.95 ms; K1 unchanged)
   pl->spill_tile_major = 0;
-  if (pl->fast_k1_wave && pl->fast_k1_log2m == 3 && pl->fast_k1_g == 8 && pl->g == 8 && pl->fast_k2_wave && !pl->coherent) {
+  if (k1_paired_planned(*pl) && pl->fast_k2_wave && !pl->coherent) {
     const int m2 = pl->c2 / 256, tps2 = 16 * m2, spw2 = tps2 < 64 ? 64 / tps2 : 1;
     const bool two = (m2 == 16) || (m2 == 8 && pl->fast_k2_nw != 8);   // two waves per sequence
     const int tt2 = two ? (pl->fast_k2_nw == 2 ? 2 : 4) : pl->fast_k2_nw * spw2;
@@ -314,8 +314,7 @@ std::string make_plan(const frbch_config& cfg, Plan* pl, size_t lds_limit, int i
   // to its four-sample tile)
   pl->fast_k2_priv = 0;
   pl->k2_priv_lds = (size_t)4 * (2048 + 256) * 8 + 1024 * 8;      // = 81,920: exactly half of the CU's 160 KiB
-  if (pl->fast_k1_wave && pl->fast_k1_log2m == 3 && pl->fast_k1_g == 8 && pl->g == 8 &&
-      pl->fast_k2_wave && pl->fast_k2_log2m == 3 && pl->c2 == 2048 && !pl->coherent &&
+  if (k1_paired_planned(*pl) && pl->fast_k2_wave && pl->fast_k2_log2m == 3 && pl->c2 == 2048 && !pl->coherent &&
       pl->k2_priv_lds <= lds_limit && pl->tscr <= 4 && !pl->k2_two_stage) {
     pl->fast_k2_priv = 1;
     pl->spill_tile_major = 2;      // (what the paired-branch K1 writes for it, whatever tile the two-wave K2 would have taken)

@@ -68,6 +68,12 @@ struct Plan {
   int dls_lg_ns;              // dynamic level setting (cfg.unpack_mode 1): log2 of the window length in samples; 0 = static table
 };
 
+// plan predicates that several units ask
+// the wave-private K2 (frbch_k2_wave) is planned: the K2 that can sum the rescale statistics while it writes
+inline bool k2_wave_planned(const Plan& pl) { return (pl.fast_k2_log2m || pl.fast_k2_m1) && pl.fast_k2_wave; }
+// the paired-branch wave K1 (R = 2048, 8 branches per workgroup)
+inline bool k1_paired_planned(const Plan& pl) { return pl.fast_k1_wave && pl.fast_k1_log2m == 3 && pl.fast_k1_g == 8 && pl.g == 8; }
+
 // returns "" on success, else the reason (InputError territory)
 std::string make_plan(const frbch_config& cfg, Plan* plan, size_t lds_limit, int in_bits = 0);
 

@@ -1,6 +1,9 @@
 // libfrbch compute side, shared by its translation units (round 4: the former single 3 000-line frbch_engine.cpp):
 //   frbch_launch.cpp    plan -> kernel launches: every HIP kernel is instantiated and launched here (the only unit that sees the
-//                       kernel sources), LDS permissions, tables, statistics / digitiser launches
+//                       kernel sources).  One selector per family of register-pass kernels maps the plan to the instantiation; the
+//                       launches, the LDS permissions, the timing-slot names and the sizing of the partial sums all go through it.
+//                       apply_plan: everything a handle derives from its plan (open, and the re-plan of a 1-bit stream); tables,
+//                       statistics / digitiser launches
 //   frbch_stream.cpp    stream state of a handle: batches, the rescale-interval state machine (buffered and two-pass forms),
 //                       the chain of stages of a scan and the two kernels that may share the chip
 //   frbch_api.cpp       the C ABI of include/frbch.h that works on device memory: life cycle, rescale state, device entry points
@@ -257,8 +260,7 @@ struct Chain {
 // ---- frbch_launch.cpp -----------------------------------------------------------------------------------------------------------
 int upload_table(frbch_handle* h, cf** dst, uint64_t n, uint64_t count, uint64_t step);
 KParams base_params(const frbch_handle* h);
-int allow_generic_lds(frbch_handle* h);                      // LDS sizes of the generic kernels for the handle's plan
-int setup_fast(frbch_handle* h);                             // tables and LDS sizes of the register-pass kernels
+int apply_plan(frbch_handle* h);                             // what a handle derives from its plan: LDS limits, tables, kernel names, plan-sized buffers (callable again after a new make_plan)
 int build_chirp(frbch_handle* h, int order_m);
 int launch_front(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s);   // K0, K1, Kc
 int launch_dls_count(frbch_handle* h, KParams& p, uint64_t nsamples, dev_stream_t s);            // dynamic level setting: the windows' low-state counts

@@ -76,12 +76,245 @@ KParams base_params(const frbch_handle* h) {
 }
 
 #ifndef FRBCH_NO_FAST
-template <int LOG2M>
-void launch_k1_fast_t(const Plan& pl, KParams& p, uint32_t nb, dev_stream_t s) {
-  hipLaunchKernelGGL(fast::frbch_k1_fast<LOG2M>, dim3(pl.c2 / pl.g, nb), dim3(1024), pl.k1_fast_lds, s, p);
+// =============================================================================================
+// Kernel selection.  Every family of register-pass kernels with more than one instantiation has ONE selector below: it maps the
+// plan and the per-launch inputs to the instantiation and calls its visitor once, f(kernel, KSel).  A launch passes a visitor that
+// launches, setup_fast one that raises the kernel's dynamic-LDS limit and names its timing slot, wave_stat_chunks one that reads
+// the threads per workgroup -- so an instantiation is added or removed in its selector and nowhere else.
+// A selector returns false when the plan has no kernel of its family (the caller runs the generic one).
+// =============================================================================================
+struct KSel {
+  int nt;               // threads per workgroup
+  size_t lds;           // dynamic LDS bytes
+  const char* family;   // timing-slot name = family<targ[0],...> : the integer template arguments, trailing bools dropped
+  int ntarg;
+  int targ[4];
+  const char* tail;     // ... and what follows them inside the brackets (frbch_k2_priv<PM,stats>)
+  int nseq;             // frbch_k2_wave: sequences (time samples; x those a wave holds) per workgroup
+  std::string name() const {
+    std::string s = family;
+    for (int i = 0; i < ntarg; ++i) s += (i ? "," : "<") + std::to_string(targ[i]);
+    return ntarg ? s + tail + ">" : s;
+  }
+};
+inline KSel ksel(int nt, size_t lds, const char* family, std::initializer_list<int> targs = {}, const char* tail = "", int nseq = 0) {
+  KSel a{nt, lds, family, 0, {0, 0, 0, 0}, tail, nseq};
+  for (int t : targs) a.targ[a.ntarg++] = t;
+  return a;
 }
-template <int LOG2M>
-void launch_k1_wave_t(const Plan& pl, KParams& p, uint32_t nb, dev_stream_t s, int ncu) {
+// calls f(std::integral_constant<int, V>) for the V among Vs that equals v; false = none does
+template <int... Vs, class F>
+bool on_value(int v, F&& f) {
+  return ((v == Vs && (f(std::integral_constant<int, Vs>()), true)) || ...);
+}
+// the visitor of a launch
+template <class K>
+void launch_sel(K kern, dim3 grid, const KSel& a, dev_stream_t s, const KParams& p) {
+  hipLaunchKernelGGL(kern, grid, dim3(a.nt), a.lds, s, p);
+}
+// product mode as the kernels' template argument PM: 2 = PP+QQ, 4 = four products, 0 = one of the others.  frbch_k2_priv keeps
+// the Stokes form (pol_mode 5) apart from the coherency products, the other families fold it into 4
+int pm_of(int pol_mode) { return pol_mode == 2 ? 2 : (pol_mode >= 4 ? 4 : 0); }
+int pm_priv_of(int pol_mode) { return (pol_mode == 2 || pol_mode == 4 || pol_mode == 5) ? pol_mode : 0; }
+
+// ---- K0: RB = input bytes per row piece, WIDE: 16-byte loads
+template <class F>
+bool select_k0_stage(uint32_t rb, bool wide, F&& f) {
+  return on_value<1, 2, 4, 8, 16>((rb == 1 || rb == 2 || rb == 4 || rb == 8) ? (int)rb : 16, [&](auto RB) {
+    if (wide) f(fast::frbch_k0_stage<RB.value, true>, ksel(256, 0, "frbch_k0_stage"));
+    else f(fast::frbch_k0_stage<RB.value, false>, ksel(256, 0, "frbch_k0_stage"));
+  });
+}
+// ---- K1, barrier form
+template <class F>
+bool select_k1_fast(const Plan& pl, F&& f) {
+  return on_value<1, 2, 3, 4, 5>(pl.fast_k1_log2m, [&](auto L) {
+    f(fast::frbch_k1_fast<L.value>, ksel(1024, pl.k1_fast_lds, "frbch_k1_fast", {L.value}));
+  });
+}
+// ---- K1, wave form.  stg: the batch was corner-turned by frbch_k0_stage; msk (with stg only): frames flagged invalid / fillers are
+// masked through one flag per n2 row beside the stage (a byte, at R = 8192 a bit)
+size_t k1_wave_lds(const Plan& pl, bool msk) {
+  return pl.k1_fast_lds + (msk ? (size_t)(pl.fast_k1_log2m >= 5 ? pl.r / 8 : pl.r) : 0);
+}
+template <int L, int WPS, bool COH, class F>
+void pick_k1_wave(const Plan& pl, bool stg, bool msk, F& f) {
+  const KSel a = ksel(512, k1_wave_lds(pl, stg && msk), "frbch_k1_wave", {L, 8, WPS});
+  if (stg && msk) f(fast::frbch_k1_wave<L, 8, WPS, true, COH, true>, a);
+  else if (stg) f(fast::frbch_k1_wave<L, 8, WPS, true, COH>, a);
+  else f(fast::frbch_k1_wave<L, 8, WPS, false, COH>, a);
+}
+template <class F>
+bool select_k1_wave(const Plan& pl, bool stg, bool msk, F&& f) {
+  switch (pl.fast_k1_log2m) {
+    case 1: pick_k1_wave<1, 1, false>(pl, stg, msk, f); return true;
+    case 2: pick_k1_wave<2, 1, false>(pl, stg, msk, f); return true;
+    case 3: pick_k1_wave<3, 1, false>(pl, stg, msk, f); return true;
+    case 4:   // R = 4096: two waves per branch; coherent: forward transform + delay only, spectrum spilled (K2c follows)
+      if (pl.coherent) pick_k1_wave<4, 2, true>(pl, stg, msk, f);
+      else pick_k1_wave<4, 2, false>(pl, stg, msk, f);
+      return true;
+    case 5: pick_k1_wave<5, 4, false>(pl, stg, msk, f); return true;   // R = 8192: two branches per workgroup, four waves (two virtual threads per lane) each
+    default: return false;
+  }
+}
+// ---- Kc: shares the 2C-point tables of the fast K2 (2C = 64: frbch_kc_lane, one lane per block, a single kernel)
+bool kc_lane_planned(const Plan& pl) { return pl.fast_k2_lane == 1; }
+template <class F>
+bool select_kc_fast(const Plan& pl, F&& f) {
+  return on_value<1, 2, 3, 4, 5>(pl.fast_k2_log2m, [&](auto L) {
+    f(fast::frbch_kc_fast<L.value>, ksel(16 << L.value, ((size_t)pl.c2 + pl.c2 / 8 + 8 + pl.c2) * 8, "frbch_kc_fast", {L.value}));
+  });
+}
+// ---- K2, 2C = 64 / 128: a whole sequence per lane (pair)
+template <class F>
+bool select_k2_lane(const Plan& pl, int pol_mode, F&& f) {
+  const size_t lds = 4 * 64 * (16 * 8 + 16);   // one transposing strip per wave
+  return on_value<1, 2>(pl.fast_k2_lane, [&](auto NH) {
+    constexpr int nh = decltype(NH)::value;
+    on_value<0, 2, 4>(pm_of(pol_mode), [&](auto PM) {
+      f(fast::frbch_k2_lane<nh, PM.value>, ksel(256, lds, "frbch_k2_lane", {nh, PM.value}));
+    });
+  });
+}
+// ---- K2, 2C = 2048: one wave per time sample (kernels_k2priv.inc)
+template <class F>
+bool select_k2_priv(const Plan& pl, int pol_mode, int out_mode, F&& f) {
+  if (!pl.fast_k2_priv) return false;
+  return on_value<0, 2, 4, 5>(pm_priv_of(pol_mode), [&](auto PM) {
+    const KSel a = ksel(256, pl.k2_priv_lds, "frbch_k2_priv", {PM.value}, out_mode == FRBCH_OUT_STATS ? ",stats" : "");
+    if (out_mode == FRBCH_OUT_CODES) f(fast::frbch_k2_priv<PM.value, fast::K2P_CODES>, a);
+    else if (out_mode == FRBCH_OUT_STATS) f(fast::frbch_k2_priv<PM.value, fast::K2P_STATS>, a);
+    else f(fast::frbch_k2_priv<PM.value, fast::K2P_POWER>, a);
+  });
+}
+// ---- K2, wave form: frbch_k2_wave<LOG2M, NW waves, PM, WPS waves per sequence, MSTAT>.  cols: the launch sums the rescale
+// statistics or digitises (per-thread column registers in the MSTAT instantiations, where there is one)
+template <int L, int NW, int PM, int WPS, bool MSTAT = false, class F>
+bool pick_k2_wave(const Plan& pl, F& f) {
+  f(fast::frbch_k2_wave<L, NW, PM, WPS, MSTAT>, ksel(64 * NW, pl.k2_fast_lds, "frbch_k2_wave", {L, NW, PM, WPS}, "", NW / WPS));
+  return true;
+}
+template <int L, int NW, int WPS, class F>
+bool pick_k2_wave_pm(const Plan& pl, int pm, F& f) {
+  return pm == 2 ? pick_k2_wave<L, NW, 2, WPS>(pl, f) : (pm == 4 ? pick_k2_wave<L, NW, 4, WPS>(pl, f) : pick_k2_wave<L, NW, 0, WPS>(pl, f));
+}
+template <int L, class F>
+bool pick_k2_wave_nw(const Plan& pl, int pm, F& f) {   // one wave per sequence: 2, 4 or (large tscrunch) 8 (x spw) sequences per workgroup
+  return pl.fast_k2_nw == 8 ? pick_k2_wave_pm<L, 8, 1>(pl, pm, f)
+                            : (pl.fast_k2_nw == 2 ? pick_k2_wave_pm<L, 2, 1>(pl, pm, f) : pick_k2_wave_pm<L, 4, 1>(pl, pm, f));
+}
+template <class F>
+bool select_k2_wave(const Plan& pl, int pol_mode, bool cols, F&& f) {
+  const int pm = pm_of(pol_mode);
+  switch (pl.fast_k2_log2m) {
+    case 5:
+      // 2C = 8192: two time samples per workgroup (32-byte pieces of the spill lines), four waves and two virtual threads per lane
+      // each; one workgroup per CU.  The instantiation with the per-thread column registers: the rescale sums while an interval is
+      // being measured, the frozen offset / scale when it digitises (loaded in the emit they wait for the whole prefetch: 2.28 vs
+      // 2.1 ms); the plain one for float rows without sums (two-stage tscrunch)
+      if (pm == 2) return cols ? pick_k2_wave<5, 8, 2, 4, true>(pl, f) : pick_k2_wave<5, 8, 2, 4>(pl, f);
+      return cols ? pick_k2_wave<5, 8, 0, 4, true>(pl, f) : pick_k2_wave<5, 8, 0, 4>(pl, f);
+    case 4: return pick_k2_wave_pm<4, 8, 2>(pl, pm, f);   // 2C = 4096: two waves per sequence, 4 sequences per workgroup (make_plan: fast_k2_nw = 4)
+    case 3:
+      if (pl.fast_k2_nw == 8) return pick_k2_wave_pm<3, 8, 1>(pl, pm, f);   // large tscrunch: 8 sequences per workgroup, one wave per sequence
+      // M = 8: two waves per sequence (16 points per lane), 2 or 4 sequences per workgroup -> 16 waves per CU
+      if (pm == 4 && cols) return pl.fast_k2_nw == 2 ? pick_k2_wave<3, 4, 4, 2, true>(pl, f) : pick_k2_wave<3, 8, 4, 2, true>(pl, f);
+      return pl.fast_k2_nw == 2 ? pick_k2_wave_pm<3, 4, 2>(pl, pm, f) : pick_k2_wave_pm<3, 8, 2>(pl, pm, f);
+    case 2: return pick_k2_wave_nw<2>(pl, pm, f);
+    case 1: return pick_k2_wave_nw<1>(pl, pm, f);
+    case 0: return pl.fast_k2_m1 ? pick_k2_wave_nw<0>(pl, pm, f) : false;   // 2C = 256
+    default: return false;
+  }
+}
+// ---- K2, barrier form: 2C = 8192 only; 512 threads = one time sample per workgroup (tscrunch 1)
+template <class F>
+bool select_k2_fast(const Plan& pl, F&& f) {
+  if (pl.fast_k2_log2m != 5) return false;
+  if (pl.fast_k2_nt == 512) f(fast::frbch_k2_fast<5, 512>, ksel(512, pl.k2_fast_lds, "frbch_k2_fast", {5, 512}));
+  else f(fast::frbch_k2_fast<5, 1024>, ksel(1024, pl.k2_fast_lds, "frbch_k2_fast", {5, 1024}));
+  return true;
+}
+// ---- coherent filterbank: K2c, K3 (reported without template arguments)
+template <class F>
+bool select_k2c_fast(const Plan& pl, F&& f) {
+  return on_value<1, 2, 3, 4, 5>(pl.coh_fast_c, [&](auto L) {
+    f(fast::frbch_k2c_fast<L.value, 1024>, ksel(1024, pl.k2c_fast_lds, "frbch_k2c_fast"));
+  });
+}
+// the wave K3 (R = 4096) sums the statistics of its channel: one row of partial sums per persistent workgroup
+constexpr uint32_t kK3WaveWgs = 2048;
+bool k3_wave_planned(const Plan& pl) {
+  return pl.coherent && pl.coh_fast_r == 4 && pl.coh_nt == 512;
+}
+template <class F>
+bool select_k3_fast(const Plan& pl, F&& f) {
+  if (pl.coh_nt == 512) {   // R = 4096: the wave form
+    if (!k3_wave_planned(pl)) return false;
+    f(fast::frbch_k3_wave<4>, ksel(256, pl.k3_fast_lds, "frbch_k3_wave", {4}));
+    return true;
+  }
+  return on_value<1, 2, 3, 5>(pl.coh_fast_r, [&](auto L) {
+    f(fast::frbch_k3_fast<L.value, 1024>, ksel(1024, pl.k3_fast_lds, "frbch_k3_fast"));
+  });
+}
+// K4 of the coherent filterbank: the register-pass transpose (a single kernel) or the generic one
+bool k4_fast_planned(const Plan& pl, uint32_t h_flags) {
+  return pl.ncol % 64 == 0 && pl.rows_per_block % 2 == 0 && pl.c % 4 == 0 && !(h_flags & kFlagGenericK2);   // (the flag: the generic back end)
+}
+
+// =============================================================================================
+// Rows of the table of partial rescale sums
+// =============================================================================================
+constexpr uint32_t kFusedStatWgs = 2048;   // persistent K2 workgroups (= rows of partial sums per thread row) while statistics are fused
+// frbch_k2_priv: one row of partial sums per (workgroup, row phase); `grid` = its workgroups (one per CU)
+int priv_stat_chunks(const Plan& pl, int grid) { return grid * (pl.ncol / 4 >= 256 ? 1 : (int)(256 / (pl.ncol / 4))); }
+// which K2 a launch of a plan with frbch_k2_priv takes: float rows stay on frbch_k2_wave (measured: four products, config 3, 1.87 ms
+// per IF against 1.97; one product, config 2, 1.15 - 1.20 against 1.20 - 1.28 -- the two-wave kernel reads whole 128-byte lines,
+// frbch_k2_priv halves of them twice, and writing float rows leaves less of the memory pipe to hide that), codes and statistics-only
+// passes run frbch_k2_priv (steady state of config 3 + 2.4 %, config 2 + 4 %)
+bool pol_mode_no_sums(int pol_mode) { return pol_mode == 3; }   // (PP+QQ)^2: its square overflows the fp32 partial sums (~1e24 squared)
+bool priv_takes(const Plan& pl, const KParams& p, int priv_grid) {
+  // (the two-wave kernel reads the tile-major spill only in its two-sample form: fast_k2_nw == 2, tscrunch <= 2)
+  return pl.fast_k2_priv && p.tile_major == 2 && priv_grid > 0 &&
+         !(p.out_mode == FRBCH_OUT_FLOAT_POWER && pl.fast_k2_nw == 2 && pl.fast_k2_log2m == 3);
+}
+// rows of partial sums the fused statistics of frbch_k2_wave / frbch_k3_wave use; 0 = this configuration cannot fuse (one column
+// group per thread needed)
+int wave_stat_chunks(const Plan& pl, uint32_t h_flags, int pol_mode) {
+  if (pol_mode_no_sums(pol_mode) || pl.k2_two_stage) return 0;   // (two-stage tscrunch: K2 does not see the output rows)
+  if (k3_wave_planned(pl)) return (h_flags & kFlagSeparateStats) ? 0 : (int)kK3WaveWgs;
+  if (!k2_wave_planned(pl) || pl.coherent || (h_flags & kFlagSeparateStats)) return 0;
+  int nt = 0;   // threads per workgroup of the instantiation the launch will take
+  select_k2_wave(pl, pol_mode, false, [&](auto, const KSel& a) { nt = a.nt; });
+  const int cg = (int)(pl.ncol / 4);
+  if (!nt) return 0;
+  if (cg > nt)   // a thread owns cg/nt column groups, one row of sums per workgroup (the MSTAT instantiations: 2C = 2048, two waves per sequence)
+    return (cg % nt == 0 && cg / nt <= 4)
+               ? (pl.fast_k2_log2m == 5 ? 256 : ((pl.fast_k2_log2m == 3 && pl.fast_k2_nw != 8) ? (int)kFusedStatWgs : 0))   // 2C = 8192: resident workgroups only
+               : 0;
+  if (nt % cg != 0) return 0;
+  return (int)kFusedStatWgs * (nt / cg);
+}
+// rows of the table of partial rescale sums the kernels of this plan may write (both K2 families add into the same table: whatever
+// mix of them ran, frbch_stats_final sums every row)
+int fused_stat_chunks(const Plan& pl, uint32_t h_flags, int pol_mode, int priv_grid = 0) {
+  const int w = wave_stat_chunks(pl, h_flags, pol_mode);
+  if (pol_mode_no_sums(pol_mode) || pl.k2_two_stage || (h_flags & kFlagSeparateStats)) return w;
+  return (pl.fast_k2_priv && priv_grid > 0) ? std::max(w, priv_stat_chunks(pl, priv_grid)) : w;
+}
+
+// =============================================================================================
+// Launches
+// =============================================================================================
+void set_fastdiv(KParams& p) {
+  const uint32_t d = p.payload_bytes;
+  uint32_t l = 0;
+  while ((1ull << l) < d) ++l;
+  p.div_magic = (uint32_t)((((1ull << l) - d) << 32) / d + 1);
+  p.div_shift = l ? l - 1 : 0;
+}
+bool launch_k1_wave(const Plan& pl, KParams& p, uint32_t nb, dev_stream_t s, int ncu) {
   // persistent over blocks: the resident workgroups each keep their branch group and loop over the batch
   p.nblk = nb;
   const int kg = pl.fast_k1_g;            // branches per workgroup (<= pl.g, the layout group)
@@ -105,162 +338,30 @@ void launch_k1_wave_t(const Plan& pl, KParams& p, uint32_t nb, dev_stream_t s, i
     const uint32_t want = resident / g;
     if (want <= nb) ny = want;
   }
-  const size_t lds_msk = pl.k1_fast_lds + (size_t)(LOG2M >= 5 ? pl.r / 8 : pl.r);   // + one flag per n2 row (frames flagged invalid / fillers: MSK): a byte, at R = 8192 a bit
-#define FRBCH_K1W(L, NWV, WPSV, NTV)                                                                                       \
-  do {                                                                                                                  \
-    if (p.stg && p.fbad) hipLaunchKernelGGL((fast::frbch_k1_wave<L, NWV, WPSV, true, false, true>), dim3(ngrp, ny), dim3(NTV), lds_msk, s, p);  \
-    else if (p.stg) hipLaunchKernelGGL((fast::frbch_k1_wave<L, NWV, WPSV, true>), dim3(ngrp, ny), dim3(NTV), pl.k1_fast_lds, s, p);  \
-    else hipLaunchKernelGGL((fast::frbch_k1_wave<L, NWV, WPSV, false>), dim3(ngrp, ny), dim3(NTV), pl.k1_fast_lds, s, p);        \
-  } while (0)
-  if constexpr (LOG2M == 5) {
-    FRBCH_K1W(5, 8, 4, 512);      // R = 8192: two branches per workgroup, four waves (two virtual threads per lane) each
-  } else if constexpr (LOG2M == 4) {
-    if (p.coherent) {   // forward transform + delay only, spectrum spilled (K2c follows)
-      if (p.stg && p.fbad) hipLaunchKernelGGL((fast::frbch_k1_wave<4, 8, 2, true, true, true>), dim3(ngrp, ny), dim3(512), lds_msk, s, p);
-      else if (p.stg) hipLaunchKernelGGL((fast::frbch_k1_wave<4, 8, 2, true, true>), dim3(ngrp, ny), dim3(512), pl.k1_fast_lds, s, p);
-      else hipLaunchKernelGGL((fast::frbch_k1_wave<4, 8, 2, false, true>), dim3(ngrp, ny), dim3(512), pl.k1_fast_lds, s, p);
-    } else
-    FRBCH_K1W(4, 8, 2, 512);
-  } else {
-    FRBCH_K1W(LOG2M, 8, 1, 512);
-  }
-#undef FRBCH_K1W
+  return select_k1_wave(pl, p.stg != nullptr, p.fbad != nullptr, [&](auto kern, const KSel& a) { launch_sel(kern, dim3(ngrp, ny), a, s, p); });
 }
-constexpr uint32_t kFusedStatWgs = 2048;   // persistent K2 workgroups (= rows of partial sums per thread row) while statistics are fused
-// threads per workgroup of the wave-private K2 variant launch_k2_wave_t selects
-int k2_wave_nt(const Plan& pl) {
-  if (pl.fast_k2_log2m == 5) return 512;
-  if (pl.fast_k2_log2m == 4) return pl.fast_k2_nw == 2 ? 256 : 512;
-  if (pl.fast_k2_nw == 8) return 512;
-  if (pl.fast_k2_log2m == 3) return pl.fast_k2_nw == 2 ? 256 : 512;
-  return pl.fast_k2_nw == 2 ? 128 : 256;
-}
-// rows of partial sums the fused statistics use; 0 = this configuration cannot fuse (one column group per thread needed)
-// the wave K3 (coherent filterbank, R = 4096) sums the statistics of its channel: one row of partial sums per persistent workgroup
-constexpr uint32_t kK3WaveWgs = 2048;
-bool k3_wave_planned(const Plan& pl) {
-  return pl.coherent && pl.coh_fast_r == 4 && pl.coh_nt == 512;
-}
-// frbch_k2_priv: one row of partial sums per (workgroup, row phase); `grid` = its workgroups (one per CU)
-int priv_stat_chunks(const Plan& pl, int grid) { return grid * (pl.ncol / 4 >= 256 ? 1 : (int)(256 / (pl.ncol / 4))); }
-// which K2 a launch of a plan with frbch_k2_priv takes: float rows stay on frbch_k2_wave (measured: four products, config 3, 1.87 ms
-// per IF against 1.97; one product, config 2, 1.15 - 1.20 against 1.20 - 1.28 -- the two-wave kernel reads whole 128-byte lines,
-// frbch_k2_priv halves of them twice, and writing float rows leaves less of the memory pipe to hide that), codes and statistics-only
-// passes run frbch_k2_priv (steady state of config 3 + 2.4 %, config 2 + 4 %)
-bool pol_mode_no_sums(int pol_mode) { return pol_mode == 3; }   // (PP+QQ)^2: its square overflows the fp32 partial sums (~1e24 squared)
-bool priv_takes(const Plan& pl, const KParams& p, int priv_grid) {
-  // (the two-wave kernel reads the tile-major spill only in its two-sample form: fast_k2_nw == 2, tscrunch <= 2)
-  return pl.fast_k2_priv && p.tile_major == 2 && priv_grid > 0 &&
-         !(p.out_mode == FRBCH_OUT_FLOAT_POWER && pl.fast_k2_nw == 2 && pl.fast_k2_log2m == 3);
-}
-int wave_stat_chunks(const Plan& pl, uint32_t h_flags, int pol_mode);
-// rows of the table of partial rescale sums the kernels of this plan may write (both K2 families add into the same table: whatever
-// mix of them ran, frbch_stats_final sums every row)
-int fused_stat_chunks(const Plan& pl, uint32_t h_flags, int pol_mode, int priv_grid = 0) {
-  if (pol_mode == 3 || pl.k2_two_stage || (h_flags & (1u << 20))) return wave_stat_chunks(pl, h_flags, pol_mode);
-  const int w = wave_stat_chunks(pl, h_flags, pol_mode);
-  return (pl.fast_k2_priv && priv_grid > 0) ? std::max(w, priv_stat_chunks(pl, priv_grid)) : w;
-}
-int wave_stat_chunks(const Plan& pl, uint32_t h_flags, int pol_mode) {
-  if (pol_mode == 3 || pl.k2_two_stage) return 0;   // (two-stage tscrunch: K2 does not see the output rows)
-  if (k3_wave_planned(pl)) return (h_flags & (1u << 20)) ? 0 : (int)kK3WaveWgs;   // (PP+QQ)^2: its square overflows the fp32 partial sums (~1e24 squared)
-  if (!(pl.fast_k2_log2m || pl.fast_k2_m1) || !pl.fast_k2_wave || pl.coherent || (h_flags & (1u << 20))) return 0;
-  const int nt = k2_wave_nt(pl), cg = (int)(pl.ncol / 4);
-  if (cg > nt)   // a thread owns cg/nt column groups, one row of sums per workgroup (the MSTAT instantiations: 2C = 2048, two waves per sequence)
-    return (cg % nt == 0 && cg / nt <= 4)
-               ? (pl.fast_k2_log2m == 5 ? 256 : ((pl.fast_k2_log2m == 3 && pl.fast_k2_nw != 8) ? (int)kFusedStatWgs : 0))   // 2C = 8192: resident workgroups only
-               : 0;
-  if (nt % cg != 0) return 0;
-  return (int)kFusedStatWgs * (nt / cg);
-}
-template <int LOG2M>
-void launch_k2_wave_t(const Plan& pl, KParams& p, uint32_t nb, dev_stream_t s, uint32_t h_flags) {
-  const int tps = 16 << LOG2M;
+bool launch_k2_wave(const Plan& pl, KParams& p, uint32_t nb, dev_stream_t s, uint32_t h_flags) {
+  const int tps = 16 << pl.fast_k2_log2m;
   const int spw = tps < 64 ? 64 / tps : 1;
   // persistent: one wave of workgroups loops over the (tiles per block) x nb tiles of the launch
   p.nblk = nb;
   if (!wave_stat_chunks(pl, h_flags, p.pol_mode)) p.stat_partial = nullptr;
-  const uint32_t npers = p.stat_partial ? kFusedStatWgs : 8192u;   // measured: 768 (= resident) 1.59 ms, 2048 1.56, 8192 1.49 (shorter tail)
-  auto pers = [&](uint32_t tiles_per_block) { return dim3(std::min<uint64_t>((uint64_t)tiles_per_block * nb, npers)); };
-  const dim3 grid2 = pers(pl.r / (2 * spw)), grid4 = pers(pl.r / (4 * spw)), grid8 = pers(pl.r / (8 * spw));
-  const int pm = p.pol_mode == 2 ? 2 : (p.pol_mode >= 4 ? 4 : 0);
-#define FRBCH_K2W(NWV, PMV, GRID) hipLaunchKernelGGL((fast::frbch_k2_wave<LOG2M, NWV, PMV>), GRID, dim3(64 * NWV), pl.k2_fast_lds, s, p)
-  if constexpr (LOG2M == 5) {   // 2C = 8192: two time samples per workgroup (32-byte pieces of the spill lines), four waves and two virtual threads per lane each; one workgroup per CU
-    const dim3 grid1 = dim3(std::min<uint64_t>((uint64_t)(pl.r / 2) * nb, p.stat_partial ? 256u : 1024u));   // (multiples of 8: XCD-aware tile order)
-    // the instantiation with the per-thread column registers: the rescale sums while an interval is being measured, the
-    // frozen offset / scale when it digitises (loaded in the emit they wait for the whole prefetch: 2.28 vs 2.1 ms);
-    // the plain one for float rows without sums (two-stage tscrunch)
-    const bool cols = p.stat_partial || p.out_mode != FRBCH_OUT_FLOAT_POWER;
-    if (pm == 2 && cols) hipLaunchKernelGGL((fast::frbch_k2_wave<5, 8, 2, 4, true>), grid1, dim3(512), pl.k2_fast_lds, s, p);
-    else if (pm == 2) hipLaunchKernelGGL((fast::frbch_k2_wave<5, 8, 2, 4>), grid1, dim3(512), pl.k2_fast_lds, s, p);
-    else if (cols) hipLaunchKernelGGL((fast::frbch_k2_wave<5, 8, 0, 4, true>), grid1, dim3(512), pl.k2_fast_lds, s, p);
-    else hipLaunchKernelGGL((fast::frbch_k2_wave<5, 8, 0, 4>), grid1, dim3(512), pl.k2_fast_lds, s, p);
-  } else
-  if constexpr (LOG2M == 4) {   // 2C = 4096: two waves per sequence; 2 or 4 sequences per workgroup
-    if (pl.fast_k2_nw == 2) {
-      if (pm == 2) hipLaunchKernelGGL((fast::frbch_k2_wave<4, 4, 2, 2>), grid2, dim3(256), pl.k2_fast_lds, s, p);
-      else if (pm == 4) hipLaunchKernelGGL((fast::frbch_k2_wave<4, 4, 4, 2>), grid2, dim3(256), pl.k2_fast_lds, s, p);
-      else hipLaunchKernelGGL((fast::frbch_k2_wave<4, 4, 0, 2>), grid2, dim3(256), pl.k2_fast_lds, s, p);
-    } else {
-      if (pm == 2) hipLaunchKernelGGL((fast::frbch_k2_wave<4, 8, 2, 2>), grid4, dim3(512), pl.k2_fast_lds, s, p);
-      else if (pm == 4) hipLaunchKernelGGL((fast::frbch_k2_wave<4, 8, 4, 2>), grid4, dim3(512), pl.k2_fast_lds, s, p);
-      else hipLaunchKernelGGL((fast::frbch_k2_wave<4, 8, 0, 2>), grid4, dim3(512), pl.k2_fast_lds, s, p);
-    }
-  } else {
-  if (pl.fast_k2_nw == 8) {   // large tscrunch: 8 (x spw) sequences per workgroup, one wave per sequence
-    if (pm == 2) FRBCH_K2W(8, 2, grid8); else if (pm == 4) FRBCH_K2W(8, 4, grid8); else FRBCH_K2W(8, 0, grid8);
-  } else
-  // M = 8: two waves per sequence (16 points per lane), 2 or 4 sequences per workgroup -> 16 waves per CU
-  if constexpr (LOG2M == 3) {
-    if (pl.fast_k2_nw == 2) {
-      if (pm == 2) hipLaunchKernelGGL((fast::frbch_k2_wave<3, 4, 2, 2>), grid2, dim3(256), pl.k2_fast_lds, s, p);
-      else if (pm == 4 && (p.stat_partial || p.out_mode != FRBCH_OUT_FLOAT_POWER)) hipLaunchKernelGGL((fast::frbch_k2_wave<3, 4, 4, 2, true>), grid2, dim3(256), pl.k2_fast_lds, s, p);
-      else if (pm == 4) hipLaunchKernelGGL((fast::frbch_k2_wave<3, 4, 4, 2>), grid2, dim3(256), pl.k2_fast_lds, s, p);
-      else hipLaunchKernelGGL((fast::frbch_k2_wave<3, 4, 0, 2>), grid2, dim3(256), pl.k2_fast_lds, s, p);
-    } else {
-      if (pm == 2) hipLaunchKernelGGL((fast::frbch_k2_wave<3, 8, 2, 2>), grid4, dim3(512), pl.k2_fast_lds, s, p);
-      else if (pm == 4 && (p.stat_partial || p.out_mode != FRBCH_OUT_FLOAT_POWER)) hipLaunchKernelGGL((fast::frbch_k2_wave<3, 8, 4, 2, true>), grid4, dim3(512), pl.k2_fast_lds, s, p);
-      else if (pm == 4) hipLaunchKernelGGL((fast::frbch_k2_wave<3, 8, 4, 2>), grid4, dim3(512), pl.k2_fast_lds, s, p);
-      else hipLaunchKernelGGL((fast::frbch_k2_wave<3, 8, 0, 2>), grid4, dim3(512), pl.k2_fast_lds, s, p);
-    }
-  } else {
-  if (pl.fast_k2_nw == 2) {
-    if (pm == 2) FRBCH_K2W(2, 2, grid2); else if (pm == 4) FRBCH_K2W(2, 4, grid2); else FRBCH_K2W(2, 0, grid2);
-  } else {
-    if (pm == 2) FRBCH_K2W(4, 2, grid4); else if (pm == 4) FRBCH_K2W(4, 4, grid4); else FRBCH_K2W(4, 0, grid4);
-  }
-  }
-  }
-#undef FRBCH_K2W
-}
-void set_fastdiv(KParams& p) {
-  const uint32_t d = p.payload_bytes;
-  uint32_t l = 0;
-  while ((1ull << l) < d) ++l;
-  p.div_magic = (uint32_t)((((1ull << l) - d) << 32) / d + 1);
-  p.div_shift = l ? l - 1 : 0;
-}
-template <int LOG2M>
-void launch_kc_fast_t(const Plan& pl, KParams& p, uint32_t nb, dev_stream_t s) {
-  const size_t lds = ((size_t)pl.c2 + pl.c2 / 8 + 8 + pl.c2) * 8;
-  hipLaunchKernelGGL(fast::frbch_kc_fast<LOG2M>, dim3(1, nb), dim3(16 << LOG2M), lds, s, p);
+  // measured: 768 (= resident) 1.59 ms, 2048 1.56, 8192 1.49 (shorter tail); 2C = 8192, one workgroup per CU: multiples of 8 (XCD-aware tile order)
+  const uint32_t npers = pl.fast_k2_log2m == 5 ? (p.stat_partial ? 256u : 1024u) : (p.stat_partial ? kFusedStatWgs : 8192u);
+  const bool cols = p.stat_partial || p.out_mode != FRBCH_OUT_FLOAT_POWER;
+  return select_k2_wave(pl, p.pol_mode, cols, [&](auto kern, const KSel& a) {
+    const uint64_t tiles_per_block = pl.r / (a.nseq * spw);
+    launch_sel(kern, dim3((unsigned)std::min<uint64_t>(tiles_per_block * nb, npers)), a, s, p);
+  });
 }
 bool launch_kc_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
   const Plan& pl = h->pl;
-  if (pl.fast_k2_lane == 1) {   // 2C = 64: one lane per block
+  if (kc_lane_planned(pl)) {
     p.nblk = nb;
     hipLaunchKernelGGL(fast::frbch_kc_lane, dim3((nb + 63) / 64), dim3(64), 0, s, p);
     return true;
   }
-  switch (pl.fast_k2_log2m) {   // shares the 2C-point tables of the fast K2
-    case 1: launch_kc_fast_t<1>(pl, p, nb, s); break;
-    case 2: launch_kc_fast_t<2>(pl, p, nb, s); break;
-    case 3: launch_kc_fast_t<3>(pl, p, nb, s); break;
-    case 4: launch_kc_fast_t<4>(pl, p, nb, s); break;
-    case 5: launch_kc_fast_t<5>(pl, p, nb, s); break;
-    default: return false;
-  }
-  return true;
+  return select_kc_fast(pl, [&](auto kern, const KSel& a) { launch_sel(kern, dim3(1, nb), a, s, p); });
 }
 // corner-turn of the batch's payload for the wave K1 (own timing slot); same preconditions as launch_k1_fast
 void launch_k0_stage(frbch_handle* h, const KParams& p, uint32_t nb, dev_stream_t s) {
@@ -283,16 +384,7 @@ void launch_k0_stage(frbch_handle* h, const KParams& p, uint32_t nb, dev_stream_
   ProfScope ps(h, s, KID_K0, (double)nb * (double)pl.block_payload_bytes * (1.0 + (double)p.frame_bytes / p.payload_bytes));
   const dim3 grid((pl.r / 64) * (pl.c / 256), nb);
   const bool wide = !(rel0 % 16 || p.payload_bytes % 16 || p.header_bytes % 16 || p.frame_bytes % 16);
-#define FRBCH_K0(RBV) do { if (wide) hipLaunchKernelGGL((fast::frbch_k0_stage<RBV, true>), grid, dim3(256), 0, s, q); \
-                           else hipLaunchKernelGGL((fast::frbch_k0_stage<RBV, false>), grid, dim3(256), 0, s, q); } while (0)
-  switch (rb) {
-    case 1: FRBCH_K0(1); break;
-    case 2: FRBCH_K0(2); break;
-    case 4: FRBCH_K0(4); break;
-    case 8: FRBCH_K0(8); break;
-    default: FRBCH_K0(16); break;
-  }
-#undef FRBCH_K0
+  select_k0_stage(rb, wide, [&](auto kern, const KSel& a) { launch_sel(kern, grid, a, s, q); });
   h->stg_ready = true;
 }
 bool launch_k1_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
@@ -314,21 +406,12 @@ bool launch_k1_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
     set_fastdiv(q);
     if (h->stg_ready) q.stg = h->stg;   // launch_k0_stage has corner-turned this batch
     h->stg_ready = false;
-    if (p.fbad) {   // flagged frames: the staged wave K1 masks them (a flag per row beside the stage: a byte, at R = 8192 a bit)
-      if (!q.stg || pl.k1_fast_lds + (size_t)(pl.fast_k1_log2m >= 5 ? pl.r / 8 : pl.r) > h->lds_limit)
-        return false;
+    if (p.fbad) {   // flagged frames: the staged wave K1 masks them
+      if (!q.stg || k1_wave_lds(pl, true) > h->lds_limit) return false;
       q.fbad_frame0 = p.fbad_frame0 + fr0;
     }
     q.tile_major = p.tile_major = pl.spill_tile_major;   // 2 (R = 2048, paired branches) or 8 (R = 8192) or 0 (K2 of this batch reads what this launch writes)
-    switch (pl.fast_k1_log2m) {
-      case 1: launch_k1_wave_t<1>(pl, q, nb, s, h->lane_cus); break;
-      case 2: launch_k1_wave_t<2>(pl, q, nb, s, h->lane_cus); break;
-      case 3: launch_k1_wave_t<3>(pl, q, nb, s, h->lane_cus); break;
-      case 4: launch_k1_wave_t<4>(pl, q, nb, s, h->lane_cus); break;
-      case 5: launch_k1_wave_t<5>(pl, q, nb, s, h->lane_cus); break;
-      default: return false;
-    }
-    return true;
+    return launch_k1_wave(pl, q, nb, s, h->lane_cus);
   }
   p.tile_major = pl.spill_tile_major == 8 ? 8 : 0;   // (K2 of this batch reads what this launch writes)
   KParams q = p;
@@ -347,99 +430,50 @@ bool launch_k1_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
       q.div_magic = 0;
     }
   }
-  switch (pl.fast_k1_log2m) {
-    case 1: launch_k1_fast_t<1>(pl, q, nb, s); break;
-    case 2: launch_k1_fast_t<2>(pl, q, nb, s); break;
-    case 3: launch_k1_fast_t<3>(pl, q, nb, s); break;
-    case 4: launch_k1_fast_t<4>(pl, q, nb, s); break;
-    case 5: launch_k1_fast_t<5>(pl, q, nb, s); break;
-    default: return false;
-  }
-  return true;
+  return select_k1_fast(pl, [&](auto kern, const KSel& a) { launch_sel(kern, dim3(pl.c2 / pl.g, nb), a, s, q); });
 }
 bool launch_k2_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
   const Plan& pl = h->pl;
-  if (pl.fast_k2_lane) {   // 2C = 64 / 128: a whole sequence per lane (pair)
+  if (pl.fast_k2_lane) {
     if (p.tile_major) return false;
-    const int pmk = p.pol_mode == 2 ? 2 : (p.pol_mode >= 4 ? 4 : 0);
     const dim3 grid((unsigned)((uint64_t)pl.r * nb * pl.fast_k2_lane / 256));
-    const size_t lds = 4 * 64 * (16 * 8 + 16);   // one transposing strip per wave
-#define FRBCH_K2L(NHV) do { if (pmk == 2) hipLaunchKernelGGL((fast::frbch_k2_lane<NHV, 2>), grid, dim3(256), lds, s, p); \
-                            else if (pmk == 4) hipLaunchKernelGGL((fast::frbch_k2_lane<NHV, 4>), grid, dim3(256), lds, s, p); \
-                            else hipLaunchKernelGGL((fast::frbch_k2_lane<NHV, 0>), grid, dim3(256), lds, s, p); } while (0)
-    if (pl.fast_k2_lane == 1) FRBCH_K2L(1); else FRBCH_K2L(2);
-#undef FRBCH_K2L
-    return true;
+    return select_k2_lane(pl, p.pol_mode, [&](auto kern, const KSel& a) { launch_sel(kern, grid, a, s, p); });
   }
-  if (priv_takes(pl, p, h->priv_grid)) {   // one wave per time sample (kernels_k2priv.inc)
-    KParams& k = p;
-    k.nblk = nb;
-    if (pol_mode_no_sums(k.pol_mode) || (h->cfg.flags & (1u << 20))) k.stat_partial = nullptr;
+  if (priv_takes(pl, p, h->priv_grid)) {
+    p.nblk = nb;
+    if (pol_mode_no_sums(p.pol_mode) || (h->cfg.flags & kFlagSeparateStats)) p.stat_partial = nullptr;
     const uint64_t ntiles = (uint64_t)nb * (uint64_t)(pl.r / 4);
     const dim3 grid((unsigned)std::min<uint64_t>(ntiles, (uint64_t)h->priv_grid));
-    const int pm = k.pol_mode == 2 ? 2 : (k.pol_mode >= 4 ? k.pol_mode : 0);
-    const size_t lds = pl.k2_priv_lds;
-#define FRBCH_K2P(PMV) do { \
-      if (k.out_mode == FRBCH_OUT_CODES) hipLaunchKernelGGL((fast::frbch_k2_priv<PMV, fast::K2P_CODES>), grid, dim3(256), lds, s, k); \
-      else if (k.out_mode == FRBCH_OUT_STATS) hipLaunchKernelGGL((fast::frbch_k2_priv<PMV, fast::K2P_STATS>), grid, dim3(256), lds, s, k); \
-      else hipLaunchKernelGGL((fast::frbch_k2_priv<PMV, fast::K2P_POWER>), grid, dim3(256), lds, s, k); } while (0)
-    if (pm == 2) FRBCH_K2P(2); else if (pm == 4) FRBCH_K2P(4); else if (pm == 5) FRBCH_K2P(5); else FRBCH_K2P(0);
-#undef FRBCH_K2P
-    return true;
+    return select_k2_priv(pl, p.pol_mode, p.out_mode, [&](auto kern, const KSel& a) { launch_sel(kern, grid, a, s, p); });
   }
   if (p.out_mode == FRBCH_OUT_STATS) return false;   // (only frbch_k2_priv has a statistics-only form: the engine asks for it nowhere else)
-  if (pl.fast_k2_wave) {
-    // tscrunch beyond the kernel's tile: rows of its largest tile into the scratch buffer (q), then the sums (p)
-    KParams q = p;
-    if (pl.k2_two_stage) {
-      q.tscr = pl.k2_stage1_tscr;
-      q.out_mode = FRBCH_OUT_FLOAT_POWER;
-      q.power_out = h->scr2;
-      q.row0 = 0;
-      q.stat_partial = nullptr;
-    }
-    KParams& k = pl.k2_two_stage ? q : p;
-    switch (pl.fast_k2_log2m) {
-      case 0:
-        if (!pl.fast_k2_m1) return false;
-        launch_k2_wave_t<0>(pl, k, nb, s, h->cfg.flags);
-        break;
-      case 1: launch_k2_wave_t<1>(pl, k, nb, s, h->cfg.flags); break;
-      case 2: launch_k2_wave_t<2>(pl, k, nb, s, h->cfg.flags); break;
-      case 3: launch_k2_wave_t<3>(pl, k, nb, s, h->cfg.flags); break;
-      case 4: launch_k2_wave_t<4>(pl, k, nb, s, h->cfg.flags); break;
-      case 5: launch_k2_wave_t<5>(pl, k, nb, s, h->cfg.flags); break;
-      default: return false;
-    }
-    if (pl.k2_two_stage) {
-      p.scr_in = h->scr2;
-      p.scr_fact = (uint32_t)pl.k2_two_stage;
-      p.scr_rows = (uint64_t)nb * pl.rows_per_block;
-      p.stat_partial = nullptr;
-      const uint64_t groups = p.scr_rows * (uint64_t)(pl.ncol / 4);
-      hipLaunchKernelGGL(fast::frbch_k2_scrunch, dim3((unsigned)std::min<uint64_t>((groups + 255) / 256, 8192)), dim3(256), 0, s, p);
-    }
-    return true;
-  }
-  if (pl.k2_two_stage && pl.fast_k2_log2m == 5) {   // barrier K2, four products: two-sample rows into the scratch buffer, then the sums
-    KParams q = p;
+  if (!pl.fast_k2_wave && pl.fast_k2_log2m != 5) return false;   // (the barrier K2: 2C = 8192 only)
+  // tscrunch beyond the kernel's tile: rows of its largest tile into the scratch buffer (q), then the sums (p)
+  // (the barrier K2 so with four products at 2C = 8192: two-sample rows)
+  KParams q = p;
+  if (pl.k2_two_stage) {
     q.tscr = pl.k2_stage1_tscr;
     q.out_mode = FRBCH_OUT_FLOAT_POWER;
     q.power_out = h->scr2;
     q.row0 = 0;
     q.stat_partial = nullptr;
-    hipLaunchKernelGGL((fast::frbch_k2_fast<5, 1024>), dim3(pl.r / 2, nb), dim3(1024), pl.k2_fast_lds, s, q);
+  }
+  KParams& k = pl.k2_two_stage ? q : p;
+  if (pl.fast_k2_wave) {
+    if (!launch_k2_wave(pl, k, nb, s, h->cfg.flags)) return false;
+  } else {
+    select_k2_fast(pl, [&](auto kern, const KSel& a) {   // a workgroup of 1024 threads takes two time samples, or the tscrunch group
+      launch_sel(kern, dim3(pl.r / (a.nt == 512 ? 1 : std::max(2, k.tscr)), nb), a, s, k);
+    });
+  }
+  if (pl.k2_two_stage) {
     p.scr_in = h->scr2;
     p.scr_fact = (uint32_t)pl.k2_two_stage;
     p.scr_rows = (uint64_t)nb * pl.rows_per_block;
     p.stat_partial = nullptr;
     const uint64_t groups = p.scr_rows * (uint64_t)(pl.ncol / 4);
     hipLaunchKernelGGL(fast::frbch_k2_scrunch, dim3((unsigned)std::min<uint64_t>((groups + 255) / 256, 8192)), dim3(256), 0, s, p);
-    return true;
   }
-  if (pl.fast_k2_log2m != 5) return false;   // (the barrier K2: 2C = 8192 only)
-  if (pl.fast_k2_nt == 512) hipLaunchKernelGGL((fast::frbch_k2_fast<5, 512>), dim3(pl.r, nb), dim3(512), pl.k2_fast_lds, s, p);   // one time sample per workgroup (tscrunch 1)
-  else hipLaunchKernelGGL((fast::frbch_k2_fast<5, 1024>), dim3(pl.r / std::max(2, pl.tscr), nb), dim3(1024), pl.k2_fast_lds, s, p);
   return true;
 }
 bool launch_k2c_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
@@ -452,38 +486,27 @@ bool launch_k2c_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
   const uint32_t ntile = (uint32_t)(pl.r / tt);
   const uint32_t want = 4u * (uint32_t)std::max(1, h->lane_ncu);
   const uint32_t gy = std::max<uint32_t>(1, std::min<uint32_t>(nb, (want + ntile - 1) / ntile));
-  const dim3 grid(ntile, gy);
-  switch (pl.coh_fast_c) {
-    case 1: hipLaunchKernelGGL((fast::frbch_k2c_fast<1, 1024>), grid, dim3(1024), pl.k2c_fast_lds, s, p); break;
-    case 2: hipLaunchKernelGGL((fast::frbch_k2c_fast<2, 1024>), grid, dim3(1024), pl.k2c_fast_lds, s, p); break;
-    case 3: hipLaunchKernelGGL((fast::frbch_k2c_fast<3, 1024>), grid, dim3(1024), pl.k2c_fast_lds, s, p); break;
-    case 4: hipLaunchKernelGGL((fast::frbch_k2c_fast<4, 1024>), grid, dim3(1024), pl.k2c_fast_lds, s, p); break;
-    case 5: hipLaunchKernelGGL((fast::frbch_k2c_fast<5, 1024>), grid, dim3(1024), pl.k2c_fast_lds, s, p); break;
-    default: return false;
-  }
-  return true;
+  return select_k2c_fast(pl, [&](auto kern, const KSel& a) { launch_sel(kern, dim3(ntile, gy), a, s, p); });
 }
 bool launch_k3_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
   const Plan& pl = h->pl;
   if (!pl.coh_fast_r || !h->coh_order_m) return false;
-  const int np = pl.coh_nt / (16 << pl.coh_fast_r) / 2;
-  const dim3 grid(pl.c / np, nb);
-  if (pl.coh_nt == 512) {   // R = 4096: the wave form, persistent over the (block, channel) tiles, next tile prefetched piecewise
-    if (pl.coh_fast_r != 4) return false;
-    p.nblk = nb;
+  if (k3_wave_planned(pl)) {   // persistent over the (block, channel) tiles, next tile prefetched piecewise
     const uint64_t ntiles = (uint64_t)nb * pl.c;
-    hipLaunchKernelGGL((fast::frbch_k3_wave<4>), dim3((unsigned)std::min<uint64_t>(ntiles, kK3WaveWgs)), dim3(256), pl.k3_fast_lds, s, p);
-    return true;
+    return select_k3_fast(pl, [&](auto kern, const KSel& a) {
+      p.nblk = nb;
+      launch_sel(kern, dim3((unsigned)std::min<uint64_t>(ntiles, kK3WaveWgs)), a, s, p);
+    });
   }
-  switch (pl.coh_fast_r) {
-    case 1: hipLaunchKernelGGL((fast::frbch_k3_fast<1, 1024>), grid, dim3(1024), pl.k3_fast_lds, s, p); break;
-    case 2: hipLaunchKernelGGL((fast::frbch_k3_fast<2, 1024>), grid, dim3(1024), pl.k3_fast_lds, s, p); break;
-    case 3: hipLaunchKernelGGL((fast::frbch_k3_fast<3, 1024>), grid, dim3(1024), pl.k3_fast_lds, s, p); break;
-    case 5: hipLaunchKernelGGL((fast::frbch_k3_fast<5, 1024>), grid, dim3(1024), pl.k3_fast_lds, s, p); break;
-    default: return false;
-  }
-  return true;
+  const int np = pl.coh_nt / (16 << pl.coh_fast_r) / 2;
+  return select_k3_fast(pl, [&](auto kern, const KSel& a) { launch_sel(kern, dim3(pl.c / np, nb), a, s, p); });
 }
+
+// =============================================================================================
+// Set-up of the register-pass kernels of the handle's plan: tables, and -- through the selectors, once for every value the
+// per-launch inputs can take on this handle -- dynamic-LDS limits and the names of the timing slots.  (The product mode is fixed
+// for the life of a handle: base_params copies it from the configuration.)
+// =============================================================================================
 template <class K>
 int allow_lds(frbch_handle* h, K kern, size_t bytes) {
   CHECK_DEV(h, dev_allow_lds(kern, bytes), "LDS size (fast kernel)");
@@ -514,8 +537,16 @@ void fft_tables(int len, std::vector<float>* tw1, std::vector<float>* tw2) {
 }
 int setup_fast(frbch_handle* h) {
   const Plan& pl = h->pl;
-  int rc;
+  const int pol = h->cfg.pol_mode;
+  int rc = FRBCH_OK;
   std::vector<float> t1, t2;
+  // the visitor of set-up: the kernel may use its LDS, and timing slot `kid` reports under its name
+  auto plan_for = [&](int kid) {
+    return [&rc, h, kid](auto kern, const KSel& a) {
+      if (!rc) rc = allow_lds(h, kern, a.lds);
+      h->kname[kid] = a.name();
+    };
+  };
   if (pl.fast_k1_log2m) {
     fft_tables(pl.r, &t1, &t2);
     if ((rc = upload_cf(h, &h->ftw1_r, t1)) || (rc = upload_cf(h, &h->ftw2_r, t2))) return rc;
@@ -534,128 +565,35 @@ int setup_fast(frbch_handle* h) {
       }
     }
     if ((rc = upload_cf(h, &h->td1, d1)) || (rc = upload_cf(h, &h->td2, d2))) return rc;
-    if (!h->stg)
-      CHECK_DEV(h, dev_malloc((void**)&h->stg, (size_t)pl.maxb * pl.block_payload_bytes), "hipMalloc(staged payload)");
-#define FRBCH_AL(L, NWV, WPSV) do { if (!rc) rc = allow_lds(h, fast::frbch_k1_wave<L, NWV, WPSV, false>, pl.k1_fast_lds); \
-                                    if (!rc) rc = allow_lds(h, fast::frbch_k1_wave<L, NWV, WPSV, true>, pl.k1_fast_lds); \
-                                    if (!rc && pl.k1_fast_lds + (size_t)(L >= 5 ? pl.r / 8 : pl.r) <= h->lds_limit) \
-                                      rc = allow_lds(h, fast::frbch_k1_wave<L, NWV, WPSV, true, false, true>, pl.k1_fast_lds + (size_t)(L >= 5 ? pl.r / 8 : pl.r)); } while (0)
-    rc = FRBCH_OK;
-    if (pl.fast_k1_wave) switch (pl.fast_k1_log2m) {
-      case 1: FRBCH_AL(1, 8, 1); break;
-      case 2: FRBCH_AL(2, 8, 1); break;
-      case 4:
-        FRBCH_AL(4, 8, 2);
-        if (!rc) rc = allow_lds(h, fast::frbch_k1_wave<4, 8, 2, false, true>, pl.k1_fast_lds);
-        if (!rc) rc = allow_lds(h, fast::frbch_k1_wave<4, 8, 2, true, true>, pl.k1_fast_lds);
-        if (!rc && pl.k1_fast_lds + (size_t)pl.r <= h->lds_limit) rc = allow_lds(h, fast::frbch_k1_wave<4, 8, 2, true, true, true>, pl.k1_fast_lds + (size_t)pl.r);
-        break;
-      case 5: FRBCH_AL(5, 8, 4); break;
-      default: FRBCH_AL(3, 8, 1); break;
-    }
-#undef FRBCH_AL
-    else switch (pl.fast_k1_log2m) {
-      case 1: rc = allow_lds(h, fast::frbch_k1_fast<1>, pl.k1_fast_lds); break;
-      case 2: rc = allow_lds(h, fast::frbch_k1_fast<2>, pl.k1_fast_lds); break;
-      case 3: rc = allow_lds(h, fast::frbch_k1_fast<3>, pl.k1_fast_lds); break;
-      case 4: rc = allow_lds(h, fast::frbch_k1_fast<4>, pl.k1_fast_lds); break;
-      default: rc = allow_lds(h, fast::frbch_k1_fast<5>, pl.k1_fast_lds); break;
+    CHECK_DEV(h, dev_malloc((void**)&h->stg, (size_t)pl.maxb * pl.block_payload_bytes), "hipMalloc(staged payload)");
+    if (pl.fast_k1_wave) {
+      select_k1_wave(pl, false, false, plan_for(KID_K1));
+      select_k1_wave(pl, true, false, plan_for(KID_K1));
+      if (k1_wave_lds(pl, true) <= h->lds_limit) select_k1_wave(pl, true, true, plan_for(KID_K1));   // (else launch_k1_fast declines masked batches)
+    } else {
+      select_k1_fast(pl, plan_for(KID_K1));
     }
     if (rc) return rc;
   }
-  if (pl.coh_fast_c) {
+  if (pl.coh_fast_c || pl.fast_k2_log2m || pl.fast_k2_m1) {   // the 2C-point tables (2C = 256: wave-private K2 only, Kc stays generic)
     fft_tables(pl.c2, &t1, &t2);
     if ((rc = upload_cf(h, &h->ftw1_c, t1)) || (rc = upload_cf(h, &h->ftw2_c, t2))) return rc;
-    switch (pl.coh_fast_c) {
-      case 1: rc = allow_lds(h, fast::frbch_k2c_fast<1, 1024>, pl.k2c_fast_lds); break;
-      case 2: rc = allow_lds(h, fast::frbch_k2c_fast<2, 1024>, pl.k2c_fast_lds); break;
-      case 3: rc = allow_lds(h, fast::frbch_k2c_fast<3, 1024>, pl.k2c_fast_lds); break;
-      case 4: rc = allow_lds(h, fast::frbch_k2c_fast<4, 1024>, pl.k2c_fast_lds); break;
-      default: rc = allow_lds(h, fast::frbch_k2c_fast<5, 1024>, pl.k2c_fast_lds); break;
-    }
-    if (rc) return rc;
   }
-  if (pl.coh_fast_r) {
-    switch (pl.coh_fast_r) {
-      case 1: rc = allow_lds(h, fast::frbch_k3_fast<1, 1024>, pl.k3_fast_lds); break;
-      case 2: rc = allow_lds(h, fast::frbch_k3_fast<2, 1024>, pl.k3_fast_lds); break;
-      case 3: rc = allow_lds(h, fast::frbch_k3_fast<3, 1024>, pl.k3_fast_lds); break;
-      case 4: rc = allow_lds(h, fast::frbch_k3_wave<4>, pl.k3_fast_lds); break;   // (R = 4096: coh_nt = 512, the wave K3)
-      default: rc = allow_lds(h, fast::frbch_k3_fast<5, 1024>, pl.k3_fast_lds); break;
-    }
-    if (rc) return rc;
+  select_k2c_fast(pl, plan_for(KID_K2));
+  select_k3_fast(pl, plan_for(KID_K3));
+  if (pl.coherent && k4_fast_planned(pl, h->cfg.flags)) h->kname[KID_K4] = "frbch_k4_fast";
+  select_kc_fast(pl, plan_for(KID_KC));
+  if (kc_lane_planned(pl)) h->kname[KID_KC] = "frbch_kc_lane";
+  if (pl.fast_k2_wave) {
+    for (const bool cols : {false, true}) select_k2_wave(pl, pol, cols, plan_for(KID_K2));
+  } else {
+    select_k2_fast(pl, plan_for(KID_K2));
   }
-  if (pl.fast_k2_m1) {   // 2C = 256: wave-private K2 only, Kc stays generic
-    fft_tables(pl.c2, &t1, &t2);
-    if ((rc = upload_cf(h, &h->ftw1_c, t1)) || (rc = upload_cf(h, &h->ftw2_c, t2))) return rc;
-    rc = FRBCH_OK;
-#define FRBCH_ALLOW0(NWV, PMV) if (!rc) rc = allow_lds(h, fast::frbch_k2_wave<0, NWV, PMV>, pl.k2_fast_lds)
-    FRBCH_ALLOW0(2, 0); FRBCH_ALLOW0(2, 2); FRBCH_ALLOW0(2, 4); FRBCH_ALLOW0(4, 0); FRBCH_ALLOW0(4, 2); FRBCH_ALLOW0(4, 4);
-    FRBCH_ALLOW0(8, 0); FRBCH_ALLOW0(8, 2); FRBCH_ALLOW0(8, 4);
-#undef FRBCH_ALLOW0
-    if (rc) return rc;
-  }
-  if (pl.fast_k2_log2m) {
-    fft_tables(pl.c2, &t1, &t2);
-    if ((rc = upload_cf(h, &h->ftw1_c, t1)) || (rc = upload_cf(h, &h->ftw2_c, t2))) return rc;
-    const size_t kc_lds = ((size_t)pl.c2 + pl.c2 / 8 + 8 + pl.c2) * 8;
-    switch (pl.fast_k2_log2m) {
-      case 1: rc = allow_lds(h, fast::frbch_kc_fast<1>, kc_lds); break;
-      case 2: rc = allow_lds(h, fast::frbch_kc_fast<2>, kc_lds); break;
-      case 3: rc = allow_lds(h, fast::frbch_kc_fast<3>, kc_lds); break;
-      case 4: rc = allow_lds(h, fast::frbch_kc_fast<4>, kc_lds); break;
-      default: rc = allow_lds(h, fast::frbch_kc_fast<5>, kc_lds); break;
-    }
-    if (rc) return rc;
-    const bool big = pl.fast_k2_nt == 1024;
-    if (pl.fast_k2_priv) {
-      rc = FRBCH_OK;
-#define FRBCH_ALLOWP(PMV) do { if (!rc) rc = allow_lds(h, fast::frbch_k2_priv<PMV, fast::K2P_CODES>, pl.k2_priv_lds); \
-                               if (!rc) rc = allow_lds(h, fast::frbch_k2_priv<PMV, fast::K2P_POWER>, pl.k2_priv_lds); \
-                               if (!rc) rc = allow_lds(h, fast::frbch_k2_priv<PMV, fast::K2P_STATS>, pl.k2_priv_lds); } while (0)
-      FRBCH_ALLOWP(0); FRBCH_ALLOWP(2); FRBCH_ALLOWP(4); FRBCH_ALLOWP(5);
-#undef FRBCH_ALLOWP
-      if (rc) return rc;
-    }
-    if (pl.fast_k2_wave) {
-      rc = FRBCH_OK;
-#define FRBCH_ALLOW_(L, NWV, PMV, W) if (!rc) rc = allow_lds(h, fast::frbch_k2_wave<L, NWV, PMV, W>, pl.k2_fast_lds)
-#define FRBCH_ALLOW4(L, NWV, PMV, W) FRBCH_ALLOW_(L, NWV, PMV, W)
-#define FRBCH_ALLOW(...) FRBCH_ALLOW_SEL(__VA_ARGS__, FRBCH_ALLOW4, FRBCH_ALLOW3)(__VA_ARGS__)
-#define FRBCH_ALLOW_SEL(a, b, c, d, NAME, ...) NAME
-#define FRBCH_ALLOW3(L, NWV, PMV) FRBCH_ALLOW_(L, NWV, PMV, 1)
-#define FRBCH_ALLOW_L(L) FRBCH_ALLOW(L, 2, 0); FRBCH_ALLOW(L, 2, 2); FRBCH_ALLOW(L, 2, 4); FRBCH_ALLOW(L, 4, 0); FRBCH_ALLOW(L, 4, 2); FRBCH_ALLOW(L, 4, 4); FRBCH_ALLOW(L, 8, 0); FRBCH_ALLOW(L, 8, 2); FRBCH_ALLOW(L, 8, 4)
-      if (pl.fast_k2_log2m == 5) {
-        if (!rc) rc = allow_lds(h, fast::frbch_k2_wave<5, 8, 2, 4, true>, pl.k2_fast_lds);
-        if (!rc) rc = allow_lds(h, fast::frbch_k2_wave<5, 8, 0, 4, true>, pl.k2_fast_lds);
-        if (!rc) rc = allow_lds(h, fast::frbch_k2_wave<5, 8, 2, 4>, pl.k2_fast_lds);
-        if (!rc) rc = allow_lds(h, fast::frbch_k2_wave<5, 8, 0, 4>, pl.k2_fast_lds);
-      } else
-      if (pl.fast_k2_log2m == 4) {
-        FRBCH_ALLOW(4, 4, 0, 2); FRBCH_ALLOW(4, 4, 2, 2); FRBCH_ALLOW(4, 4, 4, 2);
-        FRBCH_ALLOW(4, 8, 0, 2); FRBCH_ALLOW(4, 8, 2, 2); FRBCH_ALLOW(4, 8, 4, 2);
-      } else
-      if (pl.fast_k2_log2m == 1) { FRBCH_ALLOW_L(1); }
-      else if (pl.fast_k2_log2m == 2) { FRBCH_ALLOW_L(2); }
-      else {
-        FRBCH_ALLOW(3, 8, 0); FRBCH_ALLOW(3, 8, 2); FRBCH_ALLOW(3, 8, 4);
-        if (!rc) rc = allow_lds(h, fast::frbch_k2_wave<3, 4, 0, 2>, pl.k2_fast_lds);
-        if (!rc) rc = allow_lds(h, fast::frbch_k2_wave<3, 4, 2, 2>, pl.k2_fast_lds);
-        if (!rc) rc = allow_lds(h, fast::frbch_k2_wave<3, 4, 4, 2>, pl.k2_fast_lds);
-        if (!rc) rc = allow_lds(h, fast::frbch_k2_wave<3, 8, 0, 2>, pl.k2_fast_lds);
-        if (!rc) rc = allow_lds(h, fast::frbch_k2_wave<3, 8, 2, 2>, pl.k2_fast_lds);
-        if (!rc) rc = allow_lds(h, fast::frbch_k2_wave<3, 8, 4, 2>, pl.k2_fast_lds);
-        if (!rc) rc = allow_lds(h, fast::frbch_k2_wave<3, 4, 4, 2, true>, pl.k2_fast_lds);
-        if (!rc) rc = allow_lds(h, fast::frbch_k2_wave<3, 8, 4, 2, true>, pl.k2_fast_lds);
-      }
-#undef FRBCH_ALLOW_L
-#undef FRBCH_ALLOW
-    }
-    else   // the barrier K2: 2C = 8192 only
-      rc = big ? allow_lds(h, fast::frbch_k2_fast<5, 1024>, pl.k2_fast_lds) : allow_lds(h, fast::frbch_k2_fast<5, 512>, pl.k2_fast_lds);
-    if (rc) return rc;
-  }
-  return FRBCH_OK;
+  // (KID_K2 keeps frbch_k2_wave's name beside frbch_k2_priv: float rows of four products and fallen-back launches run it)
+  for (const int out_mode : {(int)FRBCH_OUT_CODES, (int)FRBCH_OUT_FLOAT_POWER, (int)FRBCH_OUT_STATS})
+    select_k2_priv(pl, pol, out_mode, plan_for(out_mode == FRBCH_OUT_STATS ? KID_K2S : KID_K2P));
+  select_k2_lane(pl, pol, plan_for(KID_K2));
+  return rc;
 }
 #else
 bool launch_kc_fast(frbch_handle*, KParams&, uint32_t, dev_stream_t) { return false; }
@@ -767,7 +705,7 @@ int launch_back(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
 #else
   const bool k3_sums = false;
 #endif
-  if ((!((pl.fast_k2_log2m || pl.fast_k2_m1) && pl.fast_k2_wave) || pl.coherent) && !k3_sums) p.stat_partial = nullptr;   // only the wave-private K2 / K3 sum while they write
+  if ((!k2_wave_planned(pl) || pl.coherent) && !k3_sums) p.stat_partial = nullptr;   // only the wave-private K2 / K3 sum while they write
   if (p.out_mode == FRBCH_OUT_STATS) {   // first pass of the two-pass rescale: the spill is read, nothing but the sums is written
     ProfScope ps(h, s, KID_K2S, (double)nb * (double)pl.n * 8.0);
     if (!launch_k2_fast(h, p, nb, s)) return fail(h, FRBCH_E_STATE, "statistics-only K2 pass without frbch_k2_priv");
@@ -788,7 +726,7 @@ int launch_back(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
       const int tc = pl.ncol < 64 ? (int)pl.ncol : 64;
       const int gx = (int)((pl.rows_per_block + 63) / 64) * (int)(pl.ncol / tc);
 #ifndef FRBCH_NO_FAST
-      if (pl.ncol % 64 == 0 && pl.rows_per_block % 2 == 0 && pl.c % 4 == 0 && !(h->cfg.flags & 2u))   // (flags & 2: the generic back end)
+      if (k4_fast_planned(pl, h->cfg.flags))
         hipLaunchKernelGGL(fast::frbch_k4_fast, dim3(gx, nb), dim3(256), 0, s, p);
       else
 #endif
@@ -818,7 +756,7 @@ int ensure_partial(frbch_handle* h) {
   h->partial_chunks = (int)std::min<uint64_t>(32768, std::max<uint64_t>(2048, (8ull << 20) / (pl.ncol * 16)));
   h->fused_chunks = 0;
 #ifndef FRBCH_NO_FAST
-  h->fused_chunks = fused_stat_chunks(pl, h->cfg.flags, h->cfg.pol_mode, h->priv_grid);   // flag bit 20 forces the separate statistics pass
+  h->fused_chunks = fused_stat_chunks(pl, h->cfg.flags, h->cfg.pol_mode, h->priv_grid);   // kFlagSeparateStats forces the separate statistics pass
 #endif
   const size_t chunks = (size_t)std::max(h->partial_chunks, h->fused_chunks);
   CHECK_DEV(h, dev_malloc((void**)&h->partial, chunks * pl.ncol * 2 * sizeof(double)), "hipMalloc(partials)");
@@ -996,6 +934,40 @@ int allow_generic_lds(frbch_handle* h) {
   if (pl.coherent) {
     CHECK_DEV(h, dev_allow_lds(frbch_k2c_chirp, pl.k2_lds), "LDS size K2c");
     CHECK_DEV(h, dev_allow_lds(frbch_k3_dedisp, pl.k3_lds), "LDS size K3");
+  }
+  return FRBCH_OK;
+}
+
+// Everything a handle derives from its plan: LDS limits, tables and timing-slot names of its kernels, the grid of frbch_k2_priv and
+// the buffers whose size follows the layout group or the kernel choice.  frbch_open calls it, and the host streaming path again
+// when the first frame of a stream makes it plan anew (1-bit samples): what an earlier call allocated is released first.
+int apply_plan(frbch_handle* h) {
+  const Plan& pl = h->pl;
+  cf** const tables[] = {&h->ftw1_r, &h->ftw2_r, &h->ftw1_c, &h->ftw2_c, &h->td1, &h->td2, &h->spill, &h->spill2, &h->chirp};
+  for (cf** t : tables) { dev_free(*t); *t = nullptr; }
+  dev_free(h->stg); h->stg = nullptr; h->stg_ready = false;
+  dev_free(h->scr2); h->scr2 = nullptr;
+  dev_free(h->ptmp); h->ptmp = nullptr;
+  dev_free(h->partial); h->partial = nullptr;   // (its rows follow the K2 of the plan: ensure_partial sizes it again)
+  h->partial_chunks = h->fused_chunks = 0;
+  h->fused_rows = 0;
+  h->fused_valid = false;
+  for (std::string& n : h->kname) n.clear();
+  int rc;
+  if ((rc = allow_generic_lds(h))) return rc;
+  h->priv_grid = pl.fast_k2_priv ? 2 * std::max(1, h->lane_ncu) : 0;   // two 80-KiB workgroups per CU
+  if ((rc = setup_fast(h))) return rc;
+  CHECK_DEV(h, dev_malloc((void**)&h->spill, (size_t)pl.maxb * (pl.c2 / pl.g) * pl.gs * sizeof(cf)), "hipMalloc(spill)");
+#ifndef FRBCH_NO_FAST
+  if (pl.k2_two_stage)
+    CHECK_DEV(h, dev_malloc((void**)&h->scr2, (size_t)pl.maxb * (pl.r / pl.k2_stage1_tscr) * pl.ncol * sizeof(float)), "hipMalloc(tscrunch scratch)");
+#endif
+  if (pl.coherent) {
+    CHECK_DEV(h, dev_malloc((void**)&h->spill2, (size_t)pl.maxb * pl.n * sizeof(cf)), "hipMalloc(spill2)");
+    CHECK_DEV(h, dev_malloc((void**)&h->chirp, (size_t)pl.n * sizeof(cf)), "hipMalloc(chirp)");
+    CHECK_DEV(h, dev_malloc((void**)&h->ptmp, (size_t)pl.maxb * pl.rows_per_block * pl.ncol * sizeof(float)), "hipMalloc(ptmp)");
+    if ((rc = build_chirp(h, pl.coh_fast_r ? (1 << pl.coh_fast_r) : 0))) return rc;
+    if (h->kname[KID_K2].empty()) h->kname[KID_K2] = "frbch_k2c_chirp";   // (the slot's own name is that of the incoherent K2)
   }
   return FRBCH_OK;
 }

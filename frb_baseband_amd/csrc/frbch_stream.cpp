@@ -211,13 +211,13 @@ int overlap_front_cus(const frbch_handle* h) {
   // 80 of 256 CUs for the digitiser make both take ~2.3 ms (1.55 + 1.14 one after the other): 39.5 -> 36.4 ms per 8-IF step of
   // config 3, the two together moving 5.2 TB/s.  One product (1.6 GB): what it hides is what K1 loses on fewer CUs: off.
   const Plan& pl = h->pl;
-  if (pl.nif == 4 && h->cfg.nbit_out == 8 && pl.fast_k1_log2m == 3 && pl.fast_k1_wave && h->lane_ncu >= 64)
+  if (pl.nif == 4 && h->cfg.nbit_out == 8 && k1_paired_planned(pl) && h->lane_ncu >= 64)
     return h->lane_ncu * 11 / 16 / 8 * 8;
   return 0;
 }
 bool overlap_usable(const frbch_handle* h) {
   const Plan& pl = h->pl;
-  return !pl.coherent && pl.fast_k1_log2m && pl.fast_k1_wave && (pl.fast_k2_log2m || pl.fast_k2_m1) && pl.fast_k2_wave &&
+  return !pl.coherent && pl.fast_k1_log2m && pl.fast_k1_wave && k2_wave_planned(pl) &&
          overlap_front_cus(h) >= 8;
 }
 

@@ -145,3 +145,19 @@ def test_few_channels_run_on_the_lane_kernel(hip_lib, nchan, want):
         c.channelise_bytes(raw)
         names = {k for k, v in c.get_timing().items() if v["launches"]}
     assert want in names and any(n.startswith("frbch_k1_wave<1") for n in names), names
+
+
+def test_one_bit_stream_replans_and_reports_its_kernels(hip_lib):
+    """A 1-bit stream through a handle opened with input_bits left at 0: the first frame makes the handle plan anew (the register-pass
+    K1 gathers 2-bit samples only; at R = 8192 the generic K1's layout group of one sends K2 to the generic kernel too).  The timing
+    report names the kernels of the new plan, and the output matches the oracle."""
+    from frb_baseband_amd import channeliser as ch, synth
+    raw = synth.make_vdif(0.55, bw_mhz=64.0, nchan=4096, bits=1)
+    with ch.Channeliser(pu.lib_cfg(hip_lib, 64.0, 4096, 0.55), hip_lib) as c:
+        c.set_profiling(True)
+        c.channelise_bytes(raw)
+        names = {k for k, v in c.get_timing().items() if v["launches"]}
+    print("slots with launches:", sorted(names))
+    assert "frbch_k1_branch" in names and "frbch_k2_chan" in names, names
+    assert not any("frbch_k2_wave" in n or "frbch_k1_wave" in n for n in names), names
+    pu.run_streaming_case(hip_lib, 64.0, 4096, 0.55, bits=1)
