@@ -60,6 +60,17 @@ class FrbchFilDesc(C.Structure):
                 ("fch1_mhz", C.c_double), ("foff_mhz", C.c_double), ("tsamp_s", C.c_double), ("tstart_mjd", C.c_double)]
 
 
+class FrbchPolycoSeg(C.Structure):
+    _fields_ = [("tmid_mjd", C.c_double), ("rphase_frac", C.c_double), ("f0_hz", C.c_double), ("span_min", C.c_double),
+                ("ncoeff", C.c_uint32), ("reserved", C.c_uint32), ("coeff", C.c_double * 15)]
+
+
+class FrbchFoldModel(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("nseg", C.c_uint32), ("seg", C.POINTER(FrbchPolycoSeg)),
+                ("f0_hz", C.c_double), ("f1", C.c_double), ("pepoch_mjd", C.c_double), ("doppler", C.c_double),
+                ("dm", C.c_double), ("apply_delays", C.c_uint32), ("nbin", C.c_uint32), ("subint_s", C.c_double)]
+
+
 class _KTiming(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double),
                 ("algorithmic_bytes", C.c_double)]
@@ -110,6 +121,10 @@ SYMBOLS = {
                                   C.c_uint32, C.c_uint32, C.c_double, C.c_int, _P, _P, C.c_uint32, C.c_char_p, C.c_size_t]),
     "frbch_fold_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double,
                                     C.c_uint32, C.c_uint32, C.c_double, C.c_int, _P, _P, C.c_uint32, C.c_char_p, C.c_size_t]),
+    "frbch_foldp_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchFoldModel), C.c_int, _P, _P,
+                                   C.c_uint32, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_foldp_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchFoldModel), C.c_int, _P, _P,
+                                     C.c_uint32, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
     "frbch_cornerturn_info": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
     "frbch_cornerturn_host": (C.c_int, [C.c_char_p, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(_P), C.c_uint32,

@@ -332,6 +332,219 @@ extern "C" int frbch_fold_host(const frbch_fil_desc* fil, const void* rows, uint
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// fold of every product with a phase model (polynomial + Doppler factor, or TEMPO polyco blocks)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+// the model as the kernels read it: blocks relative to the start of the file, first row of every block
+int foldp_model(const frbch_fil_desc* fil, uint64_t nrows, const frbch_fold_model* m, std::vector<FoldSeg>* seg,
+                std::vector<uint64_t>* seg_row, const PostErr& e) {
+  if (!m || m->size != sizeof(frbch_fold_model)) return e.fail(FRBCH_E_ARG, "frbch_fold_model: wrong size");
+  if (m->nbin < 2 || m->nbin > 65536) return e.fail(FRBCH_E_ARG, "nbin must be in [2, 65536]");
+  if (!m->nseg) {
+    if (!(m->f0_hz > 0)) return e.fail(FRBCH_E_ARG, "F0 must be positive");
+    if (!(m->doppler > -1.0) || !(m->doppler < 1.0)) return e.fail(FRBCH_E_ARG, "doppler must lie in (-1, 1)");
+    return FRBCH_OK;
+  }
+  if (!m->seg) return e.fail(FRBCH_E_ARG, "nseg > 0 without blocks");
+  if (m->doppler != 0.0) return e.fail(FRBCH_E_ARG, "doppler together with a polyco: a polyco is topocentric already");
+  const double last_s = (double)(nrows - 1) * fil->tsamp_s;
+  bool first_in = false, last_in = false;
+  for (uint32_t i = 0; i < m->nseg; ++i) {
+    const frbch_polyco_seg& g = m->seg[i];
+    if (g.ncoeff < 1 || g.ncoeff > 15) return e.fail(FRBCH_E_ARG, "polyco block " + std::to_string(i) + ": ncoeff must be 1..15");
+    if (!(g.span_min > 0) || !(g.f0_hz > 0)) return e.fail(FRBCH_E_ARG, "polyco block " + std::to_string(i) + ": span and F0 must be positive");
+    if (i && !(g.tmid_mjd > m->seg[i - 1].tmid_mjd)) return e.fail(FRBCH_E_ARG, "polyco blocks must be in ascending TMID order");
+    FoldSeg f;
+    memset(&f, 0, sizeof f);
+    f.dt0_min = (fil->tstart_mjd - g.tmid_mjd) * 1440.0;
+    f.rphase = g.rphase_frac;
+    f.f0 = g.f0_hz;
+    f.ncoeff = (int)g.ncoeff;
+    for (uint32_t k = 0; k < g.ncoeff; ++k) f.coeff[k] = g.coeff[k];
+    seg->push_back(f);
+    uint64_t first = 0;
+    if (i) {
+      const double x = ((0.5 * (m->seg[i - 1].tmid_mjd + g.tmid_mjd) - fil->tstart_mjd) * 86400.0) / fil->tsamp_s;
+      first = x <= 0.0 ? 0 : (x >= (double)nrows ? nrows : (uint64_t)ceil(x));
+    }
+    seg_row->push_back(first);
+    if (fabs(f.dt0_min) <= 0.5 * g.span_min) first_in = true;
+    if (fabs(f.dt0_min + last_s / 60.0) <= 0.5 * g.span_min) last_in = true;
+  }
+  if (!first_in || !last_in)
+    return e.fail(FRBCH_E_ARG, std::string(first_in ? "the last" : "the first") + " row lies outside the span of every polyco block");
+  return FRBCH_OK;
+}
+}  // namespace
+
+extern "C" int frbch_foldp_device(const frbch_fil_desc* fil_in, const void* d_rows, uint64_t nrows, const frbch_fold_model* m,
+                                  int device, double* d_profile, uint32_t* d_hits, uint32_t nsub, uint32_t* kernel_used,
+                                  char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  if (!fil_in || fil_in->size != sizeof(frbch_fil_desc)) return e.fail(FRBCH_E_ARG, "frbch_fil_desc: wrong size");
+  frbch_fil_desc fd = *fil_in;
+  fd.product = 0;                                          // every product is folded
+  const frbch_fil_desc* fil = &fd;
+  int rc = post_check_fil(fil, nrows, e);
+  if (rc) return rc;
+  if (fil->nifs > 4) return e.fail(FRBCH_E_ARG, "nifs must be 1..4");
+  if (!d_rows || !d_profile || !d_hits) return e.fail(FRBCH_E_ARG, "null argument");
+  std::vector<FoldSeg> seg;
+  std::vector<uint64_t> seg_row;
+  rc = foldp_model(fil, nrows, m, &seg, &seg_row, e);
+  if (rc) return rc;
+  const long want = frbch_fold_nsub(fil, nrows, m->subint_s);
+  if (want <= 0 || (uint32_t)want != nsub) return e.fail(FRBCH_E_CAPACITY, "nsub must be frbch_fold_nsub()");
+  if (device < 0 || device >= dev_count()) return e.fail(FRBCH_E_DEVICE, "no such GPU (there is no CPU fallback)");
+  DeviceGuard dg(device);
+  dev_stream_t s = 0;
+  if (dev_stream_create(&s) != 0) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  const uint32_t nbin = m->nbin;
+  const size_t nslot = (size_t)nsub * nbin * fil->nchan, nsum = nslot * fil->nifs;
+  unsigned long long* d_sum_i = nullptr;
+  double* d_dly = nullptr;
+  FoldSeg* d_seg = nullptr;
+  uint64_t* d_seg_row = nullptr;
+  uint32_t *d_slot = nullptr, *d_slot_hits = nullptr;
+  auto cleanup = [&]() {
+    dev_free(d_sum_i); dev_free(d_dly); dev_free(d_seg); dev_free(d_seg_row); dev_free(d_slot); dev_free(d_slot_hits);
+    dev_stream_destroy(s);
+  };
+#define POST_DEV(expr, what) do { if ((expr) != 0) { cleanup(); return e.fail(FRBCH_E_DEVICE, std::string(what) + ": " + dev_last_error_string()); } } while (0)
+  FoldpParams p;
+  memset(&p, 0, sizeof p);
+  p.rows = (const uint8_t*)d_rows;
+  p.nrows = nrows;
+  p.nchan = (int)fil->nchan; p.nifs = (int)fil->nifs; p.nbits = fil->nbits; p.nbin = (int)nbin;
+  p.hits = d_hits;
+  const bool integer_rows = fil->nbits != 32;
+  if (integer_rows) {      // exact uint64 sums, converted to double at the end
+    POST_DEV(dev_malloc((void**)&d_sum_i, nsum * sizeof(unsigned long long)), "hipMalloc");
+    POST_DEV(dev_memset(d_sum_i, 0, nsum * sizeof(unsigned long long), s), "clear sums");
+    p.prof_i = d_sum_i;
+  } else {
+    POST_DEV(dev_memset(d_profile, 0, nsum * sizeof(double), s), "clear profile");
+  }
+  p.prof_f = d_profile;
+  std::vector<double> dly;
+  if (m->apply_delays && m->dm != 0.0) {
+    dly.resize(fil->nchan);
+    for (uint32_t c = 0; c < fil->nchan; ++c) dly[c] = post_delay_s(fil, m->dm, c);
+    POST_DEV(dev_malloc((void**)&d_dly, dly.size() * sizeof(double)), "hipMalloc");
+    POST_DEV(dev_h2d(d_dly, dly.data(), dly.size() * sizeof(double), s), "upload delays");
+    p.chan_delay_s = d_dly;
+  }
+  if (!seg.empty()) {
+    POST_DEV(dev_malloc((void**)&d_seg, seg.size() * sizeof(FoldSeg)), "hipMalloc");
+    POST_DEV(dev_malloc((void**)&d_seg_row, seg_row.size() * sizeof(uint64_t)), "hipMalloc");
+    POST_DEV(dev_h2d(d_seg, seg.data(), seg.size() * sizeof(FoldSeg), s), "upload polyco blocks");
+    POST_DEV(dev_h2d(d_seg_row, seg_row.data(), seg_row.size() * sizeof(uint64_t), s), "upload block rows");
+    p.seg = d_seg;
+    p.seg_row = d_seg_row;
+    p.nseg = (int)seg.size();
+  }
+  p.t0_s = (fil->tstart_mjd - m->pepoch_mjd) * 86400.0;
+  p.tsamp_s = fil->tsamp_s;
+  p.f0 = m->f0_hz;
+  p.half_f1 = 0.5 * m->f1;
+  p.doppler = m->doppler;
+  p.rows_per_sub = std::max<uint64_t>(1, (uint64_t)llround(m->subint_s / fil->tsamp_s));
+  p.nsub = nsub;
+  uint32_t used = 0;
+#ifndef FRBCH_NO_FAST
+  {   // the LDS kernel: integer rows, the bin a function of the row only, a tile of >= 16 channels x nbin in the LDS
+    const int bpv = fil->nbits / 8;
+    int ct = 0, ct_log2 = 0;
+    for (int k = 8; k >= 4; --k)
+      if (fil->nchan % (1u << k) == 0 && (size_t)nbin * (1u << k) * sizeof(uint32_t) <= fast::kFoldLdsBudget) { ct = 1 << k; ct_log2 = k; break; }
+    const uint64_t row_cap = bpv == 1 ? (1ull << 24) : (1ull << 16);      // a uint32 sum of a run cannot overflow
+    if (integer_rows && !p.chan_delay_s && ct && ((uintptr_t)d_rows % 4) == 0 && (uint64_t)nsub * nbin < 0xFFFFFFFFull &&
+        (uint64_t)(fil->nchan / ct) * fil->nifs <= 65535) {
+      p.ct = ct;
+      p.ct_log2 = ct_log2;
+      p.ntile = (int)fil->nchan / ct;
+      const uint64_t nbase = (uint64_t)p.ntile * fil->nifs * nsub;          // workgroups with one row run per sub-integration
+      const uint64_t wg_goal = (uint64_t)fast::kFoldWgPerCu * std::max(1, dev_cu_count(device));
+      const uint64_t per_sub = std::max<uint64_t>(1, (wg_goal + nbase - 1) / nbase);
+      p.rows_per_chunk = std::min(row_cap, std::max<uint64_t>(fast::kFoldThreads, (p.rows_per_sub + per_sub - 1) / per_sub));
+      p.chunks_per_sub = (uint32_t)((p.rows_per_sub + p.rows_per_chunk - 1) / p.rows_per_chunk);
+      if ((uint64_t)nsub * p.chunks_per_sub <= 0x7FFFFFFFull) {
+        POST_DEV(dev_malloc((void**)&d_slot, nrows * sizeof(uint32_t)), "hipMalloc");
+        POST_DEV(dev_malloc((void**)&d_slot_hits, (size_t)nsub * nbin * sizeof(uint32_t)), "hipMalloc");
+        POST_DEV(dev_memset(d_slot_hits, 0, (size_t)nsub * nbin * sizeof(uint32_t), s), "clear slot counts");
+        p.slot = d_slot;
+        p.slot_hits = d_slot_hits;
+        p.nconv = nslot;
+        hipLaunchKernelGGL(fast::frbch_post_foldp_slots, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, s, p);
+        POST_DEV(dev_check_launch(), "launch fold slots");
+        hipLaunchKernelGGL(fast::frbch_post_foldp_hits, dim3((unsigned)((nslot + 255) / 256)), dim3(256), 0, s, p);
+        POST_DEV(dev_check_launch(), "launch fold hits");
+        const size_t lds = (size_t)nbin * ct * sizeof(uint32_t);
+        const dim3 grid((unsigned)((uint64_t)nsub * p.chunks_per_sub), (unsigned)(p.ntile * fil->nifs));
+        if (bpv == 1) {
+          POST_DEV(dev_allow_lds(fast::frbch_post_foldp_lds<1>, lds), "LDS size");
+          hipLaunchKernelGGL(fast::frbch_post_foldp_lds<1>, grid, dim3(fast::kFoldThreads), lds, s, p);
+        } else {
+          POST_DEV(dev_allow_lds(fast::frbch_post_foldp_lds<2>, lds), "LDS size");
+          hipLaunchKernelGGL(fast::frbch_post_foldp_lds<2>, grid, dim3(fast::kFoldThreads), lds, s, p);
+        }
+        POST_DEV(dev_check_launch(), "launch fold");
+        used = 1;
+      }
+    }
+  }
+#endif
+  if (!used) {
+    POST_DEV(dev_memset(d_hits, 0, nslot * sizeof(uint32_t), s), "clear hits");
+    p.rows_per_chunk = 512;
+    DEV_LAUNCH(frbch_post_foldp, (fil->nchan + 255) / 256, (nrows + p.rows_per_chunk - 1) / p.rows_per_chunk, 256, 0, s, p);
+    POST_DEV(dev_check_launch(), "launch fold");
+  }
+  if (integer_rows) {
+    p.prof_f = d_profile;
+    p.nconv = nsum;
+    DEV_LAUNCH(frbch_post_u64_to_f64, (nsum + 255) / 256, 1, 256, 0, s, p);
+    POST_DEV(dev_check_launch(), "launch convert");
+  }
+  POST_DEV(dev_sync(s), "sync");       // (also: the host vectors the uploads read stay alive until here)
+#undef POST_DEV
+  if (kernel_used) *kernel_used = used;
+  cleanup();
+  return FRBCH_OK;
+}
+
+extern "C" int frbch_foldp_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_fold_model* m, int device,
+                                double* profile, uint32_t* hits, uint32_t nsub, uint32_t* kernel_used, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  if (!fil || fil->size != sizeof(frbch_fil_desc)) return e.fail(FRBCH_E_ARG, "frbch_fil_desc: wrong size");
+  frbch_fil_desc fd = *fil;
+  fd.product = 0;
+  int rc = post_check_fil(&fd, nrows, e);
+  if (rc) return rc;
+  if (!rows || !profile || !hits) return e.fail(FRBCH_E_ARG, "null argument");
+  if (!m || m->size != sizeof(frbch_fold_model)) return e.fail(FRBCH_E_ARG, "frbch_fold_model: wrong size");
+  if (m->nbin < 2 || m->nbin > 65536) return e.fail(FRBCH_E_ARG, "nbin must be in [2, 65536]");
+  if (device < 0 || device >= dev_count()) return e.fail(FRBCH_E_DEVICE, "no such GPU (there is no CPU fallback)");
+  DeviceGuard dg(device);
+  const size_t in_bytes = (size_t)nrows * fil->nifs * fil->nchan * (size_t)(fil->nbits / 8);
+  const size_t nslot = (size_t)nsub * m->nbin * fil->nchan, nsum = nslot * fil->nifs;
+  void* d_rows = nullptr;
+  double* d_prof = nullptr;
+  uint32_t* d_hits = nullptr;
+  if (dev_malloc(&d_rows, in_bytes) != 0 || dev_malloc((void**)&d_prof, nsum * sizeof(double)) != 0 ||
+      dev_malloc((void**)&d_hits, nslot * sizeof(uint32_t)) != 0) {
+    dev_free(d_rows); dev_free(d_prof); dev_free(d_hits);
+    return e.fail(FRBCH_E_NOMEM, "device memory for the rows");
+  }
+  rc = dev_h2d(d_rows, rows, in_bytes, 0) != 0 || dev_sync(0) != 0 ? e.fail(FRBCH_E_DEVICE, "upload rows") : FRBCH_OK;
+  if (!rc) rc = frbch_foldp_device(fil, d_rows, nrows, m, device, d_prof, d_hits, nsub, kernel_used, err, err_cap);
+  if (!rc && (dev_d2h(profile, d_prof, nsum * sizeof(double), 0) != 0 || dev_d2h(hits, d_hits, nslot * sizeof(uint32_t), 0) != 0 || dev_sync(0) != 0))
+    rc = e.fail(FRBCH_E_DEVICE, "download profile");
+  dev_free(d_rows); dev_free(d_prof); dev_free(d_hits);
+  return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // corner turn
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {

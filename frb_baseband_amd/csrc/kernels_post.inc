@@ -155,6 +155,139 @@ KERNEL(frbch_post_fold, PostParams) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Fold of EVERY product of the rows in one pass, with a phase model (frbch_foldp_*): either the F0 / F1 / PEPOCH polynomial
+// of post_bin (optionally with a constant Doppler factor) or the blocks of a TEMPO polyco -- the predictor dspsr itself
+// folds with (base2fil.sh:474), which carries the barycentric, binary and position terms.
+// ---------------------------------------------------------------------------------------------------------------------
+struct FoldSeg {               // one polyco block, times relative to the start of the file
+  double dt0_min;              // (tstart - TMID) * 1440
+  double rphase, f0;           // RPHASE reduced to [0, 1), reference rotation frequency
+  double coeff[15];
+  int ncoeff, pad;
+};
+
+struct FoldpParams {
+  const uint8_t* rows;         // [nrows][nifs][nchan] samples of `nbits`
+  uint64_t nrows;
+  int nchan, nifs, nbits, nbin;
+  unsigned long long* prof_i;  // [nsub][nifs][nbin][nchan] sums (integer rows)
+  double* prof_f;              // same for float rows; for frbch_post_u64_to_f64: where the integer sums go as doubles
+  uint64_t nconv;              // frbch_post_u64_to_f64: entries
+  uint32_t* hits;              // [nsub][nbin][nchan], shared by the products
+  const double* chan_delay_s;  // [nchan] or null, as PostParams
+  double t0_s, tsamp_s, f0, half_f1, doppler;   // nseg = 0: the polynomial of post_bin, tau stretched by (1 + doppler)
+  const FoldSeg* seg;          // [nseg] ascending TMID
+  const uint64_t* seg_row;     // [nseg] first row of every block (seg_row[0] = 0); the kernels only compare row numbers
+  int nseg;
+  uint32_t nsub;
+  uint64_t rows_per_sub, rows_per_chunk;
+  // ---- LDS kernel (kernels_post_fast.inc) ----
+  uint32_t* slot;              // [nrows] sub * nbin + bin of every row (no per-channel delays: the bin depends on the row only)
+  uint32_t* slot_hits;         // [nsub * nbin] rows per slot
+  int ct, ct_log2, ntile;      // channels per tile (a power of two), tiles per row
+  uint32_t chunks_per_sub;
+};
+
+DEVFN inline double foldp_sample(const FoldpParams& p, uint64_t t, int q, int c) {
+  const uint64_t i = (t * (uint64_t)p.nifs + (uint64_t)q) * (uint64_t)p.nchan + (uint64_t)c;
+  if (p.nbits == 8) return (double)p.rows[i];
+  if (p.nbits == 16) return (double)((const uint16_t*)p.rows)[i];
+  return (double)((const float*)p.rows)[i];
+}
+
+// Phase of row t (channel c) in polyco block s -- TEMPO's PHASE = RPHASE + DT 60 F0 + C1 + DT C2 + DT^2 C3 + ..., DT in minutes:
+//   sec = t tsamp [- delay_c];  dt = (tstart - TMID_s) 1440 + sec / 60;  turns = (rphase + (dt 60) f0) + horner(coeff, dt),
+// Horner from the highest coefficient down.  nseg = 0: post_bin's tau, then tau + tau doppler when doppler != 0.  Every
+// operation is rounded on its own (no contraction), so a numpy restatement gives the same bin bit for bit.
+DEVFN inline int foldp_bin(const FoldpParams& p, uint64_t t, int c, int s) {
+  POST_NO_CONTRACT
+  const double tt = (double)t * p.tsamp_s;
+  double turns;
+  if (p.nseg) {
+    double sec = tt;
+    if (p.chan_delay_s) sec = sec - p.chan_delay_s[c];
+    const FoldSeg& g = p.seg[s];
+    const double dt = g.dt0_min + sec / 60.0;
+    double h = g.coeff[g.ncoeff - 1];
+    for (int i = g.ncoeff - 2; i >= 0; --i) {
+      const double hd = h * dt;
+      h = hd + g.coeff[i];
+    }
+    const double lin = (dt * 60.0) * g.f0;
+    const double lead = g.rphase + lin;
+    turns = lead + h;
+  } else {
+    double tau = p.t0_s + tt;
+    if (p.chan_delay_s) tau = tau - p.chan_delay_s[c];
+    if (p.doppler != 0.0) {
+      const double stretch = tau * p.doppler;
+      tau = tau + stretch;
+    }
+    const double a = p.f0 * tau;
+    const double b = (p.half_f1 * tau) * tau;
+    turns = a + b;
+  }
+  const double fr = turns - floor(turns);
+  int bin = (int)(fr * (double)p.nbin);
+  if (bin >= p.nbin) bin = p.nbin - 1;
+  return bin;
+}
+
+DEVFN inline void foldp_flush(const FoldpParams& p, long long slot, int c, const double* acc, uint32_t n) {
+  const long long sub = slot / p.nbin, bin = slot - sub * p.nbin;
+  for (int q = 0; q < p.nifs; ++q) {
+    const size_t i = (((size_t)sub * p.nifs + q) * p.nbin + (size_t)bin) * p.nchan + c;
+    if (p.prof_i) ATOMIC_ADD_U64(p.prof_i + i, (unsigned long long)acc[q]);
+    else ATOMIC_ADD_F64(p.prof_f + i, acc[q]);
+  }
+  ATOMIC_ADD_U32(p.hits + (size_t)slot * p.nchan + c, n);
+}
+
+// profile[sub][product][bin][chan] += value, hits[sub][bin][chan] += 1: the grid and the run-length accumulation of
+// frbch_post_fold; a thread loads the nifs (<= 4) products of its channel per row and computes the phase once for them all.
+KERNEL(frbch_post_foldp, FoldpParams) {
+  K_PROLOGUE;
+  (void)smem;
+  PHASE {
+    const int c = bx * nthr + tid;
+    if (c < p.nchan) {
+      const uint64_t r0 = (uint64_t)by * p.rows_per_chunk;
+      const uint64_t r1 = r0 + p.rows_per_chunk < p.nrows ? r0 + p.rows_per_chunk : p.nrows;
+      long long cur = -1;
+      double acc[4] = {0.0, 0.0, 0.0, 0.0};
+      uint32_t n = 0;
+      int s = 0;
+      for (uint64_t t = r0; t < r1; ++t) {
+        const uint64_t sub = t / p.rows_per_sub;
+        if (sub >= p.nsub) break;
+        while (s + 1 < p.nseg && p.seg_row[s + 1] <= t) ++s;
+        const long long slot = (long long)sub * p.nbin + foldp_bin(p, t, c, s);
+        if (slot != cur) {
+          if (n) foldp_flush(p, cur, c, acc, n);
+          cur = slot;
+          acc[0] = acc[1] = acc[2] = acc[3] = 0.0;
+          n = 0;
+        }
+        for (int q = 0; q < p.nifs; ++q) acc[q] += foldp_sample(p, t, q, c);      // (integer rows: < 2^53, exact)
+        ++n;
+      }
+      if (n) foldp_flush(p, cur, c, acc, n);
+    }
+  }
+}
+
+// the exact integer sums as doubles (every value < 2^53).  grid (ceil(nconv / 256), 1)
+KERNEL(frbch_post_u64_to_f64, FoldpParams) {
+  K_PROLOGUE;
+  (void)smem;
+  (void)by;
+  PHASE {
+    const uint64_t i = (uint64_t)bx * nthr + tid;
+    if (i < p.nconv) p.prof_f[i] = (double)p.prof_i[i];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Corner turn (SURVEY 8f row 2): what jive5ab's spif2file does with the recipe strings of spif2file.sh:31-113 -- one
 // recorder stream in which every W-bit word holds one time sample of ALL channels is split into one 2-channel stream
 // per IF ("tag"): output group g takes bits src[g][0..glen) of every word, in that order, LSB first.

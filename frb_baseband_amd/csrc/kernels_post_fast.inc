@@ -80,4 +80,113 @@ __global__ void __launch_bounds__(256) frbch_post_dedisp_tiled(PostParams p) {
       }
   }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// All-product fold in the LDS (HIP only; frbch_post_foldp of kernels_post.inc stays the emulable form and the fallback).
+// The production form: integer rows, no per-channel delays (what dspsr does with a filterbank), so the bin depends on the
+// row only.  frbch_post_foldp_slots computes slot[t] = sub * nbin + bin ONCE per row (nchan times fewer fp64 phases) and
+// counts the rows of every slot -- the hits are the same for every channel, frbch_post_foldp_hits copies them out.
+// frbch_post_foldp_lds: a workgroup of 1024 threads owns (one product, a tile of CT channels, a run of rows inside one
+// sub-integration) and keeps uint32 acc[nbin][CT] in the LDS.  A lane owns one dword of the row piece (4 / 2 channels of
+// 8- / 16-bit samples); the CT * BPV / 4 lanes of a row piece sit side by side, and the 1024 / that many lane groups each
+// walk a contiguous share of the run, 8 rows in flight per lane (non-temporal dword loads), summing in registers while
+// the slot stays the same (a bin lasts several rows) and adding to the LDS when it changes.  Lane l's value k of bin b
+// lives at column (k LPR + l + b LPR) mod CT: lanes of one row piece hit consecutive banks, and lane groups of one wave
+// that are in different bins are rotated apart.  At the end every non-zero (bin, channel) goes to the 64-bit global sums
+// with one atomic.  Integer sums are exact in any order: the result equals the generic kernel's to the bit.
+constexpr int kFoldThreads = 1024, kFoldUnroll = 8;
+constexpr size_t kFoldLdsBudget = 128 * 1024;      // acc[nbin][CT] (of 160 KiB per CU)
+constexpr int kFoldWgPerCu = 2;                    // row runs are sized for about this many workgroups per CU
+constexpr uint32_t kFoldNoSlot = 0xFFFFFFFFu;
+
+__global__ void __launch_bounds__(256) frbch_post_foldp_slots(FoldpParams p) {
+  const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= p.nrows) return;
+  const uint64_t sub = t / p.rows_per_sub;               // < nsub = ceil(nrows / rows_per_sub)
+  int s = 0;
+  while (s + 1 < p.nseg && p.seg_row[s + 1] <= t) ++s;
+  const uint32_t slot = (uint32_t)sub * (uint32_t)p.nbin + (uint32_t)foldp_bin(p, t, 0, s);
+  p.slot[t] = slot;
+  atomicAdd(p.slot_hits + slot, 1u);
+}
+
+__global__ void __launch_bounds__(256) frbch_post_foldp_hits(FoldpParams p) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;      // over [nsub * nbin][nchan]
+  if (i < p.nconv) p.hits[i] = p.slot_hits[i / (uint64_t)p.nchan];
+}
+
+// grid (nsub * chunks_per_sub, ntile * nifs)
+template <int BPV>
+__global__ void __launch_bounds__(kFoldThreads) frbch_post_foldp_lds(FoldpParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint32_t* acc = reinterpret_cast<uint32_t*>(smem);                    // [nbin][CT], columns rotated by bin * LPR
+  constexpr int VPL = 4 / BPV;                                          // values per lane (one dword)
+  const int tid = threadIdx.x;
+  const int ct = p.ct, cmask = ct - 1, lpr = ct / VPL, nrg = kFoldThreads / lpr;
+  const int tile = blockIdx.y % p.ntile, prod = blockIdx.y / p.ntile;
+  const uint32_t sub = blockIdx.x / p.chunks_per_sub, chunk = blockIdx.x % p.chunks_per_sub;
+  const uint64_t s0 = (uint64_t)sub * p.rows_per_sub;
+  const uint64_t s1 = s0 + p.rows_per_sub < p.nrows ? s0 + p.rows_per_sub : p.nrows;
+  const uint64_t r0 = s0 + (uint64_t)chunk * p.rows_per_chunk;
+  if (r0 >= s1) return;                                                 // (the last sub-integration may be short; whole workgroup)
+  const uint64_t r1 = r0 + p.rows_per_chunk < s1 ? r0 + p.rows_per_chunk : s1;
+  const int nacc = p.nbin * ct;
+  for (int i = tid; i < nacc; i += kFoldThreads) acc[i] = 0u;
+  __syncthreads();
+  const int g = tid / lpr, l = tid % lpr;
+  const uint64_t rpg = (r1 - r0 + (uint64_t)nrg - 1) / (uint64_t)nrg;   // rows per lane group
+  const uint64_t tb = r0 + (uint64_t)g * rpg;
+  const uint64_t te = tb + rpg < r1 ? tb + rpg : r1;
+  const size_t stride = (size_t)p.nifs * p.nchan * BPV;                 // bytes between rows of the file
+  const unsigned char* src = p.rows + ((size_t)prod * p.nchan + (size_t)tile * ct) * BPV + (size_t)l * 4;
+  const uint32_t base = sub * (uint32_t)p.nbin;
+  uint32_t cur = kFoldNoSlot;
+  uint32_t a[VPL];
+#pragma unroll
+  for (int k = 0; k < VPL; ++k) a[k] = 0u;
+  auto to_lds = [&]() {
+    if (cur == kFoldNoSlot) return;
+    const int b = (int)(cur - base);
+#pragma unroll
+    for (int k = 0; k < VPL; ++k)
+      if (a[k]) atomicAdd(acc + b * ct + ((k * lpr + l + b * lpr) & cmask), a[k]);
+  };
+  for (uint64_t t = tb; t < te; t += kFoldUnroll) {
+    uint32_t v[kFoldUnroll], sl[kFoldUnroll];
+#pragma unroll
+    for (int u = 0; u < kFoldUnroll; ++u) {
+      const bool in = t + u < te;
+      v[u] = in ? __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(src + (t + u) * stride)) : 0u;
+      sl[u] = in ? p.slot[t + u] : kFoldNoSlot;
+    }
+#pragma unroll
+    for (int u = 0; u < kFoldUnroll; ++u) {
+      if (sl[u] == kFoldNoSlot) continue;                               // past the end of this lane group's rows
+      if (sl[u] != cur) {
+        to_lds();
+        cur = sl[u];
+#pragma unroll
+        for (int k = 0; k < VPL; ++k) a[k] = 0u;
+      }
+      if constexpr (BPV == 1) {
+        a[0] += v[u] & 0xFFu;
+        a[1] += (v[u] >> 8) & 0xFFu;
+        a[2] += (v[u] >> 16) & 0xFFu;
+        a[3] += v[u] >> 24;
+      } else {
+        a[0] += v[u] & 0xFFFFu;
+        a[1] += v[u] >> 16;
+      }
+    }
+  }
+  to_lds();
+  __syncthreads();
+  unsigned long long* dst = p.prof_i + (((size_t)sub * p.nifs + prod) * p.nbin) * p.nchan + (size_t)tile * ct;
+  for (int i = tid; i < nacc; i += kFoldThreads) {
+    const int b = i >> p.ct_log2, ch = i & cmask;
+    const int pos = (ch % VPL) * lpr + ch / VPL;                        // channel ch = value ch % VPL of lane ch / VPL
+    const uint32_t v = acc[b * ct + ((pos + b * lpr) & cmask)];
+    if (v) atomicAdd(dst + (size_t)b * p.nchan + ch, (unsigned long long)v);
+  }
+}
 }  // namespace fast

@@ -7,7 +7,10 @@ reference's `dspsr -E <par> ... <IFall.fil>` stage) of SIGPROC filterbank files,
   topocentric, unweighted.
 * ``fold_fil`` mirrors base2fil.sh:465-493: spin parameters from a psrcat-style .par file, 10-s sub-integrations,
   the filterbank's channels, plus the plot (PNG) of the dedispersed, time- and frequency-scrunched profile that
-  ``psrplot -pF ... -j dedisperse,tscrunch,pscrunch,"fscrunch 128"`` draws.
+  ``psrplot -pF ... -j dedisperse,tscrunch,pscrunch,"fscrunch 128"`` draws.  Files with several products (``--pol 4``)
+  are folded in ALL products in one pass (``fold_all``), optionally with the TEMPO polyco predictor that tempo / tempo2
+  make from the .par file (``read_polyco``: barycentric, binary and position terms, as dspsr folds) or a constant
+  Doppler factor, and give the 2x2 full-polarisation plot of base2fil.sh:481-491 as well.
 There is no CPU fallback: the sums run in libfrbch.so on a gfx950 device.
 """
 from __future__ import annotations
@@ -196,6 +199,139 @@ def fold(fil: sigproc.SigprocFile, par: dict, nbin: int = 0, subint_s: float = 1
     return prof.transpose(0, 2, 1).copy(), hits.transpose(0, 2, 1).copy(), nbin
 
 
+def _num(text: str) -> float:
+    return float(text.replace("D", "E").replace("d", "e"))
+
+
+def read_polyco(path: str) -> list:
+    """Blocks of a TEMPO ``polyco.dat`` (what ``tempo -z`` and ``tempo2 -f <par> -polyco "..." -tempo1`` write), parsed by
+    whitespace, ``D`` exponents accepted.  Line 1: name, date, UTC, TMID, DM, Doppler, log10 rms; line 2: RPHASE, F0,
+    site, span (minutes), ncoeff, observing frequency, then the optional binary phase and frequency; then
+    ceil(ncoeff / 3) lines of coefficients.  ``rphase`` is the FRACTION of RPHASE in [0, 1), taken from the text in
+    decimal arithmetic: a 1e10-turn RPHASE keeps all of its fraction (``rphase_turns`` is the whole number dropped)."""
+    import decimal
+    with open(path) as f:
+        lines = [ln.split() for ln in f if ln.strip()]
+    segs, i = [], 0
+    while i < len(lines):
+        if i + 1 >= len(lines) or len(lines[i]) < 5 or len(lines[i + 1]) < 6:
+            raise InputError(f"{path}: truncated polyco block at line {i + 1}")
+        a, b = lines[i], lines[i + 1]
+        try:
+            ncoeff = int(b[4])
+            if not 1 <= ncoeff <= 15:
+                raise InputError(f"{path}: {ncoeff} coefficients in a block (1..15)")
+            nlines = (ncoeff + 2) // 3
+            coeff = [_num(w) for ln in lines[i + 2: i + 2 + nlines] for w in ln]
+            if len(coeff) != ncoeff:
+                raise InputError(f"{path}: block at line {i + 1} holds {len(coeff)} coefficients, header says {ncoeff}")
+            with decimal.localcontext() as ctx:
+                ctx.prec = 60
+                r = decimal.Decimal(b[0].replace("D", "E").replace("d", "e"))
+                whole = r.to_integral_value(rounding=decimal.ROUND_FLOOR)
+                frac = float(r - whole)
+            if frac >= 1.0:                       # (a negative fraction below 1 ulp of 1.0)
+                frac = 0.0
+            seg = {"psr": a[0], "date": a[1], "utc": a[2], "tmid": _num(a[3]), "dm": _num(a[4]),
+                   "doppler": _num(a[5]) if len(a) > 5 else 0.0, "log10rms": _num(a[6]) if len(a) > 6 else 0.0,
+                   "rphase": frac, "rphase_turns": int(whole), "f0": _num(b[1]), "site": b[2], "span": _num(b[3]),
+                   "ncoeff": ncoeff, "obsfreq": _num(b[5]),
+                   "binphase": _num(b[6]) if len(b) > 6 else None, "binfreq": _num(b[7]) if len(b) > 7 else None,
+                   "coeff": coeff}
+        except ValueError as exc:
+            raise InputError(f"{path}: bad number in the polyco block at line {i + 1}: {exc}") from exc
+        segs.append(seg)
+        i += 2 + nlines
+    if not segs:
+        raise InputError(f"{path}: no polyco blocks")
+    return segs
+
+
+def fold_model(par: dict, hdr: dict, *, polyco=None, doppler: float = 0.0, nbin: int, subint_s: float, apply_delays: bool):
+    """-> (FrbchFoldModel, the ctypes block array it points to: keep it alive for the call)"""
+    m = _lib.FrbchFoldModel()
+    m.size = C.sizeof(_lib.FrbchFoldModel)
+    segs = read_polyco(polyco) if isinstance(polyco, (str, os.PathLike)) else (polyco or [])
+    arr = (_lib.FrbchPolycoSeg * max(1, len(segs)))()
+    for dst, g in zip(arr, segs):
+        dst.tmid_mjd, dst.rphase_frac, dst.f0_hz, dst.span_min = g["tmid"], g["rphase"], g["f0"], g["span"]
+        dst.ncoeff = g.get("ncoeff", len(g["coeff"]))          # (the library refuses anything outside 1..15)
+        for k, v in enumerate(g["coeff"][:15]):
+            dst.coeff[k] = v
+    m.nseg = len(segs)
+    m.seg = C.cast(arr, C.POINTER(_lib.FrbchPolycoSeg)) if segs else None
+    m.f0_hz = par.get("F0") or (segs[0]["f0"] if segs else 0.0)
+    m.f1 = par.get("F1", 0.0) or 0.0
+    m.pepoch_mjd = par["PEPOCH"] if par.get("PEPOCH") is not None else hdr["tstart"]
+    m.doppler = float(doppler)
+    m.dm = par.get("DM", 0.0) or 0.0
+    m.apply_delays = 1 if apply_delays else 0
+    m.nbin = nbin
+    m.subint_s = float(subint_s)
+    return m, arr
+
+
+def fold_all(fil: sigproc.SigprocFile, par: dict, *, polyco=None, doppler: float = 0.0, nbin: int = 0, subint_s: float = 10.0,
+             apply_delays: bool = False, device: int = 0, lib=None, info: dict | None = None):
+    """Every product of the file in one pass -> (profile float64 [nsub][nprod][nchan][nbin] sums, hits uint32
+    [nsub][nchan][nbin] shared by the products, nbin).  ``polyco``: a TEMPO polyco file or the blocks ``read_polyco``
+    returns -- the phase then follows the predictor (``par`` supplies DM, and F0 for the default nbin); otherwise the
+    F0 / F1 / PEPOCH polynomial of ``fold``, with ``doppler`` = observed / intrinsic spin frequency - 1 applied to the
+    elapsed time.  ``info['kernel_used']`` receives 1 when the LDS kernel ran, 0 for the generic one."""
+    lib = lib or _lib.load()
+    rows = _rows_of(fil)
+    desc = fil_desc(fil.header)
+    segs = read_polyco(polyco) if isinstance(polyco, (str, os.PathLike)) else polyco
+    f0 = par.get("F0") or (segs[0]["f0"] if segs else 0.0)
+    nbin = nbin or default_nbin(f0, fil.header["tsamp"])
+    model, _keep = fold_model(par, fil.header, polyco=segs, doppler=doppler, nbin=nbin, subint_s=subint_s, apply_delays=apply_delays)
+    nsub = lib.frbch_fold_nsub(C.byref(desc), rows.shape[0], float(subint_s))
+    if nsub <= 0:
+        raise InputError("bad sub-integration length")
+    prof = np.zeros((nsub, desc.nifs, nbin, desc.nchan), dtype=np.float64)
+    hits = np.zeros((nsub, nbin, desc.nchan), dtype=np.uint32)
+    err = C.create_string_buffer(512)
+    used = C.c_uint32(0)
+    _check(lib.frbch_foldp_host(C.byref(desc), rows.ctypes.data, rows.shape[0], C.byref(model), device, prof.ctypes.data,
+                                hits.ctypes.data, nsub, C.byref(used), err, len(err)), err)
+    if info is not None:
+        info["kernel_used"] = used.value
+    return prof.transpose(0, 1, 3, 2).copy(), hits.transpose(0, 2, 1).copy(), nbin
+
+
+def stokes(prof: np.ndarray, products: str = "coherency", axis: int = 1) -> np.ndarray:
+    """Folded products -> Stokes I, Q, U, V along ``axis`` (4 long).  ``coherency``: PP, QQ, Re(PQ*), Im(PQ*) of a `-d4`
+    file, circular basis (include/frbch.h): I = PP + QQ, Q = 2 Re(PQ*), U = 2 Im(PQ*), V = PP - QQ.  ``stokes``: the file
+    holds I, Q, U, V already (the IQUV extension) and passes through.
+
+    A rescaled 8- or 16-bit file has had the bandpass offset and scale of EVERY product removed separately before
+    digitising, so the products no longer share one flux scale: the Stokes parameters keep their shape in phase (pulse
+    position, PA swing sign changes), but polarisation FRACTIONS (L / I, V / I) are faithful only for `-I0` (no rescale)
+    or float output."""
+    prof = np.asarray(prof)
+    if prof.shape[axis] != 4:
+        raise InputError(f"Stokes parameters need 4 products, not {prof.shape[axis]}")
+    if products == "stokes":
+        return prof
+    if products != "coherency":
+        raise InputError("products must be 'coherency' or 'stokes'")
+    pp, qq, re, im = (np.take(prof, k, axis=axis) for k in range(4))
+    return np.stack([pp + qq, 2.0 * re, 2.0 * im, pp - qq], axis=axis)
+
+
+def remove_baseline(profiles: np.ndarray) -> np.ndarray:
+    """subtract each product's off-pulse level (the median over phase: the pulse fills well under half a turn) -- last axis = bins"""
+    p = np.asarray(profiles, dtype=np.float64)
+    return p - np.median(p, axis=-1, keepdims=True)
+
+
+def linear_pa(iquv: np.ndarray):
+    """[4][nbin] Stokes profiles -> (I, L, V, PA in radians) with the off-pulse baseline of every product removed;
+    L = sqrt(Q^2 + U^2), PA = atan2(U, Q) / 2"""
+    i, q, u, v = remove_baseline(iquv)
+    return i, np.hypot(q, u), v, 0.5 * np.arctan2(u, q)
+
+
 def dedisperse_profile(prof: np.ndarray, hdr: dict, f0: float, dm: float) -> np.ndarray:
     """rotate every channel's profile by its dispersion delay (nearest bin): `psrplot -j dedisperse`"""
     nsub, nchan, nbin = prof.shape
@@ -213,7 +349,8 @@ ARCHIVE_MAGIC = b"FRBFOLD1"
 
 
 def write_archive(path: str, prof: np.ndarray, hits: np.ndarray, meta: dict) -> None:
-    """one file: magic, JSON header (length-prefixed), float64 sums [nsub][nchan][nbin], uint32 hits"""
+    """one file: magic, JSON header (length-prefixed), float64 sums [nsub][nchan][nbin] -- [nsub][nprod][nchan][nbin] when
+    the header has "nprod" --, uint32 hits [nsub][nchan][nbin]"""
     head = json.dumps(meta, sort_keys=True).encode()
     with open(path, "wb") as f:
         f.write(ARCHIVE_MAGIC + struct.pack("<I", len(head)) + head)
@@ -230,6 +367,11 @@ def read_archive(path: str):
     meta = json.loads(buf[12:12 + n].decode())
     shape = (meta["nsub"], meta["nchan"], meta["nbin"])
     cnt = shape[0] * shape[1] * shape[2]
+    if "nprod" in meta:       # every product: sums [nsub][nprod][nchan][nbin], then the hits they share
+        pshape = (meta["nsub"], meta["nprod"], meta["nchan"], meta["nbin"])
+        prof = np.frombuffer(buf, dtype="<f8", count=cnt * meta["nprod"], offset=12 + n).reshape(pshape)
+        hits = np.frombuffer(buf, dtype="<u4", count=cnt, offset=12 + n + 8 * cnt * meta["nprod"]).reshape(shape)
+        return prof, hits, meta
     prof = np.frombuffer(buf, dtype="<f8", count=cnt, offset=12 + n).reshape(shape)
     hits = np.frombuffer(buf, dtype="<u4", count=cnt, offset=12 + n + 8 * cnt).reshape(shape)
     return prof, hits, meta
@@ -251,24 +393,12 @@ def write_png(path: str, img: np.ndarray) -> None:
         f.write(png)
 
 
-def fold_fil(filterbankfile: str, parfile: str, nbin: int = 0, subint_s: float = 10.0, fscrunch_to: int = 128,
-             device: int = 0, lib=None, out_base: str | None = None):
-    """base2fil.sh:465-493 for one filterbank: fold with the ephemeris, write ``<fil>.ar`` (FRBFOLD1), the profile as
-    text (``<fil>.profile.txt``: bin, mean flux of the dedispersed, scrunched profile) and the phase-frequency plot
-    ``<fil>.png`` (dedispersed, time-scrunched, frequency-scrunched to ``fscrunch_to`` channels, profile strip on top)."""
-    fil = sigproc.read_fil(filterbankfile)
-    par = read_par(parfile)
-    prof, hits, nbin = fold(fil, par, nbin=nbin, subint_s=subint_s, apply_delays=False, device=device, lib=lib)
-    base = out_base or filterbankfile
-    hdr = fil.header
-    meta = {"source": par["PSR"], "f0": par["F0"], "f1": par["F1"], "dm": par["DM"],
-            "pepoch": par["PEPOCH"] if par["PEPOCH"] is not None else hdr["tstart"], "dedispersed": False,
-            "nsub": int(prof.shape[0]), "nchan": int(prof.shape[1]), "nbin": int(nbin), "subint_s": subint_s,
-            "tstart": hdr["tstart"], "tsamp": hdr["tsamp"], "fch1": hdr["fch1"], "foff": hdr["foff"],
-            "timing": "topocentric polynomial F0, F1 about PEPOCH (no barycentric, binary or position terms)"}
-    write_archive(base + ".ar", prof, hits, meta)
-    dd = dedisperse_profile(prof, hdr, par["F0"], par["DM"])
-    hh = dedisperse_profile(hits.astype(np.float64), hdr, par["F0"], par["DM"])
+def _scrunched(prof, hits, hdr, f0, dm, fscrunch_to):
+    """`psrplot -j dedisperse,tscrunch,"fscrunch N"`: [nsub][nchan][nbin] sums and hits -> (mean sample [nf][nbin], the
+    frequency-scrunched mean profile [nbin])"""
+    nbin = prof.shape[2]
+    dd = dedisperse_profile(prof, hdr, f0, dm)
+    hh = dedisperse_profile(hits.astype(np.float64), hdr, f0, dm)
     tot, cnt = dd.sum(axis=0), hh.sum(axis=0)                                   # tscrunch
     nchan = tot.shape[0]
     fs = max(1, nchan // max(1, min(fscrunch_to, nchan)))
@@ -277,19 +407,114 @@ def fold_fil(filterbankfile: str, parfile: str, nbin: int = 0, subint_s: float =
     cnt_f = cnt[: nf * fs].reshape(nf, fs, nbin).sum(axis=1)
     mean_f = np.where(cnt_f > 0, tot_f / np.maximum(cnt_f, 1), 0.0)
     profile = np.where(cnt.sum(axis=0) > 0, tot.sum(axis=0) / np.maximum(cnt.sum(axis=0), 1), 0.0)
+    return mean_f, profile
+
+
+def _unit(img):
+    img = img - img.mean(axis=1, keepdims=True)
+    return (img - img.min()) / max(1e-30, img.max() - img.min())
+
+
+def _trace_panel(i, l, v, pa, height):
+    """the Stokes profile panel of `psrplot -p stokes`-style plots as a raster: PA (where L stands out of its off-pulse
+    scatter) in the top quarter, I (white), L (light grey) and V (mid grey) below on one flux scale"""
+    nbin = i.size
+    img = np.zeros((height, nbin))
+    top = max(4, height // 4)
+    sig = 1.4826 * np.median(np.abs(l - np.median(l)))
+    for b in np.nonzero(l > np.median(l) + 5.0 * max(sig, 1e-30))[0]:
+        img[int(round((0.5 - pa[b] / np.pi) * (top - 1))), b] = 1.0
+    lo, hi = min(i.min(), v.min(), 0.0), max(i.max(), l.max(), v.max())
+    rows = height - top - 1
+    for curve, grey in ((v, 0.45), (l, 0.7), (i, 1.0)):
+        y = top + rows - np.rint((curve - lo) / max(1e-30, hi - lo) * rows).astype(int)
+        for b in range(nbin):
+            y0, y1 = sorted((y[b], y[min(b + 1, nbin - 1)]))                     # (joined to the next bin)
+            img[y0: y1 + 1, b] = grey
+    return img
+
+
+def fold_fil(filterbankfile: str, parfile: str, nbin: int = 0, subint_s: float = 10.0, fscrunch_to: int = 128,
+             device: int = 0, lib=None, out_base: str | None = None, polyco: str | None = None, doppler: float = 0.0,
+             products: str = "coherency"):
+    """base2fil.sh:465-493 for one filterbank: fold with the ephemeris, write ``<fil>.ar`` (FRBFOLD1), the profile as
+    text (``<fil>.profile.txt``: bin, mean flux of the dedispersed, scrunched profile) and the phase-frequency plot
+    ``<fil>.png`` (dedispersed, time-scrunched, frequency-scrunched to ``fscrunch_to`` channels, profile strip on top).
+
+    ``polyco``: a TEMPO polyco file made from the same .par -- the fold follows the predictor, as dspsr's does
+    (barycentric, binary and position terms); ``doppler``: a constant Doppler factor for the polynomial instead.  A file
+    with several products (nifs > 1) is folded in all of them in one pass: the archive holds them (header ``nprod``),
+    the total-intensity outputs use Stokes I, and a four-product file (``products``: ``coherency`` = the `-d4` products,
+    ``stokes`` = an IQUV file) also gives ``<fil>_fullPol.png`` -- pol 0, pol 1, Stokes I phase-frequency, and the
+    I / L / V profile with the position angle: the 2x2 plot of base2fil.sh:483-490 -- and I, L, V, PA columns in the text
+    profile (off-pulse baseline removed per product; see ``stokes`` on what a rescaled file keeps of the fractions)."""
+    fil = sigproc.read_fil(filterbankfile)
+    par = read_par(parfile)
+    hdr = fil.header
+    nprod = hdr.get("nifs", 1)
+    timing = "topocentric polynomial F0, F1 about PEPOCH (no barycentric, binary or position terms)"
+    prof_all = None
+    if nprod > 1 or polyco is not None or doppler != 0.0:
+        segs = read_polyco(polyco) if polyco is not None else None
+        prof_all, hits, nbin = fold_all(fil, par, polyco=segs, doppler=doppler, nbin=nbin, subint_s=subint_s, apply_delays=False,
+                                        device=device, lib=lib)
+        if segs:
+            timing = "TEMPO polyco predictor, %d blocks, site %s (%s)" % (len(segs), segs[0]["site"], os.path.basename(polyco))
+        elif doppler != 0.0:
+            timing = "polynomial F0, F1 about PEPOCH, elapsed time stretched by the Doppler factor %.12g" % doppler
+        prof = stokes(prof_all, products)[:, 0] if nprod == 4 else prof_all[:, 0]
+    else:
+        prof, hits, nbin = fold(fil, par, nbin=nbin, subint_s=subint_s, apply_delays=False, device=device, lib=lib)
+    base = out_base or filterbankfile
+    meta = {"source": par["PSR"], "f0": par["F0"], "f1": par["F1"], "dm": par["DM"],
+            "pepoch": par["PEPOCH"] if par["PEPOCH"] is not None else hdr["tstart"], "dedispersed": False,
+            "nsub": int(prof.shape[0]), "nchan": int(prof.shape[1]), "nbin": int(nbin), "subint_s": subint_s,
+            "tstart": hdr["tstart"], "tsamp": hdr["tsamp"], "fch1": hdr["fch1"], "foff": hdr["foff"],
+            "timing": timing}
+    if nprod > 1:
+        meta["nprod"] = int(nprod)
+        meta["products"] = products
+        write_archive(base + ".ar", prof_all, hits, meta)
+    else:
+        write_archive(base + ".ar", prof, hits, meta)
+    mean_f, profile = _scrunched(prof, hits, hdr, par["F0"], par["DM"], fscrunch_to)
+    nf = mean_f.shape[0]
+    pol = None
+    if nprod == 4:
+        iquv = stokes(prof_all, products)
+        flat = [_scrunched(iquv[:, k], hits, hdr, par["F0"], par["DM"], fscrunch_to) for k in range(4)]
+        pol = linear_pa(np.stack([f[1] for f in flat]))
+        if products == "coherency":
+            pol01 = [_scrunched(prof_all[:, k], hits, hdr, par["F0"], par["DM"], fscrunch_to)[0] for k in (0, 1)]
+        else:                                                                   # circular feeds: I = PP + QQ, V = PP - QQ
+            pol01 = [0.5 * (flat[0][0] + flat[3][0]), 0.5 * (flat[0][0] - flat[3][0])]
     with open(base + ".profile.txt", "w") as f:
-        f.write("# bin  mean_sample   (dedispersed DM=%g, tscrunched, fscrunched; %s)\n" % (par["DM"], par["PSR"]))
-        for i, v in enumerate(profile):
-            f.write("%d %.9g\n" % (i, v))
+        if pol is None:
+            f.write("# bin  mean_sample   (dedispersed DM=%g, tscrunched, fscrunched; %s)\n" % (par["DM"], par["PSR"]))
+            for i, v in enumerate(profile):
+                f.write("%d %.9g\n" % (i, v))
+        else:
+            f.write("# bin  mean_sample  I  L  V  PA_deg   (dedispersed DM=%g, tscrunched, fscrunched, baselines removed; %s)\n"
+                    % (par["DM"], par["PSR"]))
+            for i, v in enumerate(profile):
+                f.write("%d %.9g %.9g %.9g %.9g %.6f\n" % (i, v, pol[0][i], pol[1][i], pol[2][i], np.degrees(pol[3][i])))
     strip = np.tile((profile - profile.min()) / max(1e-30, profile.max() - profile.min()), (max(8, nf // 8), 1))
     wf = mean_f - mean_f.mean(axis=1, keepdims=True)
     wf = (wf - wf.min()) / max(1e-30, wf.max() - wf.min())
     write_png(base + ".png", np.concatenate([strip, wf], axis=0))
+    if pol is not None:
+        height = max(nf, 32)
+        rep = -(-height // nf)
+        panels = [np.repeat(_unit(m), rep, axis=0)[:height] for m in (pol01[0], pol01[1], flat[0][0])]
+        panels.append(_trace_panel(*pol, height))
+        gap_v, gap_h = np.zeros((height, 4)), np.zeros((4, 2 * nbin + 4))
+        write_png(base + "_fullPol.png", np.concatenate([np.concatenate([panels[0], gap_v, panels[1]], axis=1), gap_h,
+                                                         np.concatenate([panels[2], gap_v, panels[3]], axis=1)], axis=0))
     return base + ".ar", profile
 
 
 def main(argv=None):
-    """``python -m frb_baseband_amd.post fold <fil> <par> [...]`` / ``... prepdata <fil> --dm <dm> [...]``: the two stages
+    """``python -m frb_baseband_amd.post fold <fil> <par> [--polyco FILE] [--doppler X] [--products coherency|stokes] [...]`` / ``... prepdata <fil> --dm <dm> [...]``: the two stages
     as commands, for the places where base2fil.sh / process_vdif.py launch dspsr and prepdata"""
     import argparse
     ap = argparse.ArgumentParser(prog="frb_baseband_amd.post")
@@ -300,6 +525,9 @@ def main(argv=None):
     f.add_argument("--nbin", type=int, default=0, help="phase bins (0: largest power of two <= period / tsamp, at most 1024)")
     f.add_argument("-L", "--subint", type=float, default=10.0, help="sub-integration length, s (dspsr -L 10)")
     f.add_argument("--fscrunch", type=int, default=128, help='channels of the plot (psrplot -j "fscrunch 128")')
+    f.add_argument("--polyco", default=None, help="TEMPO polyco file of the same .par (tempo2 -polyco ... -tempo1): fold with the predictor")
+    f.add_argument("--doppler", type=float, default=0.0, help="constant Doppler factor (observed / intrinsic spin frequency - 1) for the F0 / F1 polynomial")
+    f.add_argument("--products", choices=("coherency", "stokes"), default="coherency", help="what a four-product file holds: the -d4 products, or I, Q, U, V")
     f.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     d = sub.add_parser("prepdata", help="incoherent dedispersion (process_vdif.py:202-229)")
     d.add_argument("fil")
@@ -311,7 +539,8 @@ def main(argv=None):
     d.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     a = ap.parse_args(argv)
     if a.cmd == "fold":
-        ar, profile = fold_fil(a.fil, a.par, nbin=a.nbin, subint_s=a.subint, fscrunch_to=a.fscrunch, device=a.device)
+        ar, profile = fold_fil(a.fil, a.par, nbin=a.nbin, subint_s=a.subint, fscrunch_to=a.fscrunch, device=a.device,
+                               polyco=a.polyco, doppler=a.doppler, products=a.products)
         print("wrote {0}, {1}.profile.txt, {1}.png; peak bin {2} of {3}".format(ar, a.fil, int(np.argmax(profile)), profile.size))
     else:
         for path in prepdata_gpu(a.fil, a.dm, zerodm=a.nozerodm, clip=a.clip, dm2=a.dm2, dmstep=a.dmstep, device=a.device):

@@ -283,6 +283,60 @@ int frbch_fold_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nr
                       double pepoch_mjd, double dm, uint32_t apply_delays, uint32_t nbin, double subint_s, int device,
                       double* d_profile, uint32_t* d_hits, uint32_t nsub, char* err, size_t err_cap);
 
+/* ---- fold of every product, with a phase predictor ------------------------------------------------
+ * dspsr folds with a predictor that tempo / tempo2 make from the .par file (base2fil.sh:474: `-E <par>`), which carries
+ * the barycentric, binary and position terms, and for `--pol 4` scans the reference plots pol 0, pol 1, Stokes I and a
+ * Stokes profile from the folded archive (base2fil.sh:481-491).  frbch_foldp_* fold ALL nifs (1..4) products of the rows
+ * in one pass (`fil->product` is ignored) with either phase model:
+ *   nseg = 0: the polynomial of frbch_fold_*, tau = (tstart - PEPOCH) 86400 + t tsamp [- delay_c], and when doppler != 0
+ *             tau := tau + tau * doppler  (doppler = observed / intrinsic spin frequency - 1, a constant for the scan);
+ *   nseg > 0: TEMPO polyco blocks (topocentric already: doppler must be 0).  Row t, channel c, block s:
+ *               sec   = t * tsamp [- delay_c]
+ *               dt    = (tstart_mjd - tmid_s) * 1440.0 + sec / 60.0                        (minutes)
+ *               turns = (rphase_frac + (dt * 60.0) * f0_hz) + horner(coeff, dt)
+ *             -- TEMPO's PHASE = RPHASE + DT 60 F0 + C1 + DT C2 + DT^2 C3 + ... -- Horner from the highest coefficient
+ *             down: h = coeff[n-1]; h = h * dt + coeff[i] for i = n-2 .. 0.
+ *   bin = min((int)((turns - floor(turns)) * nbin), nbin - 1).
+ * Every operation is an IEEE double operation rounded on its own (no fused multiply-add).
+ * The block of a row: block s >= 1 starts at the first row at or after the midpoint of tmid_{s-1} and tmid_s,
+ *   x = ((0.5 * (tmid_{s-1} + tmid_s) - tstart_mjd) * 86400.0) / tsamp_s;   first_row_s = x <= 0 ? 0 : min(ceil(x), nrows)
+ * computed by the host; row t uses the last block whose first_row <= t (channel delays do not move a row to another block).
+ * FRBCH_E_ARG: blocks not in ascending tmid, ncoeff outside 1..15, a span <= 0, doppler != 0 with nseg > 0, or the first
+ * or the last row (t tsamp, no delay) outside every block's span, |dt| <= span_min / 2 (where dspsr refuses as well).
+ *
+ * Coherency products to Stokes parameters of a folded `-d4` file (post.stokes), circular basis as pol_mode 5 above
+ * (products in file order PP, QQ, Re(PQ*), Im(PQ*)):   I = PP + QQ,  Q = 2 Re(PQ*),  U = 2 Im(PQ*),  V = PP - QQ;
+ * linear polarisation L = sqrt(Q^2 + U^2), position angle PA = atan2(U, Q) / 2. */
+typedef struct frbch_polyco_seg {      /* one TEMPO polyco block                                                         */
+  double tmid_mjd;                     /* TMID                                                                           */
+  double rphase_frac;                  /* RPHASE reduced to [0, 1) by the parser (from the text: 1e10 turns lose no fraction) */
+  double f0_hz;                        /* reference rotation frequency of the block                                      */
+  double span_min;                     /* validity: |T - TMID| <= span / 2, minutes                                      */
+  uint32_t ncoeff, reserved;           /* 1..15                                                                          */
+  double coeff[15];
+} frbch_polyco_seg;
+
+typedef struct frbch_fold_model {
+  uint32_t size, nseg;                 /* = sizeof(frbch_fold_model); nseg = 0: the F0 / F1 / PEPOCH polynomial           */
+  const frbch_polyco_seg* seg;         /* [nseg], ascending tmid                                                         */
+  double f0_hz, f1, pepoch_mjd;        /* used when nseg = 0                                                             */
+  double doppler;                      /* nseg = 0 only                                                                  */
+  double dm;                           /* as frbch_fold_*                                                                */
+  uint32_t apply_delays, nbin;
+  double subint_s;
+} frbch_fold_model;
+
+/* profile[sub][product][bin][chan] = sums (double; exact for integer rows), hits[sub][bin][chan] = rows, shared by the
+ * products; nsub as frbch_fold_nsub gives it.  *kernel_used (may be NULL): 0 = the generic kernel, 1 = the LDS kernel
+ * (8- / 16-bit rows, no per-channel delays, nbin small enough for a tile of >= 16 channels in the LDS).  Both give the
+ * same bits on integer rows.  With nseg = 0 and doppler = 0, product p equals frbch_fold_* with product = p exactly on
+ * integer rows. */
+int frbch_foldp_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_fold_model* model, int device,
+                     double* profile, uint32_t* hits, uint32_t nsub, uint32_t* kernel_used, char* err, size_t err_cap);
+int frbch_foldp_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_fold_model* model,
+                       int device, double* d_profile, uint32_t* d_hits, uint32_t nsub, uint32_t* kernel_used, char* err,
+                       size_t err_cap);
+
 /* ---- in front of the filterbank: the corner turn -------------------------------
  * jive5ab's spif2file splits the recorder's stream -- every W-bit word holds one time sample of ALL channels -- into one
  * 2-channel stream per IF, driven by the recipe strings of spif2file.sh:31-113, e.g. the 16-channel 2-bit mode
