@@ -112,6 +112,7 @@ SYMBOLS = {
     "frbch_get_rescale": (C.c_int, [_P, _P, _P]),
     "frbch_set_rescale": (C.c_int, [_P, _P, _P]),
     "frbch_dedisperse_nout": (C.c_long, [C.POINTER(FrbchFilDesc), C.c_uint64, _P, C.c_uint32]),
+    "frbch_dedisperse_kernel": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, _P, C.c_uint32]),
     "frbch_dedisperse_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_double,
                                         C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
     "frbch_dedisperse_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_double,

@@ -49,6 +49,38 @@ std::vector<int32_t> post_delays(const frbch_fil_desc* f, const double* dms, uin
 
 constexpr uint64_t kPostChunkRows = 4096;
 
+// Which dedispersion kernel a call takes -- the one decision behind frbch_dedisperse_device's launch and
+// frbch_dedisperse_kernel's answer.  true = the LDS-tiled kernel (kernels_post_fast.inc): whole 64-byte channel tiles,
+// 16-byte pieces of every row (only the ADDRESS of d_rows is examined), and every (DM group, channel tile) fits its rows into
+// the LDS; *range then holds [DM group][channel tile] (smallest delay, rows spanned beyond the time tile).  The emulator
+// build has no such kernel: false.
+bool post_dedisp_tiled(const frbch_fil_desc* fil, const void* d_rows, const std::vector<int32_t>& delays, uint32_t ndm,
+                       std::vector<int32_t>* range) {
+#ifndef FRBCH_NO_FAST
+  const int bpv = fil->nbits / 8, ct = 64 / bpv;
+  if (fil->nchan % ct != 0 || ((uintptr_t)d_rows % 16) != 0 || ((size_t)fil->nchan * bpv) % 16 != 0) return false;
+  const int nct = (int)fil->nchan / ct, ngrp = (int)((ndm + fast::kDedND - 1) / fast::kDedND);
+  range->assign((size_t)ngrp * nct * 2, 0);
+  for (int g = 0; g < ngrp; ++g)
+    for (int k = 0; k < nct; ++k) {
+      int32_t lo = INT32_MAX, hi = 0;
+      for (uint32_t d = (uint32_t)g * fast::kDedND; d < std::min<uint32_t>(ndm, (uint32_t)(g + 1) * fast::kDedND); ++d)
+        for (int c = k * ct; c < (k + 1) * ct; ++c) {
+          const int32_t v = delays[(size_t)d * fil->nchan + c];
+          lo = std::min(lo, v);
+          hi = std::max(hi, v);
+        }
+      (*range)[((size_t)g * nct + k) * 2] = lo;
+      (*range)[((size_t)g * nct + k) * 2 + 1] = hi - lo;
+      if (fast::kDedTT + (hi - lo) > fast::kDedRowsCap) return false;
+    }
+  return true;
+#else
+  (void)fil; (void)d_rows; (void)delays; (void)ndm; (void)range;
+  return false;
+#endif
+}
+
 }  // namespace
 
 extern "C" long frbch_dedisperse_nout(const frbch_fil_desc* fil, uint64_t nrows, const double* dms, uint32_t ndm) {
@@ -59,6 +91,15 @@ extern "C" long frbch_dedisperse_nout(const frbch_fil_desc* fil, uint64_t nrows,
   int64_t maxd = 0;
   (void)post_delays(fil, dms, ndm, &maxd);
   return (int64_t)nrows > maxd ? (long)((int64_t)nrows - maxd) : 0;
+}
+
+extern "C" int frbch_dedisperse_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const double* dms,
+                                       uint32_t ndm) {
+  if (!d_rows || frbch_dedisperse_nout(fil, nrows, dms, ndm) <= 0) return FRBCH_E_ARG;   // what frbch_dedisperse_device refuses
+  int64_t maxd = 0;
+  const std::vector<int32_t> delays = post_delays(fil, dms, ndm, &maxd);
+  std::vector<int32_t> range;
+  return post_dedisp_tiled(fil, d_rows, delays, ndm, &range) ? 1 : 0;
 }
 
 extern "C" int frbch_dedisperse_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const double* dms,
@@ -154,45 +195,25 @@ extern "C" int frbch_dedisperse_device(const frbch_fil_desc* fil, const void* d_
       nflag = 0;
     }
   }
-  bool tiled = false;
+  std::vector<int32_t> range;
+  const bool tiled = post_dedisp_tiled(fil, d_rows, delays, ndm, &range);
 #ifndef FRBCH_NO_FAST
-  {   // the LDS-tiled kernel whenever every (DM group, channel tile) fits its rows into the LDS (kernels_post_fast.inc)
-    const int bpv = fil->nbits / 8, ct = 64 / bpv;
-    if (fil->nchan % ct == 0 && ((uintptr_t)d_rows % 16) == 0 && ((size_t)fil->nchan * bpv) % 16 == 0) {
-      const int nct = (int)fil->nchan / ct, ngrp = (int)((ndm + fast::kDedND - 1) / fast::kDedND);
-      std::vector<int32_t> range((size_t)ngrp * nct * 2);
-      bool fits = true;
-      for (int g = 0; g < ngrp && fits; ++g)
-        for (int k = 0; k < nct; ++k) {
-          int32_t lo = INT32_MAX, hi = 0;
-          for (uint32_t d = (uint32_t)g * fast::kDedND; d < std::min<uint32_t>(ndm, (uint32_t)(g + 1) * fast::kDedND); ++d)
-            for (int c = k * ct; c < (k + 1) * ct; ++c) {
-              const int32_t v = delays[(size_t)d * fil->nchan + c];
-              lo = std::min(lo, v);
-              hi = std::max(hi, v);
-            }
-          range[((size_t)g * nct + k) * 2] = lo;
-          range[((size_t)g * nct + k) * 2 + 1] = hi - lo;
-          if (fast::kDedTT + (hi - lo) > fast::kDedRowsCap) { fits = false; break; }
-        }
-      if (fits) {
-        POST_DEV(dev_malloc((void**)&d_range, range.size() * sizeof(int32_t)), "hipMalloc");
-        POST_DEV(dev_h2d(d_range, range.data(), range.size() * sizeof(int32_t), s), "upload tile ranges");
-        POST_DEV(dev_sync(s), "sync");                       // (`range` goes out of scope)
-        p.tile_range = d_range;
-        const size_t lds = (size_t)fast::kDedRowsCap * fast::kDedRowB + 16 + (size_t)fast::kDedRowsCap * 9;
-        const dim3 grid((unsigned)((nout + fast::kDedTT - 1) / fast::kDedTT), (unsigned)ngrp);
-        const bool fl = p.flagged != nullptr, zd = p.zerodm != 0;
+  if (tiled) {
+    const int bpv = fil->nbits / 8, ngrp = (int)((ndm + fast::kDedND - 1) / fast::kDedND);
+    POST_DEV(dev_malloc((void**)&d_range, range.size() * sizeof(int32_t)), "hipMalloc");
+    POST_DEV(dev_h2d(d_range, range.data(), range.size() * sizeof(int32_t), s), "upload tile ranges");
+    POST_DEV(dev_sync(s), "sync");
+    p.tile_range = d_range;
+    const size_t lds = (size_t)fast::kDedRowsCap * fast::kDedRowB + 16 + (size_t)fast::kDedRowsCap * 9;
+    const dim3 grid((unsigned)((nout + fast::kDedTT - 1) / fast::kDedTT), (unsigned)ngrp);
+    const bool fl = p.flagged != nullptr, zd = p.zerodm != 0;
 #define POST_TILED(B) do { \
-          if (fl && zd) { POST_DEV(dev_allow_lds(fast::frbch_post_dedisp_tiled<B, true, true>, lds), "LDS size"); hipLaunchKernelGGL((fast::frbch_post_dedisp_tiled<B, true, true>), grid, dim3(256), lds, s, p); } \
-          else if (fl) { POST_DEV(dev_allow_lds(fast::frbch_post_dedisp_tiled<B, true, false>, lds), "LDS size"); hipLaunchKernelGGL((fast::frbch_post_dedisp_tiled<B, true, false>), grid, dim3(256), lds, s, p); } \
-          else if (zd) { POST_DEV(dev_allow_lds(fast::frbch_post_dedisp_tiled<B, false, true>, lds), "LDS size"); hipLaunchKernelGGL((fast::frbch_post_dedisp_tiled<B, false, true>), grid, dim3(256), lds, s, p); } \
-          else { POST_DEV(dev_allow_lds(fast::frbch_post_dedisp_tiled<B, false, false>, lds), "LDS size"); hipLaunchKernelGGL((fast::frbch_post_dedisp_tiled<B, false, false>), grid, dim3(256), lds, s, p); } } while (0)
-        if (bpv == 1) POST_TILED(1); else if (bpv == 2) POST_TILED(2); else POST_TILED(4);
+      if (fl && zd) { POST_DEV(dev_allow_lds(fast::frbch_post_dedisp_tiled<B, true, true>, lds), "LDS size"); hipLaunchKernelGGL((fast::frbch_post_dedisp_tiled<B, true, true>), grid, dim3(256), lds, s, p); } \
+      else if (fl) { POST_DEV(dev_allow_lds(fast::frbch_post_dedisp_tiled<B, true, false>, lds), "LDS size"); hipLaunchKernelGGL((fast::frbch_post_dedisp_tiled<B, true, false>), grid, dim3(256), lds, s, p); } \
+      else if (zd) { POST_DEV(dev_allow_lds(fast::frbch_post_dedisp_tiled<B, false, true>, lds), "LDS size"); hipLaunchKernelGGL((fast::frbch_post_dedisp_tiled<B, false, true>), grid, dim3(256), lds, s, p); } \
+      else { POST_DEV(dev_allow_lds(fast::frbch_post_dedisp_tiled<B, false, false>, lds), "LDS size"); hipLaunchKernelGGL((fast::frbch_post_dedisp_tiled<B, false, false>), grid, dim3(256), lds, s, p); } } while (0)
+    if (bpv == 1) POST_TILED(1); else if (bpv == 2) POST_TILED(2); else POST_TILED(4);
 #undef POST_TILED
-        tiled = true;
-      }
-    }
   }
 #endif
   if (!tiled) DEV_LAUNCH(frbch_post_dedisp, (nout + 255) / 256, ndm, 256, 0, s, p);

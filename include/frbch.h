@@ -260,6 +260,9 @@ typedef struct frbch_fil_desc {
 /* Output samples per DM: nrows minus the largest delay of any requested DM (delay of channel c = DM / 2.41e-4 *
  * (f_c^-2 - f_top^-2) s, rounded to samples as int(x + 0.5)).  < 0: bad arguments. */
 long frbch_dedisperse_nout(const frbch_fil_desc* fil, uint64_t nrows, const double* dms, uint32_t ndm);
+/* Which kernel frbch_dedisperse_device takes for these arguments (host only, nothing runs): 1 = the LDS-tiled kernel,
+ * 0 = the generic one, < 0 = bad arguments; only the ADDRESS of d_rows is examined. */
+int frbch_dedisperse_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const double* dms, uint32_t ndm);
 /* out[dm][t] = sum_c x[t + delay_c(dm)][c]  (float32), after the optional time-domain clip (`-clip <sigma>`: a time
  * sample whose zero-DM sum lies more than clip_sigma sigma off the mean -- two rounds -- is replaced by the channel means
  * of the unclipped samples) and the optional zero-DM filter (`-zerodm`: the mean over channels of every time sample is

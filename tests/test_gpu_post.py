@@ -166,6 +166,10 @@ def test_dm_range_on_the_tiled_kernel_matches_oracle(hip_lib, nbits, zerodm, cli
     data = x.astype(np.uint8) if nbits == 8 else ((x * 55).astype(np.uint16) if nbits == 16 else (x * 0.37 - 3.0).astype(np.float32))
     dms = post.dm_list(20.0, 83.0, 1.0)
     assert len(dms) == 64
+    import ctypes as C
+    desc, dm_arr = post.fil_desc(dict(HDR1K, nbits=nbits)), np.asarray(dms, dtype=np.float64)
+    # the host entry point uploads to memory of its own (hipMalloc: 256-byte aligned at least); only the address is examined
+    assert hip_lib.frbch_dedisperse_kernel(C.byref(desc), C.c_void_p(4096), data.shape[0], dm_arr.ctypes.data, 64) == 1
     got, nclip = post.dedisperse(as_fil(data, HDR1K, nbits), dms, zerodm=zerodm, clip=clip, lib=hip_lib)
     want, nclip2 = po.dedisperse(data, fch1=HDR1K["fch1"], foff=HDR1K["foff"], tsamp=HDR1K["tsamp"], dms=dms, zerodm=zerodm,
                                  clip=clip, integer=nbits != 32)
