@@ -135,6 +135,7 @@ SYMBOLS = {
     "frbch_set_profiling": (C.c_int, [_P, C.c_int]),
     "frbch_timing_reset": (C.c_int, [_P]),
     "frbch_get_timing": (C.c_int, [_P, C.POINTER(FrbchTiming)]),
+    "frbch_get_launch_record": (C.c_long, [_P, C.c_char_p, C.c_size_t]),
     "frbch_version": (C.c_char_p, []),
 }
 

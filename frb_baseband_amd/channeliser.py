@@ -184,3 +184,13 @@ class Channeliser:
         return {t.k[i].name.decode(): {"launches": t.k[i].launches, "total_ms": t.k[i].total_ms,
                                        "algorithmic_bytes": t.k[i].algorithmic_bytes}
                 for i in range(t.nkernels)}
+
+    def get_launch_record(self) -> dict:
+        """kernels launched while profiling was on, by the full name of the instantiation: launches, largest grid"""
+        buf = C.create_string_buffer(1 << 16)
+        self._check(self.lib.frbch_get_launch_record(self._h, buf, len(buf)))
+        rec = {}
+        for line in buf.value.decode().splitlines():
+            name, n, gx, gy = line.split("\t")
+            rec[name] = {"launches": int(n), "grid_x": int(gx), "grid_y": int(gy)}
+        return rec

@@ -375,7 +375,26 @@ extern "C" int frbch_timing_reset(frbch_handle* h) {
   (void)dev_sync(h->stream);
   drain_events(h);
   for (int i = 0; i < KID_COUNT; ++i) h->acc_ms[i] = h->acc_bytes[i] = 0.0, h->acc_launches[i] = 0;
+  h->launch_rec.clear();
   return FRBCH_OK;
+}
+// one line per kernel launched while profiling was on: name <tab> launches <tab> largest grid.x <tab> largest grid.y
+extern "C" long frbch_get_launch_record(frbch_handle* h, char* buf, size_t cap) {
+  if (!h || (!buf && cap)) return FRBCH_E_ARG;
+  std::map<std::string, frbch_handle::LaunchRec> by_name;   // (a generic kernel launched from two places has two keys)
+  for (const auto& kv : h->launch_rec) {
+    frbch_handle::LaunchRec& r = by_name[kv.second.name];
+    r.launches += kv.second.launches;
+    r.grid_x = std::max(r.grid_x, kv.second.grid_x);
+    r.grid_y = std::max(r.grid_y, kv.second.grid_y);
+  }
+  std::string text;
+  for (const auto& kv : by_name)
+    text += kv.first + "\t" + std::to_string(kv.second.launches) + "\t" + std::to_string(kv.second.grid_x) + "\t" +
+            std::to_string(kv.second.grid_y) + "\n";
+  if (text.size() + 1 > cap) return fail(h, FRBCH_E_CAPACITY, "launch record: " + std::to_string(text.size() + 1) + " bytes needed");
+  memcpy(buf, text.c_str(), text.size() + 1);
+  return (long)text.size();
 }
 extern "C" int frbch_get_timing(frbch_handle* h, frbch_timing* t) {
   if (!h || !t) return FRBCH_E_ARG;

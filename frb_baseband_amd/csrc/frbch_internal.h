@@ -33,6 +33,7 @@
 #include <sstream>
 #include <string>
 #include <condition_variable>
+#include <map>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -159,6 +160,17 @@ struct frbch_handle {
   double acc_ms[KID_COUNT] = {0};
   double acc_bytes[KID_COUNT] = {0};
   uint64_t acc_launches[KID_COUNT] = {0};
+  // launch record (while profiling): every kernel launch of the channeliser path under the full name of its instantiation, spelled
+  // as the demangled symbol; frbch_get_launch_record reports it, frbch_timing_reset and apply_plan clear it.  Keyed by the kernel's
+  // address (a generic kernel: that of its name's literal, one per launch site: frbch_get_launch_record merges keys of one name),
+  // so that a launch costs a look-up: the name is built once per kernel.  Like `events`, written by the thread that launches for
+  // the handle: a handle is driven by one thread at a time (the whole-file paths launch from their one compute thread)
+  struct LaunchRec {
+    std::string name;
+    uint64_t launches = 0;
+    uint32_t grid_x = 0, grid_y = 0;   // the largest grid the kernel was launched with
+  };
+  std::map<const void*, LaunchRec> launch_rec;
 };
 
 namespace frbchi {
@@ -221,6 +233,25 @@ struct ProfScope {
     }
   }
 };
+
+// the launch record's writer: callers test h->profiling first (the gate of ProfScope); name() is called the first time `key` is seen
+template <class NameFn>
+inline void note_launch(frbch_handle* h, const void* key, NameFn&& name, uint64_t gx, uint64_t gy) {
+  frbch_handle::LaunchRec& r = h->launch_rec[key];
+  if (r.name.empty()) r.name = name();
+  r.launches += 1;
+  r.grid_x = std::max(r.grid_x, (uint32_t)gx);
+  r.grid_y = std::max(r.grid_y, (uint32_t)gy);
+}
+inline void note_launch(frbch_handle* h, const char* name, uint64_t gx, uint64_t gy) {
+  note_launch(h, (const void*)name, [name] { return std::string(name); }, gx, gy);
+}
+// DEV_LAUNCH of a generic kernel, recorded under its (extern "C") name
+#define REC_LAUNCH(h, kern, gx, gy, nthr, lds, stream, params)       \
+  do {                                                               \
+    if ((h)->profiling) note_launch((h), #kern, (gx), (gy));         \
+    DEV_LAUNCH(kern, gx, gy, nthr, lds, stream, params);             \
+  } while (0)
 
 inline void drain_events(frbch_handle* h) {
   for (auto& e : h->events) {

@@ -81,6 +81,8 @@ KParams base_params(const frbch_handle* h) {
 // plan and the per-launch inputs to the instantiation and calls its visitor once, f(kernel, KSel).  A launch passes a visitor that
 // launches, setup_fast one that raises the kernel's dynamic-LDS limit and names its timing slot, wave_stat_chunks one that reads
 // the threads per workgroup -- so an instantiation is added or removed in its selector and nowhere else.
+// The selector also spells the instantiation's full name for the launch record (KSel::full: the template arguments the timing-slot
+// name drops go in through KSel::with).
 // A selector returns false when the plan has no kernel of its family (the caller runs the generic one).
 // =============================================================================================
 struct KSel {
@@ -91,14 +93,32 @@ struct KSel {
   int targ[4];
   const char* tail;     // ... and what follows them inside the brackets (frbch_k2_priv<PM,stats>)
   int nseq;             // frbch_k2_wave: sequences (time samples; x those a wave holds) per workgroup
+  // the template arguments the timing-slot name leaves out, for the launch record: integers behind targ[], then bools
+  int nxarg = 0, xarg[2] = {0, 0};
+  int nbarg = 0;
+  bool barg[3] = {false, false, false};
   std::string name() const {
     std::string s = family;
     for (int i = 0; i < ntarg; ++i) s += (i ? "," : "<") + std::to_string(targ[i]);
     return ntarg ? s + tail + ">" : s;
   }
+  // the instantiation as the demangled symbol spells it: frbch_k2_wave<3, 8, 4, 2, true>
+  std::string full() const {
+    std::string s;
+    for (int i = 0; i < ntarg; ++i) s += ", " + std::to_string(targ[i]);
+    for (int i = 0; i < nxarg; ++i) s += ", " + std::to_string(xarg[i]);
+    for (int i = 0; i < nbarg; ++i) s += barg[i] ? ", true" : ", false";
+    return s.empty() ? std::string(family) : std::string(family) + "<" + s.substr(2) + ">";
+  }
+  KSel with(std::initializer_list<int> xs, std::initializer_list<bool> bs = {}) const {
+    KSel a = *this;
+    for (int x : xs) a.xarg[a.nxarg++] = x;
+    for (bool b : bs) a.barg[a.nbarg++] = b;
+    return a;
+  }
 };
 inline KSel ksel(int nt, size_t lds, const char* family, std::initializer_list<int> targs = {}, const char* tail = "", int nseq = 0) {
-  KSel a{nt, lds, family, 0, {0, 0, 0, 0}, tail, nseq};
+  KSel a{nt, lds, family, 0, {0, 0, 0, 0}, tail, nseq, 0, {0, 0}, 0, {false, false, false}};
   for (int t : targs) a.targ[a.ntarg++] = t;
   return a;
 }
@@ -109,7 +129,8 @@ bool on_value(int v, F&& f) {
 }
 // the visitor of a launch
 template <class K>
-void launch_sel(K kern, dim3 grid, const KSel& a, dev_stream_t s, const KParams& p) {
+void launch_sel(frbch_handle* h, K kern, dim3 grid, const KSel& a, dev_stream_t s, const KParams& p) {
+  if (h->profiling) note_launch(h, reinterpret_cast<const void*>(kern), [&a] { return a.full(); }, grid.x, grid.y);
   hipLaunchKernelGGL(kern, grid, dim3(a.nt), a.lds, s, p);
 }
 // product mode as the kernels' template argument PM: 2 = PP+QQ, 4 = four products, 0 = one of the others.  frbch_k2_priv keeps
@@ -121,14 +142,16 @@ int pm_priv_of(int pol_mode) { return (pol_mode == 2 || pol_mode == 4 || pol_mod
 template <class F>
 bool select_k0_stage(uint32_t rb, bool wide, F&& f) {
   return on_value<1, 2, 4, 8, 16>((rb == 1 || rb == 2 || rb == 4 || rb == 8) ? (int)rb : 16, [&](auto RB) {
-    if (wide) f(fast::frbch_k0_stage<RB.value, true>, ksel(256, 0, "frbch_k0_stage"));
-    else f(fast::frbch_k0_stage<RB.value, false>, ksel(256, 0, "frbch_k0_stage"));
+    // (RB = 16: pieces aligned to 16 bytes are what WIDE asks for -- launch_k0_stage never comes here with wide = false)
+    if (wide) f(fast::frbch_k0_stage<RB.value, true>, ksel(256, 0, "frbch_k0_stage").with({RB.value}, {true}));
+    else if constexpr (RB.value < 16) f(fast::frbch_k0_stage<RB.value, false>, ksel(256, 0, "frbch_k0_stage").with({RB.value}, {false}));
   });
 }
-// ---- K1, barrier form
+// ---- K1, barrier form: the coherent chain.  (Not R = 4096: make_plan gives every plan whose barrier K1 fits the LDS at that length
+// the wave K1, which needs less of it)
 template <class F>
 bool select_k1_fast(const Plan& pl, F&& f) {
-  return on_value<1, 2, 3, 4, 5>(pl.fast_k1_log2m, [&](auto L) {
+  return on_value<1, 2, 3, 5>(pl.fast_k1_log2m, [&](auto L) {
     f(fast::frbch_k1_fast<L.value>, ksel(1024, pl.k1_fast_lds, "frbch_k1_fast", {L.value}));
   });
 }
@@ -140,9 +163,9 @@ size_t k1_wave_lds(const Plan& pl, bool msk) {
 template <int L, int WPS, bool COH, class F>
 void pick_k1_wave(const Plan& pl, bool stg, bool msk, F& f) {
   const KSel a = ksel(512, k1_wave_lds(pl, stg && msk), "frbch_k1_wave", {L, 8, WPS});
-  if (stg && msk) f(fast::frbch_k1_wave<L, 8, WPS, true, COH, true>, a);
-  else if (stg) f(fast::frbch_k1_wave<L, 8, WPS, true, COH>, a);
-  else f(fast::frbch_k1_wave<L, 8, WPS, false, COH>, a);
+  if (stg && msk) f(fast::frbch_k1_wave<L, 8, WPS, true, COH, true>, a.with({}, {true, COH, true}));
+  else if (stg) f(fast::frbch_k1_wave<L, 8, WPS, true, COH, false>, a.with({}, {true, COH, false}));
+  else f(fast::frbch_k1_wave<L, 8, WPS, false, COH, false>, a.with({}, {false, COH, false}));
 }
 template <class F>
 bool select_k1_wave(const Plan& pl, bool stg, bool msk, F&& f) {
@@ -183,16 +206,16 @@ bool select_k2_priv(const Plan& pl, int pol_mode, int out_mode, F&& f) {
   if (!pl.fast_k2_priv) return false;
   return on_value<0, 2, 4, 5>(pm_priv_of(pol_mode), [&](auto PM) {
     const KSel a = ksel(256, pl.k2_priv_lds, "frbch_k2_priv", {PM.value}, out_mode == FRBCH_OUT_STATS ? ",stats" : "");
-    if (out_mode == FRBCH_OUT_CODES) f(fast::frbch_k2_priv<PM.value, fast::K2P_CODES>, a);
-    else if (out_mode == FRBCH_OUT_STATS) f(fast::frbch_k2_priv<PM.value, fast::K2P_STATS>, a);
-    else f(fast::frbch_k2_priv<PM.value, fast::K2P_POWER>, a);
+    if (out_mode == FRBCH_OUT_CODES) f(fast::frbch_k2_priv<PM.value, fast::K2P_CODES>, a.with({fast::K2P_CODES}));
+    else if (out_mode == FRBCH_OUT_STATS) f(fast::frbch_k2_priv<PM.value, fast::K2P_STATS>, a.with({fast::K2P_STATS}));
+    else f(fast::frbch_k2_priv<PM.value, fast::K2P_POWER>, a.with({fast::K2P_POWER}));
   });
 }
 // ---- K2, wave form: frbch_k2_wave<LOG2M, NW waves, PM, WPS waves per sequence, MSTAT>.  cols: the launch sums the rescale
 // statistics or digitises (per-thread column registers in the MSTAT instantiations, where there is one)
 template <int L, int NW, int PM, int WPS, bool MSTAT = false, class F>
 bool pick_k2_wave(const Plan& pl, F& f) {
-  f(fast::frbch_k2_wave<L, NW, PM, WPS, MSTAT>, ksel(64 * NW, pl.k2_fast_lds, "frbch_k2_wave", {L, NW, PM, WPS}, "", NW / WPS));
+  f(fast::frbch_k2_wave<L, NW, PM, WPS, MSTAT>, ksel(64 * NW, pl.k2_fast_lds, "frbch_k2_wave", {L, NW, PM, WPS}, "", NW / WPS).with({}, {MSTAT}));
   return true;
 }
 template <int L, int NW, int WPS, class F>
@@ -239,7 +262,7 @@ bool select_k2_fast(const Plan& pl, F&& f) {
 template <class F>
 bool select_k2c_fast(const Plan& pl, F&& f) {
   return on_value<1, 2, 3, 4, 5>(pl.coh_fast_c, [&](auto L) {
-    f(fast::frbch_k2c_fast<L.value, 1024>, ksel(1024, pl.k2c_fast_lds, "frbch_k2c_fast"));
+    f(fast::frbch_k2c_fast<L.value, 1024>, ksel(1024, pl.k2c_fast_lds, "frbch_k2c_fast").with({L.value, 1024}));
   });
 }
 // the wave K3 (R = 4096) sums the statistics of its channel: one row of partial sums per persistent workgroup
@@ -255,7 +278,7 @@ bool select_k3_fast(const Plan& pl, F&& f) {
     return true;
   }
   return on_value<1, 2, 3, 5>(pl.coh_fast_r, [&](auto L) {
-    f(fast::frbch_k3_fast<L.value, 1024>, ksel(1024, pl.k3_fast_lds, "frbch_k3_fast"));
+    f(fast::frbch_k3_fast<L.value, 1024>, ksel(1024, pl.k3_fast_lds, "frbch_k3_fast").with({L.value, 1024}));
   });
 }
 // K4 of the coherent filterbank: the register-pass transpose (a single kernel) or the generic one
@@ -314,7 +337,8 @@ void set_fastdiv(KParams& p) {
   p.div_magic = (uint32_t)((((1ull << l) - d) << 32) / d + 1);
   p.div_shift = l ? l - 1 : 0;
 }
-bool launch_k1_wave(const Plan& pl, KParams& p, uint32_t nb, dev_stream_t s, int ncu) {
+bool launch_k1_wave(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s, int ncu) {
+  const Plan& pl = h->pl;
   // persistent over blocks: the resident workgroups each keep their branch group and loop over the batch
   p.nblk = nb;
   const int kg = pl.fast_k1_g;            // branches per workgroup (<= pl.g, the layout group)
@@ -338,9 +362,10 @@ bool launch_k1_wave(const Plan& pl, KParams& p, uint32_t nb, dev_stream_t s, int
     const uint32_t want = resident / g;
     if (want <= nb) ny = want;
   }
-  return select_k1_wave(pl, p.stg != nullptr, p.fbad != nullptr, [&](auto kern, const KSel& a) { launch_sel(kern, dim3(ngrp, ny), a, s, p); });
+  return select_k1_wave(pl, p.stg != nullptr, p.fbad != nullptr, [&](auto kern, const KSel& a) { launch_sel(h, kern, dim3(ngrp, ny), a, s, p); });
 }
-bool launch_k2_wave(const Plan& pl, KParams& p, uint32_t nb, dev_stream_t s, uint32_t h_flags) {
+bool launch_k2_wave(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s, uint32_t h_flags) {
+  const Plan& pl = h->pl;
   const int tps = 16 << pl.fast_k2_log2m;
   const int spw = tps < 64 ? 64 / tps : 1;
   // persistent: one wave of workgroups loops over the (tiles per block) x nb tiles of the launch
@@ -351,17 +376,18 @@ bool launch_k2_wave(const Plan& pl, KParams& p, uint32_t nb, dev_stream_t s, uin
   const bool cols = p.stat_partial || p.out_mode != FRBCH_OUT_FLOAT_POWER;
   return select_k2_wave(pl, p.pol_mode, cols, [&](auto kern, const KSel& a) {
     const uint64_t tiles_per_block = pl.r / (a.nseq * spw);
-    launch_sel(kern, dim3((unsigned)std::min<uint64_t>(tiles_per_block * nb, npers)), a, s, p);
+    launch_sel(h, kern, dim3((unsigned)std::min<uint64_t>(tiles_per_block * nb, npers)), a, s, p);
   });
 }
 bool launch_kc_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
   const Plan& pl = h->pl;
   if (kc_lane_planned(pl)) {
     p.nblk = nb;
+    if (h->profiling) note_launch(h, "frbch_kc_lane", (nb + 63) / 64, 1);
     hipLaunchKernelGGL(fast::frbch_kc_lane, dim3((nb + 63) / 64), dim3(64), 0, s, p);
     return true;
   }
-  return select_kc_fast(pl, [&](auto kern, const KSel& a) { launch_sel(kern, dim3(1, nb), a, s, p); });
+  return select_kc_fast(pl, [&](auto kern, const KSel& a) { launch_sel(h, kern, dim3(1, nb), a, s, p); });
 }
 // corner-turn of the batch's payload for the wave K1 (own timing slot); same preconditions as launch_k1_fast
 void launch_k0_stage(frbch_handle* h, const KParams& p, uint32_t nb, dev_stream_t s) {
@@ -384,7 +410,7 @@ void launch_k0_stage(frbch_handle* h, const KParams& p, uint32_t nb, dev_stream_
   ProfScope ps(h, s, KID_K0, (double)nb * (double)pl.block_payload_bytes * (1.0 + (double)p.frame_bytes / p.payload_bytes));
   const dim3 grid((pl.r / 64) * (pl.c / 256), nb);
   const bool wide = !(rel0 % 16 || p.payload_bytes % 16 || p.header_bytes % 16 || p.frame_bytes % 16);
-  select_k0_stage(rb, wide, [&](auto kern, const KSel& a) { launch_sel(kern, grid, a, s, q); });
+  select_k0_stage(rb, wide, [&](auto kern, const KSel& a) { launch_sel(h, kern, grid, a, s, q); });
   h->stg_ready = true;
 }
 bool launch_k1_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
@@ -411,7 +437,7 @@ bool launch_k1_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
       q.fbad_frame0 = p.fbad_frame0 + fr0;
     }
     q.tile_major = p.tile_major = pl.spill_tile_major;   // 2 (R = 2048, paired branches) or 8 (R = 8192) or 0 (K2 of this batch reads what this launch writes)
-    return launch_k1_wave(pl, q, nb, s, h->lane_cus);
+    return launch_k1_wave(h, q, nb, s, h->lane_cus);
   }
   p.tile_major = pl.spill_tile_major == 8 ? 8 : 0;   // (K2 of this batch reads what this launch writes)
   KParams q = p;
@@ -430,21 +456,21 @@ bool launch_k1_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
       q.div_magic = 0;
     }
   }
-  return select_k1_fast(pl, [&](auto kern, const KSel& a) { launch_sel(kern, dim3(pl.c2 / pl.g, nb), a, s, q); });
+  return select_k1_fast(pl, [&](auto kern, const KSel& a) { launch_sel(h, kern, dim3(pl.c2 / pl.g, nb), a, s, q); });
 }
 bool launch_k2_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
   const Plan& pl = h->pl;
   if (pl.fast_k2_lane) {
     if (p.tile_major) return false;
     const dim3 grid((unsigned)((uint64_t)pl.r * nb * pl.fast_k2_lane / 256));
-    return select_k2_lane(pl, p.pol_mode, [&](auto kern, const KSel& a) { launch_sel(kern, grid, a, s, p); });
+    return select_k2_lane(pl, p.pol_mode, [&](auto kern, const KSel& a) { launch_sel(h, kern, grid, a, s, p); });
   }
   if (priv_takes(pl, p, h->priv_grid)) {
     p.nblk = nb;
     if (pol_mode_no_sums(p.pol_mode) || (h->cfg.flags & kFlagSeparateStats)) p.stat_partial = nullptr;
     const uint64_t ntiles = (uint64_t)nb * (uint64_t)(pl.r / 4);
     const dim3 grid((unsigned)std::min<uint64_t>(ntiles, (uint64_t)h->priv_grid));
-    return select_k2_priv(pl, p.pol_mode, p.out_mode, [&](auto kern, const KSel& a) { launch_sel(kern, grid, a, s, p); });
+    return select_k2_priv(pl, p.pol_mode, p.out_mode, [&](auto kern, const KSel& a) { launch_sel(h, kern, grid, a, s, p); });
   }
   if (p.out_mode == FRBCH_OUT_STATS) return false;   // (only frbch_k2_priv has a statistics-only form: the engine asks for it nowhere else)
   if (!pl.fast_k2_wave && pl.fast_k2_log2m != 5) return false;   // (the barrier K2: 2C = 8192 only)
@@ -460,10 +486,10 @@ bool launch_k2_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
   }
   KParams& k = pl.k2_two_stage ? q : p;
   if (pl.fast_k2_wave) {
-    if (!launch_k2_wave(pl, k, nb, s, h->cfg.flags)) return false;
+    if (!launch_k2_wave(h, k, nb, s, h->cfg.flags)) return false;
   } else {
     select_k2_fast(pl, [&](auto kern, const KSel& a) {   // a workgroup of 1024 threads takes two time samples, or the tscrunch group
-      launch_sel(kern, dim3(pl.r / (a.nt == 512 ? 1 : std::max(2, k.tscr)), nb), a, s, k);
+      launch_sel(h, kern, dim3(pl.r / (a.nt == 512 ? 1 : std::max(2, k.tscr)), nb), a, s, k);
     });
   }
   if (pl.k2_two_stage) {
@@ -472,7 +498,9 @@ bool launch_k2_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
     p.scr_rows = (uint64_t)nb * pl.rows_per_block;
     p.stat_partial = nullptr;
     const uint64_t groups = p.scr_rows * (uint64_t)(pl.ncol / 4);
-    hipLaunchKernelGGL(fast::frbch_k2_scrunch, dim3((unsigned)std::min<uint64_t>((groups + 255) / 256, 8192)), dim3(256), 0, s, p);
+    const unsigned gx = (unsigned)std::min<uint64_t>((groups + 255) / 256, 8192);
+    if (h->profiling) note_launch(h, "frbch_k2_scrunch", gx, 1);
+    hipLaunchKernelGGL(fast::frbch_k2_scrunch, dim3(gx), dim3(256), 0, s, p);
   }
   return true;
 }
@@ -486,7 +514,7 @@ bool launch_k2c_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
   const uint32_t ntile = (uint32_t)(pl.r / tt);
   const uint32_t want = 4u * (uint32_t)std::max(1, h->lane_ncu);
   const uint32_t gy = std::max<uint32_t>(1, std::min<uint32_t>(nb, (want + ntile - 1) / ntile));
-  return select_k2c_fast(pl, [&](auto kern, const KSel& a) { launch_sel(kern, dim3(ntile, gy), a, s, p); });
+  return select_k2c_fast(pl, [&](auto kern, const KSel& a) { launch_sel(h, kern, dim3(ntile, gy), a, s, p); });
 }
 bool launch_k3_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
   const Plan& pl = h->pl;
@@ -495,11 +523,11 @@ bool launch_k3_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
     const uint64_t ntiles = (uint64_t)nb * pl.c;
     return select_k3_fast(pl, [&](auto kern, const KSel& a) {
       p.nblk = nb;
-      launch_sel(kern, dim3((unsigned)std::min<uint64_t>(ntiles, kK3WaveWgs)), a, s, p);
+      launch_sel(h, kern, dim3((unsigned)std::min<uint64_t>(ntiles, kK3WaveWgs)), a, s, p);
     });
   }
   const int np = pl.coh_nt / (16 << pl.coh_fast_r) / 2;
-  return select_k3_fast(pl, [&](auto kern, const KSel& a) { launch_sel(kern, dim3(pl.c / np, nb), a, s, p); });
+  return select_k3_fast(pl, [&](auto kern, const KSel& a) { launch_sel(h, kern, dim3(pl.c / np, nb), a, s, p); });
 }
 
 // =============================================================================================
@@ -618,7 +646,7 @@ int build_chirp(frbch_handle* h, int order_m) {
   cp.band_edge_mhz = cp.usb ? h->cfg.freq_mhz - abw / 2.0 : h->cfg.freq_mhz + abw / 2.0;
   cp.df_mhz = abw / pl.c;
   cp.dm_over_k = h->cfg.dm / kDmDispersion;
-  DEV_LAUNCH(frbch_chirp_build, (pl.n + 255) / 256, 1, 256, 0, h->stream, cp);
+  REC_LAUNCH(h, frbch_chirp_build, (pl.n + 255) / 256, 1, 256, 0, h->stream, cp);
   CHECK_DEV(h, dev_check_launch(), "launch chirp build");
   CHECK_DEV(h, dev_sync(h->stream), "sync");
   h->coh_order_m = order_m;
@@ -642,7 +670,7 @@ int launch_dls_count(frbch_handle* h, KParams& p, uint64_t nsamples, dev_stream_
   p.dls_lg_ns = pl.dls_lg_ns;
   KParams q = p;
   q.row0 = nwin;
-  DEV_LAUNCH(frbch_dls_count, (nwin + 3) / 4, 1, 256, 2048, s, q);
+  REC_LAUNCH(h, frbch_dls_count, (nwin + 3) / 4, 1, 256, 2048, s, q);
   CHECK_DEV(h, dev_check_launch(), "launch window counts");
   return FRBCH_OK;
 }
@@ -681,7 +709,7 @@ int launch_front(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
       }
     }
     if (!done) {
-      DEV_LAUNCH(frbch_k1_branch, pl.c2 / pl.g, nb, pl.nthreads, pl.k1_lds, s, p);
+      REC_LAUNCH(h, frbch_k1_branch, pl.c2 / pl.g, nb, pl.nthreads, pl.k1_lds, s, p);
       // the timing report says so when a launch of a handle planned for a register-pass K1 fell back to the generic one
       if (!h->kname[KID_K1].empty() && h->kname[KID_K1].find(kKernelNames[KID_K1]) == std::string::npos)
         h->kname[KID_K1] += std::string("+") + kKernelNames[KID_K1];
@@ -689,7 +717,7 @@ int launch_front(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
   }
   if (!pl.coherent) {
     ProfScope ps(h, s, KID_KC, (double)nb * pl.c2 * 16.0);
-    if (!launch_kc_fast(h, p, nb, s)) DEV_LAUNCH(frbch_kc_dcfix, 1, nb, pl.nthreads, pl.kc_lds, s, p);
+    if (!launch_kc_fast(h, p, nb, s)) REC_LAUNCH(h, frbch_kc_dcfix, 1, nb, pl.nthreads, pl.kc_lds, s, p);
   }
   CHECK_DEV(h, dev_check_launch(), "launch K1/Kc");
   return FRBCH_OK;
@@ -715,22 +743,23 @@ int launch_back(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
   if (pl.coherent) {   // K2c (branches -> channels, x kernel), K3 (back to time, detect), K4 (time-major rows)
     {
       ProfScope ps(h, s, KID_K2, ((double)nb * 16.0 + (pl.coh_fast_c ? 1.0 : (double)nb) * 8.0) * (double)pl.n);   // the register K2c reads the kernel table once per launch
-      if (!launch_k2c_fast(h, p, nb, s)) DEV_LAUNCH(frbch_k2c_chirp, pl.r / pl.tt, nb, pl.nthreads, pl.k2_lds, s, p);
+      if (!launch_k2c_fast(h, p, nb, s)) REC_LAUNCH(h, frbch_k2c_chirp, pl.r / pl.tt, nb, pl.nthreads, pl.k2_lds, s, p);
     }
     {
       ProfScope ps(h, s, KID_K3, (double)nb * ((double)pl.n * 8.0 + (double)pl.rows_per_block * pl.ncol * 4.0));
-      if (!launch_k3_fast(h, p, nb, s)) DEV_LAUNCH(frbch_k3_dedisp, pl.c, nb, pl.nthreads, pl.k3_lds, s, p);
+      if (!launch_k3_fast(h, p, nb, s)) REC_LAUNCH(h, frbch_k3_dedisp, pl.c, nb, pl.nthreads, pl.k3_lds, s, p);
     }
     {
       ProfScope ps(h, s, KID_K4, (double)nb * (double)pl.rows_per_block * (pl.ncol * 4.0 + out_b));
       const int tc = pl.ncol < 64 ? (int)pl.ncol : 64;
       const int gx = (int)((pl.rows_per_block + 63) / 64) * (int)(pl.ncol / tc);
 #ifndef FRBCH_NO_FAST
-      if (k4_fast_planned(pl, h->cfg.flags))
+      if (k4_fast_planned(pl, h->cfg.flags)) {
+        if (h->profiling) note_launch(h, "frbch_k4_fast", gx, nb);
         hipLaunchKernelGGL(fast::frbch_k4_fast, dim3(gx, nb), dim3(256), 0, s, p);
-      else
+      } else
 #endif
-      DEV_LAUNCH(frbch_k4_out, gx, nb, pl.nthreads, pl.k4_lds, s, p);
+      REC_LAUNCH(h, frbch_k4_out, gx, nb, pl.nthreads, pl.k4_lds, s, p);
     }
     CHECK_DEV(h, dev_check_launch(), "launch K2c/K3/K4");
     return FRBCH_OK;
@@ -741,7 +770,7 @@ int launch_back(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
   const int kid = KID_K2;
 #endif
   ProfScope ps(h, s, kid, bytes);
-  if (!launch_k2_fast(h, p, nb, s)) DEV_LAUNCH(frbch_k2_chan, pl.r / tile_t, nb, pl.nthreads, pl.k2_lds, s, p);
+  if (!launch_k2_fast(h, p, nb, s)) REC_LAUNCH(h, frbch_k2_chan, pl.r / tile_t, nb, pl.nthreads, pl.k2_lds, s, p);
   CHECK_DEV(h, dev_check_launch(), "launch K2");
   return FRBCH_OK;
 }
@@ -791,7 +820,7 @@ int run_stats(frbch_handle* h, uint64_t rows, dev_stream_t s) {
     sp.offset = h->offset;
     sp.scale = h->scale;
     ProfScope ps(h, s, KID_STATS, (double)h->fused_chunks * pl.ncol * 16.0);
-    DEV_LAUNCH(frbch_stats_final, (int)((pl.ncol + sp.cpw - 1) / sp.cpw), 1, 256, 256 * 2 * sizeof(double), s, sp);
+    REC_LAUNCH(h, frbch_stats_final, (int)((pl.ncol + sp.cpw - 1) / sp.cpw), 1, 256, 256 * 2 * sizeof(double), s, sp);
     CHECK_DEV(h, dev_check_launch(), "launch stats (final)");
     return FRBCH_OK;
   }
@@ -815,9 +844,9 @@ int run_stats(frbch_handle* h, uint64_t rows, dev_stream_t s) {
   sp.scale = h->scale;
   const int gx4 = (int)((pl.ncol / 4 * sp.rsplit + 63) / 64);
   ProfScope ps(h, s, KID_STATS, (double)rows * pl.ncol * 4.0);
-  DEV_LAUNCH(frbch_stats_partial, gx4, sp.nchunk, 64, 0, s, sp);
+  REC_LAUNCH(h, frbch_stats_partial, gx4, sp.nchunk, 64, 0, s, sp);
   sp.nchunk *= sp.rsplit;          // rows of partial sums the final reduction adds up (fixed order: deterministic)
-  DEV_LAUNCH(frbch_stats_final, (int)((pl.ncol + sp.cpw - 1) / sp.cpw), 1, 256, 256 * 2 * sizeof(double), s, sp);
+  REC_LAUNCH(h, frbch_stats_final, (int)((pl.ncol + sp.cpw - 1) / sp.cpw), 1, 256, 256 * 2 * sizeof(double), s, sp);
   CHECK_DEV(h, dev_check_launch(), "launch stats");
   return FRBCH_OK;
 }
@@ -894,8 +923,10 @@ int run_quantise(frbch_handle* h, uint64_t rows, uint8_t* dst, dev_stream_t s, i
           CHECK_DEV(h, dev_allow_lds(fast::frbch_quantise_fast<8, 512>, kHold), "LDS size digitiser");
           h->quant_lds_allowed = true;
         }
+        if (h->profiling) note_launch(h, "frbch_quantise_fast<8, 512>", qp.grid_x, 1);
         hipLaunchKernelGGL((fast::frbch_quantise_fast<8, 512>), dim3(qp.grid_x), dim3(512), kHold, s, qp);
       } else {
+        if (h->profiling) note_launch(h, "frbch_quantise_fast<8, 256>", qp.grid_x, 1);
         hipLaunchKernelGGL((fast::frbch_quantise_fast<8, 256>), dim3(qp.grid_x), dim3(256), 0, s, qp);
       }
       CHECK_DEV(h, dev_check_launch(), "launch quantise");
@@ -903,7 +934,7 @@ int run_quantise(frbch_handle* h, uint64_t rows, uint8_t* dst, dev_stream_t s, i
     }
   }
 #endif
-  DEV_LAUNCH(frbch_quantise, qp.grid_x, 1, 256, 0, s, qp);
+  REC_LAUNCH(h, frbch_quantise, qp.grid_x, 1, 256, 0, s, qp);
   CHECK_DEV(h, dev_check_launch(), "launch quantise");
   return FRBCH_OK;
 }
@@ -953,6 +984,7 @@ int apply_plan(frbch_handle* h) {
   h->fused_rows = 0;
   h->fused_valid = false;
   for (std::string& n : h->kname) n.clear();
+  h->launch_rec.clear();
   int rc;
   if ((rc = allow_generic_lds(h))) return rc;
   h->priv_grid = pl.fast_k2_priv ? 2 * std::max(1, h->lane_ncu) : 0;   // two 80-KiB workgroups per CU
@@ -989,9 +1021,10 @@ int launch_unpack_tap(frbch_handle* h, KParams& p, uint64_t nsamples, int decode
     if (rc) return rc;
   }
   if (decoder == 0) {
-    DEV_LAUNCH(frbch_unpack_tap, (nsamples + 255) / 256, 1, 256, 0, s, p);
+    REC_LAUNCH(h, frbch_unpack_tap, (nsamples + 255) / 256, 1, 256, 0, s, p);
   } else {
 #ifndef FRBCH_NO_FAST
+    if (h->profiling) note_launch(h, "frbch_unpack_tap_fast", (nsamples / 2 + 255) / 256, 1);
     hipLaunchKernelGGL(fast::frbch_unpack_tap_fast, dim3((unsigned)((nsamples / 2 + 255) / 256)), dim3(256), 0, s, p);
 #else
     return fail(h, FRBCH_E_ARG, "the register kernels are not part of this build");

@@ -361,6 +361,12 @@ int frbch_cornerturn_device(const char* recipe, const void* d_frames, size_t nfr
 int frbch_set_profiling(frbch_handle* h, int enable);
 int frbch_timing_reset(frbch_handle* h);
 int frbch_get_timing(frbch_handle* h, frbch_timing* t);
+/* Launch record: while profiling is on, every kernel launch of the channeliser path is counted under the full name of the
+ * instantiation, spelled as the demangled symbol ("frbch_k2_wave<3, 8, 4, 2, true>", "frbch_k2_chan"): what ran, where a timing
+ * slot names what was planned.  Writes one line per kernel, "name\tlaunches\tlargest grid.x\tlargest grid.y\n", NUL-terminated,
+ * and returns the text's length; FRBCH_E_CAPACITY when `cap` is too small.  frbch_timing_reset clears the record, and so does a
+ * stream that makes the handle plan anew. */
+long frbch_get_launch_record(frbch_handle* h, char* buf, size_t cap);
 
 /* library self-description: "frbch <abi> gfx950 ..." */
 const char* frbch_version(void);

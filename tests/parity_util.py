@@ -119,11 +119,29 @@ def check_codes(ref_bytes, got_bytes, ocfg):
 _ORACLE_CACHE: dict = {}
 
 
+def hurt_frames(raw, frames, frame_bytes=8032):
+    """the stream with the frames listed in frames["invalid"] flagged invalid (read as zero voltages) and those in frames["drop"]
+    missing (the stream path fills them with zero frames), as tests/test_gpu_pins.py::test_dropped_and_invalid_frames does it"""
+    fr = raw.reshape(-1, frame_bytes).copy()
+    for i in frames.get("invalid", ()):
+        fr[i, 3] |= 0x80
+    keep = np.ones(fr.shape[0], bool)
+    keep[list(frames.get("drop", ()))] = False
+    return fr[keep].reshape(-1)
+
+
 def run_streaming_case(lib, bw, nchan, secs, **kw):
-    """oracle .fil vs library .fil through push/flush/pull; returns mismatch count"""
+    """oracle .fil vs library .fil through push/flush/pull; returns mismatch count.
+    frames = dict(invalid = [...], drop = [...]): frames of the stream flagged invalid / missing (hurt_frames);
+    record = {}: the run has profiling on and the handle's launch record (kernel name -> launches, largest grid) is added to it"""
     kw = dict(kw)
     gen = {k: kw.pop(k) for k in ("bits", "payload_bytes", "legacy") if k in kw}    # input-format variants
+    frames = kw.pop("frames", None)
+    record = kw.pop("record", None)
     raw = synth.make_vdif(secs + kw.get("start", 0.0), bw_mhz=abs(bw), nchan=nchan, **gen)
+    if frames:
+        raw = hurt_frames(raw, frames, gen.get("payload_bytes", 8000) + (16 if gen.get("legacy") else 32))
+        gen["frames"] = tuple(sorted((k, tuple(v)) for k, v in frames.items()))   # (part of the oracle's cache key)
     okw = {k: v for k, v in kw.items() if k not in ("maxb", "flags")}
     # cases that differ only in kernel selection (flags) or batching (maxb) share ONE oracle run (the fp64 numpy chain at 2^24 .. 2^26
     # points is most of the GPU suite's wall time); the last few results are kept
@@ -138,8 +156,12 @@ def run_streaming_case(lib, bw, nchan, secs, **kw):
         _ORACLE_CACHE[key] = (ref, ocfg)
     cfg = lib_cfg(lib, bw, nchan, secs, **kw)
     with ch.Channeliser(cfg, lib) as c:
+        if record is not None:
+            c.set_profiling(True)
         got = c.channelise_bytes(raw)
         resc = c.get_rescale() if c.get_info().have_rescale else None
+        if record is not None:
+            record.update(c.get_launch_record())
     nbad = check_codes(ref, got, ocfg)
     if resc is not None and kw.get("interval", 10.0) > 0 and kw.get("const", 1) and "offset0" in ocfg.result:
         off0, sc0 = ocfg.result["offset0"], ocfg.result["scale0"]

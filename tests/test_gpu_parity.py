@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+from tests import kernel_table as kt
 from tests import parity_util as pu
 
 pytestmark = pytest.mark.gpu
@@ -51,7 +52,7 @@ CASES = [
     (16.0, 256, 0.04, dict(pol=4, tscr=8)),
     (-16.0, 512, 0.08, dict(tscr=2)),                        # M = 4  (R = 2C = 1024)
     (64.0, 2048, 0.3, dict(tscr=2)),                         # M = 16 (R = 2C = 4096), config-5 channel count
-    (64.0, 2048, 0.3, dict(pol=4, tscr=4)),                  # tscrunch > fast K2 tile: generic K2 + fast K1
+    (64.0, 2048, 0.3, dict(pol=4, tscr=4)),                  # -t 4 = the four-sample tile of the wave K2 at 2C = 4096 (frbch_k2_wave<4,8,4,2>)
     (32.0, 512, 0.1, dict(freq_res=2048)),                   # R != 2C: fast K1 (M=8) + fast K2 (M=4)
     (32.0, 1024, 0.2, dict(start=10 / 64e6)),                # -S not on a 4-byte boundary: generic K1 feeds the fast K2
     (32.0, 1024, 0.2, dict(start=2 / 64e6, pol=4, tscr=2)),
@@ -71,18 +72,18 @@ CASES = [
     (32.0, 2048, 0.6, dict(dm=56.7, coherent=1, freq=1400.0, start=2 / 64e6)),  # -S off the K1 piece boundary: falls back to the generic K1 / K3, kernel table rebuilt
     (16.0, 256, 0.2, dict(dm=20.0, coherent=1, freq=600.0, pol=0, nbit=16)),     # M = 2 / 2
     (64.0, 4096, 1.1, dict(tscr=8)),                         # BASELINE config 4 shape (-t 8 -F4096:8192), 2 blocks: M = 32 wave kernels, two-stage tscrunch (K2 rows of two samples + frbch_k2_scrunch)
-    (-64.0, 4096, 0.55, dict(tscr=4, nbit=2)),                # two-stage tscrunch, factor 2, 2-bit codes, LSB
+    (-64.0, 4096, 0.55, dict(tscr=4, nbit=2)),                # two-stage tscrunch, factor 2, 2-bit codes, LSB (frbch_k2_wave<5,8,2,4,false> + frbch_k2_scrunch)
     (64.0, 4096, 0.55, dict(tscr=8, flags=3)),                # the same through the generic kernels
-    (-64.0, 4096, 0.55, {}),                                  # M = 32, -t 1, LSB: wave K2 (frbch_k2_wave<5,8,2,4>, two time samples per workgroup, sums fused)
+    (-64.0, 4096, 0.55, {}),                                  # M = 32, -t 1, LSB: wave K2 (frbch_k2_wave<5,8,2,4,true>, two time samples per workgroup, sums fused)
     (64.0, 4096, 0.55, dict(tscr=2, nbit=-32)),               # the same with -t 2 (one output row per tile)
-    (64.0, 4096, 0.55, dict(pol=1, nbit=16)),                 # the same kernel family, single-product instantiation, USB
+    (64.0, 4096, 0.55, dict(pol=1, nbit=16)),                 # the same kernel family, single-product instantiation, USB (frbch_k2_wave<5,8,0,4,true>)
     (64.0, 4096, 0.55, dict(flags=1 << 20, nbit=2)),          # wave K2 with the separate statistics pass
     (64.0, 4096, 0.55, dict(pol=4, tscr=2, nbit=16)),         # M = 32, coherency products
     (64.0, 4096, 0.55, dict(pol=4, tscr=4)),                  # four products and tscrunch > 2: barrier K2 (two-sample rows) + frbch_k2_scrunch (round 3; generic K2 before)
     (-64.0, 4096, 0.55, dict(pol=5, tscr=8, nbit=16)),        # ... the IQUV spelling of config 4's `-t 8`
     (64.0, 4096, 1.1, dict(pol=4, tscr=8, interval=0.6, maxb=1)),   # ... the rescale interval ends inside the scan, one block per launch (2 blocks)
     # Stokes I,Q,U,V (pol_mode 5, the `-d4 -iquv` extension; north_star "IQUV formation") through every K2 family
-    (32.0, 1024, 0.14, dict(pol=5)),                         # wave K2, MSTAT instantiation while the interval is measured
+    (32.0, 1024, 0.14, dict(pol=5)),                         # frbch_k2_priv<5, ...>: the two-pass rescale (statistics pass, then codes), automatic with four products
     (-32.0, 1024, 0.14, dict(pol=5, tscr=2, nbit=16)),
     (32.0, 1024, 0.14, dict(pol=5, flags=2)),                # generic K2
     (16.0, 128, 0.05, dict(pol=5, tscr=8, nbit=-32)),        # 2C = 256 wave K2
@@ -104,12 +105,23 @@ CASES = [
     (16.0, 64, 0.02, dict(pol=5, nbit=-32, tscr=32)),
     (16.0, 64, 0.02, dict(pol=1, nbit=2, tscr=8, interval=0.005)),
     (16.0, 64, 0.02, dict(tscr=64)),                          # beyond the lane pair's 32 samples: generic K2
+    # M = 32 again: (PP+QQ)^2 has no fused sums, its float rows come from the plain single-product instantiation (frbch_k2_wave<5,8,0,4,false>)
+    (64.0, 4096, 0.55, dict(pol=3, nbit=2)),
 ]
 
 
 @pytest.mark.parametrize("bw,nchan,secs,kw", CASES)
 def test_fil_matches_oracle(hip_lib, bw, nchan, secs, kw):
-    pu.run_streaming_case(hip_lib, bw, nchan, secs, **kw)
+    """the cases tests/kernel_table.py points at (kernels that only the 2^26-sample block reaches) run with the launch record on:
+    the instantiation the table names is the one that ran, and no launch fell back to a generic K1, Kc or K2"""
+    want = kt.case_kernels(bw, nchan, secs, kw)
+    if not want:
+        pu.run_streaming_case(hip_lib, bw, nchan, secs, **kw)
+        return
+    rec = {}
+    pu.run_streaming_case(hip_lib, bw, nchan, secs, record=rec, **kw)
+    fallbacks = {"frbch_k1_branch", "frbch_kc_dcfix", "frbch_k2_chan"} & set(rec)
+    assert set(want) <= set(rec) and not fallbacks, (want, sorted(rec))
 
 
 def test_power_tap_matches_oracle(hip_lib):
