@@ -71,6 +71,16 @@ class FrbchFoldModel(C.Structure):
                 ("dm", C.c_double), ("apply_delays", C.c_uint32), ("nbin", C.c_uint32), ("subint_s", C.c_double)]
 
 
+class FrbchSpParams(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("nwidth", C.c_uint32), ("widths", C.c_uint32 * 16), ("detrend_len", C.c_uint32),
+                ("reserved", C.c_uint32), ("threshold", C.c_double)]
+
+
+class FrbchSpCand(C.Structure):
+    _fields_ = [("dm_index", C.c_uint32), ("width", C.c_uint32), ("sample", C.c_uint64), ("sigma", C.c_float),
+                ("reserved", C.c_uint32)]
+
+
 class _KTiming(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double),
                 ("algorithmic_bytes", C.c_double)]
@@ -126,6 +136,13 @@ SYMBOLS = {
                                    C.c_uint32, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
     "frbch_foldp_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchFoldModel), C.c_int, _P, _P,
                                      C.c_uint32, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_spsearch_host": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.POINTER(FrbchSpParams), C.c_int, _P, C.c_uint64,
+                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_spsearch_device": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.POINTER(FrbchSpParams), C.c_int, _P, C.c_uint64,
+                                        C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_dedisperse_search_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_double,
+                                               C.POINTER(FrbchSpParams), C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64), _P,
+                                               C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
     "frbch_cornerturn_info": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
     "frbch_cornerturn_host": (C.c_int, [C.c_char_p, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(_P), C.c_uint32,

@@ -41,6 +41,7 @@ typedef float frbch_nf4 __attribute__((ext_vector_type(4)));
 #define ATOMIC_ADD_U64(ptr, v) atomicAdd((unsigned long long*)(ptr), (unsigned long long)(v))
 #define ATOMIC_ADD_U32(ptr, v) atomicAdd((unsigned int*)(ptr), (unsigned int)(v))
 #define ATOMIC_ADD_F64(ptr, v) atomicAdd((double*)(ptr), (double)(v))
+#define ATOMIC_FETCH_ADD_U32(ptr, v) atomicAdd((unsigned int*)(ptr), (unsigned int)(v))   /* returns the old value */
 #define POST_NO_CONTRACT _Pragma("clang fp contract(off)")
 
 typedef hipStream_t dev_stream_t;

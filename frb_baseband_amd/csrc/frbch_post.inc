@@ -566,6 +566,210 @@ extern "C" int frbch_foldp_host(const frbch_fil_desc* fil, const void* rows, uin
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// single-pulse search of the dedispersed series
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr uint32_t kSpRawCap = 1u << 20;     // raw peaks the device list holds (24 MiB); more: FRBCH_E_CAPACITY, never a cut list
+
+int sp_check(const frbch_sp_params* sp, uint64_t* blk_len, const PostErr& e) {
+  if (!sp || sp->size != sizeof(frbch_sp_params)) return e.fail(FRBCH_E_ARG, "frbch_sp_params: wrong size");
+  if (!(sp->threshold > 0.0) || !(sp->threshold <= 1.0e6)) return e.fail(FRBCH_E_ARG, "threshold must lie in (0, 1e6]");
+  if (sp->nwidth < 1 || sp->nwidth > 16) return e.fail(FRBCH_E_ARG, "1..16 widths");
+  for (uint32_t k = 0; k < sp->nwidth; ++k)
+    if (sp->widths[k] < 1 || sp->widths[k] > 1024 || (k && sp->widths[k] <= sp->widths[k - 1]))
+      return e.fail(FRBCH_E_ARG, "widths must be strictly ascending, each 1..1024");
+  *blk_len = sp->detrend_len ? sp->detrend_len : 1000;
+  if (*blk_len < 64 || *blk_len > 65536) return e.fail(FRBCH_E_ARG, "detrend_len must be 0 (= 1000) or 64..65536");
+  return FRBCH_OK;
+}
+
+// Which search kernel a call takes -- the one decision behind frbch_spsearch_device's launch and *kernel_used.  true = the
+// LDS kernel (kernels_post_fast.inc): the tile and the halo of the largest LISTED width (one that exceeds nout included)
+// fit its prefix array, kSpTile + 2 wmax <= kSpLdsN, and sample indices fit 32 bits.  The emulator build has no such
+// kernel: false.
+bool sp_search_lds(const frbch_sp_params* sp, uint64_t nout) {
+#ifndef FRBCH_NO_FAST
+  return (int)sp->widths[sp->nwidth - 1] <= fast::kSpMaxWidth && nout < (1ull << 31);
+#else
+  (void)sp; (void)nout;
+  return false;
+#endif
+}
+
+struct SpRaw {
+  uint32_t width;
+  uint64_t centre;
+  long long sum;
+  double sigma;
+};
+}  // namespace
+
+extern "C" int frbch_spsearch_device(const float* d_series, uint32_t ndm, uint64_t nout, const frbch_sp_params* sp, int device,
+                                     frbch_sp_cand* cands, uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, char* err,
+                                     size_t err_cap) {
+  PostErr e{err, err_cap};
+  uint64_t blk_len = 0;
+  int rc = sp_check(sp, &blk_len, e);
+  if (rc) return rc;
+  if (!d_series || !ncand || (cap && !cands)) return e.fail(FRBCH_E_ARG, "null argument");
+  if (!ndm || !nout || ndm > 65535) return e.fail(FRBCH_E_ARG, "ndm must be 1..65535, nout positive");
+  if (device < 0 || device >= dev_count()) return e.fail(FRBCH_E_DEVICE, "no such GPU (there is no CPU fallback)");
+  DeviceGuard dg(device);
+  dev_stream_t s = 0;
+  if (dev_stream_create(&s) != 0) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  SpParams p;
+  memset(&p, 0, sizeof p);
+  p.series = d_series;
+  p.nout = nout;
+  p.ndm = (int)ndm;
+  p.blk_len = blk_len;
+  p.nblk = (uint32_t)std::max<uint64_t>(1, nout / blk_len);
+  p.nwidth = (int)sp->nwidth;
+  for (uint32_t k = 0; k < sp->nwidth; ++k) {
+    p.width[k] = (int)sp->widths[k];
+    const double scaled = sp->threshold * 1024.0;
+    const double t = ceil(scaled * sqrt((double)sp->widths[k]));
+    p.thr[k] = t < 9.0e18 ? (long long)t : INT64_MAX;             // (no sum reaches 2^37)
+  }
+  p.peak_cap = kSpRawCap;
+  auto cleanup = [&]() { dev_free(p.stats); dev_free(p.q); dev_free(p.peaks); dev_free(p.npeak); dev_stream_destroy(s); };
+#define POST_DEV(expr, what) do { if ((expr) != 0) { cleanup(); return e.fail(FRBCH_E_DEVICE, std::string(what) + ": " + dev_last_error_string()); } } while (0)
+  POST_DEV(dev_malloc((void**)&p.stats, (size_t)ndm * p.nblk * 2 * sizeof(double)), "hipMalloc");
+  POST_DEV(dev_malloc((void**)&p.peaks, (size_t)kSpRawCap * sizeof(SpPeak)), "hipMalloc");
+  POST_DEV(dev_malloc((void**)&p.npeak, sizeof(uint32_t)), "hipMalloc");
+  POST_DEV(dev_memset(p.npeak, 0, sizeof(uint32_t), s), "clear peak count");
+  DEV_LAUNCH(frbch_post_sp_stats, p.nblk, ndm, kSpPartials, (3 * kSpPartials + 2) * sizeof(double), s, p);
+  POST_DEV(dev_check_launch(), "launch block statistics");
+  const bool lds = sp_search_lds(sp, nout);
+#ifndef FRBCH_NO_FAST
+  if (lds)
+    hipLaunchKernelGGL(fast::frbch_post_sp_search_lds, dim3((unsigned)((nout + fast::kSpTile - 1) / fast::kSpTile), ndm),
+                       dim3(fast::kSpThreads), 0, s, p);
+#endif
+  if (!lds) {
+    POST_DEV(dev_malloc((void**)&p.q, (size_t)ndm * nout * sizeof(int32_t)), "hipMalloc");
+    DEV_LAUNCH(frbch_post_sp_quant, (nout + 255) / 256, ndm, 256, 0, s, p);
+    POST_DEV(dev_check_launch(), "launch quantise");
+    DEV_LAUNCH(frbch_post_sp_search, (nout + 255) / 256, ndm, 256, 0, s, p);
+  }
+  POST_DEV(dev_check_launch(), "launch search");
+  uint32_t nraw = 0;
+  POST_DEV(dev_d2h(&nraw, p.npeak, sizeof nraw, s), "download peak count");
+  POST_DEV(dev_sync(s), "sync");
+  if (nraw > kSpRawCap) {
+    cleanup();
+    return e.fail(FRBCH_E_CAPACITY, "threshold too low: " + std::to_string(nraw) + " raw peaks, the device list holds " +
+                                        std::to_string(kSpRawCap));
+  }
+  std::vector<SpPeak> raw(nraw);
+  if (nraw) {
+    POST_DEV(dev_d2h(raw.data(), p.peaks, (size_t)nraw * sizeof(SpPeak), s), "download peaks");
+    POST_DEV(dev_sync(s), "sync");
+  }
+#undef POST_DEV
+  cleanup();
+  if (kernel_used) *kernel_used = lds ? 1 : 0;
+  // across widths, DM by DM, on the raw list (one pass, not iterated): a raw peak falls to a stronger one whose centre
+  // lies within half the larger of the two widths; equal sigma: the narrower wins, then the earlier
+  std::sort(raw.begin(), raw.end(), [](const SpPeak& a, const SpPeak& b) {
+    return a.dm != b.dm ? a.dm < b.dm : a.t + a.width / 2 != b.t + b.width / 2 ? a.t + a.width / 2 < b.t + b.width / 2 : a.width < b.width;
+  });
+  uint64_t total = 0;
+  std::vector<SpRaw> one;
+  const uint64_t reach = sp->widths[sp->nwidth - 1] / 2;
+  for (size_t i0 = 0; i0 < raw.size();) {
+    size_t i1 = i0;
+    one.clear();
+    for (; i1 < raw.size() && raw[i1].dm == raw[i0].dm; ++i1) {
+      SpRaw r;
+      r.width = raw[i1].width;
+      r.centre = raw[i1].t + raw[i1].width / 2;
+      r.sum = raw[i1].sum;
+      r.sigma = (double)raw[i1].sum / (1024.0 * sqrt((double)raw[i1].width));
+      one.push_back(r);
+    }
+    size_t first = 0;                                             // one[first ..) may still lie within `reach` of one[i]
+    for (size_t i = 0; i < one.size(); ++i) {
+      const SpRaw& a = one[i];
+      while (one[first].centre + reach < a.centre) ++first;
+      bool dropped = false;
+      for (size_t j = first; j < one.size() && one[j].centre <= a.centre + reach && !dropped; ++j) {
+        if (j == i) continue;
+        const SpRaw& b = one[j];
+        const uint64_t dist = a.centre > b.centre ? a.centre - b.centre : b.centre - a.centre;
+        if (dist > std::max(a.width, b.width) / 2) continue;
+        dropped = b.sigma > a.sigma || (b.sigma == a.sigma && (b.width < a.width || (b.width == a.width && b.centre < a.centre)));
+      }
+      if (dropped) continue;
+      if (total < cap) {                                          // (centre, width) ascending already: the output order
+        frbch_sp_cand& c = cands[total];
+        c.dm_index = raw[i0].dm;
+        c.width = a.width;
+        c.sample = a.centre;
+        c.sigma = (float)a.sigma;
+        c.reserved = 0;
+      }
+      ++total;
+    }
+    i0 = i1;
+  }
+  *ncand = total;
+  if (total > cap) return e.fail(FRBCH_E_CAPACITY, std::to_string(total) + " candidates, room for " + std::to_string(cap));
+  return FRBCH_OK;
+}
+
+extern "C" int frbch_spsearch_host(const float* series, uint32_t ndm, uint64_t nout, const frbch_sp_params* sp, int device,
+                                   frbch_sp_cand* cands, uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, char* err,
+                                   size_t err_cap) {
+  PostErr e{err, err_cap};
+  uint64_t blk_len = 0;
+  int rc = sp_check(sp, &blk_len, e);
+  if (rc) return rc;
+  if (!series || !ndm || !nout) return e.fail(FRBCH_E_ARG, "null argument");
+  if (device < 0 || device >= dev_count()) return e.fail(FRBCH_E_DEVICE, "no such GPU (there is no CPU fallback)");
+  DeviceGuard dg(device);
+  const size_t bytes = (size_t)ndm * nout * sizeof(float);
+  float* d_series = nullptr;
+  if (dev_malloc((void**)&d_series, bytes) != 0) return e.fail(FRBCH_E_NOMEM, "device memory for the series");
+  rc = dev_h2d(d_series, series, bytes, 0) != 0 || dev_sync(0) != 0 ? e.fail(FRBCH_E_DEVICE, "upload series") : FRBCH_OK;
+  if (!rc) rc = frbch_spsearch_device(d_series, ndm, nout, sp, device, cands, cap, ncand, kernel_used, err, err_cap);
+  dev_free(d_series);
+  return rc;
+}
+
+extern "C" int frbch_dedisperse_search_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const double* dms,
+                                            uint32_t ndm, uint32_t zerodm, double clip_sigma, const frbch_sp_params* sp,
+                                            int device, float* series_out, uint64_t nout, uint64_t* nclipped,
+                                            frbch_sp_cand* cands, uint64_t cap, uint64_t* ncand, uint32_t* kernel_used,
+                                            char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  int rc = post_check_fil(fil, nrows, e);
+  if (rc) return rc;
+  uint64_t blk_len = 0;
+  rc = sp_check(sp, &blk_len, e);
+  if (rc) return rc;
+  if (!rows || !ncand || (cap && !cands)) return e.fail(FRBCH_E_ARG, "null argument");
+  if (device < 0 || device >= dev_count()) return e.fail(FRBCH_E_DEVICE, "no such GPU (there is no CPU fallback)");
+  DeviceGuard dg(device);
+  const size_t in_bytes = (size_t)nrows * fil->nifs * fil->nchan * (size_t)(fil->nbits / 8);
+  const size_t out_bytes = (size_t)ndm * nout * sizeof(float);
+  void* d_rows = nullptr;
+  float* d_out = nullptr;
+  if (dev_malloc(&d_rows, in_bytes) != 0 || dev_malloc((void**)&d_out, out_bytes) != 0) {
+    dev_free(d_rows); dev_free(d_out);
+    return e.fail(FRBCH_E_NOMEM, "device memory for the rows");
+  }
+  rc = dev_h2d(d_rows, rows, in_bytes, 0) != 0 || dev_sync(0) != 0 ? e.fail(FRBCH_E_DEVICE, "upload rows") : FRBCH_OK;
+  if (!rc) rc = frbch_dedisperse_device(fil, d_rows, nrows, dms, ndm, zerodm, clip_sigma, device, d_out, nout, nclipped, err, err_cap);
+  dev_free(d_rows);                                                // the plane stays in HBM; the rows are done with
+  d_rows = nullptr;
+  if (!rc && series_out && (dev_d2h(series_out, d_out, out_bytes, 0) != 0 || dev_sync(0) != 0)) rc = e.fail(FRBCH_E_DEVICE, "download series");
+  if (!rc) rc = frbch_spsearch_device(d_out, ndm, nout, sp, device, cands, cap, ncand, kernel_used, err, err_cap);
+  dev_free(d_out);
+  return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // corner turn
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {

@@ -288,6 +288,176 @@ KERNEL(frbch_post_u64_to_f64, FoldpParams) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Single-pulse search of the dedispersed series (frbch_spsearch_*; include/frbch.h states the arithmetic): per-block
+// statistics in double in a FIXED order, samples normalised and quantised to integers q = floor(z 1024 + 0.5), and from
+// there on integers only -- boxcar sums, threshold and local-maximum tests are exact in any order, so the generic kernel
+// below, the LDS kernel of kernels_post_fast.inc and tests/spsearch_oracle.py agree to the bit.
+// ---------------------------------------------------------------------------------------------------------------------
+#ifndef ATOMIC_FETCH_ADD_U32   // (a device layer without it: workgroups are host threads there)
+#define ATOMIC_FETCH_ADD_U32(ptr, v) __atomic_fetch_add((unsigned int*)(ptr), (unsigned int)(v), __ATOMIC_RELAXED)
+#endif
+
+struct SpPeak {                // a raw peak: local maximum of one width's boxcar series above the threshold
+  uint32_t dm, width;
+  uint64_t t;                  // first sample of the boxcar
+  long long sum;               // S_w[t]
+};
+
+struct SpParams {
+  const float* series;         // [ndm][nout]
+  uint64_t nout;
+  int ndm;
+  uint64_t blk_len;            // L: samples per statistics block (the last block runs to nout)
+  uint32_t nblk;               // max(1, nout / L)
+  double* stats;               // [ndm][nblk][2]: mean, 1 / sigma of the second round; a dead block holds (0, 0)
+  int32_t* q;                  // [ndm][nout] quantised samples (generic kernels only)
+  int nwidth;
+  int width[16];               // ascending
+  long long thr[16];           // T_w = ceil(threshold 1024 sqrt(w))
+  SpPeak* peaks;               // [peak_cap], appended in any order
+  uint32_t* npeak;             // every raw peak counts, stored or not
+  uint32_t peak_cap;
+};
+
+constexpr int kSpPartials = 64;            // partial sums per block = threads of frbch_post_sp_stats
+constexpr double kSpClip = 65536.0;        // |z| is clipped here: |q| <= 2^26, a sum of 1024 of them < 2^37
+
+// q of sample x with its block's (mean, 1 / sigma); every operation rounded on its own
+DEVFN inline int32_t sp_quantise(float x, double mean, double inv) {
+  POST_NO_CONTRACT
+  if (inv == 0.0) return 0;                                      // dead block (x may be anything, NaN included)
+  const double d = (double)x - mean;
+  double z = d * inv;
+  if (z > kSpClip) z = kSpClip;
+  if (z < -kSpClip) z = -kSpClip;
+  const double zs = z * 1024.0;
+  return (int32_t)floor(zs + 0.5);
+}
+
+DEVFN inline void sp_append(const SpParams& p, int dm, int w, uint64_t t, long long s) {
+  const uint32_t i = ATOMIC_FETCH_ADD_U32(p.npeak, 1u);
+  if (i < p.peak_cap) {
+    SpPeak k;
+    k.dm = (uint32_t)dm; k.width = (uint32_t)w; k.t = t; k.sum = s;
+    p.peaks[i] = k;
+  }
+}
+
+// Block statistics: grid (nblk, ndm), 64 threads, smem 64 x 3 doubles + 2.  Thread j sums the samples at block positions
+// j, j + 64, ... in ascending order; thread 0 adds the 64 partials in ascending j.  Round 2 keeps |x - mean1| <= 3 sigma1,
+// every sample in its own partial.
+KERNEL(frbch_post_sp_stats, SpParams) {
+  K_PROLOGUE;
+  (void)nthr;
+  double* part = (double*)smem;                                  // [3][64]: s1, s2, n
+  double* first = part + 3 * kSpPartials;                        // mean1, 3 sigma1 (sigma1 = 0: dead)
+  const uint64_t b0 = (uint64_t)bx * p.blk_len;
+  const uint64_t b1 = (uint32_t)bx + 1 == p.nblk ? p.nout : b0 + p.blk_len;
+  const float* x = p.series + (size_t)by * p.nout;
+  double* out = p.stats + ((size_t)by * p.nblk + bx) * 2;
+  for (int round = 0; round < 2; ++round) {
+    PHASE {
+      POST_NO_CONTRACT
+      double s1 = 0.0, s2 = 0.0, n = 0.0;
+      if (tid < kSpPartials && (round == 0 || first[1] > 0.0)) {
+        for (uint64_t t = b0 + tid; t < b1; t += kSpPartials) {
+          const double v = (double)x[t];
+          if (round == 1 && !(fabs(v - first[0]) <= first[1])) continue;
+          const double vv = v * v;
+          s1 = s1 + v;
+          s2 = s2 + vv;
+          n = n + 1.0;
+        }
+      }
+      if (tid < kSpPartials) { part[tid] = s1; part[kSpPartials + tid] = s2; part[2 * kSpPartials + tid] = n; }
+    }
+    SYNC;
+    PHASE {
+      POST_NO_CONTRACT
+      if (tid == 0) {
+        double s1 = 0.0, s2 = 0.0, n = 0.0;
+        for (int j = 0; j < kSpPartials; ++j) { s1 = s1 + part[j]; s2 = s2 + part[kSpPartials + j]; n = n + part[2 * kSpPartials + j]; }
+        double mean = 0.0, sig = 0.0;
+        if (n > 0.0) {
+          mean = s1 / n;
+          const double m2 = s2 / n;
+          const double mm = mean * mean;
+          const double var = m2 - mm;
+          sig = var > 0.0 ? sqrt(var) : 0.0;
+        }
+        if (round == 0) {
+          first[0] = mean;
+          first[1] = 3.0 * sig;
+        } else {
+          const bool live = first[1] > 0.0 && sig > 0.0;
+          out[0] = live ? mean : 0.0;
+          out[1] = live ? 1.0 / sig : 0.0;
+        }
+      }
+    }
+    SYNC;
+  }
+}
+
+DEVFN inline const double* sp_block(const SpParams& p, int dm, uint64_t t) {
+  uint64_t b = t / p.blk_len;
+  if (b >= p.nblk) b = p.nblk - 1;
+  return p.stats + ((size_t)dm * p.nblk + b) * 2;
+}
+
+// q[dm][t] for the generic search.  grid (ceil(nout / 256), ndm)
+KERNEL(frbch_post_sp_quant, SpParams) {
+  K_PROLOGUE;
+  (void)smem;
+  PHASE {
+    const uint64_t t = (uint64_t)bx * nthr + tid;
+    if (t < p.nout) {
+      const double* st = sp_block(p, by, t);
+      p.q[(size_t)by * p.nout + t] = sp_quantise(p.series[(size_t)by * p.nout + t], st[0], st[1]);
+    }
+  }
+}
+
+// S_w[t] of the quantised series, summed directly
+DEVFN inline long long sp_boxcar(const int32_t* q, uint64_t t, int w) {
+  long long s = 0;
+  for (int i = 0; i < w; ++i) s += q[t + i];
+  return s;
+}
+
+// The generic search: grid (ceil(nout / 256), ndm), one thread per (dm, t).  The widths ascend, so S_w[t] grows from the
+// previous width's sum; a sum that passes the threshold is compared with its neighbours t - h .. t + h (h = w / 2, cut to
+// the valid range), strictly greater than the earlier ones, not less than the later ones.
+KERNEL(frbch_post_sp_search, SpParams) {
+  K_PROLOGUE;
+  (void)smem;
+  PHASE {
+    const uint64_t t = (uint64_t)bx * nthr + tid;
+    if (t < p.nout) {
+      const int32_t* q = p.q + (size_t)by * p.nout;
+      long long s = 0;
+      int have = 0;
+      for (int k = 0; k < p.nwidth; ++k) {
+        const int w = p.width[k];
+        if ((uint64_t)w > p.nout || t > p.nout - (uint64_t)w) break;
+        for (; have < w; ++have) s += q[t + have];
+        if (s < p.thr[k]) continue;
+        const uint64_t h = (uint64_t)(w / 2), last = p.nout - (uint64_t)w;
+        const uint64_t lo = t > h ? t - h : 0, hi = t + h < last ? t + h : last;
+        bool peak = true;
+        long long v = sp_boxcar(q, lo, w);
+        for (uint64_t u = lo; u <= hi && peak; ++u) {
+          if (u < t) peak = s > v;
+          else if (u > t) peak = s >= v;
+          if (u < hi) v += (long long)q[u + w] - (long long)q[u];
+        }
+        if (peak) sp_append(p, by, w, t, s);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Corner turn (SURVEY 8f row 2): what jive5ab's spif2file does with the recipe strings of spif2file.sh:31-113 -- one
 // recorder stream in which every W-bit word holds one time sample of ALL channels is split into one 2-channel stream
 // per IF ("tag"): output group g takes bits src[g][0..glen) of every word, in that order, LSB first.

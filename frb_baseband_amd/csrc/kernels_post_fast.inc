@@ -189,4 +189,82 @@ __global__ void __launch_bounds__(kFoldThreads) frbch_post_foldp_lds(FoldpParams
     if (v) atomicAdd(dst + (size_t)b * p.nchan + ch, (unsigned long long)v);
   }
 }
+// ---------------------------------------------------------------------------------------------------------------------
+// Single-pulse search in the LDS (HIP only; frbch_post_sp_quant + frbch_post_sp_search of kernels_post.inc stay the emulable
+// form and the fallback).  A workgroup of 256 threads owns one DM and kSpTile consecutive start samples t.  It needs the
+// quantised samples q[t0 - hmax .. t0 + kSpTile - 1 + hmax + wmax - 1], hmax = wmax / 2: wmax behind the last boxcar and
+// the local-maximum window of the widest boxcar on both sides.  They are loaded ONCE, coalesced (lane i takes sample
+// a + i, a + 256 + i, ...), normalised and quantised on the way in from the per-block (mean, 1 / sigma) table, and turned
+// into one exclusive prefix sum P[0 .. n] of 64-bit integers (|q| <= 2^26 and n < 2^12: no overflow): every thread sums a
+// run of kSpRun consecutive samples in registers, the run totals are scanned with wave shuffles and four wave totals,
+// and the runs are written back.  From there S_w[t] = P[t - a + w] - P[t - a] is two LDS reads at stride 1 across the
+// lanes (64-bit words, consecutive lanes on consecutive bank pairs: conflict-free).  Every (width, t) is first held
+// against the threshold; only the rare survivors walk their local-maximum window.  Peaks go to the global list through
+// an ordinary vector atomic counter (the host sorts).  LDS: 24 KiB of P + 32 bytes: six workgroups per CU.
+// The host takes this kernel when kSpTile + 2 wmax <= kSpLdsN (wmax <= 512) and nout < 2^31 (32-bit sample indices).
+constexpr int kSpTile = 2048, kSpLdsN = 3072, kSpThreads = 256, kSpRun = kSpLdsN / kSpThreads;
+constexpr int kSpMaxWidth = (kSpLdsN - kSpTile) / 2;
+
+__global__ void __launch_bounds__(kSpThreads) frbch_post_sp_search_lds(SpParams p) {
+  __shared__ long long pre[kSpLdsN + 1];
+  __shared__ long long wave_tot[kSpThreads / 64];
+  const int tid = threadIdx.x, dm = blockIdx.y;
+  const int nout = (int)p.nout;
+  const int wmax = p.width[p.nwidth - 1], hmax = wmax / 2;
+  const int t0 = (int)blockIdx.x * kSpTile;
+  const int a = t0 - hmax;                                        // sample of P's first difference (may be negative)
+  const int n = kSpTile + 2 * hmax + wmax - 1;                    // <= kSpLdsN - 1
+  const float* x = p.series + (size_t)dm * p.nout;
+  const double* st = p.stats + (size_t)dm * p.nblk * 2;
+  const uint32_t blk_len = (uint32_t)p.blk_len;
+  for (int i = tid; i < kSpLdsN; i += kSpThreads) {               // raw q first: pre[i + 1] = q[a + i], 0 outside the series
+    const int g = a + i;
+    long long v = 0;
+    if (i < n && g >= 0 && g < nout) {
+      uint32_t b = (uint32_t)g / blk_len;
+      if (b >= p.nblk) b = p.nblk - 1;
+      v = sp_quantise(x[g], st[2 * b], st[2 * b + 1]);
+    }
+    pre[i + 1] = v;
+  }
+  if (tid == 0) pre[0] = 0;
+  __syncthreads();
+  long long run[kSpRun], tot = 0;
+#pragma unroll
+  for (int k = 0; k < kSpRun; ++k) {
+    tot += pre[tid * kSpRun + k + 1];
+    run[k] = tot;
+  }
+  long long incl = tot;                                           // inclusive scan of the run totals over the wave
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const long long up = __shfl_up(incl, d, 64);
+    if ((tid & 63) >= d) incl += up;
+  }
+  if ((tid & 63) == 63) wave_tot[tid >> 6] = incl;
+  __syncthreads();                                                // (also: every run has been read)
+  long long base = incl - tot;
+  for (int wv = 0; wv < (tid >> 6); ++wv) base += wave_tot[wv];
+#pragma unroll
+  for (int k = 0; k < kSpRun; ++k) pre[tid * kSpRun + k + 1] = base + run[k];
+  __syncthreads();
+  for (int k = 0; k < p.nwidth; ++k) {
+    const int w = p.width[k];
+    if (w > nout) break;                                          // the widths ascend
+    const long long thr = p.thr[k];
+    const int h = w / 2, last = nout - w;
+    for (int j = tid; j < kSpTile; j += kSpThreads) {
+      const int t = t0 + j;
+      if (t > last) break;
+      const int li = t - a;
+      const long long s = pre[li + w] - pre[li];
+      if (s < thr) continue;
+      const int lo = t - h > 0 ? t - h : 0, hi = t + h < last ? t + h : last;
+      bool peak = true;
+      for (int u = lo; u < t && peak; ++u) peak = s > pre[u - a + w] - pre[u - a];
+      for (int u = t + 1; u <= hi && peak; ++u) peak = s >= pre[u - a + w] - pre[u - a];
+      if (peak) sp_append(p, dm, w, (uint64_t)t, s);
+    }
+  }
+}
 }  // namespace fast

@@ -144,6 +144,135 @@ def prepdata_gpu(filterbankfile, dm1, zerodm=True, clip=5, dm2=0, dmstep=1.0, nc
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# single-pulse search
+# ------------------------------------------------------------------------------------------------------------------
+SP_WIDTHS = [1, 2, 3, 4, 6, 9, 14, 20, 30, 45, 70, 100, 150, 220, 300]
+SP_CAND = np.dtype([("dm_index", "<u4"), ("width", "<u4"), ("sample", "<u8"), ("sigma", "<f4"), ("reserved", "<u4")])
+SP_HEADER = "# DM      Sigma      Time (s)     Sample    Downfact"
+SP_ROW = "%7.2f %7.2f %13.6f %10d   %3d"
+
+
+def default_widths(tsamp: float, max_width_s: float = 0.0) -> list:
+    """Boxcar widths in samples: the downsampling factors of PRESTO's single_pulse_search.py, 1 2 3 4 6 9 14 20 30 45 70
+    100 150 220 300, AS REMEMBERED [EXT-UNVERIFIED: PRESTO is not at hand to check the list against].  Without a maximum
+    width the list is cut at 30 (PRESTO's default); with one it keeps the widths with w * tsamp <= max_width_s."""
+    if max_width_s > 0.0:
+        return [w for w in SP_WIDTHS if w * tsamp <= max_width_s] or [1]
+    return [w for w in SP_WIDTHS if w <= 30]
+
+
+def sp_params(widths, threshold: float = 5.0, detrend_len: int = 1000) -> _lib.FrbchSpParams:
+    widths = [int(w) for w in widths]
+    if not 1 <= len(widths) <= 16:
+        raise InputError("the search takes 1..16 boxcar widths")
+    if min(widths) < 0 or max(widths) >= 1 << 32 or not 0 <= int(detrend_len) < 1 << 32:
+        raise InputError("widths and detrend_len must be non-negative 32-bit integers")
+    p = _lib.FrbchSpParams()
+    p.size = C.sizeof(_lib.FrbchSpParams)
+    p.nwidth = len(widths)
+    for k, w in enumerate(widths):
+        p.widths[k] = w
+    p.detrend_len = int(detrend_len)
+    p.threshold = float(threshold)
+    return p
+
+
+def _sp_call(call, cap: int):
+    """run call(cands pointer, cap, ncand, used, err) with room for `cap` candidates; once more with the reported total"""
+    while True:
+        cands = np.zeros(cap, dtype=SP_CAND)
+        ncand, used = C.c_uint64(0), C.c_uint32(0)
+        err = C.create_string_buffer(512)
+        rc = call(cands.ctypes.data, cap, C.byref(ncand), C.byref(used), err, len(err))
+        if rc == _lib.E_CAPACITY and ncand.value > cap:
+            cap = ncand.value
+            continue
+        _check(rc, err)
+        return cands[: ncand.value].copy(), used.value
+
+
+def single_pulse_search(series, widths=None, threshold: float = 5.0, detrend_len: int = 1000, tsamp: float = 0.0,
+                        max_width_s: float = 0.0, device: int = 0, lib=None, info: dict | None = None, cap: int = 4096):
+    """Boxcar search of dedispersed series ([ndm][nout] or [nout] float32) on the GPU (frbch_spsearch_host; the arithmetic
+    is stated in include/frbch.h) -> structured array (dm_index, width, sample = centre of the boxcar, sigma, reserved),
+    sorted by (dm_index, sample, width).  ``widths`` defaults to ``default_widths(tsamp, max_width_s)``;
+    ``info['kernel_used']`` receives 1 when the LDS kernel ran, 0 for the generic one."""
+    lib = lib or _lib.load()
+    y = np.ascontiguousarray(series, dtype=np.float32)
+    y = y.reshape(1, -1) if y.ndim == 1 else y
+    if y.ndim != 2 or y.size == 0:
+        raise InputError("series must be [ndm][nout] with at least one sample")
+    params = sp_params(widths if widths is not None else default_widths(tsamp, max_width_s), threshold, detrend_len)
+    out, used = _sp_call(lambda c, n, nc, u, e, ne: lib.frbch_spsearch_host(y.ctypes.data, y.shape[0], y.shape[1], C.byref(params),
+                                                                            device, c, n, nc, u, e, ne), cap)
+    if info is not None:
+        info["kernel_used"] = used
+    return out
+
+
+def write_singlepulse(path: str, cands, dm: float, tsamp: float) -> None:
+    """PRESTO's .singlepulse text: DM, sigma, time of the boxcar's centre, its sample, the boxcar width (`Downfact`)"""
+    with open(path, "w") as f:
+        f.write(SP_HEADER + "\n")
+        for c in cands:
+            f.write(SP_ROW % (dm, c["sigma"], int(c["sample"]) * tsamp, int(c["sample"]), int(c["width"])) + "\n")
+
+
+def read_singlepulse(path: str, dm_index: int = 0) -> np.ndarray:
+    """a .singlepulse file back as candidate records (sigma as printed: two decimals)"""
+    rows = []
+    with open(path) as f:
+        for line in f:
+            if line.startswith("#") or not line.strip():
+                continue
+            _dm, sigma, _time, sample, width = line.split()
+            rows.append((dm_index, int(width), int(sample), float(sigma), 0))
+    return np.array(rows, dtype=SP_CAND) if rows else np.zeros(0, dtype=SP_CAND)
+
+
+def _series_names(filterbankfile, dm1, dm2, dms):
+    if dm2 > 0.0:
+        base = filterbankfile.replace(".fil", "")
+        return ["%s_DM%.2f" % (base, dm) for dm in dms]           # prepsubband's naming
+    return [filterbankfile.replace(".fil", "_dm{0}".format(dm1))]    # process_vdif.py:216
+
+
+def search_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, zerodm=True, clip=5, threshold=5.0, max_width_s=0.0, detrend_len=1000,
+               write_dat=False, widths=None, device=0, lib=None, info: dict | None = None):
+    """Dedisperse a filterbank over the DMs of ``prepdata_gpu`` and search every series for single pulses in one library
+    call (frbch_dedisperse_search_host: the DM x time plane never leaves the GPU unless ``write_dat`` asks for the .dat /
+    .inf files, which are then ``prepdata_gpu``'s).  Writes one ``<name>.singlepulse`` per DM, names as ``prepdata_gpu``.
+    Returns (list of .singlepulse files, candidates of all DMs as a structured array)."""
+    lib = lib or _lib.load()
+    fil = sigproc.read_fil(filterbankfile)
+    hdr = fil.header
+    dms = dm_list(dm1, dm2, dmstep)
+    rows = _rows_of(fil)
+    desc = fil_desc(hdr)
+    dm_arr = np.ascontiguousarray(dms, dtype=np.float64)
+    nout = lib.frbch_dedisperse_nout(C.byref(desc), rows.shape[0], dm_arr.ctypes.data, dm_arr.size)
+    if nout <= 0:
+        raise InputError("the dispersion delay across the band exceeds the length of the filterbank")
+    params = sp_params(widths if widths is not None else default_widths(hdr["tsamp"], max_width_s), threshold, detrend_len)
+    series = np.empty((dm_arr.size, nout), dtype=np.float32) if write_dat else None
+    nclip = C.c_uint64(0)
+    cands, used = _sp_call(lambda c, n, nc, u, e, ne: lib.frbch_dedisperse_search_host(
+        C.byref(desc), rows.ctypes.data, rows.shape[0], dm_arr.ctypes.data, dm_arr.size, 1 if zerodm else 0, float(clip),
+        C.byref(params), device, series.ctypes.data if write_dat else None, nout, C.byref(nclip), c, n, nc, u, e, ne), 4096)
+    if info is not None:
+        info.update(kernel_used=used, nclipped=nclip.value, nout=nout)
+    names = _series_names(filterbankfile, dm1, dm2, dms)
+    out = []
+    for i, (name, dm) in enumerate(zip(names, dms)):
+        write_singlepulse(name + ".singlepulse", cands[cands["dm_index"] == i], dm, hdr["tsamp"])
+        out.append(name + ".singlepulse")
+        if write_dat:
+            series[i].astype("<f4").tofile(name + ".dat")
+            write_inf(name + ".inf", basename=os.path.basename(name), hdr=hdr, nsamp=nout, dm=dm, clipped=nclip.value)
+    return out, cands
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # fold
 # ------------------------------------------------------------------------------------------------------------------
 def read_par(path: str) -> dict:
@@ -514,7 +643,8 @@ def fold_fil(filterbankfile: str, parfile: str, nbin: int = 0, subint_s: float =
 
 
 def main(argv=None):
-    """``python -m frb_baseband_amd.post fold <fil> <par> [--polyco FILE] [--doppler X] [--products coherency|stokes] [...]`` / ``... prepdata <fil> --dm <dm> [...]``: the two stages
+    """``python -m frb_baseband_amd.post fold <fil> <par> [--polyco FILE] [--doppler X] [--products coherency|stokes] [...]`` / ``... prepdata <fil> --dm <dm> [...]`` /
+    ``... search <fil> --dm <dm> [--dm2 --dmstep --threshold --max-width --detrend ...]``: the stages
     as commands, for the places where base2fil.sh / process_vdif.py launch dspsr and prepdata"""
     import argparse
     ap = argparse.ArgumentParser(prog="frb_baseband_amd.post")
@@ -537,11 +667,29 @@ def main(argv=None):
     d.add_argument("--nozerodm", action="store_false", help="do not subtract the zero-DM series")
     d.add_argument("--clip", type=float, default=5.0)
     d.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
+    q = sub.add_parser("search", help="dedisperse over a DM range and search for single pulses (what single_pulse_search.py does with the .dat files)")
+    q.add_argument("fil")
+    q.add_argument("--dm", type=float, required=True)
+    q.add_argument("--dm2", type=float, default=0.0)
+    q.add_argument("--dmstep", type=float, default=1.0)
+    q.add_argument("--threshold", type=float, default=5.0, help="sigma a boxcar sum must reach")
+    q.add_argument("--max-width", type=float, default=0.0, help="widest boxcar, s (0: widths up to 30 samples)")
+    q.add_argument("--detrend", type=int, default=1000, help="samples per normalisation block")
+    q.add_argument("--nozerodm", action="store_false", help="do not subtract the zero-DM series")
+    q.add_argument("--clip", type=float, default=5.0)
+    q.add_argument("--write-dat", action="store_true", help="also write the .dat / .inf files of prepdata")
+    q.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     a = ap.parse_args(argv)
     if a.cmd == "fold":
         ar, profile = fold_fil(a.fil, a.par, nbin=a.nbin, subint_s=a.subint, fscrunch_to=a.fscrunch, device=a.device,
                                polyco=a.polyco, doppler=a.doppler, products=a.products)
         print("wrote {0}, {1}.profile.txt, {1}.png; peak bin {2} of {3}".format(ar, a.fil, int(np.argmax(profile)), profile.size))
+    elif a.cmd == "search":
+        files, cands = search_fil(a.fil, a.dm, dm2=a.dm2, dmstep=a.dmstep, zerodm=a.nozerodm, clip=a.clip, threshold=a.threshold,
+                                  max_width_s=a.max_width, detrend_len=a.detrend, write_dat=a.write_dat, device=a.device)
+        for path in files:
+            print("wrote", path)
+        print("{0} candidates above {1} sigma".format(cands.size, a.threshold))
     else:
         for path in prepdata_gpu(a.fil, a.dm, zerodm=a.nozerodm, clip=a.clip, dm2=a.dm2, dmstep=a.dmstep, device=a.device):
             print("wrote", path)

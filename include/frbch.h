@@ -340,6 +340,64 @@ int frbch_foldp_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t n
                        int device, double* d_profile, uint32_t* d_hits, uint32_t nsub, uint32_t* kernel_used, char* err,
                        size_t err_cap);
 
+/* ---- single-pulse search of the dedispersed series -------------------------------------------------
+ * process_vdif.py:84-98,202-229 offers a DM range (`--dm --dm2 --dmstep`) so that the .dat files can be searched for
+ * single pulses, usually with PRESTO's single_pulse_search.py by hand.  frbch_spsearch_* do that search on the GPU, on
+ * series[dm][t] (float32, t < nout) still in HBM: boxcar matched filters of the listed widths over block-normalised
+ * samples.  PRESTO is not in the reference tree: the conventions are this library's (tests/spsearch_oracle.py restates
+ * them in numpy), chosen so that every result is reproducible to the bit:
+ *  1. Block statistics.  L = detrend_len (0 means 1000; 64..65536), nblk = max(1, nout / L), block b = [bL, (b+1)L), the
+ *     last block runs to nout.  Per (dm, block) two rounds of mean and sigma in double, every operation rounded on its
+ *     own (no fused multiply-add): s1 = sum x, s2 = sum x*x and the count n as 64 partial sums -- partial j adds the
+ *     samples at block positions j, j + 64, ... in ascending order -- added in ascending j; mean = s1 / n,
+ *     var = s2 / n - mean * mean, sigma = var > 0 ? sqrt(var) : 0.  Round 2 uses only the samples with
+ *     |x - mean1| <= 3.0 * sigma1, each in its own partial.  A block with sigma1 = 0, no kept sample or sigma2 = 0 is
+ *     dead (a NaN or infinite sample makes `var > 0` false: dead as well).
+ *  2. z = (x - mean2) * (1 / sigma2) in double, clipped to +-65536;  q = (int64)floor(z * 1024 + 0.5);  q = 0 in dead
+ *     blocks.  Everything below is integer arithmetic, exact in any order.
+ *  3. S_w[t] = sum_{i<w} q[t + i] for 0 <= t <= nout - w (a width above nout is skipped) is held against
+ *     T_w = ceil((threshold * 1024) * sqrt(w)), computed by the host:  S_w[t] >= T_w.
+ *  4. Peaks per width, h = w / 2 (integer): t is a raw peak iff it passes the threshold, S_w[t] > S_w[t'] for
+ *     t - h <= t' < t and S_w[t] >= S_w[t'] for t < t' <= t + h (windows cut to 0 .. nout - w).  Its centre is
+ *     c = t + w / 2, its sigma = (double)S / (1024.0 * sqrt((double)w)).
+ *  5. Across widths, on the host, over the raw list of one DM, in ONE pass (a dropped peak still drops others): a raw peak
+ *     (c, w, sigma) is dropped iff another raw peak (c', w', sigma') of that DM has |c - c'| <= max(w, w') / 2 and
+ *     sigma' > sigma, or sigma' == sigma and (w' < w, or w' == w and c' < c).
+ *  6. The survivors, sorted by (dm_index, sample, width), are the candidates.
+ * The device list of raw peaks holds 2^20 entries per call; a search that finds more returns FRBCH_E_CAPACITY with a
+ * "threshold too low" message -- never a cut list. */
+typedef struct frbch_sp_params {
+  uint32_t size, nwidth;               /* = sizeof(frbch_sp_params); 1..16 widths                                        */
+  uint32_t widths[16];                 /* boxcar widths in samples, strictly ascending, each 1..1024                     */
+  uint32_t detrend_len, reserved;      /* L of step 1: 0 = 1000, else 64..65536                                          */
+  double threshold;                    /* sigma, > 0 (at most 1e6)                                                       */
+} frbch_sp_params;
+
+typedef struct frbch_sp_cand {
+  uint32_t dm_index, width;            /* row of the series, boxcar width in samples                                     */
+  uint64_t sample;                     /* centre c = t + w / 2                                                           */
+  float sigma;                         /* float32 of the double of step 4                                                */
+  uint32_t reserved;
+} frbch_sp_cand;
+
+/* cands[cap] (host memory) receives the first `cap` candidates in output order, *ncand their total number; more than
+ * `cap`: FRBCH_E_CAPACITY (cap = 0 with cands = NULL counts them).  *kernel_used (may be NULL): 0 = the generic kernels
+ * (a quantise pass, then a thread per (dm, t) with direct sums), 1 = the LDS kernel (a workgroup per DM and tile of 2048
+ * samples: one load, one prefix sum, two LDS reads per S_w[t]), taken when the largest listed width is at most 512 and
+ * nout < 2^31.  Both give the same records.  FRBCH_E_ARG: widths not ascending or outside 1..1024, nwidth outside 1..16,
+ * threshold or detrend_len outside their ranges, a wrong `size`, ndm above 65535. */
+int frbch_spsearch_device(const float* d_series, uint32_t ndm, uint64_t nout, const frbch_sp_params* params, int device,
+                          frbch_sp_cand* cands, uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, char* err,
+                          size_t err_cap);
+int frbch_spsearch_host(const float* series, uint32_t ndm, uint64_t nout, const frbch_sp_params* params, int device,
+                        frbch_sp_cand* cands, uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, char* err, size_t err_cap);
+/* The production call: one upload of the rows, frbch_dedisperse_device, then frbch_spsearch_device on the plane where it
+ * lies in HBM.  The series is downloaded only when series_out != NULL ([ndm][nout], the bits of frbch_dedisperse_host). */
+int frbch_dedisperse_search_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const double* dms, uint32_t ndm,
+                                 uint32_t zerodm, double clip_sigma, const frbch_sp_params* params, int device,
+                                 float* series_out, uint64_t nout, uint64_t* nclipped, frbch_sp_cand* cands, uint64_t cap,
+                                 uint64_t* ncand, uint32_t* kernel_used, char* err, size_t err_cap);
+
 /* ---- in front of the filterbank: the corner turn -------------------------------
  * jive5ab's spif2file splits the recorder's stream -- every W-bit word holds one time sample of ALL channels -- into one
  * 2-channel stream per IF, driven by the recipe strings of spif2file.sh:31-113, e.g. the 16-channel 2-bit mode
