@@ -81,6 +81,20 @@ class FrbchSpCand(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class FrbchSpGroup(C.Structure):
+    _fields_ = [("best", FrbchSpCand), ("nmember", C.c_uint32), ("dm_index_lo", C.c_uint32), ("dm_index_hi", C.c_uint32),
+                ("reserved", C.c_uint32), ("sample_lo", C.c_uint64), ("sample_hi", C.c_uint64)]
+
+
+class FrbchCutoutParams(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("nt", C.c_uint32), ("nf", C.c_uint32), ("ndm", C.c_uint32)]
+
+
+class FrbchCutoutCand(C.Structure):
+    _fields_ = [("dm", C.c_double), ("dm_lo", C.c_double), ("dm_hi", C.c_double), ("sample", C.c_int64),
+                ("tfactor", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class _KTiming(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double),
                 ("algorithmic_bytes", C.c_double)]
@@ -143,6 +157,13 @@ SYMBOLS = {
     "frbch_dedisperse_search_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_double,
                                                C.POINTER(FrbchSpParams), C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64), _P,
                                                C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_sp_group_cands": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint32, _P, C.c_uint64, C.c_uint32, _P, C.c_uint64,
+                                       C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
+    "frbch_cutout_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchCutoutParams), _P, C.c_uint32, C.c_int,
+                                      _P, _P, _P, _P, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_cutout_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchCutoutParams), _P, C.c_uint32, C.c_int,
+                                    _P, _P, _P, _P, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_cutout_kernel": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchCutoutParams), _P, C.c_uint32]),
     "frbch_cornerturn_info": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
     "frbch_cornerturn_host": (C.c_int, [C.c_char_p, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(_P), C.c_uint32,

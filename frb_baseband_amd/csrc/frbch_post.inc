@@ -770,6 +770,362 @@ extern "C" int frbch_dedisperse_search_host(const frbch_fil_desc* fil, const voi
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// candidates: grouping across DMs (host only) and the two cut-out planes
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+bool sp_better(const frbch_sp_cand& a, const frbch_sp_cand& b) {        // a represents a group rather than b
+  if (a.sigma != b.sigma) return a.sigma > b.sigma;
+  if (a.width != b.width) return a.width < b.width;
+  if (a.dm_index != b.dm_index) return a.dm_index < b.dm_index;
+  return a.sample < b.sample;
+}
+}  // namespace
+
+extern "C" int frbch_sp_group_cands(const frbch_fil_desc* fil, const double* dms, uint32_t ndm, const frbch_sp_cand* cands,
+                                    uint64_t ncand, uint32_t dm_gap, frbch_sp_group* groups, uint64_t cap, uint64_t* ngroup,
+                                    char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  int rc = post_check_fil(fil, 1, e);
+  if (rc) return rc;
+  if (!dms || !ndm || !ngroup || (ncand && !cands) || (cap && !groups)) return e.fail(FRBCH_E_ARG, "null argument");
+  if (dm_gap < 1 || dm_gap > 16) return e.fail(FRBCH_E_ARG, "dm_gap must be 1..16");
+  for (uint32_t i = 0; i < ndm; ++i)
+    if (!(dms[i] >= 0.0) || !(dms[i] < 1.0e5)) return e.fail(FRBCH_E_ARG, "a DM outside [0, 1e5)");
+  for (uint64_t i = 0; i < ncand; ++i)
+    if (cands[i].dm_index >= ndm) return e.fail(FRBCH_E_ARG, "record " + std::to_string(i) + ": dm_index >= ndm");
+  *ngroup = 0;
+  if (!ncand) return FRBCH_OK;
+  // D_i: the largest delay of DM i, and the largest |D_a - D_b| two linked records can have
+  int64_t maxd = 0;
+  const std::vector<int32_t> delays = post_delays(fil, dms, ndm, &maxd);
+  std::vector<int64_t> D(ndm, 0);
+  for (uint32_t i = 0; i < ndm; ++i)
+    for (uint32_t c = 0; c < fil->nchan; ++c) D[i] = std::max<int64_t>(D[i], delays[(size_t)i * fil->nchan + c]);
+  int64_t smear = 0;
+  for (uint32_t i = 0; i < ndm; ++i)
+    for (uint32_t j = i + 1; j < ndm && j - i <= dm_gap; ++j) smear = std::max<int64_t>(smear, std::llabs(D[i] - D[j]));
+  uint32_t wmax = 0;
+  for (uint64_t i = 0; i < ncand; ++i) wmax = std::max(wmax, cands[i].width);
+  const uint64_t reach = (uint64_t)(wmax / 2) + (uint64_t)smear;       // no two linked records lie further apart
+  // sweep in sample order: record i meets the later ones within `reach`; union-find joins the linked pairs
+  std::vector<uint64_t> order(ncand), parent(ncand);
+  for (uint64_t i = 0; i < ncand; ++i) order[i] = parent[i] = i;
+  std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {
+    return cands[a].sample != cands[b].sample ? cands[a].sample < cands[b].sample : a < b;
+  });
+  auto find = [&](uint64_t x) {
+    while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; }
+    return x;
+  };
+  for (uint64_t i = 0; i < ncand; ++i) {
+    const frbch_sp_cand& a = cands[order[i]];
+    for (uint64_t j = i + 1; j < ncand && cands[order[j]].sample - a.sample <= reach; ++j) {
+      const frbch_sp_cand& b = cands[order[j]];
+      const uint32_t ddm = a.dm_index > b.dm_index ? a.dm_index - b.dm_index : b.dm_index - a.dm_index;
+      if (ddm > dm_gap) continue;
+      const uint64_t tol = (uint64_t)(std::max(a.width, b.width) / 2) + (uint64_t)std::llabs(D[a.dm_index] - D[b.dm_index]);
+      if (b.sample - a.sample > tol) continue;
+      const uint64_t ra = find(order[i]), rb = find(order[j]);
+      if (ra != rb) parent[std::max(ra, rb)] = std::min(ra, rb);
+    }
+  }
+  std::vector<int64_t> slot(ncand, -1);                                  // root -> index in `out`
+  std::vector<frbch_sp_group> out;
+  for (uint64_t i = 0; i < ncand; ++i) {
+    const uint64_t r = find(i);
+    const frbch_sp_cand& c = cands[i];
+    if (slot[r] < 0) {
+      slot[r] = (int64_t)out.size();
+      frbch_sp_group g;
+      memset(&g, 0, sizeof g);
+      g.best = c;
+      g.best.reserved = 0;
+      g.nmember = 1;
+      g.dm_index_lo = g.dm_index_hi = c.dm_index;
+      g.sample_lo = g.sample_hi = c.sample;
+      out.push_back(g);
+      continue;
+    }
+    frbch_sp_group& g = out[(size_t)slot[r]];
+    if (sp_better(c, g.best)) { g.best = c; g.best.reserved = 0; }
+    ++g.nmember;
+    g.dm_index_lo = std::min(g.dm_index_lo, c.dm_index);
+    g.dm_index_hi = std::max(g.dm_index_hi, c.dm_index);
+    g.sample_lo = std::min(g.sample_lo, c.sample);
+    g.sample_hi = std::max(g.sample_hi, c.sample);
+  }
+  std::sort(out.begin(), out.end(), [](const frbch_sp_group& a, const frbch_sp_group& b) {
+    if (a.best.dm_index != b.best.dm_index) return a.best.dm_index < b.best.dm_index;
+    if (a.best.sample != b.best.sample) return a.best.sample < b.best.sample;
+    if (a.best.width != b.best.width) return a.best.width < b.best.width;
+    return a.sample_lo < b.sample_lo;                                    // (two groups with the same best key: duplicate records apart)
+  });
+  *ngroup = out.size();
+  for (uint64_t i = 0; i < std::min<uint64_t>(cap, out.size()); ++i) groups[i] = out[i];
+  if (out.size() > cap) return e.fail(FRBCH_E_CAPACITY, std::to_string(out.size()) + " groups, room for " + std::to_string(cap));
+  return FRBCH_OK;
+}
+
+namespace {
+constexpr uint64_t kCutTableCap = 1ull << 26;    // delay-table entries of one call (256 MiB); a longer batch is refused
+
+int cut_check(const frbch_fil_desc* fil, uint64_t nrows, const frbch_cutout_params* par, const frbch_cutout_cand* cands,
+              uint32_t ncand, const PostErr& e) {
+  int rc = post_check_fil(fil, nrows, e);
+  if (rc) return rc;
+  if (!par || par->size != sizeof(frbch_cutout_params)) return e.fail(FRBCH_E_ARG, "frbch_cutout_params: wrong size");
+  if (par->nt < 2 || par->nt > 1024 || (par->nt & 1)) return e.fail(FRBCH_E_ARG, "nt must be even, 2..1024");
+  if (par->nf < 1 || fil->nchan % par->nf != 0) return e.fail(FRBCH_E_ARG, "nf must divide nchan");
+  if (par->ndm < 1 || par->ndm > 1024) return e.fail(FRBCH_E_ARG, "ndm must be 1..1024");
+  if (!cands || ncand < 1 || ncand > 65535) return e.fail(FRBCH_E_ARG, "1..65535 candidates");
+  if ((uint64_t)ncand * par->nf * par->nt >= (1ull << 31) || (uint64_t)ncand * par->ndm * par->nt >= (1ull << 31))
+    return e.fail(FRBCH_E_ARG, "a plane set of 2^31 elements or more");
+  if ((uint64_t)ncand * par->ndm * fil->nchan > kCutTableCap)
+    return e.fail(FRBCH_E_ARG, "ncand * ndm * nchan exceeds 2^26 delays: cut the batch into several calls");
+  if (nrows >= (1ull << 62)) return e.fail(FRBCH_E_ARG, "too many rows");
+  for (uint32_t i = 0; i < ncand; ++i) {
+    const frbch_cutout_cand& c = cands[i];
+    const std::string who = "candidate " + std::to_string(i) + ": ";
+    if (c.tfactor < 1 || c.tfactor > 512) return e.fail(FRBCH_E_ARG, who + "tfactor must be 1..512");
+    if (!(c.dm >= 0.0) || !(c.dm < 1.0e5) || !(c.dm_lo >= 0.0) || !(c.dm_lo < 1.0e5) || !(c.dm_hi >= 0.0) || !(c.dm_hi < 1.0e5))
+      return e.fail(FRBCH_E_ARG, who + "a DM outside [0, 1e5)");
+    if (c.dm_hi < c.dm_lo) return e.fail(FRBCH_E_ARG, who + "dm_hi < dm_lo");
+    if (c.sample < -(1ll << 62) || c.sample > (1ll << 62)) return e.fail(FRBCH_E_ARG, who + "sample out of range");
+  }
+  return FRBCH_OK;
+}
+
+// what the kernels of a call read
+struct CutPlan {
+  std::vector<CutCand> cand;
+  std::vector<int32_t> ft_delays, dt_delays;     // [count][nchan], [count][ndm][nchan]
+  bool lds = false;                              // every tile of both planes fits the LDS kernel
+  std::vector<int32_t> ft_range, dt_range;       // [count][row group][channel tile] (smallest delay, span; span < 0: not the group's)
+  int ft_ngrp = 0, dt_ngrp = 0, nct = 0;
+  int ft_rows = 0, dt_rows = 0;                  // rows of the largest tile
+  unsigned ft_tiles = 1, dt_tiles = 1;           // time tiles of the candidate that needs most
+};
+
+// Which cut-out kernel a call takes -- the one decision behind frbch_cutout_device's launches, *kernel_used and
+// frbch_cutout_kernel's answer.  true = the LDS kernel (kernels_post_fast.inc): 8- / 16-bit rows, whole 64-byte channel
+// tiles, 16-byte pieces of every row (only the ADDRESS of d_rows is examined).  cut_build then still has to find room in
+// the LDS for every (row group, channel tile, time tile).  The emulator build has no such kernel: false.
+bool cut_lds_layout(const frbch_fil_desc* fil, const void* d_rows) {
+#ifndef FRBCH_NO_FAST
+  if (fil->nbits != 8 && fil->nbits != 16) return false;
+  const int bpv = fil->nbits / 8, ct = 64 / bpv;
+  return fil->nchan % ct == 0 && (int)fil->nchan <= fast::kCutMaxChan && ((uintptr_t)d_rows % 16) == 0 &&
+         ((size_t)fil->nifs * fil->nchan * bpv) % 16 == 0;
+#else
+  (void)fil; (void)d_rows;
+  return false;
+#endif
+}
+
+// min / span of delays[r][c] over r in [0, nr) (rows `pitch` apart), c in [c0, c1) -> range[0..1]; false: does not fit
+bool cut_tile_range(const int32_t* delays, int nr, size_t pitch, int c0, int c1, int32_t* range, int* rows_max) {
+#ifndef FRBCH_NO_FAST
+  int32_t lo = INT32_MAX, hi = INT32_MIN;
+  for (int r = 0; r < nr; ++r)
+    for (int c = c0; c < c1; ++c) {
+      const int32_t v = delays[(size_t)r * pitch + c];
+      lo = std::min(lo, v);
+      hi = std::max(hi, v);
+    }
+  range[0] = lo;
+  range[1] = hi - lo;
+  if ((int64_t)hi - lo + fast::kCutTT > fast::kCutRowsCap) return false;
+  *rows_max = std::max(*rows_max, fast::kCutTT + (hi - lo));
+  return true;
+#else
+  (void)delays; (void)nr; (void)pitch; (void)c0; (void)c1; (void)range; (void)rows_max;
+  return false;
+#endif
+}
+
+int cut_build(const frbch_fil_desc* fil, const frbch_cutout_params* par, const frbch_cutout_cand* cands, uint32_t count,
+              bool layout_ok, CutPlan* plan, const PostErr& e) {
+  POST_NO_CONTRACT
+  const uint32_t nchan = fil->nchan, ndm = par->ndm;
+  // the DMs of both planes, then their delays from post_delays: n_c(.) is what frbch_dedisperse_* computes because it is
+  // computed by the same function
+  std::vector<double> ft_dms(count), dt_dms((size_t)count * ndm);
+  plan->cand.resize(count);
+  for (uint32_t i = 0; i < count; ++i) {
+    const frbch_cutout_cand& c = cands[i];
+    plan->cand[i].t0 = c.sample - (long long)(par->nt / 2) * (long long)c.tfactor;
+    plan->cand[i].tfactor = (int)c.tfactor;
+    plan->cand[i].pad = 0;
+    ft_dms[i] = c.dm;
+    const double step = ndm > 1 ? (c.dm_hi - c.dm_lo) / (double)(ndm - 1) : 0.0;
+    for (uint32_t k = 0; k < ndm; ++k) {
+      const double off = (double)k * step;
+      dt_dms[(size_t)i * ndm + k] = ndm > 1 ? c.dm_lo + off : c.dm_lo;
+    }
+  }
+  int64_t ft_max = 0, dt_max = 0;
+  plan->ft_delays = post_delays(fil, ft_dms.data(), count, &ft_max);
+  plan->dt_delays = post_delays(fil, dt_dms.data(), count * ndm, &dt_max);
+  if (std::max(ft_max, dt_max) > (int64_t)1 << 30) return e.fail(FRBCH_E_ARG, "a dispersion delay of more than 2^30 samples");
+  plan->lds = false;
+#ifndef FRBCH_NO_FAST
+  if (layout_ok) {
+    const int ct = 64 / (fil->nbits / 8), nct = (int)nchan / ct, cpb = (int)(nchan / par->nf);
+    const int NR = fast::kCutNR;
+    plan->nct = nct;
+    plan->ft_ngrp = ((int)par->nf + NR - 1) / NR;
+    plan->dt_ngrp = ((int)ndm + NR - 1) / NR;
+    plan->ft_range.assign((size_t)count * plan->ft_ngrp * nct * 2, -1);
+    plan->dt_range.assign((size_t)count * plan->dt_ngrp * nct * 2, -1);
+    plan->ft_rows = plan->dt_rows = fast::kCutTT;
+    plan->ft_tiles = plan->dt_tiles = 1;
+    bool fits = true;
+    for (uint32_t i = 0; i < count && fits; ++i) {
+      const int f = plan->cand[i].tfactor, bpt = f >= fast::kCutTT ? 1 : fast::kCutTT / f;
+      const unsigned tiles = (unsigned)((par->nt + bpt - 1) / bpt);
+      plan->ft_tiles = std::max(plan->ft_tiles, tiles);
+      plan->dt_tiles = std::max(plan->dt_tiles, tiles);
+      for (int g = 0; g < plan->dt_ngrp && fits; ++g) {
+        const int nd = std::min(NR, (int)ndm - g * NR);
+        for (int k = 0; k < nct && fits; ++k)
+          fits = cut_tile_range(&plan->dt_delays[((size_t)i * ndm + (size_t)g * NR) * nchan], nd, nchan, k * ct, (k + 1) * ct,
+                                &plan->dt_range[(((size_t)i * plan->dt_ngrp + g) * nct + k) * 2], &plan->dt_rows);
+      }
+      for (int g = 0; g < plan->ft_ngrp && fits; ++g) {
+        const int c_lo = g * NR * cpb, c_hi = std::min((int)nchan, (g + 1) * NR * cpb);
+        for (int k = c_lo / ct; k <= (c_hi - 1) / ct && fits; ++k)
+          fits = cut_tile_range(&plan->ft_delays[(size_t)i * nchan], 1, nchan, std::max(c_lo, k * ct), std::min(c_hi, (k + 1) * ct),
+                                &plan->ft_range[(((size_t)i * plan->ft_ngrp + g) * nct + k) * 2], &plan->ft_rows);
+      }
+    }
+    plan->lds = fits;
+  }
+#else
+  (void)layout_ok;
+#endif
+  return FRBCH_OK;
+}
+
+}  // namespace
+
+extern "C" int frbch_cutout_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_cutout_params* par,
+                                   const frbch_cutout_cand* cands, uint32_t ncand) {
+  PostErr e{nullptr, 0};
+  int rc = cut_check(fil, nrows, par, cands, ncand, e);
+  if (rc) return rc;
+  if (!d_rows) return FRBCH_E_ARG;
+  CutPlan plan;
+  rc = cut_build(fil, par, cands, ncand, cut_lds_layout(fil, d_rows), &plan, e);
+  return rc ? rc : (plan.lds ? 1 : 0);
+}
+
+extern "C" int frbch_cutout_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_cutout_params* par,
+                                   const frbch_cutout_cand* cands, uint32_t ncand, int device, float* d_ft, uint32_t* d_ft_hits,
+                                   float* d_dt, uint32_t* d_dt_hits, uint32_t* kernel_used, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  int rc = cut_check(fil, nrows, par, cands, ncand, e);
+  if (rc) return rc;
+  if (!d_rows || !d_ft || !d_ft_hits || !d_dt || !d_dt_hits) return e.fail(FRBCH_E_ARG, "null argument");
+  if (device < 0 || device >= dev_count()) return e.fail(FRBCH_E_DEVICE, "no such GPU (there is no CPU fallback)");
+  CutPlan plan;
+  rc = cut_build(fil, par, cands, ncand, cut_lds_layout(fil, d_rows), &plan, e);
+  if (rc) return rc;
+  const bool lds = plan.lds;
+  DeviceGuard dg(device);
+  dev_stream_t s = 0;
+  if (dev_stream_create(&s) != 0) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  CutCand* d_cand = nullptr;
+  int32_t *d_ftd = nullptr, *d_dtd = nullptr, *d_ftr = nullptr, *d_dtr = nullptr;
+  auto release = [&]() {
+    dev_free(d_cand); dev_free(d_ftd); dev_free(d_dtd); dev_free(d_ftr); dev_free(d_dtr);
+    d_cand = nullptr; d_ftd = d_dtd = d_ftr = d_dtr = nullptr;
+  };
+  auto cleanup = [&]() { release(); dev_stream_destroy(s); };
+#define POST_DEV(expr, what) do { if ((expr) != 0) { cleanup(); return e.fail(FRBCH_E_DEVICE, std::string(what) + ": " + dev_last_error_string()); } } while (0)
+  POST_DEV(dev_malloc((void**)&d_cand, plan.cand.size() * sizeof(CutCand)), "hipMalloc");
+  POST_DEV(dev_malloc((void**)&d_ftd, plan.ft_delays.size() * sizeof(int32_t)), "hipMalloc");
+  POST_DEV(dev_malloc((void**)&d_dtd, plan.dt_delays.size() * sizeof(int32_t)), "hipMalloc");
+  POST_DEV(dev_h2d(d_cand, plan.cand.data(), plan.cand.size() * sizeof(CutCand), s), "upload candidates");
+  POST_DEV(dev_h2d(d_ftd, plan.ft_delays.data(), plan.ft_delays.size() * sizeof(int32_t), s), "upload delays");
+  POST_DEV(dev_h2d(d_dtd, plan.dt_delays.data(), plan.dt_delays.size() * sizeof(int32_t), s), "upload delays");
+  CutParams p;
+  memset(&p, 0, sizeof p);
+  p.rows = (const uint8_t*)d_rows;
+  p.nrows = nrows;
+  p.nchan = (int)fil->nchan; p.nifs = (int)fil->nifs; p.nbits = fil->nbits; p.prod = (int)fil->product;
+  p.nt = (int)par->nt; p.nf = (int)par->nf; p.ndm = (int)par->ndm; p.cpb = (int)(fil->nchan / par->nf);
+  p.ncand = (int)ncand;
+  p.cand = d_cand;
+  p.ft_delays = d_ftd;
+  p.dt_delays = d_dtd;
+#ifndef FRBCH_NO_FAST
+  if (lds) {
+    POST_DEV(dev_malloc((void**)&d_ftr, plan.ft_range.size() * sizeof(int32_t)), "hipMalloc");
+    POST_DEV(dev_malloc((void**)&d_dtr, plan.dt_range.size() * sizeof(int32_t)), "hipMalloc");
+    POST_DEV(dev_h2d(d_ftr, plan.ft_range.data(), plan.ft_range.size() * sizeof(int32_t), s), "upload tile ranges");
+    POST_DEV(dev_h2d(d_dtr, plan.dt_range.data(), plan.dt_range.size() * sizeof(int32_t), s), "upload tile ranges");
+    p.nct = plan.nct;
+    const int bpv = fil->nbits / 8;
+    for (int kind = 0; kind < 2; ++kind) {
+      p.kind = kind;
+      p.out = kind ? d_dt : d_ft;
+      p.hits = kind ? d_dt_hits : d_ft_hits;
+      p.tile_range = kind ? d_dtr : d_ftr;
+      p.ngrp = kind ? plan.dt_ngrp : plan.ft_ngrp;
+      const size_t bytes = std::max((size_t)(kind ? plan.dt_rows : plan.ft_rows) * fast::kCutRowB, fast::kCutRedBytes) + 16;
+      const dim3 grid(kind ? plan.dt_tiles : plan.ft_tiles, (unsigned)p.ngrp, ncand);
+#define CUT_LDS(B, K) do { POST_DEV(dev_allow_lds(fast::frbch_post_cutout_lds<B, K>, bytes), "LDS size"); \
+        hipLaunchKernelGGL((fast::frbch_post_cutout_lds<B, K>), grid, dim3(fast::kCutTT), bytes, s, p); } while (0)
+      if (bpv == 1) { if (kind) CUT_LDS(1, 1); else CUT_LDS(1, 0); }
+      else { if (kind) CUT_LDS(2, 1); else CUT_LDS(2, 0); }
+#undef CUT_LDS
+      POST_DEV(dev_check_launch(), "launch cut-out");
+    }
+  }
+#endif
+  if (!lds)
+    for (int kind = 0; kind < 2; ++kind) {
+      p.kind = kind;
+      p.out = kind ? d_dt : d_ft;
+      p.hits = kind ? d_dt_hits : d_ft_hits;
+      const uint64_t npix = (uint64_t)(kind ? par->ndm : par->nf) * par->nt;
+      DEV_LAUNCH(frbch_post_cutout, (npix + 255) / 256, ncand, 256, 0, s, p);
+      POST_DEV(dev_check_launch(), "launch cut-out");
+    }
+  POST_DEV(dev_sync(s), "sync");      // (the host vectors the uploads read stay alive until here)
+#undef POST_DEV
+  if (kernel_used) *kernel_used = lds ? 1 : 0;
+  cleanup();
+  return FRBCH_OK;
+}
+
+extern "C" int frbch_cutout_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_cutout_params* par,
+                                 const frbch_cutout_cand* cands, uint32_t ncand, int device, float* ft, uint32_t* ft_hits,
+                                 float* dt, uint32_t* dt_hits, uint32_t* kernel_used, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  int rc = cut_check(fil, nrows, par, cands, ncand, e);
+  if (rc) return rc;
+  if (!rows || !ft || !ft_hits || !dt || !dt_hits) return e.fail(FRBCH_E_ARG, "null argument");
+  if (device < 0 || device >= dev_count()) return e.fail(FRBCH_E_DEVICE, "no such GPU (there is no CPU fallback)");
+  DeviceGuard dg(device);
+  const size_t in_bytes = (size_t)nrows * fil->nifs * fil->nchan * (size_t)(fil->nbits / 8);
+  const size_t nft = (size_t)ncand * par->nf * par->nt, ndt = (size_t)ncand * par->ndm * par->nt;
+  void* d_rows = nullptr;
+  float *d_ft = nullptr, *d_dt = nullptr;
+  uint32_t *d_fth = nullptr, *d_dth = nullptr;
+  if (dev_malloc(&d_rows, in_bytes) != 0 || dev_malloc((void**)&d_ft, nft * 4) != 0 || dev_malloc((void**)&d_fth, nft * 4) != 0 ||
+      dev_malloc((void**)&d_dt, ndt * 4) != 0 || dev_malloc((void**)&d_dth, ndt * 4) != 0)
+    rc = e.fail(FRBCH_E_NOMEM, "device memory for the rows and the planes");
+  if (!rc && (dev_h2d(d_rows, rows, in_bytes, 0) != 0 || dev_sync(0) != 0)) rc = e.fail(FRBCH_E_DEVICE, "upload rows");
+  if (!rc) rc = frbch_cutout_device(fil, d_rows, nrows, par, cands, ncand, device, d_ft, d_fth, d_dt, d_dth, kernel_used, err, err_cap);
+  if (!rc && (dev_d2h(ft, d_ft, nft * 4, 0) != 0 || dev_d2h(ft_hits, d_fth, nft * 4, 0) != 0 || dev_d2h(dt, d_dt, ndt * 4, 0) != 0 ||
+              dev_d2h(dt_hits, d_dth, ndt * 4, 0) != 0 || dev_sync(0) != 0))
+    rc = e.fail(FRBCH_E_DEVICE, "download planes");
+  dev_free(d_rows); dev_free(d_ft); dev_free(d_fth); dev_free(d_dt); dev_free(d_dth);
+  return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // corner turn
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {

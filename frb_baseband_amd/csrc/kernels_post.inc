@@ -514,3 +514,71 @@ KERNEL(frbch_post_cornerturn, CornerParams) {
     }
   }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Candidate cut-outs (frbch_cutout_*; include/frbch.h states the arithmetic): per candidate the dedispersed
+// frequency-time plane FT[nf][nt] and the DM-time plane DT[ndm][nt], time bins of `tfactor` rows, with the number of
+// present samples of every pixel.  No clip, no zero-DM filter.  A "plane row" is a frequency bin (FT: the channels
+// [b cpb, (b + 1) cpb) at the delays of the candidate's DM) or a trial DM (DT: all channels at the delays of dm_k).
+// ---------------------------------------------------------------------------------------------------------------------
+struct CutCand {
+  long long t0;                // first row of time bin 0 at the top of the band: sample - (nt / 2) * tfactor (may be negative)
+  int tfactor, pad;
+};
+
+struct CutParams {
+  const uint8_t* rows;         // [nrows][nifs][nchan] samples of `nbits`; product `prod` is used
+  uint64_t nrows;
+  int nchan, nifs, nbits, prod;
+  int nt, nf, ndm, cpb;        // cpb = nchan / nf
+  int kind;                    // 0: the frequency-time plane, 1: the DM-time plane
+  int ncand;                   // candidates of this launch
+  const CutCand* cand;         // [ncand]
+  const int32_t* ft_delays;    // [ncand][nchan]
+  const int32_t* dt_delays;    // [ncand][ndm][nchan]
+  float* out;                  // [ncand][plane rows][nt]
+  uint32_t* hits;              // same shape
+  // ---- LDS kernel (kernels_post_fast.inc) ----
+  const int32_t* tile_range;   // [ncand][row group][channel tile] (smallest delay, rows spanned beyond the time tile; span < 0: no channel of the tile belongs to the group)
+  int ngrp, nct;
+};
+
+DEVFN inline double cut_sample(const CutParams& p, long long s, int c) {
+  const uint64_t i = ((uint64_t)s * (uint64_t)p.nifs + (uint64_t)p.prod) * (uint64_t)p.nchan + (uint64_t)c;
+  if (p.nbits == 8) return (double)p.rows[i];
+  if (p.nbits == 16) return (double)((const uint16_t*)p.rows)[i];
+  return (double)((const float*)p.rows)[i];
+}
+
+// The generic form, the correctness anchor and the fallback: grid (ceil(plane rows * nt / 256), ncand), one thread per
+// pixel, channels ascending, the rows of the bin ascending inside, sums in double.
+KERNEL(frbch_post_cutout, CutParams) {
+  K_PROLOGUE;
+  (void)smem;
+  PHASE {
+    const int nrow = p.kind ? p.ndm : p.nf;
+    const long long pix = (long long)bx * nthr + tid;
+    if (pix < (long long)nrow * p.nt) {
+      const int r = (int)(pix / p.nt), j = (int)(pix - (long long)r * p.nt);
+      const CutCand cd = p.cand[by];
+      const int32_t* dly = p.kind ? p.dt_delays + ((size_t)by * p.ndm + r) * p.nchan : p.ft_delays + (size_t)by * p.nchan;
+      const int c0 = p.kind ? 0 : r * p.cpb, c1 = p.kind ? p.nchan : (r + 1) * p.cpb;
+      const long long tb = cd.t0 + (long long)j * cd.tfactor;
+      double a = 0.0;
+      uint32_t n = 0;
+      for (int c = c0; c < c1; ++c) {
+        const long long s0 = tb + (long long)dly[c];
+        for (int u = 0; u < cd.tfactor; ++u) {
+          const long long s = s0 + u;
+          if (s >= 0 && s < (long long)p.nrows) {
+            a += cut_sample(p, s, c);
+            ++n;
+          }
+        }
+      }
+      const size_t o = ((size_t)by * nrow + r) * p.nt + j;
+      p.out[o] = (float)a;
+      p.hits[o] = n;
+    }
+  }
+}

@@ -267,4 +267,127 @@ __global__ void __launch_bounds__(kSpThreads) frbch_post_sp_search_lds(SpParams 
     }
   }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Candidate cut-outs in the LDS (HIP only; frbch_post_cutout of kernels_post.inc stays the emulable form and the fallback).
+// One launch per plane kind for ALL candidates: grid (time tile, group of kCutNR plane rows, candidate).  A plane row is a
+// trial DM (KIND 1, the DM-time plane) or a frequency bin (KIND 0, the frequency-time plane).  The shape is that of
+// frbch_post_dedisp_tiled: a workgroup of 256 threads owns kCutNR plane rows and a run of whole time bins of one
+// candidate -- bpt = 256 / tfactor bins, bpt * tfactor <= 256 consecutive ROWS, one row per thread -- and walks the 64-byte
+// channel tiles in ascending order.  The rows a tile needs, [first row + dmin, ... + 256 + span) with dmin / span over the
+// tile's channels and the group's plane rows precomputed by the host, are copied to the LDS once (coalesced 16-byte
+// pieces, rows 68 bytes = 17 banks apart: the lanes of a wave read consecutive rows of one column, 64 distinct banks);
+// rows outside [0, nrows) are zero-filled.  Every thread adds its row's samples into kCutNR uint32 accumulators (at most
+// 2 rows x 16384 channels x 65535 < 2^32: exact), and keeps them across ALL channel tiles, so the DM-time plane needs no
+// global atomics.  A bin longer than 256 rows (tfactor up to 512) is one workgroup's: it walks the bin in chunks of 256
+// rows with the same accumulators.  At the end the accumulators go to the LDS once and one thread per pixel adds the
+// tfactor entries of its bin (uint64), converts and stores.  Hits need no data: interior pixels (every row of every
+// channel of the group present, decided from the same dmin / span table) hold channels x tfactor, the others add a
+// clamp per channel.  Integer sums are exact in any order: the result equals the generic kernel's to the bit.
+constexpr int kCutTT = 256, kCutRowB = 68, kCutNR = 8;
+constexpr int kCutRowsCap = 900;           // rows of a tile the LDS holds (61 KB); the launch asks only for the largest tile it has
+constexpr int kCutMaxChan = 16384;         // uint32 accumulators
+constexpr size_t kCutRedBytes = (size_t)kCutNR * kCutTT * sizeof(uint32_t);
+
+template <int BPV, int KIND>
+__global__ void __launch_bounds__(kCutTT) frbch_post_cutout_lds(CutParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int CT = 64 / BPV;
+  const int tid = threadIdx.x;
+  const int cand = blockIdx.z, g = blockIdx.y;
+  const CutCand cd = p.cand[cand];
+  const int f = cd.tfactor;
+  const int bpt = f >= kCutTT ? 1 : kCutTT / f;                            // time bins of a workgroup
+  const int j0 = (int)blockIdx.x * bpt;
+  if (j0 >= p.nt) return;                                                  // (the grid is sized for the smallest bpt; whole workgroup)
+  const int nbin = min(bpt, p.nt - j0);
+  const int rows_wg = nbin * f;                                            // <= 256 unless bpt = 1
+  const int nrow = KIND ? p.ndm : p.nf;
+  const int r0 = g * kCutNR;
+  const int nd = min(kCutNR, nrow - r0);
+  const int c_lo = KIND ? 0 : r0 * p.cpb, c_hi = KIND ? p.nchan : (r0 + nd) * p.cpb;
+  const size_t row_stride = (size_t)p.nifs * p.nchan * BPV;                // bytes between rows of the file
+  const unsigned char* src0 = p.rows + (size_t)p.prod * p.nchan * BPV;
+  const int32_t* rng = p.tile_range + ((size_t)cand * p.ngrp + g) * p.nct * 2;
+  const int32_t* dly = KIND ? p.dt_delays + ((size_t)cand * p.ndm + r0) * p.nchan : p.ft_delays + (size_t)cand * p.nchan;
+  const long long tb = cd.t0 + (long long)j0 * f;                          // first row of the workgroup at the top of the band
+  const long long nrows = (long long)p.nrows;
+  uint32_t a[kCutNR];
+#pragma unroll
+  for (int d = 0; d < kCutNR; ++d) a[d] = 0u;
+  int glo = INT32_MAX, ghi = INT32_MIN;                                    // delays of the whole group: for the hits
+  const int ct0 = c_lo / CT, ct1 = (c_hi - 1) / CT;
+  for (int chunk = 0; chunk * kCutTT < rows_wg; ++chunk) {
+    const int nr = min(kCutTT, rows_wg - chunk * kCutTT);                  // rows of this chunk, one per thread
+    for (int ctile = ct0; ctile <= ct1; ++ctile) {
+      const int32_t dmin = rng[ctile * 2], span = rng[ctile * 2 + 1];
+      if (span < 0) continue;
+      glo = min(glo, dmin);
+      ghi = max(ghi, dmin + span);
+      const int rows = nr + span;                                          // <= kCutRowsCap (the host checked)
+      const long long first = tb + (long long)chunk * kCutTT + dmin;
+      __syncthreads();                                                     // the previous tile is consumed
+      for (int i = tid; i < rows * 4; i += kCutTT) {                       // 16-byte pieces: 4 per row
+        const int r = i >> 2, part = i & 3;
+        const long long s = first + r;
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (s >= 0 && s < nrows) v = *reinterpret_cast<const uint4*>(src0 + (size_t)s * row_stride + (size_t)ctile * 64 + part * 16);
+        *reinterpret_cast<uint32_t*>(smem + r * kCutRowB + part * 16) = v.x;
+        *reinterpret_cast<uint32_t*>(smem + r * kCutRowB + part * 16 + 4) = v.y;
+        *reinterpret_cast<uint32_t*>(smem + r * kCutRowB + part * 16 + 8) = v.z;
+        *reinterpret_cast<uint32_t*>(smem + r * kCutRowB + part * 16 + 12) = v.w;
+      }
+      __syncthreads();
+      if (tid < nr) {
+        const int cb = max(c_lo, ctile * CT), ce = min(c_hi, (ctile + 1) * CT);
+        if (KIND) {
+          for (int c = cb; c < ce; ++c) {
+#pragma unroll
+            for (int d = 0; d < kCutNR; ++d)
+              if (d < nd) {
+                const unsigned char* q = smem + ((tid + (dly[(size_t)d * p.nchan + c] - dmin)) * kCutRowB + (c * BPV - ctile * 64));
+                a[d] += BPV == 1 ? (uint32_t)*q : (uint32_t)*reinterpret_cast<const uint16_t*>(q);
+              }
+          }
+        } else {
+          int dd = cb / p.cpb - r0, rem = cb % p.cpb;                      // plane row of channel c, and c's place in its bin
+          for (int c = cb; c < ce; ++c) {
+            const unsigned char* q = smem + ((tid + (dly[c] - dmin)) * kCutRowB + (c * BPV - ctile * 64));
+            const uint32_t v = BPV == 1 ? (uint32_t)*q : (uint32_t)*reinterpret_cast<const uint16_t*>(q);
+#pragma unroll
+            for (int d = 0; d < kCutNR; ++d) a[d] += d == dd ? v : 0u;
+            if (++rem == p.cpb) { rem = 0; ++dd; }
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();                                                         // the last tile is consumed
+  uint32_t* red = reinterpret_cast<uint32_t*>(smem);                       // [kCutNR][256]
+#pragma unroll
+  for (int d = 0; d < kCutNR; ++d) red[d * kCutTT + tid] = a[d];
+  __syncthreads();
+  const int per = min(f, kCutTT);                                          // entries of a bin (a bin of more rows folded them)
+  const int nch = KIND ? p.nchan : p.cpb;
+  for (int i = tid; i < nd * nbin; i += kCutTT) {
+    const int d = i / nbin, jb = i - d * nbin;
+    unsigned long long s = 0;
+    for (int k = 0; k < per; ++k) s += red[d * kCutTT + jb * per + k];
+    const long long t = tb + (long long)jb * f;
+    uint32_t n;
+    if (t + glo >= 0 && t + (f - 1) + ghi < nrows) {
+      n = (uint32_t)nch * (uint32_t)f;
+    } else {
+      n = 0;
+      const int32_t* dl = KIND ? dly + (size_t)d * p.nchan : dly + (size_t)(r0 + d) * p.cpb;
+      for (int c = 0; c < nch; ++c) {
+        const long long lo = max(t + dl[c], 0ll), hi = min(t + dl[c] + f, nrows);
+        if (hi > lo) n += (uint32_t)(hi - lo);
+      }
+    }
+    const size_t o = ((size_t)cand * nrow + r0 + d) * p.nt + j0 + jb;
+    p.out[o] = (float)(double)s;
+    p.hits[o] = n;
+  }
+}
 }  // namespace fast

@@ -5,6 +5,8 @@ reference's `dspsr -E <par> ... <IFall.fil>` stage) of SIGPROC filterbank files,
   (PRESTO's ``<outfile>.dat`` / ``.inf`` for one DM, ``<outfile>_DM<dm>.dat`` / ``.inf`` for a DM range), data
   dedispersed on the GPU instead of by PRESTO.  `-nobary -noweights -noscales` are what the reference always passes:
   topocentric, unweighted.
+* ``search_fil`` / ``candidates_fil`` search the DM range for single pulses, join the records of a pulse across DMs and cut
+  the frequency-time and DM-time planes a FETCH-style classifier reads (the hand-over of base2fil.sh:118-122, 425-432).
 * ``fold_fil`` mirrors base2fil.sh:465-493: spin parameters from a psrcat-style .par file, 10-s sub-integrations,
   the filterbank's channels, plus the plot (PNG) of the dedispersed, time- and frequency-scrunched profile that
   ``psrplot -pF ... -j dedisperse,tscrunch,pscrunch,"fscrunch 128"`` draws.  Files with several products (``--pol 4``)
@@ -270,6 +272,173 @@ def search_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, zerodm=True, clip=5, thre
             series[i].astype("<f4").tofile(name + ".dat")
             write_inf(name + ".inf", basename=os.path.basename(name), hdr=hdr, nsamp=nout, dm=dm, clipped=nclip.value)
     return out, cands
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# candidates: grouping across DMs and the two planes a classifier reads
+# ------------------------------------------------------------------------------------------------------------------
+SP_GROUP = np.dtype([("best", SP_CAND), ("nmember", "<u4"), ("dm_index_lo", "<u4"), ("dm_index_hi", "<u4"), ("reserved", "<u4"),
+                     ("sample_lo", "<u8"), ("sample_hi", "<u8")])
+CUT_CAND = np.dtype([("dm", "<f8"), ("dm_lo", "<f8"), ("dm_hi", "<f8"), ("sample", "<i8"), ("tfactor", "<u4"), ("reserved", "<u4")])
+CANDS_HEADER = "# DM      Sigma      Time (s)     Sample    Downfact  Members  DMlo  DMhi"
+CANDS_ROW = "%7.2f %7.2f %13.6f %10d   %3d %8d %5d %5d"
+
+
+def group_candidates(cands, hdr: dict, dms, dm_gap: int = 2, lib=None) -> np.ndarray:
+    """Join the records of one pulse across trial DMs (frbch_sp_group_cands, host only; include/frbch.h states the rule) ->
+    structured array SP_GROUP sorted by the best member's (dm_index, sample, width)."""
+    lib = lib or _lib.load()
+    recs = np.ascontiguousarray(cands, dtype=SP_CAND)
+    dm_arr = np.ascontiguousarray(dms, dtype=np.float64)
+    desc = fil_desc(hdr)
+    out = np.zeros(max(1, recs.size), dtype=SP_GROUP)
+    n = C.c_uint64(0)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_sp_group_cands(C.byref(desc), dm_arr.ctypes.data, dm_arr.size, recs.ctypes.data, recs.size, int(dm_gap),
+                                    out.ctypes.data, out.size, C.byref(n), err, len(err)), err)
+    return out[: n.value].copy()
+
+
+def cutout_cands(records, dms, dm_span=None) -> np.ndarray:
+    """Search records (SP_CAND, e.g. ``groups['best']``) -> the candidates of ``cutouts`` with the defaults
+    ``tfactor = max(1, width // 2)``, ``dm_lo = 0``, ``dm_hi = 2 * dm`` -- FETCH's / `your`'s candmaker as remembered
+    [EXT-UNVERIFIED: neither is at hand].  ``dm_span``: the DM-time plane spans ``dm - dm_span / 2 .. dm + dm_span / 2``
+    (cut at 0) instead.  ``dms = None``: the records carry their DM in a field ``dm``."""
+    records = np.asarray(records)
+    out = np.zeros(records.size, dtype=CUT_CAND)
+    if dms is not None and "dm_index" in records.dtype.names:
+        dm = np.asarray(dms, dtype=np.float64)[records["dm_index"].astype(np.int64)]
+    elif "dm" in records.dtype.names:
+        dm = records["dm"].astype(np.float64)
+    else:
+        raise InputError("records with dm_index need the DM list; without it they need a field dm")
+    out["dm"] = dm
+    if dm_span is None:
+        out["dm_lo"], out["dm_hi"] = 0.0, 2.0 * dm
+    else:
+        out["dm_lo"] = np.maximum(0.0, dm - 0.5 * float(dm_span))
+        out["dm_hi"] = out["dm_lo"] + float(dm_span)
+    out["sample"] = records["sample"].astype(np.int64)
+    out["tfactor"] = np.clip(records["width"].astype(np.int64) // 2, 1, 512)
+    return out
+
+
+CUT_TABLE_CAP = 1 << 26       # ncand * ndm * nchans a library call takes (include/frbch.h)
+
+
+def cutouts(fil_or_rows, hdr: dict, cands, nt: int = 256, nf: int = 0, ndm: int = 256, dm_span=None, device: int = 0, lib=None,
+            info: dict | None = None, batch: int = 0):
+    """The frequency-time and DM-time planes of every candidate in one library call (frbch_cutout_host; include/frbch.h
+    states the arithmetic: plain sums, no clip, no zero-DM filter) -> ``ft [n][nf][nt]``, ``ft_hits``, ``dt [n][ndm][nt]``,
+    ``dt_hits``.  ``fil_or_rows``: a SigprocFile or its rows; ``cands``: CUT_CAND records (``cutout_cands`` makes them
+    from search records and the DM list), or records with the fields ``dm``, ``sample`` and ``width``, which get the
+    defaults of ``cutout_cands``.  ``nf = 0``: the largest divisor of nchans that is at most 256.  ``info['kernel_used']``: 1 = the
+    LDS kernel, 0 = the generic one (in any call).  A list longer than one call takes (65535 candidates, 2^31 plane elements,
+    2^26 delays) or than ``batch`` (0: no limit of its own) goes in several calls of whole candidates, each of which uploads
+    the rows again; ``info['calls']`` counts them."""
+    lib = lib or _lib.load()
+    rows = _rows_of(fil_or_rows) if isinstance(fil_or_rows, sigproc.SigprocFile) else np.ascontiguousarray(fil_or_rows)
+    if rows.dtype.itemsize * 8 != hdr["nbits"] or rows.size % (hdr["nchans"] * hdr.get("nifs", 1)):
+        raise InputError("the rows do not match the header's nbits / nchans / nifs")
+    nrows = rows.size // (hdr["nchans"] * hdr.get("nifs", 1))
+    cands = np.asarray(cands)
+    if cands.dtype != CUT_CAND:
+        if cands.dtype.names is None or not {"dm", "sample", "width"} <= set(cands.dtype.names):
+            raise InputError("candidates need the fields dm, sample and width (cutout_cands makes them from search records)")
+        cands = cutout_cands(cands, None, dm_span)
+    cands = np.ascontiguousarray(cands)
+    if nf == 0:
+        nf = max(d for d in range(1, min(256, hdr["nchans"]) + 1) if hdr["nchans"] % d == 0)
+    par = _lib.FrbchCutoutParams(C.sizeof(_lib.FrbchCutoutParams), int(nt), int(nf), int(ndm))
+    n = cands.size
+    if n < 1 or not (0 < nt <= 1024 and 0 < nf <= hdr["nchans"] and 0 < ndm <= 1024):
+        raise InputError("at least one candidate, nt and ndm in 1..1024, nf in 1..nchans")
+    per_call = max(1, min(65535, ((1 << 31) - 1) // (max(nf, ndm) * nt), CUT_TABLE_CAP // (ndm * hdr["nchans"])))
+    if batch > 0:
+        per_call = min(per_call, int(batch))
+    ft, ft_hits = np.zeros((n, nf, nt), np.float32), np.zeros((n, nf, nt), np.uint32)
+    dt, dt_hits = np.zeros((n, ndm, nt), np.float32), np.zeros((n, ndm, nt), np.uint32)
+    err = C.create_string_buffer(512)
+    desc = fil_desc(hdr, hdr.get("product", 0))
+    kernels = []
+    for a in range(0, n, per_call):
+        b = min(n, a + per_call)
+        used = C.c_uint32(0)
+        part = np.ascontiguousarray(cands[a:b])
+        _check(lib.frbch_cutout_host(C.byref(desc), rows.ctypes.data, nrows, C.byref(par), part.ctypes.data, b - a, device,
+                                     ft[a:b].ctypes.data, ft_hits[a:b].ctypes.data, dt[a:b].ctypes.data, dt_hits[a:b].ctypes.data,
+                                     C.byref(used), err, len(err)), err)
+        kernels.append(used.value)
+    if info is not None:
+        info["kernel_used"] = min(kernels)
+        info["calls"] = len(kernels)
+    return ft, ft_hits, dt, dt_hits
+
+
+def _plane_mean(sums, hits):
+    return np.where(hits > 0, sums.astype(np.float64) / np.maximum(hits, 1), 0.0).astype(np.float32)
+
+
+def cand_name(base: str, tstart: float, tcand: float, dm: float, snr: float) -> str:
+    """the image name utils/parse_fetch_image_name.py splits: tstart_, tcand_, dm_, snr_"""
+    return "%s_cand_tstart_%.12f_tcand_%.7f_dm_%.5f_snr_%.5f" % (base, tstart, tcand, dm, snr)
+
+
+def candidates_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, zerodm=True, clip=5, threshold=5.0, max_width_s=0.0, detrend_len=1000,
+                   widths=None, dm_gap=2, min_members=1, max_cands=0, nt=256, nf=0, ndm=256, dm_span=None, device=0, lib=None,
+                   info: dict | None = None):
+    """``search_fil``, then one candidate per pulse: the records are grouped across DMs (``group_candidates``), groups of
+    fewer than ``min_members`` records are dropped, the ``max_cands`` strongest kept (0: all), and ONE frbch_cutout_host
+    call cuts the two planes of all of them (``cutouts``: several calls only for a list longer than a call takes).  Writes, next to ``search_fil``'s own files (which are unchanged),
+    ``<base>.cands.txt`` (one line per kept group) and per group ``<base>_cand_tstart_<mjd>_tcand_<s>_dm_<dm>_snr_<sigma>``
+    ``.npz`` (data_freq_time [nt][nf] and data_dm_time [ndm][nt] as means = sums / hits, 0 where hits is 0; the four raw
+    planes; the scalars) and ``.png`` (the frequency-time plane above the DM-time plane).
+    Returns (list of .npz files, kept groups as a structured array)."""
+    lib = lib or _lib.load()
+    sinfo = {}
+    _files, recs = search_fil(filterbankfile, dm1, dm2=dm2, dmstep=dmstep, zerodm=zerodm, clip=clip, threshold=threshold,
+                              max_width_s=max_width_s, detrend_len=detrend_len, widths=widths, device=device, lib=lib, info=sinfo)
+    fil = sigproc.read_fil(filterbankfile)
+    hdr = fil.header
+    dms = dm_list(dm1, dm2, dmstep)
+    groups = group_candidates(recs, hdr, dms, dm_gap=dm_gap, lib=lib)
+    groups = groups[groups["nmember"] >= min_members]
+    if max_cands > 0 and groups.size > max_cands:
+        keep = np.sort(np.argsort(-groups["best"]["sigma"], kind="stable")[:max_cands])
+        groups = groups[keep]
+    base = filterbankfile.replace(".fil", "")
+    with open(base + ".cands.txt", "w") as f:
+        f.write(CANDS_HEADER + "\n")
+        for g in groups:
+            b = g["best"]
+            f.write(CANDS_ROW % (dms[int(b["dm_index"])], b["sigma"], int(b["sample"]) * hdr["tsamp"], int(b["sample"]), int(b["width"]),
+                                 int(g["nmember"]), int(g["dm_index_lo"]), int(g["dm_index_hi"])) + "\n")
+    if info is not None:
+        info.update(sinfo, ngroup=int(groups.size), search_kernel_used=sinfo.get("kernel_used"))
+    out = []
+    if groups.size == 0:
+        return out, groups
+    cc = cutout_cands(groups["best"], dms, dm_span)
+    cinfo = {}
+    ft, ft_hits, dt, dt_hits = cutouts(fil, hdr, cc, nt=nt, nf=nf, ndm=ndm, device=device, lib=lib, info=cinfo)
+    if info is not None:
+        info["cutout_kernel_used"] = cinfo["kernel_used"]
+    for i, (g, c) in enumerate(zip(groups, cc)):
+        b = g["best"]
+        tcand = int(b["sample"]) * hdr["tsamp"]
+        name = cand_name(base, hdr["tstart"], tcand, c["dm"], float(b["sigma"]))
+        ft_mean, dt_mean = _plane_mean(ft[i], ft_hits[i]), _plane_mean(dt[i], dt_hits[i])
+        np.savez(name + ".npz", data_freq_time=ft_mean.T.copy(), data_dm_time=dt_mean, ft=ft[i], ft_hits=ft_hits[i], dt=dt[i],
+                 dt_hits=dt_hits[i], tcand=tcand, dm=c["dm"], snr=float(b["sigma"]), width=int(b["width"]), tfactor=int(c["tfactor"]),
+                 tsamp=hdr["tsamp"], fch1=hdr["fch1"], foff=hdr["foff"], nchans=hdr["nchans"], tstart=hdr["tstart"],
+                 dm_lo=c["dm_lo"], dm_hi=c["dm_hi"])
+
+        def unit(img):
+            img = img - img.mean(axis=1, keepdims=True)
+            return (img - img.min()) / max(1e-30, float(img.max() - img.min()))
+        write_png(name + ".png", np.concatenate([unit(ft_mean), np.zeros((4, ft_mean.shape[1])), unit(dt_mean)], axis=0))
+        out.append(name + ".npz")
+    return out, groups
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -644,7 +813,8 @@ def fold_fil(filterbankfile: str, parfile: str, nbin: int = 0, subint_s: float =
 
 def main(argv=None):
     """``python -m frb_baseband_amd.post fold <fil> <par> [--polyco FILE] [--doppler X] [--products coherency|stokes] [...]`` / ``... prepdata <fil> --dm <dm> [...]`` /
-    ``... search <fil> --dm <dm> [--dm2 --dmstep --threshold --max-width --detrend ...]``: the stages
+    ``... search <fil> --dm <dm> [--dm2 --dmstep --threshold --max-width --detrend ...]`` /
+    ``... candidates <fil> --dm <dm> [search options] [--dm-gap --min-members --max-cands --nt --nf --ndm]``: the stages
     as commands, for the places where base2fil.sh / process_vdif.py launch dspsr and prepdata"""
     import argparse
     ap = argparse.ArgumentParser(prog="frb_baseband_amd.post")
@@ -679,8 +849,33 @@ def main(argv=None):
     q.add_argument("--clip", type=float, default=5.0)
     q.add_argument("--write-dat", action="store_true", help="also write the .dat / .inf files of prepdata")
     q.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
+    k = sub.add_parser("candidates", help="search, group the records across DMs, cut the frequency-time and DM-time planes of every group")
+    k.add_argument("fil")
+    k.add_argument("--dm", type=float, required=True)
+    k.add_argument("--dm2", type=float, default=0.0)
+    k.add_argument("--dmstep", type=float, default=1.0)
+    k.add_argument("--threshold", type=float, default=5.0, help="sigma a boxcar sum must reach")
+    k.add_argument("--max-width", type=float, default=0.0, help="widest boxcar, s (0: widths up to 30 samples)")
+    k.add_argument("--detrend", type=int, default=1000, help="samples per normalisation block")
+    k.add_argument("--nozerodm", action="store_false", help="do not subtract the zero-DM series (search only: the planes are plain sums)")
+    k.add_argument("--clip", type=float, default=5.0)
+    k.add_argument("--dm-gap", type=int, default=2, help="records at most this many trial DMs apart can join")
+    k.add_argument("--min-members", type=int, default=1, help="drop groups of fewer records")
+    k.add_argument("--max-cands", type=int, default=0, help="keep the strongest N groups (0: all)")
+    k.add_argument("--nt", type=int, default=256)
+    k.add_argument("--nf", type=int, default=0, help="frequency bins (0: the largest divisor of nchans up to 256)")
+    k.add_argument("--ndm", type=int, default=256)
+    k.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     a = ap.parse_args(argv)
-    if a.cmd == "fold":
+    if a.cmd == "candidates":
+        files, groups = candidates_fil(a.fil, a.dm, dm2=a.dm2, dmstep=a.dmstep, zerodm=a.nozerodm, clip=a.clip, threshold=a.threshold,
+                                       max_width_s=a.max_width, detrend_len=a.detrend, dm_gap=a.dm_gap, min_members=a.min_members,
+                                       max_cands=a.max_cands, nt=a.nt, nf=a.nf, ndm=a.ndm, device=a.device)
+        print("wrote", a.fil.replace(".fil", "") + ".cands.txt")
+        for path in files:
+            print("wrote", path, "and .png")
+        print("{0} candidates above {1} sigma".format(groups.size, a.threshold))
+    elif a.cmd == "fold":
         ar, profile = fold_fil(a.fil, a.par, nbin=a.nbin, subint_s=a.subint, fscrunch_to=a.fscrunch, device=a.device,
                                polyco=a.polyco, doppler=a.doppler, products=a.products)
         print("wrote {0}, {1}.profile.txt, {1}.png; peak bin {2} of {3}".format(ar, a.fil, int(np.argmax(profile)), profile.size))

@@ -398,6 +398,71 @@ int frbch_dedisperse_search_host(const frbch_fil_desc* fil, const void* rows, ui
                                  float* series_out, uint64_t nout, uint64_t* nclipped, frbch_sp_cand* cands, uint64_t cap,
                                  uint64_t* ncand, uint32_t* kernel_used, char* err, size_t err_cap);
 
+/* ---- candidates: grouping across DMs, and the two planes a classifier reads -------------------------
+ * The search above returns one record per DM for a pulse that stands out at several trial DMs.  frbch_sp_group_cands
+ * joins them (host only, no device), and frbch_cutout_* cut, for every kept candidate, the two small images a FETCH-style
+ * classifier reads [EXT-UNVERIFIED: FETCH, `your` and heimdall are not in the reference tree; the reference only hands
+ * the spliced filterbank over (base2fil.sh:118-122, 425-432) and parses the resulting image names
+ * (utils/parse_fetch_image_name.py)]: the dedispersed frequency-time plane and the DM-time "bow tie".  The conventions
+ * are this library's own, restated in numpy in tests/cutout_oracle.py, and every result is reproducible to the bit.
+ *
+ * Grouping, integer arithmetic only.  D_i = the largest per-channel delay n_c(dms[i]) in samples (the delays of
+ * frbch_dedisperse_*).  Two records a, b are LINKED iff
+ *     |dm_index_a - dm_index_b| <= dm_gap   and   |sample_a - sample_b| <= max(width_a, width_b) / 2 + |D_a - D_b|
+ * (integer division; the second term is the smear of a pulse dedispersed at the wrong DM -- the series are referenced to
+ * the top of the band).  Groups are the connected components of the link graph.  `best` is the member with the largest
+ * sigma; ties: the narrower width, then the lower dm_index, then the earlier sample.  Groups come sorted by best's
+ * (dm_index, sample, width).  More groups than `cap`: FRBCH_E_CAPACITY with *ngroup set (cap = 0 with groups = NULL
+ * counts).  FRBCH_E_ARG: dm_gap outside 1..16, a dm_index >= ndm, a DM frbch_dedisperse_nout would refuse. */
+typedef struct frbch_sp_group {
+  frbch_sp_cand best;                  /* the member that represents the group                                            */
+  uint32_t nmember, dm_index_lo, dm_index_hi, reserved;
+  uint64_t sample_lo, sample_hi;       /* over the members' centres                                                       */
+} frbch_sp_group;
+int frbch_sp_group_cands(const frbch_fil_desc* fil, const double* dms, uint32_t ndm, const frbch_sp_cand* cands, uint64_t ncand,
+                         uint32_t dm_gap, frbch_sp_group* groups, uint64_t cap, uint64_t* ngroup, char* err, size_t err_cap);
+
+/* Cut-outs.  For candidate i with f = tfactor, t0 = sample - (nt / 2) * f (signed 64 bit) and cpb = nchan / nf:
+ *   trial DMs   dm_k = dm_lo + (double)k * ((dm_hi - dm_lo) / (double)(ndm - 1)), every operation rounded on its own
+ *               (ndm = 1: dm_lo);
+ *   delays      n_c(.) exactly as frbch_dedisperse_* compute them;
+ *   samples     V(s, c) = the sample of product fil->product at row s, channel c, PRESENT iff 0 <= s < nrows.  Absent
+ *               samples add nothing and are not counted: a window partly or wholly outside the data is no error, its
+ *               hits say so;
+ *   FT[i][b][j] = sum over c = b cpb .. (b + 1) cpb - 1 (ascending), over u = 0 .. f - 1 (ascending, the inner loop) of
+ *               V(t0 + j f + u + n_c(dm), c);  ft_hits[i][b][j] = the number of present terms.  Frequency bins are in
+ *               file channel order;
+ *   DT[i][k][j] = the same sum over ALL channels at the delays n_c(dm_k);  dt_hits likewise.
+ * Sums are in double and stored as float32, as in frbch_dedisperse_*: on integer rows every sum is exact in any order
+ * (at most 65535 * 512 * 4096 < 2^53), on float rows the order is the stated one and the result bit-identical.
+ * NO clip and NO zero-DM filter are applied: the classifier normalises the planes itself.
+ * FRBCH_E_ARG: a wrong `size`, nt odd or outside 2..1024, nf not dividing nchan, ndm outside 1..1024, tfactor outside
+ * 1..512, ncand outside 1..65535, a DM outside [0, 1e5), dm_hi < dm_lo, a plane set of 2^31 elements or more, a delay
+ * of more than 2^30 samples, and ncand * ndm * nchan > 2^26 (the delay table of a call, 256 MiB; the same query and the
+ * same tables serve frbch_cutout_kernel): cut a longer batch into several calls of whole candidates.
+ * *kernel_used (may be NULL): 1 = the LDS kernel (8- / 16-bit rows, whole 64-byte channel tiles, d_rows and the row pitch
+ * 16-byte aligned, and the rows of every (group of 8 plane rows, channel tile, time tile) fit the LDS), 0 = the generic
+ * kernel (one thread per pixel); both give the same bits.  One choice holds for both planes of all candidates. */
+typedef struct frbch_cutout_params { uint32_t size, nt, nf, ndm; } frbch_cutout_params;   /* size = sizeof(frbch_cutout_params) */
+typedef struct frbch_cutout_cand {
+  double dm, dm_lo, dm_hi;             /* DM of the frequency-time plane; the DM-time plane spans dm_lo .. dm_hi           */
+  int64_t sample;                      /* centre, in samples of the dedispersed series (row index at the top of the band)  */
+  uint32_t tfactor, reserved;          /* rows per time bin, 1..512                                                        */
+} frbch_cutout_cand;
+int frbch_cutout_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_cutout_params* par,
+                        const frbch_cutout_cand* cands /* host */, uint32_t ncand, int device,
+                        float* d_ft, uint32_t* d_ft_hits,   /* [ncand][nf][nt]  */
+                        float* d_dt, uint32_t* d_dt_hits,   /* [ncand][ndm][nt] */
+                        uint32_t* kernel_used, char* err, size_t err_cap);
+/* the same with host pointers: one upload of the rows, one download of the planes */
+int frbch_cutout_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_cutout_params* par,
+                      const frbch_cutout_cand* cands, uint32_t ncand, int device, float* ft, uint32_t* ft_hits, float* dt,
+                      uint32_t* dt_hits, uint32_t* kernel_used, char* err, size_t err_cap);
+/* Which kernel frbch_cutout_device takes for these arguments (host only, nothing runs): 1 = the LDS kernel, 0 = the
+ * generic one, < 0 = refused; only the ADDRESS of d_rows is examined. */
+int frbch_cutout_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_cutout_params* par,
+                        const frbch_cutout_cand* cands, uint32_t ncand);
+
 /* ---- in front of the filterbank: the corner turn -------------------------------
  * jive5ab's spif2file splits the recorder's stream -- every W-bit word holds one time sample of ALL channels -- into one
  * 2-channel stream per IF, driven by the recipe strings of spif2file.sh:31-113, e.g. the 16-channel 2-bit mode
