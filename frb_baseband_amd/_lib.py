@@ -95,6 +95,11 @@ class FrbchCutoutCand(C.Structure):
                 ("tfactor", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class FrbchRfiParams(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("block_rows", C.c_uint32), ("t_cell", C.c_double), ("t_chan", C.c_double),
+                ("chan_frac", C.c_double), ("block_frac", C.c_double)]
+
+
 class _KTiming(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double),
                 ("algorithmic_bytes", C.c_double)]
@@ -164,6 +169,22 @@ SYMBOLS = {
     "frbch_cutout_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchCutoutParams), _P, C.c_uint32, C.c_int,
                                     _P, _P, _P, _P, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
     "frbch_cutout_kernel": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchCutoutParams), _P, C.c_uint32]),
+    "frbch_rfi_nblk": (C.c_long, [C.c_uint64, C.c_uint32]),
+    "frbch_rfi_stats_kernel": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams)]),
+    "frbch_rfi_stats_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams), C.c_int, _P,
+                                         C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_rfi_stats_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams), C.c_int, _P,
+                                       C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_rfi_mask": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint32, C.c_uint64, C.POINTER(FrbchRfiParams), _P, _P, _P, _P, _P,
+                                 _P, C.c_char_p, C.c_size_t]),
+    "frbch_rfi_apply_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams), _P, _P, C.c_int,
+                                         C.c_char_p, C.c_size_t]),
+    "frbch_rfi_apply_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams), _P, _P, C.c_int,
+                                       C.c_char_p, C.c_size_t]),
+    "frbch_rfi_clean_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams), _P, C.c_int, _P, _P, _P,
+                                         _P, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_rfi_clean_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams), _P, C.c_int, _P, _P, _P,
+                                       _P, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
     "frbch_cornerturn_info": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
     "frbch_cornerturn_host": (C.c_int, [C.c_char_p, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(_P), C.c_uint32,

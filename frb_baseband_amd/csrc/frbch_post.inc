@@ -1,6 +1,11 @@
 // C-ABI entry points behind the filterbank (include/frbch.h, "after the filterbank"): incoherent dedispersion of SIGPROC
 // rows with PRESTO's prepdata / prepsubband options as the reference passes them (process_vdif.py:202-229) and the phase
 // fold that base2fil.sh:474 delegates to dspsr.  Included by frbch_post.cpp (its own translation unit).
+#include <limits>
+#include <new>
+#include <system_error>
+#include <thread>
+
 #include "kernels_post.inc"
 #ifndef FRBCH_NO_FAST
 #include "kernels_post_fast.inc"
@@ -1122,6 +1127,459 @@ extern "C" int frbch_cutout_host(const frbch_fil_desc* fil, const void* rows, ui
               dev_d2h(dt_hits, d_dth, ndt * 4, 0) != 0 || dev_sync(0) != 0))
     rc = e.fail(FRBCH_E_DEVICE, "download planes");
   dev_free(d_rows); dev_free(d_ft); dev_free(d_fth); dev_free(d_dt); dev_free(d_dth);
+  return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// interference: block statistics, the mask, cleaned rows
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr uint32_t kRfiMaxBlockRows = 1u << 20;
+constexpr uint32_t kRfiGridBlocks = 65535;        // blocks of one launch (grid.y)
+
+int rfi_check(const frbch_fil_desc* f, uint64_t nrows, const frbch_rfi_params* par, uint32_t* nblk, const PostErr& e) {
+  if (!f || f->size != sizeof(frbch_fil_desc)) return e.fail(FRBCH_E_ARG, "frbch_fil_desc: wrong size");
+  if (f->nchan < 1 || f->nifs < 1 || f->product >= f->nifs) return e.fail(FRBCH_E_ARG, "bad nchan / nifs / product");
+  if (f->nbits != 8 && f->nbits != 16 && f->nbits != 32) return e.fail(FRBCH_E_ARG, "nbits must be 8, 16 or 32 (float)");
+  if (!nrows) return e.fail(FRBCH_E_ARG, "no rows");
+  if (!par || par->size != sizeof(frbch_rfi_params)) return e.fail(FRBCH_E_ARG, "frbch_rfi_params: wrong size");
+  if (par->block_rows < 1 || par->block_rows > kRfiMaxBlockRows) return e.fail(FRBCH_E_ARG, "block_rows must be 1..2^20");
+  if (!(par->t_cell >= 0) || !(par->t_chan >= 0) || std::isinf(par->t_cell) || std::isinf(par->t_chan))
+    return e.fail(FRBCH_E_ARG, "t_cell and t_chan must be finite and not negative");
+  if (!(par->chan_frac >= 0) || !(par->block_frac >= 0) || par->chan_frac > 1.0 || par->block_frac > 1.0)
+    return e.fail(FRBCH_E_ARG, "chan_frac and block_frac must lie in 0..1");
+  const uint64_t n = (nrows + par->block_rows - 1) / par->block_rows;
+  if (n > 0x7FFFFFFFull || (uint64_t)f->nchan > 0x7FFFFFFFull / f->nifs) return e.fail(FRBCH_E_ARG, "too many blocks or channels");
+  *nblk = (uint32_t)n;
+  return FRBCH_OK;
+}
+
+// Which statistics kernel a call takes -- the one decision behind frbch_rfi_stats_device's launch, *kernel_used and
+// frbch_rfi_stats_kernel's answer.  > 0 = the fast kernel (kernels_post_fast.inc) with that many bytes of the row per
+// workgroup: 8- / 16-bit rows, whole 64-byte channel tiles, 16-byte pieces of every row (only the ADDRESS of d_rows is
+// examined); the tile is the largest listed width that divides the row piece.  The emulator build has no such kernel: 0.
+int rfi_fast_tile(const frbch_fil_desc* fil, const void* d_rows) {
+#ifndef FRBCH_NO_FAST
+  if (fil->nbits != 8 && fil->nbits != 16) return 0;
+  const size_t bpv = (size_t)fil->nbits / 8, piece = (size_t)fil->nchan * bpv;
+  if (piece % 64 != 0 || ((uintptr_t)d_rows % 16) != 0 || ((size_t)fil->nifs * piece) % 16 != 0) return 0;
+  for (int w = 1024; w >= 64; w >>= 1)
+    if (piece % (size_t)w == 0) return w;
+  return 0;
+#else
+  (void)fil; (void)d_rows;
+  return 0;
+#endif
+}
+
+RfiParams rfi_params(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_rfi_params* par, uint32_t nblk) {
+  RfiParams p;
+  memset(&p, 0, sizeof p);
+  p.rows = (uint8_t*)d_rows;
+  p.nrows = nrows;
+  p.nchan = (int)fil->nchan; p.nifs = (int)fil->nifs; p.nbits = fil->nbits; p.prod = (int)fil->product;
+  p.block_rows = par->block_rows;
+  p.nblk = nblk;
+  return p;
+}
+
+// The k-th smallest of v[0 .. n) (no NaN among them); reorders v so that v[k] holds it and nothing before it is larger.
+// Quickselect whose partition passes do not branch on the data: the table of a long file asks for thousands of medians.
+double rfi_select(double* v, size_t n, size_t k) {
+  size_t lo = 0, hi = n;
+  while (hi - lo > 8) {
+    const double a = v[lo], b = v[lo + (hi - lo) / 2], c = v[hi - 1];
+    const double p = std::max(std::min(a, b), std::min(std::max(a, b), c));        // median of three: a value of the range
+    size_t i = lo;
+    for (size_t j = lo; j < hi; ++j) {                                             // [lo, i) < p <= [i, hi)
+      const double x = v[j];
+      v[j] = v[i];
+      v[i] = x;
+      i += x < p ? 1 : 0;
+    }
+    if (k < i) { hi = i; continue; }
+    size_t m = i;
+    for (size_t j = i; j < hi; ++j) {                                              // [i, m) == p < [m, hi)
+      const double x = v[j];
+      v[j] = v[m];
+      v[m] = x;
+      m += x <= p ? 1 : 0;
+    }
+    if (k < m) return p;
+    lo = m;
+  }
+  for (size_t i = lo + 1; i < hi; ++i) {
+    const double x = v[i];
+    size_t j = i;
+    for (; j > lo && v[j - 1] > x; --j) v[j] = v[j - 1];
+    v[j] = x;
+  }
+  return v[k];
+}
+
+// 0.5 * (lower middle + upper middle) of v[0 .. n), n >= 1; reorders v
+double rfi_median(double* v, size_t n) {
+  const size_t k = n / 2;
+  const double hi = rfi_select(v, n, k);
+  double lo = hi;
+  if (!(n & 1)) lo = *std::max_element(v, v + k);
+  return 0.5 * (lo + hi);
+}
+
+// fn(first channel, one past the last) over all channels, on several threads when the table is large: every channel's
+// result depends on that channel alone, so the split changes no bit.  (Measured on the 306 x 1024 table of a 10-s file: the
+// four medians per channel are 20 ms of std::nth_element on one thread, more than the dedispersion the stage stands in
+// front of; rfi_select and the split bring the decision to 2 ms.)  A thread that cannot be started runs in the caller.
+template <class F>
+void rfi_over_channels(uint32_t nchan, uint32_t nblk, F fn) {
+  const uint64_t cells = (uint64_t)nchan * nblk;
+  unsigned nt = cells >= (1u << 16) ? std::min(16u, std::max(1u, std::thread::hardware_concurrency())) : 1u;
+  nt = std::min<unsigned>(nt, nchan);
+  if (nt <= 1) { fn(0u, nchan); return; }
+  std::vector<std::thread> th;
+  th.reserve(nt);
+  const uint32_t per = (nchan + nt - 1) / nt;
+  for (unsigned i = 1; i < nt; ++i) {
+    if (i * per >= nchan) break;
+    const uint32_t c0 = i * per, c1 = std::min(nchan, (i + 1) * per);
+    try {
+      th.emplace_back(fn, c0, c1);
+    } catch (const std::system_error&) {
+      fn(c0, c1);
+    }
+  }
+  fn(0u, std::min(nchan, per));
+  for (auto& t : th) t.join();
+}
+}  // namespace
+
+extern "C" long frbch_rfi_nblk(uint64_t nrows, uint32_t block_rows) {
+  if (!nrows || block_rows < 1 || block_rows > kRfiMaxBlockRows) return FRBCH_E_ARG;
+  return (long)((nrows + block_rows - 1) / block_rows);
+}
+
+extern "C" int frbch_rfi_stats_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_rfi_params* par) {
+  PostErr e{nullptr, 0};
+  uint32_t nblk = 0;
+  const int rc = rfi_check(fil, nrows, par, &nblk, e);
+  if (rc) return rc;
+  if (!d_rows) return FRBCH_E_ARG;
+  return rfi_fast_tile(fil, d_rows) > 0 ? 1 : 0;
+}
+
+extern "C" int frbch_rfi_stats_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_rfi_params* par,
+                                      int device, void* d_stats, uint32_t* kernel_used, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  uint32_t nblk = 0;
+  int rc = rfi_check(fil, nrows, par, &nblk, e);
+  if (rc) return rc;
+  if (!d_rows || !d_stats) return e.fail(FRBCH_E_ARG, "null argument");
+  if (device < 0 || device >= dev_count()) return e.fail(FRBCH_E_DEVICE, "no such GPU (there is no CPU fallback)");
+  DeviceGuard dg(device);
+  dev_stream_t s = 0;
+  if (dev_stream_create(&s) != 0) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  auto cleanup = [&]() { dev_stream_destroy(s); };
+#define POST_DEV(expr, what) do { if ((expr) != 0) { cleanup(); return e.fail(FRBCH_E_DEVICE, std::string(what) + ": " + dev_last_error_string()); } } while (0)
+  RfiParams p = rfi_params(fil, d_rows, nrows, par, nblk);
+  p.stats_i = (unsigned long long*)d_stats;
+  p.stats_f = (double*)d_stats;
+  const int tile = rfi_fast_tile(fil, d_rows);
+  for (uint32_t b0 = 0; b0 < nblk; b0 += kRfiGridBlocks) {
+    const uint32_t nb = std::min(kRfiGridBlocks, nblk - b0);
+    p.blk0 = b0;
+#ifndef FRBCH_NO_FAST
+    if (tile > 0) {
+      p.tile_bytes = tile;
+      p.ntile = (int)((size_t)fil->nchan * (fil->nbits / 8) / (size_t)tile);
+      const dim3 grid((unsigned)p.ntile, nb);
+      if (fil->nbits == 8) hipLaunchKernelGGL(fast::frbch_post_rfi_stats_fast<1>, grid, dim3(fast::kRfiThreads), 0, s, p);
+      else hipLaunchKernelGGL(fast::frbch_post_rfi_stats_fast<2>, grid, dim3(fast::kRfiThreads), 0, s, p);
+    }
+#endif
+    if (tile <= 0) DEV_LAUNCH(frbch_post_rfi_stats, (fil->nchan + 255) / 256, nb, 256, 0, s, p);
+    POST_DEV(dev_check_launch(), "launch statistics");
+  }
+  POST_DEV(dev_sync(s), "sync");
+#undef POST_DEV
+  if (kernel_used) *kernel_used = tile > 0 ? 1 : 0;
+  cleanup();
+  return FRBCH_OK;
+}
+
+extern "C" int frbch_rfi_stats_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_rfi_params* par,
+                                    int device, void* stats, uint32_t* kernel_used, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  uint32_t nblk = 0;
+  int rc = rfi_check(fil, nrows, par, &nblk, e);
+  if (rc) return rc;
+  if (!rows || !stats) return e.fail(FRBCH_E_ARG, "null argument");
+  if (device < 0 || device >= dev_count()) return e.fail(FRBCH_E_DEVICE, "no such GPU (there is no CPU fallback)");
+  DeviceGuard dg(device);
+  const size_t in_bytes = (size_t)nrows * fil->nifs * fil->nchan * (size_t)(fil->nbits / 8);
+  const size_t st_bytes = (size_t)nblk * fil->nchan * 16;
+  void *d_rows = nullptr, *d_stats = nullptr;
+  if (dev_malloc(&d_rows, in_bytes) != 0 || dev_malloc(&d_stats, st_bytes) != 0) rc = e.fail(FRBCH_E_NOMEM, "device memory for the rows");
+  if (!rc && (dev_h2d(d_rows, rows, in_bytes, 0) != 0 || dev_sync(0) != 0)) rc = e.fail(FRBCH_E_DEVICE, "upload rows");
+  if (!rc) rc = frbch_rfi_stats_device(fil, d_rows, nrows, par, device, d_stats, kernel_used, err, err_cap);
+  if (!rc && (dev_d2h(stats, d_stats, st_bytes, 0) != 0 || dev_sync(0) != 0)) rc = e.fail(FRBCH_E_DEVICE, "download statistics");
+  dev_free(d_rows); dev_free(d_stats);
+  return rc;
+}
+
+// The one decision (include/frbch.h, steps 1 to 8), host only: IEEE double, every operation rounded on its own.
+extern "C" int frbch_rfi_mask(const frbch_fil_desc* fil, const void* stats, uint32_t nblk, uint64_t nrows, const frbch_rfi_params* par,
+                              const uint8_t* zap, const uint8_t* prior, uint8_t* mask, double* repl, uint8_t* chan_flag,
+                              uint8_t* blk_flag, char* err, size_t err_cap) {
+  POST_NO_CONTRACT
+  PostErr e{err, err_cap};
+  uint32_t want = 0;
+  const int rc = rfi_check(fil, nrows, par, &want, e);
+  if (rc) return rc;
+  if (nblk != want) return e.fail(FRBCH_E_ARG, "nblk must be frbch_rfi_nblk()");
+  if (!stats || !mask || !repl || !chan_flag || !blk_flag) return e.fail(FRBCH_E_ARG, "null argument");
+  const uint32_t nchan = fil->nchan;
+  const bool integer_rows = fil->nbits != 32;
+  const uint64_t n_last = nrows - (uint64_t)(nblk - 1) * par->block_rows;          // rows of the last block
+  const double t_cell = par->t_cell;
+  try {
+  std::atomic<bool> oom(false);                     // (a worker's failed allocation must not leave its thread)
+  // mean, std and the cell flags, [channel][block]: a channel's blocks lie side by side for the medians
+  std::vector<double> mean((size_t)nchan * nblk), sdev((size_t)nchan * nblk);
+  std::vector<uint8_t> bad((size_t)nchan * nblk), cell((size_t)nchan * nblk);
+  std::vector<double> m_c(nchan), s_c(nchan);
+  std::vector<uint32_t> nbad(nchan), ncell(nchan);
+  rfi_over_channels(nchan, nblk, [&](uint32_t c0, uint32_t c1) {
+    POST_NO_CONTRACT
+    std::vector<double> a, w, d;
+    try { a.resize(nblk); w.resize(nblk); d.resize(nblk); } catch (const std::bad_alloc&) { oom = true; return; }
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (uint32_t cc = c0; cc < c1; cc += 16) {                                      // step 1, 16 channels of a table row at a time
+      for (uint32_t b = 0; b < nblk; ++b) {
+        const double nb = (double)(b + 1 < nblk ? (uint64_t)par->block_rows : n_last);
+        for (uint32_t c = cc; c < std::min(c1, cc + 16); ++c) {
+          const size_t i = ((size_t)b * nchan + c) * 2;
+          const double S = integer_rows ? (double)((const uint64_t*)stats)[i] : ((const double*)stats)[i];
+          const double Q = integer_rows ? (double)((const uint64_t*)stats)[i + 1] : ((const double*)stats)[i + 1];
+          const double m = S / nb;
+          const double mm = m * m;
+          const double qn = Q / nb;
+          double var = qn - mm;
+          if (var < 0.0) var = 0.0;                                                  // (a NaN stays a NaN)
+          const double sg = sqrt(var);
+          mean[(size_t)c * nblk + b] = m;
+          sdev[(size_t)c * nblk + b] = sg;
+          bad[(size_t)c * nblk + b] = (uint8_t)(std::isfinite(m) && std::isfinite(sg) ? 0 : 1);
+        }
+      }
+    }
+    for (uint32_t c = c0; c < c1; ++c) {
+      double* mu = &mean[(size_t)c * nblk];
+      double* sd = &sdev[(size_t)c * nblk];
+      uint8_t* bd = &bad[(size_t)c * nblk];
+      uint8_t* fl = &cell[(size_t)c * nblk];
+      size_t n = 0;
+      for (uint32_t b = 0; b < nblk; ++b)
+        if (!bd[b]) { a[n] = mu[b]; w[n] = sd[b]; ++n; }
+      nbad[c] = (uint32_t)(nblk - n);
+      if (!n) {
+        m_c[c] = s_c[c] = nan;
+        for (uint32_t b = 0; b < nblk; ++b) fl[b] = 1;
+        ncell[c] = nblk;
+        continue;
+      }
+      for (size_t i = 0; i < n; ++i) d[i] = a[i];                                  // step 2
+      const double mc = rfi_median(d.data(), n);
+      for (size_t i = 0; i < n; ++i) d[i] = w[i];
+      const double sc = rfi_median(d.data(), n);
+      for (size_t i = 0; i < n; ++i) d[i] = fabs(a[i] - mc);
+      const double dmc = 1.4826 * rfi_median(d.data(), n);
+      for (size_t i = 0; i < n; ++i) d[i] = fabs(w[i] - sc);
+      const double dsc = 1.4826 * rfi_median(d.data(), n);
+      m_c[c] = mc;
+      s_c[c] = sc;
+      double lim_m[2], lim_s[2];                                                   // step 3: [0] a whole block, [1] the last one
+      for (int k = 0; k < 2; ++k) {
+        const double nb = (double)(k ? n_last : (uint64_t)par->block_rows);
+        const double fm = sc / sqrt(nb);
+        const double two_n = 2.0 * nb;
+        const double fs = sc / sqrt(two_n);
+        lim_m[k] = t_cell * (dmc > fm ? dmc : fm);
+        lim_s[k] = t_cell * (dsc > fs ? dsc : fs);
+      }
+      uint32_t cnt = 0;
+      for (uint32_t b = 0; b < nblk; ++b) {
+        if (bd[b]) { fl[b] = 1; ++cnt; continue; }
+        const int k = b + 1 < nblk ? 0 : 1;
+        fl[b] = (uint8_t)((fabs(mu[b] - mc) > lim_m[k] || fabs(sd[b] - sc) > lim_s[k]) ? 1 : 0);
+        cnt += fl[b];
+      }
+      ncell[c] = cnt;
+    }
+  });
+  if (oom) return e.fail(FRBCH_E_NOMEM, "host memory for the mask decision");
+  for (uint32_t c = 0; c < nchan; ++c)                                             // step 4
+    chan_flag[c] = (uint8_t)(((zap && zap[c]) || nbad[c] == nblk || s_c[c] == 0.0) ? 1 : 0);
+  if (par->t_chan > 0.0) {                                                         // step 5
+    std::vector<double> v, d;
+    for (uint32_t c = 0; c < nchan; ++c)
+      if (!chan_flag[c]) v.push_back(s_c[c]);
+    if (!v.empty()) {
+      d = v;
+      const double M = rfi_median(d.data(), d.size());
+      for (size_t i = 0; i < v.size(); ++i) d[i] = fabs(v[i] - M);
+      const double D = 1.4826 * rfi_median(d.data(), d.size());
+      const double lim = par->t_chan * D;
+      for (uint32_t c = 0; c < nchan; ++c)
+        if (!chan_flag[c] && fabs(s_c[c] - M) > lim) chan_flag[c] = 1;
+    }
+  }
+  const double chan_lim = par->chan_frac * (double)nblk;                           // step 6
+  uint32_t n_u = 0;
+  for (uint32_t c = 0; c < nchan; ++c) {
+    if (!chan_flag[c] && (double)ncell[c] > chan_lim) chan_flag[c] = 1;
+    n_u += chan_flag[c] ? 0u : 1u;
+  }
+  const double blk_lim = par->block_frac * (double)n_u;
+  std::vector<uint32_t> nb_cells(nblk, 0);
+  for (uint32_t c = 0; c < nchan; ++c)
+    if (!chan_flag[c])
+      for (uint32_t b = 0; b < nblk; ++b) nb_cells[b] += cell[(size_t)c * nblk + b];
+  for (uint32_t b = 0; b < nblk; ++b) blk_flag[b] = (uint8_t)((double)nb_cells[b] > blk_lim ? 1 : 0);
+  rfi_over_channels(nchan, nblk, [&](uint32_t c0, uint32_t c1) {                   // step 7 (`cell` becomes the mask, transposed)
+    for (uint32_t c = c0; c < c1; ++c)
+      for (uint32_t b = 0; b < nblk; ++b)
+        if (chan_flag[c] || blk_flag[b]) cell[(size_t)c * nblk + b] = 1;
+    for (uint32_t b = 0; b < nblk; ++b)
+      for (uint32_t c = c0; c < c1; ++c) {
+        const size_t i = (size_t)b * nchan + c;
+        if (prior && prior[i]) cell[(size_t)c * nblk + b] = 1;
+        mask[i] = cell[(size_t)c * nblk + b];
+      }
+  });
+  const double code_max = fil->nbits == 8 ? 255.0 : 65535.0;
+  rfi_over_channels(nchan, nblk, [&](uint32_t c0, uint32_t c1) {                   // step 8
+    POST_NO_CONTRACT
+    std::vector<double> d;
+    try { d.resize(nblk); } catch (const std::bad_alloc&) { oom = true; return; }
+    for (uint32_t c = c0; c < c1; ++c) {
+      size_t n = 0, nmask = 0;
+      for (uint32_t b = 0; b < nblk; ++b) {
+        if (!cell[(size_t)c * nblk + b]) d[n++] = mean[(size_t)c * nblk + b];
+        else ++nmask;
+      }
+      // (no masked cell: the cells of m_c, the same median; none left: m_c as well)
+      double r = (n && nmask) ? rfi_median(d.data(), n) : m_c[c];
+      if (!std::isfinite(r)) r = 0.0;
+      if (integer_rows) {
+        r = floor(r + 0.5);
+        if (r < 0.0) r = 0.0;
+        if (r > code_max) r = code_max;
+      }
+      repl[c] = r;
+    }
+  });
+  if (oom) return e.fail(FRBCH_E_NOMEM, "host memory for the mask decision");
+  } catch (const std::bad_alloc&) {
+    return e.fail(FRBCH_E_NOMEM, "host memory for the mask decision");
+  }
+  return FRBCH_OK;
+}
+
+extern "C" int frbch_rfi_apply_device(const frbch_fil_desc* fil, void* d_rows, uint64_t nrows, const frbch_rfi_params* par,
+                                      const uint8_t* d_mask, const double* d_repl, int device, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  uint32_t nblk = 0;
+  int rc = rfi_check(fil, nrows, par, &nblk, e);
+  if (rc) return rc;
+  if (!d_rows || !d_mask || !d_repl) return e.fail(FRBCH_E_ARG, "null argument");
+  if (device < 0 || device >= dev_count()) return e.fail(FRBCH_E_DEVICE, "no such GPU (there is no CPU fallback)");
+  DeviceGuard dg(device);
+  dev_stream_t s = 0;
+  if (dev_stream_create(&s) != 0) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  auto cleanup = [&]() { dev_stream_destroy(s); };
+#define POST_DEV(expr, what) do { if ((expr) != 0) { cleanup(); return e.fail(FRBCH_E_DEVICE, std::string(what) + ": " + dev_last_error_string()); } } while (0)
+  RfiParams p = rfi_params(fil, d_rows, nrows, par, nblk);
+  p.mask = d_mask;
+  p.repl = d_repl;
+  for (uint32_t b0 = 0; b0 < nblk; b0 += kRfiGridBlocks) {
+    p.blk0 = b0;
+    DEV_LAUNCH(frbch_post_rfi_apply, (fil->nchan + 255) / 256, std::min(kRfiGridBlocks, nblk - b0), 256, 0, s, p);
+    POST_DEV(dev_check_launch(), "launch apply");
+  }
+  POST_DEV(dev_sync(s), "sync");
+#undef POST_DEV
+  cleanup();
+  return FRBCH_OK;
+}
+
+extern "C" int frbch_rfi_apply_host(const frbch_fil_desc* fil, void* rows, uint64_t nrows, const frbch_rfi_params* par,
+                                    const uint8_t* mask, const double* repl, int device, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  uint32_t nblk = 0;
+  int rc = rfi_check(fil, nrows, par, &nblk, e);
+  if (rc) return rc;
+  if (!rows || !mask || !repl) return e.fail(FRBCH_E_ARG, "null argument");
+  if (device < 0 || device >= dev_count()) return e.fail(FRBCH_E_DEVICE, "no such GPU (there is no CPU fallback)");
+  DeviceGuard dg(device);
+  const size_t in_bytes = (size_t)nrows * fil->nifs * fil->nchan * (size_t)(fil->nbits / 8);
+  const size_t ncell = (size_t)nblk * fil->nchan;
+  void *d_rows = nullptr, *d_mask = nullptr, *d_repl = nullptr;
+  if (dev_malloc(&d_rows, in_bytes) != 0 || dev_malloc(&d_mask, ncell) != 0 || dev_malloc(&d_repl, fil->nchan * sizeof(double)) != 0)
+    rc = e.fail(FRBCH_E_NOMEM, "device memory for the rows");
+  if (!rc && (dev_h2d(d_rows, rows, in_bytes, 0) != 0 || dev_h2d(d_mask, mask, ncell, 0) != 0 ||
+              dev_h2d(d_repl, repl, fil->nchan * sizeof(double), 0) != 0 || dev_sync(0) != 0))
+    rc = e.fail(FRBCH_E_DEVICE, "upload rows");
+  if (!rc) rc = frbch_rfi_apply_device(fil, d_rows, nrows, par, (const uint8_t*)d_mask, (const double*)d_repl, device, err, err_cap);
+  if (!rc && (dev_d2h(rows, d_rows, in_bytes, 0) != 0 || dev_sync(0) != 0)) rc = e.fail(FRBCH_E_DEVICE, "download rows");
+  dev_free(d_rows); dev_free(d_mask); dev_free(d_repl);
+  return rc;
+}
+
+extern "C" int frbch_rfi_clean_device(const frbch_fil_desc* fil, void* d_rows, uint64_t nrows, const frbch_rfi_params* par,
+                                      const uint8_t* zap, int device, uint8_t* mask, double* repl, uint8_t* chan_flag,
+                                      uint8_t* blk_flag, uint32_t* kernel_used, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  uint32_t nblk = 0;
+  int rc = rfi_check(fil, nrows, par, &nblk, e);
+  if (rc) return rc;
+  if (!d_rows || !mask || !repl || !chan_flag || !blk_flag) return e.fail(FRBCH_E_ARG, "null argument");
+  if (device < 0 || device >= dev_count()) return e.fail(FRBCH_E_DEVICE, "no such GPU (there is no CPU fallback)");
+  DeviceGuard dg(device);
+  const size_t ncell = (size_t)nblk * fil->nchan;
+  void *d_stats = nullptr, *d_mask = nullptr, *d_repl = nullptr;
+  std::vector<uint64_t> stats(ncell * 2);                        // (S, Q): uint64 or double, 16 bytes a cell either way
+  if (dev_malloc(&d_stats, ncell * 16) != 0) rc = e.fail(FRBCH_E_NOMEM, "device memory for the statistics");
+  if (!rc) rc = frbch_rfi_stats_device(fil, d_rows, nrows, par, device, d_stats, kernel_used, err, err_cap);
+  if (!rc && (dev_d2h(stats.data(), d_stats, ncell * 16, 0) != 0 || dev_sync(0) != 0)) rc = e.fail(FRBCH_E_DEVICE, "download statistics");
+  if (!rc) rc = frbch_rfi_mask(fil, stats.data(), nblk, nrows, par, zap, nullptr, mask, repl, chan_flag, blk_flag, err, err_cap);
+  if (!rc && std::any_of(mask, mask + ncell, [](uint8_t m) { return m != 0; })) {      // (nothing masked: nothing to write)
+    if (dev_malloc(&d_mask, ncell) != 0 || dev_malloc(&d_repl, fil->nchan * sizeof(double)) != 0)
+      rc = e.fail(FRBCH_E_NOMEM, "device memory for the mask");
+    if (!rc && (dev_h2d(d_mask, mask, ncell, 0) != 0 || dev_h2d(d_repl, repl, fil->nchan * sizeof(double), 0) != 0 || dev_sync(0) != 0))
+      rc = e.fail(FRBCH_E_DEVICE, "upload mask");
+    if (!rc) rc = frbch_rfi_apply_device(fil, d_rows, nrows, par, (const uint8_t*)d_mask, (const double*)d_repl, device, err, err_cap);
+  }
+  dev_free(d_stats); dev_free(d_mask); dev_free(d_repl);
+  return rc;
+}
+
+extern "C" int frbch_rfi_clean_host(const frbch_fil_desc* fil, void* rows, uint64_t nrows, const frbch_rfi_params* par,
+                                    const uint8_t* zap, int device, uint8_t* mask, double* repl, uint8_t* chan_flag,
+                                    uint8_t* blk_flag, uint32_t* kernel_used, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  uint32_t nblk = 0;
+  int rc = rfi_check(fil, nrows, par, &nblk, e);
+  if (rc) return rc;
+  if (!rows || !mask || !repl || !chan_flag || !blk_flag) return e.fail(FRBCH_E_ARG, "null argument");
+  if (device < 0 || device >= dev_count()) return e.fail(FRBCH_E_DEVICE, "no such GPU (there is no CPU fallback)");
+  DeviceGuard dg(device);
+  const size_t in_bytes = (size_t)nrows * fil->nifs * fil->nchan * (size_t)(fil->nbits / 8);
+  void* d_rows = nullptr;
+  if (dev_malloc(&d_rows, in_bytes) != 0) rc = e.fail(FRBCH_E_NOMEM, "device memory for the rows");
+  if (!rc && (dev_h2d(d_rows, rows, in_bytes, 0) != 0 || dev_sync(0) != 0)) rc = e.fail(FRBCH_E_DEVICE, "upload rows");
+  if (!rc) rc = frbch_rfi_clean_device(fil, d_rows, nrows, par, zap, device, mask, repl, chan_flag, blk_flag, kernel_used, err, err_cap);
+  if (!rc && (dev_d2h(rows, d_rows, in_bytes, 0) != 0 || dev_sync(0) != 0)) rc = e.fail(FRBCH_E_DEVICE, "download rows");
+  dev_free(d_rows);
   return rc;
 }
 

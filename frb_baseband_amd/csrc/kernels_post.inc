@@ -582,3 +582,95 @@ KERNEL(frbch_post_cutout, CutParams) {
     }
   }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Interference (frbch_rfi_*; include/frbch.h states the arithmetic): per (block of rows, channel) the sums S = sum x and
+// Q = sum x x of one product, and the in-place replacement of the masked cells.
+// ---------------------------------------------------------------------------------------------------------------------
+struct RfiParams {
+  uint8_t* rows;               // [nrows][nifs][nchan] samples of `nbits`; product `prod` is used (apply writes it)
+  uint64_t nrows;
+  int nchan, nifs, nbits, prod;
+  uint32_t block_rows, nblk;
+  uint32_t blk0, pad;          // block of workgroup row 0 (a launch holds at most 65535 blocks)
+  unsigned long long* stats_i; // [nblk][nchan][2] (S, Q), integer rows
+  double* stats_f;             // the same for float rows
+  const uint8_t* mask;         // [nblk][nchan], apply
+  const double* repl;          // [nchan], apply
+  // ---- fast kernel (kernels_post_fast.inc) ----
+  int tile_bytes, ntile;       // bytes of a row a workgroup owns (a power of two, 64 .. 1024); tiles per row
+};
+
+// The generic form, the correctness anchor and the fallback (and the only kernel for float rows): grid (ceil(nchan / 256),
+// nblk), one thread per channel, rows ascending.
+KERNEL(frbch_post_rfi_stats, RfiParams) {
+  K_PROLOGUE;
+  (void)smem;
+  PHASE {
+    POST_NO_CONTRACT
+    const int c = bx * nthr + tid;
+    const uint64_t b = (uint64_t)p.blk0 + (uint64_t)by;
+    if (c < p.nchan) {
+      const uint64_t r0 = b * p.block_rows;
+      const uint64_t r1 = r0 + p.block_rows < p.nrows ? r0 + p.block_rows : p.nrows;
+      const uint64_t pitch = (uint64_t)p.nifs * (uint64_t)p.nchan;
+      const uint64_t first = (uint64_t)p.prod * (uint64_t)p.nchan + (uint64_t)c;
+      const size_t o = ((size_t)b * p.nchan + c) * 2;
+      if (p.nbits == 32) {
+        const float* x = (const float*)p.rows;
+        double s = 0.0, q = 0.0;
+        for (uint64_t t = r0; t < r1; ++t) {
+          const double v = (double)x[t * pitch + first];
+          const double vv = v * v;
+          s = s + v;
+          q = q + vv;
+        }
+        p.stats_f[o] = s;
+        p.stats_f[o + 1] = q;
+      } else {
+        unsigned long long s = 0, q = 0;
+        for (uint64_t t = r0; t < r1; ++t) {
+          const unsigned long long v = p.nbits == 8 ? (unsigned long long)p.rows[t * pitch + first]
+                                                    : (unsigned long long)((const uint16_t*)p.rows)[t * pitch + first];
+          s += v;
+          q += v * v;
+        }
+        p.stats_i[o] = s;
+        p.stats_i[o + 1] = q;
+      }
+    }
+  }
+}
+
+// Every sample of a masked cell becomes repl[c]; nothing else is written.  grid (ceil(nchan / 256), nblk), one thread per
+// cell: a thread whose cell is unmasked returns after reading the mask, so a workgroup without a masked cell costs one read.
+KERNEL(frbch_post_rfi_apply, RfiParams) {
+  K_PROLOGUE;
+  (void)smem;
+  PHASE {
+    const int c = bx * nthr + tid;
+    const uint64_t b = (uint64_t)p.blk0 + (uint64_t)by;
+    if (c < p.nchan && p.mask[(size_t)b * p.nchan + c]) {
+      const uint64_t r0 = b * p.block_rows;
+      const uint64_t r1 = r0 + p.block_rows < p.nrows ? r0 + p.block_rows : p.nrows;
+      const uint64_t pitch = (uint64_t)p.nifs * (uint64_t)p.nchan;
+      const uint64_t first = (uint64_t)p.prod * (uint64_t)p.nchan + (uint64_t)c;
+      double r = p.repl[c];
+      if (p.nbits != 32) {                        // a caller's value outside the code range (or a NaN) is clamped, not converted
+        const double top = p.nbits == 8 ? 255.0 : 65535.0;
+        if (!(r >= 0.0)) r = 0.0;
+        if (r > top) r = top;
+      }
+      if (p.nbits == 8) {
+        const uint8_t v = (uint8_t)r;
+        for (uint64_t t = r0; t < r1; ++t) p.rows[t * pitch + first] = v;
+      } else if (p.nbits == 16) {
+        const uint16_t v = (uint16_t)r;
+        for (uint64_t t = r0; t < r1; ++t) ((uint16_t*)p.rows)[t * pitch + first] = v;
+      } else {
+        const float v = (float)r;
+        for (uint64_t t = r0; t < r1; ++t) ((float*)p.rows)[t * pitch + first] = v;
+      }
+    }
+  }
+}

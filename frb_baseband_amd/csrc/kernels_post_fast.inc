@@ -390,4 +390,98 @@ __global__ void __launch_bounds__(kCutTT) frbch_post_cutout_lds(CutParams p) {
     p.hits[o] = n;
   }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Block statistics for the interference mask (HIP only; frbch_post_rfi_stats of kernels_post.inc stays the emulable form,
+// the fallback and the kernel of float rows).  The anchor reads one sample per lane per row with lanes a channel apart --
+// the access pattern that made the per-sample dedispersion slow.  Here a workgroup of 256 threads owns one block of rows
+// and one tile of `tile_bytes` of the row (the host takes the largest of 1024 .. 64 that divides the row piece).  The
+// tile_bytes / 16 lanes of a row piece sit side by side and take 16 bytes each (16 / 8 channels of 8- / 16-bit samples),
+// coalesced across the tile; the 256 / that many lane groups take interleaved rows (group g: rows g, g + G, ...), with
+// kRfiUnroll 16-byte non-temporal loads in flight per lane.  Sums stay in registers: uint32 for S, and for Q at 8 bit,
+// over runs of kRfiRun rows per lane (4096 x 65025 and 4096 x 65535 < 2^32); Q at 16 bit is uint64 throughout.  After
+// every run the partials of the G lane groups go through the LDS once (word k L + l of group g: consecutive lanes on
+// consecutive banks, both ways) and ONE thread per channel adds them up in uint64 and stores -- or, for a block of more
+// than G kRfiRun rows, adds to what it stored itself a run earlier: every (block, channel) is written by exactly one
+// thread, there are no global atomics.  Integer sums are exact in any order: the result equals the anchor's to the bit.
+constexpr int kRfiThreads = 256, kRfiUnroll = 4, kRfiRun = 4096;
+
+template <int BPV>
+__global__ void __launch_bounds__(kRfiThreads) frbch_post_rfi_stats_fast(RfiParams p) {
+  constexpr int VPL = 16 / BPV;                                           // values per lane (one 16-byte piece)
+  constexpr int NRED = kRfiThreads * VPL;                                 // partial sums of a workgroup
+  __shared__ uint32_t red_s[NRED];
+  __shared__ unsigned long long red_q[BPV == 1 ? NRED / 2 : NRED];       // 8 bit: NRED uint32
+  const int tid = threadIdx.x;
+  const int L = p.tile_bytes / 16, G = kRfiThreads / L, nch = p.tile_bytes / BPV;
+  const int l = tid & (L - 1), g = tid / L;
+  const int tile = blockIdx.x;
+  const uint64_t b = (uint64_t)p.blk0 + blockIdx.y;
+  const uint64_t r0 = b * p.block_rows;
+  const uint64_t r1 = r0 + p.block_rows < p.nrows ? r0 + p.block_rows : p.nrows;
+  const size_t stride = (size_t)p.nifs * p.nchan * BPV;                   // bytes between rows of the file
+  const unsigned char* src = p.rows + (size_t)p.prod * p.nchan * BPV + (size_t)tile * p.tile_bytes + (size_t)l * 16;
+  unsigned long long* dst = p.stats_i + ((size_t)b * p.nchan + (size_t)tile * nch) * 2;
+  const uint64_t span = (uint64_t)G * kRfiRun;
+  for (uint64_t s0 = r0; s0 < r1; s0 += span) {
+    const uint64_t s1 = s0 + span < r1 ? s0 + span : r1;
+    uint32_t as[VPL];
+    uint32_t aq8[BPV == 1 ? VPL : 1];
+    unsigned long long aq16[BPV == 2 ? VPL : 1];
+#pragma unroll
+    for (int k = 0; k < VPL; ++k) {
+      as[k] = 0u;
+      if constexpr (BPV == 1) aq8[k] = 0u; else aq16[k] = 0ull;
+    }
+    for (uint64_t t = s0 + (uint64_t)g; t < s1; t += (uint64_t)G * kRfiUnroll) {
+      uint32_t w[kRfiUnroll][4];
+#pragma unroll
+      for (int u = 0; u < kRfiUnroll; ++u) {
+        const uint64_t tu = t + (uint64_t)u * G;
+        if (tu < s1) {
+          const frbch_nf4 v = __builtin_nontemporal_load(reinterpret_cast<const frbch_nf4*>(src + tu * stride));
+          w[u][0] = __float_as_uint(v.x); w[u][1] = __float_as_uint(v.y); w[u][2] = __float_as_uint(v.z); w[u][3] = __float_as_uint(v.w);
+        } else {
+          w[u][0] = w[u][1] = w[u][2] = w[u][3] = 0u;                     // adds nothing
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kRfiUnroll; ++u)
+#pragma unroll
+        for (int k = 0; k < VPL; ++k) {
+          if constexpr (BPV == 1) {
+            const uint32_t x = (w[u][k >> 2] >> (8 * (k & 3))) & 0xFFu;
+            as[k] += x;
+            aq8[k] += x * x;
+          } else {
+            const uint32_t x = (w[u][k >> 1] >> (16 * (k & 1))) & 0xFFFFu;
+            as[k] += x;
+            aq16[k] += (unsigned long long)(x * x);
+          }
+        }
+    }
+    __syncthreads();                                                      // the previous run's partials are consumed
+#pragma unroll
+    for (int k = 0; k < VPL; ++k) {
+      const int i = g * nch + k * L + l;
+      red_s[i] = as[k];
+      if constexpr (BPV == 1) reinterpret_cast<uint32_t*>(red_q)[i] = aq8[k]; else red_q[i] = aq16[k];
+    }
+    __syncthreads();
+    for (int pos = tid; pos < nch; pos += kRfiThreads) {                  // word pos = k L + l holds channel l VPL + k
+      unsigned long long S = 0, Q = 0;
+      for (int gg = 0; gg < G; ++gg) {
+        S += red_s[gg * nch + pos];
+        if constexpr (BPV == 1) Q += reinterpret_cast<const uint32_t*>(red_q)[gg * nch + pos]; else Q += red_q[gg * nch + pos];
+      }
+      const int ch = (pos & (L - 1)) * VPL + pos / L;
+      if (s0 != r0) {
+        S += dst[(size_t)ch * 2];
+        Q += dst[(size_t)ch * 2 + 1];
+      }
+      dst[(size_t)ch * 2] = S;
+      dst[(size_t)ch * 2 + 1] = Q;
+    }
+  }
+}
 }  // namespace fast

@@ -13,6 +13,9 @@ reference's `dspsr -E <par> ... <IFall.fil>` stage) of SIGPROC filterbank files,
   are folded in ALL products in one pass (``fold_all``), optionally with the TEMPO polyco predictor that tempo / tempo2
   make from the .par file (``read_polyco``: barycentric, binary and position terms, as dspsr folds) or a constant
   Doppler factor, and give the 2x2 full-polarisation plot of base2fil.sh:481-491 as well.
+* ``rfifind_fil`` / ``clean`` flag interference per (block of rows, channel) from block statistics taken on the GPU, write
+  and read the flag file the reference carries to Heimdall and FETCH (create_config.py:54-56 ``-F/--flag``), and replace the
+  masked samples: ``search_fil`` and ``candidates_fil`` take ``flag_file`` / ``rfi`` and then work on the cleaned rows.
 There is no CPU fallback: the sums run in libfrbch.so on a gfx950 device.
 """
 from __future__ import annotations
@@ -146,6 +149,255 @@ def prepdata_gpu(filterbankfile, dm1, zerodm=True, clip=5, dm2=0, dmstep=1.0, nc
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# interference: block statistics, the mask, the flag file, cleaned rows
+# ------------------------------------------------------------------------------------------------------------------
+RFI_DEFAULTS = dict(block_rows=1024, t_cell=5.0, t_chan=5.0, chan_frac=0.3, block_frac=0.3)
+
+
+def rfi_params(params=None) -> _lib.FrbchRfiParams:
+    """``RFI_DEFAULTS`` overridden by the dict ``params`` (``True`` / ``None``: the defaults) as the library's struct"""
+    if isinstance(params, _lib.FrbchRfiParams):
+        return params
+    kw = dict(RFI_DEFAULTS)
+    if isinstance(params, dict):
+        unknown = set(params) - set(kw)
+        if unknown:
+            raise InputError("unknown flagging parameters: " + ", ".join(sorted(unknown)))
+        kw.update(params)
+    if not 0 <= int(kw["block_rows"]) < 1 << 32:
+        raise InputError("block_rows must be a non-negative 32-bit integer")
+    p = _lib.FrbchRfiParams()
+    p.size = C.sizeof(_lib.FrbchRfiParams)
+    p.block_rows = int(kw["block_rows"])
+    p.t_cell, p.t_chan, p.chan_frac, p.block_frac = (float(kw[k]) for k in ("t_cell", "t_chan", "chan_frac", "block_frac"))
+    return p
+
+
+def read_flag_file(path: str, nchan: int) -> np.ndarray:
+    """Flag file -> bool [nchan], True = flagged.  Tokens separated by whitespace, commas or newlines; a token is a channel
+    index ``a`` or an inclusive range ``a:b`` / ``a-b``, in the FILE's channel order (index 0 = fch1); ``#`` starts a
+    comment.  The reference only passes the path on (base2fil.sh:425-432): the format Heimdall and FETCH take at a given
+    site is not pinned by it -- this function and ``write_flag_file`` are the two to adapt."""
+    flags = np.zeros(nchan, dtype=bool)
+    with open(path) as f:
+        for line in f:
+            for tok in line.split("#", 1)[0].replace(",", " ").split():
+                parts = tok.replace("-", ":").split(":")
+                try:
+                    a, b = (int(parts[0]), int(parts[-1])) if len(parts) in (1, 2) else (None, None)
+                except ValueError:
+                    a = b = None
+                if a is None or a > b:
+                    raise InputError(f"{path}: bad token '{tok}' (a channel index a, or a range a:b / a-b)")
+                if b >= nchan:
+                    raise InputError(f"{path}: token '{tok}' names a channel outside 0..{nchan - 1}")
+                flags[a: b + 1] = True
+    return flags
+
+
+def write_flag_file(path: str, chan_flag) -> None:
+    """the wholly flagged channels as ``a`` / ``a:b`` tokens, one per line, in the format ``read_flag_file`` reads"""
+    flags = np.asarray(chan_flag).astype(bool)
+    edges = np.flatnonzero(np.diff(np.concatenate([[0], flags.astype(np.int8), [0]])))
+    with open(path, "w") as f:
+        f.write("# flagged channels (file order, inclusive ranges a:b): %d of %d\n" % (int(flags.sum()), flags.size))
+        for a, b in zip(edges[0::2], edges[1::2] - 1):
+            f.write("%d\n" % a if a == b else "%d:%d\n" % (a, b))
+
+
+def _rows3(rows, hdr: dict) -> np.ndarray:
+    """rows as a C-contiguous [nrows][nifs][nchans] array of the header's sample type"""
+    rows = np.ascontiguousarray(rows)
+    nifs, nchan = hdr.get("nifs", 1), hdr["nchans"]
+    if hdr["nbits"] not in (8, 16, 32) or rows.dtype.itemsize * 8 != hdr["nbits"] or rows.size == 0 or rows.size % (nifs * nchan):
+        raise InputError("the rows do not match the header's nbits / nchans / nifs (8-, 16-bit or float32 rows)")
+    return rows.reshape(-1, nifs, nchan)
+
+
+def _zap_array(zap, nchan: int):
+    """``zap`` as the library's uint8 [nchan] mask.  A bool or uint8 array of shape [nchan] IS a mask (non-zero = flagged;
+    what this function returns is one, so a second pass changes nothing); anything else is a list of channel indices."""
+    if zap is None:
+        return None
+    z = np.asarray(zap)
+    if z.dtype in (np.dtype(bool), np.dtype(np.uint8)) and z.shape == (nchan,):
+        return np.ascontiguousarray(z != 0, dtype=np.uint8)
+    if z.size and z.dtype.kind not in "iu":
+        raise InputError("zap: a bool / uint8 mask of nchans entries, or a list of integer channel indices")
+    idx = z.astype(np.int64).ravel()
+    if idx.size and (idx.min() < 0 or idx.max() >= nchan):
+        raise InputError(f"zap: a channel outside 0..{nchan - 1}")
+    out = np.zeros(nchan, dtype=np.uint8)
+    out[idx] = 1
+    return out
+
+
+def rfi_stats(rows, hdr: dict, params=None, product: int = 0, device: int = 0, lib=None, info: dict | None = None) -> np.ndarray:
+    """Block statistics of one product (frbch_rfi_stats_host) -> [nblk][nchan][2] = (sum x, sum x^2): uint64 for integer
+    rows, float64 for float rows.  ``info['kernel_used']``: 1 = the fast kernel, 0 = the generic one."""
+    lib = lib or _lib.load()
+    x = _rows3(rows, hdr)
+    par = rfi_params(params)
+    desc = fil_desc(hdr, product)
+    nblk = lib.frbch_rfi_nblk(x.shape[0], par.block_rows)
+    if nblk <= 0:
+        raise InputError("block_rows must be 1..2^20")
+    stats = np.zeros((nblk, hdr["nchans"], 2), dtype=np.float64 if hdr["nbits"] == 32 else np.uint64)
+    used = C.c_uint32(0)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_rfi_stats_host(C.byref(desc), x.ctypes.data, x.shape[0], C.byref(par), device, stats.ctypes.data, C.byref(used),
+                                    err, len(err)), err)
+    if info is not None:
+        info["kernel_used"] = used.value
+    return stats
+
+
+def rfi_mask(stats, hdr: dict, nrows: int, params=None, zap=None, prior=None, product: int = 0, lib=None) -> dict:
+    """The mask decision (frbch_rfi_mask, host only; include/frbch.h states the rule) -> dict(mask uint8 [nblk][nchan],
+    repl float64 [nchan], chan_flag bool [nchan], blk_flag bool [nblk])."""
+    lib = lib or _lib.load()
+    par = rfi_params(params)
+    desc = fil_desc(hdr, product)
+    nchan = hdr["nchans"]
+    st = np.ascontiguousarray(stats, dtype=np.float64 if hdr["nbits"] == 32 else np.uint64)
+    if st.ndim != 3 or st.shape[1:] != (nchan, 2):
+        raise InputError("stats must be [nblk][nchans][2]")
+    nblk = st.shape[0]
+    z = _zap_array(zap, nchan)
+    pr = None if prior is None else np.ascontiguousarray(prior, dtype=np.uint8)
+    if pr is not None and pr.shape != (nblk, nchan):
+        raise InputError("prior must be [nblk][nchans]")
+    mask, repl = np.zeros((nblk, nchan), np.uint8), np.zeros(nchan, np.float64)
+    cf, bf = np.zeros(nchan, np.uint8), np.zeros(nblk, np.uint8)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_rfi_mask(C.byref(desc), st.ctypes.data, nblk, int(nrows), C.byref(par), None if z is None else z.ctypes.data,
+                              None if pr is None else pr.ctypes.data, mask.ctypes.data, repl.ctypes.data, cf.ctypes.data,
+                              bf.ctypes.data, err, len(err)), err)
+    return dict(mask=mask, repl=repl, chan_flag=cf.astype(bool), blk_flag=bf.astype(bool))
+
+
+def _clean_from_stats(lib, x, hdr, par, stats, prods, z, repl, device):
+    """The two passes of ``clean`` on statistics already taken: the mask of every listed product, their union, then
+    frbch_rfi_mask per product with ``prior`` = the union and frbch_rfi_apply_host on ``x`` in place; ``repl[p]`` is filled.
+    -> (mask, chan_flag, blk_flag)"""
+    err = C.create_string_buffer(512)
+    first = [rfi_mask(st, hdr, x.shape[0], par, zap=z, product=p, lib=lib) for st, p in zip(stats, prods)]
+    mask = np.bitwise_or.reduce([r["mask"] for r in first])
+    cf = np.logical_or.reduce([r["chan_flag"] for r in first])
+    bf = np.logical_or.reduce([r["blk_flag"] for r in first])
+    for st, p, one in zip(stats, prods, first):
+        r = one if len(prods) == 1 else rfi_mask(st, hdr, x.shape[0], par, zap=z, prior=mask, product=p, lib=lib)
+        repl[p] = r["repl"]
+        desc = fil_desc(hdr, p)
+        _check(lib.frbch_rfi_apply_host(C.byref(desc), x.ctypes.data, x.shape[0], C.byref(par), mask.ctypes.data,
+                                        repl[p].ctypes.data, device, err, len(err)), err)
+    return mask, cf, bf
+
+
+def clean(rows, hdr: dict, params=None, zap=None, device: int = 0, lib=None, info: dict | None = None, products=None):
+    """Flag and replace -> (cleaned copy of the rows, dict(mask [nblk][nchan], repl [nifs][nchan], chan_flag, blk_flag)).
+    One product (``nifs = 1``, or ``products = [p]``): one frbch_rfi_clean_host call.  Several: pass one takes the mask of
+    every product, the masks are ORed, pass two asks frbch_rfi_mask again per product with ``prior`` = the union -- all
+    products are cleaned in the same cells, each with its own replacement values (frbch_rfi_apply_host per product).
+    Products not listed keep their bytes.  ``info['kernel_used']``: the statistics kernel (the smallest over the products)."""
+    lib = lib or _lib.load()
+    x = _rows3(rows, hdr).copy()
+    par = rfi_params(params)
+    nifs, nchan = x.shape[1], x.shape[2]
+    prods = list(range(nifs)) if products is None else [int(p) for p in products]
+    z = _zap_array(zap, nchan)
+    err = C.create_string_buffer(512)
+    repl = np.zeros((nifs, nchan), np.float64)
+    kernels = []
+    if len(prods) == 1:
+        nblk = lib.frbch_rfi_nblk(x.shape[0], par.block_rows)
+        if nblk <= 0:
+            raise InputError("block_rows must be 1..2^20")
+        mask, cf, bf = np.zeros((nblk, nchan), np.uint8), np.zeros(nchan, np.uint8), np.zeros(nblk, np.uint8)
+        used = C.c_uint32(0)
+        desc = fil_desc(hdr, prods[0])
+        _check(lib.frbch_rfi_clean_host(C.byref(desc), x.ctypes.data, x.shape[0], C.byref(par), None if z is None else z.ctypes.data,
+                                        device, mask.ctypes.data, repl[prods[0]].ctypes.data, cf.ctypes.data, bf.ctypes.data,
+                                        C.byref(used), err, len(err)), err)
+        kernels.append(used.value)
+        cf, bf = cf.astype(bool), bf.astype(bool)
+    else:
+        stats = []
+        for p in prods:
+            i = {}
+            stats.append(rfi_stats(x, hdr, par, product=p, device=device, lib=lib, info=i))
+            kernels.append(i["kernel_used"])
+        mask, cf, bf = _clean_from_stats(lib, x, hdr, par, stats, prods, z, repl, device)
+    if info is not None:
+        info["kernel_used"] = min(kernels)
+    return x.reshape(np.shape(rows)), dict(mask=mask, repl=repl, chan_flag=cf, blk_flag=bf)
+
+
+def rfifind_fil(filterbankfile, block_rows=1024, t_cell=5.0, t_chan=5.0, chan_frac=0.3, block_frac=0.3, flag_file=None,
+                write_clean=False, device=0, lib=None, info: dict | None = None):
+    """Flag a filterbank: ``<base>_rfi.npz`` (mask, chan_flag, blk_flag, repl, the block statistics [nifs][nblk][nchan][2] and
+    the parameters), ``<base>.flag`` (the wholly flagged channels, ``write_flag_file``) and, with ``write_clean``,
+    ``<base>_clean.fil`` -- the header bytes unchanged, every product cleaned in the same cells.  ``flag_file``: channels
+    to flag whatever the statistics say.  Returns (list of files written, the result dict of ``clean``)."""
+    lib = lib or _lib.load()
+    fil = sigproc.read_fil(filterbankfile)
+    hdr = fil.header
+    rows = _rows_of(fil)
+    params = dict(block_rows=int(block_rows), t_cell=float(t_cell), t_chan=float(t_chan), chan_frac=float(chan_frac),
+                  block_frac=float(block_frac))
+    zap = read_flag_file(flag_file, hdr["nchans"]) if flag_file else None
+    par = rfi_params(params)
+    nifs, nchan = hdr.get("nifs", 1), hdr["nchans"]
+    cleaned = _rows3(rows, hdr).copy()
+    stats, kernels = [], []
+    for p in range(nifs):                                    # taken once: they go into the .npz and into the decision
+        i = {}
+        stats.append(rfi_stats(cleaned, hdr, par, product=p, device=device, lib=lib, info=i))
+        kernels.append(i["kernel_used"])
+    repl = np.zeros((nifs, nchan), np.float64)
+    mask, cf, bf = _clean_from_stats(lib, cleaned, hdr, par, stats, list(range(nifs)), _zap_array(zap, nchan), repl, device)
+    res = dict(mask=mask, repl=repl, chan_flag=cf, blk_flag=bf)
+    stats = np.stack(stats)
+    if info is not None:
+        info["kernel_used"] = min(kernels)
+    base = filterbankfile.replace(".fil", "")
+    np.savez(base + "_rfi.npz", mask=res["mask"], chan_flag=res["chan_flag"], blk_flag=res["blk_flag"], repl=res["repl"], stats=stats,
+             zap=np.zeros(hdr["nchans"], bool) if zap is None else zap, nrows=rows.shape[0], **params)
+    write_flag_file(base + ".flag", res["chan_flag"])
+    out = [base + "_rfi.npz", base + ".flag"]
+    if write_clean:
+        with open(filterbankfile, "rb") as f:
+            head = f.read(fil.header_bytes)
+        with open(base + "_clean.fil", "wb") as f:
+            f.write(head)
+            f.write(np.ascontiguousarray(cleaned).tobytes())
+        out.append(base + "_clean.fil")
+    return out, res
+
+
+def _read_rows(filterbankfile, flag_file, rfi, device, lib, info, detrend_len=1000):
+    """the file; with ``flag_file`` or ``rfi`` its product-0 rows cleaned once (frbch_rfi_clean_host) in a copy"""
+    fil = sigproc.read_fil(filterbankfile)
+    if flag_file is None and not rfi:
+        return fil
+    hdr = fil.header
+    zap = read_flag_file(flag_file, hdr["nchans"]) if flag_file is not None else None
+    rinfo = {}
+    cleaned, res = clean(_rows_of(fil), hdr, rfi if isinstance(rfi, dict) else None, zap=zap, device=device, lib=lib, info=rinfo,
+                         products=[0])
+    if info is not None:
+        info.update(rfi_kernel_used=rinfo["kernel_used"], rfi_chan_flag=res["chan_flag"], rfi_blk_flag=res["blk_flag"],
+                    rfi_mask=res["mask"], rfi_masked_cells=int(res["mask"].sum()))
+    block_rows = rfi_params(rfi if isinstance(rfi, dict) else None).block_rows
+    if res["blk_flag"].any() and not res["chan_flag"].all() and 2 * block_rows > (detrend_len or 1000):
+        import warnings
+        warnings.warn("%d block(s) of %d rows flagged wholly: each is a flat stretch of every dedispersed series, longer than half a "
+                      "normalisation block of the search (detrend_len = %d), which can then report the noise at the stretch's edges; "
+                      "use shorter blocks, e.g. rfi=dict(block_rows=256)" % (int(res["blk_flag"].sum()), block_rows, detrend_len or 1000))
+    return sigproc.SigprocFile(header=hdr, header_bytes=fil.header_bytes, data=cleaned)
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # single-pulse search
 # ------------------------------------------------------------------------------------------------------------------
 SP_WIDTHS = [1, 2, 3, 4, 6, 9, 14, 20, 30, 45, 70, 100, 150, 220, 300]
@@ -240,13 +492,23 @@ def _series_names(filterbankfile, dm1, dm2, dms):
 
 
 def search_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, zerodm=True, clip=5, threshold=5.0, max_width_s=0.0, detrend_len=1000,
-               write_dat=False, widths=None, device=0, lib=None, info: dict | None = None):
+               write_dat=False, widths=None, device=0, lib=None, info: dict | None = None, flag_file=None, rfi=None):
     """Dedisperse a filterbank over the DMs of ``prepdata_gpu`` and search every series for single pulses in one library
     call (frbch_dedisperse_search_host: the DM x time plane never leaves the GPU unless ``write_dat`` asks for the .dat /
     .inf files, which are then ``prepdata_gpu``'s).  Writes one ``<name>.singlepulse`` per DM, names as ``prepdata_gpu``.
+    ``flag_file`` (channels to flag, ``read_flag_file``) and / or ``rfi`` (``True`` or a dict of ``RFI_DEFAULTS`` keys): the
+    rows are flagged and cleaned once (``clean``, frbch_rfi_clean_host) and the cleaned rows searched; with neither, every
+    file is what it was without them.
     Returns (list of .singlepulse files, candidates of all DMs as a structured array)."""
     lib = lib or _lib.load()
-    fil = sigproc.read_fil(filterbankfile)
+    fil = _read_rows(filterbankfile, flag_file, rfi, device, lib, info, detrend_len)
+    return _search(fil, filterbankfile, dm1, dm2, dmstep, zerodm, clip, threshold, max_width_s, detrend_len, write_dat, widths, device,
+                   lib, info)
+
+
+def _search(fil, filterbankfile, dm1, dm2, dmstep, zerodm, clip, threshold, max_width_s, detrend_len, write_dat, widths, device, lib,
+            info):
+    """``search_fil`` on a file already read (and cleaned, where asked for)"""
     hdr = fil.header
     dms = dm_list(dm1, dm2, dmstep)
     rows = _rows_of(fil)
@@ -386,19 +648,21 @@ def cand_name(base: str, tstart: float, tcand: float, dm: float, snr: float) -> 
 
 def candidates_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, zerodm=True, clip=5, threshold=5.0, max_width_s=0.0, detrend_len=1000,
                    widths=None, dm_gap=2, min_members=1, max_cands=0, nt=256, nf=0, ndm=256, dm_span=None, device=0, lib=None,
-                   info: dict | None = None):
+                   info: dict | None = None, flag_file=None, rfi=None):
     """``search_fil``, then one candidate per pulse: the records are grouped across DMs (``group_candidates``), groups of
     fewer than ``min_members`` records are dropped, the ``max_cands`` strongest kept (0: all), and ONE frbch_cutout_host
     call cuts the two planes of all of them (``cutouts``: several calls only for a list longer than a call takes).  Writes, next to ``search_fil``'s own files (which are unchanged),
     ``<base>.cands.txt`` (one line per kept group) and per group ``<base>_cand_tstart_<mjd>_tcand_<s>_dm_<dm>_snr_<sigma>``
     ``.npz`` (data_freq_time [nt][nf] and data_dm_time [ndm][nt] as means = sums / hits, 0 where hits is 0; the four raw
     planes; the scalars) and ``.png`` (the frequency-time plane above the DM-time plane).
+    ``flag_file`` / ``rfi`` as in ``search_fil``: the search AND the planes then see the cleaned rows (cleaned once; they
+    travel to the device again for the search and for the cut-outs).
     Returns (list of .npz files, kept groups as a structured array)."""
     lib = lib or _lib.load()
     sinfo = {}
-    _files, recs = search_fil(filterbankfile, dm1, dm2=dm2, dmstep=dmstep, zerodm=zerodm, clip=clip, threshold=threshold,
-                              max_width_s=max_width_s, detrend_len=detrend_len, widths=widths, device=device, lib=lib, info=sinfo)
-    fil = sigproc.read_fil(filterbankfile)
+    fil = _read_rows(filterbankfile, flag_file, rfi, device, lib, sinfo, detrend_len)
+    _files, recs = _search(fil, filterbankfile, dm1, dm2, dmstep, zerodm, clip, threshold, max_width_s, detrend_len, False, widths,
+                           device, lib, sinfo)
     hdr = fil.header
     dms = dm_list(dm1, dm2, dmstep)
     groups = group_candidates(recs, hdr, dms, dm_gap=dm_gap, lib=lib)
@@ -814,7 +1078,9 @@ def fold_fil(filterbankfile: str, parfile: str, nbin: int = 0, subint_s: float =
 def main(argv=None):
     """``python -m frb_baseband_amd.post fold <fil> <par> [--polyco FILE] [--doppler X] [--products coherency|stokes] [...]`` / ``... prepdata <fil> --dm <dm> [...]`` /
     ``... search <fil> --dm <dm> [--dm2 --dmstep --threshold --max-width --detrend ...]`` /
-    ``... candidates <fil> --dm <dm> [search options] [--dm-gap --min-members --max-cands --nt --nf --ndm]``: the stages
+    ``... candidates <fil> --dm <dm> [search options] [--dm-gap --min-members --max-cands --nt --nf --ndm]`` /
+    ``... rfifind <fil> [--block-rows --t-cell --t-chan --chan-frac --block-frac --flag FILE --write-clean]``
+    (``search`` and ``candidates`` take ``--flag FILE`` and ``--rfi``): the stages
     as commands, for the places where base2fil.sh / process_vdif.py launch dspsr and prepdata"""
     import argparse
     ap = argparse.ArgumentParser(prog="frb_baseband_amd.post")
@@ -848,6 +1114,8 @@ def main(argv=None):
     q.add_argument("--nozerodm", action="store_false", help="do not subtract the zero-DM series")
     q.add_argument("--clip", type=float, default=5.0)
     q.add_argument("--write-dat", action="store_true", help="also write the .dat / .inf files of prepdata")
+    q.add_argument("--flag", default=None, help="flag file (channels to flag): the rows are cleaned before the search")
+    q.add_argument("--rfi", action="store_true", help="flag interference from block statistics and clean the rows first")
     q.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     k = sub.add_parser("candidates", help="search, group the records across DMs, cut the frequency-time and DM-time planes of every group")
     k.add_argument("fil")
@@ -865,12 +1133,32 @@ def main(argv=None):
     k.add_argument("--nt", type=int, default=256)
     k.add_argument("--nf", type=int, default=0, help="frequency bins (0: the largest divisor of nchans up to 256)")
     k.add_argument("--ndm", type=int, default=256)
+    k.add_argument("--flag", default=None, help="flag file (channels to flag): the rows are cleaned before the search and the cut-outs")
+    k.add_argument("--rfi", action="store_true", help="flag interference from block statistics and clean the rows first")
     k.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
+    r = sub.add_parser("rfifind", help="flag interference per (block of rows, channel): <base>_rfi.npz, <base>.flag, optionally <base>_clean.fil")
+    r.add_argument("fil")
+    r.add_argument("--block-rows", type=int, default=RFI_DEFAULTS["block_rows"], help="rows per block")
+    r.add_argument("--t-cell", type=float, default=RFI_DEFAULTS["t_cell"], help="threshold of a cell's mean and std against its channel")
+    r.add_argument("--t-chan", type=float, default=RFI_DEFAULTS["t_chan"], help="threshold of a channel's std against the band (0: off)")
+    r.add_argument("--chan-frac", type=float, default=RFI_DEFAULTS["chan_frac"], help="flag a channel with more than this fraction of its blocks flagged")
+    r.add_argument("--block-frac", type=float, default=RFI_DEFAULTS["block_frac"], help="flag a block with more than this fraction of its channels flagged")
+    r.add_argument("--flag", default=None, help="flag file: channels to flag whatever the statistics say")
+    r.add_argument("--write-clean", action="store_true", help="also write <base>_clean.fil")
+    r.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     a = ap.parse_args(argv)
-    if a.cmd == "candidates":
+    if a.cmd == "rfifind":
+        files, res = rfifind_fil(a.fil, block_rows=a.block_rows, t_cell=a.t_cell, t_chan=a.t_chan, chan_frac=a.chan_frac,
+                                 block_frac=a.block_frac, flag_file=a.flag, write_clean=a.write_clean, device=a.device)
+        for path in files:
+            print("wrote", path)
+        print("{0} of {1} channels and {2} of {3} blocks flagged wholly, {4} cells masked".format(
+            int(res["chan_flag"].sum()), res["chan_flag"].size, int(res["blk_flag"].sum()), res["blk_flag"].size, int(res["mask"].sum())))
+    elif a.cmd == "candidates":
         files, groups = candidates_fil(a.fil, a.dm, dm2=a.dm2, dmstep=a.dmstep, zerodm=a.nozerodm, clip=a.clip, threshold=a.threshold,
                                        max_width_s=a.max_width, detrend_len=a.detrend, dm_gap=a.dm_gap, min_members=a.min_members,
-                                       max_cands=a.max_cands, nt=a.nt, nf=a.nf, ndm=a.ndm, device=a.device)
+                                       max_cands=a.max_cands, nt=a.nt, nf=a.nf, ndm=a.ndm, device=a.device, flag_file=a.flag,
+                                       rfi=a.rfi or None)
         print("wrote", a.fil.replace(".fil", "") + ".cands.txt")
         for path in files:
             print("wrote", path, "and .png")
@@ -881,7 +1169,8 @@ def main(argv=None):
         print("wrote {0}, {1}.profile.txt, {1}.png; peak bin {2} of {3}".format(ar, a.fil, int(np.argmax(profile)), profile.size))
     elif a.cmd == "search":
         files, cands = search_fil(a.fil, a.dm, dm2=a.dm2, dmstep=a.dmstep, zerodm=a.nozerodm, clip=a.clip, threshold=a.threshold,
-                                  max_width_s=a.max_width, detrend_len=a.detrend, write_dat=a.write_dat, device=a.device)
+                                  max_width_s=a.max_width, detrend_len=a.detrend, write_dat=a.write_dat, device=a.device,
+                                  flag_file=a.flag, rfi=a.rfi or None)
         for path in files:
             print("wrote", path)
         print("{0} candidates above {1} sigma".format(cands.size, a.threshold))

@@ -463,6 +463,77 @@ int frbch_cutout_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrow
 int frbch_cutout_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_cutout_params* par,
                         const frbch_cutout_cand* cands, uint32_t ncand);
 
+/* ---- interference: block statistics, the mask, cleaned rows --------------------------------------
+ * The reference carries a flag file through to Heimdall and FETCH (create_config.py:54-56 `-F/--flag`, frb.conf:50,
+ * base2fil.sh:226,425-432, submit_job.py:117 `<Tel>.flag_<fmin>-<fmax>MHz_<nchan>chan`) and leaves making one to a person.
+ * frbch_rfi_* measure the rows, decide a mask and replace the masked samples IN PLACE: the cleaned rows are ordinary rows,
+ * which every entry point above takes unchanged.  The flagging rule is this library's own, rfifind-like [EXT-UNVERIFIED:
+ * PRESTO is not in the reference tree]; tests/rfi_oracle.py restates it in numpy and every result is reproducible to the bit.
+ *
+ * Blocks.  Block b holds the rows [b block_rows, min((b + 1) block_rows, nrows)), n_b of them: a short last block is an
+ * ordinary block.  nblk = frbch_rfi_nblk(nrows, block_rows) = ceil(nrows / block_rows); < 0: block_rows outside 1..2^20
+ * or nrows = 0.
+ * Statistics of product fil->product: stats[b][c] = {S, Q} = {sum x, sum x x} over the rows of block b, 16 bytes a cell.
+ * Integer rows: two uint64, exact in any order (65535^2 2^20 < 2^53).  Float rows: two doubles, x = (double)sample,
+ * S += x and Q += x * x row by row in ascending order, every operation rounded on its own (no fused multiply-add).
+ *
+ * The mask, frbch_rfi_mask: host only, double precision, every operation rounded on its own.  `median` of n >= 1 values is
+ * 0.5 * (lower middle + upper middle) of the sorted values (the middle one twice when n is odd).
+ *  1. Per cell: mean = S / n_b, var = max(0, Q / n_b - mean * mean), std = sqrt(var).  A cell whose mean or std is not
+ *     finite is BAD: it is flagged and left out of every median.
+ *  2. Per channel, over its non-bad blocks: m_c = median(mean), s_c = median(std), dm_c = 1.4826 * median|mean - m_c|,
+ *     ds_c = 1.4826 * median|std - s_c|.
+ *  3. A non-bad cell is flagged when |mean - m_c| > t_cell * max(dm_c, s_c / sqrt(n_b)) or
+ *     |std - s_c| > t_cell * max(ds_c, s_c / sqrt(2 n_b)): the floors are the sampling scatter of a block's mean and std,
+ *     so that quantised data with a zero MAD does not flag itself.
+ *  4. A channel is flagged wholly when zap[c] != 0, when s_c == 0 (dead), or when it has no non-bad cell.
+ *  5. When t_chan > 0, over the channels step 4 left (at least one): M = median(s_c), D = 1.4826 * median|s_c - M|, and
+ *     channel c of them is flagged wholly when |s_c - M| > t_chan * D.
+ *  6. A channel not yet flagged is flagged wholly when its flagged cells (steps 1 and 3) number more than
+ *     chan_frac * nblk.  Then, over the channels still unflagged, n_u of them: block b is flagged wholly when its flagged
+ *     cells among them number more than block_frac * n_u.
+ *  7. mask[b][c] = cell flag | chan_flag[c] | blk_flag[b] | prior[b][c].  `prior` is ORed into the result only: it enters
+ *     no count and no median.
+ *  8. repl[c] = median of mean[b][c] over the cells with mask = 0; none: m_c; not finite: 0.  Integer rows:
+ *     floor(repl + 0.5), clamped to 0 .. 2^nbits - 1.
+ * Apply: every sample of product fil->product in a cell with mask != 0 becomes repl[c] (float rows: (float)repl[c]; integer
+ * rows: a caller's repl[c] below 0 or not a number is taken as 0, one above the largest code as that code); no
+ * other byte is written, so other products and unmasked cells keep theirs, and a second apply changes nothing.
+ * FRBCH_E_ARG: a wrong `size`, block_rows outside 1..2^20, nrows = 0, nbits not 8 / 16 / 32, product >= nifs, a threshold
+ * or fraction x with !(x >= 0) or infinite, a fraction above 1, nblk other than frbch_rfi_nblk(). */
+typedef struct frbch_rfi_params {
+  uint32_t size, block_rows;           /* = sizeof(frbch_rfi_params); rows per block, 1..2^20                             */
+  double t_cell, t_chan;               /* thresholds of steps 3 and 5; t_chan = 0: no step 5                              */
+  double chan_frac, block_frac;        /* fractions of step 6, 0..1                                                       */
+} frbch_rfi_params;
+long frbch_rfi_nblk(uint64_t nrows, uint32_t block_rows);
+/* Which kernel frbch_rfi_stats_device takes for these arguments (host only, nothing runs): 1 = the fast kernel (8- / 16-bit
+ * rows of whole 64-byte channel tiles, d_rows and the row pitch nifs nchan bytes-per-sample 16-byte aligned), 0 = the
+ * generic one (a thread per channel; the only one for float rows), < 0 = refused; only the ADDRESS of d_rows is examined. */
+int frbch_rfi_stats_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_rfi_params* par);
+/* stats: [nblk][nchan][2] as above; *kernel_used (may be NULL) as frbch_rfi_stats_kernel.  Both kernels give the same bits. */
+int frbch_rfi_stats_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_rfi_params* par,
+                           int device, void* d_stats, uint32_t* kernel_used, char* err, size_t err_cap);
+int frbch_rfi_stats_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_rfi_params* par, int device,
+                         void* stats, uint32_t* kernel_used, char* err, size_t err_cap);
+/* zap [nchan] and prior [nblk][nchan] may be NULL; mask [nblk][nchan] receives 0 / 1, repl [nchan], chan_flag [nchan] and
+ * blk_flag [nblk] the channels and blocks flagged wholly (0 / 1). */
+int frbch_rfi_mask(const frbch_fil_desc* fil, const void* stats, uint32_t nblk, uint64_t nrows, const frbch_rfi_params* par,
+                   const uint8_t* zap, const uint8_t* prior, uint8_t* mask, double* repl, uint8_t* chan_flag,
+                   uint8_t* blk_flag, char* err, size_t err_cap);
+int frbch_rfi_apply_device(const frbch_fil_desc* fil, void* d_rows, uint64_t nrows, const frbch_rfi_params* par,
+                           const uint8_t* d_mask, const double* d_repl, int device, char* err, size_t err_cap);
+int frbch_rfi_apply_host(const frbch_fil_desc* fil, void* rows, uint64_t nrows, const frbch_rfi_params* par,
+                         const uint8_t* mask, const double* repl, int device, char* err, size_t err_cap);
+/* Statistics, mask and apply on resident rows; zap, mask, repl, chan_flag and blk_flag are HOST arrays as in frbch_rfi_mask
+ * (there is no prior).  The _host form uploads the rows, cleans them and downloads them into `rows` again. */
+int frbch_rfi_clean_device(const frbch_fil_desc* fil, void* d_rows, uint64_t nrows, const frbch_rfi_params* par,
+                           const uint8_t* zap, int device, uint8_t* mask, double* repl, uint8_t* chan_flag, uint8_t* blk_flag,
+                           uint32_t* kernel_used, char* err, size_t err_cap);
+int frbch_rfi_clean_host(const frbch_fil_desc* fil, void* rows, uint64_t nrows, const frbch_rfi_params* par,
+                         const uint8_t* zap, int device, uint8_t* mask, double* repl, uint8_t* chan_flag, uint8_t* blk_flag,
+                         uint32_t* kernel_used, char* err, size_t err_cap);
+
 /* ---- in front of the filterbank: the corner turn -------------------------------
  * jive5ab's spif2file splits the recorder's stream -- every W-bit word holds one time sample of ALL channels -- into one
  * 2-channel stream per IF, driven by the recipe strings of spif2file.sh:31-113, e.g. the 16-channel 2-bit mode
