@@ -175,7 +175,7 @@ def timing_run(lib, rows_ptr, rounds=5):
     frequency-time plane); one warm-up of each side first.  rows_ptr: device address of the TIMING_ROWS x 1024 rows."""
     import statistics
     import time
-    from tests.hipmem import DeviceBuffer
+    from tests.hipmem import GuardedBuffer as DeviceBuffer
     cands = timing_cands()
     n, nt, ndm, nf, nchan = cands.size, TIMING_NT, TIMING_NDM, TIMING_NF, TIMING_HDR["nchans"]
     desc = post.fil_desc(TIMING_HDR)
@@ -219,5 +219,7 @@ def timing_run(lib, rows_ptr, rounds=5):
     composed()
     t_cut = statistics.median(cutout() for _ in range(rounds))
     t_dd = statistics.median(composed() for _ in range(rounds))
+    for b in bufs + [d_out]:            # (free() checks the buffer's guards)
+        b.free()
     return {"rows": TIMING_ROWS, "nchan": nchan, "ncand": int(n), "nt": nt, "nf": nf, "ndm": ndm, "tfactor": cands["tfactor"].tolist(),
             "kernel_used": used.value, "cutout_device_median_s": t_cut, "dedisperse_device_x32_median_s": t_dd}

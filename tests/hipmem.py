@@ -1,5 +1,14 @@
-"""Tiny ctypes view of the HIP runtime for tests: device buffers without torch."""
+"""Tiny ctypes view of the HIP runtime for tests: device buffers without torch.
+
+DeviceBuffer is a bare hipMalloc (tools/*.py time with it).  GuardedBuffer is what the suite allocates: the same interface
+with GUARD bytes of a position-dependent pattern on both sides of the interior, an interior that starts as POISON bytes, and
+a checksum of whatever from_numpy uploaded -- so that a store past either end, an output byte that was never written and a
+changed input are all seen.  HostGuardedBuffer is its twin in host memory for the emulator build, whose `_device` entry points
+take host pointers; guarded_for(lib) picks the class by library."""
 import ctypes as C
+import sys
+import weakref
+import zlib
 
 import numpy as np
 
@@ -13,6 +22,7 @@ def hip():
         _hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
         _hip.hipFree.argtypes = [C.c_void_p]
         _hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        _hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
     return _hip
 
 
@@ -60,3 +70,157 @@ class DeviceBuffer:
             self.free()
         except Exception:
             pass
+
+
+# ---- guarded buffers ------------------------------------------------------------------------------------------------------
+GUARD = 1 << 20                 # bytes a side: 16 rows of the widest row of the suite (4096 channels x 4 products x 4 bytes), more
+#                                 than any tile of rows a kernel stores at once; a multiple of every alignment a kernel choice looks at
+POISON = 0xCB                   # float32 -2.67e7, float64 -7.8e58, uint32 3419130827, uint64 1.5e19: no case expects any of them, and
+#                                 a sum accumulated on top of one stays as far off
+_PATTERN = ((7 + 131 * np.arange(GUARD, dtype=np.int64)) & 0xFF).astype(np.uint8)
+_PATTERN.setflags(write=False)
+_LIVE = weakref.WeakSet()       # every guarded buffer not yet freed
+
+
+def check_all_live():
+    """the guards of every live guarded buffer (a failed test's buffers stay alive in its saved traceback: the message names
+    the address and the line that allocated the buffer, so a guard that trips later is traced to its owner)"""
+    for b in list(_LIVE):
+        b.check()
+
+
+def _site():
+    """file:line of the nearest caller outside this module"""
+    f = sys._getframe(1)
+    while f is not None and f.f_code.co_filename == __file__:
+        f = f.f_back
+    return "?" if f is None else "%s:%d" % (f.f_code.co_filename.rsplit("/", 1)[-1], f.f_lineno)
+
+
+class _Guards:
+    """The checking code both twins share.  A subclass provides _peek(offset, n) -> uint8 array and _poke(offset, uint8
+    array), offsets counted from the START OF THE ALLOCATION (the interior begins at GUARD), and sets ptr / nbytes."""
+    crc = None                  # zlib.crc32 of the uploaded bytes (from_numpy / expect), None for an output
+    site = "?"                  # where the buffer was allocated
+
+    def _arm(self):
+        self.site = _site()
+        self._poke(0, _PATTERN)
+        self._poke(GUARD + self.nbytes, _PATTERN)
+        _LIVE.add(self)
+
+    @classmethod
+    def from_numpy(cls, arr: np.ndarray):
+        arr = np.ascontiguousarray(arr)
+        buf = cls(arr.nbytes, poison=False)
+        buf._poke(GUARD, arr.view(np.uint8).reshape(-1))
+        buf.expect(arr)
+        return buf
+
+    def expect(self, arr):
+        """what check(contents=True) holds the interior against from now on: the bytes of `arr`"""
+        self.crc = zlib.crc32(np.ascontiguousarray(arr).view(np.uint8).reshape(-1))
+
+    def __str__(self):
+        return "buffer of %d bytes at 0x%x (allocated at %s)" % (self.nbytes, self.ptr.value or 0, self.site)
+
+    def check(self, contents=False):
+        """both guards against their pattern; contents=True: the interior against the checksum of the upload as well
+        (a buffer that was never uploaded to has none: its guards only)"""
+        if not self.ptr:
+            return
+        for side, at, base in (("below", 0, -GUARD), ("above", GUARD + self.nbytes, self.nbytes)):
+            dirty = np.flatnonzero(self._peek(at, GUARD) != _PATTERN)
+            if dirty.size:
+                raise AssertionError("guard %s a %s overwritten: %d dirty bytes, offsets %d .. %d relative to the buffer's first byte"
+                                     % (side, self, dirty.size, base + int(dirty[0]), base + int(dirty[-1])))
+        if contents and self.crc is not None:
+            now = self._peek(GUARD, self.nbytes)
+            if zlib.crc32(now) != self.crc:
+                raise AssertionError("an input %s was changed (checksum %08x, uploaded %08x)" % (self, zlib.crc32(now), self.crc))
+
+    def to_numpy(self, dtype, count=None) -> np.ndarray:
+        check_all_live()
+        n = self.nbytes if count is None else count * np.dtype(dtype).itemsize
+        return self._peek(GUARD, n).view(dtype)
+
+    def free(self):
+        if self.ptr:
+            try:
+                self.check()
+            finally:
+                _LIVE.discard(self)
+                self._release()
+
+    def __del__(self):
+        try:
+            _LIVE.discard(self)
+            self._release()
+        except Exception:
+            pass
+
+
+class GuardedBuffer(_Guards, DeviceBuffer):
+    """hipMalloc of nbytes + 2 GUARD; `ptr` is the interior, which keeps the alignment hipMalloc gave modulo 1 MiB"""
+
+    def __init__(self, nbytes: int, poison=True):
+        self.ptr = C.c_void_p()
+        self.base = C.c_void_p()
+        self.nbytes = nbytes
+        rc = hip().hipMalloc(C.byref(self.base), nbytes + 2 * GUARD)
+        if rc != 0:
+            raise RuntimeError(f"hipMalloc failed ({rc})")
+        self.ptr = C.c_void_p(self.base.value + GUARD)
+        if poison and nbytes:
+            assert hip().hipMemset(self.ptr, POISON, nbytes) == 0
+        self._arm()
+
+    def _peek(self, offset, n):
+        hip().hipDeviceSynchronize()
+        out = np.empty(n, dtype=np.uint8)
+        if n:
+            assert hip().hipMemcpy(out.ctypes.data, C.c_void_p(self.base.value + offset), n, 2) == 0
+        return out
+
+    def _poke(self, offset, data):
+        data = np.ascontiguousarray(data)
+        if data.nbytes:
+            assert hip().hipMemcpy(C.c_void_p(self.base.value + offset), data.ctypes.data, data.nbytes, 1) == 0
+
+    def _release(self):
+        if self.base:
+            hip().hipFree(self.base)
+        self.base = C.c_void_p()
+        self.ptr = C.c_void_p()
+
+
+class HostGuardedBuffer(_Guards):
+    """the same in host memory, one numpy array: for the emulator build, whose `_device` entry points take host pointers"""
+    ALIGN = 256                                     # what hipMalloc gives at least
+
+    def __init__(self, nbytes: int, poison=True):
+        self.nbytes = nbytes
+        self._mem = np.empty(nbytes + 2 * GUARD + self.ALIGN, dtype=np.uint8)
+        self._at = -self._mem.ctypes.data % self.ALIGN
+        self.base = C.c_void_p(self._mem.ctypes.data + self._at)
+        self.ptr = C.c_void_p(self.base.value + GUARD)
+        if poison:
+            self._mem[self._at + GUARD: self._at + GUARD + nbytes] = POISON
+        self._arm()
+
+    def _peek(self, offset, n):
+        return self._mem[self._at + offset: self._at + offset + n].copy()
+
+    def _poke(self, offset, data):
+        data = np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+        self._mem[self._at + offset: self._at + offset + data.size] = data
+
+    def _release(self):
+        self._mem = None
+        self.base = C.c_void_p()
+        self.ptr = C.c_void_p()
+
+
+def guarded_for(lib):
+    """the guarded buffer class for a library: host memory for the emulator build (tests/emu), device memory otherwise"""
+    return HostGuardedBuffer if "libfrbch_emu" in str(getattr(lib, "_name", "")) else GuardedBuffer

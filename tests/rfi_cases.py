@@ -246,7 +246,7 @@ def timing_run(lib, d_rows, rounds=5):
     frbch_dedisperse_device calls over 64 DMs -> dict"""
     import statistics
     import time
-    from tests.hipmem import DeviceBuffer
+    from tests.hipmem import GuardedBuffer as DeviceBuffer
     desc = post.fil_desc(TIMING_HDR)
     dms = np.asarray(post.dm_list(300.0, 363.0, 1.0), dtype=np.float64)
     nout = lib.frbch_dedisperse_nout(C.byref(desc), TIMING_ROWS, dms.ctypes.data, len(dms))

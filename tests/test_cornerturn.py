@@ -95,7 +95,7 @@ def test_recorder_stream_to_filterbank_without_per_if_files(hip_lib):
     """16-channel recorder stream in HBM -> frbch_cornerturn_device -> frbch_process_device per IF, nothing leaves the
     card in between; config-2 shape for two of the eight IFs, against the oracle"""
     import ctypes as C
-    from tests.hipmem import DeviceBuffer
+    from tests.hipmem import GuardedBuffer as DeviceBuffer
     frames, recipe, per_if = _eight_if_recorder(0.14, 32.0, 1024)
     d_in = DeviceBuffer.from_numpy(frames)
     nfr = frames.size // 8032

@@ -96,7 +96,7 @@ def _tap(lib, payload, dynamic, on_device):
                         dls_cutoff_sigma=dynamic.get("cutoff_sigma", 0.0), dls_threshold=dynamic.get("threshold", 0.0))
     with ch.Channeliser(cfg, lib) as c:
         if on_device:
-            from tests.hipmem import DeviceBuffer
+            from tests.hipmem import GuardedBuffer as DeviceBuffer
             d_raw = DeviceBuffer.from_numpy(raw)
             d_v = DeviceBuffer(2 * nsamp * 4)
             c.unpack_device(d_raw.ptr.value, nfr, 8032, 32, 0, nsamp, 0, d_v.ptr.value, d_v.nbytes)

@@ -15,7 +15,7 @@ import pytest
 from frb_baseband_amd import post, process_vdif as pv, sigproc, synth
 from tests import cutout_cases as cc
 from tests import cutout_oracle as co
-from tests.hipmem import DeviceBuffer, hip
+from tests.hipmem import GuardedBuffer as DeviceBuffer, hip
 from tests.test_cutout import candidates_round_trip
 
 pytestmark = pytest.mark.gpu

@@ -13,7 +13,7 @@ import pytest
 
 from frb_baseband_amd import _lib, post
 from tests import fold_model_oracle as fo
-from tests.hipmem import DeviceBuffer, hip
+from tests.hipmem import GuardedBuffer as DeviceBuffer, hip
 from tests.test_fold_predictor import PAR, as_fil_all, check_equal, model_kw, random_rows
 from tests.test_post import DM0, HDR, P0
 

@@ -15,7 +15,7 @@ from frb_baseband_amd import multi_if, sigproc, synth
 from oracle import frb_oracle as o
 from tests import kernel_table as kt
 from tests import parity_util as pu
-from tests.hipmem import DeviceBuffer
+from tests.hipmem import GuardedBuffer as DeviceBuffer
 from tests.test_kernel_table import library_kernels
 
 pytestmark = pytest.mark.gpu

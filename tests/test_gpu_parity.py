@@ -127,7 +127,7 @@ def test_fil_matches_oracle(hip_lib, bw, nchan, secs, kw):
 def test_power_tap_matches_oracle(hip_lib):
     """float32 power of the fused unpack->FFT->detect stream vs the fp64 oracle (tolerance stated in parity_util)."""
     from frb_baseband_amd import channeliser as ch, synth
-    from tests.hipmem import DeviceBuffer
+    from tests.hipmem import GuardedBuffer as DeviceBuffer
     from oracle import frb_oracle as o
     bw, nchan = 32.0, 1024
     raw = synth.make_vdif(0.14, bw_mhz=bw, nchan=nchan)

@@ -20,7 +20,7 @@ from frb_baseband_amd import channeliser as ch
 from frb_baseband_amd import multi_if, sigproc, synth
 from oracle import frb_oracle as o
 from tests import parity_util as pu
-from tests.hipmem import DeviceBuffer
+from tests.hipmem import GuardedBuffer as DeviceBuffer
 
 pytestmark = pytest.mark.gpu
 

@@ -182,7 +182,7 @@ def test_dm_range_device_time_at_full_size(hip_lib):
     (< 60 ms) and conservation of the total (every output sample is a sum of nchan input samples)"""
     import ctypes as C
     from frb_baseband_amd import _lib
-    from tests.hipmem import DeviceBuffer
+    from tests.hipmem import GuardedBuffer as DeviceBuffer
     rng = np.random.default_rng(11)
     nrows, nchan = 312500, 1024
     data = rng.integers(100, 156, size=(nrows, nchan), dtype=np.uint8)

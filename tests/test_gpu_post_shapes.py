@@ -16,7 +16,7 @@ import pytest
 
 from frb_baseband_amd import post, process_vdif as pv, sigproc, synth
 from tests import post_cases as pc
-from tests.hipmem import DeviceBuffer, hip
+from tests.hipmem import GuardedBuffer as DeviceBuffer, hip
 
 pytestmark = pytest.mark.gpu
 

@@ -16,7 +16,7 @@ import pytest
 from frb_baseband_amd import process_vdif as pv, sigproc, synth
 from tests import rfi_cases as rc
 from tests import rfi_oracle as ro
-from tests.hipmem import DeviceBuffer, hip
+from tests.hipmem import GuardedBuffer as DeviceBuffer, hip
 from tests.test_rfi import same_stats
 
 pytestmark = pytest.mark.gpu

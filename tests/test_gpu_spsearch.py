@@ -15,7 +15,7 @@ from frb_baseband_amd import _lib, post
 from tests import post_cases as pc
 from tests import spsearch_cases as sc
 from tests import spsearch_oracle as so
-from tests.hipmem import DeviceBuffer
+from tests.hipmem import GuardedBuffer as DeviceBuffer
 
 pytestmark = pytest.mark.gpu
 
