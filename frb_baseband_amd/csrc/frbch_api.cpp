@@ -26,6 +26,17 @@ void mark_user_stream(frbch_handle* h, dev_stream_t s) {
   dev_event_record(h->user_ev, s);
   h->user_stream = s;
 }
+// What every device entry point does first with the stream `s` it will queue on (the caller's, or the handle's own for NULL) --
+// the stream-order contract of include/frbch.h, (c): a call on another stream than the one before it waits on the host for that
+// call's work (whatever the new stream is: the handle's own stream is ordered behind nothing else), and `s` continues behind a
+// pending reset.  leave_stream is its twin behind the call's work: the handle's event on `s`, the handle's own stream included --
+// for a NULL-stream call followed by one on a caller's stream this mark is the ONLY edge, so every exit that queued work takes it.
+int enter_stream(frbch_handle* h, dev_stream_t s) {
+  if (h->user_stream && h->user_stream != s) { const int rc = settle_user_stream(h); if (rc) return rc; }
+  join_reset(h, s);
+  return FRBCH_OK;
+}
+void leave_stream(frbch_handle* h, dev_stream_t s) { mark_user_stream(h, s); }
 }  // namespace frbchi
 using namespace frbchi;
 
@@ -203,13 +214,10 @@ extern "C" int frbch_process_device(frbch_handle* h, const void* d_frames, size_
   if (nblocks && !d_out) return FRBCH_E_ARG;
   DeviceGuard dg(h->device);
   dev_stream_t s = stream ? (dev_stream_t)stream : h->stream;
-  if (stream) {
-    if (h->user_stream && h->user_stream != s) { const int rc = settle_user_stream(h); if (rc) return rc; }
-  }
-  join_reset(h, s);
+  { const int rc = enter_stream(h, s); if (rc) return rc; }
   const int rc = engine_feed(h, (const uint8_t*)d_frames, frame_bytes, header_bytes, payload_byte_offset, nblocks,
                              (uint8_t*)d_out, out_cap_bytes, rows_written, s);
-  if (stream) mark_user_stream(h, s);
+  leave_stream(h, s);
   return rc;
 }
 
@@ -218,12 +226,9 @@ extern "C" int frbch_flush_device(frbch_handle* h, void* d_out, size_t out_cap_b
   if (!h || !rows_written) return FRBCH_E_ARG;
   DeviceGuard dg(h->device);
   dev_stream_t s = stream ? (dev_stream_t)stream : h->stream;
-  if (stream) {
-    if (h->user_stream && h->user_stream != s) { const int rc = settle_user_stream(h); if (rc) return rc; }
-  }
-  join_reset(h, s);
+  { const int rc = enter_stream(h, s); if (rc) return rc; }
   const int rc = engine_flush(h, (uint8_t*)d_out, out_cap_bytes, rows_written, s);
-  if (stream) mark_user_stream(h, s);
+  leave_stream(h, s);
   return rc;
 }
 
@@ -286,10 +291,9 @@ extern "C" int frbch_scan_device(frbch_handle* const* ifs, uint32_t nif, const v
     (void)bits;
   }
   chain_end(&ch);
-  // every handle whose own stream is not `s` records the scan's work behind it: a later frbch_reset / get_rescale / set_rescale
-  // of that handle waits for this event, not only for its own (idle) stream -- with stream == NULL that is every IF but the first
-  for (uint32_t i = 0; i < nif; ++i)
-    if (stream || ifs[i] != h0) mark_user_stream(ifs[i], s);
+  // every handle records the scan's work behind it: a later frbch_reset / get_rescale / set_rescale of that handle waits for this
+  // event, not only for its own (idle) stream, and a later call on another stream settles it first (ifs[0] on the NULL stream too)
+  for (uint32_t i = 0; i < nif; ++i) leave_stream(ifs[i], s);
   *rows_written = rows_min == UINT64_MAX ? 0 : rows_min;
   return rc;
 }
@@ -306,10 +310,8 @@ extern "C" int frbch_power_device(frbch_handle* h, const void* d_frames, size_t 
     return fail(h, FRBCH_E_CAPACITY, "power buffer too small");
   DeviceGuard dg(h->device);
   dev_stream_t s = stream ? (dev_stream_t)stream : h->stream;
-  if (stream) {
-    if (h->user_stream && h->user_stream != s) { const int rc = settle_user_stream(h); if (rc) return rc; }
-  }
-  join_reset(h, s);
+  { const int rc = enter_stream(h, s); if (rc) return rc; }
+  int rc = FRBCH_OK;
   for (uint64_t b0 = 0; b0 < nblocks; b0 += pl.maxb) {
     const uint32_t nb = (uint32_t)std::min<uint64_t>(pl.maxb, nblocks - b0);
     KParams p = base_params(h);
@@ -318,16 +320,16 @@ extern "C" int frbch_power_device(frbch_handle* h, const void* d_frames, size_t 
     p.header_bytes = header_bytes;
     p.payload_bytes = frame_bytes - header_bytes;
     p.payload_off = payload_byte_offset + b0 * pl.block_stride_bytes;
-    int rc = launch_front(h, p, nb, s);
-    if (rc) return rc;
+    rc = launch_front(h, p, nb, s);
+    if (rc) break;
     p.out_mode = FRBCH_OUT_FLOAT_POWER;
     p.power_out = d_power;
     p.row0 = b0 * pl.rows_per_block;
     rc = launch_back(h, p, nb, s);
-    if (rc) return rc;
+    if (rc) break;
   }
-  if (stream) mark_user_stream(h, s);
-  return FRBCH_OK;
+  leave_stream(h, s);   // (behind a failing launch as well: the batches before it are queued)
+  return rc;
 }
 
 // the unpack tap: voltages as the filterbank sees them (A4 in isolation)
@@ -346,9 +348,7 @@ extern "C" int frbch_unpack_device(frbch_handle* h, const void* d_frames, size_t
   if (!nsamples) return FRBCH_OK;
   DeviceGuard dg(h->device);
   dev_stream_t s = stream ? (dev_stream_t)stream : h->stream;
-  if (stream) {
-    if (h->user_stream && h->user_stream != s) { const int rc = settle_user_stream(h); if (rc) return rc; }
-  }
+  if (h->user_stream && h->user_stream != s) { const int rc = settle_user_stream(h); if (rc) return rc; }   // (the tap touches no rescale state: no join_reset)
   KParams p = base_params(h);
   p.frames = (const uint8_t*)d_frames;
   p.frame_bytes = frame_bytes;
@@ -358,7 +358,7 @@ extern "C" int frbch_unpack_device(frbch_handle* h, const void* d_frames, size_t
   p.power_out = d_volt;
   p.row0 = nsamples;
   { const int rc = launch_unpack_tap(h, p, nsamples, decoder, s); if (rc) return rc; }
-  if (stream) mark_user_stream(h, s);
+  leave_stream(h, s);
   return FRBCH_OK;
 }
 

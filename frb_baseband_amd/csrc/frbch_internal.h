@@ -323,6 +323,8 @@ void join_reset(frbch_handle* h, dev_stream_t s);
 // ---- frbch_api.cpp --------------------------------------------------------------------------------------------------------------
 int settle_user_stream(frbch_handle* h);
 void mark_user_stream(frbch_handle* h, dev_stream_t s);
+int enter_stream(frbch_handle* h, dev_stream_t s);    // a device entry point's first step on the stream it queues on ...
+void leave_stream(frbch_handle* h, dev_stream_t s);   // ... and its last
 
 }  // namespace frbchi
 #endif

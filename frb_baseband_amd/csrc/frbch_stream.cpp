@@ -178,7 +178,7 @@ dev_stream_t chain_quant_stream(Chain* c, dev_stream_t s, int* ncu) {
   if (!chain_quant_lane_cus(c)) return s;
   const dev_stream_t sq = c->ln->b;
   *ncu = chain_quant_lane_cus(c);
-  if (!c->b_rooted) {
+  if (!c->b_rooted) {   // (implied by the wait on `e` below, recorded later on the same stream: kept as the lane's explicit root)
     (void)dev_stream_wait(sq, c->ev_entry);
     c->b_rooted = true;
   }

@@ -205,6 +205,22 @@ long frbch_pull(frbch_handle* h, uint8_t* dst, size_t cap);
 long frbch_sigproc_header(frbch_handle* h, uint8_t* dst, size_t cap);
 
 /* ---- device-resident path (inputs and outputs already in HBM) ----------------------------- */
+/* Stream order.  frbch_process_device, frbch_flush_device, frbch_power_device, frbch_unpack_device and frbch_scan_device
+ * take a `stream` (a hipStream_t) and queue their work; with a non-NULL `stream`:
+ *  (a) every read of d_frames and every write of d_out / d_rows / d_power / d_volt is ordered behind all work queued on
+ *      `stream` before the call (an asynchronous copy that delivers the frames, for one);
+ *  (b) all work queued on `stream` after the call has returned sees the complete rows -- those a second lane wrote (DESIGN.md
+ *      section 4b), those of a completed rescale interval and those of a deferred two-pass batch once it is emitted included;
+ *  (c) consecutive calls on one handle behave as if issued synchronously, whichever streams they name: A then B, A then NULL,
+ *      NULL then A (a call that changes the stream waits on the host for the work of the call before it);
+ *  (d) with stream == NULL the work runs on the handle's own non-blocking stream (a scan: that of ifs[0]); the inputs must be
+ *      complete on the host's side before the call, and the rows are complete once frbch_reset, frbch_get_rescale or
+ *      frbch_close of every handle of the call has returned, or after a device-wide synchronisation;
+ *  (e) the frbch_*_device entry points behind and in front of the filterbank (dedisperse, fold, foldp, spsearch, cutout,
+ *      rfi_stats / rfi_apply / rfi_clean, cornerturn) are host-synchronous: they take no stream, run on one of their own, and
+ *      their outputs are complete on return.  A caller that produced d_rows asynchronously (frbch_scan_device on a stream)
+ *      synchronises that stream first.
+ * tests/test_stream_order.py (adversary schedules of the emulator build) and tests/test_gpu_stream_order.py hold (a) - (e). */
 /* d_frames: device pointer to whole VDIF frames (frame geometry taken from `frame_bytes`,
  * `header_bytes`); the payload stream is entered `payload_byte_offset` bytes after the first
  * payload byte (any value; the fast gather needs it and the payload size to be multiples of the

@@ -46,10 +46,10 @@ def guarded():
 
 
 class Env:
-    def __init__(self, lib):
+    def __init__(self, lib, Buffer=None):
         self.lib = lib
-        self.Buffer = guarded_for(lib)
-        self.gpu = self.Buffer is GuardedBuffer
+        self.Buffer = Buffer or guarded_for(lib)
+        self.gpu = issubclass(self.Buffer, GuardedBuffer)
         self.bufs = []
 
     def out(self, nbytes):
@@ -110,9 +110,10 @@ def ids(emu_only=False):
     return [c[0] for c in CASES if c[2] or not emu_only]
 
 
-def run(lib, name):
+def run(lib, name, Buffer=None):
+    """Buffer: the guarded buffer class of the case's buffers, if not the library's own (guarded_for)"""
     fn = next(c[1] for c in CASES if c[0] == name)
-    env = Env(lib)
+    env = Env(lib, Buffer)
     try:
         fn(env)
         env.done()

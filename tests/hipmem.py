@@ -23,6 +23,20 @@ def hip():
         _hip.hipFree.argtypes = [C.c_void_p]
         _hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
         _hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+        _hip.hipStreamCreateWithFlags.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
+        _hip.hipStreamDestroy.argtypes = [C.c_void_p]
+        _hip.hipStreamSynchronize.argtypes = [C.c_void_p]
+        _hip.hipStreamWaitEvent.argtypes = [C.c_void_p, C.c_void_p, C.c_uint]
+        _hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        _hip.hipMemsetAsync.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
+        _hip.hipEventCreate.argtypes = [C.POINTER(C.c_void_p)]
+        _hip.hipEventDestroy.argtypes = [C.c_void_p]
+        _hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
+        _hip.hipEventSynchronize.argtypes = [C.c_void_p]
+        _hip.hipEventQuery.argtypes = [C.c_void_p]
+        _hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
+        _hip.hipHostMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t, C.c_uint]
+        _hip.hipHostFree.argtypes = [C.c_void_p]
     return _hip
 
 
@@ -192,6 +206,127 @@ class GuardedBuffer(_Guards, DeviceBuffer):
             hip().hipFree(self.base)
         self.base = C.c_void_p()
         self.ptr = C.c_void_p()
+
+
+# StreamOrderBuffer's reads: a non-blocking stream of their own and a pinned staging area that grows to the largest read.  Both are
+# kept for the life of the test process on purpose (one stream, one area): they go with the process, like the runtime itself
+_reader = None
+_staging = [C.c_void_p(), 0]
+
+
+class StreamOrderBuffer(GuardedBuffer):
+    """a GuardedBuffer read WITHOUT hipDeviceSynchronize: an asynchronous copy on a non-blocking stream of the reader's own
+    into pinned memory, and a synchronise of that stream alone.  What a read sees is what the streams the test synchronised
+    have written."""
+
+    def _peek(self, offset, n):
+        global _reader
+        out = np.empty(n, dtype=np.uint8)
+        if n:
+            if _reader is None:
+                _reader = Stream()
+            if _staging[1] < n:
+                if _staging[0]:
+                    hip().hipHostFree(_staging[0])
+                assert hip().hipHostMalloc(C.byref(_staging[0]), n, 0) == 0
+                _staging[1] = n
+            _reader.memcpy_async(_staging[0].value, self.base.value + offset, n, 2)   # hipMemcpyDeviceToHost
+            _reader.synchronize()
+            C.memmove(out.ctypes.data, _staging[0], n)
+        return out
+
+    def to_numpy(self, dtype, count=None) -> np.ndarray:
+        for b in list(_LIVE):                       # (the guards of every live buffer of this class: the others' reads synchronise)
+            if isinstance(b, StreamOrderBuffer):
+                b.check()
+        n = self.nbytes if count is None else count * np.dtype(dtype).itemsize
+        return self._peek(GUARD, n).view(dtype)
+
+
+# ---- streams, events, asynchronous copies -----------------------------------------------------------------------------------
+D2D, H2D = 3, 1                  # hipMemcpyDeviceToDevice, hipMemcpyHostToDevice
+
+
+class Stream:
+    """a non-blocking stream (hipStreamNonBlocking): `handle` is what the `stream` argument of the C ABI takes"""
+
+    def __init__(self):
+        s = C.c_void_p()
+        assert hip().hipStreamCreateWithFlags(C.byref(s), 1) == 0
+        self.handle = s.value
+
+    def synchronize(self):
+        assert hip().hipStreamSynchronize(C.c_void_p(self.handle)) == 0
+
+    def memcpy_async(self, dst, src, nbytes, kind=D2D):
+        """dst, src: addresses; a host source must be pinned (PinnedArray) and stay as it is until the copy has run"""
+        assert hip().hipMemcpyAsync(C.c_void_p(dst), C.c_void_p(src), nbytes, kind, C.c_void_p(self.handle)) == 0
+
+    def memset_async(self, dst, value, nbytes):
+        assert hip().hipMemsetAsync(C.c_void_p(dst), value, nbytes, C.c_void_p(self.handle)) == 0
+
+    def wait(self, event):
+        assert hip().hipStreamWaitEvent(C.c_void_p(self.handle), event.handle, 0) == 0
+
+    def destroy(self):
+        if self.handle:
+            hip().hipStreamDestroy(C.c_void_p(self.handle))
+            self.handle = None
+
+
+class Event:
+    """a timing event"""
+
+    def __init__(self):
+        self.handle = C.c_void_p()
+        assert hip().hipEventCreate(C.byref(self.handle)) == 0
+
+    def record(self, stream=None):
+        assert hip().hipEventRecord(self.handle, C.c_void_p(stream.handle if stream else None)) == 0
+        return self
+
+    def synchronize(self):
+        assert hip().hipEventSynchronize(self.handle) == 0
+
+    def done(self) -> bool:
+        """hipEventQuery: False while work in front of the record is still running (hipErrorNotReady)"""
+        rc = hip().hipEventQuery(self.handle)
+        assert rc in (0, 600), rc
+        return rc == 0
+
+    def ms_since(self, start) -> float:
+        """device time between `start` and this event, both recorded; waits for this one"""
+        self.synchronize()
+        ms = C.c_float()
+        assert hip().hipEventElapsedTime(C.byref(ms), start.handle, self.handle) == 0
+        return float(ms.value)
+
+    def destroy(self):
+        if self.handle:
+            hip().hipEventDestroy(self.handle)
+            self.handle = C.c_void_p()
+
+
+class PinnedArray:
+    """page-locked host memory holding a copy of `arr`: the source of an asynchronous upload"""
+
+    def __init__(self, arr):
+        arr = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
+        self.nbytes = arr.nbytes
+        self.ptr = C.c_void_p()
+        assert hip().hipHostMalloc(C.byref(self.ptr), max(1, self.nbytes), 0) == 0
+        C.memmove(self.ptr, arr.ctypes.data, self.nbytes)
+
+    def free(self):
+        if self.ptr:
+            hip().hipHostFree(self.ptr)
+            self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class HostGuardedBuffer(_Guards):

@@ -27,6 +27,22 @@ def test_library_exports_every_declared_symbol(hip_lib):
     out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
     exported = set(re.findall(r" T (frbch_[a-z0-9_]+)", out))
     assert set(declared_functions()) <= exported
+    # ... and nothing of the test-only builds: the hooks of the emulator's scheduler (tests/emu/emu_hooks.cpp) are its alone
+    assert not [s for s in re.findall(r" [A-Za-z] (\S+)", out) if "frbch_test" in s or "emu_" in s]
+    assert exported == set(declared_functions())
+
+
+def test_emulator_build_has_the_scheduler_hooks_and_the_product_names_none(emu_lib):
+    emu = os.path.join(ROOT, "tests", "emu", "libfrbch_emu.so")
+    out = subprocess.check_output(["nm", "-D", "--defined-only", emu]).decode()
+    hooks = set(re.findall(r" T (frbch_test_emu_[a-z0-9_]+)", out))
+    assert {"frbch_test_emu_set_mode", "frbch_test_emu_stream_create", "frbch_test_emu_stream_destroy", "frbch_test_emu_memcpy_async",
+            "frbch_test_emu_stream_sync", "frbch_test_emu_drain", "frbch_test_emu_pending", "frbch_test_emu_violations"} <= hooks
+    pkg = os.path.join(ROOT, "frb_baseband_amd")
+    for dirpath, _d, files in os.walk(pkg):
+        for fn in files:
+            if fn.endswith((".py", ".cpp", ".h", ".inc", ".hip")):
+                assert "frbch_test_emu" not in open(os.path.join(dirpath, fn)).read(), fn
 
 
 def test_struct_sizes_match(hip_lib):
