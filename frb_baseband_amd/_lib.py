@@ -100,6 +100,27 @@ class FrbchRfiParams(C.Structure):
                 ("chan_frac", C.c_double), ("block_frac", C.c_double)]
 
 
+CAND_RFI, CAND_SERIES = 1, 2
+CAND_STAGES = ("upload", "flag", "dedisperse", "search", "cut", "download")      # FRBCH_CAND_T_*
+
+
+class FrbchCandParams(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("rfi", FrbchRfiParams), ("zap", C.c_void_p),
+                ("zerodm", C.c_uint32), ("reserved", C.c_uint32), ("clip_sigma", C.c_double), ("sp", FrbchSpParams),
+                ("dm_gap", C.c_uint32), ("min_members", C.c_uint32), ("max_cands", C.c_uint32), ("reserved2", C.c_uint32),
+                ("cut", FrbchCutoutParams), ("dm_span", C.c_double)]
+
+
+class FrbchCandView(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("reserved", C.c_uint32), ("nout", C.c_uint64), ("nclipped", C.c_uint64),
+                ("ncand", C.c_uint64), ("cands", C.c_void_p), ("ngroup_all", C.c_uint64), ("ngroup", C.c_uint64),
+                ("groups", C.c_void_p), ("cut_cands", C.c_void_p), ("ft", C.c_void_p), ("ft_hits", C.c_void_p),
+                ("dt", C.c_void_p), ("dt_hits", C.c_void_p), ("nblk", C.c_uint32), ("reserved2", C.c_uint32),
+                ("mask", C.c_void_p), ("repl", C.c_void_p), ("chan_flag", C.c_void_p), ("blk_flag", C.c_void_p),
+                ("series", C.c_void_p), ("kernel_used", C.c_uint32 * 4), ("cutout_calls", C.c_uint32),
+                ("row_uploads", C.c_uint32), ("wall_ms", C.c_double * 6), ("device_ms", C.c_double * 6)]
+
+
 class _KTiming(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double),
                 ("algorithmic_bytes", C.c_double)]
@@ -185,6 +206,17 @@ SYMBOLS = {
                                          _P, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
     "frbch_rfi_clean_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams), _P, C.c_int, _P, _P, _P,
                                        _P, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_rfi_cleanp_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams), _P, C.c_int, _P, _P, _P,
+                                          _P, _P, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_rfi_cleanp_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams), _P, C.c_int, _P, _P, _P,
+                                        _P, _P, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_candidates_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, _P, C.c_uint32, C.POINTER(FrbchCandParams), C.c_int,
+                                        C.POINTER(_P), C.c_char_p, C.c_size_t]),
+    "frbch_candidates_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, _P, C.c_uint32, C.POINTER(FrbchCandParams), C.c_int,
+                                          C.POINTER(_P), C.c_char_p, C.c_size_t]),
+    "frbch_cand_result_view": (C.c_int, [_P, C.POINTER(FrbchCandView)]),
+    "frbch_cand_result_free": (None, [_P]),
+    "frbch_cand_select": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "frbch_cornerturn_info": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
     "frbch_cornerturn_host": (C.c_int, [C.c_char_p, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(_P), C.c_uint32,

@@ -2,6 +2,7 @@
 // rows with PRESTO's prepdata / prepsubband options as the reference passes them (process_vdif.py:202-229) and the phase
 // fold that base2fil.sh:474 delegates to dspsr.  Included by frbch_post.cpp (its own translation unit).
 #include <limits>
+#include <memory>
 #include <new>
 #include <system_error>
 #include <thread>
@@ -19,6 +20,29 @@ struct PostErr {
   int fail(int code, const std::string& msg) const {
     if (buf && cap) snprintf(buf, cap, "%s", msg.c_str());
     return code;
+  }
+};
+
+// Device time of a stage for frbch_candidates_*: while `tl_stage_ms` points somewhere (this thread is inside such a call), a
+// _device entry point adds the time between two events on its own stream -- its first and its last work -- to it.
+thread_local double* tl_stage_ms = nullptr;
+struct StageClock {
+  dev_stream_t s;
+  dev_event_t a, b;
+  bool on = false;
+  explicit StageClock(dev_stream_t stream) : s(stream) {
+    if (!tl_stage_ms || dev_event_create(&a) != 0) return;
+    if (dev_event_create(&b) != 0) { dev_event_destroy(a); return; }
+    dev_event_record(a, s);
+    on = true;
+  }
+  void finish() {                       // before the stream goes
+    if (!on) return;
+    on = false;
+    dev_event_record(b, s);
+    *tl_stage_ms += (double)dev_event_ms(a, b);
+    dev_event_destroy(a);
+    dev_event_destroy(b);
   }
 };
 
@@ -127,7 +151,9 @@ extern "C" int frbch_dedisperse_device(const frbch_fil_desc* fil, const void* d_
   double *d_rowsum = nullptr, *d_colsum = nullptr, *d_repl = nullptr;
   uint8_t* d_flag = nullptr;
   int32_t *d_delays = nullptr, *d_range = nullptr;
+  StageClock clk(s);
   auto cleanup = [&]() {
+    clk.finish();
     dev_free(d_rowsum); dev_free(d_colsum); dev_free(d_repl); dev_free(d_flag); dev_free(d_delays); dev_free(d_range);
     dev_stream_destroy(s);
   };
@@ -607,16 +633,26 @@ struct SpRaw {
   long long sum;
   double sigma;
 };
+// frbch_spsearch_device; with `all` every candidate goes there instead (cands and cap are then not looked at, and no
+// number of candidates is a capacity error): frbch_candidates_* own their list
+int sp_search_run(const float* d_series, uint32_t ndm, uint64_t nout, const frbch_sp_params* sp, int device, frbch_sp_cand* cands,
+                  uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, std::vector<frbch_sp_cand>* all, char* err, size_t err_cap);
 }  // namespace
 
 extern "C" int frbch_spsearch_device(const float* d_series, uint32_t ndm, uint64_t nout, const frbch_sp_params* sp, int device,
                                      frbch_sp_cand* cands, uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, char* err,
                                      size_t err_cap) {
+  return sp_search_run(d_series, ndm, nout, sp, device, cands, cap, ncand, kernel_used, nullptr, err, err_cap);
+}
+
+namespace {
+int sp_search_run(const float* d_series, uint32_t ndm, uint64_t nout, const frbch_sp_params* sp, int device, frbch_sp_cand* cands,
+                  uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, std::vector<frbch_sp_cand>* all, char* err, size_t err_cap) {
   PostErr e{err, err_cap};
   uint64_t blk_len = 0;
   int rc = sp_check(sp, &blk_len, e);
   if (rc) return rc;
-  if (!d_series || !ncand || (cap && !cands)) return e.fail(FRBCH_E_ARG, "null argument");
+  if (!d_series || !ncand || (!all && cap && !cands)) return e.fail(FRBCH_E_ARG, "null argument");
   if (!ndm || !nout || ndm > 65535) return e.fail(FRBCH_E_ARG, "ndm must be 1..65535, nout positive");
   if (device < 0 || device >= dev_count()) return e.fail(FRBCH_E_DEVICE, "no such GPU (there is no CPU fallback)");
   DeviceGuard dg(device);
@@ -637,7 +673,8 @@ extern "C" int frbch_spsearch_device(const float* d_series, uint32_t ndm, uint64
     p.thr[k] = t < 9.0e18 ? (long long)t : INT64_MAX;             // (no sum reaches 2^37)
   }
   p.peak_cap = kSpRawCap;
-  auto cleanup = [&]() { dev_free(p.stats); dev_free(p.q); dev_free(p.peaks); dev_free(p.npeak); dev_stream_destroy(s); };
+  StageClock clk(s);
+  auto cleanup = [&]() { clk.finish(); dev_free(p.stats); dev_free(p.q); dev_free(p.peaks); dev_free(p.npeak); dev_stream_destroy(s); };
 #define POST_DEV(expr, what) do { if ((expr) != 0) { cleanup(); return e.fail(FRBCH_E_DEVICE, std::string(what) + ": " + dev_last_error_string()); } } while (0)
   POST_DEV(dev_malloc((void**)&p.stats, (size_t)ndm * p.nblk * 2 * sizeof(double)), "hipMalloc");
   POST_DEV(dev_malloc((void**)&p.peaks, (size_t)kSpRawCap * sizeof(SpPeak)), "hipMalloc");
@@ -706,22 +743,25 @@ extern "C" int frbch_spsearch_device(const float* d_series, uint32_t ndm, uint64
         dropped = b.sigma > a.sigma || (b.sigma == a.sigma && (b.width < a.width || (b.width == a.width && b.centre < a.centre)));
       }
       if (dropped) continue;
-      if (total < cap) {                                          // (centre, width) ascending already: the output order
-        frbch_sp_cand& c = cands[total];
+      if (all || total < cap) {                                   // (centre, width) ascending already: the output order
+        frbch_sp_cand c;
         c.dm_index = raw[i0].dm;
         c.width = a.width;
         c.sample = a.centre;
         c.sigma = (float)a.sigma;
         c.reserved = 0;
+        if (all) all->push_back(c);
+        else cands[total] = c;
       }
       ++total;
     }
     i0 = i1;
   }
   *ncand = total;
-  if (total > cap) return e.fail(FRBCH_E_CAPACITY, std::to_string(total) + " candidates, room for " + std::to_string(cap));
+  if (!all && total > cap) return e.fail(FRBCH_E_CAPACITY, std::to_string(total) + " candidates, room for " + std::to_string(cap));
   return FRBCH_OK;
 }
+}  // namespace
 
 extern "C" int frbch_spsearch_host(const float* series, uint32_t ndm, uint64_t nout, const frbch_sp_params* sp, int device,
                                    frbch_sp_cand* cands, uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, char* err,
@@ -874,14 +914,21 @@ extern "C" int frbch_sp_group_cands(const frbch_fil_desc* fil, const double* dms
 namespace {
 constexpr uint64_t kCutTableCap = 1ull << 26;    // delay-table entries of one call (256 MiB); a longer batch is refused
 
-int cut_check(const frbch_fil_desc* fil, uint64_t nrows, const frbch_cutout_params* par, const frbch_cutout_cand* cands,
-              uint32_t ncand, const PostErr& e) {
-  int rc = post_check_fil(fil, nrows, e);
-  if (rc) return rc;
+// the part of cut_check that needs no candidate (frbch_candidates_* refuse a bad `cut` before they have any)
+int cut_check_par(const frbch_fil_desc* fil, const frbch_cutout_params* par, const PostErr& e) {
   if (!par || par->size != sizeof(frbch_cutout_params)) return e.fail(FRBCH_E_ARG, "frbch_cutout_params: wrong size");
   if (par->nt < 2 || par->nt > 1024 || (par->nt & 1)) return e.fail(FRBCH_E_ARG, "nt must be even, 2..1024");
   if (par->nf < 1 || fil->nchan % par->nf != 0) return e.fail(FRBCH_E_ARG, "nf must divide nchan");
   if (par->ndm < 1 || par->ndm > 1024) return e.fail(FRBCH_E_ARG, "ndm must be 1..1024");
+  return FRBCH_OK;
+}
+
+int cut_check(const frbch_fil_desc* fil, uint64_t nrows, const frbch_cutout_params* par, const frbch_cutout_cand* cands,
+              uint32_t ncand, const PostErr& e) {
+  int rc = post_check_fil(fil, nrows, e);
+  if (rc) return rc;
+  rc = cut_check_par(fil, par, e);
+  if (rc) return rc;
   if (!cands || ncand < 1 || ncand > 65535) return e.fail(FRBCH_E_ARG, "1..65535 candidates");
   if ((uint64_t)ncand * par->nf * par->nt >= (1ull << 31) || (uint64_t)ncand * par->ndm * par->nt >= (1ull << 31))
     return e.fail(FRBCH_E_ARG, "a plane set of 2^31 elements or more");
@@ -1045,7 +1092,8 @@ extern "C" int frbch_cutout_device(const frbch_fil_desc* fil, const void* d_rows
     dev_free(d_cand); dev_free(d_ftd); dev_free(d_dtd); dev_free(d_ftr); dev_free(d_dtr);
     d_cand = nullptr; d_ftd = d_dtd = d_ftr = d_dtr = nullptr;
   };
-  auto cleanup = [&]() { release(); dev_stream_destroy(s); };
+  StageClock clk(s);
+  auto cleanup = [&]() { clk.finish(); release(); dev_stream_destroy(s); };
 #define POST_DEV(expr, what) do { if ((expr) != 0) { cleanup(); return e.fail(FRBCH_E_DEVICE, std::string(what) + ": " + dev_last_error_string()); } } while (0)
   POST_DEV(dev_malloc((void**)&d_cand, plan.cand.size() * sizeof(CutCand)), "hipMalloc");
   POST_DEV(dev_malloc((void**)&d_ftd, plan.ft_delays.size() * sizeof(int32_t)), "hipMalloc");
@@ -1278,7 +1326,8 @@ extern "C" int frbch_rfi_stats_device(const frbch_fil_desc* fil, const void* d_r
   DeviceGuard dg(device);
   dev_stream_t s = 0;
   if (dev_stream_create(&s) != 0) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
-  auto cleanup = [&]() { dev_stream_destroy(s); };
+  StageClock clk(s);
+  auto cleanup = [&]() { clk.finish(); dev_stream_destroy(s); };
 #define POST_DEV(expr, what) do { if ((expr) != 0) { cleanup(); return e.fail(FRBCH_E_DEVICE, std::string(what) + ": " + dev_last_error_string()); } } while (0)
   RfiParams p = rfi_params(fil, d_rows, nrows, par, nblk);
   p.stats_i = (unsigned long long*)d_stats;
@@ -1496,7 +1545,8 @@ extern "C" int frbch_rfi_apply_device(const frbch_fil_desc* fil, void* d_rows, u
   DeviceGuard dg(device);
   dev_stream_t s = 0;
   if (dev_stream_create(&s) != 0) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
-  auto cleanup = [&]() { dev_stream_destroy(s); };
+  StageClock clk(s);
+  auto cleanup = [&]() { clk.finish(); dev_stream_destroy(s); };
 #define POST_DEV(expr, what) do { if ((expr) != 0) { cleanup(); return e.fail(FRBCH_E_DEVICE, std::string(what) + ": " + dev_last_error_string()); } } while (0)
   RfiParams p = rfi_params(fil, d_rows, nrows, par, nblk);
   p.mask = d_mask;
@@ -1581,6 +1631,420 @@ extern "C" int frbch_rfi_clean_host(const frbch_fil_desc* fil, void* rows, uint6
   if (!rc && (dev_d2h(rows, d_rows, in_bytes, 0) != 0 || dev_sync(0) != 0)) rc = e.fail(FRBCH_E_DEVICE, "download rows");
   dev_free(d_rows);
   return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// resident rows: every product cleaned in one residency; flagging, search, grouping and cut-outs in one call
+// ---------------------------------------------------------------------------------------------------------------------
+extern "C" int frbch_rfi_cleanp_device(const frbch_fil_desc* fil_in, void* d_rows, uint64_t nrows, const frbch_rfi_params* par,
+                                       const uint8_t* zap, int device, uint8_t* mask, double* repl, uint8_t* chan_flag,
+                                       uint8_t* blk_flag, void* stats_out, uint32_t* kernel_used, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  if (!fil_in || fil_in->size != sizeof(frbch_fil_desc)) return e.fail(FRBCH_E_ARG, "frbch_fil_desc: wrong size");
+  frbch_fil_desc fd = *fil_in;
+  fd.product = 0;                                          // every product is cleaned
+  uint32_t nblk = 0;
+  int rc = rfi_check(&fd, nrows, par, &nblk, e);
+  if (rc) return rc;
+  if (!d_rows || !mask || !repl || !chan_flag || !blk_flag) return e.fail(FRBCH_E_ARG, "null argument");
+  if (device < 0 || device >= dev_count()) return e.fail(FRBCH_E_DEVICE, "no such GPU (there is no CPU fallback)");
+  DeviceGuard dg(device);
+  const uint32_t nifs = fd.nifs, nchan = fd.nchan;
+  const size_t ncell = (size_t)nblk * nchan;
+  void *d_stats = nullptr, *d_mask = nullptr, *d_repl = nullptr;
+  uint32_t used_min = 1;
+  try {
+    std::vector<uint64_t> own;                                     // (S, Q): uint64 or double, 16 bytes a cell either way
+    if (!stats_out) own.resize((size_t)nifs * ncell * 2);
+    uint64_t* st = stats_out ? (uint64_t*)stats_out : own.data();
+    if (dev_malloc(&d_stats, ncell * 16) != 0) rc = e.fail(FRBCH_E_NOMEM, "device memory for the statistics");
+    for (uint32_t p = 0; p < nifs && !rc; ++p) {
+      uint32_t used = 0;
+      fd.product = p;
+      rc = frbch_rfi_stats_device(&fd, d_rows, nrows, par, device, d_stats, &used, err, err_cap);
+      if (!rc && (dev_d2h(st + (size_t)p * ncell * 2, d_stats, ncell * 16, 0) != 0 || dev_sync(0) != 0))
+        rc = e.fail(FRBCH_E_DEVICE, "download statistics");
+      used_min = std::min(used_min, used);
+    }
+    // every product's own decision, their union, then -- several products -- the decision again with the union as prior
+    std::vector<uint8_t> m1(ncell), cf1(nchan), bf1(nblk);
+    memset(mask, 0, ncell);
+    memset(chan_flag, 0, nchan);
+    memset(blk_flag, 0, nblk);
+    for (uint32_t p = 0; p < nifs && !rc; ++p) {
+      fd.product = p;
+      rc = frbch_rfi_mask(&fd, st + (size_t)p * ncell * 2, nblk, nrows, par, zap, nullptr, m1.data(), repl + (size_t)p * nchan,
+                          cf1.data(), bf1.data(), err, err_cap);
+      for (size_t i = 0; i < ncell; ++i) mask[i] |= m1[i];
+      for (uint32_t c = 0; c < nchan; ++c) chan_flag[c] |= cf1[c];
+      for (uint32_t b = 0; b < nblk; ++b) blk_flag[b] |= bf1[b];
+    }
+    for (uint32_t p = 0; p < nifs && nifs > 1 && !rc; ++p) {
+      fd.product = p;
+      rc = frbch_rfi_mask(&fd, st + (size_t)p * ncell * 2, nblk, nrows, par, zap, mask, m1.data(), repl + (size_t)p * nchan,
+                          cf1.data(), bf1.data(), err, err_cap);
+    }
+  } catch (const std::bad_alloc&) {
+    rc = e.fail(FRBCH_E_NOMEM, "host memory for the statistics");
+  }
+  if (!rc && std::any_of(mask, mask + ncell, [](uint8_t m) { return m != 0; })) {      // (nothing masked: nothing to write)
+    if (dev_malloc(&d_mask, ncell) != 0 || dev_malloc(&d_repl, nchan * sizeof(double)) != 0)
+      rc = e.fail(FRBCH_E_NOMEM, "device memory for the mask");
+    if (!rc && (dev_h2d(d_mask, mask, ncell, 0) != 0 || dev_sync(0) != 0)) rc = e.fail(FRBCH_E_DEVICE, "upload mask");
+    for (uint32_t p = 0; p < nifs && !rc; ++p) {
+      fd.product = p;
+      if (dev_h2d(d_repl, repl + (size_t)p * nchan, nchan * sizeof(double), 0) != 0 || dev_sync(0) != 0)
+        rc = e.fail(FRBCH_E_DEVICE, "upload replacements");
+      if (!rc) rc = frbch_rfi_apply_device(&fd, d_rows, nrows, par, (const uint8_t*)d_mask, (const double*)d_repl, device, err, err_cap);
+    }
+  }
+  dev_free(d_stats); dev_free(d_mask); dev_free(d_repl);
+  if (!rc && kernel_used) *kernel_used = used_min;
+  return rc;
+}
+
+extern "C" int frbch_rfi_cleanp_host(const frbch_fil_desc* fil, void* rows, uint64_t nrows, const frbch_rfi_params* par,
+                                     const uint8_t* zap, int device, uint8_t* mask, double* repl, uint8_t* chan_flag,
+                                     uint8_t* blk_flag, void* stats, uint32_t* kernel_used, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  if (!fil || fil->size != sizeof(frbch_fil_desc)) return e.fail(FRBCH_E_ARG, "frbch_fil_desc: wrong size");
+  frbch_fil_desc fd = *fil;
+  fd.product = 0;
+  uint32_t nblk = 0;
+  int rc = rfi_check(&fd, nrows, par, &nblk, e);
+  if (rc) return rc;
+  if (!rows || !mask || !repl || !chan_flag || !blk_flag) return e.fail(FRBCH_E_ARG, "null argument");
+  if (device < 0 || device >= dev_count()) return e.fail(FRBCH_E_DEVICE, "no such GPU (there is no CPU fallback)");
+  DeviceGuard dg(device);
+  const size_t in_bytes = (size_t)nrows * fil->nifs * fil->nchan * (size_t)(fil->nbits / 8);
+  void* d_rows = nullptr;
+  if (dev_malloc(&d_rows, in_bytes) != 0) rc = e.fail(FRBCH_E_NOMEM, "device memory for the rows");
+  if (!rc && (dev_h2d(d_rows, rows, in_bytes, 0) != 0 || dev_sync(0) != 0)) rc = e.fail(FRBCH_E_DEVICE, "upload rows");
+  if (!rc) rc = frbch_rfi_cleanp_device(fil, d_rows, nrows, par, zap, device, mask, repl, chan_flag, blk_flag, stats, kernel_used, err, err_cap);
+  if (!rc && (dev_d2h(rows, d_rows, in_bytes, 0) != 0 || dev_sync(0) != 0)) rc = e.fail(FRBCH_E_DEVICE, "download rows");
+  dev_free(d_rows);
+  return rc;
+}
+
+struct frbch_cand_result {
+  uint64_t nout = 0, nclipped = 0, ngroup_all = 0;
+  std::vector<frbch_sp_cand> cands;
+  std::vector<frbch_sp_group> groups;
+  std::vector<frbch_cutout_cand> cut_cands;
+  bool planes = false, rfi = false, keep_series = false;
+  std::vector<float> ft, dt, series;
+  std::vector<uint32_t> ft_hits, dt_hits;
+  uint32_t nblk = 0;
+  std::vector<uint8_t> mask, chan_flag, blk_flag;
+  std::vector<double> repl;
+  uint32_t kernel_used[4] = {0, 0, 0, 0}, cutout_calls = 0, row_uploads = 0;
+  double wall_ms[FRBCH_CAND_NSTAGE] = {0}, device_ms[FRBCH_CAND_NSTAGE] = {0};
+};
+
+namespace {
+std::vector<uint64_t> cand_select(const frbch_sp_group* g, uint64_t n, uint32_t min_members, uint32_t max_cands) {
+  std::vector<uint64_t> idx;
+  for (uint64_t i = 0; i < n; ++i)
+    if (g[i].nmember >= min_members) idx.push_back(i);
+  if (max_cands > 0 && idx.size() > max_cands) {
+    std::stable_sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) { return g[a].best.sigma > g[b].best.sigma; });
+    idx.resize(max_cands);
+    std::sort(idx.begin(), idx.end());
+  }
+  return idx;
+}
+
+frbch_cutout_cand cand_cutout_of(const frbch_sp_cand& b, const double* dms, double dm_span) {
+  POST_NO_CONTRACT
+  frbch_cutout_cand c;
+  memset(&c, 0, sizeof c);
+  c.dm = dms[b.dm_index];
+  if (dm_span > 0.0) {
+    const double half = 0.5 * dm_span;
+    const double lo = c.dm - half;
+    c.dm_lo = lo > 0.0 ? lo : 0.0;
+    c.dm_hi = c.dm_lo + dm_span;
+  } else {
+    c.dm_lo = 0.0;
+    c.dm_hi = 2.0 * c.dm;
+  }
+  c.sample = (int64_t)b.sample;
+  c.tfactor = std::min<uint32_t>(std::max<uint32_t>(b.width / 2, 1u), 512u);
+  return c;
+}
+
+// candidates of one frbch_cutout_* call: the three per-call limits
+uint64_t cand_per_call(const frbch_fil_desc* fil, const frbch_cutout_params* cut) {
+  const uint64_t by_plane = ((1ull << 31) - 1) / ((uint64_t)std::max(cut->nf, cut->ndm) * cut->nt);
+  const uint64_t by_table = kCutTableCap / ((uint64_t)cut->ndm * fil->nchan);
+  return std::max<uint64_t>(1, std::min<uint64_t>(65535, std::min(by_plane, by_table)));
+}
+
+struct CandDev {                                   // everything a frbch_candidates_* call holds on the device
+  void *rows = nullptr, *work = nullptr, *stats = nullptr, *mask = nullptr, *repl = nullptr;
+  float *series = nullptr, *ft = nullptr, *dt = nullptr;
+  uint32_t *fth = nullptr, *dth = nullptr;
+  dev_stream_t s = 0;
+  bool have_s = false;
+  template <class T>
+  void drop(T*& p) { dev_free(p); p = nullptr; }
+  ~CandDev() {
+    dev_free(rows); dev_free(work); dev_free(stats); dev_free(mask); dev_free(repl); dev_free(series);
+    dev_free(ft); dev_free(dt); dev_free(fth); dev_free(dth);
+    if (have_s) dev_stream_destroy(s);
+  }
+};
+
+int cand_run(const frbch_fil_desc* fil, const void* rows_h, const void* d_rows_in, uint64_t nrows, const double* dms, uint32_t ndm,
+             const frbch_cand_params* par, int device, frbch_cand_result** out, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  if (!out) return e.fail(FRBCH_E_ARG, "null argument: out");
+  *out = nullptr;
+  if (!par || par->size != sizeof(frbch_cand_params)) return e.fail(FRBCH_E_ARG, "frbch_cand_params: wrong size");
+  if (par->flags & ~(FRBCH_CAND_RFI | FRBCH_CAND_SERIES)) return e.fail(FRBCH_E_ARG, "unknown flag");
+  int rc = post_check_fil(fil, nrows, e);
+  if (rc) return rc;
+  if (!(rows_h || d_rows_in) || !dms || !ndm) return e.fail(FRBCH_E_ARG, "null argument");
+  uint64_t blk_len = 0;
+  rc = sp_check(&par->sp, &blk_len, e);
+  if (rc) return rc;
+  if (ndm > 65535) return e.fail(FRBCH_E_ARG, "ndm must be 1..65535");
+  if (par->min_members < 1) return e.fail(FRBCH_E_ARG, "min_members must be at least 1");
+  if (par->dm_gap < 1 || par->dm_gap > 16) return e.fail(FRBCH_E_ARG, "dm_gap must be 1..16");
+  const bool rfi = (par->flags & FRBCH_CAND_RFI) != 0, keep_series = (par->flags & FRBCH_CAND_SERIES) != 0, cut = par->cut.nt != 0;
+  uint32_t nblk = 0;
+  if (rfi && (rc = rfi_check(fil, nrows, &par->rfi, &nblk, e)) != 0) return rc;
+  if (cut && (rc = cut_check_par(fil, &par->cut, e)) != 0) return rc;
+  const long want = frbch_dedisperse_nout(fil, nrows, dms, ndm);
+  if (want <= 0) return e.fail(FRBCH_E_ARG, "a DM outside [0, 1e5), or the largest dispersion delay exceeds the data");
+  const uint64_t nout = (uint64_t)want;
+  if (device < 0 || device >= dev_count()) return e.fail(FRBCH_E_DEVICE, "no such GPU (there is no CPU fallback)");
+  DeviceGuard dg(device);
+  const uint32_t nchan = fil->nchan;
+  const size_t in_bytes = (size_t)nrows * fil->nifs * nchan * (size_t)(fil->nbits / 8);
+  const size_t out_bytes = (size_t)ndm * nout * sizeof(float), ncell = (size_t)nblk * nchan;
+  const uint64_t per_call = cut ? cand_per_call(fil, &par->cut) : 0;
+  // what the call asks of the device, for the message of FRBCH_E_NOMEM
+  auto nomem = [&](const char* what) {
+    std::string m = std::string("device memory for ") + what + "; the call needs:";
+    auto add = [&](const std::string& name, uint64_t bytes) { m += " " + name + " " + std::to_string(bytes) + " B,"; };
+    if (rows_h) add("rows", in_bytes);
+    if (rfi) {
+      if (!rows_h) add("cleaned copy of the rows (when a cell is masked)", in_bytes);
+      add("block statistics", ncell * 16);
+      add("mask", ncell);
+      add("replacement values", nchan * sizeof(double));
+    }
+    add("series", out_bytes);
+    add("search statistics", (uint64_t)ndm * std::max<uint64_t>(1, nout / blk_len) * 2 * sizeof(double));
+    add("raw peaks", (uint64_t)kSpRawCap * sizeof(SpPeak));
+    if (cut) {
+      add("planes of a batch of at most " + std::to_string(per_call) + " candidates, each",
+          ((uint64_t)par->cut.nf + par->cut.ndm) * par->cut.nt * 8);
+      add("delay tables of a batch, each candidate", ((uint64_t)par->cut.ndm + 1) * nchan * sizeof(int32_t));
+    }
+    m.back() = '.';
+    return e.fail(FRBCH_E_NOMEM, m);
+  };
+  try {
+    std::unique_ptr<frbch_cand_result> res(new frbch_cand_result());
+    res->nout = nout;
+    res->rfi = rfi;
+    res->keep_series = keep_series;
+    CandDev cd;
+    if (dev_stream_create(&cd.s) != 0) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+    cd.have_s = true;
+    const auto now = []() { return std::chrono::steady_clock::now(); };
+    // fn() as stage k: its wall time, and the device time its _device calls (or a StageClock of its own) report
+    auto stage = [&](int k, auto&& fn) -> int {
+      const auto t0 = now();
+      tl_stage_ms = &res->device_ms[k];
+      const int r = fn();
+      tl_stage_ms = nullptr;
+      res->wall_ms[k] += std::chrono::duration<double, std::milli>(now() - t0).count();
+      return r;
+    };
+    const void* d_use = d_rows_in;
+    if (rows_h) {
+      if (dev_malloc(&cd.rows, in_bytes) != 0) return nomem("the rows");
+      rc = stage(FRBCH_CAND_T_UPLOAD, [&]() {
+        StageClock clk(cd.s);
+        const bool bad = dev_h2d(cd.rows, rows_h, in_bytes, cd.s) != 0 || dev_sync(cd.s) != 0;
+        clk.finish();
+        return bad ? e.fail(FRBCH_E_DEVICE, "upload rows") : FRBCH_OK;
+      });
+      if (rc) return rc;
+      d_use = cd.rows;
+      res->row_uploads = 1;
+    }
+    if (rfi) {
+      res->nblk = nblk;
+      res->mask.assign(ncell, 0);
+      res->repl.assign(nchan, 0.0);
+      res->chan_flag.assign(nchan, 0);
+      res->blk_flag.assign(nblk, 0);
+      std::vector<uint64_t> st(ncell * 2);                        // (S, Q): uint64 or double, 16 bytes a cell either way
+      if (dev_malloc(&cd.stats, ncell * 16) != 0) return nomem("the block statistics");
+      rc = stage(FRBCH_CAND_T_FLAG, [&]() {
+        int r = frbch_rfi_stats_device(fil, d_use, nrows, &par->rfi, device, cd.stats, &res->kernel_used[0], err, err_cap);
+        if (!r && (dev_d2h(st.data(), cd.stats, ncell * 16, cd.s) != 0 || dev_sync(cd.s) != 0)) r = e.fail(FRBCH_E_DEVICE, "download statistics");
+        if (!r) r = frbch_rfi_mask(fil, st.data(), nblk, nrows, &par->rfi, par->zap, nullptr, res->mask.data(), res->repl.data(),
+                                   res->chan_flag.data(), res->blk_flag.data(), err, err_cap);
+        return r;
+      });
+      if (rc) return rc;
+      cd.drop(cd.stats);
+      if (std::any_of(res->mask.begin(), res->mask.end(), [](uint8_t m) { return m != 0; })) {   // (nothing masked: nothing to write)
+        void* target = cd.rows;
+        if (!rows_h) {                                            // the caller's rows keep every byte: a copy is cleaned
+          if (dev_malloc(&cd.work, in_bytes) != 0) return nomem("the cleaned copy of the rows");
+          target = cd.work;
+        }
+        if (dev_malloc(&cd.mask, ncell) != 0 || dev_malloc(&cd.repl, nchan * sizeof(double)) != 0) return nomem("the mask");
+        rc = stage(FRBCH_CAND_T_FLAG, [&]() {
+          if ((!rows_h && dev_d2d(cd.work, d_rows_in, in_bytes, cd.s) != 0) || dev_h2d(cd.mask, res->mask.data(), ncell, cd.s) != 0 ||
+              dev_h2d(cd.repl, res->repl.data(), nchan * sizeof(double), cd.s) != 0 || dev_sync(cd.s) != 0)
+            return e.fail(FRBCH_E_DEVICE, "copy rows / upload mask");
+          return frbch_rfi_apply_device(fil, target, nrows, &par->rfi, (const uint8_t*)cd.mask, (const double*)cd.repl, device, err, err_cap);
+        });
+        if (rc) return rc;
+        d_use = target;
+        cd.drop(cd.mask);
+        cd.drop(cd.repl);
+      }
+    }
+    if (dev_malloc((void**)&cd.series, out_bytes) != 0) return nomem("the series");
+    res->kernel_used[1] = frbch_dedisperse_kernel(fil, d_use, nrows, dms, ndm) > 0 ? 1u : 0u;
+    rc = stage(FRBCH_CAND_T_DEDISPERSE, [&]() {
+      return frbch_dedisperse_device(fil, d_use, nrows, dms, ndm, par->zerodm, par->clip_sigma, device, cd.series, nout, &res->nclipped,
+                                     err, err_cap);
+    });
+    if (rc) return rc;
+    if (keep_series) {
+      res->series.resize((size_t)ndm * nout);
+      rc = stage(FRBCH_CAND_T_DOWNLOAD, [&]() {
+        StageClock clk(cd.s);
+        const bool bad = dev_d2h(res->series.data(), cd.series, out_bytes, cd.s) != 0 || dev_sync(cd.s) != 0;
+        clk.finish();
+        return bad ? e.fail(FRBCH_E_DEVICE, "download series") : FRBCH_OK;
+      });
+      if (rc) return rc;
+    }
+    uint64_t ncand = 0;
+    rc = stage(FRBCH_CAND_T_SEARCH, [&]() {
+      return sp_search_run(cd.series, ndm, nout, &par->sp, device, nullptr, 0, &ncand, &res->kernel_used[2], &res->cands, err, err_cap);
+    });
+    if (rc) return rc;
+    cd.drop(cd.series);                                            // the plane is done with; the rows stay for the cut-outs
+    std::vector<frbch_sp_group> all(std::max<size_t>(1, res->cands.size()));
+    uint64_t ngroup_all = 0;
+    rc = frbch_sp_group_cands(fil, dms, ndm, res->cands.data(), res->cands.size(), par->dm_gap, all.data(), all.size(), &ngroup_all,
+                              err, err_cap);
+    if (rc) return rc;
+    res->ngroup_all = ngroup_all;
+    for (uint64_t i : cand_select(all.data(), ngroup_all, par->min_members, par->max_cands)) {
+      res->groups.push_back(all[i]);
+      res->cut_cands.push_back(cand_cutout_of(all[i].best, dms, par->dm_span));
+    }
+    const uint64_t n = res->groups.size();
+    if (cut && n) {
+      const uint32_t nt = par->cut.nt, nf = par->cut.nf, cdm = par->cut.ndm;
+      const size_t ft1 = (size_t)nf * nt, dt1 = (size_t)cdm * nt;
+      res->ft.resize(n * ft1); res->ft_hits.resize(n * ft1);
+      res->dt.resize(n * dt1); res->dt_hits.resize(n * dt1);
+      res->planes = true;
+      const uint64_t bmax = std::min(n, per_call);
+      if (dev_malloc((void**)&cd.ft, bmax * ft1 * 4) != 0 || dev_malloc((void**)&cd.fth, bmax * ft1 * 4) != 0 ||
+          dev_malloc((void**)&cd.dt, bmax * dt1 * 4) != 0 || dev_malloc((void**)&cd.dth, bmax * dt1 * 4) != 0)
+        return nomem("the planes");
+      uint32_t used_min = 1;
+      for (uint64_t a = 0; a < n; a += per_call) {
+        const uint32_t cnt = (uint32_t)std::min(per_call, n - a);
+        uint32_t used = 0;
+        rc = stage(FRBCH_CAND_T_CUT, [&]() {
+          return frbch_cutout_device(fil, d_use, nrows, &par->cut, &res->cut_cands[a], cnt, device, cd.ft, cd.fth, cd.dt, cd.dth, &used,
+                                     err, err_cap);
+        });
+        if (rc) return rc;
+        used_min = std::min(used_min, used);
+        ++res->cutout_calls;
+        rc = stage(FRBCH_CAND_T_DOWNLOAD, [&]() {
+          StageClock clk(cd.s);
+          const bool bad = dev_d2h(&res->ft[a * ft1], cd.ft, cnt * ft1 * 4, cd.s) != 0 || dev_d2h(&res->ft_hits[a * ft1], cd.fth, cnt * ft1 * 4, cd.s) != 0 ||
+                           dev_d2h(&res->dt[a * dt1], cd.dt, cnt * dt1 * 4, cd.s) != 0 || dev_d2h(&res->dt_hits[a * dt1], cd.dth, cnt * dt1 * 4, cd.s) != 0 ||
+                           dev_sync(cd.s) != 0;
+          clk.finish();
+          return bad ? e.fail(FRBCH_E_DEVICE, "download planes") : FRBCH_OK;
+        });
+        if (rc) return rc;
+      }
+      res->kernel_used[3] = used_min;
+    }
+    *out = res.release();
+  } catch (const std::bad_alloc&) {
+    tl_stage_ms = nullptr;
+    return e.fail(FRBCH_E_NOMEM, "host memory for the result");
+  }
+  return FRBCH_OK;
+}
+}  // namespace
+
+extern "C" int frbch_candidates_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const double* dms, uint32_t ndm,
+                                     const frbch_cand_params* par, int device, frbch_cand_result** out, char* err, size_t err_cap) {
+  if (out) *out = nullptr;
+  if (!rows) return PostErr{err, err_cap}.fail(FRBCH_E_ARG, "null argument");
+  return cand_run(fil, rows, nullptr, nrows, dms, ndm, par, device, out, err, err_cap);
+}
+
+extern "C" int frbch_candidates_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const double* dms, uint32_t ndm,
+                                       const frbch_cand_params* par, int device, frbch_cand_result** out, char* err, size_t err_cap) {
+  if (out) *out = nullptr;
+  if (!d_rows) return PostErr{err, err_cap}.fail(FRBCH_E_ARG, "null argument");
+  return cand_run(fil, nullptr, d_rows, nrows, dms, ndm, par, device, out, err, err_cap);
+}
+
+extern "C" int frbch_cand_result_view(const frbch_cand_result* r, frbch_cand_view* v) {
+  if (!r || !v || v->size != sizeof(frbch_cand_view)) return FRBCH_E_ARG;
+  memset(v, 0, sizeof *v);
+  v->size = sizeof *v;
+  v->nout = r->nout;
+  v->nclipped = r->nclipped;
+  v->ncand = r->cands.size();
+  v->cands = r->cands.empty() ? nullptr : r->cands.data();
+  v->ngroup_all = r->ngroup_all;
+  v->ngroup = r->groups.size();
+  v->groups = r->groups.empty() ? nullptr : r->groups.data();
+  v->cut_cands = r->cut_cands.empty() ? nullptr : r->cut_cands.data();
+  if (r->planes) {
+    v->ft = r->ft.data(); v->ft_hits = r->ft_hits.data();
+    v->dt = r->dt.data(); v->dt_hits = r->dt_hits.data();
+  }
+  if (r->rfi) {
+    v->nblk = r->nblk;
+    v->mask = r->mask.data(); v->repl = r->repl.data();
+    v->chan_flag = r->chan_flag.data(); v->blk_flag = r->blk_flag.data();
+  }
+  if (r->keep_series) v->series = r->series.data();
+  for (int k = 0; k < 4; ++k) v->kernel_used[k] = r->kernel_used[k];
+  v->cutout_calls = r->cutout_calls;
+  v->row_uploads = r->row_uploads;
+  for (int k = 0; k < FRBCH_CAND_NSTAGE; ++k) { v->wall_ms[k] = r->wall_ms[k]; v->device_ms[k] = r->device_ms[k]; }
+  return FRBCH_OK;
+}
+
+extern "C" void frbch_cand_result_free(frbch_cand_result* r) { delete r; }
+
+extern "C" int frbch_cand_select(const frbch_sp_group* groups, uint64_t ngroup, uint32_t min_members, uint32_t max_cands,
+                                 uint64_t* keep, uint64_t cap, uint64_t* nkeep) {
+  if (!nkeep || (ngroup && !groups) || (cap && !keep) || min_members < 1) return FRBCH_E_ARG;
+  try {
+    const std::vector<uint64_t> idx = cand_select(groups, ngroup, min_members, max_cands);
+    *nkeep = idx.size();
+    for (uint64_t i = 0; i < std::min<uint64_t>(cap, idx.size()); ++i) keep[i] = idx[i];
+    return idx.size() > cap ? FRBCH_E_CAPACITY : FRBCH_OK;
+  } catch (const std::bad_alloc&) {
+    return FRBCH_E_NOMEM;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -16,6 +16,9 @@ reference's `dspsr -E <par> ... <IFall.fil>` stage) of SIGPROC filterbank files,
 * ``rfifind_fil`` / ``clean`` flag interference per (block of rows, channel) from block statistics taken on the GPU, write
   and read the flag file the reference carries to Heimdall and FETCH (create_config.py:54-56 ``-F/--flag``), and replace the
   masked samples: ``search_fil`` and ``candidates_fil`` take ``flag_file`` / ``rfi`` and then work on the cleaned rows.
+* ``resident=True`` (``--resident``) of ``search_fil``, ``candidates_fil`` and ``rfifind_fil``: the rows cross to the device
+  once per command and stay there from flagging to cut-outs (``candidates_resident``: frbch_candidates_host; ``cleanp``:
+  frbch_rfi_cleanp_host); the files and the returned values are those of the default path, byte for byte.
 There is no CPU fallback: the sums run in libfrbch.so on a gfx950 device.
 """
 from __future__ import annotations
@@ -334,11 +337,12 @@ def clean(rows, hdr: dict, params=None, zap=None, device: int = 0, lib=None, inf
 
 
 def rfifind_fil(filterbankfile, block_rows=1024, t_cell=5.0, t_chan=5.0, chan_frac=0.3, block_frac=0.3, flag_file=None,
-                write_clean=False, device=0, lib=None, info: dict | None = None):
+                write_clean=False, device=0, lib=None, info: dict | None = None, resident=False):
     """Flag a filterbank: ``<base>_rfi.npz`` (mask, chan_flag, blk_flag, repl, the block statistics [nifs][nblk][nchan][2] and
     the parameters), ``<base>.flag`` (the wholly flagged channels, ``write_flag_file``) and, with ``write_clean``,
     ``<base>_clean.fil`` -- the header bytes unchanged, every product cleaned in the same cells.  ``flag_file``: channels
-    to flag whatever the statistics say.  Returns (list of files written, the result dict of ``clean``)."""
+    to flag whatever the statistics say.  ``resident``: all products in one library call on rows uploaded once and downloaded
+    once (frbch_rfi_cleanp_host) -- the same files and values.  Returns (list of files written, the result dict of ``clean``)."""
     lib = lib or _lib.load()
     fil = sigproc.read_fil(filterbankfile)
     hdr = fil.header
@@ -348,18 +352,22 @@ def rfifind_fil(filterbankfile, block_rows=1024, t_cell=5.0, t_chan=5.0, chan_fr
     zap = read_flag_file(flag_file, hdr["nchans"]) if flag_file else None
     par = rfi_params(params)
     nifs, nchan = hdr.get("nifs", 1), hdr["nchans"]
-    cleaned = _rows3(rows, hdr).copy()
-    stats, kernels = [], []
-    for p in range(nifs):                                    # taken once: they go into the .npz and into the decision
-        i = {}
-        stats.append(rfi_stats(cleaned, hdr, par, product=p, device=device, lib=lib, info=i))
-        kernels.append(i["kernel_used"])
-    repl = np.zeros((nifs, nchan), np.float64)
-    mask, cf, bf = _clean_from_stats(lib, cleaned, hdr, par, stats, list(range(nifs)), _zap_array(zap, nchan), repl, device)
-    res = dict(mask=mask, repl=repl, chan_flag=cf, blk_flag=bf)
-    stats = np.stack(stats)
-    if info is not None:
-        info["kernel_used"] = min(kernels)
+    if resident:
+        cleaned, res = cleanp(rows, hdr, par, zap=zap, device=device, lib=lib, info=info, want_stats=True)
+        cleaned, stats = _rows3(cleaned, hdr), res.pop("stats")
+    else:
+        cleaned = _rows3(rows, hdr).copy()
+        stats, kernels = [], []
+        for p in range(nifs):                                    # taken once: they go into the .npz and into the decision
+            i = {}
+            stats.append(rfi_stats(cleaned, hdr, par, product=p, device=device, lib=lib, info=i))
+            kernels.append(i["kernel_used"])
+        repl = np.zeros((nifs, nchan), np.float64)
+        mask, cf, bf = _clean_from_stats(lib, cleaned, hdr, par, stats, list(range(nifs)), _zap_array(zap, nchan), repl, device)
+        res = dict(mask=mask, repl=repl, chan_flag=cf, blk_flag=bf)
+        stats = np.stack(stats)
+        if info is not None:
+            info["kernel_used"] = min(kernels)
     base = filterbankfile.replace(".fil", "")
     np.savez(base + "_rfi.npz", mask=res["mask"], chan_flag=res["chan_flag"], blk_flag=res["blk_flag"], repl=res["repl"], stats=stats,
              zap=np.zeros(hdr["nchans"], bool) if zap is None else zap, nrows=rows.shape[0], **params)
@@ -492,15 +500,19 @@ def _series_names(filterbankfile, dm1, dm2, dms):
 
 
 def search_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, zerodm=True, clip=5, threshold=5.0, max_width_s=0.0, detrend_len=1000,
-               write_dat=False, widths=None, device=0, lib=None, info: dict | None = None, flag_file=None, rfi=None):
+               write_dat=False, widths=None, device=0, lib=None, info: dict | None = None, flag_file=None, rfi=None, resident=False):
     """Dedisperse a filterbank over the DMs of ``prepdata_gpu`` and search every series for single pulses in one library
     call (frbch_dedisperse_search_host: the DM x time plane never leaves the GPU unless ``write_dat`` asks for the .dat /
     .inf files, which are then ``prepdata_gpu``'s).  Writes one ``<name>.singlepulse`` per DM, names as ``prepdata_gpu``.
     ``flag_file`` (channels to flag, ``read_flag_file``) and / or ``rfi`` (``True`` or a dict of ``RFI_DEFAULTS`` keys): the
     rows are flagged and cleaned once (``clean``, frbch_rfi_clean_host) and the cleaned rows searched; with neither, every
-    file is what it was without them.
+    file is what it was without them.  ``resident``: flagging and search in one library call on rows uploaded once
+    (frbch_candidates_host) -- the same files and values; ``info`` gains ``row_uploads`` and the stage times.
     Returns (list of .singlepulse files, candidates of all DMs as a structured array)."""
     lib = lib or _lib.load()
+    if resident:
+        return _search_fil_resident(filterbankfile, dm1, dm2, dmstep, zerodm, clip, threshold, max_width_s, detrend_len, write_dat, widths,
+                                    device, lib, info, flag_file, rfi)
     fil = _read_rows(filterbankfile, flag_file, rfi, device, lib, info, detrend_len)
     return _search(fil, filterbankfile, dm1, dm2, dmstep, zerodm, clip, threshold, max_width_s, detrend_len, write_dat, widths, device,
                    lib, info)
@@ -648,7 +660,7 @@ def cand_name(base: str, tstart: float, tcand: float, dm: float, snr: float) -> 
 
 def candidates_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, zerodm=True, clip=5, threshold=5.0, max_width_s=0.0, detrend_len=1000,
                    widths=None, dm_gap=2, min_members=1, max_cands=0, nt=256, nf=0, ndm=256, dm_span=None, device=0, lib=None,
-                   info: dict | None = None, flag_file=None, rfi=None):
+                   info: dict | None = None, flag_file=None, rfi=None, resident=False):
     """``search_fil``, then one candidate per pulse: the records are grouped across DMs (``group_candidates``), groups of
     fewer than ``min_members`` records are dropped, the ``max_cands`` strongest kept (0: all), and ONE frbch_cutout_host
     call cuts the two planes of all of them (``cutouts``: several calls only for a list longer than a call takes).  Writes, next to ``search_fil``'s own files (which are unchanged),
@@ -656,9 +668,13 @@ def candidates_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, zerodm=True, clip=5, 
     ``.npz`` (data_freq_time [nt][nf] and data_dm_time [ndm][nt] as means = sums / hits, 0 where hits is 0; the four raw
     planes; the scalars) and ``.png`` (the frequency-time plane above the DM-time plane).
     ``flag_file`` / ``rfi`` as in ``search_fil``: the search AND the planes then see the cleaned rows (cleaned once; they
-    travel to the device again for the search and for the cut-outs).
+    travel to the device again for the search and for the cut-outs).  ``resident``: every stage in one library call on rows
+    uploaded once (frbch_candidates_host) -- the same files and values; ``info`` gains ``row_uploads`` and the stage times.
     Returns (list of .npz files, kept groups as a structured array)."""
     lib = lib or _lib.load()
+    if resident:
+        return _candidates_fil_resident(filterbankfile, dm1, dm2, dmstep, zerodm, clip, threshold, max_width_s, detrend_len, widths, dm_gap,
+                                        min_members, max_cands, nt, nf, ndm, dm_span, device, lib, info, flag_file, rfi)
     sinfo = {}
     fil = _read_rows(filterbankfile, flag_file, rfi, device, lib, sinfo, detrend_len)
     _files, recs = _search(fil, filterbankfile, dm1, dm2, dmstep, zerodm, clip, threshold, max_width_s, detrend_len, False, widths,
@@ -703,6 +719,220 @@ def candidates_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, zerodm=True, clip=5, 
         write_png(name + ".png", np.concatenate([unit(ft_mean), np.zeros((4, ft_mean.shape[1])), unit(dt_mean)], axis=0))
         out.append(name + ".npz")
     return out, groups
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# resident rows: one upload per command (frbch_candidates_host, frbch_rfi_cleanp_host)
+# ------------------------------------------------------------------------------------------------------------------
+def _from_ptr(ptr, dtype, shape):
+    """a copy of the library's array at ``ptr``; None for a NULL pointer"""
+    if not ptr:
+        return None
+    dtype = np.dtype(dtype)
+    n = int(np.prod(shape, dtype=np.int64))
+    if n == 0:
+        return np.zeros(shape, dtype)
+    return np.frombuffer((C.c_char * (n * dtype.itemsize)).from_address(ptr), dtype=dtype).reshape(shape).copy()
+
+
+def select_groups(groups, min_members: int = 1, max_cands: int = 0, lib=None) -> np.ndarray:
+    """The selection of ``candidates_fil`` as the library makes it (frbch_cand_select): indices, ascending, of the groups
+    with at least ``min_members`` records, cut to the ``max_cands`` strongest (0: all; equal sigmas: the earlier group)."""
+    lib = lib or _lib.load()
+    g = np.ascontiguousarray(groups, dtype=SP_GROUP)
+    keep = np.zeros(max(1, g.size), np.uint64)
+    n = C.c_uint64(0)
+    rc = lib.frbch_cand_select(g.ctypes.data if g.size else None, g.size, int(min_members), int(max_cands), keep.ctypes.data, keep.size,
+                               C.byref(n))
+    if rc < 0:
+        raise InputError("min_members must be at least 1")
+    return keep[: n.value].astype(np.int64)
+
+
+def candidates_resident(rows, hdr: dict, dms, *, sp, rfi=None, zap=None, zerodm=True, clip=5.0, dm_gap=2, min_members=1, max_cands=0,
+                        nt=256, nf=0, ndm=256, dm_span=None, keep_series=False, product=0, device=0, lib=None, d_rows=None,
+                        nrows=None) -> dict:
+    """Flagging (``rfi``: ``True`` or a dict of ``RFI_DEFAULTS`` keys; ``zap`` alone flags as well), the search of the DMs,
+    grouping, selection and the cut-outs in ONE library call on rows that cross to the device once (frbch_candidates_host),
+    or -- ``d_rows``: a device address, with ``nrows`` -- not at all (frbch_candidates_device, which leaves them as they
+    are).  ``sp``: ``sp_params(...)``; ``nt = 0``: no planes.  -> dict of copies of everything in the library's result view
+    (include/frbch.h): nout, nclipped, cands, ngroup_all, groups, cut_cands, ft / ft_hits / dt / dt_hits (None without
+    planes), mask / repl / chan_flag / blk_flag (None without flagging), series (None unless ``keep_series``), kernel_used
+    (RFI statistics, dedispersion, search, cut-out), cutout_calls, row_uploads, wall_ms and device_ms by stage name."""
+    lib = lib or _lib.load()
+    nchan, nifs = hdr["nchans"], hdr.get("nifs", 1)
+    if d_rows is None:
+        x = _rows3(rows, hdr)
+        nrows, ptr = x.shape[0], x.ctypes.data
+    else:
+        ptr = int(d_rows)
+    dm_arr = np.ascontiguousarray(dms, dtype=np.float64)
+    par = _lib.FrbchCandParams()
+    par.size = C.sizeof(_lib.FrbchCandParams)
+    z = _zap_array(zap, nchan)
+    flag = bool(rfi) or z is not None
+    par.flags = (_lib.CAND_RFI if flag else 0) | (_lib.CAND_SERIES if keep_series else 0)
+    par.rfi = rfi_params(rfi if isinstance(rfi, (dict, _lib.FrbchRfiParams)) else None)
+    par.zap = None if z is None else z.ctypes.data
+    par.zerodm, par.clip_sigma = (1 if zerodm else 0), float(clip)
+    par.sp = sp
+    if min(int(dm_gap), int(min_members), int(max_cands)) < 0:
+        raise InputError("dm_gap, min_members and max_cands must not be negative")
+    par.dm_gap, par.min_members, par.max_cands = int(dm_gap), int(min_members), int(max_cands)
+    if nt and nf == 0:
+        nf = max(d for d in range(1, min(256, nchan) + 1) if nchan % d == 0)
+    if min(int(nt), int(nf), int(ndm)) < 0:
+        raise InputError("nt, nf and ndm must not be negative")
+    par.cut = _lib.FrbchCutoutParams(C.sizeof(_lib.FrbchCutoutParams), int(nt), int(nf), int(ndm))
+    if dm_span is not None and not float(dm_span) > 0.0:
+        raise InputError("dm_span must be positive (None: the plane spans 0 .. 2 dm)")
+    par.dm_span = 0.0 if dm_span is None else float(dm_span)
+    desc = fil_desc(hdr, product)
+    res = C.c_void_p(None)
+    err = C.create_string_buffer(2048)
+    call = lib.frbch_candidates_host if d_rows is None else lib.frbch_candidates_device
+    _check(call(C.byref(desc), ptr, int(nrows), dm_arr.ctypes.data, dm_arr.size, C.byref(par), device, C.byref(res), err, len(err)), err)
+    try:
+        v = _lib.FrbchCandView()
+        v.size = C.sizeof(_lib.FrbchCandView)
+        if lib.frbch_cand_result_view(res, C.byref(v)) != 0:
+            raise RunError("frbch_cand_result_view refused the view")
+        n = int(v.ngroup)
+        out = dict(nout=int(v.nout), nclipped=int(v.nclipped), ngroup_all=int(v.ngroup_all),
+                   cands=_from_ptr(v.cands, SP_CAND, (int(v.ncand),)) if v.ncand else np.zeros(0, SP_CAND),
+                   groups=_from_ptr(v.groups, SP_GROUP, (n,)) if n else np.zeros(0, SP_GROUP),
+                   cut_cands=_from_ptr(v.cut_cands, CUT_CAND, (n,)) if n else np.zeros(0, CUT_CAND),
+                   ft=_from_ptr(v.ft, np.float32, (n, int(nf), int(nt))), ft_hits=_from_ptr(v.ft_hits, np.uint32, (n, int(nf), int(nt))),
+                   dt=_from_ptr(v.dt, np.float32, (n, int(ndm), int(nt))), dt_hits=_from_ptr(v.dt_hits, np.uint32, (n, int(ndm), int(nt))),
+                   nblk=int(v.nblk), mask=_from_ptr(v.mask, np.uint8, (int(v.nblk), nchan)), repl=_from_ptr(v.repl, np.float64, (nchan,)),
+                   chan_flag=_from_ptr(v.chan_flag, np.uint8, (nchan,)), blk_flag=_from_ptr(v.blk_flag, np.uint8, (int(v.nblk),)),
+                   series=_from_ptr(v.series, np.float32, (dm_arr.size, int(v.nout))), kernel_used=[int(k) for k in v.kernel_used],
+                   cutout_calls=int(v.cutout_calls), row_uploads=int(v.row_uploads),
+                   wall_ms=dict(zip(_lib.CAND_STAGES, [float(t) for t in v.wall_ms])),
+                   device_ms=dict(zip(_lib.CAND_STAGES, [float(t) for t in v.device_ms])))
+    finally:
+        lib.frbch_cand_result_free(res)
+    return out
+
+
+def _resident_run(filterbankfile, dm1, dm2, dmstep, zerodm, clip, threshold, max_width_s, detrend_len, widths, device, lib, info,
+                  flag_file, rfi, **kw):
+    """``_read_rows`` and ``_search`` of the resident commands: the file, its DMs and ``candidates_resident`` of its rows;
+    ``info`` receives what the two give it, plus row_uploads and the stage times"""
+    fil = sigproc.read_fil(filterbankfile)
+    hdr = fil.header
+    dms = dm_list(dm1, dm2, dmstep)
+    rows = _rows_of(fil)
+    desc = fil_desc(hdr)
+    dm_arr = np.ascontiguousarray(dms, dtype=np.float64)
+    if lib.frbch_dedisperse_nout(C.byref(desc), rows.shape[0], dm_arr.ctypes.data, dm_arr.size) <= 0:
+        raise InputError("the dispersion delay across the band exceeds the length of the filterbank")
+    zap = read_flag_file(flag_file, hdr["nchans"]) if flag_file is not None else None
+    flag = flag_file is not None or bool(rfi)
+    params = sp_params(widths if widths is not None else default_widths(hdr["tsamp"], max_width_s), threshold, detrend_len)
+    r = candidates_resident(rows, hdr, dms, sp=params, rfi=(rfi if isinstance(rfi, dict) else True) if flag else None, zap=zap,
+                            zerodm=zerodm, clip=float(clip), device=device, lib=lib, **kw)
+    if flag:
+        if info is not None:
+            info.update(rfi_kernel_used=r["kernel_used"][0], rfi_chan_flag=r["chan_flag"].astype(bool), rfi_blk_flag=r["blk_flag"].astype(bool),
+                        rfi_mask=r["mask"], rfi_masked_cells=int(r["mask"].sum()))
+        block_rows = rfi_params(rfi if isinstance(rfi, dict) else None).block_rows
+        if r["blk_flag"].any() and not r["chan_flag"].all() and 2 * block_rows > (detrend_len or 1000):
+            import warnings
+            warnings.warn("%d block(s) of %d rows flagged wholly: each is a flat stretch of every dedispersed series, longer than half a "
+                          "normalisation block of the search (detrend_len = %d), which can then report the noise at the stretch's edges; "
+                          "use shorter blocks, e.g. rfi=dict(block_rows=256)" % (int(r["blk_flag"].sum()), block_rows, detrend_len or 1000))
+    if info is not None:
+        info.update(kernel_used=r["kernel_used"][2], nclipped=r["nclipped"], nout=r["nout"], row_uploads=r["row_uploads"],
+                    dedisperse_kernel_used=r["kernel_used"][1], wall_ms=r["wall_ms"], device_ms=r["device_ms"])
+    return hdr, dms, r
+
+
+def _resident_singlepulse(filterbankfile, dm1, dm2, dms, hdr, r, write_dat):
+    """the files of ``_search`` from a resident result"""
+    out = []
+    for i, (name, dm) in enumerate(zip(_series_names(filterbankfile, dm1, dm2, dms), dms)):
+        write_singlepulse(name + ".singlepulse", r["cands"][r["cands"]["dm_index"] == i], dm, hdr["tsamp"])
+        out.append(name + ".singlepulse")
+        if write_dat:
+            r["series"][i].astype("<f4").tofile(name + ".dat")
+            write_inf(name + ".inf", basename=os.path.basename(name), hdr=hdr, nsamp=r["nout"], dm=dm, clipped=r["nclipped"])
+    return out
+
+
+def _search_fil_resident(filterbankfile, dm1, dm2, dmstep, zerodm, clip, threshold, max_width_s, detrend_len, write_dat, widths, device,
+                         lib, info, flag_file, rfi):
+    hdr, dms, r = _resident_run(filterbankfile, dm1, dm2, dmstep, zerodm, clip, threshold, max_width_s, detrend_len, widths, device, lib,
+                                info, flag_file, rfi, nt=0, keep_series=bool(write_dat))
+    return _resident_singlepulse(filterbankfile, dm1, dm2, dms, hdr, r, write_dat), r["cands"]
+
+
+def _candidates_fil_resident(filterbankfile, dm1, dm2, dmstep, zerodm, clip, threshold, max_width_s, detrend_len, widths, dm_gap,
+                             min_members, max_cands, nt, nf, ndm, dm_span, device, lib, info, flag_file, rfi):
+    sinfo = {}
+    hdr, dms, r = _resident_run(filterbankfile, dm1, dm2, dmstep, zerodm, clip, threshold, max_width_s, detrend_len, widths, device, lib,
+                                sinfo, flag_file, rfi, dm_gap=dm_gap, min_members=min_members, max_cands=max_cands, nt=nt, nf=nf, ndm=ndm,
+                                dm_span=dm_span)
+    _resident_singlepulse(filterbankfile, dm1, dm2, dms, hdr, r, False)
+    groups, cc = r["groups"], r["cut_cands"]
+    base = filterbankfile.replace(".fil", "")
+    with open(base + ".cands.txt", "w") as f:
+        f.write(CANDS_HEADER + "\n")
+        for g in groups:
+            b = g["best"]
+            f.write(CANDS_ROW % (dms[int(b["dm_index"])], b["sigma"], int(b["sample"]) * hdr["tsamp"], int(b["sample"]), int(b["width"]),
+                                 int(g["nmember"]), int(g["dm_index_lo"]), int(g["dm_index_hi"])) + "\n")
+    if info is not None:
+        info.update(sinfo, ngroup=int(groups.size), search_kernel_used=sinfo.get("kernel_used"))
+    out = []
+    if groups.size == 0:
+        return out, groups
+    if info is not None:
+        info["cutout_kernel_used"] = r["kernel_used"][3]
+        info["cutout_calls"] = r["cutout_calls"]
+    ft, ft_hits, dt, dt_hits = r["ft"], r["ft_hits"], r["dt"], r["dt_hits"]
+    for i, (g, c) in enumerate(zip(groups, cc)):
+        b = g["best"]
+        tcand = int(b["sample"]) * hdr["tsamp"]
+        name = cand_name(base, hdr["tstart"], tcand, c["dm"], float(b["sigma"]))
+        ft_mean, dt_mean = _plane_mean(ft[i], ft_hits[i]), _plane_mean(dt[i], dt_hits[i])
+        np.savez(name + ".npz", data_freq_time=ft_mean.T.copy(), data_dm_time=dt_mean, ft=ft[i], ft_hits=ft_hits[i], dt=dt[i],
+                 dt_hits=dt_hits[i], tcand=tcand, dm=c["dm"], snr=float(b["sigma"]), width=int(b["width"]), tfactor=int(c["tfactor"]),
+                 tsamp=hdr["tsamp"], fch1=hdr["fch1"], foff=hdr["foff"], nchans=hdr["nchans"], tstart=hdr["tstart"],
+                 dm_lo=c["dm_lo"], dm_hi=c["dm_hi"])
+        img = [u - u.mean(axis=1, keepdims=True) for u in (ft_mean, dt_mean)]
+        img = [(u - u.min()) / max(1e-30, float(u.max() - u.min())) for u in img]
+        write_png(name + ".png", np.concatenate([img[0], np.zeros((4, ft_mean.shape[1])), img[1]], axis=0))
+        out.append(name + ".npz")
+    return out, groups
+
+
+def cleanp(rows, hdr: dict, params=None, zap=None, device: int = 0, lib=None, info: dict | None = None, want_stats: bool = False):
+    """``clean`` of ALL products in one residency (frbch_rfi_cleanp_host: one upload, one download of the rows) -> (cleaned copy
+    of the rows, dict(mask, repl [nifs][nchan], chan_flag, blk_flag and, with ``want_stats``, stats [nifs][nblk][nchan][2]))."""
+    lib = lib or _lib.load()
+    x = _rows3(rows, hdr).copy()
+    par = rfi_params(params)
+    nifs, nchan = x.shape[1], x.shape[2]
+    nblk = lib.frbch_rfi_nblk(x.shape[0], par.block_rows)
+    if nblk <= 0:
+        raise InputError("block_rows must be 1..2^20")
+    z = _zap_array(zap, nchan)
+    mask, repl = np.zeros((nblk, nchan), np.uint8), np.zeros((nifs, nchan), np.float64)
+    cf, bf = np.zeros(nchan, np.uint8), np.zeros(nblk, np.uint8)
+    stats = np.zeros((nifs, nblk, nchan, 2), np.float64 if hdr["nbits"] == 32 else np.uint64) if want_stats else None
+    used = C.c_uint32(0)
+    err = C.create_string_buffer(512)
+    desc = fil_desc(hdr)
+    _check(lib.frbch_rfi_cleanp_host(C.byref(desc), x.ctypes.data, x.shape[0], C.byref(par), None if z is None else z.ctypes.data, device,
+                                     mask.ctypes.data, repl.ctypes.data, cf.ctypes.data, bf.ctypes.data,
+                                     None if stats is None else stats.ctypes.data, C.byref(used), err, len(err)), err)
+    if info is not None:
+        info.update(kernel_used=used.value, row_uploads=1, row_downloads=1)
+    res = dict(mask=mask, repl=repl, chan_flag=cf.astype(bool), blk_flag=bf.astype(bool))
+    if want_stats:
+        res["stats"] = stats
+    return x.reshape(np.shape(rows)), res
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -1080,7 +1310,8 @@ def main(argv=None):
     ``... search <fil> --dm <dm> [--dm2 --dmstep --threshold --max-width --detrend ...]`` /
     ``... candidates <fil> --dm <dm> [search options] [--dm-gap --min-members --max-cands --nt --nf --ndm]`` /
     ``... rfifind <fil> [--block-rows --t-cell --t-chan --chan-frac --block-frac --flag FILE --write-clean]``
-    (``search`` and ``candidates`` take ``--flag FILE`` and ``--rfi``): the stages
+    (``search`` and ``candidates`` take ``--flag FILE`` and ``--rfi``; ``search``, ``candidates`` and ``rfifind`` take ``--resident``:
+    one upload of the rows per command): the stages
     as commands, for the places where base2fil.sh / process_vdif.py launch dspsr and prepdata"""
     import argparse
     ap = argparse.ArgumentParser(prog="frb_baseband_amd.post")
@@ -1116,6 +1347,7 @@ def main(argv=None):
     q.add_argument("--write-dat", action="store_true", help="also write the .dat / .inf files of prepdata")
     q.add_argument("--flag", default=None, help="flag file (channels to flag): the rows are cleaned before the search")
     q.add_argument("--rfi", action="store_true", help="flag interference from block statistics and clean the rows first")
+    q.add_argument("--resident", action="store_true", help="flag and search in one library call on rows uploaded once")
     q.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     k = sub.add_parser("candidates", help="search, group the records across DMs, cut the frequency-time and DM-time planes of every group")
     k.add_argument("fil")
@@ -1135,6 +1367,7 @@ def main(argv=None):
     k.add_argument("--ndm", type=int, default=256)
     k.add_argument("--flag", default=None, help="flag file (channels to flag): the rows are cleaned before the search and the cut-outs")
     k.add_argument("--rfi", action="store_true", help="flag interference from block statistics and clean the rows first")
+    k.add_argument("--resident", action="store_true", help="flag, search and cut in one library call on rows uploaded once")
     k.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     r = sub.add_parser("rfifind", help="flag interference per (block of rows, channel): <base>_rfi.npz, <base>.flag, optionally <base>_clean.fil")
     r.add_argument("fil")
@@ -1145,11 +1378,12 @@ def main(argv=None):
     r.add_argument("--block-frac", type=float, default=RFI_DEFAULTS["block_frac"], help="flag a block with more than this fraction of its channels flagged")
     r.add_argument("--flag", default=None, help="flag file: channels to flag whatever the statistics say")
     r.add_argument("--write-clean", action="store_true", help="also write <base>_clean.fil")
+    r.add_argument("--resident", action="store_true", help="clean all products in one library call on rows uploaded and downloaded once")
     r.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     a = ap.parse_args(argv)
     if a.cmd == "rfifind":
         files, res = rfifind_fil(a.fil, block_rows=a.block_rows, t_cell=a.t_cell, t_chan=a.t_chan, chan_frac=a.chan_frac,
-                                 block_frac=a.block_frac, flag_file=a.flag, write_clean=a.write_clean, device=a.device)
+                                 block_frac=a.block_frac, flag_file=a.flag, write_clean=a.write_clean, device=a.device, resident=a.resident)
         for path in files:
             print("wrote", path)
         print("{0} of {1} channels and {2} of {3} blocks flagged wholly, {4} cells masked".format(
@@ -1158,7 +1392,7 @@ def main(argv=None):
         files, groups = candidates_fil(a.fil, a.dm, dm2=a.dm2, dmstep=a.dmstep, zerodm=a.nozerodm, clip=a.clip, threshold=a.threshold,
                                        max_width_s=a.max_width, detrend_len=a.detrend, dm_gap=a.dm_gap, min_members=a.min_members,
                                        max_cands=a.max_cands, nt=a.nt, nf=a.nf, ndm=a.ndm, device=a.device, flag_file=a.flag,
-                                       rfi=a.rfi or None)
+                                       rfi=a.rfi or None, resident=a.resident)
         print("wrote", a.fil.replace(".fil", "") + ".cands.txt")
         for path in files:
             print("wrote", path, "and .png")
@@ -1170,7 +1404,7 @@ def main(argv=None):
     elif a.cmd == "search":
         files, cands = search_fil(a.fil, a.dm, dm2=a.dm2, dmstep=a.dmstep, zerodm=a.nozerodm, clip=a.clip, threshold=a.threshold,
                                   max_width_s=a.max_width, detrend_len=a.detrend, write_dat=a.write_dat, device=a.device,
-                                  flag_file=a.flag, rfi=a.rfi or None)
+                                  flag_file=a.flag, rfi=a.rfi or None, resident=a.resident)
         for path in files:
             print("wrote", path)
         print("{0} candidates above {1} sigma".format(cands.size, a.threshold))

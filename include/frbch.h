@@ -550,6 +550,103 @@ int frbch_rfi_clean_host(const frbch_fil_desc* fil, void* rows, uint64_t nrows, 
                          const uint8_t* zap, int device, uint8_t* mask, double* repl, uint8_t* chan_flag, uint8_t* blk_flag,
                          uint32_t* kernel_used, char* err, size_t err_cap);
 
+/* All nifs products cleaned in one residency (`fil->product` is ignored): the statistics of every product, each product's own
+ * mask (frbch_rfi_mask without a prior), the OR of the masks and of the channel and block flags across the products, then --
+ * for nifs > 1 -- frbch_rfi_mask again per product with `prior` = the union, which gives repl[p], and the union mask applied
+ * to every product with its own repl[p].  nifs = 1 is frbch_rfi_clean_*.  mask [nblk][nchan], repl [nifs][nchan], chan_flag
+ * [nchan], blk_flag [nblk] and stats [nifs][nblk][nchan][2] (may be NULL) are HOST arrays; *kernel_used (may be NULL): the
+ * smallest over the products.  The _device form cleans d_rows in place; the _host form uploads the rows once, cleans them
+ * and downloads them once into `rows`. */
+int frbch_rfi_cleanp_device(const frbch_fil_desc* fil, void* d_rows, uint64_t nrows, const frbch_rfi_params* par,
+                            const uint8_t* zap, int device, uint8_t* mask, double* repl, uint8_t* chan_flag, uint8_t* blk_flag,
+                            void* stats, uint32_t* kernel_used, char* err, size_t err_cap);
+int frbch_rfi_cleanp_host(const frbch_fil_desc* fil, void* rows, uint64_t nrows, const frbch_rfi_params* par,
+                          const uint8_t* zap, int device, uint8_t* mask, double* repl, uint8_t* chan_flag, uint8_t* blk_flag,
+                          void* stats, uint32_t* kernel_used, char* err, size_t err_cap);
+
+/* ---- resident rows: flagging, DM-range search, grouping, selection and cut-outs in one call --------
+ * The production call for a DM-range search with candidates: the rows cross to the device ONCE (frbch_candidates_host) or
+ * not at all (frbch_candidates_device) and every stage above runs on them where they lie.  Every array of the result is
+ * byte-identical to what this sequence of the calls above returns for the same arguments:
+ *  1. With FRBCH_CAND_RFI: frbch_rfi_clean_host for fil->product (`rfi`, `zap`); otherwise the rows as given.
+ *  2. frbch_dedisperse_search_host on those rows (`zerodm`, `clip_sigma`, `sp`): nout, nclipped, the records and -- with
+ *     FRBCH_CAND_SERIES -- series[ndm][nout].
+ *  3. frbch_sp_group_cands with `dm_gap`: ngroup_all groups.
+ *  4. The selection (frbch_cand_select): the groups with nmember >= min_members (min_members >= 1); when max_cands > 0 and
+ *     more remain, the max_cands of them with the largest best.sigma, among equal sigmas the group that comes earlier in
+ *     group order; the kept groups stay in group order.
+ *  5. The cut-out candidate of kept group g, every operation an IEEE double operation rounded on its own:
+ *     dm = dms[best.dm_index], sample = best.sample, tfactor = min(max(best.width / 2, 1), 512) (integer division);
+ *     dm_span <= 0: dm_lo = 0, dm_hi = 2 dm;  dm_span > 0: dm_lo = max(0, dm - 0.5 dm_span), dm_hi = dm_lo + dm_span.
+ *  6. frbch_cutout_host in batches of whole candidates, in order, each of
+ *     max(1, min(65535, (2^31 - 1) / (max(nf, ndm) nt), 2^26 / (ndm nchan))) candidates (integer divisions; the three
+ *     per-call limits of frbch_cutout_*), the last one shorter.  No kept group, or cut.nt = 0 (the search-only use: `cut` is
+ *     then not looked at): no planes, the four plane pointers are NULL, cutout_calls = 0 and the call returns FRBCH_OK.
+ * The library owns the result (frbch_cand_result_free; NULL is a no-op), so no capacity is negotiated and nothing runs
+ * twice; the one capacity error left is the search's own (more than 2^20 raw peaks: FRBCH_E_CAPACITY).
+ * frbch_candidates_device never writes d_rows: with FRBCH_CAND_RFI the statistics are read from d_rows, and when the mask
+ * has a cell set the rows are copied device to device and the copy is cleaned (frbch_rfi_apply_device) and used from then
+ * on.  So kernel_used[0] is frbch_rfi_stats_kernel for the address of d_rows, and kernel_used[1] / [3] are
+ * frbch_dedisperse_kernel / frbch_cutout_kernel for the address of the rows the stage read -- d_rows, or a buffer of the
+ * library's (hipMalloc: 256-byte aligned), which is what the _host form always reads.  kernel_used of a stage that did not
+ * run is 0; of the cut-out the smallest over the batches.
+ * Errors: FRBCH_E_ARG with a message and *out = NULL for a wrong `size` in any struct, an unknown flag, NULL arguments,
+ * min_members = 0, and whatever a stage refuses (a dm_gap outside 1..16, a `cut` frbch_cutout_* refuses, ...);
+ * FRBCH_E_NOMEM when device memory runs out, the message lists every buffer of the call with its size.  Everything
+ * allocated is freed on every path; the call is host-synchronous. */
+#define FRBCH_CAND_RFI 1u
+#define FRBCH_CAND_SERIES 2u
+typedef struct frbch_cand_params {
+  uint32_t size, flags;                /* = sizeof(frbch_cand_params); FRBCH_CAND_*                                       */
+  frbch_rfi_params rfi;                /* used with FRBCH_CAND_RFI                                                        */
+  const uint8_t* zap;                  /* host [nchan] or NULL, as frbch_rfi_clean_*                                      */
+  uint32_t zerodm, reserved;           /* as frbch_dedisperse_*                                                           */
+  double clip_sigma;
+  frbch_sp_params sp;
+  uint32_t dm_gap, min_members, max_cands, reserved2;   /* max_cands = 0: all                                             */
+  frbch_cutout_params cut;             /* cut.nt = 0: no planes                                                           */
+  double dm_span;                      /* <= 0: dm_lo = 0, dm_hi = 2 dm                                                   */
+} frbch_cand_params;
+typedef struct frbch_cand_result frbch_cand_result;     /* opaque; owns the host arrays of the view                        */
+enum { FRBCH_CAND_T_UPLOAD = 0, FRBCH_CAND_T_FLAG, FRBCH_CAND_T_DEDISPERSE, FRBCH_CAND_T_SEARCH, FRBCH_CAND_T_CUT,
+       FRBCH_CAND_T_DOWNLOAD, FRBCH_CAND_NSTAGE };
+typedef struct frbch_cand_view {
+  uint32_t size, reserved;             /* = sizeof(frbch_cand_view), set by the caller                                    */
+  uint64_t nout, nclipped;
+  uint64_t ncand;                      /* all search records                                                              */
+  const frbch_sp_cand* cands;          /* [ncand]; NULL when ncand = 0                                                    */
+  uint64_t ngroup_all, ngroup;         /* groups of step 3, kept groups of step 4                                         */
+  const frbch_sp_group* groups;        /* [ngroup]; NULL when ngroup = 0                                                  */
+  const frbch_cutout_cand* cut_cands;  /* [ngroup]; NULL when ngroup = 0                                                  */
+  const float* ft;                     /* [ngroup][nf][nt]; the four planes are NULL when there are none                  */
+  const uint32_t* ft_hits;
+  const float* dt;                     /* [ngroup][ndm][nt]                                                               */
+  const uint32_t* dt_hits;
+  uint32_t nblk, reserved2;            /* with FRBCH_CAND_RFI (otherwise 0 and NULL):                                     */
+  const uint8_t* mask;                 /* [nblk][nchan]                                                                   */
+  const double* repl;                  /* [nchan]                                                                         */
+  const uint8_t* chan_flag;            /* [nchan]                                                                         */
+  const uint8_t* blk_flag;             /* [nblk]                                                                          */
+  const float* series;                 /* [ndm][nout] with FRBCH_CAND_SERIES, otherwise NULL                              */
+  uint32_t kernel_used[4];             /* RFI statistics, dedispersion, search, cut-out                                   */
+  uint32_t cutout_calls, row_uploads;  /* batches of step 6; 1 for _host, 0 for _device                                   */
+  /* milliseconds per stage, indexed by FRBCH_CAND_T_*: upload of the rows, flagging (with the mask decision on the host),
+   * dedispersion, search (with the host's merge of the raw peaks), cut-outs, downloads (series and planes) */
+  double wall_ms[FRBCH_CAND_NSTAGE];   /* on the host's clock                                                             */
+  double device_ms[FRBCH_CAND_NSTAGE]; /* between two events on the stage's stream, summed over its device calls          */
+} frbch_cand_view;
+int frbch_candidates_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const double* dms, uint32_t ndm,
+                          const frbch_cand_params* par, int device, frbch_cand_result** out, char* err, size_t err_cap);
+int frbch_candidates_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const double* dms, uint32_t ndm,
+                            const frbch_cand_params* par, int device, frbch_cand_result** out, char* err, size_t err_cap);
+/* counts and host pointers, valid until frbch_cand_result_free */
+int frbch_cand_result_view(const frbch_cand_result* res, frbch_cand_view* view);
+void frbch_cand_result_free(frbch_cand_result* res);
+/* Step 4 alone (host only): keep[cap] receives the indices of the kept groups in ascending order, *nkeep their number
+ * (never more than ngroup: cap = ngroup always suffices; fewer: FRBCH_E_CAPACITY). */
+int frbch_cand_select(const frbch_sp_group* groups, uint64_t ngroup, uint32_t min_members, uint32_t max_cands,
+                      uint64_t* keep, uint64_t cap, uint64_t* nkeep);
+
 /* ---- in front of the filterbank: the corner turn -------------------------------
  * jive5ab's spif2file splits the recorder's stream -- every W-bit word holds one time sample of ALL channels -- into one
  * 2-channel stream per IF, driven by the recipe strings of spif2file.sh:31-113, e.g. the 16-channel 2-bit mode
