@@ -8,7 +8,7 @@
 //                       the chain of stages of a scan and the two kernels that may share the chip
 //   frbch_api.cpp       the C ABI of include/frbch.h that works on device memory: life cycle, rescale state, device entry points
 //   frbch_file.cpp      the C ABI that works on host memory and files: push / pull, the pipelined whole-file and scan paths
-//   frbch_post.cpp      behind / in front of the filterbank: dedispersion, fold, corner turn
+//   frbch_post.cpp      behind / in front of the filterbank: C ABI and launches, the only unit that sees kernels_post*.inc
 // Compiled as HIP for gfx950 (FRBCH_DEV_HEADER = "dev_hip.h").  The CPU unit tests compile the same files against
 // tests/emu/dev_emu.h to exercise the host logic without a GPU; that build is test infrastructure and is never loaded by the package.
 #ifndef FRBCH_INTERNAL_H

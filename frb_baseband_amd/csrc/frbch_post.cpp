@@ -1,7 +1,2174 @@
 // libfrbch: behind and in front of the filterbank -- incoherent dedispersion, fold, corner turn; kernels in
-// kernels_post.inc / kernels_post_fast.inc (frbch_internal.h lists the units).
+// kernels_post.inc / kernels_post_fast.inc, which this translation unit alone sees (frbch_internal.h lists the units).
+// C-ABI entry points behind the filterbank (include/frbch.h, "after the filterbank"): incoherent dedispersion of SIGPROC
+// rows with PRESTO's prepdata / prepsubband options as the reference passes them (process_vdif.py:202-229) and the phase
+// fold that base2fil.sh:474 delegates to dspsr.  A stage reads check, plan, launch; what it holds on the device belongs to a
+// PostScope (_device) or a HostStage (_host), which give it back on every return.
 #include "frbch_internal.h"
 
 using namespace frbchi;
 
-#include "frbch_post.inc"
+#include <limits>
+#include <memory>
+#include <new>
+#include <system_error>
+#include <thread>
+
+#include "kernels_post.inc"
+#ifndef FRBCH_NO_FAST
+#include "kernels_post_fast.inc"
+#endif
+
+namespace {
+
+struct PostErr {
+  char* buf;
+  size_t cap;
+  int fail(int code, const std::string& msg) const {
+    if (buf && cap) snprintf(buf, cap, "%s", msg.c_str());
+    return code;
+  }
+};
+
+// Device time of a stage for frbch_candidates_*: while `tl_stage_ms` points somewhere (this thread is inside such a call), a
+// _device entry point adds the time between two events on its own stream -- its first and its last work -- to it.
+thread_local double* tl_stage_ms = nullptr;
+struct StageClock {
+  dev_stream_t s = 0;
+  dev_event_t a, b;
+  bool on = false;
+  StageClock() = default;
+  explicit StageClock(dev_stream_t stream) { start(stream); }
+  void start(dev_stream_t stream) {
+    s = stream;
+    if (!tl_stage_ms || dev_event_create(&a) != 0) return;
+    if (dev_event_create(&b) != 0) { dev_event_destroy(a); return; }
+    dev_event_record(a, s);
+    on = true;
+  }
+  void finish() {                       // before the stream goes
+    if (!on) return;
+    on = false;
+    dev_event_record(b, s);
+    *tl_stage_ms += (double)dev_event_ms(a, b);
+    dev_event_destroy(a);
+    dev_event_destroy(b);
+  }
+};
+
+// a device-layer call of a _device entry point that fails ends the call; its PostScope gives back what the call holds
+#define POST_DEV(expr, what) do { if ((expr) != 0) return e.fail(FRBCH_E_DEVICE, std::string(what) + ": " + dev_last_error_string()); } while (0)
+
+// What one _device call holds on the device: its non-blocking stream (s == 0: it could not be made), the clock of its stage
+// (PostScope(false): none; it starts here, so a stage makes its scope where its device work begins) and what alloc() hands out.
+struct PostScope {
+  dev_stream_t s = 0;
+  StageClock clk;
+  std::vector<void*> held;
+  explicit PostScope(bool clock = true) {
+    if (dev_stream_create(&s) != 0) s = 0;
+    else if (clock) clk.start(s);
+  }
+  PostScope(const PostScope&) = delete; PostScope& operator=(const PostScope&) = delete;
+  template <class T> int alloc(T** p, size_t bytes) {
+    held.push_back(nullptr);            // (a std::bad_alloc before the block exists, not with it in hand)
+    if (dev_malloc(&held.back(), bytes) != 0) { held.pop_back(); return -1; }
+    *p = (T*)held.back();
+    return 0;
+  }
+  template <class T> void drop(T*& p) {   // a buffer that is done with before the call is: freed now, and forgotten
+    held.erase(std::remove(held.begin(), held.end(), (void*)p), held.end());
+    dev_free((void*)p);
+    p = nullptr;
+  }
+  // On every return, or before it where the host has work left: the clock first, then the blocks in the order they were
+  // allocated, then the stream.  The order is not cosmetic: StageClock::finish records its second event, frbch_candidates_* report
+  // the difference as device time, and hipFree waits for the device -- a clock finished behind the frees would add them to it.
+  void release() {                      // (a second call finds nothing left)
+    clk.finish();
+    for (void* q : held) dev_free(q);
+    held.clear();
+    if (s) dev_stream_destroy(s);
+    s = 0;
+  }
+  ~PostScope() { release(); }
+};
+
+// The buffers of a _host twin: device copies of the caller's host arrays, allocated as they are named (after the first failure
+// `failed` is set and nothing more is allocated).  upload() / download() put every `in` / `out` buffer on one stream -- the NULL
+// stream, unless the caller has its own -- with one sync behind them.  The destructor frees, in that order, what drop() has not.
+struct HostStage {
+  enum { kIn = 1, kOut = 2, kCap = 20 };
+  struct Buf { void* host; void* dev; size_t bytes; int dir; };
+  Buf b[kCap];
+  int n = 0;
+  bool failed = false;
+  HostStage() = default; HostStage(const HostStage&) = delete; HostStage& operator=(const HostStage&) = delete;
+  void* add(int dir, const void* host, size_t bytes) {
+    void* d = nullptr;
+    if (failed || n == kCap || dev_malloc(&d, bytes) != 0) { failed = true; return nullptr; }
+    b[n++] = Buf{(void*)host, d, bytes, host ? dir : 0};                       // (no host array: nothing to copy)
+    return d;
+  }
+  template <class T> T* in(const T* host, size_t bytes) { return (T*)add(kIn, host, bytes); }
+  template <class T> T* out(T* host, size_t bytes) { return (T*)add(kOut, host, bytes); }
+  template <class T> T* inout(T* host, size_t bytes) { return (T*)add(kIn | kOut, host, bytes); }
+  void* scratch(size_t bytes) { return add(0, nullptr, bytes); }                  // the caller copies by hand
+  int upload(dev_stream_t s = 0) {
+    for (int i = 0; i < n; ++i)
+      if ((b[i].dir & kIn) && dev_h2d(b[i].dev, b[i].host, b[i].bytes, s) != 0) return -1;
+    return dev_sync(s);
+  }
+  int download(dev_stream_t s = 0) {          // (no `out` buffer: no sync either)
+    bool any = false;
+    for (int i = 0; i < n; ++i)
+      if (b[i].dir & kOut) { any = true; if (dev_d2h(b[i].host, b[i].dev, b[i].bytes, s) != 0) return -1; }
+    return any ? dev_sync(s) : 0;
+  }
+  // the skeleton of a _host twin: the uploads, the _device twin, the downloads; the texts of the three failures
+  template <class F> int run(const PostErr& e, const char* nomem, const char* up, const char* down, F device_twin) {
+    if (failed) return e.fail(FRBCH_E_NOMEM, nomem);
+    if (upload() != 0) return e.fail(FRBCH_E_DEVICE, up);
+    const int rc = device_twin();
+    return !rc && download() != 0 ? e.fail(FRBCH_E_DEVICE, down) : rc;
+  }
+  void drop(const void* p) {                  // a buffer that is done with before the call is
+    for (int i = 0; i < n; ++i)
+      if (b[i].dev == p) { dev_free(b[i].dev); b[i] = Buf{nullptr, nullptr, 0, 0}; }
+  }
+  ~HostStage() { for (int i = 0; i < n; ++i) dev_free(b[i].dev); }
+};
+
+int post_check_device(int device, const PostErr& e) {
+  if (device < 0 || device >= dev_count()) return e.fail(FRBCH_E_DEVICE, "no such GPU (there is no CPU fallback)");
+  return FRBCH_OK;
+}
+
+// the tests every entry point that takes rows begins with (rfi_check goes on from here with its own)
+int post_check_layout(const frbch_fil_desc* f, const PostErr& e) {
+  if (!f || f->size != sizeof(frbch_fil_desc)) return e.fail(FRBCH_E_ARG, "frbch_fil_desc: wrong size");
+  if (f->nchan < 1 || f->nifs < 1 || f->product >= f->nifs) return e.fail(FRBCH_E_ARG, "bad nchan / nifs / product");
+  if (f->nbits != 8 && f->nbits != 16 && f->nbits != 32) return e.fail(FRBCH_E_ARG, "nbits must be 8, 16 or 32 (float)");
+  return FRBCH_OK;
+}
+
+int post_check_fil(const frbch_fil_desc* f, uint64_t nrows, const PostErr& e) {
+  const int rc = post_check_layout(f, e);
+  if (rc) return rc;
+  if (!(f->tsamp_s > 0) || f->foff_mhz == 0.0 || !(f->fch1_mhz > 0)) return e.fail(FRBCH_E_ARG, "bad tsamp / fch1 / foff");
+  if (!nrows) return e.fail(FRBCH_E_ARG, "no rows");
+  return FRBCH_OK;
+}
+
+size_t post_rows_bytes(const frbch_fil_desc* fil, uint64_t nrows) { return (size_t)nrows * fil->nifs * fil->nchan * (size_t)(fil->nbits / 8); }
+
+// the fields PostParams, FoldpParams, CutParams and RfiParams share; everything else zero
+template <class P> P post_params(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows) {
+  P p;
+  memset(&p, 0, sizeof p);
+  p.rows = (decltype(p.rows))d_rows;
+  p.nrows = nrows;
+  p.nchan = (int)fil->nchan; p.nifs = (int)fil->nifs; p.nbits = fil->nbits;
+  return p;
+}
+
+#ifndef FRBCH_NO_FAST
+// a kernel with dynamic LDS: the permission for `lds` bytes, then the launch; != 0: the permission was refused
+template <class K, class P> int launch_lds(K kern, dim3 grid, dim3 block, size_t lds, dev_stream_t s, const P& p) {
+  if (dev_allow_lds(kern, lds) != 0) return -1;
+  hipLaunchKernelGGL(kern, grid, block, lds, s, p);
+  return 0;
+}
+
+template <int B> int launch_dedisp_tiled(bool flagged, bool zerodm, dim3 grid, size_t lds, dev_stream_t s, const PostParams& p) {
+  if (flagged && zerodm) return launch_lds(fast::frbch_post_dedisp_tiled<B, true, true>, grid, dim3(256), lds, s, p);
+  if (flagged) return launch_lds(fast::frbch_post_dedisp_tiled<B, true, false>, grid, dim3(256), lds, s, p);
+  if (zerodm) return launch_lds(fast::frbch_post_dedisp_tiled<B, false, true>, grid, dim3(256), lds, s, p);
+  return launch_lds(fast::frbch_post_dedisp_tiled<B, false, false>, grid, dim3(256), lds, s, p);
+}
+#endif
+
+// delay of channel c relative to the highest channel frequency of the file, seconds (DSPSR / PRESTO constant 1/2.41e-4)
+double post_delay_s(const frbch_fil_desc* f, double dm, uint32_t c) {
+  const double fc = f->fch1_mhz + (double)c * f->foff_mhz;
+  const double f_last = f->fch1_mhz + (double)(f->nchan - 1) * f->foff_mhz;
+  const double fhi = f->foff_mhz < 0 ? f->fch1_mhz : f_last;
+  return dm / kDmDispersion * (1.0 / (fc * fc) - 1.0 / (fhi * fhi));
+}
+
+std::vector<int32_t> post_delays(const frbch_fil_desc* f, const double* dms, uint32_t ndm, int64_t* maxd) {
+  std::vector<int32_t> d((size_t)ndm * f->nchan);
+  *maxd = 0;
+  for (uint32_t i = 0; i < ndm; ++i)
+    for (uint32_t c = 0; c < f->nchan; ++c) {
+      const double s = post_delay_s(f, dms[i], c) / f->tsamp_s;
+      const int64_t n = (int64_t)(s + 0.5);                 // PRESTO rounds the bin delay the same way
+      d[(size_t)i * f->nchan + c] = (int32_t)n;
+      *maxd = std::max<int64_t>(*maxd, n);
+    }
+  return d;
+}
+
+constexpr uint64_t kPostChunkRows = 4096;
+
+// Which dedispersion kernel a call takes -- the one decision behind frbch_dedisperse_device's launch and
+// frbch_dedisperse_kernel's answer.  true = the LDS-tiled kernel (kernels_post_fast.inc): whole 64-byte channel tiles,
+// 16-byte pieces of every row (only the ADDRESS of d_rows is examined), and every (DM group, channel tile) fits its rows into
+// the LDS; *range then holds [DM group][channel tile] (smallest delay, rows spanned beyond the time tile).  The emulator
+// build has no such kernel: false.
+bool post_dedisp_tiled(const frbch_fil_desc* fil, const void* d_rows, const std::vector<int32_t>& delays, uint32_t ndm,
+                       std::vector<int32_t>* range) {
+#ifndef FRBCH_NO_FAST
+  const int bpv = fil->nbits / 8, ct = 64 / bpv;
+  if (fil->nchan % ct != 0 || ((uintptr_t)d_rows % 16) != 0 || ((size_t)fil->nchan * bpv) % 16 != 0) return false;
+  const int nct = (int)fil->nchan / ct, ngrp = (int)((ndm + fast::kDedND - 1) / fast::kDedND);
+  range->assign((size_t)ngrp * nct * 2, 0);
+  for (int g = 0; g < ngrp; ++g)
+    for (int k = 0; k < nct; ++k) {
+      int32_t lo = INT32_MAX, hi = 0;
+      for (uint32_t d = (uint32_t)g * fast::kDedND; d < std::min<uint32_t>(ndm, (uint32_t)(g + 1) * fast::kDedND); ++d)
+        for (int c = k * ct; c < (k + 1) * ct; ++c) {
+          const int32_t v = delays[(size_t)d * fil->nchan + c];
+          lo = std::min(lo, v);
+          hi = std::max(hi, v);
+        }
+      (*range)[((size_t)g * nct + k) * 2] = lo;
+      (*range)[((size_t)g * nct + k) * 2 + 1] = hi - lo;
+      if (fast::kDedTT + (hi - lo) > fast::kDedRowsCap) return false;
+    }
+  return true;
+#else
+  (void)fil; (void)d_rows; (void)delays; (void)ndm; (void)range;
+  return false;
+#endif
+}
+
+}  // namespace
+
+extern "C" long frbch_dedisperse_nout(const frbch_fil_desc* fil, uint64_t nrows, const double* dms, uint32_t ndm) {
+  PostErr e{nullptr, 0};
+  if (post_check_fil(fil, nrows, e) || !dms || !ndm) return FRBCH_E_ARG;
+  for (uint32_t i = 0; i < ndm; ++i)
+    if (!(dms[i] >= 0.0) || !(dms[i] < 1.0e5)) return FRBCH_E_ARG;
+  int64_t maxd = 0;
+  (void)post_delays(fil, dms, ndm, &maxd);
+  return (int64_t)nrows > maxd ? (long)((int64_t)nrows - maxd) : 0;
+}
+
+extern "C" int frbch_dedisperse_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const double* dms,
+                                       uint32_t ndm) {
+  if (!d_rows || frbch_dedisperse_nout(fil, nrows, dms, ndm) <= 0) return FRBCH_E_ARG;   // what frbch_dedisperse_device refuses
+  int64_t maxd = 0;
+  const std::vector<int32_t> delays = post_delays(fil, dms, ndm, &maxd);
+  std::vector<int32_t> range;
+  return post_dedisp_tiled(fil, d_rows, delays, ndm, &range) ? 1 : 0;
+}
+
+extern "C" int frbch_dedisperse_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const double* dms,
+                                       uint32_t ndm, uint32_t zerodm, double clip_sigma, int device, float* d_out,
+                                       uint64_t nout, uint64_t* nclipped, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  int rc = post_check_fil(fil, nrows, e);
+  if (rc) return rc;
+  if (!d_rows || !d_out || !dms || !ndm) return e.fail(FRBCH_E_ARG, "null argument");
+  const long want = frbch_dedisperse_nout(fil, nrows, dms, ndm);
+  if (want <= 0) return e.fail(FRBCH_E_ARG, "the largest dispersion delay exceeds the data");
+  if ((uint64_t)want != nout) return e.fail(FRBCH_E_CAPACITY, "nout must be frbch_dedisperse_nout()");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  int64_t maxd = 0;
+  const std::vector<int32_t> delays = post_delays(fil, dms, ndm, &maxd);
+  const uint64_t nchunk = (nrows + kPostChunkRows - 1) / kPostChunkRows;
+  double *d_rowsum = nullptr, *d_colsum = nullptr, *d_repl = nullptr;
+  uint8_t* d_flag = nullptr;
+  int32_t* d_delays = nullptr;
+  PostScope ps;
+  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  const dev_stream_t s = ps.s;
+  POST_DEV(ps.alloc(&d_rowsum, nrows * sizeof(double)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_delays, delays.size() * sizeof(int32_t)), "hipMalloc");
+  POST_DEV(dev_h2d(d_delays, delays.data(), delays.size() * sizeof(int32_t), s), "upload delays");
+  PostParams p = post_params<PostParams>(fil, d_rows, nrows);
+  p.prod = (int)fil->product;
+  p.rowsum = d_rowsum;
+  p.delays = d_delays;
+  p.out = d_out;
+  p.nout = nout;
+  p.ndm = (int)ndm;
+  p.zerodm = zerodm ? 1 : 0;
+  p.rows_per_chunk = kPostChunkRows;
+  uint64_t nflag = 0;
+  if (clip_sigma > 0.0 || zerodm) {
+    DEV_LAUNCH(frbch_post_rowsum, (nrows + 255) / 256, 1, 256, 0, s, p);
+    POST_DEV(dev_check_launch(), "launch rowsum");
+  }
+  if (clip_sigma > 0.0) {
+    // time-domain clip on the zero-DM series S[t] (the sum over channels): two rounds of mean / sigma, the second without
+    // the samples the first one flagged; a flagged time sample reads as the channel means of the unflagged ones
+    std::vector<double> S(nrows);
+    POST_DEV(dev_d2h(S.data(), d_rowsum, nrows * sizeof(double), s), "download row sums");
+    POST_DEV(dev_sync(s), "sync");
+    std::vector<uint8_t> flag(nrows, 0);
+    for (int round = 0; round < 2; ++round) {
+      double s1 = 0.0, s2 = 0.0;
+      uint64_t n = 0;
+      for (uint64_t t = 0; t < nrows; ++t)
+        if (!flag[t]) { s1 += S[t]; s2 += S[t] * S[t]; ++n; }
+      if (!n) break;
+      const double mean = s1 / (double)n;
+      const double var = s2 / (double)n - mean * mean;
+      const double sig = var > 0.0 ? sqrt(var) : 0.0;
+      const double lim = clip_sigma * sig;
+      for (uint64_t t = 0; t < nrows; ++t) flag[t] = (uint8_t)(fabs(S[t] - mean) > lim ? 1 : 0);
+    }
+    for (uint64_t t = 0; t < nrows; ++t) nflag += flag[t];
+    if (nflag && nflag < nrows) {
+      POST_DEV(ps.alloc(&d_flag, nrows), "hipMalloc");
+      POST_DEV(dev_h2d(d_flag, flag.data(), nrows, s), "upload flags");
+      POST_DEV(ps.alloc(&d_colsum, nchunk * fil->nchan * sizeof(double)), "hipMalloc");
+      POST_DEV(ps.alloc(&d_repl, fil->nchan * sizeof(double)), "hipMalloc");
+      p.flagged = d_flag;
+      p.colsum = d_colsum;
+      DEV_LAUNCH(frbch_post_colsum, (fil->nchan + 255) / 256, nchunk, 256, 0, s, p);
+      POST_DEV(dev_check_launch(), "launch colsum");
+      std::vector<double> part(nchunk * fil->nchan), repl(fil->nchan);
+      POST_DEV(dev_d2h(part.data(), d_colsum, part.size() * sizeof(double), s), "download column sums");
+      POST_DEV(dev_sync(s), "sync");
+      const double ngood = (double)(nrows - nflag);
+      for (uint32_t c = 0; c < fil->nchan; ++c) {
+        double m = 0.0;
+        for (uint64_t k = 0; k < nchunk; ++k) m += part[k * fil->nchan + c];
+        repl[c] = fil->nbits == 32 ? m / ngood : floor(m / ngood + 0.5);     // integer rows stay integer
+      }
+      POST_DEV(dev_h2d(d_repl, repl.data(), repl.size() * sizeof(double), s), "upload replacements");
+      p.repl = d_repl;
+      if (zerodm) {
+        DEV_LAUNCH(frbch_post_rowsum, (nrows + 255) / 256, 1, 256, 0, s, p);   // S[t] of the clipped rows
+        POST_DEV(dev_check_launch(), "launch rowsum");
+      }
+    } else {
+      nflag = 0;
+    }
+  }
+  std::vector<int32_t> range;
+  const bool tiled = post_dedisp_tiled(fil, d_rows, delays, ndm, &range);
+#ifndef FRBCH_NO_FAST
+  if (tiled) {
+    const int bpv = fil->nbits / 8, ngrp = (int)((ndm + fast::kDedND - 1) / fast::kDedND);
+    int32_t* d_range = nullptr;
+    POST_DEV(ps.alloc(&d_range, range.size() * sizeof(int32_t)), "hipMalloc");
+    POST_DEV(dev_h2d(d_range, range.data(), range.size() * sizeof(int32_t), s), "upload tile ranges");
+    POST_DEV(dev_sync(s), "sync");
+    p.tile_range = d_range;
+    const size_t lds = (size_t)fast::kDedRowsCap * fast::kDedRowB + 16 + (size_t)fast::kDedRowsCap * 9;
+    const dim3 grid((unsigned)((nout + fast::kDedTT - 1) / fast::kDedTT), (unsigned)ngrp);
+    const bool fl = p.flagged != nullptr, zd = p.zerodm != 0;
+    int refused;
+    if (bpv == 1) refused = launch_dedisp_tiled<1>(fl, zd, grid, lds, s, p);
+    else if (bpv == 2) refused = launch_dedisp_tiled<2>(fl, zd, grid, lds, s, p);
+    else refused = launch_dedisp_tiled<4>(fl, zd, grid, lds, s, p);
+    POST_DEV(refused, "LDS size");
+  }
+#endif
+  if (!tiled) DEV_LAUNCH(frbch_post_dedisp, (nout + 255) / 256, ndm, 256, 0, s, p);
+  POST_DEV(dev_check_launch(), "launch dedisp");
+  POST_DEV(dev_sync(s), "sync");
+  if (nclipped) *nclipped = nflag;
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_dedisperse_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const double* dms,
+                                     uint32_t ndm, uint32_t zerodm, double clip_sigma, int device, float* out,
+                                     uint64_t nout, uint64_t* nclipped, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  int rc = post_check_fil(fil, nrows, e);
+  if (rc) return rc;
+  if (!rows || !out) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
+  float* d_out = hs.out(out, (size_t)ndm * nout * sizeof(float));
+  return hs.run(e, "device memory for the rows", "upload rows", "download series",
+                [&]() { return frbch_dedisperse_device(fil, d_rows, nrows, dms, ndm, zerodm, clip_sigma, device, d_out, nout, nclipped, err, err_cap); });
+}
+
+extern "C" long frbch_fold_nsub(const frbch_fil_desc* fil, uint64_t nrows, double subint_s) {
+  PostErr e{nullptr, 0};
+  if (post_check_fil(fil, nrows, e) || !(subint_s > 0)) return FRBCH_E_ARG;
+  const uint64_t rps = std::max<uint64_t>(1, (uint64_t)llround(subint_s / fil->tsamp_s));
+  return (long)((nrows + rps - 1) / rps);       // the last sub-integration may be short (dspsr -L keeps it too)
+}
+
+extern "C" int frbch_fold_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, double f0_hz, double f1,
+                                 double pepoch_mjd, double dm, uint32_t apply_delays, uint32_t nbin, double subint_s,
+                                 int device, double* d_profile, uint32_t* d_hits, uint32_t nsub, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  int rc = post_check_fil(fil, nrows, e);
+  if (rc) return rc;
+  if (!d_rows || !d_profile || !d_hits) return e.fail(FRBCH_E_ARG, "null argument");
+  if (!(f0_hz > 0) || nbin < 2 || nbin > 65536) return e.fail(FRBCH_E_ARG, "F0 must be positive, nbin in [2, 65536]");
+  const long want = frbch_fold_nsub(fil, nrows, subint_s);
+  if (want <= 0 || (uint32_t)want != nsub) return e.fail(FRBCH_E_CAPACITY, "nsub must be frbch_fold_nsub()");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  PostScope ps(false);                                     // (no stage of frbch_candidates_*: no clock)
+  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  const dev_stream_t s = ps.s;
+  const size_t nslot = (size_t)nsub * nbin * fil->nchan;
+  unsigned long long* d_sum_i = nullptr;
+  double* d_dly = nullptr;
+  PostParams p = post_params<PostParams>(fil, d_rows, nrows);
+  p.prod = (int)fil->product;
+  p.hits = d_hits;
+  POST_DEV(dev_memset(d_hits, 0, nslot * sizeof(uint32_t), s), "clear hits");
+  POST_DEV(dev_memset(d_profile, 0, nslot * sizeof(double), s), "clear profile");
+  const bool integer_rows = fil->nbits != 32;
+  if (integer_rows) {      // exact uint64 sums, converted to double at the end
+    POST_DEV(ps.alloc(&d_sum_i, nslot * sizeof(unsigned long long)), "hipMalloc");
+    POST_DEV(dev_memset(d_sum_i, 0, nslot * sizeof(unsigned long long), s), "clear sums");
+    p.prof_i = d_sum_i;
+  } else {
+    p.prof_f = d_profile;
+  }
+  if (apply_delays && dm != 0.0) {
+    std::vector<double> dly(fil->nchan);
+    for (uint32_t c = 0; c < fil->nchan; ++c) dly[c] = post_delay_s(fil, dm, c);
+    POST_DEV(ps.alloc(&d_dly, dly.size() * sizeof(double)), "hipMalloc");
+    POST_DEV(dev_h2d(d_dly, dly.data(), dly.size() * sizeof(double), s), "upload delays");
+    POST_DEV(dev_sync(s), "sync");
+    p.chan_delay_s = d_dly;
+  }
+  p.t0_s = (fil->tstart_mjd - pepoch_mjd) * 86400.0;
+  p.tsamp_s = fil->tsamp_s;
+  p.f0 = f0_hz;
+  p.half_f1 = 0.5 * f1;
+  p.nbin = (int)nbin;
+  p.rows_per_sub = std::max<uint64_t>(1, (uint64_t)llround(subint_s / fil->tsamp_s));
+  p.nsub = nsub;
+  p.rows_per_chunk = 512;
+  DEV_LAUNCH(frbch_post_fold, (fil->nchan + 255) / 256, (nrows + p.rows_per_chunk - 1) / p.rows_per_chunk, 256, 0, s, p);
+  POST_DEV(dev_check_launch(), "launch fold");
+  if (integer_rows) {
+    // exact integer sums -> double (every value < 2^53)
+    std::vector<unsigned long long> tmp(nslot);
+    POST_DEV(dev_d2h(tmp.data(), d_sum_i, nslot * sizeof(unsigned long long), s), "download sums");
+    POST_DEV(dev_sync(s), "sync");
+    std::vector<double> dbl(nslot);
+    for (size_t i = 0; i < nslot; ++i) dbl[i] = (double)tmp[i];
+    POST_DEV(dev_h2d(d_profile, dbl.data(), nslot * sizeof(double), s), "upload profile");
+  }
+  POST_DEV(dev_sync(s), "sync");
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_fold_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, double f0_hz, double f1,
+                               double pepoch_mjd, double dm, uint32_t apply_delays, uint32_t nbin, double subint_s,
+                               int device, double* profile, uint32_t* hits, uint32_t nsub, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  int rc = post_check_fil(fil, nrows, e);
+  if (rc) return rc;
+  if (!rows || !profile || !hits) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  const size_t nslot = (size_t)nsub * nbin * fil->nchan;
+  HostStage hs;
+  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
+  double* d_prof = hs.out(profile, nslot * sizeof(double));
+  uint32_t* d_hits = hs.out(hits, nslot * sizeof(uint32_t));
+  return hs.run(e, "device memory for the rows", "upload rows", "download profile", [&]() {
+    return frbch_fold_device(fil, d_rows, nrows, f0_hz, f1, pepoch_mjd, dm, apply_delays, nbin, subint_s, device, d_prof, d_hits, nsub, err, err_cap);
+  });
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// fold of every product with a phase model (polynomial + Doppler factor, or TEMPO polyco blocks)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+// the model as the kernels read it: blocks relative to the start of the file, first row of every block
+int foldp_model(const frbch_fil_desc* fil, uint64_t nrows, const frbch_fold_model* m, std::vector<FoldSeg>* seg,
+                std::vector<uint64_t>* seg_row, const PostErr& e) {
+  if (!m || m->size != sizeof(frbch_fold_model)) return e.fail(FRBCH_E_ARG, "frbch_fold_model: wrong size");
+  if (m->nbin < 2 || m->nbin > 65536) return e.fail(FRBCH_E_ARG, "nbin must be in [2, 65536]");
+  if (!m->nseg) {
+    if (!(m->f0_hz > 0)) return e.fail(FRBCH_E_ARG, "F0 must be positive");
+    if (!(m->doppler > -1.0) || !(m->doppler < 1.0)) return e.fail(FRBCH_E_ARG, "doppler must lie in (-1, 1)");
+    return FRBCH_OK;
+  }
+  if (!m->seg) return e.fail(FRBCH_E_ARG, "nseg > 0 without blocks");
+  if (m->doppler != 0.0) return e.fail(FRBCH_E_ARG, "doppler together with a polyco: a polyco is topocentric already");
+  const double last_s = (double)(nrows - 1) * fil->tsamp_s;
+  bool first_in = false, last_in = false;
+  for (uint32_t i = 0; i < m->nseg; ++i) {
+    const frbch_polyco_seg& g = m->seg[i];
+    if (g.ncoeff < 1 || g.ncoeff > 15) return e.fail(FRBCH_E_ARG, "polyco block " + std::to_string(i) + ": ncoeff must be 1..15");
+    if (!(g.span_min > 0) || !(g.f0_hz > 0)) return e.fail(FRBCH_E_ARG, "polyco block " + std::to_string(i) + ": span and F0 must be positive");
+    if (i && !(g.tmid_mjd > m->seg[i - 1].tmid_mjd)) return e.fail(FRBCH_E_ARG, "polyco blocks must be in ascending TMID order");
+    FoldSeg f;
+    memset(&f, 0, sizeof f);
+    f.dt0_min = (fil->tstart_mjd - g.tmid_mjd) * 1440.0;
+    f.rphase = g.rphase_frac;
+    f.f0 = g.f0_hz;
+    f.ncoeff = (int)g.ncoeff;
+    for (uint32_t k = 0; k < g.ncoeff; ++k) f.coeff[k] = g.coeff[k];
+    seg->push_back(f);
+    uint64_t first = 0;
+    if (i) {
+      const double x = ((0.5 * (m->seg[i - 1].tmid_mjd + g.tmid_mjd) - fil->tstart_mjd) * 86400.0) / fil->tsamp_s;
+      first = x <= 0.0 ? 0 : (x >= (double)nrows ? nrows : (uint64_t)ceil(x));
+    }
+    seg_row->push_back(first);
+    if (fabs(f.dt0_min) <= 0.5 * g.span_min) first_in = true;
+    if (fabs(f.dt0_min + last_s / 60.0) <= 0.5 * g.span_min) last_in = true;
+  }
+  if (!first_in || !last_in)
+    return e.fail(FRBCH_E_ARG, std::string(first_in ? "the last" : "the first") + " row lies outside the span of every polyco block");
+  return FRBCH_OK;
+}
+}  // namespace
+
+extern "C" int frbch_foldp_device(const frbch_fil_desc* fil_in, const void* d_rows, uint64_t nrows, const frbch_fold_model* m,
+                                  int device, double* d_profile, uint32_t* d_hits, uint32_t nsub, uint32_t* kernel_used,
+                                  char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  if (!fil_in || fil_in->size != sizeof(frbch_fil_desc)) return e.fail(FRBCH_E_ARG, "frbch_fil_desc: wrong size");
+  frbch_fil_desc fd = *fil_in;
+  fd.product = 0;                                          // every product is folded
+  const frbch_fil_desc* fil = &fd;
+  int rc = post_check_fil(fil, nrows, e);
+  if (rc) return rc;
+  if (fil->nifs > 4) return e.fail(FRBCH_E_ARG, "nifs must be 1..4");
+  if (!d_rows || !d_profile || !d_hits) return e.fail(FRBCH_E_ARG, "null argument");
+  std::vector<FoldSeg> seg;
+  std::vector<uint64_t> seg_row;
+  rc = foldp_model(fil, nrows, m, &seg, &seg_row, e);
+  if (rc) return rc;
+  const long want = frbch_fold_nsub(fil, nrows, m->subint_s);
+  if (want <= 0 || (uint32_t)want != nsub) return e.fail(FRBCH_E_CAPACITY, "nsub must be frbch_fold_nsub()");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  PostScope ps(false);
+  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  const dev_stream_t s = ps.s;
+  const uint32_t nbin = m->nbin;
+  const size_t nslot = (size_t)nsub * nbin * fil->nchan, nsum = nslot * fil->nifs;
+  unsigned long long* d_sum_i = nullptr;
+  double* d_dly = nullptr;
+  FoldSeg* d_seg = nullptr;
+  uint64_t* d_seg_row = nullptr;
+  FoldpParams p = post_params<FoldpParams>(fil, d_rows, nrows);
+  p.nbin = (int)nbin;
+  p.hits = d_hits;
+  const bool integer_rows = fil->nbits != 32;
+  if (integer_rows) {      // exact uint64 sums, converted to double at the end
+    POST_DEV(ps.alloc(&d_sum_i, nsum * sizeof(unsigned long long)), "hipMalloc");
+    POST_DEV(dev_memset(d_sum_i, 0, nsum * sizeof(unsigned long long), s), "clear sums");
+    p.prof_i = d_sum_i;
+  } else {
+    POST_DEV(dev_memset(d_profile, 0, nsum * sizeof(double), s), "clear profile");
+  }
+  p.prof_f = d_profile;
+  std::vector<double> dly;
+  if (m->apply_delays && m->dm != 0.0) {
+    dly.resize(fil->nchan);
+    for (uint32_t c = 0; c < fil->nchan; ++c) dly[c] = post_delay_s(fil, m->dm, c);
+    POST_DEV(ps.alloc(&d_dly, dly.size() * sizeof(double)), "hipMalloc");
+    POST_DEV(dev_h2d(d_dly, dly.data(), dly.size() * sizeof(double), s), "upload delays");
+    p.chan_delay_s = d_dly;
+  }
+  if (!seg.empty()) {
+    POST_DEV(ps.alloc(&d_seg, seg.size() * sizeof(FoldSeg)), "hipMalloc");
+    POST_DEV(ps.alloc(&d_seg_row, seg_row.size() * sizeof(uint64_t)), "hipMalloc");
+    POST_DEV(dev_h2d(d_seg, seg.data(), seg.size() * sizeof(FoldSeg), s), "upload polyco blocks");
+    POST_DEV(dev_h2d(d_seg_row, seg_row.data(), seg_row.size() * sizeof(uint64_t), s), "upload block rows");
+    p.seg = d_seg;
+    p.seg_row = d_seg_row;
+    p.nseg = (int)seg.size();
+  }
+  p.t0_s = (fil->tstart_mjd - m->pepoch_mjd) * 86400.0;
+  p.tsamp_s = fil->tsamp_s;
+  p.f0 = m->f0_hz;
+  p.half_f1 = 0.5 * m->f1;
+  p.doppler = m->doppler;
+  p.rows_per_sub = std::max<uint64_t>(1, (uint64_t)llround(m->subint_s / fil->tsamp_s));
+  p.nsub = nsub;
+  uint32_t used = 0;
+#ifndef FRBCH_NO_FAST
+  {   // the LDS kernel: integer rows, the bin a function of the row only, a tile of >= 16 channels x nbin in the LDS
+    const int bpv = fil->nbits / 8;
+    int ct = 0, ct_log2 = 0;
+    for (int k = 8; k >= 4; --k)
+      if (fil->nchan % (1u << k) == 0 && (size_t)nbin * (1u << k) * sizeof(uint32_t) <= fast::kFoldLdsBudget) { ct = 1 << k; ct_log2 = k; break; }
+    const uint64_t row_cap = bpv == 1 ? (1ull << 24) : (1ull << 16);      // a uint32 sum of a run cannot overflow
+    if (integer_rows && !p.chan_delay_s && ct && ((uintptr_t)d_rows % 4) == 0 && (uint64_t)nsub * nbin < 0xFFFFFFFFull &&
+        (uint64_t)(fil->nchan / ct) * fil->nifs <= 65535) {
+      p.ct = ct;
+      p.ct_log2 = ct_log2;
+      p.ntile = (int)fil->nchan / ct;
+      const uint64_t nbase = (uint64_t)p.ntile * fil->nifs * nsub;          // workgroups with one row run per sub-integration
+      const uint64_t wg_goal = (uint64_t)fast::kFoldWgPerCu * std::max(1, dev_cu_count(device));
+      const uint64_t per_sub = std::max<uint64_t>(1, (wg_goal + nbase - 1) / nbase);
+      p.rows_per_chunk = std::min(row_cap, std::max<uint64_t>(fast::kFoldThreads, (p.rows_per_sub + per_sub - 1) / per_sub));
+      p.chunks_per_sub = (uint32_t)((p.rows_per_sub + p.rows_per_chunk - 1) / p.rows_per_chunk);
+      if ((uint64_t)nsub * p.chunks_per_sub <= 0x7FFFFFFFull) {
+        uint32_t *d_slot = nullptr, *d_slot_hits = nullptr;
+        POST_DEV(ps.alloc(&d_slot, nrows * sizeof(uint32_t)), "hipMalloc");
+        POST_DEV(ps.alloc(&d_slot_hits, (size_t)nsub * nbin * sizeof(uint32_t)), "hipMalloc");
+        POST_DEV(dev_memset(d_slot_hits, 0, (size_t)nsub * nbin * sizeof(uint32_t), s), "clear slot counts");
+        p.slot = d_slot;
+        p.slot_hits = d_slot_hits;
+        p.nconv = nslot;
+        hipLaunchKernelGGL(fast::frbch_post_foldp_slots, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, s, p);
+        POST_DEV(dev_check_launch(), "launch fold slots");
+        hipLaunchKernelGGL(fast::frbch_post_foldp_hits, dim3((unsigned)((nslot + 255) / 256)), dim3(256), 0, s, p);
+        POST_DEV(dev_check_launch(), "launch fold hits");
+        const size_t lds = (size_t)nbin * ct * sizeof(uint32_t);
+        const dim3 grid((unsigned)((uint64_t)nsub * p.chunks_per_sub), (unsigned)(p.ntile * fil->nifs));
+        if (bpv == 1) POST_DEV(launch_lds(fast::frbch_post_foldp_lds<1>, grid, dim3(fast::kFoldThreads), lds, s, p), "LDS size");
+        else POST_DEV(launch_lds(fast::frbch_post_foldp_lds<2>, grid, dim3(fast::kFoldThreads), lds, s, p), "LDS size");
+        POST_DEV(dev_check_launch(), "launch fold");
+        used = 1;
+      }
+    }
+  }
+#endif
+  if (!used) {
+    POST_DEV(dev_memset(d_hits, 0, nslot * sizeof(uint32_t), s), "clear hits");
+    p.rows_per_chunk = 512;
+    DEV_LAUNCH(frbch_post_foldp, (fil->nchan + 255) / 256, (nrows + p.rows_per_chunk - 1) / p.rows_per_chunk, 256, 0, s, p);
+    POST_DEV(dev_check_launch(), "launch fold");
+  }
+  if (integer_rows) {
+    p.prof_f = d_profile;
+    p.nconv = nsum;
+    DEV_LAUNCH(frbch_post_u64_to_f64, (nsum + 255) / 256, 1, 256, 0, s, p);
+    POST_DEV(dev_check_launch(), "launch convert");
+  }
+  POST_DEV(dev_sync(s), "sync");       // (also: the host vectors the uploads read stay alive until here)
+  if (kernel_used) *kernel_used = used;
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_foldp_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_fold_model* m, int device,
+                                double* profile, uint32_t* hits, uint32_t nsub, uint32_t* kernel_used, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  if (!fil || fil->size != sizeof(frbch_fil_desc)) return e.fail(FRBCH_E_ARG, "frbch_fil_desc: wrong size");
+  frbch_fil_desc fd = *fil;
+  fd.product = 0;
+  int rc = post_check_fil(&fd, nrows, e);
+  if (rc) return rc;
+  if (!rows || !profile || !hits) return e.fail(FRBCH_E_ARG, "null argument");
+  if (!m || m->size != sizeof(frbch_fold_model)) return e.fail(FRBCH_E_ARG, "frbch_fold_model: wrong size");
+  if (m->nbin < 2 || m->nbin > 65536) return e.fail(FRBCH_E_ARG, "nbin must be in [2, 65536]");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  const size_t nslot = (size_t)nsub * m->nbin * fil->nchan, nsum = nslot * fil->nifs;
+  HostStage hs;
+  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
+  double* d_prof = hs.out(profile, nsum * sizeof(double));
+  uint32_t* d_hits = hs.out(hits, nslot * sizeof(uint32_t));
+  return hs.run(e, "device memory for the rows", "upload rows", "download profile",
+                [&]() { return frbch_foldp_device(fil, d_rows, nrows, m, device, d_prof, d_hits, nsub, kernel_used, err, err_cap); });
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// single-pulse search of the dedispersed series
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr uint32_t kSpRawCap = 1u << 20;     // raw peaks the device list holds (24 MiB); more: FRBCH_E_CAPACITY, never a cut list
+
+int sp_check(const frbch_sp_params* sp, uint64_t* blk_len, const PostErr& e) {
+  if (!sp || sp->size != sizeof(frbch_sp_params)) return e.fail(FRBCH_E_ARG, "frbch_sp_params: wrong size");
+  if (!(sp->threshold > 0.0) || !(sp->threshold <= 1.0e6)) return e.fail(FRBCH_E_ARG, "threshold must lie in (0, 1e6]");
+  if (sp->nwidth < 1 || sp->nwidth > 16) return e.fail(FRBCH_E_ARG, "1..16 widths");
+  for (uint32_t k = 0; k < sp->nwidth; ++k)
+    if (sp->widths[k] < 1 || sp->widths[k] > 1024 || (k && sp->widths[k] <= sp->widths[k - 1]))
+      return e.fail(FRBCH_E_ARG, "widths must be strictly ascending, each 1..1024");
+  *blk_len = sp->detrend_len ? sp->detrend_len : 1000;
+  if (*blk_len < 64 || *blk_len > 65536) return e.fail(FRBCH_E_ARG, "detrend_len must be 0 (= 1000) or 64..65536");
+  return FRBCH_OK;
+}
+
+// Which search kernel a call takes -- the one decision behind frbch_spsearch_device's launch and *kernel_used.  true = the
+// LDS kernel (kernels_post_fast.inc): the tile and the halo of the largest LISTED width (one that exceeds nout included)
+// fit its prefix array, kSpTile + 2 wmax <= kSpLdsN, and sample indices fit 32 bits.  The emulator build has no such
+// kernel: false.
+bool sp_search_lds(const frbch_sp_params* sp, uint64_t nout) {
+#ifndef FRBCH_NO_FAST
+  return (int)sp->widths[sp->nwidth - 1] <= fast::kSpMaxWidth && nout < (1ull << 31);
+#else
+  (void)sp; (void)nout;
+  return false;
+#endif
+}
+
+struct SpRaw {
+  uint32_t width;
+  uint64_t centre;
+  long long sum;
+  double sigma;
+};
+// frbch_spsearch_device; with `all` every candidate goes there instead (cands and cap are then not looked at, and no
+// number of candidates is a capacity error): frbch_candidates_* own their list
+int sp_search_run(const float* d_series, uint32_t ndm, uint64_t nout, const frbch_sp_params* sp, int device, frbch_sp_cand* cands,
+                  uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, std::vector<frbch_sp_cand>* all, char* err, size_t err_cap);
+}  // namespace
+
+extern "C" int frbch_spsearch_device(const float* d_series, uint32_t ndm, uint64_t nout, const frbch_sp_params* sp, int device,
+                                     frbch_sp_cand* cands, uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, char* err,
+                                     size_t err_cap) try {
+  return sp_search_run(d_series, ndm, nout, sp, device, cands, cap, ncand, kernel_used, nullptr, err, err_cap);
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+namespace {
+int sp_search_run(const float* d_series, uint32_t ndm, uint64_t nout, const frbch_sp_params* sp, int device, frbch_sp_cand* cands,
+                  uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, std::vector<frbch_sp_cand>* all, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  uint64_t blk_len = 0;
+  int rc = sp_check(sp, &blk_len, e);
+  if (rc) return rc;
+  if (!d_series || !ncand || (!all && cap && !cands)) return e.fail(FRBCH_E_ARG, "null argument");
+  if (!ndm || !nout || ndm > 65535) return e.fail(FRBCH_E_ARG, "ndm must be 1..65535, nout positive");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  SpParams p;
+  memset(&p, 0, sizeof p);
+  p.series = d_series;
+  p.nout = nout;
+  p.ndm = (int)ndm;
+  p.blk_len = blk_len;
+  p.nblk = (uint32_t)std::max<uint64_t>(1, nout / blk_len);
+  p.nwidth = (int)sp->nwidth;
+  for (uint32_t k = 0; k < sp->nwidth; ++k) {
+    p.width[k] = (int)sp->widths[k];
+    const double scaled = sp->threshold * 1024.0;
+    const double t = ceil(scaled * sqrt((double)sp->widths[k]));
+    p.thr[k] = t < 9.0e18 ? (long long)t : INT64_MAX;             // (no sum reaches 2^37)
+  }
+  p.peak_cap = kSpRawCap;
+  PostScope ps;
+  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  const dev_stream_t s = ps.s;
+  POST_DEV(ps.alloc(&p.stats, (size_t)ndm * p.nblk * 2 * sizeof(double)), "hipMalloc");
+  POST_DEV(ps.alloc(&p.peaks, (size_t)kSpRawCap * sizeof(SpPeak)), "hipMalloc");
+  POST_DEV(ps.alloc(&p.npeak, sizeof(uint32_t)), "hipMalloc");
+  POST_DEV(dev_memset(p.npeak, 0, sizeof(uint32_t), s), "clear peak count");
+  DEV_LAUNCH(frbch_post_sp_stats, p.nblk, ndm, kSpPartials, (3 * kSpPartials + 2) * sizeof(double), s, p);
+  POST_DEV(dev_check_launch(), "launch block statistics");
+  const bool lds = sp_search_lds(sp, nout);
+#ifndef FRBCH_NO_FAST
+  if (lds)
+    hipLaunchKernelGGL(fast::frbch_post_sp_search_lds, dim3((unsigned)((nout + fast::kSpTile - 1) / fast::kSpTile), ndm),
+                       dim3(fast::kSpThreads), 0, s, p);
+#endif
+  if (!lds) {
+    POST_DEV(ps.alloc(&p.q, (size_t)ndm * nout * sizeof(int32_t)), "hipMalloc");
+    DEV_LAUNCH(frbch_post_sp_quant, (nout + 255) / 256, ndm, 256, 0, s, p);
+    POST_DEV(dev_check_launch(), "launch quantise");
+    DEV_LAUNCH(frbch_post_sp_search, (nout + 255) / 256, ndm, 256, 0, s, p);
+  }
+  POST_DEV(dev_check_launch(), "launch search");
+  uint32_t nraw = 0;
+  POST_DEV(dev_d2h(&nraw, p.npeak, sizeof nraw, s), "download peak count");
+  POST_DEV(dev_sync(s), "sync");
+  if (nraw > kSpRawCap)
+    return e.fail(FRBCH_E_CAPACITY, "threshold too low: " + std::to_string(nraw) + " raw peaks, the device list holds " +
+                                        std::to_string(kSpRawCap));
+  std::vector<SpPeak> raw(nraw);
+  if (nraw) {
+    POST_DEV(dev_d2h(raw.data(), p.peaks, (size_t)nraw * sizeof(SpPeak), s), "download peaks");
+    POST_DEV(dev_sync(s), "sync");
+  }
+  ps.release();                           // the device is done with; the host goes on with the raw list
+  if (kernel_used) *kernel_used = lds ? 1 : 0;
+  // across widths, DM by DM, on the raw list (one pass, not iterated): a raw peak falls to a stronger one whose centre
+  // lies within half the larger of the two widths; equal sigma: the narrower wins, then the earlier
+  std::sort(raw.begin(), raw.end(), [](const SpPeak& a, const SpPeak& b) {
+    return a.dm != b.dm ? a.dm < b.dm : a.t + a.width / 2 != b.t + b.width / 2 ? a.t + a.width / 2 < b.t + b.width / 2 : a.width < b.width;
+  });
+  uint64_t total = 0;
+  std::vector<SpRaw> one;
+  const uint64_t reach = sp->widths[sp->nwidth - 1] / 2;
+  for (size_t i0 = 0; i0 < raw.size();) {
+    size_t i1 = i0;
+    one.clear();
+    for (; i1 < raw.size() && raw[i1].dm == raw[i0].dm; ++i1) {
+      SpRaw r;
+      r.width = raw[i1].width;
+      r.centre = raw[i1].t + raw[i1].width / 2;
+      r.sum = raw[i1].sum;
+      r.sigma = (double)raw[i1].sum / (1024.0 * sqrt((double)raw[i1].width));
+      one.push_back(r);
+    }
+    size_t first = 0;                                             // one[first ..) may still lie within `reach` of one[i]
+    for (size_t i = 0; i < one.size(); ++i) {
+      const SpRaw& a = one[i];
+      while (one[first].centre + reach < a.centre) ++first;
+      bool dropped = false;
+      for (size_t j = first; j < one.size() && one[j].centre <= a.centre + reach && !dropped; ++j) {
+        if (j == i) continue;
+        const SpRaw& b = one[j];
+        const uint64_t dist = a.centre > b.centre ? a.centre - b.centre : b.centre - a.centre;
+        if (dist > std::max(a.width, b.width) / 2) continue;
+        dropped = b.sigma > a.sigma || (b.sigma == a.sigma && (b.width < a.width || (b.width == a.width && b.centre < a.centre)));
+      }
+      if (dropped) continue;
+      if (all || total < cap) {                                   // (centre, width) ascending already: the output order
+        frbch_sp_cand c;
+        c.dm_index = raw[i0].dm;
+        c.width = a.width;
+        c.sample = a.centre;
+        c.sigma = (float)a.sigma;
+        c.reserved = 0;
+        if (all) all->push_back(c);
+        else cands[total] = c;
+      }
+      ++total;
+    }
+    i0 = i1;
+  }
+  *ncand = total;
+  if (!all && total > cap) return e.fail(FRBCH_E_CAPACITY, std::to_string(total) + " candidates, room for " + std::to_string(cap));
+  return FRBCH_OK;
+}
+}  // namespace
+
+extern "C" int frbch_spsearch_host(const float* series, uint32_t ndm, uint64_t nout, const frbch_sp_params* sp, int device,
+                                   frbch_sp_cand* cands, uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, char* err,
+                                   size_t err_cap) {
+  PostErr e{err, err_cap};
+  uint64_t blk_len = 0;
+  int rc = sp_check(sp, &blk_len, e);
+  if (rc) return rc;
+  if (!series || !ndm || !nout) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  float* d_series = hs.in(series, (size_t)ndm * nout * sizeof(float));
+  return hs.run(e, "device memory for the series", "upload series", "download",
+                [&]() { return frbch_spsearch_device(d_series, ndm, nout, sp, device, cands, cap, ncand, kernel_used, err, err_cap); });
+}
+
+extern "C" int frbch_dedisperse_search_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const double* dms,
+                                            uint32_t ndm, uint32_t zerodm, double clip_sigma, const frbch_sp_params* sp,
+                                            int device, float* series_out, uint64_t nout, uint64_t* nclipped,
+                                            frbch_sp_cand* cands, uint64_t cap, uint64_t* ncand, uint32_t* kernel_used,
+                                            char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  int rc = post_check_fil(fil, nrows, e);
+  if (rc) return rc;
+  uint64_t blk_len = 0;
+  rc = sp_check(sp, &blk_len, e);
+  if (rc) return rc;
+  if (!rows || !ncand || (cap && !cands)) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
+  float* d_out = hs.out(series_out, (size_t)ndm * nout * sizeof(float));          // (series_out may be null: no download then)
+  if (hs.failed) return e.fail(FRBCH_E_NOMEM, "device memory for the rows");
+  if (hs.upload() != 0) return e.fail(FRBCH_E_DEVICE, "upload rows");
+  rc = frbch_dedisperse_device(fil, d_rows, nrows, dms, ndm, zerodm, clip_sigma, device, d_out, nout, nclipped, err, err_cap);
+  hs.drop(d_rows);                                                 // the plane stays in HBM; the rows are done with
+  if (!rc && series_out && hs.download() != 0) rc = e.fail(FRBCH_E_DEVICE, "download series");
+  if (!rc) rc = frbch_spsearch_device(d_out, ndm, nout, sp, device, cands, cap, ncand, kernel_used, err, err_cap);
+  return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// candidates: grouping across DMs (host only) and the two cut-out planes
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+bool sp_better(const frbch_sp_cand& a, const frbch_sp_cand& b) {        // a represents a group rather than b
+  if (a.sigma != b.sigma) return a.sigma > b.sigma;
+  if (a.width != b.width) return a.width < b.width;
+  if (a.dm_index != b.dm_index) return a.dm_index < b.dm_index;
+  return a.sample < b.sample;
+}
+}  // namespace
+
+extern "C" int frbch_sp_group_cands(const frbch_fil_desc* fil, const double* dms, uint32_t ndm, const frbch_sp_cand* cands,
+                                    uint64_t ncand, uint32_t dm_gap, frbch_sp_group* groups, uint64_t cap, uint64_t* ngroup,
+                                    char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  int rc = post_check_fil(fil, 1, e);
+  if (rc) return rc;
+  if (!dms || !ndm || !ngroup || (ncand && !cands) || (cap && !groups)) return e.fail(FRBCH_E_ARG, "null argument");
+  if (dm_gap < 1 || dm_gap > 16) return e.fail(FRBCH_E_ARG, "dm_gap must be 1..16");
+  for (uint32_t i = 0; i < ndm; ++i)
+    if (!(dms[i] >= 0.0) || !(dms[i] < 1.0e5)) return e.fail(FRBCH_E_ARG, "a DM outside [0, 1e5)");
+  for (uint64_t i = 0; i < ncand; ++i)
+    if (cands[i].dm_index >= ndm) return e.fail(FRBCH_E_ARG, "record " + std::to_string(i) + ": dm_index >= ndm");
+  *ngroup = 0;
+  if (!ncand) return FRBCH_OK;
+  // D_i: the largest delay of DM i, and the largest |D_a - D_b| two linked records can have
+  int64_t maxd = 0;
+  const std::vector<int32_t> delays = post_delays(fil, dms, ndm, &maxd);
+  std::vector<int64_t> D(ndm, 0);
+  for (uint32_t i = 0; i < ndm; ++i)
+    for (uint32_t c = 0; c < fil->nchan; ++c) D[i] = std::max<int64_t>(D[i], delays[(size_t)i * fil->nchan + c]);
+  int64_t smear = 0;
+  for (uint32_t i = 0; i < ndm; ++i)
+    for (uint32_t j = i + 1; j < ndm && j - i <= dm_gap; ++j) smear = std::max<int64_t>(smear, std::llabs(D[i] - D[j]));
+  uint32_t wmax = 0;
+  for (uint64_t i = 0; i < ncand; ++i) wmax = std::max(wmax, cands[i].width);
+  const uint64_t reach = (uint64_t)(wmax / 2) + (uint64_t)smear;       // no two linked records lie further apart
+  // sweep in sample order: record i meets the later ones within `reach`; union-find joins the linked pairs
+  std::vector<uint64_t> order(ncand), parent(ncand);
+  for (uint64_t i = 0; i < ncand; ++i) order[i] = parent[i] = i;
+  std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {
+    return cands[a].sample != cands[b].sample ? cands[a].sample < cands[b].sample : a < b;
+  });
+  auto find = [&](uint64_t x) {
+    while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; }
+    return x;
+  };
+  for (uint64_t i = 0; i < ncand; ++i) {
+    const frbch_sp_cand& a = cands[order[i]];
+    for (uint64_t j = i + 1; j < ncand && cands[order[j]].sample - a.sample <= reach; ++j) {
+      const frbch_sp_cand& b = cands[order[j]];
+      const uint32_t ddm = a.dm_index > b.dm_index ? a.dm_index - b.dm_index : b.dm_index - a.dm_index;
+      if (ddm > dm_gap) continue;
+      const uint64_t tol = (uint64_t)(std::max(a.width, b.width) / 2) + (uint64_t)std::llabs(D[a.dm_index] - D[b.dm_index]);
+      if (b.sample - a.sample > tol) continue;
+      const uint64_t ra = find(order[i]), rb = find(order[j]);
+      if (ra != rb) parent[std::max(ra, rb)] = std::min(ra, rb);
+    }
+  }
+  std::vector<int64_t> slot(ncand, -1);                                  // root -> index in `out`
+  std::vector<frbch_sp_group> out;
+  for (uint64_t i = 0; i < ncand; ++i) {
+    const uint64_t r = find(i);
+    const frbch_sp_cand& c = cands[i];
+    if (slot[r] < 0) {
+      slot[r] = (int64_t)out.size();
+      frbch_sp_group g;
+      memset(&g, 0, sizeof g);
+      g.best = c;
+      g.best.reserved = 0;
+      g.nmember = 1;
+      g.dm_index_lo = g.dm_index_hi = c.dm_index;
+      g.sample_lo = g.sample_hi = c.sample;
+      out.push_back(g);
+      continue;
+    }
+    frbch_sp_group& g = out[(size_t)slot[r]];
+    if (sp_better(c, g.best)) { g.best = c; g.best.reserved = 0; }
+    ++g.nmember;
+    g.dm_index_lo = std::min(g.dm_index_lo, c.dm_index);
+    g.dm_index_hi = std::max(g.dm_index_hi, c.dm_index);
+    g.sample_lo = std::min(g.sample_lo, c.sample);
+    g.sample_hi = std::max(g.sample_hi, c.sample);
+  }
+  std::sort(out.begin(), out.end(), [](const frbch_sp_group& a, const frbch_sp_group& b) {
+    if (a.best.dm_index != b.best.dm_index) return a.best.dm_index < b.best.dm_index;
+    if (a.best.sample != b.best.sample) return a.best.sample < b.best.sample;
+    if (a.best.width != b.best.width) return a.best.width < b.best.width;
+    return a.sample_lo < b.sample_lo;                                    // (two groups with the same best key: duplicate records apart)
+  });
+  *ngroup = out.size();
+  for (uint64_t i = 0; i < std::min<uint64_t>(cap, out.size()); ++i) groups[i] = out[i];
+  if (out.size() > cap) return e.fail(FRBCH_E_CAPACITY, std::to_string(out.size()) + " groups, room for " + std::to_string(cap));
+  return FRBCH_OK;
+}
+
+namespace {
+constexpr uint64_t kCutTableCap = 1ull << 26;    // delay-table entries of one call (256 MiB); a longer batch is refused
+
+// the part of cut_check that needs no candidate (frbch_candidates_* refuse a bad `cut` before they have any)
+int cut_check_par(const frbch_fil_desc* fil, const frbch_cutout_params* par, const PostErr& e) {
+  if (!par || par->size != sizeof(frbch_cutout_params)) return e.fail(FRBCH_E_ARG, "frbch_cutout_params: wrong size");
+  if (par->nt < 2 || par->nt > 1024 || (par->nt & 1)) return e.fail(FRBCH_E_ARG, "nt must be even, 2..1024");
+  if (par->nf < 1 || fil->nchan % par->nf != 0) return e.fail(FRBCH_E_ARG, "nf must divide nchan");
+  if (par->ndm < 1 || par->ndm > 1024) return e.fail(FRBCH_E_ARG, "ndm must be 1..1024");
+  return FRBCH_OK;
+}
+
+int cut_check(const frbch_fil_desc* fil, uint64_t nrows, const frbch_cutout_params* par, const frbch_cutout_cand* cands,
+              uint32_t ncand, const PostErr& e) {
+  int rc = post_check_fil(fil, nrows, e);
+  if (rc) return rc;
+  rc = cut_check_par(fil, par, e);
+  if (rc) return rc;
+  if (!cands || ncand < 1 || ncand > 65535) return e.fail(FRBCH_E_ARG, "1..65535 candidates");
+  if ((uint64_t)ncand * par->nf * par->nt >= (1ull << 31) || (uint64_t)ncand * par->ndm * par->nt >= (1ull << 31))
+    return e.fail(FRBCH_E_ARG, "a plane set of 2^31 elements or more");
+  if ((uint64_t)ncand * par->ndm * fil->nchan > kCutTableCap)
+    return e.fail(FRBCH_E_ARG, "ncand * ndm * nchan exceeds 2^26 delays: cut the batch into several calls");
+  if (nrows >= (1ull << 62)) return e.fail(FRBCH_E_ARG, "too many rows");
+  for (uint32_t i = 0; i < ncand; ++i) {
+    const frbch_cutout_cand& c = cands[i];
+    const std::string who = "candidate " + std::to_string(i) + ": ";
+    if (c.tfactor < 1 || c.tfactor > 512) return e.fail(FRBCH_E_ARG, who + "tfactor must be 1..512");
+    if (!(c.dm >= 0.0) || !(c.dm < 1.0e5) || !(c.dm_lo >= 0.0) || !(c.dm_lo < 1.0e5) || !(c.dm_hi >= 0.0) || !(c.dm_hi < 1.0e5))
+      return e.fail(FRBCH_E_ARG, who + "a DM outside [0, 1e5)");
+    if (c.dm_hi < c.dm_lo) return e.fail(FRBCH_E_ARG, who + "dm_hi < dm_lo");
+    if (c.sample < -(1ll << 62) || c.sample > (1ll << 62)) return e.fail(FRBCH_E_ARG, who + "sample out of range");
+  }
+  return FRBCH_OK;
+}
+
+// what the kernels of a call read
+struct CutPlan {
+  std::vector<CutCand> cand;
+  std::vector<int32_t> ft_delays, dt_delays;     // [count][nchan], [count][ndm][nchan]
+  bool lds = false;                              // every tile of both planes fits the LDS kernel
+  std::vector<int32_t> ft_range, dt_range;       // [count][row group][channel tile] (smallest delay, span; span < 0: not the group's)
+  int ft_ngrp = 0, dt_ngrp = 0, nct = 0;
+  int ft_rows = 0, dt_rows = 0;                  // rows of the largest tile
+  unsigned ft_tiles = 1, dt_tiles = 1;           // time tiles of the candidate that needs most
+};
+
+// Which cut-out kernel a call takes -- the one decision behind frbch_cutout_device's launches, *kernel_used and
+// frbch_cutout_kernel's answer.  true = the LDS kernel (kernels_post_fast.inc): 8- / 16-bit rows, whole 64-byte channel
+// tiles, 16-byte pieces of every row (only the ADDRESS of d_rows is examined).  cut_build then still has to find room in
+// the LDS for every (row group, channel tile, time tile).  The emulator build has no such kernel: false.
+bool cut_lds_layout(const frbch_fil_desc* fil, const void* d_rows) {
+#ifndef FRBCH_NO_FAST
+  if (fil->nbits != 8 && fil->nbits != 16) return false;
+  const int bpv = fil->nbits / 8, ct = 64 / bpv;
+  return fil->nchan % ct == 0 && (int)fil->nchan <= fast::kCutMaxChan && ((uintptr_t)d_rows % 16) == 0 &&
+         ((size_t)fil->nifs * fil->nchan * bpv) % 16 == 0;
+#else
+  (void)fil; (void)d_rows;
+  return false;
+#endif
+}
+
+// min / span of delays[r][c] over r in [0, nr) (rows `pitch` apart), c in [c0, c1) -> range[0..1]; false: does not fit
+bool cut_tile_range(const int32_t* delays, int nr, size_t pitch, int c0, int c1, int32_t* range, int* rows_max) {
+#ifndef FRBCH_NO_FAST
+  int32_t lo = INT32_MAX, hi = INT32_MIN;
+  for (int r = 0; r < nr; ++r)
+    for (int c = c0; c < c1; ++c) {
+      const int32_t v = delays[(size_t)r * pitch + c];
+      lo = std::min(lo, v);
+      hi = std::max(hi, v);
+    }
+  range[0] = lo;
+  range[1] = hi - lo;
+  if ((int64_t)hi - lo + fast::kCutTT > fast::kCutRowsCap) return false;
+  *rows_max = std::max(*rows_max, fast::kCutTT + (hi - lo));
+  return true;
+#else
+  (void)delays; (void)nr; (void)pitch; (void)c0; (void)c1; (void)range; (void)rows_max;
+  return false;
+#endif
+}
+
+int cut_build(const frbch_fil_desc* fil, const frbch_cutout_params* par, const frbch_cutout_cand* cands, uint32_t count,
+              bool layout_ok, CutPlan* plan, const PostErr& e) {
+  POST_NO_CONTRACT
+  const uint32_t ndm = par->ndm;
+  // the DMs of both planes, then their delays from post_delays: n_c(.) is what frbch_dedisperse_* computes because it is
+  // computed by the same function
+  std::vector<double> ft_dms(count), dt_dms((size_t)count * ndm);
+  plan->cand.resize(count);
+  for (uint32_t i = 0; i < count; ++i) {
+    const frbch_cutout_cand& c = cands[i];
+    plan->cand[i].t0 = c.sample - (long long)(par->nt / 2) * (long long)c.tfactor;
+    plan->cand[i].tfactor = (int)c.tfactor;
+    plan->cand[i].pad = 0;
+    ft_dms[i] = c.dm;
+    const double step = ndm > 1 ? (c.dm_hi - c.dm_lo) / (double)(ndm - 1) : 0.0;
+    for (uint32_t k = 0; k < ndm; ++k) {
+      const double off = (double)k * step;
+      dt_dms[(size_t)i * ndm + k] = ndm > 1 ? c.dm_lo + off : c.dm_lo;
+    }
+  }
+  int64_t ft_max = 0, dt_max = 0;
+  plan->ft_delays = post_delays(fil, ft_dms.data(), count, &ft_max);
+  plan->dt_delays = post_delays(fil, dt_dms.data(), count * ndm, &dt_max);
+  if (std::max(ft_max, dt_max) > (int64_t)1 << 30) return e.fail(FRBCH_E_ARG, "a dispersion delay of more than 2^30 samples");
+  plan->lds = false;
+#ifndef FRBCH_NO_FAST
+  if (layout_ok) {
+    const uint32_t nchan = fil->nchan;
+    const int ct = 64 / (fil->nbits / 8), nct = (int)nchan / ct, cpb = (int)(nchan / par->nf);
+    const int NR = fast::kCutNR;
+    plan->nct = nct;
+    plan->ft_ngrp = ((int)par->nf + NR - 1) / NR;
+    plan->dt_ngrp = ((int)ndm + NR - 1) / NR;
+    plan->ft_range.assign((size_t)count * plan->ft_ngrp * nct * 2, -1);
+    plan->dt_range.assign((size_t)count * plan->dt_ngrp * nct * 2, -1);
+    plan->ft_rows = plan->dt_rows = fast::kCutTT;
+    plan->ft_tiles = plan->dt_tiles = 1;
+    bool fits = true;
+    for (uint32_t i = 0; i < count && fits; ++i) {
+      const int f = plan->cand[i].tfactor, bpt = f >= fast::kCutTT ? 1 : fast::kCutTT / f;
+      const unsigned tiles = (unsigned)((par->nt + bpt - 1) / bpt);
+      plan->ft_tiles = std::max(plan->ft_tiles, tiles);
+      plan->dt_tiles = std::max(plan->dt_tiles, tiles);
+      for (int g = 0; g < plan->dt_ngrp && fits; ++g) {
+        const int nd = std::min(NR, (int)ndm - g * NR);
+        for (int k = 0; k < nct && fits; ++k)
+          fits = cut_tile_range(&plan->dt_delays[((size_t)i * ndm + (size_t)g * NR) * nchan], nd, nchan, k * ct, (k + 1) * ct,
+                                &plan->dt_range[(((size_t)i * plan->dt_ngrp + g) * nct + k) * 2], &plan->dt_rows);
+      }
+      for (int g = 0; g < plan->ft_ngrp && fits; ++g) {
+        const int c_lo = g * NR * cpb, c_hi = std::min((int)nchan, (g + 1) * NR * cpb);
+        for (int k = c_lo / ct; k <= (c_hi - 1) / ct && fits; ++k)
+          fits = cut_tile_range(&plan->ft_delays[(size_t)i * nchan], 1, nchan, std::max(c_lo, k * ct), std::min(c_hi, (k + 1) * ct),
+                                &plan->ft_range[(((size_t)i * plan->ft_ngrp + g) * nct + k) * 2], &plan->ft_rows);
+      }
+    }
+    plan->lds = fits;
+  }
+#else
+  (void)layout_ok;
+#endif
+  return FRBCH_OK;
+}
+
+}  // namespace
+
+extern "C" int frbch_cutout_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_cutout_params* par,
+                                   const frbch_cutout_cand* cands, uint32_t ncand) {
+  PostErr e{nullptr, 0};
+  int rc = cut_check(fil, nrows, par, cands, ncand, e);
+  if (rc) return rc;
+  if (!d_rows) return FRBCH_E_ARG;
+  CutPlan plan;
+  rc = cut_build(fil, par, cands, ncand, cut_lds_layout(fil, d_rows), &plan, e);
+  return rc ? rc : (plan.lds ? 1 : 0);
+}
+
+extern "C" int frbch_cutout_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_cutout_params* par,
+                                   const frbch_cutout_cand* cands, uint32_t ncand, int device, float* d_ft, uint32_t* d_ft_hits,
+                                   float* d_dt, uint32_t* d_dt_hits, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  int rc = cut_check(fil, nrows, par, cands, ncand, e);
+  if (rc) return rc;
+  if (!d_rows || !d_ft || !d_ft_hits || !d_dt || !d_dt_hits) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  CutPlan plan;
+  rc = cut_build(fil, par, cands, ncand, cut_lds_layout(fil, d_rows), &plan, e);
+  if (rc) return rc;
+  const bool lds = plan.lds;
+  DeviceGuard dg(device);
+  PostScope ps;
+  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  const dev_stream_t s = ps.s;
+  CutCand* d_cand = nullptr;
+  int32_t *d_ftd = nullptr, *d_dtd = nullptr;
+  POST_DEV(ps.alloc(&d_cand, plan.cand.size() * sizeof(CutCand)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_ftd, plan.ft_delays.size() * sizeof(int32_t)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_dtd, plan.dt_delays.size() * sizeof(int32_t)), "hipMalloc");
+  POST_DEV(dev_h2d(d_cand, plan.cand.data(), plan.cand.size() * sizeof(CutCand), s), "upload candidates");
+  POST_DEV(dev_h2d(d_ftd, plan.ft_delays.data(), plan.ft_delays.size() * sizeof(int32_t), s), "upload delays");
+  POST_DEV(dev_h2d(d_dtd, plan.dt_delays.data(), plan.dt_delays.size() * sizeof(int32_t), s), "upload delays");
+  CutParams p = post_params<CutParams>(fil, d_rows, nrows);
+  p.prod = (int)fil->product;
+  p.nt = (int)par->nt; p.nf = (int)par->nf; p.ndm = (int)par->ndm; p.cpb = (int)(fil->nchan / par->nf);
+  p.ncand = (int)ncand;
+  p.cand = d_cand;
+  p.ft_delays = d_ftd;
+  p.dt_delays = d_dtd;
+#ifndef FRBCH_NO_FAST
+  if (lds) {
+    int32_t *d_ftr = nullptr, *d_dtr = nullptr;
+    POST_DEV(ps.alloc(&d_ftr, plan.ft_range.size() * sizeof(int32_t)), "hipMalloc");
+    POST_DEV(ps.alloc(&d_dtr, plan.dt_range.size() * sizeof(int32_t)), "hipMalloc");
+    POST_DEV(dev_h2d(d_ftr, plan.ft_range.data(), plan.ft_range.size() * sizeof(int32_t), s), "upload tile ranges");
+    POST_DEV(dev_h2d(d_dtr, plan.dt_range.data(), plan.dt_range.size() * sizeof(int32_t), s), "upload tile ranges");
+    p.nct = plan.nct;
+    const int bpv = fil->nbits / 8;
+    for (int kind = 0; kind < 2; ++kind) {
+      p.kind = kind;
+      p.out = kind ? d_dt : d_ft;
+      p.hits = kind ? d_dt_hits : d_ft_hits;
+      p.tile_range = kind ? d_dtr : d_ftr;
+      p.ngrp = kind ? plan.dt_ngrp : plan.ft_ngrp;
+      const size_t bytes = std::max((size_t)(kind ? plan.dt_rows : plan.ft_rows) * fast::kCutRowB, fast::kCutRedBytes) + 16;
+      const dim3 grid(kind ? plan.dt_tiles : plan.ft_tiles, (unsigned)p.ngrp, ncand), block(fast::kCutTT);
+      int refused;
+      if (bpv == 1 && kind) refused = launch_lds(fast::frbch_post_cutout_lds<1, 1>, grid, block, bytes, s, p);
+      else if (bpv == 1) refused = launch_lds(fast::frbch_post_cutout_lds<1, 0>, grid, block, bytes, s, p);
+      else if (kind) refused = launch_lds(fast::frbch_post_cutout_lds<2, 1>, grid, block, bytes, s, p);
+      else refused = launch_lds(fast::frbch_post_cutout_lds<2, 0>, grid, block, bytes, s, p);
+      POST_DEV(refused, "LDS size");
+      POST_DEV(dev_check_launch(), "launch cut-out");
+    }
+  }
+#endif
+  if (!lds)
+    for (int kind = 0; kind < 2; ++kind) {
+      p.kind = kind;
+      p.out = kind ? d_dt : d_ft;
+      p.hits = kind ? d_dt_hits : d_ft_hits;
+      const uint64_t npix = (uint64_t)(kind ? par->ndm : par->nf) * par->nt;
+      DEV_LAUNCH(frbch_post_cutout, (npix + 255) / 256, ncand, 256, 0, s, p);
+      POST_DEV(dev_check_launch(), "launch cut-out");
+    }
+  POST_DEV(dev_sync(s), "sync");      // (the host vectors the uploads read stay alive until here)
+  if (kernel_used) *kernel_used = lds ? 1 : 0;
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_cutout_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_cutout_params* par,
+                                 const frbch_cutout_cand* cands, uint32_t ncand, int device, float* ft, uint32_t* ft_hits,
+                                 float* dt, uint32_t* dt_hits, uint32_t* kernel_used, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  int rc = cut_check(fil, nrows, par, cands, ncand, e);
+  if (rc) return rc;
+  if (!rows || !ft || !ft_hits || !dt || !dt_hits) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  const size_t nft = (size_t)ncand * par->nf * par->nt, ndt = (size_t)ncand * par->ndm * par->nt;
+  HostStage hs;
+  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
+  float* d_ft = hs.out(ft, nft * 4);
+  uint32_t* d_fth = hs.out(ft_hits, nft * 4);
+  float* d_dt = hs.out(dt, ndt * 4);
+  uint32_t* d_dth = hs.out(dt_hits, ndt * 4);
+  return hs.run(e, "device memory for the rows and the planes", "upload rows", "download planes",
+                [&]() { return frbch_cutout_device(fil, d_rows, nrows, par, cands, ncand, device, d_ft, d_fth, d_dt, d_dth, kernel_used, err, err_cap); });
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// interference: block statistics, the mask, cleaned rows
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr uint32_t kRfiMaxBlockRows = 1u << 20;
+constexpr uint32_t kRfiGridBlocks = 65535;        // blocks of one launch (grid.y)
+
+int rfi_check(const frbch_fil_desc* f, uint64_t nrows, const frbch_rfi_params* par, uint32_t* nblk, const PostErr& e) {
+  const int rc = post_check_layout(f, e);
+  if (rc) return rc;
+  if (!nrows) return e.fail(FRBCH_E_ARG, "no rows");
+  if (!par || par->size != sizeof(frbch_rfi_params)) return e.fail(FRBCH_E_ARG, "frbch_rfi_params: wrong size");
+  if (par->block_rows < 1 || par->block_rows > kRfiMaxBlockRows) return e.fail(FRBCH_E_ARG, "block_rows must be 1..2^20");
+  if (!(par->t_cell >= 0) || !(par->t_chan >= 0) || std::isinf(par->t_cell) || std::isinf(par->t_chan))
+    return e.fail(FRBCH_E_ARG, "t_cell and t_chan must be finite and not negative");
+  if (!(par->chan_frac >= 0) || !(par->block_frac >= 0) || par->chan_frac > 1.0 || par->block_frac > 1.0)
+    return e.fail(FRBCH_E_ARG, "chan_frac and block_frac must lie in 0..1");
+  const uint64_t n = (nrows + par->block_rows - 1) / par->block_rows;
+  if (n > 0x7FFFFFFFull || (uint64_t)f->nchan > 0x7FFFFFFFull / f->nifs) return e.fail(FRBCH_E_ARG, "too many blocks or channels");
+  *nblk = (uint32_t)n;
+  return FRBCH_OK;
+}
+
+// Which statistics kernel a call takes -- the one decision behind frbch_rfi_stats_device's launch, *kernel_used and
+// frbch_rfi_stats_kernel's answer.  > 0 = the fast kernel (kernels_post_fast.inc) with that many bytes of the row per
+// workgroup: 8- / 16-bit rows, whole 64-byte channel tiles, 16-byte pieces of every row (only the ADDRESS of d_rows is
+// examined); the tile is the largest listed width that divides the row piece.  The emulator build has no such kernel: 0.
+int rfi_fast_tile(const frbch_fil_desc* fil, const void* d_rows) {
+#ifndef FRBCH_NO_FAST
+  if (fil->nbits != 8 && fil->nbits != 16) return 0;
+  const size_t bpv = (size_t)fil->nbits / 8, piece = (size_t)fil->nchan * bpv;
+  if (piece % 64 != 0 || ((uintptr_t)d_rows % 16) != 0 || ((size_t)fil->nifs * piece) % 16 != 0) return 0;
+  for (int w = 1024; w >= 64; w >>= 1)
+    if (piece % (size_t)w == 0) return w;
+  return 0;
+#else
+  (void)fil; (void)d_rows;
+  return 0;
+#endif
+}
+
+RfiParams rfi_params(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_rfi_params* par, uint32_t nblk) {
+  RfiParams p = post_params<RfiParams>(fil, d_rows, nrows);
+  p.prod = (int)fil->product;
+  p.block_rows = par->block_rows;
+  p.nblk = nblk;
+  return p;
+}
+
+// The k-th smallest of v[0 .. n) (no NaN among them); reorders v so that v[k] holds it and nothing before it is larger.
+// Quickselect whose partition passes do not branch on the data: the table of a long file asks for thousands of medians.
+double rfi_select(double* v, size_t n, size_t k) {
+  size_t lo = 0, hi = n;
+  while (hi - lo > 8) {
+    const double a = v[lo], b = v[lo + (hi - lo) / 2], c = v[hi - 1];
+    const double p = std::max(std::min(a, b), std::min(std::max(a, b), c));        // median of three: a value of the range
+    size_t i = lo;
+    for (size_t j = lo; j < hi; ++j) {                                             // [lo, i) < p <= [i, hi)
+      const double x = v[j];
+      v[j] = v[i];
+      v[i] = x;
+      i += x < p ? 1 : 0;
+    }
+    if (k < i) { hi = i; continue; }
+    size_t m = i;
+    for (size_t j = i; j < hi; ++j) {                                              // [i, m) == p < [m, hi)
+      const double x = v[j];
+      v[j] = v[m];
+      v[m] = x;
+      m += x <= p ? 1 : 0;
+    }
+    if (k < m) return p;
+    lo = m;
+  }
+  for (size_t i = lo + 1; i < hi; ++i) {
+    const double x = v[i];
+    size_t j = i;
+    for (; j > lo && v[j - 1] > x; --j) v[j] = v[j - 1];
+    v[j] = x;
+  }
+  return v[k];
+}
+
+// 0.5 * (lower middle + upper middle) of v[0 .. n), n >= 1; reorders v
+double rfi_median(double* v, size_t n) {
+  const size_t k = n / 2;
+  const double hi = rfi_select(v, n, k);
+  double lo = hi;
+  if (!(n & 1)) lo = *std::max_element(v, v + k);
+  return 0.5 * (lo + hi);
+}
+
+// fn(first channel, one past the last) over all channels, on several threads when the table is large: every channel's
+// result depends on that channel alone, so the split changes no bit.  (Measured on the 306 x 1024 table of a 10-s file: the
+// four medians per channel are 20 ms of std::nth_element on one thread, more than the dedispersion the stage stands in
+// front of; rfi_select and the split bring the decision to 2 ms.)  A thread that cannot be started runs in the caller.
+template <class F>
+void rfi_over_channels(uint32_t nchan, uint32_t nblk, F fn) {
+  const uint64_t cells = (uint64_t)nchan * nblk;
+  unsigned nt = cells >= (1u << 16) ? std::min(16u, std::max(1u, std::thread::hardware_concurrency())) : 1u;
+  nt = std::min<unsigned>(nt, nchan);
+  if (nt <= 1) { fn(0u, nchan); return; }
+  std::vector<std::thread> th;
+  th.reserve(nt);
+  const uint32_t per = (nchan + nt - 1) / nt;
+  for (unsigned i = 1; i < nt; ++i) {
+    if (i * per >= nchan) break;
+    const uint32_t c0 = i * per, c1 = std::min(nchan, (i + 1) * per);
+    try {
+      th.emplace_back(fn, c0, c1);
+    } catch (const std::system_error&) {
+      fn(c0, c1);
+    }
+  }
+  fn(0u, std::min(nchan, per));
+  for (auto& t : th) t.join();
+}
+}  // namespace
+
+extern "C" long frbch_rfi_nblk(uint64_t nrows, uint32_t block_rows) {
+  if (!nrows || block_rows < 1 || block_rows > kRfiMaxBlockRows) return FRBCH_E_ARG;
+  return (long)((nrows + block_rows - 1) / block_rows);
+}
+
+extern "C" int frbch_rfi_stats_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_rfi_params* par) {
+  PostErr e{nullptr, 0};
+  uint32_t nblk = 0;
+  const int rc = rfi_check(fil, nrows, par, &nblk, e);
+  if (rc) return rc;
+  if (!d_rows) return FRBCH_E_ARG;
+  return rfi_fast_tile(fil, d_rows) > 0 ? 1 : 0;
+}
+
+extern "C" int frbch_rfi_stats_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_rfi_params* par,
+                                      int device, void* d_stats, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  uint32_t nblk = 0;
+  int rc = rfi_check(fil, nrows, par, &nblk, e);
+  if (rc) return rc;
+  if (!d_rows || !d_stats) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  PostScope ps;
+  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  const dev_stream_t s = ps.s;
+  RfiParams p = rfi_params(fil, d_rows, nrows, par, nblk);
+  p.stats_i = (unsigned long long*)d_stats;
+  p.stats_f = (double*)d_stats;
+  const int tile = rfi_fast_tile(fil, d_rows);
+  for (uint32_t b0 = 0; b0 < nblk; b0 += kRfiGridBlocks) {
+    const uint32_t nb = std::min(kRfiGridBlocks, nblk - b0);
+    p.blk0 = b0;
+#ifndef FRBCH_NO_FAST
+    if (tile > 0) {
+      p.tile_bytes = tile;
+      p.ntile = (int)((size_t)fil->nchan * (fil->nbits / 8) / (size_t)tile);
+      const dim3 grid((unsigned)p.ntile, nb);
+      if (fil->nbits == 8) hipLaunchKernelGGL(fast::frbch_post_rfi_stats_fast<1>, grid, dim3(fast::kRfiThreads), 0, s, p);
+      else hipLaunchKernelGGL(fast::frbch_post_rfi_stats_fast<2>, grid, dim3(fast::kRfiThreads), 0, s, p);
+    }
+#endif
+    if (tile <= 0) DEV_LAUNCH(frbch_post_rfi_stats, (fil->nchan + 255) / 256, nb, 256, 0, s, p);
+    POST_DEV(dev_check_launch(), "launch statistics");
+  }
+  POST_DEV(dev_sync(s), "sync");
+  if (kernel_used) *kernel_used = tile > 0 ? 1 : 0;
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_rfi_stats_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_rfi_params* par,
+                                    int device, void* stats, uint32_t* kernel_used, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  uint32_t nblk = 0;
+  int rc = rfi_check(fil, nrows, par, &nblk, e);
+  if (rc) return rc;
+  if (!rows || !stats) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
+  void* d_stats = hs.out(stats, (size_t)nblk * fil->nchan * 16);
+  return hs.run(e, "device memory for the rows", "upload rows", "download statistics",
+                [&]() { return frbch_rfi_stats_device(fil, d_rows, nrows, par, device, d_stats, kernel_used, err, err_cap); });
+}
+
+// The one decision (include/frbch.h, steps 1 to 8), host only: IEEE double, every operation rounded on its own.
+extern "C" int frbch_rfi_mask(const frbch_fil_desc* fil, const void* stats, uint32_t nblk, uint64_t nrows, const frbch_rfi_params* par,
+                              const uint8_t* zap, const uint8_t* prior, uint8_t* mask, double* repl, uint8_t* chan_flag,
+                              uint8_t* blk_flag, char* err, size_t err_cap) {
+  POST_NO_CONTRACT
+  PostErr e{err, err_cap};
+  uint32_t want = 0;
+  const int rc = rfi_check(fil, nrows, par, &want, e);
+  if (rc) return rc;
+  if (nblk != want) return e.fail(FRBCH_E_ARG, "nblk must be frbch_rfi_nblk()");
+  if (!stats || !mask || !repl || !chan_flag || !blk_flag) return e.fail(FRBCH_E_ARG, "null argument");
+  const uint32_t nchan = fil->nchan;
+  const bool integer_rows = fil->nbits != 32;
+  const uint64_t n_last = nrows - (uint64_t)(nblk - 1) * par->block_rows;          // rows of the last block
+  const double t_cell = par->t_cell;
+  try {
+  std::atomic<bool> oom(false);                     // (a worker's failed allocation must not leave its thread)
+  // mean, std and the cell flags, [channel][block]: a channel's blocks lie side by side for the medians
+  std::vector<double> mean((size_t)nchan * nblk), sdev((size_t)nchan * nblk);
+  std::vector<uint8_t> bad((size_t)nchan * nblk), cell((size_t)nchan * nblk);
+  std::vector<double> m_c(nchan), s_c(nchan);
+  std::vector<uint32_t> nbad(nchan), ncell(nchan);
+  rfi_over_channels(nchan, nblk, [&](uint32_t c0, uint32_t c1) {
+    POST_NO_CONTRACT
+    std::vector<double> a, w, d;
+    try { a.resize(nblk); w.resize(nblk); d.resize(nblk); } catch (const std::bad_alloc&) { oom = true; return; }
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (uint32_t cc = c0; cc < c1; cc += 16) {                                      // step 1, 16 channels of a table row at a time
+      for (uint32_t b = 0; b < nblk; ++b) {
+        const double nb = (double)(b + 1 < nblk ? (uint64_t)par->block_rows : n_last);
+        for (uint32_t c = cc; c < std::min(c1, cc + 16); ++c) {
+          const size_t i = ((size_t)b * nchan + c) * 2;
+          const double S = integer_rows ? (double)((const uint64_t*)stats)[i] : ((const double*)stats)[i];
+          const double Q = integer_rows ? (double)((const uint64_t*)stats)[i + 1] : ((const double*)stats)[i + 1];
+          const double m = S / nb;
+          const double mm = m * m;
+          const double qn = Q / nb;
+          double var = qn - mm;
+          if (var < 0.0) var = 0.0;                                                  // (a NaN stays a NaN)
+          const double sg = sqrt(var);
+          mean[(size_t)c * nblk + b] = m;
+          sdev[(size_t)c * nblk + b] = sg;
+          bad[(size_t)c * nblk + b] = (uint8_t)(std::isfinite(m) && std::isfinite(sg) ? 0 : 1);
+        }
+      }
+    }
+    for (uint32_t c = c0; c < c1; ++c) {
+      double* mu = &mean[(size_t)c * nblk];
+      double* sd = &sdev[(size_t)c * nblk];
+      uint8_t* bd = &bad[(size_t)c * nblk];
+      uint8_t* fl = &cell[(size_t)c * nblk];
+      size_t n = 0;
+      for (uint32_t b = 0; b < nblk; ++b)
+        if (!bd[b]) { a[n] = mu[b]; w[n] = sd[b]; ++n; }
+      nbad[c] = (uint32_t)(nblk - n);
+      if (!n) {
+        m_c[c] = s_c[c] = nan;
+        for (uint32_t b = 0; b < nblk; ++b) fl[b] = 1;
+        ncell[c] = nblk;
+        continue;
+      }
+      for (size_t i = 0; i < n; ++i) d[i] = a[i];                                  // step 2
+      const double mc = rfi_median(d.data(), n);
+      for (size_t i = 0; i < n; ++i) d[i] = w[i];
+      const double sc = rfi_median(d.data(), n);
+      for (size_t i = 0; i < n; ++i) d[i] = fabs(a[i] - mc);
+      const double dmc = 1.4826 * rfi_median(d.data(), n);
+      for (size_t i = 0; i < n; ++i) d[i] = fabs(w[i] - sc);
+      const double dsc = 1.4826 * rfi_median(d.data(), n);
+      m_c[c] = mc;
+      s_c[c] = sc;
+      double lim_m[2], lim_s[2];                                                   // step 3: [0] a whole block, [1] the last one
+      for (int k = 0; k < 2; ++k) {
+        const double nb = (double)(k ? n_last : (uint64_t)par->block_rows);
+        const double fm = sc / sqrt(nb);
+        const double two_n = 2.0 * nb;
+        const double fs = sc / sqrt(two_n);
+        lim_m[k] = t_cell * (dmc > fm ? dmc : fm);
+        lim_s[k] = t_cell * (dsc > fs ? dsc : fs);
+      }
+      uint32_t cnt = 0;
+      for (uint32_t b = 0; b < nblk; ++b) {
+        if (bd[b]) { fl[b] = 1; ++cnt; continue; }
+        const int k = b + 1 < nblk ? 0 : 1;
+        fl[b] = (uint8_t)((fabs(mu[b] - mc) > lim_m[k] || fabs(sd[b] - sc) > lim_s[k]) ? 1 : 0);
+        cnt += fl[b];
+      }
+      ncell[c] = cnt;
+    }
+  });
+  if (oom) return e.fail(FRBCH_E_NOMEM, "host memory for the mask decision");
+  for (uint32_t c = 0; c < nchan; ++c)                                             // step 4
+    chan_flag[c] = (uint8_t)(((zap && zap[c]) || nbad[c] == nblk || s_c[c] == 0.0) ? 1 : 0);
+  if (par->t_chan > 0.0) {                                                         // step 5
+    std::vector<double> v, d;
+    for (uint32_t c = 0; c < nchan; ++c)
+      if (!chan_flag[c]) v.push_back(s_c[c]);
+    if (!v.empty()) {
+      d = v;
+      const double M = rfi_median(d.data(), d.size());
+      for (size_t i = 0; i < v.size(); ++i) d[i] = fabs(v[i] - M);
+      const double D = 1.4826 * rfi_median(d.data(), d.size());
+      const double lim = par->t_chan * D;
+      for (uint32_t c = 0; c < nchan; ++c)
+        if (!chan_flag[c] && fabs(s_c[c] - M) > lim) chan_flag[c] = 1;
+    }
+  }
+  const double chan_lim = par->chan_frac * (double)nblk;                           // step 6
+  uint32_t n_u = 0;
+  for (uint32_t c = 0; c < nchan; ++c) {
+    if (!chan_flag[c] && (double)ncell[c] > chan_lim) chan_flag[c] = 1;
+    n_u += chan_flag[c] ? 0u : 1u;
+  }
+  const double blk_lim = par->block_frac * (double)n_u;
+  std::vector<uint32_t> nb_cells(nblk, 0);
+  for (uint32_t c = 0; c < nchan; ++c)
+    if (!chan_flag[c])
+      for (uint32_t b = 0; b < nblk; ++b) nb_cells[b] += cell[(size_t)c * nblk + b];
+  for (uint32_t b = 0; b < nblk; ++b) blk_flag[b] = (uint8_t)((double)nb_cells[b] > blk_lim ? 1 : 0);
+  rfi_over_channels(nchan, nblk, [&](uint32_t c0, uint32_t c1) {                   // step 7 (`cell` becomes the mask, transposed)
+    for (uint32_t c = c0; c < c1; ++c)
+      for (uint32_t b = 0; b < nblk; ++b)
+        if (chan_flag[c] || blk_flag[b]) cell[(size_t)c * nblk + b] = 1;
+    for (uint32_t b = 0; b < nblk; ++b)
+      for (uint32_t c = c0; c < c1; ++c) {
+        const size_t i = (size_t)b * nchan + c;
+        if (prior && prior[i]) cell[(size_t)c * nblk + b] = 1;
+        mask[i] = cell[(size_t)c * nblk + b];
+      }
+  });
+  const double code_max = fil->nbits == 8 ? 255.0 : 65535.0;
+  rfi_over_channels(nchan, nblk, [&](uint32_t c0, uint32_t c1) {                   // step 8
+    POST_NO_CONTRACT
+    std::vector<double> d;
+    try { d.resize(nblk); } catch (const std::bad_alloc&) { oom = true; return; }
+    for (uint32_t c = c0; c < c1; ++c) {
+      size_t n = 0, nmask = 0;
+      for (uint32_t b = 0; b < nblk; ++b) {
+        if (!cell[(size_t)c * nblk + b]) d[n++] = mean[(size_t)c * nblk + b];
+        else ++nmask;
+      }
+      // (no masked cell: the cells of m_c, the same median; none left: m_c as well)
+      double r = (n && nmask) ? rfi_median(d.data(), n) : m_c[c];
+      if (!std::isfinite(r)) r = 0.0;
+      if (integer_rows) {
+        r = floor(r + 0.5);
+        if (r < 0.0) r = 0.0;
+        if (r > code_max) r = code_max;
+      }
+      repl[c] = r;
+    }
+  });
+  if (oom) return e.fail(FRBCH_E_NOMEM, "host memory for the mask decision");
+  } catch (const std::bad_alloc&) {
+    return e.fail(FRBCH_E_NOMEM, "host memory for the mask decision");
+  }
+  return FRBCH_OK;
+}
+
+extern "C" int frbch_rfi_apply_device(const frbch_fil_desc* fil, void* d_rows, uint64_t nrows, const frbch_rfi_params* par,
+                                      const uint8_t* d_mask, const double* d_repl, int device, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  uint32_t nblk = 0;
+  int rc = rfi_check(fil, nrows, par, &nblk, e);
+  if (rc) return rc;
+  if (!d_rows || !d_mask || !d_repl) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  PostScope ps;
+  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  const dev_stream_t s = ps.s;
+  RfiParams p = rfi_params(fil, d_rows, nrows, par, nblk);
+  p.mask = d_mask;
+  p.repl = d_repl;
+  for (uint32_t b0 = 0; b0 < nblk; b0 += kRfiGridBlocks) {
+    p.blk0 = b0;
+    DEV_LAUNCH(frbch_post_rfi_apply, (fil->nchan + 255) / 256, std::min(kRfiGridBlocks, nblk - b0), 256, 0, s, p);
+    POST_DEV(dev_check_launch(), "launch apply");
+  }
+  POST_DEV(dev_sync(s), "sync");
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_rfi_apply_host(const frbch_fil_desc* fil, void* rows, uint64_t nrows, const frbch_rfi_params* par,
+                                    const uint8_t* mask, const double* repl, int device, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  uint32_t nblk = 0;
+  int rc = rfi_check(fil, nrows, par, &nblk, e);
+  if (rc) return rc;
+  if (!rows || !mask || !repl) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  void* d_rows = hs.inout(rows, post_rows_bytes(fil, nrows));
+  uint8_t* d_mask = hs.in(mask, (size_t)nblk * fil->nchan);
+  double* d_repl = hs.in(repl, fil->nchan * sizeof(double));
+  return hs.run(e, "device memory for the rows", "upload rows", "download rows",
+                [&]() { return frbch_rfi_apply_device(fil, d_rows, nrows, par, d_mask, d_repl, device, err, err_cap); });
+}
+
+extern "C" int frbch_rfi_clean_device(const frbch_fil_desc* fil, void* d_rows, uint64_t nrows, const frbch_rfi_params* par,
+                                      const uint8_t* zap, int device, uint8_t* mask, double* repl, uint8_t* chan_flag,
+                                      uint8_t* blk_flag, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  uint32_t nblk = 0;
+  int rc = rfi_check(fil, nrows, par, &nblk, e);
+  if (rc) return rc;
+  if (!d_rows || !mask || !repl || !chan_flag || !blk_flag) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  const size_t ncell = (size_t)nblk * fil->nchan;
+  std::vector<uint64_t> stats(ncell * 2);                        // (S, Q): uint64 or double, 16 bytes a cell either way
+  HostStage hs;
+  void* d_stats = hs.out((void*)stats.data(), ncell * 16);
+  if (hs.failed) return e.fail(FRBCH_E_NOMEM, "device memory for the statistics");
+  rc = frbch_rfi_stats_device(fil, d_rows, nrows, par, device, d_stats, kernel_used, err, err_cap);
+  if (!rc && hs.download() != 0) rc = e.fail(FRBCH_E_DEVICE, "download statistics");
+  if (!rc) rc = frbch_rfi_mask(fil, stats.data(), nblk, nrows, par, zap, nullptr, mask, repl, chan_flag, blk_flag, err, err_cap);
+  if (rc || std::none_of(mask, mask + ncell, [](uint8_t m) { return m != 0; })) return rc;     // (nothing masked: nothing to write)
+  uint8_t* d_mask = hs.in(mask, ncell);
+  double* d_repl = hs.in(repl, fil->nchan * sizeof(double));
+  if (hs.failed) return e.fail(FRBCH_E_NOMEM, "device memory for the mask");
+  if (hs.upload() != 0) return e.fail(FRBCH_E_DEVICE, "upload mask");
+  return frbch_rfi_apply_device(fil, d_rows, nrows, par, d_mask, d_repl, device, err, err_cap);
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_rfi_clean_host(const frbch_fil_desc* fil, void* rows, uint64_t nrows, const frbch_rfi_params* par,
+                                    const uint8_t* zap, int device, uint8_t* mask, double* repl, uint8_t* chan_flag,
+                                    uint8_t* blk_flag, uint32_t* kernel_used, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  uint32_t nblk = 0;
+  int rc = rfi_check(fil, nrows, par, &nblk, e);
+  if (rc) return rc;
+  if (!rows || !mask || !repl || !chan_flag || !blk_flag) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  void* d_rows = hs.inout(rows, post_rows_bytes(fil, nrows));
+  return hs.run(e, "device memory for the rows", "upload rows", "download rows",
+                [&]() { return frbch_rfi_clean_device(fil, d_rows, nrows, par, zap, device, mask, repl, chan_flag, blk_flag, kernel_used, err, err_cap); });
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// resident rows: every product cleaned in one residency; flagging, search, grouping and cut-outs in one call
+// ---------------------------------------------------------------------------------------------------------------------
+extern "C" int frbch_rfi_cleanp_device(const frbch_fil_desc* fil_in, void* d_rows, uint64_t nrows, const frbch_rfi_params* par,
+                                       const uint8_t* zap, int device, uint8_t* mask, double* repl, uint8_t* chan_flag,
+                                       uint8_t* blk_flag, void* stats_out, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  if (!fil_in || fil_in->size != sizeof(frbch_fil_desc)) return e.fail(FRBCH_E_ARG, "frbch_fil_desc: wrong size");
+  frbch_fil_desc fd = *fil_in;
+  fd.product = 0;                                          // every product is cleaned
+  uint32_t nblk = 0;
+  int rc = rfi_check(&fd, nrows, par, &nblk, e);
+  if (rc) return rc;
+  if (!d_rows || !mask || !repl || !chan_flag || !blk_flag) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  const uint32_t nifs = fd.nifs, nchan = fd.nchan;
+  const size_t ncell = (size_t)nblk * nchan;
+  HostStage hs;                           // (the statistics and the replacements go product by product: copied by hand)
+  void* d_stats = nullptr;
+  uint32_t used_min = 1;
+  try {
+    std::vector<uint64_t> own;                                     // (S, Q): uint64 or double, 16 bytes a cell either way
+    if (!stats_out) own.resize((size_t)nifs * ncell * 2);
+    uint64_t* st = stats_out ? (uint64_t*)stats_out : own.data();
+    d_stats = hs.scratch(ncell * 16);
+    if (hs.failed) rc = e.fail(FRBCH_E_NOMEM, "device memory for the statistics");
+    for (uint32_t p = 0; p < nifs && !rc; ++p) {
+      uint32_t used = 0;
+      fd.product = p;
+      rc = frbch_rfi_stats_device(&fd, d_rows, nrows, par, device, d_stats, &used, err, err_cap);
+      if (!rc && (dev_d2h(st + (size_t)p * ncell * 2, d_stats, ncell * 16, 0) != 0 || dev_sync(0) != 0))
+        rc = e.fail(FRBCH_E_DEVICE, "download statistics");
+      used_min = std::min(used_min, used);
+    }
+    // every product's own decision, their union, then -- several products -- the decision again with the union as prior
+    std::vector<uint8_t> m1(ncell), cf1(nchan), bf1(nblk);
+    memset(mask, 0, ncell);
+    memset(chan_flag, 0, nchan);
+    memset(blk_flag, 0, nblk);
+    for (uint32_t p = 0; p < nifs && !rc; ++p) {
+      fd.product = p;
+      rc = frbch_rfi_mask(&fd, st + (size_t)p * ncell * 2, nblk, nrows, par, zap, nullptr, m1.data(), repl + (size_t)p * nchan,
+                          cf1.data(), bf1.data(), err, err_cap);
+      for (size_t i = 0; i < ncell; ++i) mask[i] |= m1[i];
+      for (uint32_t c = 0; c < nchan; ++c) chan_flag[c] |= cf1[c];
+      for (uint32_t b = 0; b < nblk; ++b) blk_flag[b] |= bf1[b];
+    }
+    for (uint32_t p = 0; p < nifs && nifs > 1 && !rc; ++p) {
+      fd.product = p;
+      rc = frbch_rfi_mask(&fd, st + (size_t)p * ncell * 2, nblk, nrows, par, zap, mask, m1.data(), repl + (size_t)p * nchan,
+                          cf1.data(), bf1.data(), err, err_cap);
+    }
+  } catch (const std::bad_alloc&) {
+    rc = e.fail(FRBCH_E_NOMEM, "host memory for the statistics");
+  }
+  if (!rc && std::any_of(mask, mask + ncell, [](uint8_t m) { return m != 0; })) {      // (nothing masked: nothing to write)
+    uint8_t* d_mask = hs.in(mask, ncell);
+    double* d_repl = (double*)hs.scratch(nchan * sizeof(double));
+    if (hs.failed) rc = e.fail(FRBCH_E_NOMEM, "device memory for the mask");
+    if (!rc && hs.upload() != 0) rc = e.fail(FRBCH_E_DEVICE, "upload mask");
+    for (uint32_t p = 0; p < nifs && !rc; ++p) {
+      fd.product = p;
+      if (dev_h2d(d_repl, repl + (size_t)p * nchan, nchan * sizeof(double), 0) != 0 || dev_sync(0) != 0)
+        rc = e.fail(FRBCH_E_DEVICE, "upload replacements");
+      if (!rc) rc = frbch_rfi_apply_device(&fd, d_rows, nrows, par, d_mask, d_repl, device, err, err_cap);
+    }
+  }
+  if (!rc && kernel_used) *kernel_used = used_min;
+  return rc;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_rfi_cleanp_host(const frbch_fil_desc* fil, void* rows, uint64_t nrows, const frbch_rfi_params* par,
+                                     const uint8_t* zap, int device, uint8_t* mask, double* repl, uint8_t* chan_flag,
+                                     uint8_t* blk_flag, void* stats, uint32_t* kernel_used, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  if (!fil || fil->size != sizeof(frbch_fil_desc)) return e.fail(FRBCH_E_ARG, "frbch_fil_desc: wrong size");
+  frbch_fil_desc fd = *fil;
+  fd.product = 0;
+  uint32_t nblk = 0;
+  int rc = rfi_check(&fd, nrows, par, &nblk, e);
+  if (rc) return rc;
+  if (!rows || !mask || !repl || !chan_flag || !blk_flag) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  void* d_rows = hs.inout(rows, post_rows_bytes(fil, nrows));
+  return hs.run(e, "device memory for the rows", "upload rows", "download rows",
+                [&]() { return frbch_rfi_cleanp_device(fil, d_rows, nrows, par, zap, device, mask, repl, chan_flag, blk_flag, stats, kernel_used, err, err_cap); });
+}
+
+struct frbch_cand_result {
+  uint64_t nout = 0, nclipped = 0, ngroup_all = 0;
+  std::vector<frbch_sp_cand> cands;
+  std::vector<frbch_sp_group> groups;
+  std::vector<frbch_cutout_cand> cut_cands;
+  bool planes = false, rfi = false, keep_series = false;
+  std::vector<float> ft, dt, series;
+  std::vector<uint32_t> ft_hits, dt_hits;
+  uint32_t nblk = 0;
+  std::vector<uint8_t> mask, chan_flag, blk_flag;
+  std::vector<double> repl;
+  uint32_t kernel_used[4] = {0, 0, 0, 0}, cutout_calls = 0, row_uploads = 0;
+  double wall_ms[FRBCH_CAND_NSTAGE] = {0}, device_ms[FRBCH_CAND_NSTAGE] = {0};
+};
+
+namespace {
+std::vector<uint64_t> cand_select(const frbch_sp_group* g, uint64_t n, uint32_t min_members, uint32_t max_cands) {
+  std::vector<uint64_t> idx;
+  for (uint64_t i = 0; i < n; ++i)
+    if (g[i].nmember >= min_members) idx.push_back(i);
+  if (max_cands > 0 && idx.size() > max_cands) {
+    std::stable_sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) { return g[a].best.sigma > g[b].best.sigma; });
+    idx.resize(max_cands);
+    std::sort(idx.begin(), idx.end());
+  }
+  return idx;
+}
+
+frbch_cutout_cand cand_cutout_of(const frbch_sp_cand& b, const double* dms, double dm_span) {
+  POST_NO_CONTRACT
+  frbch_cutout_cand c;
+  memset(&c, 0, sizeof c);
+  c.dm = dms[b.dm_index];
+  if (dm_span > 0.0) {
+    const double half = 0.5 * dm_span;
+    const double lo = c.dm - half;
+    c.dm_lo = lo > 0.0 ? lo : 0.0;
+    c.dm_hi = c.dm_lo + dm_span;
+  } else {
+    c.dm_lo = 0.0;
+    c.dm_hi = 2.0 * c.dm;
+  }
+  c.sample = (int64_t)b.sample;
+  c.tfactor = std::min<uint32_t>(std::max<uint32_t>(b.width / 2, 1u), 512u);
+  return c;
+}
+
+// candidates of one frbch_cutout_* call: the three per-call limits
+uint64_t cand_per_call(const frbch_fil_desc* fil, const frbch_cutout_params* cut) {
+  const uint64_t by_plane = ((1ull << 31) - 1) / ((uint64_t)std::max(cut->nf, cut->ndm) * cut->nt);
+  const uint64_t by_table = kCutTableCap / ((uint64_t)cut->ndm * fil->nchan);
+  return std::max<uint64_t>(1, std::min<uint64_t>(65535, std::min(by_plane, by_table)));
+}
+
+int cand_run(const frbch_fil_desc* fil, const void* rows_h, const void* d_rows_in, uint64_t nrows, const double* dms, uint32_t ndm,
+             const frbch_cand_params* par, int device, frbch_cand_result** out, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  if (!out) return e.fail(FRBCH_E_ARG, "null argument: out");
+  *out = nullptr;
+  if (!par || par->size != sizeof(frbch_cand_params)) return e.fail(FRBCH_E_ARG, "frbch_cand_params: wrong size");
+  if (par->flags & ~(FRBCH_CAND_RFI | FRBCH_CAND_SERIES)) return e.fail(FRBCH_E_ARG, "unknown flag");
+  int rc = post_check_fil(fil, nrows, e);
+  if (rc) return rc;
+  if (!(rows_h || d_rows_in) || !dms || !ndm) return e.fail(FRBCH_E_ARG, "null argument");
+  uint64_t blk_len = 0;
+  rc = sp_check(&par->sp, &blk_len, e);
+  if (rc) return rc;
+  if (ndm > 65535) return e.fail(FRBCH_E_ARG, "ndm must be 1..65535");
+  if (par->min_members < 1) return e.fail(FRBCH_E_ARG, "min_members must be at least 1");
+  if (par->dm_gap < 1 || par->dm_gap > 16) return e.fail(FRBCH_E_ARG, "dm_gap must be 1..16");
+  const bool rfi = (par->flags & FRBCH_CAND_RFI) != 0, keep_series = (par->flags & FRBCH_CAND_SERIES) != 0, cut = par->cut.nt != 0;
+  uint32_t nblk = 0;
+  if (rfi && (rc = rfi_check(fil, nrows, &par->rfi, &nblk, e)) != 0) return rc;
+  if (cut && (rc = cut_check_par(fil, &par->cut, e)) != 0) return rc;
+  const long want = frbch_dedisperse_nout(fil, nrows, dms, ndm);
+  if (want <= 0) return e.fail(FRBCH_E_ARG, "a DM outside [0, 1e5), or the largest dispersion delay exceeds the data");
+  const uint64_t nout = (uint64_t)want;
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  const uint32_t nchan = fil->nchan;
+  const size_t in_bytes = post_rows_bytes(fil, nrows);
+  const size_t out_bytes = (size_t)ndm * nout * sizeof(float), ncell = (size_t)nblk * nchan;
+  const uint64_t per_call = cut ? cand_per_call(fil, &par->cut) : 0;
+  // what the call asks of the device, for the message of FRBCH_E_NOMEM
+  auto nomem = [&](const char* what) {
+    std::string m = std::string("device memory for ") + what + "; the call needs:";
+    auto add = [&](const std::string& name, uint64_t bytes) { m += " " + name + " " + std::to_string(bytes) + " B,"; };
+    if (rows_h) add("rows", in_bytes);
+    if (rfi) {
+      if (!rows_h) add("cleaned copy of the rows (when a cell is masked)", in_bytes);
+      add("block statistics", ncell * 16);
+      add("mask", ncell);
+      add("replacement values", nchan * sizeof(double));
+    }
+    add("series", out_bytes);
+    add("search statistics", (uint64_t)ndm * std::max<uint64_t>(1, nout / blk_len) * 2 * sizeof(double));
+    add("raw peaks", (uint64_t)kSpRawCap * sizeof(SpPeak));
+    if (cut) {
+      add("planes of a batch of at most " + std::to_string(per_call) + " candidates, each",
+          ((uint64_t)par->cut.nf + par->cut.ndm) * par->cut.nt * 8);
+      add("delay tables of a batch, each candidate", ((uint64_t)par->cut.ndm + 1) * nchan * sizeof(int32_t));
+    }
+    m.back() = '.';
+    return e.fail(FRBCH_E_NOMEM, m);
+  };
+  try {
+    std::unique_ptr<frbch_cand_result> res(new frbch_cand_result());
+    res->nout = nout;
+    res->rfi = rfi;
+    res->keep_series = keep_series;
+    // everything the call holds on the device: the uploaded rows (`up`, given back first) and what the stages allocate (`cd`)
+    void *d_rows = nullptr, *d_work = nullptr, *d_stats = nullptr;
+    uint8_t* d_mask = nullptr; double* d_repl = nullptr;
+    float *d_series = nullptr, *d_ft = nullptr, *d_dt = nullptr;
+    uint32_t *d_fth = nullptr, *d_dth = nullptr;
+    PostScope cd(false);                                           // (every stage has a clock of its own)
+    if (!cd.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+    HostStage up;
+    const auto now = []() { return std::chrono::steady_clock::now(); };
+    // fn() as stage k: its wall time, and the device time its _device calls (or a StageClock of its own) report
+    auto stage = [&](int k, auto&& fn) -> int {
+      const auto t0 = now();
+      tl_stage_ms = &res->device_ms[k];
+      const int r = fn();
+      tl_stage_ms = nullptr;
+      res->wall_ms[k] += std::chrono::duration<double, std::milli>(now() - t0).count();
+      return r;
+    };
+    const void* d_use = d_rows_in;
+    if (rows_h) {
+      d_rows = up.in(rows_h, in_bytes);
+      if (up.failed) return nomem("the rows");
+      rc = stage(FRBCH_CAND_T_UPLOAD, [&]() {
+        StageClock clk(cd.s);
+        const bool bad = up.upload(cd.s) != 0;
+        clk.finish();
+        return bad ? e.fail(FRBCH_E_DEVICE, "upload rows") : FRBCH_OK;
+      });
+      if (rc) return rc;
+      d_use = d_rows;
+      res->row_uploads = 1;
+    }
+    if (rfi) {
+      res->nblk = nblk;
+      res->mask.assign(ncell, 0);
+      res->repl.assign(nchan, 0.0);
+      res->chan_flag.assign(nchan, 0);
+      res->blk_flag.assign(nblk, 0);
+      std::vector<uint64_t> st(ncell * 2);                        // (S, Q): uint64 or double, 16 bytes a cell either way
+      if (cd.alloc(&d_stats, ncell * 16) != 0) return nomem("the block statistics");
+      rc = stage(FRBCH_CAND_T_FLAG, [&]() {
+        int r = frbch_rfi_stats_device(fil, d_use, nrows, &par->rfi, device, d_stats, &res->kernel_used[0], err, err_cap);
+        if (!r && (dev_d2h(st.data(), d_stats, ncell * 16, cd.s) != 0 || dev_sync(cd.s) != 0)) r = e.fail(FRBCH_E_DEVICE, "download statistics");
+        if (!r) r = frbch_rfi_mask(fil, st.data(), nblk, nrows, &par->rfi, par->zap, nullptr, res->mask.data(), res->repl.data(),
+                                   res->chan_flag.data(), res->blk_flag.data(), err, err_cap);
+        return r;
+      });
+      if (rc) return rc;
+      cd.drop(d_stats);
+      if (std::any_of(res->mask.begin(), res->mask.end(), [](uint8_t m) { return m != 0; })) {   // (nothing masked: nothing to write)
+        void* target = d_rows;
+        if (!rows_h) {                                            // the caller's rows keep every byte: a copy is cleaned
+          if (cd.alloc(&d_work, in_bytes) != 0) return nomem("the cleaned copy of the rows");
+          target = d_work;
+        }
+        if (cd.alloc(&d_mask, ncell) != 0 || cd.alloc(&d_repl, nchan * sizeof(double)) != 0) return nomem("the mask");
+        rc = stage(FRBCH_CAND_T_FLAG, [&]() {
+          if ((!rows_h && dev_d2d(d_work, d_rows_in, in_bytes, cd.s) != 0) || dev_h2d(d_mask, res->mask.data(), ncell, cd.s) != 0 ||
+              dev_h2d(d_repl, res->repl.data(), nchan * sizeof(double), cd.s) != 0 || dev_sync(cd.s) != 0)
+            return e.fail(FRBCH_E_DEVICE, "copy rows / upload mask");
+          return frbch_rfi_apply_device(fil, target, nrows, &par->rfi, d_mask, d_repl, device, err, err_cap);
+        });
+        if (rc) return rc;
+        d_use = target;
+        cd.drop(d_mask);
+        cd.drop(d_repl);
+      }
+    }
+    if (cd.alloc(&d_series, out_bytes) != 0) return nomem("the series");
+    res->kernel_used[1] = frbch_dedisperse_kernel(fil, d_use, nrows, dms, ndm) > 0 ? 1u : 0u;
+    rc = stage(FRBCH_CAND_T_DEDISPERSE, [&]() {
+      return frbch_dedisperse_device(fil, d_use, nrows, dms, ndm, par->zerodm, par->clip_sigma, device, d_series, nout, &res->nclipped,
+                                     err, err_cap);
+    });
+    if (rc) return rc;
+    if (keep_series) {
+      res->series.resize((size_t)ndm * nout);
+      rc = stage(FRBCH_CAND_T_DOWNLOAD, [&]() {
+        StageClock clk(cd.s);
+        const bool bad = dev_d2h(res->series.data(), d_series, out_bytes, cd.s) != 0 || dev_sync(cd.s) != 0;
+        clk.finish();
+        return bad ? e.fail(FRBCH_E_DEVICE, "download series") : FRBCH_OK;
+      });
+      if (rc) return rc;
+    }
+    uint64_t ncand = 0;
+    rc = stage(FRBCH_CAND_T_SEARCH, [&]() {
+      return sp_search_run(d_series, ndm, nout, &par->sp, device, nullptr, 0, &ncand, &res->kernel_used[2], &res->cands, err, err_cap);
+    });
+    if (rc) return rc;
+    cd.drop(d_series);                                             // the plane is done with; the rows stay for the cut-outs
+    std::vector<frbch_sp_group> all(std::max<size_t>(1, res->cands.size()));
+    uint64_t ngroup_all = 0;
+    rc = frbch_sp_group_cands(fil, dms, ndm, res->cands.data(), res->cands.size(), par->dm_gap, all.data(), all.size(), &ngroup_all,
+                              err, err_cap);
+    if (rc) return rc;
+    res->ngroup_all = ngroup_all;
+    for (uint64_t i : cand_select(all.data(), ngroup_all, par->min_members, par->max_cands)) {
+      res->groups.push_back(all[i]);
+      res->cut_cands.push_back(cand_cutout_of(all[i].best, dms, par->dm_span));
+    }
+    const uint64_t n = res->groups.size();
+    if (cut && n) {
+      const uint32_t nt = par->cut.nt, nf = par->cut.nf, cdm = par->cut.ndm;
+      const size_t ft1 = (size_t)nf * nt, dt1 = (size_t)cdm * nt;
+      res->ft.resize(n * ft1); res->ft_hits.resize(n * ft1);
+      res->dt.resize(n * dt1); res->dt_hits.resize(n * dt1);
+      res->planes = true;
+      const uint64_t bmax = std::min(n, per_call);
+      if (cd.alloc(&d_ft, bmax * ft1 * 4) != 0 || cd.alloc(&d_fth, bmax * ft1 * 4) != 0 || cd.alloc(&d_dt, bmax * dt1 * 4) != 0 ||
+          cd.alloc(&d_dth, bmax * dt1 * 4) != 0)
+        return nomem("the planes");
+      uint32_t used_min = 1;
+      for (uint64_t a = 0; a < n; a += per_call) {
+        const uint32_t cnt = (uint32_t)std::min(per_call, n - a);
+        uint32_t used = 0;
+        rc = stage(FRBCH_CAND_T_CUT, [&]() {
+          return frbch_cutout_device(fil, d_use, nrows, &par->cut, &res->cut_cands[a], cnt, device, d_ft, d_fth, d_dt, d_dth, &used,
+                                     err, err_cap);
+        });
+        if (rc) return rc;
+        used_min = std::min(used_min, used);
+        ++res->cutout_calls;
+        rc = stage(FRBCH_CAND_T_DOWNLOAD, [&]() {
+          StageClock clk(cd.s);
+          const bool bad = dev_d2h(&res->ft[a * ft1], d_ft, cnt * ft1 * 4, cd.s) != 0 || dev_d2h(&res->ft_hits[a * ft1], d_fth, cnt * ft1 * 4, cd.s) != 0 ||
+                           dev_d2h(&res->dt[a * dt1], d_dt, cnt * dt1 * 4, cd.s) != 0 || dev_d2h(&res->dt_hits[a * dt1], d_dth, cnt * dt1 * 4, cd.s) != 0 ||
+                           dev_sync(cd.s) != 0;
+          clk.finish();
+          return bad ? e.fail(FRBCH_E_DEVICE, "download planes") : FRBCH_OK;
+        });
+        if (rc) return rc;
+      }
+      res->kernel_used[3] = used_min;
+    }
+    *out = res.release();
+  } catch (const std::bad_alloc&) {
+    tl_stage_ms = nullptr;
+    return e.fail(FRBCH_E_NOMEM, "host memory for the result");
+  }
+  return FRBCH_OK;
+}
+}  // namespace
+
+extern "C" int frbch_candidates_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const double* dms, uint32_t ndm,
+                                     const frbch_cand_params* par, int device, frbch_cand_result** out, char* err, size_t err_cap) {
+  if (out) *out = nullptr;
+  if (!rows) return PostErr{err, err_cap}.fail(FRBCH_E_ARG, "null argument");
+  return cand_run(fil, rows, nullptr, nrows, dms, ndm, par, device, out, err, err_cap);
+}
+
+extern "C" int frbch_candidates_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const double* dms, uint32_t ndm,
+                                       const frbch_cand_params* par, int device, frbch_cand_result** out, char* err, size_t err_cap) {
+  if (out) *out = nullptr;
+  if (!d_rows) return PostErr{err, err_cap}.fail(FRBCH_E_ARG, "null argument");
+  return cand_run(fil, nullptr, d_rows, nrows, dms, ndm, par, device, out, err, err_cap);
+}
+
+extern "C" int frbch_cand_result_view(const frbch_cand_result* r, frbch_cand_view* v) {
+  if (!r || !v || v->size != sizeof(frbch_cand_view)) return FRBCH_E_ARG;
+  memset(v, 0, sizeof *v);
+  v->size = sizeof *v;
+  v->nout = r->nout;
+  v->nclipped = r->nclipped;
+  v->ncand = r->cands.size();
+  v->cands = r->cands.empty() ? nullptr : r->cands.data();
+  v->ngroup_all = r->ngroup_all;
+  v->ngroup = r->groups.size();
+  v->groups = r->groups.empty() ? nullptr : r->groups.data();
+  v->cut_cands = r->cut_cands.empty() ? nullptr : r->cut_cands.data();
+  if (r->planes) {
+    v->ft = r->ft.data(); v->ft_hits = r->ft_hits.data();
+    v->dt = r->dt.data(); v->dt_hits = r->dt_hits.data();
+  }
+  if (r->rfi) {
+    v->nblk = r->nblk;
+    v->mask = r->mask.data(); v->repl = r->repl.data();
+    v->chan_flag = r->chan_flag.data(); v->blk_flag = r->blk_flag.data();
+  }
+  if (r->keep_series) v->series = r->series.data();
+  for (int k = 0; k < 4; ++k) v->kernel_used[k] = r->kernel_used[k];
+  v->cutout_calls = r->cutout_calls;
+  v->row_uploads = r->row_uploads;
+  for (int k = 0; k < FRBCH_CAND_NSTAGE; ++k) { v->wall_ms[k] = r->wall_ms[k]; v->device_ms[k] = r->device_ms[k]; }
+  return FRBCH_OK;
+}
+
+extern "C" void frbch_cand_result_free(frbch_cand_result* r) { delete r; }
+
+extern "C" int frbch_cand_select(const frbch_sp_group* groups, uint64_t ngroup, uint32_t min_members, uint32_t max_cands,
+                                 uint64_t* keep, uint64_t cap, uint64_t* nkeep) {
+  if (!nkeep || (ngroup && !groups) || (cap && !keep) || min_members < 1) return FRBCH_E_ARG;
+  try {
+    const std::vector<uint64_t> idx = cand_select(groups, ngroup, min_members, max_cands);
+    *nkeep = idx.size();
+    for (uint64_t i = 0; i < std::min<uint64_t>(cap, idx.size()); ++i) keep[i] = idx[i];
+    return idx.size() > cap ? FRBCH_E_CAPACITY : FRBCH_OK;
+  } catch (const std::bad_alloc&) {
+    return FRBCH_E_NOMEM;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// corner turn
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+// "[swap_sign_mag+]<W>>[b,b,..][b,b,..]...:<t0>[-<t1>]"   (spif2file.sh:31-113)
+int parse_recipe(const char* text, CornerParams* cp, uint32_t* first_tag, const PostErr& e) {
+  if (!text) return e.fail(FRBCH_E_ARG, "null recipe");
+  std::string s(text);
+  memset(cp, 0, sizeof *cp);
+  const std::string pre = "swap_sign_mag+";
+  if (s.compare(0, pre.size(), pre) == 0) {
+    cp->swap_sign_mag = 1;
+    s = s.substr(pre.size());
+  }
+  const size_t gt = s.find('>');
+  if (gt == std::string::npos) return e.fail(FRBCH_E_ARG, "recipe: no '>'");
+  cp->word_bits = atoi(s.substr(0, gt).c_str());
+  if (cp->word_bits != 4 && cp->word_bits != 8 && cp->word_bits != 16 && cp->word_bits != 32 && cp->word_bits != 64)
+    return e.fail(FRBCH_E_ARG, "recipe: word width must be 4, 8, 16, 32 or 64 bits");
+  size_t pos = gt + 1;
+  int ng = 0, glen = -1;
+  while (pos < s.size() && s[pos] == '[') {
+    const size_t close = s.find(']', pos);
+    if (close == std::string::npos || ng >= 16) return e.fail(FRBCH_E_ARG, "recipe: bad bracket list (at most 16 groups)");
+    std::stringstream ls(s.substr(pos + 1, close - pos - 1));
+    std::string item;
+    int k = 0;
+    while (std::getline(ls, item, ',')) {
+      const int b = atoi(item.c_str());
+      if (b < 0 || b >= cp->word_bits || k >= 8) return e.fail(FRBCH_E_ARG, "recipe: bit index outside the word, or more than 8 bits in a group");
+      cp->src[ng][k++] = (uint8_t)b;
+    }
+    if (glen < 0) glen = k;
+    if (k != glen || (k != 1 && k != 2 && k != 4 && k != 8)) return e.fail(FRBCH_E_ARG, "recipe: every group must take the same 1, 2, 4 or 8 bits");
+    ++ng;
+    pos = close + 1;
+  }
+  if (!ng) return e.fail(FRBCH_E_ARG, "recipe: no groups");
+  cp->ngroup = ng;
+  cp->glen = glen;
+  int t0 = 0, t1 = ng - 1;
+  if (pos < s.size() && s[pos] == ':') {
+    const std::string tags = s.substr(pos + 1);
+    const size_t dash = tags.find('-');
+    t0 = atoi(tags.substr(0, dash).c_str());
+    t1 = dash == std::string::npos ? t0 : atoi(tags.substr(dash + 1).c_str());
+  }
+  if (t1 - t0 + 1 != ng) return e.fail(FRBCH_E_ARG, "recipe: tag range does not match the number of groups");
+  if (first_tag) *first_tag = (uint32_t)t0;
+  return FRBCH_OK;
+}
+}  // namespace
+
+extern "C" int frbch_cornerturn_info(const char* recipe, uint32_t* word_bits, uint32_t* ntags, uint32_t* bits_per_word,
+                                     uint32_t* first_tag, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  CornerParams cp;
+  const int rc = parse_recipe(recipe, &cp, first_tag, e);
+  if (rc) return rc;
+  if (word_bits) *word_bits = (uint32_t)cp.word_bits;
+  if (ntags) *ntags = (uint32_t)cp.ngroup;
+  if (bits_per_word) *bits_per_word = (uint32_t)cp.glen;
+  return FRBCH_OK;
+}
+
+extern "C" int frbch_cornerturn_device(const char* recipe, const void* d_frames, size_t nframes, uint32_t frame_bytes,
+                                       uint32_t header_bytes, void* const* d_out, uint32_t ntags, size_t out_bytes_each,
+                                       int device, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  CornerParams cp;
+  int rc = parse_recipe(recipe, &cp, nullptr, e);
+  if (rc) return rc;
+  if (!d_frames || !d_out || frame_bytes <= header_bytes) return e.fail(FRBCH_E_ARG, "null argument or bad frame geometry");
+  if (ntags != (uint32_t)cp.ngroup) return e.fail(FRBCH_E_ARG, "ntags differs from the recipe's groups");
+  const uint64_t pay = (uint64_t)nframes * (frame_bytes - header_bytes);
+  if ((frame_bytes - header_bytes) * 8ull % (uint64_t)cp.word_bits) return e.fail(FRBCH_E_ARG, "payload is not a whole number of words");
+  const uint64_t nwords = pay * 8 / (uint64_t)cp.word_bits;
+  const uint64_t wpt = 64 / (uint64_t)cp.glen;
+  if ((nwords * cp.glen) % 8) return e.fail(FRBCH_E_ARG, "the frames must hold a whole number of output bytes per stream");
+  if (out_bytes_each != nwords * cp.glen / 8) return e.fail(FRBCH_E_CAPACITY, "out_bytes_each must be words * bits per word / 8");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  cp.frames = (const uint8_t*)d_frames;
+  cp.frame_bytes = frame_bytes;
+  cp.header_bytes = header_bytes;
+  cp.payload_bytes = frame_bytes - header_bytes;
+  cp.nwords = nwords;
+  for (uint32_t g = 0; g < ntags; ++g) {
+    if (!d_out[g]) return e.fail(FRBCH_E_ARG, "null output stream");
+    cp.out[g] = (uint8_t*)d_out[g];
+  }
+  if (nwords) {
+    DEV_LAUNCH(frbch_post_cornerturn, ((nwords + wpt - 1) / wpt + 255) / 256, 1, 256, 0, (dev_stream_t)0, cp);
+    if (dev_check_launch() != 0 || dev_sync(0) != 0) return e.fail(FRBCH_E_DEVICE, std::string("corner turn: ") + dev_last_error_string());
+  }
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_cornerturn_host(const char* recipe, const void* frames, size_t nframes, uint32_t frame_bytes,
+                                     uint32_t header_bytes, void* const* out, uint32_t ntags, size_t out_bytes_each,
+                                     int device, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  if (!frames || !out || ntags > 16) return e.fail(FRBCH_E_ARG, "null argument");
+  if (int rc = post_check_device(device, e)) return rc;
+  DeviceGuard dg(device);
+  void* d_o[16] = {nullptr};
+  HostStage hs;
+  void* d_in = hs.in(frames, nframes * (size_t)frame_bytes);
+  for (uint32_t g = 0; g < ntags; ++g) d_o[g] = hs.scratch(out_bytes_each);       // (downloaded stream by stream, below)
+  if (hs.failed) return e.fail(FRBCH_E_NOMEM, "device memory");
+  if (hs.upload() != 0) return e.fail(FRBCH_E_DEVICE, "upload frames");
+  int rc = frbch_cornerturn_device(recipe, d_in, nframes, frame_bytes, header_bytes, d_o, ntags, out_bytes_each, device, err, err_cap);
+  for (uint32_t g = 0; g < ntags && !rc; ++g)
+    if (dev_d2h(out[g], d_o[g], out_bytes_each, 0) != 0) rc = e.fail(FRBCH_E_DEVICE, "download streams");
+  if (!rc && dev_sync(0) != 0) rc = e.fail(FRBCH_E_DEVICE, "sync");
+  return rc;
+}

@@ -82,8 +82,17 @@ struct EmuState {
   uintptr_t next_stream = 0x1000;
   std::atomic<int> next_event{1};
   uint64_t violations = 0;
+  std::atomic<long> fail_in{0};              // frbch_test_emu_fail_at: the fallible calls left before one fails; 0: disarmed
+  std::atomic<long> live_blocks{0}, live_streams{0};   // dev_malloc blocks / streams not yet given back, in every mode
 };
 inline EmuState g_emu;
+// a fallible call (dev_malloc, the copies, the memsets, dev_sync, dev_stream_create, dev_check_launch) asks first: true once, at
+// the armed call, which then does nothing and returns failure
+static inline bool emu_fail_now() {
+  long n = g_emu.fail_in.load();
+  while (n > 0 && !g_emu.fail_in.compare_exchange_weak(n, n - 1)) {}
+  return n == 1;
+}
 
 static inline bool emu_deferred() { return g_emu.mode.load(std::memory_order_acquire) != 0; }
 static inline void emu_run_until(void* s, const EmuMarker* target, int depth = 0);
@@ -188,7 +197,9 @@ static inline int dev_arch_ok(int, char* name, size_t cap, size_t* lds_limit) {
 template <class K>
 static inline int dev_allow_lds(K, size_t) { return 0; }
 static inline int dev_malloc(void** p, size_t n) {
+  if (emu_fail_now()) return -1;
   *p = malloc(n ? n : 1);
+  if (*p) g_emu.live_blocks++;
   if (*p && emu_deferred()) {
     std::lock_guard<std::recursive_mutex> lk(g_emu.m);
     g_emu.sizes[*p] = n ? n : 1;
@@ -197,6 +208,7 @@ static inline int dev_malloc(void** p, size_t n) {
 }
 // (hipFree waits for the device: everything pending runs first; memory a pending copy or memset names counts as a violation)
 static inline void dev_free(void* p) {
+  if (p) g_emu.live_blocks--;
   if (p && emu_deferred()) {
     std::lock_guard<std::recursive_mutex> lk(g_emu.m);
     const auto it = g_emu.sizes.find(p);
@@ -212,17 +224,20 @@ static inline void dev_free(void* p) {
   free(p);
 }
 static inline int dev_h2d(void* d, const void* h, size_t n, dev_stream_t s) {
+  if (emu_fail_now()) return -1;
   if (!emu_deferred()) { memcpy(d, h, n); return 0; }
   auto src = std::make_shared<std::vector<unsigned char>>((const unsigned char*)h, (const unsigned char*)h + n);   // the host source as it is now
   emu_push(s, [=]() { memcpy(d, src->data(), n); }, d, n);
   return 0;
 }
 static inline int dev_d2h(void* h, const void* d, size_t n, dev_stream_t s) {
+  if (emu_fail_now()) return -1;
   if (!emu_deferred()) { memcpy(h, d, n); return 0; }
   emu_push(s, [=]() { memcpy(h, d, n); }, d, n);
   return 0;
 }
 static inline int dev_d2d(void* d, const void* s_, size_t n, dev_stream_t s) {
+  if (emu_fail_now()) return -1;
   if (!emu_deferred()) { memmove(d, s_, n); return 0; }
   emu_push(s, [=]() { memmove(d, s_, n); }, d, n, s_, n);
   return 0;
@@ -237,6 +252,7 @@ static inline int dev_copy2d(void* d, size_t dpitch, const void* s_, size_t spit
   return 0;
 }
 static inline int dev_memset(void* d, int v, size_t n, dev_stream_t s) {
+  if (emu_fail_now()) return -1;
   if (!emu_deferred()) { memset(d, v, n); return 0; }
   emu_push(s, [=]() { memset(d, v, n); }, d, n);
   return 0;
@@ -245,11 +261,13 @@ static inline void emu_memset32(void* d, uint32_t v, size_t nwords) {
   for (size_t i = 0; i < nwords; ++i) ((uint32_t*)d)[i] = v;
 }
 static inline int dev_memset32(void* d, uint32_t v, size_t nwords, dev_stream_t s) {
+  if (emu_fail_now()) return -1;
   if (!emu_deferred()) { emu_memset32(d, v, nwords); return 0; }
   emu_push(s, [=]() { emu_memset32(d, v, nwords); }, d, nwords * 4);
   return 0;
 }
 static inline int dev_sync(dev_stream_t s) {
+  if (emu_fail_now()) return -1;
   if (!emu_deferred()) return 0;
   std::lock_guard<std::recursive_mutex> lk(g_emu.m);
   emu_run_until(s, nullptr);
@@ -260,6 +278,8 @@ static inline int dev_sync(dev_stream_t s) {
 // mode-0 run made it first (the stream-order tests always run mode 0 first) and a distinct id otherwise.  Either way it differs
 // from every stream a deferring mode hands out (they start at 0x1010), which is all the scheduler needs: queues go by id.
 static inline int dev_stream_create(dev_stream_t* s) {
+  if (emu_fail_now()) return -1;
+  g_emu.live_streams++;
   *s = (void*)1;
   if (emu_deferred()) {   // distinct streams
     std::lock_guard<std::recursive_mutex> lk(g_emu.m);
@@ -269,6 +289,7 @@ static inline int dev_stream_create(dev_stream_t* s) {
 }
 // (hipStreamDestroy lets the stream's work complete: so does this, and counts the caller's omission)
 static inline void dev_stream_destroy(dev_stream_t s) {
+  g_emu.live_streams--;
   if (!emu_deferred()) return;
   std::lock_guard<std::recursive_mutex> lk(g_emu.m);
   const auto it = g_emu.q.find(s);
@@ -311,7 +332,7 @@ static inline int dev_event_sync(int e) {
   emu_run_until(w->stream, w.get());
   return w->done ? 0 : -1;
 }
-static inline int dev_check_launch() { return 0; }
+static inline int dev_check_launch() { return emu_fail_now() ? -1 : 0; }
 static inline int dev_host_alloc(void** p, size_t n) { *p = malloc(n); return *p ? 0 : -1; }
 static inline void dev_host_free(void* p) { free(p); }
 static inline int dev_event_create(dev_event_t* e) { return dev_event_create_sync(e); }

@@ -22,6 +22,13 @@ uint64_t frbch_test_emu_violations(void) {
   std::lock_guard<std::recursive_mutex> lk(g_emu.m);
   return g_emu.violations;
 }
+// the n-th fallible device-layer call from now on (dev_malloc, dev_h2d, dev_d2h, dev_d2d, dev_memset*, dev_sync, dev_stream_create,
+// dev_check_launch) returns failure, once; 0 disarms.  tests/test_post_failures.py walks every failure return with it.
+void frbch_test_emu_fail_at(long n) { g_emu.fail_in.store(n > 0 ? n : 0); }
+// dev_malloc blocks not yet freed (low 32 bits) and streams not yet destroyed (high 32 bits), in every scheduler mode
+uint64_t frbch_test_emu_live(void) {
+  return ((uint64_t)g_emu.live_blocks.load() & 0xFFFFFFFFull) | ((uint64_t)g_emu.live_streams.load() << 32);
+}
 // ops queued, since the last call with reset != 0, on the second stream of the chain whose front lane has `ncu_front` CUs (the
 // low 16 bits of frbch_config.overlap, rounded down to 8): the stream of frbchi::Lanes itself, so that nothing else is counted --
 // not the handles' own streams (frbch_open queues the identity rescale there), not another caller stream.  0 without such lanes.

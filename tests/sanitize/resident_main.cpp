@@ -1,6 +1,9 @@
 // TEST INFRASTRUCTURE ONLY: calls frbch_candidates_host (interference cases: 8-, 16-bit and float rows, two products, foff > 0,
 // with and without planes, no candidate, argument errors) and frbch_rfi_cleanp_host (2 and 4 products, the three sample widths,
-// a short last block) on the emulator build and frees every result.  Built with -fsanitize=address,undefined (Makefile).
+// a short last block) on the emulator build and frees every result.  Then the failure walk of tests/test_post_failures.py over
+// frbch_candidates_host, frbch_rfi_cleanp_host, frbch_cutout_host and frbch_foldp_host: the n-th fallible device-layer call fails,
+// n = 1, 2, ... until the call succeeds; here only "not 0" is asked of a failed call -- AddressSanitizer, UBSan and LeakSanitizer
+// give the verdict on what it left behind.  Built with -fsanitize=address,undefined (Makefile).
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -40,8 +43,29 @@ static std::vector<T> make_rows(uint64_t nrows, uint32_t nifs, uint32_t nchan, u
 static int fails = 0;
 #define EXPECT(cond) do { if (!(cond)) { fprintf(stderr, "line %d: %s\n", __LINE__, #cond); ++fails; } } while (0)
 
+// the emulator's test hooks (tests/emu/emu_hooks.cpp)
+extern "C" void frbch_test_emu_fail_at(long n);
+extern "C" uint64_t frbch_test_emu_live(void);
+
+// call() -> return code, with the n-th fallible device-layer call failing, until it returns 0; nothing stays alive on the device
+template <class F>
+static void failure_walk(const char* name, F call) {
+  const uint64_t live = frbch_test_emu_live();
+  long n = 1;
+  for (; n < 1000; ++n) {
+    frbch_test_emu_fail_at(n);
+    const int rc = call();
+    frbch_test_emu_fail_at(0);
+    EXPECT(frbch_test_emu_live() == live);
+    if (rc == FRBCH_OK) break;
+  }
+  EXPECT(n > 3 && n < 1000);
+  printf("  %s: %ld failure returns walked\n", name, n - 1);
+}
+
 template <class T>
-static void candidates_case(int nbits, uint32_t nifs, uint32_t product, double foff, double scale, double offset, uint32_t nt, double threshold) {
+static void candidates_case(int nbits, uint32_t nifs, uint32_t product, double foff, double scale, double offset, uint32_t nt, double threshold,
+                            bool walk = false) {
   const uint32_t nchan = 64;
   const uint64_t nrows = 9000;
   frbch_fil_desc fil;
@@ -115,10 +139,19 @@ static void candidates_case(int nbits, uint32_t nifs, uint32_t product, double f
   EXPECT(frbch_candidates_host(&fil, rows.data(), nrows, dms, 9, &par, 0, &res, err, sizeof err) == FRBCH_E_ARG && !res);
   EXPECT(frbch_candidates_host(&fil, rows.data(), nrows, dms, 9, nullptr, 0, nullptr, err, sizeof err) == FRBCH_E_ARG);
   frbch_cand_result_free(nullptr);
+  par.size = sizeof par;
+  if (walk)
+    failure_walk("frbch_candidates_host", [&]() {
+      frbch_cand_result* r = (frbch_cand_result*)(uintptr_t)1;
+      const int code = frbch_candidates_host(&fil, rows.data(), nrows, dms, 9, &par, 0, &r, err, sizeof err);
+      EXPECT((code == FRBCH_OK) == (r != nullptr) && rows == before);
+      frbch_cand_result_free(r);
+      return code;
+    });
 }
 
 template <class T>
-static void cleanp_case(int nbits, uint32_t nifs, uint32_t nchan, uint64_t nrows, double scale, double offset, bool want_stats) {
+static void cleanp_case(int nbits, uint32_t nifs, uint32_t nchan, uint64_t nrows, double scale, double offset, bool want_stats, bool walk = false) {
   frbch_fil_desc fil;
   memset(&fil, 0, sizeof fil);
   fil.size = sizeof fil;
@@ -154,22 +187,69 @@ static void cleanp_case(int nbits, uint32_t nifs, uint32_t nchan, uint64_t nrows
   par.block_rows = 0;
   EXPECT(frbch_rfi_cleanp_host(&fil, rows.data(), nrows, &par, zap.data(), 0, mask.data(), repl.data(), cf.data(), bf.data(), nullptr,
                                &used, err, sizeof err) == FRBCH_E_ARG);
+  par.block_rows = 256;
+  if (walk)
+    failure_walk("frbch_rfi_cleanp_host", [&]() {
+      rows = before;
+      return frbch_rfi_cleanp_host(&fil, rows.data(), nrows, &par, zap.data(), 0, mask.data(), repl.data(), cf.data(), bf.data(),
+                                   want_stats ? stats.data() : nullptr, &used, err, sizeof err);
+    });
+}
+
+// 8-bit rows of 64 channels: the planes of two candidates, one of them over the end of the data; the fold of both products
+static void cutout_and_fold_walk() {
+  const uint32_t nchan = 64, nifs = 2;
+  const uint64_t nrows = 3000;
+  frbch_fil_desc fil;
+  memset(&fil, 0, sizeof fil);
+  fil.size = sizeof fil;
+  fil.nchan = nchan; fil.nifs = nifs; fil.nbits = 8; fil.product = 1;
+  fil.fch1_mhz = 1400.0; fil.foff_mhz = -0.5; fil.tsamp_s = 64e-6; fil.tstart_mjd = 59000.25;
+  const std::vector<uint8_t> rows = make_rows<uint8_t>(nrows, nifs, nchan, 1, fil, 56.7, 1.0, 0.0);
+  char err[512] = "";
+  uint32_t used = 9;
+  frbch_cutout_params cut = {sizeof cut, 6, 16, 9};
+  frbch_cutout_cand cands[2];
+  memset(cands, 0, sizeof cands);
+  cands[0].dm = 56.7; cands[0].dm_hi = 113.4; cands[0].sample = 1500; cands[0].tfactor = 3;
+  cands[1].dm = 30.0; cands[1].dm_hi = 60.0; cands[1].sample = 2995; cands[1].tfactor = 2;
+  std::vector<float> ft(2 * 16 * 6), dt(2 * 9 * 6);
+  std::vector<uint32_t> fth(ft.size()), dth(dt.size());
+  failure_walk("frbch_cutout_host", [&]() {
+    return frbch_cutout_host(&fil, rows.data(), nrows, &cut, cands, 2, 0, ft.data(), fth.data(), dt.data(), dth.data(), &used, err, sizeof err);
+  });
+  EXPECT(used == 0 && fth[0] > 0);
+  frbch_fold_model m;
+  memset(&m, 0, sizeof m);
+  m.size = sizeof m;
+  m.f0_hz = 29.9; m.f1 = -2.5e-9; m.pepoch_mjd = 59000.0; m.dm = 56.7; m.apply_delays = 1; m.nbin = 16; m.subint_s = 0.07;
+  const long nsub = frbch_fold_nsub(&fil, nrows, m.subint_s);
+  EXPECT(nsub > 1);
+  std::vector<double> prof((size_t)nsub * nifs * m.nbin * nchan);
+  std::vector<uint32_t> hits((size_t)nsub * m.nbin * nchan);
+  failure_walk("frbch_foldp_host", [&]() {
+    return frbch_foldp_host(&fil, rows.data(), nrows, &m, 0, prof.data(), hits.data(), (uint32_t)nsub, &used, err, sizeof err);
+  });
+  uint64_t total = 0;
+  for (uint32_t h : hits) total += h;
+  EXPECT(used == 0 && total == nrows * nchan);
 }
 
 int main() {
   candidates_case<uint8_t>(8, 1, 0, -0.5, 1.0, 0.0, 32, 6.0);
   candidates_case<uint16_t>(16, 1, 0, -0.5, 201.0, 0.0, 32, 6.0);
   candidates_case<float>(32, 1, 0, -0.5, 0.37, -3.0, 32, 6.0);
-  candidates_case<uint8_t>(8, 2, 1, -0.5, 1.0, 0.0, 32, 6.0);
+  candidates_case<uint8_t>(8, 2, 1, -0.5, 1.0, 0.0, 32, 6.0, true);
   candidates_case<uint8_t>(8, 1, 0, +0.5, 1.0, 0.0, 32, 6.0);
   candidates_case<uint8_t>(8, 1, 0, -0.5, 1.0, 0.0, 0, 6.0);          // no planes
   candidates_case<uint8_t>(8, 1, 0, -0.5, 1.0, 0.0, 32, 1000.0);      // no candidate
-  cleanp_case<uint8_t>(8, 2, 64, 24 * 256 - 100, 1.0, 0.0, true);
+  cleanp_case<uint8_t>(8, 2, 64, 24 * 256 - 100, 1.0, 0.0, true, true);
   cleanp_case<uint8_t>(8, 4, 64, 2100, 1.0, 0.0, false);
   cleanp_case<uint16_t>(16, 2, 48, 1500, 201.0, 0.0, true);
   cleanp_case<uint16_t>(16, 4, 64, 1025, 201.0, 0.0, true);
   cleanp_case<float>(32, 2, 64, 1500, 0.37, -3.0, true);
   cleanp_case<float>(32, 4, 48, 2049, 0.37, -3.0, false);
+  cutout_and_fold_walk();
   printf(fails ? "FAILED: %d expectation(s)\n" : "resident_sanitize: all expectations hold, no sanitizer report\n", fails);
   return fails ? 1 : 0;
 }
