@@ -88,6 +88,7 @@ struct frbch_handle {
   uint64_t fused_rows = 0;     // rows of the current interval whose moments are in `partial`
   bool fused_valid = false;    // ... and no row of the interval is missing from them
   int fused_chunks = 0;        // rows of `partial` the fused path uses (0 = this configuration cannot fuse)
+  int fused_live = 0;          // ... and how many of them hold the current interval's sums (clear_partial, extend_partial): frbch_stats_final reads these
 
   uint64_t rows_out = 0, blocks_done = 0;
   // two-pass rescale: the first batch of a `-c` rescale interval is not written as float rows.  K2 runs over
@@ -299,6 +300,8 @@ int launch_back(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s);      
 int launch_unpack_tap(frbch_handle* h, KParams& p, uint64_t nsamples, int decoder, dev_stream_t s);
 int fused_chunks_of(const frbch_handle* h);                  // rows of partial rescale sums K2 may write (0: it cannot sum)
 int ensure_partial(frbch_handle* h);
+int clear_partial(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s);   // a rescale interval starts with the K2 launch of p
+int extend_partial(frbch_handle* h, dev_stream_t s);                            // ... and goes on with another launch that sums
 int ensure_powbuf(frbch_handle* h);
 int run_stats(frbch_handle* h, uint64_t rows, dev_stream_t s);
 bool quant_fast_geometry(const frbch_handle* h, int ncu, uint64_t* wgs_out, uint64_t* nthr_out, uint64_t* rp_out);

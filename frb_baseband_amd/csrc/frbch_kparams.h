@@ -80,6 +80,9 @@ struct KParams {
   double* stat_partial;     // fast K2, float power: [workgroup row][ncol][2] running (sum, sum of squares); null = off
   uint64_t stat_limit;      // ... of the rows below this absolute row of power_out (the end of the rescale interval)
   uint32_t nblk;            // blocks in this launch (persistent kernels loop over them)
+  uint32_t stat_first;      // frbch_k2_priv: 1 = the rescale interval starts with this launch and nobody cleared the rows of stat_partial the
+                            // launch's workgroups own -- a workgroup's first flush stores its sums instead of adding them (the host side sets
+                            // it: clear_partial)
   const uint8_t* stg;        // wave K1: the launch's payload re-ordered by frbch_k0_stage, [blk][branch group][row][RB bytes]: the
                              // rows of one workgroup and block are contiguous (null = gather from the frames)
   uint8_t* stg_out;          // frbch_k0_stage: where it writes that buffer

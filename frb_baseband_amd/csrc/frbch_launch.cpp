@@ -302,6 +302,21 @@ bool priv_takes(const Plan& pl, const KParams& p, int priv_grid) {
   return pl.fast_k2_priv && p.tile_major == 2 && priv_grid > 0 &&
          !(p.out_mode == FRBCH_OUT_FLOAT_POWER && pl.fast_k2_nw == 2 && pl.fast_k2_log2m == 3);
 }
+// the frbch_k2_priv launch of `p` over nb blocks, decided here for launch_k2_fast (which launches it) and clear_partial (which tells
+// it whose rows of the partial table are cleared): grid = its workgroups, a contiguous run of tiles each (0: the launch takes another
+// kernel); sums = it adds into p.stat_partial, rows [0, priv_stat_chunks(pl, grid))
+struct PrivLaunch {
+  unsigned grid;
+  bool sums;
+};
+PrivLaunch priv_launch(const frbch_handle* h, const KParams& p, uint32_t nb) {
+  const Plan& pl = h->pl;
+  if (pl.fast_k2_lane || !priv_takes(pl, p, h->priv_grid)) return {0u, false};
+  const uint64_t ntiles = (uint64_t)nb * (uint64_t)(pl.r / 4);
+  const bool sums = p.stat_partial && k2_wave_planned(pl) && !pl.coherent &&   // (launch_back: only the wave-private K2 sums while it writes)
+                    !pol_mode_no_sums(p.pol_mode) && !(h->cfg.flags & kFlagSeparateStats);
+  return {(unsigned)std::min<uint64_t>(ntiles, (uint64_t)h->priv_grid), sums};
+}
 // rows of partial sums the fused statistics of frbch_k2_wave / frbch_k3_wave use; 0 = this configuration cannot fuse (one column
 // group per thread needed)
 int wave_stat_chunks(const Plan& pl, uint32_t h_flags, int pol_mode) {
@@ -465,11 +480,11 @@ bool launch_k2_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
     const dim3 grid((unsigned)((uint64_t)pl.r * nb * pl.fast_k2_lane / 256));
     return select_k2_lane(pl, p.pol_mode, [&](auto kern, const KSel& a) { launch_sel(h, kern, grid, a, s, p); });
   }
-  if (priv_takes(pl, p, h->priv_grid)) {
+  if (const PrivLaunch pv = priv_launch(h, p, nb); pv.grid) {
     p.nblk = nb;
-    if (pol_mode_no_sums(p.pol_mode) || (h->cfg.flags & kFlagSeparateStats)) p.stat_partial = nullptr;
-    const uint64_t ntiles = (uint64_t)nb * (uint64_t)(pl.r / 4);
-    const dim3 grid((unsigned)std::min<uint64_t>(ntiles, (uint64_t)h->priv_grid));
+    if (!pv.sums) p.stat_partial = nullptr;
+    if (!p.stat_partial) p.stat_first = 0;
+    const dim3 grid(pv.grid);
     return select_k2_priv(pl, p.pol_mode, p.out_mode, [&](auto kern, const KSel& a) { launch_sel(h, kern, grid, a, s, p); });
   }
   if (p.out_mode == FRBCH_OUT_STATS) return false;   // (only frbch_k2_priv has a statistics-only form: the engine asks for it nowhere else)
@@ -791,6 +806,30 @@ int ensure_partial(frbch_handle* h) {
   CHECK_DEV(h, dev_malloc((void**)&h->partial, chunks * pl.ncol * 2 * sizeof(double)), "hipMalloc(partials)");
   return FRBCH_OK;
 }
+// A rescale interval starts with the K2 launch of `p` (out_mode, tile_major and stat_partial set).  The kernels add into the table, so
+// it is cleared first -- except for frbch_k2_priv, whose workgroups own a row each and store their first flush when told so
+// (KParams::stat_first): no memset in front of the pass, and frbch_stats_final reads those rows only (fused_live; the rows behind
+// them would be zeros: the sums are the same bit for bit, every column is added up in the same order).
+int clear_partial(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
+  const Plan& pl = h->pl;
+  int own = 0;   // rows this launch writes without reading them first
+#ifndef FRBCH_NO_FAST
+  if (const PrivLaunch pv = priv_launch(h, p, nb); pv.sums) own = priv_stat_chunks(pl, (int)pv.grid);   // (the launch launch_k2_fast makes of p)
+#endif
+  p.stat_first = own ? 1u : 0u;
+  h->fused_live = own;
+  return own ? FRBCH_OK : extend_partial(h, s);
+}
+// ... and goes on with another launch that adds into the table -- more workgroups, or the other K2 family: the rows nobody has
+// written yet are cleared now (never, when the interval ends with the launch it started with)
+int extend_partial(frbch_handle* h, dev_stream_t s) {
+  if (h->fused_live >= h->fused_chunks) return FRBCH_OK;
+  const size_t row_bytes = (size_t)h->pl.ncol * 2 * sizeof(double);
+  if (dev_memset((char*)h->partial + (size_t)h->fused_live * row_bytes, 0, (size_t)(h->fused_chunks - h->fused_live) * row_bytes, s) != 0)
+    return fail(h, FRBCH_E_DEVICE, "clear partial sums");
+  h->fused_live = h->fused_chunks;
+  return FRBCH_OK;
+}
 // the float rows of a buffered rescale interval (allocated on first use: a scan whose first interval takes the two-pass form never needs it)
 int ensure_powbuf(frbch_handle* h) {
   const int rc = ensure_partial(h);
@@ -815,11 +854,11 @@ int run_stats(frbch_handle* h, uint64_t rows, dev_stream_t s) {
     sp.c = pl.c;
     sp.nif = pl.nif;
     sp.flip = pl.flip;
-    sp.nchunk = h->fused_chunks;
+    sp.nchunk = h->fused_live;
     sp.cpw = stat_final_cpw(pl);
     sp.offset = h->offset;
     sp.scale = h->scale;
-    ProfScope ps(h, s, KID_STATS, (double)h->fused_chunks * pl.ncol * 16.0);
+    ProfScope ps(h, s, KID_STATS, (double)h->fused_live * pl.ncol * 16.0);
     REC_LAUNCH(h, frbch_stats_final, (int)((pl.ncol + sp.cpw - 1) / sp.cpw), 1, 256, 256 * 2 * sizeof(double), s, sp);
     CHECK_DEV(h, dev_check_launch(), "launch stats (final)");
     return FRBCH_OK;

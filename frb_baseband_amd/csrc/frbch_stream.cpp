@@ -327,17 +327,19 @@ int engine_feed_run(frbch_handle* h, const uint8_t* d_frames, uint32_t frame_byt
       // ---- two-pass rescale: statistics-only pass now, the digitising pass once the interval is complete ----------------------
       rc = ensure_partial(h);
       if (rc) break;
-      if (dev_memset(h->partial, 0, (size_t)h->fused_chunks * pl.ncol * 2 * sizeof(double), s) != 0) { rc = fail(h, FRBCH_E_DEVICE, "clear partial sums"); break; }
       p.out_mode = FRBCH_OUT_STATS;
       p.row0 = 0;
       p.stat_partial = h->partial;
       p.stat_limit = pl.interval_rows;
+      rc = clear_partial(h, p, nb, s);   // (frbch_k2_priv: nothing to clear)
+      if (rc) break;
       rc = launch_back(h, p, nb, s);
       if (rc) break;
       h->fused_rows = std::min<uint64_t>(rows, pl.interval_rows);
       h->fused_valid = true;
       h->deferred.active = true;
       h->deferred.p = p;
+      h->deferred.p.stat_first = 0;   // (the batch's later passes start no interval)
       h->deferred.nb = nb;
       h->deferred.rows = rows;
       if (rows >= pl.interval_rows) {   // the interval ends inside this batch: offset / scale now, then every row of the batch
@@ -357,8 +359,8 @@ int engine_feed_run(frbch_handle* h, const uint8_t* d_frames, uint32_t frame_byt
       p.out_mode = FRBCH_OUT_FLOAT_POWER;
       p.power_out = h->powbuf;
       p.row0 = h->pow_rows;
-      if (h->pow_rows == 0 && h->fused_chunks) {   // an interval starts here: K2 can sum it while writing it
-        if (dev_memset(h->partial, 0, (size_t)h->fused_chunks * pl.ncol * 2 * sizeof(double), s) != 0) { rc = fail(h, FRBCH_E_DEVICE, "clear partial sums"); break; }
+      const bool starts = h->pow_rows == 0 && h->fused_chunks;   // an interval starts here: K2 can sum it while writing it
+      if (starts) {
         h->fused_rows = 0;
         h->fused_valid = true;
       }
@@ -366,6 +368,9 @@ int engine_feed_run(frbch_handle* h, const uint8_t* d_frames, uint32_t frame_byt
         p.stat_partial = h->partial;
         p.stat_limit = pl.interval_rows;
       }
+      if (starts) rc = clear_partial(h, p, nb, s);
+      else if (p.stat_partial) rc = extend_partial(h, s);   // (the interval goes on: whichever K2 takes this launch finds its rows cleared)
+      if (rc) break;
       rc = launch_back(h, p, nb, s);
       if (rc) break;
       if (h->fused_valid) {

@@ -126,12 +126,18 @@ __global__ void __launch_bounds__(256, 2) frbch_k2_priv(KParams p) {
   // this workgroup's row of the fp64 partial sums is its own: a plain read-modify-write of the thread's 8 * CGT doubles, 16 bytes at
   // a time.  (No-return fp64 atomics were tried first -- no load, hence no wait in the loop: 159 M of them per IF took 2.1 ms, the
   // memory-side atomic units are far slower than the 1.2 GB they carry.)  The loads' wait also covers the next tile's loads, which
-  // the wave is about to wait for anyway: the flush sits at the very end of a trip.
-  auto flush_sums = [&]() {
+  // the wave is about to wait for anyway: the flush sits at the very end of a trip.  (Requested ahead -- in front of the transform,
+  // or behind the trip's first barrier -- the row spills with four products: 54 registers for all of it, 23 for half; profiles/NOTES.md, round 5, item 2.)
+  // `fresh`: the first flush of a launch that starts a rescale interval (p.stat_first).  Nobody cleared the row: it is not read, the
+  // sums are stored as 0.0 + sum, which is what the add into a cleared table gave.
+  // The statistics pass keeps its sums in the order the row lies in the LDS (input channels), the table is in output channel
+  // order: `flip` reverses the four columns of a group here, once per flush, not once per row.
+  auto flush_sums = [&](const bool fresh) {
     int tl = tid;
     asm volatile("" : "+v"(tl));   // (the CGT target addresses are recomputed here: hoisted out of the loop they were spilled)
     typedef double nd2 __attribute__((ext_vector_type(2)));
     constexpr int GB = CGT >= 2 ? 2 : 1;            // groups in flight at a time (16 registers each)
+    const bool fl = MODE == K2P_STATS && flip;      // (the float-row form sums in output order already)
 #pragma unroll
     for (int g0 = 0; g0 < CGT; g0 += GB) {
       nd2 cur[GB][4];
@@ -139,19 +145,25 @@ __global__ void __launch_bounds__(256, 2) frbch_k2_priv(KParams p) {
       for (int gg = 0; gg < GB; ++gg) {
         const int g = g0 + gg;
         const nd2* src = reinterpret_cast<const nd2*>(p.stat_partial + (((size_t)blockIdx.x * RS + (RS > 1 ? tl / NG : 0)) * NCOL + (size_t)((RS > 1 ? tl % NG : tl) + NT * g) * 4) * 2);
+        // (statistics pass: a first flush does not load at all.  The float-row form has no register to spare for the second path
+        // -- 10 spilled with it, none without (profiles/NOTES.md, round 5): it loads and drops what it gets, below)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) cur[gg][e] = src[e];
+        for (int e = 0; e < 4; ++e) cur[gg][e] = nd2{0.0, 0.0};
+        if (MODE != K2P_STATS || !fresh)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) cur[gg][e] = src[e];
       }
 #pragma unroll
       for (int gg = 0; gg < GB; ++gg) {
         const int g = g0 + gg;
         nd2* dst = reinterpret_cast<nd2*>(p.stat_partial + (((size_t)blockIdx.x * RS + (RS > 1 ? tl / NG : 0)) * NCOL + (size_t)((RS > 1 ? tl % NG : tl) + NT * g) * 4) * 2);
-        const float a1[4] = {of4[g].x, of4[g].y, of4[g].z, of4[g].w}, a2[4] = {sc4[g].x, sc4[g].y, sc4[g].z, sc4[g].w};
+        const float a1[4] = {fl ? of4[g].w : of4[g].x, fl ? of4[g].z : of4[g].y, fl ? of4[g].y : of4[g].z, fl ? of4[g].x : of4[g].w};
+        const float a2[4] = {fl ? sc4[g].w : sc4[g].x, fl ? sc4[g].z : sc4[g].y, fl ? sc4[g].y : sc4[g].z, fl ? sc4[g].x : sc4[g].w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           nd2 t = cur[gg][e];
-          t.x += (double)a1[e];
-          t.y += (double)a2[e];
+          t.x = (fresh ? 0.0 : t.x) + (double)a1[e];
+          t.y = (fresh ? 0.0 : t.y) + (double)a2[e];
           dst[e] = t;
         }
         of4[g] = sc4[g] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -173,8 +185,10 @@ __global__ void __launch_bounds__(256, 2) frbch_k2_priv(KParams p) {
     if (blk != cur_blk) {   // (workgroup-uniform) the DC repair of this block: dP[C ..] into the LDS; nobody reads the old one any more
       cur_blk = blk;
       const cf* dP = p.p0 + (size_t)blk * C2 + C;
+      int tl = tid;
+      asm volatile("" : "+v"(tl));   // (once or twice per workgroup: its addresses are formed here, not kept -- spilled -- across the loop)
 #pragma unroll
-      for (int i = 0; i < C / NT; ++i) dpl[pw_swz(tid + NT * i, ROT)] = dP[tid + NT * i];
+      for (int i = 0; i < C / NT; ++i) dpl[pw_swz(tl + NT * i, ROT)] = dP[tl + NT * i];
       __syncthreads();
     }
 
@@ -195,11 +209,15 @@ __global__ void __launch_bounds__(256, 2) frbch_k2_priv(KParams p) {
     for (int vt = 0; vt < VT; ++vt) {
       const int q = ql + LPS * vt;
       const int k0 = (q / M) + 16 * (q % M);
+      // the swizzle of k0 + TPS j repeats with period two in j (static_assert below): two addresses per virtual thread and constant
+      // offsets instead of sixteen addresses held -- or spilled -- across the loop
+      static_assert((2 * ROT * (TPS / 32)) % 32 == 0 && TPS % 32 == 0, "pw_swz(k + 2 TPS) == pw_swz(k) + 2 TPS");
+      const int ks0 = pw_swz(k0, ROT), ks1 = pw_swz(k0 + TPS, ROT);
       cf2* dst = reinterpret_cast<cf2*>(s + q * 18 + 8);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const cf a = add(v[vt][8 + 2 * i], dpl[pw_swz(k0 + TPS * (2 * i), ROT)]);
-        const cf b = add(v[vt][9 + 2 * i], dpl[pw_swz(k0 + TPS * (2 * i + 1), ROT)]);
+        const cf a = add(v[vt][8 + 2 * i], dpl[ks0 + 2 * TPS * i]);      // = pw_swz(k0 + TPS * (2 i), ROT)
+        const cf b = add(v[vt][9 + 2 * i], dpl[ks1 + 2 * TPS * i]);      // = pw_swz(k0 + TPS * (2 i + 1), ROT)
         dst[i] = cf2{a, b};
         __builtin_amdgcn_sched_barrier(0);
         load_reg(nbase, vt, 8 + 2 * i);
@@ -227,12 +245,12 @@ __global__ void __launch_bounds__(256, 2) frbch_k2_priv(KParams p) {
       for (int vt = 0; vt < VT; ++vt) {
         const int q = ql + LPS * vt;
         const int k0 = (q / M) + 16 * (q % M);
+        const int ks0 = pw_swz(k0, ROT), ks1 = pw_swz(k0 + TPS, ROT);
 #pragma unroll
         for (int kc = 0; kc < 8; ++kc) {
-          const int k = k0 + TPS * kc;
           const cf wk = v[vt][kc];
           const cf d = cf{wm[vt][kc].x, -wm[vt][kc].y};
-          const int ks = pw_swz(k, ROT);
+          const int ks = ((kc & 1) ? ks1 : ks0) + TPS * (kc & ~1);   // = pw_swz(k0 + TPS * kc, ROT), see the DC repair
           if constexpr (PM == 2) {
             row[ks] = 0.5f * ((wk.x * wk.x + wk.y * wk.y) + (d.x * d.x + d.y * d.y));
           } else if constexpr (PM >= 4) {
@@ -281,7 +299,8 @@ __global__ void __launch_bounds__(256, 2) frbch_k2_priv(KParams p) {
       const int nbit = p.nbit;
       const int cg0 = RS > 1 ? tid % NG : tid;          // this thread's first column group
       // one group of four columns of one output row: `a` = its sums in the order the row lies in the LDS (input channels)
-      auto emit_group = [&](const float4 a, const int g, const uint64_t orow) {
+      // (`chk`: std::true_type = the row enters the sums only below p.stat_limit; false_type = the caller knows that it does)
+      auto emit_group = [&](const float4 a, const int g, const uint64_t orow, auto chk) {
         const int col0 = (cg0 + NT * g) * 4, prod = col0 / C, cout0 = col0 - prod * C;
         if constexpr (MODE == K2P_CODES) {
           // rescale in the order the row lies in the LDS (= the order of offset / scale: input channels)
@@ -303,15 +322,19 @@ __global__ void __launch_bounds__(256, 2) frbch_k2_priv(KParams p) {
               p.code_out[oc >> 2] = (uint8_t)(code[0] | (code[1] << 2) | (code[2] << 4) | (code[3] << 6));
           }
         } else {
-          const float t4[4] = {flip ? a.w : a.x, flip ? a.z : a.y, flip ? a.y : a.z, flip ? a.x : a.w};   // output channel order
+          // float rows: output channel order, and the sums with them.  Statistics only: the sums stay in the order of the LDS row
+          // -- a sum does not care, flush_sums puts them into output order once per flush.  (Either way every column sees the same
+          // rows in the same order with the same operations.)
+          float4 t = a;
           if constexpr (MODE == K2P_POWER) {
-            const nf4 o4 = {t4[0], t4[1], t4[2], t4[3]};
+            t = make_float4(flip ? a.w : a.x, flip ? a.z : a.y, flip ? a.y : a.z, flip ? a.x : a.w);
+            const nf4 o4 = {t.x, t.y, t.z, t.w};
             __builtin_nontemporal_store(o4, reinterpret_cast<nf4*>(p.power_out + orow * (uint64_t)NCOL + col0));
           }
-          if (stat_on && orow < p.stat_limit) {
-            of4[g].x += t4[0]; of4[g].y += t4[1]; of4[g].z += t4[2]; of4[g].w += t4[3];
-            sc4[g].x = fmaf(t4[0], t4[0], sc4[g].x); sc4[g].y = fmaf(t4[1], t4[1], sc4[g].y);
-            sc4[g].z = fmaf(t4[2], t4[2], sc4[g].z); sc4[g].w = fmaf(t4[3], t4[3], sc4[g].w);
+          if (!decltype(chk)::value || (stat_on && orow < p.stat_limit)) {
+            of4[g].x += t.x; of4[g].y += t.y; of4[g].z += t.z; of4[g].w += t.w;
+            sc4[g].x = fmaf(t.x, t.x, sc4[g].x); sc4[g].y = fmaf(t.y, t.y, sc4[g].y);
+            sc4[g].z = fmaf(t.z, t.z, sc4[g].z); sc4[g].w = fmaf(t.w, t.w, sc4[g].w);
           }
         }
       };
@@ -320,7 +343,16 @@ __global__ void __launch_bounds__(256, 2) frbch_k2_priv(KParams p) {
         const int kb = flip ? (C - 4 - cout0) : cout0;
         return reinterpret_cast<const float4*>(reinterpret_cast<const float*>(lds + (size_t)t * SEQ) + prod * C + pw_swz(kb, ROT));
       };
-      if (lg_t == 0 && (MODE != K2P_CODES || nbit == 8)) {
+      // the statistics pass tests the end of the rescale interval once per tile (workgroup-uniform): a tile below it sums every
+      // row unasked, a tile behind it is not read at all, the one tile that straddles it takes the rolled path and asks per row
+      bool all_in = true, none_in = false;
+      if constexpr (MODE == K2P_STATS) {
+        const uint64_t lim = stat_on ? p.stat_limit : 0;
+        all_in = row_base + (uint64_t)rows_out <= lim;
+        none_in = row_base >= lim;
+      }
+      using Chk = std::integral_constant<bool, MODE != K2P_STATS>;
+      if (lg_t == 0 && (MODE != K2P_CODES || nbit == 8) && all_in) {
         // the common case, straight-line (in front of a rolled loop the compiler drains vmcnt: the next tile's loads, just
         // requested, would be waited for here): no tscrunch, 8-bit codes or float rows / sums; four rows at a time -- every LDS
         // read of the quartet requested first, then the arithmetic and the stores
@@ -336,9 +368,9 @@ __global__ void __launch_bounds__(256, 2) frbch_k2_priv(KParams p) {
 #pragma unroll
           for (int jj = 0; jj < QR; ++jj)
 #pragma unroll
-            for (int g = 0; g < CGT; ++g) emit_group(acc[jj][g], g, row_base + (uint64_t)(rph + RS * (j0 + jj)));
+            for (int g = 0; g < CGT; ++g) emit_group(acc[jj][g], g, row_base + (uint64_t)(rph + RS * (j0 + jj)), Chk());
         }
-      } else {
+      } else if (!none_in) {
         for (int j = rph; j < rows_out; j += RS) {
 #pragma unroll
           for (int g = 0; g < CGT; ++g) {
@@ -347,14 +379,14 @@ __global__ void __launch_bounds__(256, 2) frbch_k2_priv(KParams p) {
               const float4 x = *row_ptr((j << lg_t) + tt, g);
               acc.x += x.x; acc.y += x.y; acc.z += x.z; acc.w += x.w;
             }
-            emit_group(acc, g, row_base + (uint64_t)j);
+            emit_group(acc, g, row_base + (uint64_t)j, std::true_type());
           }
         }
       }
     }
     __syncthreads();   // the power rows are consumed: the next trip's first pass may overwrite the images
-    if constexpr (MODE != K2P_CODES) {
-      if (stat_on && ((it & kK2PFlushMask) == kK2PFlushMask || it + 1 == count)) flush_sums();   // at most 8 trips = 32 rows in fp32
+    if constexpr (MODE != K2P_CODES) {   // at most 8 trips = 32 rows in fp32
+      if (stat_on && ((it & kK2PFlushMask) == kK2PFlushMask || it + 1 == count)) flush_sums(p.stat_first && it <= kK2PFlushMask);   // (a workgroup's first flush has it <= 7)
     }
   }
 
