@@ -100,6 +100,14 @@ class FrbchRfiParams(C.Structure):
                 ("chan_frac", C.c_double), ("block_frac", C.c_double)]
 
 
+class FrbchRfiFparams(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("reserved", C.c_uint32), ("t_pow", C.c_double), ("chan_frac", C.c_double)]
+
+
+class FrbchRfiPeak(C.Structure):
+    _fields_ = [("num", C.c_float), ("k", C.c_uint32)]
+
+
 CAND_RFI, CAND_SERIES = 1, 2
 CAND_STAGES = ("upload", "flag", "dedisperse", "search", "cut", "download")      # FRBCH_CAND_T_*
 
@@ -210,6 +218,17 @@ SYMBOLS = {
                                           _P, _P, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
     "frbch_rfi_cleanp_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams), _P, C.c_int, _P, _P, _P,
                                         _P, _P, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_rfi_peaks_kernel": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams)]),
+    "frbch_rfi_peaks_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams), C.c_int, _P, _P,
+                                         C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_rfi_peaks_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams), C.c_int, _P, _P,
+                                       C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_rfi_periodic": (C.c_int, [C.POINTER(FrbchFilDesc), _P, _P, C.c_uint32, C.c_uint64, C.POINTER(FrbchRfiParams),
+                                     C.POINTER(FrbchRfiFparams), _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "frbch_rfi_cleanf_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams), C.POINTER(FrbchRfiFparams),
+                                          _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_rfi_cleanf_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams), C.POINTER(FrbchRfiFparams),
+                                        _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
     "frbch_candidates_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, _P, C.c_uint32, C.POINTER(FrbchCandParams), C.c_int,
                                         C.POINTER(_P), C.c_char_p, C.c_size_t]),
     "frbch_candidates_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, _P, C.c_uint32, C.POINTER(FrbchCandParams), C.c_int,

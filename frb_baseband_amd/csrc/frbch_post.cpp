@@ -1653,6 +1653,254 @@ extern "C" int frbch_rfi_clean_host(const frbch_fil_desc* fil, void* rows, uint6
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// interference: the periodicity test (the spectral peak of every block and channel)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int kPeaksGenericThreads = 256;
+
+// rfi_check, and block_rows as the transform length: *log2n = 3 .. 12
+int rfi_pcheck(const frbch_fil_desc* f, uint64_t nrows, const frbch_rfi_params* par, uint32_t* nblk, int* log2n, const PostErr& e) {
+  const int rc = rfi_check(f, nrows, par, nblk, e);
+  if (rc) return rc;
+  const uint32_t n = par->block_rows;
+  if (n < 8 || n > 4096 || (n & (n - 1)) != 0)
+    return e.fail(FRBCH_E_ARG, "the periodic test transforms whole blocks: block_rows must be a power of two in 8 .. 4096 (it is " +
+                                   std::to_string(n) + "); choose such a block_rows, or flag without the periodic test");
+  int L = 0;
+  while ((1u << L) < n) ++L;
+  *log2n = L;
+  return FRBCH_OK;
+}
+
+int rfi_fcheck(const frbch_rfi_fparams* fpar, const PostErr& e) {
+  if (!fpar || fpar->size != sizeof(frbch_rfi_fparams)) return e.fail(FRBCH_E_ARG, "frbch_rfi_fparams: wrong size");
+  if (!(fpar->t_pow > 0) || std::isinf(fpar->t_pow)) return e.fail(FRBCH_E_ARG, "t_pow must be positive and finite");
+  if (!(fpar->chan_frac >= 0) || fpar->chan_frac > 1.0) return e.fail(FRBCH_E_ARG, "chan_frac (periodic) must lie in 0..1");
+  return FRBCH_OK;
+}
+
+// The one decision behind frbch_rfi_peaks_device's launch, *kernel_used and frbch_rfi_peaks_kernel's answer: the clauses of the
+// fast statistics kernel, and a transform length the fast kernel has a plan for.
+bool rfi_peaks_fast(const frbch_fil_desc* fil, const void* d_rows, int log2n) {
+  return rfi_fast_tile(fil, d_rows) > 0 && log2n >= 8 && log2n <= 11;
+}
+
+// W[k] = ((float)cos(a), (float)(-sin(a))), a = 2.0 pi k / n in double, k < n / 2
+std::vector<float> rfi_twiddles(uint32_t n) {
+  std::vector<float> tw(n);
+  for (uint32_t k = 0; k < n / 2; ++k) {
+    const double a = 2.0 * M_PI * (double)k / (double)n;
+    tw[2 * k] = (float)cos(a);
+    tw[2 * k + 1] = (float)(-sin(a));
+  }
+  return tw;
+}
+
+#ifndef FRBCH_NO_FAST
+template <int BPV> int launch_peaks_fast(int log2n, dim3 grid, dev_stream_t s, const RfiParams& p) {
+  const dim3 block(fast::kPkThreads);
+  switch (log2n) {
+    case 8: return launch_lds(fast::frbch_post_rfi_peaks_fast<8, BPV, 4, 4, 0>, grid, block, fast::pk_lds(8), s, p);
+    case 9: return launch_lds(fast::frbch_post_rfi_peaks_fast<9, BPV, 3, 3, 3>, grid, block, fast::pk_lds(9), s, p);
+    case 10: return launch_lds(fast::frbch_post_rfi_peaks_fast<10, BPV, 4, 3, 3>, grid, block, fast::pk_lds(10), s, p);
+    case 11: return launch_lds(fast::frbch_post_rfi_peaks_fast<11, BPV, 4, 4, 3>, grid, block, fast::pk_lds(11), s, p);
+  }
+  return -1;
+}
+#endif
+}  // namespace
+
+extern "C" int frbch_rfi_peaks_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_rfi_params* par) {
+  PostErr e{nullptr, 0};
+  uint32_t nblk = 0;
+  int log2n = 0;
+  const int rc = rfi_pcheck(fil, nrows, par, &nblk, &log2n, e);
+  if (rc) return rc;
+  if (!d_rows) return FRBCH_E_ARG;
+  return rfi_peaks_fast(fil, d_rows, log2n) ? 1 : 0;
+}
+
+extern "C" int frbch_rfi_peaks_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_rfi_params* par,
+                                      int device, const void* d_stats, void* d_peaks, uint32_t* kernel_used, char* err,
+                                      size_t err_cap) try {
+  PostErr e{err, err_cap};
+  uint32_t nblk = 0;
+  int log2n = 0;
+  int rc = rfi_pcheck(fil, nrows, par, &nblk, &log2n, e);
+  if (rc) return rc;
+  if (!d_rows || !d_stats || !d_peaks) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  PostScope ps;
+  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  const dev_stream_t s = ps.s;
+  const uint32_t n = par->block_rows;
+  const std::vector<float> tw = rfi_twiddles(n);
+  float* d_tw = nullptr;
+  if (ps.alloc(&d_tw, tw.size() * sizeof(float)) != 0) return e.fail(FRBCH_E_NOMEM, "device memory for the twiddle table");
+  POST_DEV(dev_h2d(d_tw, tw.data(), tw.size() * sizeof(float), s), "upload the twiddle table");
+  RfiParams p = rfi_params(fil, d_rows, nrows, par, nblk);
+  p.stats_i = (unsigned long long*)d_stats;                      // (read only)
+  p.stats_f = (double*)d_stats;
+  p.peaks = (RfiPeak*)d_peaks;
+  p.tw = d_tw;
+  p.log2n = log2n;
+  const bool fast_k = rfi_peaks_fast(fil, d_rows, log2n);
+  for (uint32_t b0 = 0; b0 < nblk; b0 += kRfiGridBlocks) {
+    const uint32_t nb = std::min(kRfiGridBlocks, nblk - b0);
+    p.blk0 = b0;
+#ifndef FRBCH_NO_FAST
+    if (fast_k) {
+      const size_t piece = (size_t)fast::pk_piece(log2n);
+      const dim3 grid((unsigned)((size_t)fil->nchan * (fil->nbits / 8) / piece), nb);
+      const int lr = fil->nbits == 8 ? launch_peaks_fast<1>(log2n, grid, s, p) : launch_peaks_fast<2>(log2n, grid, s, p);
+      if (lr != 0) return e.fail(FRBCH_E_DEVICE, "the LDS of the peaks kernel was refused");
+    }
+#endif
+    if (!fast_k)
+      DEV_LAUNCH(frbch_post_rfi_peaks, (fil->nchan + 1) / 2, nb, kPeaksGenericThreads, (size_t)n * 8 + 2 * kPeaksGenericThreads * sizeof(RfiPeak), s, p);
+    POST_DEV(dev_check_launch(), "launch peaks");
+  }
+  POST_DEV(dev_sync(s), "sync");
+  if (kernel_used) *kernel_used = fast_k ? 1 : 0;
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_rfi_peaks_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_rfi_params* par,
+                                    int device, void* stats, void* peaks, uint32_t* kernel_used, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  uint32_t nblk = 0;
+  int log2n = 0;
+  int rc = rfi_pcheck(fil, nrows, par, &nblk, &log2n, e);
+  if (rc) return rc;
+  if (!rows || !peaks) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  const size_t ncell = (size_t)nblk * fil->nchan;
+  HostStage hs;
+  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
+  void* d_stats = hs.out(stats, ncell * 16);                     // (no host array: not downloaded)
+  void* d_peaks = hs.out(peaks, ncell * sizeof(frbch_rfi_peak));
+  return hs.run(e, "device memory for the rows", "upload rows", "download peaks", [&]() {
+    uint32_t used[2] = {0, 0};
+    int r = frbch_rfi_stats_device(fil, d_rows, nrows, par, device, d_stats, &used[0], err, err_cap);
+    if (!r) r = frbch_rfi_peaks_device(fil, d_rows, nrows, par, device, d_stats, d_peaks, &used[1], err, err_cap);
+    if (!r && kernel_used) { kernel_used[0] = used[0]; kernel_used[1] = used[1]; }
+    return r;
+  });
+}
+
+// The decision on the peaks (include/frbch.h), host only: IEEE double, every operation rounded on its own.
+extern "C" int frbch_rfi_periodic(const frbch_fil_desc* fil, const void* stats, const void* peaks, uint32_t nblk, uint64_t nrows,
+                                  const frbch_rfi_params* par, const frbch_rfi_fparams* fpar, uint8_t* pflag, uint8_t* pchan,
+                                  double* power, char* err, size_t err_cap) try {
+  POST_NO_CONTRACT
+  PostErr e{err, err_cap};
+  uint32_t want = 0;
+  int log2n = 0;
+  int rc = rfi_pcheck(fil, nrows, par, &want, &log2n, e);
+  if (rc) return rc;
+  if ((rc = rfi_fcheck(fpar, e)) != 0) return rc;
+  if (nblk != want) return e.fail(FRBCH_E_ARG, "nblk must be frbch_rfi_nblk()");
+  if (!stats || !peaks || !pflag || !pchan) return e.fail(FRBCH_E_ARG, "null argument");
+  const uint32_t nchan = fil->nchan;
+  const bool integer_rows = fil->nbits != 32;
+  const uint64_t n = par->block_rows;
+  const uint64_t n_last = nrows - (uint64_t)(nblk - 1) * n;
+  const frbch_rfi_peak* pk = (const frbch_rfi_peak*)peaks;
+  std::vector<uint32_t> count(nchan, 0);
+  for (uint32_t b = 0; b < nblk; ++b) {
+    const uint64_t rows_b = b + 1 < nblk ? n : n_last;
+    const double nb = (double)rows_b;
+    const double four_nb = 4.0 * nb;
+    for (uint32_t c = 0; c < nchan; ++c) {
+      const size_t cell = (size_t)b * nchan + c, i = cell * 2;
+      const double S = integer_rows ? (double)((const uint64_t*)stats)[i] : ((const double*)stats)[i];
+      const double Q = integer_rows ? (double)((const uint64_t*)stats)[i + 1] : ((const double*)stats)[i + 1];
+      const double m = S / nb;
+      const double mm = m * m;
+      const double qn = Q / nb;
+      double var = qn - mm;
+      if (var < 0.0) var = 0.0;
+      double p = 0.0;
+      if (2 * rows_b >= n && std::isfinite(m) && std::isfinite(var) && var != 0.0) {
+        const double den = four_nb * var;
+        p = (double)pk[cell].num / den;
+      }
+      if (power) power[cell] = p;
+      pflag[cell] = (uint8_t)(p > fpar->t_pow ? 1 : 0);
+      count[c] += pflag[cell];
+    }
+  }
+  const double chan_lim = fpar->chan_frac * (double)nblk;
+  for (uint32_t c = 0; c < nchan; ++c) pchan[c] = (uint8_t)((double)count[c] > chan_lim ? 1 : 0);
+  for (uint32_t b = 0; b < nblk; ++b)
+    for (uint32_t c = 0; c < nchan; ++c)
+      if (pchan[c]) pflag[(size_t)b * nchan + c] = 1;
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_rfi_cleanf_device(const frbch_fil_desc* fil, void* d_rows, uint64_t nrows, const frbch_rfi_params* par,
+                                       const frbch_rfi_fparams* fpar, const uint8_t* zap, int device, uint8_t* mask, double* repl,
+                                       uint8_t* chan_flag, uint8_t* blk_flag, uint8_t* pflag, uint8_t* pchan, void* peaks,
+                                       uint32_t* kernel_used, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  uint32_t nblk = 0;
+  int log2n = 0;
+  int rc = rfi_pcheck(fil, nrows, par, &nblk, &log2n, e);
+  if (rc) return rc;
+  if ((rc = rfi_fcheck(fpar, e)) != 0) return rc;
+  if (!d_rows || !mask || !repl || !chan_flag || !blk_flag || !pflag || !pchan) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  const size_t ncell = (size_t)nblk * fil->nchan;
+  std::vector<uint64_t> stats(ncell * 2);
+  std::vector<frbch_rfi_peak> own;
+  if (!peaks) own.resize(ncell);
+  void* pk = peaks ? peaks : (void*)own.data();
+  HostStage hs;
+  void* d_stats = hs.out((void*)stats.data(), ncell * 16);
+  void* d_peaks = hs.out(pk, ncell * sizeof(frbch_rfi_peak));
+  if (hs.failed) return e.fail(FRBCH_E_NOMEM, "device memory for the statistics and the peaks");
+  uint32_t used[2] = {0, 0};
+  rc = frbch_rfi_stats_device(fil, d_rows, nrows, par, device, d_stats, &used[0], err, err_cap);
+  if (!rc) rc = frbch_rfi_peaks_device(fil, d_rows, nrows, par, device, d_stats, d_peaks, &used[1], err, err_cap);
+  if (!rc && hs.download() != 0) rc = e.fail(FRBCH_E_DEVICE, "download statistics and peaks");
+  if (!rc) rc = frbch_rfi_periodic(fil, stats.data(), pk, nblk, nrows, par, fpar, pflag, pchan, nullptr, err, err_cap);
+  if (!rc) rc = frbch_rfi_mask(fil, stats.data(), nblk, nrows, par, zap, pflag, mask, repl, chan_flag, blk_flag, err, err_cap);
+  if (rc) return rc;
+  for (uint32_t c = 0; c < fil->nchan; ++c) chan_flag[c] = (uint8_t)(chan_flag[c] | pchan[c]);
+  if (kernel_used) { kernel_used[0] = used[0]; kernel_used[1] = used[1]; }
+  if (std::none_of(mask, mask + ncell, [](uint8_t m) { return m != 0; })) return FRBCH_OK;       // (nothing masked: nothing to write)
+  uint8_t* d_mask = hs.in(mask, ncell);
+  double* d_repl = hs.in(repl, fil->nchan * sizeof(double));
+  if (hs.failed) return e.fail(FRBCH_E_NOMEM, "device memory for the mask");
+  if (hs.upload() != 0) return e.fail(FRBCH_E_DEVICE, "upload mask");
+  return frbch_rfi_apply_device(fil, d_rows, nrows, par, d_mask, d_repl, device, err, err_cap);
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_rfi_cleanf_host(const frbch_fil_desc* fil, void* rows, uint64_t nrows, const frbch_rfi_params* par,
+                                     const frbch_rfi_fparams* fpar, const uint8_t* zap, int device, uint8_t* mask, double* repl,
+                                     uint8_t* chan_flag, uint8_t* blk_flag, uint8_t* pflag, uint8_t* pchan, void* peaks,
+                                     uint32_t* kernel_used, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  uint32_t nblk = 0;
+  int log2n = 0;
+  int rc = rfi_pcheck(fil, nrows, par, &nblk, &log2n, e);
+  if (rc) return rc;
+  if ((rc = rfi_fcheck(fpar, e)) != 0) return rc;
+  if (!rows || !mask || !repl || !chan_flag || !blk_flag || !pflag || !pchan) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  void* d_rows = hs.inout(rows, post_rows_bytes(fil, nrows));
+  return hs.run(e, "device memory for the rows", "upload rows", "download rows", [&]() {
+    return frbch_rfi_cleanf_device(fil, d_rows, nrows, par, fpar, zap, device, mask, repl, chan_flag, blk_flag, pflag, pchan, peaks,
+                                   kernel_used, err, err_cap);
+  });
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // resident rows: every product cleaned in one residency; flagging, search, grouping and cut-outs in one call
 // ---------------------------------------------------------------------------------------------------------------------
 extern "C" int frbch_rfi_cleanp_device(const frbch_fil_desc* fil_in, void* d_rows, uint64_t nrows, const frbch_rfi_params* par,

@@ -587,6 +587,7 @@ KERNEL(frbch_post_cutout, CutParams) {
 // Interference (frbch_rfi_*; include/frbch.h states the arithmetic): per (block of rows, channel) the sums S = sum x and
 // Q = sum x x of one product, and the in-place replacement of the masked cells.
 // ---------------------------------------------------------------------------------------------------------------------
+struct RfiPeak { float num; uint32_t k; };   // frbch_rfi_peak
 struct RfiParams {
   uint8_t* rows;               // [nrows][nifs][nchan] samples of `nbits`; product `prod` is used (apply writes it)
   uint64_t nrows;
@@ -599,6 +600,10 @@ struct RfiParams {
   const double* repl;          // [nchan], apply
   // ---- fast kernel (kernels_post_fast.inc) ----
   int tile_bytes, ntile;       // bytes of a row a workgroup owns (a power of two, 64 .. 1024); tiles per row
+  // ---- periodicity (frbch_rfi_peaks_*): n = block_rows = 2^log2n ----
+  const float* tw;             // [n / 2][2] the host's table W[k] = (cos, -sin)(2 pi k / n)
+  RfiPeak* peaks;              // [nblk][nchan]
+  int log2n, pad2;
 };
 
 // The generic form, the correctness anchor and the fallback (and the only kernel for float rows): grid (ceil(nchan / 256),
@@ -671,6 +676,150 @@ KERNEL(frbch_post_rfi_apply, RfiParams) {
         const float v = (float)r;
         for (uint64_t t = r0; t < r1; ++t) ((float*)p.rows)[t * pitch + first] = v;
       }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Periodicity (frbch_rfi_peaks_*; include/frbch.h states the arithmetic): the largest bin of the power spectrum of every
+// (block, channel) cell, two real channels per complex transform.  The helpers below ARE the arithmetic: the generic kernel
+// and the fast one (kernels_post_fast.inc) call the same butterfly and the same bin formula, so that they differ in schedule only.
+// ---------------------------------------------------------------------------------------------------------------------
+DEVFN inline bool rfi_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
+
+// the mean of a cell and whether the cell is tested: S, Q, mean and var of step 1 of frbch_rfi_mask
+DEVFN inline bool rfi_cell_mean(const RfiParams& p, uint64_t b, int c, double nb, double* mean) {
+  POST_NO_CONTRACT
+  const size_t i = ((size_t)b * p.nchan + c) * 2;
+  const double S = p.nbits == 32 ? p.stats_f[i] : (double)p.stats_i[i];
+  const double Q = p.nbits == 32 ? p.stats_f[i + 1] : (double)p.stats_i[i + 1];
+  const double m = S / nb;
+  const double mm = m * m;
+  const double qn = Q / nb;
+  double var = qn - mm;
+  if (var < 0.0) var = 0.0;                                                        // (a NaN stays a NaN)
+  *mean = m;
+  return rfi_finite(m) && rfi_finite(var) && var != 0.0;
+}
+
+// u' = u + w v, v' = u - w v: the two products of each component first, every operation rounded on its own
+DEVFN inline void rfi_bfly(float& ur, float& ui, float& vr, float& vi, float wr, float wi) {
+  POST_NO_CONTRACT
+  const float a = wr * vr;
+  const float b = wi * vi;
+  const float c = wr * vi;
+  const float d = wi * vr;
+  const float tr = a - b;
+  const float ti = c + d;
+  const float xr = ur + tr;
+  const float xi = ui + ti;
+  const float yr = ur - tr;
+  const float yi = ui - ti;
+  ur = xr; ui = xi; vr = yr; vi = yi;
+}
+
+// bin k of the two channels of a pair from A = Z[k], B = Z[n - k]
+DEVFN inline void rfi_bins(float ar, float ai, float br, float bi, float* n0, float* n1) {
+  POST_NO_CONTRACT
+  const float s0 = ar + br;
+  const float d0 = ai - bi;
+  const float s1 = ai + bi;
+  const float d1 = br - ar;
+  const float s0s = s0 * s0;
+  const float d0d = d0 * d0;
+  const float s1s = s1 * s1;
+  const float d1d = d1 * d1;
+  *n0 = s0s + d0d;
+  *n1 = s1s + d1d;
+}
+
+DEVFN inline int rfi_bitrev(int j, int bits) {
+  int r = 0;
+  for (int q = 0; q < bits; ++q) { r = (r << 1) | (j & 1); j >>= 1; }
+  return r;
+}
+
+// The generic form, the correctness anchor and the fallback (and the only kernel for float rows): grid (ceil(nchan / 2), nblk),
+// a workgroup per (block, channel pair); smem = n complex values and 2 x nthr partial peaks.  One stage of n / 2 butterflies
+// between two barriers; then every thread walks the bins k = 1 + tid, 1 + tid + nthr, ... and one thread per channel takes the
+// largest of the partials, the lowest k among equals -- what the walk over ascending k keeps.
+KERNEL(frbch_post_rfi_peaks, RfiParams) {
+  K_PROLOGUE;
+  const int n = (int)p.block_rows, L = p.log2n;
+  float* z = (float*)smem;                                                         // [n][2]
+  RfiPeak* part = (RfiPeak*)(smem + (size_t)n * 8);                                // [2][nthr]
+  const uint64_t b = (uint64_t)p.blk0 + (uint64_t)by;
+  const int c0 = 2 * bx, c1 = c0 + 1;
+  const uint64_t r0 = b * p.block_rows;
+  const uint64_t r1 = r0 + p.block_rows < p.nrows ? r0 + p.block_rows : p.nrows;
+  const int nbr = (int)(r1 - r0);
+  double mean0 = 0.0, mean1 = 0.0;
+  bool t0 = false, t1 = false;
+  if (2 * nbr >= n) {
+    t0 = rfi_cell_mean(p, b, c0, (double)nbr, &mean0);
+    if (c1 < p.nchan) t1 = rfi_cell_mean(p, b, c1, (double)nbr, &mean1);
+  }
+  const uint64_t pitch = (uint64_t)p.nifs * (uint64_t)p.nchan;
+  const uint64_t first = (uint64_t)p.prod * (uint64_t)p.nchan;
+  PHASE {
+    POST_NO_CONTRACT
+    for (int j = tid; j < n; j += nthr) {
+      float x0 = 0.f, x1 = 0.f;
+      if (j < nbr) {
+        const uint64_t i = (r0 + (uint64_t)j) * pitch + first;
+        if (t0) {
+          const double v = p.nbits == 8 ? (double)p.rows[i + c0] : p.nbits == 16 ? (double)((const uint16_t*)p.rows)[i + c0]
+                                                                                  : (double)((const float*)p.rows)[i + c0];
+          const double d = v - mean0;
+          x0 = (float)d;
+        }
+        if (t1) {
+          const double v = p.nbits == 8 ? (double)p.rows[i + c1] : p.nbits == 16 ? (double)((const uint16_t*)p.rows)[i + c1]
+                                                                                  : (double)((const float*)p.rows)[i + c1];
+          const double d = v - mean1;
+          x1 = (float)d;
+        }
+      }
+      const int i = rfi_bitrev(j, L);
+      z[2 * i] = x0;
+      z[2 * i + 1] = x1;
+    }
+  }
+  SYNC;
+  for (int s = 1; s <= L; ++s) {
+    PHASE {
+      const int half = 1 << (s - 1);
+      for (int i = tid; i < n / 2; i += nthr) {
+        const int j = i & (half - 1);
+        const int u = ((i >> (s - 1)) << s) + j, v = u + half;
+        const int k = j << (L - s);
+        rfi_bfly(z[2 * u], z[2 * u + 1], z[2 * v], z[2 * v + 1], p.tw[2 * k], p.tw[2 * k + 1]);
+      }
+    }
+    SYNC;
+  }
+  PHASE {
+    RfiPeak q0, q1;
+    q0.num = 0.f; q0.k = 0u; q1.num = 0.f; q1.k = 0u;
+    for (int k = 1 + tid; k < n / 2; k += nthr) {
+      float n0, n1;
+      rfi_bins(z[2 * k], z[2 * k + 1], z[2 * (n - k)], z[2 * (n - k) + 1], &n0, &n1);
+      if (n0 > q0.num) { q0.num = n0; q0.k = (uint32_t)k; }
+      if (n1 > q1.num) { q1.num = n1; q1.k = (uint32_t)k; }
+    }
+    part[tid] = q0;
+    part[nthr + tid] = q1;
+  }
+  SYNC;
+  PHASE {
+    if (tid < 2 && c0 + tid < p.nchan) {
+      RfiPeak best;
+      best.num = 0.f; best.k = 0u;
+      for (int t = 0; t < nthr; ++t) {
+        const RfiPeak q = part[tid * nthr + t];
+        if (q.num > best.num || (q.num == best.num && q.k < best.k)) best = q;
+      }
+      p.peaks[(size_t)b * p.nchan + c0 + tid] = best;
     }
   }
 }

@@ -484,4 +484,198 @@ __global__ void __launch_bounds__(kRfiThreads) frbch_post_rfi_stats_fast(RfiPara
     }
   }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Periodicity: the spectral peak of every (block, channel) cell (HIP only; frbch_post_rfi_peaks of kernels_post.inc stays the
+// emulable form, the fallback and the kernel of float rows; both call rfi_bfly and rfi_bins, so they differ in schedule only).
+// A workgroup of 256 threads owns one block of n = 2^L rows and a piece of pk_piece(L) bytes of the row (64 bytes up to
+// n = 512, 32 at 1024, 16 at 2048: the raw columns take at most 40 KB of the LDS, so that two workgroups share a CU).
+//  1. The piece of every row goes to the LDS as raw bytes: the piece / 16 lanes of a row side by side with 16 bytes each,
+//     coalesced across the tile, four loads in flight per lane; rows padded by one word against bank conflicts.
+//  2. pk_np(L) channel pairs at a time are transformed side by side in a second LDS buffer (NP n = 4096 complex values; one
+//     pair at n = 2048).  The transform is two or three register passes of radix 16 or 8 (R0 + R1 + R2 = L stages), each a
+//     network of the radix-2 butterflies of include/frbch.h on 2^R values a thread holds: the first pass converts the raw
+//     samples (minus the cell's mean, in double) straight from the bit-reversed rows it needs, the others exchange through
+//     the buffer, whose index i sits at i + i / 16 (a stride of 16 complex values would otherwise stay on two banks).
+//  3. 256 / NP threads per pair walk the bins in ascending k; a shuffle reduction per wave segment and ONE thread per
+//     (pair, channel) keep the largest value, the lowest k among equals, and store the cell: no global atomics.
+constexpr int kPkThreads = 256;
+constexpr int pk_np(int L) { return L >= 11 ? 1 : 4096 >> L; }
+constexpr int pk_piece(int L) { return (32768 >> L) > 64 ? 64 : (32768 >> L); }
+constexpr int pk_pad(int i) { return i + (i >> 4); }
+constexpr size_t kPkHead = 1280;           // means (64 doubles), tested flags (64 words), partial peaks (32)
+constexpr size_t pk_lds(int L) {
+  return kPkHead + (size_t)(4 << L) + (size_t)pk_np(L) * pk_pad(1 << L) * 8 + ((size_t)4 << L) * (pk_piece(L) / 4 + 1);
+}
+constexpr int pk_brev(int m, int bits) {
+  int r = 0;
+  for (int q = 0; q < bits; ++q) r |= ((m >> q) & 1) << (bits - 1 - q);
+  return r;
+}
+
+// stages S0 + 1 .. S0 + R on the 2^R values of index lo + (m << S0) + (hi << (S0 + R)), m = 0 .. 2^R - 1
+template <int L, int S0, int R>
+__device__ __forceinline__ void pk_pass(float (&vr)[1 << R], float (&vi)[1 << R], int lo, const float2* tw) {
+#pragma unroll
+  for (int q = 1; q <= R; ++q) {
+    const int hq = 1 << (q - 1);
+#pragma unroll
+    for (int m = 0; m < (1 << R); ++m) {
+      if (m & hq) continue;
+      const int j = lo + ((m & (hq - 1)) << S0);
+      const float2 w = tw[j << (L - S0 - q)];
+      rfi_bfly(vr[m], vi[m], vr[m + hq], vi[m + hq], w.x, w.y);
+    }
+  }
+}
+
+// a pass that exchanges through the buffer: every value is read and written by the one thread that owns it in this pass
+template <int L, int S0, int R, int NP>
+__device__ __forceinline__ void pk_pass_lds(float2* buf, const float2* tw, int tid) {
+  constexpr int N = 1 << L, NPAD = pk_pad(N), G = N >> R;
+  for (int w = tid; w < NP * G; w += kPkThreads) {
+    const int q = w / G, g = w & (G - 1);
+    const int lo = g & ((1 << S0) - 1), hi = g >> S0;
+    float2* z = buf + q * NPAD;
+    const int at = lo + (hi << (S0 + R));
+    float vr[1 << R], vi[1 << R];
+#pragma unroll
+    for (int m = 0; m < (1 << R); ++m) {
+      const float2 v = z[pk_pad(at + (m << S0))];
+      vr[m] = v.x; vi[m] = v.y;
+    }
+    pk_pass<L, S0, R>(vr, vi, lo, tw);
+#pragma unroll
+    for (int m = 0; m < (1 << R); ++m) z[pk_pad(at + (m << S0))] = make_float2(vr[m], vi[m]);
+  }
+}
+
+template <int L, int BPV, int R0, int R1, int R2>
+__global__ void __launch_bounds__(kPkThreads) frbch_post_rfi_peaks_fast(RfiParams p) {
+  constexpr int N = 1 << L, NP = pk_np(L), PB = pk_piece(L), CH = PB / BPV, PAIRS = CH / 2, RS = PB / 4 + 1, LANES = PB / 16;
+  constexpr int NPAD = pk_pad(N), G0 = N >> R0;
+  constexpr int TPP = kPkThreads / NP, W = TPP < 64 ? TPP : 64, PARTS = TPP / W;
+  static_assert(R0 + R1 + R2 == L && R0 >= 1 && R1 >= 1 && PAIRS % NP == 0 && CH <= 64 && NP * PARTS * 2 <= 32, "plan");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  double* mean = reinterpret_cast<double*>(smem);
+  uint32_t* tested = reinterpret_cast<uint32_t*>(smem + 512);
+  RfiPeak* red = reinterpret_cast<RfiPeak*>(smem + 768);
+  float2* tw = reinterpret_cast<float2*>(smem + kPkHead);
+  float2* buf = tw + N / 2;
+  uint32_t* raw = reinterpret_cast<uint32_t*>(buf + NP * NPAD);
+  const int tid = threadIdx.x;
+  const int ch0 = (int)blockIdx.x * CH;                                   // first channel of the piece
+  const uint64_t b = (uint64_t)p.blk0 + blockIdx.y;
+  const uint64_t r0 = b * p.block_rows;
+  const uint64_t r1 = r0 + p.block_rows < p.nrows ? r0 + p.block_rows : p.nrows;
+  const int nbr = (int)(r1 - r0);
+  RfiPeak* out = p.peaks + (size_t)b * p.nchan + ch0;
+  if (2 * nbr < N) {                                                      // the whole block is not tested (the same in every thread)
+    if (tid < CH) { RfiPeak z; z.num = 0.f; z.k = 0u; out[tid] = z; }
+    return;
+  }
+  for (int i = tid; i < N / 2; i += kPkThreads) tw[i] = reinterpret_cast<const float2*>(p.tw)[i];
+  if (tid < CH) {
+    double m = 0.0;
+    tested[tid] = rfi_cell_mean(p, b, ch0 + tid, (double)nbr, &m) ? 1u : 0u;
+    mean[tid] = m;
+  }
+  {
+    const size_t stride = (size_t)p.nifs * p.nchan * BPV;                 // bytes between rows of the file
+    const unsigned char* src = p.rows + (size_t)p.prod * p.nchan * BPV + (size_t)blockIdx.x * PB + r0 * stride;
+    const int total = nbr * LANES;
+    for (int i0 = tid; i0 < total; i0 += kPkThreads * 4) {
+      frbch_nf4 v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int i = i0 + u * kPkThreads;
+        if (i < total) v[u] = __builtin_nontemporal_load(reinterpret_cast<const frbch_nf4*>(src + (size_t)(i / LANES) * stride + (size_t)(i % LANES) * 16));
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int i = i0 + u * kPkThreads;
+        if (i < total) {
+          uint32_t* d = raw + (i / LANES) * RS + (i % LANES) * 4;
+          d[0] = __float_as_uint(v[u].x); d[1] = __float_as_uint(v[u].y); d[2] = __float_as_uint(v[u].z); d[3] = __float_as_uint(v[u].w);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int rd = 0; rd < PAIRS / NP; ++rd) {
+    for (int w = tid; w < NP * G0; w += kPkThreads) {                     // pass 0: from the raw rows
+      const int q = w / G0, base = w & (G0 - 1);
+      const int pq = rd * NP + q;                                         // pair of the piece: channels 2 pq, 2 pq + 1
+      const double m0 = mean[2 * pq], m1 = mean[2 * pq + 1];
+      const bool t0 = tested[2 * pq] != 0u, t1 = tested[2 * pq + 1] != 0u;
+      const int jlo = (int)(__brev((unsigned)base) >> (32 - (L - R0)));
+      float vr[1 << R0], vi[1 << R0];
+#pragma unroll
+      for (int m = 0; m < (1 << R0); ++m) {
+        const int j = (pk_brev(m, R0) << (L - R0)) + jlo;
+        float x0 = 0.f, x1 = 0.f;
+        if (j < nbr) {
+          uint32_t a, c;
+          if constexpr (BPV == 1) {
+            const uint32_t word = raw[j * RS + (pq >> 1)] >> (16 * (pq & 1));
+            a = word & 0xFFu; c = (word >> 8) & 0xFFu;
+          } else {
+            const uint32_t word = raw[j * RS + pq];
+            a = word & 0xFFFFu; c = word >> 16;
+          }
+          if (t0) x0 = (float)((double)a - m0);
+          if (t1) x1 = (float)((double)c - m1);
+        }
+        vr[m] = x0; vi[m] = x1;
+      }
+      pk_pass<L, 0, R0>(vr, vi, 0, tw);
+      float2* z = buf + q * NPAD;
+#pragma unroll
+      for (int m = 0; m < (1 << R0); ++m) z[pk_pad((base << R0) + m)] = make_float2(vr[m], vi[m]);
+    }
+    __syncthreads();
+    pk_pass_lds<L, R0, R1, NP>(buf, tw, tid);
+    __syncthreads();
+    if constexpr (R2 > 0) {
+      pk_pass_lds<L, R0 + R1, R2, NP>(buf, tw, tid);
+      __syncthreads();
+    }
+    {
+      const int q = tid / TPP, t = tid & (TPP - 1);
+      const float2* z = buf + q * NPAD;
+      float num0 = 0.f, num1 = 0.f;
+      uint32_t k0 = 0u, k1 = 0u;
+      for (int k = 1 + t; k < N / 2; k += TPP) {
+        const float2 A = z[pk_pad(k)], B = z[pk_pad(N - k)];
+        float n0, n1;
+        rfi_bins(A.x, A.y, B.x, B.y, &n0, &n1);
+        if (n0 > num0) { num0 = n0; k0 = (uint32_t)k; }
+        if (n1 > num1) { num1 = n1; k1 = (uint32_t)k; }
+      }
+#pragma unroll
+      for (int off = W / 2; off >= 1; off >>= 1) {                        // within an aligned segment of W lanes
+        const float on0 = __shfl_xor(num0, off), on1 = __shfl_xor(num1, off);
+        const uint32_t ok0 = (uint32_t)__shfl_xor((int)k0, off), ok1 = (uint32_t)__shfl_xor((int)k1, off);
+        if (on0 > num0 || (on0 == num0 && ok0 < k0)) { num0 = on0; k0 = ok0; }
+        if (on1 > num1 || (on1 == num1 && ok1 < k1)) { num1 = on1; k1 = ok1; }
+      }
+      if ((t & (W - 1)) == 0) {
+        RfiPeak* d = red + (q * PARTS + t / W) * 2;
+        d[0].num = num0; d[0].k = k0;
+        d[1].num = num1; d[1].k = k1;
+      }
+    }
+    __syncthreads();                                                      // (also: every read of buf is behind us)
+    if (tid < NP * 2) {
+      const int q = tid >> 1, ch = tid & 1;
+      RfiPeak best = red[(q * PARTS) * 2 + ch];
+#pragma unroll
+      for (int part = 1; part < PARTS; ++part) {
+        const RfiPeak o = red[(q * PARTS + part) * 2 + ch];
+        if (o.num > best.num || (o.num == best.num && o.k < best.k)) best = o;
+      }
+      out[2 * (rd * NP + q) + ch] = best;
+    }
+  }
+}
 }  // namespace fast

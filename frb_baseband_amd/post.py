@@ -16,6 +16,9 @@ reference's `dspsr -E <par> ... <IFall.fil>` stage) of SIGPROC filterbank files,
 * ``rfifind_fil`` / ``clean`` flag interference per (block of rows, channel) from block statistics taken on the GPU, write
   and read the flag file the reference carries to Heimdall and FETCH (create_config.py:54-56 ``-F/--flag``), and replace the
   masked samples: ``search_fil`` and ``candidates_fil`` take ``flag_file`` / ``rfi`` and then work on the cleaned rows.
+  ``periodic`` (``--periodic``) adds the periodicity test: the largest bin of the power spectrum of every cell
+  (``rfi_peaks``: frbch_rfi_peaks_host) against a threshold (``rfi_periodic``, ``t_pow_of``), for interference too weak for
+  the test on mean and std that still adds up in every dedispersed series.
 * ``resident=True`` (``--resident``) of ``search_fil``, ``candidates_fil`` and ``rfifind_fil``: the rows cross to the device
   once per command and stay there from flagging to cut-outs (``candidates_resident``: frbch_candidates_host; ``cleanp``:
   frbch_rfi_cleanp_host); the files and the returned values are those of the default path, byte for byte.
@@ -279,12 +282,93 @@ def rfi_mask(stats, hdr: dict, nrows: int, params=None, zap=None, prior=None, pr
     return dict(mask=mask, repl=repl, chan_flag=cf.astype(bool), blk_flag=bf.astype(bool))
 
 
-def _clean_from_stats(lib, x, hdr, par, stats, prods, z, repl, device):
-    """The two passes of ``clean`` on statistics already taken: the mask of every listed product, their union, then
-    frbch_rfi_mask per product with ``prior`` = the union and frbch_rfi_apply_host on ``x`` in place; ``repl[p]`` is filled.
+PEAK = np.dtype([("num", "<f4"), ("k", "<u4")])                 # frbch_rfi_peak
+
+
+def t_pow_of(sigma: float, n: int) -> float:
+    """The normalised spectral power that one of the n/2 - 1 bins of a noise cell (each exponentially distributed with mean 1)
+    exceeds with the one-sided probability of ``sigma`` Gaussian sigma: -ln(q / (n/2 - 1)), q = erfc(sigma / sqrt 2) / 2."""
+    import math
+    if n < 8:
+        raise InputError("t_pow_of: a transform of at least 8 rows")
+    return -math.log(0.5 * math.erfc(float(sigma) / math.sqrt(2.0)) / (n // 2 - 1))
+
+
+def _periodic_block(block_rows: int) -> int:
+    n = int(block_rows)
+    if not (8 <= n <= 4096 and n & (n - 1) == 0):
+        raise InputError("the periodic test transforms whole blocks: block_rows must be a power of two in 8 .. 4096 (it is %d); "
+                         "choose such a block_rows (1024 is the default) or leave the periodic test out" % n)
+    return n
+
+
+def rfi_fparams(periodic, par: _lib.FrbchRfiParams) -> _lib.FrbchRfiFparams:
+    """``periodic``: ``True`` / ``dict(t_freq=4.0)`` (Gaussian sigma, turned into a power by ``t_pow_of``) or ``dict(t_pow=...)``,
+    with an optional ``chan_frac`` (default: the time-domain one) -> the library's struct"""
+    if isinstance(periodic, _lib.FrbchRfiFparams):
+        return periodic
+    kw = dict(periodic) if isinstance(periodic, dict) else {}
+    unknown = set(kw) - {"t_freq", "t_pow", "chan_frac"}
+    if unknown or ("t_freq" in kw and "t_pow" in kw):
+        raise InputError("periodic: t_freq OR t_pow, and chan_frac" + (" (unknown: %s)" % ", ".join(sorted(unknown)) if unknown else ""))
+    n = _periodic_block(par.block_rows)
+    f = _lib.FrbchRfiFparams()
+    f.size = C.sizeof(_lib.FrbchRfiFparams)
+    f.t_pow = float(kw["t_pow"]) if "t_pow" in kw else t_pow_of(kw.get("t_freq", 4.0), n)
+    f.chan_frac = float(kw.get("chan_frac", par.chan_frac))
+    return f
+
+
+def rfi_peaks(rows, hdr: dict, params=None, product: int = 0, device: int = 0, lib=None, info: dict | None = None,
+              want_stats: bool = False):
+    """The spectral peak of every (block, channel) cell of one product (frbch_rfi_peaks_host: one upload, the block statistics
+    and the peaks) -> ``PEAK`` [nblk][nchan] (num = four times the largest power of the cell's own transform, k = its bin;
+    {0, 0}: not tested), or (peaks, stats) with ``want_stats``.  ``info['kernel_used']``: (statistics, peaks), 1 = fast."""
+    lib = lib or _lib.load()
+    x = _rows3(rows, hdr)
+    par = rfi_params(params)
+    _periodic_block(par.block_rows)
+    desc = fil_desc(hdr, product)
+    nblk = lib.frbch_rfi_nblk(x.shape[0], par.block_rows)
+    stats = np.zeros((nblk, hdr["nchans"], 2), dtype=np.float64 if hdr["nbits"] == 32 else np.uint64)
+    peaks = np.zeros((nblk, hdr["nchans"]), dtype=PEAK)
+    used = (C.c_uint32 * 2)(0, 0)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_rfi_peaks_host(C.byref(desc), x.ctypes.data, x.shape[0], C.byref(par), device, stats.ctypes.data,
+                                    peaks.ctypes.data, used, err, len(err)), err)
+    if info is not None:
+        info["kernel_used"] = (used[0], used[1])
+    return (peaks, stats) if want_stats else peaks
+
+
+def rfi_periodic(stats, peaks, hdr: dict, nrows: int, params=None, periodic=None, product: int = 0, lib=None) -> dict:
+    """The decision on the peaks (frbch_rfi_periodic, host only; include/frbch.h states it) -> dict(pflag uint8 [nblk][nchan],
+    pchan bool [nchan], power float64 [nblk][nchan], t_pow)."""
+    lib = lib or _lib.load()
+    par = rfi_params(params)
+    fpar = rfi_fparams(periodic, par)
+    desc = fil_desc(hdr, product)
+    nchan = hdr["nchans"]
+    st = np.ascontiguousarray(stats, dtype=np.float64 if hdr["nbits"] == 32 else np.uint64)
+    pk = np.ascontiguousarray(peaks, dtype=PEAK)
+    if st.ndim != 3 or st.shape[1:] != (nchan, 2) or pk.shape != st.shape[:2]:
+        raise InputError("stats must be [nblk][nchans][2] and peaks [nblk][nchans]")
+    nblk = st.shape[0]
+    pflag, pchan, power = np.zeros((nblk, nchan), np.uint8), np.zeros(nchan, np.uint8), np.zeros((nblk, nchan), np.float64)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_rfi_periodic(C.byref(desc), st.ctypes.data, pk.ctypes.data, nblk, int(nrows), C.byref(par), C.byref(fpar),
+                                  pflag.ctypes.data, pchan.ctypes.data, power.ctypes.data, err, len(err)), err)
+    return dict(pflag=pflag, pchan=pchan.astype(bool), power=power, t_pow=fpar.t_pow)
+
+
+def _clean_from_stats(lib, x, hdr, par, stats, prods, z, repl, device, priors=None):
+    """The two passes of ``clean`` on statistics already taken: the mask of every listed product (with ``priors[i]``, the
+    periodic flags of product i, as its ``prior``), their union, then frbch_rfi_mask per product with ``prior`` = the union
+    and frbch_rfi_apply_host on ``x`` in place; ``repl[p]`` is filled.
     -> (mask, chan_flag, blk_flag)"""
     err = C.create_string_buffer(512)
-    first = [rfi_mask(st, hdr, x.shape[0], par, zap=z, product=p, lib=lib) for st, p in zip(stats, prods)]
+    priors = priors or [None] * len(prods)
+    first = [rfi_mask(st, hdr, x.shape[0], par, zap=z, prior=pr, product=p, lib=lib) for st, p, pr in zip(stats, prods, priors)]
     mask = np.bitwise_or.reduce([r["mask"] for r in first])
     cf = np.logical_or.reduce([r["chan_flag"] for r in first])
     bf = np.logical_or.reduce([r["blk_flag"] for r in first])
@@ -297,12 +381,37 @@ def _clean_from_stats(lib, x, hdr, par, stats, prods, z, repl, device):
     return mask, cf, bf
 
 
-def clean(rows, hdr: dict, params=None, zap=None, device: int = 0, lib=None, info: dict | None = None, products=None):
+def _periodic_pass(lib, x, hdr, par, fpar, prods, device):
+    """statistics and peaks of every listed product (one upload each) and the periodic decision on them
+    -> (stats list, pflag list, dict(pflag, pchan, peaks [nifs][nblk][nchan], t_pow), statistics kernels, peaks kernels)"""
+    stats, pflags, ks, kp = [], [], [], []
+    peaks = None
+    pchan = np.zeros(x.shape[2], bool)
+    for p in prods:
+        i = {}
+        pk, st = rfi_peaks(x, hdr, par, product=p, device=device, lib=lib, info=i, want_stats=True)
+        if peaks is None:
+            peaks = np.zeros((x.shape[1],) + pk.shape, dtype=PEAK)
+        peaks[p] = pk
+        dec = rfi_periodic(st, pk, hdr, x.shape[0], par, fpar, product=p, lib=lib)
+        stats.append(st)
+        pflags.append(dec["pflag"])
+        pchan |= dec["pchan"]
+        ks.append(i["kernel_used"][0])
+        kp.append(i["kernel_used"][1])
+    return stats, pflags, dict(pflag=np.bitwise_or.reduce(pflags), pchan=pchan, peaks=peaks, t_pow=fpar.t_pow), ks, kp
+
+
+def clean(rows, hdr: dict, params=None, zap=None, device: int = 0, lib=None, info: dict | None = None, products=None, periodic=None):
     """Flag and replace -> (cleaned copy of the rows, dict(mask [nblk][nchan], repl [nifs][nchan], chan_flag, blk_flag)).
     One product (``nifs = 1``, or ``products = [p]``): one frbch_rfi_clean_host call.  Several: pass one takes the mask of
     every product, the masks are ORed, pass two asks frbch_rfi_mask again per product with ``prior`` = the union -- all
     products are cleaned in the same cells, each with its own replacement values (frbch_rfi_apply_host per product).
-    Products not listed keep their bytes.  ``info['kernel_used']``: the statistics kernel (the smallest over the products)."""
+    Products not listed keep their bytes.  ``info['kernel_used']``: the statistics kernel (the smallest over the products).
+    ``periodic`` (``True``, ``dict(t_freq=4.0)`` or ``dict(t_pow=...)``, optionally with ``chan_frac``): the periodicity test as
+    well -- one product: one frbch_rfi_cleanf_host call; several: pass one takes every product's spectral peaks and hands its
+    periodic flags to frbch_rfi_mask as ``prior``.  The result gains ``pflag`` [nblk][nchan], ``pchan`` [nchan] (ORed over the
+    products, and into ``chan_flag``), ``peaks`` [nifs][nblk][nchan] and ``t_pow``; ``info['peaks_kernel_used']``."""
     lib = lib or _lib.load()
     x = _rows3(rows, hdr).copy()
     par = rfi_params(params)
@@ -312,6 +421,28 @@ def clean(rows, hdr: dict, params=None, zap=None, device: int = 0, lib=None, inf
     err = C.create_string_buffer(512)
     repl = np.zeros((nifs, nchan), np.float64)
     kernels = []
+    if periodic:
+        fpar = rfi_fparams(periodic, par)
+        if len(prods) == 1:
+            nblk = lib.frbch_rfi_nblk(x.shape[0], par.block_rows)
+            mask, cf, bf = np.zeros((nblk, nchan), np.uint8), np.zeros(nchan, np.uint8), np.zeros(nblk, np.uint8)
+            pflag, pchan, peaks = np.zeros((nblk, nchan), np.uint8), np.zeros(nchan, np.uint8), np.zeros((nifs, nblk, nchan), PEAK)
+            used = (C.c_uint32 * 2)(0, 0)
+            desc = fil_desc(hdr, prods[0])
+            _check(lib.frbch_rfi_cleanf_host(C.byref(desc), x.ctypes.data, x.shape[0], C.byref(par), C.byref(fpar),
+                                             None if z is None else z.ctypes.data, device, mask.ctypes.data,
+                                             repl[prods[0]].ctypes.data, cf.ctypes.data, bf.ctypes.data, pflag.ctypes.data,
+                                             pchan.ctypes.data, peaks[prods[0]].ctypes.data, used, err, len(err)), err)
+            ks, kp = [used[0]], [used[1]]
+            cf, bf = cf.astype(bool), bf.astype(bool)
+            extra = dict(pflag=pflag, pchan=pchan.astype(bool), peaks=peaks, t_pow=fpar.t_pow)
+        else:
+            stats, pflags, extra, ks, kp = _periodic_pass(lib, x, hdr, par, fpar, prods, device)
+            mask, cf, bf = _clean_from_stats(lib, x, hdr, par, stats, prods, z, repl, device, priors=pflags)
+            cf = cf | extra["pchan"]
+        if info is not None:
+            info["kernel_used"], info["peaks_kernel_used"] = min(ks), min(kp)
+        return x.reshape(np.shape(rows)), dict(mask=mask, repl=repl, chan_flag=cf, blk_flag=bf, **extra)
     if len(prods) == 1:
         nblk = lib.frbch_rfi_nblk(x.shape[0], par.block_rows)
         if nblk <= 0:
@@ -337,13 +468,18 @@ def clean(rows, hdr: dict, params=None, zap=None, device: int = 0, lib=None, inf
 
 
 def rfifind_fil(filterbankfile, block_rows=1024, t_cell=5.0, t_chan=5.0, chan_frac=0.3, block_frac=0.3, flag_file=None,
-                write_clean=False, device=0, lib=None, info: dict | None = None, resident=False):
+                write_clean=False, device=0, lib=None, info: dict | None = None, resident=False, periodic=False, t_freq=4.0):
     """Flag a filterbank: ``<base>_rfi.npz`` (mask, chan_flag, blk_flag, repl, the block statistics [nifs][nblk][nchan][2] and
     the parameters), ``<base>.flag`` (the wholly flagged channels, ``write_flag_file``) and, with ``write_clean``,
     ``<base>_clean.fil`` -- the header bytes unchanged, every product cleaned in the same cells.  ``flag_file``: channels
     to flag whatever the statistics say.  ``resident``: all products in one library call on rows uploaded once and downloaded
-    once (frbch_rfi_cleanp_host) -- the same files and values.  Returns (list of files written, the result dict of ``clean``)."""
+    once (frbch_rfi_cleanp_host) -- the same files and values.  ``periodic``: the periodicity test as well (``clean``), at
+    ``t_freq`` Gaussian sigma over the bins of a cell; the ``.npz`` then gains ``peaks``, ``pflag``, ``pchan`` and ``t_pow``, and the
+    channels it flags wholly are in the ``.flag`` file.  Returns (list of files written, the result dict of ``clean``)."""
     lib = lib or _lib.load()
+    if periodic and resident:
+        raise InputError("the periodic test is not built for resident rows: run rfifind with --periodic and without --resident "
+                         "(the resident path is unchanged without --periodic)")
     fil = sigproc.read_fil(filterbankfile)
     hdr = fil.header
     rows = _rows_of(fil)
@@ -352,7 +488,19 @@ def rfifind_fil(filterbankfile, block_rows=1024, t_cell=5.0, t_chan=5.0, chan_fr
     zap = read_flag_file(flag_file, hdr["nchans"]) if flag_file else None
     par = rfi_params(params)
     nifs, nchan = hdr.get("nifs", 1), hdr["nchans"]
-    if resident:
+    extra = {}
+    if periodic:
+        fpar = rfi_fparams(periodic if isinstance(periodic, dict) else dict(t_freq=float(t_freq)), par)
+        cleaned = _rows3(rows, hdr).copy()
+        stats, pflags, extra, ks, kp = _periodic_pass(lib, cleaned, hdr, par, fpar, list(range(nifs)), device)
+        repl = np.zeros((nifs, nchan), np.float64)
+        mask, cf, bf = _clean_from_stats(lib, cleaned, hdr, par, stats, list(range(nifs)), _zap_array(zap, nchan), repl, device,
+                                         priors=pflags)
+        res = dict(mask=mask, repl=repl, chan_flag=cf | extra["pchan"], blk_flag=bf, **extra)
+        stats = np.stack(stats)
+        if info is not None:
+            info["kernel_used"], info["peaks_kernel_used"] = min(ks), min(kp)
+    elif resident:
         cleaned, res = cleanp(rows, hdr, par, zap=zap, device=device, lib=lib, info=info, want_stats=True)
         cleaned, stats = _rows3(cleaned, hdr), res.pop("stats")
     else:
@@ -370,7 +518,7 @@ def rfifind_fil(filterbankfile, block_rows=1024, t_cell=5.0, t_chan=5.0, chan_fr
             info["kernel_used"] = min(kernels)
     base = filterbankfile.replace(".fil", "")
     np.savez(base + "_rfi.npz", mask=res["mask"], chan_flag=res["chan_flag"], blk_flag=res["blk_flag"], repl=res["repl"], stats=stats,
-             zap=np.zeros(hdr["nchans"], bool) if zap is None else zap, nrows=rows.shape[0], **params)
+             zap=np.zeros(hdr["nchans"], bool) if zap is None else zap, nrows=rows.shape[0], **params, **extra)
     write_flag_file(base + ".flag", res["chan_flag"])
     out = [base + "_rfi.npz", base + ".flag"]
     if write_clean:
@@ -383,8 +531,20 @@ def rfifind_fil(filterbankfile, block_rows=1024, t_cell=5.0, t_chan=5.0, chan_fr
     return out, res
 
 
-def _read_rows(filterbankfile, flag_file, rfi, device, lib, info, detrend_len=1000):
-    """the file; with ``flag_file`` or ``rfi`` its product-0 rows cleaned once (frbch_rfi_clean_host) in a copy"""
+def _periodic_args(periodic, rfi, resident):
+    """``periodic`` of search_fil / candidates_fil: goes with ``rfi``, and not with ``resident``"""
+    if not periodic:
+        return
+    if resident:
+        raise InputError("the periodic test is not built for resident rows: use --periodic without --resident "
+                         "(the resident path is unchanged without --periodic)")
+    if not rfi:
+        raise InputError("the periodic test is part of the flagging: give --rfi (rfi=True) with --periodic")
+
+
+def _read_rows(filterbankfile, flag_file, rfi, device, lib, info, detrend_len=1000, periodic=None):
+    """the file; with ``flag_file`` or ``rfi`` its product-0 rows cleaned once (frbch_rfi_clean_host; with ``periodic``
+    frbch_rfi_cleanf_host) in a copy"""
     fil = sigproc.read_fil(filterbankfile)
     if flag_file is None and not rfi:
         return fil
@@ -392,10 +552,12 @@ def _read_rows(filterbankfile, flag_file, rfi, device, lib, info, detrend_len=10
     zap = read_flag_file(flag_file, hdr["nchans"]) if flag_file is not None else None
     rinfo = {}
     cleaned, res = clean(_rows_of(fil), hdr, rfi if isinstance(rfi, dict) else None, zap=zap, device=device, lib=lib, info=rinfo,
-                         products=[0])
+                         products=[0], **(dict(periodic=periodic) if periodic else {}))
     if info is not None:
         info.update(rfi_kernel_used=rinfo["kernel_used"], rfi_chan_flag=res["chan_flag"], rfi_blk_flag=res["blk_flag"],
                     rfi_mask=res["mask"], rfi_masked_cells=int(res["mask"].sum()))
+        if periodic:
+            info.update(rfi_pflag=res["pflag"], rfi_pchan=res["pchan"], rfi_peaks_kernel_used=rinfo["peaks_kernel_used"])
     block_rows = rfi_params(rfi if isinstance(rfi, dict) else None).block_rows
     if res["blk_flag"].any() and not res["chan_flag"].all() and 2 * block_rows > (detrend_len or 1000):
         import warnings
@@ -500,7 +662,8 @@ def _series_names(filterbankfile, dm1, dm2, dms):
 
 
 def search_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, zerodm=True, clip=5, threshold=5.0, max_width_s=0.0, detrend_len=1000,
-               write_dat=False, widths=None, device=0, lib=None, info: dict | None = None, flag_file=None, rfi=None, resident=False):
+               write_dat=False, widths=None, device=0, lib=None, info: dict | None = None, flag_file=None, rfi=None, resident=False,
+               periodic=None):
     """Dedisperse a filterbank over the DMs of ``prepdata_gpu`` and search every series for single pulses in one library
     call (frbch_dedisperse_search_host: the DM x time plane never leaves the GPU unless ``write_dat`` asks for the .dat /
     .inf files, which are then ``prepdata_gpu``'s).  Writes one ``<name>.singlepulse`` per DM, names as ``prepdata_gpu``.
@@ -508,12 +671,14 @@ def search_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, zerodm=True, clip=5, thre
     rows are flagged and cleaned once (``clean``, frbch_rfi_clean_host) and the cleaned rows searched; with neither, every
     file is what it was without them.  ``resident``: flagging and search in one library call on rows uploaded once
     (frbch_candidates_host) -- the same files and values; ``info`` gains ``row_uploads`` and the stage times.
+    ``periodic`` (with ``rfi``; ``True`` or the dict ``clean`` takes): the periodicity test is part of the flagging.
     Returns (list of .singlepulse files, candidates of all DMs as a structured array)."""
     lib = lib or _lib.load()
+    _periodic_args(periodic, rfi, resident)
     if resident:
         return _search_fil_resident(filterbankfile, dm1, dm2, dmstep, zerodm, clip, threshold, max_width_s, detrend_len, write_dat, widths,
                                     device, lib, info, flag_file, rfi)
-    fil = _read_rows(filterbankfile, flag_file, rfi, device, lib, info, detrend_len)
+    fil = _read_rows(filterbankfile, flag_file, rfi, device, lib, info, detrend_len, periodic)
     return _search(fil, filterbankfile, dm1, dm2, dmstep, zerodm, clip, threshold, max_width_s, detrend_len, write_dat, widths, device,
                    lib, info)
 
@@ -660,7 +825,7 @@ def cand_name(base: str, tstart: float, tcand: float, dm: float, snr: float) -> 
 
 def candidates_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, zerodm=True, clip=5, threshold=5.0, max_width_s=0.0, detrend_len=1000,
                    widths=None, dm_gap=2, min_members=1, max_cands=0, nt=256, nf=0, ndm=256, dm_span=None, device=0, lib=None,
-                   info: dict | None = None, flag_file=None, rfi=None, resident=False):
+                   info: dict | None = None, flag_file=None, rfi=None, resident=False, periodic=None):
     """``search_fil``, then one candidate per pulse: the records are grouped across DMs (``group_candidates``), groups of
     fewer than ``min_members`` records are dropped, the ``max_cands`` strongest kept (0: all), and ONE frbch_cutout_host
     call cuts the two planes of all of them (``cutouts``: several calls only for a list longer than a call takes).  Writes, next to ``search_fil``'s own files (which are unchanged),
@@ -670,13 +835,15 @@ def candidates_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, zerodm=True, clip=5, 
     ``flag_file`` / ``rfi`` as in ``search_fil``: the search AND the planes then see the cleaned rows (cleaned once; they
     travel to the device again for the search and for the cut-outs).  ``resident``: every stage in one library call on rows
     uploaded once (frbch_candidates_host) -- the same files and values; ``info`` gains ``row_uploads`` and the stage times.
+    ``periodic`` as in ``search_fil``.
     Returns (list of .npz files, kept groups as a structured array)."""
     lib = lib or _lib.load()
+    _periodic_args(periodic, rfi, resident)
     if resident:
         return _candidates_fil_resident(filterbankfile, dm1, dm2, dmstep, zerodm, clip, threshold, max_width_s, detrend_len, widths, dm_gap,
                                         min_members, max_cands, nt, nf, ndm, dm_span, device, lib, info, flag_file, rfi)
     sinfo = {}
-    fil = _read_rows(filterbankfile, flag_file, rfi, device, lib, sinfo, detrend_len)
+    fil = _read_rows(filterbankfile, flag_file, rfi, device, lib, sinfo, detrend_len, periodic)
     _files, recs = _search(fil, filterbankfile, dm1, dm2, dmstep, zerodm, clip, threshold, max_width_s, detrend_len, False, widths,
                            device, lib, sinfo)
     hdr = fil.header
@@ -1311,7 +1478,7 @@ def main(argv=None):
     ``... candidates <fil> --dm <dm> [search options] [--dm-gap --min-members --max-cands --nt --nf --ndm]`` /
     ``... rfifind <fil> [--block-rows --t-cell --t-chan --chan-frac --block-frac --flag FILE --write-clean]``
     (``search`` and ``candidates`` take ``--flag FILE`` and ``--rfi``; ``search``, ``candidates`` and ``rfifind`` take ``--resident``:
-    one upload of the rows per command): the stages
+    one upload of the rows per command; ``rfifind --periodic [--t-freq S]`` and ``--rfi --periodic`` add the periodicity test): the stages
     as commands, for the places where base2fil.sh / process_vdif.py launch dspsr and prepdata"""
     import argparse
     ap = argparse.ArgumentParser(prog="frb_baseband_amd.post")
@@ -1348,6 +1515,8 @@ def main(argv=None):
     q.add_argument("--flag", default=None, help="flag file (channels to flag): the rows are cleaned before the search")
     q.add_argument("--rfi", action="store_true", help="flag interference from block statistics and clean the rows first")
     q.add_argument("--resident", action="store_true", help="flag and search in one library call on rows uploaded once")
+    q.add_argument("--periodic", action="store_true", help="with --rfi: also flag cells whose power spectrum has a peak (periodic interference)")
+    q.add_argument("--t-freq", type=float, default=4.0, help="threshold of --periodic, Gaussian sigma over the bins of a cell")
     q.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     k = sub.add_parser("candidates", help="search, group the records across DMs, cut the frequency-time and DM-time planes of every group")
     k.add_argument("fil")
@@ -1368,6 +1537,8 @@ def main(argv=None):
     k.add_argument("--flag", default=None, help="flag file (channels to flag): the rows are cleaned before the search and the cut-outs")
     k.add_argument("--rfi", action="store_true", help="flag interference from block statistics and clean the rows first")
     k.add_argument("--resident", action="store_true", help="flag, search and cut in one library call on rows uploaded once")
+    k.add_argument("--periodic", action="store_true", help="with --rfi: also flag cells whose power spectrum has a peak (periodic interference)")
+    k.add_argument("--t-freq", type=float, default=4.0, help="threshold of --periodic, Gaussian sigma over the bins of a cell")
     k.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     r = sub.add_parser("rfifind", help="flag interference per (block of rows, channel): <base>_rfi.npz, <base>.flag, optionally <base>_clean.fil")
     r.add_argument("fil")
@@ -1379,11 +1550,14 @@ def main(argv=None):
     r.add_argument("--flag", default=None, help="flag file: channels to flag whatever the statistics say")
     r.add_argument("--write-clean", action="store_true", help="also write <base>_clean.fil")
     r.add_argument("--resident", action="store_true", help="clean all products in one library call on rows uploaded and downloaded once")
+    r.add_argument("--periodic", action="store_true", help="also flag cells whose power spectrum has a peak (periodic interference); block-rows a power of two in 8..4096")
+    r.add_argument("--t-freq", type=float, default=4.0, help="threshold of --periodic, Gaussian sigma over the bins of a cell")
     r.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     a = ap.parse_args(argv)
     if a.cmd == "rfifind":
         files, res = rfifind_fil(a.fil, block_rows=a.block_rows, t_cell=a.t_cell, t_chan=a.t_chan, chan_frac=a.chan_frac,
-                                 block_frac=a.block_frac, flag_file=a.flag, write_clean=a.write_clean, device=a.device, resident=a.resident)
+                                 block_frac=a.block_frac, flag_file=a.flag, write_clean=a.write_clean, device=a.device, resident=a.resident,
+                                 **(dict(periodic=True, t_freq=a.t_freq) if a.periodic else {}))
         for path in files:
             print("wrote", path)
         print("{0} of {1} channels and {2} of {3} blocks flagged wholly, {4} cells masked".format(
@@ -1392,7 +1566,8 @@ def main(argv=None):
         files, groups = candidates_fil(a.fil, a.dm, dm2=a.dm2, dmstep=a.dmstep, zerodm=a.nozerodm, clip=a.clip, threshold=a.threshold,
                                        max_width_s=a.max_width, detrend_len=a.detrend, dm_gap=a.dm_gap, min_members=a.min_members,
                                        max_cands=a.max_cands, nt=a.nt, nf=a.nf, ndm=a.ndm, device=a.device, flag_file=a.flag,
-                                       rfi=a.rfi or None, resident=a.resident)
+                                       rfi=a.rfi or None, resident=a.resident,
+                                       **(dict(periodic=dict(t_freq=a.t_freq)) if a.periodic else {}))
         print("wrote", a.fil.replace(".fil", "") + ".cands.txt")
         for path in files:
             print("wrote", path, "and .png")
@@ -1404,7 +1579,8 @@ def main(argv=None):
     elif a.cmd == "search":
         files, cands = search_fil(a.fil, a.dm, dm2=a.dm2, dmstep=a.dmstep, zerodm=a.nozerodm, clip=a.clip, threshold=a.threshold,
                                   max_width_s=a.max_width, detrend_len=a.detrend, write_dat=a.write_dat, device=a.device,
-                                  flag_file=a.flag, rfi=a.rfi or None, resident=a.resident)
+                                  flag_file=a.flag, rfi=a.rfi or None, resident=a.resident,
+                                  **(dict(periodic=dict(t_freq=a.t_freq)) if a.periodic else {}))
         for path in files:
             print("wrote", path)
         print("{0} candidates above {1} sigma".format(cands.size, a.threshold))

@@ -217,7 +217,7 @@ long frbch_sigproc_header(frbch_handle* h, uint8_t* dst, size_t cap);
  *      complete on the host's side before the call, and the rows are complete once frbch_reset, frbch_get_rescale or
  *      frbch_close of every handle of the call has returned, or after a device-wide synchronisation;
  *  (e) the frbch_*_device entry points behind and in front of the filterbank (dedisperse, fold, foldp, spsearch, cutout,
- *      rfi_stats / rfi_apply / rfi_clean, cornerturn) are host-synchronous: they take no stream, run on one of their own, and
+ *      rfi_stats / rfi_peaks / rfi_apply / rfi_clean / rfi_cleanf, cornerturn) are host-synchronous: they take no stream, run on one of their own, and
  *      their outputs are complete on return.  A caller that produced d_rows asynchronously (frbch_scan_device on a stream)
  *      synchronises that stream first.
  * tests/test_stream_order.py (adversary schedules of the emulator build) and tests/test_gpu_stream_order.py hold (a) - (e). */
@@ -563,6 +563,73 @@ int frbch_rfi_cleanp_device(const frbch_fil_desc* fil, void* d_rows, uint64_t nr
 int frbch_rfi_cleanp_host(const frbch_fil_desc* fil, void* rows, uint64_t nrows, const frbch_rfi_params* par,
                           const uint8_t* zap, int device, uint8_t* mask, double* repl, uint8_t* chan_flag, uint8_t* blk_flag,
                           void* stats, uint32_t* kernel_used, char* err, size_t err_cap);
+
+/* ---- interference: the periodicity test (the spectral peak of every block and channel) -----------
+ * A weak repeating signal (radar, mains harmonics, a switching supply) can stay below the cell test of frbch_rfi_mask on
+ * mean and std and still appear in every dedispersed series.  frbch_rfi_peaks_* take the power spectrum of every (block,
+ * channel) cell on the device and return its largest bin; frbch_rfi_periodic decides on the host; frbch_rfi_cleanf_* are
+ * frbch_rfi_clean_* with that decision handed to frbch_rfi_mask as `prior`.  tests/rfi_periodic_oracle.py restates all of it
+ * in numpy and every result is reproducible to the bit.
+ *
+ * Blocks and the untested cells.  The blocks are those of frbch_rfi_nblk; the transform length is n = block_rows, which the
+ * periodic test requires to be a power of two in 8 .. 4096 (anything else: FRBCH_E_ARG).  Block b has n_b rows.  A cell is
+ * NOT TESTED and gets the peak {0, 0} when 2 n_b < n, when its mean S / n_b is not finite, or when
+ * var = max(0, Q / n_b - mean * mean) is not finite or 0: S, Q, mean and var exactly as in step 1 of frbch_rfi_mask.
+ * Channel pairing.  Channels are transformed in pairs (c0, c1) = (2m, 2m + 1): one complex transform of length n carries two
+ * real channels.  For j < n_b: z[j] = ((float)((double)x[r0 + j][c0] - mean_c0), (float)((double)x[r0 + j][c1] - mean_c1));
+ * for j >= n_b: z[j] = (0, 0).  A component is 0 throughout for a channel that is not tested and for the missing partner
+ * of an odd last channel, so that a bad channel never reaches its partner.
+ * The transform Z = DFT_n(z): radix 2, decimation in time, float32, every operation rounded on its own (no fused
+ * multiply-add).  The input is taken in bit-reversed order; stages s = 1 .. log2 n with half = 2^(s-1); the butterfly on
+ * (u, v), v = u's partner `half` further on, j = u's index mod half, uses w = W[j n / 2^s]:
+ *     t = (wr vr - wi vi, wr vi + wi vr) (the two products first),  u' = u + t,  v' = u - t.
+ * W[k] = ((float)cos(a), (float)(-sin(a))) with a = 2.0 pi k / n evaluated in double ON THE HOST: the kernels take the table
+ * from the host and compute no sines.  The operation graph is fixed, the schedule is free: a radix-4, -8 or -16 register
+ * pass is these radix-2 butterflies with these table entries; twiddles merged into products and the three-multiplier forms
+ * give other bits and are not used.
+ * The per-channel peak.  For k = 1 .. n/2 - 1, A = Z[k], B = Z[n - k], all float32:
+ *     N_c0[k] = (Ar + Br)^2 + (Ai - Bi)^2,    N_c1[k] = (Ai + Bi)^2 + (Br - Ar)^2
+ * (four times the power of the channel's own transform).  The peak {num, k} of a cell starts at {0, 0} and walks k ascending,
+ * replacing when N[k] > num: the largest value and the lowest k that attains it; a NaN never replaces.
+ * peaks: frbch_rfi_peak [nblk][nchan].
+ * The decision, frbch_rfi_periodic: host only, double, every operation rounded on its own.  A tested cell has
+ * p = (double)num / ((4.0 n_b) var), a cell that is not tested p = 0 (for noise p is exponentially distributed with mean 1).
+ * A cell is flagged when p > t_pow; a channel is flagged wholly (pchan) when its flagged cells number more than
+ * chan_frac nblk; pflag[b][c] = cell flag | pchan[c].  `power` ([nblk][nchan] doubles, may be NULL) receives p.
+ * FRBCH_E_ARG: what frbch_rfi_mask refuses, a block_rows that is not a power of two in 8 .. 4096, a wrong `size` of
+ * frbch_rfi_fparams, a t_pow that is not positive or is infinite, a chan_frac outside 0 .. 1. */
+typedef struct frbch_rfi_peak { float num; uint32_t k; } frbch_rfi_peak;
+typedef struct frbch_rfi_fparams {
+  uint32_t size, reserved;             /* = sizeof(frbch_rfi_fparams)                                                     */
+  double t_pow, chan_frac;             /* threshold on p; fraction of a channel's blocks, 0..1                            */
+} frbch_rfi_fparams;
+/* Which kernel frbch_rfi_peaks_device takes (host only, nothing runs): 1 = the fast kernel (8- / 16-bit rows of whole 64-byte
+ * channel tiles, d_rows and the row pitch 16-byte aligned, n = 256 .. 2048: the columns of a piece of the row staged in the
+ * LDS, register passes of radix 8 and 16), 0 = the generic one (a workgroup per block and channel pair; the only one for
+ * float rows), < 0 = refused; only the ADDRESS of d_rows is examined.  Both kernels give the same bits. */
+int frbch_rfi_peaks_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_rfi_params* par);
+/* d_stats: what frbch_rfi_stats_device wrote for the same arguments; d_peaks: [nblk][nchan] frbch_rfi_peak. */
+int frbch_rfi_peaks_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_rfi_params* par,
+                           int device, const void* d_stats, void* d_peaks, uint32_t* kernel_used, char* err, size_t err_cap);
+/* One upload of the rows, then the statistics and the peaks; `stats` may be NULL; kernel_used[2] (may be NULL): the
+ * statistics kernel, the peaks kernel. */
+int frbch_rfi_peaks_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_rfi_params* par, int device,
+                         void* stats, void* peaks, uint32_t* kernel_used, char* err, size_t err_cap);
+int frbch_rfi_periodic(const frbch_fil_desc* fil, const void* stats, const void* peaks, uint32_t nblk, uint64_t nrows,
+                       const frbch_rfi_params* par, const frbch_rfi_fparams* fpar, uint8_t* pflag, uint8_t* pchan,
+                       double* power, char* err, size_t err_cap);
+/* frbch_rfi_clean_* with the periodicity test: statistics, peaks, frbch_rfi_periodic, frbch_rfi_mask with `prior` = pflag,
+ * apply.  pflag [nblk][nchan] and pchan [nchan] are HOST arrays, `peaks` a host array that may be NULL; the returned
+ * chan_flag is that of the mask ORed with pchan (what a flag file lists).  kernel_used[2] (may be NULL) as in
+ * frbch_rfi_peaks_host.  The _host form uploads the rows once and downloads them once. */
+int frbch_rfi_cleanf_device(const frbch_fil_desc* fil, void* d_rows, uint64_t nrows, const frbch_rfi_params* par,
+                            const frbch_rfi_fparams* fpar, const uint8_t* zap, int device, uint8_t* mask, double* repl,
+                            uint8_t* chan_flag, uint8_t* blk_flag, uint8_t* pflag, uint8_t* pchan, void* peaks,
+                            uint32_t* kernel_used, char* err, size_t err_cap);
+int frbch_rfi_cleanf_host(const frbch_fil_desc* fil, void* rows, uint64_t nrows, const frbch_rfi_params* par,
+                          const frbch_rfi_fparams* fpar, const uint8_t* zap, int device, uint8_t* mask, double* repl,
+                          uint8_t* chan_flag, uint8_t* blk_flag, uint8_t* pflag, uint8_t* pchan, void* peaks,
+                          uint32_t* kernel_used, char* err, size_t err_cap);
 
 /* ---- resident rows: flagging, DM-range search, grouping, selection and cut-outs in one call --------
  * The production call for a DM-range search with candidates: the rows cross to the device ONCE (frbch_candidates_host) or

@@ -26,14 +26,32 @@ nrows, nchan = rc.TIMING_ROWS, rc.TIMING_NCHAN
 data = rng.integers(100, 156, size=(nrows, nchan), dtype=np.uint8)
 data[:, rc.TIMING_DEAD_CHANNEL] = rc.TIMING_DEAD_CODE         # one dead channel: every clean flags it, uploads the mask and applies
 d_rows = DeviceBuffer.from_numpy(data)
-out = rc.timing_run(lib, d_rows.ptr.value)
 
 
 def to_ms(v):
     return [round(1e3 * x, 3) for x in v] if isinstance(v, list) else round(1e3 * v, 3)
 
 
-out = {(k[:-2] + "_ms" if k.endswith("_s") else k): (to_ms(v) if k.endswith("_s") else v) for k, v in out.items()}
+def in_ms(out):
+    return {(k[:-2] + "_ms" if k.endswith("_s") else k): (to_ms(v) if k.endswith("_s") else v) for k, v in out.items()}
+
+
+if "--periodic" in sys.argv[1:]:
+    # the periodicity test on the same rows (blocks of 1024): the median of five frbch_rfi_peaks_device calls with the fast kernel,
+    # with the generic one (the rows one byte further on), of frbch_rfi_stats_device, and of frbch_rfi_cleanf_device against
+    # frbch_rfi_clean_device; `tools/rfi_profile.py --periodic [profiles/rfi_periodic_timing.json]`
+    from tests import rfi_periodic_cases as pc               # noqa: E402
+    out = in_ms(pc.timing_run(lib, d_rows.ptr.value))
+    out["rows_bytes"] = int(data.nbytes)
+    print(json.dumps(out))
+    paths = [a for a in sys.argv[1:] if a != "--periodic"]
+    if paths:
+        with open(paths[0], "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+    raise SystemExit(0)
+
+out = in_ms(rc.timing_run(lib, d_rows.ptr.value))
 
 desc = post.fil_desc(rc.TIMING_HDR)
 par = rc.params()
