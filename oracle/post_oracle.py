@@ -56,8 +56,33 @@ def clip_flags(S, clip_sigma):
     return flag
 
 
+def clip_replacement(colsum_good, ngood, integer=True):
+    """what a clipped time sample reads as: the channel means of the `ngood` unclipped ones, whose sums per channel are
+    `colsum_good` (integer rows stay integer)"""
+    return np.floor(colsum_good / ngood + 0.5) if integer else colsum_good / ngood
+
+
+def sum_delayed(x, S, dl, nout, zerodm):
+    """out[i][t] = sum_c x[t + dl[i][c]][c] (minus the mean over channels of S at the same rows with zerodm), t < nout, as
+    float32; x: [nrows][nchan] after the clip, S: its row sums, dl: one array of per-channel delays in samples per DM"""
+    nchan = x.shape[1]
+    out = np.empty((len(dl), nout), dtype=np.float32)
+    for i, d in enumerate(dl):
+        a = np.zeros(nout)
+        b = np.zeros(nout)
+        for c in range(nchan):                       # ascending channel order, as the kernel
+            a += x[d[c]: d[c] + nout, c]
+            if zerodm:
+                b += S[d[c]: d[c] + nout]
+        out[i] = (a - b / nchan if zerodm else a).astype(np.float32)
+    return out
+
+
 def dedisperse(x, *, fch1, foff, tsamp, dms, zerodm=True, clip=5.0, integer=True):
-    """x: [nrows][nchan] samples (one product).  -> (float32 [ndm][nout], number of clipped rows)"""
+    """x: [nrows][nchan] samples (one product).  -> (float32 [ndm][nout], number of clipped rows)
+    The clip is a function of the row sums alone (clip_flags), the replacement of the column sums of the unclipped rows
+    (clip_replacement), the series of the rows after the clip (sum_delayed): a caller that knows the row sums of a long file
+    can apply the three to a window of it."""
     x = np.asarray(x, dtype=np.float64)
     nrows, nchan = x.shape
     S = seq_sum(x, 1)
@@ -69,24 +94,14 @@ def dedisperse(x, *, fch1, foff, tsamp, dms, zerodm=True, clip=5.0, integer=True
             xg = np.where(flag[:, None], 0.0, x)
             part = [seq_sum(xg[r0:r0 + CHUNK_ROWS], 0) for r0 in range(0, nrows, CHUNK_ROWS)]
             m = seq_sum(np.stack(part), 0)
-            ngood = float(nrows - nclip)
-            repl = np.floor(m / ngood + 0.5) if integer else m / ngood
+            repl = clip_replacement(m, float(nrows - nclip), integer)
             x = np.where(flag[:, None], repl[None, :], x)
             S = seq_sum(x, 1)
         else:
             nclip = 0
     dl = [delays_samples(fch1, foff, nchan, tsamp, dm) for dm in dms]
     nout = nrows - max(int(d.max()) for d in dl)
-    out = np.empty((len(dms), nout), dtype=np.float32)
-    for i, d in enumerate(dl):
-        a = np.zeros(nout)
-        b = np.zeros(nout)
-        for c in range(nchan):                       # ascending channel order, as the kernel
-            a += x[d[c]: d[c] + nout, c]
-            if zerodm:
-                b += S[d[c]: d[c] + nout]
-        out[i] = (a - b / nchan if zerodm else a).astype(np.float32)
-    return out, nclip
+    return sum_delayed(x, S, dl, nout, zerodm), nclip
 
 
 def fold(x, *, fch1, foff, tsamp, tstart_mjd, f0, f1, pepoch_mjd, dm, nbin, subint_s, apply_delays):

@@ -386,3 +386,111 @@ def test_config4_full_length_parseval_and_determinism(hip_lib):
         assert c.process_device(d_raw.ptr.value, nfr, 8032, 32, 0, nblocks, out.ptr.value, out.nbytes) == rows
         fused = out.to_numpy(np.uint8)
     assert np.array_equal(outs[0], outs[1]) and np.array_equal(outs[0], fused)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the channeliser's writers past 2^32 bytes of their output (tests/test_gpu_beyond_4gib.py holds the stages behind the
+# filterbank to the same marks).  The single-IF path is held to the fp64 oracle by the parity suite; here it is the
+# ADDRESSING reference: the same values must appear at the same rows of a buffer that is longer than 4 GiB.
+# ------------------------------------------------------------------------------------------------------------------
+def device_rows(address, first_row, nrows, row_bytes, dtype=np.uint8):
+    from tests.big_rows import DeviceMem
+    return DeviceMem.get(address + first_row * row_bytes, nrows * row_bytes).view(dtype)
+
+
+@pytest.mark.parametrize("flags", [0, 1 << 27], ids=["two_pass", "buffered"])
+def test_scan_of_eight_ifs_writes_rows_past_4_gib(hip_lib, ten_seconds, flags):
+    """the benchmark's step (BASELINE configs[2]: 8 IFs x 1024 channels, IQUV, 8 bit) at 0.43 of its length: the first 66 blocks
+    of the ten-second stream, the other IFs payload-rolled copies, through ONE frbch_scan_device call into 135 168 rows x 32 KiB
+    = 4.43 GB.  Every IF's columns in block 0, in the blocks that hold rows 65 536 (2^31 bytes) and 131 072 (2^32 bytes) and in
+    the last block are bit-identical to that IF channelised alone into 554 MB.  Automatic form: frbch_k2_priv writes the
+    codes; flags = 1 << 27: frbch_quantise_fast does."""
+    nif, nblocks = 8, 66
+    chans = [ch.Channeliser(pu.lib_cfg(hip_lib, -32.0 if i % 2 else 32.0, 1024, 10.0, pol=5, flags=flags), hip_lib) for i in range(nif)]
+    info = chans[0].info
+    rpb, rb = info.rows_per_block, info.row_bytes
+    rows = nblocks * rpb
+    assert (rows, rb, nif * rb) == (135168, 4096, 32768) and rows * nif * rb == (1 << 32) + (128 << 20)
+    nfr = -(-nblocks * info.block_payload_bytes // 8000)
+    fr = ten_seconds.reshape(-1, 8032)[:nfr]
+    bufs = []
+    for i in range(nif):
+        other = fr.copy()
+        if i:
+            other[:, 32:] = np.roll(fr[:, 32:], 700 * i, axis=0)
+        bufs.append(DeviceBuffer.from_numpy(other.reshape(-1)))
+    out = DeviceBuffer(rows * nif * rb)
+    assert multi_if.scan_device(chans, [b.ptr.value for b in bufs], nfr, 8032, 32, 0, nblocks, out.ptr.value, rows) == rows
+    blocks = sorted({0, 65536 // rpb, 131072 // rpb, nblocks - 1})
+    assert blocks == [0, 32, 64, 65]
+    wide = {b: device_rows(out.ptr.value, b * rpb, rpb, nif * rb).reshape(rpb, 4, nif * 1024) for b in blocks}
+    single = DeviceBuffer(rows * rb)
+    for i, c in enumerate(chans):
+        c.reset()
+        r1 = c.process_device(bufs[i].ptr.value, nfr, 8032, 32, 0, nblocks, single.ptr.value, single.nbytes)
+        r1 += c.flush_device(single.ptr.value + r1 * rb, single.nbytes - r1 * rb)
+        assert r1 == rows
+        for b in blocks:
+            alone = device_rows(single.ptr.value, b * rpb, rpb, rb).reshape(rpb, 4, 1024)
+            assert np.array_equal(wide[b][:, :, i * 1024:(i + 1) * 1024], alone), "IF %d, block %d" % (i, b)
+    assert not np.array_equal(wide[0][:, :, :1024], wide[64][:, :, :1024]) and not np.array_equal(wide[32][:, :, :1024], wide[64][:, :, :1024])
+    for b in [out, single] + bufs:
+        b.free()
+    for c in chans:
+        c.close()
+
+
+BLOCK_RANGES = ((126, 4), (148, 4))              # row 262 144 (2^32 bytes of 16 KiB rows) is the first row of block 128; the last four
+
+
+def test_float_rows_of_one_if_past_4_gib(hip_lib, ten_seconds):
+    """one IF, IQUV, float rows (`-b-32`), all 152 blocks through frbch_process_device: 311 296 rows x 16 KiB = 5.1 GB.  With the
+    measured offset / scale frozen, four blocks from block 126 and the last four, each set into a small buffer through
+    payload_byte_offset, are bit-identical to the same rows of the long buffer."""
+    d_raw = DeviceBuffer.from_numpy(ten_seconds)
+    nfr = ten_seconds.size // 8032
+    with ch.Channeliser(pu.lib_cfg(hip_lib, 32.0, 1024, 10.0, pol=5, nbit=-32), hip_lib) as c:
+        info = c.info
+        rpb, rb, nblocks = info.rows_per_block, info.row_bytes, 152
+        rows = nblocks * rpb
+        assert rb == 4 * 1024 * 4 and 128 * rpb * rb == 1 << 32 and rows * rb > (1 << 32) + (700 << 20)
+        out = DeviceBuffer(rows * rb)
+        r1 = c.process_device(d_raw.ptr.value, nfr, 8032, 32, 0, nblocks, out.ptr.value, out.nbytes)
+        r1 += c.flush_device(out.ptr.value + r1 * rb, out.nbytes - r1 * rb)
+        assert r1 == rows
+        off, sc = c.get_rescale()
+        small = DeviceBuffer(4 * rpb * rb)
+        for b0, nb in BLOCK_RANGES:
+            c.reset()
+            c.set_rescale(off, sc)
+            assert c.process_device(d_raw.ptr.value, nfr, 8032, 32, b0 * info.block_payload_bytes, nb, small.ptr.value, small.nbytes) == nb * rpb
+            part = small.to_numpy(np.uint8)
+            assert np.array_equal(part, device_rows(out.ptr.value, b0 * rpb, nb * rpb, rb)), "blocks %d .. %d" % (b0, b0 + nb)
+            assert np.isfinite(part.view(np.float32)).all() and part.view(np.float32).std() > 0
+        first = device_rows(out.ptr.value, 0, 4 * rpb, rb)
+        assert not np.array_equal(first, part)
+        for b in (out, small, d_raw):
+            b.free()
+
+
+def test_power_of_four_products_past_4_gib(hip_lib, ten_seconds):
+    """frbch_power_device, pol = 4, 152 blocks: 5.1 GB of float32.  It keeps no state between blocks: the same two block ranges
+    through calls of their own give the same bits."""
+    d_raw = DeviceBuffer.from_numpy(ten_seconds)
+    nfr = ten_seconds.size // 8032
+    with ch.Channeliser(pu.lib_cfg(hip_lib, 32.0, 1024, 10.0, pol=4), hip_lib) as c:
+        info = c.info
+        rpb, nblocks = info.rows_per_block, 152
+        rb = 4 * 1024 * 4
+        assert 128 * rpb * rb == 1 << 32
+        pw = DeviceBuffer(nblocks * rpb * rb)
+        c.power_device(d_raw.ptr.value, nfr, 8032, 32, 0, nblocks, pw.ptr.value, pw.nbytes)
+        small = DeviceBuffer(4 * rpb * rb)
+        for b0, nb in BLOCK_RANGES:
+            c.power_device(d_raw.ptr.value, nfr, 8032, 32, b0 * info.block_payload_bytes, nb, small.ptr.value, small.nbytes)
+            part = small.to_numpy(np.uint8)
+            assert np.array_equal(part, device_rows(pw.ptr.value, b0 * rpb, nb * rpb, rb)), "blocks %d .. %d" % (b0, b0 + nb)
+            assert np.isfinite(part.view(np.float32)).all() and part.view(np.float32).std() > 0
+        assert not np.array_equal(device_rows(pw.ptr.value, 0, 4 * rpb, rb), part)
+        for b in (pw, small, d_raw):
+            b.free()
