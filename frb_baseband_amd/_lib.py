@@ -86,6 +86,21 @@ class FrbchSpGroup(C.Structure):
                 ("reserved", C.c_uint32), ("sample_lo", C.c_uint64), ("sample_hi", C.c_uint64)]
 
 
+class FrbchPsParams(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("nfft", C.c_uint32), ("nharm", C.c_uint32), ("wblock", C.c_uint32),
+                ("sigma", C.c_double), ("flo_hz", C.c_double), ("tsamp_s", C.c_double)]
+
+
+class FrbchPsCand(C.Structure):
+    _fields_ = [("dm_index", C.c_uint32), ("h", C.c_uint32), ("k", C.c_uint32), ("power", C.c_float),
+                ("sigma", C.c_double), ("freq_hz", C.c_double)]
+
+
+class FrbchPsGroup(C.Structure):
+    _fields_ = [("best", FrbchPsCand), ("nmember", C.c_uint32), ("dm_index_lo", C.c_uint32), ("dm_index_hi", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class FrbchCutoutParams(C.Structure):
     _fields_ = [("size", C.c_uint32), ("nt", C.c_uint32), ("nf", C.c_uint32), ("ndm", C.c_uint32)]
 
@@ -191,6 +206,19 @@ SYMBOLS = {
     "frbch_dedisperse_search_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_double,
                                                C.POINTER(FrbchSpParams), C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64), _P,
                                                C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_psearch_nfft": (C.c_long, [C.c_uint64, C.POINTER(FrbchPsParams)]),
+    "frbch_psearch_thresholds": (C.c_int, [C.c_double, _P]),
+    "frbch_psearch_kernel": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.POINTER(FrbchPsParams), C.POINTER(C.c_uint32)]),
+    "frbch_psearch_device": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.POINTER(FrbchPsParams), C.c_int, _P, C.c_uint64,
+                                       C.POINTER(C.c_uint64), _P, C.c_char_p, C.c_size_t]),
+    "frbch_psearch_host": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.POINTER(FrbchPsParams), C.c_int, _P, C.c_uint64,
+                                     C.POINTER(C.c_uint64), _P, C.c_char_p, C.c_size_t]),
+    "frbch_dedisperse_psearch_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_double,
+                                                C.POINTER(FrbchPsParams), C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64), _P,
+                                                C.c_uint64, C.POINTER(C.c_uint64), _P, C.c_char_p, C.c_size_t]),
+    "frbch_psearch_sift": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_double, _P, C.c_uint64, C.POINTER(C.c_uint64), C.c_char_p,
+                                     C.c_size_t]),
+    "frbch_ps_group_cands": (C.c_int, [_P, C.c_uint64, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
     "frbch_sp_group_cands": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint32, _P, C.c_uint64, C.c_uint32, _P, C.c_uint64,
                                        C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
     "frbch_cutout_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchCutoutParams), _P, C.c_uint32, C.c_int,

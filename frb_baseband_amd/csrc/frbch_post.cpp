@@ -876,6 +876,466 @@ extern "C" int frbch_dedisperse_search_host(const frbch_fil_desc* fil, const voi
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// periodicity search of the dedispersed series
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr uint32_t kPsRawCap = 1u << 20;     // raw peaks the device list holds (16 MiB); more: FRBCH_E_CAPACITY, never a cut list
+constexpr int kPsMinLog = 12, kPsMaxLog = 22;
+constexpr double kPsSigmaMax = 30.0;
+
+struct PsPlan {
+  uint32_t n = 0, wblock = 0, nblk = 0, kmin = 0, nfold = 0;
+  int log2n = 0;
+  double tsamp = 0.0;
+};
+
+bool ps_fold_ok(uint32_t h) { return h == 1 || h == 2 || h == 4 || h == 8 || h == 16; }
+
+int ps_check(const frbch_ps_params* par, uint64_t nout, double tsamp_default, PsPlan* pl, const PostErr& e) {
+  if (!par || par->size != sizeof(frbch_ps_params)) return e.fail(FRBCH_E_ARG, "frbch_ps_params: wrong size");
+  if (!(par->sigma > 0.0) || !(par->sigma <= kPsSigmaMax)) return e.fail(FRBCH_E_ARG, "sigma must lie in (0, 30]");
+  if (par->nharm != 0 && !ps_fold_ok(par->nharm)) return e.fail(FRBCH_E_ARG, "nharm must be 1, 2, 4, 8 or 16 (0 = 16)");
+  const uint32_t B = par->wblock ? par->wblock : 128;
+  if (B < 32 || B > 1024 || (B & (B - 1))) return e.fail(FRBCH_E_ARG, "wblock must be a power of two in 32..1024 (0 = 128)");
+  if (!(par->flo_hz >= 0.0) || !(par->flo_hz < 1.0e300)) return e.fail(FRBCH_E_ARG, "flo_hz must be finite and not negative");
+  const double tsamp = par->tsamp_s != 0.0 ? par->tsamp_s : tsamp_default;
+  if (!(tsamp > 0.0) || !(tsamp < 1.0e300)) return e.fail(FRBCH_E_ARG, "tsamp_s must be positive");
+  uint64_t n = par->nfft;
+  if (!n) {
+    n = 1;
+    while (n * 2 <= nout && n < (1ull << kPsMaxLog)) n *= 2;
+  }
+  if ((n & (n - 1)) || n < (1ull << kPsMinLog) || n > (1ull << kPsMaxLog) || n > nout)
+    return e.fail(FRBCH_E_ARG, "the transform length must be a power of two in 2^12..2^22 and at most nout");
+  pl->n = (uint32_t)n;
+  pl->log2n = 0;
+  while ((1ull << pl->log2n) < n) ++pl->log2n;
+  pl->wblock = B;
+  const uint32_t nb = pl->n / 2 - 1, rest = nb % B;
+  pl->nblk = nb / B + (rest != 0 && rest >= B / 2 ? 1u : 0u);
+  const double flo = par->flo_hz != 0.0 ? par->flo_hz : 0.5;
+  const double kf = ceil(flo * (double)pl->n * tsamp);
+  pl->kmin = kf < 1.0 ? 1u : kf < (double)(pl->n / 2) ? (uint32_t)kf : pl->n / 2;      // n / 2: nothing is searched
+  const uint32_t nharm = par->nharm ? par->nharm : 16;
+  pl->nfold = 0;
+  while ((1u << pl->nfold) <= nharm) ++pl->nfold;
+  pl->tsamp = tsamp;
+  return FRBCH_OK;
+}
+
+// how the fast form cuts the log2 n stages into LDS-resident passes: one up to 2^13, two up to 2^18 (9 stages a pass with 16
+// columns in a tile of 2^13 values), three above
+int ps_passes(int L, int r[3]) {
+  r[0] = r[1] = r[2] = 0;
+  if (L <= 13) { r[0] = L; return 1; }
+  if (L <= 18) { r[0] = (L + 1) / 2; r[1] = L - r[0]; return 2; }
+  r[0] = (L + 2) / 3;
+  r[1] = (L - r[0] + 1) / 2;
+  r[2] = L - r[0] - r[1];
+  return 3;
+}
+
+// the one decision behind frbch_psearch_device's launches and frbch_psearch_kernel's answer; the emulator build has no fast form
+bool ps_fast(const float* d_series) {
+#ifndef FRBCH_NO_FAST
+  return ((uintptr_t)d_series % 16) == 0;
+#else
+  (void)d_series;
+  return false;
+#endif
+}
+
+// W[k] = ((float)cos(a), (float)(-sin(a))), a = 2.0 pi k / n, k < n / 2.  A million sines take the host longer than the device
+// takes for the transforms, so the table of the last length asked for is kept (at most 16 MiB).
+std::shared_ptr<const std::vector<float>> ps_table(uint32_t n) {
+  static std::mutex m;
+  static std::shared_ptr<const std::vector<float>> kept;
+  std::lock_guard<std::mutex> lk(m);
+  if (kept && kept->size() == (size_t)n) return kept;
+  auto tw = std::make_shared<std::vector<float>>((size_t)n);
+  for (uint32_t k = 0; k < n / 2; ++k) {
+    const double a = 2.0 * M_PI * (double)k / (double)n;
+    (*tw)[2 * (size_t)k] = (float)cos(a);
+    (*tw)[2 * (size_t)k + 1] = (float)(-sin(a));
+  }
+  kept = tw;
+  return kept;
+}
+
+// Q(h, x) = exp(-x) sum_{i<h} x^i / i!
+double ps_q(uint32_t h, double x) {
+  double term = 1.0, sum = 1.0;
+  for (uint32_t i = 1; i < h; ++i) { term = term * x / (double)i; sum = sum + term; }
+  return exp(-x) * sum;
+}
+
+// log Q(h, x) without overflow: below 1 the sum as it stands, from 1 on with its largest term x^(h-1) / (h-1)! taken out
+double ps_logq(uint32_t h, double x) {
+  if (x < 1.0) {
+    double s = 1.0;
+    for (uint32_t i = h - 1; i >= 1; --i) s = s * x / (double)i + 1.0;
+    return -x + log(s);
+  }
+  double r = 1.0, lf = 0.0;
+  for (uint32_t i = 1; i < h; ++i) r = r * (double)i / x + 1.0;          // 1 + (h-1)/x (1 + (h-2)/x (... (1 + 1/x)))
+  for (uint32_t i = 2; i < h; ++i) lf = lf + log((double)i);
+  return -x + ((double)(h - 1) * log(x) - lf + log(r));
+}
+
+double ps_logtail(double s) {
+  if (s < 30.0) return log(0.5 * erfc(s / sqrt(2.0)));
+  const double s2 = s * s;
+  return -0.5 * s2 - log(s) - 0.5 * log(2.0 * M_PI) + log1p(-1.0 / s2 + 3.0 / (s2 * s2));
+}
+
+double ps_sigma(uint32_t h, float H) {
+  double x = (double)H;
+  if (!(x <= (double)std::numeric_limits<float>::max())) x = (double)std::numeric_limits<float>::max();
+  const double lq = ps_logq(h, x);
+  if (!(lq < 0.0)) return 0.0;
+  double lo = 0.0, hi = sqrt(-2.0 * lq) + 2.0;
+  for (int it = 0; it < 64; ++it) {
+    const double mid = 0.5 * (lo + hi);
+    if (ps_logtail(mid) > lq) lo = mid; else hi = mid;
+  }
+  return 0.5 * (lo + hi);
+}
+
+// a's fundamental lies below b's: k_a / h_a < k_b / h_b
+bool ps_f_less(const frbch_ps_cand& a, const frbch_ps_cand& b) { return (uint64_t)a.k * b.h < (uint64_t)b.k * a.h; }
+// |k_a h_b - k_b h_a|
+uint64_t ps_f_dist(const frbch_ps_cand& a, const frbch_ps_cand& b) {
+  const uint64_t x = (uint64_t)a.k * b.h, y = (uint64_t)b.k * a.h;
+  return x > y ? x - y : y - x;
+}
+
+// step 8 on the raw records of all series (any order); fills sigma and freq_hz; the survivors in output order
+void ps_sift(std::vector<frbch_ps_cand>& raw, uint32_t n, double tsamp, std::vector<frbch_ps_cand>* out) {
+  for (frbch_ps_cand& c : raw) {
+    c.sigma = ps_sigma(c.h, c.power);
+    c.freq_hz = (double)c.k / ((double)c.h * ((double)n * tsamp));
+  }
+  std::sort(raw.begin(), raw.end(), [](const frbch_ps_cand& a, const frbch_ps_cand& b) {
+    if (a.dm_index != b.dm_index) return a.dm_index < b.dm_index;
+    if (ps_f_less(a, b)) return true;
+    if (ps_f_less(b, a)) return false;
+    return a.h != b.h ? a.h < b.h : a.k < b.k;
+  });
+  for (size_t i0 = 0; i0 < raw.size();) {
+    size_t i1 = i0;
+    while (i1 < raw.size() && raw[i1].dm_index == raw[i0].dm_index) ++i1;
+    size_t first = i0;                                            // raw[first ..) may still lie within one bin below raw[i]
+    for (size_t i = i0; i < i1; ++i) {
+      const frbch_ps_cand& a = raw[i];
+      while (ps_f_dist(raw[first], a) > (uint64_t)raw[first].h * a.h) ++first;       // (stops at i at the latest: distance 0)
+      bool dropped = false;
+      for (size_t j = first; j < i1 && !dropped; ++j) {
+        if (j == i) continue;
+        const frbch_ps_cand& b = raw[j];
+        if (ps_f_dist(a, b) > (uint64_t)a.h * b.h) {
+          if (j > i) break;                                       // sorted by f: every later one lies further
+          continue;
+        }
+        dropped = b.sigma > a.sigma || (b.sigma == a.sigma && (b.h < a.h || (b.h == a.h && b.k < a.k)));
+      }
+      if (!dropped) out->push_back(a);
+    }
+    i0 = i1;
+  }
+  std::sort(out->begin(), out->end(), [](const frbch_ps_cand& a, const frbch_ps_cand& b) {
+    return a.dm_index != b.dm_index ? a.dm_index < b.dm_index : a.h != b.h ? a.h < b.h : a.k < b.k;
+  });
+}
+
+int ps_deliver(const std::vector<frbch_ps_cand>& out, frbch_ps_cand* cands, uint64_t cap, uint64_t* ncand, const PostErr& e) {
+  *ncand = out.size();
+  for (uint64_t i = 0; i < std::min<uint64_t>(cap, out.size()); ++i) cands[i] = out[i];
+  if (out.size() > cap) return e.fail(FRBCH_E_CAPACITY, std::to_string(out.size()) + " candidates, room for " + std::to_string(cap));
+  return FRBCH_OK;
+}
+}  // namespace
+
+extern "C" long frbch_psearch_nfft(uint64_t nout, const frbch_ps_params* par) {
+  PsPlan pl;
+  if (ps_check(par, nout, 1.0, &pl, PostErr{nullptr, 0})) return FRBCH_E_ARG;
+  return (long)pl.n;
+}
+
+extern "C" int frbch_psearch_thresholds(double sigma, float* thr) {
+  if (!thr || !(sigma > 0.0) || !(sigma <= kPsSigmaMax)) return FRBCH_E_ARG;
+  const double tail = 0.5 * erfc(sigma / sqrt(2.0));
+  for (int f = 0; f < 5; ++f) {
+    const uint32_t h = 1u << f;
+    double lo = 0.0, hi = 1000.0;                                  // Q(lo) > tail >= Q(hi) throughout
+    for (;;) {
+      const double mid = 0.5 * (lo + hi);
+      if (!(mid > lo) || !(mid < hi)) break;                       // one step of double wide
+      if (ps_q(h, mid) > tail) lo = mid; else hi = mid;
+    }
+    float t = (float)hi;
+    if ((double)t < hi) t = nextafterf(t, std::numeric_limits<float>::infinity());
+    thr[f] = t;
+  }
+  return FRBCH_OK;
+}
+
+extern "C" int frbch_psearch_kernel(const float* d_series, uint32_t ndm, uint64_t nout, const frbch_ps_params* par, uint32_t* npass) {
+  PsPlan pl;
+  if (!d_series || !ndm || ndm > 65535 || ps_check(par, nout, 1.0, &pl, PostErr{nullptr, 0})) return FRBCH_E_ARG;
+  int r[3];
+  const bool fast = ps_fast(d_series);
+  if (npass) *npass = fast ? (uint32_t)ps_passes(pl.log2n, r) : 0u;
+  return fast ? 1 : 0;
+}
+
+extern "C" int frbch_psearch_sift(const frbch_ps_cand* raw, uint64_t nraw, uint32_t n, double tsamp_s, frbch_ps_cand* cands,
+                                  uint64_t cap, uint64_t* ncand, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  if (!ncand || (nraw && !raw) || (cap && !cands)) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((n & (n - 1)) || n < (1u << kPsMinLog) || n > (1u << kPsMaxLog)) return e.fail(FRBCH_E_ARG, "n must be a power of two in 2^12..2^22");
+  if (!(tsamp_s > 0.0) || !(tsamp_s < 1.0e300)) return e.fail(FRBCH_E_ARG, "tsamp_s must be positive");
+  for (uint64_t i = 0; i < nraw; ++i)
+    if (!ps_fold_ok(raw[i].h) || raw[i].k < 1 || raw[i].k >= n / 2)
+      return e.fail(FRBCH_E_ARG, "record " + std::to_string(i) + ": h must be 1, 2, 4, 8 or 16 and k lie in 1 .. n/2 - 1");
+  std::vector<frbch_ps_cand> all(raw, raw + nraw), out;
+  ps_sift(all, n, tsamp_s, &out);
+  return ps_deliver(out, cands, cap, ncand, e);
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+namespace {
+int ps_search_run(const float* d_series, uint32_t ndm, uint64_t nout, const frbch_ps_params* par, double tsamp_default, int device,
+                  frbch_ps_cand* cands, uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  PsPlan pl;
+  int rc = ps_check(par, nout, tsamp_default, &pl, e);
+  if (rc) return rc;
+  if (!d_series || !ncand || (cap && !cands)) return e.fail(FRBCH_E_ARG, "null argument");
+  if (!ndm || ndm > 65535) return e.fail(FRBCH_E_ARG, "ndm must be 1..65535");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  const uint32_t n = pl.n, nh = n / 2;
+  PsParams p;
+  memset(&p, 0, sizeof p);
+  p.series = d_series;
+  p.nout = nout;
+  p.ndm = (int)ndm;
+  p.npair = (int)((ndm + 1) / 2);
+  p.log2n = pl.log2n;
+  p.n = n;
+  p.wblock = pl.wblock; p.nblk = pl.nblk; p.kmin = pl.kmin; p.nfold = pl.nfold;
+  while ((1u << p.logb) < pl.wblock) ++p.logb;
+  frbch_psearch_thresholds(par->sigma, p.thr);
+  p.peak_cap = kPsRawCap;
+  const std::shared_ptr<const std::vector<float>> tw = ps_table(n);
+  PostScope ps;
+  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  const dev_stream_t s = ps.s;
+  float* d_tw = nullptr;
+  const size_t work_bytes = (size_t)p.npair * n * 2 * sizeof(float), pw_bytes = (size_t)ndm * nh * sizeof(float);
+  if (ps.alloc(&d_tw, (size_t)n * sizeof(float)) || ps.alloc(&p.mean, (size_t)ndm * sizeof(double)) ||
+      ps.alloc(&p.live, (size_t)ndm * sizeof(uint32_t)) || ps.alloc(&p.work, work_bytes) || ps.alloc(&p.pw, pw_bytes) ||
+      ps.alloc(&p.peaks, (size_t)kPsRawCap * sizeof(PsPeak)) || ps.alloc(&p.npeak, sizeof(uint32_t)))
+    return e.fail(FRBCH_E_NOMEM, "device memory for the periodicity search: work array " + std::to_string(work_bytes) + " bytes, powers " +
+                                     std::to_string(pw_bytes) + " bytes, table " + std::to_string((size_t)n * sizeof(float)) +
+                                     " bytes, raw peaks " + std::to_string((size_t)kPsRawCap * sizeof(PsPeak)) + " bytes");
+  p.tw = d_tw;
+  POST_DEV(dev_h2d(d_tw, tw->data(), (size_t)n * sizeof(float), s), "upload table");
+  POST_DEV(dev_memset(p.npeak, 0, sizeof(uint32_t), s), "clear peak count");
+  DEV_LAUNCH(frbch_post_ps_mean, ndm, 1, kPsPartials, kPsPartials * sizeof(double), s, p);
+  POST_DEV(dev_check_launch(), "launch mean");
+  int r[3];
+  const bool fast = ps_fast(d_series);
+  const int npass = fast ? ps_passes(pl.log2n, r) : 0;
+#ifndef FRBCH_NO_FAST
+  if (fast) {
+    PsParams q = p;
+    q.rcur = r[0];
+    q.logc = npass == 1 ? 0 : 4;
+    q.s0 = 0;
+    if (launch_lds(fast::frbch_post_ps_fft_first, dim3(1u << (pl.log2n - q.rcur - q.logc), (unsigned)p.npair), dim3(fast::kPsThreads),
+                   fast::ps_lds_bytes(q.rcur + q.logc), s, q) != 0)
+      return e.fail(FRBCH_E_DEVICE, "LDS permission for the first pass");
+    POST_DEV(dev_check_launch(), "launch first pass");
+    for (int i = 1; i < npass; ++i) {
+      q.s0 += q.rcur;
+      q.rcur = r[i];
+      q.logc = 4;
+      if (launch_lds(fast::frbch_post_ps_fft_later, dim3(1u << (pl.log2n - q.rcur - 4), (unsigned)p.npair), dim3(fast::kPsThreads),
+                     fast::ps_lds_bytes(q.rcur + 4), s, q) != 0)
+        return e.fail(FRBCH_E_DEVICE, "LDS permission for a later pass");
+      POST_DEV(dev_check_launch(), "launch later pass");
+    }
+  }
+#endif
+  if (!fast) {
+    DEV_LAUNCH(frbch_post_ps_load, n / 256, p.npair, 256, 0, s, p);
+    POST_DEV(dev_check_launch(), "launch load");
+    for (int st = 1; st <= pl.log2n; ++st) {
+      PsParams q = p;
+      q.stage = st;
+      DEV_LAUNCH(frbch_post_ps_stage, nh / 256, p.npair, 256, 0, s, q);
+    }
+    POST_DEV(dev_check_launch(), "launch stages");
+  }
+  DEV_LAUNCH(frbch_post_ps_power, nh / 256, p.npair, 256, 0, s, p);
+#ifndef FRBCH_NO_FAST
+  if (fast) {
+    const uint32_t per = (uint32_t)fast::kPsNormTile / pl.wblock;
+    hipLaunchKernelGGL(fast::frbch_post_ps_norm_lds, dim3((pl.nblk + per - 1) / per, ndm), dim3(fast::kPsThreads), 0, s, p);
+  }
+#endif
+  if (!fast) DEV_LAUNCH(frbch_post_ps_norm, (pl.nblk + 63) / 64, ndm, 64, 0, s, p);
+  POST_DEV(dev_check_launch(), "launch powers and levels");
+  if (pl.kmin < nh) {
+    DEV_LAUNCH(frbch_post_ps_harm, nh / 256, ndm, 256, 0, s, p);
+    POST_DEV(dev_check_launch(), "launch harmonic sums");
+  }
+  uint32_t nraw = 0;
+  POST_DEV(dev_d2h(&nraw, p.npeak, sizeof nraw, s), "download peak count");
+  POST_DEV(dev_sync(s), "sync");
+  if (nraw > kPsRawCap)
+    return e.fail(FRBCH_E_CAPACITY, "threshold too low: " + std::to_string(nraw) + " raw peaks, the device list holds " +
+                                        std::to_string(kPsRawCap));
+  std::vector<PsPeak> raw(nraw);
+  if (nraw) {
+    POST_DEV(dev_d2h(raw.data(), p.peaks, (size_t)nraw * sizeof(PsPeak), s), "download peaks");
+    POST_DEV(dev_sync(s), "sync");
+  }
+  ps.release();                           // the device is done with; the host goes on with the raw list
+  if (kernel_used) { kernel_used[0] = fast ? 1u : 0u; kernel_used[1] = (uint32_t)npass; }
+  std::vector<frbch_ps_cand> all(nraw), out;
+  for (uint32_t i = 0; i < nraw; ++i) {
+    frbch_ps_cand c;
+    memset(&c, 0, sizeof c);
+    c.dm_index = raw[i].dm; c.h = raw[i].h; c.k = raw[i].k; c.power = raw[i].H;
+    all[i] = c;
+  }
+  ps_sift(all, n, pl.tsamp, &out);
+  return ps_deliver(out, cands, cap, ncand, e);
+}
+}  // namespace
+
+extern "C" int frbch_psearch_device(const float* d_series, uint32_t ndm, uint64_t nout, const frbch_ps_params* par, int device,
+                                    frbch_ps_cand* cands, uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, char* err,
+                                    size_t err_cap) try {
+  return ps_search_run(d_series, ndm, nout, par, 0.0, device, cands, cap, ncand, kernel_used, err, err_cap);
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_psearch_host(const float* series, uint32_t ndm, uint64_t nout, const frbch_ps_params* par, int device,
+                                  frbch_ps_cand* cands, uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, char* err,
+                                  size_t err_cap) {
+  PostErr e{err, err_cap};
+  PsPlan pl;
+  int rc = ps_check(par, nout, 0.0, &pl, e);
+  if (rc) return rc;
+  if (!series || !ndm || ndm > 65535) return e.fail(FRBCH_E_ARG, "null argument, or ndm outside 1..65535");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  float* d_series = hs.in(series, (size_t)ndm * nout * sizeof(float));
+  return hs.run(e, "device memory for the series", "upload series", "download",
+                [&]() { return frbch_psearch_device(d_series, ndm, nout, par, device, cands, cap, ncand, kernel_used, err, err_cap); });
+}
+
+extern "C" int frbch_dedisperse_psearch_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const double* dms,
+                                             uint32_t ndm, uint32_t zerodm, double clip_sigma, const frbch_ps_params* par,
+                                             int device, float* series_out, uint64_t nout, uint64_t* nclipped,
+                                             frbch_ps_cand* cands, uint64_t cap, uint64_t* ncand, uint32_t* kernel_used,
+                                             char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  int rc = post_check_fil(fil, nrows, e);
+  if (rc) return rc;
+  PsPlan pl;
+  if ((rc = ps_check(par, nout, fil->tsamp_s, &pl, e)) != 0) return rc;
+  if (!rows || !ncand || (cap && !cands)) return e.fail(FRBCH_E_ARG, "null argument");
+  if (!ndm || ndm > 65535) return e.fail(FRBCH_E_ARG, "ndm must be 1..65535");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
+  float* d_out = hs.out(series_out, (size_t)ndm * nout * sizeof(float));          // (series_out may be null: no download then)
+  if (hs.failed) return e.fail(FRBCH_E_NOMEM, "device memory for the rows");
+  if (hs.upload() != 0) return e.fail(FRBCH_E_DEVICE, "upload rows");
+  rc = frbch_dedisperse_device(fil, d_rows, nrows, dms, ndm, zerodm, clip_sigma, device, d_out, nout, nclipped, err, err_cap);
+  hs.drop(d_rows);                                                 // the plane stays in HBM; the rows are done with
+  if (!rc && series_out && hs.download() != 0) rc = e.fail(FRBCH_E_DEVICE, "download series");
+  if (!rc) rc = ps_search_run(d_out, ndm, nout, par, fil->tsamp_s, device, cands, cap, ncand, kernel_used, err, err_cap);
+  return rc;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_ps_group_cands(const frbch_ps_cand* cands, uint64_t ncand, uint32_t dm_gap, frbch_ps_group* groups,
+                                    uint64_t cap, uint64_t* ngroup, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  if (!ngroup || (ncand && !cands) || (cap && !groups)) return e.fail(FRBCH_E_ARG, "null argument");
+  if (dm_gap < 1 || dm_gap > 16) return e.fail(FRBCH_E_ARG, "dm_gap must be 1..16");
+  for (uint64_t i = 0; i < ncand; ++i)
+    if (!ps_fold_ok(cands[i].h) || !cands[i].k) return e.fail(FRBCH_E_ARG, "record " + std::to_string(i) + ": h must be 1, 2, 4, 8 or 16 and k positive");
+  *ngroup = 0;
+  if (!ncand) return FRBCH_OK;
+  // sweep in order of the fundamental: record i meets the later ones within 1.5 bins; union-find joins the linked pairs
+  std::vector<uint64_t> order(ncand), parent(ncand);
+  for (uint64_t i = 0; i < ncand; ++i) order[i] = parent[i] = i;
+  std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {
+    if (ps_f_less(cands[a], cands[b])) return true;
+    if (ps_f_less(cands[b], cands[a])) return false;
+    return a < b;
+  });
+  auto find = [&](uint64_t x) {
+    while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; }
+    return x;
+  };
+  for (uint64_t i = 0; i < ncand; ++i) {
+    const frbch_ps_cand& a = cands[order[i]];
+    for (uint64_t j = i + 1; j < ncand; ++j) {
+      const frbch_ps_cand& b = cands[order[j]];
+      if (2 * ps_f_dist(a, b) > 3 * (uint64_t)a.h * b.h) break;
+      const uint32_t ddm = a.dm_index > b.dm_index ? a.dm_index - b.dm_index : b.dm_index - a.dm_index;
+      if (ddm > dm_gap) continue;
+      const uint64_t ra = find(order[i]), rb = find(order[j]);
+      if (ra != rb) parent[std::max(ra, rb)] = std::min(ra, rb);
+    }
+  }
+  auto better = [](const frbch_ps_cand& a, const frbch_ps_cand& b) {     // a represents a group rather than b
+    if (a.sigma != b.sigma) return a.sigma > b.sigma;
+    if (a.h != b.h) return a.h < b.h;
+    if (a.dm_index != b.dm_index) return a.dm_index < b.dm_index;
+    return a.k < b.k;
+  };
+  std::vector<int64_t> slot(ncand, -1);                                  // root -> index in `out`
+  std::vector<frbch_ps_group> out;
+  for (uint64_t i = 0; i < ncand; ++i) {
+    const uint64_t r = find(i);
+    const frbch_ps_cand& c = cands[i];
+    if (slot[r] < 0) {
+      slot[r] = (int64_t)out.size();
+      frbch_ps_group g;
+      memset(&g, 0, sizeof g);
+      g.best = c;
+      g.nmember = 1;
+      g.dm_index_lo = g.dm_index_hi = c.dm_index;
+      out.push_back(g);
+      continue;
+    }
+    frbch_ps_group& g = out[(size_t)slot[r]];
+    if (better(c, g.best)) g.best = c;
+    ++g.nmember;
+    g.dm_index_lo = std::min(g.dm_index_lo, c.dm_index);
+    g.dm_index_hi = std::max(g.dm_index_hi, c.dm_index);
+  }
+  std::stable_sort(out.begin(), out.end(), [](const frbch_ps_group& a, const frbch_ps_group& b) {
+    if (a.best.sigma != b.best.sigma) return a.best.sigma > b.best.sigma;
+    if (ps_f_less(a.best, b.best)) return true;
+    if (ps_f_less(b.best, a.best)) return false;
+    if (a.best.dm_index != b.best.dm_index) return a.best.dm_index < b.best.dm_index;
+    return a.best.h < b.best.h;
+  });
+  *ngroup = out.size();
+  for (uint64_t i = 0; i < std::min<uint64_t>(cap, out.size()); ++i) groups[i] = out[i];
+  if (out.size() > cap) return e.fail(FRBCH_E_CAPACITY, std::to_string(out.size()) + " groups, room for " + std::to_string(cap));
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+// ---------------------------------------------------------------------------------------------------------------------
 // candidates: grouping across DMs (host only) and the two cut-out planes
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {

@@ -823,3 +823,216 @@ KERNEL(frbch_post_rfi_peaks, RfiParams) {
     }
   }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Periodicity search of the dedispersed series (frbch_psearch_*; include/frbch.h states the arithmetic): the mean of every
+// series in a FIXED order, two series per complex transform of n = 2^L points with the butterfly and the bin formula of the
+// periodicity test above (rfi_bfly, rfi_bins), block levels in double in ascending k, harmonic sums in float in ascending j.
+// The kernels below are the generic form: the transform goes stage by stage through the work array in global memory.  The
+// fast form (kernels_post_fast.inc) replaces the load and the stages by LDS-resident passes and shares everything else.
+// ---------------------------------------------------------------------------------------------------------------------
+struct PsPeak { uint32_t dm, h, k; float H; };   // a raw peak of the fold h
+struct PsParams {
+  const float* series;         // [ndm][nout]; only t < n is read
+  uint64_t nout;
+  int ndm, npair, log2n, logb;  // logb: log2 of wblock
+  uint32_t n;                  // 2^log2n
+  const float* tw;             // [n / 2][2] the host's table W[k]
+  double* mean;                // [ndm]
+  uint32_t* live;              // [ndm] 1: the mean is finite
+  float* work;                 // [npair][n][2]
+  float* pw;                   // [ndm][n / 2]: N[k], then p[k] in place
+  uint32_t wblock, nblk;       // B; blocks of the bins 1 .. n/2 - 1 (the last one may be short or long)
+  uint32_t kmin, nfold;        // folds 1, 2, 4, ... 2^(nfold - 1)
+  float thr[5];
+  PsPeak* peaks;
+  uint32_t* npeak;
+  uint32_t peak_cap;
+  int stage;                   // generic: the stage of this launch
+  int s0, rcur, logc;          // fast: stages done before this pass, stages of it, log2 of the columns of a tile
+};
+
+constexpr int kPsPartials = 64;
+constexpr int kPsBatch = 32;                // samples of a partial sum loaded ahead of their additions (the chain of additions is what the rule fixes)
+
+// grid (ndm), 64 threads, smem 64 doubles: partial j adds positions j, j + 64, ... ascending, thread 0 the partials in ascending j
+KERNEL(frbch_post_ps_mean, PsParams) {
+  K_PROLOGUE;
+  (void)by; (void)nthr;
+  double* part = (double*)smem;
+  const float* x = p.series + (size_t)bx * p.nout;
+  PHASE {
+    POST_NO_CONTRACT
+    if (tid < kPsPartials) {
+      double s = 0.0;
+      uint32_t t = (uint32_t)tid;
+      for (; t < p.n; t += (uint32_t)(kPsBatch * kPsPartials)) {   // kPsBatch loads in flight, added in order (n is a multiple of 4096)
+        float v[kPsBatch];
+        for (int u = 0; u < kPsBatch; ++u) v[u] = x[t + (uint32_t)(u * kPsPartials)];
+        for (int u = 0; u < kPsBatch; ++u) s = s + (double)v[u];
+      }
+      part[tid] = s;
+    }
+  }
+  SYNC;
+  PHASE {
+    POST_NO_CONTRACT
+    if (tid == 0) {
+      double s = 0.0;
+      for (int j = 0; j < kPsPartials; ++j) s = s + part[j];
+      const double m = s / (double)p.n;
+      p.mean[bx] = m;
+      p.live[bx] = rfi_finite(m) ? 1u : 0u;
+    }
+  }
+}
+
+// z of sample t of the pair: (series 2 pair, series 2 pair + 1), 0 for a dead or missing one
+DEVFN inline void ps_sample(const PsParams& p, int pair, uint32_t t, float* a, float* b) {
+  POST_NO_CONTRACT
+  const int d0 = 2 * pair, d1 = d0 + 1;
+  *a = 0.f; *b = 0.f;
+  if (p.live[d0]) { const double d = (double)p.series[(size_t)d0 * p.nout + t] - p.mean[d0]; *a = (float)d; }
+  if (d1 < p.ndm && p.live[d1]) { const double d = (double)p.series[(size_t)d1 * p.nout + t] - p.mean[d1]; *b = (float)d; }
+}
+
+// grid (n / 256, npair): work[pair][bitrev(t)] = z[t]
+KERNEL(frbch_post_ps_load, PsParams) {
+  K_PROLOGUE;
+  (void)smem;
+  PHASE {
+    const uint32_t t = (uint32_t)bx * (uint32_t)nthr + (uint32_t)tid;
+    if (t < p.n) {
+      float a, b;
+      ps_sample(p, by, t, &a, &b);
+      float* z = p.work + ((size_t)by * p.n + (size_t)rfi_bitrev((int)t, p.log2n)) * 2;
+      z[0] = a; z[1] = b;
+    }
+  }
+}
+
+// grid (n / 512, npair): stage p.stage, one butterfly a thread
+KERNEL(frbch_post_ps_stage, PsParams) {
+  K_PROLOGUE;
+  (void)smem;
+  PHASE {
+    const uint32_t i = (uint32_t)bx * (uint32_t)nthr + (uint32_t)tid;
+    if (i < p.n / 2) {
+      const int s = p.stage;
+      const uint32_t half = 1u << (s - 1);
+      const uint32_t j = i & (half - 1);
+      const uint32_t u = ((i >> (s - 1)) << s) + j, v = u + half;
+      const uint32_t k = j << (p.log2n - s);
+      float* z = p.work + (size_t)by * p.n * 2;
+      rfi_bfly(z[2 * (size_t)u], z[2 * (size_t)u + 1], z[2 * (size_t)v], z[2 * (size_t)v + 1], p.tw[2 * (size_t)k], p.tw[2 * (size_t)k + 1]);
+    }
+  }
+}
+
+// grid (n / 512, npair): N[k] of both series of the pair; bin 0 holds 0
+KERNEL(frbch_post_ps_power, PsParams) {
+  K_PROLOGUE;
+  (void)smem;
+  PHASE {
+    const uint32_t k = (uint32_t)bx * (uint32_t)nthr + (uint32_t)tid;
+    const uint32_t nh = p.n / 2;
+    if (k < nh) {
+      float n0 = 0.f, n1 = 0.f;
+      if (k) {
+        const float* z = p.work + (size_t)by * p.n * 2;
+        rfi_bins(z[2 * (size_t)k], z[2 * (size_t)k + 1], z[2 * (size_t)(p.n - k)], z[2 * (size_t)(p.n - k) + 1], &n0, &n1);
+      }
+      const int d0 = 2 * by, d1 = d0 + 1;
+      p.pw[(size_t)d0 * nh + k] = p.live[d0] ? n0 : 0.f;
+      if (d1 < p.ndm) p.pw[(size_t)d1 * nh + k] = p.live[d1] ? n1 : 0.f;
+    }
+  }
+}
+
+// grid (ceil(nblk / 64), ndm), a thread per block of bins: the level m = (S - max) / (cnt - 1), then p[k] = N[k] / m in place
+KERNEL(frbch_post_ps_norm, PsParams) {
+  K_PROLOGUE;
+  (void)smem;
+  PHASE {
+    POST_NO_CONTRACT
+    const uint32_t b = (uint32_t)bx * (uint32_t)nthr + (uint32_t)tid;
+    if (b < p.nblk) {
+      const uint32_t nh = p.n / 2;
+      const uint32_t k0 = 1u + b * p.wblock, k1 = b + 1 == p.nblk ? nh : k0 + p.wblock;
+      float* x = p.pw + (size_t)by * nh;
+      double S = 0.0;
+      float mx = 0.f;
+      for (uint32_t k = k0; k < k1; ++k) {
+        const float v = x[k];
+        S = S + (double)v;
+        if (v > mx) mx = v;
+      }
+      const double num = S - (double)mx;
+      const double m = num / (double)(k1 - k0 - 1u);
+      const bool ok = rfi_finite(m) && m > 0.0;
+      for (uint32_t k = k0; k < k1; ++k) {
+        float q = 0.f;
+        if (ok && k >= p.kmin) { const double r = (double)x[k] / m; q = (float)r; }
+        x[k] = q;
+      }
+    }
+  }
+}
+
+// H_h[k]: j ascending, every addition rounded
+DEVFN inline float ps_hsum(const float* x, uint32_t k, uint32_t h) {
+  POST_NO_CONTRACT
+  float acc = 0.f;
+  for (uint32_t j = 1; j <= h; ++j) {
+    const uint32_t i = (uint32_t)(((uint64_t)j * k + h / 2) / h);
+    acc = acc + x[i];
+  }
+  return acc;
+}
+
+DEVFN inline void ps_append(const PsParams& p, int dm, uint32_t h, uint32_t k, float H) {
+  const uint32_t i = ATOMIC_FETCH_ADD_U32(p.npeak, 1u);
+  if (i < p.peak_cap) {
+    PsPeak q;
+    q.dm = (uint32_t)dm; q.h = h; q.k = k; q.H = H;
+    p.peaks[i] = q;
+  }
+}
+
+// The terms of all folds at bin k are p at the sixteen fractions m / 16 of k: term j of fold h is p[(j k + h / 2) / h] =
+// p[(m k + 8) / 16] with m = 16 j / h (the same integer; m k < 2^25).  H_h[k] from the terms q[m - 1]: j ascending, every addition
+// rounded.  (Constant trip counts and indices: the terms stay in registers.)
+template <int H> DEVFN inline float ps_hsum_terms(const float (&q)[16]) {
+  POST_NO_CONTRACT
+  float acc = 0.f;
+  for (int j = 1; j <= H; ++j) acc = acc + q[j * (16 / H) - 1];
+  return acc;
+}
+
+// bin k of series dm: every fold's sum (sixteen loads serve all five), threshold and local-maximum test
+DEVFN inline void ps_harm_bin(const PsParams& p, int dm, uint32_t k) {
+  const uint32_t nh = p.n / 2;
+  if (k < p.kmin || k < 1 || k >= nh) return;
+  const float* x = p.pw + (size_t)dm * nh;
+  uint32_t nf = 0;                                                   // folds whose range holds k
+  while (nf < p.nfold && ((uint64_t)p.kmin << nf) <= k) ++nf;
+  const uint32_t skip = (16u >> (nf - 1)) - 1u;                      // fold 2^(nf-1) needs the fractions m with m & skip == 0
+  float q[16];
+  for (int m = 1; m <= 16; ++m) q[m - 1] = ((uint32_t)m & skip) == 0u ? x[((uint32_t)m * k + 8u) >> 4] : 0.f;
+  const float H[5] = {ps_hsum_terms<1>(q), ps_hsum_terms<2>(q), ps_hsum_terms<4>(q), ps_hsum_terms<8>(q), ps_hsum_terms<16>(q)};
+  for (int f = 0; f < 5; ++f) {
+    if ((uint32_t)f >= nf || !(H[f] >= p.thr[f])) continue;
+    const uint32_t h = 1u << f;
+    const uint64_t first = (uint64_t)h * p.kmin;
+    if (k > first && !(H[f] > ps_hsum(x, k - 1, h))) continue;
+    if (k + 1 < nh && !(H[f] >= ps_hsum(x, k + 1, h))) continue;
+    ps_append(p, dm, h, k, H[f]);
+  }
+}
+
+// grid (n / 512, ndm), a thread per bin
+KERNEL(frbch_post_ps_harm, PsParams) {
+  K_PROLOGUE;
+  (void)smem;
+  PHASE { ps_harm_bin(p, by, (uint32_t)bx * (uint32_t)nthr + (uint32_t)tid); }
+}

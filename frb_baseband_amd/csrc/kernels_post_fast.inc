@@ -678,4 +678,163 @@ __global__ void __launch_bounds__(kPkThreads) frbch_post_rfi_peaks_fast(RfiParam
     }
   }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Periodicity search: the transform of n = 2^L points, L = 12 .. 22, in one, two or three LDS-resident passes (HIP only; the
+// stage-by-stage kernels of kernels_post.inc stay the emulable form and the fallback; both call rfi_bfly with the same table
+// entries, so they differ in schedule only).  A pass owns R consecutive stages of the radix-2 graph and a tile of 2^R points
+// times C columns (at most 8192 complex values, 68 KB with the padding: two workgroups share a CU):
+//   first pass   stages 1 .. R on runs of 2^R consecutive points of the bit-reversed order.  Run r gathers the samples
+//                t = m' 2^(L-R) + bitrev(r): a workgroup takes the C = 16 runs whose bitrev(r) are consecutive, so that every
+//                global read is 16 consecutive floats of a series (one 64-byte piece), and stores 16 whole runs.  The mean
+//                goes off in double on the way in.  With one pass (L <= 13) the tile is the transform: C = 1, reads contiguous.
+//   later passes stages s0 + 1 .. s0 + R on the sets i = hi 2^(s0+R) + m 2^s0 + lo: a workgroup takes 16 consecutive lo, so
+//                that every global access is 16 consecutive complex values (128 bytes), and works in place.
+// Inside a pass the stages run as register passes of radix 8 or 4 (RR = 3 or 2 stages on 2^RR values a thread holds), as in
+// the 256 .. 2048-point kernel above; LDS index i sits at i + i / 16.  Twiddles come from the table in global memory (the
+// later passes need a different entry for every column: they do not fit the LDS beside the tile, and the L2 holds them).
+constexpr int kPsThreads = 256;
+constexpr int kPsTileLog = 13;                      // a tile holds at most 2^13 complex values
+__device__ __forceinline__ int ps_pad(int i) { return i + (i >> 4); }
+constexpr size_t ps_lds_bytes(int log_points) { return (size_t)((1 << log_points) + (1 << (log_points - 4))) * 8; }
+
+// stages s0 + q0 + 1 .. s0 + q0 + RR of a tile whose point (m, c) sits at ps_pad(m C + c); a thread holds the 2^RR values
+// m = mlo + (x << q0) + (mhi << (q0 + RR)).  The low s0 bits of a point's index are lo0 + c (s0 = 0: there are none, the
+// columns are runs of their own).
+template <int RR>
+__device__ __forceinline__ void ps_subpass(float2* buf, const float2* __restrict__ tw, int tid, int logc, int R, int q0, int s0,
+                                           int L, int lo0) {
+  const int items = (1 << (logc + R)) >> RR;
+  for (int w = tid; w < items; w += kPsThreads) {
+    const int c = w & ((1 << logc) - 1), g = w >> logc;
+    const int mlo = g & ((1 << q0) - 1), mhi = g >> q0;
+    const int m0 = mlo + (mhi << (q0 + RR));
+    const int lo = s0 ? lo0 + c : 0;
+    float vr[1 << RR], vi[1 << RR];
+#pragma unroll
+    for (int x = 0; x < (1 << RR); ++x) {
+      const float2 v = buf[ps_pad(((m0 + (x << q0)) << logc) + c)];
+      vr[x] = v.x; vi[x] = v.y;
+    }
+#pragma unroll
+    for (int q = 1; q <= RR; ++q) {
+      const int hq = 1 << (q - 1);
+      const int sh = L - (s0 + q0 + q);
+#pragma unroll
+      for (int x = 0; x < (1 << RR); ++x) {
+        if (x & hq) continue;
+        const int j = ((mlo + ((x & (hq - 1)) << q0)) << s0) + lo;
+        const float2 t = tw[(size_t)j << sh];
+        rfi_bfly(vr[x], vi[x], vr[x + hq], vi[x + hq], t.x, t.y);
+      }
+    }
+#pragma unroll
+    for (int x = 0; x < (1 << RR); ++x) buf[ps_pad(((m0 + (x << q0)) << logc) + c)] = make_float2(vr[x], vi[x]);
+  }
+}
+
+// the R stages of a pass: register passes of 3, 3, ... stages, the last ones 2 where 3 do not divide R; a barrier behind each
+__device__ __forceinline__ void ps_stages(float2* buf, const float2* tw, int tid, int logc, int R, int s0, int L, int lo0) {
+  int q0 = 0;
+  while (q0 < R) {
+    const int left = R - q0, chunks = (left + 2) / 3, rr = (left + chunks - 1) / chunks;
+    if (rr == 3) ps_subpass<3>(buf, tw, tid, logc, R, q0, s0, L, lo0);
+    else if (rr == 2) ps_subpass<2>(buf, tw, tid, logc, R, q0, s0, L, lo0);
+    else ps_subpass<1>(buf, tw, tid, logc, R, q0, s0, L, lo0);
+    __syncthreads();
+    q0 += rr;
+  }
+}
+
+// grid (2^(L - R - logc), npair), dynamic LDS ps_lds_bytes(R + logc)
+__global__ void __launch_bounds__(kPsThreads) frbch_post_ps_fft_first(PsParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float2* buf = reinterpret_cast<float2*>(smem);
+  const float2* tw = reinterpret_cast<const float2*>(p.tw);
+  const int tid = threadIdx.x, L = p.log2n, R = p.rcur, logc = p.logc;
+  const int pair = (int)blockIdx.y, d0 = 2 * pair, d1 = d0 + 1;
+  const uint32_t c0 = (uint32_t)blockIdx.x << logc;
+  const bool live0 = p.live[d0] != 0u, live1 = d1 < p.ndm && p.live[d1] != 0u;
+  const double mean0 = live0 ? p.mean[d0] : 0.0, mean1 = live1 ? p.mean[d1] : 0.0;
+  const float* x0 = p.series + (size_t)d0 * p.nout;
+  const float* x1 = p.series + (size_t)(live1 ? d1 : d0) * p.nout;
+  const int total = 1 << (R + logc);
+  for (int e = tid; e < total; e += kPsThreads) {
+    const int c = e & ((1 << logc) - 1), mm = e >> logc;
+    const uint32_t t = ((uint32_t)mm << (L - R)) + c0 + (uint32_t)c;
+    float a = 0.f, b = 0.f;
+    if (live0) a = (float)((double)x0[t] - mean0);
+    if (live1) b = (float)((double)x1[t] - mean1);
+    const int m = (int)(__brev((unsigned)mm) >> (32 - R));
+    buf[ps_pad((m << logc) + c)] = make_float2(a, b);
+  }
+  __syncthreads();
+  ps_stages(buf, tw, tid, logc, R, 0, L, 0);
+  float2* out = reinterpret_cast<float2*>(p.work) + (size_t)pair * p.n;
+  for (int e = tid; e < total; e += kPsThreads) {
+    const int m = e & ((1 << R) - 1), c = e >> R;
+    const uint32_t hi = L > R ? __brev(c0 + (uint32_t)c) >> (32 - (L - R)) : 0u;
+    out[((size_t)hi << R) + m] = buf[ps_pad((m << logc) + c)];
+  }
+}
+
+// grid (2^(L - R - 4), npair), dynamic LDS ps_lds_bytes(R + 4): stages s0 + 1 .. s0 + R in place, 16 columns a tile (2^s0 >= 16)
+__global__ void __launch_bounds__(kPsThreads) frbch_post_ps_fft_later(PsParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float2* buf = reinterpret_cast<float2*>(smem);
+  const float2* tw = reinterpret_cast<const float2*>(p.tw);
+  const int tid = threadIdx.x, L = p.log2n, R = p.rcur, s0 = p.s0;
+  const uint32_t tile = blockIdx.x, cols = 1u << (s0 - 4);
+  const int lo0 = (int)((tile & (cols - 1)) << 4);
+  const size_t hi = tile >> (s0 - 4);
+  float2* z = reinterpret_cast<float2*>(p.work) + (size_t)blockIdx.y * p.n + (hi << (s0 + R)) + (size_t)lo0;
+  const int total = 1 << (R + 4);
+  for (int e = tid; e < total; e += kPsThreads) buf[ps_pad(e)] = z[((size_t)(e >> 4) << s0) + (e & 15)];
+  __syncthreads();
+  ps_stages(buf, tw, tid, 4, R, s0, L, lo0);
+  for (int e = tid; e < total; e += kPsThreads) z[((size_t)(e >> 4) << s0) + (e & 15)] = buf[ps_pad(e)];
+}
+
+// The block levels and the normalisation from an LDS tile: a workgroup owns kPsNormTile / B consecutive blocks of one series
+// (the last workgroup also the short or long last block), loads their powers once, coalesced; one thread per block adds its
+// block in ascending k from the LDS (the order the rule fixes; block b's bins sit one word further on than block b - 1's, so
+// that the threads of a wave read 64 banks); then all threads divide and store, coalesced.  grid (ceil(nblk / G), ndm).
+constexpr int kPsNormTile = 8192;
+constexpr int kPsNormLds = kPsNormTile + 1024 + (kPsNormTile + 1024) / 32;      // tile, the longest last block, a word a block
+__global__ void __launch_bounds__(kPsThreads) frbch_post_ps_norm_lds(PsParams p) {
+  __shared__ float tile[kPsNormLds];
+  __shared__ double level[kPsNormTile / 32];
+  const int tid = threadIdx.x, logb = p.logb;
+  const uint32_t B = p.wblock, G = (uint32_t)kPsNormTile >> logb, nh = p.n / 2;
+  const uint32_t b0 = blockIdx.x * G, b1 = b0 + G < p.nblk ? b0 + G : p.nblk;
+  const uint32_t k0 = 1u + b0 * B, k1 = b1 == p.nblk ? nh : 1u + b1 * B;
+  const int cnt = (int)(k1 - k0), nb = (int)(b1 - b0);
+  float* x = p.pw + (size_t)blockIdx.y * nh + k0;
+  for (int i = tid; i < cnt; i += kPsThreads) tile[i + (i >> logb)] = x[i];
+  __syncthreads();
+  if (tid < nb) {
+    POST_NO_CONTRACT
+    const int s0 = tid << logb, s1 = tid + 1 == nb ? cnt : s0 + (int)B;
+    double S = 0.0;
+    float mx = 0.f;
+    for (int i = s0; i < s1; ++i) {
+      const float v = tile[i + (i >> logb)];
+      S = S + (double)v;
+      if (v > mx) mx = v;
+    }
+    const double num = S - (double)mx;
+    const double m = num / (double)(s1 - s0 - 1);
+    level[tid] = rfi_finite(m) && m > 0.0 ? m : 0.0;
+  }
+  __syncthreads();
+  for (int i = tid; i < cnt; i += kPsThreads) {
+    POST_NO_CONTRACT
+    int b = i >> logb;
+    if (b >= nb) b = nb - 1;
+    const double m = level[b];
+    float q = 0.f;
+    if (m > 0.0 && k0 + (uint32_t)i >= p.kmin) { const double r = (double)tile[i + (i >> logb)] / m; q = (float)r; }
+    x[i] = q;
+  }
+}
 }  // namespace fast

@@ -7,6 +7,9 @@ reference's `dspsr -E <par> ... <IFall.fil>` stage) of SIGPROC filterbank files,
   topocentric, unweighted.
 * ``search_fil`` / ``candidates_fil`` search the DM range for single pulses, join the records of a pulse across DMs and cut
   the frequency-time and DM-time planes a FETCH-style classifier reads (the hand-over of base2fil.sh:118-122, 425-432).
+* ``psearch_fil`` searches the same DM range for PERIODIC signals (``periodicity_search``: frbch_psearch_host; one long
+  transform per series, red-noise normalisation, harmonic sums, peaks), joins the records across DMs (``group_periodic``)
+  and can fold the strongest candidates at their own frequency and DM: from a filterbank to a period without an ephemeris.
 * ``fold_fil`` mirrors base2fil.sh:465-493: spin parameters from a psrcat-style .par file, 10-s sub-integrations,
   the filterbank's channels, plus the plot (PNG) of the dedispersed, time- and frequency-scrunched profile that
   ``psrplot -pF ... -j dedisperse,tscrunch,pscrunch,"fscrunch 128"`` draws.  Files with several products (``--pol 4``)
@@ -714,6 +717,126 @@ def _search(fil, filterbankfile, dm1, dm2, dmstep, zerodm, clip, threshold, max_
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# periodicity search
+# ------------------------------------------------------------------------------------------------------------------
+PS_CAND = np.dtype([("dm_index", "<u4"), ("h", "<u4"), ("k", "<u4"), ("power", "<f4"), ("sigma", "<f8"), ("freq_hz", "<f8")])
+PS_GROUP = np.dtype([("best", PS_CAND), ("nmember", "<u4"), ("dm_index_lo", "<u4"), ("dm_index_hi", "<u4"), ("reserved", "<u4")])
+PS_HEADER = "# Period (s)      Freq (Hz)        DM    Sigma  Fold  Members  DMlo  DMhi"
+PS_ROW = "%14.9f %14.7f %9.2f %8.2f %5d %8d %5d %5d"
+
+
+def ps_params(tsamp: float, sigma: float = 6.0, nharm: int = 16, flo: float = 0.5, nfft: int = 0,
+              wblock: int = 128) -> _lib.FrbchPsParams:
+    for name, v in (("nharm", nharm), ("nfft", nfft), ("wblock", wblock)):
+        if not 0 <= int(v) < 1 << 32:
+            raise InputError("%s must be a non-negative 32-bit integer" % name)
+    p = _lib.FrbchPsParams()
+    p.size = C.sizeof(_lib.FrbchPsParams)
+    p.nfft, p.nharm, p.wblock = int(nfft), int(nharm), int(wblock)
+    p.sigma, p.flo_hz, p.tsamp_s = float(sigma), float(flo), float(tsamp)
+    return p
+
+
+def _ps_call(call, cap: int):
+    """run call(cands pointer, cap, ncand, used, err) with room for `cap` records; once more with the reported total"""
+    while True:
+        cands = np.zeros(cap, dtype=PS_CAND)
+        ncand, used = C.c_uint64(0), (C.c_uint32 * 2)(0, 0)
+        err = C.create_string_buffer(512)
+        rc = call(cands.ctypes.data, cap, C.byref(ncand), used, err, len(err))
+        if rc == _lib.E_CAPACITY and ncand.value > cap:
+            cap = ncand.value
+            continue
+        _check(rc, err)
+        return cands[: ncand.value].copy(), (used[0], used[1])
+
+
+def periodicity_search(series, tsamp: float, sigma: float = 6.0, nharm: int = 16, flo: float = 0.5, nfft: int = 0,
+                       wblock: int = 128, device: int = 0, lib=None, info: dict | None = None, cap: int = 4096):
+    """Periodicity search of dedispersed series ([ndm][nout] or [nout] float32) on the GPU (frbch_psearch_host; the
+    arithmetic is stated in include/frbch.h): one transform of ``nfft`` points (0: the largest power of two not above nout)
+    per series, red-noise normalisation in blocks of ``wblock`` bins, harmonic sums of up to ``nharm`` harmonics, peaks above
+    ``sigma`` -> structured array PS_CAND (dm_index, h = harmonics summed, k = bin of the highest of them, power, sigma,
+    freq_hz of the fundamental), sorted by (dm_index, h, k).  ``info['kernel_used']`` receives 1 for the fast form, 0 for the
+    generic one, ``info['passes']`` the LDS passes of the fast transform."""
+    lib = lib or _lib.load()
+    y = np.ascontiguousarray(series, dtype=np.float32)
+    y = y.reshape(1, -1) if y.ndim == 1 else y
+    if y.ndim != 2 or y.size == 0:
+        raise InputError("series must be [ndm][nout] with at least one sample")
+    params = ps_params(tsamp, sigma, nharm, flo, nfft, wblock)
+    out, used = _ps_call(lambda c, n, nc, u, e, ne: lib.frbch_psearch_host(y.ctypes.data, y.shape[0], y.shape[1], C.byref(params),
+                                                                           device, c, n, nc, u, e, ne), cap)
+    if info is not None:
+        info.update(kernel_used=used[0], passes=used[1])
+    return out
+
+
+def group_periodic(cands, dm_gap: int = 2, lib=None) -> np.ndarray:
+    """Join the records of one signal across trial DMs (frbch_ps_group_cands, host only; include/frbch.h states the rule) ->
+    structured array PS_GROUP, the strongest first.  Harmonically related groups are NOT merged."""
+    lib = lib or _lib.load()
+    recs = np.ascontiguousarray(cands, dtype=PS_CAND)
+    out = np.zeros(max(1, recs.size), dtype=PS_GROUP)
+    n = C.c_uint64(0)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_ps_group_cands(recs.ctypes.data, recs.size, int(dm_gap), out.ctypes.data, out.size, C.byref(n), err, len(err)), err)
+    return out[: n.value].copy()
+
+
+def psearch_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, zerodm=True, clip=5, sigma=6.0, nharm=16, flo=0.5, nfft=0, wblock=128,
+                dm_gap=2, max_cands=0, fold_best=0, device=0, lib=None, info: dict | None = None, flag_file=None, rfi=None,
+                periodic=None):
+    """Dedisperse a filterbank over the DMs of ``prepdata_gpu`` and search every series for periodic signals in one library
+    call (frbch_dedisperse_psearch_host: the DM x time plane never leaves the GPU), then join the records across DMs.
+    Writes ``<base>_psearch.txt`` (one line per candidate: period, frequency, DM, sigma, harmonics summed, members and DM span)
+    and ``<base>_psearch.npz`` (the records, the candidates, the DMs).  ``flag_file`` / ``rfi`` / ``periodic`` as
+    ``search_fil``.  ``max_cands`` > 0 keeps the strongest N candidates.  ``fold_best`` = K folds the K strongest candidates
+    with the ephemeris {F0 = the candidate's frequency, F1 = 0, DM = its trial DM, PEPOCH = tstart} through ``fold_fil``'s
+    machinery; their outputs are ``<base>_psearch_cand<i>.ar`` / ``.profile.txt`` / ``.png``.
+    Returns (list of files written, candidates as PS_GROUP)."""
+    lib = lib or _lib.load()
+    _periodic_args(periodic, rfi, False)
+    fil = _read_rows(filterbankfile, flag_file, rfi, device, lib, info, periodic=periodic)
+    hdr = fil.header
+    dms = dm_list(dm1, dm2, dmstep)
+    rows = _rows_of(fil)
+    desc = fil_desc(hdr)
+    dm_arr = np.ascontiguousarray(dms, dtype=np.float64)
+    nout = lib.frbch_dedisperse_nout(C.byref(desc), rows.shape[0], dm_arr.ctypes.data, dm_arr.size)
+    if nout <= 0:
+        raise InputError("the dispersion delay across the band exceeds the length of the filterbank")
+    params = ps_params(hdr["tsamp"], sigma, nharm, flo, nfft, wblock)
+    nclip = C.c_uint64(0)
+    recs, used = _ps_call(lambda c, n, nc, u, e, ne: lib.frbch_dedisperse_psearch_host(
+        C.byref(desc), rows.ctypes.data, rows.shape[0], dm_arr.ctypes.data, dm_arr.size, 1 if zerodm else 0, float(clip),
+        C.byref(params), device, None, nout, C.byref(nclip), c, n, nc, u, e, ne), 4096)
+    groups = group_periodic(recs, dm_gap, lib=lib)
+    if max_cands > 0:
+        groups = groups[:max_cands]
+    n = lib.frbch_psearch_nfft(nout, C.byref(params))
+    if info is not None:
+        info.update(kernel_used=used[0], passes=used[1], nclipped=nclip.value, nout=nout, nfft=n, records=recs)
+    base = filterbankfile.replace(".fil", "")
+    with open(base + "_psearch.txt", "w") as f:
+        f.write(PS_HEADER + "\n")
+        for g in groups:
+            b = g["best"]
+            f.write(PS_ROW % (1.0 / b["freq_hz"], b["freq_hz"], dms[int(b["dm_index"])], b["sigma"], int(b["h"]), int(g["nmember"]),
+                              int(g["dm_index_lo"]), int(g["dm_index_hi"])) + "\n")
+    np.savez(base + "_psearch.npz", records=recs, candidates=groups, dms=dm_arr, nfft=n, tsamp=hdr["tsamp"])
+    files = [base + "_psearch.txt", base + "_psearch.npz"]
+    for i, g in enumerate(groups[: max(0, int(fold_best))]):
+        b = g["best"]
+        par = {"F0": float(b["freq_hz"]), "F1": 0.0, "DM": float(dms[int(b["dm_index"])]), "PEPOCH": float(hdr["tstart"]),
+               "PSR": "cand%d" % i}
+        ar, _profile = _fold_par(fil, filterbankfile, par, 0, 10.0, 128, device, lib, "%s_psearch_cand%d" % (base, i), None, 0.0,
+                                 "coherency")
+        files.append(ar)
+    return files, groups
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # candidates: grouping across DMs and the two planes a classifier reads
 # ------------------------------------------------------------------------------------------------------------------
 SP_GROUP = np.dtype([("best", SP_CAND), ("nmember", "<u4"), ("dm_index_lo", "<u4"), ("dm_index_hi", "<u4"), ("reserved", "<u4"),
@@ -1407,8 +1530,13 @@ def fold_fil(filterbankfile: str, parfile: str, nbin: int = 0, subint_s: float =
     ``stokes`` = an IQUV file) also gives ``<fil>_fullPol.png`` -- pol 0, pol 1, Stokes I phase-frequency, and the
     I / L / V profile with the position angle: the 2x2 plot of base2fil.sh:483-490 -- and I, L, V, PA columns in the text
     profile (off-pulse baseline removed per product; see ``stokes`` on what a rescaled file keeps of the fractions)."""
-    fil = sigproc.read_fil(filterbankfile)
-    par = read_par(parfile)
+    return _fold_par(sigproc.read_fil(filterbankfile), filterbankfile, read_par(parfile), nbin, subint_s, fscrunch_to, device, lib,
+                     out_base, polyco, doppler, products)
+
+
+def _fold_par(fil, filterbankfile, par, nbin, subint_s, fscrunch_to, device, lib, out_base, polyco, doppler, products):
+    """``fold_fil`` on a file already read, with the ephemeris as the dict ``read_par`` gives (``psearch_fil`` builds one from a
+    candidate)"""
     hdr = fil.header
     nprod = hdr.get("nifs", 1)
     timing = "topocentric polynomial F0, F1 about PEPOCH (no barycentric, binary or position terms)"
@@ -1476,6 +1604,7 @@ def main(argv=None):
     """``python -m frb_baseband_amd.post fold <fil> <par> [--polyco FILE] [--doppler X] [--products coherency|stokes] [...]`` / ``... prepdata <fil> --dm <dm> [...]`` /
     ``... search <fil> --dm <dm> [--dm2 --dmstep --threshold --max-width --detrend ...]`` /
     ``... candidates <fil> --dm <dm> [search options] [--dm-gap --min-members --max-cands --nt --nf --ndm]`` /
+    ``... psearch <fil> --dm <dm> [--dm2 --dmstep --sigma --nharm --flo --nfft --wblock --dm-gap --max-cands --fold-best K]`` /
     ``... rfifind <fil> [--block-rows --t-cell --t-chan --chan-frac --block-frac --flag FILE --write-clean]``
     (``search`` and ``candidates`` take ``--flag FILE`` and ``--rfi``; ``search``, ``candidates`` and ``rfifind`` take ``--resident``:
     one upload of the rows per command; ``rfifind --periodic [--t-freq S]`` and ``--rfi --periodic`` add the periodicity test): the stages
@@ -1518,6 +1647,26 @@ def main(argv=None):
     q.add_argument("--periodic", action="store_true", help="with --rfi: also flag cells whose power spectrum has a peak (periodic interference)")
     q.add_argument("--t-freq", type=float, default=4.0, help="threshold of --periodic, Gaussian sigma over the bins of a cell")
     q.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
+    z = sub.add_parser("psearch", help="dedisperse over a DM range and search every series for periodic signals (what realfft + accelsearch -zmax 0 do with the .dat files)")
+    z.add_argument("fil")
+    z.add_argument("--dm", type=float, required=True)
+    z.add_argument("--dm2", type=float, default=0.0)
+    z.add_argument("--dmstep", type=float, default=1.0)
+    z.add_argument("--sigma", type=float, default=6.0, help="Gaussian sigma a harmonic sum must reach")
+    z.add_argument("--nharm", type=int, default=16, help="harmonics summed at most: 1, 2, 4, 8 or 16")
+    z.add_argument("--flo", type=float, default=0.5, help="lowest frequency searched, Hz")
+    z.add_argument("--nfft", type=int, default=0, help="transform length, a power of two in 2^12..2^22 (0: the largest that fits the series)")
+    z.add_argument("--wblock", type=int, default=128, help="bins per normalisation block, a power of two in 32..1024")
+    z.add_argument("--dm-gap", type=int, default=2, help="records at most this many trial DMs apart can join")
+    z.add_argument("--nozerodm", action="store_false", help="do not subtract the zero-DM series")
+    z.add_argument("--clip", type=float, default=5.0)
+    z.add_argument("--flag", default=None, help="flag file (channels to flag): the rows are cleaned before the search")
+    z.add_argument("--rfi", action="store_true", help="flag interference from block statistics and clean the rows first")
+    z.add_argument("--periodic", action="store_true", help="with --rfi: also flag cells whose power spectrum has a peak (periodic interference)")
+    z.add_argument("--t-freq", type=float, default=4.0, help="threshold of --periodic, Gaussian sigma over the bins of a cell")
+    z.add_argument("--max-cands", type=int, default=0, help="keep the strongest N candidates (0: all)")
+    z.add_argument("--fold-best", type=int, default=0, help="fold the K strongest candidates at their frequency and DM")
+    z.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     k = sub.add_parser("candidates", help="search, group the records across DMs, cut the frequency-time and DM-time planes of every group")
     k.add_argument("fil")
     k.add_argument("--dm", type=float, required=True)
@@ -1572,6 +1721,14 @@ def main(argv=None):
         for path in files:
             print("wrote", path, "and .png")
         print("{0} candidates above {1} sigma".format(groups.size, a.threshold))
+    elif a.cmd == "psearch":
+        files, groups = psearch_fil(a.fil, a.dm, dm2=a.dm2, dmstep=a.dmstep, zerodm=a.nozerodm, clip=a.clip, sigma=a.sigma, nharm=a.nharm,
+                                    flo=a.flo, nfft=a.nfft, wblock=a.wblock, dm_gap=a.dm_gap, max_cands=a.max_cands, fold_best=a.fold_best,
+                                    device=a.device, flag_file=a.flag, rfi=a.rfi or None,
+                                    **(dict(periodic=dict(t_freq=a.t_freq)) if a.periodic else {}))
+        for path in files:
+            print("wrote", path)
+        print("{0} periodic candidates above {1} sigma".format(groups.size, a.sigma))
     elif a.cmd == "fold":
         ar, profile = fold_fil(a.fil, a.par, nbin=a.nbin, subint_s=a.subint, fscrunch_to=a.fscrunch, device=a.device,
                                polyco=a.polyco, doppler=a.doppler, products=a.products)

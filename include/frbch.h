@@ -216,7 +216,7 @@ long frbch_sigproc_header(frbch_handle* h, uint8_t* dst, size_t cap);
  *  (d) with stream == NULL the work runs on the handle's own non-blocking stream (a scan: that of ifs[0]); the inputs must be
  *      complete on the host's side before the call, and the rows are complete once frbch_reset, frbch_get_rescale or
  *      frbch_close of every handle of the call has returned, or after a device-wide synchronisation;
- *  (e) the frbch_*_device entry points behind and in front of the filterbank (dedisperse, fold, foldp, spsearch, cutout,
+ *  (e) the frbch_*_device entry points behind and in front of the filterbank (dedisperse, fold, foldp, spsearch, psearch, cutout,
  *      rfi_stats / rfi_peaks / rfi_apply / rfi_clean / rfi_cleanf, cornerturn) are host-synchronous: they take no stream, run on one of their own, and
  *      their outputs are complete on return.  A caller that produced d_rows asynchronously (frbch_scan_device on a stream)
  *      synchronises that stream first.
@@ -413,6 +413,118 @@ int frbch_dedisperse_search_host(const frbch_fil_desc* fil, const void* rows, ui
                                  uint32_t zerodm, double clip_sigma, const frbch_sp_params* params, int device,
                                  float* series_out, uint64_t nout, uint64_t* nclipped, frbch_sp_cand* cands, uint64_t cap,
                                  uint64_t* ncand, uint32_t* kernel_used, char* err, size_t err_cap);
+
+/* ---- periodicity search of the dedispersed series --------------------------------------------------
+ * The other search people run on the .dat files of a DM range (process_vdif.py:78-98,202-229) is `realfft` + `accelsearch`.
+ * frbch_psearch_* do the zero-acceleration part of it on the GPU, on series[dm][t] (float32, t < nout) still in HBM: one long
+ * transform per series, a red-noise normalisation, incoherent harmonic sums of 1, 2, 4, 8 and 16 harmonics, and a list of
+ * peaks.  PRESTO is not in the reference tree: the conventions are this library's [EXT-UNVERIFIED: parity with accelsearch is
+ * not pinned] (tests/psearch_oracle.py restates them in numpy), chosen so that every record is reproducible to the bit.
+ * NOT done: acceleration or jerk search, barycentring, transform lengths that are no power of two, and the merging of
+ * harmonically related candidates (a strong signal appears at f, and at f/2, 2f/3 ... with less significance: the output says
+ * what was found and a reader can see the ladder).
+ *  0. Length.  n = nfft, or with nfft = 0 the largest power of two not above nout (frbch_psearch_nfft); 2^12 <= n <= 2^22 and
+ *     n <= nout.  Only the samples t < n are used.
+ *  1. Mean, per series, in double: 64 partial sums, partial j adds the samples at positions j, j + 64, ... in ascending
+ *     order, the partials are added in ascending j (the rule of frbch_spsearch_* step 1); mean = sum / n;
+ *     z[t] = (float)((double)x[t] - mean).  A series whose mean is not finite is DEAD: all its powers are 0, it yields no record.
+ *  2. Series are transformed in pairs (2m, 2m + 1) as the real and the imaginary part of one complex sequence; the missing
+ *     partner of an odd last series and a dead series are 0 throughout, so that a bad series never reaches its partner.
+ *     Z = DFT_n(z) exactly as in the periodicity test of frbch_rfi_peaks_*: radix 2, decimation in time, float32, no fused
+ *     multiply-add, input in bit-reversed order, the same butterfly, W[k] = ((float)cos(a), (float)(-sin(a))), a = 2.0 pi k / n
+ *     in double ON THE HOST.  The operation graph is fixed, the schedule is free.
+ *  3. Powers, k = 1 .. n/2 - 1, float32: N_c0[k], N_c1[k] of that section (four times the power).  Bins 0 and n/2 are not used.
+ *  4. Normalisation.  The nb = n/2 - 1 bins 1 .. n/2 - 1 are cut into blocks of B = wblock bins (0 = 128; a power of two in
+ *     32 .. 1024), block b = [1 + b B, 1 + (b + 1) B); the rest of r = nb mod B bins is a block of its own when r >= B / 2 and
+ *     belongs to the last whole block otherwise.  (With n and B powers of two r is always B - 1: the last block is always the
+ *     short one.  The rule is stated, and coded, for any nb.)  Level of a block of cnt bins: S = the sum of its powers in double in
+ *     ascending k; max = its largest power (a walk over ascending k that starts at 0 and replaces when N[k] > max: a NaN never
+ *     replaces); m = (S - (double)max) / (double)(cnt - 1): one strong line does not lift its own floor.
+ *     p[k] = (float)((double)N[k] / m); a block whose m is not finite or <= 0 has p = 0 (a constant or dead series: all of them).
+ *     kmin = max(1, ceil(flo_hz * (double)n * tsamp_s)) (left to right; flo_hz 0 = 0.5): p[k] = 0 for k < kmin.  For noise p is
+ *     exponentially distributed with mean 1.
+ *  5. Harmonic sums.  For every fold h in {1, 2, 4, 8, 16} with h <= nharm (1, 2, 4, 8 or 16; 0 = 16):
+ *         H_h[k] = sum over j = 1 .. h of p[(j k + h / 2) / h]          (integer divisions)
+ *     in float, starting from 0, j ascending, every addition rounded; k = h kmin .. n/2 - 1 (a fold whose range is empty is
+ *     skipped).  k counts bins of the HIGHEST summed harmonic; the fundamental is f = k / (h n tsamp).
+ *  6. Thresholds, frbch_psearch_thresholds, on the host: T_h is the power at which the survival function of a sum of h unit
+ *     exponentials, Q(h, x) = exp(-x) sum_{i<h} x^i / i!, equals the one-sided Gaussian tail 0.5 erfc(sigma / sqrt 2)
+ *     (0 < sigma <= 30): bisection in double on [0, 1000] until the interval is one step of double wide, the upper end -- where
+ *     Q <= tail -- rounded UP to float.  A bin passes when H_h[k] >= T_h.
+ *  7. Raw peaks.  A passing bin is a raw peak iff H_h[k] > H_h[k - 1] and H_h[k] >= H_h[k + 1]; a neighbour outside the range
+ *     of step 5 counts as smaller.  The device list holds 2^20 raw peaks {dm_index, h, k, H} per call; more: FRBCH_E_CAPACITY
+ *     with a "threshold too low" message -- never a cut list.
+ *  8. On the host, in double, one pass each.  sigma of a record: with x = (double)H (an infinite H counts as FLT_MAX),
+ *     lq = log Q(h, x) = -x + log(sum_{i<h} x^i / i!) -- for x < 1 the sum by Horner, s = 1, then s = s x / i + 1 for
+ *     i = h - 1 .. 1; from x = 1 on with the largest term taken out so that nothing overflows:
+ *     lq = -x + ((h - 1) log x - sum_{i=2}^{h-1} log i + log r), r = 1, then r = r i / x + 1 for i = 1 .. h - 1 -- sigma is
+ *     the s with lt(s) = lq (0 when lq >= 0), lt(s) = log(0.5 erfc(s / sqrt 2)) for s < 30 and -0.5 s s - log(s) - 0.5 log(2 pi) + log1p(-1 / (s s)
+ *     + 3 / (s s s s)) from there on (finite for every float H): 64 bisection steps on [0, sqrt(-2 lq) + 2], sigma = the middle
+ *     of the last interval.  (It goes through the C library's exp / log / erfc: equal to the last bits only on the same
+ *     library.)  freq_hz = (double)k / ((double)h * ((double)n * tsamp_s)).
+ *     Within one series a record is dropped iff another record (h', k') OF THAT SERIES -- dropped itself or not -- lies within one
+ *     bin of the fundamental, |f - f'| <= 1 / (n tsamp) evaluated exactly as |k h' - k' h| <= h h', and has a larger sigma, or
+ *     the same sigma and (h' < h, or h' = h and k' < k).  The survivors, sorted by (dm_index, h, k), are the records.
+ *  9. frbch_ps_group_cands (host only) joins the records of one signal across trial DMs: a and b are LINKED iff
+ *     |dm_index_a - dm_index_b| <= dm_gap (1..16, the rule of frbch_sp_group_cands) and |f - f'| <= 1.5 / (n tsamp), exactly
+ *     2 |k h' - k' h| <= 3 h h'; groups are the connected components.  `best` has the largest sigma; ties: the smaller h, the
+ *     lower dm_index, the smaller k.  Groups come sorted by best.sigma descending, then f ascending (exactly: k h' < k' h),
+ *     then dm_index, then h. */
+typedef struct frbch_ps_params {
+  uint32_t size, nfft;                 /* = sizeof(frbch_ps_params); n of step 0, 0 = the largest power of two <= nout      */
+  uint32_t nharm, wblock;              /* 1, 2, 4, 8, 16 (0 = 16); B of step 4 (0 = 128)                                  */
+  double sigma;                        /* Gaussian sigma of the thresholds, in (0, 30]                                    */
+  double flo_hz;                       /* lowest frequency searched, >= 0 and finite (0 = 0.5 Hz)                         */
+  double tsamp_s;                      /* sampling time of the series, > 0                                                */
+} frbch_ps_params;
+
+typedef struct frbch_ps_cand {
+  uint32_t dm_index, h, k;             /* row of the series, fold, bin of the highest summed harmonic                     */
+  float power;                         /* H_h[k]                                                                          */
+  double sigma, freq_hz;               /* of step 8                                                                       */
+} frbch_ps_cand;
+
+typedef struct frbch_ps_group {
+  frbch_ps_cand best;
+  uint32_t nmember, dm_index_lo, dm_index_hi, reserved;
+} frbch_ps_group;
+
+/* n of step 0 for these arguments; < 0: refused (FRBCH_E_ARG). */
+long frbch_psearch_nfft(uint64_t nout, const frbch_ps_params* params);
+/* thr[5] receives T_1, T_2, T_4, T_8, T_16 of step 6 (all five, whatever nharm says). */
+int frbch_psearch_thresholds(double sigma, float* thr);
+/* Which form frbch_psearch_device takes for these arguments (host only, nothing runs; only the ADDRESS of d_series is
+ * examined): 1 = the fast form (d_series 16-byte aligned: the transform in LDS-resident passes, *npass of them -- 1 for
+ * n <= 2^13, 2 up to 2^18, 3 above; every global access of a pass is 16 consecutive values), 0 = the generic form (the
+ * transform stage by stage through global memory; *npass = 0), < 0 = refused.  npass may be NULL.  Both give the same records. */
+int frbch_psearch_kernel(const float* d_series, uint32_t ndm, uint64_t nout, const frbch_ps_params* params, uint32_t* npass);
+/* cands[cap] (host memory) receives the first `cap` records in output order, *ncand their total number; more than `cap`:
+ * FRBCH_E_CAPACITY (cap = 0 with cands = NULL counts them).  kernel_used[2] (may be NULL): the form and the passes, as
+ * frbch_psearch_kernel.  d_series holds ndm * nout floats and is never written; the call allocates its scratch -- the work
+ * array [ceil(ndm / 2)][n] complex, p [ndm][n / 2], the table, the raw list -- and frees it before it returns; like the other
+ * post-filterbank _device entry points it works on a stream of its own and returns when its work is done.
+ * FRBCH_E_ARG: n outside 2^12 .. 2^22, no power of two or above nout; nharm not 0, 1, 2, 4, 8, 16; wblock not 0 or a power of
+ * two in 32 .. 1024; sigma outside (0, 30]; flo_hz negative or not finite; tsamp_s not positive; a wrong `size`; ndm above 65535. */
+int frbch_psearch_device(const float* d_series, uint32_t ndm, uint64_t nout, const frbch_ps_params* params, int device,
+                         frbch_ps_cand* cands, uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, char* err, size_t err_cap);
+int frbch_psearch_host(const float* series, uint32_t ndm, uint64_t nout, const frbch_ps_params* params, int device,
+                       frbch_ps_cand* cands, uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, char* err, size_t err_cap);
+/* The production call, the sibling of frbch_dedisperse_search_host: one upload of the rows, frbch_dedisperse_device, then
+ * frbch_psearch_device on the plane where it lies in HBM (params->tsamp_s = 0 takes fil->tsamp_s).  The series is downloaded
+ * only when series_out != NULL ([ndm][nout], the bits of frbch_dedisperse_host). */
+int frbch_dedisperse_psearch_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const double* dms, uint32_t ndm,
+                                  uint32_t zerodm, double clip_sigma, const frbch_ps_params* params, int device,
+                                  float* series_out, uint64_t nout, uint64_t* nclipped, frbch_ps_cand* cands, uint64_t cap,
+                                  uint64_t* ncand, uint32_t* kernel_used, char* err, size_t err_cap);
+/* Step 8 alone (host only), on raw peaks given as records whose dm_index, h, k and power are set: sigma and freq_hz are
+ * filled in, the survivors written in output order.  FRBCH_E_ARG: n no power of two in 2^12 .. 2^22, tsamp_s not positive, an
+ * h other than 1, 2, 4, 8, 16, a k outside 1 .. n/2 - 1. */
+int frbch_psearch_sift(const frbch_ps_cand* raw, uint64_t nraw, uint32_t n, double tsamp_s, frbch_ps_cand* cands, uint64_t cap,
+                       uint64_t* ncand, char* err, size_t err_cap);
+/* Step 9.  More groups than `cap`: FRBCH_E_CAPACITY with *ngroup set (cap = 0 with groups = NULL counts).  FRBCH_E_ARG:
+ * dm_gap outside 1..16, an h other than 1, 2, 4, 8, 16, k = 0. */
+int frbch_ps_group_cands(const frbch_ps_cand* cands, uint64_t ncand, uint32_t dm_gap, frbch_ps_group* groups, uint64_t cap,
+                         uint64_t* ngroup, char* err, size_t err_cap);
 
 /* ---- candidates: grouping across DMs, and the two planes a classifier reads -------------------------
  * The search above returns one record per DM for a pulse that stands out at several trial DMs.  frbch_sp_group_cands
