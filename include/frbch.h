@@ -195,6 +195,22 @@ int frbch_scan_device(frbch_handle* const* ifs, uint32_t nif, const void* const*
                       int flush, void* d_rows, size_t row_pitch_bytes, uint64_t rows_cap, uint64_t* rows_written, void* stream);
 
 /* ---- streaming host path ----------------------------------------------------------------- */
+/* How the stream is cut.  frbch_push takes any byte count (partial frames and partial headers included), frbch_process_device
+ * and frbch_scan_device any run of blocks at any payload_byte_offset, frbch_run_file batches on its own, and
+ * max_blocks_per_launch decides how many blocks a kernel launch sees.  What depends on none of that:
+ *   - the SIGPROC header, the number of rows, and the rows themselves under a GIVEN scale (frbch_set_rescale, or -I0) or a
+ *     FROZEN one (`-c`, once the first interval is measured): bit for bit the rows of one frbch_push of the whole stream;
+ *   - the rows of a measuring run relative to ITS scale: they are the rows of a run that is given the frbch_get_rescale of the
+ *     measuring run beforehand, bit for bit -- whether the interval was buffered, summed inside K2, deferred as a two-pass
+ *     batch or digitised on a scan's second lane, and whichever launch it ended in;
+ *   - frbch_power_device: it has no state, a block's floats do not depend on the blocks beside it in the call;
+ *   - the frame counters of frbch_info.
+ * What can depend on it: a MEASURED offset / scale, in the last bits only -- sums that K2 accumulates per launch are added in an
+ * order that follows the launches (every cut within 8e-7 of the largest offset and 4e-6 of a scale of one push of the whole stream).  With
+ * flags = 1 << 20 (statistics in a separate pass over the buffered rows, chunked by the interval's row count alone) the measured
+ * pair, and with it every row, is bit-identical across cuts; with a rescale per interval (no `-c`) and without that flag, the codes
+ * of a cut differ from those of one push of the whole stream by at most 1 in fewer than 1e-4 of the values.
+ * tests/test_partition.py (emulator build) and tests/test_gpu_partition.py (every register-pass instantiation) hold this. */
 /* push whole or partial frames (byte stream starting at a frame boundary on the first call) */
 int frbch_push(frbch_handle* h, const uint8_t* frames, size_t nbytes);
 /* signal end of input: flushes a pending rescale interval */

@@ -116,6 +116,20 @@ def check_codes(ref_bytes, got_bytes, ocfg):
     return check_code_arrays(fr.data, fg.data, ocfg)
 
 
+def codes_from_hip_floats(power_rows, off, sc, nbit, usb):
+    """oracle rescale + digitiser applied to the HIP path's own floats.
+    power_rows: float32 [t][nif][chan] in OUTPUT channel order; off/sc: [nif][chan] in INPUT channel order."""
+    if usb:
+        off, sc = off[:, ::-1], sc[:, ::-1]
+    x = o.rescale_apply(power_rows.transpose(1, 2, 0), off, sc)           # [nif][chan][t], fp32 arithmetic
+    return o.digitise_values(np.ascontiguousarray(x.transpose(2, 0, 1)), nbit)
+
+
+def unpack_codes(buf, nbit, shape):
+    flat = sigproc.unpack_samples(buf.tobytes(), 32 if nbit == -32 else nbit)
+    return flat.reshape(shape)
+
+
 _ORACLE_CACHE: dict = {}
 
 

@@ -21,6 +21,8 @@ from frb_baseband_amd import multi_if, sigproc, synth
 from oracle import frb_oracle as o
 from tests import parity_util as pu
 from tests.hipmem import GuardedBuffer as DeviceBuffer
+from tests.parity_util import codes_from_hip_floats as _codes_from_hip_floats
+from tests.parity_util import unpack_codes as _unpack_codes
 
 pytestmark = pytest.mark.gpu
 
@@ -28,18 +30,8 @@ pytestmark = pytest.mark.gpu
 # ------------------------------------------------------------------------------------------------------------------
 # A9 + A10: integer work bit-exact on identical floats
 # ------------------------------------------------------------------------------------------------------------------
-def _codes_from_hip_floats(power_rows, off, sc, nbit, usb):
-    """oracle rescale + digitiser applied to the HIP path's own floats.
-    power_rows: float32 [t][nif][chan] in OUTPUT channel order; off/sc: [nif][chan] in INPUT channel order."""
-    if usb:
-        off, sc = off[:, ::-1], sc[:, ::-1]
-    x = o.rescale_apply(power_rows.transpose(1, 2, 0), off, sc)           # [nif][chan][t], fp32 arithmetic
-    return o.digitise_values(np.ascontiguousarray(x.transpose(2, 0, 1)), nbit)
-
-
-def _unpack_codes(buf, nbit, shape):
-    flat = sigproc.unpack_samples(buf.tobytes(), 32 if nbit == -32 else nbit)
-    return flat.reshape(shape)
+# (oracle rescale + digitiser on the HIP path's own floats, and the unpacking of its rows: tests/parity_util.py, shared with
+# tests/test_gpu_partition.py)
 
 
 @pytest.mark.parametrize("bw,nchan,secs,pol,nbit,tscr,flags", [
