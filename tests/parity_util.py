@@ -147,12 +147,20 @@ def hurt_frames(raw, frames, frame_bytes=8032):
 def run_streaming_case(lib, bw, nchan, secs, **kw):
     """oracle .fil vs library .fil through push/flush/pull; returns mismatch count.
     frames = dict(invalid = [...], drop = [...]): frames of the stream flagged invalid / missing (hurt_frames);
-    record = {}: the run has profiling on and the handle's launch record (kernel name -> launches, largest grid) is added to it"""
+    record = {}: the run has profiling on and the handle's launch record (kernel name -> launches, largest grid) is added to it;
+    raw = a ready-made clean stream in place of synth.make_vdif's (frames are applied to it), raw_key = what tells it from other
+    streams in the oracle's cache key (none: the oracle's run is not kept);
+    out = {}: receives got / ref (.fil bytes), ocfg, info (frbch_info behind the run) and rescale (get_rescale, or None)"""
     kw = dict(kw)
     gen = {k: kw.pop(k) for k in ("bits", "payload_bytes", "legacy") if k in kw}    # input-format variants
     frames = kw.pop("frames", None)
     record = kw.pop("record", None)
-    raw = synth.make_vdif(secs + kw.get("start", 0.0), bw_mhz=abs(bw), nchan=nchan, **gen)
+    raw, raw_key, out = kw.pop("raw", None), kw.pop("raw_key", None), kw.pop("out", None)
+    keep = raw is None or raw_key is not None
+    if raw is None:
+        raw = synth.make_vdif(secs + kw.get("start", 0.0), bw_mhz=abs(bw), nchan=nchan, **gen)
+    else:
+        gen["raw"] = raw_key
     if frames:
         raw = hurt_frames(raw, frames, gen.get("payload_bytes", 8000) + (16 if gen.get("legacy") else 32))
         gen["frames"] = tuple(sorted((k, tuple(v)) for k, v in frames.items()))   # (part of the oracle's cache key)
@@ -165,9 +173,10 @@ def run_streaming_case(lib, bw, nchan, secs, **kw):
     else:
         ocfg = oracle_cfg(bw, nchan, secs, **okw)
         ref = o.channelise(raw, ocfg)
-        if len(_ORACLE_CACHE) >= 4:
-            _ORACLE_CACHE.pop(next(iter(_ORACLE_CACHE)))
-        _ORACLE_CACHE[key] = (ref, ocfg)
+        if keep:
+            if len(_ORACLE_CACHE) >= 4:
+                _ORACLE_CACHE.pop(next(iter(_ORACLE_CACHE)))
+            _ORACLE_CACHE[key] = (ref, ocfg)
     cfg = lib_cfg(lib, bw, nchan, secs, **kw)
     with ch.Channeliser(cfg, lib) as c:
         if record is not None:
@@ -176,6 +185,8 @@ def run_streaming_case(lib, bw, nchan, secs, **kw):
         resc = c.get_rescale() if c.get_info().have_rescale else None
         if record is not None:
             record.update(c.get_launch_record())
+        if out is not None:
+            out.update(got=got, ref=ref, ocfg=ocfg, info=c.get_info(), rescale=resc)
     nbad = check_codes(ref, got, ocfg)
     if resc is not None and kw.get("interval", 10.0) > 0 and kw.get("const", 1) and "offset0" in ocfg.result:
         off0, sc0 = ocfg.result["offset0"], ocfg.result["scale0"]
