@@ -101,6 +101,16 @@ class FrbchPsGroup(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class FrbchPaCand(C.Structure):
+    _fields_ = [("dm_index", C.c_uint32), ("acc_index", C.c_uint32), ("h", C.c_uint32), ("k", C.c_uint32), ("power", C.c_float),
+                ("reserved", C.c_uint32), ("sigma", C.c_double), ("freq_hz", C.c_double), ("acc_ms2", C.c_double)]
+
+
+class FrbchPaGroup(C.Structure):
+    _fields_ = [("best", FrbchPaCand), ("nmember", C.c_uint32), ("dm_index_lo", C.c_uint32), ("dm_index_hi", C.c_uint32),
+                ("acc_index_lo", C.c_uint32), ("acc_index_hi", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class FrbchCutoutParams(C.Structure):
     _fields_ = [("size", C.c_uint32), ("nt", C.c_uint32), ("nf", C.c_uint32), ("ndm", C.c_uint32)]
 
@@ -219,6 +229,24 @@ SYMBOLS = {
     "frbch_psearch_sift": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_double, _P, C.c_uint64, C.POINTER(C.c_uint64), C.c_char_p,
                                      C.c_size_t]),
     "frbch_ps_group_cands": (C.c_int, [_P, C.c_uint64, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
+    "frbch_resample_kernel": (C.c_int, [_P, C.c_uint64, _P]),
+    "frbch_resample_device": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_double, _P, C.c_uint32, C.c_int, _P, _P,
+                                        C.c_char_p, C.c_size_t]),
+    "frbch_resample_host": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_double, _P, C.c_uint32, C.c_int, _P, _P,
+                                      C.c_char_p, C.c_size_t]),
+    "frbch_pasearch_plan": (C.c_int, [C.c_uint32, C.c_uint64, C.POINTER(FrbchPsParams), C.c_uint32, C.c_uint32,
+                                      C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                      C.c_char_p, C.c_size_t]),
+    "frbch_pasearch_device": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.POINTER(FrbchPsParams), _P, C.c_uint32, C.c_uint32, C.c_int,
+                                        _P, C.c_uint64, C.POINTER(C.c_uint64), _P, C.c_char_p, C.c_size_t]),
+    "frbch_pasearch_host": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.POINTER(FrbchPsParams), _P, C.c_uint32, C.c_uint32, C.c_int,
+                                      _P, C.c_uint64, C.POINTER(C.c_uint64), _P, C.c_char_p, C.c_size_t]),
+    "frbch_dedisperse_pasearch_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_double,
+                                                 C.POINTER(FrbchPsParams), _P, C.c_uint32, C.c_uint32, C.c_int, _P, C.c_uint64,
+                                                 C.POINTER(C.c_uint64), _P, C.c_uint64, C.POINTER(C.c_uint64), _P, C.c_char_p,
+                                                 C.c_size_t]),
+    "frbch_pa_group_cands": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.POINTER(C.c_uint64), C.c_char_p,
+                                       C.c_size_t]),
     "frbch_sp_group_cands": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint32, _P, C.c_uint64, C.c_uint32, _P, C.c_uint64,
                                        C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
     "frbch_cutout_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchCutoutParams), _P, C.c_uint32, C.c_int,

@@ -1103,49 +1103,11 @@ extern "C" int frbch_psearch_sift(const frbch_ps_cand* raw, uint64_t nraw, uint3
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
 namespace {
-int ps_search_run(const float* d_series, uint32_t ndm, uint64_t nout, const frbch_ps_params* par, double tsamp_default, int device,
-                  frbch_ps_cand* cands, uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, char* err, size_t err_cap) {
-  PostErr e{err, err_cap};
-  PsPlan pl;
-  int rc = ps_check(par, nout, tsamp_default, &pl, e);
-  if (rc) return rc;
-  if (!d_series || !ncand || (cap && !cands)) return e.fail(FRBCH_E_ARG, "null argument");
-  if (!ndm || ndm > 65535) return e.fail(FRBCH_E_ARG, "ndm must be 1..65535");
-  if ((rc = post_check_device(device, e)) != 0) return rc;
-  DeviceGuard dg(device);
-  const uint32_t n = pl.n, nh = n / 2;
-  PsParams p;
-  memset(&p, 0, sizeof p);
-  p.series = d_series;
-  p.nout = nout;
-  p.ndm = (int)ndm;
-  p.npair = (int)((ndm + 1) / 2);
-  p.log2n = pl.log2n;
-  p.n = n;
-  p.wblock = pl.wblock; p.nblk = pl.nblk; p.kmin = pl.kmin; p.nfold = pl.nfold;
-  while ((1u << p.logb) < pl.wblock) ++p.logb;
-  frbch_psearch_thresholds(par->sigma, p.thr);
-  p.peak_cap = kPsRawCap;
-  const std::shared_ptr<const std::vector<float>> tw = ps_table(n);
-  PostScope ps;
-  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
-  const dev_stream_t s = ps.s;
-  float* d_tw = nullptr;
-  const size_t work_bytes = (size_t)p.npair * n * 2 * sizeof(float), pw_bytes = (size_t)ndm * nh * sizeof(float);
-  if (ps.alloc(&d_tw, (size_t)n * sizeof(float)) || ps.alloc(&p.mean, (size_t)ndm * sizeof(double)) ||
-      ps.alloc(&p.live, (size_t)ndm * sizeof(uint32_t)) || ps.alloc(&p.work, work_bytes) || ps.alloc(&p.pw, pw_bytes) ||
-      ps.alloc(&p.peaks, (size_t)kPsRawCap * sizeof(PsPeak)) || ps.alloc(&p.npeak, sizeof(uint32_t)))
-    return e.fail(FRBCH_E_NOMEM, "device memory for the periodicity search: work array " + std::to_string(work_bytes) + " bytes, powers " +
-                                     std::to_string(pw_bytes) + " bytes, table " + std::to_string((size_t)n * sizeof(float)) +
-                                     " bytes, raw peaks " + std::to_string((size_t)kPsRawCap * sizeof(PsPeak)) + " bytes");
-  p.tw = d_tw;
-  POST_DEV(dev_h2d(d_tw, tw->data(), (size_t)n * sizeof(float), s), "upload table");
-  POST_DEV(dev_memset(p.npeak, 0, sizeof(uint32_t), s), "clear peak count");
+// steps 1 to 7 for the p.ndm series p describes, on stream s: the table, the scratch and a cleared p.npeak are in place
+int ps_launches(const PsParams& p, const PsPlan& pl, bool fast, int npass, const int r[3], dev_stream_t s, const PostErr& e) {
+  const uint32_t ndm = (uint32_t)p.ndm, n = p.n, nh = n / 2;
   DEV_LAUNCH(frbch_post_ps_mean, ndm, 1, kPsPartials, kPsPartials * sizeof(double), s, p);
   POST_DEV(dev_check_launch(), "launch mean");
-  int r[3];
-  const bool fast = ps_fast(d_series);
-  const int npass = fast ? ps_passes(pl.log2n, r) : 0;
 #ifndef FRBCH_NO_FAST
   if (fast) {
     PsParams q = p;
@@ -1190,6 +1152,51 @@ int ps_search_run(const float* d_series, uint32_t ndm, uint64_t nout, const frbc
     DEV_LAUNCH(frbch_post_ps_harm, nh / 256, ndm, 256, 0, s, p);
     POST_DEV(dev_check_launch(), "launch harmonic sums");
   }
+  return FRBCH_OK;
+}
+
+int ps_search_run(const float* d_series, uint32_t ndm, uint64_t nout, const frbch_ps_params* par, double tsamp_default, int device,
+                  frbch_ps_cand* cands, uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  PsPlan pl;
+  int rc = ps_check(par, nout, tsamp_default, &pl, e);
+  if (rc) return rc;
+  if (!d_series || !ncand || (cap && !cands)) return e.fail(FRBCH_E_ARG, "null argument");
+  if (!ndm || ndm > 65535) return e.fail(FRBCH_E_ARG, "ndm must be 1..65535");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  const uint32_t n = pl.n, nh = n / 2;
+  PsParams p;
+  memset(&p, 0, sizeof p);
+  p.series = d_series;
+  p.nout = nout;
+  p.ndm = (int)ndm;
+  p.npair = (int)((ndm + 1) / 2);
+  p.log2n = pl.log2n;
+  p.n = n;
+  p.wblock = pl.wblock; p.nblk = pl.nblk; p.kmin = pl.kmin; p.nfold = pl.nfold;
+  while ((1u << p.logb) < pl.wblock) ++p.logb;
+  frbch_psearch_thresholds(par->sigma, p.thr);
+  p.peak_cap = kPsRawCap;
+  const std::shared_ptr<const std::vector<float>> tw = ps_table(n);
+  PostScope ps;
+  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  const dev_stream_t s = ps.s;
+  float* d_tw = nullptr;
+  const size_t work_bytes = (size_t)p.npair * n * 2 * sizeof(float), pw_bytes = (size_t)ndm * nh * sizeof(float);
+  if (ps.alloc(&d_tw, (size_t)n * sizeof(float)) || ps.alloc(&p.mean, (size_t)ndm * sizeof(double)) ||
+      ps.alloc(&p.live, (size_t)ndm * sizeof(uint32_t)) || ps.alloc(&p.work, work_bytes) || ps.alloc(&p.pw, pw_bytes) ||
+      ps.alloc(&p.peaks, (size_t)kPsRawCap * sizeof(PsPeak)) || ps.alloc(&p.npeak, sizeof(uint32_t)))
+    return e.fail(FRBCH_E_NOMEM, "device memory for the periodicity search: work array " + std::to_string(work_bytes) + " bytes, powers " +
+                                     std::to_string(pw_bytes) + " bytes, table " + std::to_string((size_t)n * sizeof(float)) +
+                                     " bytes, raw peaks " + std::to_string((size_t)kPsRawCap * sizeof(PsPeak)) + " bytes");
+  p.tw = d_tw;
+  POST_DEV(dev_h2d(d_tw, tw->data(), (size_t)n * sizeof(float), s), "upload table");
+  POST_DEV(dev_memset(p.npeak, 0, sizeof(uint32_t), s), "clear peak count");
+  int r[3];
+  const bool fast = ps_fast(d_series);
+  const int npass = fast ? ps_passes(pl.log2n, r) : 0;
+  if ((rc = ps_launches(p, pl, fast, npass, r, s, e)) != 0) return rc;
   uint32_t nraw = 0;
   POST_DEV(dev_d2h(&nraw, p.npeak, sizeof nraw, s), "download peak count");
   POST_DEV(dev_sync(s), "sync");
@@ -1327,6 +1334,403 @@ extern "C" int frbch_ps_group_cands(const frbch_ps_cand* cands, uint64_t ncand, 
     if (ps_f_less(a.best, b.best)) return true;
     if (ps_f_less(b.best, a.best)) return false;
     if (a.best.dm_index != b.best.dm_index) return a.best.dm_index < b.best.dm_index;
+    return a.best.h < b.best.h;
+  });
+  *ngroup = out.size();
+  for (uint64_t i = 0; i < std::min<uint64_t>(cap, out.size()); ++i) groups[i] = out[i];
+  if (out.size() > cap) return e.fail(FRBCH_E_CAPACITY, std::to_string(out.size()) + " groups, room for " + std::to_string(cap));
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// acceleration search: the resampler, the periodicity search of every trial's resampled plane, grouping across DMs and trials
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr double kPaLight = 299792458.0;
+constexpr uint32_t kPaMaxAcc = 1024;
+constexpr uint32_t kPaMaxRows = 65534;             // series rows of a batch: the second grid dimension, kept even
+constexpr uint64_t kPaBudget = 2ull << 30;         // bytes of per-row scratch a batch may take when the caller leaves the choice
+
+// q of every trial; FRBCH_E_ARG for a list that is not strictly ascending, a trial that is not finite or out of range
+int pa_check_accs(const double* accs, uint32_t nacc, uint32_t n, double tsamp, std::vector<double>* q, const PostErr& e) {
+  if (!accs) return e.fail(FRBCH_E_ARG, "null argument");
+  if (nacc < 1 || nacc > kPaMaxAcc) return e.fail(FRBCH_E_ARG, "nacc must be 1..1024");
+  q->resize(nacc);
+  for (uint32_t i = 0; i < nacc; ++i) {
+    const double a = accs[i];
+    if (!(fabs(a) <= std::numeric_limits<double>::max())) return e.fail(FRBCH_E_ARG, "trial " + std::to_string(i) + ": the acceleration is not finite");
+    if (i && !(a > accs[i - 1])) return e.fail(FRBCH_E_ARG, "the trial accelerations must be strictly ascending (trial " + std::to_string(i) + ")");
+    const double qi = (a * tsamp) / (2.0 * 299792458.0);
+    if (!(fabs(qi) * (double)n <= 0.5)) {
+      char buf[160];
+      snprintf(buf, sizeof buf, "trial %u: |a| = %.9g m/s^2 is too large for n = %u samples of %.9g s: the largest is %.9g m/s^2", i,
+               fabs(a), n, tsamp, kPaLight / ((double)n * tsamp));
+      return e.fail(FRBCH_E_ARG, buf);
+    }
+    (*q)[i] = qi;
+  }
+  return FRBCH_OK;
+}
+
+int pa_check_n(uint32_t n, uint64_t nout, const PostErr& e) {
+  if ((n & (n - 1)) || n < (1u << kPsMinLog) || n > (1u << kPsMaxLog) || n > nout)
+    return e.fail(FRBCH_E_ARG, "n must be a power of two in 2^12..2^22 and at most nout");
+  return FRBCH_OK;
+}
+
+// the one decision behind the resampler's launch and frbch_resample_kernel's answer; the emulator build has no fast form
+bool res_fast(const float* d_series, uint64_t nout, const float* d_out) {
+#ifndef FRBCH_NO_FAST
+  return ((uintptr_t)d_series % 16) == 0 && ((uintptr_t)d_out % 16) == 0 && nout % 4 == 0;
+#else
+  (void)d_series; (void)nout; (void)d_out;
+  return false;
+#endif
+}
+
+// `trials` trials of rp.rows_per_trial rows each (at most 65535 rows), rp.q and rp.out at the first of them
+int res_launch(bool fast, const ResParams& rp, uint32_t trials, dev_stream_t s, const PostErr& e) {
+  const uint32_t rows = trials * (uint32_t)rp.rows_per_trial;
+#ifndef FRBCH_NO_FAST
+  if (fast) hipLaunchKernelGGL(fast::frbch_post_resample_lds, dim3(rp.n / fast::kResTile, rows), dim3(fast::kResThreads), 0, s, rp);
+#endif
+  if (!fast) DEV_LAUNCH(frbch_post_resample, rp.n / 256, rows, 256, 0, s, rp);
+  POST_DEV(dev_check_launch(), "launch resampler");
+  return FRBCH_OK;
+}
+
+struct PaPlan {
+  uint32_t rpt = 0, tpb = 0, nbatch = 0;           // rows of a trial (even), trials of a batch, batches
+  uint64_t row_bytes = 0, scratch = 0;
+};
+
+void pa_plan(uint32_t ndm, uint32_t n, uint32_t nacc, uint32_t batch_rows, PaPlan* a) {
+  a->rpt = ndm + (ndm & 1u);
+  // a row of a batch: its resampled samples, its half of a pair's work array, its powers, its mean and its live word
+  a->row_bytes = (uint64_t)n * 4 + (uint64_t)n * 4 + (uint64_t)(n / 2) * 4 + sizeof(double) + sizeof(uint32_t);
+  uint64_t rows = batch_rows ? batch_rows : kPaBudget / a->row_bytes;
+  rows = std::min<uint64_t>(rows, kPaMaxRows);
+  a->tpb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nacc, rows / a->rpt));
+  a->nbatch = (nacc + a->tpb - 1) / a->tpb;
+  a->scratch = (uint64_t)a->tpb * a->rpt * a->row_bytes + (uint64_t)n * sizeof(float) + (uint64_t)nacc * sizeof(double) +
+               (uint64_t)kPsRawCap * sizeof(PsPeak) + sizeof(uint32_t);
+}
+
+int pa_check(const frbch_ps_params* par, uint32_t ndm, uint64_t nout, double tsamp_default, const double* accs, uint32_t nacc,
+             PsPlan* pl, std::vector<double>* q, const PostErr& e) {
+  int rc = ps_check(par, nout, tsamp_default, pl, e);
+  if (rc) return rc;
+  if (!ndm || ndm > kPaMaxRows) return e.fail(FRBCH_E_ARG, "ndm must be 1..65534");
+  return pa_check_accs(accs, nacc, pl->n, pl->tsamp, q, e);
+}
+
+int pa_search_run(const float* d_series, uint32_t ndm, uint64_t nout, const frbch_ps_params* par, double tsamp_default,
+                  const double* accs, uint32_t nacc, uint32_t batch_rows, int device, frbch_pa_cand* cands, uint64_t cap,
+                  uint64_t* ncand, uint32_t* kernel_used, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  PsPlan pl;
+  std::vector<double> q;
+  int rc = pa_check(par, ndm, nout, tsamp_default, accs, nacc, &pl, &q, e);
+  if (rc) return rc;
+  if (!d_series || !ncand || (cap && !cands)) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  const uint32_t n = pl.n, nh = n / 2;
+  PaPlan ap;
+  pa_plan(ndm, n, nacc, batch_rows, &ap);
+  const uint32_t rows_max = ap.tpb * ap.rpt;
+  PsParams p;
+  memset(&p, 0, sizeof p);
+  p.nout = n;                                      // the resampled plane: rows of n samples
+  p.log2n = pl.log2n;
+  p.n = n;
+  p.wblock = pl.wblock; p.nblk = pl.nblk; p.kmin = pl.kmin; p.nfold = pl.nfold;
+  while ((1u << p.logb) < pl.wblock) ++p.logb;
+  frbch_psearch_thresholds(par->sigma, p.thr);
+  p.peak_cap = kPsRawCap;
+  const std::shared_ptr<const std::vector<float>> tw = ps_table(n);
+  PostScope ps;
+  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  const dev_stream_t s = ps.s;
+  float *d_tw = nullptr, *d_res = nullptr;
+  double* d_q = nullptr;
+  if (ps.alloc(&d_tw, (size_t)n * sizeof(float)) || ps.alloc(&d_q, (size_t)nacc * sizeof(double)) ||
+      ps.alloc(&d_res, (size_t)rows_max * n * sizeof(float)) || ps.alloc(&p.mean, (size_t)rows_max * sizeof(double)) ||
+      ps.alloc(&p.live, (size_t)rows_max * sizeof(uint32_t)) || ps.alloc(&p.work, (size_t)(rows_max / 2) * n * 2 * sizeof(float)) ||
+      ps.alloc(&p.pw, (size_t)rows_max * nh * sizeof(float)) || ps.alloc(&p.peaks, (size_t)kPsRawCap * sizeof(PsPeak)) ||
+      ps.alloc(&p.npeak, sizeof(uint32_t)))
+    return e.fail(FRBCH_E_NOMEM, "device memory for the acceleration search: " + std::to_string(ap.scratch) + " bytes for batches of " +
+                                     std::to_string(rows_max) + " rows (a smaller batch_rows takes less)");
+  p.tw = d_tw;
+  p.series = d_res;
+  POST_DEV(dev_h2d(d_tw, tw->data(), (size_t)n * sizeof(float), s), "upload table");
+  POST_DEV(dev_h2d(d_q, q.data(), (size_t)nacc * sizeof(double), s), "upload trials");
+  ResParams rp;
+  memset(&rp, 0, sizeof rp);
+  rp.series = d_series;
+  rp.nout = nout;
+  rp.n = n;
+  rp.ndm = (int)ndm;
+  rp.rows_per_trial = (int)ap.rpt;
+  rp.out = d_res;
+  const bool rfast = res_fast(d_series, nout, d_res), fast = ps_fast(d_res);
+  int r[3];
+  const int npass = fast ? ps_passes(pl.log2n, r) : 0;
+  std::vector<std::vector<frbch_ps_cand>> per(nacc);
+  std::vector<PsPeak> raw;
+  for (uint32_t first = 0; first < nacc; first += ap.tpb) {
+    const uint32_t trials = std::min(ap.tpb, nacc - first), rows = trials * ap.rpt;
+    rp.q = d_q + first;
+    p.ndm = (int)rows;
+    p.npair = (int)(rows / 2);
+    POST_DEV(dev_memset(p.npeak, 0, sizeof(uint32_t), s), "clear peak count");
+    if ((rc = res_launch(rfast, rp, trials, s, e)) != 0) return rc;
+    if ((rc = ps_launches(p, pl, fast, npass, r, s, e)) != 0) return rc;
+    uint32_t nraw = 0;
+    POST_DEV(dev_d2h(&nraw, p.npeak, sizeof nraw, s), "download peak count");
+    POST_DEV(dev_sync(s), "sync");
+    if (nraw > kPsRawCap)
+      return e.fail(FRBCH_E_CAPACITY, "threshold too low: " + std::to_string(nraw) + " raw peaks in the batch of trials " +
+                                          std::to_string(first) + " .. " + std::to_string(first + trials - 1) +
+                                          ", the device list holds " + std::to_string(kPsRawCap) + " per batch");
+    raw.resize(nraw);
+    if (nraw) {
+      POST_DEV(dev_d2h(raw.data(), p.peaks, (size_t)nraw * sizeof(PsPeak), s), "download peaks");
+      POST_DEV(dev_sync(s), "sync");
+    }
+    for (uint32_t i = 0; i < nraw; ++i) {
+      frbch_ps_cand c;
+      memset(&c, 0, sizeof c);
+      c.dm_index = raw[i].dm % ap.rpt; c.h = raw[i].h; c.k = raw[i].k; c.power = raw[i].H;
+      per[first + raw[i].dm / ap.rpt].push_back(c);
+    }
+  }
+  ps.release();                           // the device is done with; the host goes on with the raw lists
+  if (kernel_used) { kernel_used[0] = rfast ? 1u : 0u; kernel_used[1] = fast ? 1u : 0u; kernel_used[2] = (uint32_t)npass; }
+  std::vector<frbch_pa_cand> out;
+  for (uint32_t i = 0; i < nacc; ++i) {   // step 8 of every trial on its own
+    std::vector<frbch_ps_cand> kept;
+    ps_sift(per[i], n, pl.tsamp, &kept);
+    for (const frbch_ps_cand& c : kept) {
+      frbch_pa_cand o;
+      memset(&o, 0, sizeof o);
+      o.dm_index = c.dm_index; o.acc_index = i; o.h = c.h; o.k = c.k; o.power = c.power;
+      o.sigma = c.sigma; o.freq_hz = c.freq_hz; o.acc_ms2 = accs[i];
+      out.push_back(o);
+    }
+  }
+  *ncand = out.size();
+  for (uint64_t i = 0; i < std::min<uint64_t>(cap, out.size()); ++i) cands[i] = out[i];
+  if (out.size() > cap) return e.fail(FRBCH_E_CAPACITY, std::to_string(out.size()) + " candidates, room for " + std::to_string(cap));
+  return FRBCH_OK;
+}
+}  // namespace
+
+extern "C" int frbch_resample_kernel(const float* d_series, uint64_t nout, const float* d_out) {
+  if (!d_series || !d_out || !nout) return FRBCH_E_ARG;
+  return res_fast(d_series, nout, d_out) ? 1 : 0;
+}
+
+extern "C" int frbch_resample_device(const float* d_series, uint32_t ndm, uint64_t nout, uint32_t n, double tsamp_s,
+                                     const double* accs, uint32_t nacc, int device, float* d_out, uint32_t* kernel_used,
+                                     char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  int rc = pa_check_n(n, nout, e);
+  if (rc) return rc;
+  if (!(tsamp_s > 0.0) || !(tsamp_s < 1.0e300)) return e.fail(FRBCH_E_ARG, "tsamp_s must be positive");
+  if (!d_series || !d_out) return e.fail(FRBCH_E_ARG, "null argument");
+  if (!ndm || ndm > 65535) return e.fail(FRBCH_E_ARG, "ndm must be 1..65535");
+  std::vector<double> q;
+  if ((rc = pa_check_accs(accs, nacc, n, tsamp_s, &q, e)) != 0) return rc;
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  PostScope ps;
+  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  double* d_q = nullptr;
+  if (ps.alloc(&d_q, (size_t)nacc * sizeof(double))) return e.fail(FRBCH_E_NOMEM, "device memory for the trials");
+  POST_DEV(dev_h2d(d_q, q.data(), (size_t)nacc * sizeof(double), ps.s), "upload trials");
+  ResParams rp;
+  memset(&rp, 0, sizeof rp);
+  rp.series = d_series;
+  rp.nout = nout;
+  rp.n = n;
+  rp.ndm = (int)ndm;
+  rp.rows_per_trial = (int)ndm;
+  const bool fast = res_fast(d_series, nout, d_out);
+  const uint32_t step = std::max<uint32_t>(1, 65535u / ndm);           // trials of a launch: at most 65535 rows
+  for (uint32_t first = 0; first < nacc; first += step) {
+    rp.q = d_q + first;
+    rp.out = d_out + (size_t)first * ndm * n;
+    if ((rc = res_launch(fast, rp, std::min(step, nacc - first), ps.s, e)) != 0) return rc;
+  }
+  POST_DEV(dev_sync(ps.s), "sync");
+  if (kernel_used) kernel_used[0] = fast ? 1u : 0u;
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_resample_host(const float* series, uint32_t ndm, uint64_t nout, uint32_t n, double tsamp_s, const double* accs,
+                                   uint32_t nacc, int device, float* out, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  int rc = pa_check_n(n, nout, e);
+  if (rc) return rc;
+  if (!(tsamp_s > 0.0) || !(tsamp_s < 1.0e300)) return e.fail(FRBCH_E_ARG, "tsamp_s must be positive");
+  if (!series || !out || !ndm || ndm > 65535) return e.fail(FRBCH_E_ARG, "null argument, or ndm outside 1..65535");
+  std::vector<double> q;
+  if ((rc = pa_check_accs(accs, nacc, n, tsamp_s, &q, e)) != 0) return rc;
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  float* d_series = hs.in(series, (size_t)ndm * nout * sizeof(float));
+  float* d_out = hs.out(out, (size_t)nacc * ndm * n * sizeof(float));
+  return hs.run(e, "device memory for the series and the resampled planes", "upload series", "download resampled planes", [&]() {
+    return frbch_resample_device(d_series, ndm, nout, n, tsamp_s, accs, nacc, device, d_out, kernel_used, err, err_cap);
+  });
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_pasearch_plan(uint32_t ndm, uint64_t nout, const frbch_ps_params* par, uint32_t nacc, uint32_t batch_rows,
+                                   uint32_t* n, uint32_t* rows_per_batch, uint32_t* nbatch, uint64_t* scratch_bytes, char* err,
+                                   size_t err_cap) {
+  PostErr e{err, err_cap};
+  PsPlan pl;
+  const int rc = ps_check(par, nout, 1.0, &pl, e);
+  if (rc) return rc;
+  if (!ndm || ndm > kPaMaxRows) return e.fail(FRBCH_E_ARG, "ndm must be 1..65534");
+  if (nacc < 1 || nacc > kPaMaxAcc) return e.fail(FRBCH_E_ARG, "nacc must be 1..1024");
+  PaPlan ap;
+  pa_plan(ndm, pl.n, nacc, batch_rows, &ap);
+  if (n) *n = pl.n;
+  if (rows_per_batch) *rows_per_batch = ap.tpb * ap.rpt;
+  if (nbatch) *nbatch = ap.nbatch;
+  if (scratch_bytes) *scratch_bytes = ap.scratch;
+  return FRBCH_OK;
+}
+
+extern "C" int frbch_pasearch_device(const float* d_series, uint32_t ndm, uint64_t nout, const frbch_ps_params* par,
+                                     const double* accs, uint32_t nacc, uint32_t batch_rows, int device, frbch_pa_cand* cands,
+                                     uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  return pa_search_run(d_series, ndm, nout, par, 0.0, accs, nacc, batch_rows, device, cands, cap, ncand, kernel_used, err, err_cap);
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_pasearch_host(const float* series, uint32_t ndm, uint64_t nout, const frbch_ps_params* par, const double* accs,
+                                   uint32_t nacc, uint32_t batch_rows, int device, frbch_pa_cand* cands, uint64_t cap,
+                                   uint64_t* ncand, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  PsPlan pl;
+  std::vector<double> q;
+  int rc = pa_check(par, ndm, nout, 0.0, accs, nacc, &pl, &q, e);
+  if (rc) return rc;
+  if (!series) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  float* d_series = hs.in(series, (size_t)ndm * nout * sizeof(float));
+  return hs.run(e, "device memory for the series", "upload series", "download", [&]() {
+    return frbch_pasearch_device(d_series, ndm, nout, par, accs, nacc, batch_rows, device, cands, cap, ncand, kernel_used, err, err_cap);
+  });
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_dedisperse_pasearch_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const double* dms,
+                                              uint32_t ndm, uint32_t zerodm, double clip_sigma, const frbch_ps_params* par,
+                                              const double* accs, uint32_t nacc, uint32_t batch_rows, int device,
+                                              float* series_out, uint64_t nout, uint64_t* nclipped, frbch_pa_cand* cands,
+                                              uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  int rc = post_check_fil(fil, nrows, e);
+  if (rc) return rc;
+  PsPlan pl;
+  std::vector<double> q;
+  if ((rc = pa_check(par, ndm, nout, fil->tsamp_s, accs, nacc, &pl, &q, e)) != 0) return rc;
+  if (!rows || !ncand || (cap && !cands)) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
+  float* d_out = hs.out(series_out, (size_t)ndm * nout * sizeof(float));          // (series_out may be null: no download then)
+  if (hs.failed) return e.fail(FRBCH_E_NOMEM, "device memory for the rows");
+  if (hs.upload() != 0) return e.fail(FRBCH_E_DEVICE, "upload rows");
+  rc = frbch_dedisperse_device(fil, d_rows, nrows, dms, ndm, zerodm, clip_sigma, device, d_out, nout, nclipped, err, err_cap);
+  hs.drop(d_rows);                                                 // the plane stays in HBM; the rows are done with
+  if (!rc && series_out && hs.download() != 0) rc = e.fail(FRBCH_E_DEVICE, "download series");
+  if (!rc) rc = pa_search_run(d_out, ndm, nout, par, fil->tsamp_s, accs, nacc, batch_rows, device, cands, cap, ncand, kernel_used, err, err_cap);
+  return rc;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_pa_group_cands(const frbch_pa_cand* cands, uint64_t ncand, uint32_t dm_gap, uint32_t acc_gap,
+                                    frbch_pa_group* groups, uint64_t cap, uint64_t* ngroup, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  if (!ngroup || (ncand && !cands) || (cap && !groups)) return e.fail(FRBCH_E_ARG, "null argument");
+  if (dm_gap < 1 || dm_gap > 16) return e.fail(FRBCH_E_ARG, "dm_gap must be 1..16");
+  if (acc_gap < 1 || acc_gap > 16) return e.fail(FRBCH_E_ARG, "acc_gap must be 1..16");
+  for (uint64_t i = 0; i < ncand; ++i)
+    if (!ps_fold_ok(cands[i].h) || !cands[i].k) return e.fail(FRBCH_E_ARG, "record " + std::to_string(i) + ": h must be 1, 2, 4, 8 or 16 and k positive");
+  *ngroup = 0;
+  if (!ncand) return FRBCH_OK;
+  auto f_less = [](const frbch_pa_cand& a, const frbch_pa_cand& b) { return (uint64_t)a.k * b.h < (uint64_t)b.k * a.h; };
+  auto f_dist = [](const frbch_pa_cand& a, const frbch_pa_cand& b) {
+    const uint64_t x = (uint64_t)a.k * b.h, y = (uint64_t)b.k * a.h;
+    return x > y ? x - y : y - x;
+  };
+  // the sweep of frbch_ps_group_cands, with the distance in trials as a third condition
+  std::vector<uint64_t> order(ncand), parent(ncand);
+  for (uint64_t i = 0; i < ncand; ++i) order[i] = parent[i] = i;
+  std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {
+    if (f_less(cands[a], cands[b])) return true;
+    if (f_less(cands[b], cands[a])) return false;
+    return a < b;
+  });
+  auto find = [&](uint64_t x) {
+    while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; }
+    return x;
+  };
+  for (uint64_t i = 0; i < ncand; ++i) {
+    const frbch_pa_cand& a = cands[order[i]];
+    for (uint64_t j = i + 1; j < ncand; ++j) {
+      const frbch_pa_cand& b = cands[order[j]];
+      if (2 * f_dist(a, b) > 3 * (uint64_t)a.h * b.h) break;
+      const uint32_t ddm = a.dm_index > b.dm_index ? a.dm_index - b.dm_index : b.dm_index - a.dm_index;
+      const uint32_t dacc = a.acc_index > b.acc_index ? a.acc_index - b.acc_index : b.acc_index - a.acc_index;
+      if (ddm > dm_gap || dacc > acc_gap) continue;
+      const uint64_t ra = find(order[i]), rb = find(order[j]);
+      if (ra != rb) parent[std::max(ra, rb)] = std::min(ra, rb);
+    }
+  }
+  auto better = [](const frbch_pa_cand& a, const frbch_pa_cand& b) {     // a represents a group rather than b
+    if (a.sigma != b.sigma) return a.sigma > b.sigma;
+    if (a.h != b.h) return a.h < b.h;
+    if (a.dm_index != b.dm_index) return a.dm_index < b.dm_index;
+    if (a.acc_index != b.acc_index) return a.acc_index < b.acc_index;
+    return a.k < b.k;
+  };
+  std::vector<int64_t> slot(ncand, -1);                                  // root -> index in `out`
+  std::vector<frbch_pa_group> out;
+  for (uint64_t i = 0; i < ncand; ++i) {
+    const uint64_t r = find(i);
+    const frbch_pa_cand& c = cands[i];
+    if (slot[r] < 0) {
+      slot[r] = (int64_t)out.size();
+      frbch_pa_group g;
+      memset(&g, 0, sizeof g);
+      g.best = c;
+      g.nmember = 1;
+      g.dm_index_lo = g.dm_index_hi = c.dm_index;
+      g.acc_index_lo = g.acc_index_hi = c.acc_index;
+      out.push_back(g);
+      continue;
+    }
+    frbch_pa_group& g = out[(size_t)slot[r]];
+    if (better(c, g.best)) g.best = c;
+    ++g.nmember;
+    g.dm_index_lo = std::min(g.dm_index_lo, c.dm_index);
+    g.dm_index_hi = std::max(g.dm_index_hi, c.dm_index);
+    g.acc_index_lo = std::min(g.acc_index_lo, c.acc_index);
+    g.acc_index_hi = std::max(g.acc_index_hi, c.acc_index);
+  }
+  std::stable_sort(out.begin(), out.end(), [&](const frbch_pa_group& a, const frbch_pa_group& b) {
+    if (a.best.sigma != b.best.sigma) return a.best.sigma > b.best.sigma;
+    if (f_less(a.best, b.best)) return true;
+    if (f_less(b.best, a.best)) return false;
+    if (a.best.dm_index != b.best.dm_index) return a.best.dm_index < b.best.dm_index;
+    if (a.best.acc_index != b.best.acc_index) return a.best.acc_index < b.best.acc_index;
     return a.best.h < b.best.h;
   });
   *ngroup = out.size();

@@ -1036,3 +1036,46 @@ KERNEL(frbch_post_ps_harm, PsParams) {
   (void)smem;
   PHASE { ps_harm_bin(p, by, (uint32_t)bx * (uint32_t)nthr + (uint32_t)tid); }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Time-domain resampling for the acceleration search (frbch_resample_*, frbch_pasearch_*; include/frbch.h states the rule):
+// out[trial][row][t] = x[row][u(t)], u(t) = t + (int64)rint(q (double)(t (t - n))), one double product per output and nothing
+// that could contract.  A pure gather: the bytes of the output are those of the input.  Rows dm >= ndm of a trial (the zero
+// partner of an odd last series) are written as 0.  The kernel below is the generic form; the fast form
+// (kernels_post_fast.inc) stages the window of a tile of outputs through the LDS.
+// ---------------------------------------------------------------------------------------------------------------------
+struct ResParams {
+  const float* series;         // [ndm][nout]; only positions < n are read
+  uint64_t nout;
+  uint32_t n;                  // outputs per row
+  int ndm, rows_per_trial;     // rows_per_trial >= ndm: rows of a trial in `out`
+  const double* q;             // [trials of this launch]
+  float* out;                  // [trials of this launch][rows_per_trial][n]
+};
+
+// u(t) of the rule.  For an accepted q (|q| n <= 0.5) it lies in 0 .. n - 1; the clamp never moves it and is there so that no
+// q whatever could take an address out of the row.
+DEVFN inline uint32_t res_index(double q, uint32_t t, uint32_t n) {
+  POST_NO_CONTRACT
+  const int64_t prod = (int64_t)t * ((int64_t)t - (int64_t)n);
+  const double g = rint(q * (double)prod);
+  int64_t u = (int64_t)t + (int64_t)g;
+  if (u < 0) u = 0;
+  if (u > (int64_t)n - 1) u = (int64_t)n - 1;
+  return (uint32_t)u;
+}
+
+// grid (n / 256, trials * rows_per_trial), one output per thread
+KERNEL(frbch_post_resample, ResParams) {
+  K_PROLOGUE;
+  (void)smem;
+  PHASE {
+    const uint32_t t = (uint32_t)bx * (uint32_t)nthr + (uint32_t)tid;
+    if (t < p.n) {
+      const int trial = by / p.rows_per_trial, dm = by - trial * p.rows_per_trial;
+      float v = 0.f;
+      if (dm < p.ndm) v = p.series[(size_t)dm * p.nout + res_index(p.q[trial], t, p.n)];
+      p.out[(size_t)by * p.n + t] = v;
+    }
+  }
+}

@@ -837,4 +837,47 @@ __global__ void __launch_bounds__(kPsThreads) frbch_post_ps_norm_lds(PsParams p)
     x[i] = q;
   }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Resampling for the acceleration search, fast form (HIP only; frbch_post_resample of kernels_post.inc is the emulable form
+// and the fallback, and both evaluate res_index: the same bytes).  A workgroup owns kResTile consecutive outputs of one row
+// of one trial, four a thread.  u(t) never steps back and never by more than 2, so the inputs of the tile are the contiguous
+// window [u(first), u(last)] of at most 2 kResTile - 1 samples: it is staged through the LDS with 16-byte loads (from the
+// 16-byte boundary at or below its start; rows are 16-byte aligned, so the last load ends inside the row), the threads pick
+// their four values from the LDS and store them with one 16-byte store.  The index rule is evaluated once per output: the
+// first and the last thread leave their outer indices in the LDS for the others.  grid (n / kResTile, trials * rows_per_trial).
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int kResThreads = 256, kResTile = 4 * kResThreads;
+constexpr int kResWin = 2 * kResTile + 8;           // floats: the window, and the up to 3 + 3 samples of the alignment
+__global__ void __launch_bounds__(kResThreads) frbch_post_resample_lds(ResParams p) {
+  __shared__ __attribute__((aligned(16))) float win[kResWin];
+  __shared__ uint32_t ends[2];
+  const int tid = threadIdx.x, row = (int)blockIdx.y;
+  const int trial = row / p.rows_per_trial, dm = row - trial * p.rows_per_trial;
+  const uint32_t t0 = blockIdx.x * (uint32_t)kResTile + 4u * (uint32_t)tid;
+  float4* dst = (float4*)(p.out + (size_t)row * p.n + t0);
+  if (dm >= p.ndm) {                                // the zero partner of an odd last series (the whole workgroup)
+    *dst = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
+  const double q = p.q[trial];
+  uint32_t u[4];
+  for (int j = 0; j < 4; ++j) u[j] = res_index(q, t0 + (uint32_t)j, p.n);
+  if (tid == 0) ends[0] = u[0];
+  if (tid == kResThreads - 1) ends[1] = u[3];
+  __syncthreads();
+  const uint32_t lo = ends[0] & ~3u, hi = ends[1];
+  uint32_t nvec = hi >= lo ? ((hi - lo) >> 2) + 1u : 0u;
+  if (nvec > (uint32_t)(kResWin / 4)) nvec = (uint32_t)(kResWin / 4);      // (never: the window bound above)
+  const float4* src = (const float4*)(p.series + (size_t)dm * p.nout + lo);
+  for (uint32_t i = (uint32_t)tid; i < nvec; i += (uint32_t)kResThreads) ((float4*)win)[i] = src[i];
+  __syncthreads();
+  float v[4];
+  for (int j = 0; j < 4; ++j) {
+    uint32_t i = u[j] - lo;
+    if (i > (uint32_t)(kResWin - 1)) i = (uint32_t)(kResWin - 1);          // (never, for the same reason)
+    v[j] = win[i];
+  }
+  *dst = make_float4(v[0], v[1], v[2], v[3]);
+}
 }  // namespace fast

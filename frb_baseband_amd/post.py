@@ -784,9 +784,118 @@ def group_periodic(cands, dm_gap: int = 2, lib=None) -> np.ndarray:
     return out[: n.value].copy()
 
 
+# ---- trial accelerations ---------------------------------------------------------------------------------------------
+C_LIGHT = 299792458.0
+PA_CAND = np.dtype([("dm_index", "<u4"), ("acc_index", "<u4"), ("h", "<u4"), ("k", "<u4"), ("power", "<f4"), ("reserved", "<u4"),
+                    ("sigma", "<f8"), ("freq_hz", "<f8"), ("acc_ms2", "<f8")])
+PA_GROUP = np.dtype([("best", PA_CAND), ("nmember", "<u4"), ("dm_index_lo", "<u4"), ("dm_index_hi", "<u4"), ("acc_index_lo", "<u4"),
+                     ("acc_index_hi", "<u4"), ("reserved", "<u4")])
+PA_HEADER = "# Period (s)      Freq (Hz)        DM    Sigma  Fold  Members  DMlo  DMhi    Acc (m/s^2)  Alo  Ahi"
+PA_ROW = "%14.9f %14.7f %9.2f %8.2f %5d %8d %5d %5d %14.6g %4d %4d"
+
+
+def acc_list(amax: float, astep: float) -> np.ndarray:
+    """Trial accelerations -amax .. 0 .. +amax in steps of ``astep`` (m/s^2), 0 always a member: k astep for
+    |k| <= floor(amax / astep); ``amax`` = 0 gives [0]."""
+    amax, astep = float(amax), float(astep)
+    if not (amax >= 0.0 and np.isfinite(amax)):
+        raise InputError("amax must be finite and not negative")
+    if amax == 0.0:
+        return np.zeros(1, dtype=np.float64)
+    if not (astep > 0.0 and np.isfinite(astep)):
+        raise InputError("astep must be positive when amax is")
+    m = int(np.floor(amax / astep * (1.0 + 1e-12)))
+    if 2 * m + 1 > 1024:
+        raise InputError("%d trial accelerations: the library takes 1024 at the most (raise astep)" % (2 * m + 1))
+    return np.arange(-m, m + 1, dtype=np.float64) * astep
+
+
+def accel_step(n: int, tsamp: float, f_hz: float, bins: float = 1.0) -> float:
+    """The acceleration (m/s^2) that moves a signal of ``f_hz`` by ``bins`` Fourier bins over a scan of ``n`` samples:
+    bins c / (f_hz (n tsamp)^2)."""
+    return float(bins) * C_LIGHT / (float(f_hz) * (float(n) * float(tsamp)) ** 2)
+
+
+def _pa_call(call, cap: int):
+    """_ps_call for frbch_pa_cand records and kernel_used[3]"""
+    while True:
+        cands = np.zeros(cap, dtype=PA_CAND)
+        ncand, used = C.c_uint64(0), (C.c_uint32 * 3)(0, 0, 0)
+        err = C.create_string_buffer(512)
+        rc = call(cands.ctypes.data, cap, C.byref(ncand), used, err, len(err))
+        if rc == _lib.E_CAPACITY and ncand.value > cap:
+            cap = ncand.value
+            continue
+        _check(rc, err)
+        return cands[: ncand.value].copy(), (used[0], used[1], used[2])
+
+
+def _accs_of(accs) -> np.ndarray:
+    a = np.ascontiguousarray(accs, dtype=np.float64).reshape(-1)
+    if not 1 <= a.size <= 1024:
+        raise InputError("1 .. 1024 trial accelerations")
+    return a
+
+
+def resample(series, tsamp: float, accs, nfft: int = 0, device: int = 0, lib=None, info: dict | None = None) -> np.ndarray:
+    """The resampler of the acceleration search alone (frbch_resample_host; include/frbch.h states the index rule) ->
+    [nacc][ndm][n] float32, n = ``nfft`` or the largest power of two not above nout."""
+    lib = lib or _lib.load()
+    y = np.ascontiguousarray(series, dtype=np.float32)
+    y = y.reshape(1, -1) if y.ndim == 1 else y
+    if y.ndim != 2 or y.size == 0:
+        raise InputError("series must be [ndm][nout] with at least one sample")
+    a = _accs_of(accs)
+    params = ps_params(tsamp, nfft=nfft)
+    n = lib.frbch_psearch_nfft(y.shape[1], C.byref(params))
+    if n <= 0:
+        raise InputError("the transform length must be a power of two in 2^12..2^22 and at most nout")
+    out = np.zeros((a.size, y.shape[0], n), dtype=np.float32)
+    used = (C.c_uint32 * 1)(0)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_resample_host(y.ctypes.data, y.shape[0], y.shape[1], n, float(tsamp), a.ctypes.data, a.size, device,
+                                   out.ctypes.data, used, err, len(err)), err)
+    if info is not None:
+        info.update(resampler=used[0])
+    return out
+
+
+def accel_search(series, tsamp: float, accs, sigma: float = 6.0, nharm: int = 16, flo: float = 0.5, nfft: int = 0,
+                 wblock: int = 128, batch_rows: int = 0, device: int = 0, lib=None, info: dict | None = None, cap: int = 4096):
+    """``periodicity_search`` for every trial acceleration of ``accs`` (m/s^2, strictly ascending) on the GPU
+    (frbch_pasearch_host): every series is resampled per trial and searched as before -> structured array PA_CAND sorted by
+    (acc_index, dm_index, h, k); freq_hz is the frequency at the middle of the scan.  ``info`` receives ``resampler``,
+    ``kernel_used`` and ``passes``."""
+    lib = lib or _lib.load()
+    y = np.ascontiguousarray(series, dtype=np.float32)
+    y = y.reshape(1, -1) if y.ndim == 1 else y
+    if y.ndim != 2 or y.size == 0:
+        raise InputError("series must be [ndm][nout] with at least one sample")
+    a = _accs_of(accs)
+    params = ps_params(tsamp, sigma, nharm, flo, nfft, wblock)
+    out, used = _pa_call(lambda c, n, nc, u, e, ne: lib.frbch_pasearch_host(
+        y.ctypes.data, y.shape[0], y.shape[1], C.byref(params), a.ctypes.data, a.size, int(batch_rows), device, c, n, nc, u, e, ne), cap)
+    if info is not None:
+        info.update(resampler=used[0], kernel_used=used[1], passes=used[2])
+    return out
+
+
+def group_accel(cands, dm_gap: int = 2, acc_gap: int = 1, lib=None) -> np.ndarray:
+    """Join the records of one signal across trial DMs and trial accelerations (frbch_pa_group_cands, host only) ->
+    structured array PA_GROUP, the strongest first."""
+    lib = lib or _lib.load()
+    recs = np.ascontiguousarray(cands, dtype=PA_CAND)
+    out = np.zeros(max(1, recs.size), dtype=PA_GROUP)
+    n = C.c_uint64(0)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_pa_group_cands(recs.ctypes.data, recs.size, int(dm_gap), int(acc_gap), out.ctypes.data, out.size, C.byref(n),
+                                    err, len(err)), err)
+    return out[: n.value].copy()
+
+
 def psearch_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, zerodm=True, clip=5, sigma=6.0, nharm=16, flo=0.5, nfft=0, wblock=128,
                 dm_gap=2, max_cands=0, fold_best=0, device=0, lib=None, info: dict | None = None, flag_file=None, rfi=None,
-                periodic=None):
+                periodic=None, amax=0.0, astep=0.0, acc_gap=1):
     """Dedisperse a filterbank over the DMs of ``prepdata_gpu`` and search every series for periodic signals in one library
     call (frbch_dedisperse_psearch_host: the DM x time plane never leaves the GPU), then join the records across DMs.
     Writes ``<base>_psearch.txt`` (one line per candidate: period, frequency, DM, sigma, harmonics summed, members and DM span)
@@ -794,7 +903,11 @@ def psearch_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, zerodm=True, clip=5, sig
     ``search_fil``.  ``max_cands`` > 0 keeps the strongest N candidates.  ``fold_best`` = K folds the K strongest candidates
     with the ephemeris {F0 = the candidate's frequency, F1 = 0, DM = its trial DM, PEPOCH = tstart} through ``fold_fil``'s
     machinery; their outputs are ``<base>_psearch_cand<i>.ar`` / ``.profile.txt`` / ``.png``.
-    Returns (list of files written, candidates as PS_GROUP)."""
+    ``amax`` > 0 adds trial accelerations ``acc_list(amax, astep)`` (m/s^2; ``astep`` = 0: two bins of drift at 100 Hz,
+    ``accel_step(n, tsamp, 100.0, 2.0)``): one call of frbch_dedisperse_pasearch_host, records joined across DMs and trials
+    (``acc_gap``), a text file with acceleration columns under PA_HEADER, ``accs`` in the ``.npz``, and folds with
+    F1 = -F0 a / c at PEPOCH = the middle of the searched span.  With ``amax`` = 0 nothing differs from before.
+    Returns (list of files written, candidates as PS_GROUP, or PA_GROUP with ``amax`` > 0)."""
     lib = lib or _lib.load()
     _periodic_args(periodic, rfi, False)
     fil = _read_rows(filterbankfile, flag_file, rfi, device, lib, info, periodic=periodic)
@@ -808,6 +921,9 @@ def psearch_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, zerodm=True, clip=5, sig
         raise InputError("the dispersion delay across the band exceeds the length of the filterbank")
     params = ps_params(hdr["tsamp"], sigma, nharm, flo, nfft, wblock)
     nclip = C.c_uint64(0)
+    if amax > 0.0:
+        return _pasearch_fil(fil, filterbankfile, rows, desc, dms, dm_arr, nout, params, zerodm, clip, dm_gap, max_cands, fold_best,
+                             device, lib, info, amax, astep, acc_gap)
     recs, used = _ps_call(lambda c, n, nc, u, e, ne: lib.frbch_dedisperse_psearch_host(
         C.byref(desc), rows.ctypes.data, rows.shape[0], dm_arr.ctypes.data, dm_arr.size, 1 if zerodm else 0, float(clip),
         C.byref(params), device, None, nout, C.byref(nclip), c, n, nc, u, e, ne), 4096)
@@ -830,6 +946,45 @@ def psearch_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, zerodm=True, clip=5, sig
         b = g["best"]
         par = {"F0": float(b["freq_hz"]), "F1": 0.0, "DM": float(dms[int(b["dm_index"])]), "PEPOCH": float(hdr["tstart"]),
                "PSR": "cand%d" % i}
+        ar, _profile = _fold_par(fil, filterbankfile, par, 0, 10.0, 128, device, lib, "%s_psearch_cand%d" % (base, i), None, 0.0,
+                                 "coherency")
+        files.append(ar)
+    return files, groups
+
+
+def _pasearch_fil(fil, filterbankfile, rows, desc, dms, dm_arr, nout, params, zerodm, clip, dm_gap, max_cands, fold_best, device, lib,
+                  info, amax, astep, acc_gap):
+    """``psearch_fil`` with trial accelerations, from the point where the two part"""
+    hdr = fil.header
+    n = lib.frbch_psearch_nfft(nout, C.byref(params))
+    if n <= 0:
+        raise InputError("the transform length must be a power of two in 2^12..2^22 and at most the dedispersed length")
+    accs = acc_list(amax, astep if astep > 0.0 else accel_step(n, hdr["tsamp"], 100.0, 2.0))
+    nclip = C.c_uint64(0)
+    recs, used = _pa_call(lambda c, m, nc, u, e, ne: lib.frbch_dedisperse_pasearch_host(
+        C.byref(desc), rows.ctypes.data, rows.shape[0], dm_arr.ctypes.data, dm_arr.size, 1 if zerodm else 0, float(clip),
+        C.byref(params), accs.ctypes.data, accs.size, 0, device, None, nout, C.byref(nclip), c, m, nc, u, e, ne), 4096)
+    groups = group_accel(recs, dm_gap, acc_gap, lib=lib)
+    if max_cands > 0:
+        groups = groups[:max_cands]
+    if info is not None:
+        info.update(resampler=used[0], kernel_used=used[1], passes=used[2], nclipped=nclip.value, nout=nout, nfft=n, records=recs,
+                    accs=accs)
+    base = filterbankfile.replace(".fil", "")
+    with open(base + "_psearch.txt", "w") as f:
+        f.write(PA_HEADER + "\n")
+        for g in groups:
+            b = g["best"]
+            f.write(PA_ROW % (1.0 / b["freq_hz"], b["freq_hz"], dms[int(b["dm_index"])], b["sigma"], int(b["h"]), int(g["nmember"]),
+                              int(g["dm_index_lo"]), int(g["dm_index_hi"]), b["acc_ms2"], int(g["acc_index_lo"]),
+                              int(g["acc_index_hi"])) + "\n")
+    np.savez(base + "_psearch.npz", records=recs, candidates=groups, dms=dm_arr, nfft=n, tsamp=hdr["tsamp"], accs=accs)
+    files = [base + "_psearch.txt", base + "_psearch.npz"]
+    for i, g in enumerate(groups[: max(0, int(fold_best))]):
+        b = g["best"]
+        f0 = float(b["freq_hz"])
+        par = {"F0": f0, "F1": -f0 * float(b["acc_ms2"]) / C_LIGHT, "DM": float(dms[int(b["dm_index"])]),
+               "PEPOCH": float(hdr["tstart"]) + (n * hdr["tsamp"] / 2.0) / 86400.0, "PSR": "cand%d" % i}
         ar, _profile = _fold_par(fil, filterbankfile, par, 0, 10.0, 128, device, lib, "%s_psearch_cand%d" % (base, i), None, 0.0,
                                  "coherency")
         files.append(ar)
@@ -1604,7 +1759,7 @@ def main(argv=None):
     """``python -m frb_baseband_amd.post fold <fil> <par> [--polyco FILE] [--doppler X] [--products coherency|stokes] [...]`` / ``... prepdata <fil> --dm <dm> [...]`` /
     ``... search <fil> --dm <dm> [--dm2 --dmstep --threshold --max-width --detrend ...]`` /
     ``... candidates <fil> --dm <dm> [search options] [--dm-gap --min-members --max-cands --nt --nf --ndm]`` /
-    ``... psearch <fil> --dm <dm> [--dm2 --dmstep --sigma --nharm --flo --nfft --wblock --dm-gap --max-cands --fold-best K]`` /
+    ``... psearch <fil> --dm <dm> [--dm2 --dmstep --sigma --nharm --flo --nfft --wblock --dm-gap --max-cands --fold-best K --amax A --astep S --acc-gap G]`` /
     ``... rfifind <fil> [--block-rows --t-cell --t-chan --chan-frac --block-frac --flag FILE --write-clean]``
     (``search`` and ``candidates`` take ``--flag FILE`` and ``--rfi``; ``search``, ``candidates`` and ``rfifind`` take ``--resident``:
     one upload of the rows per command; ``rfifind --periodic [--t-freq S]`` and ``--rfi --periodic`` add the periodicity test): the stages
@@ -1666,6 +1821,9 @@ def main(argv=None):
     z.add_argument("--t-freq", type=float, default=4.0, help="threshold of --periodic, Gaussian sigma over the bins of a cell")
     z.add_argument("--max-cands", type=int, default=0, help="keep the strongest N candidates (0: all)")
     z.add_argument("--fold-best", type=int, default=0, help="fold the K strongest candidates at their frequency and DM")
+    z.add_argument("--amax", type=float, default=0.0, help="largest trial acceleration, m/s^2 (0: no acceleration search)")
+    z.add_argument("--astep", type=float, default=0.0, help="step of the trial accelerations, m/s^2 (0: two bins of drift at 100 Hz)")
+    z.add_argument("--acc-gap", type=int, default=1, help="records at most this many trial accelerations apart can join")
     z.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     k = sub.add_parser("candidates", help="search, group the records across DMs, cut the frequency-time and DM-time planes of every group")
     k.add_argument("fil")
@@ -1724,7 +1882,7 @@ def main(argv=None):
     elif a.cmd == "psearch":
         files, groups = psearch_fil(a.fil, a.dm, dm2=a.dm2, dmstep=a.dmstep, zerodm=a.nozerodm, clip=a.clip, sigma=a.sigma, nharm=a.nharm,
                                     flo=a.flo, nfft=a.nfft, wblock=a.wblock, dm_gap=a.dm_gap, max_cands=a.max_cands, fold_best=a.fold_best,
-                                    device=a.device, flag_file=a.flag, rfi=a.rfi or None,
+                                    device=a.device, flag_file=a.flag, rfi=a.rfi or None, amax=a.amax, astep=a.astep, acc_gap=a.acc_gap,
                                     **(dict(periodic=dict(t_freq=a.t_freq)) if a.periodic else {}))
         for path in files:
             print("wrote", path)

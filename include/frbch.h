@@ -432,11 +432,11 @@ int frbch_dedisperse_search_host(const frbch_fil_desc* fil, const void* rows, ui
 
 /* ---- periodicity search of the dedispersed series --------------------------------------------------
  * The other search people run on the .dat files of a DM range (process_vdif.py:78-98,202-229) is `realfft` + `accelsearch`.
- * frbch_psearch_* do the zero-acceleration part of it on the GPU, on series[dm][t] (float32, t < nout) still in HBM: one long
+ * frbch_psearch_* do the zero-acceleration part of it on the GPU (frbch_pasearch_*, below, add trial accelerations), on series[dm][t] (float32, t < nout) still in HBM: one long
  * transform per series, a red-noise normalisation, incoherent harmonic sums of 1, 2, 4, 8 and 16 harmonics, and a list of
  * peaks.  PRESTO is not in the reference tree: the conventions are this library's [EXT-UNVERIFIED: parity with accelsearch is
  * not pinned] (tests/psearch_oracle.py restates them in numpy), chosen so that every record is reproducible to the bit.
- * NOT done: acceleration or jerk search, barycentring, transform lengths that are no power of two, and the merging of
+ * NOT done: jerk search (trial accelerations are frbch_pasearch_*, below), barycentring, transform lengths that are no power of two, and the merging of
  * harmonically related candidates (a strong signal appears at f, and at f/2, 2f/3 ... with less significance: the output says
  * what was found and a reader can see the ladder).
  *  0. Length.  n = nfft, or with nfft = 0 the largest power of two not above nout (frbch_psearch_nfft); 2^12 <= n <= 2^22 and
@@ -541,6 +541,96 @@ int frbch_psearch_sift(const frbch_ps_cand* raw, uint64_t nraw, uint32_t n, doub
  * dm_gap outside 1..16, an h other than 1, 2, 4, 8, 16, k = 0. */
 int frbch_ps_group_cands(const frbch_ps_cand* cands, uint64_t ncand, uint32_t dm_gap, frbch_ps_group* groups, uint64_t cap,
                          uint64_t* ngroup, char* err, size_t err_cap);
+
+/* ---- acceleration search of the dedispersed series --------------------------------------------------
+ * A pulsar in a binary changes its apparent frequency during the scan and smears over many Fourier bins; the search above
+ * loses it.  frbch_pasearch_* repeat that search for a list of trial accelerations: for every trial each series is re-read
+ * at quadratically stretched sample positions (time-domain resampling, a pure gather with an integer index rule), and the
+ * resampled series go through steps 1 to 8 above unchanged.  The conventions are this library's own [EXT-UNVERIFIED: parity
+ * with accelsearch or PEASOUP is not pinned] (tests/accel_oracle.py restates them in numpy); every record is reproducible to
+ * the bit.  NOT done: jerk search, barycentring, interpolation between samples (the nearest sample is taken).
+ *  A0. Given n of step 0, tsamp_s and a trial acceleration a in m/s^2:
+ *          q    = (a * tsamp_s) / (2.0 * 299792458.0)        double, on the host, evaluated as written
+ *          g(t) = rint( q * (double)( (int64)t * ((int64)t - (int64)n) ) )
+ *                 one double multiplication, rounded to the nearest integer, ties to even; the integer product is exact
+ *          u(t) = t + (int64) g(t)                           an integer addition: nothing can contract into a multiply-add
+ *          r_a[t] = x[u(t)],  0 <= t < n
+ *      Both ends are pinned: u(0) = 0 and u(n - 1) = n - 1.  A trial is accepted iff a is finite and |q| * n <= 0.5, i.e. up
+ *      to |a| = c / (n tsamp_s); otherwise FRBCH_E_ARG with a message that names that largest |a|.  Within the range
+ *      0 <= u(t) <= n - 1, u never steps back and never by more than 2, and |u(t) - t| <= n / 8 (tests/test_accel.py checks all
+ *      three at n = 2^12 and 2^22 for q n = +-0.5).  Samples at t >= n never influence anything, and no address outside
+ *      d_series[0, ndm * nout) is read.
+ *      Meaning: a signal of nu (t - q t^2) cycles (t in samples) becomes one of nu (1 - q n) t cycles, a steady tone.  POSITIVE
+ *      a therefore removes a frequency that FALLS during the scan (a source accelerating away from the observer), and
+ *      freq_hz of a record is the frequency at the MIDDLE of the n * tsamp_s span.  A fold of such a record takes F0 = freq_hz,
+ *      F1 = -F0 a / c and PEPOCH = the start + (n tsamp_s / 2).
+ *  A1. The records of trial i are exactly those of frbch_psearch_* on the plane [ndm][n] of that trial's resampled series:
+ *      the series are paired (2m, 2m + 1) WITHIN the trial, the missing partner of an odd last series is zero, every trial
+ *      goes through steps 1 to 8 on its own (a NaN sample makes a series dead only in the trials whose gather reaches it).
+ *      A trial a = 0 reproduces the records of frbch_psearch_*.  accs[nacc], 1 <= nacc <= 1024, is strictly ascending.
+ *      The records, frbch_pa_cand, come sorted by (acc_index, dm_index, h, k).
+ *  A2. Work.  The scratch is allocated once and the table uploaded once per call; the trials are searched in batches: a
+ *      resampled plane with an even number of rows per trial (ndm, and a zero row when ndm is odd) is handed to the kernels of
+ *      the periodicity search as one plane of trials * rows series.  batch_rows bounds the series rows of a batch (a batch
+ *      always holds at least one whole trial and at most 65534 rows); 0 leaves the choice to the library: as many whole
+ *      trials as 2 GiB of per-row scratch hold (10 n + 12 bytes a row: the resampled samples, the work array, the powers, the
+ *      mean, the live word).  The records never depend on batch_rows.  The raw-peak list of step 7 holds 2^20 peaks PER BATCH;
+ *      more is FRBCH_E_CAPACITY, never a cut list -- and that overflow is the one thing that may depend on batch_rows (a
+ *      smaller batch holds fewer peaks).  frbch_pasearch_plan says what a call will do.
+ *  A3. frbch_pa_group_cands (host only) joins the records of one signal across trial DMs and trial accelerations: a and b
+ *      are LINKED iff |dm_index_a - dm_index_b| <= dm_gap and |acc_index_a - acc_index_b| <= acc_gap (both 1..16) and
+ *      2 |k h' - k' h| <= 3 h h' (step 9); groups are the connected components.  `best` has the largest sigma; ties: the
+ *      smaller h, the lower dm_index, the lower acc_index, the smaller k.  Groups come sorted by best.sigma descending, then f
+ *      ascending (exactly: k h' < k' h), then dm_index, then acc_index, then h. */
+typedef struct frbch_pa_cand {
+  uint32_t dm_index, acc_index, h, k;  /* row of the series, trial, fold, bin of the highest summed harmonic               */
+  float power;                         /* H_h[k]                                                                          */
+  uint32_t reserved;
+  double sigma, freq_hz, acc_ms2;      /* of step 8; accs[acc_index]                                                      */
+} frbch_pa_cand;
+
+typedef struct frbch_pa_group {
+  frbch_pa_cand best;
+  uint32_t nmember, dm_index_lo, dm_index_hi, acc_index_lo, acc_index_hi, reserved;
+} frbch_pa_group;
+
+/* Which form the resampler takes for these addresses (host only, nothing runs; only the ADDRESSES are examined): 1 = the
+ * fast form (d_series and d_out 16-byte aligned and nout a multiple of 4, so that every row is aligned: the contiguous input
+ * window of 1024 outputs -- at most 2047 samples, since u steps by 0, 1 or 2 -- is staged through the LDS with 16-byte loads
+ * and the outputs leave in 16-byte stores), 0 = the generic form (a plain gather, one output per thread, any alignment, any
+ * nout), < 0 = refused.  Both give the same bytes.  Inside frbch_pasearch_* d_out is the library's own, aligned, plane. */
+int frbch_resample_kernel(const float* d_series, uint64_t nout, const float* d_out);
+/* Step A0 alone: d_out [nacc][ndm][n] receives r_a of every series for every trial.  n is a power of two in 2^12 .. 2^22 and
+ * at most nout.  kernel_used[1] (may be NULL): the form, as frbch_resample_kernel.  d_series is never written. */
+int frbch_resample_device(const float* d_series, uint32_t ndm, uint64_t nout, uint32_t n, double tsamp_s, const double* accs,
+                          uint32_t nacc, int device, float* d_out, uint32_t* kernel_used, char* err, size_t err_cap);
+int frbch_resample_host(const float* series, uint32_t ndm, uint64_t nout, uint32_t n, double tsamp_s, const double* accs,
+                        uint32_t nacc, int device, float* out, uint32_t* kernel_used, char* err, size_t err_cap);
+/* What frbch_pasearch_* will do for these arguments (host only): *n of step 0, the series rows of a batch (a whole number of
+ * trials, pad rows included), the number of batches and the bytes of device scratch.  Every pointer may be NULL. */
+int frbch_pasearch_plan(uint32_t ndm, uint64_t nout, const frbch_ps_params* params, uint32_t nacc, uint32_t batch_rows,
+                        uint32_t* n, uint32_t* rows_per_batch, uint32_t* nbatch, uint64_t* scratch_bytes, char* err,
+                        size_t err_cap);
+/* The siblings of the three frbch_psearch_* calls.  cands / cap / ncand as there.  kernel_used[3] (may be NULL): the form of
+ * the resampler, the form of the transform, its passes.  d_series holds ndm * nout floats and is never written; like the
+ * other post-filterbank _device entry points the call works on a stream of its own and returns when its work is done.
+ * FRBCH_E_ARG: what frbch_psearch_device refuses; ndm above 65534; nacc outside 1..1024; accs not strictly ascending; a
+ * trial that is not finite or beyond |q| n <= 0.5. */
+int frbch_pasearch_device(const float* d_series, uint32_t ndm, uint64_t nout, const frbch_ps_params* params, const double* accs,
+                          uint32_t nacc, uint32_t batch_rows, int device, frbch_pa_cand* cands, uint64_t cap, uint64_t* ncand,
+                          uint32_t* kernel_used, char* err, size_t err_cap);
+int frbch_pasearch_host(const float* series, uint32_t ndm, uint64_t nout, const frbch_ps_params* params, const double* accs,
+                        uint32_t nacc, uint32_t batch_rows, int device, frbch_pa_cand* cands, uint64_t cap, uint64_t* ncand,
+                        uint32_t* kernel_used, char* err, size_t err_cap);
+int frbch_dedisperse_pasearch_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const double* dms, uint32_t ndm,
+                                   uint32_t zerodm, double clip_sigma, const frbch_ps_params* params, const double* accs,
+                                   uint32_t nacc, uint32_t batch_rows, int device, float* series_out, uint64_t nout,
+                                   uint64_t* nclipped, frbch_pa_cand* cands, uint64_t cap, uint64_t* ncand, uint32_t* kernel_used,
+                                   char* err, size_t err_cap);
+/* Step A3.  More groups than `cap`: FRBCH_E_CAPACITY with *ngroup set (cap = 0 with groups = NULL counts).  FRBCH_E_ARG:
+ * dm_gap or acc_gap outside 1..16, an h other than 1, 2, 4, 8, 16, k = 0. */
+int frbch_pa_group_cands(const frbch_pa_cand* cands, uint64_t ncand, uint32_t dm_gap, uint32_t acc_gap, frbch_pa_group* groups,
+                         uint64_t cap, uint64_t* ngroup, char* err, size_t err_cap);
 
 /* ---- candidates: grouping across DMs, and the two planes a classifier reads -------------------------
  * The search above returns one record per DM for a pulse that stands out at several trial DMs.  frbch_sp_group_cands
