@@ -120,6 +120,33 @@ class FrbchCutoutCand(C.Structure):
                 ("tfactor", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+BURST_STOKES, BURST_COHERENCY = 0, 1
+
+
+class FrbchBurstParams(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("products", C.c_uint32)]
+
+
+class FrbchBurstCand(C.Structure):
+    _fields_ = [("dm", C.c_double), ("sample", C.c_int64), ("width", C.c_uint32), ("off_gap", C.c_uint32),
+                ("off_len", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FrbchBurstSums(C.Structure):
+    _fields_ = [("on_sum", C.c_double), ("off_sum", C.c_double), ("off_sumsq", C.c_double), ("on_hits", C.c_uint32),
+                ("off_hits", C.c_uint32)]
+
+
+class FrbchRmParams(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("nphi", C.c_uint32), ("phi_lo", C.c_double), ("dphi", C.c_double)]
+
+
+class FrbchRmResult(C.Structure):
+    _fields_ = [("rm", C.c_double), ("rm_err", C.c_double), ("peak", C.c_double), ("pa0", C.c_double), ("snr", C.c_double),
+                ("sigma_f", C.c_double), ("fwhm", C.c_double), ("kpeak", C.c_uint32), ("nused", C.c_uint32),
+                ("fitted", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class FrbchRfiParams(C.Structure):
     _fields_ = [("size", C.c_uint32), ("block_rows", C.c_uint32), ("t_cell", C.c_double), ("t_chan", C.c_double),
                 ("chan_frac", C.c_double), ("block_frac", C.c_double)]
@@ -254,6 +281,23 @@ SYMBOLS = {
     "frbch_cutout_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchCutoutParams), _P, C.c_uint32, C.c_int,
                                     _P, _P, _P, _P, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
     "frbch_cutout_kernel": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchCutoutParams), _P, C.c_uint32]),
+    "frbch_burstspec_kernel": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32]),
+    "frbch_burstspec_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32, _P,
+                                         C.c_int, _P, _P, _P, _P, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_burstspec_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32, _P,
+                                       C.c_int, _P, _P, _P, _P, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_rm_table": (C.c_int, [_P]),
+    "frbch_rmsynth_kernel": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint32, C.POINTER(FrbchRmParams), C.POINTER(C.c_uint32)]),
+    "frbch_rmsynth_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, _P, _P, C.c_uint32, C.POINTER(FrbchRmParams), C.c_int, _P, _P,
+                                       C.c_char_p, C.c_size_t]),
+    "frbch_rmsynth_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, _P, _P, C.c_uint32, C.POINTER(FrbchRmParams), C.c_int, _P, _P,
+                                     C.c_char_p, C.c_size_t]),
+    "frbch_rm_peaks": (C.c_int, [C.POINTER(FrbchFilDesc), _P, _P, _P, _P, C.c_uint32, C.POINTER(FrbchRmParams), _P, C.c_char_p,
+                                 C.c_size_t]),
+    "frbch_burst_rm_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32, _P, _P,
+                                        C.POINTER(FrbchRmParams), C.c_int, _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "frbch_burst_rm_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32, _P, _P,
+                                      C.POINTER(FrbchRmParams), C.c_int, _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
     "frbch_rfi_nblk": (C.c_long, [C.c_uint64, C.c_uint32]),
     "frbch_rfi_stats_kernel": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams)]),
     "frbch_rfi_stats_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams), C.c_int, _P,

@@ -3284,3 +3284,580 @@ extern "C" int frbch_cornerturn_host(const char* recipe, const void* frames, siz
   if (!rc && dev_sync(0) != 0) rc = e.fail(FRBCH_E_DEVICE, "sync");
   return rc;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// burst polarisation: spectra of every product, RM synthesis, peaks (include/frbch.h states the arithmetic)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr uint32_t kBurstMaxCand = 4096, kBurstMaxWidth = 65536, kBurstMaxOff = 1u << 20;
+constexpr uint32_t kRmMaxPhi = 1u << 20, kRmMaxChan = 16384, kRmTableN = 16384;
+constexpr uint64_t kRmMaxOut = 1ull << 26;
+constexpr double kRmPhiMax = 1.0e7, kRmC = 299.792458, kRmPi = 3.14159265358979323846;
+
+int burst_check(const frbch_fil_desc* fil, uint64_t nrows, const frbch_burst_params* par, const frbch_burst_cand* cands,
+                uint32_t ncand, const PostErr& e) {
+  const int rc = post_check_fil(fil, nrows, e);
+  if (rc) return rc;
+  if (!par || par->size != sizeof(frbch_burst_params)) return e.fail(FRBCH_E_ARG, "frbch_burst_params: wrong size");
+  if (par->products > FRBCH_BURST_COHERENCY) return e.fail(FRBCH_E_ARG, "products must be 0 (Stokes) or 1 (coherency)");
+  if (par->products == FRBCH_BURST_COHERENCY && fil->nifs != 4) return e.fail(FRBCH_E_ARG, "coherency products need nifs = 4");
+  if (!cands || ncand < 1 || ncand > kBurstMaxCand) return e.fail(FRBCH_E_ARG, "1..4096 candidates");
+  if ((uint64_t)ncand * fil->nchan > kCutTableCap) return e.fail(FRBCH_E_ARG, "ncand * nchan exceeds 2^26: cut the batch into several calls");
+  if ((uint64_t)ncand * fil->nifs > 65535) return e.fail(FRBCH_E_ARG, "ncand * nifs exceeds 65535 (the second grid dimension): cut the batch");
+  if (nrows >= (1ull << 62) || (uint64_t)fil->nchan > 0x7FFFFFFFull / fil->nifs) return e.fail(FRBCH_E_ARG, "too many rows or channels");
+  for (uint32_t i = 0; i < ncand; ++i) {
+    const frbch_burst_cand& c = cands[i];
+    const std::string who = "candidate " + std::to_string(i) + ": ";
+    if (c.width < 1 || c.width > kBurstMaxWidth) return e.fail(FRBCH_E_ARG, who + "width must be 1..65536");
+    if (c.off_len < 2 || c.off_len > kBurstMaxOff) return e.fail(FRBCH_E_ARG, who + "off_len must be 2..2^20");
+    if (!(c.dm >= 0.0) || !(c.dm < 1.0e5)) return e.fail(FRBCH_E_ARG, who + "a DM outside [0, 1e5)");
+    if (c.sample < -(1ll << 62) || c.sample > (1ll << 62)) return e.fail(FRBCH_E_ARG, who + "sample out of range");
+  }
+  return FRBCH_OK;
+}
+
+struct BurstPlan {
+  std::vector<BurstCand> cand;
+  std::vector<int32_t> delays;                   // [ncand][nchan]
+};
+
+int burst_build(const frbch_fil_desc* fil, const frbch_burst_cand* cands, uint32_t ncand, BurstPlan* plan, const PostErr& e) {
+  std::vector<double> dms(ncand);
+  plan->cand.resize(ncand);
+  for (uint32_t i = 0; i < ncand; ++i) {
+    dms[i] = cands[i].dm;
+    BurstCand& b = plan->cand[i];
+    b.on_lo = (long long)cands[i].sample - (long long)(cands[i].width / 2);
+    b.width = cands[i].width; b.off_gap = cands[i].off_gap; b.off_len = cands[i].off_len; b.pad = 0;
+  }
+  int64_t maxd = 0;
+  plan->delays = post_delays(fil, dms.data(), ncand, &maxd);      // n_c(.) of frbch_dedisperse_*: the same function
+  if (maxd > (int64_t)1 << 30) return e.fail(FRBCH_E_ARG, "a dispersion delay of more than 2^30 samples");
+  return FRBCH_OK;
+}
+
+// Which burst-sums kernel a call takes -- the one decision behind frbch_burstspec_device's launch, *kernel_used and
+// frbch_burstspec_kernel's answer.  true = the fast kernel (kernels_post_fast.inc): 8- / 16-bit rows, at most 4 products,
+// whole 64-byte channel tiles, 16-byte pieces of every row (only the ADDRESS of d_rows is examined).  The emulator build
+// has no such kernel: false.
+bool burst_fast_layout(const frbch_fil_desc* fil, const void* d_rows) {
+#ifndef FRBCH_NO_FAST
+  if (fil->nbits != 8 && fil->nbits != 16) return false;
+  const size_t piece = (size_t)fil->nchan * (size_t)(fil->nbits / 8);
+  return fil->nifs <= (uint32_t)fast::kBsMaxIfs && piece % 64 == 0 && ((uintptr_t)d_rows % 16) == 0 && ((size_t)fil->nifs * piece) % 16 == 0;
+#else
+  (void)fil; (void)d_rows;
+  return false;
+#endif
+}
+
+// the launch of step 1 on the scope's stream; `plan` stays alive until the caller has synchronised
+int burst_launch(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const BurstPlan& plan, uint32_t ncand,
+                 BurstSums* d_sums, bool fastk, PostScope& ps, const PostErr& e) {
+  BurstCand* d_cand = nullptr;
+  int32_t* d_dly = nullptr;
+  POST_DEV(ps.alloc(&d_cand, plan.cand.size() * sizeof(BurstCand)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_dly, plan.delays.size() * sizeof(int32_t)), "hipMalloc");
+  POST_DEV(dev_h2d(d_cand, plan.cand.data(), plan.cand.size() * sizeof(BurstCand), ps.s), "upload candidates");
+  POST_DEV(dev_h2d(d_dly, plan.delays.data(), plan.delays.size() * sizeof(int32_t), ps.s), "upload delays");
+  BurstParams p = post_params<BurstParams>(fil, d_rows, nrows);
+  p.ncand = (int)ncand;
+  p.cand = d_cand;
+  p.delays = d_dly;
+  p.sums = d_sums;
+#ifndef FRBCH_NO_FAST
+  if (fastk) {
+    const int bpv = fil->nbits / 8;
+    const dim3 grid((unsigned)((size_t)fil->nchan * bpv / 64), ncand), block(fast::kBsThreads);
+    if (bpv == 1) hipLaunchKernelGGL(fast::frbch_post_burst_sums_fast<1>, grid, block, 0, ps.s, p);
+    else hipLaunchKernelGGL(fast::frbch_post_burst_sums_fast<2>, grid, block, 0, ps.s, p);
+    POST_DEV(dev_check_launch(), "launch burst sums");
+    return FRBCH_OK;
+  }
+#else
+  (void)fastk;
+#endif
+  DEV_LAUNCH(frbch_post_burst_sums, (fil->nchan + 255) / 256, (uint64_t)ncand * fil->nifs, 256, 0, ps.s, p);
+  POST_DEV(dev_check_launch(), "launch burst sums");
+  return FRBCH_OK;
+}
+
+bool rm_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
+bool rm_finitef(float x) { return fabsf(x) <= 3.402823466e38f; }
+
+// spectra, noise and `used` from the sums (host, double, no FMA): step 1 of the header
+void burst_derive(const frbch_fil_desc* fil, uint32_t products, const frbch_burst_sums* sums, uint32_t ncand, const float* gain,
+                  float* spec, float* noise, uint8_t* used) {
+  POST_NO_CONTRACT
+  const size_t nchan = fil->nchan, nifs = fil->nifs;
+  for (uint32_t i = 0; i < ncand; ++i)
+    for (size_t c = 0; c < nchan; ++c) {
+      bool ok = true;
+      for (size_t pr = 0; pr < nifs; ++pr) {
+        const size_t o = ((size_t)i * nifs + pr) * nchan + c;
+        const frbch_burst_sums& s = sums[o];
+        float sp = 0.f, nz = 0.f;
+        if (s.on_hits == 0 || s.off_hits < 2) {
+          ok = false;
+        } else {
+          const double g = gain ? (double)gain[pr * nchan + c] : 1.0;
+          const double non = (double)s.on_hits, noff = (double)s.off_hits;
+          const double mon = s.on_sum / non, moff = s.off_sum / noff;
+          const double d = mon - moff;
+          sp = (float)(d * g);
+          const double ss = s.off_sum * s.off_sum;
+          const double sn = ss / noff;
+          const double num = s.off_sumsq - sn;
+          double var = num / (noff - 1.0);
+          if (var < 0.0) var = 0.0;
+          const double vn = var / non;
+          nz = (float)(sqrt(vn) * fabs(g));
+          if (!rm_finitef(sp) || !rm_finitef(nz)) ok = false;
+        }
+        spec[o] = sp;
+        noise[o] = nz;
+      }
+      if (ok && products == FRBCH_BURST_COHERENCY) {
+        float* s0 = spec + (size_t)i * 4 * nchan + c;
+        float* n0 = noise + (size_t)i * 4 * nchan + c;
+        const float pp = s0[0], qq = s0[nchan], re = s0[2 * nchan], im = s0[3 * nchan];
+        const double npp = (double)n0[0], nqq = (double)n0[nchan];
+        const double a = npp * npp, b = nqq * nqq;
+        const float nq = (float)sqrt(a + b);
+        s0[0] = pp + qq; s0[nchan] = 2.0f * re; s0[2 * nchan] = 2.0f * im; s0[3 * nchan] = pp - qq;
+        n0[nchan] = 2.0f * n0[2 * nchan];             // noise_Q = 2 nRe (before nRe's slot takes noise_U)
+        n0[2 * nchan] = 2.0f * n0[3 * nchan];         // noise_U = 2 nIm
+        n0[0] = nq; n0[3 * nchan] = nq;
+        for (size_t pr = 0; pr < 4; ++pr)
+          if (!rm_finitef(s0[pr * nchan]) || !rm_finitef(n0[pr * nchan])) ok = false;
+      }
+      if (!ok)
+        for (size_t pr = 0; pr < nifs; ++pr) spec[((size_t)i * nifs + pr) * nchan + c] = noise[((size_t)i * nifs + pr) * nchan + c] = 0.f;
+      used[(size_t)i * nchan + c] = ok ? 1 : 0;
+    }
+}
+
+void rm_table_fill(int32_t* C) {
+  POST_NO_CONTRACT
+  for (int j = 0; j < 4096; ++j) {
+    const double x = (2.0 * kRmPi * (double)j) / 16384.0;
+    C[j] = (int32_t)rint(cos(x) * 4194304.0);
+  }
+  C[4096] = 0;
+  for (int j = 4097; j <= 8192; ++j) C[j] = -C[8192 - j];
+  for (int j = 8193; j < 16384; ++j) C[j] = C[16384 - j];
+}
+
+int rm_check(const frbch_fil_desc* fil, uint32_t ncand, const frbch_rm_params* par, const PostErr& e) {
+  POST_NO_CONTRACT
+  const int rc = post_check_fil(fil, 1, e);
+  if (rc) return rc;
+  if (fil->nchan > kRmMaxChan) return e.fail(FRBCH_E_ARG, "more than 16384 channels");
+  if (!(fil->fch1_mhz + (double)(fil->nchan - 1) * fil->foff_mhz > 0)) return e.fail(FRBCH_E_ARG, "a channel frequency that is not positive");
+  if (ncand < 1 || ncand > kBurstMaxCand) return e.fail(FRBCH_E_ARG, "1..4096 candidates");
+  if (!par || par->size != sizeof(frbch_rm_params)) return e.fail(FRBCH_E_ARG, "frbch_rm_params: wrong size");
+  if (par->nphi < 1 || par->nphi > kRmMaxPhi) return e.fail(FRBCH_E_ARG, "nphi must be 1..2^20");
+  if ((uint64_t)ncand * par->nphi > kRmMaxOut) return e.fail(FRBCH_E_ARG, "ncand * nphi exceeds 2^26");
+  if (!(par->dphi > 0) || !rm_finite(par->dphi)) return e.fail(FRBCH_E_ARG, "dphi must be positive and finite");
+  const double hi = par->phi_lo + (double)par->nphi * par->dphi;
+  if (!(fabs(par->phi_lo) <= kRmPhiMax) || !(fabs(hi) <= kRmPhiMax)) return e.fail(FRBCH_E_ARG, "|phi| above 1e7 rad m^-2");
+  return FRBCH_OK;
+}
+
+// The plan rule of the transform -- the one decision behind frbch_rmsynth_device's launches, kernel_used and
+// frbch_rmsynth_kernel's answer.  The fast kernel wants whole waves along k (nphi >= 64) and stores a trial as one 8-byte
+// piece (only the ADDRESS of d_F is examined); a candidate's channels are split until (ncand x k tiles x split) reaches two
+// workgroups per CU, in pieces of at least 64 channels, so that the 64 KiB table a workgroup loads serves at least 65536
+// terms.  The emulator build has no such kernel: generic, split 1.
+struct RmPlanRule { bool fastk; int nsplit, chunk; };
+RmPlanRule rm_plan_rule(uint32_t nchan, uint32_t ncand, uint32_t nphi, const float* d_F) {
+  RmPlanRule r{false, 1, (int)nchan};
+#ifndef FRBCH_NO_FAST
+  if (nphi < 64 || ((uintptr_t)d_F % 8) != 0) return r;
+  r.fastk = true;
+  const uint64_t base = (uint64_t)ncand * ((nphi + fast::kRmThreads * fast::kRmKpt - 1) / (fast::kRmThreads * fast::kRmKpt));
+  if (base < 512) {
+    const uint64_t want = (512 + base - 1) / base, most = (nchan + 63) / 64;
+    const uint32_t ns = (uint32_t)std::min(want, most);
+    r.chunk = (int)((nchan + ns - 1) / ns);
+    r.nsplit = (int)((nchan + (uint32_t)r.chunk - 1) / (uint32_t)r.chunk);
+  }
+#else
+  (void)ncand; (void)nphi; (void)d_F;
+#endif
+  return r;
+}
+
+struct RmPlan {
+  std::vector<RmRec> rec;                        // [ncand][nchan]
+  std::vector<RmCand> cand;
+  std::vector<int32_t> table;
+};
+
+// x 2^64 of the fractional part of x, as the header states it
+uint64_t rm_fix(double x) {
+  POST_NO_CONTRACT
+  const double fr = x - floor(x);
+  const double v = fr * 18446744073709551616.0;
+  if (!(v < 18446744073709551616.0)) return 0;
+  return (uint64_t)v;
+}
+
+std::vector<double> rm_l2(const frbch_fil_desc* fil) {
+  POST_NO_CONTRACT
+  std::vector<double> l2(fil->nchan);
+  for (uint32_t c = 0; c < fil->nchan; ++c) {
+    const double f = fil->fch1_mhz + (double)c * fil->foff_mhz;
+    const double t = kRmC / f;
+    l2[c] = t * t;
+  }
+  return l2;
+}
+
+// the records of step 2 (host): l2, l0, the fixed-point phases, the quantised spectra, inv
+int rm_build(const frbch_fil_desc* fil, const float* q, const float* u, const uint8_t* used, uint32_t ncand, const frbch_rm_params* par,
+             RmPlan* plan, const PostErr& e) {
+  POST_NO_CONTRACT
+  const uint32_t nchan = fil->nchan;
+  const std::vector<double> l2 = rm_l2(fil);
+  plan->rec.assign((size_t)ncand * nchan, RmRec{0, 0, 0ull, 0ull});
+  plan->cand.assign(ncand, RmCand{0u, 0u, 0.0});
+  plan->table.resize(kRmTableN);
+  rm_table_fill(plan->table.data());
+  for (uint32_t i = 0; i < ncand; ++i) {
+    const float* qi = q + (size_t)i * nchan;
+    const float* ui = u + (size_t)i * nchan;
+    const uint8_t* us = used + (size_t)i * nchan;
+    uint32_t N = 0;
+    double sum = 0.0;
+    float m = 0.f;
+    for (uint32_t c = 0; c < nchan; ++c)
+      if (us[c]) {
+        if (!rm_finitef(qi[c]) || !rm_finitef(ui[c]))
+          return e.fail(FRBCH_E_ARG, "candidate " + std::to_string(i) + ": q or u of a used channel is not finite");
+        ++N;
+        sum = sum + l2[c];
+        m = std::max(m, std::max(fabsf(qi[c]), fabsf(ui[c])));
+      }
+    if (N == 0 || m == 0.f) continue;              // F = 0: no records, inv = 0
+    const double l0 = sum / (double)N;
+    int ex = 0;
+    (void)frexp((double)m, &ex);
+    RmRec* rec = plan->rec.data() + (size_t)i * nchan;
+    uint32_t n = 0;
+    for (uint32_t c = 0; c < nchan; ++c)
+      if (us[c]) {
+        const double a = (l2[c] - l0) / kRmPi;
+        RmRec& r = rec[n++];
+        r.qi = (int32_t)rint(ldexp((double)qi[c], 23 - ex));
+        r.ui = (int32_t)rint(ldexp((double)ui[c], 23 - ex));
+        r.p0 = rm_fix(par->phi_lo * a);
+        r.d = rm_fix(par->dphi * a);
+      }
+    plan->cand[i].nrec = n;
+    plan->cand[i].inv = 1.0 / ldexp((double)N, 45 - ex);
+  }
+  return FRBCH_OK;
+}
+
+// the launches of step 2 on the scope's stream; `plan` stays alive until the caller has synchronised
+int rm_launch(const frbch_fil_desc* fil, uint32_t ncand, const frbch_rm_params* par, const RmPlan& plan, float* d_F,
+              PostScope& ps, uint32_t* kernel_used, const PostErr& e) {
+  const RmPlanRule rule = rm_plan_rule(fil->nchan, ncand, par->nphi, d_F);
+  RmRec* d_rec = nullptr;
+  RmCand* d_cand = nullptr;
+  int32_t* d_tab = nullptr;
+  POST_DEV(ps.alloc(&d_rec, plan.rec.size() * sizeof(RmRec)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_cand, plan.cand.size() * sizeof(RmCand)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_tab, (size_t)kRmTableN * sizeof(int32_t)), "hipMalloc");
+  POST_DEV(dev_h2d(d_rec, plan.rec.data(), plan.rec.size() * sizeof(RmRec), ps.s), "upload records");
+  POST_DEV(dev_h2d(d_cand, plan.cand.data(), plan.cand.size() * sizeof(RmCand), ps.s), "upload records");
+  POST_DEV(dev_h2d(d_tab, plan.table.data(), (size_t)kRmTableN * sizeof(int32_t), ps.s), "upload table");
+  RmParams p;
+  memset(&p, 0, sizeof p);
+  p.rec = d_rec; p.cand = d_cand; p.table = d_tab; p.out = d_F;
+  p.nchan = (int)fil->nchan; p.nphi = (int)par->nphi; p.ncand = (int)ncand; p.nsplit = rule.nsplit; p.chunk = rule.chunk;
+  if (kernel_used) { kernel_used[0] = rule.fastk ? 1 : 0; kernel_used[1] = (uint32_t)rule.nsplit; }
+#ifndef FRBCH_NO_FAST
+  if (rule.fastk) {
+    if (rule.nsplit > 1) {
+      long long* d_part = nullptr;
+      POST_DEV(ps.alloc(&d_part, (size_t)rule.nsplit * ncand * par->nphi * 2 * sizeof(long long)), "hipMalloc");
+      p.part = d_part;
+    }
+    const unsigned ktiles = (par->nphi + fast::kRmThreads * fast::kRmKpt - 1) / (fast::kRmThreads * fast::kRmKpt);
+    POST_DEV(launch_lds(fast::frbch_post_rm_fast, dim3(ktiles, (unsigned)rule.nsplit, ncand), dim3(fast::kRmThreads), fast::kRmLds, ps.s, p), "LDS size");
+    POST_DEV(dev_check_launch(), "launch RM synthesis");
+    if (rule.nsplit > 1) {
+      hipLaunchKernelGGL(fast::frbch_post_rm_join, dim3((par->nphi + fast::kRmThreads - 1) / fast::kRmThreads, ncand), dim3(fast::kRmThreads), 0, ps.s, p);
+      POST_DEV(dev_check_launch(), "launch RM join");
+    }
+    return FRBCH_OK;
+  }
+#endif
+  DEV_LAUNCH(frbch_post_rm, (par->nphi + 255) / 256, ncand, 256, 0, ps.s, p);
+  POST_DEV(dev_check_launch(), "launch RM synthesis");
+  return FRBCH_OK;
+}
+
+int rm_peaks_run(const frbch_fil_desc* fil, const float* F, const uint8_t* used, const float* noise_q, const float* noise_u,
+                 uint32_t ncand, const frbch_rm_params* par, frbch_rm_result* res) {
+  POST_NO_CONTRACT
+  const uint32_t nchan = fil->nchan, nphi = par->nphi;
+  const std::vector<double> l2 = rm_l2(fil);
+  for (uint32_t i = 0; i < ncand; ++i) {
+    frbch_rm_result& r = res[i];
+    memset(&r, 0, sizeof r);
+    const float* f = F + (size_t)i * nphi * 2;
+    const uint8_t* us = used + (size_t)i * nchan;
+    auto power = [&](uint32_t k) {
+      const double re = (double)f[2 * (size_t)k], im = (double)f[2 * (size_t)k + 1];
+      const double a = re * re, b = im * im;
+      return a + b;
+    };
+    uint32_t kp = 0;
+    double best = power(0);
+    for (uint32_t k = 1; k < nphi; ++k) {
+      const double v = power(k);
+      if (v > best) { best = v; kp = k; }
+    }
+    r.kpeak = kp;
+    r.rm = par->phi_lo + (double)kp * par->dphi;
+    r.peak = sqrt(best);
+    if (kp > 0 && kp + 1 < nphi) {
+      const double ym = power(kp - 1), yp = power(kp + 1);
+      const double den = (ym - 2.0 * best) + yp;
+      if (den < 0.0) {
+        const double diff = ym - yp;
+        const double delta = (0.5 * diff) / den;
+        r.rm = par->phi_lo + ((double)kp + delta) * par->dphi;
+        const double corr = (0.25 * diff) * delta;
+        r.peak = sqrt(best - corr);
+        r.fitted = 1;
+      }
+    }
+    r.pa0 = atan2((double)f[2 * (size_t)kp + 1], (double)f[2 * (size_t)kp]) / 2.0;
+    uint32_t N = 0;
+    double lo = 0.0, hi = 0.0, acc = 0.0;
+    for (uint32_t c = 0; c < nchan; ++c)
+      if (us[c]) {
+        if (!N || l2[c] < lo) lo = l2[c];
+        if (!N || l2[c] > hi) hi = l2[c];
+        ++N;
+        if (noise_q && noise_u) {
+          const double nq = (double)noise_q[(size_t)i * nchan + c], nu = (double)noise_u[(size_t)i * nchan + c];
+          const double a = nq * nq, b = nu * nu;
+          acc = acc + (a + b);
+        }
+      }
+    r.nused = N;
+    if (N) r.sigma_f = sqrt(acc / 2.0) / (double)N;
+    if (r.sigma_f > 0.0) r.snr = sqrt(best) / r.sigma_f;
+    if (hi > lo) r.fwhm = (2.0 * sqrt(3.0)) / (hi - lo);
+    if (r.snr > 0.0) r.rm_err = r.fwhm / (2.0 * r.snr);
+  }
+  return FRBCH_OK;
+}
+
+}  // namespace
+
+extern "C" int frbch_burstspec_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* par,
+                                      const frbch_burst_cand* cands, uint32_t ncand) try {
+  PostErr e{nullptr, 0};
+  int rc = burst_check(fil, nrows, par, cands, ncand, e);
+  if (rc) return rc;
+  if (!d_rows) return FRBCH_E_ARG;
+  BurstPlan plan;
+  rc = burst_build(fil, cands, ncand, &plan, e);
+  return rc ? rc : (burst_fast_layout(fil, d_rows) ? 1 : 0);
+} catch (const std::bad_alloc&) { return FRBCH_E_NOMEM; }
+
+namespace {
+// step 1 inside a scope: the sums into d_sums, then host copies of sums, spectra, noise and `used` (all synchronised)
+int burst_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* par,
+              const frbch_burst_cand* cands, uint32_t ncand, const float* gain, BurstSums* d_sums, PostScope& ps,
+              std::vector<frbch_burst_sums>* sums, float* spec, float* noise, uint8_t* used, uint32_t* kernel_used, const PostErr& e) {
+  BurstPlan plan;
+  int rc = burst_build(fil, cands, ncand, &plan, e);
+  if (rc) return rc;
+  const bool fastk = burst_fast_layout(fil, d_rows);
+  if ((rc = burst_launch(fil, d_rows, nrows, plan, ncand, d_sums, fastk, ps, e)) != 0) return rc;
+  const size_t n = (size_t)ncand * fil->nifs * fil->nchan;
+  sums->resize(n);
+  POST_DEV(dev_d2h(sums->data(), d_sums, n * sizeof(frbch_burst_sums), ps.s), "download sums");
+  POST_DEV(dev_sync(ps.s), "sync");
+  burst_derive(fil, par->products, sums->data(), ncand, gain, spec, noise, used);
+  if (kernel_used) *kernel_used = fastk ? 1 : 0;
+  return FRBCH_OK;
+}
+}  // namespace
+
+extern "C" int frbch_burstspec_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* par,
+                                      const frbch_burst_cand* cands, uint32_t ncand, const float* gain, int device,
+                                      frbch_burst_sums* d_sums, float* spec, float* noise, uint8_t* used, uint32_t* kernel_used,
+                                      char* err, size_t err_cap) try {
+  static_assert(sizeof(BurstSums) == sizeof(frbch_burst_sums) && sizeof(BurstSums) == 32, "frbch_burst_sums");
+  PostErr e{err, err_cap};
+  int rc = burst_check(fil, nrows, par, cands, ncand, e);
+  if (rc) return rc;
+  if (!d_rows || !d_sums) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  const size_t n = (size_t)ncand * fil->nifs * fil->nchan;
+  std::vector<frbch_burst_sums> sums;
+  std::vector<float> sp(n), nz(n);
+  std::vector<uint8_t> us((size_t)ncand * fil->nchan);
+  DeviceGuard dg(device);
+  PostScope ps;
+  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  rc = burst_run(fil, d_rows, nrows, par, cands, ncand, gain, (BurstSums*)d_sums, ps, &sums, sp.data(), nz.data(), us.data(), kernel_used, e);
+  if (rc) return rc;
+  if (spec) memcpy(spec, sp.data(), n * sizeof(float));
+  if (noise) memcpy(noise, nz.data(), n * sizeof(float));
+  if (used) memcpy(used, us.data(), us.size());
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_burstspec_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* par,
+                                    const frbch_burst_cand* cands, uint32_t ncand, const float* gain, int device,
+                                    frbch_burst_sums* sums, float* spec, float* noise, uint8_t* used, uint32_t* kernel_used,
+                                    char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  int rc = burst_check(fil, nrows, par, cands, ncand, e);
+  if (rc) return rc;
+  if (!rows) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
+  const size_t nb = (size_t)ncand * fil->nifs * fil->nchan * sizeof(frbch_burst_sums);
+  frbch_burst_sums* d_sums = sums ? hs.out(sums, nb) : (frbch_burst_sums*)hs.scratch(nb);
+  return hs.run(e, "device memory for the rows and the sums", "upload rows", "download sums", [&]() {
+    return frbch_burstspec_device(fil, d_rows, nrows, par, cands, ncand, gain, device, d_sums, spec, noise, used, kernel_used, err, err_cap);
+  });
+}
+
+extern "C" int frbch_rm_table(int32_t* out) {
+  if (!out) return FRBCH_E_ARG;
+  rm_table_fill(out);
+  return FRBCH_OK;
+}
+
+extern "C" int frbch_rmsynth_kernel(const frbch_fil_desc* fil, const float* d_F, uint32_t ncand, const frbch_rm_params* par,
+                                    uint32_t* nsplit) {
+  PostErr e{nullptr, 0};
+  const int rc = rm_check(fil, ncand, par, e);
+  if (rc) return rc;
+  if (!d_F) return FRBCH_E_ARG;
+  const RmPlanRule rule = rm_plan_rule(fil->nchan, ncand, par->nphi, d_F);
+  if (nsplit) *nsplit = (uint32_t)rule.nsplit;
+  return rule.fastk ? 1 : 0;
+}
+
+extern "C" int frbch_rmsynth_device(const frbch_fil_desc* fil, const float* d_q, const float* d_u, const uint8_t* d_used,
+                                    uint32_t ncand, const frbch_rm_params* par, int device, float* d_F, uint32_t* kernel_used,
+                                    char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  int rc = rm_check(fil, ncand, par, e);
+  if (rc) return rc;
+  if (!d_q || !d_u || !d_used || !d_F) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  const size_t n = (size_t)ncand * fil->nchan;
+  std::vector<float> q(n), u(n);
+  std::vector<uint8_t> used(n);
+  RmPlan plan;
+  DeviceGuard dg(device);
+  PostScope ps;
+  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  POST_DEV(dev_d2h(q.data(), d_q, n * sizeof(float), ps.s), "download q");
+  POST_DEV(dev_d2h(u.data(), d_u, n * sizeof(float), ps.s), "download u");
+  POST_DEV(dev_d2h(used.data(), d_used, n, ps.s), "download used");
+  POST_DEV(dev_sync(ps.s), "sync");
+  if ((rc = rm_build(fil, q.data(), u.data(), used.data(), ncand, par, &plan, e)) != 0) return rc;
+  if ((rc = rm_launch(fil, ncand, par, plan, d_F, ps, kernel_used, e)) != 0) return rc;
+  POST_DEV(dev_sync(ps.s), "sync");         // (the host vectors the uploads read stay alive until here)
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_rmsynth_host(const frbch_fil_desc* fil, const float* q, const float* u, const uint8_t* used, uint32_t ncand,
+                                  const frbch_rm_params* par, int device, float* F, uint32_t* kernel_used, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  int rc = rm_check(fil, ncand, par, e);
+  if (rc) return rc;
+  if (!q || !u || !used || !F) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  const size_t n = (size_t)ncand * fil->nchan;
+  HostStage hs;
+  const float* d_q = hs.in(q, n * sizeof(float));
+  const float* d_u = hs.in(u, n * sizeof(float));
+  const uint8_t* d_used = hs.in(used, n);
+  float* d_F = hs.out(F, (size_t)ncand * par->nphi * 2 * sizeof(float));
+  return hs.run(e, "device memory for the spectra and F", "upload spectra", "download F",
+                [&]() { return frbch_rmsynth_device(fil, d_q, d_u, d_used, ncand, par, device, d_F, kernel_used, err, err_cap); });
+}
+
+extern "C" int frbch_rm_peaks(const frbch_fil_desc* fil, const float* F, const uint8_t* used, const float* noise_q, const float* noise_u,
+                              uint32_t ncand, const frbch_rm_params* par, frbch_rm_result* results, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  const int rc = rm_check(fil, ncand, par, e);
+  if (rc) return rc;
+  if (!F || !used || !results) return e.fail(FRBCH_E_ARG, "null argument");
+  return rm_peaks_run(fil, F, used, noise_q, noise_u, ncand, par, results);
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_burst_rm_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                     const frbch_burst_cand* cands, uint32_t ncand, const float* gain, const uint8_t* flag,
+                                     const frbch_rm_params* par, int device, float* spec, float* noise, uint8_t* used, float* F,
+                                     frbch_rm_result* results, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  int rc = burst_check(fil, nrows, bpar, cands, ncand, e);
+  if (rc) return rc;
+  if (fil->nifs != 4) return e.fail(FRBCH_E_ARG, "the composite needs the four products of a full-Stokes file (nifs = 4)");
+  if ((rc = rm_check(fil, ncand, par, e)) != 0) return rc;
+  if (!d_rows || !spec || !noise || !used || !F || !results) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  const size_t nchan = fil->nchan, n = (size_t)ncand * nchan;
+  std::vector<frbch_burst_sums> sums;
+  std::vector<float> q(n), u(n), nq(n), nu(n);
+  RmPlan plan;
+  uint32_t k1 = 0, k2[2] = {0, 1};
+  DeviceGuard dg(device);
+  PostScope ps;
+  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  BurstSums* d_sums = nullptr;
+  float* d_F = nullptr;
+  POST_DEV(ps.alloc(&d_sums, n * 4 * sizeof(BurstSums)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_F, (size_t)ncand * par->nphi * 2 * sizeof(float)), "hipMalloc");
+  if ((rc = burst_run(fil, d_rows, nrows, bpar, cands, ncand, gain, d_sums, ps, &sums, spec, noise, used, &k1, e)) != 0) return rc;
+  for (uint32_t i = 0; i < ncand; ++i)
+    for (size_t c = 0; c < nchan; ++c) {
+      if (flag && flag[c]) used[i * nchan + c] = 0;
+      q[i * nchan + c] = spec[((size_t)i * 4 + 1) * nchan + c];
+      u[i * nchan + c] = spec[((size_t)i * 4 + 2) * nchan + c];
+      nq[i * nchan + c] = noise[((size_t)i * 4 + 1) * nchan + c];
+      nu[i * nchan + c] = noise[((size_t)i * 4 + 2) * nchan + c];
+    }
+  if ((rc = rm_build(fil, q.data(), u.data(), used, ncand, par, &plan, e)) != 0) return rc;
+  if ((rc = rm_launch(fil, ncand, par, plan, d_F, ps, k2, e)) != 0) return rc;
+  POST_DEV(dev_d2h(F, d_F, (size_t)ncand * par->nphi * 2 * sizeof(float), ps.s), "download F");
+  POST_DEV(dev_sync(ps.s), "sync");
+  if (kernel_used) { kernel_used[0] = k1; kernel_used[1] = k2[0]; kernel_used[2] = k2[1]; }
+  return rm_peaks_run(fil, F, used, nq.data(), nu.data(), ncand, par, results);
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_burst_rm_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                   const frbch_burst_cand* cands, uint32_t ncand, const float* gain, const uint8_t* flag,
+                                   const frbch_rm_params* par, int device, float* spec, float* noise, uint8_t* used, float* F,
+                                   frbch_rm_result* results, uint32_t* kernel_used, char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  int rc = burst_check(fil, nrows, bpar, cands, ncand, e);
+  if (rc) return rc;
+  if (!rows) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
+  return hs.run(e, "device memory for the rows", "upload rows", "download", [&]() {
+    return frbch_burst_rm_device(fil, d_rows, nrows, bpar, cands, ncand, gain, flag, par, device, spec, noise, used, F, results, kernel_used, err, err_cap);
+  });
+}

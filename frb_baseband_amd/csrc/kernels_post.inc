@@ -1079,3 +1079,132 @@ KERNEL(frbch_post_resample, ResParams) {
     }
   }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Burst polarisation (frbch_burstspec_*, frbch_rmsynth_*; include/frbch.h states the arithmetic).  The sums of a burst's
+// three windows for every (candidate, product, channel), and the integer transform of Q and U over the Faraday depths.
+// The kernels below are the generic forms; the fast forms (kernels_post_fast.inc) give the same bits.
+// ---------------------------------------------------------------------------------------------------------------------
+struct BurstCand {
+  long long on_lo;             // first on-pulse row at the top of the band: sample - width / 2 (may be negative)
+  uint32_t width, off_gap, off_len, pad;
+};
+struct BurstSums { double on_sum, off_sum, off_sumsq; uint32_t on_hits, off_hits; };   // frbch_burst_sums
+struct BurstParams {
+  const uint8_t* rows;         // [nrows][nifs][nchan] samples of `nbits`; every product is read
+  uint64_t nrows;
+  int nchan, nifs, nbits, ncand;
+  const BurstCand* cand;       // [ncand]
+  const int32_t* delays;       // [ncand][nchan]
+  BurstSums* sums;             // [ncand][nifs][nchan]
+};
+
+// window w of a candidate in ascending row order: 0 = the earlier off-pulse window, 1 = on-pulse, 2 = the later off-pulse window
+DEVFN inline void burst_window(const BurstCand& cd, int w, long long* w0, uint32_t* len) {
+  if (w == 0) { *w0 = cd.on_lo - (long long)cd.off_gap - (long long)cd.off_len; *len = cd.off_len; }
+  else if (w == 1) { *w0 = cd.on_lo; *len = cd.width; }
+  else { *w0 = cd.on_lo + (long long)cd.width + (long long)cd.off_gap; *len = cd.off_len; }
+}
+// present rows of window [w0, w0 + len) read at delay n: [lo, hi) of the file
+DEVFN inline void burst_clip(long long w0, uint32_t len, long long n, long long nrows, long long* lo, long long* hi) {
+  long long a = w0 + n, b = w0 + n + (long long)len;
+  if (a < 0) a = 0;
+  if (b > nrows) b = nrows;
+  if (b < a) b = a;
+  *lo = a;
+  *hi = b;
+}
+
+// grid (ceil(nchan / 256), ncand * nifs), one thread per (candidate, product, channel), rows ascending
+KERNEL(frbch_post_burst_sums, BurstParams) {
+  K_PROLOGUE;
+  (void)smem;
+  PHASE {
+    POST_NO_CONTRACT
+    const int c = bx * nthr + tid;
+    const int cand = by / p.nifs, pr = by - cand * p.nifs;
+    if (c < p.nchan) {
+      const BurstCand cd = p.cand[cand];
+      const long long n = (long long)p.delays[(size_t)cand * p.nchan + c];
+      const uint64_t pitch = (uint64_t)p.nifs * (uint64_t)p.nchan;
+      const uint64_t first = (uint64_t)pr * (uint64_t)p.nchan + (uint64_t)c;
+      unsigned long long si[2] = {0, 0}, qi = 0;       // [0] on, [1] off
+      double sf[2] = {0.0, 0.0}, qf = 0.0;
+      uint32_t hits[2] = {0, 0};
+      for (int w = 0; w < 3; ++w) {
+        long long w0, lo, hi;
+        uint32_t len;
+        burst_window(cd, w, &w0, &len);
+        burst_clip(w0, len, n, (long long)p.nrows, &lo, &hi);
+        const int a = w == 1 ? 0 : 1;
+        hits[a] += (uint32_t)(hi - lo);
+        if (p.nbits == 32) {
+          const float* x = (const float*)p.rows;
+          for (long long t = lo; t < hi; ++t) {
+            const double v = (double)x[(uint64_t)t * pitch + first];
+            const double vv = v * v;
+            sf[a] = sf[a] + v;
+            if (a) qf = qf + vv;
+          }
+        } else {
+          for (long long t = lo; t < hi; ++t) {
+            const unsigned long long v = p.nbits == 8 ? (unsigned long long)p.rows[(uint64_t)t * pitch + first]
+                                                      : (unsigned long long)((const uint16_t*)p.rows)[(uint64_t)t * pitch + first];
+            si[a] += v;
+            if (a) qi += v * v;
+          }
+        }
+      }
+      BurstSums o;
+      o.on_sum = p.nbits == 32 ? sf[0] : (double)si[0];
+      o.off_sum = p.nbits == 32 ? sf[1] : (double)si[1];
+      o.off_sumsq = p.nbits == 32 ? qf : (double)qi;
+      o.on_hits = hits[0];
+      o.off_hits = hits[1];
+      p.sums[((size_t)cand * p.nifs + pr) * p.nchan + c] = o;
+    }
+  }
+}
+
+struct RmRec { int32_t qi, ui; unsigned long long p0, d; };    // one used channel of a candidate: 24 bytes
+struct RmCand { uint32_t nrec, pad; double inv; };             // used channels (the records are packed); inv_i of the rule
+struct RmParams {
+  const RmRec* rec;            // [ncand][nchan], the first nrec of a candidate are its used channels in ascending c
+  const RmCand* cand;          // [ncand]
+  const int32_t* table;        // C[16384]
+  float* out;                  // [ncand][nphi][2]
+  long long* part;             // fast kernel with nsplit > 1: [nsplit][ncand][nphi][2]
+  int nchan, nphi, ncand, nsplit, chunk, pad;
+};
+
+// one term of the transform: the table index of phase ph, and the four products
+DEVFN inline void rm_term(const int32_t* tab, unsigned long long ph, int32_t qi, int32_t ui, long long* re, long long* im) {
+  const int j = (int)(((ph + (1ull << 49)) >> 50) & 16383ull);
+  const long long cj = tab[j], sj = tab[(j - 4096) & 16383];
+  *re += (long long)qi * cj + (long long)ui * sj;
+  *im += (long long)ui * cj - (long long)qi * sj;
+}
+DEVFN inline void rm_store(float* out, long long re, long long im, double inv) {
+  POST_NO_CONTRACT
+  out[0] = (float)((double)re * inv);
+  out[1] = (float)((double)im * inv);
+}
+
+// grid (ceil(nphi / 256), ncand), one thread per (candidate, trial), channels ascending, the table in global memory
+KERNEL(frbch_post_rm, RmParams) {
+  K_PROLOGUE;
+  (void)smem;
+  PHASE {
+    const int k = bx * nthr + tid;
+    if (k < p.nphi) {
+      const RmCand cd = p.cand[by];
+      const RmRec* rec = p.rec + (size_t)by * p.nchan;
+      long long re = 0, im = 0;
+      for (uint32_t r = 0; r < cd.nrec; ++r) {
+        const RmRec rc = rec[r];
+        rm_term(p.table, rc.p0 + rc.d * (unsigned long long)k, rc.qi, rc.ui, &re, &im);
+      }
+      rm_store(p.out + ((size_t)by * p.nphi + k) * 2, re, im, cd.inv);
+    }
+  }
+}

@@ -880,4 +880,220 @@ __global__ void __launch_bounds__(kResThreads) frbch_post_resample_lds(ResParams
   }
   *dst = make_float4(v[0], v[1], v[2], v[3]);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Burst sums (HIP only; frbch_post_burst_sums of kernels_post.inc stays the emulable form, the fallback and the kernel of
+// float rows).  A workgroup of 256 threads owns one candidate and one 64-byte tile of the row: 4 lanes side by side take the
+// 16-byte pieces of a row (16 / 8 channels of 8- / 16-bit samples) of ALL nifs products in one trip, the 64 lane groups
+// take interleaved rows (group g: rows g, g + 64, ...), so the rows of a window are split across the four waves.  The
+// delays differ per channel: for a window [w0, w0 + len) the workgroup walks the rows w0 + dmin .. w0 + len - 1 + dmax of
+// its tile (dmin / dmax over the tile's channels, clipped to the file) and a channel takes a row iff the row minus its own
+// delay falls into the window -- one subtraction and one unsigned compare.  Partials are uint32 over runs of kBsRun rows
+// per lane (16 lanes x 256 rows x 65535 < 2^32; the squares of 16-bit samples are uint64 throughout); after every run the
+// 16 lanes of a wave that share a piece add theirs up by shuffles and one lane per piece adds the 64-bit result to the
+// workgroup's totals in the LDS.  At the end ONE thread per (product, channel) computes the hits -- they need no data -- and
+// stores the record: no global atomics.  Integer sums are exact in any order: the result equals the generic kernel's.
+// All row arithmetic is 64 bit.  grid (row bytes / 64, ncand).
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int kBsThreads = 256, kBsGroups = 64, kBsRun = 256, kBsMaxIfs = 4;
+
+template <class T> __device__ __forceinline__ T bs_wave_sum(T v) {       // over the 16 lanes of a wave with equal lane & 3
+  v += __shfl_xor(v, 4);
+  v += __shfl_xor(v, 8);
+  v += __shfl_xor(v, 16);
+  v += __shfl_xor(v, 32);
+  return v;
+}
+
+template <int BPV>
+__global__ void __launch_bounds__(kBsThreads) frbch_post_burst_sums_fast(BurstParams p) {
+  constexpr int VPL = 16 / BPV, CT = 64 / BPV;
+  __shared__ unsigned long long tot[3][kBsMaxIfs][CT];                     // on_sum, off_sum, off_sumsq
+  const int tid = threadIdx.x, l = tid & 3, g = tid >> 2;
+  const int tile = blockIdx.x, cand = blockIdx.y;
+  for (int i = tid; i < 3 * kBsMaxIfs * CT; i += kBsThreads) (&tot[0][0][0])[i] = 0ull;
+  const BurstCand cd = p.cand[cand];
+  const int32_t* dly = p.delays + (size_t)cand * p.nchan + (size_t)tile * CT + (size_t)l * VPL;
+  int dk[VPL];
+  int dmin = INT32_MAX, dmax = 0;
+#pragma unroll
+  for (int k = 0; k < VPL; ++k) {
+    dk[k] = dly[k];
+    dmin = min(dmin, dk[k]);
+    dmax = max(dmax, dk[k]);
+  }
+  dmin = min(dmin, __shfl_xor(dmin, 1)); dmin = min(dmin, __shfl_xor(dmin, 2));      // over the four pieces of the tile:
+  dmax = max(dmax, __shfl_xor(dmax, 1)); dmax = max(dmax, __shfl_xor(dmax, 2));      // the same in every thread
+#pragma unroll
+  for (int k = 0; k < VPL; ++k) dk[k] -= dmin;
+  const size_t stride = (size_t)p.nifs * p.nchan * BPV, pstride = (size_t)p.nchan * BPV;
+  const unsigned char* src = p.rows + (size_t)tile * 64 + (size_t)l * 16;
+  const long long nrows = (long long)p.nrows;
+  __syncthreads();
+  for (int w = 0; w < 3; ++w) {
+    long long w0;
+    uint32_t len;
+    burst_window(cd, w, &w0, &len);
+    const long long base = w0 + dmin;
+    const long long first = base < 0 ? 0 : base;
+    long long last = base + (long long)len - 1 + (long long)(dmax - dmin);
+    if (last > nrows - 1) last = nrows - 1;
+    const int qa = w == 1 ? 0 : 1;
+    for (long long ch0 = first; ch0 <= last; ch0 += (long long)kBsGroups * kBsRun) {
+      long long ce = ch0 + (long long)kBsGroups * kBsRun - 1;
+      if (ce > last) ce = last;
+      uint32_t s[kBsMaxIfs][VPL];
+      uint32_t q8[kBsMaxIfs][BPV == 1 ? VPL : 1];
+      unsigned long long q16[kBsMaxIfs][BPV == 2 ? VPL : 1];
+#pragma unroll
+      for (int pr = 0; pr < kBsMaxIfs; ++pr)
+#pragma unroll
+        for (int k = 0; k < VPL; ++k) {
+          s[pr][k] = 0u;
+          if constexpr (BPV == 1) q8[pr][k] = 0u; else q16[pr][k] = 0ull;
+        }
+      for (long long r = ch0 + g; r <= ce; r += kBsGroups) {
+        const int rr = (int)(r - base);
+        uint32_t wv[kBsMaxIfs][4];
+#pragma unroll
+        for (int pr = 0; pr < kBsMaxIfs; ++pr)
+          if (pr < p.nifs) {
+            const uint4 v = *reinterpret_cast<const uint4*>(src + (size_t)r * stride + (size_t)pr * pstride);
+            wv[pr][0] = v.x; wv[pr][1] = v.y; wv[pr][2] = v.z; wv[pr][3] = v.w;
+          }
+#pragma unroll
+        for (int k = 0; k < VPL; ++k) {
+          const bool in = (uint32_t)(rr - dk[k]) < len;
+#pragma unroll
+          for (int pr = 0; pr < kBsMaxIfs; ++pr)
+            if (pr < p.nifs) {
+              if constexpr (BPV == 1) {
+                const uint32_t x = in ? (wv[pr][k >> 2] >> (8 * (k & 3))) & 0xFFu : 0u;
+                s[pr][k] += x;
+                q8[pr][k] += x * x;
+              } else {
+                const uint32_t x = in ? (wv[pr][k >> 1] >> (16 * (k & 1))) & 0xFFFFu : 0u;
+                s[pr][k] += x;
+                q16[pr][k] += (unsigned long long)(x * x);
+              }
+            }
+        }
+      }
+      // (every thread of the workgroup makes the same trips through both outer loops: the shuffles meet whole waves)
+#pragma unroll
+      for (int pr = 0; pr < kBsMaxIfs; ++pr)
+        if (pr < p.nifs) {
+#pragma unroll
+          for (int k = 0; k < VPL; ++k) {
+            const unsigned long long ss = (unsigned long long)bs_wave_sum(s[pr][k]);
+            unsigned long long qq;
+            if constexpr (BPV == 1) qq = (unsigned long long)bs_wave_sum(q8[pr][k]); else qq = bs_wave_sum(q16[pr][k]);
+            if ((tid & 63) < 4) {
+              atomicAdd(&tot[qa][pr][l * VPL + k], ss);
+              if (qa) atomicAdd(&tot[2][pr][l * VPL + k], qq);
+            }
+          }
+        }
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < p.nifs * CT; i += kBsThreads) {
+    const int pr = i / CT, ch = i - pr * CT, c = tile * CT + ch;
+    const long long n = (long long)p.delays[(size_t)cand * p.nchan + c];
+    uint32_t hits[2] = {0u, 0u};
+    for (int w = 0; w < 3; ++w) {
+      long long w0, lo, hi;
+      uint32_t len;
+      burst_window(cd, w, &w0, &len);
+      burst_clip(w0, len, n, nrows, &lo, &hi);
+      hits[w == 1 ? 0 : 1] += (uint32_t)(hi - lo);
+    }
+    BurstSums o;
+    o.on_sum = (double)tot[0][pr][ch];
+    o.off_sum = (double)tot[1][pr][ch];
+    o.off_sumsq = (double)tot[2][pr][ch];
+    o.on_hits = hits[0];
+    o.off_hits = hits[1];
+    p.sums[((size_t)cand * p.nifs + pr) * p.nchan + c] = o;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// RM synthesis (HIP only; frbch_post_rm of kernels_post.inc stays the emulable form and the fallback; both call rm_term, so
+// they differ in schedule only).  The 64 KiB table lies in the LDS once per workgroup; lanes run along k, kRmKpt trials
+// 256 apart per thread, so that a record -- staged through the LDS in tiles of kRmTile, read at one address by the whole
+// wave -- serves 1024 terms: one 64 x 32 bit product for the first phase, then an addition of 256 D per further trial, two
+// table reads and four 32 x 32 + 64 bit multiply-adds per term.  blockIdx.y splits a candidate's records in pieces of
+// `chunk`; with nsplit > 1 the int64 partials go to p.part and frbch_post_rm_join adds them up (exact in any order), with
+// nsplit = 1 the kernel stores F itself.  grid (ceil(nphi / 1024), nsplit, ncand).
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int kRmThreads = 256, kRmKpt = 4, kRmTile = 256;
+constexpr size_t kRmLds = 65536 + (size_t)kRmTile * sizeof(RmRec);
+
+// rm_store's values as one 8-byte store (the host takes this kernel for an 8-byte aligned F only)
+__device__ __forceinline__ void rm_store2(float* out, long long re, long long im, double inv) {
+  POST_NO_CONTRACT
+  float2 v;
+  v.x = (float)((double)re * inv);
+  v.y = (float)((double)im * inv);
+  *reinterpret_cast<float2*>(out) = v;
+}
+
+__global__ void __launch_bounds__(kRmThreads) frbch_post_rm_fast(RmParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  int32_t* tab = reinterpret_cast<int32_t*>(smem);
+  RmRec* recs = reinterpret_cast<RmRec*>(smem + 65536);
+  const int tid = threadIdx.x, cand = blockIdx.z, split = blockIdx.y;
+  const int k0 = (int)blockIdx.x * (kRmThreads * kRmKpt) + tid;
+  for (int i = tid; i < 4096; i += kRmThreads) reinterpret_cast<int4*>(tab)[i] = reinterpret_cast<const int4*>(p.table)[i];
+  const RmCand cd = p.cand[cand];
+  const int r0 = split * p.chunk;
+  const int r1 = min(r0 + p.chunk, (int)cd.nrec);
+  long long re[kRmKpt], im[kRmKpt];
+#pragma unroll
+  for (int j = 0; j < kRmKpt; ++j) re[j] = im[j] = 0;
+  for (int t0 = r0; t0 < r1; t0 += kRmTile) {
+    const int n = min(kRmTile, r1 - t0);
+    __syncthreads();                                                       // the previous tile is consumed
+    const uint32_t* srcw = reinterpret_cast<const uint32_t*>(p.rec + (size_t)cand * p.nchan + t0);
+    for (int i = tid; i < n * 6; i += kRmThreads) reinterpret_cast<uint32_t*>(recs)[i] = srcw[i];
+    __syncthreads();                                                       // (the first one covers the table as well)
+    for (int r = 0; r < n; ++r) {
+      const RmRec rc = recs[r];
+      unsigned long long ph = rc.p0 + rc.d * (unsigned long long)(uint32_t)k0;
+      const unsigned long long step = rc.d << 8;                           // kRmThreads D
+#pragma unroll
+      for (int j = 0; j < kRmKpt; ++j) {
+        rm_term(tab, ph, rc.qi, rc.ui, &re[j], &im[j]);
+        ph += step;
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < kRmKpt; ++j) {
+    const int k = k0 + j * kRmThreads;
+    if (k < p.nphi) {
+      if (p.nsplit == 1) {
+        rm_store2(p.out + ((size_t)cand * p.nphi + k) * 2, re[j], im[j], cd.inv);
+      } else {
+        long long* o = p.part + (((size_t)split * p.ncand + cand) * p.nphi + k) * 2;
+        o[0] = re[j];
+        o[1] = im[j];
+      }
+    }
+  }
+}
+
+// grid (ceil(nphi / 256), ncand): the partials of the splits, added in ascending split
+__global__ void __launch_bounds__(kRmThreads) frbch_post_rm_join(RmParams p) {
+  const int k = (int)blockIdx.x * kRmThreads + (int)threadIdx.x, cand = blockIdx.y;
+  if (k >= p.nphi) return;
+  long long re = 0, im = 0;
+  for (int s = 0; s < p.nsplit; ++s) {
+    const long long* o = p.part + (((size_t)s * p.ncand + cand) * p.nphi + k) * 2;
+    re += o[0];
+    im += o[1];
+  }
+  rm_store2(p.out + ((size_t)cand * p.nphi + k) * 2, re, im, p.cand[cand].inv);
+}
 }  // namespace fast

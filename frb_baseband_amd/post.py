@@ -25,6 +25,10 @@ reference's `dspsr -E <par> ... <IFall.fil>` stage) of SIGPROC filterbank files,
 * ``resident=True`` (``--resident``) of ``search_fil``, ``candidates_fil`` and ``rfifind_fil``: the rows cross to the device
   once per command and stay there from flagging to cut-outs (``candidates_resident``: frbch_candidates_host; ``cleanp``:
   frbch_rfi_cleanp_host); the files and the returned values are those of the default path, byte for byte.
+* ``rmsynth_fil`` (``post rmsynth``) answers what a full-Stokes file is written for: the on-pulse minus off-pulse spectra of all
+  four products of every burst (``burst_spectra``: frbch_burstspec_host), the Faraday dispersion function of Q and U by an
+  integer, bit-reproducible transform (``rm_synthesis``: frbch_rmsynth_host), its peak -- the rotation measure -- with PA0,
+  L/I and V/I (``rm_peaks``), or all of it on rows uploaded once (``burst_rm``: frbch_burst_rm_host).
 There is no CPU fallback: the sums run in libfrbch.so on a gfx950 device.
 """
 from __future__ import annotations
@@ -1755,12 +1759,281 @@ def _fold_par(fil, filterbankfile, par, nbin, subint_s, fscrunch_to, device, lib
     return base + ".ar", profile
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# burst polarisation: spectra of every product, RM synthesis (frbch_burstspec_*, frbch_rmsynth_*, frbch_burst_rm_*)
+# ------------------------------------------------------------------------------------------------------------------
+BURST_CAND = np.dtype([("dm", "<f8"), ("sample", "<i8"), ("width", "<u4"), ("off_gap", "<u4"), ("off_len", "<u4"), ("reserved", "<u4")])
+BURST_SUMS = np.dtype([("on_sum", "<f8"), ("off_sum", "<f8"), ("off_sumsq", "<f8"), ("on_hits", "<u4"), ("off_hits", "<u4")])
+RM_RESULT = np.dtype([("rm", "<f8"), ("rm_err", "<f8"), ("peak", "<f8"), ("pa0", "<f8"), ("snr", "<f8"), ("sigma_f", "<f8"),
+                      ("fwhm", "<f8"), ("kpeak", "<u4"), ("nused", "<u4"), ("fitted", "<u4"), ("reserved", "<u4")])
+RM_C = 299.792458             # c in m MHz: lambda = RM_C / f_MHz
+RM_NPHI_CAP = 1 << 17         # trials of the default grid
+RM_ROW = "%s  DM %.3f  sample %d  RM %+.3f +- %.3f rad/m2  L/I %.4f  V/I %+.4f  PA0 %.2f deg  S/N %.1f"
+
+
+def burst_cands(bursts, off_gap=None, off_len=None) -> np.ndarray:
+    """BURST_CAND records from (dm, sample, width[, off_gap, off_len]) tuples, dicts or records; the defaults keep the
+    off-pulse windows two widths (at least 16 rows) clear of the burst and make each 1024 rows long"""
+    bursts = np.asarray(bursts) if isinstance(bursts, np.ndarray) else bursts
+    if isinstance(bursts, np.ndarray) and bursts.dtype == BURST_CAND:
+        return np.ascontiguousarray(bursts)
+    out = np.zeros(len(bursts), dtype=BURST_CAND)
+    for i, b in enumerate(bursts):
+        if isinstance(b, dict) or (hasattr(b, "dtype") and b.dtype.names):
+            dm, sample, width = float(b["dm"]), int(b["sample"]), int(b["width"])
+            names = b.keys() if isinstance(b, dict) else b.dtype.names
+            gap = int(b["off_gap"]) if "off_gap" in names else None
+            length = int(b["off_len"]) if "off_len" in names else None
+        else:
+            dm, sample, width = float(b[0]), int(b[1]), int(b[2])
+            gap = int(b[3]) if len(b) > 3 else None
+            length = int(b[4]) if len(b) > 4 else None
+        gap = gap if gap is not None else (off_gap if off_gap is not None else max(16, 2 * width))
+        length = length if length is not None else (off_len if off_len is not None else 1024)
+        out[i] = (dm, sample, width, gap, length, 0)
+    return out
+
+
+def _burst_args(fil_or_rows, hdr, cands, gains, products):
+    rows = _rows_of(fil_or_rows) if isinstance(fil_or_rows, sigproc.SigprocFile) else np.ascontiguousarray(fil_or_rows)
+    nifs, nchan = hdr.get("nifs", 1), hdr["nchans"]
+    if rows.dtype.itemsize * 8 != hdr["nbits"] or rows.size % (nchan * nifs):
+        raise InputError("the rows do not match the header's nbits / nchans / nifs")
+    cands = burst_cands(cands)
+    if products not in ("stokes", "coherency"):
+        raise InputError("products must be 'stokes' or 'coherency'")
+    par = _lib.FrbchBurstParams(C.sizeof(_lib.FrbchBurstParams), _lib.BURST_COHERENCY if products == "coherency" else _lib.BURST_STOKES)
+    g = None
+    if gains is not None:
+        g = np.ascontiguousarray(gains, dtype=np.float32)
+        if g.shape != (nifs, nchan):
+            raise InputError("gains must have the shape [nifs][nchans]")
+    return rows, rows.size // (nchan * nifs), cands, par, g
+
+
+def burst_spectra(fil_or_rows, hdr: dict, cands, gains=None, products: str = "stokes", device: int = 0, lib=None,
+                  info: dict | None = None):
+    """On-pulse minus off-pulse spectra of every product for every burst (frbch_burstspec_host; include/frbch.h states the
+    arithmetic) -> ``spec [n][nifs][nchans]`` float32, ``noise`` (the off-pulse scatter scaled to the on-pulse mean), ``used
+    [n][nchans]`` bytes.  ``cands``: BURST_CAND records or what ``burst_cands`` takes.  ``gains [nifs][nchans]`` multiply the
+    spectra.  ``products='coherency'``: the file holds PP, QQ, Re, Im and the spectra come back as I, Q, U, V.
+    ``info['kernel_used']``: 1 = the fast kernel, 0 = the generic one; ``info['sums']``: the BURST_SUMS records."""
+    lib = lib or _lib.load()
+    rows, nrows, cands, par, g = _burst_args(fil_or_rows, hdr, cands, gains, products)
+    n, nifs, nchan = cands.size, hdr.get("nifs", 1), hdr["nchans"]
+    sums = np.zeros((n, nifs, nchan), dtype=BURST_SUMS)
+    spec, noise = np.zeros((n, nifs, nchan), np.float32), np.zeros((n, nifs, nchan), np.float32)
+    used = np.zeros((n, nchan), np.uint8)
+    k = C.c_uint32(0)
+    err = C.create_string_buffer(512)
+    desc = fil_desc(hdr, hdr.get("product", 0))
+    _check(lib.frbch_burstspec_host(C.byref(desc), rows.ctypes.data, nrows, C.byref(par), cands.ctypes.data, n,
+                                    g.ctypes.data if g is not None else None, device, sums.ctypes.data, spec.ctypes.data,
+                                    noise.ctypes.data, used.ctypes.data, C.byref(k), err, len(err)), err)
+    if info is not None:
+        info.update(kernel_used=k.value, sums=sums)
+    return spec, noise, used
+
+
+def rm_params(nphi: int, phi_lo: float, dphi: float) -> _lib.FrbchRmParams:
+    return _lib.FrbchRmParams(C.sizeof(_lib.FrbchRmParams), int(nphi), float(phi_lo), float(dphi))
+
+
+def lambda2(hdr: dict) -> np.ndarray:
+    """lambda^2 of every channel, m^2, as the library computes it"""
+    f = hdr["fch1"] + np.arange(hdr["nchans"], dtype=np.float64) * hdr["foff"]
+    t = RM_C / f
+    return t * t
+
+
+def rm_grid(hdr: dict, used=None, phi_max: float = 0.0, dphi: float = 0.0, nphi: int = 0):
+    """The default grid of Faraday depths -> (nphi, phi_lo, dphi): dphi = fwhm / 8 with fwhm = 2 sqrt(3) / (span of lambda^2
+    over the used channels); phi_max = sqrt(3) / (the largest lambda^2 step between adjacent channels), lowered until
+    nphi = 2 round(phi_max / dphi) + 1 <= 2^17.  The grid is symmetric about 0, which is one of its trials."""
+    l2 = lambda2(hdr)
+    sel = l2 if used is None else l2[np.asarray(used).reshape(-1, hdr["nchans"]).any(axis=0)]
+    if sel.size < 2:
+        raise InputError("RM synthesis needs at least two used channels")
+    if dphi <= 0.0:
+        dphi = 2.0 * np.sqrt(3.0) / float(sel.max() - sel.min()) / 8.0
+    if nphi > 0:
+        half = (int(nphi) - 1) // 2
+    else:
+        if phi_max <= 0.0:
+            phi_max = np.sqrt(3.0) / float(np.abs(np.diff(l2)).max())
+        half = min(int(round(phi_max / dphi)), (RM_NPHI_CAP - 1) // 2)
+    half = max(half, 1)
+    return 2 * half + 1, -half * dphi, float(dphi)
+
+
+def rm_synthesis(q, u, used, hdr: dict, nphi: int, phi_lo: float, dphi: float, device: int = 0, lib=None, info: dict | None = None):
+    """F(phi) of ``q``, ``u`` [n][nchans] over the channels with ``used != 0`` at phi_k = phi_lo + k dphi (frbch_rmsynth_host;
+    include/frbch.h states the integer transform) -> complex64 ``F [n][nphi]``.  The RMSF is ``rm_synthesis(used, 0, used,
+    ...)``.  ``info['kernel_used']``: 1 = the fast kernel, 0 = the generic one; ``info['split']``: the channel split."""
+    lib = lib or _lib.load()
+    nchan = hdr["nchans"]
+    q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, nchan)
+    u = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, nchan)
+    used = np.ascontiguousarray(used, dtype=np.uint8).reshape(-1, nchan)
+    if not q.shape == u.shape == used.shape:
+        raise InputError("q, u and used must have the same shape [n][nchans]")
+    par = rm_params(nphi, phi_lo, dphi)
+    F = np.zeros((q.shape[0], int(nphi), 2), np.float32)
+    k = (C.c_uint32 * 2)(0, 1)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_rmsynth_host(C.byref(fil_desc(hdr)), q.ctypes.data, u.ctypes.data, used.ctypes.data, q.shape[0], C.byref(par),
+                                  device, F.ctypes.data, k, err, len(err)), err)
+    if info is not None:
+        info.update(kernel_used=k[0], split=k[1])
+    return F.view(np.complex64)[..., 0]
+
+
+def rm_peaks(F, used, noise_q, noise_u, hdr: dict, nphi: int, phi_lo: float, dphi: float, lib=None) -> np.ndarray:
+    """RM_RESULT records from F (frbch_rm_peaks: the first largest trial, a three-point parabola, PA0, the noise in F)"""
+    lib = lib or _lib.load()
+    nchan = hdr["nchans"]
+    Ff = np.ascontiguousarray(np.asarray(F, dtype=np.complex64).reshape(-1, int(nphi))).view(np.float32)
+    used = np.ascontiguousarray(used, dtype=np.uint8).reshape(-1, nchan)
+    nq = None if noise_q is None else np.ascontiguousarray(noise_q, dtype=np.float32).reshape(-1, nchan)
+    nu = None if noise_u is None else np.ascontiguousarray(noise_u, dtype=np.float32).reshape(-1, nchan)
+    res = np.zeros(used.shape[0], dtype=RM_RESULT)
+    par = rm_params(nphi, phi_lo, dphi)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_rm_peaks(C.byref(fil_desc(hdr)), Ff.ctypes.data, used.ctypes.data, nq.ctypes.data if nq is not None else None,
+                              nu.ctypes.data if nu is not None else None, used.shape[0], C.byref(par), res.ctypes.data, err, len(err)), err)
+    return res
+
+
+def burst_rm(fil_or_rows, hdr: dict, cands, nphi: int, phi_lo: float, dphi: float, gains=None, flag=None, products: str = "stokes",
+             device: int = 0, lib=None, info: dict | None = None):
+    """Rows -> spectra -> RM synthesis of Q and U -> peaks in one library call on rows uploaded once (frbch_burst_rm_host)
+    -> dict(spec, noise, used, F, results).  ``flag [nchans]``: non-zero clears the channel in ``used``."""
+    lib = lib or _lib.load()
+    rows, nrows, cands, par, g = _burst_args(fil_or_rows, hdr, cands, gains, products)
+    n, nchan = cands.size, hdr["nchans"]
+    spec, noise = np.zeros((n, 4, nchan), np.float32), np.zeros((n, 4, nchan), np.float32)
+    used = np.zeros((n, nchan), np.uint8)
+    F = np.zeros((n, int(nphi), 2), np.float32)
+    res = np.zeros(n, dtype=RM_RESULT)
+    fl = None if flag is None else np.ascontiguousarray(flag, dtype=np.uint8)
+    if fl is not None and fl.shape != (nchan,):
+        raise InputError("flag must have the shape [nchans]")
+    rpar = rm_params(nphi, phi_lo, dphi)
+    k = (C.c_uint32 * 3)(0, 0, 1)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_burst_rm_host(C.byref(fil_desc(hdr, hdr.get("product", 0))), rows.ctypes.data, nrows, C.byref(par), cands.ctypes.data, n,
+                                   g.ctypes.data if g is not None else None, fl.ctypes.data if fl is not None else None, C.byref(rpar),
+                                   device, spec.ctypes.data, noise.ctypes.data, used.ctypes.data, F.ctypes.data, res.ctypes.data, k,
+                                   err, len(err)), err)
+    if info is not None:
+        info.update(spectra_kernel_used=k[0], kernel_used=k[1], split=k[2])
+    return dict(spec=spec, noise=noise, used=used, F=F.view(np.complex64)[..., 0], results=res)
+
+
+def pol_fractions(spec, noise, used, res):
+    """-> (L/I debiased as sqrt(L^2 - sigma_L^2), V/I) of one burst, from the band-averaged spectra: L is the peak of |F|"""
+    m = used != 0
+    if not m.any():
+        return 0.0, 0.0
+    imean = float(spec[0][m].astype(np.float64).mean())
+    vmean = float(spec[3][m].astype(np.float64).mean())
+    lin2 = float(res["peak"]) ** 2 - float(res["sigma_f"]) ** 2
+    lin = np.sqrt(lin2) if lin2 > 0 else 0.0
+    return (lin / imean, vmean / imean) if imean != 0 else (0.0, 0.0)
+
+
+def _curve_panel(curves, width, height):
+    """curves (each resampled to `width` columns) drawn on one scale, the later ones brighter"""
+    img = np.zeros((height, width))
+    ok = [np.asarray(c, dtype=np.float64) for c in curves if len(c)]
+    if not ok:
+        return img
+    lo, hi = min(float(c.min()) for c in ok), max(float(c.max()) for c in ok)
+    for i, c in enumerate(ok):
+        x = np.interp(np.linspace(0, c.size - 1, width), np.arange(c.size), c)
+        y = (height - 1) - np.rint((x - lo) / max(1e-30, hi - lo) * (height - 1)).astype(int)
+        img[y, np.arange(width)] = 0.5 + 0.5 * (i + 1) / len(ok)
+    return img
+
+
+def _rm_png(path, hdr, r, i, rmsf, phi):
+    """|F| with the RMSF; Q/I and U/I against lambda^2 with the fitted rotation; the PA after de-rotation"""
+    width, height = 512, 96
+    m = r["used"][i] != 0
+    l2 = lambda2(hdr)[m]
+    order = np.argsort(l2)
+    l2 = l2[order]
+    res = r["results"][i]
+    I = np.maximum(np.abs(r["spec"][i, 0][m][order].astype(np.float64)), 1e-30)
+    qi, ui = r["spec"][i, 1][m][order] / I, r["spec"][i, 2][m][order] / I
+    lin = float(res["peak"]) / max(1e-30, float(np.mean(I)))
+    l0 = float(l2.mean()) if l2.size else 0.0
+    ang = 2.0 * (float(res["pa0"]) + float(res["rm"]) * (l2 - l0))
+    pa = 0.5 * np.arctan2(ui, qi) - float(res["rm"]) * (l2 - l0)
+    pa = (pa + np.pi / 2) % np.pi - np.pi / 2
+    shift = np.abs(rmsf) * float(res["peak"])
+    panels = [_curve_panel([np.roll(shift, int(res["kpeak"]) - int(np.argmin(np.abs(phi)))), np.abs(r["F"][i])], width, height),
+              _curve_panel([lin * np.cos(ang), qi], width, height), _curve_panel([lin * np.sin(ang), ui], width, height),
+              _curve_panel([np.full(l2.size, -np.pi / 2), np.full(l2.size, np.pi / 2), pa], width, height)]
+    gap = np.zeros((4, width))
+    write_png(path, np.concatenate([panels[0], gap, panels[1], gap, panels[2], gap, panels[3]], axis=0))
+
+
+def rmsynth_fil(filterbankfile, bursts=None, dm1=None, dm2=0.0, dmstep=1.0, width=0, off_gap=None, off_len=None, phi_max=0.0, dphi=0.0,
+                nphi=0, flag_file=None, gains=None, products="stokes", threshold=8.0, max_cands=8, device=0, lib=None,
+                info: dict | None = None):
+    """Rotation measure of the bursts of a full-Stokes filterbank: ``bursts`` = (dm, sample, width) tuples; or, with ``dm1 ..
+    dm2 .. dmstep`` and no bursts, the ``max_cands`` strongest groups ``candidates_fil``'s search finds on product 0 above
+    ``threshold`` (the search writes its ``.singlepulse`` files, as ``search_fil`` does).  ``gains``: an .npy file or an array [4][nchans]; ``flag_file``: channels left out of the transform.  The
+    grid: ``rm_grid``.  Writes ``<base>_rm.npz`` (spec, noise, used, phi, F, rmsf, results, bursts), ``<base>_rm.txt`` (one
+    line per burst: RM +- err, L/I debiased, V/I, PA0) and ``<base>_rm_burst<i>.png``.  Returns (files, RM_RESULT records)."""
+    lib = lib or _lib.load()
+    fil = sigproc.read_fil(filterbankfile)
+    hdr = fil.header
+    if hdr.get("nifs", 1) != 4:
+        raise InputError("rmsynth needs a four-product file (pol_mode 4 or 5)")
+    if not bursts:
+        if dm1 is None:
+            raise InputError("give bursts (--dm --sample/--time --width) or a DM range to search")
+        dms = dm_list(dm1, dm2, dmstep)
+        _files, recs = _search(fil, filterbankfile, dm1, dm2, dmstep, True, 5, threshold, 0.0, 1000, False, None, device, lib, {})
+        groups = group_candidates(recs, hdr, dms, lib=lib)
+        groups = groups[np.argsort(-groups["best"]["sigma"], kind="stable")[:max_cands]]
+        bursts = [(dms[int(g["best"]["dm_index"])], int(g["best"]["sample"]), max(int(width), int(g["best"]["width"]))) for g in groups]
+        if not bursts:
+            raise InputError("the search found no burst above the threshold")
+    cands = burst_cands(bursts, off_gap, off_len)
+    flag = read_flag_file(flag_file, hdr["nchans"]).astype(np.uint8) if flag_file else None
+    if isinstance(gains, str):
+        gains = np.load(gains)
+    keep = None if flag is None else (flag == 0)[None, :]
+    n_phi, phi_lo, d_phi = rm_grid(hdr, keep, phi_max=phi_max, dphi=dphi, nphi=nphi)
+    rinfo = {}
+    r = burst_rm(fil, hdr, cands, n_phi, phi_lo, d_phi, gains=gains, flag=flag, products=products, device=device, lib=lib, info=rinfo)
+    rmsf = rm_synthesis(r["used"], np.zeros_like(r["spec"][:, 0]), r["used"], hdr, n_phi, phi_lo, d_phi, device=device, lib=lib)
+    phi = phi_lo + np.arange(n_phi) * d_phi
+    base = filterbankfile.replace(".fil", "")
+    files = [base + "_rm.npz", base + "_rm.txt"]
+    np.savez(files[0], spec=r["spec"], noise=r["noise"], used=r["used"], phi=phi, F=r["F"], rmsf=rmsf, results=r["results"], bursts=cands)
+    with open(files[1], "w") as f:
+        for i, (c, res) in enumerate(zip(cands, r["results"])):
+            li, vi = pol_fractions(r["spec"][i], r["noise"][i], r["used"][i], res)
+            f.write(RM_ROW % ("burst%d" % i, c["dm"], int(c["sample"]), res["rm"], res["rm_err"], li, vi, np.degrees(res["pa0"]), res["snr"]) + "\n")
+            _rm_png(base + "_rm_burst%d.png" % i, hdr, r, i, rmsf[i], phi)
+            files.append(base + "_rm_burst%d.png" % i)
+    if info is not None:
+        info.update(rinfo, nphi=n_phi, phi_lo=phi_lo, dphi=d_phi)
+    return files, r["results"]
+
+
 def main(argv=None):
     """``python -m frb_baseband_amd.post fold <fil> <par> [--polyco FILE] [--doppler X] [--products coherency|stokes] [...]`` / ``... prepdata <fil> --dm <dm> [...]`` /
     ``... search <fil> --dm <dm> [--dm2 --dmstep --threshold --max-width --detrend ...]`` /
     ``... candidates <fil> --dm <dm> [search options] [--dm-gap --min-members --max-cands --nt --nf --ndm]`` /
     ``... psearch <fil> --dm <dm> [--dm2 --dmstep --sigma --nharm --flo --nfft --wblock --dm-gap --max-cands --fold-best K --amax A --astep S --acc-gap G]`` /
-    ``... rfifind <fil> [--block-rows --t-cell --t-chan --chan-frac --block-frac --flag FILE --write-clean]``
+    ``... rfifind <fil> [--block-rows --t-cell --t-chan --chan-frac --block-frac --flag FILE --write-clean]`` /
+    ``... rmsynth <fil> (--dm D --sample S | --time T) --width W [--off-gap G --off-len L] [--phi-max X --dphi Y | --nphi N] [--flag FILE]
+    [--gains FILE.npy] [--products stokes|coherency]`` (burst options repeatable; or ``--dm .. --dm2 .. --dmstep ..`` to search for them)
     (``search`` and ``candidates`` take ``--flag FILE`` and ``--rfi``; ``search``, ``candidates`` and ``rfifind`` take ``--resident``:
     one upload of the rows per command; ``rfifind --periodic [--t-freq S]`` and ``--rfi --periodic`` add the periodicity test): the stages
     as commands, for the places where base2fil.sh / process_vdif.py launch dspsr and prepdata"""
@@ -1860,8 +2133,42 @@ def main(argv=None):
     r.add_argument("--periodic", action="store_true", help="also flag cells whose power spectrum has a peak (periodic interference); block-rows a power of two in 8..4096")
     r.add_argument("--t-freq", type=float, default=4.0, help="threshold of --periodic, Gaussian sigma over the bins of a cell")
     r.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
+    m = sub.add_parser("rmsynth", help="rotation measure of the bursts of a full-Stokes filterbank: spectra of every product, RM synthesis of Q and U")
+    m.add_argument("fil")
+    m.add_argument("--dm", type=float, action="append", required=True, help="DM of a burst (repeatable, one per burst); with --dm2: the first DM of the search")
+    m.add_argument("--sample", type=int, action="append", default=None, help="centre of a burst, row at the top of the band (repeatable)")
+    m.add_argument("--time", type=float, action="append", default=None, help="the same in seconds from the start of the file (repeatable)")
+    m.add_argument("--width", type=int, action="append", default=None, help="on-pulse rows (repeatable; one value serves every burst)")
+    m.add_argument("--dm2", type=float, default=0.0, help="search DM .. DM2 for the bursts instead (the groups of `candidates` on product 0)")
+    m.add_argument("--dmstep", type=float, default=1.0)
+    m.add_argument("--threshold", type=float, default=8.0, help="sigma of the search of --dm2")
+    m.add_argument("--max-cands", type=int, default=8, help="bursts kept from the search of --dm2")
+    m.add_argument("--off-gap", type=int, default=None, help="rows between the burst and each off-pulse window (default: 2 widths, at least 16)")
+    m.add_argument("--off-len", type=int, default=None, help="rows of each off-pulse window (default 1024)")
+    m.add_argument("--phi-max", type=float, default=0.0, help="largest |Faraday depth|, rad/m2 (0: sqrt(3) / the largest lambda^2 step)")
+    m.add_argument("--dphi", type=float, default=0.0, help="step of the Faraday depth (0: fwhm / 8)")
+    m.add_argument("--nphi", type=int, default=0, help="trials, instead of --phi-max")
+    m.add_argument("--flag", default=None, help="flag file: channels left out of the transform")
+    m.add_argument("--gains", default=None, help=".npy file [4][nchans] of gains that multiply the spectra")
+    m.add_argument("--products", choices=("coherency", "stokes"), default="stokes", help="what the file holds: I, Q, U, V or the -d4 products")
+    m.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     a = ap.parse_args(argv)
-    if a.cmd == "rfifind":
+    if a.cmd == "rmsynth":
+        bursts = None
+        if a.dm2 <= 0.0:
+            tsamp = sigproc.read_fil(a.fil).header["tsamp"]
+            centres = list(a.sample or []) + [int(round(t / tsamp)) for t in (a.time or [])]
+            widths = a.width or []
+            if not centres or len(centres) != len(a.dm) or len(widths) not in (1, len(centres)):
+                raise InputError("rmsynth: one --sample or --time per --dm, and --width once or once per burst")
+            bursts = [(dm, s, widths[i if len(widths) > 1 else 0]) for i, (dm, s) in enumerate(zip(a.dm, centres))]
+        files, res = rmsynth_fil(a.fil, bursts, dm1=a.dm[0], dm2=a.dm2, dmstep=a.dmstep, width=(a.width or [0])[0], off_gap=a.off_gap,
+                                 off_len=a.off_len, phi_max=a.phi_max, dphi=a.dphi, nphi=a.nphi, flag_file=a.flag, gains=a.gains,
+                                 products=a.products, threshold=a.threshold, max_cands=a.max_cands, device=a.device)
+        for path in files:
+            print("wrote", path)
+        print(open(files[1]).read(), end="")
+    elif a.cmd == "rfifind":
         files, res = rfifind_fil(a.fil, block_rows=a.block_rows, t_cell=a.t_cell, t_chan=a.t_chan, chan_frac=a.chan_frac,
                                  block_frac=a.block_frac, flag_file=a.flag, write_clean=a.write_clean, device=a.device, resident=a.resident,
                                  **(dict(periodic=True, t_freq=a.t_freq) if a.periodic else {}))

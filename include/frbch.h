@@ -697,6 +697,120 @@ int frbch_cutout_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrow
 int frbch_cutout_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_cutout_params* par,
                         const frbch_cutout_cand* cands, uint32_t ncand);
 
+/* ---- burst polarisation: spectra of every product, rotation measure synthesis ------------------------
+ * What a full-Stokes file (pol_mode 4 / 5 above) is written for: the spectra of a burst in all nifs products, and from Q and
+ * U the Faraday dispersion function F(phi), its peak (the rotation measure) and the position angle.  The conventions are
+ * this library's own, restated in numpy in tests/rm_oracle.py; every result but frbch_rm_peaks' libm calls is reproducible
+ * to the bit, and the transform itself is integer arithmetic, exact in any order of summation.
+ *
+ * 1. Burst spectra.  Candidate i: on_lo = sample - width / 2 (integer division, signed 64 bit); the on-pulse rows are
+ *    on_lo .. on_lo + width - 1 at the top of the band; the off-pulse windows are the off_len rows that end off_gap rows
+ *    before on_lo (on_lo - off_gap - off_len .. on_lo - off_gap - 1) and the off_len rows that start off_gap rows behind
+ *    the last on-pulse row (on_lo + width + off_gap ..).  Channel c is read at row s + n_c(dm), n_c exactly as
+ *    frbch_dedisperse_* compute it; a row outside 0 .. nrows - 1 is absent, adds nothing and is not counted.  For every
+ *    product p < nifs and channel c (frbch_burst_sums, [ncand][nifs][nchan]):
+ *      on_sum = sum of the on-pulse samples, off_sum / off_sumsq = sum of x / of x x over both off-pulse windows,
+ *      on_hits / off_hits = the numbers of present rows.
+ *    8- / 16-bit rows: every sum is exact in any order (width <= 65536, off_len <= 2^20: 65535^2 2^21 < 2^53).  float32
+ *    rows: double sums in ascending row order (the earlier off window, then the later one), x x rounded before it is added.
+ *    Derived on the host in double, every operation rounded on its own (no FMA), g = gain[p][c] (NULL: 1):
+ *      spec[i][p][c]  = (float)((on_sum / on_hits - off_sum / off_hits) * g)
+ *      var_off        = (off_sumsq - off_sum off_sum / off_hits) / (off_hits - 1), a negative value counts as 0
+ *      noise[i][p][c] = (float)(sqrt(var_off / on_hits) * |g|)
+ *    used[i][c] = 1 unless, in any product, on_hits = 0, off_hits < 2, or spec or noise (as float) is not finite; an unused
+ *    channel has spec = noise = 0 in every product.  products = FRBCH_BURST_COHERENCY (file order PP, QQ, Re, Im; needs
+ *    nifs = 4): afterwards, in float, I = PP + QQ, Q = 2 Re, U = 2 Im, V = PP - QQ (the relation of pol_mode 5 above), and
+ *    noise_I = noise_V = (float)sqrt((double)nPP nPP + (double)nQQ nQQ), noise_Q = 2 nRe, noise_U = 2 nIm; a channel whose
+ *    converted values are not finite becomes unused.  FRBCH_BURST_STOKES (0) leaves the products as they are.
+ *    *kernel_used: 1 = the fast kernel (8- / 16-bit rows, nifs <= 4, whole 64-byte channel tiles, d_rows and the row pitch
+ *    16-byte aligned), 0 = the generic one (one thread per (candidate, product, channel)); both give the same bits.
+ *    FRBCH_E_ARG: a wrong `size`, products > 1 (or 1 with nifs != 4), ncand outside 1..4096, width 0 or above 65536,
+ *    off_len < 2 or above 2^20, a DM outside [0, 1e5), a delay beyond 2^30 samples, ncand * nchan > 2^26, ncand * nifs > 65535.
+ *
+ * 2. RM synthesis of q[ncand][nchan], u[ncand][nchan] (float32) over the channels with used[i][c] != 0.
+ *    Host, double, ascending c, every operation rounded on its own:
+ *      f_c = fch1 + c foff (MHz);  l2_c = (299.792458 / f_c)^2 (m^2);  N_i = the number of used channels;
+ *      l0_i = (sum over used c of l2_c) / N_i;  a_ic = (l2_c - l0_i) / pi  (turns per rad m^-2).
+ *    Phase in 64-bit fixed point, 2^64 = one turn; frac(x) = x - floor(x), and a product frac(x) 2^64 of 2^64 counts as 0:
+ *      P0_ic = (uint64)(frac(phi_lo a_ic) 2^64),  D_ic = (uint64)(frac(dphi a_ic) 2^64),
+ *      ph_ick = P0_ic + k D_ic mod 2^64,  table index j = ((ph + 2^49) >> 50) mod 2^14   (phi_k = phi_lo + k dphi).
+ *    Table (frbch_rm_table, 16384 int32): C[j] = (int32)rint(cos(2 pi j / 2^14) 2^22) for j = 0 .. 4096 in double, with
+ *    C[4096] = 0; C[8192 - j] = -C[j], C[8192 + j] = -C[j], C[16384 - j] = C[j]: the symmetry is exact.  S[j] = C[(j - 4096)
+ *    mod 2^14].
+ *    Quantisation per candidate: m = the largest |q_c|, |u_c| over used channels = f 2^e, f in [0.5, 1) (frexp);
+ *      Qi_c = (int32)rintf(q_c 2^(23 - e)), Ui_c likewise (the scaling by a power of two is exact, ties to even).
+ *    Transform, exact in int64 (2^23 2^22 2 2^14 = 2^60):
+ *      Re_ik = sum over used c of (Qi C[j] + Ui S[j]),  Im_ik = sum over used c of (Ui C[j] - Qi S[j]),
+ *    that is (q + i u) exp(-2 i phi_k (l2_c - l0_i)).  F[i][k] = ((float)((double)Re inv_i), (float)((double)Im inv_i)),
+ *    inv_i = 1 / (2^(23 - e) 2^22 N_i) in double.  m = 0 or N_i = 0: F = 0 for that candidate.
+ *    Two costs: the phase is quantised to 2^-14 turn (at most 1.9e-4 rad off), the spectra to 2^-23 of their largest value.
+ *    The RMSF is the transform of q = used, u = 0; its value at phi = 0 is exactly 1.
+ *    kernel_used[2] (may be NULL): the form (1 = the fast kernel: table in the LDS, lanes along k, channels split over
+ *    kernel_used[1] workgroups whose int64 partials a second kernel joins; taken for nphi >= 64 and an 8-byte aligned d_F;
+ *    0 = the generic one, one thread per (i, k), split 1).  Both give the same bits.  FRBCH_E_ARG: a wrong `size`, nchan > 16384, ncand outside 1..4096, nphi outside
+ *    1..2^20, ncand * nphi > 2^26, dphi <= 0 or not finite, |phi_lo| or |phi_lo + nphi dphi| above 1e7, a q or u that is
+ *    not finite in a used channel.
+ *
+ * 3. Peaks (frbch_rm_peaks, host only).  P_k = re re + im im in double; kp = the first largest k.  With 0 < kp < nphi - 1,
+ *    y- = P[kp-1], y0 = P[kp], y+ = P[kp+1], den = y- - 2 y0 + y+ < 0:  delta = 0.5 (y- - y+) / den,
+ *    rm = phi_lo + (kp + delta) dphi,  peak = sqrt(y0 - 0.25 (y- - y+) delta),  fitted = 1;  otherwise rm = phi_lo + kp dphi,
+ *    peak = sqrt(y0), fitted = 0.  pa0 = atan2(im, re) / 2 at kp (rad);  sigma_f = sqrt(sum over used c of (noise_q^2 +
+ *    noise_u^2) / 2) / N;  snr = sqrt(P[kp]) / sigma_f (0 when sigma_f = 0);  fwhm = 2 sqrt(3) / (l2_max - l2_min) over
+ *    used channels;  rm_err = fwhm / (2 snr).  noise_q / noise_u may be NULL (sigma_f = snr = rm_err = 0). */
+#define FRBCH_BURST_STOKES 0u
+#define FRBCH_BURST_COHERENCY 1u
+typedef struct frbch_burst_params { uint32_t size, products; } frbch_burst_params;      /* size = sizeof(frbch_burst_params) */
+typedef struct frbch_burst_cand {
+  double dm;
+  int64_t sample;                      /* centre, row index at the top of the band (as frbch_cutout_cand)                  */
+  uint32_t width, off_gap, off_len, reserved;
+} frbch_burst_cand;
+typedef struct frbch_burst_sums { double on_sum, off_sum, off_sumsq; uint32_t on_hits, off_hits; } frbch_burst_sums;
+typedef struct frbch_rm_params { uint32_t size, nphi; double phi_lo, dphi; } frbch_rm_params;   /* size = sizeof(frbch_rm_params) */
+typedef struct frbch_rm_result {
+  double rm, rm_err, peak, pa0, snr, sigma_f, fwhm;
+  uint32_t kpeak, nused, fitted, reserved;
+} frbch_rm_result;
+/* Which kernel frbch_burstspec_device takes (host only, nothing runs): 1 = fast, 0 = generic, < 0 = refused; only the
+ * ADDRESS of d_rows is examined. */
+int frbch_burstspec_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* par,
+                           const frbch_burst_cand* cands, uint32_t ncand);
+/* d_rows (never written) and d_sums [ncand][nifs][nchan] are device memory; cands, gain [nifs][nchan] (may be NULL) and
+ * the outputs spec, noise [ncand][nifs][nchan] and used [ncand][nchan] are host arrays (each output may be NULL). */
+int frbch_burstspec_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* par,
+                           const frbch_burst_cand* cands, uint32_t ncand, const float* gain, int device,
+                           frbch_burst_sums* d_sums, float* spec, float* noise, uint8_t* used, uint32_t* kernel_used,
+                           char* err, size_t err_cap);
+/* the same with host pointers: one upload of the rows; sums may be NULL */
+int frbch_burstspec_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* par,
+                         const frbch_burst_cand* cands, uint32_t ncand, const float* gain, int device, frbch_burst_sums* sums,
+                         float* spec, float* noise, uint8_t* used, uint32_t* kernel_used, char* err, size_t err_cap);
+int frbch_rm_table(int32_t* out /* [16384] */);
+/* The plan rule (host only, nothing runs): 1 = fast, 0 = generic, < 0 = refused; *nsplit (may be NULL): the channel split.
+ * Only the ADDRESS of d_F is examined: the fast kernel stores a trial as one 8-byte piece and wants d_F 8-byte aligned. */
+int frbch_rmsynth_kernel(const frbch_fil_desc* fil, const float* d_F, uint32_t ncand, const frbch_rm_params* par, uint32_t* nsplit);
+/* d_q, d_u [ncand][nchan] float32, d_used [ncand][nchan] bytes (read, never written) and d_F [ncand][nphi][2] float32 are
+ * device memory. */
+int frbch_rmsynth_device(const frbch_fil_desc* fil, const float* d_q, const float* d_u, const uint8_t* d_used, uint32_t ncand,
+                         const frbch_rm_params* par, int device, float* d_F, uint32_t* kernel_used, char* err, size_t err_cap);
+int frbch_rmsynth_host(const frbch_fil_desc* fil, const float* q, const float* u, const uint8_t* used, uint32_t ncand,
+                       const frbch_rm_params* par, int device, float* F, uint32_t* kernel_used, char* err, size_t err_cap);
+int frbch_rm_peaks(const frbch_fil_desc* fil, const float* F, const uint8_t* used, const float* noise_q, const float* noise_u,
+                   uint32_t ncand, const frbch_rm_params* par, frbch_rm_result* results, char* err, size_t err_cap);
+/* The composite: rows -> spectra (step 1; nifs must be 4) -> RM synthesis of Q and U (products 1 and 2 after the
+ * conversion) of every candidate -> peaks, in one device scope.  _host: one upload of the rows; _device: rows already in
+ * HBM, never written.  flag [nchan] (may be NULL): a non-zero byte clears the channel in `used` of every candidate before
+ * the transform.  Outputs are host arrays: spec, noise [ncand][4][nchan], used [ncand][nchan], F [ncand][nphi][2],
+ * results [ncand].  kernel_used[3] (may be NULL): the spectra's kernel, the transform's form and its split. */
+int frbch_burst_rm_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                          const frbch_burst_cand* cands, uint32_t ncand, const float* gain, const uint8_t* flag,
+                          const frbch_rm_params* par, int device, float* spec, float* noise, uint8_t* used, float* F,
+                          frbch_rm_result* results, uint32_t* kernel_used, char* err, size_t err_cap);
+int frbch_burst_rm_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* bpar,
+                        const frbch_burst_cand* cands, uint32_t ncand, const float* gain, const uint8_t* flag,
+                        const frbch_rm_params* par, int device, float* spec, float* noise, uint8_t* used, float* F,
+                        frbch_rm_result* results, uint32_t* kernel_used, char* err, size_t err_cap);
+
 /* ---- interference: block statistics, the mask, cleaned rows --------------------------------------
  * The reference carries a flag file through to Heimdall and FETCH (create_config.py:54-56 `-F/--flag`, frb.conf:50,
  * base2fil.sh:226,425-432, submit_job.py:117 `<Tel>.flag_<fmin>-<fmax>MHz_<nchan>chan`) and leaves making one to a person.
