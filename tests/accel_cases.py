@@ -10,6 +10,7 @@ from frb_baseband_amd import post
 from tests import accel_oracle as ao
 from tests import psearch_cases as pc
 from tests import psearch_oracle as pso
+from tests.hipmem import guarded_for
 
 TSAMP = pc.TSAMP
 A12 = 3.0e7           # m/s^2 at n = 2^12, tsamp 1 ms: q n = 0.205 (the largest accepted is c / (n tsamp) = 7.3e7)
@@ -156,6 +157,31 @@ def pasearch_host(lib, y, tsamp, accs, cap=8192, batch_rows=0, nacc=None, **kw):
                                  accs.size if nacc is None else nacc, batch_rows, 0, cands.ctypes.data if cap else None, cap,
                                  C.byref(ncand), used, err, len(err))
     return rc, cands[: min(cap, ncand.value)], ncand.value, (used[0], used[1], used[2]), err.value.decode()
+
+
+def held(lib, y, misalign):
+    """-> (guarded buffer, pointer to the series): misalign puts one float in front, so that the series is 4-byte aligned only.
+    Device memory for the product library, host memory for the emulator build"""
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    buf = guarded_for(lib).from_numpy(np.concatenate([np.zeros(1, dtype=np.float32), y.reshape(-1)]) if misalign else y)
+    return buf, C.c_void_p(buf.ptr.value + (4 if misalign else 0))
+
+
+def device_search(lib, y, tsamp, accs, misalign=False, cap=8192, batch_rows=0, **kw):
+    """frbch_pasearch_device on a guarded buffer of exactly ndm * nout floats -> (records, (resampler, form, passes)); the
+    input's checksum and both guard bands are checked behind the call"""
+    accs = np.ascontiguousarray(accs, dtype=np.float64)
+    buf, ptr = held(lib, y, misalign)
+    params = pc.params_of(tsamp, **kw)
+    cands = np.zeros(cap, dtype=post.PA_CAND)
+    ncand, used = C.c_uint64(0), (C.c_uint32 * 3)(99, 99, 99)
+    err = C.create_string_buffer(512)
+    rc = lib.frbch_pasearch_device(ptr, y.shape[0], y.shape[1], C.byref(params), accs.ctypes.data, accs.size, batch_rows, 0,
+                                   cands.ctypes.data, cap, C.byref(ncand), used, err, len(err))
+    assert rc == 0, err.value
+    buf.check(contents=True)
+    buf.free()
+    return cands[: ncand.value], (used[0], used[1], used[2])
 
 
 def same_records(got, want):

@@ -8,6 +8,7 @@ import numpy as np
 
 from frb_baseband_amd import _lib, post
 from tests import psearch_oracle as pso
+from tests.hipmem import guarded_for
 
 TSAMP = 1e-3
 
@@ -134,6 +135,29 @@ def psearch_host(lib, y, tsamp, cap=8192, **kw):
     rc = lib.frbch_psearch_host(y.ctypes.data, y.shape[0], y.shape[1], C.byref(params), 0, cands.ctypes.data if cap else None, cap,
                                 C.byref(ncand), used, err, len(err))
     return rc, cands[: min(cap, ncand.value)], ncand.value, (used[0], used[1]), err.value.decode()
+
+
+def device_search(lib, y, tsamp, misalign=False, cap=8192, **kw):
+    """frbch_psearch_device on a guarded buffer of exactly ndm * nout floats (misalign: one float more, the series from its
+    second float on) -> (records, (form, passes)); the input's checksum and both guard bands are checked behind the call.  The
+    buffer is device memory for the product library and host memory for the emulator build, whose _device entry points take
+    host pointers"""
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    held = np.concatenate([np.zeros(1, dtype=np.float32), y.reshape(-1)]) if misalign else y
+    buf = guarded_for(lib).from_numpy(held)
+    ptr = C.c_void_p(buf.ptr.value + (4 if misalign else 0))
+    params = params_of(tsamp, **kw)
+    npass = C.c_uint32(9)
+    form = lib.frbch_psearch_kernel(ptr, y.shape[0], y.shape[1], C.byref(params), C.byref(npass))
+    cands = np.zeros(cap, dtype=post.PS_CAND)
+    ncand, used = C.c_uint64(0), (C.c_uint32 * 2)(99, 99)
+    err = C.create_string_buffer(512)
+    rc = lib.frbch_psearch_device(ptr, y.shape[0], y.shape[1], C.byref(params), 0, cands.ctypes.data, cap, C.byref(ncand), used, err, len(err))
+    assert rc == 0, err.value
+    buf.check(contents=True)
+    buf.free()
+    assert (used[0], used[1]) == (form, npass.value)
+    return cands[: ncand.value], (used[0], used[1])
 
 
 def same_records(got, want):

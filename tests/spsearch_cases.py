@@ -8,6 +8,7 @@ import numpy as np
 
 from frb_baseband_amd import _lib, post
 from tests import spsearch_oracle as so
+from tests.hipmem import guarded_for
 
 DEFAULT = post.default_widths(64e-6)                      # 1 .. 30
 WIDE = [1, 7, 300, 1024]
@@ -138,6 +139,25 @@ def spsearch_host(lib, y, widths, thr, L, cap=4096):
     rc = lib.frbch_spsearch_host(y.ctypes.data, y.shape[0], y.shape[1], C.byref(params), 0, cands.ctypes.data, cap, C.byref(ncand),
                                  C.byref(used), err, len(err))
     return rc, cands[: min(cap, ncand.value)], ncand.value, used.value, err.value.decode()
+
+
+def device_search(lib, y, widths, thr, L, misalign=False, cap=4096):
+    """frbch_spsearch_device on a guarded buffer of exactly ndm * nout floats (misalign: one float more, the series from its
+    second float on) -> (candidates, kernel_used); the input's checksum and both guard bands are checked behind the call.
+    Device memory for the product library, host memory for the emulator build"""
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    buf = guarded_for(lib).from_numpy(np.concatenate([np.zeros(1, dtype=np.float32), y.reshape(-1)]) if misalign else y)
+    ptr = C.c_void_p(buf.ptr.value + (4 if misalign else 0))
+    params = post.sp_params(widths, thr, L)
+    cands = np.zeros(cap, dtype=post.SP_CAND)
+    ncand, used = C.c_uint64(0), C.c_uint32(99)
+    err = C.create_string_buffer(512)
+    rc = lib.frbch_spsearch_device(ptr, y.shape[0], y.shape[1], C.byref(params), 0, cands.ctypes.data, cap, C.byref(ncand),
+                                   C.byref(used), err, len(err))
+    assert rc == 0, err.value
+    buf.check(contents=True)
+    buf.free()
+    return cands[: ncand.value], used.value
 
 
 def same_records(got, want):

@@ -26,17 +26,13 @@ def passes_of(n):
     return 1 if n <= 1 << 13 else 2 if n <= 1 << 18 else 3
 
 
-def held(y, misalign):
-    """-> (guarded buffer, pointer to the series): misalign puts one float in front, so that the series is 4-byte aligned only"""
-    y = np.ascontiguousarray(y, dtype=np.float32)
-    buf = GuardedBuffer.from_numpy(np.concatenate([np.zeros(1, dtype=np.float32), y.reshape(-1)]) if misalign else y)
-    return buf, C.c_void_p(buf.ptr.value + (4 if misalign else 0))
+device_search = ac.device_search          # (shared with tests/test_gpu_search_dense.py and the emulator twins)
 
 
 def device_resample(lib, y, n, tsamp, accs, misalign=False):
     """frbch_resample_device -> ([nacc][ndm][n], form); the output buffer is guarded too"""
     accs = np.ascontiguousarray(accs, dtype=np.float64)
-    buf, ptr = held(y, misalign)
+    buf, ptr = ac.held(lib, y, misalign)
     out = GuardedBuffer(accs.size * y.shape[0] * n * 4)
     form = lib.frbch_resample_kernel(ptr, y.shape[1], out.ptr)
     used = (C.c_uint32 * 1)(99)
@@ -50,22 +46,6 @@ def device_resample(lib, y, n, tsamp, accs, misalign=False):
     out.free()
     assert used[0] == form
     return got, used[0]
-
-
-def device_search(lib, y, tsamp, accs, misalign=False, cap=8192, batch_rows=0, **kw):
-    """frbch_pasearch_device on a guarded buffer of exactly ndm * nout floats -> (records, (resampler, form, passes))"""
-    accs = np.ascontiguousarray(accs, dtype=np.float64)
-    buf, ptr = held(y, misalign)
-    params = pc.params_of(tsamp, **kw)
-    cands = np.zeros(cap, dtype=post.PA_CAND)
-    ncand, used = C.c_uint64(0), (C.c_uint32 * 3)(99, 99, 99)
-    err = C.create_string_buffer(512)
-    rc = lib.frbch_pasearch_device(ptr, y.shape[0], y.shape[1], C.byref(params), accs.ctypes.data, accs.size, batch_rows, 0,
-                                   cands.ctypes.data, cap, C.byref(ncand), used, err, len(err))
-    assert rc == 0, err.value
-    buf.check(contents=True)
-    buf.free()
-    return cands[: ncand.value], (used[0], used[1], used[2])
 
 
 # ---- the resampler alone ---------------------------------------------------------------------------------------------
