@@ -147,6 +147,24 @@ class FrbchRmResult(C.Structure):
                 ("fitted", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+PROF_REF_MEAN, PROF_REF_ZERO = 0, 1
+
+
+class FrbchProfParams(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("nbin", C.c_uint32), ("tfactor", C.c_uint32), ("ref", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FrbchProfBin(C.Structure):
+    _fields_ = [("i", C.c_double), ("q", C.c_double), ("u", C.c_double), ("v", C.c_double), ("l", C.c_double), ("l_db", C.c_double),
+                ("pa", C.c_double), ("pa_err", C.c_double), ("hits", C.c_uint32), ("pa_valid", C.c_uint32)]
+
+
+class FrbchProfResult(C.Structure):
+    _fields_ = [("sigma_i", C.c_double), ("sigma_q", C.c_double), ("sigma_u", C.c_double), ("sigma_v", C.c_double),
+                ("sigma_l", C.c_double), ("lref", C.c_double), ("k", C.c_int32), ("nused", C.c_uint32), ("on_lo_bin", C.c_uint32),
+                ("on_hi_bin", C.c_uint32)]
+
+
 class FrbchRfiParams(C.Structure):
     _fields_ = [("size", C.c_uint32), ("block_rows", C.c_uint32), ("t_cell", C.c_double), ("t_chan", C.c_double),
                 ("chan_frac", C.c_double), ("block_frac", C.c_double)]
@@ -298,6 +316,12 @@ SYMBOLS = {
                                         C.POINTER(FrbchRmParams), C.c_int, _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
     "frbch_burst_rm_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32, _P, _P,
                                       C.POINTER(FrbchRmParams), C.c_int, _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "frbch_polprof_kernel": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32,
+                                       C.POINTER(FrbchProfParams)]),
+    "frbch_polprof_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32, _P, _P, _P,
+                                       C.POINTER(FrbchProfParams), C.c_int, _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "frbch_polprof_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32, _P, _P, _P,
+                                     C.POINTER(FrbchProfParams), C.c_int, _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
     "frbch_rfi_nblk": (C.c_long, [C.c_uint64, C.c_uint32]),
     "frbch_rfi_stats_kernel": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams)]),
     "frbch_rfi_stats_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams), C.c_int, _P,

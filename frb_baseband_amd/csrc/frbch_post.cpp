@@ -3861,3 +3861,316 @@ extern "C" int frbch_burst_rm_host(const frbch_fil_desc* fil, const void* rows, 
     return frbch_burst_rm_device(fil, d_rows, nrows, bpar, cands, ncand, gain, flag, par, device, spec, noise, used, F, results, kernel_used, err, err_cap);
   });
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// polarisation profile of a burst: derotated I, L, V and PA per time bin (include/frbch.h states the arithmetic)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr uint32_t kPolMaxBin = 1024, kPolMaxT = 512;
+constexpr uint64_t kPolMaxOut = 1ull << 22, kPolPartCap = 1ull << 30;
+
+int pol_check(const frbch_fil_desc* fil, uint64_t nrows, const frbch_burst_params* bpar, const frbch_burst_cand* cands,
+              uint32_t ncand, const frbch_prof_params* par, const PostErr& e) {
+  POST_NO_CONTRACT
+  const int rc = burst_check(fil, nrows, bpar, cands, ncand, e);
+  if (rc) return rc;
+  if (fil->nifs != 4) return e.fail(FRBCH_E_ARG, "the profile needs the four products of a full-Stokes file (nifs = 4)");
+  if (fil->nbits == 32) return e.fail(FRBCH_E_ARG, "the profile is not built for float32 rows: its fixed-point scale needs a bound on the samples");
+  if (!par || par->size != sizeof(frbch_prof_params)) return e.fail(FRBCH_E_ARG, "frbch_prof_params: wrong size");
+  if (par->nbin < 1 || par->nbin > kPolMaxBin) return e.fail(FRBCH_E_ARG, "nbin must be 1..1024");
+  if (par->tfactor < 1 || par->tfactor > kPolMaxT) return e.fail(FRBCH_E_ARG, "tfactor must be 1..512");
+  if (par->ref > FRBCH_PROF_REF_ZERO) return e.fail(FRBCH_E_ARG, "ref must be 0 (the mean lambda^2) or 1 (lambda^2 = 0)");
+  if (fil->nchan > kRmMaxChan) return e.fail(FRBCH_E_ARG, "more than 16384 channels");
+  if (!(fil->fch1_mhz + (double)(fil->nchan - 1) * fil->foff_mhz > 0)) return e.fail(FRBCH_E_ARG, "a channel frequency that is not positive");
+  if ((uint64_t)ncand * par->nbin > kPolMaxOut) return e.fail(FRBCH_E_ARG, "ncand * nbin exceeds 2^22: cut the batch into several calls");
+  return FRBCH_OK;
+}
+
+int pol_check_rm(const double* rm, uint32_t ncand, const PostErr& e) {
+  if (!rm) return e.fail(FRBCH_E_ARG, "null argument");
+  for (uint32_t i = 0; i < ncand; ++i)
+    if (!(fabs(rm[i]) <= kRmPhiMax)) return e.fail(FRBCH_E_ARG, "candidate " + std::to_string(i) + ": an rm that is not finite or above 1e7 rad m^-2 in size");
+  return FRBCH_OK;
+}
+
+// The plan rule of the profile -- the one decision behind frbch_polprof_device's launches, kernel_used[1] and
+// frbch_polprof_kernel's answer.  The fast kernel wants the layout of the fast burst-sums kernel (only the ADDRESS of d_rows
+// is examined), room in its stage for one bin behind the largest delay spread of any 64-byte tile of any candidate
+// (tfactor + spread <= kPpSpan rows), and partials of at most 2^30 bytes; brun = the bins of a run that then fit, the same
+// for every workgroup.  The emulator build has no such kernel: generic.
+struct PolPlanRule { bool fastk; int brun, ntile; };
+PolPlanRule pol_plan_rule(const frbch_fil_desc* fil, const void* d_rows, const std::vector<int32_t>& delays, uint32_t ncand,
+                          const frbch_prof_params* par) {
+  PolPlanRule r{false, 0, 0};
+#ifndef FRBCH_NO_FAST
+  if (!burst_fast_layout(fil, d_rows)) return r;
+  const uint32_t ct = 64u / (uint32_t)(fil->nbits / 8), ntile = fil->nchan / ct;
+  int64_t spread = 0;
+  for (uint32_t i = 0; i < ncand; ++i)
+    for (uint32_t t = 0; t < ntile; ++t) {
+      const int32_t* d = delays.data() + (size_t)i * fil->nchan + (size_t)t * ct;
+      const auto mm = std::minmax_element(d, d + ct);
+      spread = std::max<int64_t>(spread, (int64_t)*mm.second - (int64_t)*mm.first);
+    }
+  if ((int64_t)par->tfactor + spread > (int64_t)fast::kPpSpan) return r;
+  if ((uint64_t)ncand * ntile * par->nbin * 36ull > kPolPartCap) return r;
+  r.fastk = true;
+  r.brun = (int)std::min<int64_t>((int64_t)par->nbin, ((int64_t)fast::kPpSpan - spread) / (int64_t)par->tfactor);
+  r.ntile = (int)ntile;
+#else
+  (void)fil; (void)d_rows; (void)delays; (void)ncand; (void)par;
+#endif
+  return r;
+}
+
+struct PolOut {
+  std::vector<long long> acc;
+  std::vector<uint32_t> hits;
+  std::vector<frbch_prof_bin> bins;
+  std::vector<frbch_prof_result> res;
+  std::vector<uint8_t> used;
+  uint32_t k[2] = {0, 0};
+};
+
+// floor(a / b), b > 0
+long long pol_floordiv(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+
+// everything of a call inside its scope: the burst sums, the records, the launches, the derivation (all synchronised)
+int pol_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+            const frbch_burst_cand* cands, uint32_t ncand, const double* rm, const float* gain, const uint8_t* flag,
+            const frbch_prof_params* par, PostScope& ps, PolOut* out, const PostErr& e) {
+  POST_NO_CONTRACT
+  const size_t nchan = fil->nchan, n = (size_t)ncand * nchan, nbin = par->nbin;
+  BurstPlan bplan;
+  int rc = burst_build(fil, cands, ncand, &bplan, e);
+  if (rc) return rc;
+  const PolPlanRule rule = pol_plan_rule(fil, d_rows, bplan.delays, ncand, par);
+  std::vector<frbch_burst_sums> sums;
+  std::vector<float> spec(n * 4), noise(n * 4);
+  out->used.assign(n, 0);
+  BurstSums* d_sums = nullptr;
+  POST_DEV(ps.alloc(&d_sums, n * 4 * sizeof(BurstSums)), "hipMalloc");
+  if ((rc = burst_run(fil, d_rows, nrows, bpar, cands, ncand, gain, d_sums, ps, &sums, spec.data(), noise.data(), out->used.data(), &out->k[0], e)) != 0) return rc;
+  ps.drop(d_sums);
+  uint8_t* used = out->used.data();
+  if (flag)
+    for (uint32_t i = 0; i < ncand; ++i)
+      for (size_t c = 0; c < nchan; ++c)
+        if (flag[c]) used[i * nchan + c] = 0;
+
+  // the records
+  const bool coh = bpar->products == FRBCH_BURST_COHERENCY;
+  const std::vector<double> l2 = rm_l2(fil);
+  std::vector<int32_t> table(kRmTableN);
+  rm_table_fill(table.data());
+  std::vector<PolRec> rec(n);
+  std::vector<PolCand> pc(ncand);
+  out->res.assign(ncand, frbch_prof_result{});
+  memset((void*)rec.data(), 0, n * sizeof(PolRec));
+  for (size_t o = 0; o < n; ++o) rec[o].delay = bplan.delays[o];      // (of unused channels too: the fast kernel sizes its stage by them)
+  memset((void*)out->res.data(), 0, (size_t)ncand * sizeof(frbch_prof_result));
+  const double tf = (double)par->tfactor;
+  for (uint32_t i = 0; i < ncand; ++i) {
+    frbch_prof_result& r = out->res[i];
+    const uint8_t* us = used + (size_t)i * nchan;
+    const long long on_lo = (long long)cands[i].sample - (long long)(cands[i].width / 2);
+    const long long t0 = (long long)cands[i].sample - (long long)(par->nbin / 2) * (long long)par->tfactor;
+    pc[i].t0 = t0;
+    pc[i].scale = 0.0;
+    const long long last = (long long)nbin - 1;
+    r.on_lo_bin = (uint32_t)std::min(last, std::max(0ll, pol_floordiv(on_lo - t0, (long long)par->tfactor)));
+    r.on_hi_bin = (uint32_t)std::min(last, std::max(0ll, pol_floordiv(on_lo + (long long)cands[i].width - 1 - t0, (long long)par->tfactor)));
+    uint32_t N = 0;
+    double sum = 0.0, gmax = 0.0;
+    for (size_t c = 0; c < nchan; ++c)
+      if (us[c]) {
+        ++N;
+        sum = sum + l2[c];
+        for (size_t p = 0; p < 4; ++p) gmax = std::max(gmax, gain ? fabs((double)gain[p * nchan + c]) : 1.0);
+      }
+    r.nused = N;
+    if (N == 0 || gmax == 0.0) continue;                       // every output 0: no used record
+    const double lref = par->ref == FRBCH_PROF_REF_MEAN ? sum / (double)N : 0.0;
+    const double M = (tf * ldexp(1.0, fil->nbits)) * gmax;
+    int ex = 0;
+    (void)frexp(M, &ex);
+    r.k = 22 - ex;
+    r.lref = lref;
+    pc[i].scale = ldexp(1.0, r.k);
+    double W[4] = {0.0, 0.0, 0.0, 0.0};
+    for (size_t c = 0; c < nchan; ++c) {
+      PolRec& q = rec[(size_t)i * nchan + c];
+      if (!us[c]) continue;
+      q.used = 1;
+      double w[4];
+      for (size_t p = 0; p < 4; ++p) {
+        const frbch_burst_sums& s = sums[((size_t)i * 4 + p) * nchan + c];
+        const double noff = (double)s.off_hits;
+        const double g = gain ? (double)gain[p * nchan + c] : 1.0;
+        q.mean[p] = s.off_sum / noff;
+        q.g[p] = g;
+        const double ss = s.off_sum * s.off_sum;
+        const double sn = ss / noff;
+        const double num = s.off_sumsq - sn;
+        double var = num / (noff - 1.0);
+        if (var < 0.0) var = 0.0;
+        const double gg = g * g;
+        w[p] = gg * var;
+      }
+      if (coh) {
+        const double wi = w[0] + w[1];
+        W[0] = W[0] + wi; W[1] = W[1] + 4.0 * w[2]; W[2] = W[2] + 4.0 * w[3]; W[3] = W[3] + wi;
+      } else {
+        for (int p = 0; p < 4; ++p) W[p] = W[p] + w[p];
+      }
+      const double a = (l2[c] - lref) / kRmPi;
+      const uint64_t ph = rm_fix(rm[i] * a);
+      const int j = (int)(((ph + (1ull << 49)) >> 50) & 16383ull);
+      q.cc = table[j];
+      q.sc = table[(j - 4096) & 16383];
+    }
+    double sg[4];
+    const double den = (double)N * tf;
+    for (int p = 0; p < 4; ++p) {
+      const double t1 = tf * W[p];
+      sg[p] = sqrt(t1) / den;
+    }
+    r.sigma_i = sg[0]; r.sigma_q = sg[1]; r.sigma_u = sg[2]; r.sigma_v = sg[3];
+    const double qq = sg[1] * sg[1], uu = sg[2] * sg[2];
+    r.sigma_l = sqrt((qq + uu) / 2.0);
+  }
+
+  // the launches
+  PolRec* d_rec = nullptr;
+  PolCand* d_pc = nullptr;
+  long long* d_acc = nullptr;
+  uint32_t* d_hits = nullptr;
+  POST_DEV(ps.alloc(&d_rec, n * sizeof(PolRec)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_pc, (size_t)ncand * sizeof(PolCand)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_acc, (size_t)ncand * nbin * 4 * sizeof(long long)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_hits, (size_t)ncand * nbin * sizeof(uint32_t)), "hipMalloc");
+  POST_DEV(dev_h2d(d_rec, rec.data(), n * sizeof(PolRec), ps.s), "upload records");
+  POST_DEV(dev_h2d(d_pc, pc.data(), (size_t)ncand * sizeof(PolCand), ps.s), "upload records");
+  PolParams p = post_params<PolParams>(fil, d_rows, nrows);
+  p.ncand = (int)ncand; p.cand = d_pc; p.rec = d_rec; p.acc = d_acc; p.hits = d_hits;
+  p.nbin = (int)par->nbin; p.tfactor = (int)par->tfactor; p.coh = coh ? 1 : 0; p.ntile = rule.ntile; p.brun = rule.brun;
+  out->k[1] = rule.fastk ? 1 : 0;
+  bool launched = false;
+#ifndef FRBCH_NO_FAST
+  if (rule.fastk) {
+    long long* d_part = nullptr;
+    uint32_t* d_hpart = nullptr;
+    const size_t np = (size_t)ncand * rule.ntile * nbin;
+    POST_DEV(ps.alloc(&d_part, np * 4 * sizeof(long long)), "hipMalloc");
+    POST_DEV(ps.alloc(&d_hpart, np * sizeof(uint32_t)), "hipMalloc");
+    p.part = d_part; p.hpart = d_hpart;
+    const dim3 grid((unsigned)rule.ntile, (unsigned)((par->nbin + rule.brun - 1) / rule.brun), ncand), block(fast::kPpThreads);
+    if (fil->nbits == 8) POST_DEV(launch_lds(fast::frbch_post_polprof_fast<1>, grid, block, fast::kPpLds, ps.s, p), "LDS size");
+    else POST_DEV(launch_lds(fast::frbch_post_polprof_fast<2>, grid, block, fast::kPpLds, ps.s, p), "LDS size");
+    POST_DEV(dev_check_launch(), "launch profile");
+    hipLaunchKernelGGL(fast::frbch_post_polprof_join, dim3((par->nbin + fast::kPpThreads - 1) / fast::kPpThreads, ncand), dim3(fast::kPpThreads), 0, ps.s, p);
+    POST_DEV(dev_check_launch(), "launch profile join");
+    launched = true;
+  }
+#endif
+  if (!launched) {
+    DEV_LAUNCH(frbch_post_polprof, (par->nbin + 255) / 256, ncand, 256, 0, ps.s, p);
+    POST_DEV(dev_check_launch(), "launch profile");
+  }
+  out->acc.resize((size_t)ncand * nbin * 4);
+  out->hits.resize((size_t)ncand * nbin);
+  POST_DEV(dev_d2h(out->acc.data(), d_acc, out->acc.size() * sizeof(long long), ps.s), "download profile");
+  POST_DEV(dev_d2h(out->hits.data(), d_hits, out->hits.size() * sizeof(uint32_t), ps.s), "download profile");
+  POST_DEV(dev_sync(ps.s), "sync");
+
+  // the derivation
+  out->bins.assign((size_t)ncand * nbin, frbch_prof_bin{});
+  memset((void*)out->bins.data(), 0, out->bins.size() * sizeof(frbch_prof_bin));
+  for (uint32_t i = 0; i < ncand; ++i) {
+    const frbch_prof_result& r = out->res[i];
+    if (pc[i].scale == 0.0) continue;
+    const double inv = ldexp(1.0, -r.k), inv22 = ldexp(1.0, -(r.k + 22)), sl = r.sigma_l;
+    for (size_t j = 0; j < nbin; ++j) {
+      const long long* a = out->acc.data() + ((size_t)i * nbin + j) * 4;
+      frbch_prof_bin& b = out->bins[(size_t)i * nbin + j];
+      b.hits = out->hits[(size_t)i * nbin + j];
+      if (!b.hits) continue;
+      const double h = (double)b.hits;
+      b.i = ((double)a[0] * inv) / h;
+      b.q = ((double)a[1] * inv22) / h;
+      b.u = ((double)a[2] * inv22) / h;
+      b.v = ((double)a[3] * inv) / h;
+      const double qq = b.q * b.q, uu = b.u * b.u;
+      b.l = sqrt(qq + uu);
+      if (b.l >= 1.57 * sl) {
+        const double ll = b.l * b.l, s2 = sl * sl;
+        b.l_db = sqrt(ll - s2);
+      }
+      b.pa = atan2(b.u, b.q) / 2.0;
+      if (b.l_db > 0.0) {
+        b.pa_err = sl / (2.0 * b.l_db);
+        b.pa_valid = 1;
+      }
+    }
+  }
+  return FRBCH_OK;
+}
+}  // namespace
+
+extern "C" int frbch_polprof_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                    const frbch_burst_cand* cands, uint32_t ncand, const frbch_prof_params* par) try {
+  PostErr e{nullptr, 0};
+  int rc = pol_check(fil, nrows, bpar, cands, ncand, par, e);
+  if (rc) return rc;
+  if (!d_rows) return FRBCH_E_ARG;
+  BurstPlan plan;
+  if ((rc = burst_build(fil, cands, ncand, &plan, e)) != 0) return rc;
+  return pol_plan_rule(fil, d_rows, plan.delays, ncand, par).fastk ? 1 : 0;
+} catch (const std::bad_alloc&) { return FRBCH_E_NOMEM; }
+
+extern "C" int frbch_polprof_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                    const frbch_burst_cand* cands, uint32_t ncand, const double* rm, const float* gain,
+                                    const uint8_t* flag, const frbch_prof_params* par, int device, int64_t* acc, uint32_t* hits,
+                                    frbch_prof_bin* bins, frbch_prof_result* results, uint8_t* used, uint32_t* kernel_used,
+                                    char* err, size_t err_cap) try {
+  static_assert(sizeof(PolRec) == 80 && sizeof(frbch_prof_bin) == 72 && sizeof(frbch_prof_result) == 64 && sizeof(long long) == sizeof(int64_t), "profile records");
+  PostErr e{err, err_cap};
+  int rc = pol_check(fil, nrows, bpar, cands, ncand, par, e);
+  if (rc) return rc;
+  if (!d_rows) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = pol_check_rm(rm, ncand, e)) != 0) return rc;
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  PolOut out;
+  {
+    DeviceGuard dg(device);
+    PostScope ps;
+    if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+    if ((rc = pol_run(fil, d_rows, nrows, bpar, cands, ncand, rm, gain, flag, par, ps, &out, e)) != 0) return rc;
+  }
+  if (acc) memcpy(acc, out.acc.data(), out.acc.size() * sizeof(long long));
+  if (hits) memcpy(hits, out.hits.data(), out.hits.size() * sizeof(uint32_t));
+  if (bins) memcpy((void*)bins, out.bins.data(), out.bins.size() * sizeof(frbch_prof_bin));
+  if (results) memcpy((void*)results, out.res.data(), out.res.size() * sizeof(frbch_prof_result));
+  if (used) memcpy(used, out.used.data(), out.used.size());
+  if (kernel_used) { kernel_used[0] = out.k[0]; kernel_used[1] = out.k[1]; }
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_polprof_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                  const frbch_burst_cand* cands, uint32_t ncand, const double* rm, const float* gain,
+                                  const uint8_t* flag, const frbch_prof_params* par, int device, int64_t* acc, uint32_t* hits,
+                                  frbch_prof_bin* bins, frbch_prof_result* results, uint8_t* used, uint32_t* kernel_used,
+                                  char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  int rc = pol_check(fil, nrows, bpar, cands, ncand, par, e);
+  if (rc) return rc;
+  if (!rows) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = pol_check_rm(rm, ncand, e)) != 0) return rc;
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
+  return hs.run(e, "device memory for the rows", "upload rows", "download", [&]() {
+    return frbch_polprof_device(fil, d_rows, nrows, bpar, cands, ncand, rm, gain, flag, par, device, acc, hits, bins, results, used, kernel_used, err, err_cap);
+  });
+}

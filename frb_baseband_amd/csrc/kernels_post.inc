@@ -1208,3 +1208,83 @@ KERNEL(frbch_post_rm, RmParams) {
     }
   }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Polarisation profile of a burst (frbch_polprof_*; include/frbch.h states the arithmetic): per (candidate, time bin) the
+// band sum of I, V and of (Q, U) rotated back by the RM, in int64.  Every channel's part of a bin goes through pp_term in
+// both forms, so the generic kernel below and the fast one (kernels_post_fast.inc) differ in schedule only; the sums are
+// exact, so they give the same bits.
+// ---------------------------------------------------------------------------------------------------------------------
+struct PolRec {                // one channel of a candidate: 80 bytes
+  double mean[4], g[4];        // the off-pulse mean and the gain of every product
+  int32_t cc, sc;              // C[j], S[j] of the channel's rotation
+  int32_t delay;               // n_c(dm)
+  uint32_t used;
+};
+struct PolCand { long long t0; double scale; };   // first row of bin 0 at the top of the band; 2^k
+struct PolParams {
+  const uint8_t* rows;         // [nrows][4][nchan] samples of `nbits` (8 or 16)
+  uint64_t nrows;
+  int nchan, nifs, nbits, ncand;
+  const PolCand* cand;         // [ncand]
+  const PolRec* rec;           // [ncand][nchan]
+  long long* acc;              // [ncand][nbin][4]: I, Re, Im, V
+  uint32_t* hits;              // [ncand][nbin]
+  long long* part;             // fast kernel: [ncand][ntile][nbin][4]
+  uint32_t* hpart;             // fast kernel: [ncand][ntile][nbin]
+  int nbin, tfactor, coh, ntile, brun, pad;
+};
+
+// the part of one channel in one bin: S[p] the sums of its h present rows
+DEVFN inline void pp_term(const PolRec& r, int coh, double scale, const uint32_t* S, uint32_t h, long long* a) {
+  POST_NO_CONTRACT
+  double x[4];
+  for (int pr = 0; pr < 4; ++pr) {
+    const double m = (double)h * r.mean[pr];
+    const double d = (double)S[pr] - m;
+    x[pr] = d * r.g[pr];
+  }
+  double xi = x[0], xq = x[1], xu = x[2], xv = x[3];
+  if (coh) { xi = x[0] + x[1]; xq = 2.0 * x[2]; xu = 2.0 * x[3]; xv = x[0] - x[1]; }
+  const long long Xi = (long long)rint(xi * scale), Xq = (long long)rint(xq * scale);
+  const long long Xu = (long long)rint(xu * scale), Xv = (long long)rint(xv * scale);
+  const long long cj = r.cc, sj = r.sc;
+  a[0] += Xi;
+  a[1] += Xq * cj + Xu * sj;
+  a[2] += Xu * cj - Xq * sj;
+  a[3] += Xv;
+}
+
+// grid (ceil(nbin / 256), ncand), one thread per (candidate, bin), channels ascending, rows ascending
+KERNEL(frbch_post_polprof, PolParams) {
+  K_PROLOGUE;
+  (void)smem;
+  PHASE {
+    const int j = bx * nthr + tid;
+    if (j < p.nbin) {
+      const PolCand cd = p.cand[by];
+      const PolRec* rec = p.rec + (size_t)by * p.nchan;
+      const uint64_t pitch = (uint64_t)p.nifs * (uint64_t)p.nchan;
+      const long long b0 = cd.t0 + (long long)j * (long long)p.tfactor;
+      long long a[4] = {0, 0, 0, 0};
+      uint32_t hits = 0;
+      for (int c = 0; c < p.nchan; ++c) {
+        if (!rec[c].used) continue;
+        long long lo, hi;
+        burst_clip(b0, (uint32_t)p.tfactor, (long long)rec[c].delay, (long long)p.nrows, &lo, &hi);
+        if (hi <= lo) continue;
+        uint32_t S[4] = {0, 0, 0, 0};
+        for (long long t = lo; t < hi; ++t)
+          for (int pr = 0; pr < 4; ++pr) {
+            const uint64_t o = (uint64_t)t * pitch + (uint64_t)pr * (uint64_t)p.nchan + (uint64_t)c;
+            S[pr] += p.nbits == 8 ? (uint32_t)p.rows[o] : (uint32_t)((const uint16_t*)p.rows)[o];
+          }
+        pp_term(rec[c], p.coh, cd.scale, S, (uint32_t)(hi - lo), a);
+        hits += (uint32_t)(hi - lo);
+      }
+      long long* o = p.acc + ((size_t)by * p.nbin + j) * 4;
+      o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = a[3];
+      p.hits[(size_t)by * p.nbin + j] = hits;
+    }
+  }
+}

@@ -1096,4 +1096,100 @@ __global__ void __launch_bounds__(kRmThreads) frbch_post_rm_join(RmParams p) {
   }
   rm_store2(p.out + ((size_t)cand * p.nphi + k) * 2, re, im, p.cand[cand].inv);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Polarisation profile (HIP only; frbch_post_polprof of kernels_post.inc stays the emulable form and the fallback; both call
+// pp_term).  A workgroup of 256 threads owns one candidate, one 64-byte tile of the row (CT = 64 / 32 channels of 8- / 16-bit
+// samples) and a run of `brun` bins.  It stages the rows the run needs -- from its first bin's first row at the tile's
+// smallest delay to its last bin's last row at the largest: nb tfactor + (dmax - dmin) <= kPpSpan rows, the host's plan rule
+// sees to that -- of all four products into the LDS in 16-byte pieces, four lanes side by side on the 64 bytes of a product
+// (the layout of the LDS is [row][product][64 bytes], piece i at byte 16 i).  Then one thread per (channel, bin), 256 / CT
+// bins per trip, sums its tfactor samples at its own delay from the LDS, forms its term, and the CT lanes of a bin add
+// theirs up by shuffles; lane 0 stores the tile's int64 partial.  Rows outside the file are neither loaded nor read.
+// frbch_post_polprof_join adds the tiles in ascending order.  All row arithmetic is 64 bit.
+// grid (row bytes / 64, ceil(nbin / brun), ncand).
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int kPpThreads = 256, kPpSpan = 256;
+constexpr size_t kPpLds = (size_t)kPpSpan * 256;                           // 64 KiB: two workgroups per CU
+
+template <int BPV>
+__global__ void __launch_bounds__(kPpThreads) frbch_post_polprof_fast(PolParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int CT = 64 / BPV, BPP = kPpThreads / CT;
+  const int tid = threadIdx.x, ch = tid % CT, jl = tid / CT;
+  const int tile = blockIdx.x, cand = blockIdx.z;
+  const int j0 = (int)blockIdx.y * p.brun;
+  const int nb = min(p.brun, p.nbin - j0);
+  const PolCand cd = p.cand[cand];
+  const PolRec r = p.rec[(size_t)cand * p.nchan + (size_t)tile * CT + ch];
+  int dmin = r.delay, dmax = r.delay;
+#pragma unroll
+  for (int m = 1; m < CT; m <<= 1) {                                       // over the tile's channels: the same in every thread
+    dmin = min(dmin, __shfl_xor(dmin, m));
+    dmax = max(dmax, __shfl_xor(dmax, m));
+  }
+  const long long nrows = (long long)p.nrows;
+  const long long base = cd.t0 + (long long)j0 * (long long)p.tfactor + (long long)dmin;     // the file row of LDS row 0
+  const int span = nb * p.tfactor + (dmax - dmin);
+  const size_t stride = (size_t)4 * p.nchan * BPV, pstride = (size_t)p.nchan * BPV;
+  const unsigned char* src = p.rows + (size_t)tile * 64;
+  for (int i = tid; i < span * 16; i += kPpThreads) {
+    const long long row = base + (long long)(i >> 4);
+    if (row >= 0 && row < nrows)
+      *reinterpret_cast<uint4*>(smem + (size_t)i * 16) =
+          *reinterpret_cast<const uint4*>(src + (size_t)row * stride + (size_t)((i >> 2) & 3) * pstride + (size_t)(i & 3) * 16);
+  }
+  __syncthreads();
+  for (int jb0 = 0; jb0 < nb; jb0 += BPP) {                                // (the same trips in every thread: the shuffles meet whole waves)
+    const int jb = jb0 + jl;
+    long long a[4] = {0, 0, 0, 0};
+    uint32_t h = 0;
+    if (jb < nb && r.used) {
+      const long long b0 = cd.t0 + (long long)(j0 + jb) * (long long)p.tfactor;
+      long long lo, hi;
+      burst_clip(b0, (uint32_t)p.tfactor, (long long)r.delay, nrows, &lo, &hi);
+      if (hi > lo) {
+        uint32_t S[4] = {0, 0, 0, 0};
+        const unsigned char* q = smem + (size_t)(lo - base) * 256 + (size_t)ch * BPV;
+        for (long long t = lo; t < hi; ++t, q += 256) {
+#pragma unroll
+          for (int pr = 0; pr < 4; ++pr) {
+            if constexpr (BPV == 1) S[pr] += (uint32_t)q[pr * 64];
+            else S[pr] += (uint32_t)*reinterpret_cast<const uint16_t*>(q + pr * 64);
+          }
+        }
+        h = (uint32_t)(hi - lo);
+        pp_term(r, p.coh, cd.scale, S, h, a);
+      }
+    }
+#pragma unroll
+    for (int m = 1; m < CT; m <<= 1) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) a[k] += __shfl_xor(a[k], m);
+      h += __shfl_xor(h, m);
+    }
+    if (ch == 0 && jb < nb) {
+      const size_t o = ((size_t)cand * p.ntile + tile) * p.nbin + (size_t)(j0 + jb);
+      p.part[o * 4 + 0] = a[0]; p.part[o * 4 + 1] = a[1]; p.part[o * 4 + 2] = a[2]; p.part[o * 4 + 3] = a[3];
+      p.hpart[o] = h;
+    }
+  }
+}
+
+// grid (ceil(nbin / 256), ncand): the partials of the tiles, added in ascending tile
+__global__ void __launch_bounds__(kPpThreads) frbch_post_polprof_join(PolParams p) {
+  const int j = (int)blockIdx.x * kPpThreads + (int)threadIdx.x, cand = blockIdx.y;
+  if (j >= p.nbin) return;
+  long long a[4] = {0, 0, 0, 0};
+  uint32_t h = 0;
+  for (int t = 0; t < p.ntile; ++t) {
+    const size_t o = ((size_t)cand * p.ntile + t) * p.nbin + (size_t)j;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a[k] += p.part[o * 4 + k];
+    h += p.hpart[o];
+  }
+  long long* out = p.acc + ((size_t)cand * p.nbin + j) * 4;
+  out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
+  p.hits[(size_t)cand * p.nbin + j] = h;
+}
 }  // namespace fast

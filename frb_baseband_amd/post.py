@@ -29,6 +29,8 @@ reference's `dspsr -E <par> ... <IFall.fil>` stage) of SIGPROC filterbank files,
   four products of every burst (``burst_spectra``: frbch_burstspec_host), the Faraday dispersion function of Q and U by an
   integer, bit-reproducible transform (``rm_synthesis``: frbch_rmsynth_host), its peak -- the rotation measure -- with PA0,
   L/I and V/I (``rm_peaks``), or all of it on rows uploaded once (``burst_rm``: frbch_burst_rm_host).
+* ``polprof_fil`` (``post polprof``, ``post rmsynth --profile``) draws the burst against time at that RM: I, debiased L, V and the
+  position angle per time bin, (Q, U) of every channel rotated back and summed over the band (``pol_profile``: frbch_polprof_host).
 There is no CPU fallback: the sums run in libfrbch.so on a gfx950 device.
 """
 from __future__ import annotations
@@ -1981,12 +1983,14 @@ def _rm_png(path, hdr, r, i, rmsf, phi):
 
 def rmsynth_fil(filterbankfile, bursts=None, dm1=None, dm2=0.0, dmstep=1.0, width=0, off_gap=None, off_len=None, phi_max=0.0, dphi=0.0,
                 nphi=0, flag_file=None, gains=None, products="stokes", threshold=8.0, max_cands=8, device=0, lib=None,
-                info: dict | None = None):
+                info: dict | None = None, profile=False, nbin=256, tfactor=1):
     """Rotation measure of the bursts of a full-Stokes filterbank: ``bursts`` = (dm, sample, width) tuples; or, with ``dm1 ..
     dm2 .. dmstep`` and no bursts, the ``max_cands`` strongest groups ``candidates_fil``'s search finds on product 0 above
     ``threshold`` (the search writes its ``.singlepulse`` files, as ``search_fil`` does).  ``gains``: an .npy file or an array [4][nchans]; ``flag_file``: channels left out of the transform.  The
     grid: ``rm_grid``.  Writes ``<base>_rm.npz`` (spec, noise, used, phi, F, rmsf, results, bursts), ``<base>_rm.txt`` (one
-    line per burst: RM +- err, L/I debiased, V/I, PA0) and ``<base>_rm_burst<i>.png``.  Returns (files, RM_RESULT records)."""
+    line per burst: RM +- err, L/I debiased, V/I, PA0) and ``<base>_rm_burst<i>.png``.  ``profile=True``: each burst's
+    polarisation profile at its fitted RM as well (``nbin`` bins of ``tfactor`` rows), in the files of ``polprof_fil``.  Returns
+    (files, RM_RESULT records)."""
     lib = lib or _lib.load()
     fil = sigproc.read_fil(filterbankfile)
     hdr = fil.header
@@ -2021,9 +2025,124 @@ def rmsynth_fil(filterbankfile, bursts=None, dm1=None, dm2=0.0, dmstep=1.0, widt
             f.write(RM_ROW % ("burst%d" % i, c["dm"], int(c["sample"]), res["rm"], res["rm_err"], li, vi, np.degrees(res["pa0"]), res["snr"]) + "\n")
             _rm_png(base + "_rm_burst%d.png" % i, hdr, r, i, rmsf[i], phi)
             files.append(base + "_rm_burst%d.png" % i)
+    if profile:
+        prof = pol_profile(fil, hdr, cands, r["results"]["rm"], nbin=nbin, tfactor=tfactor, gains=gains, flag=flag, products=products,
+                           device=device, lib=lib)
+        files += _polprof_write(base, hdr, cands, r["results"]["rm"], prof, tfactor)
     if info is not None:
         info.update(rinfo, nphi=n_phi, phi_lo=phi_lo, dphi=d_phi)
     return files, r["results"]
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# polarisation profile of a burst: derotated I, L, V and PA per time bin (frbch_polprof_*)
+# ------------------------------------------------------------------------------------------------------------------
+PROF_BIN = np.dtype([("i", "<f8"), ("q", "<f8"), ("u", "<f8"), ("v", "<f8"), ("l", "<f8"), ("l_db", "<f8"), ("pa", "<f8"),
+                     ("pa_err", "<f8"), ("hits", "<u4"), ("pa_valid", "<u4")])
+PROF_RESULT = np.dtype([("sigma_i", "<f8"), ("sigma_q", "<f8"), ("sigma_u", "<f8"), ("sigma_v", "<f8"), ("sigma_l", "<f8"),
+                        ("lref", "<f8"), ("k", "<i4"), ("nused", "<u4"), ("on_lo_bin", "<u4"), ("on_hi_bin", "<u4")])
+PROF_ROW = "%.9f %.6g %.6g %.6g %.4f %.4f"
+
+
+def prof_params(nbin: int, tfactor: int, ref="mean") -> _lib.FrbchProfParams:
+    if ref not in ("mean", "zero", _lib.PROF_REF_MEAN, _lib.PROF_REF_ZERO):
+        raise InputError("ref must be 'mean' or 'zero'")
+    code = {"mean": _lib.PROF_REF_MEAN, "zero": _lib.PROF_REF_ZERO}.get(ref, ref)
+    return _lib.FrbchProfParams(C.sizeof(_lib.FrbchProfParams), int(nbin), int(tfactor), int(code), 0)
+
+
+def pol_profile(fil_or_rows, hdr: dict, cands, rm, nbin: int = 256, tfactor: int = 1, ref="mean", gains=None, flag=None,
+                products: str = "stokes", device: int = 0, lib=None, info: dict | None = None):
+    """The polarisation profile of every burst at its RM (frbch_polprof_host; include/frbch.h states the arithmetic): ``nbin``
+    bins of ``tfactor`` rows about ``sample`` at the burst's DM, every channel's baseline removed, (Q, U) rotated back by
+    ``rm[i]`` to ``ref`` ('mean': the mean lambda^2 of the used channels, 'zero': infinite frequency) and summed over the band
+    -> dict(acc int64 [n][nbin][4], hits [n][nbin], bins PROF_BIN [n][nbin], results PROF_RESULT [n], used [n][nchans]).
+    ``info['kernel_used']``: 1 = the fast kernel, 0 = the generic one; ``info['spectra_kernel_used']``: the burst sums'."""
+    lib = lib or _lib.load()
+    rows, nrows, cands, par, g = _burst_args(fil_or_rows, hdr, cands, gains, products)
+    n, nchan = cands.size, hdr["nchans"]
+    rm = np.ascontiguousarray(np.broadcast_to(np.asarray(rm, dtype=np.float64), (n,)))
+    fl = None if flag is None else np.ascontiguousarray(flag, dtype=np.uint8)
+    if fl is not None and fl.shape != (nchan,):
+        raise InputError("flag must have the shape [nchans]")
+    ppar = prof_params(nbin, tfactor, ref)
+    nb = max(1, min(int(nbin), 1024))
+    acc = np.zeros((n, nb, 4), np.int64)
+    hits = np.zeros((n, nb), np.uint32)
+    bins = np.zeros((n, nb), dtype=PROF_BIN)
+    res = np.zeros(n, dtype=PROF_RESULT)
+    used = np.zeros((n, nchan), np.uint8)
+    k = (C.c_uint32 * 2)(0, 0)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_polprof_host(C.byref(fil_desc(hdr, hdr.get("product", 0))), rows.ctypes.data, nrows, C.byref(par), cands.ctypes.data, n,
+                                  rm.ctypes.data, g.ctypes.data if g is not None else None, fl.ctypes.data if fl is not None else None,
+                                  C.byref(ppar), device, acc.ctypes.data, hits.ctypes.data, bins.ctypes.data, res.ctypes.data,
+                                  used.ctypes.data, k, err, len(err)), err)
+    if info is not None:
+        info.update(spectra_kernel_used=k[0], kernel_used=k[1])
+    return dict(acc=acc, hits=hits, bins=bins, results=res, used=used)
+
+
+def _polprof_png(path, bins):
+    """above: the PA of the bins with a valid one, -90 .. 90 degrees bottom to top; below: I, L (debiased) and V on one scale"""
+    width, height = 512, 96
+    n = bins.size
+    top = np.zeros((height, width))
+    for j in np.flatnonzero(bins["pa_valid"] != 0):
+        x = min(width - 1, int((j + 0.5) * width / n))
+        deg = min(90.0, max(-90.0, float(np.degrees(bins["pa"][j]))))
+        top[(height - 1) - int(round((deg + 90.0) / 180.0 * (height - 1))), x] = 1.0
+    low = _curve_panel([bins["i"], bins["l_db"], bins["v"]], width, height)
+    write_png(path, np.concatenate([top, np.zeros((4, width)), low], axis=0))
+
+
+def _polprof_write(base, hdr, cands, rm, prof, tfactor, ref="mean"):
+    """-> the files: <base>_polprof.npz, <base>_polprof.txt (per burst a '#' line, then one line per bin: the time of the bin's
+    centre at the top of the band in seconds, I, L debiased, V, PA and its error in degrees, nan without a valid PA) and
+    <base>_polprof_burst<i>.png"""
+    files = [base + "_polprof.npz", base + "_polprof.txt"]
+    rm = np.broadcast_to(np.asarray(rm, dtype=np.float64), (cands.size,))
+    nbin = prof["bins"].shape[1]
+    np.savez(files[0], acc=prof["acc"], hits=prof["hits"], bins=prof["bins"], results=prof["results"], used=prof["used"], bursts=cands,
+             rm=np.array(rm), tfactor=np.int64(tfactor), ref=np.array(str(ref)))
+    with open(files[1], "w") as f:
+        for i, c in enumerate(cands):
+            r = prof["results"][i]
+            f.write("# burst%d  DM %.3f  sample %d  RM %+.3f  nbin %d  tfactor %d  ref %s  sigma_I %.6g  sigma_L %.6g  on-pulse bins %d..%d\n"
+                    % (i, c["dm"], int(c["sample"]), rm[i], nbin, tfactor, ref, r["sigma_i"], r["sigma_l"], r["on_lo_bin"], r["on_hi_bin"]))
+            t0 = int(c["sample"]) - (nbin // 2) * int(tfactor)
+            for j, b in enumerate(prof["bins"][i]):
+                ok = b["pa_valid"] != 0
+                f.write(PROF_ROW % ((t0 + (j + 0.5) * tfactor) * hdr["tsamp"], b["i"], b["l_db"], b["v"],
+                                    np.degrees(b["pa"]) if ok else np.nan, np.degrees(b["pa_err"]) if ok else np.nan) + "\n")
+            _polprof_png(base + "_polprof_burst%d.png" % i, prof["bins"][i])
+            files.append(base + "_polprof_burst%d.png" % i)
+    return files
+
+
+def polprof_fil(filterbankfile, bursts=None, rm=None, nbin=256, tfactor=1, ref="mean", off_gap=None, off_len=None, flag_file=None,
+                gains=None, products="stokes", rm_from=None, device=0, lib=None, info: dict | None = None):
+    """Polarisation profiles of the bursts of a full-Stokes filterbank: ``bursts`` = (dm, sample, width) tuples with ``rm`` (one
+    value or one per burst), or ``rm_from`` = the ``<base>_rm.npz`` that ``rmsynth_fil`` wrote (its bursts and fitted RMs).
+    Writes ``<base>_polprof.npz / .txt`` and ``<base>_polprof_burst<i>.png``.  Returns (files, what ``pol_profile`` returns)."""
+    lib = lib or _lib.load()
+    fil = sigproc.read_fil(filterbankfile)
+    hdr = fil.header
+    if hdr.get("nifs", 1) != 4:
+        raise InputError("polprof needs a four-product file (pol_mode 4 or 5)")
+    if rm_from:
+        back = np.load(rm_from)
+        cands, rm = np.ascontiguousarray(back["bursts"]), back["results"]["rm"]
+    else:
+        if not bursts or rm is None:
+            raise InputError("give bursts (--dm --sample/--time --width) with --rm, or --rm-from")
+        cands = burst_cands(bursts, off_gap, off_len)
+    flag = read_flag_file(flag_file, hdr["nchans"]).astype(np.uint8) if flag_file else None
+    if isinstance(gains, str):
+        gains = np.load(gains)
+    prof = pol_profile(fil, hdr, cands, rm, nbin=nbin, tfactor=tfactor, ref=ref, gains=gains, flag=flag, products=products,
+                       device=device, lib=lib, info=info)
+    return _polprof_write(filterbankfile.replace(".fil", ""), hdr, cands, rm, prof, tfactor, ref), prof
 
 
 def main(argv=None):
@@ -2033,7 +2152,8 @@ def main(argv=None):
     ``... psearch <fil> --dm <dm> [--dm2 --dmstep --sigma --nharm --flo --nfft --wblock --dm-gap --max-cands --fold-best K --amax A --astep S --acc-gap G]`` /
     ``... rfifind <fil> [--block-rows --t-cell --t-chan --chan-frac --block-frac --flag FILE --write-clean]`` /
     ``... rmsynth <fil> (--dm D --sample S | --time T) --width W [--off-gap G --off-len L] [--phi-max X --dphi Y | --nphi N] [--flag FILE]
-    [--gains FILE.npy] [--products stokes|coherency]`` (burst options repeatable; or ``--dm .. --dm2 .. --dmstep ..`` to search for them)
+    [--gains FILE.npy] [--products stokes|coherency] [--profile --nbin N --tfactor F]`` (burst options repeatable; or ``--dm .. --dm2 .. --dmstep ..`` to search for them) /
+    ``... polprof <fil> (--dm D (--sample S | --time T) --width W --rm R | --rm-from BASE_rm.npz) [--nbin N --tfactor F --ref mean|zero --flag FILE --gains FILE.npy --coherency]``
     (``search`` and ``candidates`` take ``--flag FILE`` and ``--rfi``; ``search``, ``candidates`` and ``rfifind`` take ``--resident``:
     one upload of the rows per command; ``rfifind --periodic [--t-freq S]`` and ``--rfi --periodic`` add the periodicity test): the stages
     as commands, for the places where base2fil.sh / process_vdif.py launch dspsr and prepdata"""
@@ -2152,8 +2272,43 @@ def main(argv=None):
     m.add_argument("--gains", default=None, help=".npy file [4][nchans] of gains that multiply the spectra")
     m.add_argument("--products", choices=("coherency", "stokes"), default="stokes", help="what the file holds: I, Q, U, V or the -d4 products")
     m.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
+    m.add_argument("--profile", action="store_true", help="also write each burst's polarisation profile at its fitted RM (the files of `polprof`)")
+    m.add_argument("--nbin", type=int, default=256, help="bins of --profile")
+    m.add_argument("--tfactor", type=int, default=1, help="rows per bin of --profile")
+    f = sub.add_parser("polprof", help="polarisation profile of the bursts of a full-Stokes filterbank: derotated I, L, V and PA per time bin")
+    f.add_argument("fil")
+    f.add_argument("--dm", type=float, action="append", default=None, help="DM of a burst (repeatable, one per burst)")
+    f.add_argument("--sample", type=int, action="append", default=None, help="centre of a burst, row at the top of the band (repeatable)")
+    f.add_argument("--time", type=float, action="append", default=None, help="the same in seconds from the start of the file (repeatable)")
+    f.add_argument("--width", type=int, action="append", default=None, help="on-pulse rows (repeatable; one value serves every burst)")
+    f.add_argument("--rm", type=float, action="append", default=None, help="rotation measure, rad/m2 (repeatable; one value serves every burst)")
+    f.add_argument("--rm-from", default=None, help="<base>_rm.npz of `rmsynth`: its bursts and fitted RMs instead of --dm .. --rm")
+    f.add_argument("--nbin", type=int, default=256, help="time bins (1..1024)")
+    f.add_argument("--tfactor", type=int, default=1, help="rows per bin (1..512)")
+    f.add_argument("--ref", choices=("mean", "zero"), default="mean", help="the PA refers to the mean lambda^2 of the used channels, or to lambda = 0")
+    f.add_argument("--off-gap", type=int, default=None, help="rows between the burst and each off-pulse window (default: 2 widths, at least 16)")
+    f.add_argument("--off-len", type=int, default=None, help="rows of each off-pulse window (default 1024)")
+    f.add_argument("--flag", default=None, help="flag file: channels left out")
+    f.add_argument("--gains", default=None, help=".npy file [4][nchans] of gains")
+    f.add_argument("--coherency", action="store_true", help="the file holds the -d4 products PP, QQ, Re, Im")
+    f.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     a = ap.parse_args(argv)
-    if a.cmd == "rmsynth":
+    if a.cmd == "polprof":
+        bursts, rm = None, None
+        if not a.rm_from:
+            tsamp = sigproc.read_fil(a.fil).header["tsamp"]
+            centres = list(a.sample or []) + [int(round(t / tsamp)) for t in (a.time or [])]
+            widths, rms, dms = a.width or [], a.rm or [], a.dm or []
+            if not centres or len(centres) != len(dms) or len(widths) not in (1, len(centres)) or len(rms) not in (1, len(centres)):
+                raise InputError("polprof: one --sample or --time per --dm, --width and --rm once or once per burst (or --rm-from)")
+            bursts = [(dm, s, widths[i if len(widths) > 1 else 0]) for i, (dm, s) in enumerate(zip(dms, centres))]
+            rm = [rms[i if len(rms) > 1 else 0] for i in range(len(centres))]
+        files, _prof = polprof_fil(a.fil, bursts, rm=rm, nbin=a.nbin, tfactor=a.tfactor, ref=a.ref, off_gap=a.off_gap, off_len=a.off_len,
+                                   flag_file=a.flag, gains=a.gains, products="coherency" if a.coherency else "stokes", rm_from=a.rm_from,
+                                   device=a.device)
+        for path in files:
+            print("wrote", path)
+    elif a.cmd == "rmsynth":
         bursts = None
         if a.dm2 <= 0.0:
             tsamp = sigproc.read_fil(a.fil).header["tsamp"]
@@ -2164,7 +2319,8 @@ def main(argv=None):
             bursts = [(dm, s, widths[i if len(widths) > 1 else 0]) for i, (dm, s) in enumerate(zip(a.dm, centres))]
         files, res = rmsynth_fil(a.fil, bursts, dm1=a.dm[0], dm2=a.dm2, dmstep=a.dmstep, width=(a.width or [0])[0], off_gap=a.off_gap,
                                  off_len=a.off_len, phi_max=a.phi_max, dphi=a.dphi, nphi=a.nphi, flag_file=a.flag, gains=a.gains,
-                                 products=a.products, threshold=a.threshold, max_cands=a.max_cands, device=a.device)
+                                 products=a.products, threshold=a.threshold, max_cands=a.max_cands, device=a.device,
+                                 **(dict(profile=True, nbin=a.nbin, tfactor=a.tfactor) if a.profile else {}))
         for path in files:
             print("wrote", path)
         print(open(files[1]).read(), end="")

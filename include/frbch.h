@@ -811,6 +811,83 @@ int frbch_burst_rm_host(const frbch_fil_desc* fil, const void* rows, uint64_t nr
                         const frbch_rm_params* par, int device, float* spec, float* noise, uint8_t* used, float* F,
                         frbch_rm_result* results, uint32_t* kernel_used, char* err, size_t err_cap);
 
+/* ---- polarisation profile of a burst: derotated I, L, V and PA per time bin ---------------------------
+ * What an RM is measured for: the burst against time at its DM, Q and U of every channel rotated back by the RM and summed
+ * over the band.  n_c(dm), the windows, frbch_burst_sums, used, l2_c, the table C[] / S[] and frac() are those of the burst
+ * polarisation section above; tests/polprof_oracle.py restates what follows in numpy.  Rows must be 8 or 16 bit and nifs 4:
+ * the fixed-point scale below needs an a-priori bound on the samples, which float32 rows do not have.
+ *
+ * Window.  Candidate i: t0_i = sample - (nbin / 2) tfactor (integer division, signed 64 bit).  Bin j < nbin holds the rows
+ *    t0_i + j tfactor + u, u < tfactor, at the top of the band; channel c is read n_c(dm) rows later; a row outside
+ *    0 .. nrows - 1 is absent, adds nothing and is not counted.
+ *
+ * Host preparation (double, ascending c, every operation rounded on its own):
+ *    the burst sums of the candidates (step 1 above, the same kernel), used[i][c] by its rule (gains included), then
+ *    used[i][c] = 0 where flag[c] != 0;  N_i = the number of used channels;
+ *    mean_pc = off_sum / off_hits;  g_pc = gain[p][c] (NULL: 1);  gmax_i = the largest |g_pc| over used c and p < 4;
+ *    M_i = (double)tfactor 2^nbits gmax_i = f 2^e, f in [0.5, 1) (frexp);  k_i = 22 - e;
+ *    N_i = 0 or gmax_i = 0: every acc, hit and bin of the candidate is 0, and of its result only nused and on_lo_bin /
+ *    on_hi_bin are set.
+ *    lref_i = l0_i of step 2 above (ref = FRBCH_PROF_REF_MEAN) or 0 (FRBCH_PROF_REF_ZERO: the PA at infinite frequency);
+ *    a_ic = (l2_c - lref_i) / pi;  ph_ic = (uint64)(frac(rm_i a_ic) 2^64), a product of 2^64 counts as 0;
+ *    j_ic = ((ph_ic + 2^49) >> 50) mod 2^14;  Cc_ic = C[j_ic], Sc_ic = S[j_ic].
+ *
+ * Device.  For every used c and every bin j with h > 0, h = the number of present rows of the bin in channel c (the same
+ *    in all four products):
+ *      S_p = the integer sum of the present samples of product p (exact: 512 x 65535 < 2^25);
+ *      x_p = ((double)S_p - (double)h mean_pc) g_pc   (three roundings, no FMA);
+ *      coherency order: xI = x0 + x1, xQ = 2 x2, xU = 2 x3, xV = x0 - x1;  Stokes order: as they are;
+ *      X_p = (int64)rint(x_p 2^k_i), ties to even (the scaling by a power of two is exact);
+ *      acc[i][j] += (X_I,  X_Q Cc + X_U Sc,  X_U Cc - X_Q Sc,  X_V);   hits[i][j] += h.
+ *    |x_p| <= tfactor 2^nbits gmax < 2^e, so |X| <= 2^22 (2^23 after the coherency combinations) and |C| <= 2^22: at most
+ *    2^46 per channel and 2^60 over nchan <= 16384 channels.  acc (int64 [ncand][nbin][4]: I, Re, Im, V) and hits (uint32
+ *    [ncand][nbin]) are exact in any order of summation: both kernels and the restatement give the same bits.
+ *
+ * Host derivation into frbch_prof_bin [ncand][nbin] (double, every operation rounded on its own; 0 where hits = 0):
+ *      I = acc_I 2^-k / hits,  V = acc_V 2^-k / hits,  Q = acc_Re 2^-(k+22) / hits,  U = acc_Im 2^-(k+22) / hits;
+ *      L = sqrt(Q Q + U U);  L_db = sqrt(L L - sigma_L^2) where L >= 1.57 sigma_L, else 0;  pa = atan2(U, Q) / 2;
+ *      pa_err = sigma_L / (2 L_db) and pa_valid = 1 where L_db > 0, else both 0.
+ *    frbch_prof_result [ncand]: w_pc = (g_pc g_pc) var_off_pc (var_off of step 1 above); Stokes order: W_p = w_p; coherency
+ *    order: W_I = W_V = w_0 + w_1, W_Q = 4 w_2, W_U = 4 w_3;
+ *      sigma_p = sqrt((double)tfactor sum over used c of W_pc) / ((double)N_i (double)tfactor)   (the noise of a complete bin),
+ *      sigma_l = sqrt((sigma_q^2 + sigma_u^2) / 2);  nused = N_i;  lref;  k;
+ *      on_lo_bin / on_hi_bin = floor((on_lo - t0) / tfactor) and floor((on_lo + width - 1 - t0) / tfactor), each limited to
+ *      0 .. nbin - 1: the bins that the candidate's on-pulse window covers.
+ *    Only pa goes through libm's atan2.
+ *
+ * kernel_used[2] (may be NULL): the burst-sums kernel, and the profile kernel: 1 = the fast one (the conditions of the fast
+ * burst-sums kernel; one workgroup per (64-byte channel tile, run of bins, candidate) stages the rows its bins need -- the
+ * run plus the tile's delay spread -- into the LDS, one thread per (channel, bin), a join adds the tiles), 0 = the generic
+ * one (one thread per (candidate, bin)).  A tile whose delay spread leaves no room for one bin in the LDS (tfactor + spread >
+ * 256 rows) sends the whole call to the generic kernel, and so do tile partials of more than 2^30 bytes (ncand x tiles x nbin
+ * x 36).  Both give the same bits.
+ * FRBCH_E_ARG: a wrong `size`, nifs != 4, float rows, nbin outside 1..1024, tfactor outside 1..512, ref > 1, nchan > 16384,
+ * ncand outside 1..4096, ncand * nbin > 2^22, an rm that is not finite or beyond 1e7 in size, and every refusal of step 1. */
+#define FRBCH_PROF_REF_MEAN 0u
+#define FRBCH_PROF_REF_ZERO 1u
+typedef struct frbch_prof_params { uint32_t size, nbin, tfactor, ref, reserved; } frbch_prof_params;   /* size = sizeof(frbch_prof_params) */
+typedef struct frbch_prof_bin { double i, q, u, v, l, l_db, pa, pa_err; uint32_t hits, pa_valid; } frbch_prof_bin;
+typedef struct frbch_prof_result {
+  double sigma_i, sigma_q, sigma_u, sigma_v, sigma_l, lref;
+  int32_t k;
+  uint32_t nused, on_lo_bin, on_hi_bin;
+} frbch_prof_result;
+/* The plan rule (host only, nothing runs): 1 = fast, 0 = generic, < 0 = refused; only the ADDRESS of d_rows is examined. */
+int frbch_polprof_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                         const frbch_burst_cand* cands, uint32_t ncand, const frbch_prof_params* par);
+/* d_rows is device memory, never written; everything else is host memory: rm [ncand], gain [4][nchan] and flag [nchan] (each
+ * may be NULL), and the outputs acc [ncand][nbin][4], hits [ncand][nbin], bins [ncand][nbin], results [ncand], used
+ * [ncand][nchan] (each may be NULL).  One device scope. */
+int frbch_polprof_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                         const frbch_burst_cand* cands, uint32_t ncand, const double* rm, const float* gain, const uint8_t* flag,
+                         const frbch_prof_params* par, int device, int64_t* acc, uint32_t* hits, frbch_prof_bin* bins,
+                         frbch_prof_result* results, uint8_t* used, uint32_t* kernel_used, char* err, size_t err_cap);
+/* the same with host rows: one upload */
+int frbch_polprof_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* bpar,
+                       const frbch_burst_cand* cands, uint32_t ncand, const double* rm, const float* gain, const uint8_t* flag,
+                       const frbch_prof_params* par, int device, int64_t* acc, uint32_t* hits, frbch_prof_bin* bins,
+                       frbch_prof_result* results, uint8_t* used, uint32_t* kernel_used, char* err, size_t err_cap);
+
 /* ---- interference: block statistics, the mask, cleaned rows --------------------------------------
  * The reference carries a flag file through to Heimdall and FETCH (create_config.py:54-56 `-F/--flag`, frb.conf:50,
  * base2fil.sh:226,425-432, submit_job.py:117 `<Tel>.flag_<fmin>-<fmax>MHz_<nchan>chan`) and leaves making one to a person.
