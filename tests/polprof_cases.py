@@ -190,3 +190,63 @@ def check_known(bins, res, injected):
     print("known answer: %d bins, largest |PA - injected| / (4 pa_err) = %.3f, sigma_L = %.4f" % (strong.size, worst.max(), sl))
     assert (worst <= 1.0).all(), (strong, diff, bins["pa_err"][strong])
     return strong.size
+
+
+# ---- rows past a byte mark -------------------------------------------------------------------------------------------
+def check_beyond_the_mark(lib, br, mem, behind, front, off_len, nbin, tfactor, kernels):
+    """The profile on the rows of a tests/big_rows.BigRows with four products, four candidates of DM 104: one whose bins begin
+    `behind` rows behind the row of the last byte mark, one centred `front` rows in front of it -- the delays carry the bins of some
+    tiles across the mark inside one run --, one in front of the first mark and one whose bins run off nrows; a burst with its own
+    amplitude in every product lies on the first two.  kernels: (shift of the rows in bytes, the burst-sums kernel, the profile
+    kernel) per pass.  The expected values are the oracle's on the window of rows each candidate reads, the sample moved."""
+    from tests import big_rows as bg
+    res = bg.Resident(br, mem)
+    try:
+        hdr = br.hdr()
+        mark, width, gap = br.byte_mark_rows[-1], 4, 16
+        d = ro.delays(hdr, 104.0)
+        maxd, half, reach = int(d.max()), (nbin // 2) * tfactor, gap + off_len
+        samples = [mark + behind + half, mark - front, min(1000, br.byte_mark_rows[0] // 2), br.nrows - maxd - half // 2]
+        cands = post.burst_cands([(104.0, s, width) for s in samples], gap, off_len)
+        rm = np.array([900.0, -2500.0, 0.0, 1.0e7])
+        c = dict(hdr=hdr, rows=None, cands=cands, coh=False, nbin=nbin, tfactor=tfactor, ref="mean", rm=rm, gain=None, flag=None)
+        t0 = [s - half for s in samples]
+        assert t0[0] >= mark and t0[2] + nbin * tfactor + maxd < br.byte_mark_rows[0] and t0[3] + nbin * tfactor + maxd > br.nrows
+        # candidate 1: a run of bins of some tile is staged from rows on both sides of the mark
+        ct = 64 // br.dtype.itemsize
+        dt = d.reshape(-1, ct)
+        spread = int((dt.max(axis=1) - dt.min(axis=1)).max())
+        brun = min(nbin, (256 - spread) // tfactor)
+        firsts = [t0[1] + j0 * tfactor + dt.min(axis=1) for j0 in range(0, nbin, brun)]
+        lasts = [t0[1] + min(nbin, j0 + brun) * tfactor + dt.max(axis=1) for j0 in range(0, nbin, brun)]
+        assert brun >= 1 and any(((a < mark) & (mark < b)).any() for a, b in zip(firsts, lasts))
+        for shift, k_spec, k_prof in kernels:
+            res.lay(shift)
+            for i in (0, 1):
+                for prod, amp in enumerate((9, 5, 3, 2)):
+                    bg.write_burst(res, prod, 104.0, samples[i] - width // 2, width, amp)
+            wants = []
+            for i, cd in enumerate(cands):
+                on_lo = samples[i] - width // 2
+                w0 = max(0, min(on_lo - reach, t0[i]))
+                w1 = min(br.nrows, max(on_lo + width + reach, t0[i] + nbin * tfactor) + maxd + 1)
+                moved = cands[i:i + 1].copy()
+                moved["sample"] -= w0
+                wants.append(ppo.profile(res.window(w0, w1 - w0), hdr, moved, rm[i:i + 1], nbin, tfactor, "mean"))
+            want = {f: np.concatenate([w[f] for w in wants]) for f in wants[0]}
+            assert want["used"].all() and (want["hits"][:3] == br.nchan * tfactor).all()
+            assert 0 < want["hits"][3, -1] < want["hits"][3, 0] == br.nchan * tfactor                # the last bins lose rows behind nrows
+            r = want["results"]
+            assert all(want["bins"]["i"][i, r["on_lo_bin"][i]] > 5.0 for i in (0, 1)) and abs(want["bins"]["i"][2]).max() < 1.0      # the burst is seen
+            ptr = C.c_void_p(res.address)
+            q = lib.frbch_polprof_kernel(C.byref(post.fil_desc(hdr)), ptr, br.nrows, C.byref(rc.burst_par(False)), cands.ctypes.data, cands.size,
+                                         C.byref(par_of(c)))
+            with bg.guarded():
+                code, msg, out, k = call(lib.frbch_polprof_device, c, ptr, nrows=br.nrows, out=outputs(cands.size, nbin, br.nchan, fill=0xA5))
+            assert code == 0, msg
+            assert k == (k_spec, k_prof) and q == k_prof, (shift, k, q)
+            assert same(out, want), shift
+            res.buf.check()
+        res.check_equals()                                   # the rows are never written
+    finally:
+        res.free()
