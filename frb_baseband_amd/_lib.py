@@ -165,6 +165,23 @@ class FrbchProfResult(C.Structure):
                 ("on_hi_bin", C.c_uint32)]
 
 
+class FrbchDmscanParams(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("ntrial", C.c_uint32), ("nbin", C.c_uint32), ("tfactor", C.c_uint32), ("ddm", C.c_double)]
+
+
+class FrbchDmscanPeakParams(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("nwidth", C.c_uint32), ("widths", C.c_uint32 * 16), ("smooth", C.c_uint32),
+                ("reserved", C.c_uint32), ("fit_frac", C.c_double)]
+
+
+class FrbchDmscanResult(C.Structure):
+    _fields_ = [("dm_snr", C.c_double), ("dm_snr_err", C.c_double), ("dm_struct", C.c_double), ("snr_peak", C.c_double),
+                ("struct_peak", C.c_double), ("snr_at_struct", C.c_double), ("k_snr", C.c_uint32), ("width_snr", C.c_uint32),
+                ("bin_snr", C.c_uint32), ("nfit_snr", C.c_uint32), ("fitted_snr", C.c_uint32), ("k_struct", C.c_uint32),
+                ("width_struct", C.c_uint32), ("bin_struct", C.c_uint32), ("nfit_struct", C.c_uint32), ("fitted_struct", C.c_uint32),
+                ("k", C.c_int32), ("nused", C.c_uint32)]
+
+
 class FrbchRfiParams(C.Structure):
     _fields_ = [("size", C.c_uint32), ("block_rows", C.c_uint32), ("t_cell", C.c_double), ("t_chan", C.c_double),
                 ("chan_frac", C.c_double), ("block_frac", C.c_double)]
@@ -322,6 +339,17 @@ SYMBOLS = {
                                        C.POINTER(FrbchProfParams), C.c_int, _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
     "frbch_polprof_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32, _P, _P, _P,
                                      C.POINTER(FrbchProfParams), C.c_int, _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "frbch_dm_sample_step": (C.c_double, [C.POINTER(FrbchFilDesc)]),
+    "frbch_dmscan_kernel": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32,
+                                      C.POINTER(FrbchDmscanParams)]),
+    "frbch_dmscan_peaks": (C.c_int, [C.POINTER(FrbchDmscanParams), C.POINTER(FrbchDmscanPeakParams), _P, C.c_uint32, _P, _P, _P, _P, _P, _P,
+                                     _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "frbch_dmscan_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32, _P,
+                                      C.POINTER(FrbchDmscanParams), C.POINTER(FrbchDmscanPeakParams), C.c_int, _P, _P, _P, _P, _P, _P, _P,
+                                      C.c_char_p, C.c_size_t]),
+    "frbch_dmscan_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32, _P,
+                                    C.POINTER(FrbchDmscanParams), C.POINTER(FrbchDmscanPeakParams), C.c_int, _P, _P, _P, _P, _P, _P, _P,
+                                    C.c_char_p, C.c_size_t]),
     "frbch_rfi_nblk": (C.c_long, [C.c_uint64, C.c_uint32]),
     "frbch_rfi_stats_kernel": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams)]),
     "frbch_rfi_stats_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams), C.c_int, _P,

@@ -4174,3 +4174,471 @@ extern "C" int frbch_polprof_host(const frbch_fil_desc* fil, const void* rows, u
     return frbch_polprof_device(fil, d_rows, nrows, bpar, cands, ncand, rm, gain, flag, par, device, acc, hits, bins, results, used, kernel_used, err, err_cap);
   });
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// DM of a burst: fine DM scan, S/N and structure maxima (include/frbch.h states the arithmetic)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr uint32_t kDmMaxTrial = 4096, kDmMaxBin = 1024, kDmMaxTf = 512, kDmMaxWidths = 16;
+constexpr uint64_t kDmMaxOut = 1ull << 24, kDmPartCap = 1ull << 30;
+
+int dm_check(const frbch_fil_desc* fil, uint64_t nrows, const frbch_burst_params* bpar, const frbch_burst_cand* cands,
+             uint32_t ncand, const frbch_dmscan_params* par, const PostErr& e) {
+  const int rc = burst_check(fil, nrows, bpar, cands, ncand, e);
+  if (rc) return rc;
+  if (fil->nbits == 32) return e.fail(FRBCH_E_ARG, "the DM scan is not built for float32 rows: its fixed-point scale needs a bound on the samples");
+  if (!par || par->size != sizeof(frbch_dmscan_params)) return e.fail(FRBCH_E_ARG, "frbch_dmscan_params: wrong size");
+  if (par->ntrial < 1 || par->ntrial > kDmMaxTrial) return e.fail(FRBCH_E_ARG, "ntrial must be 1..4096");
+  if (par->nbin < 1 || par->nbin > kDmMaxBin) return e.fail(FRBCH_E_ARG, "nbin must be 1..1024");
+  if (par->tfactor < 1 || par->tfactor > kDmMaxTf) return e.fail(FRBCH_E_ARG, "tfactor must be 1..512");
+  if (par->ntrial > 1 && (!(par->ddm > 0.0) || !rm_finite(par->ddm))) return e.fail(FRBCH_E_ARG, "ddm must be finite and above 0");
+  if (fil->nchan > kRmMaxChan) return e.fail(FRBCH_E_ARG, "more than 16384 channels");
+  if ((uint64_t)ncand * par->ntrial * fil->nchan > kCutTableCap) return e.fail(FRBCH_E_ARG, "ncand * ntrial * nchan exceeds 2^26: cut the batch or the scan");
+  if ((uint64_t)ncand * par->ntrial * par->nbin > kDmMaxOut) return e.fail(FRBCH_E_ARG, "ncand * ntrial * nbin exceeds 2^24: cut the batch or the scan");
+  return FRBCH_OK;
+}
+
+int dm_check_peaks(const frbch_dmscan_params* par, const frbch_dmscan_peak_params* pk, const PostErr& e) {
+  if (!pk || pk->size != sizeof(frbch_dmscan_peak_params)) return e.fail(FRBCH_E_ARG, "frbch_dmscan_peak_params: wrong size");
+  if (pk->nwidth < 1 || pk->nwidth > kDmMaxWidths) return e.fail(FRBCH_E_ARG, "nwidth must be 1..16");
+  for (uint32_t i = 0; i < pk->nwidth; ++i)
+    if (pk->widths[i] < 1 || pk->widths[i] > par->nbin || (i && pk->widths[i] <= pk->widths[i - 1]))
+      return e.fail(FRBCH_E_ARG, "the widths must ascend within 1..nbin");
+  if (par->nbin > 1 && (pk->smooth < 1 || pk->smooth > par->nbin - 1)) return e.fail(FRBCH_E_ARG, "smooth must be 1..nbin - 1");
+  if (!(pk->fit_frac > 0.0) || !(pk->fit_frac < 1.0)) return e.fail(FRBCH_E_ARG, "fit_frac must lie inside (0, 1)");
+  return FRBCH_OK;
+}
+
+// dm_k of every candidate, [ncand][ntrial]; a value outside [0, 1e5) is refused
+int dm_trials(const frbch_burst_cand* cands, uint32_t ncand, const frbch_dmscan_params* par, std::vector<double>* dms, const PostErr& e) {
+  POST_NO_CONTRACT
+  dms->resize((size_t)ncand * par->ntrial);
+  const double kc = (double)(par->ntrial / 2);
+  for (uint32_t i = 0; i < ncand; ++i)
+    for (uint32_t k = 0; k < par->ntrial; ++k) {
+      double dm = cands[i].dm;
+      if (par->ntrial > 1) {
+        const double off = ((double)k - kc) * par->ddm;
+        dm = cands[i].dm + off;
+      }
+      if (!(dm >= 0.0) || !(dm < 1.0e5)) return e.fail(FRBCH_E_ARG, "candidate " + std::to_string(i) + ": a trial DM outside [0, 1e5)");
+      (*dms)[(size_t)i * par->ntrial + k] = dm;
+    }
+  return FRBCH_OK;
+}
+
+// the trial DMs and their delay table [ncand][ntrial][nchan]
+int dm_build(const frbch_fil_desc* fil, const frbch_burst_cand* cands, uint32_t ncand, const frbch_dmscan_params* par,
+             std::vector<double>* dms, std::vector<int32_t>* delays, const PostErr& e) {
+  const int rc = dm_trials(cands, ncand, par, dms, e);
+  if (rc) return rc;
+  int64_t maxd = 0;
+  *delays = post_delays(fil, dms->data(), (uint32_t)dms->size(), &maxd);
+  if (maxd > (int64_t)1 << 30) return e.fail(FRBCH_E_ARG, "a dispersion delay of more than 2^30 samples");
+  return FRBCH_OK;
+}
+
+// The plan rule of the scan -- the one decision behind frbch_dmscan_device's launches, kernel_used[1] and
+// frbch_dmscan_kernel's answer.  The fast kernel wants the layout of the fast burst-sums kernel (only the ADDRESS of d_rows is
+// examined), bins of at most kDmMaxT rows, a trial run -- the largest of 16, 8, 4, 2, 1 within ntrial -- whose delay range
+// over any 64-byte tile of any candidate leaves room for one bin in the stage (tfactor + range <= kDmLds / (64 products)
+// rows), and partials of at most 2^30 bytes; brun = the bins of a run that then fit, the same for every workgroup.  The
+// emulator build has no such kernel: generic.
+struct DmPlanRule { bool fastk; int trun, brun, ntile; };
+DmPlanRule dm_plan_rule(const frbch_fil_desc* fil, const void* d_rows, uint32_t products, const std::vector<int32_t>& delays,
+                        uint32_t ncand, const frbch_dmscan_params* par) {
+  DmPlanRule r{false, 0, 0, 0};
+#ifndef FRBCH_NO_FAST
+  if (!burst_fast_layout(fil, d_rows) || par->tfactor > (uint32_t)fast::kDmMaxT) return r;
+  const uint32_t ct = 64u / (uint32_t)(fil->nbits / 8), ntile = fil->nchan / ct, nt = par->ntrial;
+  const int64_t cap = (int64_t)(fast::kDmLds / (64u * (products == FRBCH_BURST_COHERENCY ? 2u : 1u)));
+  if ((uint64_t)ncand * ntile * nt * par->nbin * 12ull > kDmPartCap) return r;
+  // smallest and largest delay of every (candidate, trial, tile)
+  std::vector<int32_t> lo((size_t)ncand * nt * ntile), hi(lo.size());
+  for (size_t ik = 0; ik < (size_t)ncand * nt; ++ik)
+    for (uint32_t t = 0; t < ntile; ++t) {
+      const int32_t* d = delays.data() + ik * fil->nchan + (size_t)t * ct;
+      const auto mm = std::minmax_element(d, d + ct);
+      lo[ik * ntile + t] = *mm.first;
+      hi[ik * ntile + t] = *mm.second;
+    }
+  for (uint32_t trun = (uint32_t)fast::kDmTrun; trun >= 1; trun /= 2) {
+    if (trun > nt && trun > 1) continue;
+    int64_t range = 0;
+    for (uint32_t i = 0; i < ncand; ++i)
+      for (uint32_t k0 = 0; k0 < nt; k0 += trun)
+        for (uint32_t t = 0; t < ntile; ++t) {
+          int32_t a = INT32_MAX, b = INT32_MIN;
+          for (uint32_t k = k0; k < std::min(nt, k0 + trun); ++k) {
+            a = std::min(a, lo[((size_t)i * nt + k) * ntile + t]);
+            b = std::max(b, hi[((size_t)i * nt + k) * ntile + t]);
+          }
+          range = std::max<int64_t>(range, (int64_t)b - (int64_t)a);
+        }
+    if ((int64_t)par->tfactor + range > cap) continue;
+    r.fastk = true;
+    r.trun = (int)trun;
+    r.brun = (int)std::min<int64_t>((int64_t)par->nbin, (cap - range) / (int64_t)par->tfactor);
+    r.ntile = (int)ntile;
+    return r;
+  }
+#else
+  (void)fil; (void)d_rows; (void)products; (void)delays; (void)ncand; (void)par;
+#endif
+  return r;
+}
+
+struct DmCurves {
+  std::vector<double> snr, strc;
+  std::vector<uint32_t> width, bin;
+  std::vector<frbch_dmscan_result> res;
+};
+
+// B(w, j) of the header from the prefix sums of a trial
+inline double dm_boxcar(const __int128* pa, const uint64_t* ph, uint32_t w, uint32_t j, double inv) {
+  POST_NO_CONTRACT
+  const uint64_t H = ph[j + w] - ph[j];
+  if (!H) return 0.0;
+  const double a = (double)(pa[j + w] - pa[j]);
+  const double b = a * inv;
+  return b / sqrt((double)H);
+}
+
+// the fit of one curve: -> the peak's trial, n, fitted, dm and (err != NULL) the half-width at 1 below the vertex
+void dm_fit(const double* v, uint32_t nt, double fit_frac, const double* dms, double ddm, uint32_t* kpeak, uint32_t* nfit,
+            uint32_t* fitted, double* dm, double* err) {
+  POST_NO_CONTRACT
+  uint32_t kp = 0;
+  for (uint32_t k = 1; k < nt; ++k)
+    if (v[k] > v[kp]) kp = k;
+  *kpeak = kp; *nfit = 0; *fitted = 0; *dm = dms[kp];
+  if (err) *err = 0.0;
+  if (!(v[kp] > 0.0)) return;
+  const double thr = fit_frac * v[kp];
+  uint32_t lo = kp, hi = kp;
+  while (lo > 0 && v[lo - 1] >= thr) --lo;
+  while (hi + 1 < nt && v[hi + 1] >= thr) ++hi;
+  *nfit = hi - lo + 1;
+  if (*nfit < 3 || lo == 0 || hi == nt - 1) return;
+  long long s[5] = {0, 0, 0, 0, 0};
+  double T0 = 0.0, T1 = 0.0, T2 = 0.0;
+  for (uint32_t k = lo; k <= hi; ++k) {
+    const long long x = (long long)k - (long long)kp;
+    s[0] += 1; s[1] += x; s[2] += x * x; s[3] += x * x * x; s[4] += x * x * x * x;
+    const double xv = (double)x * v[k], xxv = (double)(x * x) * v[k];
+    T0 = T0 + v[k];
+    T1 = T1 + xv;
+    T2 = T2 + xxv;
+  }
+  const double S0 = (double)s[0], S1 = (double)s[1], S2 = (double)s[2], S3 = (double)s[3], S4 = (double)s[4];
+  const double m0 = S2 * S0 - S1 * S1, m1 = S3 * S0 - S1 * S2, m2 = S3 * S1 - S2 * S2;
+  const double D = (S4 * m0 - S3 * m1) + S2 * m2;
+  const double p1 = T1 * S0 - S1 * T0, p2 = T1 * S1 - S2 * T0, p3 = S3 * T0 - S2 * T1;
+  const double Da = (T2 * m0 - S3 * p1) + S2 * p2;
+  const double Db = (S4 * p1 - T2 * m1) + S2 * p3;
+  const double a = Da / D, b = Db / D;
+  if (!(a < 0.0)) return;
+  const double vertex = (-b) / (2.0 * a);
+  const double shift = vertex * ddm;
+  *dm = dms[kp] + shift;
+  *fitted = 1;
+  if (err) *err = sqrt(-1.0 / a) * ddm;
+}
+
+// the peaks section of the header; every check has been made
+void dm_peaks(const frbch_dmscan_params* par, const frbch_dmscan_peak_params* pk, const std::vector<double>& dms, uint32_t ncand,
+              const int32_t* kscale, const uint32_t* nused, const int64_t* acc, const uint32_t* hits, DmCurves* out) {
+  POST_NO_CONTRACT
+  const uint32_t nt = par->ntrial, nb = par->nbin;
+  out->snr.assign((size_t)ncand * nt, 0.0);
+  out->strc.assign((size_t)ncand * nt, 0.0);
+  out->width.assign((size_t)ncand * nt, 0);
+  out->bin.assign((size_t)ncand * nt, 0);
+  out->res.assign(ncand, frbch_dmscan_result{});
+  memset((void*)out->res.data(), 0, (size_t)ncand * sizeof(frbch_dmscan_result));
+  std::vector<__int128> pa(nb + 1);
+  std::vector<uint64_t> ph(nb + 1);
+  std::vector<double> z(nb);
+  for (uint32_t i = 0; i < ncand; ++i) {
+    if (!nused[i]) continue;
+    frbch_dmscan_result& r = out->res[i];
+    r.k = kscale[i];
+    r.nused = nused[i];
+    const double inv = ldexp(1.0, -kscale[i]);
+    double* snr = out->snr.data() + (size_t)i * nt;
+    double* strc = out->strc.data() + (size_t)i * nt;
+    uint32_t* wd = out->width.data() + (size_t)i * nt;
+    uint32_t* bn = out->bin.data() + (size_t)i * nt;
+    for (uint32_t k = 0; k < nt; ++k) {
+      const int64_t* a = acc + ((size_t)i * nt + k) * nb;
+      const uint32_t* h = hits + ((size_t)i * nt + k) * nb;
+      pa[0] = 0; ph[0] = 0;
+      for (uint32_t j = 0; j < nb; ++j) { pa[j + 1] = pa[j] + (__int128)a[j]; ph[j + 1] = ph[j] + h[j]; }
+      double best = dm_boxcar(pa.data(), ph.data(), pk->widths[0], 0, inv);
+      uint32_t bw = pk->widths[0], bj = 0;
+      for (uint32_t wi = 0; wi < pk->nwidth; ++wi) {
+        const uint32_t w = pk->widths[wi];
+        for (uint32_t j = 0; j + w <= nb; ++j) {
+          const double B = dm_boxcar(pa.data(), ph.data(), w, j, inv);
+          if (B > best) { best = B; bw = w; bj = j; }
+        }
+      }
+      snr[k] = best; wd[k] = bw; bn[k] = bj;
+      if (nb > 1) {
+        const uint32_t s = pk->smooth;
+        for (uint32_t j = 0; j + s <= nb; ++j) z[j] = dm_boxcar(pa.data(), ph.data(), s, j, inv);
+        double sum = 0.0;
+        for (uint32_t j = 0; j + s < nb; ++j) {
+          const double d = z[j + 1] - z[j];
+          const double dd = d * d;
+          sum = sum + dd;
+        }
+        const double ex = (2.0 * (double)(nb - s)) / (double)s;
+        strc[k] = sum - ex;
+      }
+    }
+    const double* dm = dms.data() + (size_t)i * nt;
+    dm_fit(snr, nt, pk->fit_frac, dm, par->ddm, &r.k_snr, &r.nfit_snr, &r.fitted_snr, &r.dm_snr, &r.dm_snr_err);
+    r.snr_peak = snr[r.k_snr]; r.width_snr = wd[r.k_snr]; r.bin_snr = bn[r.k_snr];
+    if (nb > 1) {
+      dm_fit(strc, nt, pk->fit_frac, dm, par->ddm, &r.k_struct, &r.nfit_struct, &r.fitted_struct, &r.dm_struct, nullptr);
+    } else {
+      r.k_struct = 0; r.dm_struct = dm[0];
+    }
+    r.struct_peak = strc[r.k_struct]; r.snr_at_struct = snr[r.k_struct]; r.width_struct = wd[r.k_struct]; r.bin_struct = bn[r.k_struct];
+  }
+}
+
+struct DmOut {
+  std::vector<long long> acc;
+  std::vector<uint32_t> hits;
+  std::vector<uint8_t> used;
+  DmCurves cv;
+  uint32_t k[2] = {0, 0};
+};
+
+// everything of a call inside its scope: the burst sums, the records, the launches, the peaks (all synchronised)
+int dm_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+           const frbch_burst_cand* cands, uint32_t ncand, const uint8_t* flag, const frbch_dmscan_params* par,
+           const frbch_dmscan_peak_params* pk, PostScope& ps, DmOut* out, const PostErr& e) {
+  POST_NO_CONTRACT
+  const size_t nchan = fil->nchan, n = (size_t)ncand * nchan, nbin = par->nbin, nt = par->ntrial, nifs = fil->nifs;
+  std::vector<double> dms;
+  std::vector<int32_t> delays;
+  int rc = dm_build(fil, cands, ncand, par, &dms, &delays, e);
+  if (rc) return rc;
+  const DmPlanRule rule = dm_plan_rule(fil, d_rows, bpar->products, delays, ncand, par);
+  std::vector<frbch_burst_sums> sums;
+  std::vector<float> spec(n * nifs), noise(n * nifs);
+  std::vector<uint8_t> bused(n);
+  BurstSums* d_sums = nullptr;
+  POST_DEV(ps.alloc(&d_sums, n * nifs * sizeof(BurstSums)), "hipMalloc");
+  if ((rc = burst_run(fil, d_rows, nrows, bpar, cands, ncand, nullptr, d_sums, ps, &sums, spec.data(), noise.data(), bused.data(), &out->k[0], e)) != 0) return rc;
+  ps.drop(d_sums);
+
+  // the records
+  const bool coh = bpar->products == FRBCH_BURST_COHERENCY;
+  const uint32_t p0 = coh ? 0u : fil->product, np = coh ? 2u : 1u;
+  std::vector<DmRec> rec(n);
+  std::vector<DmCand> dc(ncand);
+  std::vector<int32_t> kscale(ncand, 0);
+  std::vector<uint32_t> nused(ncand, 0);
+  memset((void*)rec.data(), 0, n * sizeof(DmRec));
+  out->used.assign(n, 0);
+  for (uint32_t i = 0; i < ncand; ++i) {
+    dc[i].t0 = (long long)cands[i].sample - (long long)(par->nbin / 2) * (long long)par->tfactor;
+    dc[i].scale = 0.0;
+    double wmax = 0.0;
+    for (size_t c = 0; c < nchan; ++c) {
+      bool ok = !(flag && flag[c]);
+      double mean = 0.0, var = 0.0;
+      for (uint32_t p = p0; p < p0 + np; ++p) {
+        const frbch_burst_sums& s = sums[((size_t)i * nifs + p) * nchan + c];
+        if (s.on_hits == 0 || s.off_hits < 2) { ok = false; break; }
+        const double noff = (double)s.off_hits;
+        const double mp = s.off_sum / noff;
+        const double ss = s.off_sum * s.off_sum;
+        const double sn = ss / noff;
+        const double num = s.off_sumsq - sn;
+        double vp = num / (noff - 1.0);
+        if (vp < 0.0) vp = 0.0;
+        mean = p == p0 ? mp : mean + mp;
+        var = p == p0 ? vp : var + vp;
+      }
+      if (!ok || !(var > 0.0)) continue;
+      DmRec& q = rec[(size_t)i * nchan + c];
+      q.mean = mean;
+      q.w = 1.0 / sqrt(var);
+      q.used = 1;
+      out->used[(size_t)i * nchan + c] = 1;
+      ++nused[i];
+      wmax = std::max(wmax, q.w);
+    }
+    if (!nused[i]) continue;
+    double M = ((double)par->tfactor * ldexp(1.0, fil->nbits)) * wmax;
+    if (coh) M = 2.0 * M;
+    int ex = 0;
+    (void)frexp(M, &ex);
+    kscale[i] = 40 - ex;
+    dc[i].scale = ldexp(1.0, kscale[i]);
+  }
+
+  // the launches
+  DmRec* d_rec = nullptr;
+  DmCand* d_dc = nullptr;
+  int32_t* d_dly = nullptr;
+  long long* d_acc = nullptr;
+  uint32_t* d_hits = nullptr;
+  const size_t nout = (size_t)ncand * nt * nbin;
+  POST_DEV(ps.alloc(&d_rec, n * sizeof(DmRec)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_dc, (size_t)ncand * sizeof(DmCand)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_dly, delays.size() * sizeof(int32_t)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_acc, nout * sizeof(long long)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_hits, nout * sizeof(uint32_t)), "hipMalloc");
+  POST_DEV(dev_h2d(d_rec, rec.data(), n * sizeof(DmRec), ps.s), "upload records");
+  POST_DEV(dev_h2d(d_dc, dc.data(), (size_t)ncand * sizeof(DmCand), ps.s), "upload records");
+  POST_DEV(dev_h2d(d_dly, delays.data(), delays.size() * sizeof(int32_t), ps.s), "upload delays");
+  DmParams p = post_params<DmParams>(fil, d_rows, nrows);
+  p.ncand = (int)ncand; p.cand = d_dc; p.rec = d_rec; p.delays = d_dly; p.acc = d_acc; p.hits = d_hits;
+  p.ntrial = (int)par->ntrial; p.nbin = (int)par->nbin; p.tfactor = (int)par->tfactor; p.p0 = (int)p0; p.np = (int)np;
+  p.ntile = rule.ntile; p.trun = rule.trun; p.brun = rule.brun;
+  out->k[1] = rule.fastk ? 1 : 0;
+  bool launched = false;
+#ifndef FRBCH_NO_FAST
+  if (rule.fastk) {
+    long long* d_part = nullptr;
+    uint32_t* d_hpart = nullptr;
+    const size_t npart = nout * (size_t)rule.ntile;
+    POST_DEV(ps.alloc(&d_part, npart * sizeof(long long)), "hipMalloc");
+    POST_DEV(ps.alloc(&d_hpart, npart * sizeof(uint32_t)), "hipMalloc");
+    p.part = d_part; p.hpart = d_hpart;
+    const unsigned nbr = (unsigned)((par->nbin + rule.brun - 1) / rule.brun), ntr = (unsigned)((par->ntrial + rule.trun - 1) / rule.trun);
+    const dim3 grid((unsigned)rule.ntile * nbr, ntr, ncand), block(fast::kDmThreads);
+    int lrc;
+    if (fil->nbits == 8) lrc = coh ? launch_lds(fast::frbch_post_dmscan_fast<1, 2>, grid, block, fast::kDmLds, ps.s, p)
+                                   : launch_lds(fast::frbch_post_dmscan_fast<1, 1>, grid, block, fast::kDmLds, ps.s, p);
+    else lrc = coh ? launch_lds(fast::frbch_post_dmscan_fast<2, 2>, grid, block, fast::kDmLds, ps.s, p)
+                   : launch_lds(fast::frbch_post_dmscan_fast<2, 1>, grid, block, fast::kDmLds, ps.s, p);
+    POST_DEV(lrc, "LDS size");
+    POST_DEV(dev_check_launch(), "launch DM scan");
+    hipLaunchKernelGGL(fast::frbch_post_dmscan_join, dim3((unsigned)((nout + fast::kDmThreads - 1) / fast::kDmThreads)), dim3(fast::kDmThreads), 0, ps.s, p);
+    POST_DEV(dev_check_launch(), "launch DM scan join");
+    launched = true;
+  }
+#endif
+  if (!launched) {
+    DEV_LAUNCH(frbch_post_dmscan, (nout + 255) / 256, 1, 256, 0, ps.s, p);
+    POST_DEV(dev_check_launch(), "launch DM scan");
+  }
+  out->acc.resize(nout);
+  out->hits.resize(nout);
+  POST_DEV(dev_d2h(out->acc.data(), d_acc, nout * sizeof(long long), ps.s), "download DM scan");
+  POST_DEV(dev_d2h(out->hits.data(), d_hits, nout * sizeof(uint32_t), ps.s), "download DM scan");
+  POST_DEV(dev_sync(ps.s), "sync");
+  dm_peaks(par, pk, dms, ncand, kscale.data(), nused.data(), (const int64_t*)out->acc.data(), out->hits.data(), &out->cv);
+  return FRBCH_OK;
+}
+}  // namespace
+
+extern "C" double frbch_dm_sample_step(const frbch_fil_desc* fil) {
+  if (!fil || fil->size != sizeof(frbch_fil_desc) || fil->nchan < 2 || !(fil->tsamp_s > 0) || fil->foff_mhz == 0.0) return 0.0;
+  const double d = post_delay_s(fil, 1.0, fil->foff_mhz < 0 ? fil->nchan - 1 : 0);
+  return d > 0.0 ? fil->tsamp_s / d : 0.0;
+}
+
+extern "C" int frbch_dmscan_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                   const frbch_burst_cand* cands, uint32_t ncand, const frbch_dmscan_params* par) try {
+  PostErr e{nullptr, 0};
+  int rc = dm_check(fil, nrows, bpar, cands, ncand, par, e);
+  if (rc) return rc;
+  if (!d_rows) return FRBCH_E_ARG;
+  std::vector<double> dms;
+  std::vector<int32_t> delays;
+  if ((rc = dm_build(fil, cands, ncand, par, &dms, &delays, e)) != 0) return rc;
+  return dm_plan_rule(fil, d_rows, bpar->products, delays, ncand, par).fastk ? 1 : 0;
+} catch (const std::bad_alloc&) { return FRBCH_E_NOMEM; }
+
+extern "C" int frbch_dmscan_peaks(const frbch_dmscan_params* par, const frbch_dmscan_peak_params* pk, const frbch_burst_cand* cands,
+                                  uint32_t ncand, const int32_t* k, const uint32_t* nused, const int64_t* acc, const uint32_t* hits,
+                                  double* snr, double* strc, uint32_t* width, uint32_t* bin, frbch_dmscan_result* results, char* err,
+                                  size_t err_cap) try {
+  PostErr e{err, err_cap};
+  if (!par || par->size != sizeof(frbch_dmscan_params)) return e.fail(FRBCH_E_ARG, "frbch_dmscan_params: wrong size");
+  if (par->ntrial < 1 || par->ntrial > kDmMaxTrial) return e.fail(FRBCH_E_ARG, "ntrial must be 1..4096");
+  if (par->nbin < 1 || par->nbin > kDmMaxBin) return e.fail(FRBCH_E_ARG, "nbin must be 1..1024");
+  if (par->ntrial > 1 && (!(par->ddm > 0.0) || !rm_finite(par->ddm))) return e.fail(FRBCH_E_ARG, "ddm must be finite and above 0");
+  if (!cands || ncand < 1 || ncand > kBurstMaxCand) return e.fail(FRBCH_E_ARG, "1..4096 candidates");
+  if ((uint64_t)ncand * par->ntrial * par->nbin > kDmMaxOut) return e.fail(FRBCH_E_ARG, "ncand * ntrial * nbin exceeds 2^24: cut the batch or the scan");
+  int rc = dm_check_peaks(par, pk, e);
+  if (rc) return rc;
+  if (!k || !nused || !acc || !hits) return e.fail(FRBCH_E_ARG, "null argument");
+  std::vector<double> dms;
+  if ((rc = dm_trials(cands, ncand, par, &dms, e)) != 0) return rc;
+  DmCurves cv;
+  dm_peaks(par, pk, dms, ncand, k, nused, acc, hits, &cv);
+  const size_t n = (size_t)ncand * par->ntrial;
+  if (snr) memcpy(snr, cv.snr.data(), n * sizeof(double));
+  if (strc) memcpy(strc, cv.strc.data(), n * sizeof(double));
+  if (width) memcpy(width, cv.width.data(), n * sizeof(uint32_t));
+  if (bin) memcpy(bin, cv.bin.data(), n * sizeof(uint32_t));
+  if (results) memcpy((void*)results, cv.res.data(), (size_t)ncand * sizeof(frbch_dmscan_result));
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_dmscan_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                   const frbch_burst_cand* cands, uint32_t ncand, const uint8_t* flag, const frbch_dmscan_params* par,
+                                   const frbch_dmscan_peak_params* pk, int device, int64_t* acc, uint32_t* hits, double* snr,
+                                   double* strc, frbch_dmscan_result* results, uint8_t* used, uint32_t* kernel_used, char* err,
+                                   size_t err_cap) try {
+  static_assert(sizeof(DmRec) == 24 && sizeof(frbch_dmscan_result) == 96 && sizeof(frbch_dmscan_params) == 24 &&
+                sizeof(frbch_dmscan_peak_params) == 88 && sizeof(long long) == sizeof(int64_t), "DM scan records");
+  PostErr e{err, err_cap};
+  int rc = dm_check(fil, nrows, bpar, cands, ncand, par, e);
+  if (rc) return rc;
+  if ((rc = dm_check_peaks(par, pk, e)) != 0) return rc;
+  if (!d_rows) return e.fail(FRBCH_E_ARG, "null argument");
+  {
+    std::vector<double> dms;                                    // (the trial DMs are refused before anything is allocated)
+    if ((rc = dm_trials(cands, ncand, par, &dms, e)) != 0) return rc;
+  }
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DmOut out;
+  {
+    DeviceGuard dg(device);
+    PostScope ps;
+    if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+    if ((rc = dm_run(fil, d_rows, nrows, bpar, cands, ncand, flag, par, pk, ps, &out, e)) != 0) return rc;
+  }
+  const size_t n = (size_t)ncand * par->ntrial;
+  if (acc) memcpy(acc, out.acc.data(), out.acc.size() * sizeof(long long));
+  if (hits) memcpy(hits, out.hits.data(), out.hits.size() * sizeof(uint32_t));
+  if (snr) memcpy(snr, out.cv.snr.data(), n * sizeof(double));
+  if (strc) memcpy(strc, out.cv.strc.data(), n * sizeof(double));
+  if (results) memcpy((void*)results, out.cv.res.data(), (size_t)ncand * sizeof(frbch_dmscan_result));
+  if (used) memcpy(used, out.used.data(), out.used.size());
+  if (kernel_used) { kernel_used[0] = out.k[0]; kernel_used[1] = out.k[1]; }
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_dmscan_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                 const frbch_burst_cand* cands, uint32_t ncand, const uint8_t* flag, const frbch_dmscan_params* par,
+                                 const frbch_dmscan_peak_params* pk, int device, int64_t* acc, uint32_t* hits, double* snr,
+                                 double* strc, frbch_dmscan_result* results, uint8_t* used, uint32_t* kernel_used, char* err,
+                                 size_t err_cap) try {
+  PostErr e{err, err_cap};
+  int rc = dm_check(fil, nrows, bpar, cands, ncand, par, e);
+  if (rc) return rc;
+  if ((rc = dm_check_peaks(par, pk, e)) != 0) return rc;
+  if (!rows) return e.fail(FRBCH_E_ARG, "null argument");
+  {
+    std::vector<double> dms;
+    if ((rc = dm_trials(cands, ncand, par, &dms, e)) != 0) return rc;
+  }
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
+  return hs.run(e, "device memory for the rows", "upload rows", "download", [&]() {
+    return frbch_dmscan_device(fil, d_rows, nrows, bpar, cands, ncand, flag, par, pk, device, acc, hits, snr, strc, results, used, kernel_used, err, err_cap);
+  });
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }

@@ -1288,3 +1288,74 @@ KERNEL(frbch_post_polprof, PolParams) {
     }
   }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// DM of a burst (frbch_dmscan_*; include/frbch.h states the arithmetic): per (candidate, trial DM, time bin) the band sum of
+// the baseline-free, noise-weighted samples read at the trial's delays, in int64.  Every channel's part of a bin goes through
+// dm_term in both forms, so the generic kernel below and the fast one (kernels_post_fast.inc) differ in schedule only; the
+// sums are exact, so they give the same bits.
+// ---------------------------------------------------------------------------------------------------------------------
+struct DmRec {                 // one channel of a candidate: 24 bytes
+  double mean, w;              // the off-pulse mean (over the products read) and 1 / sqrt(var_c)
+  uint32_t used, pad;
+};
+struct DmCand { long long t0; double scale; };    // first row of bin 0 at the top of the band; 2^k
+struct DmParams {
+  const uint8_t* rows;         // [nrows][nifs][nchan] samples of `nbits` (8 or 16)
+  uint64_t nrows;
+  int nchan, nifs, nbits, ncand;
+  const DmCand* cand;          // [ncand]
+  const DmRec* rec;            // [ncand][nchan]
+  const int32_t* delays;       // [ncand][ntrial][nchan]: n_c(dm_k)
+  long long* acc;              // [ncand][ntrial][nbin]
+  uint32_t* hits;              // [ncand][ntrial][nbin]
+  long long* part;             // fast kernel: [ncand][ntile][ntrial][nbin]
+  uint32_t* hpart;             // fast kernel: the same shape
+  int ntrial, nbin, tfactor, p0, np, ntile, trun, brun;      // p0, np: the first product read and their number (1 or 2)
+};
+
+// the part of one channel in one bin of one trial: S the sum of its h present rows over the products read
+DEVFN inline long long dm_term(double mean, double w, double scale, uint32_t S, uint32_t h) {
+  POST_NO_CONTRACT
+  const double m = (double)h * mean;
+  const double d = (double)S - m;
+  const double x = d * w;
+  return (long long)rint(x * scale);
+}
+
+// grid (ceil(ncand ntrial nbin / 256)), one thread per (candidate, trial, bin), channels ascending, rows ascending
+KERNEL(frbch_post_dmscan, DmParams) {
+  K_PROLOGUE;
+  (void)smem; (void)by;
+  PHASE {
+    const long long idx = (long long)bx * nthr + tid;
+    if (idx < (long long)p.ncand * p.ntrial * p.nbin) {
+      const int j = (int)(idx % p.nbin);
+      const long long ik = idx / p.nbin;                       // candidate * ntrial + trial
+      const int cand = (int)(ik / p.ntrial);
+      const DmCand cd = p.cand[cand];
+      const DmRec* rec = p.rec + (size_t)cand * p.nchan;
+      const int32_t* dl = p.delays + (size_t)ik * p.nchan;
+      const uint64_t pitch = (uint64_t)p.nifs * (uint64_t)p.nchan;
+      const long long b0 = cd.t0 + (long long)j * (long long)p.tfactor;
+      long long a = 0;
+      uint32_t hits = 0;
+      for (int c = 0; c < p.nchan; ++c) {
+        if (!rec[c].used) continue;
+        long long lo, hi;
+        burst_clip(b0, (uint32_t)p.tfactor, (long long)dl[c], (long long)p.nrows, &lo, &hi);
+        if (hi <= lo) continue;
+        uint32_t S = 0;
+        for (long long t = lo; t < hi; ++t)
+          for (int pr = p.p0; pr < p.p0 + p.np; ++pr) {
+            const uint64_t o = (uint64_t)t * pitch + (uint64_t)pr * (uint64_t)p.nchan + (uint64_t)c;
+            S += p.nbits == 8 ? (uint32_t)p.rows[o] : (uint32_t)((const uint16_t*)p.rows)[o];
+          }
+        a += dm_term(rec[c].mean, rec[c].w, cd.scale, S, (uint32_t)(hi - lo));
+        hits += (uint32_t)(hi - lo);
+      }
+      p.acc[idx] = a;
+      p.hits[idx] = hits;
+    }
+  }
+}

@@ -1192,4 +1192,110 @@ __global__ void __launch_bounds__(kPpThreads) frbch_post_polprof_join(PolParams 
   out[0] = a[0]; out[1] = a[1]; out[2] = a[2]; out[3] = a[3];
   p.hits[(size_t)cand * p.nbin + j] = h;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// DM of a burst (HIP only; frbch_post_dmscan of kernels_post.inc stays the emulable form and the fallback; both call dm_term).
+// What is new against the profile kernel above is reuse: a staged row serves every trial of a run, not one.  A workgroup of 256
+// threads owns one candidate, one 64-byte tile of the row (CT = 64 / 32 channels of 8- / 16-bit samples), a run of `trun`
+// trials and a run of `brun` bins.  It stages the rows the bins need over the delay range of its tile over its trials -- from
+// its first bin's first row at the smallest delay to its last bin's last row at the largest: nb tfactor + (dmax - dmin) <=
+// kDmLds / (64 NP) rows, the host's plan rule sees to that -- of the NP products read into the LDS in 16-byte pieces (layout
+// [row][product][64 bytes]).  Then, trial after trial, one thread per (channel, bin), 256 / CT bins per trip, sums its tfactor
+// samples at its channel's delay of that trial from the LDS and forms its term; the CT lanes of a bin add theirs up by
+// shuffles and lane 0 stores the tile's int64 partial.  Lanes run along the channels, so a wave reads neighbouring bytes of
+// one or two LDS rows: no bank collides (lanes along the bins would, at a row stride of 64 bytes).  Rows outside the file are
+// neither loaded nor read.  frbch_post_dmscan_join adds the tiles in ascending order.  All row arithmetic is 64 bit.
+// grid (tiles x ceil(nbin / brun), ceil(ntrial / trun), ncand).
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int kDmThreads = 256, kDmTrun = 16, kDmMaxT = 256;
+constexpr size_t kDmLds = 65536;                                           // 64 KiB: two workgroups per CU
+
+template <int BPV, int NP>
+__global__ void __launch_bounds__(kDmThreads) frbch_post_dmscan_fast(DmParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int CT = 64 / BPV, BPP = kDmThreads / CT, ROWB = 64 * NP, CAP = (int)(kDmLds / ROWB);
+  const int tid = threadIdx.x, ch = tid % CT, jl = tid / CT;
+  const int tile = (int)blockIdx.x % p.ntile, cand = blockIdx.z;
+  const int j0 = ((int)blockIdx.x / p.ntile) * p.brun, k0 = (int)blockIdx.y * p.trun;
+  const int nb = min(p.brun, p.nbin - j0), nk = min(p.trun, p.ntrial - k0);
+  const DmCand cd = p.cand[cand];
+  const DmRec r = p.rec[(size_t)cand * p.nchan + (size_t)tile * CT + ch];
+  const int32_t* dl = p.delays + ((size_t)cand * p.ntrial + k0) * p.nchan + (size_t)tile * CT + ch;
+  int dmin = dl[0], dmax = dl[0];
+  for (int k = 1; k < nk; ++k) {
+    const int d = dl[(size_t)k * p.nchan];
+    dmin = min(dmin, d);
+    dmax = max(dmax, d);
+  }
+#pragma unroll
+  for (int m = 1; m < CT; m <<= 1) {                                       // over the tile's channels: the same in every thread
+    dmin = min(dmin, __shfl_xor(dmin, m));
+    dmax = max(dmax, __shfl_xor(dmax, m));
+  }
+  const long long nrows = (long long)p.nrows;
+  const long long base = cd.t0 + (long long)j0 * (long long)p.tfactor + (long long)dmin;     // the file row of LDS row 0
+  const long long span = (long long)nb * p.tfactor + ((long long)dmax - (long long)dmin);
+  if (span > CAP) return;                                                  // (the plan rule never launches such a run)
+  const size_t stride = (size_t)p.nifs * p.nchan * BPV, pstride = (size_t)p.nchan * BPV;
+  const unsigned char* src = p.rows + (size_t)p.p0 * pstride + (size_t)tile * 64;
+  for (int i = tid; i < (int)span * (ROWB / 16); i += kDmThreads) {
+    const long long row = base + (long long)(i / (ROWB / 16));
+    if (row >= 0 && row < nrows)
+      *reinterpret_cast<uint4*>(smem + (size_t)i * 16) =
+          *reinterpret_cast<const uint4*>(src + (size_t)row * stride + (size_t)((i >> 2) % NP) * pstride + (size_t)(i & 3) * 16);
+  }
+  __syncthreads();
+  for (int k = 0; k < nk; ++k) {                                           // (the same trips in every thread: the shuffles meet whole waves)
+    const long long delay = (long long)dl[(size_t)k * p.nchan];
+    for (int jb0 = 0; jb0 < nb; jb0 += BPP) {
+      const int jb = jb0 + jl;
+      long long a = 0;
+      uint32_t h = 0;
+      if (jb < nb && r.used) {
+        const long long b0 = cd.t0 + (long long)(j0 + jb) * (long long)p.tfactor;
+        long long lo, hi;
+        burst_clip(b0, (uint32_t)p.tfactor, delay, nrows, &lo, &hi);
+        if (hi > lo) {
+          uint32_t S = 0;
+          const unsigned char* q = smem + (size_t)(lo - base) * ROWB + (size_t)ch * BPV;
+          for (long long t = lo; t < hi; ++t, q += ROWB) {
+#pragma unroll
+            for (int pr = 0; pr < NP; ++pr) {
+              if constexpr (BPV == 1) S += (uint32_t)q[pr * 64];
+              else S += (uint32_t)*reinterpret_cast<const uint16_t*>(q + pr * 64);
+            }
+          }
+          h = (uint32_t)(hi - lo);
+          a = dm_term(r.mean, r.w, cd.scale, S, h);
+        }
+      }
+#pragma unroll
+      for (int m = 1; m < CT; m <<= 1) {
+        a += __shfl_xor(a, m);
+        h += __shfl_xor(h, m);
+      }
+      if (ch == 0 && jb < nb) {
+        const size_t o = (((size_t)cand * p.ntile + tile) * p.ntrial + (size_t)(k0 + k)) * p.nbin + (size_t)(j0 + jb);
+        p.part[o] = a;
+        p.hpart[o] = h;
+      }
+    }
+  }
+}
+
+// grid (ceil(ncand ntrial nbin / 256)): the partials of the tiles, added in ascending tile
+__global__ void __launch_bounds__(kDmThreads) frbch_post_dmscan_join(DmParams p) {
+  const size_t per = (size_t)p.ntrial * p.nbin, idx = (size_t)blockIdx.x * kDmThreads + threadIdx.x;
+  if (idx >= (size_t)p.ncand * per) return;
+  const size_t cand = idx / per, kj = idx % per;
+  long long a = 0;
+  uint32_t h = 0;
+  for (int t = 0; t < p.ntile; ++t) {
+    const size_t o = (cand * p.ntile + t) * per + kj;
+    a += p.part[o];
+    h += p.hpart[o];
+  }
+  p.acc[idx] = a;
+  p.hits[idx] = h;
+}
 }  // namespace fast

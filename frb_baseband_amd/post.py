@@ -31,6 +31,9 @@ reference's `dspsr -E <par> ... <IFall.fil>` stage) of SIGPROC filterbank files,
   L/I and V/I (``rm_peaks``), or all of it on rows uploaded once (``burst_rm``: frbch_burst_rm_host).
 * ``polprof_fil`` (``post polprof``, ``post rmsynth --profile``) draws the burst against time at that RM: I, debiased L, V and the
   position angle per time bin, (Q, U) of every channel rotated back and summed over the band (``pol_profile``: frbch_polprof_host).
+* ``dmfit_fil`` (``post dmfit``) measures the DM those stages take as given: the burst's noise-weighted profile at a fine grid of
+  trial DMs, the S/N- and the structure-maximising DM by a parabola over each curve's peak (``dm_scan``: frbch_dmscan_host);
+  ``post rmsynth`` and ``post polprof`` take the result with ``--dm-from``.
 There is no CPU fallback: the sums run in libfrbch.so on a gfx950 device.
 """
 from __future__ import annotations
@@ -2145,6 +2148,187 @@ def polprof_fil(filterbankfile, bursts=None, rm=None, nbin=256, tfactor=1, ref="
     return _polprof_write(filterbankfile.replace(".fil", ""), hdr, cands, rm, prof, tfactor, ref), prof
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# DM of a burst: fine DM scan, S/N and structure maxima (frbch_dmscan_*)
+# ------------------------------------------------------------------------------------------------------------------
+DMSCAN_RESULT = np.dtype([("dm_snr", "<f8"), ("dm_snr_err", "<f8"), ("dm_struct", "<f8"), ("snr_peak", "<f8"), ("struct_peak", "<f8"),
+                          ("snr_at_struct", "<f8"), ("k_snr", "<u4"), ("width_snr", "<u4"), ("bin_snr", "<u4"), ("nfit_snr", "<u4"),
+                          ("fitted_snr", "<u4"), ("k_struct", "<u4"), ("width_struct", "<u4"), ("bin_struct", "<u4"),
+                          ("nfit_struct", "<u4"), ("fitted_struct", "<u4"), ("k", "<i4"), ("nused", "<u4")])
+DM_ROW = "%-8s DM0 %9.3f sample %10d  DM_snr %10.4f +- %7.4f (S/N %7.2f, width %3d bins%s)  DM_struct %10.4f (S/N %7.2f%s)"
+
+
+def dm_sample_step(hdr: dict, lib=None) -> float:
+    """The change of DM that moves the bottom of the band by one row (frbch_dm_sample_step), pc cm^-3"""
+    lib = lib or _lib.load()
+    return float(lib.frbch_dm_sample_step(C.byref(fil_desc(hdr, hdr.get("product", 0)))))
+
+
+def dmscan_params(ntrial: int, ddm: float, nbin: int, tfactor: int) -> _lib.FrbchDmscanParams:
+    return _lib.FrbchDmscanParams(C.sizeof(_lib.FrbchDmscanParams), int(ntrial), int(nbin), int(tfactor), float(ddm))
+
+
+def dmscan_peak_params(widths=(1, 2, 4, 8), smooth: int = 3, fit_frac: float = 0.5) -> _lib.FrbchDmscanPeakParams:
+    widths = [int(w) for w in widths]
+    if not 1 <= len(widths) <= 16:
+        raise InputError("1..16 boxcar widths")
+    p = _lib.FrbchDmscanPeakParams(C.sizeof(_lib.FrbchDmscanPeakParams), len(widths))
+    for i, w in enumerate(widths):
+        p.widths[i] = w
+    p.smooth, p.fit_frac = int(smooth), float(fit_frac)
+    return p
+
+
+def dm_scan(fil_or_rows, hdr: dict, cands, ntrial: int, ddm: float, nbin: int = 64, tfactor: int = 1, widths=(1, 2, 4, 8),
+            smooth: int = 3, fit_frac: float = 0.5, flag=None, products: str = "stokes", device: int = 0, lib=None,
+            info: dict | None = None):
+    """The DM of every burst (frbch_dmscan_host; include/frbch.h states the arithmetic): its noise-weighted, band-summed profile
+    in ``nbin`` bins of ``tfactor`` rows about ``sample`` at ``ntrial`` DMs ``ddm`` apart about the burst's own, the largest
+    boxcar S/N (over ``widths``, in bins) and the structure (squared differences of the profile smoothed over ``smooth`` bins)
+    of every trial, and a parabola over the part of each curve above ``fit_frac`` of its peak -> dict(acc int64
+    [n][ntrial][nbin], hits, snr and struct [n][ntrial], dm [n][ntrial], results DMSCAN_RESULT [n], used [n][nchans]).
+    ``products='stokes'`` reads product ``hdr['product']`` (0), ``'coherency'`` PP + QQ of a four-product file.
+    ``info['kernel_used']``: 1 = the fast kernel, 0 = the generic one; ``info['spectra_kernel_used']``: the burst sums'."""
+    lib = lib or _lib.load()
+    rows, nrows, cands, par, _g = _burst_args(fil_or_rows, hdr, cands, None, products)
+    n, nchan = cands.size, hdr["nchans"]
+    fl = None if flag is None else np.ascontiguousarray(flag, dtype=np.uint8)
+    if fl is not None and fl.shape != (nchan,):
+        raise InputError("flag must have the shape [nchans]")
+    dpar, pk = dmscan_params(ntrial, ddm, nbin, tfactor), dmscan_peak_params(widths, smooth, fit_frac)
+    nt, nb = max(1, min(int(ntrial), 4096)), max(1, min(int(nbin), 1024))
+    if n * nt * nb > 1 << 24:
+        raise InputError("ncand * ntrial * nbin exceeds 2^24: cut the batch or the scan")
+    acc = np.zeros((n, nt, nb), np.int64)
+    hits = np.zeros((n, nt, nb), np.uint32)
+    snr, strc = np.zeros((n, nt)), np.zeros((n, nt))
+    res = np.zeros(n, dtype=DMSCAN_RESULT)
+    used = np.zeros((n, nchan), np.uint8)
+    k = (C.c_uint32 * 2)(0, 0)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_dmscan_host(C.byref(fil_desc(hdr, hdr.get("product", 0))), rows.ctypes.data, nrows, C.byref(par), cands.ctypes.data, n,
+                                 fl.ctypes.data if fl is not None else None, C.byref(dpar), C.byref(pk), device, acc.ctypes.data,
+                                 hits.ctypes.data, snr.ctypes.data, strc.ctypes.data, res.ctypes.data, used.ctypes.data, k, err, len(err)), err)
+    if info is not None:
+        info.update(spectra_kernel_used=k[0], kernel_used=k[1])
+    dm = cands["dm"][:, None] + (np.arange(nt, dtype=np.float64) - float(nt // 2))[None, :] * (float(ddm) if nt > 1 else 0.0)
+    return dict(acc=acc, hits=hits, snr=snr, struct=strc, dm=dm, results=res, used=used)
+
+
+def _dm_parabola(v, kpeak, nfit_lo_hi, width):
+    """the least-squares parabola over trials lo .. hi of a curve, drawn over all `width` columns (nan outside lo .. hi)"""
+    lo, hi = nfit_lo_hi
+    out = np.full(v.size, np.nan)
+    if hi - lo >= 2:
+        x = np.arange(lo, hi + 1) - kpeak
+        out[lo:hi + 1] = np.polyval(np.polyfit(x, v[lo:hi + 1], 2), x)
+    return out
+
+
+def _dm_fit_range(v, kpeak, fit_frac):
+    lo = hi = int(kpeak)
+    thr = fit_frac * v[kpeak]
+    while lo > 0 and v[lo - 1] >= thr:
+        lo -= 1
+    while hi + 1 < v.size and v[hi + 1] >= thr:
+        hi += 1
+    return lo, hi
+
+
+def _dm_png(path, scan, i, fit_frac):
+    """above: the bow tie, trials bottom to top against the bins; below: the S/N and the structure curve against the trial, each
+    with its fitted parabola"""
+    width, height = 512, 96
+    res = scan["results"][i]
+    a = scan["acc"][i].astype(np.float64) / np.sqrt(np.maximum(scan["hits"][i], 1))
+    nt, nb = a.shape
+    rows = np.clip((np.arange(2 * height) * nt) // (2 * height), 0, nt - 1)[::-1]
+    cols = np.clip((np.arange(width) * nb) // width, 0, nb - 1)
+    tie = a[rows][:, cols]
+    tie = (tie - tie.min()) / max(1e-30, float(tie.max() - tie.min()))
+    panels = [tie]
+    for name, kname, fname in (("snr", "k_snr", "fitted_snr"), ("struct", "k_struct", "fitted_struct")):
+        v = scan[name][i]
+        curves = [v]
+        if res[fname]:
+            fit = _dm_parabola(v, int(res[kname]), _dm_fit_range(v, int(res[kname]), fit_frac), width)
+            curves = [np.where(np.isnan(fit), v, fit), v]
+        panels += [np.zeros((4, width)), _curve_panel(curves, width, height)]
+    write_png(path, np.concatenate(panels, axis=0))
+
+
+def dmfit_fil(filterbankfile, bursts=None, dm1=None, dm2=0.0, dmstep=1.0, width=0, dm_half=None, ddm=None, nbin=None, tfactor=None,
+              smooth=3, fit_frac=0.5, off_gap=None, off_len=None, flag_file=None, products="stokes", threshold=8.0, max_cands=8,
+              device=0, lib=None, info: dict | None = None):
+    """The DM of the bursts of a filterbank: ``bursts`` = (dm, sample, width) tuples; or, with ``dm1 .. dm2 .. dmstep`` and no
+    bursts, the strongest groups of the search, exactly as ``rmsynth_fil`` finds them.  Defaults, in DM sample steps (one step
+    moves the bottom of the band by one row: ``dm_sample_step``): ``ddm`` a quarter of a step, ``dm_half`` 32 steps either side
+    (cut so that no trial lies below DM 0); ``tfactor`` an eighth of the largest width (at least 1 row) and ``nbin`` so that the
+    window holds four widths plus the sweep of the edge trial on either side (16 .. 1024 bins); the boxcars are 1, 2, 4 .. bins up
+    to half the window; ``off_gap`` is at least that sweep, so that no trial drags the burst into an off-pulse window.  The S/N
+    curve of a burst much wider than the sweep has a flat top: give it a larger ``dm_half`` or ``fit_frac``.  Writes
+    ``<base>_dm.npz`` (acc, hits, snr, struct, dm, results, used, bursts, ddm, tfactor, smooth, fit_frac), ``<base>_dm.txt`` (one line
+    per burst: the S/N-maximising DM +- its error and the structure-maximising DM) and ``<base>_dm_burst<i>.png`` (the bow tie and
+    the two curves with their fits).  Returns (files, what ``dm_scan`` returns)."""
+    lib = lib or _lib.load()
+    fil = sigproc.read_fil(filterbankfile)
+    hdr = fil.header
+    if not bursts:
+        if dm1 is None:
+            raise InputError("give bursts (--dm --sample/--time --width) or a DM range to search")
+        dms = dm_list(dm1, dm2, dmstep)
+        _files, recs = _search(fil, filterbankfile, dm1, dm2, dmstep, True, 5, threshold, 0.0, 1000, False, None, device, lib, {})
+        groups = group_candidates(recs, hdr, dms, lib=lib)
+        groups = groups[np.argsort(-groups["best"]["sigma"], kind="stable")[:max_cands]]
+        bursts = [(dms[int(g["best"]["dm_index"])], int(g["best"]["sample"]), max(int(width), int(g["best"]["width"]))) for g in groups]
+        if not bursts:
+            raise InputError("the search found no burst above the threshold")
+    step = dm_sample_step(hdr, lib)
+    if not step > 0:
+        raise InputError("dmfit needs at least two channels")
+    ddm = float(ddm) if ddm else step / 4.0
+    half = float(dm_half) if dm_half else 32.0 * step
+    lowest = min(float(b["dm"] if isinstance(b, dict) or hasattr(b, "dtype") else b[0]) for b in bursts)
+    ntrial = 2 * int(min(2047, max(0, min(half, lowest) // ddm))) + 1
+    sweep = int(np.ceil((ntrial // 2) * ddm / step))
+    wmax = max(int(b["width"] if isinstance(b, dict) or hasattr(b, "dtype") else b[2]) for b in bursts)
+    tfactor = int(tfactor) if tfactor else max(1, min(512, wmax // 8))
+    nbin = int(nbin) if nbin else int(min(1024, max(16, -(-(4 * wmax + 2 * sweep) // tfactor))))
+    cands = burst_cands(bursts, off_gap, off_len)
+    if off_gap is None:
+        cands = cands.copy()
+        cands["off_gap"] = np.maximum(cands["off_gap"], sweep)
+    flag = read_flag_file(flag_file, hdr["nchans"]).astype(np.uint8) if flag_file else None
+    widths = [w for w in (1, 2, 4, 8, 16, 32, 64) if w <= max(1, nbin // 2)]
+    scan = dm_scan(fil, hdr, cands, ntrial, ddm, nbin, tfactor, widths=widths, smooth=min(int(smooth), max(1, nbin - 1)), fit_frac=fit_frac,
+                   flag=flag, products=products, device=device, lib=lib, info=info)
+    base = filterbankfile.replace(".fil", "")
+    files = [base + "_dm.npz", base + "_dm.txt"]
+    np.savez(files[0], acc=scan["acc"], hits=scan["hits"], snr=scan["snr"], struct=scan["struct"], dm=scan["dm"], results=scan["results"],
+             used=scan["used"], bursts=cands, ddm=np.float64(ddm), tfactor=np.int64(tfactor), smooth=np.int64(smooth),
+             fit_frac=np.float64(fit_frac), step=np.float64(step))
+    with open(files[1], "w") as f:
+        for i, (c, r) in enumerate(zip(cands, scan["results"])):
+            f.write(DM_ROW % ("burst%d" % i, c["dm"], int(c["sample"]), r["dm_snr"], r["dm_snr_err"], r["snr_peak"], int(r["width_snr"]),
+                              "" if r["fitted_snr"] else ", not fitted", r["dm_struct"], r["snr_at_struct"],
+                              "" if r["fitted_struct"] else ", not fitted") + "\n")
+            _dm_png(base + "_dm_burst%d.png" % i, scan, i, fit_frac)
+            files.append(base + "_dm_burst%d.png" % i)
+    return files, scan
+
+
+def bursts_from_dm(path, kind="snr") -> np.ndarray:
+    """The BURST_CAND records of a ``<base>_dm.npz`` with the DM that ``dmfit_fil`` measured in place of the one it was given;
+    ``kind``: 'snr' or 'struct'"""
+    if kind not in ("snr", "struct"):
+        raise InputError("--dm-kind must be snr or struct")
+    back = np.load(path)
+    cands = np.ascontiguousarray(back["bursts"]).copy()
+    res = back["results"]
+    cands["dm"] = np.where(res["nused"] > 0, res["dm_" + kind], cands["dm"])       # (a dead burst keeps the DM it came with)
+    return cands
+
+
 def main(argv=None):
     """``python -m frb_baseband_amd.post fold <fil> <par> [--polyco FILE] [--doppler X] [--products coherency|stokes] [...]`` / ``... prepdata <fil> --dm <dm> [...]`` /
     ``... search <fil> --dm <dm> [--dm2 --dmstep --threshold --max-width --detrend ...]`` /
@@ -2153,6 +2337,8 @@ def main(argv=None):
     ``... rfifind <fil> [--block-rows --t-cell --t-chan --chan-frac --block-frac --flag FILE --write-clean]`` /
     ``... rmsynth <fil> (--dm D --sample S | --time T) --width W [--off-gap G --off-len L] [--phi-max X --dphi Y | --nphi N] [--flag FILE]
     [--gains FILE.npy] [--products stokes|coherency] [--profile --nbin N --tfactor F]`` (burst options repeatable; or ``--dm .. --dm2 .. --dmstep ..`` to search for them) /
+    ``... dmfit <fil> --dm D (--sample S | --time T) --width W [--dm-half H --ddm X --nbin N --tfactor F --smooth S --fit-frac R --flag FILE --coherency]``
+    (or ``--dm .. --dm2 .. --dmstep ..`` to search for the bursts; ``rmsynth`` and ``polprof`` take ``--dm-from BASE_dm.npz [--dm-kind snr|struct]`` in place of ``--dm``) /
     ``... polprof <fil> (--dm D (--sample S | --time T) --width W --rm R | --rm-from BASE_rm.npz) [--nbin N --tfactor F --ref mean|zero --flag FILE --gains FILE.npy --coherency]``
     (``search`` and ``candidates`` take ``--flag FILE`` and ``--rfi``; ``search``, ``candidates`` and ``rfifind`` take ``--resident``:
     one upload of the rows per command; ``rfifind --periodic [--t-freq S]`` and ``--rfi --periodic`` add the periodicity test): the stages
@@ -2255,7 +2441,9 @@ def main(argv=None):
     r.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     m = sub.add_parser("rmsynth", help="rotation measure of the bursts of a full-Stokes filterbank: spectra of every product, RM synthesis of Q and U")
     m.add_argument("fil")
-    m.add_argument("--dm", type=float, action="append", required=True, help="DM of a burst (repeatable, one per burst); with --dm2: the first DM of the search")
+    m.add_argument("--dm", type=float, action="append", default=None, help="DM of a burst (repeatable, one per burst); with --dm2: the first DM of the search")
+    m.add_argument("--dm-from", default=None, help="<base>_dm.npz of `dmfit`: its bursts at their measured DMs instead of --dm .. --width")
+    m.add_argument("--dm-kind", choices=("snr", "struct"), default="snr", help="which DM of --dm-from: the S/N- or the structure-maximising one")
     m.add_argument("--sample", type=int, action="append", default=None, help="centre of a burst, row at the top of the band (repeatable)")
     m.add_argument("--time", type=float, action="append", default=None, help="the same in seconds from the start of the file (repeatable)")
     m.add_argument("--width", type=int, action="append", default=None, help="on-pulse rows (repeatable; one value serves every burst)")
@@ -2283,6 +2471,8 @@ def main(argv=None):
     f.add_argument("--width", type=int, action="append", default=None, help="on-pulse rows (repeatable; one value serves every burst)")
     f.add_argument("--rm", type=float, action="append", default=None, help="rotation measure, rad/m2 (repeatable; one value serves every burst)")
     f.add_argument("--rm-from", default=None, help="<base>_rm.npz of `rmsynth`: its bursts and fitted RMs instead of --dm .. --rm")
+    f.add_argument("--dm-from", default=None, help="<base>_dm.npz of `dmfit`: its bursts at their measured DMs instead of --dm .. --width (with --rm)")
+    f.add_argument("--dm-kind", choices=("snr", "struct"), default="snr", help="which DM of --dm-from: the S/N- or the structure-maximising one")
     f.add_argument("--nbin", type=int, default=256, help="time bins (1..1024)")
     f.add_argument("--tfactor", type=int, default=1, help="rows per bin (1..512)")
     f.add_argument("--ref", choices=("mean", "zero"), default="mean", help="the PA refers to the mean lambda^2 of the used channels, or to lambda = 0")
@@ -2292,10 +2482,53 @@ def main(argv=None):
     f.add_argument("--gains", default=None, help=".npy file [4][nchans] of gains")
     f.add_argument("--coherency", action="store_true", help="the file holds the -d4 products PP, QQ, Re, Im")
     f.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
+    d = sub.add_parser("dmfit", help="DM of the bursts of a filterbank: a fine DM scan, the S/N- and the structure-maximising DM")
+    d.add_argument("fil")
+    d.add_argument("--dm", type=float, action="append", required=True, help="DM of a burst (repeatable, one per burst); with --dm2: the first DM of the search")
+    d.add_argument("--sample", type=int, action="append", default=None, help="centre of a burst, row at the top of the band (repeatable)")
+    d.add_argument("--time", type=float, action="append", default=None, help="the same in seconds from the start of the file (repeatable)")
+    d.add_argument("--width", type=int, action="append", default=None, help="on-pulse rows (repeatable; one value serves every burst)")
+    d.add_argument("--dm2", type=float, default=0.0, help="search DM .. DM2 for the bursts instead (the groups of `candidates` on product 0)")
+    d.add_argument("--dmstep", type=float, default=1.0)
+    d.add_argument("--threshold", type=float, default=8.0, help="sigma of the search of --dm2")
+    d.add_argument("--max-cands", type=int, default=8, help="bursts kept from the search of --dm2")
+    d.add_argument("--dm-half", type=float, default=None, help="half range of the scan, pc cm^-3 (default: 32 DM sample steps)")
+    d.add_argument("--ddm", type=float, default=None, help="step of the scan, pc cm^-3 (default: a quarter of a DM sample step)")
+    d.add_argument("--nbin", type=int, default=None, help="time bins (1..1024; default: four widths plus twice the sweep of the edge trial)")
+    d.add_argument("--tfactor", type=int, default=None, help="rows per bin (1..512; default: an eighth of the width)")
+    d.add_argument("--smooth", type=int, default=3, help="bins the profile is smoothed over before the structure metric")
+    d.add_argument("--fit-frac", type=float, default=0.5, help="the parabola is fitted to the trials above this fraction of the peak")
+    d.add_argument("--off-gap", type=int, default=None, help="rows between the burst and each off-pulse window (default: 2 widths, at least 16 and the sweep)")
+    d.add_argument("--off-len", type=int, default=None, help="rows of each off-pulse window (default 1024)")
+    d.add_argument("--flag", default=None, help="flag file: channels left out")
+    d.add_argument("--coherency", action="store_true", help="the file holds the -d4 products: PP + QQ is scanned")
+    d.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     a = ap.parse_args(argv)
-    if a.cmd == "polprof":
+    if a.cmd == "dmfit":
+        bursts = None
+        if a.dm2 <= 0.0:
+            tsamp = sigproc.read_fil(a.fil).header["tsamp"]
+            centres = list(a.sample or []) + [int(round(t / tsamp)) for t in (a.time or [])]
+            widths = a.width or []
+            if not centres or len(centres) != len(a.dm) or len(widths) not in (1, len(centres)):
+                raise InputError("dmfit: one --sample or --time per --dm, and --width once or once per burst")
+            bursts = [(dm, s, widths[i if len(widths) > 1 else 0]) for i, (dm, s) in enumerate(zip(a.dm, centres))]
+        files, _scan = dmfit_fil(a.fil, bursts, dm1=a.dm[0], dm2=a.dm2, dmstep=a.dmstep, width=(a.width or [0])[0], dm_half=a.dm_half, ddm=a.ddm,
+                                 nbin=a.nbin, tfactor=a.tfactor, smooth=a.smooth, fit_frac=a.fit_frac, off_gap=a.off_gap, off_len=a.off_len,
+                                 flag_file=a.flag, products="coherency" if a.coherency else "stokes", threshold=a.threshold,
+                                 max_cands=a.max_cands, device=a.device)
+        for path in files:
+            print("wrote", path)
+        print(open(files[1]).read(), end="")
+    elif a.cmd == "polprof":
         bursts, rm = None, None
-        if not a.rm_from:
+        if a.dm_from and not a.rm_from:
+            bursts = list(bursts_from_dm(a.dm_from, a.dm_kind))
+            rms = a.rm or []
+            if len(rms) not in (1, len(bursts)):
+                raise InputError("polprof --dm-from: --rm once or once per burst")
+            rm = [rms[i if len(rms) > 1 else 0] for i in range(len(bursts))]
+        elif not a.rm_from:
             tsamp = sigproc.read_fil(a.fil).header["tsamp"]
             centres = list(a.sample or []) + [int(round(t / tsamp)) for t in (a.time or [])]
             widths, rms, dms = a.width or [], a.rm or [], a.dm or []
@@ -2310,7 +2543,12 @@ def main(argv=None):
             print("wrote", path)
     elif a.cmd == "rmsynth":
         bursts = None
-        if a.dm2 <= 0.0:
+        if a.dm_from:
+            bursts = list(bursts_from_dm(a.dm_from, a.dm_kind))
+            a.dm = [float(bursts[0]["dm"])]
+        elif not a.dm:
+            m.error("the following arguments are required: --dm")
+        elif a.dm2 <= 0.0:
             tsamp = sigproc.read_fil(a.fil).header["tsamp"]
             centres = list(a.sample or []) + [int(round(t / tsamp)) for t in (a.time or [])]
             widths = a.width or []

@@ -888,6 +888,113 @@ int frbch_polprof_host(const frbch_fil_desc* fil, const void* rows, uint64_t nro
                        const frbch_prof_params* par, int device, int64_t* acc, uint32_t* hits, frbch_prof_bin* bins,
                        frbch_prof_result* results, uint8_t* used, uint32_t* kernel_used, char* err, size_t err_cap);
 
+/* ---- DM of a burst: fine DM scan, S/N and structure maxima -------------------------------------------
+ * The stages above take the DM of a burst as given; this one measures it: the burst's band-summed, noise-weighted profile at
+ * ntrial DMs about cand.dm (the DM-time "bow tie"), and from it the DM of the largest boxcar S/N and the DM of the most
+ * structure, each with a least-squares parabola over the peak of its curve.  frbch_burst_cand, frbch_burst_params, n_c(.),
+ * the windows, frbch_burst_sums and "a row outside 0 .. nrows - 1 is absent" are those of the burst polarisation section
+ * above; tests/dmscan_oracle.py restates what follows in numpy.  Rows must be 8 or 16 bit: the fixed-point scale below needs
+ * an a-priori bound on the samples, which float32 rows do not have.
+ *
+ * Trials.  kc = ntrial / 2;  dm_k = cand.dm + ((double)k - (double)kc) ddm, every operation rounded on its own (ntrial = 1:
+ *    dm_0 = cand.dm, ddm is not looked at).  Channel c of trial k is read n_c(dm_k) rows later.
+ * Window.  t0_i = sample - (nbin / 2) tfactor (integer division, signed 64 bit).  Bin j < nbin holds the rows t0_i + j tfactor
+ *    + u, u < tfactor, at the top of the band, which has delay 0 at every trial: `sample` stays put and the bow tie is centred.
+ *
+ * Host preparation (double, ascending c, every operation rounded on its own):
+ *    the burst sums of the candidates at cand.dm (step 1 of the burst polarisation section, the same kernel).  Products read:
+ *    FRBCH_BURST_STOKES: P = {fil->product} (a one-product file works); FRBCH_BURST_COHERENCY (needs nifs = 4): P = {0, 1}.
+ *    mean_pc = off_sum / off_hits;  var_pc = var_off of step 1;  mean_c = the sum over p in P of mean_pc, var_c likewise
+ *    (ascending p);  used[i][c] = 1 unless on_hits = 0 or off_hits < 2 in a product of P (step 1's rule on the products read:
+ *    with integer rows and no gains nothing there can be non-finite), or var_c is not > 0, or flag[c] != 0.
+ *    w_c = 1 / sqrt(var_c): every used channel has unit off-pulse variance per row.  N_i = the number of used channels;
+ *    wmax_i = the largest w_c over them;  M_i = (double)tfactor 2^nbits wmax_i, doubled in coherency order, = f 2^e, f in
+ *    [0.5, 1) (frexp);  k_i = 40 - e.  N_i = 0: every acc, hit, curve value and result field of the candidate is 0.
+ *
+ * Device.  For every used c, trial k and bin j with h > 0, h = the number of present rows of the bin in channel c at dm_k:
+ *      S = the integer sum of the present samples over the products of P (exact: 2 x 512 x 65535 < 2^27);
+ *      x = ((double)S - (double)h mean_c) w_c   (three roundings, no FMA);
+ *      X = (int64)rint(x 2^k_i), ties to even (the scaling by a power of two is exact);
+ *      acc[i][k][j] += X;   hits[i][k][j] += h.
+ *    |x| <= tfactor 2^nbits w_c (twice that in coherency order) < 2^e, so |X| <= 2^40 and |acc| <= 2^54 over nchan <= 16384:
+ *    acc (int64 [ncand][ntrial][nbin]) and hits (uint32, the same shape) are exact in any order of summation; both kernels
+ *    and the restatement give the same bits.
+ *
+ * Peaks (frbch_dmscan_peaks, host only, double, every operation rounded on its own; sqrt is the only function called).
+ *    Boxcar of w bins at j <= nbin - w: A = the sum of acc[i][k][j .. j + w - 1], H = the sum of the hits (integers, exact);
+ *      B(w, j) = ((double)A 2^-k_i) / sqrt((double)H), 0 where H = 0.
+ *    snr[i][k] = the first largest B over the listed widths (in their order, which must ascend) and j ascending, with its
+ *      width and bin.
+ *    Structure, s = smooth, nbin > 1: z_j = B(s, j);  struct[i][k] = (the sum over ascending j < nbin - s of (z_{j+1} - z_j)^2)
+ *      - (2 (double)(nbin - s)) / (double)s; the term taken off is the expectation of the sum for unit-variance noise.
+ *      nbin = 1: struct = 0, smooth is not looked at, and the structure DM is not fitted.
+ *    Fit of a curve v[0 .. ntrial - 1] (snr, then struct): kp = the first largest trial;  thr = fit_frac v[kp];  lo .. hi = the
+ *      contiguous trials about kp with v >= thr;  n = hi - lo + 1.  With x = k - kp:  S_m = the sums of x^m, m = 0 .. 4, in
+ *      int64 and then converted;  T_0 = sum v, T_1 = sum (double)x v, T_2 = sum (double)(x x) v (ascending k, each product
+ *      rounded before it is added);
+ *        m0 = S2 S0 - S1 S1,  m1 = S3 S0 - S1 S2,  m2 = S3 S1 - S2 S2,  D  = (S4 m0 - S3 m1) + S2 m2;
+ *        p1 = T1 S0 - S1 T0,  p2 = T1 S1 - S2 T0,                       Da = (T2 m0 - S3 p1) + S2 p2;
+ *        p3 = S3 T0 - S2 T1,                                           Db = (S4 p1 - T2 m1) + S2 p3;
+ *        a = Da / D,  b = Db / D,  vertex = (-b) / (2 a),  dm = dm_kp + vertex ddm,  fitted = 1
+ *      (y = a x^2 + b x + c by the normal equations, Cramer's rule).  Not fitted -- dm = dm_kp, fitted = 0 -- where v[kp] is
+ *      not > 0, n < 3, lo = 0 or hi = ntrial - 1 (the peak is not bracketed), or a is not < 0.
+ *    dm_snr_err = sqrt(-1 / a) ddm of the fitted S/N parabola: the half-width at which it lies 1 below its vertex (0 where not
+ *    fitted).  The structure DM gets no error: its curve is not in units of a variance, and none is claimed.
+ *    frbch_dmscan_result: for each curve the peak's trial, the S/N, width and bin of that trial, the number of points n and
+ *    `fitted`; struct_peak = struct at its peak;  k = k_i;  nused = N_i.
+ *
+ * frbch_dm_sample_step: tsamp / ((1 / 2.41e-4) (f_lo^-2 - f_hi^-2)), f_lo / f_hi the lowest and highest channel frequency:
+ * the change of DM that moves the bottom of the band by one row (0 for a bad descriptor or one channel).
+ *
+ * kernel_used[2] (may be NULL): the burst-sums kernel, and the scan kernel: 1 = the fast one (the conditions of the fast
+ * burst-sums kernel and tfactor <= 256; one workgroup per (64-byte channel tile, run of bins, run of trials, candidate)
+ * stages the rows that its bins need over the delay range of its tile and trials into 64 KiB of the LDS once and forms the
+ * terms of all its trials from there; a join adds the tiles), 0 = the generic one (one thread per (candidate, trial, bin)).
+ * The trial run is the largest of 16, 8, 4, 2, 1 (at most ntrial) for which every (candidate, tile, run) leaves room for one
+ * bin: tfactor + delay range <= 1024 rows (512 in coherency order, which stages two products); no such run, or tile partials
+ * of more than 2^30 bytes (ncand x tiles x ntrial x nbin x 12), send the whole call to the generic kernel.  Both give the
+ * same bits.
+ * FRBCH_E_ARG (outputs untouched): a wrong `size`, ntrial outside 1..4096, nbin outside 1..1024, tfactor outside 1..512, ddm
+ * not finite or <= 0 (ntrial > 1), a dm_k outside [0, 1e5), float rows, coherency order without nifs = 4, nchan > 16384, ncand
+ * outside 1..4096, ncand * ntrial * nchan > 2^26, ncand * ntrial * nbin > 2^24, nwidth outside 1..16, a width outside 1..nbin
+ * or not above the one before it, smooth outside 1..nbin - 1 (nbin > 1), fit_frac outside (0, 1), and every refusal of step 1. */
+typedef struct frbch_dmscan_params { uint32_t size, ntrial, nbin, tfactor; double ddm; } frbch_dmscan_params;   /* size = sizeof(frbch_dmscan_params) */
+typedef struct frbch_dmscan_peak_params {
+  uint32_t size, nwidth;               /* size = sizeof(frbch_dmscan_peak_params) */
+  uint32_t widths[16];                 /* boxcar widths in bins, ascending; the first nwidth count */
+  uint32_t smooth, reserved;
+  double fit_frac;
+} frbch_dmscan_peak_params;
+typedef struct frbch_dmscan_result {
+  double dm_snr, dm_snr_err, dm_struct;
+  double snr_peak, struct_peak, snr_at_struct;   /* snr[k_snr], struct[k_struct], snr[k_struct] */
+  uint32_t k_snr, width_snr, bin_snr, nfit_snr, fitted_snr;
+  uint32_t k_struct, width_struct, bin_struct, nfit_struct, fitted_struct;
+  int32_t k;
+  uint32_t nused;
+} frbch_dmscan_result;
+double frbch_dm_sample_step(const frbch_fil_desc* fil);
+/* The plan rule (host only, nothing runs): 1 = fast, 0 = generic, < 0 = refused; only the ADDRESS of d_rows is examined. */
+int frbch_dmscan_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                        const frbch_burst_cand* cands, uint32_t ncand, const frbch_dmscan_params* par);
+/* Host only: snr, strc [ncand][ntrial] (double), width, bin [ncand][ntrial] (uint32) and results [ncand] from acc and hits
+ * [ncand][ntrial][nbin], k and nused [ncand] (what frbch_dmscan_* put into their results); every output may be NULL. */
+int frbch_dmscan_peaks(const frbch_dmscan_params* par, const frbch_dmscan_peak_params* pk, const frbch_burst_cand* cands,
+                       uint32_t ncand, const int32_t* k, const uint32_t* nused, const int64_t* acc, const uint32_t* hits,
+                       double* snr, double* strc, uint32_t* width, uint32_t* bin, frbch_dmscan_result* results, char* err,
+                       size_t err_cap);
+/* d_rows is device memory, never written; everything else is host memory: flag [nchan] (may be NULL) and the outputs acc, hits
+ * [ncand][ntrial][nbin], snr, strc [ncand][ntrial], results [ncand], used [ncand][nchan] (each may be NULL).  One device scope. */
+int frbch_dmscan_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                        const frbch_burst_cand* cands, uint32_t ncand, const uint8_t* flag, const frbch_dmscan_params* par,
+                        const frbch_dmscan_peak_params* pk, int device, int64_t* acc, uint32_t* hits, double* snr, double* strc,
+                        frbch_dmscan_result* results, uint8_t* used, uint32_t* kernel_used, char* err, size_t err_cap);
+/* the same with host rows: one upload */
+int frbch_dmscan_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* bpar,
+                      const frbch_burst_cand* cands, uint32_t ncand, const uint8_t* flag, const frbch_dmscan_params* par,
+                      const frbch_dmscan_peak_params* pk, int device, int64_t* acc, uint32_t* hits, double* snr, double* strc,
+                      frbch_dmscan_result* results, uint8_t* used, uint32_t* kernel_used, char* err, size_t err_cap);
+
 /* ---- interference: block statistics, the mask, cleaned rows --------------------------------------
  * The reference carries a flag file through to Heimdall and FETCH (create_config.py:54-56 `-F/--flag`, frb.conf:50,
  * base2fil.sh:226,425-432, submit_job.py:117 `<Tel>.flag_<fmin>-<fmax>MHz_<nchan>chan`) and leaves making one to a person.

@@ -1,0 +1,224 @@
+"""Numpy restatement of the DM of a burst (include/frbch.h, "DM of a burst"): the trial DMs and their delays, the host
+preparation (products read, used channels, baselines, weights, the scale 2^k), the integer sums per (candidate, trial, bin) in
+int64 -- and, on request, once more in Python integers of unbounded size --, the boxcar S/N and the structure metric of every
+trial, and the least-squares parabola over each curve's peak.  Beside it `scan_fp64`: the same sums in plain double precision
+with nothing rounded to integers, which the accuracy test holds the integer form against.  The burst sums are
+tests/rm_oracle.py's.  Test infrastructure only."""
+import math
+
+import numpy as np
+
+from frb_baseband_amd import post
+from tests import rm_oracle as ro
+
+DM_K = 2.41e-4
+
+
+def delays(hdr, dm):
+    """n_c(dm) exactly as post_delays of the library computes it: dm / 2.41e-4 (f_c^-2 - f_hi^-2) / tsamp + 0.5, truncated"""
+    fc = hdr["fch1"] + np.arange(hdr["nchans"], dtype=np.float64) * hdr["foff"]
+    fhi = hdr["fch1"] if hdr["foff"] < 0 else float(fc[-1])
+    s = (float(dm) / DM_K * (1.0 / (fc * fc) - 1.0 / (fhi * fhi))) / hdr["tsamp"]
+    return (s + 0.5).astype(np.int64)
+
+
+def sample_step(hdr):
+    fc = hdr["fch1"] + np.arange(hdr["nchans"], dtype=np.float64) * hdr["foff"]
+    flo, fhi = (float(fc[-1]), float(fc[0])) if hdr["foff"] < 0 else (float(fc[0]), float(fc[-1]))
+    return hdr["tsamp"] / (1.0 / DM_K * (1.0 / (flo * flo) - 1.0 / (fhi * fhi)))
+
+
+def trial_dms(dm0, ntrial, ddm):
+    if ntrial == 1:
+        return [float(dm0)]
+    kc = float(ntrial // 2)
+    return [float(dm0) + (float(k) - kc) * float(ddm) for k in range(ntrial)]
+
+
+def bin_sums(x, d, t0, nbin, tfactor):
+    """x [nrows][nchan] integers, d [nchan] delays -> (S int64 [nchan][nbin], h int64 [nchan][nbin])"""
+    nrows, nchan = x.shape
+    edges = t0 + np.arange(nbin + 1, dtype=np.int64) * tfactor
+    e = np.clip(edges[None, :] + d[:, None], 0, nrows)
+    lo = int(e.min())
+    hi = max(lo, int(e.max()))
+    cs = np.zeros((hi - lo + 1, nchan), np.int64)
+    np.cumsum(x[lo:hi], axis=0, dtype=np.int64, out=cs[1:])
+    cc = np.arange(nchan)[:, None]
+    return cs[e[:, 1:] - lo, cc] - cs[e[:, :-1] - lo, cc], e[:, 1:] - e[:, :-1]
+
+
+def prepare(x, hdr, cands, nbin, tfactor, flag=None, coherency=False):
+    """-> (one dict per candidate, used [ncand][nchan], xs [nrows][nchan] int64: the sum of the products read)"""
+    nchan, nbits = hdr["nchans"], x.dtype.itemsize * 8
+    prods = [0, 1] if coherency else [int(hdr.get("product", 0))]
+    sums = ro.burst_sums(x, hdr, cands)
+    used = np.zeros((len(cands), nchan), np.uint8)
+    out = []
+    for i, cd in enumerate(cands):
+        ok = np.ones(nchan, bool) if flag is None else np.asarray(flag) == 0
+        mean, var = None, None
+        with np.errstate(all="ignore"):
+            for p in prods:
+                s = sums[i, p]
+                ok &= (s["on_hits"] != 0) & (s["off_hits"] >= 2)
+                noff = s["off_hits"].astype(np.float64)
+                mp = s["off_sum"] / noff
+                vp = (s["off_sumsq"] - (s["off_sum"] * s["off_sum"]) / noff) / (noff - 1.0)
+                vp = np.where(vp < 0.0, 0.0, vp)
+                mean = mp if mean is None else mean + mp
+                var = vp if var is None else var + vp
+            ok &= var > 0.0
+            w = 1.0 / np.sqrt(np.where(ok, var, 1.0))
+        used[i] = ok
+        N = int(ok.sum())
+        c = dict(t0=int(cd["sample"]) - (nbin // 2) * tfactor, N=N, k=0, mean=np.where(ok, mean, 0.0), w=np.where(ok, w, 0.0), ok=ok)
+        if N:
+            M = (float(tfactor) * 2.0 ** nbits) * float(w[ok].max())
+            if coherency:
+                M = 2.0 * M
+            c["k"] = 40 - math.frexp(M)[1]
+        out.append(c)
+    xs = x[:, prods[0], :].astype(np.int64)
+    for p in prods[1:]:
+        xs = xs + x[:, p, :]
+    return out, used, xs
+
+
+def planes(x, hdr, cands, ntrial, ddm, nbin, tfactor, flag=None, coherency=False, unbounded=False, fp64=False):
+    """-> dict(acc int64 [ncand][ntrial][nbin], hits uint32, used, k, nused; with `unbounded` also `largest`: the largest |X| and
+    the largest sum of |X| over a bin, in Python integers; with `fp64` also `plain`: the same sums with nothing rounded, 2^-k
+    applied, and `units`: N 2^-k-1 per candidate)"""
+    prep, used, xs = prepare(x, hdr, cands, nbin, tfactor, flag, coherency)
+    ncand = len(cands)
+    acc = np.zeros((ncand, ntrial, nbin), np.int64)
+    hits = np.zeros((ncand, ntrial, nbin), np.uint32)
+    plain = np.zeros((ncand, ntrial, nbin))
+    big_x, big_sum = 0, 0
+    for i, c in enumerate(prep):
+        if not c["N"]:
+            continue
+        scale = 2.0 ** c["k"]
+        for k, dm in enumerate(trial_dms(cands[i]["dm"], ntrial, ddm)):
+            S, h = bin_sums(xs, delays(hdr, dm), c["t0"], nbin, tfactor)
+            live = c["ok"][:, None] & (h > 0)
+            xv = (S.astype(np.float64) - h.astype(np.float64) * c["mean"][:, None]) * c["w"][:, None]
+            X = np.where(live, np.rint(xv * scale), 0.0).astype(np.int64)
+            acc[i, k] = X.sum(axis=0)
+            hits[i, k] = np.where(live, h, 0).sum(axis=0)
+            if fp64:
+                plain[i, k] = np.where(live, xv, 0.0).sum(axis=0)
+            if unbounded:
+                big_x = max(big_x, max(abs(int(X.max())), abs(int(X.min()))))
+                tot = [sum(abs(int(v)) for v in col) for col in X.T]
+                assert [sum(int(v) for v in col) for col in X.T] == [int(v) for v in acc[i, k]]
+                big_sum = max(big_sum, max(tot))
+    out = dict(acc=acc, hits=hits, used=used, k=np.array([c["k"] for c in prep], np.int32), nused=np.array([c["N"] for c in prep], np.uint32))
+    if unbounded:
+        out["largest"] = (big_x, big_sum)
+    if fp64:
+        out["plain"] = plain
+        out["units"] = np.array([c["N"] * 2.0 ** (-c["k"] - 1) for c in prep])
+    return out
+
+
+# ---- the peaks ---------------------------------------------------------------------------------------------------------
+def boxcars(a, h, w, inv):
+    """B(w, j), j = 0 .. nbin - w, of one trial: a, h lists of Python integers"""
+    out = []
+    A, H = sum(a[:w]), sum(h[:w])
+    for j in range(len(a) - w + 1):
+        if j:
+            A += a[j + w - 1] - a[j - 1]
+            H += h[j + w - 1] - h[j - 1]
+        out.append((float(A) * inv) / math.sqrt(float(H)) if H else 0.0)
+    return out
+
+
+def fit(v, fit_frac, dms, ddm):
+    """-> (kpeak, nfit, fitted, dm, err)"""
+    nt = len(v)
+    kp = 0
+    for k in range(1, nt):
+        if v[k] > v[kp]:
+            kp = k
+    if not v[kp] > 0.0:
+        return kp, 0, 0, dms[kp], 0.0
+    thr = fit_frac * v[kp]
+    lo = hi = kp
+    while lo > 0 and v[lo - 1] >= thr:
+        lo -= 1
+    while hi + 1 < nt and v[hi + 1] >= thr:
+        hi += 1
+    n = hi - lo + 1
+    if n < 3 or lo == 0 or hi == nt - 1:
+        return kp, n, 0, dms[kp], 0.0
+    s = [0] * 5
+    T0 = T1 = T2 = 0.0
+    for k in range(lo, hi + 1):
+        x = k - kp
+        for m in range(5):
+            s[m] += x ** m
+        xv, xxv = float(x) * v[k], float(x * x) * v[k]
+        T0 = T0 + v[k]
+        T1 = T1 + xv
+        T2 = T2 + xxv
+    S0, S1, S2, S3, S4 = (float(t) for t in s)
+    m0, m1, m2 = S2 * S0 - S1 * S1, S3 * S0 - S1 * S2, S3 * S1 - S2 * S2
+    D = (S4 * m0 - S3 * m1) + S2 * m2
+    p1, p2, p3 = T1 * S0 - S1 * T0, T1 * S1 - S2 * T0, S3 * T0 - S2 * T1
+    Da = (T2 * m0 - S3 * p1) + S2 * p2
+    Db = (S4 * p1 - T2 * m1) + S2 * p3
+    if D == 0.0:
+        return kp, n, 0, dms[kp], 0.0
+    a, b = Da / D, Db / D
+    if not a < 0.0:
+        return kp, n, 0, dms[kp], 0.0
+    vertex = (-b) / (2.0 * a)
+    return kp, n, 1, dms[kp] + vertex * ddm, math.sqrt(-1.0 / a) * ddm
+
+
+def peaks(acc, hits, kscale, nused, cands, ntrial, ddm, widths, smooth, fit_frac):
+    """-> dict(snr, struct float64 [ncand][ntrial], width, bin uint32 [ncand][ntrial], results DMSCAN_RESULT [ncand])"""
+    ncand, nt, nb = acc.shape
+    snr, strc = np.zeros((ncand, nt)), np.zeros((ncand, nt))
+    wd, bn = np.zeros((ncand, nt), np.uint32), np.zeros((ncand, nt), np.uint32)
+    res = np.zeros(ncand, dtype=post.DMSCAN_RESULT)
+    for i in range(ncand):
+        if not nused[i]:
+            continue
+        inv = 2.0 ** -int(kscale[i])
+        for k in range(nt):
+            a, h = [int(v) for v in acc[i, k]], [int(v) for v in hits[i, k]]
+            best = None
+            for w in widths:
+                for j, B in enumerate(boxcars(a, h, w, inv)):
+                    if best is None or B > best[0]:
+                        best = (B, w, j)
+            snr[i, k], wd[i, k], bn[i, k] = best
+            if nb > 1:
+                z = boxcars(a, h, smooth, inv)
+                total = 0.0
+                for j in range(nb - smooth):
+                    d = z[j + 1] - z[j]
+                    total = total + d * d
+                strc[i, k] = total - (2.0 * float(nb - smooth)) / float(smooth)
+        dms = trial_dms(cands[i]["dm"], nt, ddm)
+        r = res[i]
+        r["k"], r["nused"] = kscale[i], nused[i]
+        r["k_snr"], r["nfit_snr"], r["fitted_snr"], r["dm_snr"], r["dm_snr_err"] = fit([float(v) for v in snr[i]], fit_frac, dms, ddm)
+        if nb > 1:
+            r["k_struct"], r["nfit_struct"], r["fitted_struct"], r["dm_struct"], _e = fit([float(v) for v in strc[i]], fit_frac, dms, ddm)
+        else:
+            r["dm_struct"] = dms[0]
+        ks, kt = int(r["k_snr"]), int(r["k_struct"])
+        r["snr_peak"], r["width_snr"], r["bin_snr"] = snr[i, ks], wd[i, ks], bn[i, ks]
+        r["struct_peak"], r["snr_at_struct"], r["width_struct"], r["bin_struct"] = strc[i, kt], snr[i, kt], wd[i, kt], bn[i, kt]
+    return dict(snr=snr, struct=strc, width=wd, bin=bn, results=res)
+
+
+def scan(x, hdr, cands, ntrial, ddm, nbin, tfactor, widths=(1, 2, 4, 8), smooth=3, fit_frac=0.5, flag=None, coherency=False, **kw):
+    """everything: the planes, then the peaks"""
+    out = planes(x, hdr, cands, ntrial, ddm, nbin, tfactor, flag, coherency, **kw)
+    out.update(peaks(out["acc"], out["hits"], out["k"], out["nused"], cands, ntrial, ddm, list(widths), smooth, fit_frac))
+    return out
