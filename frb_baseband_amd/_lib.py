@@ -182,6 +182,25 @@ class FrbchDmscanResult(C.Structure):
                 ("k", C.c_int32), ("nused", C.c_uint32)]
 
 
+class FrbchAcfParams(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("nbin", C.c_uint32), ("tfactor", C.c_uint32), ("ffactor", C.c_uint32), ("nlagf", C.c_uint32),
+                ("nlagt", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class FrbchAcfFitParams(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("reserved", C.c_uint32), ("fit_frac", C.c_double)]
+
+
+class FrbchAcfResult(C.Structure):
+    _fields_ = [("width_f_mhz", C.c_double), ("width_t_ms", C.c_double), ("dt_df", C.c_double), ("drift", C.c_double),
+                ("ref", C.c_double), ("mff", C.c_double), ("mtf", C.c_double), ("mtt", C.c_double), ("k", C.c_int32),
+                ("r", C.c_uint32), ("nused", C.c_uint32), ("ncomplete", C.c_uint32), ("fitted_f", C.c_uint32),
+                ("fitted_t", C.c_uint32), ("fitted_d", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+ACF_PLAN, ACF_GENERIC = 0, 1
+
+
 class FrbchRfiParams(C.Structure):
     _fields_ = [("size", C.c_uint32), ("block_rows", C.c_uint32), ("t_cell", C.c_double), ("t_chan", C.c_double),
                 ("chan_frac", C.c_double), ("block_frac", C.c_double)]
@@ -350,6 +369,21 @@ SYMBOLS = {
     "frbch_dmscan_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32, _P,
                                     C.POINTER(FrbchDmscanParams), C.POINTER(FrbchDmscanPeakParams), C.c_int, _P, _P, _P, _P, _P, _P, _P,
                                     C.c_char_p, C.c_size_t]),
+    "frbch_acf2d_kernel": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "frbch_acf2d_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _P,
+                                     C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_acf2d_host": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _P,
+                                   C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_burstacf_fit": (C.c_int, [C.POINTER(FrbchFilDesc), C.POINTER(FrbchAcfParams), C.POINTER(FrbchAcfFitParams), C.c_uint32, _P, _P,
+                                     _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "frbch_burstacf_kernel": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32,
+                                        C.POINTER(FrbchAcfParams), _P]),
+    "frbch_burstacf_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32, _P,
+                                        C.POINTER(FrbchAcfParams), C.POINTER(FrbchAcfFitParams), C.c_int, _P, _P, _P, _P, _P, _P, _P,
+                                        C.c_char_p, C.c_size_t]),
+    "frbch_burstacf_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32, _P,
+                                      C.POINTER(FrbchAcfParams), C.POINTER(FrbchAcfFitParams), C.c_int, _P, _P, _P, _P, _P, _P, _P,
+                                      C.c_char_p, C.c_size_t]),
     "frbch_rfi_nblk": (C.c_long, [C.c_uint64, C.c_uint32]),
     "frbch_rfi_stats_kernel": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams)]),
     "frbch_rfi_stats_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams), C.c_int, _P,

@@ -4417,36 +4417,46 @@ struct DmOut {
   uint32_t k[2] = {0, 0};
 };
 
-// everything of a call inside its scope: the burst sums, the records, the launches, the peaks (all synchronised)
-int dm_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
-           const frbch_burst_cand* cands, uint32_t ncand, const uint8_t* flag, const frbch_dmscan_params* par,
-           const frbch_dmscan_peak_params* pk, PostScope& ps, DmOut* out, const PostErr& e) {
+// The host preparation of the header's DM section, inside a scope: the burst sums at cand.dm (synchronised), then per
+// candidate the window's first row, the records of the used channels, N_i and k_i.  The DM scan and the burst ACF share it.
+struct DmPrep {
+  std::vector<DmRec> rec;               // [ncand][nchan]
+  std::vector<DmCand> dc;               // [ncand]
+  std::vector<int32_t> kscale;          // [ncand]
+  std::vector<uint32_t> nused;          // [ncand]
+  std::vector<uint8_t> used;            // [ncand][nchan]
+  uint32_t p0 = 0, np = 1;              // the first product read and their number
+};
+int dm_prepare(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+               const frbch_burst_cand* cands, uint32_t ncand, const uint8_t* flag, uint32_t par_nbin, uint32_t par_tfactor,
+               PostScope& ps, DmPrep* out, uint32_t* kernel_used, const PostErr& e) {
   POST_NO_CONTRACT
-  const size_t nchan = fil->nchan, n = (size_t)ncand * nchan, nbin = par->nbin, nt = par->ntrial, nifs = fil->nifs;
-  std::vector<double> dms;
-  std::vector<int32_t> delays;
-  int rc = dm_build(fil, cands, ncand, par, &dms, &delays, e);
-  if (rc) return rc;
-  const DmPlanRule rule = dm_plan_rule(fil, d_rows, bpar->products, delays, ncand, par);
+  const size_t nchan = fil->nchan, n = (size_t)ncand * nchan, nifs = fil->nifs;
+  int rc;
   std::vector<frbch_burst_sums> sums;
   std::vector<float> spec(n * nifs), noise(n * nifs);
   std::vector<uint8_t> bused(n);
   BurstSums* d_sums = nullptr;
   POST_DEV(ps.alloc(&d_sums, n * nifs * sizeof(BurstSums)), "hipMalloc");
-  if ((rc = burst_run(fil, d_rows, nrows, bpar, cands, ncand, nullptr, d_sums, ps, &sums, spec.data(), noise.data(), bused.data(), &out->k[0], e)) != 0) return rc;
+  if ((rc = burst_run(fil, d_rows, nrows, bpar, cands, ncand, nullptr, d_sums, ps, &sums, spec.data(), noise.data(), bused.data(), kernel_used, e)) != 0) return rc;
   ps.drop(d_sums);
 
   // the records
   const bool coh = bpar->products == FRBCH_BURST_COHERENCY;
   const uint32_t p0 = coh ? 0u : fil->product, np = coh ? 2u : 1u;
-  std::vector<DmRec> rec(n);
-  std::vector<DmCand> dc(ncand);
-  std::vector<int32_t> kscale(ncand, 0);
-  std::vector<uint32_t> nused(ncand, 0);
+  out->p0 = p0; out->np = np;
+  std::vector<DmRec>& rec = out->rec;
+  std::vector<DmCand>& dc = out->dc;
+  std::vector<int32_t>& kscale = out->kscale;
+  std::vector<uint32_t>& nused = out->nused;
+  rec.resize(n);
+  dc.resize(ncand);
+  kscale.assign(ncand, 0);
+  nused.assign(ncand, 0);
   memset((void*)rec.data(), 0, n * sizeof(DmRec));
   out->used.assign(n, 0);
   for (uint32_t i = 0; i < ncand; ++i) {
-    dc[i].t0 = (long long)cands[i].sample - (long long)(par->nbin / 2) * (long long)par->tfactor;
+    dc[i].t0 = (long long)cands[i].sample - (long long)(par_nbin / 2) * (long long)par_tfactor;
     dc[i].scale = 0.0;
     double wmax = 0.0;
     for (size_t c = 0; c < nchan; ++c) {
@@ -4475,13 +4485,35 @@ int dm_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const 
       wmax = std::max(wmax, q.w);
     }
     if (!nused[i]) continue;
-    double M = ((double)par->tfactor * ldexp(1.0, fil->nbits)) * wmax;
+    double M = ((double)par_tfactor * ldexp(1.0, fil->nbits)) * wmax;
     if (coh) M = 2.0 * M;
     int ex = 0;
     (void)frexp(M, &ex);
     kscale[i] = 40 - ex;
     dc[i].scale = ldexp(1.0, kscale[i]);
   }
+  return FRBCH_OK;
+}
+
+// everything of a call inside its scope: the burst sums, the records, the launches, the peaks (all synchronised)
+int dm_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+           const frbch_burst_cand* cands, uint32_t ncand, const uint8_t* flag, const frbch_dmscan_params* par,
+           const frbch_dmscan_peak_params* pk, PostScope& ps, DmOut* out, const PostErr& e) {
+  POST_NO_CONTRACT
+  const size_t nchan = fil->nchan, n = (size_t)ncand * nchan, nbin = par->nbin, nt = par->ntrial;
+  std::vector<double> dms;
+  std::vector<int32_t> delays;
+  int rc = dm_build(fil, cands, ncand, par, &dms, &delays, e);
+  if (rc) return rc;
+  const DmPlanRule rule = dm_plan_rule(fil, d_rows, bpar->products, delays, ncand, par);
+  DmPrep prep;
+  if ((rc = dm_prepare(fil, d_rows, nrows, bpar, cands, ncand, flag, par->nbin, par->tfactor, ps, &prep, &out->k[0], e)) != 0) return rc;
+  out->used.swap(prep.used);
+  const uint32_t p0 = prep.p0, np = prep.np;
+  const std::vector<DmRec>& rec = prep.rec;
+  const std::vector<DmCand>& dc = prep.dc;
+  const std::vector<int32_t>& kscale = prep.kscale;
+  const std::vector<uint32_t>& nused = prep.nused;
 
   // the launches
   DmRec* d_rec = nullptr;
@@ -4512,6 +4544,7 @@ int dm_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const 
     POST_DEV(ps.alloc(&d_part, npart * sizeof(long long)), "hipMalloc");
     POST_DEV(ps.alloc(&d_hpart, npart * sizeof(uint32_t)), "hipMalloc");
     p.part = d_part; p.hpart = d_hpart;
+    const bool coh = np == 2;
     const unsigned nbr = (unsigned)((par->nbin + rule.brun - 1) / rule.brun), ntr = (unsigned)((par->ntrial + rule.trun - 1) / rule.trun);
     const dim3 grid((unsigned)rule.ntile * nbr, ntr, ncand), block(fast::kDmThreads);
     int lrc;
@@ -4640,5 +4673,487 @@ extern "C" int frbch_dmscan_host(const frbch_fil_desc* fil, const void* rows, ui
   void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
   return hs.run(e, "device memory for the rows", "upload rows", "download", [&]() {
     return frbch_dmscan_device(fil, d_rows, nrows, bpar, cands, ncand, flag, par, pk, device, acc, hits, snr, strc, results, used, kernel_used, err, err_cap);
+  });
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Structure of a burst: dedispersed dynamic spectrum and its two-dimensional ACF (include/frbch.h states the arithmetic)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr uint32_t kAcfMaxLagF = 1024, kAcfMaxLagT = 256;
+constexpr uint64_t kAcfMaxPlane = 1ull << 20, kAcfMaxCells = 1ull << 24, kAcfMaxLags = 1ull << 24, kAcfPartCap = 1ull << 30;
+constexpr int32_t kAcfMaxY = 1 << 21;
+
+int acf2_check(uint32_t n, uint32_t nsub, uint32_t nbin, uint32_t nlagf, uint32_t nlagt, uint32_t form, const PostErr& e) {
+  if (n < 1 || nsub < 1) return e.fail(FRBCH_E_ARG, "at least one plane and one subband");
+  if (nbin < 1 || nbin > kDmMaxBin) return e.fail(FRBCH_E_ARG, "nbin must be 1..1024");
+  if ((uint64_t)nsub * nbin > kAcfMaxPlane) return e.fail(FRBCH_E_ARG, "nsub * nbin exceeds 2^20: raise ffactor or cut the window");
+  if ((uint64_t)n * nsub * nbin > kAcfMaxCells) return e.fail(FRBCH_E_ARG, "ncand * nsub * nbin exceeds 2^24: cut the batch");
+  if (nlagf < 1 || nlagf > std::min(nsub, kAcfMaxLagF)) return e.fail(FRBCH_E_ARG, "nlagf must be 1..min(nsub, 1024)");
+  if (nlagt < 1 || nlagt > std::min(nbin, kAcfMaxLagT)) return e.fail(FRBCH_E_ARG, "nlagt must be 1..min(nbin, 256)");
+  if ((uint64_t)n * nlagf * (2ull * nlagt - 1) > kAcfMaxLags) return e.fail(FRBCH_E_ARG, "ncand * nlagf * (2 nlagt - 1) exceeds 2^24: cut the batch or the lags");
+  if (form > FRBCH_ACF_GENERIC) return e.fail(FRBCH_E_ARG, "form must be FRBCH_ACF_PLAN or FRBCH_ACF_GENERIC");
+  return FRBCH_OK;
+}
+
+// The plan rule of the ACF stage -- the one decision behind the launches, kernel_used and frbch_acf2d_kernel's answer.  Every
+// thread of the fast kernel owns 8 time lags: nrun = ceil((2 nlagt - 1) / 8) runs, nrunp = the next power of two; a workgroup
+// takes dfr = min(256 / nrunp, 8, nlagf rounded up to a power of two) frequency lags.  A b line holds nbin8 + 8 nrun positions
+// (nbin8 = nbin rounded up to 8) skewed by one word in eight, and the line stride bw is the next value = 9 nrunp (mod 32).  The
+// slab is the largest sb with (sb nbin8 + (sb + dfr - 1) bw) words <= 64 KiB, at most nsub.  Not fast: `form` asks for the
+// generic kernel, more than 65535 planes (the third grid dimension), or partials of the slabs above 2^30 bytes.  The emulator
+// build has no such kernel: generic.
+struct Acf2Plan { bool fastk; int sb, dfr, nrun, nrunp, bw, nslab, threads; size_t lds; };
+Acf2Plan acf2_plan_rule(uint32_t n, uint32_t nsub, uint32_t nbin, uint32_t nlagf, uint32_t nlagt, uint32_t form) {
+  Acf2Plan r{false, 0, 0, 0, 0, 0, 0, 0, 0};
+#ifndef FRBCH_NO_FAST
+  if (form == FRBCH_ACF_GENERIC || n > 65535u) return r;
+  const int ndt = 2 * (int)nlagt - 1, nrun = (ndt + fast::kAcfRun - 1) / fast::kAcfRun;
+  int nrunp = 1, lf = 1;
+  while (nrunp < nrun) nrunp <<= 1;
+  while (lf < (int)nlagf) lf <<= 1;
+  const int dfr = std::min({fast::kAcfThreads / nrunp, fast::kAcfMaxDfr, lf});
+  const int nbin8 = ((int)nbin + 7) & ~7, bwl = nbin8 + 8 * nrun, words = (int)(fast::kAcfLds / 4);
+  int bw = bwl + bwl / 8;
+  while (bw % 32 != (9 * nrunp) % 32) ++bw;
+  int sb = (words - (dfr - 1) * bw) / (nbin8 + bw);
+  if (sb < 1) return r;
+  sb = std::min(sb, (int)nsub);
+  const int nslab = ((int)nsub + sb - 1) / sb;
+  if ((uint64_t)n * (uint64_t)nslab * nlagf * (uint64_t)ndt * 8ull > kAcfPartCap) return r;
+  r = Acf2Plan{true, sb, dfr, nrun, nrunp, bw, nslab, std::max(64, dfr * nrunp), (size_t)(sb * nbin8 + (sb + dfr - 1) * bw) * 4};
+#else
+  (void)n; (void)nsub; (void)nbin; (void)nlagf; (void)nlagt; (void)form;
+#endif
+  return r;
+}
+
+// the launches of the stage on device planes, inside a scope; not synchronised
+int acf2_launch(const int32_t* d_y, uint32_t n, uint32_t nsub, uint32_t nbin, uint32_t nlagf, uint32_t nlagt, uint32_t form,
+                long long* d_A, PostScope& ps, uint32_t* kernel_used, const PostErr& e) {
+  const Acf2Plan pl = acf2_plan_rule(n, nsub, nbin, nlagf, nlagt, form);
+  Acf2Params p;
+  memset(&p, 0, sizeof p);
+  p.y = d_y; p.A = d_A; p.n = (int)n; p.nsub = (int)nsub; p.nbin = (int)nbin; p.nlagf = (int)nlagf; p.nlagt = (int)nlagt;
+  p.sb = pl.sb; p.dfr = pl.dfr; p.nrun = pl.nrun; p.nrunp = pl.nrunp; p.bw = pl.bw; p.nslab = pl.nslab;
+  const size_t nout = (size_t)n * nlagf * (2 * (size_t)nlagt - 1);
+  if (kernel_used) *kernel_used = pl.fastk ? 1 : 0;
+#ifndef FRBCH_NO_FAST
+  if (pl.fastk) {
+    long long* d_part = nullptr;
+    POST_DEV(ps.alloc(&d_part, nout * (size_t)pl.nslab * sizeof(long long)), "hipMalloc");
+    p.part = d_part;
+    const dim3 grid((unsigned)pl.nslab, (unsigned)((nlagf + pl.dfr - 1) / pl.dfr), n), block((unsigned)pl.threads);
+    POST_DEV(launch_lds(fast::frbch_post_acf2d_fast, grid, block, pl.lds, ps.s, p), "LDS size");
+    POST_DEV(dev_check_launch(), "launch ACF");
+    hipLaunchKernelGGL(fast::frbch_post_acf2d_join, dim3((unsigned)((nout + fast::kAcfThreads - 1) / fast::kAcfThreads)), dim3(fast::kAcfThreads), 0, ps.s, p);
+    POST_DEV(dev_check_launch(), "launch ACF join");
+    return FRBCH_OK;
+  }
+#endif
+  DEV_LAUNCH(frbch_post_acf2d, (nout + 255) / 256, 1, 256, 0, ps.s, p);
+  POST_DEV(dev_check_launch(), "launch ACF");
+  return FRBCH_OK;
+}
+
+int acf_check(const frbch_fil_desc* fil, uint64_t nrows, const frbch_burst_params* bpar, const frbch_burst_cand* cands,
+              uint32_t ncand, const frbch_acf_params* par, const PostErr& e) {
+  const int rc = burst_check(fil, nrows, bpar, cands, ncand, e);
+  if (rc) return rc;
+  if (fil->nbits == 32) return e.fail(FRBCH_E_ARG, "the burst ACF is not built for float32 rows: its fixed-point scale needs a bound on the samples");
+  if (!par || par->size != sizeof(frbch_acf_params)) return e.fail(FRBCH_E_ARG, "frbch_acf_params: wrong size");
+  if (par->nbin < 1 || par->nbin > kDmMaxBin) return e.fail(FRBCH_E_ARG, "nbin must be 1..1024");
+  if (par->tfactor < 1 || par->tfactor > kDmMaxTf) return e.fail(FRBCH_E_ARG, "tfactor must be 1..512");
+  if (fil->nchan > kRmMaxChan) return e.fail(FRBCH_E_ARG, "more than 16384 channels");
+  if (par->ffactor < 1 || par->ffactor > fil->nchan || fil->nchan % par->ffactor) return e.fail(FRBCH_E_ARG, "ffactor must be 1..nchan and divide nchan");
+  return acf2_check(ncand, fil->nchan / par->ffactor, par->nbin, par->nlagf, par->nlagt, FRBCH_ACF_PLAN, e);
+}
+
+int acf_check_fit(const frbch_acf_fit_params* fp, const PostErr& e) {
+  if (!fp || fp->size != sizeof(frbch_acf_fit_params)) return e.fail(FRBCH_E_ARG, "frbch_acf_fit_params: wrong size");
+  if (!(fp->fit_frac > 0.0) || !(fp->fit_frac < 1.0)) return e.fail(FRBCH_E_ARG, "fit_frac must lie inside (0, 1)");
+  return FRBCH_OK;
+}
+
+// the delays of the candidates at their own DM, [ncand][nchan]: the DM scan's table at one trial
+int acf_delays(const frbch_fil_desc* fil, const frbch_burst_cand* cands, uint32_t ncand, const frbch_acf_params* par,
+               std::vector<int32_t>* delays, const PostErr& e) {
+  const frbch_dmscan_params one{sizeof(frbch_dmscan_params), 1, par->nbin, par->tfactor, 0.0};
+  std::vector<double> dms;
+  return dm_build(fil, cands, ncand, &one, &dms, delays, e);
+}
+
+// The plan rule of the dynamic spectrum -- the one decision behind its launches, kernel_used[1] and frbch_burstacf_kernel's
+// answer.  The fast kernel wants what the fast DM scan kernel wants at one trial (the layout of the fast burst-sums kernel, bins
+// of at most kDmMaxT rows, tfactor + the delay range of every (candidate, 64-byte tile) <= kDmLds / (64 products) rows) and an
+// ffactor it can reduce: a power of two of at most the CT channels of a tile (shuffles over ffactor lanes, gl = ffactor), or a
+// multiple of CT (shuffles over the tile, gl = CT, and a join over tps = ffactor / CT tiles, whose partials stay within 2^30
+// bytes).  The emulator build has no such kernel: generic.
+struct DynPlan { bool fastk; int brun, ntile, gl, tps; };
+DynPlan dyn_plan_rule(const frbch_fil_desc* fil, const void* d_rows, uint32_t products, const std::vector<int32_t>& delays,
+                      uint32_t ncand, const frbch_acf_params* par) {
+  DynPlan r{false, 0, 0, 0, 0};
+#ifndef FRBCH_NO_FAST
+  if (!burst_fast_layout(fil, d_rows) || par->tfactor > (uint32_t)fast::kDmMaxT) return r;
+  const uint32_t ct = 64u / (uint32_t)(fil->nbits / 8), ntile = fil->nchan / ct, ff = par->ffactor;
+  const bool shuffle = (ff & (ff - 1)) == 0 && ff <= ct, join = ff > ct && ff % ct == 0;
+  if (!shuffle && !join) return r;
+  if (join && (uint64_t)ncand * ntile * par->nbin * 12ull > kDmPartCap) return r;
+  const int64_t cap = (int64_t)(fast::kDmLds / (64u * (products == FRBCH_BURST_COHERENCY ? 2u : 1u)));
+  int64_t range = 0;
+  for (size_t i = 0; i < ncand; ++i)
+    for (uint32_t t = 0; t < ntile; ++t) {
+      const int32_t* d = delays.data() + i * fil->nchan + (size_t)t * ct;
+      const auto mm = std::minmax_element(d, d + ct);
+      range = std::max<int64_t>(range, (int64_t)*mm.second - (int64_t)*mm.first);
+    }
+  if ((int64_t)par->tfactor + range > cap) return r;
+  r = DynPlan{true, (int)std::min<int64_t>((int64_t)par->nbin, (cap - range) / (int64_t)par->tfactor), (int)ntile, (int)std::min(ff, ct),
+              join ? (int)(ff / ct) : 0};
+#else
+  (void)fil; (void)d_rows; (void)products; (void)delays; (void)ncand; (void)par;
+#endif
+  return r;
+}
+
+// half-width at half maximum of a cut v[0 .. nl - 1] whose lag 0 is left out (the header's rule) -> x, *fitted
+double acf_half_width(const double* v, uint32_t nl, uint32_t* fitted) {
+  POST_NO_CONTRACT
+  *fitted = 0;
+  if (nl < 2 || !(v[1] > 0.0)) return 0.0;
+  const double h = v[1] / 2.0;
+  for (uint32_t d = 2; d < nl; ++d)
+    if (v[d] < h) {
+      const double a = v[d - 1] - h, b = v[d - 1] - v[d];
+      const double q = a / b;
+      *fitted = 1;
+      return (double)(d - 1) + q;
+    }
+  return (double)(nl - 1);
+}
+
+// step 4 of the header; every check has been made.  norm may be NULL.
+void acf_fit(const frbch_fil_desc* fil, const frbch_acf_params* par, double fit_frac, uint32_t ncand, const int32_t* k,
+             const uint32_t* r, const uint32_t* nused, const uint32_t* ncomplete, const int64_t* A, const uint32_t* P, double* norm,
+             frbch_acf_result* res) {
+  POST_NO_CONTRACT
+  const uint32_t nlf = par->nlagf, nlt = par->nlagt, ndt = 2 * nlt - 1, L = nlt - 1;
+  const size_t per = (size_t)nlf * ndt;
+  const double tu = (double)par->tfactor * fil->tsamp_s;
+  const double unit_t = tu * 1000.0;
+  const double unit_f = (double)par->ffactor * fil->foff_mhz;
+  std::vector<double> own(per), cut(std::max(nlf, nlt));
+  memset((void*)res, 0, (size_t)ncand * sizeof(frbch_acf_result));
+  for (uint32_t i = 0; i < ncand; ++i) {
+    double* nm = norm ? norm + (size_t)i * per : own.data();
+    if (!nused[i]) {
+      std::fill(nm, nm + per, 0.0);
+      continue;
+    }
+    frbch_acf_result& R = res[i];
+    R.k = k[i]; R.r = r[i]; R.nused = nused[i]; R.ncomplete = ncomplete[i];
+    const double q = ldexp(1.0, -2 * (k[i] - (int32_t)r[i]));
+    for (size_t l = 0; l < per; ++l) {
+      const uint32_t pv = P[(size_t)i * per + l];
+      const double a = (double)A[(size_t)i * per + l] * q;
+      nm[l] = pv ? a / (double)pv : 0.0;
+    }
+    for (uint32_t d = 0; d < nlf; ++d) cut[d] = nm[(size_t)d * ndt + L];
+    const double xf = acf_half_width(cut.data(), nlf, &R.fitted_f);
+    R.width_f_mhz = xf * fabs(unit_f);
+    for (uint32_t d = 0; d < nlt; ++d) cut[d] = nm[L + d];
+    const double xt = acf_half_width(cut.data(), nlt, &R.fitted_t);
+    R.width_t_ms = xt * unit_t;
+    bool any = false;
+    double ref = 0.0;
+    for (uint32_t df = 0; df < nlf; ++df)
+      for (uint32_t x = 0; x < ndt; ++x) {
+        if (df == 0 && x == L) continue;
+        const double v = nm[(size_t)df * ndt + x];
+        if (!any || v > ref) { ref = v; any = true; }
+      }
+    R.ref = ref;
+    if (!(ref > 0.0)) continue;
+    const double thr = fit_frac * ref;
+    double mff = 0.0, mtf = 0.0, mtt = 0.0;
+    for (uint32_t df = 0; df < nlf; ++df)
+      for (uint32_t x = 0; x < ndt; ++x) {
+        const long long dt = (long long)x - (long long)L;
+        if (df == 0 && dt <= 0) continue;
+        const double v = nm[(size_t)df * ndt + x];
+        if (!(v >= thr)) continue;
+        const double tf = v * (double)((long long)df * (long long)df), tx = v * (double)((long long)df * dt), tt = v * (double)(dt * dt);
+        mff = mff + tf;
+        mtf = mtf + tx;
+        mtt = mtt + tt;
+      }
+    R.mff = 2.0 * mff; R.mtf = 2.0 * mtf; R.mtt = 2.0 * mtt;
+    if (!(R.mff > 0.0)) continue;
+    const double slope = R.mtf / R.mff;
+    const double ms = slope * unit_t;
+    R.dt_df = ms / unit_f;
+    R.drift = R.dt_df != 0.0 ? 1.0 / R.dt_df : 0.0;
+    R.fitted_d = 1;
+  }
+}
+
+struct AcfOut {
+  std::vector<long long> Y, A;
+  std::vector<uint32_t> yhits, P;
+  std::vector<uint8_t> used;
+  std::vector<frbch_acf_result> res;
+  uint32_t k[3] = {0, 0, 0};
+};
+
+// everything of a call inside its scope: the preparation, the dynamic spectrum, the quantised plane, the ACFs, the fit
+int acf_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+            const frbch_burst_cand* cands, uint32_t ncand, const uint8_t* flag, const frbch_acf_params* par,
+            const frbch_acf_fit_params* fp, PostScope& ps, AcfOut* out, const PostErr& e) {
+  const size_t nchan = fil->nchan, n = (size_t)ncand * nchan, nbin = par->nbin, nsub = nchan / par->ffactor;
+  const size_t ncell = (size_t)ncand * nsub * nbin, ndt = 2 * (size_t)par->nlagt - 1, nlag = (size_t)ncand * par->nlagf * ndt;
+  std::vector<int32_t> delays;
+  int rc = acf_delays(fil, cands, ncand, par, &delays, e);
+  if (rc) return rc;
+  const DynPlan rule = dyn_plan_rule(fil, d_rows, bpar->products, delays, ncand, par);
+  DmPrep prep;
+  if ((rc = dm_prepare(fil, d_rows, nrows, bpar, cands, ncand, flag, par->nbin, par->tfactor, ps, &prep, &out->k[0], e)) != 0) return rc;
+  out->used.swap(prep.used);
+  std::vector<uint32_t> nused_s((size_t)ncand * nsub, 0);
+  for (size_t i = 0; i < ncand; ++i)
+    for (size_t c = 0; c < nchan; ++c) nused_s[i * nsub + c / par->ffactor] += out->used[i * nchan + c];
+
+  DmRec* d_rec = nullptr;
+  DmCand* d_dc = nullptr;
+  int32_t *d_dly = nullptr, *d_shift = nullptr, *d_y = nullptr, *d_mask = nullptr;
+  uint32_t *d_nu = nullptr, *d_hits = nullptr;
+  long long *d_Y = nullptr, *d_rowmax = nullptr, *d_A = nullptr;
+  POST_DEV(ps.alloc(&d_rec, n * sizeof(DmRec)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_dc, (size_t)ncand * sizeof(DmCand)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_dly, delays.size() * sizeof(int32_t)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_nu, nused_s.size() * sizeof(uint32_t)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_Y, ncell * sizeof(long long)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_hits, ncell * sizeof(uint32_t)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_rowmax, (size_t)ncand * nsub * sizeof(long long)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_shift, (size_t)ncand * sizeof(int32_t)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_y, ncell * sizeof(int32_t)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_mask, ncell * sizeof(int32_t)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_A, nlag * sizeof(long long)), "hipMalloc");
+  POST_DEV(dev_h2d(d_rec, prep.rec.data(), n * sizeof(DmRec), ps.s), "upload records");
+  POST_DEV(dev_h2d(d_dc, prep.dc.data(), (size_t)ncand * sizeof(DmCand), ps.s), "upload records");
+  POST_DEV(dev_h2d(d_dly, delays.data(), delays.size() * sizeof(int32_t), ps.s), "upload delays");
+  POST_DEV(dev_h2d(d_nu, nused_s.data(), nused_s.size() * sizeof(uint32_t), ps.s), "upload records");
+  DynParams p = post_params<DynParams>(fil, d_rows, nrows);
+  p.ncand = (int)ncand; p.cand = d_dc; p.rec = d_rec; p.delays = d_dly; p.nused_s = d_nu; p.Y = d_Y; p.yhits = d_hits;
+  p.rowmax = d_rowmax; p.shift = d_shift; p.y = d_y; p.mask = d_mask;
+  p.nsub = (int)nsub; p.nbin = (int)par->nbin; p.tfactor = (int)par->tfactor; p.ffactor = (int)par->ffactor;
+  p.p0 = (int)prep.p0; p.np = (int)prep.np; p.ntile = rule.ntile; p.brun = rule.brun; p.gl = rule.gl;
+  out->k[1] = rule.fastk ? 1 : 0;
+  bool launched = false;
+#ifndef FRBCH_NO_FAST
+  if (rule.fastk) {
+    long long* d_part = nullptr;
+    uint32_t* d_hpart = nullptr;
+    if (rule.tps) {
+      const size_t npart = (size_t)ncand * rule.ntile * nbin;
+      POST_DEV(ps.alloc(&d_part, npart * sizeof(long long)), "hipMalloc");
+      POST_DEV(ps.alloc(&d_hpart, npart * sizeof(uint32_t)), "hipMalloc");
+      p.part = d_part; p.hpart = d_hpart;
+    }
+    const bool coh = prep.np == 2;
+    const unsigned nbr = (unsigned)((par->nbin + rule.brun - 1) / rule.brun);
+    const dim3 grid((unsigned)rule.ntile * nbr, 1, ncand), block(fast::kDmThreads);
+    int lrc;
+    if (fil->nbits == 8) lrc = coh ? launch_lds(fast::frbch_post_dynspec_fast<1, 2>, grid, block, fast::kDmLds, ps.s, p)
+                                   : launch_lds(fast::frbch_post_dynspec_fast<1, 1>, grid, block, fast::kDmLds, ps.s, p);
+    else lrc = coh ? launch_lds(fast::frbch_post_dynspec_fast<2, 2>, grid, block, fast::kDmLds, ps.s, p)
+                   : launch_lds(fast::frbch_post_dynspec_fast<2, 1>, grid, block, fast::kDmLds, ps.s, p);
+    POST_DEV(lrc, "LDS size");
+    POST_DEV(dev_check_launch(), "launch dynamic spectrum");
+    if (rule.tps) {
+      hipLaunchKernelGGL(fast::frbch_post_dynspec_join, dim3((unsigned)((ncell + fast::kDmThreads - 1) / fast::kDmThreads)), dim3(fast::kDmThreads), 0, ps.s, p, rule.tps);
+      POST_DEV(dev_check_launch(), "launch dynamic spectrum join");
+    }
+    launched = true;
+  }
+#endif
+  if (!launched) {
+    DEV_LAUNCH(frbch_post_dynspec, (ncell + 255) / 256, 1, 256, 0, ps.s, p);
+    POST_DEV(dev_check_launch(), "launch dynamic spectrum");
+  }
+  DEV_LAUNCH(frbch_post_acf_rowmax, ((size_t)ncand * nsub + 255) / 256, 1, 256, 0, ps.s, p);
+  POST_DEV(dev_check_launch(), "launch row maxima");
+  DEV_LAUNCH(frbch_post_acf_shift, (ncand + 255) / 256, 1, 256, 0, ps.s, p);
+  POST_DEV(dev_check_launch(), "launch scale");
+  DEV_LAUNCH(frbch_post_acf_quant, (ncell + 255) / 256, 1, 256, 0, ps.s, p);
+  POST_DEV(dev_check_launch(), "launch quantisation");
+  if ((rc = acf2_launch(d_y, ncand, (uint32_t)nsub, par->nbin, par->nlagf, par->nlagt, FRBCH_ACF_PLAN, d_A, ps, &out->k[2], e)) != 0) return rc;
+  std::vector<int32_t> shift(ncand);
+  out->Y.resize(ncell);
+  out->yhits.resize(ncell);
+  out->A.resize(nlag);
+  POST_DEV(dev_d2h(out->Y.data(), d_Y, ncell * sizeof(long long), ps.s), "download dynamic spectrum");
+  POST_DEV(dev_d2h(out->yhits.data(), d_hits, ncell * sizeof(uint32_t), ps.s), "download dynamic spectrum");
+  POST_DEV(dev_d2h(shift.data(), d_shift, (size_t)ncand * sizeof(int32_t), ps.s), "download scale");
+  POST_DEV(dev_d2h(out->A.data(), d_A, nlag * sizeof(long long), ps.s), "download ACF");
+  POST_DEV(dev_sync(ps.s), "sync");
+
+  // the complete cells of every candidate; all of them complete: P in closed form, else the same kernel on the 0 / 1 plane
+  std::vector<uint32_t> ncomplete(ncand, 0), ushift(ncand);
+  for (size_t i = 0; i < ncand; ++i) {
+    ushift[i] = (uint32_t)shift[i];
+    for (size_t s = 0; s < nsub; ++s) {
+      const uint32_t nu = nused_s[i * nsub + s];
+      if (!nu) continue;
+      const uint32_t* h = out->yhits.data() + (i * nsub + s) * nbin;
+      for (size_t j = 0; j < nbin; ++j) ncomplete[i] += h[j] == par->tfactor * nu ? 1u : 0u;
+    }
+  }
+  out->P.resize(nlag);
+  bool all = true;
+  for (size_t i = 0; i < ncand; ++i) all = all && ncomplete[i] == nsub * nbin;
+  if (all) {
+    for (size_t i = 0; i < ncand; ++i)
+      for (size_t df = 0; df < par->nlagf; ++df)
+        for (size_t x = 0; x < ndt; ++x) {
+          const size_t adt = x >= par->nlagt - 1 ? x - (par->nlagt - 1) : (par->nlagt - 1) - x;
+          out->P[(i * par->nlagf + df) * ndt + x] = (uint32_t)((nsub - df) * (nbin - adt));
+        }
+  } else {
+    std::vector<long long> pairs(nlag);
+    uint32_t kp = 0;
+    if ((rc = acf2_launch(d_mask, ncand, (uint32_t)nsub, par->nbin, par->nlagf, par->nlagt, FRBCH_ACF_PLAN, d_A, ps, &kp, e)) != 0) return rc;
+    POST_DEV(dev_d2h(pairs.data(), d_A, nlag * sizeof(long long), ps.s), "download pair counts");
+    POST_DEV(dev_sync(ps.s), "sync");
+    for (size_t l = 0; l < nlag; ++l) out->P[l] = (uint32_t)pairs[l];
+  }
+  out->res.resize(ncand);
+  acf_fit(fil, par, fp->fit_frac, ncand, prep.kscale.data(), ushift.data(), prep.nused.data(), ncomplete.data(),
+          (const int64_t*)out->A.data(), out->P.data(), nullptr, out->res.data());
+  return FRBCH_OK;
+}
+}  // namespace
+
+extern "C" int frbch_acf2d_kernel(uint32_t n, uint32_t nsub, uint32_t nbin, uint32_t nlagf, uint32_t nlagt, uint32_t form) {
+  const int rc = acf2_check(n, nsub, nbin, nlagf, nlagt, form, PostErr{nullptr, 0});
+  return rc ? rc : (acf2_plan_rule(n, nsub, nbin, nlagf, nlagt, form).fastk ? 1 : 0);
+}
+
+extern "C" int frbch_acf2d_device(const int32_t* d_y, uint32_t n, uint32_t nsub, uint32_t nbin, uint32_t nlagf, uint32_t nlagt,
+                                  uint32_t form, int device, int64_t* d_A, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  static_assert(sizeof(frbch_acf_params) == 32 && sizeof(frbch_acf_fit_params) == 16 && sizeof(frbch_acf_result) == 96, "ACF records");
+  PostErr e{err, err_cap};
+  int rc = acf2_check(n, nsub, nbin, nlagf, nlagt, form, e);
+  if (rc) return rc;
+  if (!d_y || !d_A) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  PostScope ps;
+  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  uint32_t k = 0;
+  if ((rc = acf2_launch(d_y, n, nsub, nbin, nlagf, nlagt, form, (long long*)d_A, ps, &k, e)) != 0) return rc;
+  POST_DEV(dev_sync(ps.s), "sync");
+  if (kernel_used) *kernel_used = k;
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_acf2d_host(const int32_t* y, uint32_t n, uint32_t nsub, uint32_t nbin, uint32_t nlagf, uint32_t nlagt,
+                                uint32_t form, int device, int64_t* A, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  int rc = acf2_check(n, nsub, nbin, nlagf, nlagt, form, e);
+  if (rc) return rc;
+  if (!y || !A) return e.fail(FRBCH_E_ARG, "null argument");
+  const size_t ncell = (size_t)n * nsub * nbin, nlag = (size_t)n * nlagf * (2 * (size_t)nlagt - 1);
+  for (size_t i = 0; i < ncell; ++i)
+    if (y[i] > kAcfMaxY || y[i] < -kAcfMaxY) return e.fail(FRBCH_E_ARG, "a value of the plane lies outside -2^21 .. 2^21: the int64 sums are not safe");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  int32_t* d_y = hs.in(y, ncell * sizeof(int32_t));
+  int64_t* d_A = hs.out(A, nlag * sizeof(int64_t));
+  return hs.run(e, "device memory for the plane", "upload plane", "download ACF", [&]() {
+    return frbch_acf2d_device(d_y, n, nsub, nbin, nlagf, nlagt, form, device, d_A, kernel_used, err, err_cap);
+  });
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_burstacf_fit(const frbch_fil_desc* fil, const frbch_acf_params* par, const frbch_acf_fit_params* fp, uint32_t ncand,
+                                  const int32_t* k, const uint32_t* r, const uint32_t* nused, const uint32_t* ncomplete, const int64_t* A,
+                                  const uint32_t* P, double* norm, frbch_acf_result* results, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  if (!fil || fil->size != sizeof(frbch_fil_desc) || fil->nchan < 1 || !(fil->tsamp_s > 0) || fil->foff_mhz == 0.0) return e.fail(FRBCH_E_ARG, "frbch_fil_desc: wrong size, or bad nchan / tsamp / foff");
+  if (!par || par->size != sizeof(frbch_acf_params)) return e.fail(FRBCH_E_ARG, "frbch_acf_params: wrong size");
+  if (par->tfactor < 1 || par->tfactor > kDmMaxTf) return e.fail(FRBCH_E_ARG, "tfactor must be 1..512");
+  if (par->ffactor < 1 || par->ffactor > fil->nchan || fil->nchan % par->ffactor) return e.fail(FRBCH_E_ARG, "ffactor must be 1..nchan and divide nchan");
+  int rc = acf2_check(ncand, fil->nchan / par->ffactor, par->nbin, par->nlagf, par->nlagt, FRBCH_ACF_PLAN, e);
+  if (rc) return rc;
+  if ((rc = acf_check_fit(fp, e)) != 0) return rc;
+  if (!k || !r || !nused || !ncomplete || !A || !P) return e.fail(FRBCH_E_ARG, "null argument");
+  for (uint32_t i = 0; i < ncand; ++i)
+    if (r[i] > 40 || k[i] < -1024 || k[i] > 1024) return e.fail(FRBCH_E_ARG, "candidate " + std::to_string(i) + ": k or r out of range");
+  std::vector<frbch_acf_result> res(ncand);
+  std::vector<double> nm(norm ? (size_t)ncand * par->nlagf * (2 * (size_t)par->nlagt - 1) : 0);
+  acf_fit(fil, par, fp->fit_frac, ncand, k, r, nused, ncomplete, A, P, norm ? nm.data() : nullptr, res.data());
+  if (norm) memcpy(norm, nm.data(), nm.size() * sizeof(double));
+  if (results) memcpy((void*)results, res.data(), (size_t)ncand * sizeof(frbch_acf_result));
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_burstacf_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                     const frbch_burst_cand* cands, uint32_t ncand, const frbch_acf_params* par, uint32_t* kernel_used) try {
+  PostErr e{nullptr, 0};
+  int rc = acf_check(fil, nrows, bpar, cands, ncand, par, e);
+  if (rc) return rc;
+  if (!d_rows) return FRBCH_E_ARG;
+  std::vector<int32_t> delays;
+  if ((rc = acf_delays(fil, cands, ncand, par, &delays, e)) != 0) return rc;
+  if (kernel_used) {
+    kernel_used[0] = burst_fast_layout(fil, d_rows) ? 1 : 0;
+    kernel_used[1] = dyn_plan_rule(fil, d_rows, bpar->products, delays, ncand, par).fastk ? 1 : 0;
+    kernel_used[2] = acf2_plan_rule(ncand, fil->nchan / par->ffactor, par->nbin, par->nlagf, par->nlagt, FRBCH_ACF_PLAN).fastk ? 1 : 0;
+  }
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return FRBCH_E_NOMEM; }
+
+extern "C" int frbch_burstacf_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                     const frbch_burst_cand* cands, uint32_t ncand, const uint8_t* flag, const frbch_acf_params* par,
+                                     const frbch_acf_fit_params* fp, int device, int64_t* Y, uint32_t* yhits, int64_t* A, uint32_t* P,
+                                     frbch_acf_result* results, uint8_t* used, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  int rc = acf_check(fil, nrows, bpar, cands, ncand, par, e);
+  if (rc) return rc;
+  if ((rc = acf_check_fit(fp, e)) != 0) return rc;
+  if (!d_rows) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  AcfOut out;
+  {
+    DeviceGuard dg(device);
+    PostScope ps;
+    if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+    if ((rc = acf_run(fil, d_rows, nrows, bpar, cands, ncand, flag, par, fp, ps, &out, e)) != 0) return rc;
+  }
+  if (Y) memcpy(Y, out.Y.data(), out.Y.size() * sizeof(long long));
+  if (yhits) memcpy(yhits, out.yhits.data(), out.yhits.size() * sizeof(uint32_t));
+  if (A) memcpy(A, out.A.data(), out.A.size() * sizeof(long long));
+  if (P) memcpy(P, out.P.data(), out.P.size() * sizeof(uint32_t));
+  if (results) memcpy((void*)results, out.res.data(), out.res.size() * sizeof(frbch_acf_result));
+  if (used) memcpy(used, out.used.data(), out.used.size());
+  if (kernel_used) { kernel_used[0] = out.k[0]; kernel_used[1] = out.k[1]; kernel_used[2] = out.k[2]; }
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_burstacf_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                   const frbch_burst_cand* cands, uint32_t ncand, const uint8_t* flag, const frbch_acf_params* par,
+                                   const frbch_acf_fit_params* fp, int device, int64_t* Y, uint32_t* yhits, int64_t* A, uint32_t* P,
+                                   frbch_acf_result* results, uint8_t* used, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  int rc = acf_check(fil, nrows, bpar, cands, ncand, par, e);
+  if (rc) return rc;
+  if ((rc = acf_check_fit(fp, e)) != 0) return rc;
+  if (!rows) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
+  return hs.run(e, "device memory for the rows", "upload rows", "download", [&]() {
+    return frbch_burstacf_device(fil, d_rows, nrows, bpar, cands, ncand, flag, par, fp, device, Y, yhits, A, P, results, used, kernel_used, err, err_cap);
   });
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }

@@ -1359,3 +1359,149 @@ KERNEL(frbch_post_dmscan, DmParams) {
     }
   }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Structure of a burst (frbch_burstacf_*, frbch_acf2d_*; include/frbch.h states the arithmetic): the dedispersed dynamic
+// spectrum per (candidate, subband, bin) from the same dm_term as the DM scan, its largest complete cell, the quantised
+// int32 plane, and the two-dimensional autocorrelation of such a plane in int64.  Every sum is an exact integer sum, so the
+// generic kernels below and the fast ones (kernels_post_fast.inc) differ in schedule only.
+// ---------------------------------------------------------------------------------------------------------------------
+struct DynParams {
+  const uint8_t* rows;         // [nrows][nifs][nchan] samples of `nbits` (8 or 16)
+  uint64_t nrows;
+  int nchan, nifs, nbits, ncand;
+  const DmCand* cand;          // [ncand]
+  const DmRec* rec;            // [ncand][nchan]
+  const int32_t* delays;       // [ncand][nchan]: n_c(cand.dm)
+  const uint32_t* nused_s;     // [ncand][nsub]: the used channels of a subband
+  long long* Y;                // [ncand][nsub][nbin]
+  uint32_t* yhits;             // [ncand][nsub][nbin]
+  long long* part;             // fast kernel, join form: [ncand][ntile][nbin]
+  uint32_t* hpart;             // the same shape
+  long long* rowmax;           // [ncand][nsub]: the largest |Y| over the complete cells of a subband
+  int32_t* shift;              // [ncand]: r_i
+  int32_t* y;                  // [ncand][nsub][nbin]
+  int32_t* mask;               // [ncand][nsub][nbin]: 1 = complete
+  int nsub, nbin, tfactor, ffactor, p0, np, ntile, brun, gl;      // gl: the lanes a shuffle reduction spans (fast kernel)
+};
+
+// grid (ceil(ncand nsub nbin / 256)), one thread per (candidate, subband, bin), channels ascending, rows ascending
+KERNEL(frbch_post_dynspec, DynParams) {
+  K_PROLOGUE;
+  (void)smem; (void)by;
+  PHASE {
+    const long long idx = (long long)bx * nthr + tid;
+    if (idx < (long long)p.ncand * p.nsub * p.nbin) {
+      const int j = (int)(idx % p.nbin);
+      const long long is = idx / p.nbin;                       // candidate * nsub + subband
+      const int cand = (int)(is / p.nsub), s = (int)(is % p.nsub);
+      const DmCand cd = p.cand[cand];
+      const DmRec* rec = p.rec + (size_t)cand * p.nchan;
+      const int32_t* dl = p.delays + (size_t)cand * p.nchan;
+      const uint64_t pitch = (uint64_t)p.nifs * (uint64_t)p.nchan;
+      const long long b0 = cd.t0 + (long long)j * (long long)p.tfactor;
+      long long a = 0;
+      uint32_t hits = 0;
+      for (int c = s * p.ffactor; c < (s + 1) * p.ffactor; ++c) {
+        if (!rec[c].used) continue;
+        long long lo, hi;
+        burst_clip(b0, (uint32_t)p.tfactor, (long long)dl[c], (long long)p.nrows, &lo, &hi);
+        if (hi <= lo) continue;
+        uint32_t S = 0;
+        for (long long t = lo; t < hi; ++t)
+          for (int pr = p.p0; pr < p.p0 + p.np; ++pr) {
+            const uint64_t o = (uint64_t)t * pitch + (uint64_t)pr * (uint64_t)p.nchan + (uint64_t)c;
+            S += p.nbits == 8 ? (uint32_t)p.rows[o] : (uint32_t)((const uint16_t*)p.rows)[o];
+          }
+        a += dm_term(rec[c].mean, rec[c].w, cd.scale, S, (uint32_t)(hi - lo));
+        hits += (uint32_t)(hi - lo);
+      }
+      p.Y[idx] = a;
+      p.yhits[idx] = hits;
+    }
+  }
+}
+
+DEVFN inline bool acf_complete(uint32_t nused_s, uint32_t yhits, int tfactor) { return nused_s > 0 && yhits == (uint32_t)tfactor * nused_s; }
+
+// grid (ceil(ncand nsub / 256)), one thread per (candidate, subband): the largest |Y| over its complete cells
+KERNEL(frbch_post_acf_rowmax, DynParams) {
+  K_PROLOGUE;
+  (void)smem; (void)by;
+  PHASE {
+    const long long is = (long long)bx * nthr + tid;
+    if (is < (long long)p.ncand * p.nsub) {
+      const uint32_t nu = p.nused_s[is];
+      long long m = 0;
+      for (int j = 0; j < p.nbin; ++j) {
+        const long long v = p.Y[(size_t)is * p.nbin + j];
+        if (acf_complete(nu, p.yhits[(size_t)is * p.nbin + j], p.tfactor)) m = m > (v < 0 ? -v : v) ? m : (v < 0 ? -v : v);
+      }
+      p.rowmax[is] = m;
+    }
+  }
+}
+
+// grid (ceil(ncand / 256)), one thread per candidate: m_i, and from its bit length the shift r_i
+KERNEL(frbch_post_acf_shift, DynParams) {
+  K_PROLOGUE;
+  (void)smem; (void)by;
+  PHASE {
+    const int cand = bx * nthr + tid;
+    if (cand < p.ncand) {
+      long long m = 0;
+      for (int s = 0; s < p.nsub; ++s) m = m > p.rowmax[(size_t)cand * p.nsub + s] ? m : p.rowmax[(size_t)cand * p.nsub + s];
+      int b = 0;
+      while (m) { ++b; m >>= 1; }
+      p.shift[cand] = b > 21 ? b - 21 : 0;
+    }
+  }
+}
+
+// grid (ceil(ncand nsub nbin / 256)), one thread per cell: y and the 0 / 1 plane of the complete cells
+KERNEL(frbch_post_acf_quant, DynParams) {
+  K_PROLOGUE;
+  (void)smem; (void)by;
+  PHASE {
+    const long long idx = (long long)bx * nthr + tid;
+    if (idx < (long long)p.ncand * p.nsub * p.nbin) {
+      const long long is = idx / p.nbin;
+      const int r = p.shift[is / p.nsub];
+      const bool ok = acf_complete(p.nused_s[is], p.yhits[idx], p.tfactor);
+      const long long v = p.Y[idx];
+      p.y[idx] = !ok ? 0 : (int32_t)(r > 0 ? (v + (1ll << (r - 1))) >> r : v);
+      p.mask[idx] = ok ? 1 : 0;
+    }
+  }
+}
+
+struct Acf2Params {
+  const int32_t* y;            // [n][nsub][nbin], |y| <= 2^21
+  long long* A;                // [n][nlagf][2 nlagt - 1]
+  long long* part;             // fast kernel: [n][nslab][nlagf][2 nlagt - 1]
+  int n, nsub, nbin, nlagf, nlagt;
+  int sb, dfr, nrun, nrunp, bw, nslab;       // fast kernel: the plan (acf2_plan_rule)
+};
+
+// grid (ceil(n nlagf (2 nlagt - 1) / 256)), one thread per (plane, df, dt), s then j ascending
+KERNEL(frbch_post_acf2d, Acf2Params) {
+  K_PROLOGUE;
+  (void)smem; (void)by;
+  PHASE {
+    const int ndt = 2 * p.nlagt - 1;
+    const long long idx = (long long)bx * nthr + tid;
+    if (idx < (long long)p.n * p.nlagf * ndt) {
+      const int dt = (int)(idx % ndt) - (p.nlagt - 1);
+      const int df = (int)((idx / ndt) % p.nlagf);
+      const int32_t* y = p.y + (size_t)(idx / ((long long)ndt * p.nlagf)) * p.nsub * p.nbin;
+      const int jlo = dt < 0 ? -dt : 0, jhi = dt > 0 ? p.nbin - dt : p.nbin;
+      long long a = 0;
+      for (int s = 0; s + df < p.nsub; ++s) {
+        const int32_t* u = y + (size_t)s * p.nbin;
+        const int32_t* v = y + (size_t)(s + df) * p.nbin + dt;
+        for (int j = jlo; j < jhi; ++j) a += (long long)u[j] * (long long)v[j];
+      }
+      p.A[idx] = a;
+    }
+  }
+}

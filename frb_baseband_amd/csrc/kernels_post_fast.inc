@@ -1298,4 +1298,177 @@ __global__ void __launch_bounds__(kDmThreads) frbch_post_dmscan_join(DmParams p)
   p.acc[idx] = a;
   p.hits[idx] = h;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Structure of a burst, the dynamic spectrum (HIP only; frbch_post_dynspec of kernels_post.inc stays the emulable form and the
+// fallback; both call dm_term).  The staging scheme of frbch_post_dmscan_fast at one trial: a workgroup of 256 threads owns one
+// candidate, one 64-byte tile of the row (CT = 64 / 32 channels) and a run of `brun` bins, and stages the rows those bins need
+// over the delay range of its tile -- nb tfactor + (dmax - dmin) <= kDmLds / (64 NP) rows, the host's plan rule sees to that.
+// One thread per (channel, bin) forms its term; then only the gl = min(ffactor, CT) neighbouring lanes of a subband add theirs
+// up by shuffles (gl is a power of two).  ffactor <= CT: the leading lane of every group stores the cell of its subband, no
+// join.  ffactor a multiple of CT: gl = CT, the tile's sum is a partial and frbch_post_dynspec_join adds the ffactor / CT tiles
+// of a subband in ascending order.  grid (tiles x ceil(nbin / brun), 1, ncand).
+// ---------------------------------------------------------------------------------------------------------------------
+template <int BPV, int NP>
+__global__ void __launch_bounds__(kDmThreads) frbch_post_dynspec_fast(DynParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int CT = 64 / BPV, BPP = kDmThreads / CT, ROWB = 64 * NP, CAP = (int)(kDmLds / ROWB);
+  const int tid = threadIdx.x, ch = tid % CT, jl = tid / CT;
+  const int tile = (int)blockIdx.x % p.ntile, cand = blockIdx.z;
+  const int j0 = ((int)blockIdx.x / p.ntile) * p.brun;
+  const int nb = min(p.brun, p.nbin - j0);
+  const DmCand cd = p.cand[cand];
+  const DmRec r = p.rec[(size_t)cand * p.nchan + (size_t)tile * CT + ch];
+  const int delay = p.delays[(size_t)cand * p.nchan + (size_t)tile * CT + ch];
+  int dmin = delay, dmax = delay;
+#pragma unroll
+  for (int m = 1; m < CT; m <<= 1) {                                       // over the tile's channels: the same in every thread
+    dmin = min(dmin, __shfl_xor(dmin, m));
+    dmax = max(dmax, __shfl_xor(dmax, m));
+  }
+  const long long nrows = (long long)p.nrows;
+  const long long base = cd.t0 + (long long)j0 * (long long)p.tfactor + (long long)dmin;     // the file row of LDS row 0
+  const long long span = (long long)nb * p.tfactor + ((long long)dmax - (long long)dmin);
+  if (span > CAP) return;                                                  // (the plan rule never launches such a run)
+  const size_t stride = (size_t)p.nifs * p.nchan * BPV, pstride = (size_t)p.nchan * BPV;
+  const unsigned char* src = p.rows + (size_t)p.p0 * pstride + (size_t)tile * 64;
+  for (int i = tid; i < (int)span * (ROWB / 16); i += kDmThreads) {
+    const long long row = base + (long long)(i / (ROWB / 16));
+    if (row >= 0 && row < nrows)
+      *reinterpret_cast<uint4*>(smem + (size_t)i * 16) =
+          *reinterpret_cast<const uint4*>(src + (size_t)row * stride + (size_t)((i >> 2) % NP) * pstride + (size_t)(i & 3) * 16);
+  }
+  __syncthreads();
+  for (int jb0 = 0; jb0 < nb; jb0 += BPP) {                                // (the same trips in every thread: the shuffles meet whole waves)
+    const int jb = jb0 + jl;
+    long long a = 0;
+    uint32_t h = 0;
+    if (jb < nb && r.used) {
+      const long long b0 = cd.t0 + (long long)(j0 + jb) * (long long)p.tfactor;
+      long long lo, hi;
+      burst_clip(b0, (uint32_t)p.tfactor, (long long)delay, nrows, &lo, &hi);
+      if (hi > lo) {
+        uint32_t S = 0;
+        const unsigned char* q = smem + (size_t)(lo - base) * ROWB + (size_t)ch * BPV;
+        for (long long t = lo; t < hi; ++t, q += ROWB) {
+#pragma unroll
+          for (int pr = 0; pr < NP; ++pr) {
+            if constexpr (BPV == 1) S += (uint32_t)q[pr * 64];
+            else S += (uint32_t)*reinterpret_cast<const uint16_t*>(q + pr * 64);
+          }
+        }
+        h = (uint32_t)(hi - lo);
+        a = dm_term(r.mean, r.w, cd.scale, S, h);
+      }
+    }
+    for (int m = 1; m < p.gl; m <<= 1) {
+      a += __shfl_xor(a, m);
+      h += __shfl_xor(h, m);
+    }
+    if (ch % p.gl == 0 && jb < nb) {
+      if (p.ffactor <= CT) {
+        const size_t o = ((size_t)cand * p.nsub + (size_t)(tile * CT + ch) / p.ffactor) * p.nbin + (size_t)(j0 + jb);
+        p.Y[o] = a;
+        p.yhits[o] = h;
+      } else {
+        const size_t o = ((size_t)cand * p.ntile + tile) * p.nbin + (size_t)(j0 + jb);
+        p.part[o] = a;
+        p.hpart[o] = h;
+      }
+    }
+  }
+}
+
+// grid (ceil(ncand nsub nbin / 256)): the ffactor / CT tiles of a subband, added in ascending tile (tps = tiles per subband)
+__global__ void __launch_bounds__(kDmThreads) frbch_post_dynspec_join(DynParams p, int tps) {
+  const size_t idx = (size_t)blockIdx.x * kDmThreads + threadIdx.x;
+  if (idx >= (size_t)p.ncand * p.nsub * p.nbin) return;
+  const size_t j = idx % p.nbin, is = idx / p.nbin, cand = is / p.nsub, s = is % p.nsub;
+  long long a = 0;
+  uint32_t h = 0;
+  for (int t = 0; t < tps; ++t) {
+    const size_t o = (cand * p.ntile + s * tps + t) * p.nbin + j;
+    a += p.part[o];
+    h += p.hpart[o];
+  }
+  p.Y[idx] = a;
+  p.yhits[idx] = h;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Structure of a burst, the two-dimensional autocorrelation (HIP only; frbch_post_acf2d of kernels_post.inc stays the emulable
+// form and the fallback).  A[df][dt] = sum over s, j of y[s][j] y[s + df][j + dt], int64, exact in any order.
+// A workgroup owns one plane, a run of `dfr` frequency lags from df0 and a slab of `sb` subbands from s0.  It stages
+//   a: the slab's rows, [sb][nbin8] int32, nbin8 = nbin rounded up to 8, zero behind the row's end and behind the plane's, and
+//   b: the rows s0 + df0 .. s0 + df0 + sb + dfr - 2, each as positions x = bin + (nlagt - 1) of a line of nbin8 + 8 nrun
+//      words with zeros wherever the bin lies outside the row or the row outside the plane -- so the inner loop has no bounds.
+// Thread (dfi, run) owns df = df0 + dfi and the eight time lags dt = 8 run - (nlagt - 1) + i, i < 8, in eight int64
+// accumulators.  Walking j it keeps the eight b values at positions j + 8 run .. + 7 in registers: every step loads ONE new b
+// word and multiplies a[j] -- read 8 bins at a time as two 16-byte broadcasts, the same address in every lane -- into all eight:
+// 10 LDS reads per 64 multiply-adds, against 128 with one thread per lag.  The window rotates by renaming: the loop over eight
+// steps is unrolled and position x lives in register x mod 8.
+// Banks (ds_read_b32: 32 lanes a group, bank = word mod 32): the lanes of a group differ in `run`, i.e. by 8 words, which would
+// put four lanes on every bank; b is therefore stored skewed, position x at word x + x / 8, which makes the lane stride 9 words,
+// and the row stride bw is chosen = 9 nrunp (mod 32) so that the rows of the dfi of one group interleave as well: no conflict.
+// The partial of every (plane, slab, df, dt) goes to `part`; frbch_post_acf2d_join adds the slabs in ascending order.
+// grid (nslab, ceil(nlagf / dfr), n), max(64, dfr nrunp) threads, (sb nbin8 + (sb + dfr - 1) bw) 4 <= kAcfLds bytes of LDS.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int kAcfThreads = 256, kAcfRun = 8, kAcfMaxDfr = 8;
+constexpr size_t kAcfLds = 65536;                                          // 64 KiB: two workgroups per CU
+
+__global__ void __launch_bounds__(kAcfThreads) frbch_post_acf2d_fast(Acf2Params p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int nbin8 = (p.nbin + 7) & ~7, L = p.nlagt - 1, bwl = nbin8 + 8 * p.nrun, nbr = p.sb + p.dfr - 1;
+  int32_t* sa = reinterpret_cast<int32_t*>(smem);
+  int32_t* sb = sa + p.sb * nbin8;
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const int s0 = (int)blockIdx.x * p.sb, df0 = (int)blockIdx.y * p.dfr;
+  const int ns = min(p.sb, p.nsub - s0), ndt = 2 * p.nlagt - 1;
+  const int32_t* y = p.y + (size_t)blockIdx.z * p.nsub * p.nbin;
+  for (int i = tid; i < p.sb * nbin8; i += nthr) {
+    const int s = i / nbin8, j = i % nbin8;
+    sa[i] = (s < ns && j < p.nbin) ? y[(size_t)(s0 + s) * p.nbin + j] : 0;
+  }
+  for (int i = tid; i < nbr * bwl; i += nthr) {
+    const int q = i / bwl, x = i % bwl, s = s0 + df0 + q, j = x - L;
+    sb[q * p.bw + x + (x >> 3)] = (s < p.nsub && j >= 0 && j < p.nbin) ? y[(size_t)s * p.nbin + j] : 0;
+  }
+  __syncthreads();
+  const int run = tid % p.nrunp, dfi = tid / p.nrunp;
+  if (dfi >= p.dfr || run >= p.nrun || df0 + dfi >= p.nlagf) return;
+  long long acc[kAcfRun];
+#pragma unroll
+  for (int i = 0; i < kAcfRun; ++i) acc[i] = 0;
+  for (int s = 0; s < ns; ++s) {
+    const int32_t* a = sa + s * nbin8;
+    const int32_t* b = sb + (s + dfi) * p.bw + 9 * run;                    // position 8 run lives at word 9 run
+    int32_t w[kAcfRun];
+#pragma unroll
+    for (int i = 0; i < kAcfRun - 1; ++i) w[i] = b[i];
+    for (int m = 0; m < nbin8 / 8; ++m, b += 9, a += 8) {
+      const int4 a0 = *reinterpret_cast<const int4*>(a), a1 = *reinterpret_cast<const int4*>(a + 4);
+      const int32_t av[kAcfRun] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+#pragma unroll
+      for (int jj = 0; jj < kAcfRun; ++jj) {
+        w[(jj + 7) & 7] = b[jj == 0 ? 7 : 8 + jj];                         // position 8 (run + m) + 7 + jj (word 9 (run + m) + 8 is the skew's gap)
+#pragma unroll
+        for (int i = 0; i < kAcfRun; ++i) acc[i] += (long long)av[jj] * (long long)w[(jj + i) & 7];
+      }
+    }
+  }
+  long long* out = p.part + (((size_t)blockIdx.z * p.nslab + blockIdx.x) * p.nlagf + (size_t)(df0 + dfi)) * ndt;
+#pragma unroll
+  for (int i = 0; i < kAcfRun; ++i)
+    if (8 * run + i < ndt) out[8 * run + i] = acc[i];
+}
+
+// grid (ceil(n nlagf (2 nlagt - 1) / 256)): the partials of the slabs, added in ascending slab
+__global__ void __launch_bounds__(kAcfThreads) frbch_post_acf2d_join(Acf2Params p) {
+  const size_t per = (size_t)p.nlagf * (2 * p.nlagt - 1), idx = (size_t)blockIdx.x * kAcfThreads + threadIdx.x;
+  if (idx >= (size_t)p.n * per) return;
+  const size_t plane = idx / per, l = idx % per;
+  long long a = 0;
+  for (int t = 0; t < p.nslab; ++t) a += p.part[(plane * p.nslab + t) * per + l];
+  p.A[idx] = a;
+}
 }  // namespace fast

@@ -34,6 +34,9 @@ reference's `dspsr -E <par> ... <IFall.fil>` stage) of SIGPROC filterbank files,
 * ``dmfit_fil`` (``post dmfit``) measures the DM those stages take as given: the burst's noise-weighted profile at a fine grid of
   trial DMs, the S/N- and the structure-maximising DM by a parabola over each curve's peak (``dm_scan``: frbch_dmscan_host);
   ``post rmsynth`` and ``post polprof`` take the result with ``--dm-from``.
+* ``burstacf_fil`` (``post burstacf``) keeps frequency and time together: the dedispersed, noise-weighted dynamic spectrum of a
+  burst, its two-dimensional autocorrelation in exact integers, and from it the scintillation bandwidth, the sub-burst duration
+  and the drift of sub-bursts in frequency (``burst_acf``: frbch_burstacf_host).
 There is no CPU fallback: the sums run in libfrbch.so on a gfx950 device.
 """
 from __future__ import annotations
@@ -2329,6 +2332,149 @@ def bursts_from_dm(path, kind="snr") -> np.ndarray:
     return cands
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# Structure of a burst: dynamic spectrum and its two-dimensional ACF (frbch_burstacf_*, frbch_acf2d_*)
+# ------------------------------------------------------------------------------------------------------------------
+ACF_RESULT = np.dtype([("width_f_mhz", "<f8"), ("width_t_ms", "<f8"), ("dt_df", "<f8"), ("drift", "<f8"), ("ref", "<f8"), ("mff", "<f8"),
+                       ("mtf", "<f8"), ("mtt", "<f8"), ("k", "<i4"), ("r", "<u4"), ("nused", "<u4"), ("ncomplete", "<u4"),
+                       ("fitted_f", "<u4"), ("fitted_t", "<u4"), ("fitted_d", "<u4"), ("reserved", "<u4")])
+ACF_ROW = "%-8s DM %9.3f sample %10d  bandwidth %9.4f MHz%s  duration %9.4f ms%s  drift %10.3f MHz/ms (%+.5f ms/MHz%s)"
+
+
+def acf_params(nbin: int, tfactor: int, ffactor: int, nlagf: int, nlagt: int) -> _lib.FrbchAcfParams:
+    return _lib.FrbchAcfParams(C.sizeof(_lib.FrbchAcfParams), int(nbin), int(tfactor), int(ffactor), int(nlagf), int(nlagt))
+
+
+def acf_fit_params(fit_frac: float = 0.5) -> _lib.FrbchAcfFitParams:
+    return _lib.FrbchAcfFitParams(C.sizeof(_lib.FrbchAcfFitParams), 0, float(fit_frac))
+
+
+def acf2d(y, nlagf: int, nlagt: int, form: int = _lib.ACF_PLAN, device: int = 0, lib=None, info: dict | None = None) -> np.ndarray:
+    """The two-dimensional autocorrelation of int32 planes ``y [n][nsub][nbin]`` with |y| <= 2^21 (frbch_acf2d_host) -> int64
+    ``[n][nlagf][2 nlagt - 1]``: A[df][dt + nlagt - 1] = the sum of y[s][j] y[s + df][j + dt].  ``info['kernel_used']``: 1 = the
+    fast kernel, 0 = the generic one; ``form=_lib.ACF_GENERIC`` asks for the generic one."""
+    lib = lib or _lib.load()
+    y = np.ascontiguousarray(y, dtype=np.int32)
+    if y.ndim != 3:
+        raise InputError("y must have the shape [n][nsub][nbin]")
+    n, nsub, nbin = y.shape
+    lf, lt = max(1, min(int(nlagf), 1024)), max(1, min(int(nlagt), 256))
+    if n * lf * (2 * lt - 1) > 1 << 24:
+        raise InputError("ncand * nlagf * (2 nlagt - 1) exceeds 2^24: cut the batch or the lags")
+    A = np.zeros((n, lf, 2 * lt - 1), np.int64)
+    k = C.c_uint32(0)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_acf2d_host(y.ctypes.data, n, nsub, nbin, int(nlagf), int(nlagt), int(form), device, A.ctypes.data, C.byref(k), err, len(err)), err)
+    if info is not None:
+        info.update(kernel_used=k.value)
+    return A
+
+
+def burst_acf(fil_or_rows, hdr: dict, cands, nbin: int = 256, tfactor: int = 1, ffactor: int = 1, nlagf: int | None = None,
+              nlagt: int | None = None, fit_frac: float = 0.5, flag=None, products: str = "stokes", device: int = 0, lib=None,
+              info: dict | None = None):
+    """The structure of every burst (frbch_burstacf_host; include/frbch.h states the arithmetic): the dedispersed, baseline-free,
+    noise-weighted dynamic spectrum in ``nchans / ffactor`` subbands and ``nbin`` bins of ``tfactor`` rows about ``sample``, its
+    two-dimensional autocorrelation at ``nlagf`` frequency lags and ``-(nlagt - 1) .. nlagt - 1`` time lags (defaults: half the
+    plane, at most 1024 and 256), and from it the half-widths of the two cuts and the drift -> dict(Y int64 [n][nsub][nbin], yhits,
+    A int64 [n][nlagf][2 nlagt - 1], P uint32 (complete pairs per lag), norm float64 (A scaled back and divided by P), results
+    ACF_RESULT [n], used [n][nchans]).  ``info``: ``spectra_kernel_used``, ``dynspec_kernel_used``, ``kernel_used`` (the ACF's): 1 =
+    the fast kernel, 0 = the generic one."""
+    lib = lib or _lib.load()
+    rows, nrows, cands, par, _g = _burst_args(fil_or_rows, hdr, cands, None, products)
+    n, nchan = cands.size, hdr["nchans"]
+    fl = None if flag is None else np.ascontiguousarray(flag, dtype=np.uint8)
+    if fl is not None and fl.shape != (nchan,):
+        raise InputError("flag must have the shape [nchans]")
+    ffactor = int(ffactor)
+    if ffactor < 1 or ffactor > nchan or nchan % ffactor:
+        raise InputError("ffactor must be 1..nchans and divide nchans")
+    nsub, nb = nchan // ffactor, max(1, min(int(nbin), 1024))
+    nlagf = max(1, min(nsub // 2, 1024)) if nlagf is None else int(nlagf)
+    nlagt = max(1, min(nb // 2, 256)) if nlagt is None else int(nlagt)
+    lf, lt = max(1, min(nlagf, 1024)), max(1, min(nlagt, 256))
+    if nsub * nb > 1 << 20 or n * nsub * nb > 1 << 24 or n * lf * (2 * lt - 1) > 1 << 24:
+        raise InputError("nsub * nbin exceeds 2^20, or ncand * nsub * nbin or ncand * nlagf * (2 nlagt - 1) exceeds 2^24: cut the batch, the window or the lags")
+    apar, fpar = acf_params(nbin, tfactor, ffactor, nlagf, nlagt), acf_fit_params(fit_frac)
+    Y, yhits = np.zeros((n, nsub, nb), np.int64), np.zeros((n, nsub, nb), np.uint32)
+    A, P = np.zeros((n, lf, 2 * lt - 1), np.int64), np.zeros((n, lf, 2 * lt - 1), np.uint32)
+    res = np.zeros(n, dtype=ACF_RESULT)
+    used = np.zeros((n, nchan), np.uint8)
+    k = (C.c_uint32 * 3)(0, 0, 0)
+    err = C.create_string_buffer(512)
+    desc = fil_desc(hdr, hdr.get("product", 0))
+    _check(lib.frbch_burstacf_host(C.byref(desc), rows.ctypes.data, nrows, C.byref(par), cands.ctypes.data, n,
+                                   fl.ctypes.data if fl is not None else None, C.byref(apar), C.byref(fpar), device, Y.ctypes.data,
+                                   yhits.ctypes.data, A.ctypes.data, P.ctypes.data, res.ctypes.data, used.ctypes.data, k, err, len(err)), err)
+    if info is not None:
+        info.update(spectra_kernel_used=k[0], dynspec_kernel_used=k[1], kernel_used=k[2])
+    norm = np.zeros(A.shape)
+    ks, rs, nu, nc = (np.ascontiguousarray(res[f]) for f in ("k", "r", "nused", "ncomplete"))
+    _check(lib.frbch_burstacf_fit(C.byref(desc), C.byref(apar), C.byref(fpar), n, ks.ctypes.data, rs.ctypes.data, nu.ctypes.data,
+                                  nc.ctypes.data, A.ctypes.data, P.ctypes.data, norm.ctypes.data, None, err, len(err)), err)
+    return dict(Y=Y, yhits=yhits, A=A, P=P, norm=norm, results=res, used=used)
+
+
+def _resample(img, height, width):
+    r = np.clip((np.arange(height) * img.shape[0]) // height, 0, img.shape[0] - 1)
+    c = np.clip((np.arange(width) * img.shape[1]) // width, 0, img.shape[1] - 1)
+    return img[r][:, c]
+
+
+def _unit(img):
+    return (img - img.min()) / max(1e-30, float(img.max() - img.min()))
+
+
+def _acf_panels(acf, i):
+    """above: the dynamic spectrum, subbands top to bottom against the bins; then the ACF (both half-planes, df top to bottom,
+    the lag (0, 0) taken out) with its ridge line dt = dt_df df; below: the frequency cut and the time cut"""
+    width, height = 512, 96
+    res = acf["results"][i]
+    dyn = acf["Y"][i].astype(np.float64) / np.maximum(acf["yhits"][i], 1)
+    nm = acf["norm"][i].copy()
+    nlf, ndt = nm.shape
+    L = ndt // 2
+    nm[0, L] = 0.0
+    full = np.concatenate([nm[:0:-1, ::-1], nm], axis=0)               # df = -(nlagf - 1) .. nlagf - 1
+    img = _unit(_resample(full, 2 * height, width))
+    if res["fitted_d"] and res["mff"] > 0:
+        slope = res["mtf"] / res["mff"]                                  # bins per subband
+        for row in range(2 * height):
+            df = (row * full.shape[0]) // (2 * height) - (nlf - 1)
+            col = int(round((slope * df + L) * width / ndt))
+            if 0 <= col < width:
+                img[row, col] = 1.0
+    panels = [_unit(_resample(dyn, 2 * height, width)), np.zeros((4, width)), img, np.zeros((4, width)),
+              _curve_panel([nm[1:, L]] if nlf > 1 else [np.zeros(1)], width, height), np.zeros((4, width)),
+              _curve_panel([nm[0, L + 1:]] if L > 0 else [np.zeros(1)], width, height)]
+    return np.concatenate(panels + [np.zeros((8, width))], axis=0)
+
+
+def burstacf_fil(filterbankfile, bursts, nbin=256, tfactor=1, ffactor=1, nlagf=None, nlagt=None, fit_frac=0.5, off_gap=None,
+                 off_len=None, flag_file=None, products="stokes", device=0, lib=None, info: dict | None = None):
+    """The structure of the bursts of a filterbank: ``bursts`` = (dm, sample, width) tuples or BURST_CAND records.  Writes
+    ``<base>_acf.npz`` (Y, yhits, A, P, norm, results, used, bursts, nbin, tfactor, ffactor, fit_frac), ``<base>_acf.txt`` (one line
+    per burst: the half-widths at half maximum of the frequency and the time cut of the ACF, and the drift) and ``<base>_acf.png``
+    (per burst, one below the other: the dynamic spectrum, the ACF with its ridge line, the two cuts).  Returns (files, what
+    ``burst_acf`` returns)."""
+    lib = lib or _lib.load()
+    fil = sigproc.read_fil(filterbankfile)
+    hdr = fil.header
+    cands = burst_cands(bursts, off_gap, off_len)
+    flag = read_flag_file(flag_file, hdr["nchans"]).astype(np.uint8) if flag_file else None
+    acf = burst_acf(fil, hdr, cands, nbin, tfactor, ffactor, nlagf, nlagt, fit_frac=fit_frac, flag=flag, products=products, device=device,
+                    lib=lib, info=info)
+    base = filterbankfile.replace(".fil", "")
+    files = [base + "_acf.npz", base + "_acf.txt", base + "_acf.png"]
+    np.savez(files[0], bursts=cands, nbin=np.int64(nbin), tfactor=np.int64(tfactor), ffactor=np.int64(ffactor), fit_frac=np.float64(fit_frac), **acf)
+    with open(files[1], "w") as f:
+        for i, (c, r) in enumerate(zip(cands, acf["results"])):
+            f.write(ACF_ROW % ("burst%d" % i, c["dm"], int(c["sample"]), r["width_f_mhz"], "" if r["fitted_f"] else " (not fitted)", r["width_t_ms"],
+                               "" if r["fitted_t"] else " (not fitted)", r["drift"], r["dt_df"], "" if r["fitted_d"] else ", not fitted") + "\n")
+    write_png(files[2], np.concatenate([_acf_panels(acf, i) for i in range(cands.size)], axis=0))
+    return files, acf
+
+
 def main(argv=None):
     """``python -m frb_baseband_amd.post fold <fil> <par> [--polyco FILE] [--doppler X] [--products coherency|stokes] [...]`` / ``... prepdata <fil> --dm <dm> [...]`` /
     ``... search <fil> --dm <dm> [--dm2 --dmstep --threshold --max-width --detrend ...]`` /
@@ -2339,6 +2485,7 @@ def main(argv=None):
     [--gains FILE.npy] [--products stokes|coherency] [--profile --nbin N --tfactor F]`` (burst options repeatable; or ``--dm .. --dm2 .. --dmstep ..`` to search for them) /
     ``... dmfit <fil> --dm D (--sample S | --time T) --width W [--dm-half H --ddm X --nbin N --tfactor F --smooth S --fit-frac R --flag FILE --coherency]``
     (or ``--dm .. --dm2 .. --dmstep ..`` to search for the bursts; ``rmsynth`` and ``polprof`` take ``--dm-from BASE_dm.npz [--dm-kind snr|struct]`` in place of ``--dm``) /
+    ``... burstacf <fil> (--dm D (--sample S | --time T) --width W | --dm-from BASE_dm.npz [--dm-kind snr|struct]) [--nbin N --tfactor F --ffactor F --lagf N --lagt N --fit-frac R --flag FILE --coherency]`` /
     ``... polprof <fil> (--dm D (--sample S | --time T) --width W --rm R | --rm-from BASE_rm.npz) [--nbin N --tfactor F --ref mean|zero --flag FILE --gains FILE.npy --coherency]``
     (``search`` and ``candidates`` take ``--flag FILE`` and ``--rfi``; ``search``, ``candidates`` and ``rfifind`` take ``--resident``:
     one upload of the rows per command; ``rfifind --periodic [--t-freq S]`` and ``--rfi --periodic`` add the periodicity test): the stages
@@ -2503,8 +2650,43 @@ def main(argv=None):
     d.add_argument("--flag", default=None, help="flag file: channels left out")
     d.add_argument("--coherency", action="store_true", help="the file holds the -d4 products: PP + QQ is scanned")
     d.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
+    c = sub.add_parser("burstacf", help="structure of the bursts of a filterbank: dedispersed dynamic spectrum, its 2-D autocorrelation, bandwidth, duration and drift")
+    c.add_argument("fil")
+    c.add_argument("--dm", type=float, action="append", default=None, help="DM of a burst (repeatable, one per burst)")
+    c.add_argument("--dm-from", default=None, help="<base>_dm.npz of `dmfit`: its bursts at their measured DMs instead of --dm .. --width")
+    c.add_argument("--dm-kind", choices=("snr", "struct"), default="struct", help="which DM of --dm-from: the S/N- or the structure-maximising one")
+    c.add_argument("--sample", type=int, action="append", default=None, help="centre of a burst, row at the top of the band (repeatable)")
+    c.add_argument("--time", type=float, action="append", default=None, help="the same in seconds from the start of the file (repeatable)")
+    c.add_argument("--width", type=int, action="append", default=None, help="on-pulse rows (repeatable; one value serves every burst)")
+    c.add_argument("--nbin", type=int, default=256, help="time bins (1..1024)")
+    c.add_argument("--tfactor", type=int, default=1, help="rows per bin (1..512)")
+    c.add_argument("--ffactor", type=int, default=1, help="channels per subband (divides nchans)")
+    c.add_argument("--lagf", type=int, default=None, help="frequency lags 0 .. lagf - 1, in subbands (default: half the subbands, at most 1024)")
+    c.add_argument("--lagt", type=int, default=None, help="time lags -(lagt - 1) .. lagt - 1, in bins (default: half the bins, at most 256)")
+    c.add_argument("--fit-frac", type=float, default=0.5, help="the drift is fitted to the lags above this fraction of the largest one")
+    c.add_argument("--off-gap", type=int, default=None, help="rows between the burst and each off-pulse window (default: 2 widths, at least 16)")
+    c.add_argument("--off-len", type=int, default=None, help="rows of each off-pulse window (default 1024)")
+    c.add_argument("--flag", default=None, help="flag file: channels left out")
+    c.add_argument("--coherency", action="store_true", help="the file holds the -d4 products: PP + QQ is used")
+    c.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     a = ap.parse_args(argv)
-    if a.cmd == "dmfit":
+    if a.cmd == "burstacf":
+        if a.dm_from:
+            bursts = list(bursts_from_dm(a.dm_from, a.dm_kind))
+        else:
+            tsamp = sigproc.read_fil(a.fil).header["tsamp"]
+            centres = list(a.sample or []) + [int(round(t / tsamp)) for t in (a.time or [])]
+            widths, dms = a.width or [], a.dm or []
+            if not centres or len(centres) != len(dms) or len(widths) not in (1, len(centres)):
+                raise InputError("burstacf: one --sample or --time per --dm, and --width once or once per burst (or --dm-from)")
+            bursts = [(dm, s, widths[i if len(widths) > 1 else 0]) for i, (dm, s) in enumerate(zip(dms, centres))]
+        files, _acf = burstacf_fil(a.fil, bursts, nbin=a.nbin, tfactor=a.tfactor, ffactor=a.ffactor, nlagf=a.lagf, nlagt=a.lagt,
+                                   fit_frac=a.fit_frac, off_gap=a.off_gap, off_len=a.off_len, flag_file=a.flag,
+                                   products="coherency" if a.coherency else "stokes", device=a.device)
+        for path in files:
+            print("wrote", path)
+        print(open(files[1]).read(), end="")
+    elif a.cmd == "dmfit":
         bursts = None
         if a.dm2 <= 0.0:
             tsamp = sigproc.read_fil(a.fil).header["tsamp"]

@@ -995,6 +995,114 @@ int frbch_dmscan_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrow
                       const frbch_dmscan_peak_params* pk, int device, int64_t* acc, uint32_t* hits, double* snr, double* strc,
                       frbch_dmscan_result* results, uint8_t* used, uint32_t* kernel_used, char* err, size_t err_cap);
 
+/* ---- structure of a burst: dedispersed dynamic spectrum and its two-dimensional autocorrelation ------------------
+ * The stages above sum over the band before they look at a burst.  This one keeps frequency and time: the dedispersed,
+ * baseline-free, noise-weighted dynamic spectrum Y of a burst, its two-dimensional autocorrelation (ACF) A, and from A the
+ * scintillation bandwidth, the sub-burst duration and the drift of sub-bursts in frequency.  frbch_burst_cand,
+ * frbch_burst_params, n_c(.), the windows, frbch_burst_sums and "a row outside 0 .. nrows - 1 is absent" are those of the burst
+ * sections above; tests/acf_oracle.py restates what follows in numpy.  Rows must be 8 or 16 bit, for the DM scan's reason.
+ *
+ * Grid.  ffactor divides nchan, nsub = nchan / ffactor; subband s holds the channels s ffactor .. (s + 1) ffactor - 1.  The
+ *    window is the DM scan's: t0_i = sample - (nbin / 2) tfactor; bin j holds the rows t0_i + j tfactor + u, u < tfactor, at
+ *    the top of the band; channel c is read n_c(cand.dm) rows later.
+ * Host preparation.  Exactly the DM scan's at cand.dm (one function serves both): the burst sums, the products read, mean_c,
+ *    var_c, used, flag, w_c = 1 / sqrt(var_c), M_i = (double)tfactor 2^nbits wmax_i (doubled in coherency order; NOT
+ *    multiplied by ffactor), k_i = 40 - e.  N_i = 0: every output of the candidate is 0.
+ * 1. Dynamic spectrum (device).  Y[i][s][j] (int64) = the sum over the used channels c of subband s with h > 0 present rows in
+ *    bin j of X = (int64)rint(((double)S - (double)h mean_c) w_c 2^k_i) -- the DM scan's term, the same function in every
+ *    kernel --, yhits[i][s][j] (uint32) = the sum of h.  |X| <= 2^40, so |Y| <= 2^40 ffactor <= 2^54: exact in any order.
+ *    Consequence: the sum over s of Y[i][s][j] and of yhits[i][s][j] equals acc[i][0][j] and hits[i][0][j] of frbch_dmscan_*
+ *    called with ntrial = 1 on the same arguments, bit for bit.
+ *    Complete cells.  nused_s = the used channels of subband s.  A cell is complete when nused_s > 0 and yhits = tfactor
+ *    nused_s: every used channel of the subband has all its rows.  mask[i][s][j] = 1 for complete cells, else 0.
+ * 2. Quantisation (device).  m_i = the largest |Y| over the complete cells (an integer maximum: order-free); b = the bit
+ *    length of m_i (0 for m_i = 0); r_i = max(0, b - 21).  Complete cells: y[i][s][j] (int32) = (Y + 2^(r-1)) >> r (arithmetic
+ *    shift) for r > 0 and Y for r = 0; incomplete cells: y = 0.  m_i < 2^b gives |y| <= 2^21 (the rounding can reach 2^21
+ *    itself), so a product of two cells is <= 2^42 and a sum over nsub nbin <= 2^20 cells is <= 2^62 < 2^63: int64 sums of
+ *    products of y cannot overflow, in any order.  The resolution is 2^-21 of the brightest cell of the burst itself.
+ * 3. ACF (device).  For 0 <= df < nlagf and -(nlagt - 1) <= dt <= nlagt - 1:
+ *      A[i][df][dt + nlagt - 1] (int64) = the sum over s, j of y[i][s][j] y[i][s + df][j + dt],
+ *    over 0 <= s, s + df < nsub, 0 <= j, 0 <= j + dt < nbin.  The other half-plane is A[-df][-dt] = A[df][dt] and is not
+ *    stored.  Incomplete cells are zero and drop out.  P[i][df][.] (uint32), the number of complete pairs at a lag, is the
+ *    same sum over mask: the same kernel on the 0 / 1 plane.  When every cell of every candidate of the call is complete the
+ *    library writes the closed form (nsub - df)(nbin - |dt|) instead; the two are equal.
+ *    Direct sums, not an FFT: the sums are exact integers, and the lag window is a small part of the plane.
+ *    frbch_acf2d_* are this stage alone on int32 planes y [n][nsub][nbin] with the contract |y| <= 2^21 (n nsub nbin <= 2^24,
+ *    nsub nbin <= 2^20, nbin 1..1024, nlagf 1..min(nsub, 1024), nlagt 1..min(nbin, 256), n nlagf (2 nlagt - 1) <= 2^24);
+ *    frbch_acf2d_host checks the contract on the host and refuses a plane that breaks it; frbch_acf2d_device cannot look.
+ * 4. Derivation (frbch_burstacf_fit, host only; double, every operation rounded on its own, no FMA; this library's own rule,
+ *    no error bars are claimed).  q = 2^(-2 (k_i - r_i));  norm[df][dt] = ((double)A q) / (double)P, 0 where P = 0.  The lag
+ *    (0, 0) carries the noise variance and is left out of everything below.
+ *    Frequency width.  F[df] = norm[df][0].  With nlagf >= 2 and F[1] > 0: the first df >= 2 with F[df] < h, h = F[1] / 2;
+ *      x = (double)(df - 1) + (F[df - 1] - h) / (F[df - 1] - F[df]), the half-width at half maximum in subbands;
+ *      width_f_mhz = x ((double)ffactor |foff|), fitted_f = 1.  No such df below nlagf: x = (double)(nlagf - 1), the last lag
+ *      looked at as it is, fitted_f = 0.  nlagf < 2 or F[1] not > 0: x = 0, fitted_f = 0.
+ *    Time width.  The same on T[dt] = norm[0][dt], dt >= 1, with nlagt: width_t_ms = x (((double)tfactor tsamp) 1000).
+ *    Drift.  ref = the largest norm over the stored lags other than (0, 0).  w = norm where ref > 0 and norm >= fit_frac ref,
+ *      else 0.  Second moments over the mirrored plane, each half counted once and doubled: over H = {df = 0, dt > 0} and
+ *      {df > 0, every dt}, df then dt ascending, Mff = 2 sum w (double)(df df), Mtf = 2 sum w (double)(df dt), Mtt = 2 sum w
+ *      (double)(dt dt) (the integer products exact in int64, each term rounded before it is added).  Mff > 0:  q = Mtf / Mff
+ *      (bins per subband: the regression of time on frequency, the ridge line of a drifting burst);  dt_df = (q (((double)
+ *      tfactor tsamp) 1000)) / ((double)ffactor foff), ms per MHz with the sign of foff;  drift = 1 / dt_df (MHz / ms) where
+ *      dt_df != 0, else 0;  fitted_d = 1.  Mff not > 0: dt_df = drift = 0, fitted_d = 0.
+ *    frbch_acf_result also holds k = k_i, r = r_i, nused = N_i, ncomplete = the number of complete cells, ref, and the moments.
+ *
+ * kernel_used[3] (may be NULL): the burst-sums kernel, the dynamic-spectrum kernel, the ACF kernel; 1 = fast, 0 = generic.
+ *    Dynamic spectrum, fast: the conditions of the fast burst-sums kernel, tfactor <= 256, ffactor a power of two <= the 64
+ *    (8 bit) / 32 (16 bit) channels of a 64-byte tile (a shuffle reduction over ffactor lanes) or a multiple of them (the whole
+ *    tile by shuffles, a join over the ffactor / 64 tiles of a subband), every (candidate, tile) leaving room for one bin in
+ *    the stage (tfactor + delay range <= 1024 rows, 512 in coherency order), and join partials of at most 2^30 bytes (ncand x
+ *    tiles x nbin x 12); everything else: generic, one thread per (candidate, subband, bin).
+ *    ACF, fast: a workgroup owns a plane, a run of up to 8 df and a slab of subbands, stages the slab's rows and the rows df
+ *    further on into 64 KiB of the LDS, every thread owns 8 consecutive dt and walks j with a sliding register window, a join
+ *    adds the slabs.  The staging rule places every shape these entry points accept (the smallest slab is 4 rows, at 1024 bins
+ *    and 256 lags); the fast kernel is not taken where the partials of the slabs would exceed 2^30 bytes (n x slabs x nlagf x
+ *    (2 nlagt - 1) x 8): generic, one thread per (plane, df, dt).  frbch_acf2d_* take `form`: FRBCH_ACF_PLAN = the plan rule
+ *    decides, FRBCH_ACF_GENERIC = the generic kernel whatever the rule says (for comparing the two).  Both give the same bits.
+ * FRBCH_E_ARG (outputs untouched): a wrong `size`, nbin outside 1..1024, tfactor outside 1..512, ffactor outside 1..nchan or
+ * not dividing nchan, nsub nbin > 2^20, ncand nsub nbin > 2^24, nlagf outside 1..min(nsub, 1024), nlagt outside 1..min(nbin,
+ * 256), ncand nlagf (2 nlagt - 1) > 2^24, fit_frac outside (0, 1), float rows, coherency order without nifs = 4, nchan > 16384,
+ * and every refusal of the burst sums. */
+#define FRBCH_ACF_PLAN 0u
+#define FRBCH_ACF_GENERIC 1u
+typedef struct frbch_acf_params { uint32_t size, nbin, tfactor, ffactor, nlagf, nlagt, reserved[2]; } frbch_acf_params;   /* size = sizeof(frbch_acf_params) */
+typedef struct frbch_acf_fit_params { uint32_t size, reserved; double fit_frac; } frbch_acf_fit_params;                   /* size = sizeof(frbch_acf_fit_params) */
+typedef struct frbch_acf_result {
+  double width_f_mhz, width_t_ms;      /* half-widths at half maximum of the two cuts */
+  double dt_df, drift;                 /* ms per MHz, MHz per ms */
+  double ref, mff, mtf, mtt;
+  int32_t k;
+  uint32_t r, nused, ncomplete, fitted_f, fitted_t, fitted_d, reserved;
+} frbch_acf_result;
+/* The plan rule of the ACF stage (host only, nothing runs): 1 = fast, 0 = generic, < 0 = refused. */
+int frbch_acf2d_kernel(uint32_t n, uint32_t nsub, uint32_t nbin, uint32_t nlagf, uint32_t nlagt, uint32_t form);
+/* d_y [n][nsub][nbin] int32 and d_A [n][nlagf][2 nlagt - 1] int64 are device memory; d_y is never written.  Synchronised. */
+int frbch_acf2d_device(const int32_t* d_y, uint32_t n, uint32_t nsub, uint32_t nbin, uint32_t nlagf, uint32_t nlagt, uint32_t form,
+                       int device, int64_t* d_A, uint32_t* kernel_used, char* err, size_t err_cap);
+/* the same with host arrays; refuses a plane with a |y| above 2^21 */
+int frbch_acf2d_host(const int32_t* y, uint32_t n, uint32_t nsub, uint32_t nbin, uint32_t nlagf, uint32_t nlagt, uint32_t form,
+                     int device, int64_t* A, uint32_t* kernel_used, char* err, size_t err_cap);
+/* Host only: norm [ncand][nlagf][2 nlagt - 1] (double) and results [ncand] from A (int64) and P (uint32) of that shape and
+ * k, r, nused, ncomplete [ncand]; norm and results may be NULL.  Only nchan, foff_mhz and tsamp_s of `fil` are looked at. */
+int frbch_burstacf_fit(const frbch_fil_desc* fil, const frbch_acf_params* par, const frbch_acf_fit_params* fp, uint32_t ncand,
+                       const int32_t* k, const uint32_t* r, const uint32_t* nused, const uint32_t* ncomplete, const int64_t* A,
+                       const uint32_t* P, double* norm, frbch_acf_result* results, char* err, size_t err_cap);
+/* The plan rules (host only, nothing runs): 0 and kernel_used[3] filled, or < 0 = refused; only the ADDRESS of d_rows is examined. */
+int frbch_burstacf_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                          const frbch_burst_cand* cands, uint32_t ncand, const frbch_acf_params* par, uint32_t* kernel_used);
+/* d_rows is device memory, never written; everything else is host memory: flag [nchan] (may be NULL) and the outputs Y (int64),
+ * yhits (uint32) [ncand][nsub][nbin], A (int64), P (uint32) [ncand][nlagf][2 nlagt - 1], results [ncand], used [ncand][nchan],
+ * kernel_used[3] (each may be NULL).  One device scope. */
+int frbch_burstacf_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                          const frbch_burst_cand* cands, uint32_t ncand, const uint8_t* flag, const frbch_acf_params* par,
+                          const frbch_acf_fit_params* fp, int device, int64_t* Y, uint32_t* yhits, int64_t* A, uint32_t* P,
+                          frbch_acf_result* results, uint8_t* used, uint32_t* kernel_used, char* err, size_t err_cap);
+/* the same with host rows: one upload */
+int frbch_burstacf_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* bpar,
+                        const frbch_burst_cand* cands, uint32_t ncand, const uint8_t* flag, const frbch_acf_params* par,
+                        const frbch_acf_fit_params* fp, int device, int64_t* Y, uint32_t* yhits, int64_t* A, uint32_t* P,
+                        frbch_acf_result* results, uint8_t* used, uint32_t* kernel_used, char* err, size_t err_cap);
+
 /* ---- interference: block statistics, the mask, cleaned rows --------------------------------------
  * The reference carries a flag file through to Heimdall and FETCH (create_config.py:54-56 `-F/--flag`, frb.conf:50,
  * base2fil.sh:226,425-432, submit_job.py:117 `<Tel>.flag_<fmin>-<fmax>MHz_<nchan>chan`) and leaves making one to a person.
