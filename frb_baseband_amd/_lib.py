@@ -201,6 +201,28 @@ class FrbchAcfResult(C.Structure):
 ACF_PLAN, ACF_GENERIC = 0, 1
 
 
+class FrbchScatBankParams(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("nsig", C.c_uint32), ("ntau", C.c_uint32), ("ntap", C.c_uint32), ("lead", C.c_uint32),
+                ("reserved", C.c_uint32 * 3), ("sigma0", C.c_double), ("rsig", C.c_double), ("tau0", C.c_double), ("rtau", C.c_double)]
+
+
+class FrbchTbankShape(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("nsub", C.c_uint32), ("nbin", C.c_uint32), ("ntemp", C.c_uint32), ("ntap", C.c_uint32),
+                ("lead", C.c_uint32), ("shift0", C.c_uint32), ("nshift", C.c_uint32)]
+
+
+class FrbchScatParams(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("nbin", C.c_uint32), ("tfactor", C.c_uint32), ("ffactor", C.c_uint32), ("shift0", C.c_uint32),
+                ("nshift", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class FrbchScatFitParams(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("nalpha", C.c_uint32), ("snr_min", C.c_double), ("alpha", C.c_double * 32)]
+
+
+TBANK_PLAN, TBANK_GENERIC = 0, 1
+
+
 class FrbchRfiParams(C.Structure):
     _fields_ = [("size", C.c_uint32), ("block_rows", C.c_uint32), ("t_cell", C.c_double), ("t_chan", C.c_double),
                 ("chan_frac", C.c_double), ("block_frac", C.c_double)]
@@ -384,6 +406,22 @@ SYMBOLS = {
     "frbch_burstacf_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32, _P,
                                       C.POINTER(FrbchAcfParams), C.POINTER(FrbchAcfFitParams), C.c_int, _P, _P, _P, _P, _P, _P, _P,
                                       C.c_char_p, C.c_size_t]),
+    "frbch_scat_bank": (C.c_int, [C.POINTER(FrbchScatBankParams), _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "frbch_tbank_kernel": (C.c_int, [C.c_uint32, C.POINTER(FrbchTbankShape), C.c_uint32]),
+    "frbch_tbank_device": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(FrbchTbankShape), C.c_uint32, C.c_int, _P, C.POINTER(C.c_uint32),
+                                     C.c_char_p, C.c_size_t]),
+    "frbch_tbank_host": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(FrbchTbankShape), C.c_uint32, C.c_int, _P, C.POINTER(C.c_uint32),
+                                   C.c_char_p, C.c_size_t]),
+    "frbch_burstscat_fit": (C.c_int, [C.POINTER(FrbchFilDesc), C.POINTER(FrbchScatParams), C.POINTER(FrbchScatBankParams),
+                                      C.POINTER(FrbchScatFitParams), C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "frbch_burstscat_kernel": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32,
+                                         C.POINTER(FrbchScatParams), C.POINTER(FrbchScatBankParams), _P]),
+    "frbch_burstscat_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32, _P,
+                                         C.POINTER(FrbchScatParams), C.POINTER(FrbchScatBankParams), C.POINTER(FrbchScatFitParams), C.c_int,
+                                         _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "frbch_burstscat_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32, _P,
+                                       C.POINTER(FrbchScatParams), C.POINTER(FrbchScatBankParams), C.POINTER(FrbchScatFitParams), C.c_int,
+                                       _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
     "frbch_rfi_nblk": (C.c_long, [C.c_uint64, C.c_uint32]),
     "frbch_rfi_stats_kernel": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams)]),
     "frbch_rfi_stats_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchRfiParams), C.c_int, _P,

@@ -4905,20 +4905,31 @@ struct AcfOut {
   uint32_t k[3] = {0, 0, 0};
 };
 
-// everything of a call inside its scope: the preparation, the dynamic spectrum, the quantised plane, the ACFs, the fit
-int acf_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
-            const frbch_burst_cand* cands, uint32_t ncand, const uint8_t* flag, const frbch_acf_params* par,
-            const frbch_acf_fit_params* fp, PostScope& ps, AcfOut* out, const PostErr& e) {
+// Steps 1 and 2 of the header inside a scope, launched and not synchronised: the preparation (synchronised), the dynamic
+// spectrum, the row maxima, the shift, the quantised plane and the 0 / 1 plane of the complete cells.  Only nbin, tfactor and
+// ffactor of `par` are looked at.  The burst ACF and the scattering fit share it.
+struct DynOut {
+  DmPrep prep;
+  std::vector<uint8_t> used;            // [ncand][nchan]
+  std::vector<uint32_t> nused_s;        // [ncand][nsub]
+  long long* d_Y = nullptr;             // [ncand][nsub][nbin], the scope's
+  uint32_t* d_hits = nullptr;
+  int32_t *d_shift = nullptr, *d_y = nullptr, *d_mask = nullptr;
+};
+int dyn_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+            const frbch_burst_cand* cands, uint32_t ncand, const uint8_t* flag, const frbch_acf_params* par, PostScope& ps,
+            DynOut* out, uint32_t* kernel_used, const PostErr& e) {
   const size_t nchan = fil->nchan, n = (size_t)ncand * nchan, nbin = par->nbin, nsub = nchan / par->ffactor;
-  const size_t ncell = (size_t)ncand * nsub * nbin, ndt = 2 * (size_t)par->nlagt - 1, nlag = (size_t)ncand * par->nlagf * ndt;
+  const size_t ncell = (size_t)ncand * nsub * nbin;
   std::vector<int32_t> delays;
   int rc = acf_delays(fil, cands, ncand, par, &delays, e);
   if (rc) return rc;
   const DynPlan rule = dyn_plan_rule(fil, d_rows, bpar->products, delays, ncand, par);
-  DmPrep prep;
-  if ((rc = dm_prepare(fil, d_rows, nrows, bpar, cands, ncand, flag, par->nbin, par->tfactor, ps, &prep, &out->k[0], e)) != 0) return rc;
+  DmPrep& prep = out->prep;
+  if ((rc = dm_prepare(fil, d_rows, nrows, bpar, cands, ncand, flag, par->nbin, par->tfactor, ps, &prep, &kernel_used[0], e)) != 0) return rc;
   out->used.swap(prep.used);
-  std::vector<uint32_t> nused_s((size_t)ncand * nsub, 0);
+  std::vector<uint32_t>& nused_s = out->nused_s;
+  nused_s.assign((size_t)ncand * nsub, 0);
   for (size_t i = 0; i < ncand; ++i)
     for (size_t c = 0; c < nchan; ++c) nused_s[i * nsub + c / par->ffactor] += out->used[i * nchan + c];
 
@@ -4926,7 +4937,7 @@ int acf_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const
   DmCand* d_dc = nullptr;
   int32_t *d_dly = nullptr, *d_shift = nullptr, *d_y = nullptr, *d_mask = nullptr;
   uint32_t *d_nu = nullptr, *d_hits = nullptr;
-  long long *d_Y = nullptr, *d_rowmax = nullptr, *d_A = nullptr;
+  long long *d_Y = nullptr, *d_rowmax = nullptr;
   POST_DEV(ps.alloc(&d_rec, n * sizeof(DmRec)), "hipMalloc");
   POST_DEV(ps.alloc(&d_dc, (size_t)ncand * sizeof(DmCand)), "hipMalloc");
   POST_DEV(ps.alloc(&d_dly, delays.size() * sizeof(int32_t)), "hipMalloc");
@@ -4937,7 +4948,6 @@ int acf_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const
   POST_DEV(ps.alloc(&d_shift, (size_t)ncand * sizeof(int32_t)), "hipMalloc");
   POST_DEV(ps.alloc(&d_y, ncell * sizeof(int32_t)), "hipMalloc");
   POST_DEV(ps.alloc(&d_mask, ncell * sizeof(int32_t)), "hipMalloc");
-  POST_DEV(ps.alloc(&d_A, nlag * sizeof(long long)), "hipMalloc");
   POST_DEV(dev_h2d(d_rec, prep.rec.data(), n * sizeof(DmRec), ps.s), "upload records");
   POST_DEV(dev_h2d(d_dc, prep.dc.data(), (size_t)ncand * sizeof(DmCand), ps.s), "upload records");
   POST_DEV(dev_h2d(d_dly, delays.data(), delays.size() * sizeof(int32_t), ps.s), "upload delays");
@@ -4947,7 +4957,7 @@ int acf_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const
   p.rowmax = d_rowmax; p.shift = d_shift; p.y = d_y; p.mask = d_mask;
   p.nsub = (int)nsub; p.nbin = (int)par->nbin; p.tfactor = (int)par->tfactor; p.ffactor = (int)par->ffactor;
   p.p0 = (int)prep.p0; p.np = (int)prep.np; p.ntile = rule.ntile; p.brun = rule.brun; p.gl = rule.gl;
-  out->k[1] = rule.fastk ? 1 : 0;
+  kernel_used[1] = rule.fastk ? 1 : 0;
   bool launched = false;
 #ifndef FRBCH_NO_FAST
   if (rule.fastk) {
@@ -4986,6 +4996,26 @@ int acf_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const
   POST_DEV(dev_check_launch(), "launch scale");
   DEV_LAUNCH(frbch_post_acf_quant, (ncell + 255) / 256, 1, 256, 0, ps.s, p);
   POST_DEV(dev_check_launch(), "launch quantisation");
+  out->d_Y = d_Y; out->d_hits = d_hits; out->d_shift = d_shift; out->d_y = d_y; out->d_mask = d_mask;
+  return FRBCH_OK;
+}
+
+// everything of a call inside its scope: the preparation, the dynamic spectrum, the quantised plane, the ACFs, the fit
+int acf_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+            const frbch_burst_cand* cands, uint32_t ncand, const uint8_t* flag, const frbch_acf_params* par,
+            const frbch_acf_fit_params* fp, PostScope& ps, AcfOut* out, const PostErr& e) {
+  const size_t nbin = par->nbin, nsub = fil->nchan / par->ffactor;
+  const size_t ncell = (size_t)ncand * nsub * nbin, ndt = 2 * (size_t)par->nlagt - 1, nlag = (size_t)ncand * par->nlagf * ndt;
+  DynOut dyn;
+  int rc = dyn_run(fil, d_rows, nrows, bpar, cands, ncand, flag, par, ps, &dyn, out->k, e);
+  if (rc) return rc;
+  out->used.swap(dyn.used);
+  const DmPrep& prep = dyn.prep;
+  const std::vector<uint32_t>& nused_s = dyn.nused_s;
+  long long *d_Y = dyn.d_Y, *d_A = nullptr;
+  uint32_t* d_hits = dyn.d_hits;
+  int32_t *d_shift = dyn.d_shift, *d_y = dyn.d_y, *d_mask = dyn.d_mask;
+  POST_DEV(ps.alloc(&d_A, nlag * sizeof(long long)), "hipMalloc");
   if ((rc = acf2_launch(d_y, ncand, (uint32_t)nsub, par->nbin, par->nlagf, par->nlagt, FRBCH_ACF_PLAN, d_A, ps, &out->k[2], e)) != 0) return rc;
   std::vector<int32_t> shift(ncand);
   out->Y.resize(ncell);
@@ -5155,5 +5185,533 @@ extern "C" int frbch_burstacf_host(const frbch_fil_desc* fil, const void* rows, 
   void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
   return hs.run(e, "device memory for the rows", "upload rows", "download", [&]() {
     return frbch_burstacf_device(fil, d_rows, nrows, bpar, cands, ncand, flag, par, fp, device, Y, yhits, A, P, results, used, kernel_used, err, err_cap);
+  });
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Scattering of a burst: a bank of scattered Gaussians per subband, tau(nu) across the band (include/frbch.h states the arithmetic)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr uint32_t kTbMaxTap = 1024, kTbMaxTemp = 4096, kScatMaxAlpha = 32;
+constexpr uint64_t kTbMaxCells = 1ull << 24, kTbMaxOut = 1ull << 24;
+constexpr int32_t kTbMaxY = 1 << 21, kTbMaxP = 1 << 30;
+
+int tbank_check(uint32_t n, const frbch_tbank_shape* sh, uint32_t form, const PostErr& e) {
+  if (!sh || sh->size != sizeof(frbch_tbank_shape)) return e.fail(FRBCH_E_ARG, "frbch_tbank_shape: wrong size");
+  if (n < 1 || sh->nsub < 1) return e.fail(FRBCH_E_ARG, "at least one plane and one subband");
+  if (sh->nbin < 1 || sh->nbin > kDmMaxBin) return e.fail(FRBCH_E_ARG, "nbin must be 1..1024");
+  if (sh->ntap < 1 || sh->ntap > kTbMaxTap) return e.fail(FRBCH_E_ARG, "ntap must be 1..1024");
+  if (sh->lead >= sh->ntap) return e.fail(FRBCH_E_ARG, "lead must lie below ntap");
+  if (sh->ntemp < 1 || sh->ntemp > kTbMaxTemp) return e.fail(FRBCH_E_ARG, "1..4096 templates");
+  if (sh->nshift < 1 || sh->shift0 > sh->nbin || sh->nshift > sh->nbin - sh->shift0) return e.fail(FRBCH_E_ARG, "nshift must be at least 1 and shift0 + nshift at most nbin");
+  if ((uint64_t)n * sh->nsub * sh->nbin > kTbMaxCells) return e.fail(FRBCH_E_ARG, "n * nsub * nbin exceeds 2^24: cut the batch");
+  if ((uint64_t)n * sh->nsub * sh->ntemp * sh->nshift > kTbMaxOut) return e.fail(FRBCH_E_ARG, "n * nsub * templates * nshift exceeds 2^24: cut the batch, the bank or the shifts");
+  if (form > FRBCH_TBANK_GENERIC) return e.fail(FRBCH_E_ARG, "form must be FRBCH_TBANK_PLAN or FRBCH_TBANK_GENERIC");
+  return FRBCH_OK;
+}
+
+// The plan rule of the template-bank stage -- the one decision behind the launches, kernel_used and frbch_tbank_kernel's
+// answer.  Every thread of the fast kernel owns 8 shifts: nrun = ceil(nshift / 8) runs, nrunp = the next power of two; a
+// workgroup takes sw = min(max(1, 64 / nrunp), 8, nsub rounded up to a power of two) subbands, so that sw nrunp lanes -- a whole
+// wave where the shape allows -- share a template.  A line holds 8 nrun + ntap8 positions (ntap8 = ntap rounded up to 8) skewed
+// by one word in eight, and the line stride lw is the next value = 9 nrunp (mod 32).  sw is halved while the lines leave no room
+// for one template in 64 KiB (sw = 1 always does); the templates are cut into the fewest runs that fit, of equal length kr.
+// Not fast: `form` asks for the generic kernel, or more than 65535 planes (the third grid dimension).  The emulator build
+// has no such kernel: generic.
+struct TbankPlan { bool fastk; int sw, kr, nrun, nrunp, lw, ntap8; size_t lds; };
+TbankPlan tbank_plan_rule(uint32_t n, const frbch_tbank_shape* sh, uint32_t form) {
+  TbankPlan r{false, 0, 0, 0, 0, 0, 0, 0};
+#ifndef FRBCH_NO_FAST
+  if (form == FRBCH_TBANK_GENERIC || n > 65535u) return r;
+  const int nrun = ((int)sh->nshift + fast::kTbRun - 1) / fast::kTbRun, ntap8 = ((int)sh->ntap + 7) & ~7;
+  int nrunp = 1, ls = 1;
+  while (nrunp < nrun) nrunp <<= 1;
+  while (ls < (int)sh->nsub) ls <<= 1;
+  int sw = std::min({std::max(1, 64 / nrunp), fast::kTbMaxSw, ls});
+  const int lwl = 8 * nrun + ntap8, words = (int)(fast::kTbLds / 4);
+  int lw = lwl + lwl / 8;
+  while (lw % 32 != (9 * nrunp) % 32) ++lw;
+  while (sw > 1 && words - sw * lw < ntap8) sw >>= 1;
+  const int krmax = (words - sw * lw) / ntap8;
+  if (krmax < 1) return r;
+  const int nkr = ((int)sh->ntemp + krmax - 1) / krmax, kr = ((int)sh->ntemp + nkr - 1) / nkr;
+  r = TbankPlan{true, sw, kr, nrun, nrunp, lw, ntap8, (size_t)(kr * ntap8 + sw * lw) * 4};
+#else
+  (void)n; (void)sh; (void)form;
+#endif
+  return r;
+}
+
+// the launch of the stage on device planes, inside a scope; not synchronised
+int tbank_launch(const int32_t* d_y, const int32_t* d_P, uint32_t n, const frbch_tbank_shape* sh, uint32_t form, long long* d_C,
+                 PostScope& ps, uint32_t* kernel_used, const PostErr& e) {
+  const TbankPlan pl = tbank_plan_rule(n, sh, form);
+  TbankParams p;
+  memset(&p, 0, sizeof p);
+  p.y = d_y; p.P = d_P; p.C = d_C; p.n = (int)n; p.nsub = (int)sh->nsub; p.nbin = (int)sh->nbin; p.ntemp = (int)sh->ntemp;
+  p.ntap = (int)sh->ntap; p.lead = (int)sh->lead; p.shift0 = (int)sh->shift0; p.nshift = (int)sh->nshift;
+  p.sw = pl.sw; p.kr = pl.kr; p.nrun = pl.nrun; p.nrunp = pl.nrunp; p.lw = pl.lw; p.ntap8 = pl.ntap8;
+  if (kernel_used) *kernel_used = pl.fastk ? 1 : 0;
+#ifndef FRBCH_NO_FAST
+  if (pl.fastk) {
+    const dim3 grid((unsigned)((sh->nsub + pl.sw - 1) / pl.sw), (unsigned)((sh->ntemp + pl.kr - 1) / pl.kr), n), block(fast::kTbThreads);
+    POST_DEV(launch_lds(fast::frbch_post_tbank_fast, grid, block, pl.lds, ps.s, p), "LDS size");
+    POST_DEV(dev_check_launch(), "launch template bank");
+    return FRBCH_OK;
+  }
+#endif
+  const size_t nout = (size_t)n * sh->nsub * sh->ntemp * sh->nshift;
+  DEV_LAUNCH(frbch_post_tbank, (nout + 255) / 256, 1, 256, 0, ps.s, p);
+  POST_DEV(dev_check_launch(), "launch template bank");
+  return FRBCH_OK;
+}
+
+int scat_check_bank(const frbch_scat_bank_params* bp, const PostErr& e) {
+  if (!bp || bp->size != sizeof(frbch_scat_bank_params)) return e.fail(FRBCH_E_ARG, "frbch_scat_bank_params: wrong size");
+  if (bp->ntap < 1 || bp->ntap > kTbMaxTap) return e.fail(FRBCH_E_ARG, "ntap must be 1..1024");
+  if (bp->lead >= bp->ntap) return e.fail(FRBCH_E_ARG, "lead must lie below ntap");
+  if (bp->nsig < 1 || bp->ntau < 1 || (uint64_t)bp->nsig * bp->ntau > kTbMaxTemp) return e.fail(FRBCH_E_ARG, "nsig * ntau must be 1..4096 templates");
+  if (!rm_finite(bp->sigma0) || !rm_finite(bp->rsig) || !rm_finite(bp->tau0) || !rm_finite(bp->rtau)) return e.fail(FRBCH_E_ARG, "the grid of the bank must be finite");
+  if (!(bp->sigma0 >= 0.25) || !(bp->tau0 >= 0.25)) return e.fail(FRBCH_E_ARG, "sigma0 and tau0 must be at least 0.25 bins");
+  if (!(bp->rsig > 1.0) || !(bp->rtau > 1.0)) return e.fail(FRBCH_E_ARG, "rsig and rtau must be above 1");
+  double s = bp->sigma0, t = bp->tau0;
+  for (uint32_t a = 1; a < bp->nsig; ++a) s = s * bp->rsig;
+  for (uint32_t b = 1; b < bp->ntau; ++b) t = t * bp->rtau;
+  if (!rm_finite(s) || !rm_finite(t) || !rm_finite(s * s)) return e.fail(FRBCH_E_ARG, "the grid of the bank must be finite");
+  return FRBCH_OK;
+}
+
+// the bank of the header; every check has been made
+struct ScatBank {
+  std::vector<int32_t> p, psq;          // [K][ntap]
+  std::vector<int64_t> s1, cum;         // [K], [K][ntap + 1]
+  std::vector<double> tail, sigma, tau; // [K], [nsig], [ntau]
+};
+void scat_bank(const frbch_scat_bank_params* bp, ScatBank* out) {
+  POST_NO_CONTRACT
+  const size_t ntap = bp->ntap, nsig = bp->nsig, ntau = bp->ntau, K = nsig * ntau;
+  out->p.assign(K * ntap, 0); out->psq.assign(K * ntap, 0); out->s1.assign(K, 0); out->cum.assign(K * (ntap + 1), 0);
+  out->tail.assign(K, 0.0); out->sigma.resize(nsig); out->tau.resize(ntau);
+  for (size_t a = 0; a < nsig; ++a) out->sigma[a] = a ? out->sigma[a - 1] * bp->rsig : bp->sigma0;
+  for (size_t b = 0; b < ntau; ++b) out->tau[b] = b ? out->tau[b - 1] * bp->rtau : bp->tau0;
+  std::vector<double> g(ntap), ex(ntap), f(ntap);
+  for (size_t a = 0; a < nsig; ++a) {
+    const double sg = out->sigma[a];
+    const double den = 2.0 * (sg * sg);
+    for (size_t j = 0; j < ntap; ++j) {
+      const double d = (double)((long long)j - (long long)bp->lead);
+      const double dd = d * d;
+      g[j] = exp(-dd / den);
+    }
+    for (size_t b = 0; b < ntau; ++b) {
+      const size_t k = a * ntau + b;
+      const double tau = out->tau[b];
+      for (size_t n = 0; n < ntap; ++n) ex[n] = exp(-(double)n / tau);
+      double fmax = 0.0;
+      for (size_t m = 0; m < ntap; ++m) {
+        double acc = 0.0;
+        for (size_t n = 0; n <= m; ++n) {
+          const double t = g[m - n] * ex[n];
+          acc = acc + t;
+        }
+        f[m] = acc;
+        if (acc > fmax) fmax = acc;
+      }
+      int64_t s1 = 0, c = 0;
+      for (size_t m = 0; m < ntap; ++m) {
+        const double u = f[m] / fmax;
+        const int32_t pv = (int32_t)rint(u * 32768.0);
+        out->p[k * ntap + m] = pv;
+        out->psq[k * ntap + m] = pv * pv;
+        s1 += pv;
+        out->cum[k * (ntap + 1) + m] = c;
+        c += (int64_t)pv * pv;
+      }
+      out->cum[k * (ntap + 1) + ntap] = c;
+      out->s1[k] = s1;
+      out->tail[k] = f[ntap - 1] / fmax;
+    }
+  }
+}
+
+int scat_check(const frbch_fil_desc* fil, uint64_t nrows, const frbch_burst_params* bpar, const frbch_burst_cand* cands,
+               uint32_t ncand, const frbch_scat_params* par, const frbch_scat_bank_params* bp, frbch_acf_params* apar,
+               frbch_tbank_shape* sh, const PostErr& e) {
+  int rc = burst_check(fil, nrows, bpar, cands, ncand, e);
+  if (rc) return rc;
+  if (fil->nbits == 32) return e.fail(FRBCH_E_ARG, "the scattering fit is not built for float32 rows: its fixed-point scale needs a bound on the samples");
+  if (!par || par->size != sizeof(frbch_scat_params)) return e.fail(FRBCH_E_ARG, "frbch_scat_params: wrong size");
+  if (par->nbin < 1 || par->nbin > kDmMaxBin) return e.fail(FRBCH_E_ARG, "nbin must be 1..1024");
+  if (par->tfactor < 1 || par->tfactor > kDmMaxTf) return e.fail(FRBCH_E_ARG, "tfactor must be 1..512");
+  if (fil->nchan > kRmMaxChan) return e.fail(FRBCH_E_ARG, "more than 16384 channels");
+  if (par->ffactor < 1 || par->ffactor > fil->nchan || fil->nchan % par->ffactor) return e.fail(FRBCH_E_ARG, "ffactor must be 1..nchan and divide nchan");
+  if ((rc = scat_check_bank(bp, e)) != 0) return rc;
+  *apar = frbch_acf_params{sizeof(frbch_acf_params), par->nbin, par->tfactor, par->ffactor, 1, 1, {0, 0}};
+  *sh = frbch_tbank_shape{sizeof(frbch_tbank_shape), fil->nchan / par->ffactor, par->nbin, bp->nsig * bp->ntau, bp->ntap, bp->lead, par->shift0, par->nshift};
+  return tbank_check(ncand, sh, FRBCH_TBANK_PLAN, e);
+}
+
+int scat_check_fit(const frbch_scat_fit_params* fp, const PostErr& e) {
+  if (!fp || fp->size != sizeof(frbch_scat_fit_params)) return e.fail(FRBCH_E_ARG, "frbch_scat_fit_params: wrong size");
+  if (fp->nalpha < 1 || fp->nalpha > kScatMaxAlpha) return e.fail(FRBCH_E_ARG, "nalpha must be 1..32");
+  if (!rm_finite(fp->snr_min)) return e.fail(FRBCH_E_ARG, "snr_min must be finite");
+  for (uint32_t i = 0; i < fp->nalpha; ++i)
+    if (!rm_finite(fp->alpha[i])) return e.fail(FRBCH_E_ARG, "every alpha must be finite");
+  return FRBCH_OK;
+}
+
+// step 3 of the header; every check has been made.  q may be NULL.
+void scat_fit(const frbch_fil_desc* fil, const frbch_scat_params* par, const frbch_scat_bank_params* bp, const ScatBank& bank,
+              const frbch_scat_fit_params* fp, uint32_t ncand, const int32_t* k, const uint32_t* r, const uint32_t* nused,
+              const uint32_t* nused_s, const int64_t* C, const int64_t* N, double* qout, frbch_scat_sub* sub, frbch_scat_band* band) {
+  POST_NO_CONTRACT
+  const size_t nsub = fil->nchan / par->ffactor, nsig = bp->nsig, ntau = bp->ntau, K = nsig * ntau, nsh = par->nshift;
+  const size_t per = nsub * K * nsh;
+  const double tu = (double)par->tfactor * fil->tsamp_s;
+  const double unit = tu * 1000.0;
+  const double nu_ref = fil->fch1_mhz + ((double)(fil->nchan - 1) / 2.0) * fil->foff_mhz;
+  const double lrt = log(bp->rtau);
+  std::vector<double> own(qout ? 0 : per), prof(std::max<size_t>(ntau, fp->nalpha)), profa(fp->nalpha), Qrow(nsh);
+  std::vector<long long> ds(nsub);
+  std::vector<size_t> part;
+  memset((void*)sub, 0, (size_t)ncand * nsub * sizeof(frbch_scat_sub));
+  memset((void*)band, 0, (size_t)ncand * sizeof(frbch_scat_band));
+  for (uint32_t i = 0; i < ncand; ++i) {
+    double* q = qout ? qout + (size_t)i * per : own.data();
+    const int64_t *Ci = C + (size_t)i * per, *Ni = N + (size_t)i * per;
+    frbch_scat_band& B = band[i];
+    B.k = k[i]; B.r = r[i]; B.nused = nused[i]; B.nu_ref_mhz = nu_ref;
+    const int kr = k[i] - (int32_t)r[i];
+    part.clear();
+    for (size_t s = 0; s < nsub; ++s) {
+      frbch_scat_sub& R = sub[(size_t)i * nsub + s];
+      const uint32_t nu = nused_s[(size_t)i * nsub + s];
+      R.nused = nu;
+      R.freq_mhz = fil->fch1_mhz + ((double)(s * par->ffactor) + (double)(par->ffactor - 1) / 2.0) * fil->foff_mhz;
+      double* qs = q + s * K * nsh;
+      const double cells = (double)par->tfactor * (double)nu;
+      const double vs = ldexp(cells, 2 * kr);
+      size_t best = 0;
+      double qb = 0.0;
+      for (size_t l = 0; l < K * nsh; ++l) {
+        const int64_t c = Ci[s * K * nsh + l], nn = Ni[s * K * nsh + l];
+        double v = 0.0;
+        if (nu && nn > 0 && c > 0) {
+          const double cc = (double)c * (double)c;
+          const double x = cc / (double)nn;
+          v = x / vs;
+        }
+        qs[l] = v;
+        if (v > qb) { qb = v; best = l; }
+      }
+      if (!(qb > 0.0)) continue;
+      const size_t kb = best / nsh, ub = best % nsh, ab = kb / ntau, bb = kb % ntau;
+      R.k = (uint32_t)kb; R.u = (uint32_t)ub; R.q = qb; R.snr = sqrt(qb);
+      R.sigma = bank.sigma[ab]; R.tau = bank.tau[bb]; R.arrival = (double)(par->shift0 + ub);
+      R.sigma_ms = R.sigma * unit; R.tau_ms = R.tau * unit; R.arrival_ms = R.arrival * unit;
+      const double amp = (double)Ci[s * K * nsh + best] / (double)Ni[s * K * nsh + best];
+      R.amp = ldexp(amp, 15 - kr);
+      const double ar = amp * (double)bank.s1[kb];
+      R.area = ldexp(ar, -kr);
+      for (size_t b = 0; b < ntau; ++b) {
+        double m = 0.0;
+        for (size_t a = 0; a < nsig; ++a)
+          for (size_t u = 0; u < nsh; ++u) m = std::max(m, qs[(a * ntau + b) * nsh + u]);
+        prof[b] = m;
+      }
+      size_t lo = bb, hi = bb;
+      const double thr = qb - 1.0;
+      for (size_t b = 0; b < ntau; ++b)
+        if (prof[b] >= thr) { lo = std::min(lo, b); hi = std::max(hi, b); }
+      R.tau_lo = bank.tau[lo] * unit; R.tau_hi = bank.tau[hi] * unit;
+      R.bounded_lo = lo > 0 ? 1 : 0; R.bounded_hi = hi + 1 < ntau ? 1 : 0;
+      R.dq_unscattered = qb - prof[0];
+      if (R.snr >= fp->snr_min) part.push_back(s);
+    }
+    B.nfit = (uint32_t)part.size();
+    if (part.empty()) continue;
+    // the band: Q over (alpha, b_ref, a, u)
+    double Qb = -1.0;
+    size_t bia = 0, bbr = 0, ba = 0, bu = 0;
+    std::fill(prof.begin(), prof.end(), 0.0);
+    std::fill(profa.begin(), profa.end(), 0.0);
+    for (uint32_t ia = 0; ia < fp->nalpha; ++ia) {
+      for (size_t s : part) {
+        const double nus = sub[(size_t)i * nsub + s].freq_mhz;
+        const double lg = log(nus / nu_ref);
+        const double t = (-fp->alpha[ia]) * lg;
+        ds[s] = (long long)rint(t / lrt);
+      }
+      for (size_t br = 0; br < ntau; ++br)
+        for (size_t a = 0; a < nsig; ++a) {
+          std::fill(Qrow.begin(), Qrow.end(), 0.0);
+          for (size_t s : part) {
+            const long long bs = std::min<long long>(std::max<long long>((long long)br + ds[s], 0), (long long)ntau - 1);
+            const double* qs = q + (s * K + a * ntau + (size_t)bs) * nsh;
+            for (size_t u = 0; u < nsh; ++u) Qrow[u] = Qrow[u] + qs[u];
+          }
+          for (size_t u = 0; u < nsh; ++u) {
+            const double v = Qrow[u];
+            if (v > Qb) { Qb = v; bia = ia; bbr = br; ba = a; bu = u; }
+            if (v > prof[br]) prof[br] = v;
+            if (v > profa[ia]) profa[ia] = v;
+          }
+        }
+    }
+    B.q = Qb; B.ialpha = (uint32_t)bia; B.b_ref = (uint32_t)bbr; B.a = (uint32_t)ba; B.u = (uint32_t)bu;
+    B.alpha = fp->alpha[bia]; B.tau_ref = bank.tau[bbr]; B.tau_ref_ms = B.tau_ref * unit;
+    B.sigma = bank.sigma[ba]; B.sigma_ms = B.sigma * unit; B.arrival = (double)(par->shift0 + bu); B.arrival_ms = B.arrival * unit;
+    for (size_t s : part) {
+      const double lg = log(sub[(size_t)i * nsub + s].freq_mhz / nu_ref);
+      const double t = (-fp->alpha[bia]) * lg;
+      const long long bs = (long long)bbr + (long long)rint(t / lrt);
+      if (bs < 0 || bs > (long long)ntau - 1) ++B.nclipped;
+    }
+    const double thr = Qb - 1.0;
+    size_t lo = bbr, hi = bbr;
+    for (size_t b = 0; b < ntau; ++b)
+      if (prof[b] >= thr) { lo = std::min(lo, b); hi = std::max(hi, b); }
+    B.tau_ref_lo = bank.tau[lo] * unit; B.tau_ref_hi = bank.tau[hi] * unit;
+    B.bounded_lo = lo > 0 ? 1 : 0; B.bounded_hi = hi + 1 < ntau ? 1 : 0;
+    B.alpha_lo = B.alpha_hi = B.alpha;
+    for (uint32_t ia = 0; ia < fp->nalpha; ++ia)
+      if (profa[ia] >= thr) { B.alpha_lo = std::min(B.alpha_lo, fp->alpha[ia]); B.alpha_hi = std::max(B.alpha_hi, fp->alpha[ia]); }
+  }
+}
+
+struct ScatOut {
+  std::vector<long long> Y, C, N;
+  std::vector<uint32_t> yhits;
+  std::vector<int32_t> y;
+  std::vector<uint8_t> used;
+  std::vector<frbch_scat_sub> sub;
+  std::vector<frbch_scat_band> band;
+  uint32_t k[3] = {0, 0, 0};
+};
+
+// everything of a call inside its scope: the preparation, the dynamic spectrum, the quantised plane, C, N, the fit
+int scat_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+             const frbch_burst_cand* cands, uint32_t ncand, const uint8_t* flag, const frbch_scat_params* par,
+             const frbch_acf_params* apar, const frbch_tbank_shape* sh, const frbch_scat_bank_params* bp,
+             const frbch_scat_fit_params* fp, PostScope& ps, ScatOut* out, const PostErr& e) {
+  const size_t nbin = par->nbin, nsub = sh->nsub, K = sh->ntemp, ntap = sh->ntap, nsh = sh->nshift;
+  const size_t ncell = (size_t)ncand * nsub * nbin, nout = (size_t)ncand * nsub * K * nsh;
+  ScatBank bank;
+  scat_bank(bp, &bank);
+  DynOut dyn;
+  int rc = dyn_run(fil, d_rows, nrows, bpar, cands, ncand, flag, apar, ps, &dyn, out->k, e);
+  if (rc) return rc;
+  out->used.swap(dyn.used);
+  int32_t* d_P = nullptr;
+  long long* d_C = nullptr;
+  POST_DEV(ps.alloc(&d_P, K * ntap * sizeof(int32_t)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_C, nout * sizeof(long long)), "hipMalloc");
+  POST_DEV(dev_h2d(d_P, bank.p.data(), K * ntap * sizeof(int32_t), ps.s), "upload bank");
+  if ((rc = tbank_launch(dyn.d_y, d_P, ncand, sh, FRBCH_TBANK_PLAN, d_C, ps, &out->k[2], e)) != 0) return rc;
+  std::vector<int32_t> shift(ncand);
+  out->Y.resize(ncell); out->yhits.resize(ncell); out->y.resize(ncell); out->C.resize(nout); out->N.resize(nout);
+  POST_DEV(dev_d2h(out->Y.data(), dyn.d_Y, ncell * sizeof(long long), ps.s), "download dynamic spectrum");
+  POST_DEV(dev_d2h(out->yhits.data(), dyn.d_hits, ncell * sizeof(uint32_t), ps.s), "download dynamic spectrum");
+  POST_DEV(dev_d2h(out->y.data(), dyn.d_y, ncell * sizeof(int32_t), ps.s), "download quantised plane");
+  POST_DEV(dev_d2h(shift.data(), dyn.d_shift, (size_t)ncand * sizeof(int32_t), ps.s), "download scale");
+  POST_DEV(dev_d2h(out->C.data(), d_C, nout * sizeof(long long), ps.s), "download correlations");
+  POST_DEV(dev_sync(ps.s), "sync");
+
+  // all cells complete: N in closed form from the prefix sums, else the same kernel on the 0 / 1 plane with the squared bank
+  bool all = true;
+  for (size_t i = 0; i < ncand && all; ++i)
+    for (size_t s = 0; s < nsub && all; ++s) {
+      const uint32_t nu = dyn.nused_s[i * nsub + s];
+      const uint32_t* h = out->yhits.data() + (i * nsub + s) * nbin;
+      for (size_t j = 0; j < nbin && all; ++j) all = nu > 0 && h[j] == par->tfactor * nu;
+    }
+  if (all) {
+    for (size_t k = 0; k < K; ++k) {
+      const int64_t* cum = bank.cum.data() + k * (ntap + 1);
+      for (size_t u = 0; u < nsh; ++u) {
+        const long long j0 = (long long)par->shift0 + (long long)u - (long long)sh->lead;
+        const long long lo = std::max<long long>(0, -j0), hi = std::min<long long>((long long)ntap, (long long)nbin - j0);
+        out->N[k * nsh + u] = cum[hi] - cum[lo];
+      }
+    }
+    for (size_t is = 1; is < (size_t)ncand * nsub; ++is) memcpy(out->N.data() + is * K * nsh, out->N.data(), K * nsh * sizeof(long long));
+  } else {
+    uint32_t kn = 0;
+    POST_DEV(dev_h2d(d_P, bank.psq.data(), K * ntap * sizeof(int32_t), ps.s), "upload bank");
+    if ((rc = tbank_launch(dyn.d_mask, d_P, ncand, sh, FRBCH_TBANK_PLAN, d_C, ps, &kn, e)) != 0) return rc;
+    POST_DEV(dev_d2h(out->N.data(), d_C, nout * sizeof(long long), ps.s), "download template energies");
+    POST_DEV(dev_sync(ps.s), "sync");
+  }
+  std::vector<uint32_t> ushift(ncand);
+  for (size_t i = 0; i < ncand; ++i) ushift[i] = (uint32_t)shift[i];
+  out->sub.resize((size_t)ncand * nsub);
+  out->band.resize(ncand);
+  scat_fit(fil, par, bp, bank, fp, ncand, dyn.prep.kscale.data(), ushift.data(), dyn.prep.nused.data(), dyn.nused_s.data(),
+           (const int64_t*)out->C.data(), (const int64_t*)out->N.data(), nullptr, out->sub.data(), out->band.data());
+  return FRBCH_OK;
+}
+}  // namespace
+
+extern "C" int frbch_scat_bank(const frbch_scat_bank_params* bp, int32_t* p, int64_t* s1, int64_t* cum, double* tail, double* sigma,
+                               double* tau, char* err, size_t err_cap) try {
+  static_assert(sizeof(frbch_scat_bank_params) == 64 && sizeof(frbch_tbank_shape) == 32 && sizeof(frbch_scat_params) == 32 &&
+                sizeof(frbch_scat_fit_params) == 272 && sizeof(frbch_scat_sub) == 136 && sizeof(frbch_scat_band) == 152, "scattering records");
+  PostErr e{err, err_cap};
+  const int rc = scat_check_bank(bp, e);
+  if (rc) return rc;
+  ScatBank b;
+  scat_bank(bp, &b);
+  if (p) memcpy(p, b.p.data(), b.p.size() * sizeof(int32_t));
+  if (s1) memcpy(s1, b.s1.data(), b.s1.size() * sizeof(int64_t));
+  if (cum) memcpy(cum, b.cum.data(), b.cum.size() * sizeof(int64_t));
+  if (tail) memcpy(tail, b.tail.data(), b.tail.size() * sizeof(double));
+  if (sigma) memcpy(sigma, b.sigma.data(), b.sigma.size() * sizeof(double));
+  if (tau) memcpy(tau, b.tau.data(), b.tau.size() * sizeof(double));
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_tbank_kernel(uint32_t n, const frbch_tbank_shape* sh, uint32_t form) {
+  const int rc = tbank_check(n, sh, form, PostErr{nullptr, 0});
+  return rc ? rc : (tbank_plan_rule(n, sh, form).fastk ? 1 : 0);
+}
+
+extern "C" int frbch_tbank_device(const int32_t* d_y, const int32_t* d_P, uint32_t n, const frbch_tbank_shape* sh, uint32_t form,
+                                  int device, int64_t* d_C, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  int rc = tbank_check(n, sh, form, e);
+  if (rc) return rc;
+  if (!d_y || !d_P || !d_C) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  PostScope ps;
+  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  uint32_t k = 0;
+  if ((rc = tbank_launch(d_y, d_P, n, sh, form, (long long*)d_C, ps, &k, e)) != 0) return rc;
+  POST_DEV(dev_sync(ps.s), "sync");
+  if (kernel_used) *kernel_used = k;
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_tbank_host(const int32_t* y, const int32_t* P, uint32_t n, const frbch_tbank_shape* sh, uint32_t form, int device,
+                                int64_t* C, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  int rc = tbank_check(n, sh, form, e);
+  if (rc) return rc;
+  if (!y || !P || !C) return e.fail(FRBCH_E_ARG, "null argument");
+  const size_t ncell = (size_t)n * sh->nsub * sh->nbin, nbank = (size_t)sh->ntemp * sh->ntap, nout = (size_t)n * sh->nsub * sh->ntemp * sh->nshift;
+  for (size_t i = 0; i < ncell; ++i)
+    if (y[i] > kTbMaxY || y[i] < -kTbMaxY) return e.fail(FRBCH_E_ARG, "a value of the plane lies outside -2^21 .. 2^21: the int64 sums are not safe");
+  for (size_t i = 0; i < nbank; ++i)
+    if (P[i] > kTbMaxP || P[i] < -kTbMaxP) return e.fail(FRBCH_E_ARG, "a tap of the bank lies outside -2^30 .. 2^30: the int64 sums are not safe");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  int32_t* d_y = hs.in(y, ncell * sizeof(int32_t));
+  int32_t* d_P = hs.in(P, nbank * sizeof(int32_t));
+  int64_t* d_C = hs.out(C, nout * sizeof(int64_t));
+  return hs.run(e, "device memory for the plane", "upload plane", "download correlations", [&]() {
+    return frbch_tbank_device(d_y, d_P, n, sh, form, device, d_C, kernel_used, err, err_cap);
+  });
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_burstscat_fit(const frbch_fil_desc* fil, const frbch_scat_params* par, const frbch_scat_bank_params* bp,
+                                   const frbch_scat_fit_params* fp, uint32_t ncand, const int32_t* k, const uint32_t* r,
+                                   const uint32_t* nused, const uint32_t* nused_s, const int64_t* C, const int64_t* N, double* q,
+                                   frbch_scat_sub* sub, frbch_scat_band* band, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  if (!fil || fil->size != sizeof(frbch_fil_desc) || fil->nchan < 1 || !(fil->tsamp_s > 0) || fil->foff_mhz == 0.0) return e.fail(FRBCH_E_ARG, "frbch_fil_desc: wrong size, or bad nchan / tsamp / foff");
+  if (!par || par->size != sizeof(frbch_scat_params)) return e.fail(FRBCH_E_ARG, "frbch_scat_params: wrong size");
+  if (par->tfactor < 1 || par->tfactor > kDmMaxTf) return e.fail(FRBCH_E_ARG, "tfactor must be 1..512");
+  if (par->ffactor < 1 || par->ffactor > fil->nchan || fil->nchan % par->ffactor) return e.fail(FRBCH_E_ARG, "ffactor must be 1..nchan and divide nchan");
+  int rc = scat_check_bank(bp, e);
+  if (rc) return rc;
+  const frbch_tbank_shape sh{sizeof(frbch_tbank_shape), fil->nchan / par->ffactor, par->nbin, bp->nsig * bp->ntau, bp->ntap, bp->lead, par->shift0, par->nshift};
+  if ((rc = tbank_check(ncand, &sh, FRBCH_TBANK_PLAN, e)) != 0) return rc;
+  if ((rc = scat_check_fit(fp, e)) != 0) return rc;
+  if (!k || !r || !nused || !nused_s || !C || !N) return e.fail(FRBCH_E_ARG, "null argument");
+  for (uint32_t i = 0; i < ncand; ++i)
+    if (r[i] > 40 || k[i] < -1024 || k[i] > 1024) return e.fail(FRBCH_E_ARG, "candidate " + std::to_string(i) + ": k or r out of range");
+  ScatBank bank;
+  scat_bank(bp, &bank);
+  const size_t nout = (size_t)ncand * sh.nsub * sh.ntemp * sh.nshift;
+  std::vector<double> qv(q ? nout : 0);
+  std::vector<frbch_scat_sub> sv((size_t)ncand * sh.nsub);
+  std::vector<frbch_scat_band> bv(ncand);
+  scat_fit(fil, par, bp, bank, fp, ncand, k, r, nused, nused_s, C, N, q ? qv.data() : nullptr, sv.data(), bv.data());
+  if (q) memcpy(q, qv.data(), nout * sizeof(double));
+  if (sub) memcpy((void*)sub, sv.data(), sv.size() * sizeof(frbch_scat_sub));
+  if (band) memcpy((void*)band, bv.data(), bv.size() * sizeof(frbch_scat_band));
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_burstscat_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                      const frbch_burst_cand* cands, uint32_t ncand, const frbch_scat_params* par,
+                                      const frbch_scat_bank_params* bp, uint32_t* kernel_used) try {
+  PostErr e{nullptr, 0};
+  frbch_acf_params apar;
+  frbch_tbank_shape sh;
+  int rc = scat_check(fil, nrows, bpar, cands, ncand, par, bp, &apar, &sh, e);
+  if (rc) return rc;
+  if (!d_rows) return FRBCH_E_ARG;
+  std::vector<int32_t> delays;
+  if ((rc = acf_delays(fil, cands, ncand, &apar, &delays, e)) != 0) return rc;
+  if (kernel_used) {
+    kernel_used[0] = burst_fast_layout(fil, d_rows) ? 1 : 0;
+    kernel_used[1] = dyn_plan_rule(fil, d_rows, bpar->products, delays, ncand, &apar).fastk ? 1 : 0;
+    kernel_used[2] = tbank_plan_rule(ncand, &sh, FRBCH_TBANK_PLAN).fastk ? 1 : 0;
+  }
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return FRBCH_E_NOMEM; }
+
+extern "C" int frbch_burstscat_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                      const frbch_burst_cand* cands, uint32_t ncand, const uint8_t* flag, const frbch_scat_params* par,
+                                      const frbch_scat_bank_params* bp, const frbch_scat_fit_params* fp, int device, int64_t* Y,
+                                      uint32_t* yhits, int32_t* y, int64_t* C, int64_t* N, frbch_scat_sub* sub, frbch_scat_band* band,
+                                      uint8_t* used, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  frbch_acf_params apar;
+  frbch_tbank_shape sh;
+  int rc = scat_check(fil, nrows, bpar, cands, ncand, par, bp, &apar, &sh, e);
+  if (rc) return rc;
+  if ((rc = scat_check_fit(fp, e)) != 0) return rc;
+  if (!d_rows) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  ScatOut out;
+  {
+    DeviceGuard dg(device);
+    PostScope ps;
+    if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+    if ((rc = scat_run(fil, d_rows, nrows, bpar, cands, ncand, flag, par, &apar, &sh, bp, fp, ps, &out, e)) != 0) return rc;
+  }
+  if (Y) memcpy(Y, out.Y.data(), out.Y.size() * sizeof(long long));
+  if (yhits) memcpy(yhits, out.yhits.data(), out.yhits.size() * sizeof(uint32_t));
+  if (y) memcpy(y, out.y.data(), out.y.size() * sizeof(int32_t));
+  if (C) memcpy(C, out.C.data(), out.C.size() * sizeof(long long));
+  if (N) memcpy(N, out.N.data(), out.N.size() * sizeof(long long));
+  if (sub) memcpy((void*)sub, out.sub.data(), out.sub.size() * sizeof(frbch_scat_sub));
+  if (band) memcpy((void*)band, out.band.data(), out.band.size() * sizeof(frbch_scat_band));
+  if (used) memcpy(used, out.used.data(), out.used.size());
+  if (kernel_used) { kernel_used[0] = out.k[0]; kernel_used[1] = out.k[1]; kernel_used[2] = out.k[2]; }
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_burstscat_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                    const frbch_burst_cand* cands, uint32_t ncand, const uint8_t* flag, const frbch_scat_params* par,
+                                    const frbch_scat_bank_params* bp, const frbch_scat_fit_params* fp, int device, int64_t* Y,
+                                    uint32_t* yhits, int32_t* y, int64_t* C, int64_t* N, frbch_scat_sub* sub, frbch_scat_band* band,
+                                    uint8_t* used, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  frbch_acf_params apar;
+  frbch_tbank_shape sh;
+  int rc = scat_check(fil, nrows, bpar, cands, ncand, par, bp, &apar, &sh, e);
+  if (rc) return rc;
+  if ((rc = scat_check_fit(fp, e)) != 0) return rc;
+  if (!rows) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
+  return hs.run(e, "device memory for the rows", "upload rows", "download", [&]() {
+    return frbch_burstscat_device(fil, d_rows, nrows, bpar, cands, ncand, flag, par, bp, fp, device, Y, yhits, y, C, N, sub, band, used, kernel_used, err, err_cap);
   });
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }

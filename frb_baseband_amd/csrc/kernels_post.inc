@@ -1505,3 +1505,37 @@ KERNEL(frbch_post_acf2d, Acf2Params) {
     }
   }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Scattering of a burst, the template-bank stage (frbch_tbank_*, frbch_burstscat_*; include/frbch.h states the arithmetic):
+// C[plane][s][k][u] = the sum over the taps m of y[plane][s][shift0 + u - lead + m] P[k][m], int64, terms whose bin lies
+// outside the row absent.  |y| <= 2^21, |P| <= 2^30, ntap <= 1024: every sum is below 2^61 and exact in any order, so the
+// generic kernel below and the fast one (kernels_post_fast.inc) differ in schedule only.
+// ---------------------------------------------------------------------------------------------------------------------
+struct TbankParams {
+  const int32_t* y;            // [n][nsub][nbin], |y| <= 2^21
+  const int32_t* P;            // [ntemp][ntap], |P| <= 2^30
+  long long* C;                // [n][nsub][ntemp][nshift]
+  int n, nsub, nbin, ntemp, ntap, lead, shift0, nshift;
+  int sw, kr, nrun, nrunp, lw, ntap8;        // fast kernel: the plan (tbank_plan_rule)
+};
+
+// grid (ceil(n nsub ntemp nshift / 256)), one thread per (plane, subband, template, shift), taps ascending
+KERNEL(frbch_post_tbank, TbankParams) {
+  K_PROLOGUE;
+  (void)smem; (void)by;
+  PHASE {
+    const long long idx = (long long)bx * nthr + tid;
+    if (idx < (long long)p.n * p.nsub * p.ntemp * p.nshift) {
+      const int u = (int)(idx % p.nshift);
+      const int k = (int)((idx / p.nshift) % p.ntemp);
+      const int32_t* y = p.y + (size_t)(idx / ((long long)p.nshift * p.ntemp)) * p.nbin;      // row (plane, s)
+      const int32_t* t = p.P + (size_t)k * p.ntap;
+      const int j0 = p.shift0 + u - p.lead;                                                  // the bin of tap 0
+      const int mlo = j0 < 0 ? -j0 : 0, mhi = p.nbin - j0 < p.ntap ? p.nbin - j0 : p.ntap;
+      long long a = 0;
+      for (int m = mlo; m < mhi; ++m) a += (long long)y[j0 + m] * (long long)t[m];
+      p.C[idx] = a;
+    }
+  }
+}

@@ -1471,4 +1471,74 @@ __global__ void __launch_bounds__(kAcfThreads) frbch_post_acf2d_join(Acf2Params 
   for (int t = 0; t < p.nslab; ++t) a += p.part[(plane * p.nslab + t) * per + l];
   p.A[idx] = a;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Scattering of a burst, the template-bank stage (HIP only; frbch_post_tbank of kernels_post.inc stays the emulable form and
+// the fallback).  C[s][k][u] = sum over the taps m of y[s][shift0 + u - lead + m] P[k][m], int64, exact in any order.
+// A workgroup owns one plane, `sw` subbands from s0 and a run of `kr` templates from k0.  It stages
+//   t: the templates of its run, [kr][ntap8] int32, ntap8 = ntap rounded up to 8, zero behind the last tap and the last template,
+//   l: per subband a line of 8 nrun + ntap8 positions, position x = bin shift0 - lead + x, zero wherever the bin lies outside
+//      the row or the row outside the plane -- so the inner loop has no bounds.
+// The 256 threads are 256 / (sw nrunp) template lanes times sw nrunp items; item (si, run) owns subband s0 + si and the eight
+// shifts u = 8 run + i, i < 8, in eight int64 accumulators, and takes the templates k0 + kp, k0 + kp + 256 / (sw nrunp), ...
+// Walking the taps it keeps the eight line values at positions m + 8 run .. + 7 in registers: every tap loads ONE new line
+// word and multiplies P[k][m] -- read 8 taps at a time as two 16-byte reads, the same address in every lane that shares k, and
+// with sw nrunp >= 64 that is the whole wave -- into all eight: 10 LDS reads per 64 multiply-adds.  The window rotates by
+// renaming: the loop over eight taps is unrolled and position x lives in register x mod 8 (the scheme of
+// frbch_post_acf2d_fast, with the template in the place of the slab row).
+// Banks: the lanes of a wave differ in `run`, i.e. by 8 positions; a line is stored skewed, position x at word x + x / 8, which
+// makes the lane stride 9 words, and the line stride lw is chosen = 9 nrunp (mod 32) so that the subbands of one wave
+// interleave as well.  Nothing is reduced across workgroups: every thread stores its own eight sums, no join.
+// grid (ceil(nsub / sw), ceil(ntemp / kr), n), 256 threads, (kr ntap8 + sw lw) 4 <= kTbLds bytes of LDS.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int kTbThreads = 256, kTbRun = 8, kTbMaxSw = 8;
+constexpr size_t kTbLds = 65536;                                           // 64 KiB: two workgroups per CU
+
+__global__ void __launch_bounds__(kTbThreads) frbch_post_tbank_fast(TbankParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int lwl = 8 * p.nrun + p.ntap8, items = p.sw * p.nrunp;
+  int32_t* st = reinterpret_cast<int32_t*>(smem);
+  int32_t* sl = st + p.kr * p.ntap8;
+  const int tid = threadIdx.x;
+  const int s0 = (int)blockIdx.x * p.sw, k0 = (int)blockIdx.y * p.kr;
+  const int nk = min(p.kr, p.ntemp - k0);
+  const int32_t* y = p.y + (size_t)blockIdx.z * p.nsub * p.nbin;
+  for (int i = tid; i < p.kr * p.ntap8; i += kTbThreads) {
+    const int kk = i / p.ntap8, m = i % p.ntap8;
+    st[i] = (kk < nk && m < p.ntap) ? p.P[(size_t)(k0 + kk) * p.ntap + m] : 0;
+  }
+  for (int i = tid; i < p.sw * lwl; i += kTbThreads) {
+    const int q = i / lwl, x = i % lwl, s = s0 + q, j = p.shift0 - p.lead + x;
+    sl[q * p.lw + x + (x >> 3)] = (s < p.nsub && j >= 0 && j < p.nbin) ? y[(size_t)s * p.nbin + j] : 0;
+  }
+  __syncthreads();
+  const int item = tid % items, kp = tid / items, kpar = kTbThreads / items;
+  const int run = item % p.nrunp, si = item / p.nrunp;
+  if (run >= p.nrun || s0 + si >= p.nsub) return;
+  const int32_t* line = sl + si * p.lw + 9 * run;                          // position 8 run lives at word 9 run
+  for (int kk = kp; kk < nk; kk += kpar) {
+    long long acc[kTbRun];
+#pragma unroll
+    for (int i = 0; i < kTbRun; ++i) acc[i] = 0;
+    const int32_t* a = st + kk * p.ntap8;
+    const int32_t* b = line;
+    int32_t w[kTbRun];
+#pragma unroll
+    for (int i = 0; i < kTbRun - 1; ++i) w[i] = b[i];
+    for (int m = 0; m < p.ntap8 / 8; ++m, b += 9, a += 8) {
+      const int4 a0 = *reinterpret_cast<const int4*>(a), a1 = *reinterpret_cast<const int4*>(a + 4);
+      const int32_t av[kTbRun] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+#pragma unroll
+      for (int jj = 0; jj < kTbRun; ++jj) {
+        w[(jj + 7) & 7] = b[jj == 0 ? 7 : 8 + jj];                         // position 8 (run + m) + 7 + jj (word 9 (run + m) + 8 is the skew's gap)
+#pragma unroll
+        for (int i = 0; i < kTbRun; ++i) acc[i] += (long long)av[jj] * (long long)w[(jj + i) & 7];
+      }
+    }
+    long long* out = p.C + (((size_t)blockIdx.z * p.nsub + (size_t)(s0 + si)) * p.ntemp + (size_t)(k0 + kk)) * p.nshift;
+#pragma unroll
+    for (int i = 0; i < kTbRun; ++i)
+      if (8 * run + i < p.nshift) out[8 * run + i] = acc[i];
+  }
+}
 }  // namespace fast

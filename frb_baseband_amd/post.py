@@ -37,6 +37,10 @@ reference's `dspsr -E <par> ... <IFall.fil>` stage) of SIGPROC filterbank files,
 * ``burstacf_fil`` (``post burstacf``) keeps frequency and time together: the dedispersed, noise-weighted dynamic spectrum of a
   burst, its two-dimensional autocorrelation in exact integers, and from it the scintillation bandwidth, the sub-burst duration
   and the drift of sub-bursts in frequency (``burst_acf``: frbch_burstacf_host).
+* ``burstscat_fil`` (``post scatter``) fits a pulse shape: every subband of that dynamic spectrum is correlated with a bank of
+  Gaussians convolved with one-sided exponentials at every trial arrival bin, in exact integers; the best template gives the
+  subband's scattering time, and tau(nu) = tau_ref (nu / nu_ref)^-alpha is fitted across the band (``burst_scatter``:
+  frbch_burstscat_host).
 There is no CPU fallback: the sums run in libfrbch.so on a gfx950 device.
 """
 from __future__ import annotations
@@ -2475,6 +2479,196 @@ def burstacf_fil(filterbankfile, bursts, nbin=256, tfactor=1, ffactor=1, nlagf=N
     return files, acf
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# Scattering of a burst: a bank of scattered Gaussians per subband, tau(nu) across the band (frbch_burstscat_*, frbch_tbank_*)
+# ------------------------------------------------------------------------------------------------------------------
+SCAT_SUB = np.dtype([("sigma", "<f8"), ("tau", "<f8"), ("arrival", "<f8"), ("sigma_ms", "<f8"), ("tau_ms", "<f8"), ("arrival_ms", "<f8"),
+                     ("amp", "<f8"), ("area", "<f8"), ("snr", "<f8"), ("q", "<f8"), ("tau_lo", "<f8"), ("tau_hi", "<f8"),
+                     ("dq_unscattered", "<f8"), ("freq_mhz", "<f8"), ("k", "<u4"), ("u", "<u4"), ("nused", "<u4"), ("bounded_lo", "<u4"),
+                     ("bounded_hi", "<u4"), ("reserved", "<u4")])
+SCAT_BAND = np.dtype([("tau_ref", "<f8"), ("tau_ref_ms", "<f8"), ("alpha", "<f8"), ("sigma", "<f8"), ("sigma_ms", "<f8"), ("arrival", "<f8"),
+                      ("arrival_ms", "<f8"), ("q", "<f8"), ("tau_ref_lo", "<f8"), ("tau_ref_hi", "<f8"), ("alpha_lo", "<f8"),
+                      ("alpha_hi", "<f8"), ("nu_ref_mhz", "<f8"), ("k", "<i4"), ("r", "<u4"), ("nused", "<u4"), ("nfit", "<u4"),
+                      ("nclipped", "<u4"), ("b_ref", "<u4"), ("a", "<u4"), ("u", "<u4"), ("ialpha", "<u4"), ("bounded_lo", "<u4"),
+                      ("bounded_hi", "<u4"), ("reserved", "<u4")])
+SCAT_ROW = "%-8s DM %9.3f sample %10d  tau(%.1f MHz) %9.4f ms (%.4f .. %.4f%s)  alpha %6.3f (%.3f .. %.3f)  sigma %8.4f ms  %d subbands, %d clipped"
+SCAT_SUB_ROW = "  %10.3f MHz  snr %8.2f  tau %9.4f ms (%.4f .. %.4f%s)  sigma %8.4f ms  arrival %9.4f ms  dq(unscattered) %8.2f"
+SCAT_ALPHAS = (0.0, 1.0, 2.0, 3.0, 4.0, 4.4, 5.0, 6.0)
+
+
+def scat_bank_params(nsig=16, ntau=32, ntap=256, lead=None, sigma0=0.5, rsig=2.0 ** 0.25, tau0=0.5, rtau=2.0 ** 0.25) -> _lib.FrbchScatBankParams:
+    lead = int(ntap) // 4 if lead is None else int(lead)
+    return _lib.FrbchScatBankParams(C.sizeof(_lib.FrbchScatBankParams), int(nsig), int(ntau), int(ntap), lead, (C.c_uint32 * 3)(0, 0, 0),
+                                    float(sigma0), float(rsig), float(tau0), float(rtau))
+
+
+def scat_params(nbin: int, tfactor: int, ffactor: int, shift0: int, nshift: int) -> _lib.FrbchScatParams:
+    return _lib.FrbchScatParams(C.sizeof(_lib.FrbchScatParams), int(nbin), int(tfactor), int(ffactor), int(shift0), int(nshift))
+
+
+def scat_fit_params(alphas=SCAT_ALPHAS, snr_min: float = 5.0) -> _lib.FrbchScatFitParams:
+    alphas = [float(a) for a in np.atleast_1d(alphas)]
+    if not 1 <= len(alphas) <= 32:
+        raise InputError("1..32 values of alpha")
+    return _lib.FrbchScatFitParams(C.sizeof(_lib.FrbchScatFitParams), len(alphas), float(snr_min), (C.c_double * 32)(*alphas))
+
+
+def tbank_shape(nsub, nbin, ntemp, ntap, lead, shift0, nshift) -> _lib.FrbchTbankShape:
+    return _lib.FrbchTbankShape(C.sizeof(_lib.FrbchTbankShape), int(nsub), int(nbin), int(ntemp), int(ntap), int(lead), int(shift0), int(nshift))
+
+
+def scat_bank(bank: _lib.FrbchScatBankParams, lib=None) -> dict:
+    """The bank of scattered Gaussians, from the library (frbch_scat_bank, host only) -> dict(p int32 [K][ntap], s1 int64 [K], cum
+    int64 [K][ntap + 1], tail float64 [K], sigma [nsig], tau [ntau], in bins)."""
+    lib = lib or _lib.load()
+    nsig, ntau, ntap = bank.nsig, bank.ntau, bank.ntap
+    if not (1 <= ntap <= 1024 and nsig >= 1 and ntau >= 1 and nsig * ntau <= 4096):
+        raise InputError("ntap must be 1..1024 and nsig * ntau 1..4096")
+    K = nsig * ntau
+    out = dict(p=np.zeros((K, ntap), np.int32), s1=np.zeros(K, np.int64), cum=np.zeros((K, ntap + 1), np.int64), tail=np.zeros(K),
+               sigma=np.zeros(nsig), tau=np.zeros(ntau))
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_scat_bank(C.byref(bank), out["p"].ctypes.data, out["s1"].ctypes.data, out["cum"].ctypes.data, out["tail"].ctypes.data,
+                               out["sigma"].ctypes.data, out["tau"].ctypes.data, err, len(err)), err)
+    return out
+
+
+def tbank(y, P, lead: int, shift0: int, nshift: int, form: int = _lib.TBANK_PLAN, device: int = 0, lib=None, info: dict | None = None) -> np.ndarray:
+    """The correlation of int32 planes ``y [n][nsub][nbin]`` (|y| <= 2^21) with a bank ``P [K][ntap]`` (|P| <= 2^30) at ``nshift``
+    arrival bins from ``shift0`` (frbch_tbank_host) -> int64 ``[n][nsub][K][nshift]``.  ``info['kernel_used']``: 1 = the fast kernel,
+    0 = the generic one; ``form=_lib.TBANK_GENERIC`` asks for the generic one."""
+    lib = lib or _lib.load()
+    y, P = np.ascontiguousarray(y, dtype=np.int32), np.ascontiguousarray(P, dtype=np.int32)
+    if y.ndim != 3 or P.ndim != 2:
+        raise InputError("y must have the shape [n][nsub][nbin] and P the shape [K][ntap]")
+    n, nsub, nbin = y.shape
+    sh = tbank_shape(nsub, nbin, P.shape[0], P.shape[1], lead, shift0, nshift)
+    if int(nshift) < 1 or n * nsub * P.shape[0] * int(nshift) > 1 << 24:
+        raise InputError("nshift must be at least 1 and n * nsub * templates * nshift at most 2^24")
+    Cc = np.zeros((n, nsub, P.shape[0], int(nshift)), np.int64)
+    k = C.c_uint32(0)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_tbank_host(y.ctypes.data, P.ctypes.data, n, C.byref(sh), int(form), device, Cc.ctypes.data, C.byref(k), err, len(err)), err)
+    if info is not None:
+        info.update(kernel_used=k.value)
+    return Cc
+
+
+def burst_scatter(fil_or_rows, hdr: dict, cands, nbin: int = 256, tfactor: int = 1, ffactor: int = 1, bank=None, shift0: int | None = None,
+                  nshift: int | None = None, alphas=SCAT_ALPHAS, snr_min: float = 5.0, flag=None, products: str = "stokes",
+                  device: int = 0, lib=None, info: dict | None = None):
+    """The scattering of every burst (frbch_burstscat_host; include/frbch.h states the arithmetic): the dedispersed dynamic spectrum
+    in ``nchans / ffactor`` subbands and ``nbin`` bins of ``tfactor`` rows, every subband correlated with the bank of scattered
+    Gaussians ``bank`` (``scat_bank_params``) at ``nshift`` arrival bins from ``shift0`` (default: the middle half of the window),
+    the best template per subband and tau(nu) = tau_ref (nu / nu_ref)^-alpha over the listed ``alphas`` -> dict(Y, yhits, y
+    [n][nsub][nbin], C, N int64 [n][nsub][K][nshift], q float64 of that shape, sub SCAT_SUB [n][nsub], band SCAT_BAND [n], used,
+    bank: what ``scat_bank`` returns).  The intervals are profile intervals on the grid and claim no more (see the header).
+    ``info``: ``spectra_kernel_used``, ``dynspec_kernel_used``, ``kernel_used`` (the template bank's): 1 = fast, 0 = generic."""
+    lib = lib or _lib.load()
+    rows, nrows, cands, par, _g = _burst_args(fil_or_rows, hdr, cands, None, products)
+    n, nchan = cands.size, hdr["nchans"]
+    fl = None if flag is None else np.ascontiguousarray(flag, dtype=np.uint8)
+    if fl is not None and fl.shape != (nchan,):
+        raise InputError("flag must have the shape [nchans]")
+    ffactor = int(ffactor)
+    if ffactor < 1 or ffactor > nchan or nchan % ffactor:
+        raise InputError("ffactor must be 1..nchans and divide nchans")
+    bank = bank if bank is not None else scat_bank_params()
+    bk = scat_bank(bank, lib)
+    nsub, nb, K = nchan // ffactor, max(1, min(int(nbin), 1024)), bank.nsig * bank.ntau
+    shift0 = nb // 4 if shift0 is None else int(shift0)
+    nshift = max(1, nb // 2) if nshift is None else int(nshift)
+    if shift0 < 0 or nshift < 1 or shift0 + nshift > nb:
+        raise InputError("nshift must be at least 1 and shift0 + nshift at most nbin")
+    if n * nsub * nb > 1 << 24 or n * nsub * K * nshift > 1 << 24:
+        raise InputError("ncand * nsub * nbin or ncand * nsub * templates * nshift exceeds 2^24: cut the batch, the bank or the shifts")
+    spar, fpar = scat_params(nbin, tfactor, ffactor, shift0, nshift), scat_fit_params(alphas, snr_min)
+    Y, yhits, y = np.zeros((n, nsub, nb), np.int64), np.zeros((n, nsub, nb), np.uint32), np.zeros((n, nsub, nb), np.int32)
+    Cc, Nn = np.zeros((n, nsub, K, nshift), np.int64), np.zeros((n, nsub, K, nshift), np.int64)
+    sub, band = np.zeros((n, nsub), dtype=SCAT_SUB), np.zeros(n, dtype=SCAT_BAND)
+    used = np.zeros((n, nchan), np.uint8)
+    k = (C.c_uint32 * 3)(0, 0, 0)
+    err = C.create_string_buffer(512)
+    desc = fil_desc(hdr, hdr.get("product", 0))
+    _check(lib.frbch_burstscat_host(C.byref(desc), rows.ctypes.data, nrows, C.byref(par), cands.ctypes.data, n,
+                                    fl.ctypes.data if fl is not None else None, C.byref(spar), C.byref(bank), C.byref(fpar), device,
+                                    Y.ctypes.data, yhits.ctypes.data, y.ctypes.data, Cc.ctypes.data, Nn.ctypes.data, sub.ctypes.data,
+                                    band.ctypes.data, used.ctypes.data, k, err, len(err)), err)
+    if info is not None:
+        info.update(spectra_kernel_used=k[0], dynspec_kernel_used=k[1], kernel_used=k[2])
+    q = np.zeros(Cc.shape)
+    ks, rs, nu = (np.ascontiguousarray(band[f]) for f in ("k", "r", "nused"))
+    nus = np.ascontiguousarray(sub["nused"])
+    _check(lib.frbch_burstscat_fit(C.byref(desc), C.byref(spar), C.byref(bank), C.byref(fpar), n, ks.ctypes.data, rs.ctypes.data, nu.ctypes.data,
+                                   nus.ctypes.data, Cc.ctypes.data, Nn.ctypes.data, q.ctypes.data, None, None, err, len(err)), err)
+    return dict(Y=Y, yhits=yhits, y=y, C=Cc, N=Nn, q=q, sub=sub, band=band, used=used, bank=bk)
+
+
+def _scat_panels(sc, i, shift0, lead, tfactor, tsamp):
+    """above: the dynamic spectrum, subbands top to bottom against the bins; then one strip per subband (at most 16, evenly
+    picked): its profile with the fitted template over it; below: log tau against log nu of the subbands in the band fit with
+    the fitted power law"""
+    width, height = 512, 96
+    dyn = sc["Y"][i].astype(np.float64) / np.maximum(sc["yhits"][i], 1)
+    nsub, nbin = dyn.shape
+    panels = [_unit(_resample(dyn, 2 * height, width)), np.zeros((4, width))]
+    p, ntap = sc["bank"]["p"], sc["bank"]["p"].shape[1]
+    for s in np.unique(np.linspace(0, nsub - 1, min(nsub, 16)).astype(int)):
+        r = sc["sub"][i, s]
+        prof = sc["y"][i, s].astype(np.float64)
+        model = np.zeros(nbin)
+        if r["q"] > 0:
+            j0 = shift0 + int(r["u"]) - lead
+            lo, hi = max(0, -j0), min(ntap, nbin - j0)
+            amp = float(sc["C"][i, s, r["k"], r["u"]]) / float(sc["N"][i, s, r["k"], r["u"]])
+            model[j0 + lo:j0 + hi] = amp * p[r["k"], lo:hi]
+        panels += [_curve_panel([prof, model], width, height // 2), np.zeros((2, width))]
+    band = sc["band"][i]
+    ok = sc["sub"][i]["snr"] > 0
+    law = np.zeros((height, width))
+    if band["nfit"] and ok.any():
+        f = sc["sub"][i]["freq_mhz"][ok]
+        order = np.argsort(f)
+        fit = band["tau_ref_ms"] * (f[order] / band["nu_ref_mhz"]) ** (-band["alpha"])
+        law = _curve_panel([np.log(np.maximum(sc["sub"][i]["tau_ms"][ok][order], 1e-30)), np.log(np.maximum(fit, 1e-30))], width, height)
+    return np.concatenate(panels + [law, np.zeros((8, width))], axis=0)
+
+
+def burstscat_fil(filterbankfile, bursts, nbin=256, tfactor=1, ffactor=1, bank=None, shift0=None, nshift=None, alphas=SCAT_ALPHAS,
+                  snr_min=5.0, off_gap=None, off_len=None, flag_file=None, products="stokes", device=0, lib=None, info: dict | None = None):
+    """The scattering of the bursts of a filterbank: ``bursts`` = (dm, sample, width) tuples or BURST_CAND records.  Writes
+    ``<base>_scat.npz`` (Y, yhits, y, C, N, q, sub, band, used, the bank, bursts and the grid), ``<base>_scat.txt`` (per burst the band
+    fit, then one line per subband) and ``<base>_scat.png`` (per burst: the dynamic spectrum, the per-subband fits over the
+    profiles, tau against nu with the fitted power law).  Returns (files, what ``burst_scatter`` returns)."""
+    lib = lib or _lib.load()
+    fil = sigproc.read_fil(filterbankfile)
+    hdr = fil.header
+    cands = burst_cands(bursts, off_gap, off_len)
+    flag = read_flag_file(flag_file, hdr["nchans"]).astype(np.uint8) if flag_file else None
+    bank = bank if bank is not None else scat_bank_params()
+    sc = burst_scatter(fil, hdr, cands, nbin, tfactor, ffactor, bank, shift0, nshift, alphas, snr_min, flag=flag, products=products,
+                       device=device, lib=lib, info=info)
+    nshift_used = sc["C"].shape[3]
+    shift0_used = int(nbin) // 4 if shift0 is None else int(shift0)
+    base = filterbankfile.replace(".fil", "")
+    files = [base + "_scat.npz", base + "_scat.txt", base + "_scat.png"]
+    arrays = {f: sc[f] for f in ("Y", "yhits", "y", "C", "N", "q", "sub", "band", "used")}
+    np.savez(files[0], bursts=cands, nbin=np.int64(nbin), tfactor=np.int64(tfactor), ffactor=np.int64(ffactor), shift0=np.int64(shift0_used),
+             nshift=np.int64(nshift_used), lead=np.int64(bank.lead), alphas=np.asarray(alphas, np.float64), snr_min=np.float64(snr_min),
+             **arrays, **{"bank_" + f: v for f, v in sc["bank"].items()})
+    with open(files[1], "w") as f:
+        for i, (c, b) in enumerate(zip(cands, sc["band"])):
+            edge = "" if b["bounded_lo"] and b["bounded_hi"] else ", at the grid's edge"
+            f.write(SCAT_ROW % ("burst%d" % i, c["dm"], int(c["sample"]), b["nu_ref_mhz"], b["tau_ref_ms"], b["tau_ref_lo"], b["tau_ref_hi"], edge,
+                                b["alpha"], b["alpha_lo"], b["alpha_hi"], b["sigma_ms"], b["nfit"], b["nclipped"]) + "\n")
+            for r in sc["sub"][i]:
+                edge = "" if r["bounded_lo"] and r["bounded_hi"] else ", at the grid's edge"
+                f.write(SCAT_SUB_ROW % (r["freq_mhz"], r["snr"], r["tau_ms"], r["tau_lo"], r["tau_hi"], edge, r["sigma_ms"], r["arrival_ms"],
+                                        r["dq_unscattered"]) + "\n")
+    write_png(files[2], np.concatenate([_scat_panels(sc, i, shift0_used, bank.lead, tfactor, hdr["tsamp"]) for i in range(cands.size)], axis=0))
+    return files, sc
+
+
 def main(argv=None):
     """``python -m frb_baseband_amd.post fold <fil> <par> [--polyco FILE] [--doppler X] [--products coherency|stokes] [...]`` / ``... prepdata <fil> --dm <dm> [...]`` /
     ``... search <fil> --dm <dm> [--dm2 --dmstep --threshold --max-width --detrend ...]`` /
@@ -2486,6 +2680,7 @@ def main(argv=None):
     ``... dmfit <fil> --dm D (--sample S | --time T) --width W [--dm-half H --ddm X --nbin N --tfactor F --smooth S --fit-frac R --flag FILE --coherency]``
     (or ``--dm .. --dm2 .. --dmstep ..`` to search for the bursts; ``rmsynth`` and ``polprof`` take ``--dm-from BASE_dm.npz [--dm-kind snr|struct]`` in place of ``--dm``) /
     ``... burstacf <fil> (--dm D (--sample S | --time T) --width W | --dm-from BASE_dm.npz [--dm-kind snr|struct]) [--nbin N --tfactor F --ffactor F --lagf N --lagt N --fit-frac R --flag FILE --coherency]`` /
+    ``... scatter <fil> (--dm D (--sample S | --time T) --width W | --dm-from BASE_dm.npz [--dm-kind snr|struct]) [--nbin N --tfactor F --ffactor F --sigma0 S --nsig N --rsig R --tau0 T --ntau N --rtau R --ntap N --lead M --shift0 J --nshift N --alpha A [A ...] --snr-min S --flag FILE --coherency]`` /
     ``... polprof <fil> (--dm D (--sample S | --time T) --width W --rm R | --rm-from BASE_rm.npz) [--nbin N --tfactor F --ref mean|zero --flag FILE --gains FILE.npy --coherency]``
     (``search`` and ``candidates`` take ``--flag FILE`` and ``--rfi``; ``search``, ``candidates`` and ``rfifind`` take ``--resident``:
     one upload of the rows per command; ``rfifind --periodic [--t-freq S]`` and ``--rfi --periodic`` add the periodicity test): the stages
@@ -2669,8 +2864,53 @@ def main(argv=None):
     c.add_argument("--flag", default=None, help="flag file: channels left out")
     c.add_argument("--coherency", action="store_true", help="the file holds the -d4 products: PP + QQ is used")
     c.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
+    c = sub.add_parser("scatter", help="scattering of the bursts of a filterbank: a bank of scattered Gaussians fitted per subband, tau(nu) across the band")
+    c.add_argument("fil")
+    c.add_argument("--dm", type=float, action="append", default=None, help="DM of a burst (repeatable, one per burst)")
+    c.add_argument("--dm-from", default=None, help="<base>_dm.npz of `dmfit`: its bursts at their measured DMs instead of --dm .. --width")
+    c.add_argument("--dm-kind", choices=("snr", "struct"), default="struct", help="which DM of --dm-from: the S/N- or the structure-maximising one")
+    c.add_argument("--sample", type=int, action="append", default=None, help="centre of a burst, row at the top of the band (repeatable)")
+    c.add_argument("--time", type=float, action="append", default=None, help="the same in seconds from the start of the file (repeatable)")
+    c.add_argument("--width", type=int, action="append", default=None, help="on-pulse rows (repeatable; one value serves every burst)")
+    c.add_argument("--nbin", type=int, default=256, help="time bins (1..1024)")
+    c.add_argument("--tfactor", type=int, default=1, help="rows per bin (1..512)")
+    c.add_argument("--ffactor", type=int, default=1, help="channels per subband (divides nchans)")
+    c.add_argument("--sigma0", type=float, default=0.5, help="the smallest Gaussian sigma of the bank, in bins")
+    c.add_argument("--nsig", type=int, default=16, help="values of sigma")
+    c.add_argument("--rsig", type=float, default=2.0 ** 0.25, help="ratio of neighbouring sigmas")
+    c.add_argument("--tau0", type=float, default=0.5, help="the smallest scattering time of the bank, in bins")
+    c.add_argument("--ntau", type=int, default=32, help="values of tau")
+    c.add_argument("--rtau", type=float, default=2.0 ** 0.25, help="ratio of neighbouring taus")
+    c.add_argument("--ntap", type=int, default=256, help="taps of a template (1..1024)")
+    c.add_argument("--lead", type=int, default=None, help="the tap of the Gaussian's centre (default: ntap / 4)")
+    c.add_argument("--shift0", type=int, default=None, help="first trial arrival bin (default: nbin / 4)")
+    c.add_argument("--nshift", type=int, default=None, help="trial arrival bins (default: nbin / 2)")
+    c.add_argument("--alpha", type=float, nargs="+", default=list(SCAT_ALPHAS), help="the trial indices of tau ~ nu^-alpha (1..32 values)")
+    c.add_argument("--snr-min", type=float, default=5.0, help="subbands below this S/N stay out of the band fit")
+    c.add_argument("--off-gap", type=int, default=None, help="rows between the burst and each off-pulse window (default: 2 widths, at least 16)")
+    c.add_argument("--off-len", type=int, default=None, help="rows of each off-pulse window (default 1024)")
+    c.add_argument("--flag", default=None, help="flag file: channels left out")
+    c.add_argument("--coherency", action="store_true", help="the file holds the -d4 products: PP + QQ is used")
+    c.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     a = ap.parse_args(argv)
-    if a.cmd == "burstacf":
+    if a.cmd == "scatter":
+        if a.dm_from:
+            bursts = list(bursts_from_dm(a.dm_from, a.dm_kind))
+        else:
+            tsamp = sigproc.read_fil(a.fil).header["tsamp"]
+            centres = list(a.sample or []) + [int(round(t / tsamp)) for t in (a.time or [])]
+            widths, dms = a.width or [], a.dm or []
+            if not centres or len(centres) != len(dms) or len(widths) not in (1, len(centres)):
+                raise InputError("scatter: one --sample or --time per --dm, and --width once or once per burst (or --dm-from)")
+            bursts = [(dm, s, widths[i if len(widths) > 1 else 0]) for i, (dm, s) in enumerate(zip(dms, centres))]
+        bank = scat_bank_params(a.nsig, a.ntau, a.ntap, a.lead, a.sigma0, a.rsig, a.tau0, a.rtau)
+        files, _sc = burstscat_fil(a.fil, bursts, nbin=a.nbin, tfactor=a.tfactor, ffactor=a.ffactor, bank=bank, shift0=a.shift0, nshift=a.nshift,
+                                   alphas=a.alpha, snr_min=a.snr_min, off_gap=a.off_gap, off_len=a.off_len, flag_file=a.flag,
+                                   products="coherency" if a.coherency else "stokes", device=a.device)
+        for path in files:
+            print("wrote", path)
+        print(open(files[1]).read(), end="")
+    elif a.cmd == "burstacf":
         if a.dm_from:
             bursts = list(bursts_from_dm(a.dm_from, a.dm_kind))
         else:

@@ -1103,6 +1103,131 @@ int frbch_burstacf_host(const frbch_fil_desc* fil, const void* rows, uint64_t nr
                         const frbch_acf_fit_params* fp, int device, int64_t* Y, uint32_t* yhits, int64_t* A, uint32_t* P,
                         frbch_acf_result* results, uint8_t* used, uint32_t* kernel_used, char* err, size_t err_cap);
 
+/* ---- scattering of a burst: a bank of scattered Gaussians fitted to every subband, tau(nu) across the band ---------
+ * The stages above measure where a burst is and how wide; none fits a pulse SHAPE.  This one fits a Gaussian convolved with
+ * a one-sided exponential -- the thin-screen scattering tail -- to every subband of the dedispersed dynamic spectrum by
+ * correlating the subband's profile with a bank of templates at every trial arrival bin, and then tau(nu) = tau_ref
+ * (nu / nu_ref)^-alpha across the band.  frbch_burst_cand, frbch_burst_params, the window, the host preparation, the dynamic
+ * spectrum Y, yhits, the complete cells, the 0 / 1 plane `mask` and the quantised plane y (|y| <= 2^21, shift r_i) are those of
+ * the section above -- the same functions, the same bits; tests/scat_oracle.py restates what follows in numpy.
+ *
+ * Bank (frbch_scat_bank, host only, nothing runs on the device).  sigma_0 = sigma0, sigma_a = sigma_(a-1) rsig, a < nsig;
+ *    tau_0 = tau0, tau_b = tau_(b-1) rtau, b < ntau; both in bins, rsig, rtau > 1.  Template k = a ntau + b, K = nsig ntau.
+ *    g[j] = exp(-(d d) / (2 (sigma sigma))), d = (double)(j - lead), j < ntap: a Gaussian with its centre at tap `lead`;
+ *    e[n] = exp(-(double)n / tau), n >= 0;  f[m] = the sum over n = 0 .. m, ascending from 0.0, of g[m - n] e[n].  Double,
+ *    every operation rounded on its own, no FMA; only exp comes from libm.  fmax = the largest f;
+ *    p_k[m] (int32) = rint((f[m] / fmax) 32768.0), 0 <= p <= 2^15;  S1_k (int64) = the sum of p;  cum_k[m] (int64), m = 0 ..
+ *    ntap, = the sum of p[m'] p[m'] over m' < m (cum[0] = 0);  tail_k = f[ntap - 1] / fmax, the last tap's share of the peak:
+ *    a caller sees a truncated tail there.  exp is libm's, so two machines may differ in a last bit of f and, rarely, in a
+ *    unit of p: everything below takes the bank as it is, and the Python side takes it from this library.
+ * 1. Stage (device; frbch_tbank_* are this stage alone).  For planes y [n][nsub][nbin] (int32) and a bank P [ntemp][ntap] (int32):
+ *      C[i][s][k][u] (int64) = the sum over m < ntap of y[i][s][shift0 + u - lead + m] P[k][m],  u < nshift:
+ *    the template's Gaussian centre laid on bin shift0 + u.  Terms whose bin lies outside 0 .. nbin - 1 are absent.
+ *    Contract: |y| <= 2^21, |P| <= 2^30, ntap <= 1024: every sum is below 2^21 2^30 2^10 = 2^61 and exact in any order.
+ *    frbch_tbank_host checks the contract and refuses; frbch_tbank_device cannot look.  Limits: n, nsub >= 1, nbin 1..1024,
+ *    ntap 1..1024, lead < ntap, ntemp 1..4096, nshift >= 1, shift0 + nshift <= nbin, n nsub nbin <= 2^24, n nsub ntemp nshift
+ *    <= 2^24.  Direct sums, not an FFT: exact integers.
+ * 2. Composite (frbch_burstscat_*).  The preparation at cand.dm, Y, yhits, mask, y as above;  C = the stage on y with p;
+ *    N[i][s][k][u] (int64) = the stage on the 0 / 1 plane with the squared bank p p (<= 2^30): the template's energy over the
+ *    complete cells it covers.  When every cell of every candidate of the call is complete the library writes the closed form
+ *    cum_k[hi] - cum_k[lo], lo = max(0, lead - shift0 - u), hi = min(ntap, nbin - (shift0 + u - lead)), instead; the two are
+ *    equal.  In the composite the products are small (|C| < 2^46, N < 2^40).
+ * 3. Fit (frbch_burstscat_fit, host only; double, every operation rounded on its own, no FMA, fixed loop order, ties to the
+ *    lowest index; only log, exp and sqrt come from libm).
+ *    Noise scale.  The DM scan's boxcar S/N divides a sum of X 2^-k over H samples by sqrt(H): a term of one row of one used
+ *      channel has unit variance.  A complete cell of subband s holds tfactor nused_s of them and y = Y 2^-r, so
+ *      v_s = ((double)tfactor (double)nused_s) 2^(2 (k_i - r_i)) is the variance of a complete cell in units of y.
+ *      q[s][k][u] = (((double)C (double)C) / (double)N) / v_s, and 0 where N = 0 or C <= 0 or nused_s = 0: the drop of chi^2 of
+ *      the least-squares amplitude C / N of template k at shift u (negative amplitudes are not bursts).
+ *    Per subband (frbch_scat_sub).  The first largest q over k, then u, ascending; all of q zero: the record stays zero but for
+ *      nused and freq_mhz.  sigma, tau (bins) of template k; arrival = (double)(shift0 + u), bins from the window's first;
+ *      unit = ((double)tfactor tsamp) 1000: sigma_ms, tau_ms, arrival_ms = the three times unit;  amp = (C / N) 2^(15 - (k_i -
+ *      r_i)), the fitted template's peak in the DM scan's units;  area = ((C / N) (double)S1_k) 2^-(k_i - r_i);  snr = sqrt(q).
+ *      prof[b] = the largest q over (a, u) at tau_b.  tau_lo / tau_hi (ms) = the smallest / largest tau_b with prof[b] >= q -
+ *      1;  bounded_lo = 0 where that is b = 0, bounded_hi = 0 where it is b = ntau - 1, else 1;  dq_unscattered = q - prof[0].
+ *    Band (frbch_scat_band).  Subbands with snr >= snr_min take part (nfit of them; none: the record stays zero but for k, r,
+ *      nused, nu_ref).  nu_s = fch1 + ((double)(s ffactor) + (double)(ffactor - 1) / 2.0) foff;  nu_ref = fch1 + ((double)(nchan
+ *      - 1) / 2.0) foff.  d_s(alpha) = rint(((-alpha) log(nu_s / nu_ref)) / log(rtau)).  For every alpha of the list, in its
+ *      order, every b_ref < ntau, every a < nsig, every u < nshift:
+ *        Q = the sum over the participating s, ascending from 0.0, of q[s][a ntau + clip(b_ref + d_s(alpha), 0, ntau - 1)][u].
+ *      The first largest Q gives alpha, tau_ref = tau_(b_ref), sigma_a, the arrival; nclipped = the participating subbands whose
+ *      b_ref + d_s left 0 .. ntau - 1 there.  tau_ref_lo / _hi (ms) = the smallest / largest tau_b whose largest Q over (alpha,
+ *      a, u) is >= Q - 1, bounded_lo / _hi as above;  alpha_lo / _hi = the smallest / largest listed alpha whose largest Q over
+ *      (b_ref, a, u) is >= Q - 1 (with one alpha: that alpha).  ONE sigma and ONE arrival bin for all subbands is an assumption
+ *      of the band fit: a residual DM error or a frequency-dependent width goes into alpha.
+ *    No claim beyond these profile intervals: they are the grid points within 1 of the maximum of a chi^2 drop profiled over
+ *    the other grid parameters, for the noise scale above; nothing accounts for the grid's step, for correlated noise, or for
+ *    a template that does not describe the burst.
+ *
+ * kernel_used[3] (may be NULL): the burst-sums kernel, the dynamic-spectrum kernel, the template-bank kernel; 1 = fast, 0 =
+ *    generic.  Template bank, fast: a workgroup owns a plane, sw <= 8 subbands and a run of templates; it stages the subbands'
+ *    lines, zero-padded so that the inner loop has no bounds, and the templates of its run into 64 KiB of the LDS; a thread
+ *    owns 8 consecutive shifts of one (subband, template) and walks the taps with a sliding register window; no join.  The
+ *    staging rule places every shape these entry points accept; not fast: more than 65535 planes, `form` =
+ *    FRBCH_TBANK_GENERIC (one thread per (plane, s, k, u); for comparing the two), the emulator build.  Both give the same bits.
+ * FRBCH_E_ARG (outputs untouched): a wrong `size`, the limits of the stage, ntap outside 1..1024, lead >= ntap, nsig ntau
+ * outside 1..4096, a grid value that is not finite and positive, rsig or rtau not > 1, sigma0 or tau0 < 0.25, nalpha outside
+ * 1..32, an alpha or snr_min that is not finite, and every refusal of the section above. */
+#define FRBCH_TBANK_PLAN 0u
+#define FRBCH_TBANK_GENERIC 1u
+typedef struct frbch_scat_bank_params { uint32_t size, nsig, ntau, ntap, lead, reserved[3]; double sigma0, rsig, tau0, rtau; } frbch_scat_bank_params;
+typedef struct frbch_tbank_shape { uint32_t size, nsub, nbin, ntemp, ntap, lead, shift0, nshift; } frbch_tbank_shape;
+typedef struct frbch_scat_params { uint32_t size, nbin, tfactor, ffactor, shift0, nshift, reserved[2]; } frbch_scat_params;
+typedef struct frbch_scat_fit_params { uint32_t size, nalpha; double snr_min; double alpha[32]; } frbch_scat_fit_params;
+typedef struct frbch_scat_sub {
+  double sigma, tau, arrival;               /* bins */
+  double sigma_ms, tau_ms, arrival_ms;
+  double amp, area, snr, q;
+  double tau_lo, tau_hi, dq_unscattered;    /* ms, ms, chi^2 */
+  double freq_mhz;
+  uint32_t k, u, nused, bounded_lo, bounded_hi, reserved;
+} frbch_scat_sub;
+typedef struct frbch_scat_band {
+  double tau_ref, tau_ref_ms, alpha, sigma, sigma_ms, arrival, arrival_ms, q;
+  double tau_ref_lo, tau_ref_hi, alpha_lo, alpha_hi;    /* ms, ms */
+  double nu_ref_mhz;
+  int32_t k;
+  uint32_t r, nused, nfit, nclipped, b_ref, a, u, ialpha, bounded_lo, bounded_hi, reserved;
+} frbch_scat_band;
+/* Host only: p (int32) [K][ntap], s1 (int64) [K], cum (int64) [K][ntap + 1], tail (double) [K], sigma (double) [nsig], tau
+ * (double) [ntau]; each may be NULL. */
+int frbch_scat_bank(const frbch_scat_bank_params* bp, int32_t* p, int64_t* s1, int64_t* cum, double* tail, double* sigma,
+                    double* tau, char* err, size_t err_cap);
+/* The plan rule of the stage (host only, nothing runs): 1 = fast, 0 = generic, < 0 = refused. */
+int frbch_tbank_kernel(uint32_t n, const frbch_tbank_shape* sh, uint32_t form);
+/* d_y [n][nsub][nbin] int32, d_P [ntemp][ntap] int32 and d_C [n][nsub][ntemp][nshift] int64 are device memory; d_y and d_P are
+ * never written.  Synchronised. */
+int frbch_tbank_device(const int32_t* d_y, const int32_t* d_P, uint32_t n, const frbch_tbank_shape* sh, uint32_t form, int device,
+                       int64_t* d_C, uint32_t* kernel_used, char* err, size_t err_cap);
+/* the same with host arrays; refuses a |y| above 2^21 or a |P| above 2^30 */
+int frbch_tbank_host(const int32_t* y, const int32_t* P, uint32_t n, const frbch_tbank_shape* sh, uint32_t form, int device,
+                     int64_t* C, uint32_t* kernel_used, char* err, size_t err_cap);
+/* Host only: q [ncand][nsub][K][nshift] (double), sub [ncand][nsub], band [ncand] from C and N (int64) of q's shape, k, r,
+ * nused [ncand] and nused_s [ncand][nsub]; q, sub and band may be NULL.  Only nchan, fch1_mhz, foff_mhz and tsamp_s of `fil`
+ * are looked at. */
+int frbch_burstscat_fit(const frbch_fil_desc* fil, const frbch_scat_params* par, const frbch_scat_bank_params* bp,
+                        const frbch_scat_fit_params* fp, uint32_t ncand, const int32_t* k, const uint32_t* r, const uint32_t* nused,
+                        const uint32_t* nused_s, const int64_t* C, const int64_t* N, double* q, frbch_scat_sub* sub,
+                        frbch_scat_band* band, char* err, size_t err_cap);
+/* The plan rules (host only, nothing runs): 0 and kernel_used[3] filled, or < 0 = refused; only the ADDRESS of d_rows is examined. */
+int frbch_burstscat_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                           const frbch_burst_cand* cands, uint32_t ncand, const frbch_scat_params* par,
+                           const frbch_scat_bank_params* bp, uint32_t* kernel_used);
+/* d_rows is device memory, never written; everything else is host memory: flag [nchan] (may be NULL) and the outputs Y (int64),
+ * yhits (uint32), y (int32) [ncand][nsub][nbin], C, N (int64) [ncand][nsub][K][nshift], sub [ncand][nsub], band [ncand], used
+ * [ncand][nchan], kernel_used[3] (each may be NULL).  One device scope. */
+int frbch_burstscat_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                           const frbch_burst_cand* cands, uint32_t ncand, const uint8_t* flag, const frbch_scat_params* par,
+                           const frbch_scat_bank_params* bp, const frbch_scat_fit_params* fp, int device, int64_t* Y,
+                           uint32_t* yhits, int32_t* y, int64_t* C, int64_t* N, frbch_scat_sub* sub, frbch_scat_band* band,
+                           uint8_t* used, uint32_t* kernel_used, char* err, size_t err_cap);
+/* the same with host rows: one upload */
+int frbch_burstscat_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* bpar,
+                         const frbch_burst_cand* cands, uint32_t ncand, const uint8_t* flag, const frbch_scat_params* par,
+                         const frbch_scat_bank_params* bp, const frbch_scat_fit_params* fp, int device, int64_t* Y,
+                         uint32_t* yhits, int32_t* y, int64_t* C, int64_t* N, frbch_scat_sub* sub, frbch_scat_band* band,
+                         uint8_t* used, uint32_t* kernel_used, char* err, size_t err_cap);
+
 /* ---- interference: block statistics, the mask, cleaned rows --------------------------------------
  * The reference carries a flag file through to Heimdall and FETCH (create_config.py:54-56 `-F/--flag`, frb.conf:50,
  * base2fil.sh:226,425-432, submit_job.py:117 `<Tel>.flag_<fmin>-<fmax>MHz_<nchan>chan`) and leaves making one to a person.
