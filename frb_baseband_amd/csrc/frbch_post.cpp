@@ -3316,6 +3316,62 @@ int burst_check(const frbch_fil_desc* fil, uint64_t nrows, const frbch_burst_par
   return FRBCH_OK;
 }
 
+// The checks that every windowed analysis of the family (profile, DM scan, burst ACF, scattering fit) makes on its rows and
+// its grid, in the family's one order: the float32 refusal, the size of the parameter block `P` (named `pname`), nbin, tfactor,
+// nchan and -- own.ffactor given -- ffactor.  An analysis's own refusals that stand between these keep their place: own.pre in
+// front of nbin, own.mid in front of nchan, each a function that returns its message or NULL (a NULL function: none).  The
+// first failing check decides the message.
+constexpr uint32_t kWinMaxBin = 1024, kWinMaxT = 512;
+template <class P> struct WindowOwn {
+  const char* (*pre)(const P&);
+  const char* (*mid)(const P&);
+  const uint32_t P::*ffactor;
+};
+template <class P>
+int window_check(const frbch_fil_desc* fil, const P* par, const char* what, const char* pname, const WindowOwn<P>& own, const PostErr& e) {
+  const char* msg;
+  if (fil->nbits == 32) return e.fail(FRBCH_E_ARG, std::string(what) + " is not built for float32 rows: its fixed-point scale needs a bound on the samples");
+  if (!par || par->size != sizeof(P)) return e.fail(FRBCH_E_ARG, std::string(pname) + ": wrong size");
+  if (own.pre && (msg = own.pre(*par)) != nullptr) return e.fail(FRBCH_E_ARG, msg);
+  if (par->nbin < 1 || par->nbin > kWinMaxBin) return e.fail(FRBCH_E_ARG, "nbin must be 1..1024");
+  if (par->tfactor < 1 || par->tfactor > kWinMaxT) return e.fail(FRBCH_E_ARG, "tfactor must be 1..512");
+  if (own.mid && (msg = own.mid(*par)) != nullptr) return e.fail(FRBCH_E_ARG, msg);
+  if (fil->nchan > kRmMaxChan) return e.fail(FRBCH_E_ARG, "more than 16384 channels");
+  if (own.ffactor && (par->*own.ffactor < 1 || par->*own.ffactor > fil->nchan || fil->nchan % (par->*own.ffactor))) return e.fail(FRBCH_E_ARG, "ffactor must be 1..nchan and divide nchan");
+  return FRBCH_OK;
+}
+
+// A _device entry point of the family from where its arguments have passed: the device check, the device made current, a
+// scope, then run(scope) -- the scope and what it holds are gone when this returns.
+template <class F> int burst_device_call(int device, const PostErr& e, F run) {
+  const int rc = post_check_device(device, e);
+  if (rc) return rc;
+  DeviceGuard dg(device);
+  PostScope ps;
+  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  return run(ps);
+}
+
+// The _host twin of a composite from where its arguments have passed: rows up, device_twin(d_rows), nothing else (the
+// outputs of a composite are host arrays already).
+template <class F> int burst_host_twin(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, int device, const PostErr& e, F device_twin) {
+  const int rc = post_check_device(device, e);
+  if (rc) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
+  return hs.run(e, "device memory for the rows", "upload rows", "download", [&]() { return device_twin(d_rows); });
+}
+
+// an optional output of an entry point: the caller's array gets the vector (or the kernel_used words), a NULL gets nothing
+template <class T, class V> void deliver(T* dst, const std::vector<V>& v) {
+  static_assert(sizeof(T) == sizeof(V), "deliver: the element sizes differ");
+  if (dst) memcpy((void*)dst, v.data(), v.size() * sizeof(V));
+}
+template <size_t N> void deliver(uint32_t* dst, const uint32_t (&k)[N]) {
+  if (dst) memcpy(dst, k, sizeof k);
+}
+
 struct BurstPlan {
   std::vector<BurstCand> cand;
   std::vector<int32_t> delays;                   // [ncand][nchan]
@@ -3351,6 +3407,48 @@ bool burst_fast_layout(const frbch_fil_desc* fil, const void* d_rows) {
 #endif
 }
 
+#ifndef FRBCH_NO_FAST
+// The smallest and largest delay of every 64-byte channel tile of a delay table [record][nchan] -> lo, hi [record][tile]: what
+// the fast profile, DM scan and dynamic spectrum kernels size their stage by (a record: a candidate, or a trial of one).
+struct TileScan {
+  uint32_t ntile = 0;
+  std::vector<int32_t> lo, hi;
+  // The bins of a run that a stage of `cap` rows holds behind the widest delay range that any tile spans over `trun`
+  // consecutive records of a candidate's `nt` -- the same for every workgroup; 0: not even one bin of tfactor rows fits.
+  int brun(uint32_t ncand, uint32_t nt, uint32_t trun, int64_t cap, uint32_t nbin, uint32_t tfactor) const {
+    int64_t range = 0;
+    for (uint32_t i = 0; i < ncand; ++i)
+      for (uint32_t k0 = 0; k0 < nt; k0 += trun)
+        for (uint32_t t = 0; t < ntile; ++t) {
+          int32_t a = INT32_MAX, b = INT32_MIN;
+          for (uint32_t k = k0; k < std::min(nt, k0 + trun); ++k) {
+            a = std::min(a, lo[((size_t)i * nt + k) * ntile + t]);
+            b = std::max(b, hi[((size_t)i * nt + k) * ntile + t]);
+          }
+          range = std::max<int64_t>(range, (int64_t)b - (int64_t)a);
+        }
+    if ((int64_t)tfactor + range > cap) return 0;
+    return (int)std::min<int64_t>((int64_t)nbin, (cap - range) / (int64_t)tfactor);
+  }
+};
+TileScan tile_scan(const frbch_fil_desc* fil, const std::vector<int32_t>& delays) {
+  TileScan ts;
+  const uint32_t ct = 64u / (uint32_t)(fil->nbits / 8);
+  const size_t nrec = delays.size() / fil->nchan;
+  ts.ntile = fil->nchan / ct;
+  ts.lo.resize(nrec * ts.ntile);
+  ts.hi.resize(nrec * ts.ntile);
+  for (size_t r = 0; r < nrec; ++r)
+    for (uint32_t t = 0; t < ts.ntile; ++t) {
+      const int32_t* d = delays.data() + r * fil->nchan + (size_t)t * ct;
+      const auto mm = std::minmax_element(d, d + ct);
+      ts.lo[r * ts.ntile + t] = *mm.first;
+      ts.hi[r * ts.ntile + t] = *mm.second;
+    }
+  return ts;
+}
+#endif
+
 // the launch of step 1 on the scope's stream; `plan` stays alive until the caller has synchronised
 int burst_launch(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const BurstPlan& plan, uint32_t ncand,
                  BurstSums* d_sums, bool fastk, PostScope& ps, const PostErr& e) {
@@ -3385,6 +3483,20 @@ int burst_launch(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, 
 bool rm_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
 bool rm_finitef(float x) { return fabsf(x) <= 3.402823466e38f; }
 
+// mean and variance of the off-pulse window of one (candidate, product, channel), off_hits >= 2 (host, double, no FMA): the
+// one statement of the operation order that the oracles restate bit for bit
+struct OffStat { double mean, var; };
+inline OffStat burst_off_stat(const frbch_burst_sums& s) {
+  POST_NO_CONTRACT
+  const double noff = (double)s.off_hits;
+  const double ss = s.off_sum * s.off_sum;
+  const double sn = ss / noff;
+  const double num = s.off_sumsq - sn;
+  double var = num / (noff - 1.0);
+  if (var < 0.0) var = 0.0;
+  return OffStat{s.off_sum / noff, var};
+}
+
 // spectra, noise and `used` from the sums (host, double, no FMA): step 1 of the header
 void burst_derive(const frbch_fil_desc* fil, uint32_t products, const frbch_burst_sums* sums, uint32_t ncand, const float* gain,
                   float* spec, float* noise, uint8_t* used) {
@@ -3401,16 +3513,12 @@ void burst_derive(const frbch_fil_desc* fil, uint32_t products, const frbch_burs
           ok = false;
         } else {
           const double g = gain ? (double)gain[pr * nchan + c] : 1.0;
-          const double non = (double)s.on_hits, noff = (double)s.off_hits;
-          const double mon = s.on_sum / non, moff = s.off_sum / noff;
-          const double d = mon - moff;
+          const double non = (double)s.on_hits;
+          const OffStat off = burst_off_stat(s);
+          const double mon = s.on_sum / non;
+          const double d = mon - off.mean;
           sp = (float)(d * g);
-          const double ss = s.off_sum * s.off_sum;
-          const double sn = ss / noff;
-          const double num = s.off_sumsq - sn;
-          double var = num / (noff - 1.0);
-          if (var < 0.0) var = 0.0;
-          const double vn = var / non;
+          const double vn = off.var / non;
           nz = (float)(sqrt(vn) * fabs(g));
           if (!rm_finitef(sp) || !rm_finitef(nz)) ok = false;
         }
@@ -3701,26 +3809,24 @@ extern "C" int frbch_burstspec_device(const frbch_fil_desc* fil, const void* d_r
   int rc = burst_check(fil, nrows, par, cands, ncand, e);
   if (rc) return rc;
   if (!d_rows || !d_sums) return e.fail(FRBCH_E_ARG, "null argument");
-  if ((rc = post_check_device(device, e)) != 0) return rc;
   const size_t n = (size_t)ncand * fil->nifs * fil->nchan;
   std::vector<frbch_burst_sums> sums;
   std::vector<float> sp(n), nz(n);
   std::vector<uint8_t> us((size_t)ncand * fil->nchan);
-  DeviceGuard dg(device);
-  PostScope ps;
-  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
-  rc = burst_run(fil, d_rows, nrows, par, cands, ncand, gain, (BurstSums*)d_sums, ps, &sums, sp.data(), nz.data(), us.data(), kernel_used, e);
+  rc = burst_device_call(device, e, [&](PostScope& ps) {
+    return burst_run(fil, d_rows, nrows, par, cands, ncand, gain, (BurstSums*)d_sums, ps, &sums, sp.data(), nz.data(), us.data(), kernel_used, e);
+  });
   if (rc) return rc;
-  if (spec) memcpy(spec, sp.data(), n * sizeof(float));
-  if (noise) memcpy(noise, nz.data(), n * sizeof(float));
-  if (used) memcpy(used, us.data(), us.size());
+  deliver(spec, sp);
+  deliver(noise, nz);
+  deliver(used, us);
   return FRBCH_OK;
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
 extern "C" int frbch_burstspec_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* par,
                                     const frbch_burst_cand* cands, uint32_t ncand, const float* gain, int device,
                                     frbch_burst_sums* sums, float* spec, float* noise, uint8_t* used, uint32_t* kernel_used,
-                                    char* err, size_t err_cap) {
+                                    char* err, size_t err_cap) try {
   PostErr e{err, err_cap};
   int rc = burst_check(fil, nrows, par, cands, ncand, e);
   if (rc) return rc;
@@ -3734,7 +3840,7 @@ extern "C" int frbch_burstspec_host(const frbch_fil_desc* fil, const void* rows,
   return hs.run(e, "device memory for the rows and the sums", "upload rows", "download sums", [&]() {
     return frbch_burstspec_device(fil, d_rows, nrows, par, cands, ncand, gain, device, d_sums, spec, noise, used, kernel_used, err, err_cap);
   });
-}
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
 extern "C" int frbch_rm_table(int32_t* out) {
   if (!out) return FRBCH_E_ARG;
@@ -3743,7 +3849,7 @@ extern "C" int frbch_rm_table(int32_t* out) {
 }
 
 extern "C" int frbch_rmsynth_kernel(const frbch_fil_desc* fil, const float* d_F, uint32_t ncand, const frbch_rm_params* par,
-                                    uint32_t* nsplit) {
+                                    uint32_t* nsplit) try {
   PostErr e{nullptr, 0};
   const int rc = rm_check(fil, ncand, par, e);
   if (rc) return rc;
@@ -3751,7 +3857,7 @@ extern "C" int frbch_rmsynth_kernel(const frbch_fil_desc* fil, const float* d_F,
   const RmPlanRule rule = rm_plan_rule(fil->nchan, ncand, par->nphi, d_F);
   if (nsplit) *nsplit = (uint32_t)rule.nsplit;
   return rule.fastk ? 1 : 0;
-}
+} catch (const std::bad_alloc&) { return FRBCH_E_NOMEM; }
 
 extern "C" int frbch_rmsynth_device(const frbch_fil_desc* fil, const float* d_q, const float* d_u, const uint8_t* d_used,
                                     uint32_t ncand, const frbch_rm_params* par, int device, float* d_F, uint32_t* kernel_used,
@@ -3760,26 +3866,25 @@ extern "C" int frbch_rmsynth_device(const frbch_fil_desc* fil, const float* d_q,
   int rc = rm_check(fil, ncand, par, e);
   if (rc) return rc;
   if (!d_q || !d_u || !d_used || !d_F) return e.fail(FRBCH_E_ARG, "null argument");
-  if ((rc = post_check_device(device, e)) != 0) return rc;
   const size_t n = (size_t)ncand * fil->nchan;
   std::vector<float> q(n), u(n);
   std::vector<uint8_t> used(n);
   RmPlan plan;
-  DeviceGuard dg(device);
-  PostScope ps;
-  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
-  POST_DEV(dev_d2h(q.data(), d_q, n * sizeof(float), ps.s), "download q");
-  POST_DEV(dev_d2h(u.data(), d_u, n * sizeof(float), ps.s), "download u");
-  POST_DEV(dev_d2h(used.data(), d_used, n, ps.s), "download used");
-  POST_DEV(dev_sync(ps.s), "sync");
-  if ((rc = rm_build(fil, q.data(), u.data(), used.data(), ncand, par, &plan, e)) != 0) return rc;
-  if ((rc = rm_launch(fil, ncand, par, plan, d_F, ps, kernel_used, e)) != 0) return rc;
-  POST_DEV(dev_sync(ps.s), "sync");         // (the host vectors the uploads read stay alive until here)
-  return FRBCH_OK;
+  return burst_device_call(device, e, [&](PostScope& ps) {
+    int rc;
+    POST_DEV(dev_d2h(q.data(), d_q, n * sizeof(float), ps.s), "download q");
+    POST_DEV(dev_d2h(u.data(), d_u, n * sizeof(float), ps.s), "download u");
+    POST_DEV(dev_d2h(used.data(), d_used, n, ps.s), "download used");
+    POST_DEV(dev_sync(ps.s), "sync");
+    if ((rc = rm_build(fil, q.data(), u.data(), used.data(), ncand, par, &plan, e)) != 0) return rc;
+    if ((rc = rm_launch(fil, ncand, par, plan, d_F, ps, kernel_used, e)) != 0) return rc;
+    POST_DEV(dev_sync(ps.s), "sync");       // (the host vectors the uploads read stay alive until here)
+    return (int)FRBCH_OK;
+  });
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
 extern "C" int frbch_rmsynth_host(const frbch_fil_desc* fil, const float* q, const float* u, const uint8_t* used, uint32_t ncand,
-                                  const frbch_rm_params* par, int device, float* F, uint32_t* kernel_used, char* err, size_t err_cap) {
+                                  const frbch_rm_params* par, int device, float* F, uint32_t* kernel_used, char* err, size_t err_cap) try {
   PostErr e{err, err_cap};
   int rc = rm_check(fil, ncand, par, e);
   if (rc) return rc;
@@ -3794,7 +3899,7 @@ extern "C" int frbch_rmsynth_host(const frbch_fil_desc* fil, const float* q, con
   float* d_F = hs.out(F, (size_t)ncand * par->nphi * 2 * sizeof(float));
   return hs.run(e, "device memory for the spectra and F", "upload spectra", "download F",
                 [&]() { return frbch_rmsynth_device(fil, d_q, d_u, d_used, ncand, par, device, d_F, kernel_used, err, err_cap); });
-}
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
 extern "C" int frbch_rm_peaks(const frbch_fil_desc* fil, const float* F, const uint8_t* used, const float* noise_q, const float* noise_u,
                               uint32_t ncand, const frbch_rm_params* par, frbch_rm_result* results, char* err, size_t err_cap) try {
@@ -3815,72 +3920,67 @@ extern "C" int frbch_burst_rm_device(const frbch_fil_desc* fil, const void* d_ro
   if (fil->nifs != 4) return e.fail(FRBCH_E_ARG, "the composite needs the four products of a full-Stokes file (nifs = 4)");
   if ((rc = rm_check(fil, ncand, par, e)) != 0) return rc;
   if (!d_rows || !spec || !noise || !used || !F || !results) return e.fail(FRBCH_E_ARG, "null argument");
-  if ((rc = post_check_device(device, e)) != 0) return rc;
   const size_t nchan = fil->nchan, n = (size_t)ncand * nchan;
   std::vector<frbch_burst_sums> sums;
   std::vector<float> q(n), u(n), nq(n), nu(n);
   RmPlan plan;
-  uint32_t k1 = 0, k2[2] = {0, 1};
-  DeviceGuard dg(device);
-  PostScope ps;
-  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
-  BurstSums* d_sums = nullptr;
-  float* d_F = nullptr;
-  POST_DEV(ps.alloc(&d_sums, n * 4 * sizeof(BurstSums)), "hipMalloc");
-  POST_DEV(ps.alloc(&d_F, (size_t)ncand * par->nphi * 2 * sizeof(float)), "hipMalloc");
-  if ((rc = burst_run(fil, d_rows, nrows, bpar, cands, ncand, gain, d_sums, ps, &sums, spec, noise, used, &k1, e)) != 0) return rc;
-  for (uint32_t i = 0; i < ncand; ++i)
-    for (size_t c = 0; c < nchan; ++c) {
-      if (flag && flag[c]) used[i * nchan + c] = 0;
-      q[i * nchan + c] = spec[((size_t)i * 4 + 1) * nchan + c];
-      u[i * nchan + c] = spec[((size_t)i * 4 + 2) * nchan + c];
-      nq[i * nchan + c] = noise[((size_t)i * 4 + 1) * nchan + c];
-      nu[i * nchan + c] = noise[((size_t)i * 4 + 2) * nchan + c];
-    }
-  if ((rc = rm_build(fil, q.data(), u.data(), used, ncand, par, &plan, e)) != 0) return rc;
-  if ((rc = rm_launch(fil, ncand, par, plan, d_F, ps, k2, e)) != 0) return rc;
-  POST_DEV(dev_d2h(F, d_F, (size_t)ncand * par->nphi * 2 * sizeof(float), ps.s), "download F");
-  POST_DEV(dev_sync(ps.s), "sync");
-  if (kernel_used) { kernel_used[0] = k1; kernel_used[1] = k2[0]; kernel_used[2] = k2[1]; }
+  uint32_t k[3] = {0, 0, 1};
+  rc = burst_device_call(device, e, [&](PostScope& ps) {
+    int rc;
+    BurstSums* d_sums = nullptr;
+    float* d_F = nullptr;
+    POST_DEV(ps.alloc(&d_sums, n * 4 * sizeof(BurstSums)), "hipMalloc");
+    POST_DEV(ps.alloc(&d_F, (size_t)ncand * par->nphi * 2 * sizeof(float)), "hipMalloc");
+    if ((rc = burst_run(fil, d_rows, nrows, bpar, cands, ncand, gain, d_sums, ps, &sums, spec, noise, used, &k[0], e)) != 0) return rc;
+    for (uint32_t i = 0; i < ncand; ++i)
+      for (size_t c = 0; c < nchan; ++c) {
+        if (flag && flag[c]) used[i * nchan + c] = 0;
+        q[i * nchan + c] = spec[((size_t)i * 4 + 1) * nchan + c];
+        u[i * nchan + c] = spec[((size_t)i * 4 + 2) * nchan + c];
+        nq[i * nchan + c] = noise[((size_t)i * 4 + 1) * nchan + c];
+        nu[i * nchan + c] = noise[((size_t)i * 4 + 2) * nchan + c];
+      }
+    if ((rc = rm_build(fil, q.data(), u.data(), used, ncand, par, &plan, e)) != 0) return rc;
+    if ((rc = rm_launch(fil, ncand, par, plan, d_F, ps, &k[1], e)) != 0) return rc;
+    POST_DEV(dev_d2h(F, d_F, (size_t)ncand * par->nphi * 2 * sizeof(float), ps.s), "download F");
+    POST_DEV(dev_sync(ps.s), "sync");
+    return (int)FRBCH_OK;
+  });
+  if (rc) return rc;
+  deliver(kernel_used, k);
   return rm_peaks_run(fil, F, used, nq.data(), nu.data(), ncand, par, results);
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
 extern "C" int frbch_burst_rm_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* bpar,
                                    const frbch_burst_cand* cands, uint32_t ncand, const float* gain, const uint8_t* flag,
                                    const frbch_rm_params* par, int device, float* spec, float* noise, uint8_t* used, float* F,
-                                   frbch_rm_result* results, uint32_t* kernel_used, char* err, size_t err_cap) {
+                                   frbch_rm_result* results, uint32_t* kernel_used, char* err, size_t err_cap) try {
   PostErr e{err, err_cap};
-  int rc = burst_check(fil, nrows, bpar, cands, ncand, e);
+  const int rc = burst_check(fil, nrows, bpar, cands, ncand, e);
   if (rc) return rc;
   if (!rows) return e.fail(FRBCH_E_ARG, "null argument");
-  if ((rc = post_check_device(device, e)) != 0) return rc;
-  DeviceGuard dg(device);
-  HostStage hs;
-  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
-  return hs.run(e, "device memory for the rows", "upload rows", "download", [&]() {
+  return burst_host_twin(fil, rows, nrows, device, e, [&](void* d_rows) {
     return frbch_burst_rm_device(fil, d_rows, nrows, bpar, cands, ncand, gain, flag, par, device, spec, noise, used, F, results, kernel_used, err, err_cap);
   });
-}
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // polarisation profile of a burst: derotated I, L, V and PA per time bin (include/frbch.h states the arithmetic)
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
-constexpr uint32_t kPolMaxBin = 1024, kPolMaxT = 512;
 constexpr uint64_t kPolMaxOut = 1ull << 22, kPolPartCap = 1ull << 30;
+
+const char* pol_bad_ref(const frbch_prof_params& p) {
+  return p.ref > FRBCH_PROF_REF_ZERO ? "ref must be 0 (the mean lambda^2) or 1 (lambda^2 = 0)" : nullptr;
+}
 
 int pol_check(const frbch_fil_desc* fil, uint64_t nrows, const frbch_burst_params* bpar, const frbch_burst_cand* cands,
               uint32_t ncand, const frbch_prof_params* par, const PostErr& e) {
   POST_NO_CONTRACT
-  const int rc = burst_check(fil, nrows, bpar, cands, ncand, e);
+  int rc = burst_check(fil, nrows, bpar, cands, ncand, e);
   if (rc) return rc;
   if (fil->nifs != 4) return e.fail(FRBCH_E_ARG, "the profile needs the four products of a full-Stokes file (nifs = 4)");
-  if (fil->nbits == 32) return e.fail(FRBCH_E_ARG, "the profile is not built for float32 rows: its fixed-point scale needs a bound on the samples");
-  if (!par || par->size != sizeof(frbch_prof_params)) return e.fail(FRBCH_E_ARG, "frbch_prof_params: wrong size");
-  if (par->nbin < 1 || par->nbin > kPolMaxBin) return e.fail(FRBCH_E_ARG, "nbin must be 1..1024");
-  if (par->tfactor < 1 || par->tfactor > kPolMaxT) return e.fail(FRBCH_E_ARG, "tfactor must be 1..512");
-  if (par->ref > FRBCH_PROF_REF_ZERO) return e.fail(FRBCH_E_ARG, "ref must be 0 (the mean lambda^2) or 1 (lambda^2 = 0)");
-  if (fil->nchan > kRmMaxChan) return e.fail(FRBCH_E_ARG, "more than 16384 channels");
+  if ((rc = window_check(fil, par, "the profile", "frbch_prof_params", {nullptr, pol_bad_ref, nullptr}, e)) != 0) return rc;
   if (!(fil->fch1_mhz + (double)(fil->nchan - 1) * fil->foff_mhz > 0)) return e.fail(FRBCH_E_ARG, "a channel frequency that is not positive");
   if ((uint64_t)ncand * par->nbin > kPolMaxOut) return e.fail(FRBCH_E_ARG, "ncand * nbin exceeds 2^22: cut the batch into several calls");
   return FRBCH_OK;
@@ -3895,28 +3995,19 @@ int pol_check_rm(const double* rm, uint32_t ncand, const PostErr& e) {
 
 // The plan rule of the profile -- the one decision behind frbch_polprof_device's launches, kernel_used[1] and
 // frbch_polprof_kernel's answer.  The fast kernel wants the layout of the fast burst-sums kernel (only the ADDRESS of d_rows
-// is examined), room in its stage for one bin behind the largest delay spread of any 64-byte tile of any candidate
-// (tfactor + spread <= kPpSpan rows), and partials of at most 2^30 bytes; brun = the bins of a run that then fit, the same
-// for every workgroup.  The emulator build has no such kernel: generic.
+// is examined), room in its stage of kPpSpan rows for one bin behind the largest delay spread of any 64-byte tile of any
+// candidate (tile_scan, TileScan::brun, which gives the bins of a run as well), and partials of at most 2^30 bytes.  The
+// emulator build has no such kernel: generic.
 struct PolPlanRule { bool fastk; int brun, ntile; };
 PolPlanRule pol_plan_rule(const frbch_fil_desc* fil, const void* d_rows, const std::vector<int32_t>& delays, uint32_t ncand,
                           const frbch_prof_params* par) {
   PolPlanRule r{false, 0, 0};
 #ifndef FRBCH_NO_FAST
   if (!burst_fast_layout(fil, d_rows)) return r;
-  const uint32_t ct = 64u / (uint32_t)(fil->nbits / 8), ntile = fil->nchan / ct;
-  int64_t spread = 0;
-  for (uint32_t i = 0; i < ncand; ++i)
-    for (uint32_t t = 0; t < ntile; ++t) {
-      const int32_t* d = delays.data() + (size_t)i * fil->nchan + (size_t)t * ct;
-      const auto mm = std::minmax_element(d, d + ct);
-      spread = std::max<int64_t>(spread, (int64_t)*mm.second - (int64_t)*mm.first);
-    }
-  if ((int64_t)par->tfactor + spread > (int64_t)fast::kPpSpan) return r;
-  if ((uint64_t)ncand * ntile * par->nbin * 36ull > kPolPartCap) return r;
-  r.fastk = true;
-  r.brun = (int)std::min<int64_t>((int64_t)par->nbin, ((int64_t)fast::kPpSpan - spread) / (int64_t)par->tfactor);
-  r.ntile = (int)ntile;
+  const TileScan ts = tile_scan(fil, delays);
+  const int brun = ts.brun(ncand, 1, 1, (int64_t)fast::kPpSpan, par->nbin, par->tfactor);
+  if (!brun || (uint64_t)ncand * ts.ntile * par->nbin * 36ull > kPolPartCap) return r;
+  r = PolPlanRule{true, brun, (int)ts.ntile};
 #else
   (void)fil; (void)d_rows; (void)delays; (void)ncand; (void)par;
 #endif
@@ -4004,18 +4095,12 @@ int pol_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const
       q.used = 1;
       double w[4];
       for (size_t p = 0; p < 4; ++p) {
-        const frbch_burst_sums& s = sums[((size_t)i * 4 + p) * nchan + c];
-        const double noff = (double)s.off_hits;
+        const OffStat off = burst_off_stat(sums[((size_t)i * 4 + p) * nchan + c]);
         const double g = gain ? (double)gain[p * nchan + c] : 1.0;
-        q.mean[p] = s.off_sum / noff;
+        q.mean[p] = off.mean;
         q.g[p] = g;
-        const double ss = s.off_sum * s.off_sum;
-        const double sn = ss / noff;
-        const double num = s.off_sumsq - sn;
-        double var = num / (noff - 1.0);
-        if (var < 0.0) var = 0.0;
         const double gg = g * g;
-        w[p] = gg * var;
+        w[p] = gg * off.var;
       }
       if (coh) {
         const double wi = w[0] + w[1];
@@ -4139,20 +4224,15 @@ extern "C" int frbch_polprof_device(const frbch_fil_desc* fil, const void* d_row
   if (rc) return rc;
   if (!d_rows) return e.fail(FRBCH_E_ARG, "null argument");
   if ((rc = pol_check_rm(rm, ncand, e)) != 0) return rc;
-  if ((rc = post_check_device(device, e)) != 0) return rc;
   PolOut out;
-  {
-    DeviceGuard dg(device);
-    PostScope ps;
-    if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
-    if ((rc = pol_run(fil, d_rows, nrows, bpar, cands, ncand, rm, gain, flag, par, ps, &out, e)) != 0) return rc;
-  }
-  if (acc) memcpy(acc, out.acc.data(), out.acc.size() * sizeof(long long));
-  if (hits) memcpy(hits, out.hits.data(), out.hits.size() * sizeof(uint32_t));
-  if (bins) memcpy((void*)bins, out.bins.data(), out.bins.size() * sizeof(frbch_prof_bin));
-  if (results) memcpy((void*)results, out.res.data(), out.res.size() * sizeof(frbch_prof_result));
-  if (used) memcpy(used, out.used.data(), out.used.size());
-  if (kernel_used) { kernel_used[0] = out.k[0]; kernel_used[1] = out.k[1]; }
+  rc = burst_device_call(device, e, [&](PostScope& ps) { return pol_run(fil, d_rows, nrows, bpar, cands, ncand, rm, gain, flag, par, ps, &out, e); });
+  if (rc) return rc;
+  deliver(acc, out.acc);
+  deliver(hits, out.hits);
+  deliver(bins, out.bins);
+  deliver(results, out.res);
+  deliver(used, out.used);
+  deliver(kernel_used, out.k);
   return FRBCH_OK;
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
@@ -4160,39 +4240,34 @@ extern "C" int frbch_polprof_host(const frbch_fil_desc* fil, const void* rows, u
                                   const frbch_burst_cand* cands, uint32_t ncand, const double* rm, const float* gain,
                                   const uint8_t* flag, const frbch_prof_params* par, int device, int64_t* acc, uint32_t* hits,
                                   frbch_prof_bin* bins, frbch_prof_result* results, uint8_t* used, uint32_t* kernel_used,
-                                  char* err, size_t err_cap) {
+                                  char* err, size_t err_cap) try {
   PostErr e{err, err_cap};
   int rc = pol_check(fil, nrows, bpar, cands, ncand, par, e);
   if (rc) return rc;
   if (!rows) return e.fail(FRBCH_E_ARG, "null argument");
   if ((rc = pol_check_rm(rm, ncand, e)) != 0) return rc;
-  if ((rc = post_check_device(device, e)) != 0) return rc;
-  DeviceGuard dg(device);
-  HostStage hs;
-  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
-  return hs.run(e, "device memory for the rows", "upload rows", "download", [&]() {
+  return burst_host_twin(fil, rows, nrows, device, e, [&](void* d_rows) {
     return frbch_polprof_device(fil, d_rows, nrows, bpar, cands, ncand, rm, gain, flag, par, device, acc, hits, bins, results, used, kernel_used, err, err_cap);
   });
-}
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // DM of a burst: fine DM scan, S/N and structure maxima (include/frbch.h states the arithmetic)
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
-constexpr uint32_t kDmMaxTrial = 4096, kDmMaxBin = 1024, kDmMaxTf = 512, kDmMaxWidths = 16;
+constexpr uint32_t kDmMaxTrial = 4096, kDmMaxWidths = 16;
 constexpr uint64_t kDmMaxOut = 1ull << 24, kDmPartCap = 1ull << 30;
+
+const char* dm_bad_ntrial(const frbch_dmscan_params& p) { return p.ntrial < 1 || p.ntrial > kDmMaxTrial ? "ntrial must be 1..4096" : nullptr; }
+const char* dm_bad_ddm(const frbch_dmscan_params& p) {
+  return p.ntrial > 1 && (!(p.ddm > 0.0) || !rm_finite(p.ddm)) ? "ddm must be finite and above 0" : nullptr;
+}
 
 int dm_check(const frbch_fil_desc* fil, uint64_t nrows, const frbch_burst_params* bpar, const frbch_burst_cand* cands,
              uint32_t ncand, const frbch_dmscan_params* par, const PostErr& e) {
-  const int rc = burst_check(fil, nrows, bpar, cands, ncand, e);
+  int rc = burst_check(fil, nrows, bpar, cands, ncand, e);
   if (rc) return rc;
-  if (fil->nbits == 32) return e.fail(FRBCH_E_ARG, "the DM scan is not built for float32 rows: its fixed-point scale needs a bound on the samples");
-  if (!par || par->size != sizeof(frbch_dmscan_params)) return e.fail(FRBCH_E_ARG, "frbch_dmscan_params: wrong size");
-  if (par->ntrial < 1 || par->ntrial > kDmMaxTrial) return e.fail(FRBCH_E_ARG, "ntrial must be 1..4096");
-  if (par->nbin < 1 || par->nbin > kDmMaxBin) return e.fail(FRBCH_E_ARG, "nbin must be 1..1024");
-  if (par->tfactor < 1 || par->tfactor > kDmMaxTf) return e.fail(FRBCH_E_ARG, "tfactor must be 1..512");
-  if (par->ntrial > 1 && (!(par->ddm > 0.0) || !rm_finite(par->ddm))) return e.fail(FRBCH_E_ARG, "ddm must be finite and above 0");
-  if (fil->nchan > kRmMaxChan) return e.fail(FRBCH_E_ARG, "more than 16384 channels");
+  if ((rc = window_check(fil, par, "the DM scan", "frbch_dmscan_params", {dm_bad_ntrial, dm_bad_ddm, nullptr}, e)) != 0) return rc;
   if ((uint64_t)ncand * par->ntrial * fil->nchan > kCutTableCap) return e.fail(FRBCH_E_ARG, "ncand * ntrial * nchan exceeds 2^26: cut the batch or the scan");
   if ((uint64_t)ncand * par->ntrial * par->nbin > kDmMaxOut) return e.fail(FRBCH_E_ARG, "ncand * ntrial * nbin exceeds 2^24: cut the batch or the scan");
   return FRBCH_OK;
@@ -4241,46 +4316,27 @@ int dm_build(const frbch_fil_desc* fil, const frbch_burst_cand* cands, uint32_t 
 // The plan rule of the scan -- the one decision behind frbch_dmscan_device's launches, kernel_used[1] and
 // frbch_dmscan_kernel's answer.  The fast kernel wants the layout of the fast burst-sums kernel (only the ADDRESS of d_rows is
 // examined), bins of at most kDmMaxT rows, a trial run -- the largest of 16, 8, 4, 2, 1 within ntrial -- whose delay range
-// over any 64-byte tile of any candidate leaves room for one bin in the stage (tfactor + range <= kDmLds / (64 products)
-// rows), and partials of at most 2^30 bytes; brun = the bins of a run that then fit, the same for every workgroup.  The
-// emulator build has no such kernel: generic.
+// over any 64-byte tile of any candidate leaves room for one bin in the stage (tile_scan, dm_stage_brun), and partials of at
+// most 2^30 bytes.  The emulator build has no such kernel: generic.
 struct DmPlanRule { bool fastk; int trun, brun, ntile; };
+#ifndef FRBCH_NO_FAST
+// the bins of a run of the fast DM scan kernel's stage (kDmLds / (64 products) rows) at a trial run of `trun`; 0: none fits
+int dm_stage_brun(const TileScan& ts, uint32_t products, uint32_t ncand, uint32_t ntrial, uint32_t trun, uint32_t nbin, uint32_t tfactor) {
+  const int64_t cap = (int64_t)(fast::kDmLds / (64u * (products == FRBCH_BURST_COHERENCY ? 2u : 1u)));
+  return ts.brun(ncand, ntrial, trun, cap, nbin, tfactor);
+}
+#endif
 DmPlanRule dm_plan_rule(const frbch_fil_desc* fil, const void* d_rows, uint32_t products, const std::vector<int32_t>& delays,
                         uint32_t ncand, const frbch_dmscan_params* par) {
   DmPlanRule r{false, 0, 0, 0};
 #ifndef FRBCH_NO_FAST
   if (!burst_fast_layout(fil, d_rows) || par->tfactor > (uint32_t)fast::kDmMaxT) return r;
-  const uint32_t ct = 64u / (uint32_t)(fil->nbits / 8), ntile = fil->nchan / ct, nt = par->ntrial;
-  const int64_t cap = (int64_t)(fast::kDmLds / (64u * (products == FRBCH_BURST_COHERENCY ? 2u : 1u)));
-  if ((uint64_t)ncand * ntile * nt * par->nbin * 12ull > kDmPartCap) return r;
-  // smallest and largest delay of every (candidate, trial, tile)
-  std::vector<int32_t> lo((size_t)ncand * nt * ntile), hi(lo.size());
-  for (size_t ik = 0; ik < (size_t)ncand * nt; ++ik)
-    for (uint32_t t = 0; t < ntile; ++t) {
-      const int32_t* d = delays.data() + ik * fil->nchan + (size_t)t * ct;
-      const auto mm = std::minmax_element(d, d + ct);
-      lo[ik * ntile + t] = *mm.first;
-      hi[ik * ntile + t] = *mm.second;
-    }
+  const TileScan ts = tile_scan(fil, delays);
+  if ((uint64_t)ncand * ts.ntile * par->ntrial * par->nbin * 12ull > kDmPartCap) return r;
   for (uint32_t trun = (uint32_t)fast::kDmTrun; trun >= 1; trun /= 2) {
-    if (trun > nt && trun > 1) continue;
-    int64_t range = 0;
-    for (uint32_t i = 0; i < ncand; ++i)
-      for (uint32_t k0 = 0; k0 < nt; k0 += trun)
-        for (uint32_t t = 0; t < ntile; ++t) {
-          int32_t a = INT32_MAX, b = INT32_MIN;
-          for (uint32_t k = k0; k < std::min(nt, k0 + trun); ++k) {
-            a = std::min(a, lo[((size_t)i * nt + k) * ntile + t]);
-            b = std::max(b, hi[((size_t)i * nt + k) * ntile + t]);
-          }
-          range = std::max<int64_t>(range, (int64_t)b - (int64_t)a);
-        }
-    if ((int64_t)par->tfactor + range > cap) continue;
-    r.fastk = true;
-    r.trun = (int)trun;
-    r.brun = (int)std::min<int64_t>((int64_t)par->nbin, (cap - range) / (int64_t)par->tfactor);
-    r.ntile = (int)ntile;
-    return r;
+    if (trun > par->ntrial && trun > 1) continue;
+    const int brun = dm_stage_brun(ts, products, ncand, par->ntrial, trun, par->nbin, par->tfactor);
+    if (brun) return DmPlanRule{true, (int)trun, brun, (int)ts.ntile};
   }
 #else
   (void)fil; (void)d_rows; (void)products; (void)delays; (void)ncand; (void)par;
@@ -4445,19 +4501,16 @@ int dm_prepare(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, co
   const bool coh = bpar->products == FRBCH_BURST_COHERENCY;
   const uint32_t p0 = coh ? 0u : fil->product, np = coh ? 2u : 1u;
   out->p0 = p0; out->np = np;
-  std::vector<DmRec>& rec = out->rec;
-  std::vector<DmCand>& dc = out->dc;
-  std::vector<int32_t>& kscale = out->kscale;
-  std::vector<uint32_t>& nused = out->nused;
-  rec.resize(n);
-  dc.resize(ncand);
-  kscale.assign(ncand, 0);
-  nused.assign(ncand, 0);
-  memset((void*)rec.data(), 0, n * sizeof(DmRec));
+  out->rec.resize(n);
+  out->dc.resize(ncand);
+  out->kscale.assign(ncand, 0);
+  out->nused.assign(ncand, 0);
+  memset((void*)out->rec.data(), 0, n * sizeof(DmRec));
   out->used.assign(n, 0);
   for (uint32_t i = 0; i < ncand; ++i) {
-    dc[i].t0 = (long long)cands[i].sample - (long long)(par_nbin / 2) * (long long)par_tfactor;
-    dc[i].scale = 0.0;
+    DmCand& dc = out->dc[i];
+    dc.t0 = (long long)cands[i].sample - (long long)(par_nbin / 2) * (long long)par_tfactor;
+    dc.scale = 0.0;
     double wmax = 0.0;
     for (size_t c = 0; c < nchan; ++c) {
       bool ok = !(flag && flag[c]);
@@ -4465,32 +4518,26 @@ int dm_prepare(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, co
       for (uint32_t p = p0; p < p0 + np; ++p) {
         const frbch_burst_sums& s = sums[((size_t)i * nifs + p) * nchan + c];
         if (s.on_hits == 0 || s.off_hits < 2) { ok = false; break; }
-        const double noff = (double)s.off_hits;
-        const double mp = s.off_sum / noff;
-        const double ss = s.off_sum * s.off_sum;
-        const double sn = ss / noff;
-        const double num = s.off_sumsq - sn;
-        double vp = num / (noff - 1.0);
-        if (vp < 0.0) vp = 0.0;
-        mean = p == p0 ? mp : mean + mp;
-        var = p == p0 ? vp : var + vp;
+        const OffStat off = burst_off_stat(s);
+        mean = p == p0 ? off.mean : mean + off.mean;
+        var = p == p0 ? off.var : var + off.var;
       }
       if (!ok || !(var > 0.0)) continue;
-      DmRec& q = rec[(size_t)i * nchan + c];
+      DmRec& q = out->rec[(size_t)i * nchan + c];
       q.mean = mean;
       q.w = 1.0 / sqrt(var);
       q.used = 1;
       out->used[(size_t)i * nchan + c] = 1;
-      ++nused[i];
+      ++out->nused[i];
       wmax = std::max(wmax, q.w);
     }
-    if (!nused[i]) continue;
+    if (!out->nused[i]) continue;
     double M = ((double)par_tfactor * ldexp(1.0, fil->nbits)) * wmax;
     if (coh) M = 2.0 * M;
     int ex = 0;
     (void)frexp(M, &ex);
-    kscale[i] = 40 - ex;
-    dc[i].scale = ldexp(1.0, kscale[i]);
+    out->kscale[i] = 40 - ex;
+    dc.scale = ldexp(1.0, out->kscale[i]);
   }
   return FRBCH_OK;
 }
@@ -4509,11 +4556,6 @@ int dm_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const 
   DmPrep prep;
   if ((rc = dm_prepare(fil, d_rows, nrows, bpar, cands, ncand, flag, par->nbin, par->tfactor, ps, &prep, &out->k[0], e)) != 0) return rc;
   out->used.swap(prep.used);
-  const uint32_t p0 = prep.p0, np = prep.np;
-  const std::vector<DmRec>& rec = prep.rec;
-  const std::vector<DmCand>& dc = prep.dc;
-  const std::vector<int32_t>& kscale = prep.kscale;
-  const std::vector<uint32_t>& nused = prep.nused;
 
   // the launches
   DmRec* d_rec = nullptr;
@@ -4527,12 +4569,12 @@ int dm_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const 
   POST_DEV(ps.alloc(&d_dly, delays.size() * sizeof(int32_t)), "hipMalloc");
   POST_DEV(ps.alloc(&d_acc, nout * sizeof(long long)), "hipMalloc");
   POST_DEV(ps.alloc(&d_hits, nout * sizeof(uint32_t)), "hipMalloc");
-  POST_DEV(dev_h2d(d_rec, rec.data(), n * sizeof(DmRec), ps.s), "upload records");
-  POST_DEV(dev_h2d(d_dc, dc.data(), (size_t)ncand * sizeof(DmCand), ps.s), "upload records");
+  POST_DEV(dev_h2d(d_rec, prep.rec.data(), n * sizeof(DmRec), ps.s), "upload records");
+  POST_DEV(dev_h2d(d_dc, prep.dc.data(), (size_t)ncand * sizeof(DmCand), ps.s), "upload records");
   POST_DEV(dev_h2d(d_dly, delays.data(), delays.size() * sizeof(int32_t), ps.s), "upload delays");
   DmParams p = post_params<DmParams>(fil, d_rows, nrows);
   p.ncand = (int)ncand; p.cand = d_dc; p.rec = d_rec; p.delays = d_dly; p.acc = d_acc; p.hits = d_hits;
-  p.ntrial = (int)par->ntrial; p.nbin = (int)par->nbin; p.tfactor = (int)par->tfactor; p.p0 = (int)p0; p.np = (int)np;
+  p.ntrial = (int)par->ntrial; p.nbin = (int)par->nbin; p.tfactor = (int)par->tfactor; p.p0 = (int)prep.p0; p.np = (int)prep.np;
   p.ntile = rule.ntile; p.trun = rule.trun; p.brun = rule.brun;
   out->k[1] = rule.fastk ? 1 : 0;
   bool launched = false;
@@ -4544,7 +4586,7 @@ int dm_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const 
     POST_DEV(ps.alloc(&d_part, npart * sizeof(long long)), "hipMalloc");
     POST_DEV(ps.alloc(&d_hpart, npart * sizeof(uint32_t)), "hipMalloc");
     p.part = d_part; p.hpart = d_hpart;
-    const bool coh = np == 2;
+    const bool coh = prep.np == 2;
     const unsigned nbr = (unsigned)((par->nbin + rule.brun - 1) / rule.brun), ntr = (unsigned)((par->ntrial + rule.trun - 1) / rule.trun);
     const dim3 grid((unsigned)rule.ntile * nbr, ntr, ncand), block(fast::kDmThreads);
     int lrc;
@@ -4568,7 +4610,7 @@ int dm_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const 
   POST_DEV(dev_d2h(out->acc.data(), d_acc, nout * sizeof(long long), ps.s), "download DM scan");
   POST_DEV(dev_d2h(out->hits.data(), d_hits, nout * sizeof(uint32_t), ps.s), "download DM scan");
   POST_DEV(dev_sync(ps.s), "sync");
-  dm_peaks(par, pk, dms, ncand, kscale.data(), nused.data(), (const int64_t*)out->acc.data(), out->hits.data(), &out->cv);
+  dm_peaks(par, pk, dms, ncand, prep.kscale.data(), prep.nused.data(), (const int64_t*)out->acc.data(), out->hits.data(), &out->cv);
   return FRBCH_OK;
 }
 }  // namespace
@@ -4597,9 +4639,9 @@ extern "C" int frbch_dmscan_peaks(const frbch_dmscan_params* par, const frbch_dm
                                   size_t err_cap) try {
   PostErr e{err, err_cap};
   if (!par || par->size != sizeof(frbch_dmscan_params)) return e.fail(FRBCH_E_ARG, "frbch_dmscan_params: wrong size");
-  if (par->ntrial < 1 || par->ntrial > kDmMaxTrial) return e.fail(FRBCH_E_ARG, "ntrial must be 1..4096");
-  if (par->nbin < 1 || par->nbin > kDmMaxBin) return e.fail(FRBCH_E_ARG, "nbin must be 1..1024");
-  if (par->ntrial > 1 && (!(par->ddm > 0.0) || !rm_finite(par->ddm))) return e.fail(FRBCH_E_ARG, "ddm must be finite and above 0");
+  if (dm_bad_ntrial(*par)) return e.fail(FRBCH_E_ARG, dm_bad_ntrial(*par));
+  if (par->nbin < 1 || par->nbin > kWinMaxBin) return e.fail(FRBCH_E_ARG, "nbin must be 1..1024");
+  if (dm_bad_ddm(*par)) return e.fail(FRBCH_E_ARG, dm_bad_ddm(*par));
   if (!cands || ncand < 1 || ncand > kBurstMaxCand) return e.fail(FRBCH_E_ARG, "1..4096 candidates");
   if ((uint64_t)ncand * par->ntrial * par->nbin > kDmMaxOut) return e.fail(FRBCH_E_ARG, "ncand * ntrial * nbin exceeds 2^24: cut the batch or the scan");
   int rc = dm_check_peaks(par, pk, e);
@@ -4609,12 +4651,11 @@ extern "C" int frbch_dmscan_peaks(const frbch_dmscan_params* par, const frbch_dm
   if ((rc = dm_trials(cands, ncand, par, &dms, e)) != 0) return rc;
   DmCurves cv;
   dm_peaks(par, pk, dms, ncand, k, nused, acc, hits, &cv);
-  const size_t n = (size_t)ncand * par->ntrial;
-  if (snr) memcpy(snr, cv.snr.data(), n * sizeof(double));
-  if (strc) memcpy(strc, cv.strc.data(), n * sizeof(double));
-  if (width) memcpy(width, cv.width.data(), n * sizeof(uint32_t));
-  if (bin) memcpy(bin, cv.bin.data(), n * sizeof(uint32_t));
-  if (results) memcpy((void*)results, cv.res.data(), (size_t)ncand * sizeof(frbch_dmscan_result));
+  deliver(snr, cv.snr);
+  deliver(strc, cv.strc);
+  deliver(width, cv.width);
+  deliver(bin, cv.bin);
+  deliver(results, cv.res);
   return FRBCH_OK;
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
@@ -4634,22 +4675,16 @@ extern "C" int frbch_dmscan_device(const frbch_fil_desc* fil, const void* d_rows
     std::vector<double> dms;                                    // (the trial DMs are refused before anything is allocated)
     if ((rc = dm_trials(cands, ncand, par, &dms, e)) != 0) return rc;
   }
-  if ((rc = post_check_device(device, e)) != 0) return rc;
   DmOut out;
-  {
-    DeviceGuard dg(device);
-    PostScope ps;
-    if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
-    if ((rc = dm_run(fil, d_rows, nrows, bpar, cands, ncand, flag, par, pk, ps, &out, e)) != 0) return rc;
-  }
-  const size_t n = (size_t)ncand * par->ntrial;
-  if (acc) memcpy(acc, out.acc.data(), out.acc.size() * sizeof(long long));
-  if (hits) memcpy(hits, out.hits.data(), out.hits.size() * sizeof(uint32_t));
-  if (snr) memcpy(snr, out.cv.snr.data(), n * sizeof(double));
-  if (strc) memcpy(strc, out.cv.strc.data(), n * sizeof(double));
-  if (results) memcpy((void*)results, out.cv.res.data(), (size_t)ncand * sizeof(frbch_dmscan_result));
-  if (used) memcpy(used, out.used.data(), out.used.size());
-  if (kernel_used) { kernel_used[0] = out.k[0]; kernel_used[1] = out.k[1]; }
+  rc = burst_device_call(device, e, [&](PostScope& ps) { return dm_run(fil, d_rows, nrows, bpar, cands, ncand, flag, par, pk, ps, &out, e); });
+  if (rc) return rc;
+  deliver(acc, out.acc);
+  deliver(hits, out.hits);
+  deliver(snr, out.cv.snr);
+  deliver(strc, out.cv.strc);
+  deliver(results, out.cv.res);
+  deliver(used, out.used);
+  deliver(kernel_used, out.k);
   return FRBCH_OK;
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
@@ -4667,11 +4702,7 @@ extern "C" int frbch_dmscan_host(const frbch_fil_desc* fil, const void* rows, ui
     std::vector<double> dms;
     if ((rc = dm_trials(cands, ncand, par, &dms, e)) != 0) return rc;
   }
-  if ((rc = post_check_device(device, e)) != 0) return rc;
-  DeviceGuard dg(device);
-  HostStage hs;
-  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
-  return hs.run(e, "device memory for the rows", "upload rows", "download", [&]() {
+  return burst_host_twin(fil, rows, nrows, device, e, [&](void* d_rows) {
     return frbch_dmscan_device(fil, d_rows, nrows, bpar, cands, ncand, flag, par, pk, device, acc, hits, snr, strc, results, used, kernel_used, err, err_cap);
   });
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
@@ -4686,7 +4717,7 @@ constexpr int32_t kAcfMaxY = 1 << 21;
 
 int acf2_check(uint32_t n, uint32_t nsub, uint32_t nbin, uint32_t nlagf, uint32_t nlagt, uint32_t form, const PostErr& e) {
   if (n < 1 || nsub < 1) return e.fail(FRBCH_E_ARG, "at least one plane and one subband");
-  if (nbin < 1 || nbin > kDmMaxBin) return e.fail(FRBCH_E_ARG, "nbin must be 1..1024");
+  if (nbin < 1 || nbin > kWinMaxBin) return e.fail(FRBCH_E_ARG, "nbin must be 1..1024");
   if ((uint64_t)nsub * nbin > kAcfMaxPlane) return e.fail(FRBCH_E_ARG, "nsub * nbin exceeds 2^20: raise ffactor or cut the window");
   if ((uint64_t)n * nsub * nbin > kAcfMaxCells) return e.fail(FRBCH_E_ARG, "ncand * nsub * nbin exceeds 2^24: cut the batch");
   if (nlagf < 1 || nlagf > std::min(nsub, kAcfMaxLagF)) return e.fail(FRBCH_E_ARG, "nlagf must be 1..min(nsub, 1024)");
@@ -4758,14 +4789,9 @@ int acf2_launch(const int32_t* d_y, uint32_t n, uint32_t nsub, uint32_t nbin, ui
 
 int acf_check(const frbch_fil_desc* fil, uint64_t nrows, const frbch_burst_params* bpar, const frbch_burst_cand* cands,
               uint32_t ncand, const frbch_acf_params* par, const PostErr& e) {
-  const int rc = burst_check(fil, nrows, bpar, cands, ncand, e);
+  int rc = burst_check(fil, nrows, bpar, cands, ncand, e);
   if (rc) return rc;
-  if (fil->nbits == 32) return e.fail(FRBCH_E_ARG, "the burst ACF is not built for float32 rows: its fixed-point scale needs a bound on the samples");
-  if (!par || par->size != sizeof(frbch_acf_params)) return e.fail(FRBCH_E_ARG, "frbch_acf_params: wrong size");
-  if (par->nbin < 1 || par->nbin > kDmMaxBin) return e.fail(FRBCH_E_ARG, "nbin must be 1..1024");
-  if (par->tfactor < 1 || par->tfactor > kDmMaxTf) return e.fail(FRBCH_E_ARG, "tfactor must be 1..512");
-  if (fil->nchan > kRmMaxChan) return e.fail(FRBCH_E_ARG, "more than 16384 channels");
-  if (par->ffactor < 1 || par->ffactor > fil->nchan || fil->nchan % par->ffactor) return e.fail(FRBCH_E_ARG, "ffactor must be 1..nchan and divide nchan");
+  if ((rc = window_check(fil, par, "the burst ACF", "frbch_acf_params", {nullptr, nullptr, &frbch_acf_params::ffactor}, e)) != 0) return rc;
   return acf2_check(ncand, fil->nchan / par->ffactor, par->nbin, par->nlagf, par->nlagt, FRBCH_ACF_PLAN, e);
 }
 
@@ -4785,7 +4811,7 @@ int acf_delays(const frbch_fil_desc* fil, const frbch_burst_cand* cands, uint32_
 
 // The plan rule of the dynamic spectrum -- the one decision behind its launches, kernel_used[1] and frbch_burstacf_kernel's
 // answer.  The fast kernel wants what the fast DM scan kernel wants at one trial (the layout of the fast burst-sums kernel, bins
-// of at most kDmMaxT rows, tfactor + the delay range of every (candidate, 64-byte tile) <= kDmLds / (64 products) rows) and an
+// of at most kDmMaxT rows, a bin that fits the stage: dm_stage_brun with ntrial = trun = 1) and an
 // ffactor it can reduce: a power of two of at most the CT channels of a tile (shuffles over ffactor lanes, gl = ffactor), or a
 // multiple of CT (shuffles over the tile, gl = CT, and a join over tps = ffactor / CT tiles, whose partials stay within 2^30
 // bytes).  The emulator build has no such kernel: generic.
@@ -4799,17 +4825,9 @@ DynPlan dyn_plan_rule(const frbch_fil_desc* fil, const void* d_rows, uint32_t pr
   const bool shuffle = (ff & (ff - 1)) == 0 && ff <= ct, join = ff > ct && ff % ct == 0;
   if (!shuffle && !join) return r;
   if (join && (uint64_t)ncand * ntile * par->nbin * 12ull > kDmPartCap) return r;
-  const int64_t cap = (int64_t)(fast::kDmLds / (64u * (products == FRBCH_BURST_COHERENCY ? 2u : 1u)));
-  int64_t range = 0;
-  for (size_t i = 0; i < ncand; ++i)
-    for (uint32_t t = 0; t < ntile; ++t) {
-      const int32_t* d = delays.data() + i * fil->nchan + (size_t)t * ct;
-      const auto mm = std::minmax_element(d, d + ct);
-      range = std::max<int64_t>(range, (int64_t)*mm.second - (int64_t)*mm.first);
-    }
-  if ((int64_t)par->tfactor + range > cap) return r;
-  r = DynPlan{true, (int)std::min<int64_t>((int64_t)par->nbin, (cap - range) / (int64_t)par->tfactor), (int)ntile, (int)std::min(ff, ct),
-              join ? (int)(ff / ct) : 0};
+  const int brun = dm_stage_brun(tile_scan(fil, delays), products, ncand, 1, 1, par->nbin, par->tfactor);     // the DM scan's stage at one trial
+  if (!brun) return r;
+  r = DynPlan{true, brun, (int)ntile, (int)std::min(ff, ct), join ? (int)(ff / ct) : 0};
 #else
   (void)fil; (void)d_rows; (void)products; (void)delays; (void)ncand; (void)par;
 #endif
@@ -5010,20 +5028,16 @@ int acf_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const
   int rc = dyn_run(fil, d_rows, nrows, bpar, cands, ncand, flag, par, ps, &dyn, out->k, e);
   if (rc) return rc;
   out->used.swap(dyn.used);
-  const DmPrep& prep = dyn.prep;
-  const std::vector<uint32_t>& nused_s = dyn.nused_s;
-  long long *d_Y = dyn.d_Y, *d_A = nullptr;
-  uint32_t* d_hits = dyn.d_hits;
-  int32_t *d_shift = dyn.d_shift, *d_y = dyn.d_y, *d_mask = dyn.d_mask;
+  long long* d_A = nullptr;
   POST_DEV(ps.alloc(&d_A, nlag * sizeof(long long)), "hipMalloc");
-  if ((rc = acf2_launch(d_y, ncand, (uint32_t)nsub, par->nbin, par->nlagf, par->nlagt, FRBCH_ACF_PLAN, d_A, ps, &out->k[2], e)) != 0) return rc;
+  if ((rc = acf2_launch(dyn.d_y, ncand, (uint32_t)nsub, par->nbin, par->nlagf, par->nlagt, FRBCH_ACF_PLAN, d_A, ps, &out->k[2], e)) != 0) return rc;
   std::vector<int32_t> shift(ncand);
   out->Y.resize(ncell);
   out->yhits.resize(ncell);
   out->A.resize(nlag);
-  POST_DEV(dev_d2h(out->Y.data(), d_Y, ncell * sizeof(long long), ps.s), "download dynamic spectrum");
-  POST_DEV(dev_d2h(out->yhits.data(), d_hits, ncell * sizeof(uint32_t), ps.s), "download dynamic spectrum");
-  POST_DEV(dev_d2h(shift.data(), d_shift, (size_t)ncand * sizeof(int32_t), ps.s), "download scale");
+  POST_DEV(dev_d2h(out->Y.data(), dyn.d_Y, ncell * sizeof(long long), ps.s), "download dynamic spectrum");
+  POST_DEV(dev_d2h(out->yhits.data(), dyn.d_hits, ncell * sizeof(uint32_t), ps.s), "download dynamic spectrum");
+  POST_DEV(dev_d2h(shift.data(), dyn.d_shift, (size_t)ncand * sizeof(int32_t), ps.s), "download scale");
   POST_DEV(dev_d2h(out->A.data(), d_A, nlag * sizeof(long long), ps.s), "download ACF");
   POST_DEV(dev_sync(ps.s), "sync");
 
@@ -5032,7 +5046,7 @@ int acf_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const
   for (size_t i = 0; i < ncand; ++i) {
     ushift[i] = (uint32_t)shift[i];
     for (size_t s = 0; s < nsub; ++s) {
-      const uint32_t nu = nused_s[i * nsub + s];
+      const uint32_t nu = dyn.nused_s[i * nsub + s];
       if (!nu) continue;
       const uint32_t* h = out->yhits.data() + (i * nsub + s) * nbin;
       for (size_t j = 0; j < nbin; ++j) ncomplete[i] += h[j] == par->tfactor * nu ? 1u : 0u;
@@ -5051,22 +5065,22 @@ int acf_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const
   } else {
     std::vector<long long> pairs(nlag);
     uint32_t kp = 0;
-    if ((rc = acf2_launch(d_mask, ncand, (uint32_t)nsub, par->nbin, par->nlagf, par->nlagt, FRBCH_ACF_PLAN, d_A, ps, &kp, e)) != 0) return rc;
+    if ((rc = acf2_launch(dyn.d_mask, ncand, (uint32_t)nsub, par->nbin, par->nlagf, par->nlagt, FRBCH_ACF_PLAN, d_A, ps, &kp, e)) != 0) return rc;
     POST_DEV(dev_d2h(pairs.data(), d_A, nlag * sizeof(long long), ps.s), "download pair counts");
     POST_DEV(dev_sync(ps.s), "sync");
     for (size_t l = 0; l < nlag; ++l) out->P[l] = (uint32_t)pairs[l];
   }
   out->res.resize(ncand);
-  acf_fit(fil, par, fp->fit_frac, ncand, prep.kscale.data(), ushift.data(), prep.nused.data(), ncomplete.data(),
+  acf_fit(fil, par, fp->fit_frac, ncand, dyn.prep.kscale.data(), ushift.data(), dyn.prep.nused.data(), ncomplete.data(),
           (const int64_t*)out->A.data(), out->P.data(), nullptr, out->res.data());
   return FRBCH_OK;
 }
 }  // namespace
 
-extern "C" int frbch_acf2d_kernel(uint32_t n, uint32_t nsub, uint32_t nbin, uint32_t nlagf, uint32_t nlagt, uint32_t form) {
+extern "C" int frbch_acf2d_kernel(uint32_t n, uint32_t nsub, uint32_t nbin, uint32_t nlagf, uint32_t nlagt, uint32_t form) try {
   const int rc = acf2_check(n, nsub, nbin, nlagf, nlagt, form, PostErr{nullptr, 0});
   return rc ? rc : (acf2_plan_rule(n, nsub, nbin, nlagf, nlagt, form).fastk ? 1 : 0);
-}
+} catch (const std::bad_alloc&) { return FRBCH_E_NOMEM; }
 
 extern "C" int frbch_acf2d_device(const int32_t* d_y, uint32_t n, uint32_t nsub, uint32_t nbin, uint32_t nlagf, uint32_t nlagt,
                                   uint32_t form, int device, int64_t* d_A, uint32_t* kernel_used, char* err, size_t err_cap) try {
@@ -5075,14 +5089,15 @@ extern "C" int frbch_acf2d_device(const int32_t* d_y, uint32_t n, uint32_t nsub,
   int rc = acf2_check(n, nsub, nbin, nlagf, nlagt, form, e);
   if (rc) return rc;
   if (!d_y || !d_A) return e.fail(FRBCH_E_ARG, "null argument");
-  if ((rc = post_check_device(device, e)) != 0) return rc;
-  DeviceGuard dg(device);
-  PostScope ps;
-  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
-  uint32_t k = 0;
-  if ((rc = acf2_launch(d_y, n, nsub, nbin, nlagf, nlagt, form, (long long*)d_A, ps, &k, e)) != 0) return rc;
-  POST_DEV(dev_sync(ps.s), "sync");
-  if (kernel_used) *kernel_used = k;
+  uint32_t k[1] = {0};
+  rc = burst_device_call(device, e, [&](PostScope& ps) {
+    const int rc = acf2_launch(d_y, n, nsub, nbin, nlagf, nlagt, form, (long long*)d_A, ps, k, e);
+    if (rc) return rc;
+    POST_DEV(dev_sync(ps.s), "sync");
+    return (int)FRBCH_OK;
+  });
+  if (rc) return rc;
+  deliver(kernel_used, k);
   return FRBCH_OK;
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
@@ -5111,7 +5126,7 @@ extern "C" int frbch_burstacf_fit(const frbch_fil_desc* fil, const frbch_acf_par
   PostErr e{err, err_cap};
   if (!fil || fil->size != sizeof(frbch_fil_desc) || fil->nchan < 1 || !(fil->tsamp_s > 0) || fil->foff_mhz == 0.0) return e.fail(FRBCH_E_ARG, "frbch_fil_desc: wrong size, or bad nchan / tsamp / foff");
   if (!par || par->size != sizeof(frbch_acf_params)) return e.fail(FRBCH_E_ARG, "frbch_acf_params: wrong size");
-  if (par->tfactor < 1 || par->tfactor > kDmMaxTf) return e.fail(FRBCH_E_ARG, "tfactor must be 1..512");
+  if (par->tfactor < 1 || par->tfactor > kWinMaxT) return e.fail(FRBCH_E_ARG, "tfactor must be 1..512");
   if (par->ffactor < 1 || par->ffactor > fil->nchan || fil->nchan % par->ffactor) return e.fail(FRBCH_E_ARG, "ffactor must be 1..nchan and divide nchan");
   int rc = acf2_check(ncand, fil->nchan / par->ffactor, par->nbin, par->nlagf, par->nlagt, FRBCH_ACF_PLAN, e);
   if (rc) return rc;
@@ -5122,8 +5137,8 @@ extern "C" int frbch_burstacf_fit(const frbch_fil_desc* fil, const frbch_acf_par
   std::vector<frbch_acf_result> res(ncand);
   std::vector<double> nm(norm ? (size_t)ncand * par->nlagf * (2 * (size_t)par->nlagt - 1) : 0);
   acf_fit(fil, par, fp->fit_frac, ncand, k, r, nused, ncomplete, A, P, norm ? nm.data() : nullptr, res.data());
-  if (norm) memcpy(norm, nm.data(), nm.size() * sizeof(double));
-  if (results) memcpy((void*)results, res.data(), (size_t)ncand * sizeof(frbch_acf_result));
+  deliver(norm, nm);
+  deliver(results, res);
   return FRBCH_OK;
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
@@ -5152,21 +5167,16 @@ extern "C" int frbch_burstacf_device(const frbch_fil_desc* fil, const void* d_ro
   if (rc) return rc;
   if ((rc = acf_check_fit(fp, e)) != 0) return rc;
   if (!d_rows) return e.fail(FRBCH_E_ARG, "null argument");
-  if ((rc = post_check_device(device, e)) != 0) return rc;
   AcfOut out;
-  {
-    DeviceGuard dg(device);
-    PostScope ps;
-    if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
-    if ((rc = acf_run(fil, d_rows, nrows, bpar, cands, ncand, flag, par, fp, ps, &out, e)) != 0) return rc;
-  }
-  if (Y) memcpy(Y, out.Y.data(), out.Y.size() * sizeof(long long));
-  if (yhits) memcpy(yhits, out.yhits.data(), out.yhits.size() * sizeof(uint32_t));
-  if (A) memcpy(A, out.A.data(), out.A.size() * sizeof(long long));
-  if (P) memcpy(P, out.P.data(), out.P.size() * sizeof(uint32_t));
-  if (results) memcpy((void*)results, out.res.data(), out.res.size() * sizeof(frbch_acf_result));
-  if (used) memcpy(used, out.used.data(), out.used.size());
-  if (kernel_used) { kernel_used[0] = out.k[0]; kernel_used[1] = out.k[1]; kernel_used[2] = out.k[2]; }
+  rc = burst_device_call(device, e, [&](PostScope& ps) { return acf_run(fil, d_rows, nrows, bpar, cands, ncand, flag, par, fp, ps, &out, e); });
+  if (rc) return rc;
+  deliver(Y, out.Y);
+  deliver(yhits, out.yhits);
+  deliver(A, out.A);
+  deliver(P, out.P);
+  deliver(results, out.res);
+  deliver(used, out.used);
+  deliver(kernel_used, out.k);
   return FRBCH_OK;
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
@@ -5179,11 +5189,7 @@ extern "C" int frbch_burstacf_host(const frbch_fil_desc* fil, const void* rows, 
   if (rc) return rc;
   if ((rc = acf_check_fit(fp, e)) != 0) return rc;
   if (!rows) return e.fail(FRBCH_E_ARG, "null argument");
-  if ((rc = post_check_device(device, e)) != 0) return rc;
-  DeviceGuard dg(device);
-  HostStage hs;
-  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
-  return hs.run(e, "device memory for the rows", "upload rows", "download", [&]() {
+  return burst_host_twin(fil, rows, nrows, device, e, [&](void* d_rows) {
     return frbch_burstacf_device(fil, d_rows, nrows, bpar, cands, ncand, flag, par, fp, device, Y, yhits, A, P, results, used, kernel_used, err, err_cap);
   });
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
@@ -5199,7 +5205,7 @@ constexpr int32_t kTbMaxY = 1 << 21, kTbMaxP = 1 << 30;
 int tbank_check(uint32_t n, const frbch_tbank_shape* sh, uint32_t form, const PostErr& e) {
   if (!sh || sh->size != sizeof(frbch_tbank_shape)) return e.fail(FRBCH_E_ARG, "frbch_tbank_shape: wrong size");
   if (n < 1 || sh->nsub < 1) return e.fail(FRBCH_E_ARG, "at least one plane and one subband");
-  if (sh->nbin < 1 || sh->nbin > kDmMaxBin) return e.fail(FRBCH_E_ARG, "nbin must be 1..1024");
+  if (sh->nbin < 1 || sh->nbin > kWinMaxBin) return e.fail(FRBCH_E_ARG, "nbin must be 1..1024");
   if (sh->ntap < 1 || sh->ntap > kTbMaxTap) return e.fail(FRBCH_E_ARG, "ntap must be 1..1024");
   if (sh->lead >= sh->ntap) return e.fail(FRBCH_E_ARG, "lead must lie below ntap");
   if (sh->ntemp < 1 || sh->ntemp > kTbMaxTemp) return e.fail(FRBCH_E_ARG, "1..4096 templates");
@@ -5339,12 +5345,7 @@ int scat_check(const frbch_fil_desc* fil, uint64_t nrows, const frbch_burst_para
                frbch_tbank_shape* sh, const PostErr& e) {
   int rc = burst_check(fil, nrows, bpar, cands, ncand, e);
   if (rc) return rc;
-  if (fil->nbits == 32) return e.fail(FRBCH_E_ARG, "the scattering fit is not built for float32 rows: its fixed-point scale needs a bound on the samples");
-  if (!par || par->size != sizeof(frbch_scat_params)) return e.fail(FRBCH_E_ARG, "frbch_scat_params: wrong size");
-  if (par->nbin < 1 || par->nbin > kDmMaxBin) return e.fail(FRBCH_E_ARG, "nbin must be 1..1024");
-  if (par->tfactor < 1 || par->tfactor > kDmMaxTf) return e.fail(FRBCH_E_ARG, "tfactor must be 1..512");
-  if (fil->nchan > kRmMaxChan) return e.fail(FRBCH_E_ARG, "more than 16384 channels");
-  if (par->ffactor < 1 || par->ffactor > fil->nchan || fil->nchan % par->ffactor) return e.fail(FRBCH_E_ARG, "ffactor must be 1..nchan and divide nchan");
+  if ((rc = window_check(fil, par, "the scattering fit", "frbch_scat_params", {nullptr, nullptr, &frbch_scat_params::ffactor}, e)) != 0) return rc;
   if ((rc = scat_check_bank(bp, e)) != 0) return rc;
   *apar = frbch_acf_params{sizeof(frbch_acf_params), par->nbin, par->tfactor, par->ffactor, 1, 1, {0, 0}};
   *sh = frbch_tbank_shape{sizeof(frbch_tbank_shape), fil->nchan / par->ffactor, par->nbin, bp->nsig * bp->ntau, bp->ntap, bp->lead, par->shift0, par->nshift};
@@ -5561,19 +5562,19 @@ extern "C" int frbch_scat_bank(const frbch_scat_bank_params* bp, int32_t* p, int
   if (rc) return rc;
   ScatBank b;
   scat_bank(bp, &b);
-  if (p) memcpy(p, b.p.data(), b.p.size() * sizeof(int32_t));
-  if (s1) memcpy(s1, b.s1.data(), b.s1.size() * sizeof(int64_t));
-  if (cum) memcpy(cum, b.cum.data(), b.cum.size() * sizeof(int64_t));
-  if (tail) memcpy(tail, b.tail.data(), b.tail.size() * sizeof(double));
-  if (sigma) memcpy(sigma, b.sigma.data(), b.sigma.size() * sizeof(double));
-  if (tau) memcpy(tau, b.tau.data(), b.tau.size() * sizeof(double));
+  deliver(p, b.p);
+  deliver(s1, b.s1);
+  deliver(cum, b.cum);
+  deliver(tail, b.tail);
+  deliver(sigma, b.sigma);
+  deliver(tau, b.tau);
   return FRBCH_OK;
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
-extern "C" int frbch_tbank_kernel(uint32_t n, const frbch_tbank_shape* sh, uint32_t form) {
+extern "C" int frbch_tbank_kernel(uint32_t n, const frbch_tbank_shape* sh, uint32_t form) try {
   const int rc = tbank_check(n, sh, form, PostErr{nullptr, 0});
   return rc ? rc : (tbank_plan_rule(n, sh, form).fastk ? 1 : 0);
-}
+} catch (const std::bad_alloc&) { return FRBCH_E_NOMEM; }
 
 extern "C" int frbch_tbank_device(const int32_t* d_y, const int32_t* d_P, uint32_t n, const frbch_tbank_shape* sh, uint32_t form,
                                   int device, int64_t* d_C, uint32_t* kernel_used, char* err, size_t err_cap) try {
@@ -5581,14 +5582,15 @@ extern "C" int frbch_tbank_device(const int32_t* d_y, const int32_t* d_P, uint32
   int rc = tbank_check(n, sh, form, e);
   if (rc) return rc;
   if (!d_y || !d_P || !d_C) return e.fail(FRBCH_E_ARG, "null argument");
-  if ((rc = post_check_device(device, e)) != 0) return rc;
-  DeviceGuard dg(device);
-  PostScope ps;
-  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
-  uint32_t k = 0;
-  if ((rc = tbank_launch(d_y, d_P, n, sh, form, (long long*)d_C, ps, &k, e)) != 0) return rc;
-  POST_DEV(dev_sync(ps.s), "sync");
-  if (kernel_used) *kernel_used = k;
+  uint32_t k[1] = {0};
+  rc = burst_device_call(device, e, [&](PostScope& ps) {
+    const int rc = tbank_launch(d_y, d_P, n, sh, form, (long long*)d_C, ps, k, e);
+    if (rc) return rc;
+    POST_DEV(dev_sync(ps.s), "sync");
+    return (int)FRBCH_OK;
+  });
+  if (rc) return rc;
+  deliver(kernel_used, k);
   return FRBCH_OK;
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
@@ -5621,7 +5623,7 @@ extern "C" int frbch_burstscat_fit(const frbch_fil_desc* fil, const frbch_scat_p
   PostErr e{err, err_cap};
   if (!fil || fil->size != sizeof(frbch_fil_desc) || fil->nchan < 1 || !(fil->tsamp_s > 0) || fil->foff_mhz == 0.0) return e.fail(FRBCH_E_ARG, "frbch_fil_desc: wrong size, or bad nchan / tsamp / foff");
   if (!par || par->size != sizeof(frbch_scat_params)) return e.fail(FRBCH_E_ARG, "frbch_scat_params: wrong size");
-  if (par->tfactor < 1 || par->tfactor > kDmMaxTf) return e.fail(FRBCH_E_ARG, "tfactor must be 1..512");
+  if (par->tfactor < 1 || par->tfactor > kWinMaxT) return e.fail(FRBCH_E_ARG, "tfactor must be 1..512");
   if (par->ffactor < 1 || par->ffactor > fil->nchan || fil->nchan % par->ffactor) return e.fail(FRBCH_E_ARG, "ffactor must be 1..nchan and divide nchan");
   int rc = scat_check_bank(bp, e);
   if (rc) return rc;
@@ -5638,9 +5640,9 @@ extern "C" int frbch_burstscat_fit(const frbch_fil_desc* fil, const frbch_scat_p
   std::vector<frbch_scat_sub> sv((size_t)ncand * sh.nsub);
   std::vector<frbch_scat_band> bv(ncand);
   scat_fit(fil, par, bp, bank, fp, ncand, k, r, nused, nused_s, C, N, q ? qv.data() : nullptr, sv.data(), bv.data());
-  if (q) memcpy(q, qv.data(), nout * sizeof(double));
-  if (sub) memcpy((void*)sub, sv.data(), sv.size() * sizeof(frbch_scat_sub));
-  if (band) memcpy((void*)band, bv.data(), bv.size() * sizeof(frbch_scat_band));
+  deliver(q, qv);
+  deliver(sub, sv);
+  deliver(band, bv);
   return FRBCH_OK;
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
@@ -5675,23 +5677,18 @@ extern "C" int frbch_burstscat_device(const frbch_fil_desc* fil, const void* d_r
   if (rc) return rc;
   if ((rc = scat_check_fit(fp, e)) != 0) return rc;
   if (!d_rows) return e.fail(FRBCH_E_ARG, "null argument");
-  if ((rc = post_check_device(device, e)) != 0) return rc;
   ScatOut out;
-  {
-    DeviceGuard dg(device);
-    PostScope ps;
-    if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
-    if ((rc = scat_run(fil, d_rows, nrows, bpar, cands, ncand, flag, par, &apar, &sh, bp, fp, ps, &out, e)) != 0) return rc;
-  }
-  if (Y) memcpy(Y, out.Y.data(), out.Y.size() * sizeof(long long));
-  if (yhits) memcpy(yhits, out.yhits.data(), out.yhits.size() * sizeof(uint32_t));
-  if (y) memcpy(y, out.y.data(), out.y.size() * sizeof(int32_t));
-  if (C) memcpy(C, out.C.data(), out.C.size() * sizeof(long long));
-  if (N) memcpy(N, out.N.data(), out.N.size() * sizeof(long long));
-  if (sub) memcpy((void*)sub, out.sub.data(), out.sub.size() * sizeof(frbch_scat_sub));
-  if (band) memcpy((void*)band, out.band.data(), out.band.size() * sizeof(frbch_scat_band));
-  if (used) memcpy(used, out.used.data(), out.used.size());
-  if (kernel_used) { kernel_used[0] = out.k[0]; kernel_used[1] = out.k[1]; kernel_used[2] = out.k[2]; }
+  rc = burst_device_call(device, e, [&](PostScope& ps) { return scat_run(fil, d_rows, nrows, bpar, cands, ncand, flag, par, &apar, &sh, bp, fp, ps, &out, e); });
+  if (rc) return rc;
+  deliver(Y, out.Y);
+  deliver(yhits, out.yhits);
+  deliver(y, out.y);
+  deliver(C, out.C);
+  deliver(N, out.N);
+  deliver(sub, out.sub);
+  deliver(band, out.band);
+  deliver(used, out.used);
+  deliver(kernel_used, out.k);
   return FRBCH_OK;
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
@@ -5707,11 +5704,7 @@ extern "C" int frbch_burstscat_host(const frbch_fil_desc* fil, const void* rows,
   if (rc) return rc;
   if ((rc = scat_check_fit(fp, e)) != 0) return rc;
   if (!rows) return e.fail(FRBCH_E_ARG, "null argument");
-  if ((rc = post_check_device(device, e)) != 0) return rc;
-  DeviceGuard dg(device);
-  HostStage hs;
-  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
-  return hs.run(e, "device memory for the rows", "upload rows", "download", [&]() {
+  return burst_host_twin(fil, rows, nrows, device, e, [&](void* d_rows) {
     return frbch_burstscat_device(fil, d_rows, nrows, bpar, cands, ncand, flag, par, bp, fp, device, Y, yhits, y, C, N, sub, band, used, kernel_used, err, err_cap);
   });
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }

@@ -1101,15 +1101,55 @@ __global__ void __launch_bounds__(kRmThreads) frbch_post_rm_join(RmParams p) {
 // Polarisation profile (HIP only; frbch_post_polprof of kernels_post.inc stays the emulable form and the fallback; both call
 // pp_term).  A workgroup of 256 threads owns one candidate, one 64-byte tile of the row (CT = 64 / 32 channels of 8- / 16-bit
 // samples) and a run of `brun` bins.  It stages the rows the run needs -- from its first bin's first row at the tile's
-// smallest delay to its last bin's last row at the largest: nb tfactor + (dmax - dmin) <= kPpSpan rows, the host's plan rule
-// sees to that -- of all four products into the LDS in 16-byte pieces, four lanes side by side on the 64 bytes of a product
-// (the layout of the LDS is [row][product][64 bytes], piece i at byte 16 i).  Then one thread per (channel, bin), 256 / CT
-// bins per trip, sums its tfactor samples at its own delay from the LDS, forms its term, and the CT lanes of a bin add
-// theirs up by shuffles; lane 0 stores the tile's int64 partial.  Rows outside the file are neither loaded nor read.
+// smallest delay (tile_delay_range) to its last bin's last row at the largest: nb tfactor + (dmax - dmin) <= kPpSpan rows,
+// the host's plan rule sees to that -- of all four products (tile_stage).  Then one thread per (channel, bin), 256 / CT bins
+// per trip, sums its tfactor samples at its own delay from the LDS (tile_row_add), forms its term, and the CT lanes of a bin
+// add theirs up by shuffles; lane 0 stores the tile's int64 partial.  Rows outside the file are neither loaded nor read.
 // frbch_post_polprof_join adds the tiles in ascending order.  All row arithmetic is 64 bit.
 // grid (row bytes / 64, ceil(nbin / brun), ncand).
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int kPpThreads = 256, kPpSpan = 256;
+// The three blocks that the profile, DM scan and dynamic spectrum kernels share: a workgroup of kTileThreads threads on one
+// 64-byte tile of the row, CT = 64 / BPV channels, lanes along the channels.
+constexpr int kTileThreads = 256;
+
+// the smallest and largest delay over the CT lanes of a tile, by shuffles: the same in every thread afterwards
+template <int BPV> __device__ __forceinline__ void tile_delay_range(int& dmin, int& dmax) {
+#pragma unroll
+  for (int m = 1; m < 64 / BPV; m <<= 1) {
+    dmin = min(dmin, __shfl_xor(dmin, m));
+    dmax = max(dmax, __shfl_xor(dmax, m));
+  }
+}
+
+// `span` rows from file row `base` on, NP products of each, into the LDS as [row][product][64 bytes] in 16-byte pieces, four
+// lanes side by side on the 64 bytes of a product (src: the tile's bytes of the first product read in row 0; stride, pstride:
+// the bytes of a row and of a product).  Rows outside the file are not loaded.  The caller synchronises.
+template <int NP>
+__device__ __forceinline__ void tile_stage(unsigned char* smem, const unsigned char* src, size_t stride, size_t pstride, long long base,
+                                           int span, long long nrows, int tid) {
+  constexpr int PIECES = 4 * NP;                                           // of a staged row
+  for (int i = tid; i < span * PIECES; i += kTileThreads) {
+    const long long row = base + (long long)(i / PIECES);
+    if (row >= 0 && row < nrows)
+      *reinterpret_cast<uint4*>(smem + (size_t)i * 16) =
+          *reinterpret_cast<const uint4*>(src + (size_t)row * stride + (size_t)((i >> 2) % NP) * pstride + (size_t)(i & 3) * 16);
+  }
+}
+
+// The window sum, one staged row of it: a channel's samples of the NP products (q: its sample of the first) added to NS = NP
+// sums, one a product, or to NS = 1, the products together.  The loop over the rows of a window stays in the kernels: inside
+// this function it changes how the compiler unrolls the profile kernel's (64 VGPRs against 56).
+template <int BPV, int NP, int NS>
+__device__ __forceinline__ void tile_row_add(const unsigned char* q, uint32_t (&S)[NS]) {
+  static_assert(NS == 1 || NS == NP, "one sum, or one a product");
+#pragma unroll
+  for (int pr = 0; pr < NP; ++pr) {
+    if constexpr (BPV == 1) S[pr % NS] += (uint32_t)q[pr * 64];
+    else S[pr % NS] += (uint32_t)*reinterpret_cast<const uint16_t*>(q + pr * 64);
+  }
+}
+
+constexpr int kPpThreads = kTileThreads, kPpSpan = 256;
 constexpr size_t kPpLds = (size_t)kPpSpan * 256;                           // 64 KiB: two workgroups per CU
 
 template <int BPV>
@@ -1123,22 +1163,12 @@ __global__ void __launch_bounds__(kPpThreads) frbch_post_polprof_fast(PolParams 
   const PolCand cd = p.cand[cand];
   const PolRec r = p.rec[(size_t)cand * p.nchan + (size_t)tile * CT + ch];
   int dmin = r.delay, dmax = r.delay;
-#pragma unroll
-  for (int m = 1; m < CT; m <<= 1) {                                       // over the tile's channels: the same in every thread
-    dmin = min(dmin, __shfl_xor(dmin, m));
-    dmax = max(dmax, __shfl_xor(dmax, m));
-  }
+  tile_delay_range<BPV>(dmin, dmax);
   const long long nrows = (long long)p.nrows;
   const long long base = cd.t0 + (long long)j0 * (long long)p.tfactor + (long long)dmin;     // the file row of LDS row 0
   const int span = nb * p.tfactor + (dmax - dmin);
   const size_t stride = (size_t)4 * p.nchan * BPV, pstride = (size_t)p.nchan * BPV;
-  const unsigned char* src = p.rows + (size_t)tile * 64;
-  for (int i = tid; i < span * 16; i += kPpThreads) {
-    const long long row = base + (long long)(i >> 4);
-    if (row >= 0 && row < nrows)
-      *reinterpret_cast<uint4*>(smem + (size_t)i * 16) =
-          *reinterpret_cast<const uint4*>(src + (size_t)row * stride + (size_t)((i >> 2) & 3) * pstride + (size_t)(i & 3) * 16);
-  }
+  tile_stage<4>(smem, p.rows + (size_t)tile * 64, stride, pstride, base, span, nrows, tid);
   __syncthreads();
   for (int jb0 = 0; jb0 < nb; jb0 += BPP) {                                // (the same trips in every thread: the shuffles meet whole waves)
     const int jb = jb0 + jl;
@@ -1151,13 +1181,7 @@ __global__ void __launch_bounds__(kPpThreads) frbch_post_polprof_fast(PolParams 
       if (hi > lo) {
         uint32_t S[4] = {0, 0, 0, 0};
         const unsigned char* q = smem + (size_t)(lo - base) * 256 + (size_t)ch * BPV;
-        for (long long t = lo; t < hi; ++t, q += 256) {
-#pragma unroll
-          for (int pr = 0; pr < 4; ++pr) {
-            if constexpr (BPV == 1) S[pr] += (uint32_t)q[pr * 64];
-            else S[pr] += (uint32_t)*reinterpret_cast<const uint16_t*>(q + pr * 64);
-          }
-        }
+        for (long long t = lo; t < hi; ++t, q += 256) tile_row_add<BPV, 4>(q, S);
         h = (uint32_t)(hi - lo);
         pp_term(r, p.coh, cd.scale, S, h, a);
       }
@@ -1199,15 +1223,15 @@ __global__ void __launch_bounds__(kPpThreads) frbch_post_polprof_join(PolParams 
 // threads owns one candidate, one 64-byte tile of the row (CT = 64 / 32 channels of 8- / 16-bit samples), a run of `trun`
 // trials and a run of `brun` bins.  It stages the rows the bins need over the delay range of its tile over its trials -- from
 // its first bin's first row at the smallest delay to its last bin's last row at the largest: nb tfactor + (dmax - dmin) <=
-// kDmLds / (64 NP) rows, the host's plan rule sees to that -- of the NP products read into the LDS in 16-byte pieces (layout
-// [row][product][64 bytes]).  Then, trial after trial, one thread per (channel, bin), 256 / CT bins per trip, sums its tfactor
-// samples at its channel's delay of that trial from the LDS and forms its term; the CT lanes of a bin add theirs up by
+// kDmLds / (64 NP) rows, the host's plan rule sees to that -- of the NP products read (tile_stage).  Then, trial after
+// trial, one thread per (channel, bin), 256 / CT bins per trip, sums its tfactor samples at its channel's delay of that
+// trial from the LDS (tile_row_add) and forms its term; the CT lanes of a bin add theirs up by
 // shuffles and lane 0 stores the tile's int64 partial.  Lanes run along the channels, so a wave reads neighbouring bytes of
 // one or two LDS rows: no bank collides (lanes along the bins would, at a row stride of 64 bytes).  Rows outside the file are
 // neither loaded nor read.  frbch_post_dmscan_join adds the tiles in ascending order.  All row arithmetic is 64 bit.
 // grid (tiles x ceil(nbin / brun), ceil(ntrial / trun), ncand).
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int kDmThreads = 256, kDmTrun = 16, kDmMaxT = 256;
+constexpr int kDmThreads = kTileThreads, kDmTrun = 16, kDmMaxT = 256;
 constexpr size_t kDmLds = 65536;                                           // 64 KiB: two workgroups per CU
 
 template <int BPV, int NP>
@@ -1227,23 +1251,13 @@ __global__ void __launch_bounds__(kDmThreads) frbch_post_dmscan_fast(DmParams p)
     dmin = min(dmin, d);
     dmax = max(dmax, d);
   }
-#pragma unroll
-  for (int m = 1; m < CT; m <<= 1) {                                       // over the tile's channels: the same in every thread
-    dmin = min(dmin, __shfl_xor(dmin, m));
-    dmax = max(dmax, __shfl_xor(dmax, m));
-  }
+  tile_delay_range<BPV>(dmin, dmax);
   const long long nrows = (long long)p.nrows;
   const long long base = cd.t0 + (long long)j0 * (long long)p.tfactor + (long long)dmin;     // the file row of LDS row 0
   const long long span = (long long)nb * p.tfactor + ((long long)dmax - (long long)dmin);
   if (span > CAP) return;                                                  // (the plan rule never launches such a run)
   const size_t stride = (size_t)p.nifs * p.nchan * BPV, pstride = (size_t)p.nchan * BPV;
-  const unsigned char* src = p.rows + (size_t)p.p0 * pstride + (size_t)tile * 64;
-  for (int i = tid; i < (int)span * (ROWB / 16); i += kDmThreads) {
-    const long long row = base + (long long)(i / (ROWB / 16));
-    if (row >= 0 && row < nrows)
-      *reinterpret_cast<uint4*>(smem + (size_t)i * 16) =
-          *reinterpret_cast<const uint4*>(src + (size_t)row * stride + (size_t)((i >> 2) % NP) * pstride + (size_t)(i & 3) * 16);
-  }
+  tile_stage<NP>(smem, p.rows + (size_t)p.p0 * pstride + (size_t)tile * 64, stride, pstride, base, (int)span, nrows, tid);
   __syncthreads();
   for (int k = 0; k < nk; ++k) {                                           // (the same trips in every thread: the shuffles meet whole waves)
     const long long delay = (long long)dl[(size_t)k * p.nchan];
@@ -1256,17 +1270,11 @@ __global__ void __launch_bounds__(kDmThreads) frbch_post_dmscan_fast(DmParams p)
         long long lo, hi;
         burst_clip(b0, (uint32_t)p.tfactor, delay, nrows, &lo, &hi);
         if (hi > lo) {
-          uint32_t S = 0;
+          uint32_t S[1] = {0};
           const unsigned char* q = smem + (size_t)(lo - base) * ROWB + (size_t)ch * BPV;
-          for (long long t = lo; t < hi; ++t, q += ROWB) {
-#pragma unroll
-            for (int pr = 0; pr < NP; ++pr) {
-              if constexpr (BPV == 1) S += (uint32_t)q[pr * 64];
-              else S += (uint32_t)*reinterpret_cast<const uint16_t*>(q + pr * 64);
-            }
-          }
+          for (long long t = lo; t < hi; ++t, q += ROWB) tile_row_add<BPV, NP>(q, S);
           h = (uint32_t)(hi - lo);
-          a = dm_term(r.mean, r.w, cd.scale, S, h);
+          a = dm_term(r.mean, r.w, cd.scale, S[0], h);
         }
       }
 #pragma unroll
@@ -1301,9 +1309,10 @@ __global__ void __launch_bounds__(kDmThreads) frbch_post_dmscan_join(DmParams p)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Structure of a burst, the dynamic spectrum (HIP only; frbch_post_dynspec of kernels_post.inc stays the emulable form and the
-// fallback; both call dm_term).  The staging scheme of frbch_post_dmscan_fast at one trial: a workgroup of 256 threads owns one
-// candidate, one 64-byte tile of the row (CT = 64 / 32 channels) and a run of `brun` bins, and stages the rows those bins need
-// over the delay range of its tile -- nb tfactor + (dmax - dmin) <= kDmLds / (64 NP) rows, the host's plan rule sees to that.
+// fallback; both call dm_term).  frbch_post_dmscan_fast at one trial, built from the same three blocks: a workgroup of 256
+// threads owns one candidate, one 64-byte tile of the row (CT = 64 / 32 channels) and a run of `brun` bins, and stages the rows
+// those bins need over the delay range of its tile -- nb tfactor + (dmax - dmin) <= kDmLds / (64 NP) rows, the host's plan rule
+// (dm_stage_brun at one trial) sees to that.
 // One thread per (channel, bin) forms its term; then only the gl = min(ffactor, CT) neighbouring lanes of a subband add theirs
 // up by shuffles (gl is a power of two).  ffactor <= CT: the leading lane of every group stores the cell of its subband, no
 // join.  ffactor a multiple of CT: gl = CT, the tile's sum is a partial and frbch_post_dynspec_join adds the ffactor / CT tiles
@@ -1321,23 +1330,13 @@ __global__ void __launch_bounds__(kDmThreads) frbch_post_dynspec_fast(DynParams 
   const DmRec r = p.rec[(size_t)cand * p.nchan + (size_t)tile * CT + ch];
   const int delay = p.delays[(size_t)cand * p.nchan + (size_t)tile * CT + ch];
   int dmin = delay, dmax = delay;
-#pragma unroll
-  for (int m = 1; m < CT; m <<= 1) {                                       // over the tile's channels: the same in every thread
-    dmin = min(dmin, __shfl_xor(dmin, m));
-    dmax = max(dmax, __shfl_xor(dmax, m));
-  }
+  tile_delay_range<BPV>(dmin, dmax);
   const long long nrows = (long long)p.nrows;
   const long long base = cd.t0 + (long long)j0 * (long long)p.tfactor + (long long)dmin;     // the file row of LDS row 0
   const long long span = (long long)nb * p.tfactor + ((long long)dmax - (long long)dmin);
   if (span > CAP) return;                                                  // (the plan rule never launches such a run)
   const size_t stride = (size_t)p.nifs * p.nchan * BPV, pstride = (size_t)p.nchan * BPV;
-  const unsigned char* src = p.rows + (size_t)p.p0 * pstride + (size_t)tile * 64;
-  for (int i = tid; i < (int)span * (ROWB / 16); i += kDmThreads) {
-    const long long row = base + (long long)(i / (ROWB / 16));
-    if (row >= 0 && row < nrows)
-      *reinterpret_cast<uint4*>(smem + (size_t)i * 16) =
-          *reinterpret_cast<const uint4*>(src + (size_t)row * stride + (size_t)((i >> 2) % NP) * pstride + (size_t)(i & 3) * 16);
-  }
+  tile_stage<NP>(smem, p.rows + (size_t)p.p0 * pstride + (size_t)tile * 64, stride, pstride, base, (int)span, nrows, tid);
   __syncthreads();
   for (int jb0 = 0; jb0 < nb; jb0 += BPP) {                                // (the same trips in every thread: the shuffles meet whole waves)
     const int jb = jb0 + jl;
@@ -1348,17 +1347,11 @@ __global__ void __launch_bounds__(kDmThreads) frbch_post_dynspec_fast(DynParams 
       long long lo, hi;
       burst_clip(b0, (uint32_t)p.tfactor, (long long)delay, nrows, &lo, &hi);
       if (hi > lo) {
-        uint32_t S = 0;
+        uint32_t S[1] = {0};
         const unsigned char* q = smem + (size_t)(lo - base) * ROWB + (size_t)ch * BPV;
-        for (long long t = lo; t < hi; ++t, q += ROWB) {
-#pragma unroll
-          for (int pr = 0; pr < NP; ++pr) {
-            if constexpr (BPV == 1) S += (uint32_t)q[pr * 64];
-            else S += (uint32_t)*reinterpret_cast<const uint16_t*>(q + pr * 64);
-          }
-        }
+        for (long long t = lo; t < hi; ++t, q += ROWB) tile_row_add<BPV, NP>(q, S);
         h = (uint32_t)(hi - lo);
-        a = dm_term(r.mean, r.w, cd.scale, S, h);
+        a = dm_term(r.mean, r.w, cd.scale, S[0], h);
       }
     }
     for (int m = 1; m < p.gl; m <<= 1) {

@@ -1664,8 +1664,8 @@ def _scrunched(prof, hits, hdr, f0, dm, fscrunch_to):
 
 
 def _unit(img):
-    img = img - img.mean(axis=1, keepdims=True)
-    return (img - img.min()) / max(1e-30, img.max() - img.min())
+    """an image scaled to 0 .. 1, for the plots"""
+    return (img - img.min()) / max(1e-30, float(img.max() - img.min()))
 
 
 def _trace_panel(i, l, v, pa, height):
@@ -1847,6 +1847,16 @@ def burst_spectra(fil_or_rows, hdr: dict, cands, gains=None, products: str = "st
     return spec, noise, used
 
 
+def _flag_arg(flag, nchan: int):
+    """``flag`` of the burst analyses as the library's uint8 [nchan] mask, or None"""
+    if flag is None:
+        return None
+    fl = np.ascontiguousarray(flag, dtype=np.uint8)
+    if fl.shape != (nchan,):
+        raise InputError("flag must have the shape [nchans]")
+    return fl
+
+
 def rm_params(nphi: int, phi_lo: float, dphi: float) -> _lib.FrbchRmParams:
     return _lib.FrbchRmParams(C.sizeof(_lib.FrbchRmParams), int(nphi), float(phi_lo), float(dphi))
 
@@ -1927,9 +1937,7 @@ def burst_rm(fil_or_rows, hdr: dict, cands, nphi: int, phi_lo: float, dphi: floa
     used = np.zeros((n, nchan), np.uint8)
     F = np.zeros((n, int(nphi), 2), np.float32)
     res = np.zeros(n, dtype=RM_RESULT)
-    fl = None if flag is None else np.ascontiguousarray(flag, dtype=np.uint8)
-    if fl is not None and fl.shape != (nchan,):
-        raise InputError("flag must have the shape [nchans]")
+    fl = _flag_arg(flag, nchan)
     rpar = rm_params(nphi, phi_lo, dphi)
     k = (C.c_uint32 * 3)(0, 0, 1)
     err = C.create_string_buffer(512)
@@ -2072,9 +2080,7 @@ def pol_profile(fil_or_rows, hdr: dict, cands, rm, nbin: int = 256, tfactor: int
     rows, nrows, cands, par, g = _burst_args(fil_or_rows, hdr, cands, gains, products)
     n, nchan = cands.size, hdr["nchans"]
     rm = np.ascontiguousarray(np.broadcast_to(np.asarray(rm, dtype=np.float64), (n,)))
-    fl = None if flag is None else np.ascontiguousarray(flag, dtype=np.uint8)
-    if fl is not None and fl.shape != (nchan,):
-        raise InputError("flag must have the shape [nchans]")
+    fl = _flag_arg(flag, nchan)
     ppar = prof_params(nbin, tfactor, ref)
     nb = max(1, min(int(nbin), 1024))
     acc = np.zeros((n, nb, 4), np.int64)
@@ -2199,9 +2205,7 @@ def dm_scan(fil_or_rows, hdr: dict, cands, ntrial: int, ddm: float, nbin: int = 
     lib = lib or _lib.load()
     rows, nrows, cands, par, _g = _burst_args(fil_or_rows, hdr, cands, None, products)
     n, nchan = cands.size, hdr["nchans"]
-    fl = None if flag is None else np.ascontiguousarray(flag, dtype=np.uint8)
-    if fl is not None and fl.shape != (nchan,):
-        raise InputError("flag must have the shape [nchans]")
+    fl = _flag_arg(flag, nchan)
     dpar, pk = dmscan_params(ntrial, ddm, nbin, tfactor), dmscan_peak_params(widths, smooth, fit_frac)
     nt, nb = max(1, min(int(ntrial), 4096)), max(1, min(int(nbin), 1024))
     if n * nt * nb > 1 << 24:
@@ -2387,9 +2391,7 @@ def burst_acf(fil_or_rows, hdr: dict, cands, nbin: int = 256, tfactor: int = 1, 
     lib = lib or _lib.load()
     rows, nrows, cands, par, _g = _burst_args(fil_or_rows, hdr, cands, None, products)
     n, nchan = cands.size, hdr["nchans"]
-    fl = None if flag is None else np.ascontiguousarray(flag, dtype=np.uint8)
-    if fl is not None and fl.shape != (nchan,):
-        raise InputError("flag must have the shape [nchans]")
+    fl = _flag_arg(flag, nchan)
     ffactor = int(ffactor)
     if ffactor < 1 or ffactor > nchan or nchan % ffactor:
         raise InputError("ffactor must be 1..nchans and divide nchans")
@@ -2423,10 +2425,6 @@ def _resample(img, height, width):
     r = np.clip((np.arange(height) * img.shape[0]) // height, 0, img.shape[0] - 1)
     c = np.clip((np.arange(width) * img.shape[1]) // width, 0, img.shape[1] - 1)
     return img[r][:, c]
-
-
-def _unit(img):
-    return (img - img.min()) / max(1e-30, float(img.max() - img.min()))
 
 
 def _acf_panels(acf, i):
@@ -2567,9 +2565,7 @@ def burst_scatter(fil_or_rows, hdr: dict, cands, nbin: int = 256, tfactor: int =
     lib = lib or _lib.load()
     rows, nrows, cands, par, _g = _burst_args(fil_or_rows, hdr, cands, None, products)
     n, nchan = cands.size, hdr["nchans"]
-    fl = None if flag is None else np.ascontiguousarray(flag, dtype=np.uint8)
-    if fl is not None and fl.shape != (nchan,):
-        raise InputError("flag must have the shape [nchans]")
+    fl = _flag_arg(flag, nchan)
     ffactor = int(ffactor)
     if ffactor < 1 or ffactor > nchan or nchan % ffactor:
         raise InputError("ffactor must be 1..nchans and divide nchans")

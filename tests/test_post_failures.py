@@ -12,7 +12,11 @@ the file).  A case is one (entry point, n):
     statistics are held to their restatements as well, in a test of their own).
 The shapes are the smallest of each family in tests/bounds_cases.py (whose expected bytes the plain call's are: that suite holds
 the same calls to the restatements), the interference case of tests/resident_cases.py cut to 3000 rows for frbch_candidates_*,
-and two products for frbch_rfi_cleanp_*.  Integer rows throughout: their sums have one value in any order."""
+and two products for frbch_rfi_cleanp_*.  Integer rows throughout: their sums have one value in any order.
+The burst family (frbch_burstspec_* to frbch_burstscat_*, both twins of each) joined the table later, recorded in the same way
+on the commit BEFORE its entry points were rewritten around burst_device_call / burst_host_twin: each family in the shape of its
+own walk test (tests/test_polprof.py, test_dmscan.py, test_acf.py, test_scat.py, both cases of the last two), the three-candidate
+case of tests/test_rm.py, and the small planes of tests/test_acf.py and tests/test_scat.py for the two stages."""
 import ctypes as C
 import json
 import os
@@ -22,12 +26,17 @@ import numpy as np
 import pytest
 
 from frb_baseband_amd import _lib, cornerturn as ct, post
+from tests import acf_cases as ac
 from tests import cutout_cases as cc
 from tests import cutout_oracle as co
+from tests import dmscan_cases as dmc
+from tests import polprof_cases as ppc
 from tests import post_cases as pc
 from tests import resident_cases as rs
 from tests import rfi_cases as rc
 from tests import rfi_oracle as ro
+from tests import rm_cases as rmc
+from tests import scat_cases as scc
 from tests import spsearch_cases as sc
 from tests.hipmem import GUARD, POISON, HostGuardedBuffer
 from tests.test_spsearch import dispersed_burst_rows
@@ -266,6 +275,131 @@ def _candidates(twin):
     return make
 
 
+# ---- the burst family: the shapes of each family's own walk test (tests/test_polprof.py, test_dmscan.py, test_acf.py, test_scat.py),
+# ---- the three-candidate case of tests/test_rm.py and the small planes of the two stages -------------------------------------------
+def _kused(e, n):
+    k = (C.c_uint32 * n)(*([99] * n))
+    e.keep.append(k)
+    return k
+
+
+def _opt(e, arr):
+    return e.inp(arr) if arr is not None else None
+
+
+def _burst_head(e, hdr, rows, cands, coh, product=0):
+    """fil, rows, nrows, burst params, cands, ncand: what every composite of the family begins with"""
+    fil = post.fil_desc(dict(hdr, nifs=rows.shape[1], nbits=rows.dtype.itemsize * 8), product)
+    return [e.hold(fil), e.inp(rows), rows.shape[0], e.hold(rmc.burst_par(coh)), e.inp(cands), cands.size]
+
+
+def _burstspec(twin):
+    def make(lib):
+        e = Entry(lib, "frbch_burstspec_" + twin)
+        hdr, rows, cands, coh = rmc.case("u8_64ch_3cand")
+        n = cands.size * 4 * 64
+        e.args = _burst_head(e, hdr, rows, cands, coh) + [None, 0, e.out(n * 32), e.out(n * 4), e.out(n * 4), e.out(cands.size * 64),
+                                                          e.hold(C.c_uint32(99))]
+        e.want = lambda: [np.ascontiguousarray(a).tobytes() for a in rmc.want_spectra("u8_64ch_3cand")]
+        return e
+    return make
+
+
+def _rmsynth(twin):
+    def make(lib):
+        e = Entry(lib, "frbch_rmsynth_" + twin)
+        hdr, q, u, used = rmc.spectra(64, 3, 0, (3, 40))
+        e.args = [e.hold(post.fil_desc(hdr)), e.inp(q), e.inp(u), e.inp(used), 3, e.hold(post.rm_params(**rmc.GRID)), 0,
+                  e.out(3 * rmc.GRID["nphi"] * 8), _kused(e, 2)]
+        e.want = lambda: [rmc.want_transform(64, 3, rmc.GRID["nphi"], rmc.GRID["phi_lo"], rmc.GRID["dphi"], 0, (3, 40)).tobytes()]
+        return e
+    return make
+
+
+def _burst_rm(twin):
+    def make(lib):
+        e = Entry(lib, "frbch_burst_rm_" + twin)
+        hdr, rows, cands, coh = rmc.case("u8_64ch_3cand")
+        n, nphi = cands.size * 64, rmc.GRID["nphi"]
+        e.args = _burst_head(e, hdr, rows, cands, coh) + [None, None, e.hold(post.rm_params(**rmc.GRID)), 0, e.out(n * 16), e.out(n * 16), e.out(n),
+                                                          e.out(cands.size * nphi * 8), e.out(cands.size * post.RM_RESULT.itemsize), _kused(e, 3)]
+        return e
+    return make
+
+
+def _polprof(twin):
+    def make(lib):
+        e = Entry(lib, "frbch_polprof_" + twin)
+        c = ppc.case("u8_64ch_33x3")
+        n, nbin = c["cands"].size, c["nbin"]
+        e.args = _burst_head(e, c["hdr"], c["rows"], c["cands"], c["coh"]) + [
+            e.inp(c["rm"]), _opt(e, c["gain"]), _opt(e, c["flag"]), e.hold(ppc.par_of(c)), 0, e.out(n * nbin * 32), e.out(n * nbin * 4),
+            e.out(n * nbin * post.PROF_BIN.itemsize), e.out(n * post.PROF_RESULT.itemsize), e.out(n * 64), _kused(e, 2)]
+        return e
+    return make
+
+
+def _dmscan(twin):
+    def make(lib):
+        e = Entry(lib, "frbch_dmscan_" + twin)
+        c = dmc.case("u8_64ch_33x33x3")
+        n, nt, nbin = c["cands"].size, c["ntrial"], c["nbin"]
+        e.args = _burst_head(e, c["hdr"], c["rows"], c["cands"], c["coh"], c["hdr"].get("product", 0)) + [
+            _opt(e, c["flag"]), e.hold(dmc.par_of(c)), e.hold(dmc.peak_par_of(c)), 0, e.out(n * nt * nbin * 8), e.out(n * nt * nbin * 4),
+            e.out(n * nt * 8), e.out(n * nt * 8), e.out(n * post.DMSCAN_RESULT.itemsize), e.out(n * c["hdr"]["nchans"]), _kused(e, 2)]
+        w = dmc.want("u8_64ch_33x33x3")
+        e.want = lambda: [np.ascontiguousarray(w[f]).tobytes() for f in ("acc", "hits", "snr", "struct", "results", "used")]
+        return e
+    return make
+
+
+def _acf2d(twin):
+    def make(lib):
+        e = Entry(lib, "frbch_acf2d_" + twin)
+        name = "random_3x5_full_lags"
+        n, nsub, nbin, lf, lt, _kind = ac.PLANES[name]
+        e.args = [e.inp(ac.plane(name)), n, nsub, nbin, lf, lt, _lib.ACF_PLAN, 0, e.out(n * lf * (2 * lt - 1) * 8), e.hold(C.c_uint32(99))]
+        e.want = lambda: [ac.plane_want(name).tobytes()]
+        return e
+    return make
+
+
+def _burstacf(twin, name):
+    def make(lib):
+        e = Entry(lib, "frbch_burstacf_" + twin)
+        c = ac.case(name)
+        out = ac.outputs_of(c)
+        e.args = _burst_head(e, c["hdr"], c["rows"], c["cands"], c["coh"], c["hdr"].get("product", 0)) + [
+            _opt(e, c["flag"]), e.hold(ac.par_of(c)), e.hold(ac.fit_par_of(c)), 0] + [
+            e.out(out[f].nbytes) for f in ("Y", "yhits", "A", "P", "results", "used")] + [_kused(e, 3)]
+        return e
+    return make
+
+
+def _tbank(twin):
+    def make(lib):
+        e = Entry(lib, "frbch_tbank_" + twin)
+        name = "three_planes"
+        y, P = scc.plane(name)
+        e.args = [e.inp(y), e.inp(P), scc.PLANES[name][0], e.hold(scc.shape_of(name)), _lib.TBANK_PLAN, 0, e.out(scc.plane_want(name).nbytes),
+                  e.hold(C.c_uint32(99))]
+        e.want = lambda: [scc.plane_want(name).tobytes()]
+        return e
+    return make
+
+
+def _burstscat(twin, name):
+    def make(lib):
+        e = Entry(lib, "frbch_burstscat_" + twin)
+        c = scc.case(name)
+        out = scc.outputs_of(c)
+        e.args = _burst_head(e, c["hdr"], c["rows"], c["cands"], c["coh"], c["hdr"].get("product", 0)) + [
+            _opt(e, c["flag"]), e.hold(scc.par_of(c)), e.hold(scc.bank_par(c["bp"])), e.hold(scc.fit_par_of(c)), 0] + [
+            e.out(out[f].nbytes) for f in ("Y", "yhits", "y", "C", "N", "sub", "band", "used")] + [_kused(e, 3)]
+        return e
+    return make
+
+
 ENTRIES = {}
 for _twin in ("device", "host"):
     ENTRIES["dedisperse_" + _twin] = _dedisperse(_twin, 1, 1, False, 0.0)
@@ -280,6 +414,13 @@ for _twin in ("device", "host"):
     ENTRIES["rfi_cleanp_2products_" + _twin] = _rfi("cleanp", _twin, nifs=2)
     ENTRIES["cornerturn_" + _twin] = _cornerturn(_twin)
     ENTRIES["candidates_rfi_planes_" + _twin] = _candidates(_twin)
+    for _name, _make in (("burstspec", _burstspec), ("rmsynth", _rmsynth), ("burst_rm", _burst_rm), ("polprof", _polprof), ("dmscan", _dmscan),
+                         ("acf2d", _acf2d), ("tbank", _tbank)):
+        ENTRIES["%s_%s" % (_name, _twin)] = _make(_twin)
+    for _case in ("u8_64ch_f4_full_lags", "u8_64ch_flag_constant_dead"):                        # (the second counts its pairs on the device)
+        ENTRIES["burstacf_%s_%s" % (_case, _twin)] = _burstacf(_twin, _case)
+    for _case in ("u8_64ch_f4_mixed_dms", "u8_64ch_flag_dead_subband"):                         # (the second forms N on the device)
+        ENTRIES["burstscat_%s_%s" % (_case, _twin)] = _burstscat(_twin, _case)
 ENTRIES["dedisperse_search_host"] = _dedisperse_search
 
 _made = {}

@@ -4,7 +4,7 @@ cur = None; rows = {}
 for l in open(sys.argv[1]) if len(sys.argv) > 1 else sys.stdin:
     m = re.search(r'Function Name: (\S+)', l)
     if m: cur = m.group(1); rows[cur] = {}; continue
-    m = re.search(r'remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+) \[-R', l)
+    m = re.search(r'remark:\s+(?:\S+:\d+:\d+:\s+)?([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+) \[-R', l)    # (with or without file:line:col)
     if m and cur: rows[cur][m.group(1).strip()] = int(m.group(2))
 names = subprocess.run(['c++filt'] + list(rows), capture_output=True, text=True).stdout.split('\n')
 for n, (k, v) in zip(names, rows.items()):
