@@ -86,6 +86,21 @@ class FrbchSpGroup(C.Structure):
                 ("reserved", C.c_uint32), ("sample_lo", C.c_uint64), ("sample_hi", C.c_uint64)]
 
 
+class FrbchBandParams(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("nsub", C.c_uint32), ("min_sub", C.c_uint32), ("max_sub", C.c_uint32)]
+
+
+class FrbchSpbCand(C.Structure):
+    _fields_ = [("dm_index", C.c_uint32), ("width", C.c_uint32), ("sample", C.c_uint64), ("sigma", C.c_float),
+                ("sub_lo", C.c_uint16), ("sub_hi", C.c_uint16)]
+
+
+class FrbchSpbGroup(C.Structure):
+    _fields_ = [("best", FrbchSpbCand), ("nmember", C.c_uint32), ("dm_index_lo", C.c_uint32), ("dm_index_hi", C.c_uint32),
+                ("sub_lo_min", C.c_uint16), ("sub_hi_max", C.c_uint16), ("sample_lo", C.c_uint64), ("sample_hi", C.c_uint64),
+                ("full_sigma", C.c_float), ("reserved", C.c_uint32)]
+
+
 class FrbchPsParams(C.Structure):
     _fields_ = [("size", C.c_uint32), ("nfft", C.c_uint32), ("nharm", C.c_uint32), ("wblock", C.c_uint32),
                 ("sigma", C.c_double), ("flo_hz", C.c_double), ("tsamp_s", C.c_double)]
@@ -352,6 +367,25 @@ SYMBOLS = {
                                        C.c_size_t]),
     "frbch_sp_group_cands": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint32, _P, C.c_uint64, C.c_uint32, _P, C.c_uint64,
                                        C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
+    "frbch_band_list": (C.c_int, [C.c_uint32, C.POINTER(FrbchBandParams), _P, _P, C.c_uint32, C.POINTER(C.c_uint32), C.c_char_p,
+                                  C.c_size_t]),
+    "frbch_dedisperse_bands_kernel": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, _P, C.c_uint32, C.POINTER(FrbchBandParams)]),
+    "frbch_dedisperse_bands_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_double,
+                                                C.POINTER(FrbchBandParams), C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64),
+                                                C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_dedisperse_bands_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_double,
+                                              C.POINTER(FrbchBandParams), C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64),
+                                              C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_bandsearch_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_double,
+                                          C.POINTER(FrbchBandParams), C.POINTER(FrbchSpParams), C.c_uint64, C.c_int, C.c_uint64,
+                                          C.POINTER(C.c_uint64), _P, C.c_uint64, C.POINTER(C.c_uint64), _P, C.POINTER(C.c_uint32),
+                                          _P, C.c_char_p, C.c_size_t]),
+    "frbch_bandsearch_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_double,
+                                        C.POINTER(FrbchBandParams), C.POINTER(FrbchSpParams), C.c_uint64, C.c_int, C.c_uint64,
+                                        C.POINTER(C.c_uint64), _P, C.c_uint64, C.POINTER(C.c_uint64), _P, C.POINTER(C.c_uint32),
+                                        _P, C.c_char_p, C.c_size_t]),
+    "frbch_spb_group_cands": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.c_uint32, _P,
+                                        C.c_uint64, C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
     "frbch_cutout_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchCutoutParams), _P, C.c_uint32, C.c_int,
                                       _P, _P, _P, _P, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
     "frbch_cutout_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchCutoutParams), _P, C.c_uint32, C.c_int,

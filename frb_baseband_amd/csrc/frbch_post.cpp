@@ -8,6 +8,7 @@
 
 using namespace frbchi;
 
+#include <chrono>
 #include <limits>
 #include <memory>
 #include <new>
@@ -243,60 +244,15 @@ bool post_dedisp_tiled(const frbch_fil_desc* fil, const void* d_rows, const std:
 #endif
 }
 
-}  // namespace
-
-extern "C" long frbch_dedisperse_nout(const frbch_fil_desc* fil, uint64_t nrows, const double* dms, uint32_t ndm) {
-  PostErr e{nullptr, 0};
-  if (post_check_fil(fil, nrows, e) || !dms || !ndm) return FRBCH_E_ARG;
-  for (uint32_t i = 0; i < ndm; ++i)
-    if (!(dms[i] >= 0.0) || !(dms[i] < 1.0e5)) return FRBCH_E_ARG;
-  int64_t maxd = 0;
-  (void)post_delays(fil, dms, ndm, &maxd);
-  return (int64_t)nrows > maxd ? (long)((int64_t)nrows - maxd) : 0;
-}
-
-extern "C" int frbch_dedisperse_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const double* dms,
-                                       uint32_t ndm) {
-  if (!d_rows || frbch_dedisperse_nout(fil, nrows, dms, ndm) <= 0) return FRBCH_E_ARG;   // what frbch_dedisperse_device refuses
-  int64_t maxd = 0;
-  const std::vector<int32_t> delays = post_delays(fil, dms, ndm, &maxd);
-  std::vector<int32_t> range;
-  return post_dedisp_tiled(fil, d_rows, delays, ndm, &range) ? 1 : 0;
-}
-
-extern "C" int frbch_dedisperse_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const double* dms,
-                                       uint32_t ndm, uint32_t zerodm, double clip_sigma, int device, float* d_out,
-                                       uint64_t nout, uint64_t* nclipped, char* err, size_t err_cap) try {
-  PostErr e{err, err_cap};
-  int rc = post_check_fil(fil, nrows, e);
-  if (rc) return rc;
-  if (!d_rows || !d_out || !dms || !ndm) return e.fail(FRBCH_E_ARG, "null argument");
-  const long want = frbch_dedisperse_nout(fil, nrows, dms, ndm);
-  if (want <= 0) return e.fail(FRBCH_E_ARG, "the largest dispersion delay exceeds the data");
-  if ((uint64_t)want != nout) return e.fail(FRBCH_E_CAPACITY, "nout must be frbch_dedisperse_nout()");
-  if ((rc = post_check_device(device, e)) != 0) return rc;
-  DeviceGuard dg(device);
-  int64_t maxd = 0;
-  const std::vector<int32_t> delays = post_delays(fil, dms, ndm, &maxd);
-  const uint64_t nchunk = (nrows + kPostChunkRows - 1) / kPostChunkRows;
-  double *d_rowsum = nullptr, *d_colsum = nullptr, *d_repl = nullptr;
-  uint8_t* d_flag = nullptr;
-  int32_t* d_delays = nullptr;
-  PostScope ps;
-  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+// The clip and zero-DM pre-pass of frbch_dedisperse_* on the stream of `ps`: S[t] into p.rowsum (the caller's, [nrows]) where
+// it is needed, then the clip -- flags, replacement values and S[t] of the clipped rows, in blocks `ps` holds; p.flagged and
+// p.repl are set when a row clips.  It depends on the rows alone, not on the DMs: frbch_bandsearch_* run it once for all batches.
+int post_dedisp_prepass(PostScope& ps, const PostErr& e, const frbch_fil_desc* fil, uint64_t nrows, uint32_t zerodm,
+                        double clip_sigma, PostParams& p, uint64_t* nclip) {
   const dev_stream_t s = ps.s;
-  POST_DEV(ps.alloc(&d_rowsum, nrows * sizeof(double)), "hipMalloc");
-  POST_DEV(ps.alloc(&d_delays, delays.size() * sizeof(int32_t)), "hipMalloc");
-  POST_DEV(dev_h2d(d_delays, delays.data(), delays.size() * sizeof(int32_t), s), "upload delays");
-  PostParams p = post_params<PostParams>(fil, d_rows, nrows);
-  p.prod = (int)fil->product;
-  p.rowsum = d_rowsum;
-  p.delays = d_delays;
-  p.out = d_out;
-  p.nout = nout;
-  p.ndm = (int)ndm;
-  p.zerodm = zerodm ? 1 : 0;
-  p.rows_per_chunk = kPostChunkRows;
+  const uint64_t nchunk = (nrows + kPostChunkRows - 1) / kPostChunkRows;
+  double *d_colsum = nullptr, *d_repl = nullptr;
+  uint8_t* d_flag = nullptr;
   uint64_t nflag = 0;
   if (clip_sigma > 0.0 || zerodm) {
     DEV_LAUNCH(frbch_post_rowsum, (nrows + 255) / 256, 1, 256, 0, s, p);
@@ -306,7 +262,7 @@ extern "C" int frbch_dedisperse_device(const frbch_fil_desc* fil, const void* d_
     // time-domain clip on the zero-DM series S[t] (the sum over channels): two rounds of mean / sigma, the second without
     // the samples the first one flagged; a flagged time sample reads as the channel means of the unflagged ones
     std::vector<double> S(nrows);
-    POST_DEV(dev_d2h(S.data(), d_rowsum, nrows * sizeof(double), s), "download row sums");
+    POST_DEV(dev_d2h(S.data(), p.rowsum, nrows * sizeof(double), s), "download row sums");
     POST_DEV(dev_sync(s), "sync");
     std::vector<uint8_t> flag(nrows, 0);
     for (int round = 0; round < 2; ++round) {
@@ -350,6 +306,64 @@ extern "C" int frbch_dedisperse_device(const frbch_fil_desc* fil, const void* d_
       nflag = 0;
     }
   }
+  *nclip = nflag;
+  return FRBCH_OK;
+}
+
+}  // namespace
+
+extern "C" long frbch_dedisperse_nout(const frbch_fil_desc* fil, uint64_t nrows, const double* dms, uint32_t ndm) {
+  PostErr e{nullptr, 0};
+  if (post_check_fil(fil, nrows, e) || !dms || !ndm) return FRBCH_E_ARG;
+  for (uint32_t i = 0; i < ndm; ++i)
+    if (!(dms[i] >= 0.0) || !(dms[i] < 1.0e5)) return FRBCH_E_ARG;
+  int64_t maxd = 0;
+  (void)post_delays(fil, dms, ndm, &maxd);
+  return (int64_t)nrows > maxd ? (long)((int64_t)nrows - maxd) : 0;
+}
+
+extern "C" int frbch_dedisperse_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const double* dms,
+                                       uint32_t ndm) {
+  if (!d_rows || frbch_dedisperse_nout(fil, nrows, dms, ndm) <= 0) return FRBCH_E_ARG;   // what frbch_dedisperse_device refuses
+  int64_t maxd = 0;
+  const std::vector<int32_t> delays = post_delays(fil, dms, ndm, &maxd);
+  std::vector<int32_t> range;
+  return post_dedisp_tiled(fil, d_rows, delays, ndm, &range) ? 1 : 0;
+}
+
+extern "C" int frbch_dedisperse_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const double* dms,
+                                       uint32_t ndm, uint32_t zerodm, double clip_sigma, int device, float* d_out,
+                                       uint64_t nout, uint64_t* nclipped, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  int rc = post_check_fil(fil, nrows, e);
+  if (rc) return rc;
+  if (!d_rows || !d_out || !dms || !ndm) return e.fail(FRBCH_E_ARG, "null argument");
+  const long want = frbch_dedisperse_nout(fil, nrows, dms, ndm);
+  if (want <= 0) return e.fail(FRBCH_E_ARG, "the largest dispersion delay exceeds the data");
+  if ((uint64_t)want != nout) return e.fail(FRBCH_E_CAPACITY, "nout must be frbch_dedisperse_nout()");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  int64_t maxd = 0;
+  const std::vector<int32_t> delays = post_delays(fil, dms, ndm, &maxd);
+  double* d_rowsum = nullptr;
+  int32_t* d_delays = nullptr;
+  PostScope ps;
+  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  const dev_stream_t s = ps.s;
+  POST_DEV(ps.alloc(&d_rowsum, nrows * sizeof(double)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_delays, delays.size() * sizeof(int32_t)), "hipMalloc");
+  POST_DEV(dev_h2d(d_delays, delays.data(), delays.size() * sizeof(int32_t), s), "upload delays");
+  PostParams p = post_params<PostParams>(fil, d_rows, nrows);
+  p.prod = (int)fil->product;
+  p.rowsum = d_rowsum;
+  p.delays = d_delays;
+  p.out = d_out;
+  p.nout = nout;
+  p.ndm = (int)ndm;
+  p.zerodm = zerodm ? 1 : 0;
+  p.rows_per_chunk = kPostChunkRows;
+  uint64_t nflag = 0;
+  if ((rc = post_dedisp_prepass(ps, e, fil, nrows, zerodm, clip_sigma, p, &nflag)) != 0) return rc;
   std::vector<int32_t> range;
   const bool tiled = post_dedisp_tiled(fil, d_rows, delays, ndm, &range);
 #ifndef FRBCH_NO_FAST
@@ -1749,22 +1763,10 @@ bool sp_better(const frbch_sp_cand& a, const frbch_sp_cand& b) {        // a rep
   if (a.dm_index != b.dm_index) return a.dm_index < b.dm_index;
   return a.sample < b.sample;
 }
-}  // namespace
-
-extern "C" int frbch_sp_group_cands(const frbch_fil_desc* fil, const double* dms, uint32_t ndm, const frbch_sp_cand* cands,
-                                    uint64_t ncand, uint32_t dm_gap, frbch_sp_group* groups, uint64_t cap, uint64_t* ngroup,
-                                    char* err, size_t err_cap) {
-  PostErr e{err, err_cap};
-  int rc = post_check_fil(fil, 1, e);
-  if (rc) return rc;
-  if (!dms || !ndm || !ngroup || (ncand && !cands) || (cap && !groups)) return e.fail(FRBCH_E_ARG, "null argument");
-  if (dm_gap < 1 || dm_gap > 16) return e.fail(FRBCH_E_ARG, "dm_gap must be 1..16");
-  for (uint32_t i = 0; i < ndm; ++i)
-    if (!(dms[i] >= 0.0) || !(dms[i] < 1.0e5)) return e.fail(FRBCH_E_ARG, "a DM outside [0, 1e5)");
-  for (uint64_t i = 0; i < ncand; ++i)
-    if (cands[i].dm_index >= ndm) return e.fail(FRBCH_E_ARG, "record " + std::to_string(i) + ": dm_index >= ndm");
-  *ngroup = 0;
-  if (!ncand) return FRBCH_OK;
+// The link rule of frbch_sp_group_cands on records with dm_index, sample and width (frbch_sp_cand, frbch_spb_cand):
+// -> for every record the smallest index of its group, the connected component of the link graph.
+template <class Rec> std::vector<uint64_t> sp_link(const frbch_fil_desc* fil, const double* dms, uint32_t ndm, const Rec* cands,
+                                                   uint64_t ncand, uint32_t dm_gap) {
   // D_i: the largest delay of DM i, and the largest |D_a - D_b| two linked records can have
   int64_t maxd = 0;
   const std::vector<int32_t> delays = post_delays(fil, dms, ndm, &maxd);
@@ -1788,9 +1790,9 @@ extern "C" int frbch_sp_group_cands(const frbch_fil_desc* fil, const double* dms
     return x;
   };
   for (uint64_t i = 0; i < ncand; ++i) {
-    const frbch_sp_cand& a = cands[order[i]];
+    const Rec& a = cands[order[i]];
     for (uint64_t j = i + 1; j < ncand && cands[order[j]].sample - a.sample <= reach; ++j) {
-      const frbch_sp_cand& b = cands[order[j]];
+      const Rec& b = cands[order[j]];
       const uint32_t ddm = a.dm_index > b.dm_index ? a.dm_index - b.dm_index : b.dm_index - a.dm_index;
       if (ddm > dm_gap) continue;
       const uint64_t tol = (uint64_t)(std::max(a.width, b.width) / 2) + (uint64_t)std::llabs(D[a.dm_index] - D[b.dm_index]);
@@ -1799,10 +1801,31 @@ extern "C" int frbch_sp_group_cands(const frbch_fil_desc* fil, const double* dms
       if (ra != rb) parent[std::max(ra, rb)] = std::min(ra, rb);
     }
   }
+  std::vector<uint64_t> root(ncand);
+  for (uint64_t i = 0; i < ncand; ++i) root[i] = find(i);
+  return root;
+}
+}  // namespace
+
+extern "C" int frbch_sp_group_cands(const frbch_fil_desc* fil, const double* dms, uint32_t ndm, const frbch_sp_cand* cands,
+                                    uint64_t ncand, uint32_t dm_gap, frbch_sp_group* groups, uint64_t cap, uint64_t* ngroup,
+                                    char* err, size_t err_cap) {
+  PostErr e{err, err_cap};
+  int rc = post_check_fil(fil, 1, e);
+  if (rc) return rc;
+  if (!dms || !ndm || !ngroup || (ncand && !cands) || (cap && !groups)) return e.fail(FRBCH_E_ARG, "null argument");
+  if (dm_gap < 1 || dm_gap > 16) return e.fail(FRBCH_E_ARG, "dm_gap must be 1..16");
+  for (uint32_t i = 0; i < ndm; ++i)
+    if (!(dms[i] >= 0.0) || !(dms[i] < 1.0e5)) return e.fail(FRBCH_E_ARG, "a DM outside [0, 1e5)");
+  for (uint64_t i = 0; i < ncand; ++i)
+    if (cands[i].dm_index >= ndm) return e.fail(FRBCH_E_ARG, "record " + std::to_string(i) + ": dm_index >= ndm");
+  *ngroup = 0;
+  if (!ncand) return FRBCH_OK;
+  const std::vector<uint64_t> root = sp_link(fil, dms, ndm, cands, ncand, dm_gap);
   std::vector<int64_t> slot(ncand, -1);                                  // root -> index in `out`
   std::vector<frbch_sp_group> out;
   for (uint64_t i = 0; i < ncand; ++i) {
-    const uint64_t r = find(i);
+    const uint64_t r = root[i];
     const frbch_sp_cand& c = cands[i];
     if (slot[r] < 0) {
       slot[r] = (int64_t)out.size();
@@ -1836,8 +1859,401 @@ extern "C" int frbch_sp_group_cands(const frbch_fil_desc* fil, const double* dms
   return FRBCH_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// band-limited single-pulse search: the series of every range of sub-bands, their search in batches of DMs, the grouping
+// ---------------------------------------------------------------------------------------------------------------------
 namespace {
-constexpr uint64_t kCutTableCap = 1ull << 26;    // delay-table entries of one call (256 MiB); a longer batch is refused
+struct BandPlan {
+  uint32_t nsub = 0, cps = 0, wmin = 0, wmax = 0;
+  std::vector<uint16_t> ab;              // [nband][2] (a, b), ascending a, then b
+  uint32_t nband() const { return (uint32_t)(ab.size() / 2); }
+};
+
+int band_check(uint32_t nchan, const frbch_band_params* bp, BandPlan* plan, const PostErr& e) {
+  if (!bp || bp->size != sizeof(frbch_band_params)) return e.fail(FRBCH_E_ARG, "frbch_band_params: wrong size");
+  if (bp->nsub < 1 || bp->nsub > 16) return e.fail(FRBCH_E_ARG, "nsub must be 1..16");
+  if (!nchan || nchan % bp->nsub != 0) return e.fail(FRBCH_E_ARG, "nsub must divide nchan");
+  plan->nsub = bp->nsub;
+  plan->cps = nchan / bp->nsub;
+  plan->wmin = bp->min_sub ? bp->min_sub : 1;
+  plan->wmax = bp->max_sub ? bp->max_sub : bp->nsub;
+  if (plan->wmax > bp->nsub) return e.fail(FRBCH_E_ARG, "max_sub exceeds nsub");
+  if (plan->wmin > plan->wmax) return e.fail(FRBCH_E_ARG, "min_sub exceeds max_sub");
+  plan->ab.clear();
+  for (uint32_t a = 0; a < bp->nsub; ++a)
+    for (uint32_t b = a + plan->wmin; b <= bp->nsub && b - a <= plan->wmax; ++b) {
+      plan->ab.push_back((uint16_t)a);
+      plan->ab.push_back((uint16_t)b);
+    }
+  return FRBCH_OK;
+}
+
+// everything frbch_dedisperse_bands_* and frbch_bandsearch_* refuse before the device is looked at; fills *plan
+int bands_check(const frbch_fil_desc* fil, uint64_t nrows, const double* dms, uint32_t ndm, const frbch_band_params* bp,
+                BandPlan* plan, uint64_t nout, const PostErr& e) {
+  int rc = post_check_fil(fil, nrows, e);
+  if (rc) return rc;
+  if (!dms || !ndm) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = band_check(fil->nchan, bp, plan, e)) != 0) return rc;
+  if ((uint64_t)ndm * plan->nband() > 65535)
+    return e.fail(FRBCH_E_ARG, "ndm * nband = " + std::to_string((uint64_t)ndm * plan->nband()) + " series, the search takes 65535");
+  const long want = frbch_dedisperse_nout(fil, nrows, dms, ndm);
+  if (want < 0) return e.fail(FRBCH_E_ARG, "a DM outside [0, 1e5)");
+  if (want == 0) return e.fail(FRBCH_E_ARG, "the largest dispersion delay exceeds the data");
+  if ((uint64_t)want != nout) return e.fail(FRBCH_E_CAPACITY, "nout must be frbch_dedisperse_nout()");
+  return FRBCH_OK;
+}
+
+// Which form a run of DMs takes -- the one decision behind the launch, *kernel_used and frbch_dedisperse_bands_kernel's
+// answer.  true = the tiled prefix kernel + the range kernel: integer rows, a running sum that fits uint32, a sub-band of whole
+// channel tiles, and the tiled dedispersion's own conditions (post_dedisp_tiled; *range is its table).
+bool bands_tiled(const frbch_fil_desc* fil, const void* d_rows, const std::vector<int32_t>& delays, uint32_t ndm, const BandPlan& plan,
+                 std::vector<int32_t>* range) {
+  if (fil->nbits != 8 && fil->nbits != 16) return false;
+  if (fil->nchan > 65536 || plan.cps % (64 / (fil->nbits / 8)) != 0) return false;
+  return post_dedisp_tiled(fil, d_rows, delays, ndm, range);
+}
+
+#ifndef FRBCH_NO_FAST
+template <int B> int launch_bands_tiled(bool flagged, bool zerodm, dim3 grid, size_t lds, dev_stream_t s, const PostParams& p) {
+  if (flagged && zerodm) return launch_lds(fast::frbch_post_dedisp_bands_tiled<B, true, true>, grid, dim3(256), lds, s, p);
+  if (flagged) return launch_lds(fast::frbch_post_dedisp_bands_tiled<B, true, false>, grid, dim3(256), lds, s, p);
+  if (zerodm) return launch_lds(fast::frbch_post_dedisp_bands_tiled<B, false, true>, grid, dim3(256), lds, s, p);
+  return launch_lds(fast::frbch_post_dedisp_bands_tiled<B, false, false>, grid, dim3(256), lds, s, p);
+}
+#endif
+
+// What a bands dedispersion holds on the device next to the pre-pass: the band list, and per run of at most `ndm_cap` DMs the
+// delays, the tile table and the prefix planes of the tiled form (allocated when a run first takes it).
+struct BandsDev {
+  uint16_t* d_ab = nullptr;
+  int32_t *d_delays = nullptr, *d_range = nullptr;
+  uint32_t* d_pre = nullptr;
+  double* d_prez = nullptr;
+  uint32_t ndm_cap = 0;
+};
+
+int bands_dev_init(PostScope& ps, const PostErr& e, const frbch_fil_desc* fil, const BandPlan& plan, uint32_t ndm_cap, BandsDev* bd) {
+  bd->ndm_cap = ndm_cap;
+  POST_DEV(ps.alloc(&bd->d_ab, plan.ab.size() * sizeof(uint16_t)), "hipMalloc");
+  POST_DEV(dev_h2d(bd->d_ab, plan.ab.data(), plan.ab.size() * sizeof(uint16_t), ps.s), "upload bands");
+  POST_DEV(ps.alloc(&bd->d_delays, (size_t)ndm_cap * fil->nchan * sizeof(int32_t)), "hipMalloc");
+  return FRBCH_OK;
+}
+
+// One run of consecutive DMs on the stream of `ps`, behind the pre-pass (p holds its results): d_out [ndm * nband][nout].
+// Synchronous: the stream is idle when it returns.  *tiled_out: the form taken.
+int bands_run(PostScope& ps, const PostErr& e, const frbch_fil_desc* fil, const void* d_rows, PostParams p, const BandPlan& plan,
+              BandsDev& bd, const double* dms, uint32_t ndm, float* d_out, bool* tiled_out) {
+  const dev_stream_t s = ps.s;
+  int64_t maxd = 0;
+  const std::vector<int32_t> delays = post_delays(fil, dms, ndm, &maxd);
+  POST_DEV(dev_h2d(bd.d_delays, delays.data(), delays.size() * sizeof(int32_t), s), "upload delays");
+  p.delays = bd.d_delays;
+  p.out = d_out;
+  p.ndm = (int)ndm;
+  p.band_ab = bd.d_ab;
+  p.nband = (int)plan.nband();
+  p.bsub = (int)plan.nsub;
+  p.cps = (int)plan.cps;
+  p.bw_min = (int)plan.wmin;
+  p.bw_max = (int)plan.wmax;
+  std::vector<int32_t> range;
+  const bool tiled = bands_tiled(fil, d_rows, delays, ndm, plan, &range);
+#ifndef FRBCH_NO_FAST
+  if (tiled) {
+    const int bpv = fil->nbits / 8, ngrp = (int)((ndm + fast::kDedND - 1) / fast::kDedND);
+    const size_t ngrp_cap = (bd.ndm_cap + fast::kDedND - 1) / fast::kDedND, nct = fil->nchan / (64 / bpv);
+    const size_t npre = (size_t)bd.ndm_cap * plan.nsub * p.nout;
+    if (!bd.d_range) POST_DEV(ps.alloc(&bd.d_range, ngrp_cap * nct * 2 * sizeof(int32_t)), "hipMalloc");
+    if (!bd.d_pre) POST_DEV(ps.alloc(&bd.d_pre, npre * sizeof(uint32_t)), "hipMalloc");
+    if (p.zerodm && !bd.d_prez) POST_DEV(ps.alloc(&bd.d_prez, npre * sizeof(double)), "hipMalloc");
+    POST_DEV(dev_h2d(bd.d_range, range.data(), range.size() * sizeof(int32_t), s), "upload tile ranges");
+    POST_DEV(dev_sync(s), "sync");
+    p.tile_range = bd.d_range;
+    p.pre = bd.d_pre;
+    p.prez = bd.d_prez;
+    const size_t lds = (size_t)fast::kDedRowsCap * fast::kDedRowB + 16 + (size_t)fast::kDedRowsCap * 9;
+    const unsigned gx = (unsigned)((p.nout + fast::kDedTT - 1) / fast::kDedTT);
+    const bool fl = p.flagged != nullptr, zd = p.zerodm != 0;
+    const int refused = bpv == 1 ? launch_bands_tiled<1>(fl, zd, dim3(gx, (unsigned)ngrp), lds, s, p)
+                                 : launch_bands_tiled<2>(fl, zd, dim3(gx, (unsigned)ngrp), lds, s, p);
+    POST_DEV(refused, "LDS size");
+    POST_DEV(dev_check_launch(), "launch band prefixes");
+    const dim3 grid(gx, (unsigned)plan.nband(), ndm);
+    if (zd) hipLaunchKernelGGL(fast::frbch_post_bands_ranges<true>, grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(fast::frbch_post_bands_ranges<false>, grid, dim3(256), 0, s, p);
+  }
+#endif
+  if (!tiled) DEV_LAUNCH(frbch_post_dedisp_bands, (p.nout + 255) / 256, ndm, 256, 0, s, p);
+  POST_DEV(dev_check_launch(), "launch band series");
+  POST_DEV(dev_sync(s), "sync");                                   // (the host's delays and tile table were read)
+  *tiled_out = tiled;
+  return FRBCH_OK;
+}
+
+// the parameters of the pre-pass and of every run behind it
+PostParams bands_params(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, double* d_rowsum, uint64_t nout, uint32_t zerodm) {
+  PostParams p = post_params<PostParams>(fil, d_rows, nrows);
+  p.prod = (int)fil->product;
+  p.rowsum = d_rowsum;
+  p.nout = nout;
+  p.zerodm = zerodm ? 1 : 0;
+  p.rows_per_chunk = kPostChunkRows;
+  return p;
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+}  // namespace
+
+extern "C" int frbch_band_list(uint32_t nchan, const frbch_band_params* bands, uint16_t* sub_lo, uint16_t* sub_hi, uint32_t cap,
+                               uint32_t* nband, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  BandPlan plan;
+  const int rc = band_check(nchan, bands, &plan, e);
+  if (rc) return rc;
+  if (!nband || (cap && (!sub_lo || !sub_hi))) return e.fail(FRBCH_E_ARG, "null argument");
+  *nband = plan.nband();
+  for (uint32_t j = 0; j < std::min(cap, plan.nband()); ++j) {
+    sub_lo[j] = plan.ab[2 * j];
+    sub_hi[j] = plan.ab[2 * j + 1];
+  }
+  if (plan.nband() > cap) return e.fail(FRBCH_E_CAPACITY, std::to_string(plan.nband()) + " bands, room for " + std::to_string(cap));
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_dedisperse_bands_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const double* dms,
+                                             uint32_t ndm, const frbch_band_params* bands) try {
+  PostErr e{nullptr, 0};
+  BandPlan plan;
+  const long nout = frbch_dedisperse_nout(fil, nrows, dms, ndm);
+  if (!d_rows || nout <= 0 || bands_check(fil, nrows, dms, ndm, bands, &plan, (uint64_t)nout, e)) return FRBCH_E_ARG;
+  int64_t maxd = 0;
+  const std::vector<int32_t> delays = post_delays(fil, dms, ndm, &maxd);
+  std::vector<int32_t> range;
+  return bands_tiled(fil, d_rows, delays, ndm, plan, &range) ? 1 : 0;
+} catch (const std::bad_alloc&) { return FRBCH_E_NOMEM; }
+
+extern "C" int frbch_dedisperse_bands_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const double* dms,
+                                             uint32_t ndm, uint32_t zerodm, double clip_sigma, const frbch_band_params* bands,
+                                             int device, float* d_out, uint64_t nout, uint64_t* nclipped, uint32_t* kernel_used,
+                                             char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  BandPlan plan;
+  int rc = bands_check(fil, nrows, dms, ndm, bands, &plan, nout, e);
+  if (rc) return rc;
+  if (!d_rows || !d_out) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  PostScope ps;
+  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  double* d_rowsum = nullptr;
+  POST_DEV(ps.alloc(&d_rowsum, nrows * sizeof(double)), "hipMalloc");
+  PostParams p = bands_params(fil, d_rows, nrows, d_rowsum, nout, zerodm);
+  uint64_t nflag = 0;
+  if ((rc = post_dedisp_prepass(ps, e, fil, nrows, zerodm, clip_sigma, p, &nflag)) != 0) return rc;
+  BandsDev bd;
+  if ((rc = bands_dev_init(ps, e, fil, plan, ndm, &bd)) != 0) return rc;
+  bool tiled = false;
+  if ((rc = bands_run(ps, e, fil, d_rows, p, plan, bd, dms, ndm, d_out, &tiled)) != 0) return rc;
+  if (nclipped) *nclipped = nflag;
+  if (kernel_used) *kernel_used = tiled ? 1 : 0;
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_dedisperse_bands_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const double* dms,
+                                           uint32_t ndm, uint32_t zerodm, double clip_sigma, const frbch_band_params* bands,
+                                           int device, float* out, uint64_t nout, uint64_t* nclipped, uint32_t* kernel_used,
+                                           char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  BandPlan plan;
+  int rc = bands_check(fil, nrows, dms, ndm, bands, &plan, nout, e);
+  if (rc) return rc;
+  if (!rows || !out) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
+  float* d_out = hs.out(out, (size_t)ndm * plan.nband() * nout * sizeof(float));
+  return hs.run(e, "device memory for the rows", "upload rows", "download series", [&]() {
+    return frbch_dedisperse_bands_device(fil, d_rows, nrows, dms, ndm, zerodm, clip_sigma, bands, device, d_out, nout, nclipped,
+                                         kernel_used, err, err_cap);
+  });
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_bandsearch_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const double* dms, uint32_t ndm,
+                                       uint32_t zerodm, double clip_sigma, const frbch_band_params* bands, const frbch_sp_params* sp,
+                                       uint64_t plane_bytes, int device, uint64_t nout, uint64_t* nclipped, frbch_spb_cand* cands,
+                                       uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, uint32_t* nbatch, double* stage_ms,
+                                       char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  BandPlan plan;
+  int rc = bands_check(fil, nrows, dms, ndm, bands, &plan, nout, e);
+  if (rc) return rc;
+  uint64_t blk_len = 0;
+  if ((rc = sp_check(sp, &blk_len, e)) != 0) return rc;
+  if (!d_rows || !ncand || (cap && !cands)) return e.fail(FRBCH_E_ARG, "null argument");
+  const uint64_t one = (uint64_t)plan.nband() * nout * sizeof(float), budget = plane_bytes ? plane_bytes : 1ull << 30;
+  if (budget < one)
+    return e.fail(FRBCH_E_ARG, "plane_bytes = " + std::to_string(budget) + " holds no DM: one DM's plane takes " + std::to_string(one));
+  const uint32_t per = (uint32_t)std::min<uint64_t>(ndm, budget / one);
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  PostScope ps(false);
+  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  auto t0 = std::chrono::steady_clock::now();
+  double ms[3] = {0.0, 0.0, 0.0};
+  double* d_rowsum = nullptr;
+  float* d_plane = nullptr;
+  POST_DEV(ps.alloc(&d_rowsum, nrows * sizeof(double)), "hipMalloc");
+  PostParams p = bands_params(fil, d_rows, nrows, d_rowsum, nout, zerodm);
+  uint64_t nflag = 0;
+  if ((rc = post_dedisp_prepass(ps, e, fil, nrows, zerodm, clip_sigma, p, &nflag)) != 0) return rc;
+  BandsDev bd;
+  if ((rc = bands_dev_init(ps, e, fil, plan, per, &bd)) != 0) return rc;
+  POST_DEV(ps.alloc(&d_plane, (size_t)per * one), "hipMalloc");
+  POST_DEV(dev_sync(ps.s), "sync");
+  ms[0] = ms_since(t0);
+  std::vector<frbch_sp_cand> part;
+  uint64_t total = 0;
+  uint32_t nb = 0, search_kernel = 0;
+  bool all_tiled = true;
+  for (uint32_t d0 = 0; d0 < ndm; d0 += per, ++nb) {
+    const uint32_t n = std::min(per, ndm - d0);
+    bool tiled = false;
+    t0 = std::chrono::steady_clock::now();
+    if ((rc = bands_run(ps, e, fil, d_rows, p, plan, bd, dms + d0, n, d_plane, &tiled)) != 0) return rc;
+    ms[1] += ms_since(t0);
+    all_tiled = all_tiled && tiled;
+    t0 = std::chrono::steady_clock::now();
+    part.clear();
+    uint64_t npart = 0;
+    if ((rc = sp_search_run(d_plane, n * plan.nband(), nout, sp, device, nullptr, 0, &npart, &search_kernel, &part, err, err_cap)) != 0)
+      return rc;
+    ms[2] += ms_since(t0);
+    for (const frbch_sp_cand& c : part) {               // series = dm * nband + j, sorted by (series, sample, width) already
+      if (total < cap) {
+        const uint32_t j = c.dm_index % plan.nband();
+        frbch_spb_cand r;
+        r.dm_index = d0 + c.dm_index / plan.nband();
+        r.width = c.width;
+        r.sample = c.sample;
+        r.sigma = c.sigma;
+        r.sub_lo = plan.ab[2 * j];
+        r.sub_hi = plan.ab[2 * j + 1];
+        cands[total] = r;
+      }
+      ++total;
+    }
+  }
+  *ncand = total;
+  if (nclipped) *nclipped = nflag;
+  if (kernel_used) { kernel_used[0] = all_tiled ? 1 : 0; kernel_used[1] = search_kernel; }
+  if (nbatch) *nbatch = nb;
+  if (stage_ms) for (int i = 0; i < 3; ++i) stage_ms[i] = ms[i];
+  if (total > cap) return e.fail(FRBCH_E_CAPACITY, std::to_string(total) + " candidates, room for " + std::to_string(cap));
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_bandsearch_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const double* dms, uint32_t ndm,
+                                     uint32_t zerodm, double clip_sigma, const frbch_band_params* bands, const frbch_sp_params* sp,
+                                     uint64_t plane_bytes, int device, uint64_t nout, uint64_t* nclipped, frbch_spb_cand* cands,
+                                     uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, uint32_t* nbatch, double* stage_ms,
+                                     char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  BandPlan plan;
+  int rc = bands_check(fil, nrows, dms, ndm, bands, &plan, nout, e);
+  if (rc) return rc;
+  if (!rows) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  HostStage hs;
+  void* d_rows = hs.in(rows, post_rows_bytes(fil, nrows));
+  return hs.run(e, "device memory for the rows", "upload rows", "download", [&]() {
+    return frbch_bandsearch_device(fil, d_rows, nrows, dms, ndm, zerodm, clip_sigma, bands, sp, plane_bytes, device, nout, nclipped,
+                                   cands, cap, ncand, kernel_used, nbatch, stage_ms, err, err_cap);
+  });
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+namespace {
+bool spb_better(const frbch_spb_cand& a, const frbch_spb_cand& b) {     // a represents a group rather than b
+  if (a.sigma != b.sigma) return a.sigma > b.sigma;
+  const int wa = a.sub_hi - a.sub_lo, wb = b.sub_hi - b.sub_lo;
+  if (wa != wb) return wa < wb;
+  if (a.width != b.width) return a.width < b.width;
+  if (a.dm_index != b.dm_index) return a.dm_index < b.dm_index;
+  if (a.sample != b.sample) return a.sample < b.sample;
+  return a.sub_lo < b.sub_lo;
+}
+}  // namespace
+
+extern "C" int frbch_spb_group_cands(const frbch_fil_desc* fil, const double* dms, uint32_t ndm, uint32_t nsub,
+                                     const frbch_spb_cand* cands, uint64_t ncand, uint32_t dm_gap, frbch_spb_group* groups,
+                                     uint64_t cap, uint64_t* ngroup, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  int rc = post_check_fil(fil, 1, e);
+  if (rc) return rc;
+  if (!dms || !ndm || !ngroup || (ncand && !cands) || (cap && !groups)) return e.fail(FRBCH_E_ARG, "null argument");
+  if (dm_gap < 1 || dm_gap > 16) return e.fail(FRBCH_E_ARG, "dm_gap must be 1..16");
+  if (nsub < 1 || nsub > 16) return e.fail(FRBCH_E_ARG, "nsub must be 1..16");
+  for (uint32_t i = 0; i < ndm; ++i)
+    if (!(dms[i] >= 0.0) || !(dms[i] < 1.0e5)) return e.fail(FRBCH_E_ARG, "a DM outside [0, 1e5)");
+  for (uint64_t i = 0; i < ncand; ++i) {
+    if (cands[i].dm_index >= ndm) return e.fail(FRBCH_E_ARG, "record " + std::to_string(i) + ": dm_index >= ndm");
+    if (cands[i].sub_lo >= cands[i].sub_hi || cands[i].sub_hi > nsub)
+      return e.fail(FRBCH_E_ARG, "record " + std::to_string(i) + ": not a band of " + std::to_string(nsub) + " sub-bands");
+  }
+  *ngroup = 0;
+  if (!ncand) return FRBCH_OK;
+  const std::vector<uint64_t> root = sp_link(fil, dms, ndm, cands, ncand, dm_gap);
+  std::vector<int64_t> slot(ncand, -1);                                  // root -> index in `out`
+  std::vector<frbch_spb_group> out;
+  for (uint64_t i = 0; i < ncand; ++i) {
+    const frbch_spb_cand& c = cands[i];
+    const bool full = c.sub_lo == 0 && c.sub_hi == nsub;
+    if (slot[root[i]] < 0) {
+      slot[root[i]] = (int64_t)out.size();
+      frbch_spb_group g;
+      memset(&g, 0, sizeof g);
+      g.best = c;
+      g.nmember = 1;
+      g.dm_index_lo = g.dm_index_hi = c.dm_index;
+      g.sub_lo_min = c.sub_lo;
+      g.sub_hi_max = c.sub_hi;
+      g.sample_lo = g.sample_hi = c.sample;
+      g.full_sigma = full ? c.sigma : 0.0f;
+      out.push_back(g);
+      continue;
+    }
+    frbch_spb_group& g = out[(size_t)slot[root[i]]];
+    if (spb_better(c, g.best)) g.best = c;
+    ++g.nmember;
+    g.dm_index_lo = std::min(g.dm_index_lo, c.dm_index);
+    g.dm_index_hi = std::max(g.dm_index_hi, c.dm_index);
+    g.sub_lo_min = std::min(g.sub_lo_min, c.sub_lo);
+    g.sub_hi_max = std::max(g.sub_hi_max, c.sub_hi);
+    g.sample_lo = std::min(g.sample_lo, c.sample);
+    g.sample_hi = std::max(g.sample_hi, c.sample);
+    if (full) g.full_sigma = std::max(g.full_sigma, c.sigma);
+  }
+  std::sort(out.begin(), out.end(), [](const frbch_spb_group& a, const frbch_spb_group& b) {
+    if (a.best.dm_index != b.best.dm_index) return a.best.dm_index < b.best.dm_index;
+    if (a.best.sample != b.best.sample) return a.best.sample < b.best.sample;
+    if (a.best.width != b.best.width) return a.best.width < b.best.width;
+    if (a.best.sub_lo != b.best.sub_lo) return a.best.sub_lo < b.best.sub_lo;
+    if (a.best.sub_hi != b.best.sub_hi) return a.best.sub_hi < b.best.sub_hi;
+    return a.sample_lo < b.sample_lo;
+  });
+  *ngroup = out.size();
+  for (uint64_t i = 0; i < std::min<uint64_t>(cap, out.size()); ++i) groups[i] = out[i];
+  if (out.size() > cap) return e.fail(FRBCH_E_CAPACITY, std::to_string(out.size()) + " groups, room for " + std::to_string(cap));
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+namespace {
+constexpr uint64_t kCutTableCap = 1ull << 26;   // delay-table entries of one call (256 MiB); a longer batch is refused
 
 // the part of cut_check that needs no candidate (frbch_candidates_* refuse a bad `cut` before they have any)
 int cut_check_par(const frbch_fil_desc* fil, const frbch_cutout_params* par, const PostErr& e) {

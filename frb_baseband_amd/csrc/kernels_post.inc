@@ -30,6 +30,12 @@ struct PostParams {
   int nbin;
   uint64_t rows_per_sub;
   uint32_t nsub;
+  // ---- band-limited dedispersion (frbch_dedisperse_bands_*): out is [ndm * nband][nout] ----
+  const uint16_t* band_ab;     // [nband][2] (a, b) of band j (the range kernel of the tiled form reads it)
+  int nband, bsub, cps;        // bands, sub-bands, channels per sub-band
+  int bw_min, bw_max;          // widths b - a that are listed
+  uint32_t* pre;               // tiled form: [ndm][bsub][nout] sum over the channels below sub-band edge k + 1
+  double* prez;                // ... the same sum of the zero-DM row sums S (zerodm only)
 };
 
 DEVFN inline double post_sample(const PostParams& p, uint64_t t, int c) {
@@ -94,6 +100,38 @@ KERNEL(frbch_post_dedisp, PostParams) {
       }
       const double y = p.zerodm ? a - b / (double)p.nchan : a;
       p.out[(size_t)by * p.nout + t] = (float)y;
+    }
+  }
+}
+
+// Band-limited dedispersion (include/frbch.h, "band-limited single-pulse search"): for band j = [a, b) of sub-bands
+// y[dm][j][t] = sum_{c in [a cps, b cps)} value(t + delay[dm][c], c)  -  (zerodm ? the same sum of S / nchan : 0), as float32.
+// grid (ceil(nout / 256), ndm), one thread per (dm, t).  For every first sub-band a the thread walks the channels upwards
+// once and stores the running sums at the sub-band edges b whose width is listed: every band is summed from its own first
+// channel in ascending order (float rows come out to the bit; band [0, bsub) is frbch_post_dedisp's series), and the rows
+// are read once per first sub-band, not once per band.  Bands are numbered by ascending a, then b: the order of the walk.
+KERNEL(frbch_post_dedisp_bands, PostParams) {
+  K_PROLOGUE;
+  (void)smem;
+  PHASE {
+    const uint64_t t = (uint64_t)bx * nthr + tid;
+    if (t < p.nout) {
+      const int32_t* dly = p.delays + (size_t)by * p.nchan;
+      int j = 0;
+      for (int a = 0; a < p.bsub; ++a) {
+        double s = 0.0, z = 0.0;
+        for (int b = a + 1; b <= p.bsub && b - a <= p.bw_max; ++b) {
+          for (int c = (b - 1) * p.cps; c < b * p.cps; ++c) {
+            const uint64_t ti = t + (uint64_t)dly[c];
+            s += post_value(p, ti, c);
+            if (p.zerodm) z += p.rowsum[ti];
+          }
+          if (b - a < p.bw_min) continue;
+          const double y = p.zerodm ? s - z / (double)p.nchan : s;
+          p.out[((size_t)by * p.nband + j) * p.nout + t] = (float)y;
+          ++j;
+        }
+      }
     }
   }
 }

@@ -81,6 +81,107 @@ __global__ void __launch_bounds__(256) frbch_post_dedisp_tiled(PostParams p) {
   }
 }
 
+// Band-limited dedispersion, tiled form (frbch_dedisperse_bands_*; the generic frbch_post_dedisp_bands stays the emulable
+// form and the fallback).  The schedule is frbch_post_dedisp_tiled's -- 256 output samples x kDedND DMs per workgroup, the
+// rows of a channel tile staged through the LDS with their clip flags and row sums, channels ascending -- so the rows are
+// read once per DM group whatever the number of bands.  8- / 16-bit rows only: the running sum over the channels is an
+// exact integer (nchan <= 65536 samples of 16 bit fit uint32), and so is the running sum of the zero-DM row sums (below 2^48:
+// exact in a double, its 64 bits).  A sub-band is a whole number of tiles (the host checked): behind the last tile of sub-band
+// k the running sums are stored as the prefix at edge k + 1, pre[dm][k][t] (the prefix at edge 0 is 0 and is not stored).
+// frbch_post_bands_ranges then forms band [a, b) as the difference of two prefixes: exact, whatever cancels.
+template <int BPV, bool FLAGS, bool ZERODM>
+__global__ void __launch_bounds__(256) frbch_post_dedisp_bands_tiled(PostParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  unsigned char* tile = smem;                                              // [rows][68]
+  double* rs = reinterpret_cast<double*>(smem + (size_t)kDedRowsCap * kDedRowB + 16);   // [rows] zero-DM row sums
+  unsigned char* fl = reinterpret_cast<unsigned char*>(rs + kDedRowsCap);  // [rows] clip flags
+  constexpr int CT = 64 / BPV;
+  const int tid = threadIdx.x;
+  const uint64_t t0 = (uint64_t)blockIdx.x * kDedTT;
+  const uint64_t t = t0 + tid;
+  const int dm0 = blockIdx.y * kDedND;
+  const int nd = min(kDedND, p.ndm - dm0);
+  const int nct = p.nchan / CT, tps = p.cps / CT;                          // channel tiles, tiles per sub-band
+  const size_t row_stride = (size_t)p.nifs * p.nchan * BPV;
+  const unsigned char* src0 = p.rows + (size_t)p.prod * p.nchan * BPV;
+  uint32_t a[kDedND];
+  double b[kDedND];
+#pragma unroll
+  for (int d = 0; d < kDedND; ++d) { a[d] = 0u; b[d] = 0.0; }
+  for (int ctile = 0, left = tps, k = 0; ctile < nct; ++ctile) {
+    const int32_t dmin = p.tile_range[((size_t)blockIdx.y * nct + ctile) * 2];
+    const int32_t span = p.tile_range[((size_t)blockIdx.y * nct + ctile) * 2 + 1];
+    const int rows = kDedTT + span;                                        // <= kDedRowsCap (the host checked)
+    const uint64_t r0 = t0 + (uint64_t)dmin;
+    __syncthreads();                                                       // the previous tile is consumed
+    for (int i = tid; i < rows * 4; i += 256) {                            // 16-byte pieces: 4 per row
+      const int r = i >> 2, part = i & 3;
+      uint4 v = make_uint4(0u, 0u, 0u, 0u);
+      if (r0 + r < p.nrows) v = *reinterpret_cast<const uint4*>(src0 + (r0 + r) * row_stride + (size_t)ctile * 64 + part * 16);
+      *reinterpret_cast<uint32_t*>(tile + r * kDedRowB + part * 16) = v.x;
+      *reinterpret_cast<uint32_t*>(tile + r * kDedRowB + part * 16 + 4) = v.y;
+      *reinterpret_cast<uint32_t*>(tile + r * kDedRowB + part * 16 + 8) = v.z;
+      *reinterpret_cast<uint32_t*>(tile + r * kDedRowB + part * 16 + 12) = v.w;
+    }
+    if (ZERODM || FLAGS)
+      for (int r = tid; r < rows; r += 256) {
+        const bool in = r0 + r < p.nrows;
+        if (ZERODM) rs[r] = in ? p.rowsum[r0 + r] : 0.0;
+        if (FLAGS) fl[r] = in ? p.flagged[r0 + r] : 0;
+      }
+    __syncthreads();
+    if (t < p.nout) {
+      for (int cl = 0; cl < CT; ++cl) {
+        const int c = ctile * CT + cl;
+        const uint32_t rep = FLAGS ? (uint32_t)p.repl[c] : 0u;             // (an integer on integer rows)
+#pragma unroll
+        for (int d = 0; d < kDedND; ++d) {
+          if (d < nd) {
+            const int r = tid + p.delays[(size_t)(dm0 + d) * p.nchan + c] - dmin;
+            uint32_t v;
+            if (BPV == 1) v = tile[r * kDedRowB + cl];
+            else v = *reinterpret_cast<const uint16_t*>(tile + r * kDedRowB + cl * 2);
+            if (FLAGS && fl[r]) v = rep;
+            a[d] += v;
+            if (ZERODM) b[d] += rs[r];
+          }
+        }
+      }
+      if (--left == 0) {                                                   // sub-band k ends with this tile
+#pragma unroll
+        for (int d = 0; d < kDedND; ++d)
+          if (d < nd) {
+            const size_t at = ((size_t)(dm0 + d) * p.bsub + k) * p.nout + t;
+            p.pre[at] = a[d];
+            if (ZERODM) p.prez[at] = b[d];
+          }
+        left = tps;
+        ++k;
+      }
+    }
+  }
+}
+
+// out[dm * nband + j][t] = (float)( (double)(pre_b - pre_a) - (zerodm ? (prez_b - prez_a) / nchan : 0) ) for band j = [a, b).
+// grid (ceil(nout / 256), nband, ndm), one thread per output sample: two (four) coalesced loads, one coalesced store.
+template <bool ZERODM>
+__global__ void __launch_bounds__(256) frbch_post_bands_ranges(PostParams p) {
+  const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= p.nout) return;
+  const int j = blockIdx.y, dm = blockIdx.z;
+  const int a = p.band_ab[2 * j], b = p.band_ab[2 * j + 1];
+  const size_t base = (size_t)dm * p.bsub * p.nout + t;
+  const uint32_t hi = p.pre[base + (size_t)(b - 1) * p.nout];
+  const uint32_t lo = a ? p.pre[base + (size_t)(a - 1) * p.nout] : 0u;
+  double y = (double)(hi - lo);
+  if (ZERODM) {
+    const double zh = p.prez[base + (size_t)(b - 1) * p.nout];
+    const double zl = a ? p.prez[base + (size_t)(a - 1) * p.nout] : 0.0;
+    y = y - (zh - zl) / (double)p.nchan;
+  }
+  p.out[((size_t)dm * p.nband + j) * p.nout + t] = (float)y;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // All-product fold in the LDS (HIP only; frbch_post_foldp of kernels_post.inc stays the emulable form and the fallback).
 // The production form: integer rows, no per-channel delays (what dspsr does with a filterbank), so the bin depends on the

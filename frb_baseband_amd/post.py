@@ -733,6 +733,153 @@ def _search(fil, filterbankfile, dm1, dm2, dmstep, zerodm, clip, threshold, max_
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# band-limited single-pulse search
+# ------------------------------------------------------------------------------------------------------------------
+SPB_CAND = np.dtype([("dm_index", "<u4"), ("width", "<u4"), ("sample", "<u8"), ("sigma", "<f4"), ("sub_lo", "<u2"), ("sub_hi", "<u2")])
+SPB_GROUP = np.dtype([("best", SPB_CAND), ("nmember", "<u4"), ("dm_index_lo", "<u4"), ("dm_index_hi", "<u4"), ("sub_lo_min", "<u2"),
+                      ("sub_hi_max", "<u2"), ("sample_lo", "<u8"), ("sample_hi", "<u8"), ("full_sigma", "<f4"), ("reserved", "<u4")])
+BANDS_HEADER = "# DM      Sigma      Time (s)     Sample    Downfact  Members   Flo (MHz)   Fhi (MHz)  Sub  FullSigma"
+BANDS_ROW = "%7.2f %7.2f %13.6f %10d   %3d %8d %11.4f %11.4f  %d-%d %9.2f"
+
+
+def band_params(nsub: int = 8, min_sub: int = 1, max_sub: int = 0) -> _lib.FrbchBandParams:
+    if not all(0 <= int(v) < 1 << 32 for v in (nsub, min_sub, max_sub)):
+        raise InputError("nsub, min_sub and max_sub must be non-negative 32-bit integers")
+    p = _lib.FrbchBandParams()
+    p.size = C.sizeof(_lib.FrbchBandParams)
+    p.nsub, p.min_sub, p.max_sub = int(nsub), int(min_sub), int(max_sub)
+    return p
+
+
+def band_list(nchan: int, nsub: int = 8, min_sub: int = 1, max_sub: int = 0, lib=None) -> np.ndarray:
+    """The bands of frbch_band_list: every range [a, b) of the ``nsub`` equal sub-bands of ``nchan`` channels with
+    ``min_sub <= b - a <= max_sub`` (0 = ``nsub``), by ascending a, then b -> uint16 [nband][2]."""
+    lib = lib or _lib.load()
+    bp = band_params(nsub, min_sub, max_sub)
+    lo, hi = np.zeros(136, dtype=np.uint16), np.zeros(136, dtype=np.uint16)
+    n = C.c_uint32(0)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_band_list(int(nchan), C.byref(bp), lo.ctypes.data, hi.ctypes.data, lo.size, C.byref(n), err, len(err)), err)
+    return np.stack([lo[: n.value], hi[: n.value]], axis=1)
+
+
+def band_edges_mhz(hdr: dict, nsub: int, sub_lo: int, sub_hi: int):
+    """(lowest, highest) frequency in MHz of the channels of band [sub_lo, sub_hi), channel edges included"""
+    cps = hdr["nchans"] // nsub
+    f = [hdr["fch1"] + (c - 0.5) * hdr["foff"] for c in (sub_lo * cps, sub_hi * cps)]
+    return min(f), max(f)
+
+
+def _bands_nout(lib, desc, rows, dm_arr):
+    nout = lib.frbch_dedisperse_nout(C.byref(desc), rows.shape[0], dm_arr.ctypes.data, dm_arr.size)
+    if nout <= 0:
+        raise InputError("the dispersion delay across the band exceeds the length of the filterbank" if nout == 0 else
+                         "bad header, or a DM outside [0, 1e5)")
+    return nout
+
+
+def dedisperse_bands(rows, hdr: dict, dms, nsub: int = 8, min_sub: int = 1, max_sub: int = 0, zerodm: bool = True, clip: float = 5.0,
+                     product: int = 0, device: int = 0, lib=None, info: dict | None = None):
+    """The series of every band of ``band_list`` on the GPU (frbch_dedisperse_bands_host; include/frbch.h states the
+    arithmetic) -> (float32 [ndm][nband][nout], number of clipped time samples).  Band [0, nsub) is ``dedisperse``'s series
+    to the bit.  ``info['kernel_used']``: 1 = the tiled prefix kernel, 0 = the generic one."""
+    lib = lib or _lib.load()
+    x = _rows3(rows, hdr)
+    desc = fil_desc(dict(hdr, nifs=x.shape[1], nbits=x.dtype.itemsize * 8), product)
+    dm_arr = np.ascontiguousarray(dms, dtype=np.float64)
+    bp = band_params(nsub, min_sub, max_sub)
+    nband = band_list(desc.nchan, nsub, min_sub, max_sub, lib).shape[0]
+    nout = _bands_nout(lib, desc, x, dm_arr)
+    out = np.empty((dm_arr.size, nband, nout), dtype=np.float32)
+    nclip, used = C.c_uint64(0), C.c_uint32(0)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_dedisperse_bands_host(C.byref(desc), x.ctypes.data, x.shape[0], dm_arr.ctypes.data, dm_arr.size, 1 if zerodm else 0,
+                                           float(clip), C.byref(bp), device, out.ctypes.data, nout, C.byref(nclip), C.byref(used), err,
+                                           len(err)), err)
+    if info is not None:
+        info.update(kernel_used=used.value, nout=nout, nband=nband)
+    return out, nclip.value
+
+
+def band_search(rows, hdr: dict, dms, nsub: int = 8, min_sub: int = 1, max_sub: int = 0, zerodm: bool = True, clip: float = 5.0,
+                widths=None, threshold: float = 5.0, detrend_len: int = 1000, max_width_s: float = 0.0, plane_bytes: int = 0,
+                product: int = 0, device: int = 0, lib=None, info: dict | None = None, cap: int = 4096) -> np.ndarray:
+    """Single-pulse search of every band's series over the DMs (frbch_bandsearch_host: one upload of the rows, one clip /
+    zero-DM pre-pass, batches of DMs whose plane fits ``plane_bytes`` -- 0 = 1 GiB -- searched where they lie in HBM) ->
+    SPB_CAND records sorted by (dm_index, sub_lo, sub_hi, sample, width); the list does not depend on ``plane_bytes``.
+    ``info`` receives kernel_used (dedispersion, search), nbatch, nclipped, nout and the stage times in ms."""
+    lib = lib or _lib.load()
+    x = _rows3(rows, hdr)
+    desc = fil_desc(dict(hdr, nifs=x.shape[1], nbits=x.dtype.itemsize * 8), product)
+    dm_arr = np.ascontiguousarray(dms, dtype=np.float64)
+    bp = band_params(nsub, min_sub, max_sub)
+    params = sp_params(widths if widths is not None else default_widths(hdr["tsamp"], max_width_s), threshold, detrend_len)
+    nout = _bands_nout(lib, desc, x, dm_arr)
+    while True:
+        cands = np.zeros(cap, dtype=SPB_CAND)
+        ncand, nclip, nbatch = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        used, ms = (C.c_uint32 * 2)(), (C.c_double * 3)()
+        err = C.create_string_buffer(512)
+        rc = lib.frbch_bandsearch_host(C.byref(desc), x.ctypes.data, x.shape[0], dm_arr.ctypes.data, dm_arr.size, 1 if zerodm else 0,
+                                       float(clip), C.byref(bp), C.byref(params), int(plane_bytes), device, nout, C.byref(nclip),
+                                       cands.ctypes.data, cap, C.byref(ncand), used, C.byref(nbatch), ms, err, len(err))
+        if rc == _lib.E_CAPACITY and ncand.value > cap:
+            cap = ncand.value
+            continue
+        _check(rc, err)
+        break
+    if info is not None:
+        info.update(kernel_used=(used[0], used[1]), nbatch=nbatch.value, nclipped=nclip.value, nout=nout,
+                    stage_ms=dict(prepass=ms[0], dedisperse=ms[1], search=ms[2]))
+    return cands[: ncand.value].copy()
+
+
+def group_band_candidates(cands, hdr: dict, dms, nsub: int = 8, dm_gap: int = 2, lib=None) -> np.ndarray:
+    """Join the records of one pulse across trial DMs AND bands (frbch_spb_group_cands, host only: the link rule of
+    ``group_candidates`` on (dm_index, sample, width); the band plays no part in it) -> SPB_GROUP sorted by the best member's
+    (dm_index, sample, width, sub_lo, sub_hi); ``full_sigma`` is the strongest full-band member's sigma, 0 without one."""
+    lib = lib or _lib.load()
+    recs = np.ascontiguousarray(cands, dtype=SPB_CAND)
+    dm_arr = np.ascontiguousarray(dms, dtype=np.float64)
+    desc = fil_desc(hdr)
+    out = np.zeros(max(1, recs.size), dtype=SPB_GROUP)
+    n = C.c_uint64(0)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_spb_group_cands(C.byref(desc), dm_arr.ctypes.data, dm_arr.size, int(nsub), recs.ctypes.data, recs.size,
+                                     int(dm_gap), out.ctypes.data, out.size, C.byref(n), err, len(err)), err)
+    return out[: n.value].copy()
+
+
+def bandsearch_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, nsub=8, min_sub=1, max_sub=0, zerodm=True, clip=5, threshold=5.0,
+                   max_width_s=0.0, detrend_len=1000, widths=None, dm_gap=2, plane_bytes=0, device=0, lib=None,
+                   info: dict | None = None, flag_file=None, rfi=None, periodic=None):
+    """Band-limited search of a filterbank over the DMs of ``prepdata_gpu``: ``band_search`` on the rows -- cleaned first where
+    ``flag_file`` / ``rfi`` / ``periodic`` ask for it, exactly as ``search_fil`` does -- then ``group_band_candidates``.
+    Writes ``<base>_bands.npz`` (cands, groups, bands, dms, nsub) and ``<base>_bands.txt``: one line per group, strongest
+    first, with the band's frequency edges and the full-band sigma next to the band's; DM, sample and width are what
+    ``--dm --sample --width`` of the burst commands take.  Returns (npz, txt, records, groups)."""
+    lib = lib or _lib.load()
+    _periodic_args(periodic, rfi, False)
+    fil = _read_rows(filterbankfile, flag_file, rfi, device, lib, info, detrend_len, periodic)
+    hdr = fil.header
+    dms = dm_list(dm1, dm2, dmstep)
+    cands = band_search(_rows_of(fil), hdr, dms, nsub, min_sub, max_sub, zerodm, clip, widths, threshold, detrend_len, max_width_s,
+                        plane_bytes, 0, device, lib, info)
+    groups = group_band_candidates(cands, hdr, dms, nsub, dm_gap, lib)
+    bands = band_list(hdr["nchans"], nsub, min_sub, max_sub, lib)
+    base = filterbankfile.replace(".fil", "")
+    np.savez(base + "_bands.npz", cands=cands, groups=groups, bands=bands, dms=np.asarray(dms, dtype=np.float64), nsub=np.int64(nsub))
+    with open(base + "_bands.txt", "w") as f:
+        f.write(BANDS_HEADER + "\n")
+        for g in groups[np.argsort(-groups["best"]["sigma"], kind="stable")]:
+            b = g["best"]
+            flo, fhi = band_edges_mhz(hdr, nsub, int(b["sub_lo"]), int(b["sub_hi"]))
+            f.write(BANDS_ROW % (dms[b["dm_index"]], b["sigma"], int(b["sample"]) * hdr["tsamp"], int(b["sample"]), int(b["width"]),
+                                 int(g["nmember"]), flo, fhi, int(b["sub_lo"]), int(b["sub_hi"]), g["full_sigma"]) + "\n")
+    return base + "_bands.npz", base + "_bands.txt", cands, groups
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # periodicity search
 # ------------------------------------------------------------------------------------------------------------------
 PS_CAND = np.dtype([("dm_index", "<u4"), ("h", "<u4"), ("k", "<u4"), ("power", "<f4"), ("sigma", "<f8"), ("freq_hz", "<f8")])
@@ -2668,6 +2815,7 @@ def burstscat_fil(filterbankfile, bursts, nbin=256, tfactor=1, ffactor=1, bank=N
 def main(argv=None):
     """``python -m frb_baseband_amd.post fold <fil> <par> [--polyco FILE] [--doppler X] [--products coherency|stokes] [...]`` / ``... prepdata <fil> --dm <dm> [...]`` /
     ``... search <fil> --dm <dm> [--dm2 --dmstep --threshold --max-width --detrend ...]`` /
+    ``... bandsearch <fil> --dm <dm> [--dm2 --dmstep --nsub N --min-sub A --max-sub B --dm-gap G --plane-mib M, search options]`` /
     ``... candidates <fil> --dm <dm> [search options] [--dm-gap --min-members --max-cands --nt --nf --ndm]`` /
     ``... psearch <fil> --dm <dm> [--dm2 --dmstep --sigma --nharm --flo --nfft --wblock --dm-gap --max-cands --fold-best K --amax A --astep S --acc-gap G]`` /
     ``... rfifind <fil> [--block-rows --t-cell --t-chan --chan-frac --block-frac --flag FILE --write-clean]`` /
@@ -2719,6 +2867,26 @@ def main(argv=None):
     q.add_argument("--periodic", action="store_true", help="with --rfi: also flag cells whose power spectrum has a peak (periodic interference)")
     q.add_argument("--t-freq", type=float, default=4.0, help="threshold of --periodic, Gaussian sigma over the bins of a cell")
     q.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
+    b = sub.add_parser("bandsearch", help="search every contiguous range of sub-bands over a DM range for single pulses: bursts that fill only part of the band")
+    b.add_argument("fil")
+    b.add_argument("--dm", type=float, required=True)
+    b.add_argument("--dm2", type=float, default=0.0)
+    b.add_argument("--dmstep", type=float, default=1.0)
+    b.add_argument("--nsub", type=int, default=8, help="equal sub-bands the band is cut into (1..16, a divisor of nchans)")
+    b.add_argument("--min-sub", type=int, default=1, help="narrowest range searched, in sub-bands")
+    b.add_argument("--max-sub", type=int, default=0, help="widest range searched, in sub-bands (0: the full band)")
+    b.add_argument("--threshold", type=float, default=5.0, help="sigma a boxcar sum must reach")
+    b.add_argument("--max-width", type=float, default=0.0, help="widest boxcar, s (0: widths up to 30 samples)")
+    b.add_argument("--detrend", type=int, default=1000, help="samples per normalisation block")
+    b.add_argument("--nozerodm", action="store_false", help="do not subtract the zero-DM series")
+    b.add_argument("--clip", type=float, default=5.0)
+    b.add_argument("--dm-gap", type=int, default=2, help="records at most this many trial DMs apart can join")
+    b.add_argument("--plane-mib", type=int, default=0, help="device memory of the (DM, band) x time plane of one batch of DMs, MiB (0: 1024)")
+    b.add_argument("--flag", default=None, help="flag file (channels to flag): the rows are cleaned before the search")
+    b.add_argument("--rfi", action="store_true", help="flag interference from block statistics and clean the rows first")
+    b.add_argument("--periodic", action="store_true", help="with --rfi: also flag cells whose power spectrum has a peak (periodic interference)")
+    b.add_argument("--t-freq", type=float, default=4.0, help="threshold of --periodic, Gaussian sigma over the bins of a cell")
+    b.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     z = sub.add_parser("psearch", help="dedisperse over a DM range and search every series for periodic signals (what realfft + accelsearch -zmax 0 do with the .dat files)")
     z.add_argument("fil")
     z.add_argument("--dm", type=float, required=True)
@@ -3010,6 +3178,15 @@ def main(argv=None):
         ar, profile = fold_fil(a.fil, a.par, nbin=a.nbin, subint_s=a.subint, fscrunch_to=a.fscrunch, device=a.device,
                                polyco=a.polyco, doppler=a.doppler, products=a.products)
         print("wrote {0}, {1}.profile.txt, {1}.png; peak bin {2} of {3}".format(ar, a.fil, int(np.argmax(profile)), profile.size))
+    elif a.cmd == "bandsearch":
+        npz, txt, cands, groups = bandsearch_fil(a.fil, a.dm, dm2=a.dm2, dmstep=a.dmstep, nsub=a.nsub, min_sub=a.min_sub, max_sub=a.max_sub,
+                                                 zerodm=a.nozerodm, clip=a.clip, threshold=a.threshold, max_width_s=a.max_width,
+                                                 detrend_len=a.detrend, dm_gap=a.dm_gap, plane_bytes=a.plane_mib << 20, device=a.device,
+                                                 flag_file=a.flag, rfi=a.rfi or None,
+                                                 **(dict(periodic=dict(t_freq=a.t_freq)) if a.periodic else {}))
+        print("wrote", npz)
+        print("wrote", txt)
+        print("{0} records in {1} groups above {2} sigma".format(cands.size, groups.size, a.threshold))
     elif a.cmd == "search":
         files, cands = search_fil(a.fil, a.dm, dm2=a.dm2, dmstep=a.dmstep, zerodm=a.nozerodm, clip=a.clip, threshold=a.threshold,
                                   max_width_s=a.max_width, detrend_len=a.detrend, write_dat=a.write_dat, device=a.device,

@@ -1463,6 +1463,98 @@ void frbch_cand_result_free(frbch_cand_result* res);
 int frbch_cand_select(const frbch_sp_group* groups, uint64_t ngroup, uint32_t min_members, uint32_t max_cands,
                       uint64_t* keep, uint64_t cap, uint64_t* nkeep);
 
+/* ---- band-limited single-pulse search ---------------------------------------------------------------
+ * Every search above sums the whole band first; a burst that fills 1/k of the band loses sqrt(k) of its S/N there.  Bursts
+ * of repeaters are often band-limited, so frbch_dedisperse_bands_* make, next to the full-band series, the series of every
+ * contiguous RANGE of sub-bands, and frbch_bandsearch_* search them all with frbch_spsearch_device (every series is
+ * normalised on its own: a range gets its own noise scale).  The conventions are this library's; tests/bands_oracle.py
+ * restates them in numpy.  Every sum stays exact (this is not an approximate sub-band dedispersion).
+ *
+ * Bands.  nsub (1..16) divides nchan; cps = nchan / nsub; sub-band s holds channels s cps .. (s + 1) cps - 1.  A band is a
+ * range [a, b) of sub-bands with min_sub <= b - a <= max_sub (min_sub = 0 means 1, max_sub = 0 means nsub), numbered by
+ * ascending a, then ascending b: the full band [0, nsub), where it is listed, is the last band that starts at 0.
+ *
+ * Series.  For band j = [a, b), with n_c, value (the clip's replacement), S (the zero-DM row sums over the FULL band),
+ * nout and the clip exactly those of frbch_dedisperse_*:
+ *     y[dm][j][t] = (float)( sum_{c in [a cps, b cps)} value(t + n_c(dm), c)
+ *                            - (zerodm ? (sum over the same c of S[t + n_c(dm)]) / nchan : 0) )
+ * both sums in double over ascending c.  The delays stay referenced to the top of the FULL band, so that ranges add up,
+ * and band [0, nsub) is frbch_dedisperse_*'s series to the bit for every row type.  On 8- / 16-bit rows every sum is an
+ * exact integer in any order.  The plane is out[dm * nband + j][t], float32: the layout frbch_spsearch_device reads, with
+ * ndm * nband series.
+ *
+ * FRBCH_E_ARG, each with its own message: a wrong `size`; nsub outside 1..16 or no divisor of nchan; min_sub > max_sub;
+ * max_sub > nsub; ndm * nband above 65535 (the search's limit on series); everything frbch_dedisperse_* refuses. */
+typedef struct frbch_band_params {
+  uint32_t size, nsub;                 /* = sizeof(frbch_band_params); 1..16, a divisor of nchan                         */
+  uint32_t min_sub, max_sub;           /* widths b - a that are listed; 0 = 1 and 0 = nsub                                */
+} frbch_band_params;
+/* Host only.  *nband receives the number of bands; sub_lo[cap] / sub_hi[cap] (either may be NULL with cap = 0, which counts)
+ * receive a and b of the first `cap` bands.  More bands than `cap`: FRBCH_E_CAPACITY with *nband set. */
+int frbch_band_list(uint32_t nchan, const frbch_band_params* bands, uint16_t* sub_lo, uint16_t* sub_hi, uint32_t cap,
+                    uint32_t* nband, char* err, size_t err_cap);
+/* Which kernels frbch_dedisperse_bands_device takes for these arguments (host only, nothing runs): 1 = the tiled prefix
+ * kernel and the range kernel behind it (8- / 16-bit rows, nchan <= 65536, a sub-band a whole number of 64-byte channel
+ * tiles, and what frbch_dedisperse_kernel asks of the tiled dedispersion: 16-byte aligned d_rows and row pitch, every
+ * (DM group, channel tile) within the rows the LDS holds), 0 = the generic kernel (a thread per (dm, t) that walks the
+ * channels once per first sub-band), < 0 = refused.  Only the ADDRESS of d_rows is examined.  Both give the same bytes. */
+int frbch_dedisperse_bands_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const double* dms, uint32_t ndm,
+                                  const frbch_band_params* bands);
+/* d_out / out is [ndm * nband][nout] with nout = frbch_dedisperse_nout(); *kernel_used (may be NULL) as above.  The tiled
+ * form allocates its scratch itself: the prefix plane [ndm][nsub][nout] of uint32, and with zerodm one of double. */
+int frbch_dedisperse_bands_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const double* dms, uint32_t ndm,
+                                  uint32_t zerodm, double clip_sigma, const frbch_band_params* bands, int device, float* d_out,
+                                  uint64_t nout, uint64_t* nclipped, uint32_t* kernel_used, char* err, size_t err_cap);
+int frbch_dedisperse_bands_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const double* dms, uint32_t ndm,
+                                uint32_t zerodm, double clip_sigma, const frbch_band_params* bands, int device, float* out,
+                                uint64_t nout, uint64_t* nclipped, uint32_t* kernel_used, char* err, size_t err_cap);
+
+typedef struct frbch_spb_cand {
+  uint32_t dm_index, width;            /* index into dms, boxcar width in samples                                        */
+  uint64_t sample;                     /* centre c = t + w / 2                                                           */
+  float sigma;
+  uint16_t sub_lo, sub_hi;             /* the band [sub_lo, sub_hi) whose series holds the record                        */
+} frbch_spb_cand;
+/* The production call.  The rows cross to the device once (_host) or lie in HBM already and are never written (_device);
+ * the clip / zero-DM pre-pass runs once; then batches of consecutive DMs: frbch_dedisperse_bands_device's kernels and
+ * frbch_spsearch_device on a plane that stays on the device.  A batch holds the largest number of DMs whose plane
+ * (nband * nout floats per DM) fits plane_bytes (0 means 1 GiB; fewer bytes than one DM's plane: FRBCH_E_ARG); the scratch
+ * of the tiled form comes on top.  The records -- those of frbch_spsearch_device on every series, sorted by (dm_index,
+ * sub_lo, sub_hi, sample, width) -- do not depend on the batch size.  The search's cap of 2^20 raw peaks holds per batch
+ * and is reported as FRBCH_E_CAPACITY ("threshold too low"), never as a cut list; more records than `cap`:
+ * FRBCH_E_CAPACITY with *ncand set (cap = 0 with cands = NULL counts).  kernel_used (may be NULL) receives [0] the
+ * dedispersion form (1 only if every batch took the tiled form) and [1] the search kernel; *nbatch (may be NULL) the number
+ * of batches; stage_ms (may be NULL) the host's clock around [0] the pre-pass, [1] the dedispersion of all batches and
+ * [2] their searches, each with the download of its raw peaks. */
+int frbch_bandsearch_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const double* dms, uint32_t ndm,
+                            uint32_t zerodm, double clip_sigma, const frbch_band_params* bands, const frbch_sp_params* params,
+                            uint64_t plane_bytes, int device, uint64_t nout, uint64_t* nclipped, frbch_spb_cand* cands,
+                            uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, uint32_t* nbatch, double* stage_ms, char* err,
+                            size_t err_cap);
+int frbch_bandsearch_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const double* dms, uint32_t ndm,
+                          uint32_t zerodm, double clip_sigma, const frbch_band_params* bands, const frbch_sp_params* params,
+                          uint64_t plane_bytes, int device, uint64_t nout, uint64_t* nclipped, frbch_spb_cand* cands,
+                          uint64_t cap, uint64_t* ncand, uint32_t* kernel_used, uint32_t* nbatch, double* stage_ms, char* err,
+                          size_t err_cap);
+/* Grouping (host only): the link rule of frbch_sp_group_cands on (dm_index, sample, width).  The band plays NO part in
+ * linking -- a pulse shows in every range that overlaps it, and two pulses at one time in disjoint bands join as well.
+ * `best` is the member with the largest sigma; ties: the narrower range (sub_hi - sub_lo), then frbch_sp_group_cands'
+ * order (narrower width, lower dm_index, earlier sample), then the lower sub_lo.  full_sigma is the largest sigma among
+ * the members whose band is [0, nsub), 0 if there is none.  Groups come sorted by best's (dm_index, sample, width, sub_lo,
+ * sub_hi).  FRBCH_E_ARG: what frbch_sp_group_cands refuses, nsub outside 1..16, a record with sub_lo >= sub_hi or
+ * sub_hi > nsub. */
+typedef struct frbch_spb_group {
+  frbch_spb_cand best;
+  uint32_t nmember, dm_index_lo, dm_index_hi;
+  uint16_t sub_lo_min, sub_hi_max;     /* over the members' bands                                                         */
+  uint64_t sample_lo, sample_hi;       /* over the members' centres                                                       */
+  float full_sigma;
+  uint32_t reserved;
+} frbch_spb_group;
+int frbch_spb_group_cands(const frbch_fil_desc* fil, const double* dms, uint32_t ndm, uint32_t nsub, const frbch_spb_cand* cands,
+                          uint64_t ncand, uint32_t dm_gap, frbch_spb_group* groups, uint64_t cap, uint64_t* ngroup, char* err,
+                          size_t err_cap);
+
 /* ---- in front of the filterbank: the corner turn -------------------------------
  * jive5ab's spif2file splits the recorder's stream -- every W-bit word holds one time sample of ALL channels -- into one
  * 2-channel stream per IF, driven by the recipe strings of spif2file.sh:31-113, e.g. the 16-channel 2-bit mode
