@@ -108,7 +108,7 @@ extern "C" void frbch_close(frbch_handle* h) {
   dev_free(h->ftw1_r); dev_free(h->ftw2_r); dev_free(h->ftw1_c); dev_free(h->ftw2_c); dev_free(h->td1); dev_free(h->td2);
   dev_free(h->spill); dev_free(h->s_dc); dev_free(h->p0);
   dev_free(h->spill2); dev_free(h->chirp); dev_free(h->ptmp); dev_free(h->scr2);
-  dev_free(h->offset); dev_free(h->scale); dev_free(h->powbuf); dev_free(h->partial);
+  dev_free(h->offset); dev_free(h->scale); dev_free(h->powbuf); dev_free(h->partial); dev_free(h->stat_slices);
   dev_free(h->d_frames); dev_free(h->d_out); dev_free(h->stg); dev_free(h->d_fbad); dev_free(h->scan_rows);
   dev_free(h->dls_tab); dev_free(h->dls_nlow);
   for (int i = 0; i < 8; ++i) { dev_host_free(h->pin_in[i]); dev_host_free(h->pin_out[i]); }

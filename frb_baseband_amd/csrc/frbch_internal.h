@@ -86,6 +86,8 @@ struct frbch_handle {
   uint64_t pow_cap_rows = 0, pow_rows = 0;
   double* partial = nullptr;
   int partial_chunks = 0;
+  float* stat_slices = nullptr;   // frbch_k2_priv: the fp32 sums of every flush of a launch, [priv_grid][stat_slots][2][ncol]; lives and dies with `partial`
+  uint32_t stat_slots = 0;        // ... slots per workgroup: the flushes of a launch of maxb blocks (priv_stat_slots)
   // rescale statistics accumulated by the fast K2 while it emits the float power (no second pass)
   uint64_t fused_rows = 0;     // rows of the current interval whose moments are in `partial`
   bool fused_valid = false;    // ... and no row of the interval is missing from them

@@ -81,8 +81,11 @@ struct KParams {
   uint64_t stat_limit;      // ... of the rows below this absolute row of power_out (the end of the rescale interval)
   uint32_t nblk;            // blocks in this launch (persistent kernels loop over them)
   uint32_t stat_first;      // frbch_k2_priv: 1 = the rescale interval starts with this launch and nobody cleared the rows of stat_partial the
-                            // launch's workgroups own -- a workgroup's first flush stores its sums instead of adding them (the host side sets
-                            // it: clear_partial)
+                            // launch's workgroups own -- a workgroup's sums start from 0.0, not from its row (the host side sets it:
+                            // clear_partial)
+  float* stat_slices;       // frbch_k2_priv: [workgroup][slot][2][ncol] the fp32 sums (then sums of squares) of each flush, output column
+                            // order: written in the loop, folded into the workgroup's row of stat_partial when the workgroup ends
+  uint32_t stat_slots;      // ... slots per workgroup (the host side refuses a launch whose trips need more)
   const uint8_t* stg;        // wave K1: the launch's payload re-ordered by frbch_k0_stage, [blk][branch group][row][RB bytes]: the
                              // rows of one workgroup and block are contiguous (null = gather from the frames)
   uint8_t* stg_out;          // frbch_k0_stage: where it writes that buffer

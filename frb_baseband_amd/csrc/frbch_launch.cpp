@@ -317,6 +317,14 @@ PrivLaunch priv_launch(const frbch_handle* h, const KParams& p, uint32_t nb) {
                     !pol_mode_no_sums(p.pol_mode) && !(h->cfg.flags & kFlagSeparateStats);
   return {(unsigned)std::min<uint64_t>(ntiles, (uint64_t)h->priv_grid), sums};
 }
+// slots of fp32 sums a workgroup of that launch fills (KParams::stat_slices): one per flush, a flush every 8 trips
+// (fast::kK2PFlushMask) and behind the last trip; `grid` workgroups over nb blocks of r / 4 tiles, the longest run rounded up
+uint32_t priv_stat_slots(const Plan& pl, uint32_t nb, unsigned grid) {
+  if (!grid) return 0;
+  const uint64_t ntiles = (uint64_t)nb * (uint64_t)(pl.r / 4);
+  const uint64_t trips = (ntiles + grid - 1) / grid;
+  return (uint32_t)((trips + fast::kK2PFlushMask) / (fast::kK2PFlushMask + 1u));
+}
 // rows of partial sums the fused statistics of frbch_k2_wave / frbch_k3_wave use; 0 = this configuration cannot fuse (one column
 // group per thread needed)
 int wave_stat_chunks(const Plan& pl, uint32_t h_flags, int pol_mode) {
@@ -484,6 +492,8 @@ bool launch_k2_fast(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
     p.nblk = nb;
     if (!pv.sums) p.stat_partial = nullptr;
     if (!p.stat_partial) p.stat_first = 0;
+    p.stat_slices = p.stat_partial ? h->stat_slices : nullptr;   // (launch_back has checked that the launch's flushes fit the slots)
+    p.stat_slots = p.stat_partial ? h->stat_slots : 0u;
     const dim3 grid(pv.grid);
     return select_k2_priv(pl, p.pol_mode, p.out_mode, [&](auto kern, const KSel& a) { launch_sel(h, kern, grid, a, s, p); });
   }
@@ -749,6 +759,13 @@ int launch_back(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
   const bool k3_sums = false;
 #endif
   if ((!k2_wave_planned(pl) || pl.coherent) && !k3_sums) p.stat_partial = nullptr;   // only the wave-private K2 / K3 sum while they write
+#ifndef FRBCH_NO_FAST
+  // frbch_k2_priv writes one slot of fp32 sums per flush: a launch with more flushes per workgroup than ensure_partial allocated
+  // slots (more blocks than the plan's batch) is refused here, it never runs with an index that leaves the buffer
+  if (const PrivLaunch pv = priv_launch(h, p, nb); pv.sums && (!h->stat_slices || priv_stat_slots(pl, nb, pv.grid) > h->stat_slots))
+    return fail(h, FRBCH_E_CAPACITY, "frbch_k2_priv: " + std::to_string(priv_stat_slots(pl, nb, pv.grid)) + " flushes per workgroup, " +
+                                         std::to_string(h->stat_slots) + " slots of rescale sums allocated");
+#endif
   if (p.out_mode == FRBCH_OUT_STATS) {   // first pass of the two-pass rescale: the spill is read, nothing but the sums is written
     ProfScope ps(h, s, KID_K2S, (double)nb * (double)pl.n * 8.0);
     if (!launch_k2_fast(h, p, nb, s)) return fail(h, FRBCH_E_STATE, "statistics-only K2 pass without frbch_k2_priv");
@@ -804,10 +821,19 @@ int ensure_partial(frbch_handle* h) {
 #endif
   const size_t chunks = (size_t)std::max(h->partial_chunks, h->fused_chunks);
   CHECK_DEV(h, dev_malloc((void**)&h->partial, chunks * pl.ncol * 2 * sizeof(double)), "hipMalloc(partials)");
+#ifndef FRBCH_NO_FAST
+  // ... and the slices frbch_k2_priv flushes its fp32 sums into, one slot per flush of the longest launch (maxb blocks): at
+  // config 3 512 workgroups x 19 slots x 32 KB = 319 MB per handle (beside a 5.1-GB spill)
+  h->stat_slots = 0;
+  if (pl.fast_k2_priv && h->priv_grid > 0 && !pol_mode_no_sums(h->cfg.pol_mode) && !(h->cfg.flags & kFlagSeparateStats)) {
+    h->stat_slots = priv_stat_slots(pl, (uint32_t)pl.maxb, (unsigned)h->priv_grid);
+    CHECK_DEV(h, dev_malloc((void**)&h->stat_slices, (size_t)h->priv_grid * h->stat_slots * pl.ncol * 2 * sizeof(float)), "hipMalloc(slices of partials)");
+  }
+#endif
   return FRBCH_OK;
 }
 // A rescale interval starts with the K2 launch of `p` (out_mode, tile_major and stat_partial set).  The kernels add into the table, so
-// it is cleared first -- except for frbch_k2_priv, whose workgroups own a row each and store their first flush when told so
+// it is cleared first -- except for frbch_k2_priv, whose workgroups own a row each and start their sums from 0.0, not from the row, when told so
 // (KParams::stat_first): no memset in front of the pass, and frbch_stats_final reads those rows only (fused_live; the rows behind
 // them would be zeros: the sums are the same bit for bit, every column is added up in the same order).
 int clear_partial(frbch_handle* h, KParams& p, uint32_t nb, dev_stream_t s) {
@@ -1019,6 +1045,8 @@ int apply_plan(frbch_handle* h) {
   dev_free(h->scr2); h->scr2 = nullptr;
   dev_free(h->ptmp); h->ptmp = nullptr;
   dev_free(h->partial); h->partial = nullptr;   // (its rows follow the K2 of the plan: ensure_partial sizes it again)
+  dev_free(h->stat_slices); h->stat_slices = nullptr;
+  h->stat_slots = 0;
   h->partial_chunks = h->fused_chunks = 0;
   h->fused_rows = 0;
   h->fused_valid = false;

@@ -29,8 +29,11 @@
 // Three output modes (template MODE): codes (A9 + A10 with the frozen scale), float power rows with the rescale sums of the
 // interval (the buffered path), and STATISTICS ONLY -- the first pass of the two-pass rescale (frbch_stream.cpp: the float rows of
 // a first rescale interval are never written; K2 runs twice over the resident spill instead, 18 B per sample behind K1 instead of 26).
-// Rescale sums: fp32 in registers over at most 8 trips (32 rows), then added into the workgroup's own row of the fp64 partial table
-// (exclusive: a plain read-modify-write, bit-reproducible); frbch_stats_final reduces the rows in a fixed order.
+// Rescale sums: fp32 in registers over at most 8 trips (32 rows), then STORED, as fp32, into the next slot of the workgroup's own
+// slice (KParams::stat_slices: write-only inside the loop, no load, no wait); when the workgroup has run its last trip every
+// thread adds the slots of its columns, in ascending order and in fp64, into the workgroup's own row of the fp64 partial table
+// (exclusive, bit-reproducible: the chain of adds the in-place flush of rounds 4 and 5 evaluated); frbch_stats_final reduces the
+// rows in a fixed order.
 //
 // grid (<= 2 x CUs), 256 threads, LDS 4 images + dP = 81,920 bytes (two workgroups per CU).  HIP only.
 
@@ -123,52 +126,66 @@ __global__ void __launch_bounds__(256, 2) frbch_k2_priv(KParams p) {
   const bool stat_on = MODE != K2P_CODES && p.stat_partial != nullptr;
   const int lg_t = 31 - __builtin_clz(p.tscr);
   const int R = p.r;
-  // this workgroup's row of the fp64 partial sums is its own: a plain read-modify-write of the thread's 8 * CGT doubles, 16 bytes at
-  // a time.  (No-return fp64 atomics were tried first -- no load, hence no wait in the loop: 159 M of them per IF took 2.1 ms, the
-  // memory-side atomic units are far slower than the 1.2 GB they carry.)  The loads' wait also covers the next tile's loads, which
-  // the wave is about to wait for anyway: the flush sits at the very end of a trip.  (Requested ahead -- in front of the transform,
-  // or behind the trip's first barrier -- the row spills with four products: 54 registers for all of it, 23 for half; profiles/NOTES.md, round 5, item 2.)
-  // `fresh`: the first flush of a launch that starts a rescale interval (p.stat_first).  Nobody cleared the row: it is not read, the
-  // sums are stored as 0.0 + sum, which is what the add into a cleared table gave.
-  // The statistics pass keeps its sums in the order the row lies in the LDS (input channels), the table is in output channel
-  // order: `flip` reverses the four columns of a group here, once per flush, not once per row.
-  auto flush_sums = [&](const bool fresh) {
+  // The fp32 sums of flush k (trips 8 k .. 8 k + 7) leave the registers as they are: 16-byte stores into slot k of the workgroup's
+  // own slice of p.stat_slices, [workgroup][slot][sums | sums of squares][NCOL], nothing loaded, nothing waited for.  The workgroup's
+  // row of the fp64 table is formed once, behind the loop (fold_sums).  (Before round 6 every flush added into the row in place:
+  // load, wait, add in fp64, store at the end of every 8th trip -- 64 KB read and 64 KB written per flush through a table that
+  // 5 GB of spill had long pushed out of the caches, and a wait that covered the whole in-order vector-memory queue.  No-return
+  // fp64 atomics, tried first of all, took 2.1 ms per IF.)
+  // The statistics pass keeps its sums in the order the row lies in the LDS (input channels), slices and table are in output
+  // channel order: `flip` reverses the four columns of a group here, once per flush, not once per row.
+  static_assert(MODE == K2P_CODES || RS == 1, "the slices hold one row of sums per workgroup");
+  auto flush_sums = [&](const uint32_t k) {
     int tl = tid;
     asm volatile("" : "+v"(tl));   // (the CGT target addresses are recomputed here: hoisted out of the loop they were spilled)
-    typedef double nd2 __attribute__((ext_vector_type(2)));
-    constexpr int GB = CGT >= 2 ? 2 : 1;            // groups in flight at a time (16 registers each)
     const bool fl = MODE == K2P_STATS && flip;      // (the float-row form sums in output order already)
+    float* const sl = p.stat_slices + ((uint64_t)blockIdx.x * (uint64_t)p.stat_slots + (uint64_t)k) * (uint64_t)(2 * NCOL);
 #pragma unroll
-    for (int g0 = 0; g0 < CGT; g0 += GB) {
-      nd2 cur[GB][4];
+    for (int g = 0; g < CGT; ++g) {
+      const uint64_t col = (uint64_t)(tl + NT * g) * 4u;
+      const nf4 a1 = {fl ? of4[g].w : of4[g].x, fl ? of4[g].z : of4[g].y, fl ? of4[g].y : of4[g].z, fl ? of4[g].x : of4[g].w};
+      const nf4 a2 = {fl ? sc4[g].w : sc4[g].x, fl ? sc4[g].z : sc4[g].y, fl ? sc4[g].y : sc4[g].z, fl ? sc4[g].x : sc4[g].w};
+      *reinterpret_cast<nf4*>(sl + col) = a1;
+      *reinterpret_cast<nf4*>(sl + (uint64_t)NCOL + col) = a2;
+      of4[g] = sc4[g] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  };
+  // The end of the workgroup's life: every thread adds up the slots of its own columns -- what it wrote itself, nobody else's -- one
+  // at a time in ascending k, in fp64, starting from 0.0 when the launch starts a rescale interval (p.stat_first: nobody cleared the
+  // row, it is not read) and from the row of the table otherwise: ((row + a0) + a1) + ..., the chain the in-place add evaluated, on
+  // the same values in the same order, hence the same bits.  The loads of kFoldSlots slots are requested before their adds.
+  auto fold_sums = [&](const uint32_t nflush) {
+    typedef double nd2 __attribute__((ext_vector_type(2)));
+    constexpr uint32_t kFoldSlots = 4;
+    const float* const sl0 = p.stat_slices + (uint64_t)blockIdx.x * (uint64_t)p.stat_slots * (uint64_t)(2 * NCOL);
+    const bool fresh = p.stat_first != 0;
+    for (int g = 0; g < CGT; ++g) {
+      const uint64_t col = (uint64_t)(tid + NT * g) * 4u;
+      nd2* const row = reinterpret_cast<nd2*>(p.stat_partial + ((uint64_t)blockIdx.x * (uint64_t)NCOL + col) * 2u);
+      nd2 acc[4];
 #pragma unroll
-      for (int gg = 0; gg < GB; ++gg) {
-        const int g = g0 + gg;
-        const nd2* src = reinterpret_cast<const nd2*>(p.stat_partial + (((size_t)blockIdx.x * RS + (RS > 1 ? tl / NG : 0)) * NCOL + (size_t)((RS > 1 ? tl % NG : tl) + NT * g) * 4) * 2);
-        // (statistics pass: a first flush does not load at all.  The float-row form has no register to spare for the second path
-        // -- 10 spilled with it, none without (profiles/NOTES.md, round 5): it loads and drops what it gets, below)
+      for (int e = 0; e < 4; ++e) acc[e] = fresh ? nd2{0.0, 0.0} : row[e];
+      for (uint32_t k0 = 0; k0 < nflush; k0 += kFoldSlots) {
+        nf4 a1[kFoldSlots], a2[kFoldSlots];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) cur[gg][e] = nd2{0.0, 0.0};
-        if (MODE != K2P_STATS || !fresh)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) cur[gg][e] = src[e];
-      }
-#pragma unroll
-      for (int gg = 0; gg < GB; ++gg) {
-        const int g = g0 + gg;
-        nd2* dst = reinterpret_cast<nd2*>(p.stat_partial + (((size_t)blockIdx.x * RS + (RS > 1 ? tl / NG : 0)) * NCOL + (size_t)((RS > 1 ? tl % NG : tl) + NT * g) * 4) * 2);
-        const float a1[4] = {fl ? of4[g].w : of4[g].x, fl ? of4[g].z : of4[g].y, fl ? of4[g].y : of4[g].z, fl ? of4[g].x : of4[g].w};
-        const float a2[4] = {fl ? sc4[g].w : sc4[g].x, fl ? sc4[g].z : sc4[g].y, fl ? sc4[g].y : sc4[g].z, fl ? sc4[g].x : sc4[g].w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          nd2 t = cur[gg][e];
-          t.x = (fresh ? 0.0 : t.x) + (double)a1[e];
-          t.y = (fresh ? 0.0 : t.y) + (double)a2[e];
-          dst[e] = t;
+        for (uint32_t j = 0; j < kFoldSlots; ++j) {
+          const uint32_t k = k0 + j < nflush ? k0 + j : nflush - 1u;   // (past the end: the last slot again, not added)
+          const float* const sl = sl0 + (uint64_t)k * (uint64_t)(2 * NCOL) + col;
+          a1[j] = *reinterpret_cast<const nf4*>(sl);
+          a2[j] = *reinterpret_cast<const nf4*>(sl + NCOL);
         }
-        of4[g] = sc4[g] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (uint32_t j = 0; j < kFoldSlots; ++j) {
+          if (k0 + j < nflush) {
+            acc[0].x += (double)a1[j].x; acc[0].y += (double)a2[j].x;
+            acc[1].x += (double)a1[j].y; acc[1].y += (double)a2[j].y;
+            acc[2].x += (double)a1[j].z; acc[2].y += (double)a2[j].z;
+            acc[3].x += (double)a1[j].w; acc[3].y += (double)a2[j].w;
+          }
+        }
       }
-      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) row[e] = acc[e];
     }
   };
   int cur_blk = -1;
@@ -386,10 +403,13 @@ __global__ void __launch_bounds__(256, 2) frbch_k2_priv(KParams p) {
     }
     __syncthreads();   // the power rows are consumed: the next trip's first pass may overwrite the images
     if constexpr (MODE != K2P_CODES) {   // at most 8 trips = 32 rows in fp32
-      if (stat_on && ((it & kK2PFlushMask) == kK2PFlushMask || it + 1 == count)) flush_sums(p.stat_first && it <= kK2PFlushMask);   // (a workgroup's first flush has it <= 7)
+      if (stat_on && ((it & kK2PFlushMask) == kK2PFlushMask || it + 1 == count)) flush_sums(it >> 3);   // slot it / 8 (kK2PFlushMask + 1 = 8)
     }
   }
-
+  if constexpr (MODE != K2P_CODES) {
+    static_assert(kK2PFlushMask == 7u, "slot = trip / 8");
+    if (stat_on) fold_sums((count + kK2PFlushMask) >> 3);
+  }
 }
 
 }  // namespace fast
