@@ -30,16 +30,17 @@ DTYPES = {8: np.uint8, 16: np.uint16}
 
 
 # ---- the second restatement of the burst sums ------------------------------------------------------------------------
-def window_sums(x, hdr, cands):
+def window_sums(x, hdr, cands, c0=0):
     """x [nrows][nifs][nchan] integers -> BURST_SUMS [ncand][nifs][nchan]: per-channel prefix sums of x and of x x in int64,
-    differenced at clip(w0 + d, 0, nrows) and clip(w0 + d + len, 0, nrows) of every window"""
+    differenced at clip(w0 + d, 0, nrows) and clip(w0 + d + len, 0, nrows) of every window.  x may hold a block of the header's
+    channels, c0 .. c0 + nchan - 1 (a block at a time keeps the int64 plane of 65 536 channels small)"""
     nrows, nifs, nchan = x.shape
     assert x.dtype in (np.uint8, np.uint16)
     out = np.zeros((len(cands), nifs, nchan), dtype=post.BURST_SUMS)
     chans = np.arange(nchan)
     edges = []
     for i, cd in enumerate(cands):
-        d = ro.delays(hdr, float(cd["dm"]))
+        d = ro.delays(hdr, float(cd["dm"]))[c0:c0 + nchan]
         edges.append([(which, np.clip(w0 + d, 0, nrows), np.clip(w0 + d + length, 0, nrows)) for w0, length, which in ro.windows(cd)])
         hits = np.zeros((2, nchan), np.int64)
         for which, lo, hi in edges[-1]:
@@ -51,10 +52,10 @@ def window_sums(x, hdr, cands):
             if square:
                 v = x[:, p, :].astype(np.int64)
                 v *= v
-                np.cumsum(v, axis=0, out=cs[1:])
+                ro.cumsum_rows(v, cs)
                 del v
             else:
-                np.cumsum(x[:, p, :], axis=0, dtype=np.int64, out=cs[1:])
+                ro.cumsum_rows(x[:, p, :], cs)
             for i, e in enumerate(edges):
                 tot = np.zeros((2, nchan), np.int64)
                 for which, lo, hi in e:

@@ -43,7 +43,7 @@ def bin_sums(x, d, t0, nbin, tfactor):
     lo = int(e.min())
     hi = max(lo, int(e.max()))
     cs = np.zeros((hi - lo + 1, nchan), np.int64)
-    np.cumsum(x[lo:hi], axis=0, dtype=np.int64, out=cs[1:])
+    ro.cumsum_rows(x[lo:hi], cs)
     cc = np.arange(nchan)[:, None]
     return cs[e[:, 1:] - lo, cc] - cs[e[:, :-1] - lo, cc], e[:, 1:] - e[:, :-1]
 

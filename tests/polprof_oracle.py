@@ -27,7 +27,7 @@ def bin_sums(x, d, t0, nbin, tfactor):
         lo = int(e.min())
         hi = max(lo, int(e.max()))
         cs = np.zeros((hi - lo + 1, 4, c1 - c0), np.int64)
-        np.cumsum(x[lo:hi, :, c0:c1], axis=0, dtype=np.int64, out=cs[1:])
+        ro.cumsum_rows(x[lo:hi, :, c0:c1], cs)
         cc = np.arange(c1 - c0)[:, None]
         for p in range(4):
             S[p, c0:c1] = cs[e[:, 1:] - lo, p, cc] - cs[e[:, :-1] - lo, p, cc]

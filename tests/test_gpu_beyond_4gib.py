@@ -1,13 +1,18 @@
-"""GPU tests of every device entry point behind the filterbank on rows that pass 2^31 and 2^32 -- counted in bytes, in elements
-and in t * nchan -- at the shapes of the spliced files: A8 (8192 channels x 4 products x 8 bit, config 3's IFall), A16 (8192 x 2 x
+"""GPU tests of the device entry points behind the filterbank that walk the whole file -- dedispersion, the interference stages,
+both folds, the cut-outs, the single-pulse search and frbch_candidates_device -- on rows that pass 2^31 and 2^32, counted in
+bytes, in elements and in t * nchan; the entry points that are pointed at a candidate or at sub-bands (burst spectra and RM,
+profile, DM scan, burst ACF, scattering, the band series and the band search) are held on the same rows by
+tests/test_gpu_beyond_4gib_burst.py.  The shapes are those of the spliced files: A8 (8192 channels x 4 products x 8 bit, config 3's IFall), A16 (8192 x 2 x
 16 bit: the same row, the element count passes 2^31) and B8 (65 536 channels of Stokes I, config 4's IFall).  tests/big_rows.py
 describes the 4.4 GB of rows by a base of 3001 rows, fills the device buffer by device-to-device copies and rebuilds any window
 on the host; tests/test_big_rows.py holds its references to the restatements on a whole small array.  Every stage runs at the
 16-byte aligned address (its fast kernel) and a few bytes further on (its generic kernel) and asserts which kernel it took;
 outputs are compared at the start, where the input rows straddle each mark, and at the ragged end -- `==`, no tolerance.
 
-Not covered here: the writers whose row count shrinks with `-t` (frbch_k2_scrunch) and the coherent chain's frbch_k4_fast, the
-emulator build at this size, and the `_host` forms other than frbch_dedisperse_host."""
+Not covered here or in tests/test_gpu_beyond_4gib_burst.py, so not held past the mark: the series readers of the periodicity and
+acceleration searches and frbch_resample_device; the `_host` twins other than frbch_dedisperse_host; the band plane past 2^32
+ELEMENTS (both modules pass 2^32 bytes of it); the writers whose row count shrinks with `-t` (frbch_k2_scrunch) and the coherent
+chain's frbch_k4_fast; the emulator build at this size."""
 import ctypes as C
 import functools
 
