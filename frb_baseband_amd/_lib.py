@@ -162,6 +162,18 @@ class FrbchRmResult(C.Structure):
                 ("fitted", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class FrbchRmdParams(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("nphi", C.c_uint32), ("ntau", C.c_uint32), ("reserved", C.c_uint32), ("phi_lo", C.c_double),
+                ("dphi", C.c_double), ("tau_lo", C.c_double), ("dtau", C.c_double)]
+
+
+class FrbchRmdResult(C.Structure):
+    _fields_ = [("tau", C.c_double), ("tau_err", C.c_double), ("rm", C.c_double), ("rm_err", C.c_double), ("peak", C.c_double),
+                ("psi", C.c_double), ("snr", C.c_double), ("sigma_f", C.c_double), ("fwhm", C.c_double), ("fwhm_tau", C.c_double),
+                ("ridge_slope", C.c_double), ("mpeak", C.c_uint32), ("kpeak", C.c_uint32), ("nused", C.c_uint32),
+                ("fitted_tau", C.c_uint32), ("fitted_rm", C.c_uint32), ("nridge", C.c_uint32)]
+
+
 PROF_REF_MEAN, PROF_REF_ZERO = 0, 1
 
 
@@ -408,6 +420,21 @@ SYMBOLS = {
                                         C.POINTER(FrbchRmParams), C.c_int, _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
     "frbch_burst_rm_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32, _P, _P,
                                       C.POINTER(FrbchRmParams), C.c_int, _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "frbch_rmdelay_kernel": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint32, C.POINTER(FrbchRmdParams), C.POINTER(C.c_uint32)]),
+    "frbch_rmdelay_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, _P, _P, C.c_uint32, C.POINTER(FrbchRmdParams), C.c_int, _P, _P,
+                                       C.c_char_p, C.c_size_t]),
+    "frbch_rmdelay_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, _P, _P, C.c_uint32, C.POINTER(FrbchRmdParams), C.c_int, _P, _P,
+                                     C.c_char_p, C.c_size_t]),
+    "frbch_rmdelay_peaks": (C.c_int, [C.POINTER(FrbchFilDesc), _P, _P, _P, _P, C.c_uint32, C.POINTER(FrbchRmdParams), _P, C.c_char_p,
+                                      C.c_size_t]),
+    "frbch_burst_polcal_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32, _P, _P,
+                                            C.POINTER(FrbchRmdParams), C.c_int, _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "frbch_burst_polcal_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32, _P, _P,
+                                          C.POINTER(FrbchRmdParams), C.c_int, _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "frbch_polprof_cal_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32, _P, _P, _P,
+                                           _P, C.POINTER(FrbchProfParams), C.c_int, _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "frbch_polprof_cal_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32, _P, _P, _P,
+                                         _P, C.POINTER(FrbchProfParams), C.c_int, _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
     "frbch_polprof_kernel": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32,
                                        C.POINTER(FrbchProfParams)]),
     "frbch_polprof_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchBurstParams), _P, C.c_uint32, _P, _P, _P,

@@ -4183,6 +4183,292 @@ int rm_peaks_run(const frbch_fil_desc* fil, const float* F, const uint8_t* used,
   return FRBCH_OK;
 }
 
+// ---- polarisation calibration: the delay x RM transform (include/frbch.h states the arithmetic) ------------------------
+constexpr uint32_t kRmdMaxTau = 4096;
+constexpr double kRmdTauLim = 100.0;
+
+inline frbch_rm_params rmd_rm_params(const frbch_rmd_params* par) {
+  return frbch_rm_params{(uint32_t)sizeof(frbch_rm_params), par->nphi, par->phi_lo, par->dphi};
+}
+
+int rmd_check(const frbch_fil_desc* fil, uint32_t ncand, const frbch_rmd_params* par, const PostErr& e) {
+  POST_NO_CONTRACT
+  if (!par || par->size != sizeof(frbch_rmd_params)) return e.fail(FRBCH_E_ARG, "frbch_rmd_params: wrong size");
+  const frbch_rm_params rp = rmd_rm_params(par);
+  const int rc = rm_check(fil, ncand, &rp, e);
+  if (rc) return rc;
+  if (par->ntau < 1 || par->ntau > kRmdMaxTau) return e.fail(FRBCH_E_ARG, "ntau must be 1..4096");
+  if ((uint64_t)ncand * par->nphi * par->ntau > kRmMaxOut) return e.fail(FRBCH_E_ARG, "ncand * ntau * nphi exceeds 2^26");
+  if (!(par->dtau > 0) || !rm_finite(par->dtau)) return e.fail(FRBCH_E_ARG, "dtau must be positive and finite");
+  const double hi = par->tau_lo + (double)par->ntau * par->dtau;
+  if (!(fabs(par->tau_lo) <= kRmdTauLim) || !(fabs(hi) <= kRmdTauLim)) return e.fail(FRBCH_E_ARG, "|tau| above 100 microseconds");
+  return FRBCH_OK;
+}
+
+// The plan rule of the delay x RM transform -- the one decision behind frbch_rmdelay_device's launches, kernel_used and
+// frbch_rmdelay_kernel's answer.  Form and split as rm_plan_rule has them (whole waves along k, an 8-byte aligned F, two
+// workgroups per CU before a candidate's channels are split in pieces of at least 64), with the tau tiles counted among the
+// workgroups.  The tau tile is the largest of 8, 4, 2, 1 whose tail -- trials beyond ntau that the last tile computes in
+// vain -- is at most an eighth of ntau: the registers hold 8 (kernels_post_fast.inc), and a term saved by sharing a record
+// is worth far less than a term wasted.  The emulator build has no such kernel: generic, split 1.
+struct RmdPlanRule { bool fastk; int nsplit, chunk, ttile; };
+RmdPlanRule rmd_plan_rule(uint32_t nchan, uint32_t ncand, uint32_t nphi, uint32_t ntau, const float* d_F) {
+  RmdPlanRule r{false, 1, (int)nchan, 1};
+#ifndef FRBCH_NO_FAST
+  if (nphi < 64 || ((uintptr_t)d_F % 8) != 0) return r;
+  r.fastk = true;
+  for (uint32_t t = fast::kRmdTauMax; t > 1; t /= 2)
+    if ((((ntau + t - 1) / t) * t - ntau) * 8 <= ntau) { r.ttile = (int)t; break; }
+  const uint64_t ttiles = (ntau + (uint32_t)r.ttile - 1) / (uint32_t)r.ttile;
+  const uint64_t base = (uint64_t)ncand * ttiles * ((nphi + fast::kRmThreads * fast::kRmKpt - 1) / (fast::kRmThreads * fast::kRmKpt));
+  if (base < 512) {
+    const uint64_t want = (512 + base - 1) / base, most = (nchan + 63) / 64;
+    const uint32_t ns = (uint32_t)std::min(want, most);
+    r.chunk = (int)((nchan + ns - 1) / ns);
+    r.nsplit = (int)((nchan + (uint32_t)r.chunk - 1) / (uint32_t)r.chunk);
+  }
+#else
+  (void)ncand; (void)nphi; (void)ntau; (void)d_F;
+#endif
+  return r;
+}
+
+struct RmdPlan {
+  std::vector<RmdRec> rec;                       // [ncand][nchan]
+  std::vector<RmCand> cand;
+  std::vector<int32_t> table;
+};
+
+// the records: those of step 2 (rm_build, unchanged), then f0, b, T0 and E of the used channels in the same order
+int rmd_build(const frbch_fil_desc* fil, const float* q, const float* u, const uint8_t* used, uint32_t ncand, const frbch_rmd_params* par,
+              RmdPlan* plan, const PostErr& e) {
+  POST_NO_CONTRACT
+  const uint32_t nchan = fil->nchan;
+  const frbch_rm_params rp = rmd_rm_params(par);
+  RmPlan base;
+  const int rc = rm_build(fil, q, u, used, ncand, &rp, &base, e);
+  if (rc) return rc;
+  plan->rec.assign((size_t)ncand * nchan, RmdRec{0, 0, 0ull, 0ull, 0ull});
+  plan->cand.swap(base.cand);
+  plan->table.swap(base.table);
+  for (uint32_t i = 0; i < ncand; ++i) {
+    if (!plan->cand[i].nrec) continue;
+    const uint8_t* us = used + (size_t)i * nchan;
+    uint32_t N = 0;
+    double sum = 0.0;
+    for (uint32_t c = 0; c < nchan; ++c)
+      if (us[c]) {
+        const double f = fil->fch1_mhz + (double)c * fil->foff_mhz;
+        ++N;
+        sum = sum + f;
+      }
+    const double f0 = sum / (double)N;
+    const RmRec* src = base.rec.data() + (size_t)i * nchan;
+    RmdRec* rec = plan->rec.data() + (size_t)i * nchan;
+    uint32_t n = 0;
+    for (uint32_t c = 0; c < nchan; ++c)
+      if (us[c]) {
+        const double f = fil->fch1_mhz + (double)c * fil->foff_mhz;
+        const double b = f - f0;
+        RmdRec& r = rec[n];
+        r.qi = src[n].qi; r.ui = src[n].ui;
+        r.p0 = src[n].p0 + rm_fix(par->tau_lo * b);
+        r.d = src[n].d;
+        r.e = rm_fix(par->dtau * b);
+        ++n;
+      }
+  }
+  return FRBCH_OK;
+}
+
+// the launches on the scope's stream; `plan` stays alive until the caller has synchronised
+int rmd_launch(const frbch_fil_desc* fil, uint32_t ncand, const frbch_rmd_params* par, const RmdPlan& plan, float* d_F,
+               PostScope& ps, uint32_t* kernel_used, const PostErr& e) {
+  const RmdPlanRule rule = rmd_plan_rule(fil->nchan, ncand, par->nphi, par->ntau, d_F);
+  RmdRec* d_rec = nullptr;
+  RmCand* d_cand = nullptr;
+  int32_t* d_tab = nullptr;
+  POST_DEV(ps.alloc(&d_rec, plan.rec.size() * sizeof(RmdRec)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_cand, plan.cand.size() * sizeof(RmCand)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_tab, (size_t)kRmTableN * sizeof(int32_t)), "hipMalloc");
+  POST_DEV(dev_h2d(d_rec, plan.rec.data(), plan.rec.size() * sizeof(RmdRec), ps.s), "upload records");
+  POST_DEV(dev_h2d(d_cand, plan.cand.data(), plan.cand.size() * sizeof(RmCand), ps.s), "upload records");
+  POST_DEV(dev_h2d(d_tab, plan.table.data(), (size_t)kRmTableN * sizeof(int32_t), ps.s), "upload table");
+  RmdParams p;
+  memset(&p, 0, sizeof p);
+  p.rec = d_rec; p.cand = d_cand; p.table = d_tab; p.out = d_F;
+  p.nchan = (int)fil->nchan; p.nphi = (int)par->nphi; p.ntau = (int)par->ntau; p.ncand = (int)ncand; p.nsplit = rule.nsplit; p.chunk = rule.chunk;
+  if (kernel_used) { kernel_used[0] = rule.fastk ? 1 : 0; kernel_used[1] = (uint32_t)rule.nsplit; }
+  const size_t per = (size_t)par->ntau * par->nphi;
+#ifndef FRBCH_NO_FAST
+  if (rule.fastk) {
+    if (rule.nsplit > 1) {
+      long long* d_part = nullptr;
+      POST_DEV(ps.alloc(&d_part, (size_t)rule.nsplit * ncand * per * 2 * sizeof(long long)), "hipMalloc");
+      p.part = d_part;
+    }
+    const unsigned ktiles = (par->nphi + fast::kRmThreads * fast::kRmKpt - 1) / (fast::kRmThreads * fast::kRmKpt);
+    const unsigned ttiles = (par->ntau + (unsigned)rule.ttile - 1) / (unsigned)rule.ttile;
+    const dim3 grid(ktiles, ttiles * (unsigned)rule.nsplit, ncand), block(fast::kRmThreads);
+    switch (rule.ttile) {
+      case 8: POST_DEV(launch_lds(fast::frbch_post_rmd_fast<8>, grid, block, fast::kRmdLds, ps.s, p), "LDS size"); break;
+      case 4: POST_DEV(launch_lds(fast::frbch_post_rmd_fast<4>, grid, block, fast::kRmdLds, ps.s, p), "LDS size"); break;
+      case 2: POST_DEV(launch_lds(fast::frbch_post_rmd_fast<2>, grid, block, fast::kRmdLds, ps.s, p), "LDS size"); break;
+      default: POST_DEV(launch_lds(fast::frbch_post_rmd_fast<1>, grid, block, fast::kRmdLds, ps.s, p), "LDS size"); break;
+    }
+    POST_DEV(dev_check_launch(), "launch delay x RM transform");
+    if (rule.nsplit > 1) {
+      hipLaunchKernelGGL(fast::frbch_post_rmd_join, dim3((unsigned)((per + fast::kRmThreads - 1) / fast::kRmThreads), ncand), dim3(fast::kRmThreads), 0, ps.s, p);
+      POST_DEV(dev_check_launch(), "launch delay x RM join");
+    }
+    return FRBCH_OK;
+  }
+#endif
+  DEV_LAUNCH(frbch_post_rmd, (per + 255) / 256, ncand, 256, 0, ps.s, p);
+  POST_DEV(dev_check_launch(), "launch delay x RM transform");
+  return FRBCH_OK;
+}
+
+// the parabola of step 3 along one axis: the vertex offset in trial steps, or false (the grid value stands)
+inline bool rmd_vertex(bool interior, double ym, double y0, double yp, double* delta) {
+  POST_NO_CONTRACT
+  if (!interior) return false;
+  const double den = (ym - 2.0 * y0) + yp;
+  if (!(den < 0.0)) return false;
+  const double diff = ym - yp;
+  *delta = (0.5 * diff) / den;
+  return true;
+}
+
+// peak and ridge of one map P[ntau][nphi] into r (tau, rm, fitted_*, mpeak, kpeak, ridge_slope, nridge); -> P[mp][kp]
+double rmd_map_peak(const double* P, const frbch_rmd_params* par, frbch_rmd_result& r) {
+  POST_NO_CONTRACT
+  const size_t nphi = par->nphi, ntau = par->ntau;
+  size_t at = 0;
+  double best = P[0];
+  for (size_t x = 1; x < ntau * nphi; ++x)
+    if (P[x] > best) { best = P[x]; at = x; }
+  const size_t mp = at / nphi, kp = at % nphi;
+  r.mpeak = (uint32_t)mp;
+  r.kpeak = (uint32_t)kp;
+  double delta = 0.0;
+  r.tau = par->tau_lo + (double)mp * par->dtau;
+  if (rmd_vertex(mp > 0 && mp + 1 < ntau, mp > 0 ? P[at - nphi] : 0.0, best, mp + 1 < ntau ? P[at + nphi] : 0.0, &delta)) {
+    r.tau = par->tau_lo + ((double)mp + delta) * par->dtau;
+    r.fitted_tau = 1;
+  }
+  r.rm = par->phi_lo + (double)kp * par->dphi;
+  if (rmd_vertex(kp > 0 && kp + 1 < nphi, kp > 0 ? P[at - 1] : 0.0, best, kp + 1 < nphi ? P[at + 1] : 0.0, &delta)) {
+    r.rm = par->phi_lo + ((double)kp + delta) * par->dphi;
+    r.fitted_rm = 1;
+  }
+  std::vector<double> ts, fs;
+  const double floor_ = 0.5 * best;
+  for (size_t m = 0; m < ntau; ++m) {
+    const double* row = P + m * nphi;
+    size_t km = 0;
+    for (size_t k = 1; k < nphi; ++k)
+      if (row[k] > row[km]) km = k;
+    if (row[km] >= floor_) {
+      ts.push_back(par->tau_lo + (double)m * par->dtau);
+      fs.push_back(par->phi_lo + (double)km * par->dphi);
+    }
+  }
+  r.nridge = (uint32_t)ts.size();
+  if (ts.size() >= 2) {
+    double st = 0.0, sf = 0.0;
+    for (size_t j = 0; j < ts.size(); ++j) { st = st + ts[j]; sf = sf + fs[j]; }
+    const double mt = st / (double)ts.size(), mf = sf / (double)ts.size();
+    double sxx = 0.0, sxy = 0.0;
+    for (size_t j = 0; j < ts.size(); ++j) {
+      const double dt = ts[j] - mt, df = fs[j] - mf;
+      const double a = dt * dt, b = dt * df;
+      sxx = sxx + a;
+      sxy = sxy + b;
+    }
+    if (sxx > 0.0) r.ridge_slope = sxy / sxx;
+  }
+  return best;
+}
+
+int rmd_peaks_run(const frbch_fil_desc* fil, const float* F, const uint8_t* used, const float* noise_q, const float* noise_u,
+                  uint32_t ncand, const frbch_rmd_params* par, frbch_rmd_result* res) {
+  POST_NO_CONTRACT
+  const uint32_t nchan = fil->nchan;
+  const size_t per = (size_t)par->ntau * par->nphi;
+  const std::vector<double> l2 = rm_l2(fil);
+  std::vector<double> P(per), Psum(per, 0.0);
+  std::vector<uint8_t> any(nchan, 0);
+  uint32_t entered = 0;
+  // l2 and f spans of a channel selection, as fwhm and fwhm_tau want them
+  auto widths = [&](const uint8_t* us, frbch_rmd_result& r) {
+    uint32_t N = 0;
+    double lo = 0.0, hi = 0.0, flo = 0.0, fhi = 0.0;
+    for (uint32_t c = 0; c < nchan; ++c)
+      if (us[c]) {
+        const double f = fil->fch1_mhz + (double)c * fil->foff_mhz;
+        if (!N || l2[c] < lo) lo = l2[c];
+        if (!N || l2[c] > hi) hi = l2[c];
+        if (!N || f < flo) flo = f;
+        if (!N || f > fhi) fhi = f;
+        ++N;
+      }
+    if (hi > lo) r.fwhm = (2.0 * sqrt(3.0)) / (hi - lo);
+    if (fhi > flo) r.fwhm_tau = (2.0 * sqrt(3.0)) / (kRmPi * (fhi - flo));
+    return N;
+  };
+  for (uint32_t i = 0; i < ncand; ++i) {
+    frbch_rmd_result& r = res[i];
+    memset(&r, 0, sizeof r);
+    const float* f = F + (size_t)i * per * 2;
+    const uint8_t* us = used + (size_t)i * nchan;
+    for (size_t x = 0; x < per; ++x) {
+      const double re = (double)f[2 * x], im = (double)f[2 * x + 1];
+      const double a = re * re, b = im * im;
+      P[x] = a + b;
+    }
+    const double best = rmd_map_peak(P.data(), par, r);
+    const size_t at = (size_t)r.mpeak * par->nphi + r.kpeak;
+    r.peak = sqrt(best);
+    r.psi = atan2((double)f[2 * at + 1], (double)f[2 * at]);
+    r.nused = widths(us, r);
+    double acc = 0.0;
+    if (noise_q && noise_u)
+      for (uint32_t c = 0; c < nchan; ++c)
+        if (us[c]) {
+          const double nq = (double)noise_q[(size_t)i * nchan + c], nu = (double)noise_u[(size_t)i * nchan + c];
+          const double a = nq * nq, b = nu * nu;
+          acc = acc + (a + b);
+        }
+    if (r.nused) r.sigma_f = sqrt(acc / 2.0) / (double)r.nused;
+    if (r.sigma_f > 0.0) r.snr = sqrt(best) / r.sigma_f;
+    if (r.snr > 0.0) {
+      r.rm_err = r.fwhm / (2.0 * r.snr);
+      r.tau_err = r.fwhm_tau / (2.0 * r.snr);
+    }
+    if (r.sigma_f > 0.0 && r.nused) {
+      const double s2 = r.sigma_f * r.sigma_f;
+      for (size_t x = 0; x < per; ++x) Psum[x] = Psum[x] + P[x] / s2;
+      for (uint32_t c = 0; c < nchan; ++c)
+        if (us[c]) any[c] = 1;
+      ++entered;
+    }
+  }
+  frbch_rmd_result& r = res[ncand];
+  memset(&r, 0, sizeof r);
+  if (!entered) return FRBCH_OK;
+  const double best = rmd_map_peak(Psum.data(), par, r);
+  r.peak = r.snr = sqrt(best);
+  r.sigma_f = 1.0;
+  (void)widths(any.data(), r);
+  r.nused = entered;
+  if (r.snr > 0.0) {
+    r.rm_err = r.fwhm / (2.0 * r.snr);
+    r.tau_err = r.fwhm_tau / (2.0 * r.snr);
+  }
+  return FRBCH_OK;
+}
+
 }  // namespace
 
 extern "C" int frbch_burstspec_kernel(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* par,
@@ -4380,6 +4666,124 @@ extern "C" int frbch_burst_rm_host(const frbch_fil_desc* fil, const void* rows, 
   });
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
+// ---- polarisation calibration: the delay x RM transform ---------------------------------------------------------------
+extern "C" int frbch_rmdelay_kernel(const frbch_fil_desc* fil, const float* d_F, uint32_t ncand, const frbch_rmd_params* par,
+                                    uint32_t* nsplit) try {
+  PostErr e{nullptr, 0};
+  const int rc = rmd_check(fil, ncand, par, e);
+  if (rc) return rc;
+  if (!d_F) return FRBCH_E_ARG;
+  const RmdPlanRule rule = rmd_plan_rule(fil->nchan, ncand, par->nphi, par->ntau, d_F);
+  if (nsplit) *nsplit = (uint32_t)rule.nsplit;
+  return rule.fastk ? 1 : 0;
+} catch (const std::bad_alloc&) { return FRBCH_E_NOMEM; }
+
+extern "C" int frbch_rmdelay_device(const frbch_fil_desc* fil, const float* d_q, const float* d_u, const uint8_t* d_used,
+                                    uint32_t ncand, const frbch_rmd_params* par, int device, float* d_F, uint32_t* kernel_used,
+                                    char* err, size_t err_cap) try {
+  static_assert(sizeof(RmdRec) == 32 && sizeof(frbch_rmd_params) == 48 && sizeof(frbch_rmd_result) == 112, "delay x RM records");
+  PostErr e{err, err_cap};
+  int rc = rmd_check(fil, ncand, par, e);
+  if (rc) return rc;
+  if (!d_q || !d_u || !d_used || !d_F) return e.fail(FRBCH_E_ARG, "null argument");
+  const size_t n = (size_t)ncand * fil->nchan;
+  std::vector<float> q(n), u(n);
+  std::vector<uint8_t> used(n);
+  RmdPlan plan;
+  return burst_device_call(device, e, [&](PostScope& ps) {
+    int rc;
+    POST_DEV(dev_d2h(q.data(), d_q, n * sizeof(float), ps.s), "download q");
+    POST_DEV(dev_d2h(u.data(), d_u, n * sizeof(float), ps.s), "download u");
+    POST_DEV(dev_d2h(used.data(), d_used, n, ps.s), "download used");
+    POST_DEV(dev_sync(ps.s), "sync");
+    if ((rc = rmd_build(fil, q.data(), u.data(), used.data(), ncand, par, &plan, e)) != 0) return rc;
+    if ((rc = rmd_launch(fil, ncand, par, plan, d_F, ps, kernel_used, e)) != 0) return rc;
+    POST_DEV(dev_sync(ps.s), "sync");       // (the host vectors the uploads read stay alive until here)
+    return (int)FRBCH_OK;
+  });
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_rmdelay_host(const frbch_fil_desc* fil, const float* q, const float* u, const uint8_t* used, uint32_t ncand,
+                                  const frbch_rmd_params* par, int device, float* F, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  int rc = rmd_check(fil, ncand, par, e);
+  if (rc) return rc;
+  if (!q || !u || !used || !F) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  const size_t n = (size_t)ncand * fil->nchan;
+  HostStage hs;
+  const float* d_q = hs.in(q, n * sizeof(float));
+  const float* d_u = hs.in(u, n * sizeof(float));
+  const uint8_t* d_used = hs.in(used, n);
+  float* d_F = hs.out(F, (size_t)ncand * par->ntau * par->nphi * 2 * sizeof(float));
+  return hs.run(e, "device memory for the spectra and F", "upload spectra", "download F",
+                [&]() { return frbch_rmdelay_device(fil, d_q, d_u, d_used, ncand, par, device, d_F, kernel_used, err, err_cap); });
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_rmdelay_peaks(const frbch_fil_desc* fil, const float* F, const uint8_t* used, const float* noise_q, const float* noise_u,
+                                   uint32_t ncand, const frbch_rmd_params* par, frbch_rmd_result* results, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  const int rc = rmd_check(fil, ncand, par, e);
+  if (rc) return rc;
+  if (!F || !used || !results) return e.fail(FRBCH_E_ARG, "null argument");
+  return rmd_peaks_run(fil, F, used, noise_q, noise_u, ncand, par, results);
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_burst_polcal_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                         const frbch_burst_cand* cands, uint32_t ncand, const float* gain, const uint8_t* flag,
+                                         const frbch_rmd_params* par, int device, float* spec, float* noise, uint8_t* used, float* F,
+                                         frbch_rmd_result* results, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  int rc = burst_check(fil, nrows, bpar, cands, ncand, e);
+  if (rc) return rc;
+  if (fil->nifs != 4) return e.fail(FRBCH_E_ARG, "the composite needs the four products of a full-Stokes file (nifs = 4)");
+  if ((rc = rmd_check(fil, ncand, par, e)) != 0) return rc;
+  if (!d_rows || !spec || !noise || !used || !F || !results) return e.fail(FRBCH_E_ARG, "null argument");
+  const size_t nchan = fil->nchan, n = (size_t)ncand * nchan, nF = (size_t)ncand * par->ntau * par->nphi * 2;
+  std::vector<frbch_burst_sums> sums;
+  std::vector<float> q(n), u(n), nq(n), nu(n);
+  RmdPlan plan;
+  uint32_t k[3] = {0, 0, 1};
+  rc = burst_device_call(device, e, [&](PostScope& ps) {
+    int rc;
+    BurstSums* d_sums = nullptr;
+    float* d_F = nullptr;
+    POST_DEV(ps.alloc(&d_sums, n * 4 * sizeof(BurstSums)), "hipMalloc");
+    POST_DEV(ps.alloc(&d_F, nF * sizeof(float)), "hipMalloc");
+    if ((rc = burst_run(fil, d_rows, nrows, bpar, cands, ncand, gain, d_sums, ps, &sums, spec, noise, used, &k[0], e)) != 0) return rc;
+    for (uint32_t i = 0; i < ncand; ++i)
+      for (size_t c = 0; c < nchan; ++c) {
+        if (flag && flag[c]) used[i * nchan + c] = 0;
+        q[i * nchan + c] = spec[((size_t)i * 4 + 1) * nchan + c];
+        u[i * nchan + c] = spec[((size_t)i * 4 + 2) * nchan + c];
+        nq[i * nchan + c] = noise[((size_t)i * 4 + 1) * nchan + c];
+        nu[i * nchan + c] = noise[((size_t)i * 4 + 2) * nchan + c];
+      }
+    if ((rc = rmd_build(fil, q.data(), u.data(), used, ncand, par, &plan, e)) != 0) return rc;
+    if ((rc = rmd_launch(fil, ncand, par, plan, d_F, ps, &k[1], e)) != 0) return rc;
+    POST_DEV(dev_d2h(F, d_F, nF * sizeof(float), ps.s), "download F");
+    POST_DEV(dev_sync(ps.s), "sync");
+    return (int)FRBCH_OK;
+  });
+  if (rc) return rc;
+  deliver(kernel_used, k);
+  return rmd_peaks_run(fil, F, used, nq.data(), nu.data(), ncand, par, results);
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_burst_polcal_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                       const frbch_burst_cand* cands, uint32_t ncand, const float* gain, const uint8_t* flag,
+                                       const frbch_rmd_params* par, int device, float* spec, float* noise, uint8_t* used, float* F,
+                                       frbch_rmd_result* results, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  const int rc = burst_check(fil, nrows, bpar, cands, ncand, e);
+  if (rc) return rc;
+  if (!rows) return e.fail(FRBCH_E_ARG, "null argument");
+  return burst_host_twin(fil, rows, nrows, device, e, [&](void* d_rows) {
+    return frbch_burst_polcal_device(fil, d_rows, nrows, bpar, cands, ncand, gain, flag, par, device, spec, noise, used, F, results, kernel_used, err, err_cap);
+  });
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
 // ---------------------------------------------------------------------------------------------------------------------
 // polarisation profile of a burst: derotated I, L, V and PA per time bin (include/frbch.h states the arithmetic)
 // ---------------------------------------------------------------------------------------------------------------------
@@ -4406,6 +4810,12 @@ int pol_check_rm(const double* rm, uint32_t ncand, const PostErr& e) {
   if (!rm) return e.fail(FRBCH_E_ARG, "null argument");
   for (uint32_t i = 0; i < ncand; ++i)
     if (!(fabs(rm[i]) <= kRmPhiMax)) return e.fail(FRBCH_E_ARG, "candidate " + std::to_string(i) + ": an rm that is not finite or above 1e7 rad m^-2 in size");
+  return FRBCH_OK;
+}
+
+int pol_check_tau(const double* tau, uint32_t ncand, const PostErr& e) {
+  for (uint32_t i = 0; tau && i < ncand; ++i)
+    if (!(fabs(tau[i]) <= kRmdTauLim)) return e.fail(FRBCH_E_ARG, "candidate " + std::to_string(i) + ": a tau that is not finite or above 100 microseconds in size");
   return FRBCH_OK;
 }
 
@@ -4444,8 +4854,8 @@ long long pol_floordiv(long long a, long long b) { return a >= 0 ? a / b : -((-a
 
 // everything of a call inside its scope: the burst sums, the records, the launches, the derivation (all synchronised)
 int pol_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
-            const frbch_burst_cand* cands, uint32_t ncand, const double* rm, const float* gain, const uint8_t* flag,
-            const frbch_prof_params* par, PostScope& ps, PolOut* out, const PostErr& e) {
+            const frbch_burst_cand* cands, uint32_t ncand, const double* rm, const double* tau, const float* gain,
+            const uint8_t* flag, const frbch_prof_params* par, PostScope& ps, PolOut* out, const PostErr& e) {
   POST_NO_CONTRACT
   const size_t nchan = fil->nchan, n = (size_t)ncand * nchan, nbin = par->nbin;
   BurstPlan bplan;
@@ -4488,16 +4898,18 @@ int pol_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const
     r.on_lo_bin = (uint32_t)std::min(last, std::max(0ll, pol_floordiv(on_lo - t0, (long long)par->tfactor)));
     r.on_hi_bin = (uint32_t)std::min(last, std::max(0ll, pol_floordiv(on_lo + (long long)cands[i].width - 1 - t0, (long long)par->tfactor)));
     uint32_t N = 0;
-    double sum = 0.0, gmax = 0.0;
+    double sum = 0.0, fsum = 0.0, gmax = 0.0;
     for (size_t c = 0; c < nchan; ++c)
       if (us[c]) {
         ++N;
         sum = sum + l2[c];
+        fsum = fsum + (fil->fch1_mhz + (double)c * fil->foff_mhz);
         for (size_t p = 0; p < 4; ++p) gmax = std::max(gmax, gain ? fabs((double)gain[p * nchan + c]) : 1.0);
       }
     r.nused = N;
     if (N == 0 || gmax == 0.0) continue;                       // every output 0: no used record
     const double lref = par->ref == FRBCH_PROF_REF_MEAN ? sum / (double)N : 0.0;
+    const double f0 = fsum / (double)N;                        // (of the delay term: the polarisation calibration section)
     const double M = (tf * ldexp(1.0, fil->nbits)) * gmax;
     int ex = 0;
     (void)frexp(M, &ex);
@@ -4525,7 +4937,11 @@ int pol_run(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const
         for (int p = 0; p < 4; ++p) W[p] = W[p] + w[p];
       }
       const double a = (l2[c] - lref) / kRmPi;
-      const uint64_t ph = rm_fix(rm[i] * a);
+      uint64_t ph = rm_fix(rm[i] * a);
+      if (tau) {
+        const double b = (fil->fch1_mhz + (double)c * fil->foff_mhz) - f0;
+        ph += rm_fix(tau[i] * b);
+      }
       const int j = (int)(((ph + (1ull << 49)) >> 50) & 16383ull);
       q.cc = table[j];
       q.sc = table[(j - 4096) & 16383];
@@ -4629,9 +5045,9 @@ extern "C" int frbch_polprof_kernel(const frbch_fil_desc* fil, const void* d_row
   return pol_plan_rule(fil, d_rows, plan.delays, ncand, par).fastk ? 1 : 0;
 } catch (const std::bad_alloc&) { return FRBCH_E_NOMEM; }
 
-extern "C" int frbch_polprof_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
-                                    const frbch_burst_cand* cands, uint32_t ncand, const double* rm, const float* gain,
-                                    const uint8_t* flag, const frbch_prof_params* par, int device, int64_t* acc, uint32_t* hits,
+extern "C" int frbch_polprof_cal_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                        const frbch_burst_cand* cands, uint32_t ncand, const double* rm, const double* tau, const float* gain,
+                                        const uint8_t* flag, const frbch_prof_params* par, int device, int64_t* acc, uint32_t* hits,
                                     frbch_prof_bin* bins, frbch_prof_result* results, uint8_t* used, uint32_t* kernel_used,
                                     char* err, size_t err_cap) try {
   static_assert(sizeof(PolRec) == 80 && sizeof(frbch_prof_bin) == 72 && sizeof(frbch_prof_result) == 64 && sizeof(long long) == sizeof(int64_t), "profile records");
@@ -4640,8 +5056,9 @@ extern "C" int frbch_polprof_device(const frbch_fil_desc* fil, const void* d_row
   if (rc) return rc;
   if (!d_rows) return e.fail(FRBCH_E_ARG, "null argument");
   if ((rc = pol_check_rm(rm, ncand, e)) != 0) return rc;
+  if ((rc = pol_check_tau(tau, ncand, e)) != 0) return rc;
   PolOut out;
-  rc = burst_device_call(device, e, [&](PostScope& ps) { return pol_run(fil, d_rows, nrows, bpar, cands, ncand, rm, gain, flag, par, ps, &out, e); });
+  rc = burst_device_call(device, e, [&](PostScope& ps) { return pol_run(fil, d_rows, nrows, bpar, cands, ncand, rm, tau, gain, flag, par, ps, &out, e); });
   if (rc) return rc;
   deliver(acc, out.acc);
   deliver(hits, out.hits);
@@ -4652,9 +5069,9 @@ extern "C" int frbch_polprof_device(const frbch_fil_desc* fil, const void* d_row
   return FRBCH_OK;
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
-extern "C" int frbch_polprof_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* bpar,
-                                  const frbch_burst_cand* cands, uint32_t ncand, const double* rm, const float* gain,
-                                  const uint8_t* flag, const frbch_prof_params* par, int device, int64_t* acc, uint32_t* hits,
+extern "C" int frbch_polprof_cal_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                      const frbch_burst_cand* cands, uint32_t ncand, const double* rm, const double* tau, const float* gain,
+                                      const uint8_t* flag, const frbch_prof_params* par, int device, int64_t* acc, uint32_t* hits,
                                   frbch_prof_bin* bins, frbch_prof_result* results, uint8_t* used, uint32_t* kernel_used,
                                   char* err, size_t err_cap) try {
   PostErr e{err, err_cap};
@@ -4662,10 +5079,28 @@ extern "C" int frbch_polprof_host(const frbch_fil_desc* fil, const void* rows, u
   if (rc) return rc;
   if (!rows) return e.fail(FRBCH_E_ARG, "null argument");
   if ((rc = pol_check_rm(rm, ncand, e)) != 0) return rc;
+  if ((rc = pol_check_tau(tau, ncand, e)) != 0) return rc;
   return burst_host_twin(fil, rows, nrows, device, e, [&](void* d_rows) {
-    return frbch_polprof_device(fil, d_rows, nrows, bpar, cands, ncand, rm, gain, flag, par, device, acc, hits, bins, results, used, kernel_used, err, err_cap);
+    return frbch_polprof_cal_device(fil, d_rows, nrows, bpar, cands, ncand, rm, tau, gain, flag, par, device, acc, hits, bins, results, used, kernel_used, err, err_cap);
   });
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+// the calls without a delay: tau = NULL
+extern "C" int frbch_polprof_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                    const frbch_burst_cand* cands, uint32_t ncand, const double* rm, const float* gain,
+                                    const uint8_t* flag, const frbch_prof_params* par, int device, int64_t* acc, uint32_t* hits,
+                                    frbch_prof_bin* bins, frbch_prof_result* results, uint8_t* used, uint32_t* kernel_used,
+                                    char* err, size_t err_cap) {
+  return frbch_polprof_cal_device(fil, d_rows, nrows, bpar, cands, ncand, rm, nullptr, gain, flag, par, device, acc, hits, bins, results, used, kernel_used, err, err_cap);
+}
+
+extern "C" int frbch_polprof_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                  const frbch_burst_cand* cands, uint32_t ncand, const double* rm, const float* gain,
+                                  const uint8_t* flag, const frbch_prof_params* par, int device, int64_t* acc, uint32_t* hits,
+                                  frbch_prof_bin* bins, frbch_prof_result* results, uint8_t* used, uint32_t* kernel_used,
+                                  char* err, size_t err_cap) {
+  return frbch_polprof_cal_host(fil, rows, nrows, bpar, cands, ncand, rm, nullptr, gain, flag, par, device, acc, hits, bins, results, used, kernel_used, err, err_cap);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // DM of a burst: fine DM scan, S/N and structure maxima (include/frbch.h states the arithmetic)

@@ -1247,6 +1247,38 @@ KERNEL(frbch_post_rm, RmParams) {
   }
 }
 
+// The delay x RM transform (frbch_rmdelay_*): a second axis on the transform above, ph = p0 + k d + m e with the first tau
+// trial's phase folded into p0.  Every term goes through rm_term, so this kernel and the fast one differ in schedule only.
+struct RmdRec { int32_t qi, ui; unsigned long long p0, d, e; };   // one used channel of a candidate: 32 bytes
+struct RmdParams {
+  const RmdRec* rec;           // [ncand][nchan], packed as RmParams::rec
+  const RmCand* cand;          // [ncand]
+  const int32_t* table;        // C[16384]
+  float* out;                  // [ncand][ntau][nphi][2]
+  long long* part;             // fast kernel with nsplit > 1: [nsplit][ncand][ntau][nphi][2]
+  int nchan, nphi, ntau, ncand, nsplit, chunk;
+};
+
+// grid (ceil(ntau nphi / 256), ncand), one thread per (candidate, tau trial, phi trial), channels ascending
+KERNEL(frbch_post_rmd, RmdParams) {
+  K_PROLOGUE;
+  (void)smem;
+  PHASE {
+    const long long idx = (long long)bx * nthr + tid;
+    if (idx < (long long)p.ntau * p.nphi) {
+      const unsigned long long m = (unsigned long long)(idx / p.nphi), k = (unsigned long long)(idx % p.nphi);
+      const RmCand cd = p.cand[by];
+      const RmdRec* rec = p.rec + (size_t)by * p.nchan;
+      long long re = 0, im = 0;
+      for (uint32_t r = 0; r < cd.nrec; ++r) {
+        const RmdRec rc = rec[r];
+        rm_term(p.table, rc.p0 + rc.d * k + rc.e * m, rc.qi, rc.ui, &re, &im);
+      }
+      rm_store(p.out + ((size_t)by * p.ntau * p.nphi + (size_t)idx) * 2, re, im, cd.inv);
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Polarisation profile of a burst (frbch_polprof_*; include/frbch.h states the arithmetic): per (candidate, time bin) the
 // band sum of I, V and of (Q, U) rotated back by the RM, in int64.  Every channel's part of a bin goes through pp_term in

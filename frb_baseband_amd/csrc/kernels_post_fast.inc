@@ -1199,6 +1199,93 @@ __global__ void __launch_bounds__(kRmThreads) frbch_post_rm_join(RmParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// The delay x RM transform (HIP only; frbch_post_rmd of kernels_post.inc stays the emulable form and the fallback; both call
+// rm_term).  frbch_post_rm_fast with a second axis in registers: a thread carries T consecutive tau trials next to its
+// kRmKpt phi trials, so that one staged record and one first-phase product (p0 + k0 d + m0 e) serve kRmKpt x T terms, each
+// further one at one 64-bit addition.  The accumulators are 4 kRmKpt T VGPRs, 128 at T = 8; the compiler's counts are 59,
+// 56, 90 and 169 VGPRs at T = 1, 2, 4 and 8, none spilled (profiles/polcal_resusage.txt).  The 72 KiB of LDS admit two
+// workgroups a CU, that is two waves a SIMD with 256 VGPRs each, so T = 8 costs no occupancy that the LDS had not taken
+// already; at T = 16 the accumulators alone would be those 256.  T is the host's choice
+// (rmd_plan_rule): a tail tile computes its trials beyond ntau in vain, so short or ragged tau axes take a smaller T.
+// blockIdx.y = tau tile x nsplit + split, grid (ceil(nphi / 1024), ceil(ntau / T) nsplit, ncand).
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int kRmdTile = 256, kRmdTauMax = 8;
+constexpr size_t kRmdLds = 65536 + (size_t)kRmdTile * sizeof(RmdRec);
+
+template <int T>
+__global__ void __launch_bounds__(kRmThreads) frbch_post_rmd_fast(RmdParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  int32_t* tab = reinterpret_cast<int32_t*>(smem);
+  RmdRec* recs = reinterpret_cast<RmdRec*>(smem + 65536);
+  const int tid = threadIdx.x, cand = blockIdx.z;
+  const int split = (int)blockIdx.y % p.nsplit, m0 = ((int)blockIdx.y / p.nsplit) * T;
+  const int k0 = (int)blockIdx.x * (kRmThreads * kRmKpt) + tid;
+  for (int i = tid; i < 4096; i += kRmThreads) reinterpret_cast<int4*>(tab)[i] = reinterpret_cast<const int4*>(p.table)[i];
+  const RmCand cd = p.cand[cand];
+  const int r0 = split * p.chunk;
+  const int r1 = min(r0 + p.chunk, (int)cd.nrec);
+  long long re[kRmKpt][T], im[kRmKpt][T];
+#pragma unroll
+  for (int j = 0; j < kRmKpt; ++j)
+#pragma unroll
+    for (int m = 0; m < T; ++m) re[j][m] = im[j][m] = 0;
+  for (int t0 = r0; t0 < r1; t0 += kRmdTile) {
+    const int n = min(kRmdTile, r1 - t0);
+    __syncthreads();                                                       // the previous tile is consumed
+    const uint32_t* srcw = reinterpret_cast<const uint32_t*>(p.rec + (size_t)cand * p.nchan + t0);
+    for (int i = tid; i < n * 8; i += kRmThreads) reinterpret_cast<uint32_t*>(recs)[i] = srcw[i];
+    __syncthreads();                                                       // (the first one covers the table as well)
+    for (int r = 0; r < n; ++r) {
+      const RmdRec rc = recs[r];
+      unsigned long long ph = rc.p0 + rc.d * (unsigned long long)(uint32_t)k0 + rc.e * (unsigned long long)(uint32_t)m0;
+      const unsigned long long step = rc.d << 8;                           // kRmThreads D
+#pragma unroll
+      for (int j = 0; j < kRmKpt; ++j) {
+        unsigned long long pm = ph;
+#pragma unroll
+        for (int m = 0; m < T; ++m) {
+          rm_term(tab, pm, rc.qi, rc.ui, &re[j][m], &im[j][m]);
+          pm += rc.e;
+        }
+        ph += step;
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < kRmKpt; ++j) {
+    const int k = k0 + j * kRmThreads;
+#pragma unroll
+    for (int m = 0; m < T; ++m) {
+      if (k < p.nphi && m0 + m < p.ntau) {
+        const size_t o = ((size_t)cand * p.ntau + (size_t)(m0 + m)) * p.nphi + k;
+        if (p.nsplit == 1) {
+          rm_store2(p.out + o * 2, re[j][m], im[j][m], cd.inv);
+        } else {
+          long long* q = p.part + ((size_t)split * p.ncand * p.ntau * p.nphi + o) * 2;
+          q[0] = re[j][m];
+          q[1] = im[j][m];
+        }
+      }
+    }
+  }
+}
+
+// grid (ceil(ntau nphi / 256), ncand): the partials of the splits, added in ascending split
+__global__ void __launch_bounds__(kRmThreads) frbch_post_rmd_join(RmdParams p) {
+  const size_t per = (size_t)p.ntau * p.nphi, idx = (size_t)blockIdx.x * kRmThreads + threadIdx.x;
+  const int cand = blockIdx.y;
+  if (idx >= per) return;
+  const size_t o = (size_t)cand * per + idx;
+  long long re = 0, im = 0;
+  for (int s = 0; s < p.nsplit; ++s) {
+    const long long* q = p.part + ((size_t)s * p.ncand * per + o) * 2;
+    re += q[0];
+    im += q[1];
+  }
+  rm_store2(p.out + o * 2, re, im, p.cand[cand].inv);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Polarisation profile (HIP only; frbch_post_polprof of kernels_post.inc stays the emulable form and the fallback; both call
 // pp_term).  A workgroup of 256 threads owns one candidate, one 64-byte tile of the row (CT = 64 / 32 channels of 8- / 16-bit
 // samples) and a run of `brun` bins.  It stages the rows the run needs -- from its first bin's first row at the tile's

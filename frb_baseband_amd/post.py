@@ -31,6 +31,10 @@ reference's `dspsr -E <par> ... <IFall.fil>` stage) of SIGPROC filterbank files,
   L/I and V/I (``rm_peaks``), or all of it on rows uploaded once (``burst_rm``: frbch_burst_rm_host).
 * ``polprof_fil`` (``post polprof``, ``post rmsynth --profile``) draws the burst against time at that RM: I, debiased L, V and the
   position angle per time bin, (Q, U) of every channel rotated back and summed over the band (``pol_profile``: frbch_polprof_host).
+* ``polcal_fil`` (``post polcal``) measures what both need first with dual circular feeds, the delay between the R and L paths,
+  on the pulses of a calibrator of known RM: RM synthesis at a grid of trial delays (``rm_delay``: frbch_rmdelay_host), the peak
+  of the (delay, RM) plane with the slope of its ridge and one combined estimate (``rm_delay_peaks``), or all of it on rows
+  uploaded once (``polcal``: frbch_burst_polcal_host); ``post rmsynth`` and ``post polprof`` take the result with ``--polcal``.
 * ``dmfit_fil`` (``post dmfit``) measures the DM those stages take as given: the burst's noise-weighted profile at a fine grid of
   trial DMs, the S/N- and the structure-maximising DM by a parabola over each curve's peak (``dm_scan``: frbch_dmscan_host);
   ``post rmsynth`` and ``post polprof`` take the result with ``--dm-from``.
@@ -2097,6 +2101,200 @@ def burst_rm(fil_or_rows, hdr: dict, cands, nphi: int, phi_lo: float, dphi: floa
     return dict(spec=spec, noise=noise, used=used, F=F.view(np.complex64)[..., 0], results=res)
 
 
+# ---- polarisation calibration: the delay x RM transform (frbch_rmdelay_*, frbch_burst_polcal_*) ------------------
+RMD_RESULT = np.dtype([("tau", "<f8"), ("tau_err", "<f8"), ("rm", "<f8"), ("rm_err", "<f8"), ("peak", "<f8"), ("psi", "<f8"),
+                       ("snr", "<f8"), ("sigma_f", "<f8"), ("fwhm", "<f8"), ("fwhm_tau", "<f8"), ("ridge_slope", "<f8"),
+                       ("mpeak", "<u4"), ("kpeak", "<u4"), ("nused", "<u4"), ("fitted_tau", "<u4"), ("fitted_rm", "<u4"),
+                       ("nridge", "<u4")])
+POLCAL_DTAU_ONE = 1.0e-3      # dtau of a one-trial tau axis (it must be positive; no trial uses it), microseconds
+POLCAL_ROW = "%-9s tau %+9.4f +- %.4f ns  RM %+10.3f +- %.3f rad/m2  psi %+8.2f deg  ridge %+8.3f rad/m2/ns (%d rows)  S/N %.1f"
+
+
+def rmd_params(nphi: int, phi_lo: float, dphi: float, ntau: int, tau_lo: float, dtau: float) -> _lib.FrbchRmdParams:
+    """the grid of the delay x RM transform: phi in rad m^-2, tau in MICROSECONDS"""
+    return _lib.FrbchRmdParams(C.sizeof(_lib.FrbchRmdParams), int(nphi), int(ntau), 0, float(phi_lo), float(dphi), float(tau_lo), float(dtau))
+
+
+def rm_delay(q, u, used, hdr: dict, nphi: int, phi_lo: float, dphi: float, ntau: int, tau_lo: float, dtau: float, device: int = 0,
+             lib=None, info: dict | None = None):
+    """F(tau, phi) of ``q``, ``u`` [n][nchans]: RM synthesis at ``ntau`` trial delays tau_m = tau_lo + m dtau (microseconds)
+    between the two circular feeds, each taken out as a phase ramp across the band before the transform (frbch_rmdelay_host;
+    include/frbch.h states the arithmetic) -> complex64 ``F [n][ntau][nphi]``.  ``ntau = 1, tau_lo = 0`` is ``rm_synthesis``
+    to the bit.  ``info['kernel_used']``: 1 = the fast kernel, 0 = the generic one; ``info['split']``: the channel split."""
+    lib = lib or _lib.load()
+    nchan = hdr["nchans"]
+    q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, nchan)
+    u = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, nchan)
+    used = np.ascontiguousarray(used, dtype=np.uint8).reshape(-1, nchan)
+    if not q.shape == u.shape == used.shape:
+        raise InputError("q, u and used must have the same shape [n][nchans]")
+    par = rmd_params(nphi, phi_lo, dphi, ntau, tau_lo, dtau)
+    nt, nk = max(1, min(int(ntau), 4096)), max(1, min(int(nphi), 1 << 20))
+    if q.shape[0] * nt * nk > 1 << 26:
+        raise InputError("ncand * ntau * nphi exceeds 2^26: cut the batch or the grid")
+    F = np.zeros((q.shape[0], nt, nk, 2), np.float32)
+    k = (C.c_uint32 * 2)(0, 1)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_rmdelay_host(C.byref(fil_desc(hdr)), q.ctypes.data, u.ctypes.data, used.ctypes.data, q.shape[0], C.byref(par),
+                                  device, F.ctypes.data, k, err, len(err)), err)
+    if info is not None:
+        info.update(kernel_used=k[0], split=k[1])
+    return F.view(np.complex64)[..., 0]
+
+
+def rm_delay_peaks(F, used, noise_q, noise_u, hdr: dict, nphi: int, phi_lo: float, dphi: float, ntau: int, tau_lo: float, dtau: float,
+                   lib=None) -> np.ndarray:
+    """RMD_RESULT records [n + 1] from F [n][ntau][nphi] (frbch_rmdelay_peaks): per pulse the first largest trial of the plane,
+    a parabola along each axis, psi, the noise and the slope of the ridge; the last record is the combined estimate of all
+    pulses (their planes added with weights 1 / sigma_f^2)"""
+    lib = lib or _lib.load()
+    nchan = hdr["nchans"]
+    Ff = np.ascontiguousarray(np.asarray(F, dtype=np.complex64).reshape(-1, int(ntau), int(nphi))).view(np.float32)
+    used = np.ascontiguousarray(used, dtype=np.uint8).reshape(-1, nchan)
+    nq = None if noise_q is None else np.ascontiguousarray(noise_q, dtype=np.float32).reshape(-1, nchan)
+    nu = None if noise_u is None else np.ascontiguousarray(noise_u, dtype=np.float32).reshape(-1, nchan)
+    res = np.zeros(used.shape[0] + 1, dtype=RMD_RESULT)
+    par = rmd_params(nphi, phi_lo, dphi, ntau, tau_lo, dtau)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_rmdelay_peaks(C.byref(fil_desc(hdr)), Ff.ctypes.data, used.ctypes.data, nq.ctypes.data if nq is not None else None,
+                                   nu.ctypes.data if nu is not None else None, used.shape[0], C.byref(par), res.ctypes.data, err, len(err)), err)
+    return res
+
+
+def polcal(fil_or_rows, hdr: dict, cands, nphi: int, phi_lo: float, dphi: float, ntau: int, tau_lo: float, dtau: float, gains=None,
+           flag=None, products: str = "stokes", device: int = 0, lib=None, info: dict | None = None):
+    """Rows -> spectra -> the delay x RM transform of Q and U -> peaks and the combined record, in one library call on rows
+    uploaded once (frbch_burst_polcal_host) -> dict(spec, noise, used, F [n][ntau][nphi], results RMD_RESULT [n + 1])."""
+    lib = lib or _lib.load()
+    rows, nrows, cands, par, g = _burst_args(fil_or_rows, hdr, cands, gains, products)
+    n, nchan = cands.size, hdr["nchans"]
+    nt, nk = max(1, min(int(ntau), 4096)), max(1, min(int(nphi), 1 << 20))
+    if n * nt * nk > 1 << 26:
+        raise InputError("ncand * ntau * nphi exceeds 2^26: cut the batch or the grid")
+    spec, noise = np.zeros((n, 4, nchan), np.float32), np.zeros((n, 4, nchan), np.float32)
+    used = np.zeros((n, nchan), np.uint8)
+    F = np.zeros((n, nt, nk, 2), np.float32)
+    res = np.zeros(n + 1, dtype=RMD_RESULT)
+    fl = _flag_arg(flag, nchan)
+    rpar = rmd_params(nphi, phi_lo, dphi, ntau, tau_lo, dtau)
+    k = (C.c_uint32 * 3)(0, 0, 1)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_burst_polcal_host(C.byref(fil_desc(hdr, hdr.get("product", 0))), rows.ctypes.data, nrows, C.byref(par), cands.ctypes.data, n,
+                                       g.ctypes.data if g is not None else None, fl.ctypes.data if fl is not None else None, C.byref(rpar),
+                                       device, spec.ctypes.data, noise.ctypes.data, used.ctypes.data, F.ctypes.data, res.ctypes.data, k,
+                                       err, len(err)), err)
+    if info is not None:
+        info.update(spectra_kernel_used=k[0], kernel_used=k[1], split=k[2])
+    return dict(spec=spec, noise=noise, used=used, F=F.view(np.complex64)[..., 0], results=res)
+
+
+def polcal_tau(polcal_file) -> float:
+    """the delay (microseconds) of a ``<base>_polcal.npz`` that ``polcal_fil`` wrote: the combined estimate of its pulses"""
+    try:
+        return float(np.load(polcal_file)["tau_us"])
+    except (OSError, KeyError, ValueError) as ex:
+        raise InputError("%s: not a _polcal.npz of `post polcal` (%s)" % (polcal_file, ex))
+
+
+def tau_grid(hdr: dict, used=None, tau_half_ns: float = 0.0, dtau_ns: float = 0.0):
+    """The default grid of delays -> (ntau, tau_lo, dtau) in microseconds: dtau = fwhm_tau / 8 with fwhm_tau = 2 sqrt(3) / (pi x
+    the span of the used channels' frequencies), tau_half = 8 fwhm_tau either side of 0, which is one of its trials; at most
+    4096 trials"""
+    f = hdr["fch1"] + np.arange(hdr["nchans"], dtype=np.float64) * hdr["foff"]
+    sel = f if used is None else f[np.asarray(used).reshape(-1, hdr["nchans"]).any(axis=0)]
+    if sel.size < 2:
+        raise InputError("the delay search needs at least two used channels")
+    fwhm = 2.0 * np.sqrt(3.0) / (np.pi * float(sel.max() - sel.min()))
+    dtau = dtau_ns * 1e-3 if dtau_ns > 0.0 else fwhm / 8.0
+    half_us = tau_half_ns * 1e-3 if tau_half_ns > 0.0 else 8.0 * fwhm
+    half = max(1, min(int(round(half_us / dtau)), 2047))
+    return 2 * half + 1, -half * dtau, float(dtau)
+
+
+def _polcal_png(path, P, results_i):
+    """|F|^2 of the (tau, RM) plane, tau bottom to top against the RM trials about the peak, with the ridge's trials marked"""
+    width, height = 512, 192
+    nt, nk = P.shape
+    span = max(8, min(nk, 4 * nt))
+    k0 = min(max(0, int(results_i["kpeak"]) - span // 2), max(0, nk - span))
+    win = P[:, k0:k0 + span]
+    rows = np.clip((np.arange(height) * nt) // height, 0, nt - 1)[::-1]
+    cols = np.clip((np.arange(width) * win.shape[1]) // width, 0, win.shape[1] - 1)
+    img = win[rows][:, cols]
+    img = img / max(1e-30, float(img.max()))
+    ridge = np.argmax(win, axis=1)
+    for y, m in enumerate(rows):
+        if win[m, ridge[m]] >= 0.5 * float(win.max()):
+            img[y, min(width - 1, int((ridge[m] + 0.5) * width / win.shape[1]))] = 1.0
+    write_png(path, img)
+
+
+def polcal_fil(filterbankfile, bursts=None, dm1=None, dm2=0.0, dmstep=1.0, width=0, off_gap=None, off_len=None, rm_known=None,
+               rm_lo=None, rm_hi=None, rm_step=None, tau_half=0.0, dtau=0.0, flag_file=None, gains=None, products="stokes", threshold=8.0,
+               max_cands=8, device=0, lib=None, info: dict | None = None):
+    """The delay between the two circular feeds from the pulses of a calibrator of known RM in a full-Stokes filterbank.
+    ``bursts`` or a DM range as ``rmsynth_fil`` takes them; ``rm_known`` (one RM trial) or ``rm_lo .. rm_hi`` in steps of
+    ``rm_step`` (the ionosphere moves an RM by a few units); ``tau_half`` and ``dtau`` in NANOSECONDS (defaults: ``tau_grid``).
+    Writes ``<base>_polcal.npz`` (spec, noise, used, phi, tau [microseconds], F, results [the pulses, then the combined
+    record], bursts, tau_us = the combined delay, tau_ns, tau_err_ns, rm), ``<base>_polcal.txt`` (one line per pulse and one for
+    the combined record: tau +- err in ns, RM, psi, the ridge slope in rad m^-2 per ns) and ``<base>_polcal.png`` (the summed
+    plane with its ridge).  Returns (files, RMD_RESULT records)."""
+    lib = lib or _lib.load()
+    fil = sigproc.read_fil(filterbankfile)
+    hdr = fil.header
+    if hdr.get("nifs", 1) != 4:
+        raise InputError("polcal needs a four-product file (pol_mode 4 or 5)")
+    if rm_known is None and (rm_lo is None or rm_hi is None or rm_step is None):
+        raise InputError("give --rm-known R, or --rm-lo A --rm-hi B --rm-step S")
+    if rm_known is not None:
+        n_phi, phi_lo, d_phi = 1, float(rm_known), 1.0
+    else:
+        if not (rm_step > 0.0 and rm_hi >= rm_lo):
+            raise InputError("--rm-step must be positive and --rm-hi not below --rm-lo")
+        n_phi, phi_lo, d_phi = int(np.floor((rm_hi - rm_lo) / rm_step + 1e-9)) + 1, float(rm_lo), float(rm_step)
+    if not bursts:
+        if dm1 is None:
+            raise InputError("give bursts (--dm --sample/--time --width) or a DM range to search")
+        dms = dm_list(dm1, dm2, dmstep)
+        _files, recs = _search(fil, filterbankfile, dm1, dm2, dmstep, True, 5, threshold, 0.0, 1000, False, None, device, lib, {})
+        groups = group_candidates(recs, hdr, dms, lib=lib)
+        groups = groups[np.argsort(-groups["best"]["sigma"], kind="stable")[:max_cands]]
+        bursts = [(dms[int(g["best"]["dm_index"])], int(g["best"]["sample"]), max(int(width), int(g["best"]["width"]))) for g in groups]
+        if not bursts:
+            raise InputError("the search found no burst above the threshold")
+    cands = burst_cands(bursts, off_gap, off_len)
+    flag = read_flag_file(flag_file, hdr["nchans"]).astype(np.uint8) if flag_file else None
+    if isinstance(gains, str):
+        gains = np.load(gains)
+    keep = None if flag is None else (flag == 0)[None, :]
+    n_tau, tau_lo, d_tau = tau_grid(hdr, keep, tau_half, dtau)
+    rinfo = {}
+    r = polcal(fil, hdr, cands, n_phi, phi_lo, d_phi, n_tau, tau_lo, d_tau, gains=gains, flag=flag, products=products, device=device,
+               lib=lib, info=rinfo)
+    res = r["results"]
+    phi = phi_lo + np.arange(n_phi) * d_phi
+    tau = tau_lo + np.arange(n_tau) * d_tau
+    base = filterbankfile.replace(".fil", "")
+    files = [base + "_polcal.npz", base + "_polcal.txt", base + "_polcal.png"]
+    comb = res[-1]
+    np.savez(files[0], spec=r["spec"], noise=r["noise"], used=r["used"], phi=phi, tau=tau, F=r["F"], results=res, bursts=cands,
+             tau_us=np.float64(comb["tau"]), tau_ns=np.float64(comb["tau"] * 1e3), tau_err_ns=np.float64(comb["tau_err"] * 1e3),
+             rm=np.float64(comb["rm"]))
+    with open(files[1], "w") as f:
+        for i, x in enumerate(res):
+            name = "pulse%d" % i if i < cands.size else "combined"
+            f.write(POLCAL_ROW % (name, x["tau"] * 1e3, x["tau_err"] * 1e3, x["rm"], x["rm_err"], np.degrees(x["psi"]), x["ridge_slope"] * 1e-3,
+                                  x["nridge"], x["snr"]) + "\n")
+    P = np.zeros((n_tau, n_phi))
+    for i in range(cands.size):
+        if res[i]["sigma_f"] > 0 and res[i]["nused"] > 0:
+            P += np.abs(r["F"][i].astype(np.complex128)) ** 2 / float(res[i]["sigma_f"]) ** 2
+    _polcal_png(files[2], P, comb)
+    if info is not None:
+        info.update(rinfo, nphi=n_phi, phi_lo=phi_lo, dphi=d_phi, ntau=n_tau, tau_lo=tau_lo, dtau=d_tau)
+    return files, res
+
+
 def pol_fractions(spec, noise, used, res):
     """-> (L/I debiased as sqrt(L^2 - sigma_L^2), V/I) of one burst, from the band-averaged spectra: L is the peak of |F|"""
     m = used != 0
@@ -2148,14 +2346,16 @@ def _rm_png(path, hdr, r, i, rmsf, phi):
 
 def rmsynth_fil(filterbankfile, bursts=None, dm1=None, dm2=0.0, dmstep=1.0, width=0, off_gap=None, off_len=None, phi_max=0.0, dphi=0.0,
                 nphi=0, flag_file=None, gains=None, products="stokes", threshold=8.0, max_cands=8, device=0, lib=None,
-                info: dict | None = None, profile=False, nbin=256, tfactor=1):
+                info: dict | None = None, profile=False, nbin=256, tfactor=1, polcal_file=None):
     """Rotation measure of the bursts of a full-Stokes filterbank: ``bursts`` = (dm, sample, width) tuples; or, with ``dm1 ..
     dm2 .. dmstep`` and no bursts, the ``max_cands`` strongest groups ``candidates_fil``'s search finds on product 0 above
     ``threshold`` (the search writes its ``.singlepulse`` files, as ``search_fil`` does).  ``gains``: an .npy file or an array [4][nchans]; ``flag_file``: channels left out of the transform.  The
     grid: ``rm_grid``.  Writes ``<base>_rm.npz`` (spec, noise, used, phi, F, rmsf, results, bursts), ``<base>_rm.txt`` (one
     line per burst: RM +- err, L/I debiased, V/I, PA0) and ``<base>_rm_burst<i>.png``.  ``profile=True``: each burst's
-    polarisation profile at its fitted RM as well (``nbin`` bins of ``tfactor`` rows), in the files of ``polprof_fil``.  Returns
-    (files, RM_RESULT records)."""
+    polarisation profile at its fitted RM as well (``nbin`` bins of ``tfactor`` rows), in the files of ``polprof_fil``.
+    ``polcal_file``: the ``<base>_polcal.npz`` of a calibrator (``polcal_fil``); its delay between the two circular feeds is
+    taken out of Q + iU before the transform (and of the profile), every file keeps its layout.  Returns (files, RM_RESULT
+    records)."""
     lib = lib or _lib.load()
     fil = sigproc.read_fil(filterbankfile)
     hdr = fil.header
@@ -2178,7 +2378,14 @@ def rmsynth_fil(filterbankfile, bursts=None, dm1=None, dm2=0.0, dmstep=1.0, widt
     keep = None if flag is None else (flag == 0)[None, :]
     n_phi, phi_lo, d_phi = rm_grid(hdr, keep, phi_max=phi_max, dphi=dphi, nphi=nphi)
     rinfo = {}
-    r = burst_rm(fil, hdr, cands, n_phi, phi_lo, d_phi, gains=gains, flag=flag, products=products, device=device, lib=lib, info=rinfo)
+    tau = polcal_tau(polcal_file) if polcal_file else None
+    if tau is None:
+        r = burst_rm(fil, hdr, cands, n_phi, phi_lo, d_phi, gains=gains, flag=flag, products=products, device=device, lib=lib, info=rinfo)
+    else:
+        r = polcal(fil, hdr, cands, n_phi, phi_lo, d_phi, 1, tau, POLCAL_DTAU_ONE, gains=gains, flag=flag, products=products,
+                   device=device, lib=lib, info=rinfo)
+        r["F"] = np.ascontiguousarray(r["F"][:, 0])
+        r["results"] = rm_peaks(r["F"], r["used"], r["noise"][:, 1], r["noise"][:, 2], hdr, n_phi, phi_lo, d_phi, lib=lib)
     rmsf = rm_synthesis(r["used"], np.zeros_like(r["spec"][:, 0]), r["used"], hdr, n_phi, phi_lo, d_phi, device=device, lib=lib)
     phi = phi_lo + np.arange(n_phi) * d_phi
     base = filterbankfile.replace(".fil", "")
@@ -2192,7 +2399,7 @@ def rmsynth_fil(filterbankfile, bursts=None, dm1=None, dm2=0.0, dmstep=1.0, widt
             files.append(base + "_rm_burst%d.png" % i)
     if profile:
         prof = pol_profile(fil, hdr, cands, r["results"]["rm"], nbin=nbin, tfactor=tfactor, gains=gains, flag=flag, products=products,
-                           device=device, lib=lib)
+                           device=device, lib=lib, tau=tau)
         files += _polprof_write(base, hdr, cands, r["results"]["rm"], prof, tfactor)
     if info is not None:
         info.update(rinfo, nphi=n_phi, phi_lo=phi_lo, dphi=d_phi)
@@ -2217,16 +2424,19 @@ def prof_params(nbin: int, tfactor: int, ref="mean") -> _lib.FrbchProfParams:
 
 
 def pol_profile(fil_or_rows, hdr: dict, cands, rm, nbin: int = 256, tfactor: int = 1, ref="mean", gains=None, flag=None,
-                products: str = "stokes", device: int = 0, lib=None, info: dict | None = None):
+                products: str = "stokes", device: int = 0, lib=None, info: dict | None = None, tau=None):
     """The polarisation profile of every burst at its RM (frbch_polprof_host; include/frbch.h states the arithmetic): ``nbin``
     bins of ``tfactor`` rows about ``sample`` at the burst's DM, every channel's baseline removed, (Q, U) rotated back by
     ``rm[i]`` to ``ref`` ('mean': the mean lambda^2 of the used channels, 'zero': infinite frequency) and summed over the band
     -> dict(acc int64 [n][nbin][4], hits [n][nbin], bins PROF_BIN [n][nbin], results PROF_RESULT [n], used [n][nchans]).
+    ``tau`` (microseconds, one value or one per burst; None: none): the delay between the two circular feeds that ``polcal_fil``
+    measures, taken out with the rotation (frbch_polprof_cal_host).
     ``info['kernel_used']``: 1 = the fast kernel, 0 = the generic one; ``info['spectra_kernel_used']``: the burst sums'."""
     lib = lib or _lib.load()
     rows, nrows, cands, par, g = _burst_args(fil_or_rows, hdr, cands, gains, products)
     n, nchan = cands.size, hdr["nchans"]
     rm = np.ascontiguousarray(np.broadcast_to(np.asarray(rm, dtype=np.float64), (n,)))
+    tau = None if tau is None else np.ascontiguousarray(np.broadcast_to(np.asarray(tau, dtype=np.float64), (n,)))
     fl = _flag_arg(flag, nchan)
     ppar = prof_params(nbin, tfactor, ref)
     nb = max(1, min(int(nbin), 1024))
@@ -2237,10 +2447,14 @@ def pol_profile(fil_or_rows, hdr: dict, cands, rm, nbin: int = 256, tfactor: int
     used = np.zeros((n, nchan), np.uint8)
     k = (C.c_uint32 * 2)(0, 0)
     err = C.create_string_buffer(512)
-    _check(lib.frbch_polprof_host(C.byref(fil_desc(hdr, hdr.get("product", 0))), rows.ctypes.data, nrows, C.byref(par), cands.ctypes.data, n,
-                                  rm.ctypes.data, g.ctypes.data if g is not None else None, fl.ctypes.data if fl is not None else None,
-                                  C.byref(ppar), device, acc.ctypes.data, hits.ctypes.data, bins.ctypes.data, res.ctypes.data,
-                                  used.ctypes.data, k, err, len(err)), err)
+    desc, tail = fil_desc(hdr, hdr.get("product", 0)), (g.ctypes.data if g is not None else None, fl.ctypes.data if fl is not None else None,
+                                                         C.byref(ppar), device, acc.ctypes.data, hits.ctypes.data, bins.ctypes.data,
+                                                         res.ctypes.data, used.ctypes.data, k, err, len(err))
+    if tau is None:
+        _check(lib.frbch_polprof_host(C.byref(desc), rows.ctypes.data, nrows, C.byref(par), cands.ctypes.data, n, rm.ctypes.data, *tail), err)
+    else:
+        _check(lib.frbch_polprof_cal_host(C.byref(desc), rows.ctypes.data, nrows, C.byref(par), cands.ctypes.data, n, rm.ctypes.data,
+                                          tau.ctypes.data, *tail), err)
     if info is not None:
         info.update(spectra_kernel_used=k[0], kernel_used=k[1])
     return dict(acc=acc, hits=hits, bins=bins, results=res, used=used)
@@ -2284,9 +2498,10 @@ def _polprof_write(base, hdr, cands, rm, prof, tfactor, ref="mean"):
 
 
 def polprof_fil(filterbankfile, bursts=None, rm=None, nbin=256, tfactor=1, ref="mean", off_gap=None, off_len=None, flag_file=None,
-                gains=None, products="stokes", rm_from=None, device=0, lib=None, info: dict | None = None):
+                gains=None, products="stokes", rm_from=None, device=0, lib=None, info: dict | None = None, polcal_file=None):
     """Polarisation profiles of the bursts of a full-Stokes filterbank: ``bursts`` = (dm, sample, width) tuples with ``rm`` (one
     value or one per burst), or ``rm_from`` = the ``<base>_rm.npz`` that ``rmsynth_fil`` wrote (its bursts and fitted RMs).
+    ``polcal_file``: the ``<base>_polcal.npz`` of a calibrator, whose delay between the two circular feeds is taken out.
     Writes ``<base>_polprof.npz / .txt`` and ``<base>_polprof_burst<i>.png``.  Returns (files, what ``pol_profile`` returns)."""
     lib = lib or _lib.load()
     fil = sigproc.read_fil(filterbankfile)
@@ -2304,7 +2519,7 @@ def polprof_fil(filterbankfile, bursts=None, rm=None, nbin=256, tfactor=1, ref="
     if isinstance(gains, str):
         gains = np.load(gains)
     prof = pol_profile(fil, hdr, cands, rm, nbin=nbin, tfactor=tfactor, ref=ref, gains=gains, flag=flag, products=products,
-                       device=device, lib=lib, info=info)
+                       device=device, lib=lib, info=info, tau=polcal_tau(polcal_file) if polcal_file else None)
     return _polprof_write(filterbankfile.replace(".fil", ""), hdr, cands, rm, prof, tfactor, ref), prof
 
 
@@ -2820,7 +3035,9 @@ def main(argv=None):
     ``... psearch <fil> --dm <dm> [--dm2 --dmstep --sigma --nharm --flo --nfft --wblock --dm-gap --max-cands --fold-best K --amax A --astep S --acc-gap G]`` /
     ``... rfifind <fil> [--block-rows --t-cell --t-chan --chan-frac --block-frac --flag FILE --write-clean]`` /
     ``... rmsynth <fil> (--dm D --sample S | --time T) --width W [--off-gap G --off-len L] [--phi-max X --dphi Y | --nphi N] [--flag FILE]
-    [--gains FILE.npy] [--products stokes|coherency] [--profile --nbin N --tfactor F]`` (burst options repeatable; or ``--dm .. --dm2 .. --dmstep ..`` to search for them) /
+    [--gains FILE.npy] [--products stokes|coherency] [--profile --nbin N --tfactor F] [--polcal BASE_polcal.npz]`` (burst options repeatable; or ``--dm .. --dm2 .. --dmstep ..`` to search for them) /
+    ``... polcal <fil> --dm D (--sample S | --time T) --width W (--rm-known R | --rm-lo A --rm-hi B --rm-step S) [--tau-half NS --dtau NS --flag FILE --gains FILE.npy]``
+    (pulses of a calibrator of known RM, repeatable or searched as for ``rmsynth``: the delay between the two circular feeds, which ``rmsynth`` and ``polprof`` take with ``--polcal``) /
     ``... dmfit <fil> --dm D (--sample S | --time T) --width W [--dm-half H --ddm X --nbin N --tfactor F --smooth S --fit-frac R --flag FILE --coherency]``
     (or ``--dm .. --dm2 .. --dmstep ..`` to search for the bursts; ``rmsynth`` and ``polprof`` take ``--dm-from BASE_dm.npz [--dm-kind snr|struct]`` in place of ``--dm``) /
     ``... burstacf <fil> (--dm D (--sample S | --time T) --width W | --dm-from BASE_dm.npz [--dm-kind snr|struct]) [--nbin N --tfactor F --ffactor F --lagf N --lagt N --fit-frac R --flag FILE --coherency]`` /
@@ -2969,6 +3186,31 @@ def main(argv=None):
     m.add_argument("--profile", action="store_true", help="also write each burst's polarisation profile at its fitted RM (the files of `polprof`)")
     m.add_argument("--nbin", type=int, default=256, help="bins of --profile")
     m.add_argument("--tfactor", type=int, default=1, help="rows per bin of --profile")
+    m.add_argument("--polcal", default=None, help="<base>_polcal.npz of `polcal` on a calibrator: its R/L delay is taken out before the transform")
+    pc = sub.add_parser("polcal", help="delay between the two circular feeds from the pulses of a calibrator of known RM: the delay x RM transform")
+    pc.add_argument("fil")
+    pc.add_argument("--dm", type=float, action="append", default=None, help="DM of a pulse (repeatable, one per pulse); with --dm2: the first DM of the search")
+    pc.add_argument("--dm-from", default=None, help="<base>_dm.npz of `dmfit`: its bursts at their measured DMs instead of --dm .. --width")
+    pc.add_argument("--dm-kind", choices=("snr", "struct"), default="snr", help="which DM of --dm-from: the S/N- or the structure-maximising one")
+    pc.add_argument("--sample", type=int, action="append", default=None, help="centre of a pulse, row at the top of the band (repeatable)")
+    pc.add_argument("--time", type=float, action="append", default=None, help="the same in seconds from the start of the file (repeatable)")
+    pc.add_argument("--width", type=int, action="append", default=None, help="on-pulse rows (repeatable; one value serves every pulse)")
+    pc.add_argument("--dm2", type=float, default=0.0, help="search DM .. DM2 for the pulses instead (the groups of `candidates` on product 0)")
+    pc.add_argument("--dmstep", type=float, default=1.0)
+    pc.add_argument("--threshold", type=float, default=8.0, help="sigma of the search of --dm2")
+    pc.add_argument("--max-cands", type=int, default=8, help="pulses kept from the search of --dm2")
+    pc.add_argument("--off-gap", type=int, default=None, help="rows between the pulse and each off-pulse window (default: 2 widths, at least 16)")
+    pc.add_argument("--off-len", type=int, default=None, help="rows of each off-pulse window (default 1024)")
+    pc.add_argument("--rm-known", type=float, default=None, help="the calibrator's RM, rad/m2: one RM trial")
+    pc.add_argument("--rm-lo", type=float, default=None, help="or a range of RM trials: first")
+    pc.add_argument("--rm-hi", type=float, default=None, help="last")
+    pc.add_argument("--rm-step", type=float, default=None, help="step")
+    pc.add_argument("--tau-half", type=float, default=0.0, help="delays searched either side of 0, NANOSECONDS (0: 8 fwhm_tau)")
+    pc.add_argument("--dtau", type=float, default=0.0, help="step of the delay, NANOSECONDS (0: fwhm_tau / 8)")
+    pc.add_argument("--flag", default=None, help="flag file: channels left out of the transform")
+    pc.add_argument("--gains", default=None, help=".npy file [4][nchans] of gains that multiply the spectra")
+    pc.add_argument("--products", choices=("coherency", "stokes"), default="stokes", help="what the file holds: I, Q, U, V or the -d4 products")
+    pc.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     f = sub.add_parser("polprof", help="polarisation profile of the bursts of a full-Stokes filterbank: derotated I, L, V and PA per time bin")
     f.add_argument("fil")
     f.add_argument("--dm", type=float, action="append", default=None, help="DM of a burst (repeatable, one per burst)")
@@ -2987,6 +3229,7 @@ def main(argv=None):
     f.add_argument("--flag", default=None, help="flag file: channels left out")
     f.add_argument("--gains", default=None, help=".npy file [4][nchans] of gains")
     f.add_argument("--coherency", action="store_true", help="the file holds the -d4 products PP, QQ, Re, Im")
+    f.add_argument("--polcal", default=None, help="<base>_polcal.npz of `polcal` on a calibrator: its R/L delay is taken out with the rotation")
     f.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     d = sub.add_parser("dmfit", help="DM of the bursts of a filterbank: a fine DM scan, the S/N- and the structure-maximising DM")
     d.add_argument("fil")
@@ -3124,7 +3367,7 @@ def main(argv=None):
             rm = [rms[i if len(rms) > 1 else 0] for i in range(len(centres))]
         files, _prof = polprof_fil(a.fil, bursts, rm=rm, nbin=a.nbin, tfactor=a.tfactor, ref=a.ref, off_gap=a.off_gap, off_len=a.off_len,
                                    flag_file=a.flag, gains=a.gains, products="coherency" if a.coherency else "stokes", rm_from=a.rm_from,
-                                   device=a.device)
+                                   device=a.device, **(dict(polcal_file=a.polcal) if a.polcal else {}))
         for path in files:
             print("wrote", path)
     elif a.cmd == "rmsynth":
@@ -3144,7 +3387,29 @@ def main(argv=None):
         files, res = rmsynth_fil(a.fil, bursts, dm1=a.dm[0], dm2=a.dm2, dmstep=a.dmstep, width=(a.width or [0])[0], off_gap=a.off_gap,
                                  off_len=a.off_len, phi_max=a.phi_max, dphi=a.dphi, nphi=a.nphi, flag_file=a.flag, gains=a.gains,
                                  products=a.products, threshold=a.threshold, max_cands=a.max_cands, device=a.device,
-                                 **(dict(profile=True, nbin=a.nbin, tfactor=a.tfactor) if a.profile else {}))
+                                 **(dict(profile=True, nbin=a.nbin, tfactor=a.tfactor) if a.profile else {}),
+                                 **(dict(polcal_file=a.polcal) if a.polcal else {}))
+        for path in files:
+            print("wrote", path)
+        print(open(files[1]).read(), end="")
+    elif a.cmd == "polcal":
+        bursts = None
+        if a.dm_from:
+            bursts = list(bursts_from_dm(a.dm_from, a.dm_kind))
+            a.dm = [float(bursts[0]["dm"])]
+        elif not a.dm:
+            pc.error("the following arguments are required: --dm")
+        elif a.dm2 <= 0.0:
+            tsamp = sigproc.read_fil(a.fil).header["tsamp"]
+            centres = list(a.sample or []) + [int(round(t / tsamp)) for t in (a.time or [])]
+            widths = a.width or []
+            if not centres or len(centres) != len(a.dm) or len(widths) not in (1, len(centres)):
+                raise InputError("polcal: one --sample or --time per --dm, and --width once or once per pulse")
+            bursts = [(dm, s, widths[i if len(widths) > 1 else 0]) for i, (dm, s) in enumerate(zip(a.dm, centres))]
+        files, res = polcal_fil(a.fil, bursts, dm1=a.dm[0], dm2=a.dm2, dmstep=a.dmstep, width=(a.width or [0])[0], off_gap=a.off_gap,
+                                off_len=a.off_len, rm_known=a.rm_known, rm_lo=a.rm_lo, rm_hi=a.rm_hi, rm_step=a.rm_step, tau_half=a.tau_half,
+                                dtau=a.dtau, flag_file=a.flag, gains=a.gains, products=a.products, threshold=a.threshold,
+                                max_cands=a.max_cands, device=a.device)
         for path in files:
             print("wrote", path)
         print(open(files[1]).read(), end="")

@@ -811,6 +811,74 @@ int frbch_burst_rm_host(const frbch_fil_desc* fil, const void* rows, uint64_t nr
                         const frbch_rm_params* par, int device, float* spec, float* noise, uint8_t* used, float* F,
                         frbch_rm_result* results, uint32_t* kernel_used, char* err, size_t err_cap);
 
+/* ---- polarisation calibration: the delay x RM transform ------------------------------------------------
+ * Dual circular feeds: a cable or sampler delay tau between the R and L paths multiplies Q + iU by exp(2 pi i f tau), a phase
+ * ramp across the band that RM synthesis cannot tell from Faraday rotation (at 1.2 - 1.5 GHz the ridge of |F|^2 in the
+ * (RM, tau) plane runs at about +43 rad m^-2 per nanosecond; to first order pi f^3 / (2 c^2)).  A calibrator of known RM is
+ * searched over tau (and a narrow range of RM), and the delay found is taken out of the target's bursts (frbch_polprof_cal_*
+ * below; this transform at ntau = 1, tau_lo = tau).  Which feed lags for positive tau depends on the backend's sign
+ * convention, which is not pinned here: the correction is consistent with the search, and that is all it needs to be.
+ * Absolute PA calibration is out of scope: psi below is twice the PA plus the R/L phase offset, which cannot be separated.
+ * tests/polcal_oracle.py restates what follows in numpy.
+ *
+ * Transform.  f_c, l2_c, used, N_i, l0_i, a_ic, frac(), the fix to 2^64, the table C[] / S[], the index rule, the
+ * quantisation Qi / Ui and inv_i are those of step 2 of the burst polarisation section, unchanged.  New, on the host in
+ * double, ascending c, every operation rounded on its own:
+ *      f0_i = (sum over used c of f_c) / N_i;   b_ic = f_c - f0_i  (MHz; tau is in MICROSECONDS, so tau b is in turns);
+ *      T0_ic = (uint64)(frac(tau_lo b_ic) 2^64),  E_ic = (uint64)(frac(dtau b_ic) 2^64),
+ *      ph_ickm = P0_ic + k D_ic + T0_ic + m E_ic mod 2^64   (tau_m = tau_lo + m dtau);
+ *    Re, Im are the sums of step 2 at that phase, that is (q + i u) exp(-2 i phi_k (l2_c - l0_i)) exp(-2 pi i tau_m (f_c -
+ *    f0_i)), exact in int64 in any order (the same 2^60 bound);  F[ncand][ntau][nphi][2] float32 through inv_i.
+ *    ntau = 1, tau_lo = 0 gives the bits of frbch_rmsynth_* on the same phi grid.
+ *    kernel_used[2] (may be NULL): the form (1 = the fast kernel: table in the LDS, lanes along k, a tile of tau trials in
+ *    registers next to each thread's k trials, channels split over kernel_used[1] workgroups whose int64 partials a second
+ *    kernel joins; taken for nphi >= 64 and an 8-byte aligned d_F; 0 = the generic one, one thread per (i, m, k), split 1).
+ *    Both give the same bits.  FRBCH_E_ARG: every refusal of step 2 above, a wrong `size`, ntau outside 1..4096,
+ *    ncand * ntau * nphi > 2^26, dtau <= 0 or not finite, |tau_lo| or |tau_lo + ntau dtau| above 100.
+ *
+ * Peaks (frbch_rmdelay_peaks, host only, double, no FMA).  Per candidate P[m][k] = re re + im im; (mp, kp) = the first
+ *    largest in row-major order.  Along each axis on its own the parabola of step 3 (interior and den < 0: delta = 0.5 (y- -
+ *    y+) / den, fitted = 1; else the grid value): tau = tau_lo + (mp + delta_m) dtau, rm = phi_lo + (kp + delta_k) dphi.
+ *    peak = sqrt(P[mp][kp]);  psi = atan2(im, re) there;  sigma_f, snr, fwhm, rm_err as in step 3;  fwhm_tau = 2 sqrt(3) /
+ *    (pi (f_max - f_min)) over the used channels;  tau_err = fwhm_tau / (2 snr).
+ *    Ridge: k_m = the first largest k of row m; over the rows with P[m][k_m] >= 0.5 P[mp][kp], in ascending m, the
+ *    least-squares line of phi_{k_m} on tau_m:  n = nridge, mt = (sum tau) / n, mf = (sum phi) / n, sxx = sum (tau - mt)^2,
+ *    sxy = sum (tau - mt)(phi - mf), ridge_slope = sxy / sxx (rad m^-2 per microsecond; 0 if nridge < 2 or sxx = 0): what an
+ *    error in the delay does to an RM.
+ *    results[ncand] (one extra record), several pulses of one calibrator (one tau and RM, a PA each):  Psum[m][k] = sum over
+ *    i of P_i[m][k] / sigma_f_i^2 in ascending i, candidates with sigma_f = 0 or nused = 0 skipped; the same peak and ridge
+ *    rule on Psum; there peak = snr = sqrt(Psum[mp][kp]), sigma_f = 1, psi = 0, nused = the number of candidates that
+ *    entered, fwhm and fwhm_tau over the channels used by any of them; all 0 if none entered. */
+typedef struct frbch_rmd_params { uint32_t size, nphi, ntau, reserved; double phi_lo, dphi, tau_lo, dtau; } frbch_rmd_params;   /* size = sizeof(frbch_rmd_params) */
+typedef struct frbch_rmd_result {
+  double tau, tau_err, rm, rm_err, peak, psi, snr, sigma_f, fwhm, fwhm_tau, ridge_slope;
+  uint32_t mpeak, kpeak, nused, fitted_tau, fitted_rm, nridge;
+} frbch_rmd_result;
+/* The plan rule (host only, nothing runs): 1 = fast, 0 = generic, < 0 = refused; *nsplit (may be NULL): the channel split.
+ * Only the ADDRESS of d_F is examined. */
+int frbch_rmdelay_kernel(const frbch_fil_desc* fil, const float* d_F, uint32_t ncand, const frbch_rmd_params* par, uint32_t* nsplit);
+/* d_q, d_u [ncand][nchan] float32, d_used [ncand][nchan] bytes (read, never written) and d_F [ncand][ntau][nphi][2] float32
+ * are device memory. */
+int frbch_rmdelay_device(const frbch_fil_desc* fil, const float* d_q, const float* d_u, const uint8_t* d_used, uint32_t ncand,
+                         const frbch_rmd_params* par, int device, float* d_F, uint32_t* kernel_used, char* err, size_t err_cap);
+int frbch_rmdelay_host(const frbch_fil_desc* fil, const float* q, const float* u, const uint8_t* used, uint32_t ncand,
+                       const frbch_rmd_params* par, int device, float* F, uint32_t* kernel_used, char* err, size_t err_cap);
+/* results [ncand + 1]: the candidates, then the combined record */
+int frbch_rmdelay_peaks(const frbch_fil_desc* fil, const float* F, const uint8_t* used, const float* noise_q, const float* noise_u,
+                        uint32_t ncand, const frbch_rmd_params* par, frbch_rmd_result* results, char* err, size_t err_cap);
+/* The composite: rows -> spectra (step 1 of the burst polarisation section; nifs must be 4) -> `flag` -> the delay x RM
+ * transform of Q and U -> peaks and the combined record, in one device scope (_host: one upload of the rows).  The arguments
+ * are those of frbch_burst_rm_*, with F [ncand][ntau][nphi][2] and results [ncand + 1].  kernel_used[3] (may be NULL): the
+ * spectra's kernel, the transform's form and its split. */
+int frbch_burst_polcal_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                              const frbch_burst_cand* cands, uint32_t ncand, const float* gain, const uint8_t* flag,
+                              const frbch_rmd_params* par, int device, float* spec, float* noise, uint8_t* used, float* F,
+                              frbch_rmd_result* results, uint32_t* kernel_used, char* err, size_t err_cap);
+int frbch_burst_polcal_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* bpar,
+                            const frbch_burst_cand* cands, uint32_t ncand, const float* gain, const uint8_t* flag,
+                            const frbch_rmd_params* par, int device, float* spec, float* noise, uint8_t* used, float* F,
+                            frbch_rmd_result* results, uint32_t* kernel_used, char* err, size_t err_cap);
+
 /* ---- polarisation profile of a burst: derotated I, L, V and PA per time bin ---------------------------
  * What an RM is measured for: the burst against time at its DM, Q and U of every channel rotated back by the RM and summed
  * over the band.  n_c(dm), the windows, frbch_burst_sums, used, l2_c, the table C[] / S[] and frac() are those of the burst
@@ -887,6 +955,20 @@ int frbch_polprof_host(const frbch_fil_desc* fil, const void* rows, uint64_t nro
                        const frbch_burst_cand* cands, uint32_t ncand, const double* rm, const float* gain, const uint8_t* flag,
                        const frbch_prof_params* par, int device, int64_t* acc, uint32_t* hits, frbch_prof_bin* bins,
                        frbch_prof_result* results, uint8_t* used, uint32_t* kernel_used, char* err, size_t err_cap);
+/* The same with the R/L delay of the polarisation calibration section taken out: tau [ncand] (microseconds; NULL: none, the
+ * bits of the calls above, which pass NULL).  Only the host preparation changes:
+ *    ph_ic = fix(rm_i a_ic) + fix(tau_i b_ic) mod 2^64,  b_ic = f_c - f0_i as defined there, for either `ref`.
+ * FRBCH_E_ARG besides: a tau that is not finite or above 100 in size. */
+int frbch_polprof_cal_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                             const frbch_burst_cand* cands, uint32_t ncand, const double* rm, const double* tau, const float* gain,
+                             const uint8_t* flag, const frbch_prof_params* par, int device, int64_t* acc, uint32_t* hits,
+                             frbch_prof_bin* bins, frbch_prof_result* results, uint8_t* used, uint32_t* kernel_used, char* err,
+                             size_t err_cap);
+int frbch_polprof_cal_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* bpar,
+                           const frbch_burst_cand* cands, uint32_t ncand, const double* rm, const double* tau, const float* gain,
+                           const uint8_t* flag, const frbch_prof_params* par, int device, int64_t* acc, uint32_t* hits,
+                           frbch_prof_bin* bins, frbch_prof_result* results, uint8_t* used, uint32_t* kernel_used, char* err,
+                           size_t err_cap);
 
 /* ---- DM of a burst: fine DM scan, S/N and structure maxima -------------------------------------------
  * The stages above take the DM of a burst as given; this one measures it: the burst's band-summed, noise-weighted profile at
