@@ -71,6 +71,13 @@ class FrbchFoldModel(C.Structure):
                 ("dm", C.c_double), ("apply_delays", C.c_uint32), ("nbin", C.c_uint32), ("subint_s", C.c_double)]
 
 
+class FrbchFoldfitParams(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("nbin", C.c_uint32), ("nsub", C.c_uint32), ("products", C.c_uint32), ("ndm", C.c_uint32),
+                ("nfreq", C.c_uint32), ("nfdot", C.c_uint32), ("nwidth", C.c_uint32), ("f0_fold", C.c_double), ("subint_s", C.c_double),
+                ("dm0", C.c_double), ("ddm", C.c_double), ("dfreq", C.c_double), ("dfdot", C.c_double), ("fit_frac", C.c_double),
+                ("widths", C.c_uint32 * 8)]
+
+
 class FrbchSpParams(C.Structure):
     _fields_ = [("size", C.c_uint32), ("nwidth", C.c_uint32), ("widths", C.c_uint32 * 16), ("detrend_len", C.c_uint32),
                 ("reserved", C.c_uint32), ("threshold", C.c_double)]
@@ -339,6 +346,18 @@ SYMBOLS = {
                                    C.c_uint32, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
     "frbch_foldp_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchFoldModel), C.c_int, _P, _P,
                                      C.c_uint32, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    "frbch_foldfit_steps": (C.c_int, [C.POINTER(FrbchFilDesc), C.c_uint64, C.c_uint32, C.c_double, C.POINTER(C.c_double),
+                                      C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "frbch_foldfit_kernel": (C.c_int, [C.POINTER(FrbchFilDesc), C.c_uint64, C.POINTER(FrbchFoldfitParams), _P, _P, C.POINTER(C.c_uint32)]),
+    "frbch_foldfit_device": (C.c_int, [C.POINTER(FrbchFilDesc), C.c_uint64, C.POINTER(FrbchFoldfitParams), _P, _P, _P, C.c_int, _P, _P, _P,
+                                       _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "frbch_foldfit_host": (C.c_int, [C.POINTER(FrbchFilDesc), C.c_uint64, C.POINTER(FrbchFoldfitParams), _P, _P, _P, C.c_int, _P, _P, _P,
+                                     _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "frbch_foldfit_peaks": (C.c_int, [C.POINTER(FrbchFoldfitParams), _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "frbch_fold_refine_device": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchFoldModel), C.POINTER(FrbchFoldfitParams),
+                                           _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
+    "frbch_fold_refine_host": (C.c_int, [C.POINTER(FrbchFilDesc), _P, C.c_uint64, C.POINTER(FrbchFoldModel), C.POINTER(FrbchFoldfitParams),
+                                         _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_char_p, C.c_size_t]),
     "frbch_spsearch_host": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.POINTER(FrbchSpParams), C.c_int, _P, C.c_uint64,
                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
     "frbch_spsearch_device": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.POINTER(FrbchSpParams), C.c_int, _P, C.c_uint64,

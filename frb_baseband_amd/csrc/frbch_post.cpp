@@ -6559,3 +6559,534 @@ extern "C" int frbch_burstscat_host(const frbch_fil_desc* fil, const void* rows,
     return frbch_burstscat_device(fil, d_rows, nrows, bpar, cands, ncand, flag, par, bp, fp, device, Y, yhits, y, C, N, sub, band, used, kernel_used, err, err_cap);
   });
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// refinement of a fold: DM, spin frequency and frequency derivative (include/frbch.h states the arithmetic)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr uint32_t kFfMaxBin = 4096, kFfMaxSub = 4096, kFfMaxChan = 16384;
+constexpr uint64_t kFfMaxTrial = 1ull << 22, kFfMaxProf = 1ull << 24, kFfMaxPlane = 1ull << 31;
+
+inline uint64_t ff_rows_per_sub(const frbch_fil_desc* fil, double subint_s) {
+  return std::max<uint64_t>(1, (uint64_t)llround(subint_s / fil->tsamp_s));
+}
+inline uint32_t ff_popcount(uint32_t m) { uint32_t n = 0; for (; m; m &= m - 1) ++n; return n; }
+inline uint64_t ff_ntrial(const frbch_foldfit_params* par) { return (uint64_t)par->ndm * par->nfdot * par->nfreq; }
+
+// every refusal that needs neither the flag nor a table
+int ff_check(const frbch_fil_desc* fil, uint64_t nrows, const frbch_foldfit_params* par, const PostErr& e) {
+  POST_NO_CONTRACT
+  if (!par || par->size != sizeof(frbch_foldfit_params)) return e.fail(FRBCH_E_ARG, "frbch_foldfit_params: wrong size");
+  const int rc = post_check_fil(fil, nrows, e);
+  if (rc) return rc;
+  if (fil->nbits == 32) return e.fail(FRBCH_E_ARG, "float rows: the search adds exact integers, 8- or 16-bit rows only");
+  if (fil->nifs > 4) return e.fail(FRBCH_E_ARG, "nifs must be 1..4");
+  if (fil->nchan > kFfMaxChan) return e.fail(FRBCH_E_ARG, "more than 16384 channels");
+  if (par->nbin < 2 || par->nbin > kFfMaxBin) return e.fail(FRBCH_E_ARG, "nbin must be 2..4096");
+  if (par->nsub < 1 || par->nsub > kFfMaxSub) return e.fail(FRBCH_E_ARG, "nsub must be 1..4096");
+  const uint32_t n[3] = {par->ndm, par->nfreq, par->nfdot};
+  const char* const name[3] = {"ndm", "nfreq", "nfdot"};
+  for (int a = 0; a < 3; ++a)
+    if (n[a] < 1 || (n[a] > 1 && n[a] % 2 == 0)) return e.fail(FRBCH_E_ARG, std::string(name[a]) + " must be odd or 1");
+  if (ff_ntrial(par) > kFfMaxTrial) return e.fail(FRBCH_E_ARG, "ndm * nfdot * nfreq exceeds 2^22");
+  if ((uint64_t)par->ndm * par->nsub * par->nbin > kFfMaxPlane) return e.fail(FRBCH_E_ARG, "ndm * nsub * nbin exceeds 2^31: cut the DM axis");
+  if (!par->products) return e.fail(FRBCH_E_ARG, "products: an empty mask");
+  if (par->products >> fil->nifs) return e.fail(FRBCH_E_ARG, "products: a product beyond nifs");
+  if (!(par->f0_fold > 0) || !std::isfinite(par->f0_fold)) return e.fail(FRBCH_E_ARG, "f0_fold must be positive and finite");
+  const double step[3] = {par->ddm, par->dfreq, par->dfdot};
+  const char* const sname[3] = {"ddm", "dfreq", "dfdot"};
+  for (int a = 0; a < 3; ++a) {
+    if (!std::isfinite(step[a])) return e.fail(FRBCH_E_ARG, std::string(sname[a]) + " is not finite");
+    if (n[a] > 1 && !(step[a] > 0)) return e.fail(FRBCH_E_ARG, std::string(sname[a]) + " must be positive where its axis has more than one trial");
+  }
+  if (!std::isfinite(par->dm0)) return e.fail(FRBCH_E_ARG, "dm0 is not finite");
+  if (!(par->fit_frac > 0) || !(par->fit_frac <= 1)) return e.fail(FRBCH_E_ARG, "fit_frac must lie in (0, 1]");
+  if (par->nwidth < 1 || par->nwidth > 8) return e.fail(FRBCH_E_ARG, "nwidth must be 1..8");
+  for (uint32_t w = 0; w < par->nwidth; ++w)
+    if (par->widths[w] < 1 || par->widths[w] > par->nbin / 2) return e.fail(FRBCH_E_ARG, "a width outside 1..nbin / 2");
+  const unsigned __int128 big = (unsigned __int128)((1ull << fil->nbits) - 1) * nrows * fil->nchan * ff_popcount(par->products);
+  if (big >= ((unsigned __int128)1 << 53)) return e.fail(FRBCH_E_ARG, "(2^nbits - 1) * nrows * nchan * products reaches 2^53: the sums would not be exact doubles");
+  if (!(par->subint_s > 0)) return e.fail(FRBCH_E_ARG, "subint_s must be positive");
+  const long want = frbch_fold_nsub(fil, nrows, par->subint_s);
+  if (want <= 0 || (uint32_t)want != par->nsub) return e.fail(FRBCH_E_ARG, "nsub must be frbch_fold_nsub()");
+  return FRBCH_OK;
+}
+
+struct FfPlan {
+  uint64_t L = 0;
+  std::vector<int32_t> shd;        // [ndm][nchan]
+  std::vector<int32_t> shp;        // [nfdot][nfreq][nsub]: (-shP) mod nbin, which the kernels add
+  std::vector<uint8_t> use;        // [nchan]
+};
+
+inline double ff_axis(uint32_t i, uint32_t n, double step) {
+  POST_NO_CONTRACT
+  return (double)((long long)i - (long long)(n / 2)) * step;
+}
+
+// y bins -> 0 .. nbin - 1; false: beyond 2^52
+inline bool ff_reduce(double y, uint32_t nbin, int32_t* out) {
+  if (!(fabs(y) <= 4503599627370496.0)) return false;
+  long long m = (long long)rint(y) % (long long)nbin;
+  if (m < 0) m += nbin;
+  *out = (int32_t)m;
+  return true;
+}
+
+// the tables of the header; `flag` may be NULL
+int ff_build(const frbch_fil_desc* fil, uint64_t nrows, const frbch_foldfit_params* par, const uint8_t* flag, FfPlan* plan,
+             const PostErr& e) {
+  POST_NO_CONTRACT
+  const uint32_t nchan = fil->nchan, nbin = par->nbin, nsub = par->nsub;
+  plan->L = ff_rows_per_sub(fil, par->subint_s);
+  plan->use.assign(nchan, 1);
+  for (uint32_t c = 0; flag && c < nchan; ++c)
+    if (flag[c]) plan->use[c] = 0;
+  plan->shd.resize((size_t)par->ndm * nchan);
+  for (uint32_t k = 0; k < par->ndm; ++k) {
+    const double dm = par->dm0 + ff_axis(k, par->ndm, par->ddm);
+    if (!(dm >= 0.0) || !(dm < 1.0e5)) return e.fail(FRBCH_E_ARG, "DM trial " + std::to_string(k) + " lies outside [0, 1e5)");
+    for (uint32_t c = 0; c < nchan; ++c) {
+      const double turns = post_delay_s(fil, dm, c) * par->f0_fold;
+      if (!ff_reduce(turns * (double)nbin, nbin, &plan->shd[(size_t)k * nchan + c])) return e.fail(FRBCH_E_ARG, "a DM shift beyond 2^52 bins");
+    }
+  }
+  std::vector<double> tau(nsub);
+  for (uint32_t s = 0; s < nsub; ++s) {
+    const uint64_t first = (uint64_t)s * plan->L, r = std::min<uint64_t>(plan->L, nrows - first);
+    const double mid = ((double)first + 0.5 * (double)r) - 0.5 * (double)nrows;
+    tau[s] = mid * fil->tsamp_s;
+  }
+  plan->shp.resize((size_t)par->nfdot * par->nfreq * nsub);
+  for (uint32_t j = 0; j < par->nfdot; ++j) {
+    const double hd = 0.5 * ff_axis(j, par->nfdot, par->dfdot);
+    for (uint32_t i = 0; i < par->nfreq; ++i) {
+      const double df = ff_axis(i, par->nfreq, par->dfreq);
+      for (uint32_t s = 0; s < nsub; ++s) {
+        const double lin = df * tau[s];
+        const double quad = (hd * tau[s]) * tau[s];
+        const double turns = lin + quad;                       // (bin b reads b - shP: the table holds the shift negated)
+        if (!ff_reduce(-(turns * (double)nbin), nbin, &plan->shp[((size_t)j * par->nfreq + i) * nsub + s])) return e.fail(FRBCH_E_ARG, "a spin shift beyond 2^52 bins");
+      }
+    }
+  }
+  return FRBCH_OK;
+}
+
+// The plan rule of the fold refinement -- the one decision behind frbch_foldfit_device's launches, kernel_used and
+// frbch_foldfit_kernel's answer.  The fast forms (kernels_post_fast.inc) want the cube and its hits 16-byte aligned (only the
+// ADDRESSES are examined; a call that fails this runs the generic form in BOTH stages, so that every shape has a complete
+// generic run next to its fast one) and the sums of a sub-integration in 32 bits.  Stage 1: whole tiles of 8 channels and a
+// tile of all bins in the LDS (nbin <= 1024); the channel tiles are cut into runs of kFfTileRun, joined when there are
+// several.  Stage 2: at least two spin trials a DM (one trial has nothing to share a staged chunk with); sc sub-integrations
+// of 12 bytes a bin fill the 64 KiB stage.  The emulator build has no such kernels: generic.
+struct FfPlanRule { bool fast1 = false, fast2 = false; int ngrp = 1, bpt1 = 1, bpt2 = 1, sc = 1, lstride = 0, nrun = 1; };
+FfPlanRule ff_plan_rule(const frbch_fil_desc* fil, const frbch_foldfit_params* par, const double* d_cube, const uint32_t* d_hits) {
+  FfPlanRule r;
+#ifndef FRBCH_NO_FAST
+  const uint64_t L = ff_rows_per_sub(fil, par->subint_s);
+  const unsigned __int128 vmax = (unsigned __int128)((1ull << fil->nbits) - 1) * ff_popcount(par->products) * L;
+  const unsigned __int128 hmax = (unsigned __int128)L * fil->nchan;
+  const unsigned __int128 lim = (unsigned __int128)1 << 32;
+  if (((uintptr_t)d_cube % 16) != 0 || ((uintptr_t)d_hits % 16) != 0 || vmax >= lim || hmax >= lim) return r;
+  auto bpt = [](uint32_t nbin) { int b = 1; while ((uint32_t)(b * fast::kFfThreads) < nbin) b *= 2; return b; };
+  if (fil->nchan % fast::kFfCT == 0 && par->nbin <= (uint32_t)fast::kFfMaxBin1) {
+    r.fast1 = true;
+    r.bpt1 = bpt(par->nbin);
+    r.lstride = (int)((par->nbin + 31) / 32 * 32 + 4);
+    r.ngrp = (int)((fil->nchan / fast::kFfCT + fast::kFfTileRun - 1) / fast::kFfTileRun);
+  }
+  if ((uint64_t)par->nfdot * par->nfreq >= 2) {
+    r.fast2 = true;
+    r.bpt2 = bpt(par->nbin);
+    r.sc = (int)std::min<uint64_t>(par->nsub, fast::kFfStage2 / (12ull * par->nbin));
+    const uint32_t run = (uint32_t)(fast::kFfElems / r.bpt2);
+    r.nrun = (int)((par->nfdot * par->nfreq + run - 1) / run);
+  }
+#else
+  (void)fil; (void)par; (void)d_cube; (void)d_hits;
+#endif
+  return r;
+}
+
+// S/N of a profile (the header's rule) -> *snr, *width, *bin
+void ff_snr(const int64_t* B, const uint64_t* H, const frbch_foldfit_params* par, double* snr, uint32_t* width, uint32_t* bin) {
+  POST_NO_CONTRACT
+  const uint32_t nb = par->nbin, nw = nb / 2;
+  std::vector<double> x(nb);
+  for (uint32_t b = 0; b < nb; ++b) x[b] = H[b] ? (double)B[b] / (double)H[b] : 0.0;
+  auto window = [&](uint32_t j, uint32_t w) {
+    double s = 0.0;
+    for (uint32_t i = 0; i < w; ++i) s = s + x[(j + i) % nb];
+    return s;
+  };
+  uint32_t off = 0;
+  double best = window(0, nw);
+  for (uint32_t j = 1; j < nb; ++j) {
+    const double s = window(j, nw);
+    if (s < best) { best = s; off = j; }
+  }
+  const double base = best / (double)nw;
+  double ss = 0.0;
+  for (uint32_t i = 0; i < nw; ++i) {
+    const double d = x[(off + i) % nb] - base;
+    const double dd = d * d;
+    ss = ss + dd;
+  }
+  const double rms = sqrt(ss / (double)nw);
+  *snr = 0.0; *width = par->widths[0]; *bin = 0;
+  if (!(rms > 0.0)) return;
+  bool first = true;
+  for (uint32_t wi = 0; wi < par->nwidth; ++wi) {
+    const uint32_t w = par->widths[wi];
+    const double rw = sqrt((double)w);
+    for (uint32_t j = 0; j < nb; ++j) {
+      const double m = window(j, w) / (double)w;
+      const double v = ((m - base) * rw) / rms;
+      if (first || v > *snr) { *snr = v; *width = w; *bin = j; first = false; }
+    }
+  }
+}
+
+// the peaks section of the header; every check has been made
+void ff_peaks(const frbch_foldfit_params* par, const double* score, const int64_t* pacc, const uint64_t* phits, frbch_foldfit_result* r) {
+  POST_NO_CONTRACT
+  memset(r, 0, sizeof *r);
+  const uint32_t n[3] = {par->ndm, par->nfdot, par->nfreq};                 // in memory order
+  const uint64_t nt = ff_ntrial(par);
+  uint64_t at = 0;
+  for (uint64_t t = 1; t < nt; ++t)
+    if (score[t] > score[at]) at = t;
+  const uint32_t kp = (uint32_t)(at / ((uint64_t)n[1] * n[2])), jp = (uint32_t)((at / n[2]) % n[1]), ip = (uint32_t)(at % n[2]);
+  r->kpeak = kp; r->jpeak = jp; r->ipeak = ip;
+  r->score_peak = score[at];
+  r->score_nominal = score[((uint64_t)(n[0] / 2) * n[1] + n[1] / 2) * n[2] + n[2] / 2];
+  std::vector<double> border;
+  for (uint64_t t = 0; t < nt; ++t) {
+    const uint32_t idx[3] = {(uint32_t)(t / ((uint64_t)n[1] * n[2])), (uint32_t)((t / n[2]) % n[1]), (uint32_t)(t % n[2])};
+    bool edge = false;
+    for (int a = 0; a < 3; ++a)
+      if (n[a] > 1 && (idx[a] == 0 || idx[a] == n[a] - 1)) edge = true;
+    if (edge) border.push_back(score[t]);
+  }
+  if (!border.empty()) {
+    std::sort(border.begin(), border.end());
+    const size_t m = border.size();
+    r->border_median = m % 2 ? border[m / 2] : 0.5 * (border[m / 2 - 1] + border[m / 2]);
+  }
+  const double wide = r->border_median > 0.0 ? sqrt(r->border_median) : 0.0;
+  // the three cuts through the peak: values of the axis, the scores along it, then the parabola of frbch_dmscan_peaks
+  const double step[3] = {par->ddm, par->dfdot, par->dfreq}, origin[3] = {par->dm0, 0.0, 0.0};
+  const uint64_t stride[3] = {(uint64_t)n[1] * n[2], n[2], 1};
+  const uint32_t peak[3] = {kp, jp, ip};
+  double* value[3] = {&r->dm, &r->dfdot, &r->dfreq};
+  double* res[3] = {&r->dm_res, &r->dfdot_res, &r->dfreq_res};
+  uint32_t* fitted[3] = {&r->fitted_dm, &r->fitted_fdot, &r->fitted_freq};
+  uint32_t* nfit[3] = {&r->nfit_dm, &r->nfit_fdot, &r->nfit_freq};
+  for (int a = 0; a < 3; ++a) {
+    std::vector<double> v(n[a]), x(n[a]);
+    for (uint32_t i = 0; i < n[a]; ++i) {
+      v[i] = score[at - (uint64_t)peak[a] * stride[a] + (uint64_t)i * stride[a]];
+      x[i] = origin[a] + ff_axis(i, n[a], step[a]);
+    }
+    uint32_t where = 0;
+    double unit = 0.0;
+    dm_fit(v.data(), n[a], par->fit_frac, x.data(), step[a], &where, nfit[a], fitted[a], value[a], &unit);
+    *res[a] = *fitted[a] ? unit * wide : 0.0;
+  }
+  ff_snr(pacc, phits, par, &r->snr_nominal, &r->width_nominal, &r->bin_nominal);
+  ff_snr(pacc + par->nbin, phits + par->nbin, par, &r->snr_best, &r->width_best, &r->bin_best);
+}
+
+struct FfOut {
+  std::vector<double> score;
+  std::vector<long long> prof, tacc, plane;
+  std::vector<unsigned long long> prof_hits, thits, plane_hits;
+  frbch_foldfit_result res;
+  uint32_t k[2] = {0, 0};
+};
+
+// everything of a call inside its scope: the tables up, stage 1, the totals, stage 2, the two profiles, the peaks
+int ff_run(const frbch_fil_desc* fil, const frbch_foldfit_params* par, const FfPlan& plan, const double* d_cube, const uint32_t* d_hits,
+           bool want_trials, bool want_plane, PostScope& ps, FfOut* out, const PostErr& e) {
+  const size_t nchan = fil->nchan, nbin = par->nbin, nsub = par->nsub, ndm = par->ndm, nspin = (size_t)par->nfdot * par->nfreq;
+  const size_t nt = ndm * nspin, nplane = ndm * nsub * nbin;
+  const FfPlanRule rule = ff_plan_rule(fil, par, d_cube, d_hits);
+  out->k[0] = rule.fast1 ? 1 : 0;
+  out->k[1] = rule.fast2 ? 1 : 0;
+  uint8_t* d_use = nullptr;
+  int32_t *d_shd = nullptr, *d_shp = nullptr, *d_shp2 = nullptr;
+  uint32_t* d_trial = nullptr;
+  long long *d_A = nullptr, *d_totA = nullptr, *d_tacc = nullptr, *d_prof = nullptr;
+  unsigned long long *d_HA = nullptr, *d_totH = nullptr, *d_thits = nullptr, *d_prof_hits = nullptr;
+  double* d_score = nullptr;
+  POST_DEV(ps.alloc(&d_use, nchan), "hipMalloc");
+  POST_DEV(ps.alloc(&d_shd, plan.shd.size() * sizeof(int32_t)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_shp, plan.shp.size() * sizeof(int32_t)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_A, nplane * sizeof(long long)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_HA, nplane * sizeof(unsigned long long)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_totA, ndm * nsub * sizeof(long long)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_totH, ndm * nsub * sizeof(unsigned long long)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_score, nt * sizeof(double)), "hipMalloc");
+  POST_DEV(dev_h2d(d_use, plan.use.data(), nchan, ps.s), "upload the channel mask");
+  POST_DEV(dev_h2d(d_shd, plan.shd.data(), plan.shd.size() * sizeof(int32_t), ps.s), "upload the DM shifts");
+  POST_DEV(dev_h2d(d_shp, plan.shp.data(), plan.shp.size() * sizeof(int32_t), ps.s), "upload the spin shifts");
+  if (want_trials) {
+    POST_DEV(ps.alloc(&d_tacc, nt * nbin * sizeof(long long)), "hipMalloc");
+    POST_DEV(ps.alloc(&d_thits, nt * nbin * sizeof(unsigned long long)), "hipMalloc");
+  }
+  FfParams p;
+  memset(&p, 0, sizeof p);
+  p.cube = d_cube; p.chits = d_hits; p.use = d_use; p.shd = d_shd; p.shp = d_shp;
+  p.A = d_A; p.HA = d_HA; p.totA = d_totA; p.totH = d_totH; p.score = d_score; p.pacc = d_tacc; p.phits = d_thits;
+  p.nchan = (int)nchan; p.nifs = (int)fil->nifs; p.nbin = (int)nbin; p.nsub = (int)nsub; p.ndm = (int)ndm; p.nspin = (int)nspin;
+  p.ntrial = (int)nt; p.products = (int)par->products;
+  p.ngrp = rule.ngrp; p.sc = rule.sc; p.lstride = rule.lstride; p.nrun = rule.nrun;
+  // stage 1
+  bool launched = false;
+#ifndef FRBCH_NO_FAST
+  if (rule.fast1) {
+    if (rule.ngrp > 1) {
+      long long* d_part = nullptr;
+      uint32_t* d_hpart = nullptr;
+      POST_DEV(ps.alloc(&d_part, (size_t)rule.ngrp * nplane * sizeof(long long)), "hipMalloc");
+      POST_DEV(ps.alloc(&d_hpart, (size_t)rule.ngrp * nplane * sizeof(uint32_t)), "hipMalloc");
+      p.part = d_part; p.hpart = d_hpart;
+    }
+    const dim3 grid((unsigned)((ndm + fast::kFfND - 1) / fast::kFfND), (unsigned)rule.ngrp, (unsigned)nsub), block(fast::kFfThreads);
+    const size_t lds = (size_t)2 * fast::kFfCT * rule.lstride * sizeof(uint32_t);
+    int lrc;
+    switch (rule.bpt1) {
+      case 1: lrc = launch_lds(fast::frbch_post_ff_dm_fast<1>, grid, block, lds, ps.s, p); break;
+      case 2: lrc = launch_lds(fast::frbch_post_ff_dm_fast<2>, grid, block, lds, ps.s, p); break;
+      default: lrc = launch_lds(fast::frbch_post_ff_dm_fast<4>, grid, block, lds, ps.s, p); break;
+    }
+    POST_DEV(lrc, "LDS size");
+    POST_DEV(dev_check_launch(), "launch fold refinement, stage 1");
+    if (rule.ngrp > 1) {
+      hipLaunchKernelGGL(fast::frbch_post_ff_dm_join, dim3((unsigned)((nplane + fast::kFfThreads - 1) / fast::kFfThreads)), dim3(fast::kFfThreads), 0, ps.s, p);
+      POST_DEV(dev_check_launch(), "launch fold refinement, join");
+    }
+    launched = true;
+  }
+#endif
+  if (!launched) {
+    DEV_LAUNCH(frbch_post_ff_dm, (nplane + 255) / 256, 1, 256, 0, ps.s, p);
+    POST_DEV(dev_check_launch(), "launch fold refinement, stage 1");
+  }
+  DEV_LAUNCH(frbch_post_ff_tot, (ndm * nsub + 255) / 256, 1, 256, 0, ps.s, p);
+  POST_DEV(dev_check_launch(), "launch fold refinement, totals");
+  // stage 2
+  launched = false;
+#ifndef FRBCH_NO_FAST
+  if (rule.fast2) {
+    const dim3 grid((unsigned)(ndm * (size_t)rule.nrun)), block(fast::kFfThreads);
+    int lrc;
+    switch (rule.bpt2) {
+      case 1: lrc = launch_lds(fast::frbch_post_ff_spin_fast<1>, grid, block, fast::kFfLds2, ps.s, p); break;
+      case 2: lrc = launch_lds(fast::frbch_post_ff_spin_fast<2>, grid, block, fast::kFfLds2, ps.s, p); break;
+      case 4: lrc = launch_lds(fast::frbch_post_ff_spin_fast<4>, grid, block, fast::kFfLds2, ps.s, p); break;
+      case 8: lrc = launch_lds(fast::frbch_post_ff_spin_fast<8>, grid, block, fast::kFfLds2, ps.s, p); break;
+      default: lrc = launch_lds(fast::frbch_post_ff_spin_fast<16>, grid, block, fast::kFfLds2, ps.s, p); break;
+    }
+    POST_DEV(lrc, "LDS size");
+    POST_DEV(dev_check_launch(), "launch fold refinement, stage 2");
+    launched = true;
+  }
+#endif
+  if (!launched) {
+    DEV_LAUNCH(frbch_post_ff_spin, (nt + 255) / 256, 1, 256, 0, ps.s, p);
+    POST_DEV(dev_check_launch(), "launch fold refinement, stage 2");
+  }
+  out->score.resize(nt);
+  POST_DEV(dev_d2h(out->score.data(), d_score, nt * sizeof(double), ps.s), "download the scores");
+  if (want_trials) {
+    out->tacc.resize(nt * nbin);
+    out->thits.resize(nt * nbin);
+    POST_DEV(dev_d2h(out->tacc.data(), d_tacc, nt * nbin * sizeof(long long), ps.s), "download the trial profiles");
+    POST_DEV(dev_d2h(out->thits.data(), d_thits, nt * nbin * sizeof(unsigned long long), ps.s), "download the trial profiles");
+  }
+  if (want_plane) {
+    out->plane.resize(nsub * nbin);
+    out->plane_hits.resize(nsub * nbin);
+    const size_t at = (ndm / 2) * nsub * nbin;
+    POST_DEV(dev_d2h(out->plane.data(), d_A + at, nsub * nbin * sizeof(long long), ps.s), "download the phase-time plane");
+    POST_DEV(dev_d2h(out->plane_hits.data(), d_HA + at, nsub * nbin * sizeof(unsigned long long), ps.s), "download the phase-time plane");
+  }
+  POST_DEV(dev_sync(ps.s), "sync");
+  // the profiles of the nominal and of the peak trial
+  size_t best = 0;
+  for (size_t t = 1; t < nt; ++t)
+    if (out->score[t] > out->score[best]) best = t;
+  const uint32_t two[2] = {(uint32_t)((ndm / 2) * nspin + ((size_t)(par->nfdot / 2) * par->nfreq + par->nfreq / 2)), (uint32_t)best};
+  std::vector<int32_t> shp2(2 * nsub);
+  for (int t = 0; t < 2; ++t)
+    memcpy(shp2.data() + (size_t)t * nsub, plan.shp.data() + (size_t)(two[t] % nspin) * nsub, nsub * sizeof(int32_t));
+  POST_DEV(ps.alloc(&d_shp2, shp2.size() * sizeof(int32_t)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_trial, sizeof two), "hipMalloc");
+  POST_DEV(ps.alloc(&d_prof, 2 * nbin * sizeof(long long)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_prof_hits, 2 * nbin * sizeof(unsigned long long)), "hipMalloc");
+  POST_DEV(dev_h2d(d_shp2, shp2.data(), shp2.size() * sizeof(int32_t), ps.s), "upload the spin shifts");
+  POST_DEV(dev_h2d(d_trial, two, sizeof two, ps.s), "upload the trial list");
+  p.shp = d_shp2; p.trial = d_trial; p.ntrial = 2; p.score = nullptr; p.pacc = d_prof; p.phits = d_prof_hits;
+  DEV_LAUNCH(frbch_post_ff_prof, (2 * nbin + 255) / 256, 1, 256, 0, ps.s, p);
+  POST_DEV(dev_check_launch(), "launch fold refinement, profiles");
+  out->prof.resize(2 * nbin);
+  out->prof_hits.resize(2 * nbin);
+  POST_DEV(dev_d2h(out->prof.data(), d_prof, 2 * nbin * sizeof(long long), ps.s), "download the profiles");
+  POST_DEV(dev_d2h(out->prof_hits.data(), d_prof_hits, 2 * nbin * sizeof(unsigned long long), ps.s), "download the profiles");
+  POST_DEV(dev_sync(ps.s), "sync");
+  ff_peaks(par, out->score.data(), (const int64_t*)out->prof.data(), (const uint64_t*)out->prof_hits.data(), &out->res);
+  return FRBCH_OK;
+}
+
+// the arguments of frbch_foldfit_device / _host behind the cube
+int ff_check_outputs(const frbch_foldfit_params* par, const void* cube, const void* hits, const void* score, const void* pacc, const void* phits,
+                     const void* result, const void* tacc, const void* thits, const void* plane, const void* plane_hits, const PostErr& e) {
+  if (!cube || !hits || !score || !pacc || !phits || !result) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((tacc == nullptr) != (thits == nullptr)) return e.fail(FRBCH_E_ARG, "trial_acc and trial_hits come together");
+  if ((plane == nullptr) != (plane_hits == nullptr)) return e.fail(FRBCH_E_ARG, "plane_acc and plane_hits come together");
+  if (tacc && ff_ntrial(par) * par->nbin > kFfMaxProf) return e.fail(FRBCH_E_ARG, "the trial profiles exceed 2^24 elements: ask for the scores alone");
+  return FRBCH_OK;
+}
+}  // namespace
+
+extern "C" int frbch_foldfit_steps(const frbch_fil_desc* fil, uint64_t nrows, uint32_t nbin, double f0_fold, double* ddm, double* dfreq,
+                                   double* dfdot) {
+  POST_NO_CONTRACT
+  PostErr e{nullptr, 0};
+  if (post_check_fil(fil, nrows, e) || nbin < 2 || !(f0_fold > 0)) return FRBCH_E_ARG;
+  const double T = (double)nrows * fil->tsamp_s;
+  if (dfreq) *dfreq = 1.0 / ((double)nbin * T);
+  if (dfdot) *dfdot = 8.0 / (((double)nbin * T) * T);
+  if (ddm) {
+    const double d = post_delay_s(fil, 1.0, fil->foff_mhz < 0 ? fil->nchan - 1 : 0);     // seconds per unit DM across the band
+    *ddm = d > 0.0 ? 1.0 / (((double)nbin * f0_fold) * d) : 0.0;
+  }
+  return FRBCH_OK;
+}
+
+extern "C" int frbch_foldfit_kernel(const frbch_fil_desc* fil, uint64_t nrows, const frbch_foldfit_params* par, const double* d_cube,
+                                    const uint32_t* d_hits, uint32_t* kernel) {
+  PostErr e{nullptr, 0};
+  const int rc = ff_check(fil, nrows, par, e);
+  if (rc) return rc;
+  if (!d_cube || !d_hits || !kernel) return FRBCH_E_ARG;
+  const FfPlanRule rule = ff_plan_rule(fil, par, d_cube, d_hits);
+  kernel[0] = rule.fast1 ? 1 : 0;
+  kernel[1] = rule.fast2 ? 1 : 0;
+  return FRBCH_OK;
+}
+
+extern "C" int frbch_foldfit_device(const frbch_fil_desc* fil, uint64_t nrows, const frbch_foldfit_params* par, const double* d_cube,
+                                    const uint32_t* d_hits, const uint8_t* flag, int device, double* score, int64_t* prof_acc,
+                                    uint64_t* prof_hits, frbch_foldfit_result* result, int64_t* trial_acc, uint64_t* trial_hits,
+                                    int64_t* plane_acc, uint64_t* plane_hits, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  static_assert(sizeof(frbch_foldfit_params) == 120 && sizeof(frbch_foldfit_result) == 144 && sizeof(long long) == sizeof(int64_t), "fold refinement records");
+  PostErr e{err, err_cap};
+  int rc = ff_check(fil, nrows, par, e);
+  if (rc) return rc;
+  if ((rc = ff_check_outputs(par, d_cube, d_hits, score, prof_acc, prof_hits, result, trial_acc, trial_hits, plane_acc, plane_hits, e)) != 0) return rc;
+  FfPlan plan;
+  if ((rc = ff_build(fil, nrows, par, flag, &plan, e)) != 0) return rc;
+  FfOut out;
+  rc = burst_device_call(device, e, [&](PostScope& ps) { return ff_run(fil, par, plan, d_cube, d_hits, trial_acc != nullptr, plane_acc != nullptr, ps, &out, e); });
+  if (rc) return rc;
+  deliver(score, out.score);
+  deliver(prof_acc, out.prof);
+  deliver(prof_hits, out.prof_hits);
+  deliver(trial_acc, out.tacc);
+  deliver(trial_hits, out.thits);
+  deliver(plane_acc, out.plane);
+  deliver(plane_hits, out.plane_hits);
+  *result = out.res;
+  deliver(kernel_used, out.k);
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_foldfit_host(const frbch_fil_desc* fil, uint64_t nrows, const frbch_foldfit_params* par, const double* cube,
+                                  const uint32_t* hits, const uint8_t* flag, int device, double* score, int64_t* prof_acc,
+                                  uint64_t* prof_hits, frbch_foldfit_result* result, int64_t* trial_acc, uint64_t* trial_hits,
+                                  int64_t* plane_acc, uint64_t* plane_hits, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  int rc = ff_check(fil, nrows, par, e);
+  if (rc) return rc;
+  if ((rc = ff_check_outputs(par, cube, hits, score, prof_acc, prof_hits, result, trial_acc, trial_hits, plane_acc, plane_hits, e)) != 0) return rc;
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  const size_t nslot = (size_t)par->nsub * par->nbin * fil->nchan;
+  HostStage hs;
+  const double* d_cube = hs.in(cube, nslot * fil->nifs * sizeof(double));
+  const uint32_t* d_hits = hs.in(hits, nslot * sizeof(uint32_t));
+  return hs.run(e, "device memory for the cube", "upload the cube", "download", [&]() {
+    return frbch_foldfit_device(fil, nrows, par, d_cube, d_hits, flag, device, score, prof_acc, prof_hits, result, trial_acc, trial_hits, plane_acc,
+                                plane_hits, kernel_used, err, err_cap);
+  });
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_foldfit_peaks(const frbch_foldfit_params* par, const double* score, const int64_t* prof_acc, const uint64_t* prof_hits,
+                                   frbch_foldfit_result* result, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  if (!par || par->size != sizeof(frbch_foldfit_params)) return e.fail(FRBCH_E_ARG, "frbch_foldfit_params: wrong size");
+  if (par->nbin < 2 || par->nbin > kFfMaxBin) return e.fail(FRBCH_E_ARG, "nbin must be 2..4096");
+  if (par->ndm < 1 || par->nfreq < 1 || par->nfdot < 1 || ff_ntrial(par) > kFfMaxTrial) return e.fail(FRBCH_E_ARG, "ndm * nfdot * nfreq exceeds 2^22");
+  if (!(par->fit_frac > 0) || !(par->fit_frac <= 1)) return e.fail(FRBCH_E_ARG, "fit_frac must lie in (0, 1]");
+  if (par->nwidth < 1 || par->nwidth > 8) return e.fail(FRBCH_E_ARG, "nwidth must be 1..8");
+  for (uint32_t w = 0; w < par->nwidth; ++w)
+    if (par->widths[w] < 1 || par->widths[w] > par->nbin / 2) return e.fail(FRBCH_E_ARG, "a width outside 1..nbin / 2");
+  if (!score || !prof_acc || !prof_hits || !result) return e.fail(FRBCH_E_ARG, "null argument");
+  frbch_foldfit_result r;
+  ff_peaks(par, score, prof_acc, prof_hits, &r);
+  *result = r;
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_fold_refine_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_fold_model* model,
+                                        const frbch_foldfit_params* par, const uint8_t* flag, int device, double* cube, uint32_t* cube_hits,
+                                        double* score, int64_t* prof_acc, uint64_t* prof_hits, frbch_foldfit_result* result,
+                                        int64_t* plane_acc, uint64_t* plane_hits, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  int rc = ff_check(fil, nrows, par, e);
+  if (rc) return rc;
+  if (!model || model->size != sizeof(frbch_fold_model)) return e.fail(FRBCH_E_ARG, "frbch_fold_model: wrong size");
+  if (model->apply_delays) return e.fail(FRBCH_E_ARG, "a fold with apply_delays: the search shifts the channels itself, fold without per-channel delays");
+  if (model->nbin != par->nbin || model->subint_s != par->subint_s) return e.fail(FRBCH_E_ARG, "the model and the search differ in nbin or subint_s");
+  if (!d_rows || !score || !prof_acc || !prof_hits || !result) return e.fail(FRBCH_E_ARG, "null argument");
+  if ((plane_acc == nullptr) != (plane_hits == nullptr)) return e.fail(FRBCH_E_ARG, "plane_acc and plane_hits come together");
+  {                                                        // the refusals that only the tables show, before anything is written
+    FfPlan probe;
+    if ((rc = ff_build(fil, nrows, par, flag, &probe, e)) != 0) return rc;
+  }
+  if ((rc = post_check_device(device, e)) != 0) return rc;
+  DeviceGuard dg(device);
+  PostScope ps(false);                                     // holds the cube between the two stages
+  if (!ps.s) return e.fail(FRBCH_E_DEVICE, "hipStreamCreate");
+  const size_t nslot = (size_t)par->nsub * par->nbin * fil->nchan;
+  double* d_cube = nullptr;
+  uint32_t* d_chits = nullptr;
+  POST_DEV(ps.alloc(&d_cube, nslot * fil->nifs * sizeof(double)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_chits, nslot * sizeof(uint32_t)), "hipMalloc");
+  uint32_t k[3] = {0, 0, 0};
+  if ((rc = frbch_foldp_device(fil, d_rows, nrows, model, device, d_cube, d_chits, par->nsub, &k[0], err, err_cap)) != 0) return rc;
+  if (cube) POST_DEV(dev_d2h(cube, d_cube, nslot * fil->nifs * sizeof(double), ps.s), "download the cube");
+  if (cube_hits) POST_DEV(dev_d2h(cube_hits, d_chits, nslot * sizeof(uint32_t), ps.s), "download the cube");
+  POST_DEV(dev_sync(ps.s), "sync");                        // (the results below are written last, and only by a call that succeeds)
+  if ((rc = frbch_foldfit_device(fil, nrows, par, d_cube, d_chits, flag, device, score, prof_acc, prof_hits, result, nullptr, nullptr, plane_acc,
+                                 plane_hits, &k[1], err, err_cap)) != 0) return rc;
+  deliver(kernel_used, k);
+  return FRBCH_OK;
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+
+extern "C" int frbch_fold_refine_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_fold_model* model,
+                                      const frbch_foldfit_params* par, const uint8_t* flag, int device, double* cube, uint32_t* cube_hits,
+                                      double* score, int64_t* prof_acc, uint64_t* prof_hits, frbch_foldfit_result* result,
+                                      int64_t* plane_acc, uint64_t* plane_hits, uint32_t* kernel_used, char* err, size_t err_cap) try {
+  PostErr e{err, err_cap};
+  const int rc = ff_check(fil, nrows, par, e);
+  if (rc) return rc;
+  if (!rows) return e.fail(FRBCH_E_ARG, "null argument");
+  return burst_host_twin(fil, rows, nrows, device, e, [&](void* d_rows) {
+    return frbch_fold_refine_device(fil, d_rows, nrows, model, par, flag, device, cube, cube_hits, score, prof_acc, prof_hits, result, plane_acc,
+                                    plane_hits, kernel_used, err, err_cap);
+  });
+} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }

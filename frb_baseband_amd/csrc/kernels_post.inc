@@ -1609,3 +1609,165 @@ KERNEL(frbch_post_tbank, TbankParams) {
     }
   }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Refinement of a fold (frbch_foldfit_*; include/frbch.h states the arithmetic): the folded cube of frbch_foldp_* is shifted
+// per channel over a run of DMs (stage 1) and per sub-integration over a grid of spin offsets (stage 2), in exact integers,
+// and every trial profile is scored in double with a fixed summation order.  The integer sums are exact in any order, the
+// score goes through ff_term and the 64 partial sums of the header, so the generic kernels below and the fast ones
+// (kernels_post_fast.inc) differ in schedule only.
+// ---------------------------------------------------------------------------------------------------------------------
+struct FfParams {
+  const double* cube;          // [nsub][nifs][nbin][nchan], exact integers (frbch_foldp_*)
+  const uint32_t* chits;       // [nsub][nbin][nchan]
+  const uint8_t* use;          // [nchan]: 1 = the channel is added
+  const int32_t* shd;          // [ndm][nchan], 0 .. nbin - 1
+  const int32_t* shp;          // [nspin][nsub]: (-shP) mod nbin, 0 .. nbin - 1 (frbch_post_ff_prof: [ntrial][nsub], the listed trials')
+  const uint32_t* trial;       // frbch_post_ff_prof: [ntrial], a listed trial as dm * nspin + spin
+  long long* A;                // [ndm][nsub][nbin]
+  unsigned long long* HA;      // [ndm][nsub][nbin]
+  long long* totA;             // [ndm][nsub]: the sum of A over the bins
+  unsigned long long* totH;    // [ndm][nsub]
+  double* score;               // [ntrial] or NULL
+  long long* pacc;             // [ntrial][nbin] or NULL: the trial profiles
+  unsigned long long* phits;   // [ntrial][nbin] or NULL
+  long long* part;             // fast stage 1 with ngrp > 1: [ngrp][ndm][nsub][nbin]
+  uint32_t* hpart;             // the same shape
+  int nchan, nifs, nbin, nsub, ndm, nspin, ntrial, products;   // nspin = nfdot * nfreq
+  int ngrp, sc, lstride, nrun;                                  // fast kernels: the plan (ff_plan_rule)
+};
+
+// the masked products of one (sub-integration, bin, channel)
+DEVFN inline long long ff_sample(const FfParams& p, int s, int b, int c) {
+  long long v = 0;
+  for (int q = 0; q < p.nifs; ++q)
+    if ((p.products >> q) & 1) v += (long long)p.cube[(((size_t)s * p.nifs + q) * p.nbin + b) * p.nchan + c];
+  return v;
+}
+
+// stage 1: grid (ceil(ndm nsub nbin / 256)), one thread per (DM, sub-integration, bin), channels ascending
+KERNEL(frbch_post_ff_dm, FfParams) {
+  K_PROLOGUE;
+  (void)smem; (void)by;
+  PHASE {
+    const long long idx = (long long)bx * nthr + tid;
+    if (idx < (long long)p.ndm * p.nsub * p.nbin) {
+      const int b = (int)(idx % p.nbin);
+      const int s = (int)((idx / p.nbin) % p.nsub);
+      const int32_t* sh = p.shd + (size_t)(idx / ((long long)p.nbin * p.nsub)) * p.nchan;
+      long long a = 0;
+      unsigned long long h = 0;
+      for (int c = 0; c < p.nchan; ++c) {
+        if (!p.use[c]) continue;
+        int j = b + sh[c];
+        if (j >= p.nbin) j -= p.nbin;
+        a += ff_sample(p, s, j, c);
+        h += p.chits[((size_t)s * p.nbin + j) * p.nchan + c];
+      }
+      p.A[idx] = a;
+      p.HA[idx] = h;
+    }
+  }
+}
+
+// the totals of a (DM, sub-integration): grid (ceil(ndm nsub / 256)), one thread each; both forms run it
+KERNEL(frbch_post_ff_tot, FfParams) {
+  K_PROLOGUE;
+  (void)smem; (void)by;
+  PHASE {
+    const long long idx = (long long)bx * nthr + tid;
+    if (idx < (long long)p.ndm * p.nsub) {
+      const long long* a = p.A + (size_t)idx * p.nbin;
+      const unsigned long long* h = p.HA + (size_t)idx * p.nbin;
+      long long ta = 0;
+      unsigned long long th = 0;
+      for (int b = 0; b < p.nbin; ++b) { ta += a[b]; th += h[b]; }
+      p.totA[idx] = ta;
+      p.totH[idx] = th;
+    }
+  }
+}
+
+// the part of one bin in the score of a trial (0 for a bin without hits, which leaves every partial sum as it is)
+DEVFN inline double ff_term(long long B, unsigned long long H, double M) {
+  POST_NO_CONTRACT
+  if (!H) return 0.0;
+  const double x = (double)B / (double)H;
+  const double d = x - M;
+  const double dd = d * d;
+  return (double)H * dd;
+}
+
+// M of a DM from the totals of its sub-integrations; *any = 0: no hit at all
+DEVFN inline double ff_mean(const FfParams& p, int k, int* any) {
+  POST_NO_CONTRACT
+  long long ta = 0;
+  unsigned long long th = 0;
+  for (int s = 0; s < p.nsub; ++s) { ta += p.totA[(size_t)k * p.nsub + s]; th += p.totH[(size_t)k * p.nsub + s]; }
+  *any = th != 0;
+  return th ? (double)ta / (double)th : 0.0;
+}
+
+// B and H of one bin of a trial
+DEVFN inline void ff_bin(const FfParams& p, int k, const int32_t* sh, int b, long long* B, unsigned long long* H) {
+  long long a = 0;
+  unsigned long long h = 0;
+  for (int s = 0; s < p.nsub; ++s) {
+    int j = b + sh[s];
+    if (j >= p.nbin) j -= p.nbin;
+    const size_t at = ((size_t)k * p.nsub + s) * p.nbin + j;
+    a += p.A[at];
+    h += p.HA[at];
+  }
+  *B = a;
+  *H = h;
+}
+
+// stage 2: grid (ceil(ntrial / 256)), one thread per trial; the 64 partial sums one after the other, each over its bins
+// ascending, added as they are finished (ascending q)
+KERNEL(frbch_post_ff_spin, FfParams) {
+  K_PROLOGUE;
+  (void)smem; (void)by;
+  PHASE {
+    POST_NO_CONTRACT
+    const long long t = (long long)bx * nthr + tid;
+    if (t < (long long)p.ntrial) {
+      const int k = (int)(t / p.nspin);
+      const int32_t* sh = p.shp + (size_t)(t % p.nspin) * p.nsub;
+      int any = 0;
+      const double M = ff_mean(p, k, &any);
+      double sum = 0.0;
+      int nhit = 0;
+      for (int q = 0; q < 64; ++q) {
+        double part = 0.0;
+        for (int b = q; b < p.nbin; b += 64) {
+          long long B;
+          unsigned long long H;
+          ff_bin(p, k, sh, b, &B, &H);
+          if (p.pacc) { p.pacc[(size_t)t * p.nbin + b] = B; p.phits[(size_t)t * p.nbin + b] = H; }
+          if (H) ++nhit;
+          part = part + ff_term(B, H, M);
+        }
+        sum = sum + part;
+      }
+      if (p.score) p.score[t] = any && nhit >= 2 ? sum : 0.0;
+    }
+  }
+}
+
+// the profiles of a short list of trials (the nominal and the best one): grid (ceil(ntrial nbin / 256)), one thread per (trial, bin)
+KERNEL(frbch_post_ff_prof, FfParams) {
+  K_PROLOGUE;
+  (void)smem; (void)by;
+  PHASE {
+    const long long idx = (long long)bx * nthr + tid;
+    if (idx < (long long)p.ntrial * p.nbin) {
+      const long long t = idx / p.nbin;
+      long long B;
+      unsigned long long H;
+      ff_bin(p, (int)(p.trial[t] / (uint32_t)p.nspin), p.shp + (size_t)t * p.nsub, (int)(idx % p.nbin), &B, &H);
+      p.pacc[idx] = B;
+      p.phits[idx] = H;
+    }
+  }
+}

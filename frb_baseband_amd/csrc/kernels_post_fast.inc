@@ -1723,3 +1723,193 @@ __global__ void __launch_bounds__(kTbThreads) frbch_post_tbank_fast(TbankParams 
   }
 }
 }  // namespace fast
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Refinement of a fold (HIP only; frbch_post_ff_dm / frbch_post_ff_spin of kernels_post.inc stay the emulable forms and the
+// fallback; the sums are exact integers and the score goes through ff_term, ff_mean and the 64 partial sums of the header).
+//
+// Stage 1, frbch_post_ff_dm_fast: per sub-integration a dedispersion with circular time.  A workgroup owns (a run of
+// kFfTileRun channel tiles, kFfND consecutive DMs, one sub-integration).  A tile is 8 channels -- 64 bytes of every cube row
+// -- of all nbin bins, read coalesced along the channels, the masked products added and converted to uint32 on the way,
+// transposed into the LDS as val[channel][bin] and hit[channel][bin] with rows lstride = 32 ceil(nbin / 32) + 4 words apart:
+// the 32 lanes of a ds_write group (4 bins x 8 channels) land on 32 banks, and in the main loop consecutive lanes read
+// consecutive words (65792 bytes at 1024 bins: a little above 64 KiB, so the launch asks for its dynamic LDS).  A thread keeps BPT bins x kFfND DMs in registers (3 VGPRs each: 96 at BPT = 4).  The host's plan rule
+// (ff_plan_rule) holds the sums to uint32: (2^nbits - 1) products L < 2^32 and L nchan < 2^32, L the rows of a
+// sub-integration -- a cube of frbch_foldp_* has 0 <= P <= (2^nbits - 1) hits and hits <= L.  With more than one run of
+// tiles the partial sums go to part / hpart and frbch_post_ff_dm_join adds them: no global atomics.
+//
+// Stage 2, frbch_post_ff_spin_fast: a workgroup owns (one DM, a run of R = 32 / BPT spin trials) and walks the
+// sub-integrations in chunks of p.sc, whose A (int64) and HA (uint32, the same bound) lie in 64 KiB of LDS; a thread keeps
+// BPT bins x R trials of B and H in registers (4 VGPRs each: 128).  Then the stage is reused for the terms of the score,
+// term[trial][bin], which 64 threads a trial add into the partial sums in the order of the header, and one thread a trial
+// adds those: only the score leaves the chip (and the profiles, where the caller asked for them).
+// ---------------------------------------------------------------------------------------------------------------------
+namespace fast {
+constexpr int kFfThreads = 256, kFfCT = 8, kFfND = 8, kFfTileRun = 32, kFfMaxBin1 = 1024, kFfElems = 32;
+constexpr size_t kFfStage2 = 64 * 1024;                                    // the sub-integration chunk, then the terms
+constexpr size_t kFfLds2 = kFfStage2 + (size_t)kFfElems * 64 * sizeof(double) + kFfElems * sizeof(int);
+
+template <int BPT>
+__global__ void __launch_bounds__(kFfThreads) frbch_post_ff_dm_fast(FfParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint32_t* val = reinterpret_cast<uint32_t*>(smem);                       // [kFfCT][lstride]
+  uint32_t* hit = val + kFfCT * p.lstride;                                 // [kFfCT][lstride]
+  const int tid = threadIdx.x, s = blockIdx.z, k0 = blockIdx.x * kFfND, grp = blockIdx.y;      // grid (DM runs, tile runs, nsub)
+  const int ntile = p.nchan / kFfCT;
+  const int t0 = grp * kFfTileRun, t1 = min(ntile, t0 + kFfTileRun);
+  unsigned long long a[kFfND][BPT];
+  uint32_t h[kFfND][BPT];
+#pragma unroll
+  for (int d = 0; d < kFfND; ++d)
+#pragma unroll
+    for (int m = 0; m < BPT; ++m) { a[d][m] = 0; h[d][m] = 0; }
+  for (int tile = t0; tile < t1; ++tile) {
+    const int c0 = tile * kFfCT;
+    __syncthreads();                                                       // the previous tile is consumed
+    for (int i = tid; i < p.nbin * kFfCT; i += kFfThreads) {
+      const int c = i & (kFfCT - 1), b = i / kFfCT;
+      uint32_t v = 0, hh = 0;
+      if (p.use[c0 + c]) {
+        for (int q = 0; q < p.nifs; ++q)
+          if ((p.products >> q) & 1) v += (uint32_t)(long long)p.cube[(((size_t)s * p.nifs + q) * p.nbin + b) * p.nchan + c0 + c];
+        hh = p.chits[((size_t)s * p.nbin + b) * p.nchan + c0 + c];
+      }
+      val[c * p.lstride + b] = v;
+      hit[c * p.lstride + b] = hh;
+    }
+    __syncthreads();
+    for (int c = 0; c < kFfCT; ++c) {
+      const uint32_t* vr = val + c * p.lstride;
+      const uint32_t* hr = hit + c * p.lstride;
+#pragma unroll
+      for (int d = 0; d < kFfND; ++d) {
+        const int k = min(k0 + d, p.ndm - 1);                              // (a run past ndm repeats the last DM, never stored)
+        const int sh = p.shd[(size_t)k * p.nchan + c0 + c];
+#pragma unroll
+        for (int m = 0; m < BPT; ++m) {
+          const int b = tid + m * kFfThreads;
+          if (b < p.nbin) {
+            int j = b + sh;
+            if (j >= p.nbin) j -= p.nbin;
+            a[d][m] += vr[j];
+            h[d][m] += hr[j];
+          }
+        }
+      }
+    }
+  }
+  const size_t plane = (size_t)p.ndm * p.nsub * p.nbin;
+#pragma unroll
+  for (int d = 0; d < kFfND; ++d)
+#pragma unroll
+    for (int m = 0; m < BPT; ++m) {
+      const int b = tid + m * kFfThreads;
+      if (k0 + d < p.ndm && b < p.nbin) {
+        const size_t at = ((size_t)(k0 + d) * p.nsub + s) * p.nbin + b;
+        if (p.ngrp == 1) {
+          p.A[at] = (long long)a[d][m];
+          p.HA[at] = h[d][m];
+        } else {
+          p.part[(size_t)grp * plane + at] = (long long)a[d][m];
+          p.hpart[(size_t)grp * plane + at] = h[d][m];
+        }
+      }
+    }
+}
+
+// grid (ceil(ndm nsub nbin / 256)), one thread per element of A: the runs of tiles ascending
+__global__ void __launch_bounds__(kFfThreads) frbch_post_ff_dm_join(FfParams p) {
+  const size_t plane = (size_t)p.ndm * p.nsub * p.nbin;
+  const size_t at = (size_t)blockIdx.x * kFfThreads + threadIdx.x;
+  if (at >= plane) return;
+  long long a = 0;
+  unsigned long long h = 0;
+  for (int g = 0; g < p.ngrp; ++g) { a += p.part[(size_t)g * plane + at]; h += p.hpart[(size_t)g * plane + at]; }
+  p.A[at] = a;
+  p.HA[at] = h;
+}
+
+template <int BPT>
+__global__ void __launch_bounds__(kFfThreads) frbch_post_ff_spin_fast(FfParams p) {
+  POST_NO_CONTRACT
+  constexpr int R = kFfElems / BPT;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  long long* As = reinterpret_cast<long long*>(smem);                      // [sc][nbin]
+  uint32_t* Hs = reinterpret_cast<uint32_t*>(As + (size_t)p.sc * p.nbin);  // [sc][nbin]
+  double* term = reinterpret_cast<double*>(smem);                          // [R][nbin], once the sums are done
+  double* parts = reinterpret_cast<double*>(smem + kFfStage2);             // [R][64]
+  int* cnt = reinterpret_cast<int*>(parts + kFfElems * 64);                // [R]: bins with hits
+  const int tid = threadIdx.x, k = blockIdx.x / p.nrun, r0 = (blockIdx.x % p.nrun) * R;       // grid (ndm * runs of trials)
+  long long B[R][BPT];
+  unsigned long long H[R][BPT];
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int m = 0; m < BPT; ++m) { B[r][m] = 0; H[r][m] = 0; }
+  for (int s0 = 0; s0 < p.nsub; s0 += p.sc) {
+    const int ns = min(p.sc, p.nsub - s0);
+    const size_t base = ((size_t)k * p.nsub + s0) * p.nbin;
+    __syncthreads();                                                       // the previous chunk is consumed
+    for (int i = tid; i < ns * p.nbin; i += kFfThreads) {
+      As[i] = p.A[base + i];
+      Hs[i] = (uint32_t)p.HA[base + i];
+    }
+    __syncthreads();
+    for (int si = 0; si < ns; ++si) {
+      const long long* ar = As + (size_t)si * p.nbin;
+      const uint32_t* hr = Hs + (size_t)si * p.nbin;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int sp = min(r0 + r, p.nspin - 1);                           // (a run past nspin repeats the last trial, never stored)
+        const int sh = p.shp[(size_t)sp * p.nsub + s0 + si];
+#pragma unroll
+        for (int m = 0; m < BPT; ++m) {
+          const int b = tid + m * kFfThreads;
+          if (b < p.nbin) {
+            int j = b + sh;
+            if (j >= p.nbin) j -= p.nbin;
+            B[r][m] += ar[j];
+            H[r][m] += hr[j];
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();                                                         // the stage is consumed: it holds the terms from here
+  if (tid < R) cnt[tid] = 0;
+  __syncthreads();
+  int any = 0;
+  const double M = ff_mean(p, k, &any);
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    int n = 0;
+#pragma unroll
+    for (int m = 0; m < BPT; ++m) {
+      const int b = tid + m * kFfThreads;
+      if (b < p.nbin) {
+        term[(size_t)r * p.nbin + b] = ff_term(B[r][m], H[r][m], M);
+        if (H[r][m]) ++n;
+        if (p.pacc && r0 + r < p.nspin) {
+          const size_t at = ((size_t)k * p.nspin + r0 + r) * p.nbin + b;
+          p.pacc[at] = B[r][m];
+          p.phits[at] = H[r][m];
+        }
+      }
+    }
+    if (n) atomicAdd(&cnt[r], n);                                          // (an LDS counter)
+  }
+  __syncthreads();
+  for (int job = tid; job < R * 64; job += kFfThreads) {
+    const int r = job >> 6, q = job & 63;
+    double part = 0.0;
+    for (int b = q; b < p.nbin; b += 64) part = part + term[(size_t)r * p.nbin + b];
+    parts[job] = part;
+  }
+  __syncthreads();
+  if (tid < R && r0 + tid < p.nspin) {
+    double sum = 0.0;
+    for (int q = 0; q < 64; ++q) sum = sum + parts[tid * 64 + q];
+    p.score[(size_t)k * p.nspin + r0 + tid] = any && cnt[tid] >= 2 ? sum : 0.0;
+  }
+}
+}  // namespace fast

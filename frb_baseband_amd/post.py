@@ -1062,7 +1062,7 @@ def group_accel(cands, dm_gap: int = 2, acc_gap: int = 1, lib=None) -> np.ndarra
 
 def psearch_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, zerodm=True, clip=5, sigma=6.0, nharm=16, flo=0.5, nfft=0, wblock=128,
                 dm_gap=2, max_cands=0, fold_best=0, device=0, lib=None, info: dict | None = None, flag_file=None, rfi=None,
-                periodic=None, amax=0.0, astep=0.0, acc_gap=1):
+                periodic=None, amax=0.0, astep=0.0, acc_gap=1, refine=False):
     """Dedisperse a filterbank over the DMs of ``prepdata_gpu`` and search every series for periodic signals in one library
     call (frbch_dedisperse_psearch_host: the DM x time plane never leaves the GPU), then join the records across DMs.
     Writes ``<base>_psearch.txt`` (one line per candidate: period, frequency, DM, sigma, harmonics summed, members and DM span)
@@ -1070,6 +1070,8 @@ def psearch_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, zerodm=True, clip=5, sig
     ``search_fil``.  ``max_cands`` > 0 keeps the strongest N candidates.  ``fold_best`` = K folds the K strongest candidates
     with the ephemeris {F0 = the candidate's frequency, F1 = 0, DM = its trial DM, PEPOCH = tstart} through ``fold_fil``'s
     machinery; their outputs are ``<base>_psearch_cand<i>.ar`` / ``.profile.txt`` / ``.png``.
+    ``refine``: every folded candidate also goes through ``foldfit_fil`` (``<base>_psearch_cand<i>_foldfit.*``): a frequency known
+    to half a Fourier bin lets the pulse drift by up to half a turn over the observation.
     ``amax`` > 0 adds trial accelerations ``acc_list(amax, astep)`` (m/s^2; ``astep`` = 0: two bins of drift at 100 Hz,
     ``accel_step(n, tsamp, 100.0, 2.0)``): one call of frbch_dedisperse_pasearch_host, records joined across DMs and trials
     (``acc_gap``), a text file with acceleration columns under PA_HEADER, ``accs`` in the ``.npz``, and folds with
@@ -1090,7 +1092,7 @@ def psearch_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, zerodm=True, clip=5, sig
     nclip = C.c_uint64(0)
     if amax > 0.0:
         return _pasearch_fil(fil, filterbankfile, rows, desc, dms, dm_arr, nout, params, zerodm, clip, dm_gap, max_cands, fold_best,
-                             device, lib, info, amax, astep, acc_gap)
+                             device, lib, info, amax, astep, acc_gap, refine)
     recs, used = _ps_call(lambda c, n, nc, u, e, ne: lib.frbch_dedisperse_psearch_host(
         C.byref(desc), rows.ctypes.data, rows.shape[0], dm_arr.ctypes.data, dm_arr.size, 1 if zerodm else 0, float(clip),
         C.byref(params), device, None, nout, C.byref(nclip), c, n, nc, u, e, ne), 4096)
@@ -1116,11 +1118,13 @@ def psearch_fil(filterbankfile, dm1, dm2=0, dmstep=1.0, zerodm=True, clip=5, sig
         ar, _profile = _fold_par(fil, filterbankfile, par, 0, 10.0, 128, device, lib, "%s_psearch_cand%d" % (base, i), None, 0.0,
                                  "coherency")
         files.append(ar)
+        if refine:
+            files += foldfit_fil(filterbankfile, fil=fil, par=par, device=device, lib=lib, out_base="%s_psearch_cand%d" % (base, i))[0]
     return files, groups
 
 
 def _pasearch_fil(fil, filterbankfile, rows, desc, dms, dm_arr, nout, params, zerodm, clip, dm_gap, max_cands, fold_best, device, lib,
-                  info, amax, astep, acc_gap):
+                  info, amax, astep, acc_gap, refine=False):
     """``psearch_fil`` with trial accelerations, from the point where the two part"""
     hdr = fil.header
     n = lib.frbch_psearch_nfft(nout, C.byref(params))
@@ -1155,6 +1159,8 @@ def _pasearch_fil(fil, filterbankfile, rows, desc, dms, dm_arr, nout, params, ze
         ar, _profile = _fold_par(fil, filterbankfile, par, 0, 10.0, 128, device, lib, "%s_psearch_cand%d" % (base, i), None, 0.0,
                                  "coherency")
         files.append(ar)
+        if refine:
+            files += foldfit_fil(filterbankfile, fil=fil, par=par, device=device, lib=lib, out_base="%s_psearch_cand%d" % (base, i))[0]
     return files, groups
 
 
@@ -1920,6 +1926,244 @@ def _fold_par(fil, filterbankfile, par, nbin, subint_s, fscrunch_to, device, lib
         write_png(base + "_fullPol.png", np.concatenate([np.concatenate([panels[0], gap_v, panels[1]], axis=1), gap_h,
                                                          np.concatenate([panels[2], gap_v, panels[3]], axis=1)], axis=0))
     return base + ".ar", profile
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# refinement of a fold: DM, spin frequency and frequency derivative (frbch_foldfit_*, frbch_fold_refine_*)
+# ------------------------------------------------------------------------------------------------------------------
+FOLDFIT_RESULT = np.dtype([("dm", "<f8"), ("dm_res", "<f8"), ("dfreq", "<f8"), ("dfreq_res", "<f8"), ("dfdot", "<f8"), ("dfdot_res", "<f8"),
+                           ("score_peak", "<f8"), ("score_nominal", "<f8"), ("border_median", "<f8"), ("snr_nominal", "<f8"),
+                           ("snr_best", "<f8"), ("kpeak", "<u4"), ("jpeak", "<u4"), ("ipeak", "<u4"), ("fitted_dm", "<u4"),
+                           ("fitted_freq", "<u4"), ("fitted_fdot", "<u4"), ("nfit_dm", "<u4"), ("nfit_freq", "<u4"), ("nfit_fdot", "<u4"),
+                           ("width_nominal", "<u4"), ("bin_nominal", "<u4"), ("width_best", "<u4"), ("bin_best", "<u4"), ("reserved", "<u4")])
+FOLDFIT_WIDTHS = (1, 2, 4, 8, 16, 32)
+
+
+def foldfit_steps(hdr: dict, nrows: int, nbin: int, f0_fold: float, lib=None):
+    """-> (ddm, dfreq, dfdot): one bin at the bottom of the band, over the span, at the ends of the span (frbch_foldfit_steps)"""
+    lib = lib or _lib.load()
+    ddm, dfreq, dfdot = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+    if lib.frbch_foldfit_steps(C.byref(fil_desc(hdr)), int(nrows), int(nbin), float(f0_fold), C.byref(ddm), C.byref(dfreq), C.byref(dfdot)) < 0:
+        raise InputError("foldfit_steps: bad header, nrows, nbin or f0_fold")
+    return ddm.value, dfreq.value, dfdot.value
+
+
+def foldfit_params(hdr: dict, nrows: int, nbin: int, nsub: int, f0_fold: float, subint_s: float, dm0: float, *, products=None, ndm=1,
+                   nfreq=1, nfdot=1, ddm=None, dfreq=None, dfdot=None, fit_frac=0.5, widths=None, lib=None) -> _lib.FrbchFoldfitParams:
+    """the search's parameters; a step left at None is the natural one (``foldfit_steps``), ``products`` the mask of the products
+    that are added (None: ``hdr['product']``, or product 0), ``widths`` the boxcar widths of the S/N (None: the powers of two up
+    to 32 that fit into half a turn)"""
+    p = _lib.FrbchFoldfitParams()
+    p.size = C.sizeof(_lib.FrbchFoldfitParams)
+    p.nbin, p.nsub, p.ndm, p.nfreq, p.nfdot = int(nbin), int(nsub), int(ndm), int(nfreq), int(nfdot)
+    p.products = int(products) if products is not None else 1 << int(hdr.get("product", 0))
+    p.f0_fold, p.subint_s, p.dm0, p.fit_frac = float(f0_fold), float(subint_s), float(dm0), float(fit_frac)
+    if ddm is None or dfreq is None or dfdot is None:
+        nat = foldfit_steps(hdr, nrows, nbin, f0_fold, lib=lib)
+        ddm, dfreq, dfdot = (nat[0] if ddm is None else ddm), (nat[1] if dfreq is None else dfreq), (nat[2] if dfdot is None else dfdot)
+    p.ddm, p.dfreq, p.dfdot = float(ddm), float(dfreq), float(dfdot)
+    ws = [int(w) for w in (widths if widths is not None else [w for w in FOLDFIT_WIDTHS if w <= max(1, nbin // 2)])]
+    if not 1 <= len(ws) <= 8:
+        raise InputError("foldfit: 1..8 boxcar widths")
+    p.nwidth = len(ws)
+    for i, w in enumerate(ws):
+        p.widths[i] = w
+    return p
+
+
+def _foldfit_outputs(par, nchan, nifs, want_trials, want_plane, want_cube):
+    nt = (par.ndm, par.nfdot, par.nfreq)
+    out = dict(score=np.zeros(nt, np.float64), prof_acc=np.zeros((2, par.nbin), np.int64), prof_hits=np.zeros((2, par.nbin), np.uint64),
+               results=np.zeros(1, FOLDFIT_RESULT))
+    if want_trials:
+        out.update(trial_acc=np.zeros(nt + (par.nbin,), np.int64), trial_hits=np.zeros(nt + (par.nbin,), np.uint64))
+    if want_plane:
+        out.update(plane_acc=np.zeros((par.nsub, par.nbin), np.int64), plane_hits=np.zeros((par.nsub, par.nbin), np.uint64))
+    if want_cube:
+        out.update(cube=np.zeros((par.nsub, nifs, par.nbin, nchan), np.float64), cube_hits=np.zeros((par.nsub, par.nbin, nchan), np.uint32))
+    return out
+
+
+def _ptr(out, key):
+    return out[key].ctypes.data if key in out else None
+
+
+def foldfit_axes(par) -> dict:
+    """the trial values of a search: dm [ndm], dfreq [nfreq], dfdot [nfdot]"""
+    ax = lambda n, step: (np.arange(n, dtype=np.int64) - n // 2).astype(np.float64) * np.float64(step)    # noqa: E731
+    return dict(dm=np.float64(par.dm0) + ax(par.ndm, par.ddm), dfreq=ax(par.nfreq, par.dfreq), dfdot=ax(par.nfdot, par.dfdot))
+
+
+def fold_fit(cube, hits, hdr: dict, nrows: int, par, flag=None, want_trials=False, want_plane=True, device: int = 0, lib=None,
+             info: dict | None = None) -> dict:
+    """Search the folded cube over DM, spin frequency and frequency derivative (frbch_foldfit_host).  ``cube`` float64
+    [nsub][nifs][nbin][nchan] and ``hits`` uint32 [nsub][nbin][nchan] in the library's layout, as frbch_foldp_* leave them for a
+    fold WITHOUT per-channel delays; ``par`` from ``foldfit_params``.  -> dict(score [ndm][nfdot][nfreq], prof_acc / prof_hits
+    [2][nbin] (the nominal and the best trial), results FOLDFIT_RESULT [1], plane_acc / plane_hits [nsub][nbin] of the central DM,
+    trial_acc / trial_hits when asked for).  ``info['kernel_used']``: (stage 1, stage 2), 1 = the fast kernel."""
+    lib = lib or _lib.load()
+    cube = np.ascontiguousarray(cube, dtype=np.float64)
+    hits = np.ascontiguousarray(hits, dtype=np.uint32)
+    nchan, nifs = hdr["nchans"], hdr.get("nifs", 1)
+    if cube.shape != (par.nsub, nifs, par.nbin, nchan) or hits.shape != (par.nsub, par.nbin, nchan):
+        raise InputError("fold_fit: the cube must be [nsub][nifs][nbin][nchan] and the hits [nsub][nbin][nchan]")
+    fl = _flag_arg(flag, nchan)
+    out = _foldfit_outputs(par, nchan, nifs, want_trials, want_plane, False)
+    k = (C.c_uint32 * 2)(0, 0)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_foldfit_host(C.byref(fil_desc(hdr, hdr.get("product", 0))), int(nrows), C.byref(par), cube.ctypes.data, hits.ctypes.data,
+                                  fl.ctypes.data if fl is not None else None, device, out["score"].ctypes.data, out["prof_acc"].ctypes.data,
+                                  out["prof_hits"].ctypes.data, out["results"].ctypes.data, _ptr(out, "trial_acc"), _ptr(out, "trial_hits"),
+                                  _ptr(out, "plane_acc"), _ptr(out, "plane_hits"), k, err, len(err)), err)
+    if info is not None:
+        info.update(kernel_used=(k[0], k[1]))
+    return out
+
+
+def fold_refine(fil_or_rows, hdr: dict, model, par, flag=None, want_cube=False, want_plane=True, device: int = 0, lib=None,
+                info: dict | None = None) -> dict:
+    """Fold and search in one residency (frbch_fold_refine_host): the rows go up once, the cube stays on the device unless
+    ``want_cube``.  ``model`` from ``fold_model`` with ``apply_delays=False`` and the ``nbin`` / ``subint_s`` of ``par``.
+    -> the dict of ``fold_fit`` (and cube, cube_hits).  ``info['kernel_used']``: (fold, stage 1, stage 2)."""
+    lib = lib or _lib.load()
+    rows = _rows_of(fil_or_rows) if isinstance(fil_or_rows, sigproc.SigprocFile) else np.ascontiguousarray(fil_or_rows)
+    nchan, nifs = hdr["nchans"], hdr.get("nifs", 1)
+    fl = _flag_arg(flag, nchan)
+    out = _foldfit_outputs(par, nchan, nifs, False, want_plane, want_cube)
+    k = (C.c_uint32 * 3)(0, 0, 0)
+    err = C.create_string_buffer(512)
+    _check(lib.frbch_fold_refine_host(C.byref(fil_desc(hdr, hdr.get("product", 0))), rows.ctypes.data, rows.shape[0], C.byref(model), C.byref(par),
+                                      fl.ctypes.data if fl is not None else None, device, _ptr(out, "cube"), _ptr(out, "cube_hits"),
+                                      out["score"].ctypes.data, out["prof_acc"].ctypes.data, out["prof_hits"].ctypes.data,
+                                      out["results"].ctypes.data, _ptr(out, "plane_acc"), _ptr(out, "plane_hits"), k, err, len(err)), err)
+    if info is not None:
+        info.update(kernel_used=(k[0], k[1], k[2]))
+    return out
+
+
+def _mean_of(acc, hits):
+    return np.where(hits > 0, acc / np.maximum(hits, 1).astype(np.float64), 0.0)
+
+
+def foldfit_planes(cube, hits, hdr: dict, nrows: int, par, r, flag=None):
+    """The two planes of the plot from the cube in the library's layout, in numpy, at the PEAK trial of the record ``r``:
+    phase against time at its DM (sums int64 and hits uint64 [nsub][nbin], what the library's plane_acc / plane_hits are at the
+    central DM) and phase against frequency at its spin and DM (mean sample [nchan][nbin]; flagged channels 0)."""
+    nsub, nifs, nbin, nchan = cube.shape
+    ax = foldfit_axes(par)
+    use = np.ones(nchan, bool) if flag is None else ~np.asarray(flag, bool)
+    val = sum(cube[:, q] for q in range(nifs) if (par.products >> q) & 1).astype(np.int64)      # [nsub][nbin][nchan]
+    fc = hdr["fch1"] + np.arange(nchan) * hdr["foff"]
+    delay = ax["dm"][r["kpeak"]] / 2.41e-4 * (1.0 / (fc * fc) - 1.0 / (fc.max() * fc.max()))
+    shd = np.rint((delay * par.f0_fold) * nbin).astype(np.int64) % nbin
+    L = max(1, int(np.floor(par.subint_s / hdr["tsamp"] + 0.5)))
+    first = np.arange(nsub, dtype=np.int64) * L
+    tau = ((first + 0.5 * np.minimum(L, nrows - first)) - 0.5 * nrows) * hdr["tsamp"]
+    df, hd = ax["dfreq"][r["ipeak"]], 0.5 * ax["dfdot"][r["jpeak"]]
+    shp = np.rint((df * tau + (hd * tau) * tau) * nbin).astype(np.int64) % nbin
+    pt_acc, pt_hits = np.zeros((nsub, nbin), np.int64), np.zeros((nsub, nbin), np.uint64)
+    pf_acc, pf_hits = np.zeros((nchan, nbin), np.int64), np.zeros((nchan, nbin), np.uint64)
+    for c in np.flatnonzero(use):
+        v, h = np.roll(val[:, :, c], -int(shd[c]), axis=1), np.roll(hits[:, :, c], -int(shd[c]), axis=1).astype(np.uint64)
+        pt_acc += v
+        pt_hits += h
+        for s in range(nsub):
+            pf_acc[c] += np.roll(v[s], int(shp[s]))
+            pf_hits[c] += np.roll(h[s], int(shp[s]))
+    return pt_acc, pt_hits, _mean_of(pf_acc, pf_hits)
+
+
+def foldfit_fil(filterbankfile: str, parfile: str | None = None, f0: float | None = None, dm: float | None = None, f1: float = 0.0,
+                nbin: int = 0, subint_s: float = 10.0, ndm: int = 33, nfreq: int = 33, nfdot: int = 17, ddm=None, dfreq=None, dfdot=None,
+                fit_frac: float = 0.5, flag_file: str | None = None, polyco: str | None = None, refold: bool = False,
+                products: str = "coherency", device: int = 0, lib=None, out_base: str | None = None, fil=None, par: dict | None = None):
+    """`post foldfit`: fold a filterbank with an ephemeris (a .par file, or F0 / F1 / DM) and refine it on the device.
+
+    Writes ``<base>_foldfit.npz`` (score, the axes, both profiles, the phase-time plane of the nominal and of the best DM, the
+    phase-frequency plane of the best trial, results), ``<base>_foldfit.txt`` (the best F0 / F1 / DM with their resolutions, the
+    S/N of the nominal and of the best profile, the kernels used), ``<base>_foldfit.png`` (top to bottom: phase against time at
+    the best DM, phase against frequency at the best spin and DM, the nominal and the best profile, and the three score cuts
+    through the peak: DM, F1, F0) and ``<base>_foldfit.par`` with the polynomial model: PEPOCH = mid-observation, F0' = F0 + F1 (t_mid - PEPOCH) + df,
+    F1' = F1 + dfd, DM' (under a polyco only the offsets are reported: the predictor stays the timing model).  ``refold``: fold
+    once more with that .par -- integer bin shifts cannot undo the smear inside a sub-integration, a second fold can -- and
+    write its outputs as ``fold_fil`` does under ``<base>_refold``.  -> (files, results record)"""
+    lib = lib or _lib.load()
+    fil = fil or sigproc.read_fil(filterbankfile)
+    hdr = fil.header
+    if par is None:
+        if parfile is not None:
+            par = read_par(parfile)
+        elif f0 is not None and dm is not None:
+            par = {"F0": float(f0), "F1": float(f1), "DM": float(dm), "PEPOCH": None, "PSR": "unknown"}
+        else:
+            raise InputError("foldfit: a .par file, or --f0 and --dm")
+    rows = _rows_of(fil)
+    nrows, nifs = rows.shape[0], hdr.get("nifs", 1)
+    segs = read_polyco(polyco) if polyco is not None else None
+    f0_fold = par.get("F0") or (segs[0]["f0"] if segs else 0.0)
+    nbin = nbin or default_nbin(f0_fold, hdr["tsamp"])
+    model, _keep = fold_model(par, hdr, polyco=segs, nbin=nbin, subint_s=subint_s, apply_delays=False)
+    nsub = lib.frbch_fold_nsub(C.byref(fil_desc(hdr)), nrows, float(subint_s))
+    if nsub <= 0:
+        raise InputError("bad sub-integration length")
+    mask = 3 if (nifs == 4 and products == "coherency") else 1 << int(hdr.get("product", 0))
+    fpar = foldfit_params(hdr, nrows, nbin, nsub, f0_fold, subint_s, par["DM"], products=mask, ndm=ndm, nfreq=nfreq, nfdot=nfdot, ddm=ddm,
+                          dfreq=dfreq, dfdot=dfdot, fit_frac=fit_frac, lib=lib)
+    flag = read_flag_file(flag_file, hdr["nchans"]) if flag_file else None
+    info = {}
+    out = fold_refine(rows, hdr, model, fpar, flag=flag, want_cube=True, device=device, lib=lib, info=info)     # (the cube: for the two planes of the plot)
+    r = out["results"][0]
+    ax = foldfit_axes(fpar)
+    pt_acc, pt_hits, pf_mean = foldfit_planes(out["cube"], out["cube_hits"], hdr, nrows, fpar, r, flag=flag)
+    base = (out_base or filterbankfile) + "_foldfit"
+    span = nrows * hdr["tsamp"]
+    t_mid = hdr["tstart"] + 0.5 * span / 86400.0
+    pepoch = par["PEPOCH"] if par.get("PEPOCH") is not None else hdr["tstart"]
+    f0_new = par["F0"] + par["F1"] * (t_mid - pepoch) * 86400.0 + r["dfreq"] if not segs else None
+    f1_new = par["F1"] + r["dfdot"] if not segs else None
+    np.savez(base + ".npz", score=out["score"], dm=ax["dm"], dfreq=ax["dfreq"], dfdot=ax["dfdot"], prof_acc=out["prof_acc"],
+             prof_hits=out["prof_hits"], plane_acc=out["plane_acc"], plane_hits=out["plane_hits"], best_plane_acc=pt_acc,
+             best_plane_hits=pt_hits, phase_freq=pf_mean, results=out["results"],
+             kernel_used=np.array(info["kernel_used"], np.uint32), f0_fold=f0_fold, t_mid=t_mid)
+    with open(base + ".txt", "w") as f:
+        f.write("# %s: fold refinement, %d x %d x %d trials (DM x F1 x F0), nbin %d, %d sub-integrations of %g s\n"
+                % (par["PSR"], fpar.ndm, fpar.nfdot, fpar.nfreq, nbin, nsub, subint_s))
+        f.write("# resolutions, not error bars: how far the grid tells two values apart\n")
+        if segs:
+            f.write("polyco %s: offsets from the predictor\n" % os.path.basename(polyco))
+        else:
+            f.write("F0  %.12f Hz   (nominal at mid-observation %.12f)\n" % (f0_new, f0_new - r["dfreq"]))
+            f.write("F1  %.6e Hz/s   (nominal %.6e)\n" % (f1_new, par["F1"]))
+        f.write("dF0 %+.6e +- %.2e Hz%s\n" % (r["dfreq"], r["dfreq_res"], "" if r["fitted_freq"] else "   (grid value)"))
+        f.write("dF1 %+.6e +- %.2e Hz/s%s\n" % (r["dfdot"], r["dfdot_res"], "" if r["fitted_fdot"] else "   (grid value)"))
+        f.write("DM  %.6f +- %.6f pc cm-3   (nominal %.6f)%s\n" % (r["dm"], r["dm_res"], par["DM"], "" if r["fitted_dm"] else "   (grid value)"))
+        f.write("S/N %.2f -> %.2f   (boxcar %d -> %d bins; score %.6g -> %.6g)\n"
+                % (r["snr_nominal"], r["snr_best"], r["width_nominal"], r["width_best"], r["score_nominal"], r["score_peak"]))
+        f.write("kernels: fold %d, DM stage %d, spin stage %d   (1 = fast, 0 = generic)\n" % tuple(info["kernel_used"]))
+    files = [base + ".npz", base + ".txt", base + ".png"]
+    plane = _mean_of(pt_acc, pt_hits)
+    plane = _unit(plane - plane.mean(axis=1, keepdims=True))
+    nf = max(1, pf_mean.shape[0] // max(1, min(128, pf_mean.shape[0])))
+    pf = pf_mean[: pf_mean.shape[0] // nf * nf].reshape(-1, nf, nbin).mean(axis=1)
+    pf = _unit(pf - pf.mean(axis=1, keepdims=True))
+    strips = [np.tile(_unit(_mean_of(out["prof_acc"][t], out["prof_hits"][t])), (8, 1)) for t in (0, 1)]
+    cuts = []
+    for v in (out["score"][:, r["jpeak"], r["ipeak"]], out["score"][r["kpeak"], :, r["ipeak"]], out["score"][r["kpeak"], r["jpeak"], :]):
+        cut = np.zeros((16, nbin))
+        y = _unit(np.interp(np.linspace(0, v.size - 1, nbin), np.arange(v.size), v))
+        cut[15 - np.rint(y * 15).astype(int), np.arange(nbin)] = 1.0
+        cuts.append(cut)
+    gap = np.zeros((2, nbin))
+    write_png(files[2], np.concatenate([plane, gap, pf, gap, strips[0], gap, strips[1], gap, cuts[0], gap, cuts[1], gap, cuts[2]], axis=0))
+    if not segs:
+        files.append(base + ".par")
+        with open(files[-1], "w") as f:
+            f.write("PSR %s\nF0 %.15g\nF1 %.15g\nPEPOCH %.15f\nDM %.9f\n" % (par["PSR"], f0_new, f1_new, t_mid, r["dm"]))
+        if refold:
+            ar, _prof = _fold_par(fil, filterbankfile, read_par(files[-1]), nbin, subint_s, 128, device, lib, (out_base or filterbankfile) + "_refold",
+                                  None, 0.0, products)
+            files.append(ar)
+    return files, r
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -3058,7 +3302,28 @@ def main(argv=None):
     f.add_argument("--polyco", default=None, help="TEMPO polyco file of the same .par (tempo2 -polyco ... -tempo1): fold with the predictor")
     f.add_argument("--doppler", type=float, default=0.0, help="constant Doppler factor (observed / intrinsic spin frequency - 1) for the F0 / F1 polynomial")
     f.add_argument("--products", choices=("coherency", "stokes"), default="coherency", help="what a four-product file holds: the -d4 products, or I, Q, U, V")
+    f.add_argument("--refine", action="store_true", help="search DM, F0 and F1 about the ephemeris behind the fold: the outputs of `foldfit`")
     f.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
+    ff = sub.add_parser("foldfit", help="fold with an ephemeris and refine it: a search over DM, spin frequency and its derivative on the folded cube")
+    ff.add_argument("fil")
+    ff.add_argument("par", nargs="?", default=None, help=".par file (or --f0 and --dm)")
+    ff.add_argument("--f0", type=float, default=None, help="spin frequency, Hz")
+    ff.add_argument("--f1", type=float, default=0.0, help="frequency derivative, Hz / s")
+    ff.add_argument("--dm", type=float, default=None)
+    ff.add_argument("--nbin", type=int, default=0, help="phase bins (0: as `fold`)")
+    ff.add_argument("-L", "--subint", type=float, default=10.0, help="sub-integration length, s")
+    ff.add_argument("--ndm", type=int, default=33, help="DM trials (odd, or 1)")
+    ff.add_argument("--nfreq", type=int, default=33, help="frequency trials (odd, or 1)")
+    ff.add_argument("--nfdot", type=int, default=17, help="frequency derivative trials (odd, or 1)")
+    ff.add_argument("--ddm", type=float, default=None, help="DM step (default: one bin at the bottom of the band)")
+    ff.add_argument("--dfreq", type=float, default=None, help="frequency step, Hz (default: one bin of drift over the span)")
+    ff.add_argument("--dfdot", type=float, default=None, help="derivative step, Hz / s (default: one bin at the ends of the span)")
+    ff.add_argument("--fit-frac", type=float, default=0.5, help="the parabola is fitted over the points at or above this fraction of the peak")
+    ff.add_argument("--flag", default=None, help="flag file: channels left out")
+    ff.add_argument("--polyco", default=None, help="TEMPO polyco file: fold with the predictor, report the offsets from it")
+    ff.add_argument("--refold", action="store_true", help="fold once more with the refined .par (integer bin shifts cannot undo smear inside a sub-integration)")
+    ff.add_argument("--products", choices=("coherency", "stokes"), default="coherency", help="what a four-product file holds")
+    ff.add_argument("--device", type=int, default=int(os.environ.get("FRBCH_DEVICE", "0")))
     d = sub.add_parser("prepdata", help="incoherent dedispersion (process_vdif.py:202-229)")
     d.add_argument("fil")
     d.add_argument("--dm", type=float, required=True)
@@ -3123,6 +3388,7 @@ def main(argv=None):
     z.add_argument("--t-freq", type=float, default=4.0, help="threshold of --periodic, Gaussian sigma over the bins of a cell")
     z.add_argument("--max-cands", type=int, default=0, help="keep the strongest N candidates (0: all)")
     z.add_argument("--fold-best", type=int, default=0, help="fold the K strongest candidates at their frequency and DM")
+    z.add_argument("--refine", action="store_true", help="with --fold-best: refine every folded candidate in DM, F0 and F1 (the outputs of `foldfit`)")
     z.add_argument("--amax", type=float, default=0.0, help="largest trial acceleration, m/s^2 (0: no acceleration search)")
     z.add_argument("--astep", type=float, default=0.0, help="step of the trial accelerations, m/s^2 (0: two bins of drift at 100 Hz)")
     z.add_argument("--acc-gap", type=int, default=1, help="records at most this many trial accelerations apart can join")
@@ -3433,16 +3699,31 @@ def main(argv=None):
         print("{0} candidates above {1} sigma".format(groups.size, a.threshold))
     elif a.cmd == "psearch":
         files, groups = psearch_fil(a.fil, a.dm, dm2=a.dm2, dmstep=a.dmstep, zerodm=a.nozerodm, clip=a.clip, sigma=a.sigma, nharm=a.nharm,
-                                    flo=a.flo, nfft=a.nfft, wblock=a.wblock, dm_gap=a.dm_gap, max_cands=a.max_cands, fold_best=a.fold_best,
+                                    flo=a.flo, nfft=a.nfft, wblock=a.wblock, dm_gap=a.dm_gap, max_cands=a.max_cands, fold_best=a.fold_best, refine=a.refine,
                                     device=a.device, flag_file=a.flag, rfi=a.rfi or None, amax=a.amax, astep=a.astep, acc_gap=a.acc_gap,
                                     **(dict(periodic=dict(t_freq=a.t_freq)) if a.periodic else {}))
         for path in files:
             print("wrote", path)
         print("{0} periodic candidates above {1} sigma".format(groups.size, a.sigma))
     elif a.cmd == "fold":
+        if a.refine and a.doppler != 0.0:
+            raise InputError("fold --refine with --doppler: the refinement folds with the F0 / F1 polynomial alone; put the Doppler factor into F0 "
+                             "(F0 (1 + doppler)) or fold with a polyco")
         ar, profile = fold_fil(a.fil, a.par, nbin=a.nbin, subint_s=a.subint, fscrunch_to=a.fscrunch, device=a.device,
                                polyco=a.polyco, doppler=a.doppler, products=a.products)
         print("wrote {0}, {1}.profile.txt, {1}.png; peak bin {2} of {3}".format(ar, a.fil, int(np.argmax(profile)), profile.size))
+        if a.refine:
+            files, _r = foldfit_fil(a.fil, a.par, nbin=a.nbin, subint_s=a.subint, polyco=a.polyco, products=a.products, device=a.device)
+            for path in files:
+                print("wrote", path)
+            print(open(files[1]).read(), end="")
+    elif a.cmd == "foldfit":
+        files, _r = foldfit_fil(a.fil, a.par, f0=a.f0, dm=a.dm, f1=a.f1, nbin=a.nbin, subint_s=a.subint, ndm=a.ndm, nfreq=a.nfreq, nfdot=a.nfdot,
+                                ddm=a.ddm, dfreq=a.dfreq, dfdot=a.dfdot, fit_frac=a.fit_frac, flag_file=a.flag, polyco=a.polyco, refold=a.refold,
+                                products=a.products, device=a.device)
+        for path in files:
+            print("wrote", path)
+        print(open(files[1]).read(), end="")
     elif a.cmd == "bandsearch":
         npz, txt, cands, groups = bandsearch_fil(a.fil, a.dm, dm2=a.dm2, dmstep=a.dmstep, nsub=a.nsub, min_sub=a.min_sub, max_sub=a.max_sub,
                                                  zerodm=a.nozerodm, clip=a.clip, threshold=a.threshold, max_width_s=a.max_width,

@@ -1654,6 +1654,142 @@ int frbch_cornerturn_device(const char* recipe, const void* d_frames, size_t nfr
                             uint32_t header_bytes, void* const* d_out, uint32_t ntags, size_t out_bytes_each, int device,
                             char* err, size_t err_cap);
 
+/* ---- refinement of a fold: period, period derivative and DM search ---------------------------------
+ * A fold follows the ephemeris it is handed; a topocentric polynomial from a catalogue is off by the Earth's Doppler factor,
+ * a candidate of the periodicity search by up to half a Fourier bin.  frbch_foldfit_* shift the sub-integrations and the
+ * channels of the folded cube against each other over a grid of DM, spin frequency and frequency derivative and score every
+ * trial profile (what pdmp / prepfold do behind a fold).  Neither program is in the reference tree: the conventions are this
+ * library's (tests/foldfit_oracle.py restates them in numpy), chosen so that every result is reproducible to the bit: the
+ * host works in double with every operation rounded on its own (no fused multiply-add), the device adds integers, exact in
+ * any order, and scores in double in one fixed order.
+ *
+ * Input.  The cube d_cube[nsub][nifs][nbin][nchan] (double) and d_hits[nsub][nbin][nchan] (uint32) exactly as
+ * frbch_foldp_device leaves them for 8- or 16-bit rows folded WITHOUT per-channel delays (apply_delays = 0): every value an
+ * exact integer, 0 <= cube <= (2^nbits - 1) hits, and a (sub-integration, bin, channel) holds at most L rows.  `fil`, `nrows`
+ * and par->nsub / nbin / subint_s are the fold's; f0_fold is the frequency the cube was folded at (the polynomial's F0, or
+ * the polyco's reference frequency).  par->products is a mask over the nifs products: those that are added (1 << fil->product
+ * for one product, 3 for PP + QQ of a coherency file).  flag[nchan] (host, may be NULL): a non-zero byte leaves a channel out.
+ *
+ * Trials.  Three axes, each count odd or 1, centred on the nominal value (kc = ndm / 2, ic = nfreq / 2, jc = nfdot / 2):
+ *   dm_k  = dm0 + (double)(k - kc) * ddm,    df_i = (double)(i - ic) * dfreq,    dfd_j = (double)(j - jc) * dfdot.
+ * Sub-integration times.  L = max(1, round(subint_s / tsamp)) as frbch_fold_nsub has it, r_s = min(L, nrows - s L),
+ *   tau_s = ((double)(s L) + 0.5 * (double)r_s - 0.5 * (double)nrows) * tsamp
+ * -- the middle of sub-integration s about the middle of the observation, which keeps the two spin axes decoupled.
+ * Shift tables (host, int64 reduced to 0 .. nbin - 1; rint rounds ties to even):
+ *   shD[k][c]    = rint((delay_c(dm_k) * f0_fold) * (double)nbin),  delay_c the delay of frbch_dedisperse_* in seconds
+ *                  (post.dedisperse_profile rotates by the same number);
+ *   shP[j][i][s] = rint((df_i * tau_s + ((0.5 * dfd_j) * tau_s) * tau_s) * (double)nbin).
+ * The two shifts are rounded separately and added: the separability is the convention.  Its cost: a trial's total shift is
+ * off by at most one bin where a single rounding would be off by at most half a bin.
+ * Stage 1, DM: for every k, s and bin b, over the unflagged channels c and the masked products p,
+ *   A[k][s][b]  = sum (int64)cube[s][p][(b + shD[k][c]) mod nbin][c]          (int64)
+ *   HA[k][s][b] = sum over the unflagged channels of hits[s][(b + shD[k][c]) mod nbin][c]   (uint64; once a channel: the
+ *                 products share their hits).
+ * Stage 2, spin: for every trial (k, j, i) and bin b,
+ *   B[b] = sum over s of A[k][s][(b - shP[j][i][s]) mod nbin],     H[b] likewise from HA.
+ * The signs: a channel's delay puts its pulse at a LATER phase, which stage 1 reads from (b + shD); a trial frequency above the
+ * fold's moves what the fold put into bin b' on to bin b' + shP, so bin b of the trial reads from (b - shP): with these the
+ * best trial is the correction to ADD, DM' = dm_k, F0' = f0_fold + df_i, F1' = F1 + dfd_j.
+ * Score of a trial (double, every operation rounded on its own): M_k = (double)(sum of all B) / (double)(sum of all H) --
+ * both totals are those of A[k] and HA[k], the same for every spin trial --; a bin with H[b] > 0 gives
+ * d = (double)B[b] / (double)H[b] - M_k and the term (double)H[b] * (d * d); the terms are added as 64 partial sums --
+ * partial q adds the bins q, q + 64, ... in ascending order -- which are then added in ascending q (the summation rule of
+ * the single-pulse search's block statistics).  Fewer than two bins with hits: score 0.  This is the numerator of
+ * prepfold's chi-squared with the hits as weights.
+ *
+ * Consequence: with one trial on every axis B / H is the dedispersed, scrunched profile that post.py makes of the same cube
+ * in numpy (post._scrunched), to the bit.
+ *
+ * Peaks (frbch_foldfit_peaks, host only).  The first largest score in the order [ndm][nfdot][nfreq] is the peak trial.  Along
+ * each axis through it the least-squares parabola of frbch_dmscan_peaks (its normal equations, its code) is fitted over the
+ * contiguous points at or above fit_frac times the peak; the refined value is the vertex; an axis whose points reach the
+ * edge of the grid, with fewer than three points or without a maximum keeps its grid value with fitted = 0.  *_res is the
+ * half-width at which that parabola lies below its vertex by the median score of the grid's border trials (a trial with index
+ * 0 or n - 1 on an axis with n > 1; sorted ascending, the middle one, or 0.5 * (the two middle ones added)):
+ * (sqrt(-1.0 / a) * step) * sqrt(median), 0 on an unfitted axis.  It is a resolution -- how far the grid tells two values
+ * apart -- not an error bar.
+ * S/N of a profile x[b] = B[b] / H[b] (0 without hits): the off-pulse region is the nbin / 2 circularly contiguous bins with
+ * the smallest sum (added from its first bin on; the first such start), baseline = its mean, rms = sqrt(sum (x - baseline)^2
+ * / (nbin / 2)); S/N is the first largest of ((boxcar sum / w) - baseline) * sqrt(w) / rms over the listed widths w (in list
+ * order) and the start bins ascending, the boxcar taken circularly; rms = 0: S/N 0.  Computed for the nominal (central) trial
+ * and for the peak trial.
+ *
+ * frbch_foldfit_steps gives the natural steps for a span T = nrows tsamp: dfreq = 1 / (nbin T), a drift of one bin over the
+ * span; dfdot = 8 / (nbin T^2), one bin at the ends; ddm = 1 / (nbin f0 (1 / 2.41e-4) (f_lo^-2 - f_hi^-2)), one bin at the
+ * bottom of the band.
+ *
+ * FRBCH_E_ARG, each with its own message and every output untouched: a wrong `size`; an even count above 1; ndm nfdot nfreq
+ * above 2^22; nbin outside 2..4096; nsub outside 1..4096 or not frbch_fold_nsub(); nchan above 16384; float rows; an empty
+ * `products` or one beyond nifs; a step that is not finite, or not positive where its count exceeds 1; a dm_k outside
+ * [0, 1e5); fit_frac outside (0, 1]; nwidth outside 1..8 or a width outside 1..nbin / 2; a shift beyond 2^52 bins; and
+ * (2^nbits - 1) nrows nchan popcount(products) >= 2^53, the bound that keeps every sum an exact double.
+ *
+ * Not built: no orbital or jerk axis, no barycentring (the offsets are topocentric), no channel weights beyond the flag, no
+ * sub-bin interpolation -- integer bin shifts cannot undo the smear inside a sub-integration: fold again with the refined
+ * values for that --, and resolutions, not error bars. */
+typedef struct frbch_foldfit_params {
+  uint32_t size;               /* = sizeof(frbch_foldfit_params)                                                 */
+  uint32_t nbin, nsub;         /* of the cube                                                                    */
+  uint32_t products;           /* mask of the products that are added                                            */
+  uint32_t ndm, nfreq, nfdot;  /* trial counts, each odd or 1                                                    */
+  uint32_t nwidth;             /* 1..8 boxcar widths of the S/N                                                  */
+  double f0_fold, subint_s;    /* of the fold                                                                    */
+  double dm0, ddm;             /* nominal DM and its step                                                        */
+  double dfreq, dfdot;         /* steps of the spin axes, Hz and Hz / s                                          */
+  double fit_frac;             /* (0, 1]                                                                         */
+  uint32_t widths[8];
+} frbch_foldfit_params;
+
+typedef struct frbch_foldfit_result {
+  double dm, dm_res;           /* refined DM                                                                     */
+  double dfreq, dfreq_res;     /* refined offset from f0_fold, Hz                                                */
+  double dfdot, dfdot_res;     /* refined offset of the frequency derivative, Hz / s                             */
+  double score_peak, score_nominal, border_median;
+  double snr_nominal, snr_best;
+  uint32_t kpeak, jpeak, ipeak;                      /* the peak trial: DM, derivative, frequency index          */
+  uint32_t fitted_dm, fitted_freq, fitted_fdot;
+  uint32_t nfit_dm, nfit_freq, nfit_fdot;            /* points at or above fit_frac times the peak               */
+  uint32_t width_nominal, bin_nominal, width_best, bin_best, reserved;
+} frbch_foldfit_result;
+
+int frbch_foldfit_steps(const frbch_fil_desc* fil, uint64_t nrows, uint32_t nbin, double f0_fold, double* ddm, double* dfreq,
+                        double* dfdot);
+/* Which form each stage of frbch_foldfit_device takes (host only, nothing runs): kernel[0] stage 1, kernel[1] stage 2, 1 = the
+ * fast kernel, 0 = the generic one; only the ADDRESSES of d_cube and d_hits are examined.  The fast forms want both 16-byte
+ * aligned and the sums of a sub-integration in 32 bits ((2^nbits - 1) popcount(products) L < 2^32, L nchan < 2^32); stage 1
+ * also whole tiles of 8 channels and nbin <= 1024 (a tile of all bins in the LDS), stage 2 at least two spin trials a DM. */
+int frbch_foldfit_kernel(const frbch_fil_desc* fil, uint64_t nrows, const frbch_foldfit_params* par, const double* d_cube,
+                         const uint32_t* d_hits, uint32_t* kernel);
+/* score[ndm][nfdot][nfreq]; prof_acc / prof_hits [2][nbin]: B and H of the nominal and of the peak trial; result; and, each
+ * where not NULL: trial_acc / trial_hits [ndm][nfdot][nfreq][nbin], the profiles of every trial (at most 2^24 elements, else
+ * FRBCH_E_ARG); plane_acc / plane_hits [nsub][nbin], A and HA of the central DM (the phase-time plane).  All host arrays; the
+ * cube and its hits are device memory, never written.  Host-synchronous on a stream of its own, as the other _device entry
+ * points behind the filterbank.  kernel_used[2] as frbch_foldfit_kernel.  Both forms give the same bytes. */
+int frbch_foldfit_device(const frbch_fil_desc* fil, uint64_t nrows, const frbch_foldfit_params* par, const double* d_cube,
+                         const uint32_t* d_hits, const uint8_t* flag, int device, double* score, int64_t* prof_acc,
+                         uint64_t* prof_hits, frbch_foldfit_result* result, int64_t* trial_acc, uint64_t* trial_hits,
+                         int64_t* plane_acc, uint64_t* plane_hits, uint32_t* kernel_used, char* err, size_t err_cap);
+/* the same with the cube and its hits in host memory: one upload, one download of the results */
+int frbch_foldfit_host(const frbch_fil_desc* fil, uint64_t nrows, const frbch_foldfit_params* par, const double* cube,
+                       const uint32_t* hits, const uint8_t* flag, int device, double* score, int64_t* prof_acc,
+                       uint64_t* prof_hits, frbch_foldfit_result* result, int64_t* trial_acc, uint64_t* trial_hits,
+                       int64_t* plane_acc, uint64_t* plane_hits, uint32_t* kernel_used, char* err, size_t err_cap);
+/* The peaks alone, from a score grid and the two profiles (host only). */
+int frbch_foldfit_peaks(const frbch_foldfit_params* par, const double* score, const int64_t* prof_acc, const uint64_t* prof_hits,
+                        frbch_foldfit_result* result, char* err, size_t err_cap);
+/* Rows -> frbch_foldp_device -> frbch_foldfit_device in one residency: the cube stays in HBM and is downloaded only where
+ * cube / cube_hits are not NULL ([nsub][nifs][nbin][nchan] and [nsub][nbin][nchan]).  The model must fold without per-channel
+ * delays (apply_delays = 0: FRBCH_E_ARG otherwise) with par's nbin and subint_s.  The results are the bytes of the two calls in
+ * sequence.  kernel_used[3]: the fold, stage 1, stage 2. */
+int frbch_fold_refine_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_fold_model* model,
+                             const frbch_foldfit_params* par, const uint8_t* flag, int device, double* cube, uint32_t* cube_hits,
+                             double* score, int64_t* prof_acc, uint64_t* prof_hits, frbch_foldfit_result* result,
+                             int64_t* plane_acc, uint64_t* plane_hits, uint32_t* kernel_used, char* err, size_t err_cap);
+int frbch_fold_refine_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_fold_model* model,
+                           const frbch_foldfit_params* par, const uint8_t* flag, int device, double* cube, uint32_t* cube_hits,
+                           double* score, int64_t* prof_acc, uint64_t* prof_hits, frbch_foldfit_result* result,
+                           int64_t* plane_acc, uint64_t* plane_hits, uint32_t* kernel_used, char* err, size_t err_cap);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 int frbch_set_profiling(frbch_handle* h, int enable);
 int frbch_timing_reset(frbch_handle* h);
