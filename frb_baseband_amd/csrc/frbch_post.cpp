@@ -3972,34 +3972,76 @@ void rm_table_fill(int32_t* C) {
   for (int j = 8193; j < 16384; ++j) C[j] = C[16384 - j];
 }
 
-int rm_check(const frbch_fil_desc* fil, uint32_t ncand, const frbch_rm_params* par, const PostErr& e) {
+// ---- RM synthesis and the delay x RM transform: one family (include/frbch.h states the arithmetic of both) ----------------
+// The second is the first with a tau axis in front of phi: a fifth field in the record, a tau tile in the plan, a plane where
+// the first has a row.  The grid record names the member; everything below is written once for both and reads the delay axis
+// from it.  ntau = 1, tau_lo = 0 of the delay family gives RM synthesis to the bit (through its own kernels and records).
+constexpr uint32_t kRmdMaxTau = 4096;
+constexpr double kRmdTauLim = 100.0;
+
+template <class Par> struct RmFam;
+template <> struct RmFam<frbch_rm_params> {
+  using Rec = RmRec;
+  using KPar = RmParams;
+  using Res = frbch_rm_result;
+  static constexpr bool delay = false;
+  static constexpr const char *wrong_size = "frbch_rm_params: wrong size", *launch = "launch RM synthesis", *join = "launch RM join";
+  static uint32_t ntau(const frbch_rm_params*) { return 1; }
+};
+template <> struct RmFam<frbch_rmd_params> {
+  using Rec = RmdRec;
+  using KPar = RmdParams;
+  using Res = frbch_rmd_result;
+  static constexpr bool delay = true;
+  static constexpr const char *wrong_size = "frbch_rmd_params: wrong size", *launch = "launch delay x RM transform", *join = "launch delay x RM join";
+  static uint32_t ntau(const frbch_rmd_params* par) { return par->ntau; }
+};
+
+// the grid checks; the delay family refuses a record of the wrong size before it looks at the file, RM synthesis after
+template <class Par> int rm_check(const frbch_fil_desc* fil, uint32_t ncand, const Par* par, const PostErr& e) {
   POST_NO_CONTRACT
+  using Fam = RmFam<Par>;
+  const bool sized = par && par->size == sizeof(Par);
+  if (Fam::delay && !sized) return e.fail(FRBCH_E_ARG, Fam::wrong_size);
   const int rc = post_check_fil(fil, 1, e);
   if (rc) return rc;
   if (fil->nchan > kRmMaxChan) return e.fail(FRBCH_E_ARG, "more than 16384 channels");
   if (!(fil->fch1_mhz + (double)(fil->nchan - 1) * fil->foff_mhz > 0)) return e.fail(FRBCH_E_ARG, "a channel frequency that is not positive");
   if (ncand < 1 || ncand > kBurstMaxCand) return e.fail(FRBCH_E_ARG, "1..4096 candidates");
-  if (!par || par->size != sizeof(frbch_rm_params)) return e.fail(FRBCH_E_ARG, "frbch_rm_params: wrong size");
+  if (!sized) return e.fail(FRBCH_E_ARG, Fam::wrong_size);
   if (par->nphi < 1 || par->nphi > kRmMaxPhi) return e.fail(FRBCH_E_ARG, "nphi must be 1..2^20");
   if ((uint64_t)ncand * par->nphi > kRmMaxOut) return e.fail(FRBCH_E_ARG, "ncand * nphi exceeds 2^26");
   if (!(par->dphi > 0) || !rm_finite(par->dphi)) return e.fail(FRBCH_E_ARG, "dphi must be positive and finite");
   const double hi = par->phi_lo + (double)par->nphi * par->dphi;
   if (!(fabs(par->phi_lo) <= kRmPhiMax) || !(fabs(hi) <= kRmPhiMax)) return e.fail(FRBCH_E_ARG, "|phi| above 1e7 rad m^-2");
+  if constexpr (Fam::delay) {
+    if (par->ntau < 1 || par->ntau > kRmdMaxTau) return e.fail(FRBCH_E_ARG, "ntau must be 1..4096");
+    if ((uint64_t)ncand * par->nphi * par->ntau > kRmMaxOut) return e.fail(FRBCH_E_ARG, "ncand * ntau * nphi exceeds 2^26");
+    if (!(par->dtau > 0) || !rm_finite(par->dtau)) return e.fail(FRBCH_E_ARG, "dtau must be positive and finite");
+    const double thi = par->tau_lo + (double)par->ntau * par->dtau;
+    if (!(fabs(par->tau_lo) <= kRmdTauLim) || !(fabs(thi) <= kRmdTauLim)) return e.fail(FRBCH_E_ARG, "|tau| above 100 microseconds");
+  }
   return FRBCH_OK;
 }
 
-// The plan rule of the transform -- the one decision behind frbch_rmsynth_device's launches, kernel_used and
-// frbch_rmsynth_kernel's answer.  The fast kernel wants whole waves along k (nphi >= 64) and stores a trial as one 8-byte
-// piece (only the ADDRESS of d_F is examined); a candidate's channels are split until (ncand x k tiles x split) reaches two
-// workgroups per CU, in pieces of at least 64 channels, so that the 64 KiB table a workgroup loads serves at least 65536
+// The plan rule of the family -- the one decision behind the launches of frbch_rmsynth_device and frbch_rmdelay_device, their
+// kernel_used, and the answers of frbch_rmsynth_kernel and frbch_rmdelay_kernel; RM synthesis is ntau = 1.  The fast kernel
+// wants whole waves along k (nphi >= 64) and stores a trial as one 8-byte piece (only the ADDRESS of d_F is examined).  The
+// tau tile is the largest of 8, 4, 2, 1 whose tail -- trials beyond ntau that the last tile computes in vain -- is at most an
+// eighth of ntau: the registers hold 8 (kernels_post_fast.inc), and a term saved by sharing a record is worth far less than
+// a term wasted; at ntau = 1 it is 1.  A candidate's channels are split until (ncand x tau tiles x k tiles x split) reaches
+// two workgroups per CU, in pieces of at least 64 channels, so that the 64 KiB table a workgroup loads serves at least 65536
 // terms.  The emulator build has no such kernel: generic, split 1.
-struct RmPlanRule { bool fastk; int nsplit, chunk; };
-RmPlanRule rm_plan_rule(uint32_t nchan, uint32_t ncand, uint32_t nphi, const float* d_F) {
-  RmPlanRule r{false, 1, (int)nchan};
+struct RmPlanRule { bool fastk; int nsplit, chunk, ttile; };
+RmPlanRule rm_plan_rule(uint32_t nchan, uint32_t ncand, uint32_t nphi, uint32_t ntau, const float* d_F) {
+  RmPlanRule r{false, 1, (int)nchan, 1};
 #ifndef FRBCH_NO_FAST
   if (nphi < 64 || ((uintptr_t)d_F % 8) != 0) return r;
   r.fastk = true;
-  const uint64_t base = (uint64_t)ncand * ((nphi + fast::kRmThreads * fast::kRmKpt - 1) / (fast::kRmThreads * fast::kRmKpt));
+  for (uint32_t t = fast::kRmdTauMax; t > 1; t /= 2)
+    if ((((ntau + t - 1) / t) * t - ntau) * 8 <= ntau) { r.ttile = (int)t; break; }
+  const uint64_t ttiles = (ntau + (uint32_t)r.ttile - 1) / (uint32_t)r.ttile;
+  const uint64_t base = (uint64_t)ncand * ttiles * ((nphi + fast::kRmThreads * fast::kRmKpt - 1) / (fast::kRmThreads * fast::kRmKpt));
   if (base < 512) {
     const uint64_t want = (512 + base - 1) / base, most = (nchan + 63) / 64;
     const uint32_t ns = (uint32_t)std::min(want, most);
@@ -4007,13 +4049,13 @@ RmPlanRule rm_plan_rule(uint32_t nchan, uint32_t ncand, uint32_t nphi, const flo
     r.nsplit = (int)((nchan + (uint32_t)r.chunk - 1) / (uint32_t)r.chunk);
   }
 #else
-  (void)ncand; (void)nphi; (void)d_F;
+  (void)ncand; (void)nphi; (void)ntau; (void)d_F;
 #endif
   return r;
 }
 
-struct RmPlan {
-  std::vector<RmRec> rec;                        // [ncand][nchan]
+template <class Rec> struct RmPlan {
+  std::vector<Rec> rec;                          // [ncand][nchan]
   std::vector<RmCand> cand;
   std::vector<int32_t> table;
 };
@@ -4038,13 +4080,16 @@ std::vector<double> rm_l2(const frbch_fil_desc* fil) {
   return l2;
 }
 
-// the records of step 2 (host): l2, l0, the fixed-point phases, the quantised spectra, inv
-int rm_build(const frbch_fil_desc* fil, const float* q, const float* u, const uint8_t* used, uint32_t ncand, const frbch_rm_params* par,
-             RmPlan* plan, const PostErr& e) {
+// the records of step 2 (host), written once: l2, l0, the fixed-point phases, the quantised spectra, inv; the delay family
+// adds f0, b, T0 (into p0) and E of the same channels
+template <class Par>
+int rm_build(const frbch_fil_desc* fil, const float* q, const float* u, const uint8_t* used, uint32_t ncand, const Par* par,
+             RmPlan<typename RmFam<Par>::Rec>* plan, const PostErr& e) {
   POST_NO_CONTRACT
+  using Rec = typename RmFam<Par>::Rec;
   const uint32_t nchan = fil->nchan;
   const std::vector<double> l2 = rm_l2(fil);
-  plan->rec.assign((size_t)ncand * nchan, RmRec{0, 0, 0ull, 0ull});
+  plan->rec.assign((size_t)ncand * nchan, Rec{});
   plan->cand.assign(ncand, RmCand{0u, 0u, 0.0});
   plan->table.resize(kRmTableN);
   rm_table_fill(plan->table.data());
@@ -4053,7 +4098,7 @@ int rm_build(const frbch_fil_desc* fil, const float* q, const float* u, const ui
     const float* ui = u + (size_t)i * nchan;
     const uint8_t* us = used + (size_t)i * nchan;
     uint32_t N = 0;
-    double sum = 0.0;
+    double sum = 0.0, fsum = 0.0;
     float m = 0.f;
     for (uint32_t c = 0; c < nchan; ++c)
       if (us[c]) {
@@ -4061,22 +4106,30 @@ int rm_build(const frbch_fil_desc* fil, const float* q, const float* u, const ui
           return e.fail(FRBCH_E_ARG, "candidate " + std::to_string(i) + ": q or u of a used channel is not finite");
         ++N;
         sum = sum + l2[c];
+        const double f = fil->fch1_mhz + (double)c * fil->foff_mhz;
+        fsum = fsum + f;
         m = std::max(m, std::max(fabsf(qi[c]), fabsf(ui[c])));
       }
     if (N == 0 || m == 0.f) continue;              // F = 0: no records, inv = 0
-    const double l0 = sum / (double)N;
+    const double l0 = sum / (double)N, f0 = fsum / (double)N;
     int ex = 0;
     (void)frexp((double)m, &ex);
-    RmRec* rec = plan->rec.data() + (size_t)i * nchan;
+    Rec* rec = plan->rec.data() + (size_t)i * nchan;
     uint32_t n = 0;
     for (uint32_t c = 0; c < nchan; ++c)
       if (us[c]) {
         const double a = (l2[c] - l0) / kRmPi;
-        RmRec& r = rec[n++];
+        Rec& r = rec[n++];
         r.qi = (int32_t)rint(ldexp((double)qi[c], 23 - ex));
         r.ui = (int32_t)rint(ldexp((double)ui[c], 23 - ex));
         r.p0 = rm_fix(par->phi_lo * a);
         r.d = rm_fix(par->dphi * a);
+        if constexpr (RmFam<Par>::delay) {
+          const double f = fil->fch1_mhz + (double)c * fil->foff_mhz;
+          const double b = f - f0;
+          r.p0 = r.p0 + rm_fix(par->tau_lo * b);
+          r.e = rm_fix(par->dtau * b);
+        }
       }
     plan->cand[i].nrec = n;
     plan->cand[i].inv = 1.0 / ldexp((double)N, 45 - ex);
@@ -4084,44 +4137,119 @@ int rm_build(const frbch_fil_desc* fil, const float* q, const float* u, const ui
   return FRBCH_OK;
 }
 
+#ifndef FRBCH_NO_FAST
+// the fast kernel of each member on the grid the plan rule gives
+int rm_launch_fast(const RmPlanRule&, dim3 grid, dev_stream_t s, const RmParams& p) {
+  return launch_lds(fast::frbch_post_rm_fast, grid, dim3(fast::kRmThreads), fast::kRmLds, s, p);
+}
+int rm_launch_fast(const RmPlanRule& rule, dim3 grid, dev_stream_t s, const RmdParams& p) {
+  const dim3 block(fast::kRmThreads);
+  switch (rule.ttile) {
+    case 8: return launch_lds(fast::frbch_post_rmd_fast<8>, grid, block, fast::kRmdLds, s, p);
+    case 4: return launch_lds(fast::frbch_post_rmd_fast<4>, grid, block, fast::kRmdLds, s, p);
+    case 2: return launch_lds(fast::frbch_post_rmd_fast<2>, grid, block, fast::kRmdLds, s, p);
+    default: return launch_lds(fast::frbch_post_rmd_fast<1>, grid, block, fast::kRmdLds, s, p);
+  }
+}
+#endif
+
 // the launches of step 2 on the scope's stream; `plan` stays alive until the caller has synchronised
-int rm_launch(const frbch_fil_desc* fil, uint32_t ncand, const frbch_rm_params* par, const RmPlan& plan, float* d_F,
+template <class Par>
+int rm_launch(const frbch_fil_desc* fil, uint32_t ncand, const Par* par, const RmPlan<typename RmFam<Par>::Rec>& plan, float* d_F,
               PostScope& ps, uint32_t* kernel_used, const PostErr& e) {
-  const RmPlanRule rule = rm_plan_rule(fil->nchan, ncand, par->nphi, d_F);
-  RmRec* d_rec = nullptr;
+  using Fam = RmFam<Par>;
+  using Rec = typename Fam::Rec;
+  const uint32_t ntau = Fam::ntau(par);
+  const RmPlanRule rule = rm_plan_rule(fil->nchan, ncand, par->nphi, ntau, d_F);
+  Rec* d_rec = nullptr;
   RmCand* d_cand = nullptr;
   int32_t* d_tab = nullptr;
-  POST_DEV(ps.alloc(&d_rec, plan.rec.size() * sizeof(RmRec)), "hipMalloc");
+  POST_DEV(ps.alloc(&d_rec, plan.rec.size() * sizeof(Rec)), "hipMalloc");
   POST_DEV(ps.alloc(&d_cand, plan.cand.size() * sizeof(RmCand)), "hipMalloc");
   POST_DEV(ps.alloc(&d_tab, (size_t)kRmTableN * sizeof(int32_t)), "hipMalloc");
-  POST_DEV(dev_h2d(d_rec, plan.rec.data(), plan.rec.size() * sizeof(RmRec), ps.s), "upload records");
+  POST_DEV(dev_h2d(d_rec, plan.rec.data(), plan.rec.size() * sizeof(Rec), ps.s), "upload records");
   POST_DEV(dev_h2d(d_cand, plan.cand.data(), plan.cand.size() * sizeof(RmCand), ps.s), "upload records");
   POST_DEV(dev_h2d(d_tab, plan.table.data(), (size_t)kRmTableN * sizeof(int32_t), ps.s), "upload table");
-  RmParams p;
+  typename Fam::KPar p;
   memset(&p, 0, sizeof p);
   p.rec = d_rec; p.cand = d_cand; p.table = d_tab; p.out = d_F;
   p.nchan = (int)fil->nchan; p.nphi = (int)par->nphi; p.ncand = (int)ncand; p.nsplit = rule.nsplit; p.chunk = rule.chunk;
+  if constexpr (Fam::delay) p.ntau = (int)ntau;
   if (kernel_used) { kernel_used[0] = rule.fastk ? 1 : 0; kernel_used[1] = (uint32_t)rule.nsplit; }
+  const size_t per = (size_t)ntau * par->nphi;
 #ifndef FRBCH_NO_FAST
   if (rule.fastk) {
     if (rule.nsplit > 1) {
       long long* d_part = nullptr;
-      POST_DEV(ps.alloc(&d_part, (size_t)rule.nsplit * ncand * par->nphi * 2 * sizeof(long long)), "hipMalloc");
+      POST_DEV(ps.alloc(&d_part, (size_t)rule.nsplit * ncand * per * 2 * sizeof(long long)), "hipMalloc");
       p.part = d_part;
     }
     const unsigned ktiles = (par->nphi + fast::kRmThreads * fast::kRmKpt - 1) / (fast::kRmThreads * fast::kRmKpt);
-    POST_DEV(launch_lds(fast::frbch_post_rm_fast, dim3(ktiles, (unsigned)rule.nsplit, ncand), dim3(fast::kRmThreads), fast::kRmLds, ps.s, p), "LDS size");
-    POST_DEV(dev_check_launch(), "launch RM synthesis");
+    const unsigned ttiles = (ntau + (unsigned)rule.ttile - 1) / (unsigned)rule.ttile;
+    POST_DEV(rm_launch_fast(rule, dim3(ktiles, ttiles * (unsigned)rule.nsplit, ncand), ps.s, p), "LDS size");
+    POST_DEV(dev_check_launch(), Fam::launch);
     if (rule.nsplit > 1) {
-      hipLaunchKernelGGL(fast::frbch_post_rm_join, dim3((par->nphi + fast::kRmThreads - 1) / fast::kRmThreads, ncand), dim3(fast::kRmThreads), 0, ps.s, p);
-      POST_DEV(dev_check_launch(), "launch RM join");
+      const dim3 jgrid((unsigned)((per + fast::kRmThreads - 1) / fast::kRmThreads), ncand), jblock(fast::kRmThreads);
+      if constexpr (Fam::delay) hipLaunchKernelGGL(fast::frbch_post_rmd_join, jgrid, jblock, 0, ps.s, p);
+      else hipLaunchKernelGGL(fast::frbch_post_rm_join, jgrid, jblock, 0, ps.s, p);
+      POST_DEV(dev_check_launch(), Fam::join);
     }
     return FRBCH_OK;
   }
 #endif
-  DEV_LAUNCH(frbch_post_rm, (par->nphi + 255) / 256, ncand, 256, 0, ps.s, p);
-  POST_DEV(dev_check_launch(), "launch RM synthesis");
+  if constexpr (Fam::delay) DEV_LAUNCH(frbch_post_rmd, (per + 255) / 256, ncand, 256, 0, ps.s, p);
+  else DEV_LAUNCH(frbch_post_rm, (per + 255) / 256, ncand, 256, 0, ps.s, p);
+  POST_DEV(dev_check_launch(), Fam::launch);
   return FRBCH_OK;
+}
+
+// ---- the peaks of step 3: what both members ask of a power series and of a channel selection --------------------------
+// the parabola through three neighbouring trials: the vertex offset in trial steps, or false (the grid value stands)
+inline bool rm_vertex(bool interior, double ym, double y0, double yp, double* delta) {
+  POST_NO_CONTRACT
+  if (!interior) return false;
+  const double den = (ym - 2.0 * y0) + yp;
+  if (!(den < 0.0)) return false;
+  const double diff = ym - yp;
+  *delta = (0.5 * diff) / den;
+  return true;
+}
+
+// the sum of noise_q^2 + noise_u^2 over the used channels of one candidate, whose noises begin at `at` (0 without both)
+inline double rm_noise_sum(const uint8_t* us, const float* noise_q, const float* noise_u, size_t at, uint32_t nchan) {
+  POST_NO_CONTRACT
+  double acc = 0.0;
+  if (noise_q && noise_u)
+    for (uint32_t c = 0; c < nchan; ++c)
+      if (us[c]) {
+        const double nq = (double)noise_q[at + c], nu = (double)noise_u[at + c];
+        const double a = nq * nq, b = nu * nu;
+        acc = acc + (a + b);
+      }
+  return acc;
+}
+
+// the used channels of a selection and their spans of lambda^2 and of frequency, as fwhm and fwhm_tau want them
+struct RmSpan {
+  uint32_t N;
+  double l2, f;                                  // hi - lo, 0 where fewer than two values differ
+  double fwhm() const { return l2 > 0.0 ? (2.0 * sqrt(3.0)) / l2 : 0.0; }
+  double fwhm_tau() const { return f > 0.0 ? (2.0 * sqrt(3.0)) / (kRmPi * f) : 0.0; }
+};
+inline RmSpan rm_span(const frbch_fil_desc* fil, const std::vector<double>& l2, const uint8_t* us) {
+  POST_NO_CONTRACT
+  uint32_t N = 0;
+  double lo = 0.0, hi = 0.0, flo = 0.0, fhi = 0.0;
+  for (uint32_t c = 0; c < fil->nchan; ++c)
+    if (us[c]) {
+      const double f = fil->fch1_mhz + (double)c * fil->foff_mhz;
+      if (!N || l2[c] < lo) lo = l2[c];
+      if (!N || l2[c] > hi) hi = l2[c];
+      if (!N || f < flo) flo = f;
+      if (!N || f > fhi) fhi = f;
+      ++N;
+    }
+  return RmSpan{N, hi > lo ? hi - lo : 0.0, fhi > flo ? fhi - flo : 0.0};
 }
 
 int rm_peaks_run(const frbch_fil_desc* fil, const float* F, const uint8_t* used, const float* noise_q, const float* noise_u,
@@ -4148,196 +4276,25 @@ int rm_peaks_run(const frbch_fil_desc* fil, const float* F, const uint8_t* used,
     r.kpeak = kp;
     r.rm = par->phi_lo + (double)kp * par->dphi;
     r.peak = sqrt(best);
-    if (kp > 0 && kp + 1 < nphi) {
-      const double ym = power(kp - 1), yp = power(kp + 1);
-      const double den = (ym - 2.0 * best) + yp;
-      if (den < 0.0) {
-        const double diff = ym - yp;
-        const double delta = (0.5 * diff) / den;
-        r.rm = par->phi_lo + ((double)kp + delta) * par->dphi;
-        const double corr = (0.25 * diff) * delta;
-        r.peak = sqrt(best - corr);
-        r.fitted = 1;
-      }
+    const bool interior = kp > 0 && kp + 1 < nphi;
+    const double ym = interior ? power(kp - 1) : 0.0, yp = interior ? power(kp + 1) : 0.0;
+    double delta = 0.0;
+    if (rm_vertex(interior, ym, best, yp, &delta)) {
+      r.rm = par->phi_lo + ((double)kp + delta) * par->dphi;
+      const double corr = (0.25 * (ym - yp)) * delta;
+      r.peak = sqrt(best - corr);
+      r.fitted = 1;
     }
     r.pa0 = atan2((double)f[2 * (size_t)kp + 1], (double)f[2 * (size_t)kp]) / 2.0;
-    uint32_t N = 0;
-    double lo = 0.0, hi = 0.0, acc = 0.0;
-    for (uint32_t c = 0; c < nchan; ++c)
-      if (us[c]) {
-        if (!N || l2[c] < lo) lo = l2[c];
-        if (!N || l2[c] > hi) hi = l2[c];
-        ++N;
-        if (noise_q && noise_u) {
-          const double nq = (double)noise_q[(size_t)i * nchan + c], nu = (double)noise_u[(size_t)i * nchan + c];
-          const double a = nq * nq, b = nu * nu;
-          acc = acc + (a + b);
-        }
-      }
-    r.nused = N;
-    if (N) r.sigma_f = sqrt(acc / 2.0) / (double)N;
+    const RmSpan span = rm_span(fil, l2, us);
+    const double acc = rm_noise_sum(us, noise_q, noise_u, (size_t)i * nchan, nchan);
+    r.nused = span.N;
+    if (span.N) r.sigma_f = sqrt(acc / 2.0) / (double)span.N;
     if (r.sigma_f > 0.0) r.snr = sqrt(best) / r.sigma_f;
-    if (hi > lo) r.fwhm = (2.0 * sqrt(3.0)) / (hi - lo);
+    r.fwhm = span.fwhm();
     if (r.snr > 0.0) r.rm_err = r.fwhm / (2.0 * r.snr);
   }
   return FRBCH_OK;
-}
-
-// ---- polarisation calibration: the delay x RM transform (include/frbch.h states the arithmetic) ------------------------
-constexpr uint32_t kRmdMaxTau = 4096;
-constexpr double kRmdTauLim = 100.0;
-
-inline frbch_rm_params rmd_rm_params(const frbch_rmd_params* par) {
-  return frbch_rm_params{(uint32_t)sizeof(frbch_rm_params), par->nphi, par->phi_lo, par->dphi};
-}
-
-int rmd_check(const frbch_fil_desc* fil, uint32_t ncand, const frbch_rmd_params* par, const PostErr& e) {
-  POST_NO_CONTRACT
-  if (!par || par->size != sizeof(frbch_rmd_params)) return e.fail(FRBCH_E_ARG, "frbch_rmd_params: wrong size");
-  const frbch_rm_params rp = rmd_rm_params(par);
-  const int rc = rm_check(fil, ncand, &rp, e);
-  if (rc) return rc;
-  if (par->ntau < 1 || par->ntau > kRmdMaxTau) return e.fail(FRBCH_E_ARG, "ntau must be 1..4096");
-  if ((uint64_t)ncand * par->nphi * par->ntau > kRmMaxOut) return e.fail(FRBCH_E_ARG, "ncand * ntau * nphi exceeds 2^26");
-  if (!(par->dtau > 0) || !rm_finite(par->dtau)) return e.fail(FRBCH_E_ARG, "dtau must be positive and finite");
-  const double hi = par->tau_lo + (double)par->ntau * par->dtau;
-  if (!(fabs(par->tau_lo) <= kRmdTauLim) || !(fabs(hi) <= kRmdTauLim)) return e.fail(FRBCH_E_ARG, "|tau| above 100 microseconds");
-  return FRBCH_OK;
-}
-
-// The plan rule of the delay x RM transform -- the one decision behind frbch_rmdelay_device's launches, kernel_used and
-// frbch_rmdelay_kernel's answer.  Form and split as rm_plan_rule has them (whole waves along k, an 8-byte aligned F, two
-// workgroups per CU before a candidate's channels are split in pieces of at least 64), with the tau tiles counted among the
-// workgroups.  The tau tile is the largest of 8, 4, 2, 1 whose tail -- trials beyond ntau that the last tile computes in
-// vain -- is at most an eighth of ntau: the registers hold 8 (kernels_post_fast.inc), and a term saved by sharing a record
-// is worth far less than a term wasted.  The emulator build has no such kernel: generic, split 1.
-struct RmdPlanRule { bool fastk; int nsplit, chunk, ttile; };
-RmdPlanRule rmd_plan_rule(uint32_t nchan, uint32_t ncand, uint32_t nphi, uint32_t ntau, const float* d_F) {
-  RmdPlanRule r{false, 1, (int)nchan, 1};
-#ifndef FRBCH_NO_FAST
-  if (nphi < 64 || ((uintptr_t)d_F % 8) != 0) return r;
-  r.fastk = true;
-  for (uint32_t t = fast::kRmdTauMax; t > 1; t /= 2)
-    if ((((ntau + t - 1) / t) * t - ntau) * 8 <= ntau) { r.ttile = (int)t; break; }
-  const uint64_t ttiles = (ntau + (uint32_t)r.ttile - 1) / (uint32_t)r.ttile;
-  const uint64_t base = (uint64_t)ncand * ttiles * ((nphi + fast::kRmThreads * fast::kRmKpt - 1) / (fast::kRmThreads * fast::kRmKpt));
-  if (base < 512) {
-    const uint64_t want = (512 + base - 1) / base, most = (nchan + 63) / 64;
-    const uint32_t ns = (uint32_t)std::min(want, most);
-    r.chunk = (int)((nchan + ns - 1) / ns);
-    r.nsplit = (int)((nchan + (uint32_t)r.chunk - 1) / (uint32_t)r.chunk);
-  }
-#else
-  (void)ncand; (void)nphi; (void)ntau; (void)d_F;
-#endif
-  return r;
-}
-
-struct RmdPlan {
-  std::vector<RmdRec> rec;                       // [ncand][nchan]
-  std::vector<RmCand> cand;
-  std::vector<int32_t> table;
-};
-
-// the records: those of step 2 (rm_build, unchanged), then f0, b, T0 and E of the used channels in the same order
-int rmd_build(const frbch_fil_desc* fil, const float* q, const float* u, const uint8_t* used, uint32_t ncand, const frbch_rmd_params* par,
-              RmdPlan* plan, const PostErr& e) {
-  POST_NO_CONTRACT
-  const uint32_t nchan = fil->nchan;
-  const frbch_rm_params rp = rmd_rm_params(par);
-  RmPlan base;
-  const int rc = rm_build(fil, q, u, used, ncand, &rp, &base, e);
-  if (rc) return rc;
-  plan->rec.assign((size_t)ncand * nchan, RmdRec{0, 0, 0ull, 0ull, 0ull});
-  plan->cand.swap(base.cand);
-  plan->table.swap(base.table);
-  for (uint32_t i = 0; i < ncand; ++i) {
-    if (!plan->cand[i].nrec) continue;
-    const uint8_t* us = used + (size_t)i * nchan;
-    uint32_t N = 0;
-    double sum = 0.0;
-    for (uint32_t c = 0; c < nchan; ++c)
-      if (us[c]) {
-        const double f = fil->fch1_mhz + (double)c * fil->foff_mhz;
-        ++N;
-        sum = sum + f;
-      }
-    const double f0 = sum / (double)N;
-    const RmRec* src = base.rec.data() + (size_t)i * nchan;
-    RmdRec* rec = plan->rec.data() + (size_t)i * nchan;
-    uint32_t n = 0;
-    for (uint32_t c = 0; c < nchan; ++c)
-      if (us[c]) {
-        const double f = fil->fch1_mhz + (double)c * fil->foff_mhz;
-        const double b = f - f0;
-        RmdRec& r = rec[n];
-        r.qi = src[n].qi; r.ui = src[n].ui;
-        r.p0 = src[n].p0 + rm_fix(par->tau_lo * b);
-        r.d = src[n].d;
-        r.e = rm_fix(par->dtau * b);
-        ++n;
-      }
-  }
-  return FRBCH_OK;
-}
-
-// the launches on the scope's stream; `plan` stays alive until the caller has synchronised
-int rmd_launch(const frbch_fil_desc* fil, uint32_t ncand, const frbch_rmd_params* par, const RmdPlan& plan, float* d_F,
-               PostScope& ps, uint32_t* kernel_used, const PostErr& e) {
-  const RmdPlanRule rule = rmd_plan_rule(fil->nchan, ncand, par->nphi, par->ntau, d_F);
-  RmdRec* d_rec = nullptr;
-  RmCand* d_cand = nullptr;
-  int32_t* d_tab = nullptr;
-  POST_DEV(ps.alloc(&d_rec, plan.rec.size() * sizeof(RmdRec)), "hipMalloc");
-  POST_DEV(ps.alloc(&d_cand, plan.cand.size() * sizeof(RmCand)), "hipMalloc");
-  POST_DEV(ps.alloc(&d_tab, (size_t)kRmTableN * sizeof(int32_t)), "hipMalloc");
-  POST_DEV(dev_h2d(d_rec, plan.rec.data(), plan.rec.size() * sizeof(RmdRec), ps.s), "upload records");
-  POST_DEV(dev_h2d(d_cand, plan.cand.data(), plan.cand.size() * sizeof(RmCand), ps.s), "upload records");
-  POST_DEV(dev_h2d(d_tab, plan.table.data(), (size_t)kRmTableN * sizeof(int32_t), ps.s), "upload table");
-  RmdParams p;
-  memset(&p, 0, sizeof p);
-  p.rec = d_rec; p.cand = d_cand; p.table = d_tab; p.out = d_F;
-  p.nchan = (int)fil->nchan; p.nphi = (int)par->nphi; p.ntau = (int)par->ntau; p.ncand = (int)ncand; p.nsplit = rule.nsplit; p.chunk = rule.chunk;
-  if (kernel_used) { kernel_used[0] = rule.fastk ? 1 : 0; kernel_used[1] = (uint32_t)rule.nsplit; }
-  const size_t per = (size_t)par->ntau * par->nphi;
-#ifndef FRBCH_NO_FAST
-  if (rule.fastk) {
-    if (rule.nsplit > 1) {
-      long long* d_part = nullptr;
-      POST_DEV(ps.alloc(&d_part, (size_t)rule.nsplit * ncand * per * 2 * sizeof(long long)), "hipMalloc");
-      p.part = d_part;
-    }
-    const unsigned ktiles = (par->nphi + fast::kRmThreads * fast::kRmKpt - 1) / (fast::kRmThreads * fast::kRmKpt);
-    const unsigned ttiles = (par->ntau + (unsigned)rule.ttile - 1) / (unsigned)rule.ttile;
-    const dim3 grid(ktiles, ttiles * (unsigned)rule.nsplit, ncand), block(fast::kRmThreads);
-    switch (rule.ttile) {
-      case 8: POST_DEV(launch_lds(fast::frbch_post_rmd_fast<8>, grid, block, fast::kRmdLds, ps.s, p), "LDS size"); break;
-      case 4: POST_DEV(launch_lds(fast::frbch_post_rmd_fast<4>, grid, block, fast::kRmdLds, ps.s, p), "LDS size"); break;
-      case 2: POST_DEV(launch_lds(fast::frbch_post_rmd_fast<2>, grid, block, fast::kRmdLds, ps.s, p), "LDS size"); break;
-      default: POST_DEV(launch_lds(fast::frbch_post_rmd_fast<1>, grid, block, fast::kRmdLds, ps.s, p), "LDS size"); break;
-    }
-    POST_DEV(dev_check_launch(), "launch delay x RM transform");
-    if (rule.nsplit > 1) {
-      hipLaunchKernelGGL(fast::frbch_post_rmd_join, dim3((unsigned)((per + fast::kRmThreads - 1) / fast::kRmThreads), ncand), dim3(fast::kRmThreads), 0, ps.s, p);
-      POST_DEV(dev_check_launch(), "launch delay x RM join");
-    }
-    return FRBCH_OK;
-  }
-#endif
-  DEV_LAUNCH(frbch_post_rmd, (per + 255) / 256, ncand, 256, 0, ps.s, p);
-  POST_DEV(dev_check_launch(), "launch delay x RM transform");
-  return FRBCH_OK;
-}
-
-// the parabola of step 3 along one axis: the vertex offset in trial steps, or false (the grid value stands)
-inline bool rmd_vertex(bool interior, double ym, double y0, double yp, double* delta) {
-  POST_NO_CONTRACT
-  if (!interior) return false;
-  const double den = (ym - 2.0 * y0) + yp;
-  if (!(den < 0.0)) return false;
-  const double diff = ym - yp;
-  *delta = (0.5 * diff) / den;
-  return true;
 }
 
 // peak and ridge of one map P[ntau][nphi] into r (tau, rm, fitted_*, mpeak, kpeak, ridge_slope, nridge); -> P[mp][kp]
@@ -4353,12 +4310,12 @@ double rmd_map_peak(const double* P, const frbch_rmd_params* par, frbch_rmd_resu
   r.kpeak = (uint32_t)kp;
   double delta = 0.0;
   r.tau = par->tau_lo + (double)mp * par->dtau;
-  if (rmd_vertex(mp > 0 && mp + 1 < ntau, mp > 0 ? P[at - nphi] : 0.0, best, mp + 1 < ntau ? P[at + nphi] : 0.0, &delta)) {
+  if (rm_vertex(mp > 0 && mp + 1 < ntau, mp > 0 ? P[at - nphi] : 0.0, best, mp + 1 < ntau ? P[at + nphi] : 0.0, &delta)) {
     r.tau = par->tau_lo + ((double)mp + delta) * par->dtau;
     r.fitted_tau = 1;
   }
   r.rm = par->phi_lo + (double)kp * par->dphi;
-  if (rmd_vertex(kp > 0 && kp + 1 < nphi, kp > 0 ? P[at - 1] : 0.0, best, kp + 1 < nphi ? P[at + 1] : 0.0, &delta)) {
+  if (rm_vertex(kp > 0 && kp + 1 < nphi, kp > 0 ? P[at - 1] : 0.0, best, kp + 1 < nphi ? P[at + 1] : 0.0, &delta)) {
     r.rm = par->phi_lo + ((double)kp + delta) * par->dphi;
     r.fitted_rm = 1;
   }
@@ -4400,22 +4357,17 @@ int rmd_peaks_run(const frbch_fil_desc* fil, const float* F, const uint8_t* used
   std::vector<double> P(per), Psum(per, 0.0);
   std::vector<uint8_t> any(nchan, 0);
   uint32_t entered = 0;
-  // l2 and f spans of a channel selection, as fwhm and fwhm_tau want them
   auto widths = [&](const uint8_t* us, frbch_rmd_result& r) {
-    uint32_t N = 0;
-    double lo = 0.0, hi = 0.0, flo = 0.0, fhi = 0.0;
-    for (uint32_t c = 0; c < nchan; ++c)
-      if (us[c]) {
-        const double f = fil->fch1_mhz + (double)c * fil->foff_mhz;
-        if (!N || l2[c] < lo) lo = l2[c];
-        if (!N || l2[c] > hi) hi = l2[c];
-        if (!N || f < flo) flo = f;
-        if (!N || f > fhi) fhi = f;
-        ++N;
-      }
-    if (hi > lo) r.fwhm = (2.0 * sqrt(3.0)) / (hi - lo);
-    if (fhi > flo) r.fwhm_tau = (2.0 * sqrt(3.0)) / (kRmPi * (fhi - flo));
-    return N;
+    const RmSpan span = rm_span(fil, l2, us);
+    r.fwhm = span.fwhm();
+    r.fwhm_tau = span.fwhm_tau();
+    return span.N;
+  };
+  auto errors = [](frbch_rmd_result& r) {
+    if (r.snr > 0.0) {
+      r.rm_err = r.fwhm / (2.0 * r.snr);
+      r.tau_err = r.fwhm_tau / (2.0 * r.snr);
+    }
   };
   for (uint32_t i = 0; i < ncand; ++i) {
     frbch_rmd_result& r = res[i];
@@ -4432,20 +4384,10 @@ int rmd_peaks_run(const frbch_fil_desc* fil, const float* F, const uint8_t* used
     r.peak = sqrt(best);
     r.psi = atan2((double)f[2 * at + 1], (double)f[2 * at]);
     r.nused = widths(us, r);
-    double acc = 0.0;
-    if (noise_q && noise_u)
-      for (uint32_t c = 0; c < nchan; ++c)
-        if (us[c]) {
-          const double nq = (double)noise_q[(size_t)i * nchan + c], nu = (double)noise_u[(size_t)i * nchan + c];
-          const double a = nq * nq, b = nu * nu;
-          acc = acc + (a + b);
-        }
+    const double acc = rm_noise_sum(us, noise_q, noise_u, (size_t)i * nchan, nchan);
     if (r.nused) r.sigma_f = sqrt(acc / 2.0) / (double)r.nused;
     if (r.sigma_f > 0.0) r.snr = sqrt(best) / r.sigma_f;
-    if (r.snr > 0.0) {
-      r.rm_err = r.fwhm / (2.0 * r.snr);
-      r.tau_err = r.fwhm_tau / (2.0 * r.snr);
-    }
+    errors(r);
     if (r.sigma_f > 0.0 && r.nused) {
       const double s2 = r.sigma_f * r.sigma_f;
       for (size_t x = 0; x < per; ++x) Psum[x] = Psum[x] + P[x] / s2;
@@ -4462,10 +4404,7 @@ int rmd_peaks_run(const frbch_fil_desc* fil, const float* F, const uint8_t* used
   r.sigma_f = 1.0;
   (void)widths(any.data(), r);
   r.nused = entered;
-  if (r.snr > 0.0) {
-    r.rm_err = r.fwhm / (2.0 * r.snr);
-    r.tau_err = r.fwhm_tau / (2.0 * r.snr);
-  }
+  errors(r);
   return FRBCH_OK;
 }
 
@@ -4550,20 +4489,33 @@ extern "C" int frbch_rm_table(int32_t* out) {
   return FRBCH_OK;
 }
 
-extern "C" int frbch_rmsynth_kernel(const frbch_fil_desc* fil, const float* d_F, uint32_t ncand, const frbch_rm_params* par,
-                                    uint32_t* nsplit) try {
+// ---- the entry points of the family, each body once; the extern "C" names below only name the member (by its grid record) --
+namespace {
+static_assert(sizeof(RmdRec) == 32 && sizeof(frbch_rmd_params) == 48 && sizeof(frbch_rmd_result) == 112, "delay x RM records");
+
+// floats of F
+template <class Par> size_t rm_nf(uint32_t ncand, const Par* par) { return (size_t)ncand * RmFam<Par>::ntau(par) * par->nphi * 2; }
+
+template <class Par>
+int rm_family_peaks(const frbch_fil_desc* fil, const float* F, const uint8_t* used, const float* noise_q, const float* noise_u,
+                    uint32_t ncand, const Par* par, typename RmFam<Par>::Res* res) {
+  if constexpr (RmFam<Par>::delay) return rmd_peaks_run(fil, F, used, noise_q, noise_u, ncand, par, res);
+  else return rm_peaks_run(fil, F, used, noise_q, noise_u, ncand, par, res);
+}
+
+template <class Par> int rm_entry_kernel(const frbch_fil_desc* fil, const float* d_F, uint32_t ncand, const Par* par, uint32_t* nsplit) try {
   PostErr e{nullptr, 0};
   const int rc = rm_check(fil, ncand, par, e);
   if (rc) return rc;
   if (!d_F) return FRBCH_E_ARG;
-  const RmPlanRule rule = rm_plan_rule(fil->nchan, ncand, par->nphi, d_F);
+  const RmPlanRule rule = rm_plan_rule(fil->nchan, ncand, par->nphi, RmFam<Par>::ntau(par), d_F);
   if (nsplit) *nsplit = (uint32_t)rule.nsplit;
   return rule.fastk ? 1 : 0;
 } catch (const std::bad_alloc&) { return FRBCH_E_NOMEM; }
 
-extern "C" int frbch_rmsynth_device(const frbch_fil_desc* fil, const float* d_q, const float* d_u, const uint8_t* d_used,
-                                    uint32_t ncand, const frbch_rm_params* par, int device, float* d_F, uint32_t* kernel_used,
-                                    char* err, size_t err_cap) try {
+template <class Par>
+int rm_entry_device(const frbch_fil_desc* fil, const float* d_q, const float* d_u, const uint8_t* d_used, uint32_t ncand, const Par* par,
+                    int device, float* d_F, uint32_t* kernel_used, char* err, size_t err_cap) try {
   PostErr e{err, err_cap};
   int rc = rm_check(fil, ncand, par, e);
   if (rc) return rc;
@@ -4571,7 +4523,7 @@ extern "C" int frbch_rmsynth_device(const frbch_fil_desc* fil, const float* d_q,
   const size_t n = (size_t)ncand * fil->nchan;
   std::vector<float> q(n), u(n);
   std::vector<uint8_t> used(n);
-  RmPlan plan;
+  RmPlan<typename RmFam<Par>::Rec> plan;
   return burst_device_call(device, e, [&](PostScope& ps) {
     int rc;
     POST_DEV(dev_d2h(q.data(), d_q, n * sizeof(float), ps.s), "download q");
@@ -4585,8 +4537,9 @@ extern "C" int frbch_rmsynth_device(const frbch_fil_desc* fil, const float* d_q,
   });
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
-extern "C" int frbch_rmsynth_host(const frbch_fil_desc* fil, const float* q, const float* u, const uint8_t* used, uint32_t ncand,
-                                  const frbch_rm_params* par, int device, float* F, uint32_t* kernel_used, char* err, size_t err_cap) try {
+template <class Par>
+int rm_entry_host(const frbch_fil_desc* fil, const float* q, const float* u, const uint8_t* used, uint32_t ncand, const Par* par, int device,
+                  float* F, uint32_t* kernel_used, char* err, size_t err_cap) try {
   PostErr e{err, err_cap};
   int rc = rm_check(fil, ncand, par, e);
   if (rc) return rc;
@@ -4598,152 +4551,37 @@ extern "C" int frbch_rmsynth_host(const frbch_fil_desc* fil, const float* q, con
   const float* d_q = hs.in(q, n * sizeof(float));
   const float* d_u = hs.in(u, n * sizeof(float));
   const uint8_t* d_used = hs.in(used, n);
-  float* d_F = hs.out(F, (size_t)ncand * par->nphi * 2 * sizeof(float));
+  float* d_F = hs.out(F, rm_nf(ncand, par) * sizeof(float));
   return hs.run(e, "device memory for the spectra and F", "upload spectra", "download F",
-                [&]() { return frbch_rmsynth_device(fil, d_q, d_u, d_used, ncand, par, device, d_F, kernel_used, err, err_cap); });
+                [&]() { return rm_entry_device(fil, d_q, d_u, d_used, ncand, par, device, d_F, kernel_used, err, err_cap); });
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
-extern "C" int frbch_rm_peaks(const frbch_fil_desc* fil, const float* F, const uint8_t* used, const float* noise_q, const float* noise_u,
-                              uint32_t ncand, const frbch_rm_params* par, frbch_rm_result* results, char* err, size_t err_cap) try {
+template <class Par>
+int rm_entry_peaks(const frbch_fil_desc* fil, const float* F, const uint8_t* used, const float* noise_q, const float* noise_u, uint32_t ncand,
+                   const Par* par, typename RmFam<Par>::Res* results, char* err, size_t err_cap) try {
   PostErr e{err, err_cap};
   const int rc = rm_check(fil, ncand, par, e);
   if (rc) return rc;
   if (!F || !used || !results) return e.fail(FRBCH_E_ARG, "null argument");
-  return rm_peaks_run(fil, F, used, noise_q, noise_u, ncand, par, results);
+  return rm_family_peaks(fil, F, used, noise_q, noise_u, ncand, par, results);
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
-extern "C" int frbch_burst_rm_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
-                                     const frbch_burst_cand* cands, uint32_t ncand, const float* gain, const uint8_t* flag,
-                                     const frbch_rm_params* par, int device, float* spec, float* noise, uint8_t* used, float* F,
-                                     frbch_rm_result* results, uint32_t* kernel_used, char* err, size_t err_cap) try {
+// the composite: rows -> spectra (step 1) -> Q, U and their noises, less the flagged channels -> the transform -> the peaks
+template <class Par>
+int rm_entry_burst_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                          const frbch_burst_cand* cands, uint32_t ncand, const float* gain, const uint8_t* flag, const Par* par, int device,
+                          float* spec, float* noise, uint8_t* used, float* F, typename RmFam<Par>::Res* results, uint32_t* kernel_used,
+                          char* err, size_t err_cap) try {
   PostErr e{err, err_cap};
   int rc = burst_check(fil, nrows, bpar, cands, ncand, e);
   if (rc) return rc;
   if (fil->nifs != 4) return e.fail(FRBCH_E_ARG, "the composite needs the four products of a full-Stokes file (nifs = 4)");
   if ((rc = rm_check(fil, ncand, par, e)) != 0) return rc;
   if (!d_rows || !spec || !noise || !used || !F || !results) return e.fail(FRBCH_E_ARG, "null argument");
-  const size_t nchan = fil->nchan, n = (size_t)ncand * nchan;
+  const size_t nchan = fil->nchan, n = (size_t)ncand * nchan, nF = rm_nf(ncand, par);
   std::vector<frbch_burst_sums> sums;
   std::vector<float> q(n), u(n), nq(n), nu(n);
-  RmPlan plan;
-  uint32_t k[3] = {0, 0, 1};
-  rc = burst_device_call(device, e, [&](PostScope& ps) {
-    int rc;
-    BurstSums* d_sums = nullptr;
-    float* d_F = nullptr;
-    POST_DEV(ps.alloc(&d_sums, n * 4 * sizeof(BurstSums)), "hipMalloc");
-    POST_DEV(ps.alloc(&d_F, (size_t)ncand * par->nphi * 2 * sizeof(float)), "hipMalloc");
-    if ((rc = burst_run(fil, d_rows, nrows, bpar, cands, ncand, gain, d_sums, ps, &sums, spec, noise, used, &k[0], e)) != 0) return rc;
-    for (uint32_t i = 0; i < ncand; ++i)
-      for (size_t c = 0; c < nchan; ++c) {
-        if (flag && flag[c]) used[i * nchan + c] = 0;
-        q[i * nchan + c] = spec[((size_t)i * 4 + 1) * nchan + c];
-        u[i * nchan + c] = spec[((size_t)i * 4 + 2) * nchan + c];
-        nq[i * nchan + c] = noise[((size_t)i * 4 + 1) * nchan + c];
-        nu[i * nchan + c] = noise[((size_t)i * 4 + 2) * nchan + c];
-      }
-    if ((rc = rm_build(fil, q.data(), u.data(), used, ncand, par, &plan, e)) != 0) return rc;
-    if ((rc = rm_launch(fil, ncand, par, plan, d_F, ps, &k[1], e)) != 0) return rc;
-    POST_DEV(dev_d2h(F, d_F, (size_t)ncand * par->nphi * 2 * sizeof(float), ps.s), "download F");
-    POST_DEV(dev_sync(ps.s), "sync");
-    return (int)FRBCH_OK;
-  });
-  if (rc) return rc;
-  deliver(kernel_used, k);
-  return rm_peaks_run(fil, F, used, nq.data(), nu.data(), ncand, par, results);
-} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
-
-extern "C" int frbch_burst_rm_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* bpar,
-                                   const frbch_burst_cand* cands, uint32_t ncand, const float* gain, const uint8_t* flag,
-                                   const frbch_rm_params* par, int device, float* spec, float* noise, uint8_t* used, float* F,
-                                   frbch_rm_result* results, uint32_t* kernel_used, char* err, size_t err_cap) try {
-  PostErr e{err, err_cap};
-  const int rc = burst_check(fil, nrows, bpar, cands, ncand, e);
-  if (rc) return rc;
-  if (!rows) return e.fail(FRBCH_E_ARG, "null argument");
-  return burst_host_twin(fil, rows, nrows, device, e, [&](void* d_rows) {
-    return frbch_burst_rm_device(fil, d_rows, nrows, bpar, cands, ncand, gain, flag, par, device, spec, noise, used, F, results, kernel_used, err, err_cap);
-  });
-} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
-
-// ---- polarisation calibration: the delay x RM transform ---------------------------------------------------------------
-extern "C" int frbch_rmdelay_kernel(const frbch_fil_desc* fil, const float* d_F, uint32_t ncand, const frbch_rmd_params* par,
-                                    uint32_t* nsplit) try {
-  PostErr e{nullptr, 0};
-  const int rc = rmd_check(fil, ncand, par, e);
-  if (rc) return rc;
-  if (!d_F) return FRBCH_E_ARG;
-  const RmdPlanRule rule = rmd_plan_rule(fil->nchan, ncand, par->nphi, par->ntau, d_F);
-  if (nsplit) *nsplit = (uint32_t)rule.nsplit;
-  return rule.fastk ? 1 : 0;
-} catch (const std::bad_alloc&) { return FRBCH_E_NOMEM; }
-
-extern "C" int frbch_rmdelay_device(const frbch_fil_desc* fil, const float* d_q, const float* d_u, const uint8_t* d_used,
-                                    uint32_t ncand, const frbch_rmd_params* par, int device, float* d_F, uint32_t* kernel_used,
-                                    char* err, size_t err_cap) try {
-  static_assert(sizeof(RmdRec) == 32 && sizeof(frbch_rmd_params) == 48 && sizeof(frbch_rmd_result) == 112, "delay x RM records");
-  PostErr e{err, err_cap};
-  int rc = rmd_check(fil, ncand, par, e);
-  if (rc) return rc;
-  if (!d_q || !d_u || !d_used || !d_F) return e.fail(FRBCH_E_ARG, "null argument");
-  const size_t n = (size_t)ncand * fil->nchan;
-  std::vector<float> q(n), u(n);
-  std::vector<uint8_t> used(n);
-  RmdPlan plan;
-  return burst_device_call(device, e, [&](PostScope& ps) {
-    int rc;
-    POST_DEV(dev_d2h(q.data(), d_q, n * sizeof(float), ps.s), "download q");
-    POST_DEV(dev_d2h(u.data(), d_u, n * sizeof(float), ps.s), "download u");
-    POST_DEV(dev_d2h(used.data(), d_used, n, ps.s), "download used");
-    POST_DEV(dev_sync(ps.s), "sync");
-    if ((rc = rmd_build(fil, q.data(), u.data(), used.data(), ncand, par, &plan, e)) != 0) return rc;
-    if ((rc = rmd_launch(fil, ncand, par, plan, d_F, ps, kernel_used, e)) != 0) return rc;
-    POST_DEV(dev_sync(ps.s), "sync");       // (the host vectors the uploads read stay alive until here)
-    return (int)FRBCH_OK;
-  });
-} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
-
-extern "C" int frbch_rmdelay_host(const frbch_fil_desc* fil, const float* q, const float* u, const uint8_t* used, uint32_t ncand,
-                                  const frbch_rmd_params* par, int device, float* F, uint32_t* kernel_used, char* err, size_t err_cap) try {
-  PostErr e{err, err_cap};
-  int rc = rmd_check(fil, ncand, par, e);
-  if (rc) return rc;
-  if (!q || !u || !used || !F) return e.fail(FRBCH_E_ARG, "null argument");
-  if ((rc = post_check_device(device, e)) != 0) return rc;
-  DeviceGuard dg(device);
-  const size_t n = (size_t)ncand * fil->nchan;
-  HostStage hs;
-  const float* d_q = hs.in(q, n * sizeof(float));
-  const float* d_u = hs.in(u, n * sizeof(float));
-  const uint8_t* d_used = hs.in(used, n);
-  float* d_F = hs.out(F, (size_t)ncand * par->ntau * par->nphi * 2 * sizeof(float));
-  return hs.run(e, "device memory for the spectra and F", "upload spectra", "download F",
-                [&]() { return frbch_rmdelay_device(fil, d_q, d_u, d_used, ncand, par, device, d_F, kernel_used, err, err_cap); });
-} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
-
-extern "C" int frbch_rmdelay_peaks(const frbch_fil_desc* fil, const float* F, const uint8_t* used, const float* noise_q, const float* noise_u,
-                                   uint32_t ncand, const frbch_rmd_params* par, frbch_rmd_result* results, char* err, size_t err_cap) try {
-  PostErr e{err, err_cap};
-  const int rc = rmd_check(fil, ncand, par, e);
-  if (rc) return rc;
-  if (!F || !used || !results) return e.fail(FRBCH_E_ARG, "null argument");
-  return rmd_peaks_run(fil, F, used, noise_q, noise_u, ncand, par, results);
-} catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
-
-extern "C" int frbch_burst_polcal_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
-                                         const frbch_burst_cand* cands, uint32_t ncand, const float* gain, const uint8_t* flag,
-                                         const frbch_rmd_params* par, int device, float* spec, float* noise, uint8_t* used, float* F,
-                                         frbch_rmd_result* results, uint32_t* kernel_used, char* err, size_t err_cap) try {
-  PostErr e{err, err_cap};
-  int rc = burst_check(fil, nrows, bpar, cands, ncand, e);
-  if (rc) return rc;
-  if (fil->nifs != 4) return e.fail(FRBCH_E_ARG, "the composite needs the four products of a full-Stokes file (nifs = 4)");
-  if ((rc = rmd_check(fil, ncand, par, e)) != 0) return rc;
-  if (!d_rows || !spec || !noise || !used || !F || !results) return e.fail(FRBCH_E_ARG, "null argument");
-  const size_t nchan = fil->nchan, n = (size_t)ncand * nchan, nF = (size_t)ncand * par->ntau * par->nphi * 2;
-  std::vector<frbch_burst_sums> sums;
-  std::vector<float> q(n), u(n), nq(n), nu(n);
-  RmdPlan plan;
+  RmPlan<typename RmFam<Par>::Rec> plan;
   uint32_t k[3] = {0, 0, 1};
   rc = burst_device_call(device, e, [&](PostScope& ps) {
     int rc;
@@ -4760,29 +4598,92 @@ extern "C" int frbch_burst_polcal_device(const frbch_fil_desc* fil, const void* 
         nq[i * nchan + c] = noise[((size_t)i * 4 + 1) * nchan + c];
         nu[i * nchan + c] = noise[((size_t)i * 4 + 2) * nchan + c];
       }
-    if ((rc = rmd_build(fil, q.data(), u.data(), used, ncand, par, &plan, e)) != 0) return rc;
-    if ((rc = rmd_launch(fil, ncand, par, plan, d_F, ps, &k[1], e)) != 0) return rc;
+    if ((rc = rm_build(fil, q.data(), u.data(), used, ncand, par, &plan, e)) != 0) return rc;
+    if ((rc = rm_launch(fil, ncand, par, plan, d_F, ps, &k[1], e)) != 0) return rc;
     POST_DEV(dev_d2h(F, d_F, nF * sizeof(float), ps.s), "download F");
     POST_DEV(dev_sync(ps.s), "sync");
     return (int)FRBCH_OK;
   });
   if (rc) return rc;
   deliver(kernel_used, k);
-  return rmd_peaks_run(fil, F, used, nq.data(), nu.data(), ncand, par, results);
+  return rm_family_peaks(fil, F, used, nq.data(), nu.data(), ncand, par, results);
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
 
-extern "C" int frbch_burst_polcal_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* bpar,
-                                       const frbch_burst_cand* cands, uint32_t ncand, const float* gain, const uint8_t* flag,
-                                       const frbch_rmd_params* par, int device, float* spec, float* noise, uint8_t* used, float* F,
-                                       frbch_rmd_result* results, uint32_t* kernel_used, char* err, size_t err_cap) try {
+template <class Par>
+int rm_entry_burst_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* bpar,
+                        const frbch_burst_cand* cands, uint32_t ncand, const float* gain, const uint8_t* flag, const Par* par, int device,
+                        float* spec, float* noise, uint8_t* used, float* F, typename RmFam<Par>::Res* results, uint32_t* kernel_used,
+                        char* err, size_t err_cap) try {
   PostErr e{err, err_cap};
   const int rc = burst_check(fil, nrows, bpar, cands, ncand, e);
   if (rc) return rc;
   if (!rows) return e.fail(FRBCH_E_ARG, "null argument");
   return burst_host_twin(fil, rows, nrows, device, e, [&](void* d_rows) {
-    return frbch_burst_polcal_device(fil, d_rows, nrows, bpar, cands, ncand, gain, flag, par, device, spec, noise, used, F, results, kernel_used, err, err_cap);
+    return rm_entry_burst_device(fil, d_rows, nrows, bpar, cands, ncand, gain, flag, par, device, spec, noise, used, F, results, kernel_used,
+                                 err, err_cap);
   });
 } catch (const std::bad_alloc&) { return PostErr{err, err_cap}.fail(FRBCH_E_NOMEM, "host memory"); }
+}  // namespace
+
+extern "C" int frbch_rmsynth_kernel(const frbch_fil_desc* fil, const float* d_F, uint32_t ncand, const frbch_rm_params* par, uint32_t* nsplit) {
+  return rm_entry_kernel(fil, d_F, ncand, par, nsplit);
+}
+extern "C" int frbch_rmdelay_kernel(const frbch_fil_desc* fil, const float* d_F, uint32_t ncand, const frbch_rmd_params* par, uint32_t* nsplit) {
+  return rm_entry_kernel(fil, d_F, ncand, par, nsplit);
+}
+
+extern "C" int frbch_rmsynth_device(const frbch_fil_desc* fil, const float* d_q, const float* d_u, const uint8_t* d_used, uint32_t ncand,
+                                    const frbch_rm_params* par, int device, float* d_F, uint32_t* kernel_used, char* err, size_t err_cap) {
+  return rm_entry_device(fil, d_q, d_u, d_used, ncand, par, device, d_F, kernel_used, err, err_cap);
+}
+extern "C" int frbch_rmdelay_device(const frbch_fil_desc* fil, const float* d_q, const float* d_u, const uint8_t* d_used, uint32_t ncand,
+                                    const frbch_rmd_params* par, int device, float* d_F, uint32_t* kernel_used, char* err, size_t err_cap) {
+  return rm_entry_device(fil, d_q, d_u, d_used, ncand, par, device, d_F, kernel_used, err, err_cap);
+}
+
+extern "C" int frbch_rmsynth_host(const frbch_fil_desc* fil, const float* q, const float* u, const uint8_t* used, uint32_t ncand,
+                                  const frbch_rm_params* par, int device, float* F, uint32_t* kernel_used, char* err, size_t err_cap) {
+  return rm_entry_host(fil, q, u, used, ncand, par, device, F, kernel_used, err, err_cap);
+}
+extern "C" int frbch_rmdelay_host(const frbch_fil_desc* fil, const float* q, const float* u, const uint8_t* used, uint32_t ncand,
+                                  const frbch_rmd_params* par, int device, float* F, uint32_t* kernel_used, char* err, size_t err_cap) {
+  return rm_entry_host(fil, q, u, used, ncand, par, device, F, kernel_used, err, err_cap);
+}
+
+extern "C" int frbch_rm_peaks(const frbch_fil_desc* fil, const float* F, const uint8_t* used, const float* noise_q, const float* noise_u,
+                              uint32_t ncand, const frbch_rm_params* par, frbch_rm_result* results, char* err, size_t err_cap) {
+  return rm_entry_peaks(fil, F, used, noise_q, noise_u, ncand, par, results, err, err_cap);
+}
+extern "C" int frbch_rmdelay_peaks(const frbch_fil_desc* fil, const float* F, const uint8_t* used, const float* noise_q, const float* noise_u,
+                                   uint32_t ncand, const frbch_rmd_params* par, frbch_rmd_result* results, char* err, size_t err_cap) {
+  return rm_entry_peaks(fil, F, used, noise_q, noise_u, ncand, par, results, err, err_cap);
+}
+
+extern "C" int frbch_burst_rm_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                     const frbch_burst_cand* cands, uint32_t ncand, const float* gain, const uint8_t* flag,
+                                     const frbch_rm_params* par, int device, float* spec, float* noise, uint8_t* used, float* F,
+                                     frbch_rm_result* results, uint32_t* kernel_used, char* err, size_t err_cap) {
+  return rm_entry_burst_device(fil, d_rows, nrows, bpar, cands, ncand, gain, flag, par, device, spec, noise, used, F, results, kernel_used, err, err_cap);
+}
+extern "C" int frbch_burst_polcal_device(const frbch_fil_desc* fil, const void* d_rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                         const frbch_burst_cand* cands, uint32_t ncand, const float* gain, const uint8_t* flag,
+                                         const frbch_rmd_params* par, int device, float* spec, float* noise, uint8_t* used, float* F,
+                                         frbch_rmd_result* results, uint32_t* kernel_used, char* err, size_t err_cap) {
+  return rm_entry_burst_device(fil, d_rows, nrows, bpar, cands, ncand, gain, flag, par, device, spec, noise, used, F, results, kernel_used, err, err_cap);
+}
+
+extern "C" int frbch_burst_rm_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                   const frbch_burst_cand* cands, uint32_t ncand, const float* gain, const uint8_t* flag,
+                                   const frbch_rm_params* par, int device, float* spec, float* noise, uint8_t* used, float* F,
+                                   frbch_rm_result* results, uint32_t* kernel_used, char* err, size_t err_cap) {
+  return rm_entry_burst_host(fil, rows, nrows, bpar, cands, ncand, gain, flag, par, device, spec, noise, used, F, results, kernel_used, err, err_cap);
+}
+extern "C" int frbch_burst_polcal_host(const frbch_fil_desc* fil, const void* rows, uint64_t nrows, const frbch_burst_params* bpar,
+                                       const frbch_burst_cand* cands, uint32_t ncand, const float* gain, const uint8_t* flag,
+                                       const frbch_rmd_params* par, int device, float* spec, float* noise, uint8_t* used, float* F,
+                                       frbch_rmd_result* results, uint32_t* kernel_used, char* err, size_t err_cap) {
+  return rm_entry_burst_host(fil, rows, nrows, bpar, cands, ncand, gain, flag, par, device, spec, noise, used, F, results, kernel_used, err, err_cap);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // polarisation profile of a burst: derotated I, L, V and PA per time bin (include/frbch.h states the arithmetic)

@@ -2283,42 +2283,86 @@ def rm_grid(hdr: dict, used=None, phi_max: float = 0.0, dphi: float = 0.0, nphi:
     return 2 * half + 1, -half * dphi, float(dphi)
 
 
-def rm_synthesis(q, u, used, hdr: dict, nphi: int, phi_lo: float, dphi: float, device: int = 0, lib=None, info: dict | None = None):
-    """F(phi) of ``q``, ``u`` [n][nchans] over the channels with ``used != 0`` at phi_k = phi_lo + k dphi (frbch_rmsynth_host;
-    include/frbch.h states the integer transform) -> complex64 ``F [n][nphi]``.  The RMSF is ``rm_synthesis(used, 0, used,
-    ...)``.  ``info['kernel_used']``: 1 = the fast kernel, 0 = the generic one; ``info['split']``: the channel split."""
-    lib = lib or _lib.load()
-    nchan = hdr["nchans"]
+# ---- RM synthesis and the delay x RM transform share their calls: the second is the first with a tau axis in front of phi ----
+def _qu_args(q, u, used, nchan: int):
+    """``q``, ``u``, ``used`` of a transform as contiguous float32, float32, uint8 [n][nchans]"""
     q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, nchan)
     u = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, nchan)
     used = np.ascontiguousarray(used, dtype=np.uint8).reshape(-1, nchan)
     if not q.shape == u.shape == used.shape:
         raise InputError("q, u and used must have the same shape [n][nchans]")
-    par = rm_params(nphi, phi_lo, dphi)
-    F = np.zeros((q.shape[0], int(nphi), 2), np.float32)
+    return q, u, used
+
+
+def _rmd_plane(n: int, ntau: int, nphi: int):
+    """(ntau, nphi) of an F the delay x RM transform can return for ``n`` candidates, clamped to what the library takes (it
+    refuses the rest by name)"""
+    nt, nk = max(1, min(int(ntau), 4096)), max(1, min(int(nphi), 1 << 20))
+    if n * nt * nk > 1 << 26:
+        raise InputError("ncand * ntau * nphi exceeds 2^26: cut the batch or the grid")
+    return nt, nk
+
+
+def _transform_call(entry, q, u, used, hdr, par, plane, device, info):
+    """frbch_rmsynth_host / frbch_rmdelay_host -> complex64 F [n] + plane"""
+    F = np.zeros((q.shape[0],) + plane + (2,), np.float32)
     k = (C.c_uint32 * 2)(0, 1)
     err = C.create_string_buffer(512)
-    _check(lib.frbch_rmsynth_host(C.byref(fil_desc(hdr)), q.ctypes.data, u.ctypes.data, used.ctypes.data, q.shape[0], C.byref(par),
-                                  device, F.ctypes.data, k, err, len(err)), err)
+    _check(entry(C.byref(fil_desc(hdr)), q.ctypes.data, u.ctypes.data, used.ctypes.data, q.shape[0], C.byref(par), device, F.ctypes.data, k,
+                 err, len(err)), err)
     if info is not None:
         info.update(kernel_used=k[0], split=k[1])
     return F.view(np.complex64)[..., 0]
 
 
-def rm_peaks(F, used, noise_q, noise_u, hdr: dict, nphi: int, phi_lo: float, dphi: float, lib=None) -> np.ndarray:
-    """RM_RESULT records from F (frbch_rm_peaks: the first largest trial, a three-point parabola, PA0, the noise in F)"""
-    lib = lib or _lib.load()
+def _peaks_call(entry, F, plane, used, noise_q, noise_u, hdr, par, dtype, extra):
+    """frbch_rm_peaks / frbch_rmdelay_peaks -> records [n + extra]"""
     nchan = hdr["nchans"]
-    Ff = np.ascontiguousarray(np.asarray(F, dtype=np.complex64).reshape(-1, int(nphi))).view(np.float32)
+    Ff = np.ascontiguousarray(np.asarray(F, dtype=np.complex64).reshape((-1,) + plane)).view(np.float32)
     used = np.ascontiguousarray(used, dtype=np.uint8).reshape(-1, nchan)
     nq = None if noise_q is None else np.ascontiguousarray(noise_q, dtype=np.float32).reshape(-1, nchan)
     nu = None if noise_u is None else np.ascontiguousarray(noise_u, dtype=np.float32).reshape(-1, nchan)
-    res = np.zeros(used.shape[0], dtype=RM_RESULT)
-    par = rm_params(nphi, phi_lo, dphi)
+    res = np.zeros(used.shape[0] + extra, dtype=dtype)
     err = C.create_string_buffer(512)
-    _check(lib.frbch_rm_peaks(C.byref(fil_desc(hdr)), Ff.ctypes.data, used.ctypes.data, nq.ctypes.data if nq is not None else None,
-                              nu.ctypes.data if nu is not None else None, used.shape[0], C.byref(par), res.ctypes.data, err, len(err)), err)
+    _check(entry(C.byref(fil_desc(hdr)), Ff.ctypes.data, used.ctypes.data, nq.ctypes.data if nq is not None else None,
+                 nu.ctypes.data if nu is not None else None, used.shape[0], C.byref(par), res.ctypes.data, err, len(err)), err)
     return res
+
+
+def _composite_call(entry, fil_or_rows, hdr, cands, gains, flag, products, plane_of, make_par, grid, dtype, extra, device, info):
+    """frbch_burst_rm_host / frbch_burst_polcal_host -> dict(spec, noise, used, F [n] + plane_of(n), results [n + extra])"""
+    rows, nrows, cands, par, g = _burst_args(fil_or_rows, hdr, cands, gains, products)
+    n, nchan = cands.size, hdr["nchans"]
+    plane = plane_of(n)
+    spec, noise = np.zeros((n, 4, nchan), np.float32), np.zeros((n, 4, nchan), np.float32)
+    used = np.zeros((n, nchan), np.uint8)
+    F = np.zeros((n,) + plane + (2,), np.float32)
+    res = np.zeros(n + extra, dtype=dtype)
+    fl = _flag_arg(flag, nchan)
+    rpar = make_par(*grid)
+    k = (C.c_uint32 * 3)(0, 0, 1)
+    err = C.create_string_buffer(512)
+    _check(entry(C.byref(fil_desc(hdr, hdr.get("product", 0))), rows.ctypes.data, nrows, C.byref(par), cands.ctypes.data, n,
+                 g.ctypes.data if g is not None else None, fl.ctypes.data if fl is not None else None, C.byref(rpar), device,
+                 spec.ctypes.data, noise.ctypes.data, used.ctypes.data, F.ctypes.data, res.ctypes.data, k, err, len(err)), err)
+    if info is not None:
+        info.update(spectra_kernel_used=k[0], kernel_used=k[1], split=k[2])
+    return dict(spec=spec, noise=noise, used=used, F=F.view(np.complex64)[..., 0], results=res)
+
+
+def rm_synthesis(q, u, used, hdr: dict, nphi: int, phi_lo: float, dphi: float, device: int = 0, lib=None, info: dict | None = None):
+    """F(phi) of ``q``, ``u`` [n][nchans] over the channels with ``used != 0`` at phi_k = phi_lo + k dphi (frbch_rmsynth_host;
+    include/frbch.h states the integer transform) -> complex64 ``F [n][nphi]``.  The RMSF is ``rm_synthesis(used, 0, used,
+    ...)``.  ``info['kernel_used']``: 1 = the fast kernel, 0 = the generic one; ``info['split']``: the channel split."""
+    lib = lib or _lib.load()
+    q, u, used = _qu_args(q, u, used, hdr["nchans"])
+    return _transform_call(lib.frbch_rmsynth_host, q, u, used, hdr, rm_params(nphi, phi_lo, dphi), (int(nphi),), device, info)
+
+
+def rm_peaks(F, used, noise_q, noise_u, hdr: dict, nphi: int, phi_lo: float, dphi: float, lib=None) -> np.ndarray:
+    """RM_RESULT records from F (frbch_rm_peaks: the first largest trial, a three-point parabola, PA0, the noise in F)"""
+    lib = lib or _lib.load()
+    return _peaks_call(lib.frbch_rm_peaks, F, (int(nphi),), used, noise_q, noise_u, hdr, rm_params(nphi, phi_lo, dphi), RM_RESULT, 0)
 
 
 def burst_rm(fil_or_rows, hdr: dict, cands, nphi: int, phi_lo: float, dphi: float, gains=None, flag=None, products: str = "stokes",
@@ -2326,23 +2370,8 @@ def burst_rm(fil_or_rows, hdr: dict, cands, nphi: int, phi_lo: float, dphi: floa
     """Rows -> spectra -> RM synthesis of Q and U -> peaks in one library call on rows uploaded once (frbch_burst_rm_host)
     -> dict(spec, noise, used, F, results).  ``flag [nchans]``: non-zero clears the channel in ``used``."""
     lib = lib or _lib.load()
-    rows, nrows, cands, par, g = _burst_args(fil_or_rows, hdr, cands, gains, products)
-    n, nchan = cands.size, hdr["nchans"]
-    spec, noise = np.zeros((n, 4, nchan), np.float32), np.zeros((n, 4, nchan), np.float32)
-    used = np.zeros((n, nchan), np.uint8)
-    F = np.zeros((n, int(nphi), 2), np.float32)
-    res = np.zeros(n, dtype=RM_RESULT)
-    fl = _flag_arg(flag, nchan)
-    rpar = rm_params(nphi, phi_lo, dphi)
-    k = (C.c_uint32 * 3)(0, 0, 1)
-    err = C.create_string_buffer(512)
-    _check(lib.frbch_burst_rm_host(C.byref(fil_desc(hdr, hdr.get("product", 0))), rows.ctypes.data, nrows, C.byref(par), cands.ctypes.data, n,
-                                   g.ctypes.data if g is not None else None, fl.ctypes.data if fl is not None else None, C.byref(rpar),
-                                   device, spec.ctypes.data, noise.ctypes.data, used.ctypes.data, F.ctypes.data, res.ctypes.data, k,
-                                   err, len(err)), err)
-    if info is not None:
-        info.update(spectra_kernel_used=k[0], kernel_used=k[1], split=k[2])
-    return dict(spec=spec, noise=noise, used=used, F=F.view(np.complex64)[..., 0], results=res)
+    return _composite_call(lib.frbch_burst_rm_host, fil_or_rows, hdr, cands, gains, flag, products, lambda n: (int(nphi),), rm_params,
+                           (nphi, phi_lo, dphi), RM_RESULT, 0, device, info)
 
 
 # ---- polarisation calibration: the delay x RM transform (frbch_rmdelay_*, frbch_burst_polcal_*) ------------------
@@ -2366,24 +2395,9 @@ def rm_delay(q, u, used, hdr: dict, nphi: int, phi_lo: float, dphi: float, ntau:
     include/frbch.h states the arithmetic) -> complex64 ``F [n][ntau][nphi]``.  ``ntau = 1, tau_lo = 0`` is ``rm_synthesis``
     to the bit.  ``info['kernel_used']``: 1 = the fast kernel, 0 = the generic one; ``info['split']``: the channel split."""
     lib = lib or _lib.load()
-    nchan = hdr["nchans"]
-    q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, nchan)
-    u = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, nchan)
-    used = np.ascontiguousarray(used, dtype=np.uint8).reshape(-1, nchan)
-    if not q.shape == u.shape == used.shape:
-        raise InputError("q, u and used must have the same shape [n][nchans]")
+    q, u, used = _qu_args(q, u, used, hdr["nchans"])
     par = rmd_params(nphi, phi_lo, dphi, ntau, tau_lo, dtau)
-    nt, nk = max(1, min(int(ntau), 4096)), max(1, min(int(nphi), 1 << 20))
-    if q.shape[0] * nt * nk > 1 << 26:
-        raise InputError("ncand * ntau * nphi exceeds 2^26: cut the batch or the grid")
-    F = np.zeros((q.shape[0], nt, nk, 2), np.float32)
-    k = (C.c_uint32 * 2)(0, 1)
-    err = C.create_string_buffer(512)
-    _check(lib.frbch_rmdelay_host(C.byref(fil_desc(hdr)), q.ctypes.data, u.ctypes.data, used.ctypes.data, q.shape[0], C.byref(par),
-                                  device, F.ctypes.data, k, err, len(err)), err)
-    if info is not None:
-        info.update(kernel_used=k[0], split=k[1])
-    return F.view(np.complex64)[..., 0]
+    return _transform_call(lib.frbch_rmdelay_host, q, u, used, hdr, par, _rmd_plane(q.shape[0], ntau, nphi), device, info)
 
 
 def rm_delay_peaks(F, used, noise_q, noise_u, hdr: dict, nphi: int, phi_lo: float, dphi: float, ntau: int, tau_lo: float, dtau: float,
@@ -2392,17 +2406,8 @@ def rm_delay_peaks(F, used, noise_q, noise_u, hdr: dict, nphi: int, phi_lo: floa
     a parabola along each axis, psi, the noise and the slope of the ridge; the last record is the combined estimate of all
     pulses (their planes added with weights 1 / sigma_f^2)"""
     lib = lib or _lib.load()
-    nchan = hdr["nchans"]
-    Ff = np.ascontiguousarray(np.asarray(F, dtype=np.complex64).reshape(-1, int(ntau), int(nphi))).view(np.float32)
-    used = np.ascontiguousarray(used, dtype=np.uint8).reshape(-1, nchan)
-    nq = None if noise_q is None else np.ascontiguousarray(noise_q, dtype=np.float32).reshape(-1, nchan)
-    nu = None if noise_u is None else np.ascontiguousarray(noise_u, dtype=np.float32).reshape(-1, nchan)
-    res = np.zeros(used.shape[0] + 1, dtype=RMD_RESULT)
-    par = rmd_params(nphi, phi_lo, dphi, ntau, tau_lo, dtau)
-    err = C.create_string_buffer(512)
-    _check(lib.frbch_rmdelay_peaks(C.byref(fil_desc(hdr)), Ff.ctypes.data, used.ctypes.data, nq.ctypes.data if nq is not None else None,
-                                   nu.ctypes.data if nu is not None else None, used.shape[0], C.byref(par), res.ctypes.data, err, len(err)), err)
-    return res
+    return _peaks_call(lib.frbch_rmdelay_peaks, F, (int(ntau), int(nphi)), used, noise_q, noise_u, hdr,
+                       rmd_params(nphi, phi_lo, dphi, ntau, tau_lo, dtau), RMD_RESULT, 1)
 
 
 def polcal(fil_or_rows, hdr: dict, cands, nphi: int, phi_lo: float, dphi: float, ntau: int, tau_lo: float, dtau: float, gains=None,
@@ -2410,26 +2415,8 @@ def polcal(fil_or_rows, hdr: dict, cands, nphi: int, phi_lo: float, dphi: float,
     """Rows -> spectra -> the delay x RM transform of Q and U -> peaks and the combined record, in one library call on rows
     uploaded once (frbch_burst_polcal_host) -> dict(spec, noise, used, F [n][ntau][nphi], results RMD_RESULT [n + 1])."""
     lib = lib or _lib.load()
-    rows, nrows, cands, par, g = _burst_args(fil_or_rows, hdr, cands, gains, products)
-    n, nchan = cands.size, hdr["nchans"]
-    nt, nk = max(1, min(int(ntau), 4096)), max(1, min(int(nphi), 1 << 20))
-    if n * nt * nk > 1 << 26:
-        raise InputError("ncand * ntau * nphi exceeds 2^26: cut the batch or the grid")
-    spec, noise = np.zeros((n, 4, nchan), np.float32), np.zeros((n, 4, nchan), np.float32)
-    used = np.zeros((n, nchan), np.uint8)
-    F = np.zeros((n, nt, nk, 2), np.float32)
-    res = np.zeros(n + 1, dtype=RMD_RESULT)
-    fl = _flag_arg(flag, nchan)
-    rpar = rmd_params(nphi, phi_lo, dphi, ntau, tau_lo, dtau)
-    k = (C.c_uint32 * 3)(0, 0, 1)
-    err = C.create_string_buffer(512)
-    _check(lib.frbch_burst_polcal_host(C.byref(fil_desc(hdr, hdr.get("product", 0))), rows.ctypes.data, nrows, C.byref(par), cands.ctypes.data, n,
-                                       g.ctypes.data if g is not None else None, fl.ctypes.data if fl is not None else None, C.byref(rpar),
-                                       device, spec.ctypes.data, noise.ctypes.data, used.ctypes.data, F.ctypes.data, res.ctypes.data, k,
-                                       err, len(err)), err)
-    if info is not None:
-        info.update(spectra_kernel_used=k[0], kernel_used=k[1], split=k[2])
-    return dict(spec=spec, noise=noise, used=used, F=F.view(np.complex64)[..., 0], results=res)
+    return _composite_call(lib.frbch_burst_polcal_host, fil_or_rows, hdr, cands, gains, flag, products, lambda n: _rmd_plane(n, ntau, nphi),
+                           rmd_params, (nphi, phi_lo, dphi, ntau, tau_lo, dtau), RMD_RESULT, 1, device, info)
 
 
 def polcal_tau(polcal_file) -> float:

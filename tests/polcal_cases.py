@@ -26,7 +26,7 @@ def tau_tile(ntau):
 
 
 def expected_plan(nchan, ncand, nphi, ntau, misalign=0):
-    """(form, split) of the plan rule, restated"""
+    """(form, split) of the plan rule (rm_plan_rule of csrc/frbch_post.cpp, the one RM synthesis takes at ntau = 1), restated"""
     if nphi < 64 or misalign % 8:
         return GENERIC, 1
     base = ncand * -(-ntau // tau_tile(ntau)) * -(-nphi // 1024)

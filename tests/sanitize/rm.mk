@@ -1,6 +1,7 @@
-# TEST INFRASTRUCTURE ONLY: the burst polarisation stage (frbch_burstspec_*, frbch_rm_table, frbch_rmsynth_*, frbch_rm_peaks,
-# frbch_burst_rm_host, the refusals, a failure walk) under AddressSanitizer and UBSan, as a stand-alone program linked against
-# the emulator sources (CPU only; never loaded into python, never run on a GPU).
+# TEST INFRASTRUCTURE ONLY: the burst polarisation stage and the polarisation calibration, which share one host path
+# (frbch_burstspec_*, frbch_rm_table, frbch_rmsynth_* / frbch_rmdelay_*, frbch_rm_peaks / frbch_rmdelay_peaks, frbch_burst_rm_host /
+# frbch_burst_polcal_host, the refusals, the failure walks) under AddressSanitizer and UBSan, as a stand-alone program linked
+# against the emulator sources (CPU only; never loaded into python, never run on a GPU).
 #   make -C tests/sanitize -f rm.mk run
 CSRC := ../../frb_baseband_amd/csrc
 EMU := ../emu

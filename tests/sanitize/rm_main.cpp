@@ -1,7 +1,10 @@
-// TEST INFRASTRUCTURE ONLY: the burst polarisation stage under AddressSanitizer and UBSan, as a stand-alone program linked
-// against the emulator sources (CPU only; never loaded into python, never run on a GPU): one small call of every new entry
-// point through the generic kernels (8-bit and float rows, windows partly and wholly outside the data, a masked channel, a
-// dead candidate, the RMSF), the refusals, and a failure walk of the composite.
+// TEST INFRASTRUCTURE ONLY: the burst polarisation stage and the polarisation calibration under AddressSanitizer and UBSan,
+// as a stand-alone program linked against the emulator sources (CPU only; never loaded into python, never run on a GPU): one
+// small call of every entry point through the generic kernels (8-bit and float rows, windows partly and wholly outside the
+// data, a masked channel, a dead candidate, the RMSF), the refusals, and a failure walk of the composite.  RM synthesis and
+// the delay x RM transform run through one host path (RmFam in frbch_post.cpp), so both members are called here on the same
+// data: three trial delays, the one-trial identity with frbch_rmsynth_host byte for byte, the refusals of frbch_rmd_params,
+// and the failure walk of frbch_burst_polcal_host.
 //   make -C tests/sanitize -f rm.mk run
 #include <math.h>
 #include <stdint.h>
@@ -143,8 +146,40 @@ int main() {
     CHECK(res[0].fitted == 1 && fabs(res[0].rm - 1500.0) < 100.0 && res[0].nused == nchan - 1 && res[0].snr > 0 && res[0].rm_err > 0);
     CHECK(res[2].nused == 0 && res[2].kpeak == 0 && res[2].fitted == 0 && res[2].peak == 0.0);
     CHECK(frbch_rm_peaks(&fil, F.data(), used.data(), nullptr, nullptr, 4, &rpar, res.data(), err, sizeof err) == FRBCH_OK && res[0].snr == 0.0);
+    // the delay x RM transform of the same spectra: three trial delays, of which the second is tau = 0 and so RM synthesis
+    {
+      const uint32_t ntau = 3;
+      const frbch_rmd_params dpar = {sizeof(frbch_rmd_params), nphi, ntau, 0, -6400.0, 100.0, -1.0e-3, 1.0e-3};
+      std::vector<float> D((size_t)4 * ntau * nphi * 2, 7.f);
+      uint32_t kd[2] = {9, 9};
+      ns = 9;
+      CHECK(frbch_rmdelay_kernel(&fil, dummy, 4, &dpar, &ns) == 0 && ns == 1 && frbch_rmdelay_kernel(&fil, nullptr, 4, &dpar, &ns) == FRBCH_E_ARG);
+      CHECK(frbch_rmdelay_host(&fil, q.data(), u.data(), used.data(), 4, &dpar, 0, D.data(), kd, err, sizeof err) == FRBCH_OK);
+      CHECK(kd[0] == 0 && kd[1] == 1);
+      for (uint32_t i = 0; i < 4; ++i)
+        CHECK(memcmp(&D[((size_t)i * ntau + 1) * nphi * 2], &F[(size_t)i * nphi * 2], (size_t)nphi * 2 * sizeof(float)) == 0);
+      std::vector<frbch_rmd_result> dres(5);
+      CHECK(frbch_rmdelay_peaks(&fil, D.data(), used.data(), nq.data(), nq.data(), 4, &dpar, dres.data(), err, sizeof err) == FRBCH_OK);
+      CHECK(fabs(dres[0].rm - 1500.0) < 100.0 && dres[0].nused == nchan - 1 && dres[0].snr > 0 && dres[0].rm_err > 0 && dres[0].tau_err > 0);
+      CHECK(dres[0].sigma_f > 0 && dres[0].fwhm == res[0].fwhm && dres[2].nused == 0 && dres[2].peak == 0.0);
+      CHECK(dres[4].nused == 3 && dres[4].sigma_f == 1.0 && dres[4].peak > 0);
+      CHECK(frbch_rmdelay_peaks(&fil, D.data(), used.data(), nullptr, nullptr, 4, &dpar, dres.data(), err, sizeof err) == FRBCH_OK);
+      CHECK(dres[0].snr == 0.0 && dres[4].nused == 0);
+      // ntau = 1, tau_lo = 0: the bytes of frbch_rmsynth_host
+      const frbch_rmd_params one_tau = {sizeof(frbch_rmd_params), nphi, 1, 0, -6400.0, 100.0, 0.0, 1.0e-3};
+      std::vector<float> E((size_t)4 * nphi * 2, 7.f);
+      CHECK(frbch_rmdelay_host(&fil, q.data(), u.data(), used.data(), 4, &one_tau, 0, E.data(), nullptr, err, sizeof err) == FRBCH_OK);
+      CHECK(E == F);
+    }
     used[17] = 1;
     CHECK(frbch_rmsynth_host(&fil, q.data(), u.data(), used.data(), 4, &rpar, 0, F.data(), k2, err, sizeof err) == FRBCH_E_ARG);
+    {
+      const frbch_rmd_params dpar = {sizeof(frbch_rmd_params), nphi, 3, 0, -6400.0, 100.0, -1.0e-3, 1.0e-3};
+      std::vector<float> D((size_t)4 * 3 * nphi * 2);
+      err[0] = 0;
+      CHECK(frbch_rmdelay_host(&fil, q.data(), u.data(), used.data(), 4, &dpar, 0, D.data(), nullptr, err, sizeof err) == FRBCH_E_ARG);   // q[17] is NaN
+      CHECK(strstr(err, "candidate 0: q or u of a used channel is not finite"));
+    }
     // the RMSF: q = used, u = 0 -> exactly 1 at phi = 0 (trial 64)
     std::vector<float> ones((size_t)4 * nchan), zeros((size_t)4 * nchan, 0.f);
     for (size_t i = 0; i < ones.size(); ++i) ones[i] = used[i] ? 1.f : 0.f;
@@ -182,6 +217,30 @@ int main() {
     neg.foff_mhz = -30.0;
     CHECK(frbch_rmsynth_kernel(&neg, dummy, 1, &rpar, nullptr) == FRBCH_E_ARG);
     CHECK(frbch_rmsynth_host(&fil, nullptr, q.data(), us.data(), 1, &rpar, 0, F.data(), nullptr, err, sizeof err) == FRBCH_E_ARG);
+    // frbch_rmd_params: its size before the file, the phi tests before the tau tests
+    const uint32_t sz = sizeof(frbch_rmd_params);
+    const struct { frbch_rmd_params p; const char* text; } dbads[] = {
+        {{8, nphi, 3, 0, -6400.0, 100.0, 0.0, 1.0e-3}, "frbch_rmd_params: wrong size"},
+        {{sz, 0, 3, 0, -6400.0, 100.0, 0.0, 1.0e-3}, "nphi must be 1..2^20"},
+        {{sz, nphi, 3, 0, -6400.0, NAN, 0.0, 1.0e-3}, "dphi must be positive and finite"},
+        {{sz, nphi, 0, 0, -6400.0, 100.0, 0.0, 1.0e-3}, "ntau must be 1..4096"},
+        {{sz, nphi, 4097, 0, -6400.0, 100.0, 0.0, 1.0e-3}, "ntau must be 1..4096"},
+        {{sz, 1u << 20, 65, 0, -5.0e5, 1.0, 0.0, 1.0e-3}, "ncand * ntau * nphi exceeds 2^26"},
+        {{sz, nphi, 3, 0, -6400.0, 100.0, 0.0, 0.0}, "dtau must be positive and finite"},
+        {{sz, nphi, 3, 0, -6400.0, 100.0, 0.0, INFINITY}, "dtau must be positive and finite"},
+        {{sz, nphi, 3, 0, -6400.0, 100.0, NAN, 1.0e-3}, "|tau| above 100 microseconds"},
+        {{sz, nphi, 3, 0, -6400.0, 100.0, 99.9, 0.1}, "|tau| above 100 microseconds"}};
+    for (const auto& b : dbads) {
+      err[0] = 0;
+      CHECK(frbch_rmdelay_host(&fil, q.data(), q.data(), us.data(), 1, &b.p, 0, F.data(), nullptr, err, sizeof err) == FRBCH_E_ARG && strstr(err, b.text));
+      CHECK(frbch_rmdelay_kernel(&fil, dummy, 1, &b.p, nullptr) == FRBCH_E_ARG);
+    }
+    err[0] = 0;
+    CHECK(frbch_rmdelay_host(&wide, q.data(), q.data(), us.data(), 1, &dbads[0].p, 0, F.data(), nullptr, err, sizeof err) == FRBCH_E_ARG);
+    CHECK(strstr(err, "frbch_rmd_params: wrong size"));                                   // (not "more than 16384 channels")
+    CHECK(frbch_rmdelay_host(&fil, q.data(), q.data(), us.data(), 1, nullptr, 0, F.data(), nullptr, err, sizeof err) == FRBCH_E_ARG);
+    const frbch_rmd_params good = {sz, nphi, 3, 0, -6400.0, 100.0, 0.0, 1.0e-3};
+    CHECK(frbch_rmdelay_host(&fil, nullptr, q.data(), us.data(), 1, &good, 0, F.data(), nullptr, err, sizeof err) == FRBCH_E_ARG);
   }
 
   // the composite, a flagged channel, and its failure walk: every fallible device-layer call fails once; nothing is left behind
@@ -209,6 +268,41 @@ int main() {
       err[0] = 0;
       const int rc = frbch_burst_rm_host(&fil, rows.data(), nrows, &bpar, cands, 4, gain.data(), flag.data(), &rpar, 0, spec.data(), noise.data(),
                                          used.data(), F.data(), res.data(), k3, err, sizeof err);
+      frbch_test_emu_fail_at(0);
+      CHECK(frbch_test_emu_live() == live);
+      if (rc == FRBCH_OK) break;
+      CHECK(rc < 0 && err[0]);
+    }
+    CHECK(steps > 10 && steps < 199 && rows == rows0 && F == want);
+  }
+
+  // the same for the composite of the delay family (one more result record: the combined estimate)
+  {
+    const uint32_t ntau = 3;
+    const frbch_rmd_params dpar = {sizeof(frbch_rmd_params), nphi, ntau, 0, -6400.0, 100.0, -1.0e-3, 1.0e-3};
+    std::vector<float> F((size_t)4 * ntau * nphi * 2), want;
+    std::vector<frbch_rmd_result> res(5);
+    std::vector<uint8_t> flag(nchan, 0);
+    flag[3] = flag[95] = 1;
+    uint32_t k3[3] = {9, 9, 9};
+    CHECK(frbch_burst_polcal_host(&fil, rows.data(), nrows, &bpar, cands, 4, gain.data(), flag.data(), &dpar, 0, spec.data(), noise.data(),
+                                  used.data(), F.data(), res.data(), k3, err, sizeof err) == FRBCH_OK);
+    CHECK(k3[0] == 0 && k3[1] == 0 && k3[2] == 1 && used[3] == 0 && used[95] == 0 && used[4] == 1 && res[0].nused == nchan - 2);
+    CHECK(fabs(res[0].rm - 1500.0) < 100.0 && res[2].nused == 0 && res[4].nused >= 1 && res[4].nused <= 3 && rows == rows0);
+    want = F;
+    frbch_fil_desc two = fil;
+    two.nifs = 2;
+    CHECK(frbch_burst_polcal_host(&two, rows.data(), nrows, &bpar, cands, 4, nullptr, nullptr, &dpar, 0, spec.data(), noise.data(), used.data(),
+                                  F.data(), res.data(), nullptr, err, sizeof err) == FRBCH_E_ARG);
+    CHECK(frbch_burst_polcal_host(&fil, rows.data(), nrows, &bpar, cands, 4, nullptr, nullptr, &dpar, 0, spec.data(), noise.data(), used.data(),
+                                  nullptr, res.data(), nullptr, err, sizeof err) == FRBCH_E_ARG);
+    const uint64_t live = frbch_test_emu_live();
+    int steps = 0;
+    for (long k = 1; k < 200; ++k, ++steps) {
+      frbch_test_emu_fail_at(k);
+      err[0] = 0;
+      const int rc = frbch_burst_polcal_host(&fil, rows.data(), nrows, &bpar, cands, 4, gain.data(), flag.data(), &dpar, 0, spec.data(), noise.data(),
+                                             used.data(), F.data(), res.data(), k3, err, sizeof err);
       frbch_test_emu_fail_at(0);
       CHECK(frbch_test_emu_live() == live);
       if (rc == FRBCH_OK) break;

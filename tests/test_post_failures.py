@@ -16,7 +16,9 @@ and two products for frbch_rfi_cleanp_*.  Integer rows throughout: their sums ha
 The burst family (frbch_burstspec_* to frbch_burstscat_*, both twins of each) joined the table later, recorded in the same way
 on the commit BEFORE its entry points were rewritten around burst_device_call / burst_host_twin: each family in the shape of its
 own walk test (tests/test_polprof.py, test_dmscan.py, test_acf.py, test_scat.py, both cases of the last two), the three-candidate
-case of tests/test_rm.py, and the small planes of tests/test_acf.py and tests/test_scat.py for the two stages."""
+case of tests/test_rm.py, and the small planes of tests/test_acf.py and tests/test_scat.py for the two stages.
+The delay x RM transform (frbch_rmdelay_*, frbch_burst_polcal_*) joined last, recorded on the commit BEFORE it and RM synthesis
+were given one host path: the "generic_nphi63" grid of tests/polcal_cases.py, on its own spectra and on the three-candidate case."""
 import ctypes as C
 import json
 import os
@@ -30,6 +32,7 @@ from tests import acf_cases as ac
 from tests import cutout_cases as cc
 from tests import cutout_oracle as co
 from tests import dmscan_cases as dmc
+from tests import polcal_cases as plc
 from tests import polprof_cases as ppc
 from tests import post_cases as pc
 from tests import resident_cases as rs
@@ -327,6 +330,31 @@ def _burst_rm(twin):
     return make
 
 
+def _rmdelay(twin):
+    def make(lib):
+        e = Entry(lib, "frbch_rmdelay_" + twin)
+        nchan, ncand, _nphi, _lo, _d, _ntau, _tlo, _dt, masked = plc.SHAPES["generic_nphi63"]
+        grid = plc.grid_of("generic_nphi63")
+        hdr, q, u, used = rmc.spectra(nchan, ncand, 0, masked)
+        e.args = [e.hold(post.fil_desc(hdr)), e.inp(q), e.inp(u), e.inp(used), ncand, e.hold(post.rmd_params(**grid)), 0,
+                  e.out(ncand * grid["ntau"] * grid["nphi"] * 8), _kused(e, 2)]
+        e.want = lambda: [plc.want_transform("generic_nphi63").tobytes()]
+        return e
+    return make
+
+
+def _burst_polcal(twin):
+    def make(lib):
+        e = Entry(lib, "frbch_burst_polcal_" + twin)
+        hdr, rows, cands, coh = rmc.case("u8_64ch_3cand")
+        grid = plc.grid_of("generic_nphi63")
+        n, per = cands.size * 64, grid["ntau"] * grid["nphi"]
+        e.args = _burst_head(e, hdr, rows, cands, coh) + [None, None, e.hold(post.rmd_params(**grid)), 0, e.out(n * 16), e.out(n * 16), e.out(n),
+                                                          e.out(cands.size * per * 8), e.out((cands.size + 1) * post.RMD_RESULT.itemsize), _kused(e, 3)]
+        return e
+    return make
+
+
 def _polprof(twin):
     def make(lib):
         e = Entry(lib, "frbch_polprof_" + twin)
@@ -414,8 +442,8 @@ for _twin in ("device", "host"):
     ENTRIES["rfi_cleanp_2products_" + _twin] = _rfi("cleanp", _twin, nifs=2)
     ENTRIES["cornerturn_" + _twin] = _cornerturn(_twin)
     ENTRIES["candidates_rfi_planes_" + _twin] = _candidates(_twin)
-    for _name, _make in (("burstspec", _burstspec), ("rmsynth", _rmsynth), ("burst_rm", _burst_rm), ("polprof", _polprof), ("dmscan", _dmscan),
-                         ("acf2d", _acf2d), ("tbank", _tbank)):
+    for _name, _make in (("burstspec", _burstspec), ("rmsynth", _rmsynth), ("burst_rm", _burst_rm), ("rmdelay", _rmdelay), ("burst_polcal", _burst_polcal),
+                         ("polprof", _polprof), ("dmscan", _dmscan), ("acf2d", _acf2d), ("tbank", _tbank)):
         ENTRIES["%s_%s" % (_name, _twin)] = _make(_twin)
     for _case in ("u8_64ch_f4_full_lags", "u8_64ch_flag_constant_dead"):                        # (the second counts its pairs on the device)
         ENTRIES["burstacf_%s_%s" % (_case, _twin)] = _burstacf(_twin, _case)
